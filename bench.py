@@ -2,6 +2,12 @@
 """Benchmark of the HybridGL hot path on MI355X (contract: see the task statement / DESIGN.md).
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py --gpus 1 --full                      (+ every secondary measurement of the line)
+    python bench.py --gpus 1 --dump-outputs DIR          (+ the last timed step's outputs as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the legs that take runs of their
+own: the roofline group with per-kernel HIP events, the live rocprofv3 counter passes, the secondary configurations under
+`also`, the evaluator fed from disk, the RCCL self-check and the CPU baseline.
 
 One step = one dataset item ("ref") of BASELINE.json configs[1]: a 640x640 image with 64 mask
 proposals and 3 text queries, G2L fusion, CLIP ViT-B/16 -- SAM ViT-H proposal stage, view synthesis, CLIP hybrid
@@ -531,6 +537,32 @@ def evaluator_from_disk(args, model, gen, gem_model, dev, group, n_images=208, k
             shutil.rmtree(root, ignore_errors=True)
 
 
+def dump_outputs(out_dir, last_step, n_sent, rows, winners):
+    """--dump-outputs: the arrays the caller of the timed loop receives for its LAST ref -- (hybrid, text, last-sentence
+    tensors) as HybridGLPipeline.step() returns them and run(collect=True) keeps them, plus that ref's `n_sent` rows of
+    partial_rows() / winning_indices() -- as out_dir/<name>.npy, float32 (features, scores) or float64 (indices, counts).
+    Two outputs are NaN by definition in places, as in the reference: the coherence score of an empty proposal (0 / 0) and
+    the negative-noun logits of a sentence without other nouns.  Every file holds finite values only, so those two are
+    written with 0 in place of a NaN, and <name>_finite.npy (1 / 0 per entry) says which entries the path defined."""
+    hybrid, text, last = last_step
+    out = {"hybrid_features": hybrid, "text_features": text,
+           "sentence_winning_indices": winners[len(winners) - n_sent:],
+           "sentence_iou_counts": rows[len(rows) - n_sent:, 2:6]}
+    if last is not None:
+        idx, score_clip, score_neg, coherence = last
+        out.update(last_sentence_indices=idx, last_sentence_score_clip=score_clip, last_sentence_score_neg=score_neg,
+                   last_sentence_coherence=coherence)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        a = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+        if name in ("last_sentence_score_neg", "last_sentence_coherence"):
+            finite = np.isfinite(a)
+            np.save(os.path.join(out_dir, name + "_finite.npy"), finite.astype(np.float32))
+            a = np.where(finite, a, np.zeros_like(a))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -579,6 +611,16 @@ def main():
                     help="N = 1: skip the RCCL self-check (nccl backend in a world of one, the timed steps' metric rows through it)")
     ap.add_argument("--no-disk", action="store_true", help="skip also['evaluator_from_disk'] (the evaluator fed from a REFER tree on disk)")
     ap.add_argument("--timeout", type=float, default=3600.0, help="--gpus N without a launcher: seconds before the ranks are killed")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the measurements that take runs of their own: the roofline leg (one "
+                         "serial group with HIP events around every launch), and at N = 1 the live counter passes, the `also` "
+                         "legs, the evaluator from disk, the RCCL self-check and the CPU baseline (each --no-* option above "
+                         "drops one of them); without it the line carries the headline and the timed region only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step (the last ref) computed as DIR/<name>.npy (float32 / float64): its "
+                         "hybrid and text features, the last sentence's scores, every sentence's winning indices and IoU "
+                         "counts (rank 0; the timed run keeps each ref's outputs, HybridGLPipeline.run(collect=True)); entries "
+                         "the path leaves NaN are written as 0 and flagged in <name>_finite.npy")
     args = ap.parse_args()
 
     from hybridgl_amd import dist as D
@@ -660,19 +702,24 @@ def main():
 
     nbatch = args.sam_batch
 
-    def do_steps(k, p=None, cap=args.masks, pool=None, group=None):
+    def do_steps(k, p=None, cap=args.masks, pool=None, group=None, collect=False):
         """k steps = k refs completed, start to finish (proposal stage + CLIP/scoring stage of each), through the PRODUCT's
         loop: HybridGLPipeline.run over a loader that yields k resident refs (hybridgl_amd.main runs the same call over a
-        Prefetcher)."""
+        Prefetcher).  collect=True: returns the last ref's (hybrid, text, last-sentence tensors), as step() returns them."""
         p = p or pipe
         pool = pool or refs
         if nbatch == 1:
+            out = None
             for i in range(k):
-                p.step(pool[i % len(pool)])
-            return
+                out = p.step(pool[i % len(pool)])
+            return out if collect else None
         n = p.run((pool[i % len(pool)] for i in range(k)), group=group or nbatch, proposal_cap=cap if p.use_sam_masks else None,
-                  serial=args.no_overlap, total=None if args.no_balance else k)
+                  serial=args.no_overlap, total=None if args.no_balance else k, collect=collect)
         assert n == k, f"{k - n} refs were skipped (no proposals)"
+        if collect:
+            last = p.collected[-1] if p.collected else None
+            p.collected = None
+            return last
 
     prepared = None
     if nbatch >= 2 and not args.no_prepare:
@@ -699,7 +746,7 @@ def main():
     ev0 = torch.cuda.Event(enable_timing=True)
     ev0.record()
     t0 = time.perf_counter()
-    do_steps(args.steps)
+    last_step = do_steps(args.steps, collect=args.dump_outputs is not None)
     t_enq = time.perf_counter() - t0
     torch.cuda.synchronize()
     barrier()
@@ -715,25 +762,29 @@ def main():
     rows = pipe.partial_rows()
     # fp16 range guard of the f16x3 mode (ops.check_split_overflow): GPU threads that met |x| > 65504 in the timed steps
     overflow = ops.split_overflow_count(reset=True)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last_step, len(refs[(args.steps - 1) % len(refs)].sentences), rows, pipe.winning_indices())
+    del last_step
 
     # ---- roofline leg: one group of the same loop with every stage on ONE stream, HIP events around every launch
-    lib.hgl_prof_enable(1)
-    nprof = max(nbatch, 2)
-    keep_rows = (pipe.cum.clone(), list(pipe.iu_log), list(pipe.iu_owner), list(pipe.idx_log))
-    if nbatch == 1:
-        for i in range(nprof):
-            pipe.step(refs[i % len(refs)])
-    else:
-        pipe.run((refs[i % len(refs)] for i in range(nprof)), group=nbatch, proposal_cap=args.masks if pipe.use_sam_masks else None,
-                 serial=True)
-    torch.cuda.synchronize()
-    lib.hgl_prof_enable(0)
-    pipe.cum.copy_(keep_rows[0]); pipe.iu_log[:] = keep_rows[1]; pipe.iu_owner[:] = keep_rows[2]; pipe.idx_log[:] = keep_rows[3]
-    g_n, g_ms, g_fl, g_by = prof_read(lib, 0)
-    a_n, a_ms, a_fl, a_by = prof_read(lib, 1)
-    x_n, x_ms, x_fl, x_by = prof_read(lib, 3)
-    xg_n, xg_ms, xg_fl, xg_by = prof_read(lib, 4)
-    fw_n, fw_ms, fw_fl, fw_by = prof_read(lib, 5)
+    if args.full:
+        lib.hgl_prof_enable(1)
+        nprof = max(nbatch, 2)
+        keep_rows = (pipe.cum.clone(), list(pipe.iu_log), list(pipe.iu_owner), list(pipe.idx_log))
+        if nbatch == 1:
+            for i in range(nprof):
+                pipe.step(refs[i % len(refs)])
+        else:
+            pipe.run((refs[i % len(refs)] for i in range(nprof)), group=nbatch, proposal_cap=args.masks if pipe.use_sam_masks else None,
+                     serial=True)
+        torch.cuda.synchronize()
+        lib.hgl_prof_enable(0)
+        pipe.cum.copy_(keep_rows[0]); pipe.iu_log[:] = keep_rows[1]; pipe.iu_owner[:] = keep_rows[2]; pipe.idx_log[:] = keep_rows[3]
+        g_n, g_ms, g_fl, g_by = prof_read(lib, 0)
+        a_n, a_ms, a_fl, a_by = prof_read(lib, 1)
+        x_n, x_ms, x_fl, x_by = prof_read(lib, 3)
+        xg_n, xg_ms, xg_fl, xg_by = prof_read(lib, 4)
+        fw_n, fw_ms, fw_fl, fw_by = prof_read(lib, 5)
     precision = "f16x3" if lib.hgl_get_precision() == 1 else "f32"
 
     dt = D.max_over_ranks(dt, dist, dev)
@@ -743,7 +794,7 @@ def main():
 
     # ---- short secondary timings in the same process (N = 1 only)
     also = None
-    if world == 1 and not args.no_also and args.scope == "B" and args.fusion == "G2L" and args.clip == "ViT-B/16" and nbatch >= 2 \
+    if args.full and world == 1 and not args.no_also and args.scope == "B" and args.fusion == "G2L" and args.clip == "ViT-B/16" and nbatch >= 2 \
             and dependent:
         also = {}
 
@@ -902,7 +953,7 @@ def main():
     # ---- RCCL once on a 1-GPU box: the nccl branch of hybridgl_amd/dist.py in a world of one (device tensors through the
     # same two all-gathers + all-reduce the multi-GPU job uses); no process group is alive here at N = 1
     rccl = None
-    if world == 1 and not args.no_rccl_check:
+    if args.full and world == 1 and not args.no_rccl_check:
         try:
             rccl = D.rccl_selfcheck(dev, rows)
         except Exception as e:
@@ -917,7 +968,7 @@ def main():
             if os.path.exists(tpath):
                 break
         live = None
-        if world == 1 and not args.no_live_pmc:
+        if args.full and world == 1 and not args.no_live_pmc:
             if precision == "f16x3":
                 live_prefix = "gemm_x3p_kernel<" if xg_ms > x_ms else "gemm_f16x3_kernel<"
             else:
@@ -927,7 +978,7 @@ def main():
             live = live_pmc_traffic(pmc_table, pmc_note, live_prefix)
         if live is not None and live[0] is not None:
             traffic, traffic_src = live
-        elif os.path.exists(tpath):
+        elif args.full and os.path.exists(tpath):
             try:
                 tj = json.load(open(tpath))
                 # launch-weighted mean over the template instantiations of the dominant kernel
@@ -999,23 +1050,24 @@ def main():
                 "fusion_mode": args.fusion, "proposals": args.masks, "image": "640x640", "queries": 3,
                 "parallelism": f"image-parallel x{world}",
             },
-            "roofline": roofline(precision, nprof, (g_n, g_ms, g_fl), (x_n, x_ms, x_fl), (a_n, a_ms, a_fl), traffic,
-                                 algorithmic_flops_per_ref(args.masks, sam=args.scope == "B", gem=use_gem, clip_name=args.clip,
-                                                           text_S=max(r.token_len or 77 for r in refs)) / (dt / args.steps) / 1e12,
-                                 xg=(xg_n, xg_ms, xg_fl), few=(fw_n, fw_ms, fw_fl)),
             "precision": precision,
             "split_overflow_count": overflow,
             "metrics": m,
             "timed_region": timed_region,
         }
-        rec["roofline"]["traffic_source"] = traffic_src
-        if pmc_table is not None:
-            rec["roofline"]["hbm_kernels"] = hbm_kernel_table(pmc_table, tail_group=TAIL_GROUP_REFS)
+        if args.full:
+            rec["roofline"] = roofline(precision, nprof, (g_n, g_ms, g_fl), (x_n, x_ms, x_fl), (a_n, a_ms, a_fl), traffic,
+                                       algorithmic_flops_per_ref(args.masks, sam=args.scope == "B", gem=use_gem, clip_name=args.clip,
+                                                                 text_S=max(r.token_len or 77 for r in refs)) / (dt / args.steps) / 1e12,
+                                       xg=(xg_n, xg_ms, xg_fl), few=(fw_n, fw_ms, fw_fl))
+            rec["roofline"]["traffic_source"] = traffic_src
+            if pmc_table is not None:
+                rec["roofline"]["hbm_kernels"] = hbm_kernel_table(pmc_table, tail_group=TAIL_GROUP_REFS)
         if also is not None:
             rec["also"] = also
         if rccl is not None:
             rec["rccl_selfcheck"] = rccl
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args.fusion, with_sam=args.scope == "B", with_gem=use_gem, clip_name=args.clip,
                                                host_cores=host_cores_at_start)
         os.write(real_stdout, (json.dumps(rec) + "\n").encode())

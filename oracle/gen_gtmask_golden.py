@@ -1,5 +1,10 @@
 """Golden vectors of the ground-truth mask codec, produced by the reference's own C file compiled into
-oracle/_ref (make -C oracle).  Run here only:  python -m oracle.gen_gtmask_golden"""
+oracle/_ref (make -C oracle).  Run here only:  python -m oracle.gen_gtmask_golden
+
+tests/golden/gtmask.npz holds whole vectors; tests/golden/gtmask_fuzz.npz holds SHA-256 digests of the reference's outputs on
+the seeded fuzz cases of tests/test_gtmask.py (fuzz_cases / fuzz_rle_masks below), so that those tests pin the codec to the
+reference bit for bit where oracle/_ref is not built."""
+import hashlib
 import os
 
 import numpy as np
@@ -38,6 +43,70 @@ def cases():
     return out
 
 
+def digest(x):
+    """SHA-256 of a mask / count list (shape + int64 values) or of an RLE string"""
+    if isinstance(x, str):
+        return hashlib.sha256(x.encode("ascii")).hexdigest()
+    a = np.asarray(x, dtype=np.int64)
+    return hashlib.sha256(np.asarray(a.shape, np.int64).tobytes() + a.tobytes()).hexdigest()
+
+
+def fuzz_cases():
+    """tests/test_gtmask.py::test_fuzz_against_compiled_reference: 400 random polygon sets [(H, W, polys)], then 50 random
+    0/1 masks for the RLE string round trip (one generator, seed 5)"""
+    rng = np.random.default_rng(5)
+    polys_cases = []
+    for t in range(400):
+        H, W = int(rng.integers(3, 200)), int(rng.integers(3, 200))
+        polys = []
+        for _ in range(int(rng.integers(1, 4))):
+            k = int(rng.integers(1, 14))
+            xy = rng.random(2 * k) * np.tile([W + 20, H + 20], k) - 10
+            if t % 3 == 0:
+                xy = np.round(xy * 2) / 2
+            polys.append(xy.tolist())
+        polys_cases.append((H, W, polys))
+    masks = []
+    for t in range(50):
+        H, W = int(rng.integers(2, 120)), int(rng.integers(2, 120))
+        masks.append((rng.random((H, W)) < rng.random()).astype(np.uint8))
+    return polys_cases, masks
+
+
+def fuzz_rle_masks():
+    """tests/test_gtmask.py::test_rle_encoding_fuzz_against_compiled_reference: 120 masks, blobs (long runs) and noise (seed 8)"""
+    rng = np.random.default_rng(8)
+    out = []
+    for t in range(120):
+        H, W = int(rng.integers(1, 300)), int(rng.integers(1, 300))
+        if t % 4 == 0:       # blobs: long runs
+            m = np.zeros((H, W), np.uint8)
+            for _ in range(int(rng.integers(0, 5))):
+                y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
+                m[y0:y0 + int(rng.integers(1, H + 1)), x0:x0 + int(rng.integers(1, W + 1))] = 1
+        else:
+            m = (rng.random((H, W)) < rng.random() ** 2).astype(np.uint8)
+        out.append(m)
+    return out
+
+
+def fuzz_main(ref):
+    polys_cases, masks = fuzz_cases()
+    rec = {"poly_digest": [], "poly_area": [], "rt_string_digest": [], "rt_counts_digest": [],
+           "rle_string_digest": [], "rle_counts_digest": []}
+    for H, W, polys in polys_cases:
+        m, area = ref.poly_to_mask(polys, H, W)
+        rec["poly_digest"].append(digest(m))
+        rec["poly_area"].append(area)
+    for key, ms in (("rt", masks), ("rle", fuzz_rle_masks())):
+        for m in ms:
+            s, cnts = ref.encode_to_string(m)
+            rec[f"{key}_string_digest"].append(digest(s))
+            rec[f"{key}_counts_digest"].append(digest(cnts))
+    np.savez_compressed(os.path.join(GOLD, "gtmask_fuzz.npz"), **{k: np.array(v) for k, v in rec.items()})
+    print("gtmask fuzz golden:", len(polys_cases), "polygon cases,", len(masks), "+", len(rec["rle_string_digest"]), "RLE cases")
+
+
 def main():
     ref = G.RefMaskApi()
     rec = {}
@@ -73,6 +142,7 @@ def main():
     rec["n_rle"] = np.array([len(strs)])
     np.savez_compressed(os.path.join(GOLD, "gtmask.npz"), **rec)
     print("gtmask golden:", len(cs), "polygon cases,", len(strs), "RLE cases")
+    fuzz_main(ref)
 
 
 if __name__ == "__main__":

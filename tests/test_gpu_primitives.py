@@ -640,7 +640,7 @@ def test_gemm_f16x3_fp16_valued_weights_drop_the_zero_products(cuda):
 
 
 @pytest.mark.parametrize("B,H,S,hd,rel", [(2, 4, 2304, 80, True), (1, 8, 2048, 64, False), (1, 2, 2100, 80, False)])
-def test_ping_pong_attention_is_bit_identical_to_the_tile_kernel(cuda, B, H, S, hd, rel):
+def test_ping_pong_attention_is_bit_identical_to_the_tile_kernel(cuda, tmp_path, B, H, S, hd, rel):
     """attn_x3pp_kernel (one 8-wave workgroup per 256 queries, two wave groups one barrier interval apart, K / V chunks
     double-buffered) against attn_x3_kernel (HGL_ATTN_PP=0, a child process): same arithmetic per (query tile, key tile)
     pair -> identical bits; with the rel-pos tensors of SAM's global blocks, a 64-wide head, a ragged last key tile."""
@@ -661,7 +661,7 @@ np.save(sys.argv[1], ops.attention(q, k, v, {H}, **kw).cpu().numpy())
 """
     outs = []
     for pp in ("1", "0"):
-        path = f"/tmp/hgl_pp_{pp}_{S}_{hd}.npy"
+        path = str(tmp_path / f"hgl_pp_{pp}_{S}_{hd}.npy")
         r = subprocess.run([sys.executable, "-c", code, path], env=dict(os.environ, HGL_ATTN_PP=pp), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-1500:]
         outs.append(np.load(path))

@@ -1,8 +1,9 @@
 """Ground-truth mask codec + REFER reader.  Host code: runs without a GPU.
 
 hgl_gt_mask_* (C++ in libhybridgl.so) and the Python oracle are checked against vectors produced by the
-reference's own maskApi.c (tests/golden/gtmask.npz, oracle/gen_gtmask_golden.py) and, where the compiled
-reference is present (oracle/_ref), against it directly on random polygons.  Bar: bit-exact."""
+reference's own maskApi.c (tests/golden/gtmask.npz, oracle/gen_gtmask_golden.py) and on seeded random polygons / masks
+against the digests of that reference's outputs (tests/golden/gtmask_fuzz.npz) -- and against the compiled reference itself
+where it is present (oracle/_ref).  Bar: bit-exact."""
 import json
 import os
 import pickle
@@ -11,12 +12,18 @@ import numpy as np
 import pytest
 
 from hybridgl_amd import refer_io
+from oracle import gen_gtmask_golden as GG
 from oracle import gtmask_oracle as G
 
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
     return np.load(os.path.join(golden_dir, "gtmask.npz"))
+
+
+@pytest.fixture(scope="module")
+def fuzz_gold(golden_dir):
+    return np.load(os.path.join(golden_dir, "gtmask_fuzz.npz"))
 
 
 def _polys(gold, i):
@@ -64,26 +71,28 @@ def test_overlapping_polygons_count_twice(gold):
     assert m.max() == 2 and (m == 2).sum() > 0
 
 
-@pytest.mark.skipif(not G.have_ref(), reason="oracle/_ref not built (needs /root/reference at build time)")
-def test_fuzz_against_compiled_reference():
-    ref = G.RefMaskApi()
-    rng = np.random.default_rng(5)
-    for t in range(400):
-        H, W = int(rng.integers(3, 200)), int(rng.integers(3, 200))
-        polys = []
-        for _ in range(int(rng.integers(1, 4))):
-            k = int(rng.integers(1, 14))
-            xy = rng.random(2 * k) * np.tile([W + 20, H + 20], k) - 10
-            if t % 3 == 0:
-                xy = np.round(xy * 2) / 2
-            polys.append(xy.tolist())
-        want, wa = ref.poly_to_mask(polys, H, W)
+def test_fuzz_against_compiled_reference(fuzz_gold):
+    """400 random polygon sets and 50 RLE round trips (oracle/gen_gtmask_golden.py fuzz_cases): the masks and areas equal the
+    compiled reference's (their digests in tests/golden/gtmask_fuzz.npz; the reference itself too where oracle/_ref is built).
+    The round trips decode the reference's string and counts -- without oracle/_ref, the codec's own, pinned to the
+    reference's by their digests."""
+    from hybridgl_amd import sam as hsam
+    ref = G.RefMaskApi() if G.have_ref() else None
+    polys_cases, masks = GG.fuzz_cases()
+    for t, (H, W, polys) in enumerate(polys_cases):
         got, ga = refer_io.gt_mask_from_polygons(polys, H, W)
-        assert np.array_equal(got, want) and ga == wa, t
-    for t in range(50):
-        H, W = int(rng.integers(2, 120)), int(rng.integers(2, 120))
-        m = (rng.random((H, W)) < rng.random()).astype(np.uint8)
-        s, cnts = ref.encode_to_string(m)
+        assert GG.digest(got) == str(fuzz_gold["poly_digest"][t]) and ga == int(fuzz_gold["poly_area"][t]), t
+        if ref is not None:
+            want, wa = ref.poly_to_mask(polys, H, W)
+            assert np.array_equal(got, want) and ga == wa, t
+    for t, m in enumerate(masks):
+        H, W = m.shape
+        if ref is not None:
+            s, cnts = ref.encode_to_string(m)
+        else:
+            rle = hsam.mask_to_rle(m)
+            s, cnts = hsam.coco_encode_rle(rle)["counts"], rle["counts"]
+        assert GG.digest(s) == str(fuzz_gold["rt_string_digest"][t]) and GG.digest(cnts) == str(fuzz_gold["rt_counts_digest"][t]), t
         assert np.array_equal(refer_io.gt_mask_from_rle({"size": [H, W], "counts": s})[0], m)
         assert np.array_equal(refer_io.gt_mask_from_rle({"size": [H, W], "counts": cnts})[0], m)
 
@@ -109,26 +118,21 @@ def test_rle_output_modes_against_reference_vectors(gold):
     assert hsam.mask_to_rle(m)["counts"] == [0, 1, 1, 4]
 
 
-@pytest.mark.skipif(not G.have_ref(), reason="oracle/_ref not built (needs /root/reference at build time)")
-def test_rle_encoding_fuzz_against_compiled_reference():
+def test_rle_encoding_fuzz_against_compiled_reference(fuzz_gold):
     """hgl_rle_encode_mask / hgl_rle_to_string == rleEncode / rleToString of the reference's maskApi.c, incl. long runs
-    (negative differences between counts two places apart: the sign digit of the string format)"""
+    (negative differences between counts two places apart: the sign digit of the string format): against the digests of
+    the reference's outputs (tests/golden/gtmask_fuzz.npz) and, where oracle/_ref is built, against the reference itself"""
     from hybridgl_amd import sam as hsam
-    ref = G.RefMaskApi()
-    rng = np.random.default_rng(8)
-    for t in range(120):
-        H, W = int(rng.integers(1, 300)), int(rng.integers(1, 300))
-        if t % 4 == 0:       # blobs: long runs
-            m = np.zeros((H, W), np.uint8)
-            for _ in range(int(rng.integers(0, 5))):
-                y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                m[y0:y0 + int(rng.integers(1, H + 1)), x0:x0 + int(rng.integers(1, W + 1))] = 1
-        else:
-            m = (rng.random((H, W)) < rng.random() ** 2).astype(np.uint8)
-        s, cnts = ref.encode_to_string(m)
+    ref = G.RefMaskApi() if G.have_ref() else None
+    for t, m in enumerate(GG.fuzz_rle_masks()):
         rle = hsam.mask_to_rle(m)
-        assert rle["counts"] == cnts, t
-        assert hsam.coco_encode_rle(rle)["counts"] == s, t
+        s = hsam.coco_encode_rle(rle)["counts"]
+        assert GG.digest(rle["counts"]) == str(fuzz_gold["rle_counts_digest"][t]), t
+        assert GG.digest(s) == str(fuzz_gold["rle_string_digest"][t]), t
+        if ref is not None:
+            want_s, want_cnts = ref.encode_to_string(m)
+            assert rle["counts"] == want_cnts, t
+            assert s == want_s, t
 
 
 def test_error_reporting():

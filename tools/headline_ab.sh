@@ -11,6 +11,6 @@ print('$2', round(d['value'],2), 'img/s', round(d['ms_per_step'],2), 'ms/step; e
 for s in t['stages']: print('    ', s)
 "; }
 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 $F --no-prepare --no-balance > $O/${tag}_1_reduced_old.json 2>/dev/null; show $O/${tag}_1_reduced_old.json reduced_old
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-prepare --no-balance > $O/${tag}_2_full_old.json 2>/dev/null; show $O/${tag}_2_full_old.json full_old
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/${tag}_3_full_new.json 2>$O/${tag}_3_full_new.err; show $O/${tag}_3_full_new.json full_new
+python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-prepare --no-balance > $O/${tag}_2_full_old.json 2>/dev/null; show $O/${tag}_2_full_old.json full_old
+python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${tag}_3_full_new.json 2>$O/${tag}_3_full_new.err; show $O/${tag}_3_full_new.json full_new
 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 $F > $O/${tag}_4_reduced_new.json 2>/dev/null; show $O/${tag}_4_reduced_new.json reduced_new

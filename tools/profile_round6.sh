@@ -14,12 +14,12 @@ rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${tag}_dec_f
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${tag}_dec_write -o p -- python3 $R/tools/decoder_bench.py 5 23 > $O/${tag}_dec_write.log 2>&1
 python3 $R/tools/decoder_traffic.py $O/${tag}_dec_fetch $O/${tag}_dec_write 8 529 ${tag} > $O/${tag}_decoder_traffic.log 2>&1
 cp $R/profiles/${tag}_decoder_traffic.json $O/ 2>/dev/null
-python3 $R/bench.py > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.err
+python3 $R/bench.py --full > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.err
 tail -c 300 $O/${tag}_bench_default.json | head -c 200; echo
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_stats_serial -o p -- python3 $R/tools/group_profile.py 3 16 > $O/${tag}_stats_serial.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_stats -o p -- python3 $R/bench.py --steps 32 --warmup 16 --no-cpu-baseline --no-also --no-disk --no-rccl-check --no-live-pmc > $O/${tag}_stats.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${tag}_fetch -o p -- python3 $R/bench.py --steps 16 --warmup 16 --no-cpu-baseline --no-also --no-disk --no-rccl-check --no-live-pmc > $O/${tag}_fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${tag}_write -o p -- python3 $R/bench.py --steps 16 --warmup 16 --no-cpu-baseline --no-also --no-disk --no-rccl-check --no-live-pmc > $O/${tag}_write.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_stats -o p -- python3 $R/bench.py --full --steps 32 --warmup 16 --no-cpu-baseline --no-also --no-disk --no-rccl-check --no-live-pmc > $O/${tag}_stats.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${tag}_fetch -o p -- python3 $R/bench.py --full --steps 16 --warmup 16 --no-cpu-baseline --no-also --no-disk --no-rccl-check --no-live-pmc > $O/${tag}_fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/${tag}_write -o p -- python3 $R/bench.py --full --steps 16 --warmup 16 --no-cpu-baseline --no-also --no-disk --no-rccl-check --no-live-pmc > $O/${tag}_write.log 2>&1
 for f in $O/${tag}_stats_serial; do
   s=$(find $f -name "*kernel_stats.csv" | head -1); [ -n "$s" ] && cp $s $O/${tag}_serial_group_kernel_stats.csv
 done
@@ -50,7 +50,7 @@ for t in attn_win attn_glob attn_clip; do cp $O/pmc_${tag}_$t/summary.json $O/${
 find $O/${tag}_stats $O/${tag}_stats_serial -name "*kernel_trace.csv" -delete 2>/dev/null
 rm -rf $O/${tag}_fetch $O/${tag}_write $O/${tag}_dec_fetch $O/${tag}_dec_write
 # LAST: the driver's own command, as the driver runs it (a fresh process after everything above), and its repeatability
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/${tag}_bench_driver_cmd.json 2> $O/${tag}_bench_driver_cmd.err
+python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${tag}_bench_driver_cmd.json 2> $O/${tag}_bench_driver_cmd.err
 bash $R/tools/headline_repeat.sh ${tag} 3 > /dev/null 2>&1
 python3 -c "
 import json
