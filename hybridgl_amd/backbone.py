@@ -59,7 +59,7 @@ class _Blocks:
                 t = _to_dev(sd[f"{prefix}.resblocks.{i}.{key}"], device)
                 self.t.append(t)
                 setattr(self.arr[i], field, t.data_ptr())
-                if precision == "f16x3" and field in ("in_proj_w", "out_proj_w", "fc_w", "proj_w"):
+                if ops.split_mode(precision) and field in ("in_proj_w", "out_proj_w", "fc_w", "proj_w"):
                     ops.register_split_weight(t)   # fp16 hi/lo halves for the split matrix-core path
 
 
@@ -95,7 +95,7 @@ class _ClipModel:
             "ln_post_b": _to_dev(sd["visual.ln_post.bias"], device),
             "proj_t": _to_dev(np.ascontiguousarray(np.asarray(sd["visual.proj"]).T), device),
         }
-        if precision == "f16x3" and self._vt["conv1"].shape[1] % 64 == 0:
+        if ops.split_mode(precision) and self._vt["conv1"].shape[1] % 64 == 0:
             ops.register_split_weight(self._vt["conv1"])     # patch embedding as a split-fp16 GEMM
         v = HglClipVisionW()
         v.width, v.layers, v.heads, v.patch, v.grid, v.embed = vw, vl, vw // 64, p, grid, cfg["embed_dim"]
@@ -186,8 +186,9 @@ class CLIPViTFM:
 
     def __init__(self, model_name="ViT-B/16", size=224, state_dict=None, checkpoint=None, seed=0,
                  device="cuda", precision=None):
-        """precision: 'f32' (exact fp32 MFMA) or 'f16x3' (split-fp16 MFMA, fp32-class accuracy, ~2.4x
-        faster GEMMs); default from HYBRIDGL_PRECISION (ops.default_precision)."""
+        """precision: 'f32' (exact fp32 MFMA), 'f16x3' (split-fp16 MFMA, fp32-class accuracy, ~2.4x faster GEMMs) or
+        'f16' (fp16 GEMM operands, fp32 accumulation: opt-in, not fp32-class); default from HYBRIDGL_PRECISION
+        (ops.default_precision)."""
         _lib.load()
         precision = precision or ops.default_precision()
         ops.use_precision(precision)

@@ -280,7 +280,9 @@ __device__ __forceinline__ h16x4 lds_tr4(const _Float16* p) {
 // NW waves per workgroup, 32 queries each: 4 (two workgroups per CU) or 8 (one workgroup per CU, 256 queries: a
 // 14 x 14 window or a 197-token CLIP sequence is then ONE workgroup that stages the keys and values once instead of
 // two workgroups that each stage all of them).
-template <int HD, int RELW, int NW = 4>
+// TERMS = 1 (f16 mode): q, k, v, P and the rel-pos tables are rounded to fp16 and only the hi halves are staged and multiplied
+// (P rounded to nearest); the rel-pos BIAS of the global blocks is added as its hi + lo pair as before.
+template <int HD, int RELW, int NW = 4, int TERMS = 3>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnArgs a) {
   constexpr int NT = NW * 64;
   constexpr int KS = HD / 16;                 // k-steps of the QK^T contraction
@@ -380,7 +382,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
         _Float16 hi, lo;
         hgl_split_hi_lo(v[e], hi, lo, amax);
         qh[s][4 * half + e] = hi;
-        ql[s][4 * half + e] = lo;
+        if constexpr (TERMS != 1) ql[s][4 * half + e] = lo;
       }
     }
   }
@@ -426,7 +428,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
 #pragma unroll
             for (int sx = 0; sx < KS; ++sx) {
               thr[sx] = *(const h16x8*)(Th + to + 16 * sx);
-              tlr[sx] = *(const h16x8*)(Tl + to + 16 * sx);
+              if constexpr (TERMS != 1) tlr[sx] = *(const h16x8*)(Tl + to + 16 * sx);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (r >= 2 * RELW - 1) {
@@ -437,8 +439,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
             }
 #pragma unroll
             for (int sx = 0; sx < KS; ++sx) {
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(tlr[sx], qh[sx], acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(thr[sx], ql[sx], acc, 0, 0, 0);
+              if constexpr (TERMS != 1) {   // TERMS = 1: the tables' hi halves only
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(tlr[sx], qh[sx], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(thr[sx], ql[sx], acc, 0, 0, 0);
+              }
               acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(thr[sx], qh[sx], acc, 0, 0, 0);
             }
           } else {
@@ -468,8 +472,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
                   tl[4 * half + e] = lo;
                 }
               }
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh[sx], acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql[sx], acc, 0, 0, 0);
+              if constexpr (TERMS != 1) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl, qh[sx], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, ql[sx], acc, 0, 0, 0);
+              }
               acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(th, qh[sx], acc, 0, 0, 0);
             }
           }
@@ -544,7 +550,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
       h16x4 hi, lo;
       split4(pk[i], hi, lo, amax);
       *(h16x4*)(Ks + row * KROW + c4 * 4) = hi;
-      *(h16x4*)(Ks + row * KROW + HD + c4 * 4) = lo;
+      if constexpr (TERMS != 1) *(h16x4*)(Ks + row * KROW + HD + c4 * 4) = lo;
     }
     if (RELW > 0 && t < 256) {   // indicator columns: thread -> (key row t/4, 8 of the 32 columns)
       const int row = t >> 2, j0 = 8 * (t & 3), kg = kc + row;
@@ -562,7 +568,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
       h16x4 hi, lo;
       split4(pv[i], hi, lo, amax);
       *(h16x4*)(Vh + row * VP + c4 * 4) = hi;
-      *(h16x4*)(Vl + row * VP + c4 * 4) = lo;
+      if constexpr (TERMS != 1) *(h16x4*)(Vl + row * VP + c4 * 4) = lo;
     }
   };
   if (VP > HD) {  // zero the d padding of every row once (it feeds output rows that are never stored)
@@ -625,8 +631,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
       for (int c = 0; c < KS; ++c) {
         const h16x8 kh8 = *(const h16x8*)(krow + 16 * c);
         const h16x8 kl8 = *(const h16x8*)(krow + HD + 16 * c);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[c], s, 0, 0, 0);
+        if constexpr (TERMS != 1) {
+          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[c], s, 0, 0, 0);
+          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[c], s, 0, 0, 0);
+        }
         s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qh[c], s, 0, 0, 0);
       }
       if constexpr (RELW > 0) {
@@ -697,10 +705,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
         rs += p0;
         rs += p1;
         // hi by one packed round-toward-zero conversion (any rounding works: lo is the exact remainder, rounded to nearest)
-        const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-        ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
-        pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
-        pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
+        if constexpr (TERMS == 1) {   // P rounded to nearest, hi only
+          ph[e >> 3][e & 7] = (_Float16)p0; ph[e >> 3][(e & 7) + 1] = (_Float16)p1;
+        } else {
+          const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
+          ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
+          pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
+          pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
+        }
       }
       l_run += rs;
       // the scores are dead from here on: the next tile's rel-pos terms are requested now and travel under the P V products
@@ -717,8 +729,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
           h16x8 vh8, vl8;
 #pragma unroll
           for (int e = 0; e < 4; ++e) { vh8[e] = vh0[e]; vh8[4 + e] = vh1[e]; vl8[e] = vl0[e]; vl8[4 + e] = vl1[e]; }
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[d], 0, 0, 0);
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[d], 0, 0, 0);
+          if constexpr (TERMS != 1) {
+            o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[d], 0, 0, 0);
+            o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[d], 0, 0, 0);
+          }
           o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, ph[s2], o[d], 0, 0, 0);
         }
       }
@@ -756,7 +770,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
               lo[e] = c2;
             }
             *(h16x4*)(a.out_hi + oo + dd) = hi;
-            *(h16x4*)(a.out_lo + oo + dd) = lo;
+            if (a.out_lo) *(h16x4*)(a.out_lo + oo + dd) = lo;
           }
         }
       }
@@ -782,7 +796,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
 // (each thread its own pieces, fetched four intervals earlier), after the last reader of the buffer's previous chunk
 // (group B's P V of tile 2c-3, interval 4c-3) and before its first reader (group A's Q K^T of tile 2c, interval 4c).
 // The arithmetic of a (query tile, key tile) pair is attn_x3_kernel's, instruction for instruction: identical results.
-template <int HD>
+template <int HD, int TERMS = 3>   // TERMS = 1: see attn_x3_kernel
 __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
   constexpr int NT = 512;
   constexpr int KS = HD / 16;
@@ -849,10 +863,10 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
       split4(pc[i], hi, lo, amax);
       if (p < HALF) {
         *(h16x4*)(Ks + buf * KBUF + row * KROW + c4 * 4) = hi;
-        *(h16x4*)(Ks + buf * KBUF + row * KROW + HD + c4 * 4) = lo;
+        if constexpr (TERMS != 1) *(h16x4*)(Ks + buf * KBUF + row * KROW + HD + c4 * 4) = lo;
       } else {
         *(h16x4*)(Vh + buf * VBUF + row * VP + c4 * 4) = hi;
-        *(h16x4*)(Vl + buf * VBUF + row * VP + c4 * 4) = lo;
+        if constexpr (TERMS != 1) *(h16x4*)(Vl + buf * VBUF + row * VP + c4 * 4) = lo;
       }
     }
   };
@@ -879,7 +893,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
           _Float16 hi, lo;
           hgl_split_hi_lo(qraw[s][half][e], hi, lo, amax);
           qh[s][4 * half + e] = hi;
-          ql[s][4 * half + e] = lo;
+          if constexpr (TERMS != 1) ql[s][4 * half + e] = lo;
         }
   }
   if (VP > HD) {   // zero the d padding of both V buffers once
@@ -944,8 +958,10 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
         h16x8 vh8, vl8;
 #pragma unroll
         for (int e = 0; e < 4; ++e) { vh8[e] = vh0[e]; vh8[4 + e] = vh1[e]; vl8[e] = vl0[e]; vl8[4 + e] = vl1[e]; }
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[d], 0, 0, 0);
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[d], 0, 0, 0);
+        if constexpr (TERMS != 1) {
+          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[d], 0, 0, 0);
+          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[d], 0, 0, 0);
+        }
         o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, ph[s2], o[d], 0, 0, 0);
       }
     }
@@ -971,8 +987,10 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
       for (int c = 0; c < KS; ++c) {
         const h16x8 kh8 = *(const h16x8*)(krow + 16 * c);
         const h16x8 kl8 = *(const h16x8*)(krow + HD + 16 * c);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[c], s, 0, 0, 0);
+        if constexpr (TERMS != 1) {
+          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[c], s, 0, 0, 0);
+          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[c], s, 0, 0, 0);
+        }
         s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qh[c], s, 0, 0, 0);
       }
       __builtin_amdgcn_s_setprio(0);
@@ -1026,10 +1044,14 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
         const float p1 = __builtin_amdgcn_exp2f(fmaf(s[e + 1], sl2e, mneg));
         rs += p0;
         rs += p1;
-        const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-        ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
-        pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
-        pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
+        if constexpr (TERMS == 1) {   // P rounded to nearest, hi only
+          ph[e >> 3][e & 7] = (_Float16)p0; ph[e >> 3][(e & 7) + 1] = (_Float16)p1;
+        } else {
+          const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
+          ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
+          pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
+          pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
+        }
       }
       l_run += rs;
     }
@@ -1068,7 +1090,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
               lo[e] = c2;
             }
             *(h16x4*)(a.out_hi + oo + dd) = hi;
-            *(h16x4*)(a.out_lo + oo + dd) = lo;
+            if (a.out_lo) *(h16x4*)(a.out_lo + oo + dd) = lo;
           }
         }
       }
@@ -1083,7 +1105,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
 // waits for its loads, splits a chunk or stores its output rows, the other multiplies.  (The 8-wave workgroups put both
 // waves of a SIMD on the SAME item: they meet at every chunk barrier and wait for the same loads.)  Arithmetic per
 // (query tile, key tile) is that of attn_x3_kernel, operation for operation.
-template <int HD, int QT>
+template <int HD, int QT, int TERMS = 3>   // TERMS = 1: see attn_x3_kernel
 __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
   constexpr int NW = 4, NT = NW * 64;
   constexpr int KS = HD / 16;
@@ -1145,7 +1167,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
           _Float16 hi, lo;
           hgl_split_hi_lo(v[e] * a.scale, hi, lo, amax);
           qh[qt][s][4 * half + e] = hi;
-          ql[qt][s][4 * half + e] = lo;
+          if constexpr (TERMS != 1) ql[qt][s][4 * half + e] = lo;
         }
       }
   }
@@ -1187,10 +1209,10 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
         h16x4 hi, lo;
         split4(pk[i], hi, lo, amax);
         *(h16x4*)(Ks + row * KROW + c4 * 4) = hi;
-        *(h16x4*)(Ks + row * KROW + HD + c4 * 4) = lo;
+        if constexpr (TERMS != 1) *(h16x4*)(Ks + row * KROW + HD + c4 * 4) = lo;
         split4(pv[i], hi, lo, amax);
         *(h16x4*)(Vh + row * VP + c4 * 4) = hi;
-        *(h16x4*)(Vl + row * VP + c4 * 4) = lo;
+        if constexpr (TERMS != 1) *(h16x4*)(Vl + row * VP + c4 * 4) = lo;
       }
     }
   };
@@ -1225,8 +1247,10 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
         for (int c = 0; c < KS; ++c) {
           const h16x8 kh8 = *(const h16x8*)(krow + 16 * c);
           const h16x8 kl8 = *(const h16x8*)(krow + HD + 16 * c);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[qt][c], s, 0, 0, 0);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[qt][c], s, 0, 0, 0);
+          if constexpr (TERMS != 1) {
+            s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[qt][c], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[qt][c], s, 0, 0, 0);
+          }
           s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qh[qt][c], s, 0, 0, 0);
         }
         if (kbase + 32 > a.Sk) {   // uniform: the tile that crosses the end of the sequence
@@ -1272,10 +1296,14 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
           const float p1 = __builtin_amdgcn_exp2f(fmaf(s[e + 1], LOG2E, mneg));
           rs += p0;
           rs += p1;
-          const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-          ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
-          pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
-          pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
+          if constexpr (TERMS == 1) {   // P rounded to nearest, hi only
+            ph[e >> 3][e & 7] = (_Float16)p0; ph[e >> 3][(e & 7) + 1] = (_Float16)p1;
+          } else {
+            const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
+            ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
+            pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
+            pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
+          }
         }
         l_run[qt] += rs;
 #pragma unroll
@@ -1289,8 +1317,10 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
             h16x8 vh8, vl8;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { vh8[e] = vh0[e]; vh8[4 + e] = vh1[e]; vl8[e] = vl0[e]; vl8[4 + e] = vl1[e]; }
-            o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[qt][d], 0, 0, 0);
-            o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[qt][d], 0, 0, 0);
+            if constexpr (TERMS != 1) {
+              o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[qt][d], 0, 0, 0);
+              o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[qt][d], 0, 0, 0);
+            }
             o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, ph[s2], o[qt][d], 0, 0, 0);
           }
         }
@@ -1331,7 +1361,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
                 lo[e] = c2;
               }
               *(h16x4*)(a.out_hi + oo + dd) = hi;
-              *(h16x4*)(a.out_lo + oo + dd) = lo;
+              if (a.out_lo) *(h16x4*)(a.out_lo + oo + dd) = lo;
             }
           }
         }
@@ -1431,7 +1461,7 @@ __global__ __launch_bounds__(256) void attn_smallk_kernel(SmallKArgs a) {
         lo[e] = c2;
       }
       *(h16x4*)(a.out_hi + oo + 4 * c) = hi;
-      *(h16x4*)(a.out_lo + oo + 4 * c) = lo;
+      if (a.out_lo) *(h16x4*)(a.out_lo + oo + 4 * c) = lo;
     }
   }
 }
@@ -1716,12 +1746,13 @@ __global__ __launch_bounds__(128) void attn_fewq_combine_kernel(const float* __r
   out[b * sob + (long long)qi * ldo + ll * 8 + d] = acc / lsum;
 }
 
-template <int HD>
+// TERMS: 3 (f16x3) or 1 (f16 mode: the one-term flavours)
+template <int HD, int TERMS>
 int launch_hd(const AttnArgs& a, hipStream_t st) {
   dim3 grid((a.Sq + 127) / 128, a.B * a.H);
   HglProfScope prof(HGL_PROF_ATTN, 4.0 * a.B * a.H * (double)a.Sq * a.Sk * HD,
                     4.0 * a.B * a.H * HD * (2.0 * a.Sq + 2.0 * a.Sk), st);
-  if (hgl_precision() == HGL_PREC_F16X3) {
+  if (hgl_split_layout()) {   // (f16 mode: q, k, v arrive as fp32; the TERMS = 1 flavours round them to fp16 in the kernel)
     // sequences of 129..256 queries (a 14 x 14 window, a 197-token CLIP sequence): one 8-wave workgroup per (batch, head)
     static const int wide = HGL_DIAG_SWITCH("HGL_ATTN_WIDE", 1);
     static const int dual = HGL_DIAG_SWITCH("HGL_ATTN_DUAL", 1);
@@ -1740,22 +1771,22 @@ int launch_hd(const AttnArgs& a, hipStream_t st) {
           ((a.Sk & 31) == 0 || !a.rel_h)) {
         constexpr int KROW_ = 2 * HD + 8, VP_ = 96;
         constexpr size_t lds = (size_t)2 * KV_CHUNK * (KROW_ + 2 * VP_) * sizeof(_Float16);
-        HGL_RESERVE_LDS((attn_x3pp_kernel<HD>), lds, "attention (ping-pong kernel)");
-        hipLaunchKernelGGL((attn_x3pp_kernel<HD>), dim3((a.Sq + 255) / 256, a.B * a.H), dim3(512), lds, st, a);
+        HGL_RESERVE_LDS((attn_x3pp_kernel<HD, TERMS>), lds, "attention (ping-pong kernel)");
+        hipLaunchKernelGGL((attn_x3pp_kernel<HD, TERMS>), dim3((a.Sq + 255) / 256, a.B * a.H), dim3(512), lds, st, a);
         return hgl_check_launch("attention");
       }
     }
     if (HD == 80 && a.rel_h && a.kh == 14 && a.kw == 14 && a.Sk == 196 && a.mask_kind == HGL_MASK_NONE) {
-      hipLaunchKernelGGL((attn_x3_kernel<HD, HD == 80 ? 14 : 0>), grid, dim3(256), 0, st, a);   // rel_h / rel_w given as tensors
+      hipLaunchKernelGGL((attn_x3_kernel<HD, HD == 80 ? 14 : 0, 4, TERMS>), grid, dim3(256), 0, st, a);   // rel_h / rel_w given as tensors
     } else if (w8 && !a.rel_h && dual && HD == 64 && (a.mask_kind != HGL_MASK_CLS_KEEP || a.Sk <= 257)) {
       // head dim 64 (the CLIP sequences): two items per CU -- one 4-wave workgroup per item, two query tiles per wave.
       // 868 against 976 us on 1024 x 12 x 197 x 64 (141 against 125 TF/s), -0.4 ms per benchmark step (HGL_ATTN_DUAL=0: the
       // persistent 8-wave kernel)
-      hipLaunchKernelGGL((attn_x3q_kernel<HD == 64 ? 64 : 16, 2>), dim3((unsigned)(a.B * a.H)), dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_x3q_kernel<HD == 64 ? 64 : 16, 2, TERMS>), dim3((unsigned)(a.B * a.H)), dim3(256), 0, st, a);
     } else if (w8 && !a.rel_h) {   // one 8-wave workgroup per item (K / V staged once)
-      hipLaunchKernelGGL((attn_x3_kernel<HD, 0, 8>), dim3((a.Sq + 255) / 256, a.B * a.H), dim3(512), 0, st, a);
+      hipLaunchKernelGGL((attn_x3_kernel<HD, 0, 8, TERMS>), dim3((a.Sq + 255) / 256, a.B * a.H), dim3(512), 0, st, a);
     } else {
-      hipLaunchKernelGGL((attn_x3_kernel<HD, 0>), grid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((attn_x3_kernel<HD, 0, 4, TERMS>), grid, dim3(256), 0, st, a);
     }
   }
   else hipLaunchKernelGGL(attn_f32_kernel<HD>, grid, dim3(256), 0, st, a);
@@ -1773,7 +1804,7 @@ int hgl_launch_attention_win14(const float* q, const float* k, const float* v, v
                                float scale, const float* Rh, const float* Rw, hipStream_t st) {
   static const int wide = HGL_DIAG_SWITCH("HGL_ATTN_WIDE", 1);
   static const int fused = HGL_DIAG_SWITCH("HGL_ATTN_RELPOS_FUSED", 1);
-  if (!wide || !fused || hd != 80 || hgl_precision() != HGL_PREC_F16X3 || !out_hi || !out_lo || !Rh || !Rw) return 1;
+  if (!wide || !fused || hd != 80 || !hgl_split_layout() || !out_hi || !out_lo || !Rh || !Rw) return 1;
   HGL_REQUIRE(q && k && v && B > 0 && H > 0 && (long long)B * H <= 65535, "attention_win14: bad arguments");
   AttnArgs a;
   a.q = q; a.k = k; a.v = v; a.out = nullptr;
@@ -1792,9 +1823,10 @@ int hgl_launch_attention_win14(const float* q, const float* k, const float* v, v
       a.tabw_hi = (const _Float16*)wh; a.tabw_lo = (const _Float16*)wl;
     }
   }
-  a.out_hi = (_Float16*)out_hi; a.out_lo = (_Float16*)out_lo;
+  a.out_hi = (_Float16*)out_hi; a.out_lo = hgl_split_terms() == 1 ? nullptr : (_Float16*)out_lo;   // f16 mode: hi plane only
   HglProfScope prof(HGL_PROF_ATTN, 4.0 * B * H * 196.0 * 196.0 * 80, 0.0, st);
-  hipLaunchKernelGGL((attn_x3_kernel<80, 14, 8>), dim3(1, (unsigned)(B * H)), dim3(512), 0, st, a);
+  if (hgl_split_terms() == 1) hipLaunchKernelGGL((attn_x3_kernel<80, 14, 8, 1>), dim3(1, (unsigned)(B * H)), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((attn_x3_kernel<80, 14, 8>), dim3(1, (unsigned)(B * H)), dim3(512), 0, st, a);
   return hgl_check_launch("attention_win14");
 }
 
@@ -1807,7 +1839,8 @@ int hgl_launch_attention_smallk(const float* q, const float* k, const float* v, 
   HGL_REQUIRE(((ldq | ldk | ldv | ldo) & 3) == 0 && ((sqb | skb | svb | sob) & 3) == 0, "attention_smallk: strides must be multiples of 4");
   HGL_REQUIRE(B <= 65535, "attention_smallk: B too large");
   SmallKArgs a;
-  a.q = q; a.k = k; a.v = v; a.out = out; a.out_hi = (_Float16*)out_hi; a.out_lo = (_Float16*)out_lo;
+  a.q = q; a.k = k; a.v = v; a.out = out; a.out_hi = (_Float16*)out_hi;
+  a.out_lo = hgl_split_terms() == 1 ? nullptr : (_Float16*)out_lo;   // f16 mode: hi plane only
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
   a.sqb = sqb; a.skb = skb; a.svb = svb; a.sob = sob; a.scale = scale;
   const int qpb = 256 / H;
@@ -1871,7 +1904,7 @@ int hgl_launch_attention_split(const float* q, const float* k, const float* v, f
                                const uint8_t* keep, int keep_b0, int keep_n, const float* rel_h,
                                const float* rel_w, int kh, int kw, hipStream_t st) {
   HGL_REQUIRE(q && k && v && (out || (out_hi && out_lo)), "attention: null operand");
-  HGL_REQUIRE(out || hgl_precision() == HGL_PREC_F16X3, "attention: split output exists in f16x3 mode only");
+  HGL_REQUIRE(out || hgl_split_layout(), "attention: split output exists in the split-fp16 modes only");
   HGL_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "attention: bad shape");
   HGL_REQUIRE((ldq & 3) == 0 && (ldk & 3) == 0 && (ldv & 3) == 0 && (ldo & 3) == 0, "attention: leading dims must be multiples of 4");
   HGL_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15) == 0,
@@ -1895,12 +1928,13 @@ int hgl_launch_attention_split(const float* q, const float* k, const float* v, f
   a.scale = scale; a.mask_kind = mask_kind; a.keep = keep; a.keep_b0 = keep_b0; a.keep_n = keep_n > 0 ? keep_n : B;
   a.rel_h = rel_h; a.rel_w = rel_w; a.kh = kh; a.kw = kw;
   a.tab_h = nullptr; a.tab_w = nullptr;
-  a.out_hi = (_Float16*)out_hi; a.out_lo = (_Float16*)out_lo;
+  a.out_hi = (_Float16*)out_hi; a.out_lo = hgl_split_terms() == 1 ? nullptr : (_Float16*)out_lo;   // f16 mode: hi plane only
+  const bool one = hgl_split_terms() == 1;
   switch (hd) {
-    case 16: return launch_hd<16>(a, st);
-    case 32: return launch_hd<32>(a, st);
-    case 64: return launch_hd<64>(a, st);
-    case 80: return launch_hd<80>(a, st);
+    case 16: return one ? launch_hd<16, 1>(a, st) : launch_hd<16, 3>(a, st);
+    case 32: return one ? launch_hd<32, 1>(a, st) : launch_hd<32, 3>(a, st);
+    case 64: return one ? launch_hd<64, 1>(a, st) : launch_hd<64, 3>(a, st);
+    case 80: return one ? launch_hd<80, 1>(a, st) : launch_hd<80, 3>(a, st);
     default:
       hgl_set_error("attention: unsupported head dim %d (16,32,64,80)", hd);
       return HGL_EINVAL;

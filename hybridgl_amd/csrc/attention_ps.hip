@@ -1056,7 +1056,8 @@ extern "C" int hgl_debug_ps_stamps(unsigned long long* out, int n, int block, in
 }
 #endif
 
-bool hgl_attention_ps_enabled() { return attn_ps_flag() != 0 && hgl_precision() == HGL_PREC_F16X3; }
+// the kernels here read the lo planes the qkv GEMM writes: three-term mode only (f16 mode takes the fp32-input kernels)
+bool hgl_attention_ps_enabled() { return attn_ps_flag() != 0 && hgl_split_layout() && hgl_split_terms() == 3; }
 
 extern "C" int hgl_attention_presplit(int on) {
   const int prev = attn_ps_flag();
@@ -1163,7 +1164,7 @@ extern "C" int hgl_attention_presplit_f32(const float* qkv, int ld, int B, int H
   HGL_REQUIRE(qkv && out && scratch && B > 0 && H > 0 && S > 0 && ld >= 3 * H * hd && (ld & 7) == 0, "attention_presplit: bad arguments");
   const size_t n = (size_t)B * S * ld;
   HGL_REQUIRE(scratch_bytes >= n * 4, "attention_presplit: scratch too small (%zu bytes for %zu)", scratch_bytes, n * 4);
-  HGL_REQUIRE(hgl_precision() == HGL_PREC_F16X3, "attention_presplit: split-fp16 mode only");
+  HGL_REQUIRE(hgl_split_layout() && hgl_split_terms() == 3, "attention_presplit: f16x3 mode only");
   hipStream_t st = (hipStream_t)stream;
   uint16_t* hi = (uint16_t*)scratch;
   uint16_t* lo = hi + n;

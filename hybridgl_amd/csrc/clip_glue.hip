@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void im2col_patch_split_kernel(const float* __
       b[j] = l0;
     }
     *(h16x4_t*)(hi + e) = a;
-    *(h16x4_t*)(lo + e) = b;
+    if (lo) *(h16x4_t*)(lo + e) = b;   // nullptr: f16 mode, hi plane only
   }
 }
 
@@ -320,7 +320,8 @@ int hgl_launch_im2col_patch_split(const float* img, int N, int res, int patch, v
   HGL_REQUIRE(img && hi && lo && N > 0 && res > 0 && patch > 0 && res % patch == 0 && patch % 4 == 0,
               "im2col_split: bad arguments (res=%d patch=%d)", res, patch);
   const long long total = (long long)N * 3 * res * res;
-  hipLaunchKernelGGL(im2col_patch_split_kernel, dim3(grid_for(total / 4)), dim3(256), 0, st, img, (_Float16*)hi, (_Float16*)lo, N,
+  hipLaunchKernelGGL(im2col_patch_split_kernel, dim3(grid_for(total / 4)), dim3(256), 0, st, img, (_Float16*)hi,
+                     hgl_split_terms() == 1 ? nullptr : (_Float16*)lo, N,
                      res, patch, total / 4);
   return hgl_check_launch("im2col_patch_split");
 }

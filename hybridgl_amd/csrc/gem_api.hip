@@ -34,17 +34,17 @@ __global__ __launch_bounds__(256) void row_norm_kernel(const float* __restrict__
   if (lane == 0) norms[row] = sqrtf(s);
 }
 
-// the same from the fp16 (hi, lo) pair of the split path: x = hi + lo
+// the same from the fp16 (hi, lo) pair of the split path: x = hi + lo (Hl == nullptr, f16 mode: x = hi, the operand the GEMMs see)
 __global__ __launch_bounds__(256) void row_norm_split_kernel(const _Float16* __restrict__ Hh, const _Float16* __restrict__ Hl, int S,
                                                              int D, float* __restrict__ norms) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= S) return;
   const _Float16* h = Hh + (long long)row * D;
-  const _Float16* l = Hl + (long long)row * D;
+  const _Float16* l = Hl ? Hl + (long long)row * D : nullptr;
   float s = 0.f;
   for (int i = lane; i < D; i += 64) {
-    const float x = (float)h[i] + (float)l[i];
+    const float x = l ? (float)h[i] + (float)l[i] : (float)h[i];
     s += x * x;
   }
   s = wave_sum(s);
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void mean3_split_kernel(const float* __restric
     _Float16 h, l;
     hgl_split_hi_lo(m, h, l);
     hi[i] = h;
-    lo[i] = l;
+    if (lo) lo[i] = l;   // nullptr: f16 mode, hi plane only
   }
 }
 
@@ -314,7 +314,7 @@ int gem_block(const HglResBlockW& w, const GemPlan& p, int S, int D, int heads, 
   } else {
     if (x3)
       hipLaunchKernelGGL(row_norm_split_kernel, dim3((M + 3) / 4), dim3(256), 0, st, (const _Float16*)p.H,
-                         (const _Float16*)p.H + MD, M, D, p.norms);
+                         hgl_split_terms() == 1 ? nullptr : (const _Float16*)p.H + MD, M, D, p.norms);
     else
       hipLaunchKernelGGL(row_norm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, p.H, M, D, p.norms);
     hipLaunchKernelGGL(temp_kernel, dim3(nb), dim3(256), 0, st, p.norms, S, scale, p.t);   // one temperature per image
@@ -341,7 +341,8 @@ int gem_block(const HglResBlockW& w, const GemPlan& p, int S, int D, int heads, 
   if (x3) {
     _Float16* Mh = (_Float16*)p.N3;
     _Float16* Ml = Mh + MD;
-    hipLaunchKernelGGL(mean3_split_kernel, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, p.X1, MD, MD, Mh, Ml);
+    hipLaunchKernelGGL(mean3_split_kernel, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, p.X1, MD, MD, Mh,
+                       hgl_split_terms() == 1 ? nullptr : Ml);
     HGL_TRY(hgl_check_launch("gem_mean3"));
     HGL_TRY(hgl_launch_gemm_f16x3(Mh, Ml, D, w.out_proj_w, w.out_proj_b, p.Xg, D, p.Xg, nullptr, nullptr, D, M, D, D,
                                   HGL_ACT_NONE, st));

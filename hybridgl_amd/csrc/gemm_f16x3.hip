@@ -60,6 +60,7 @@ struct Args {
   int M, N, K, lda, ldw, ldr, ldc;
   float out_scale;
   int lo_zero;                // the W_lo plane is all zero: the A_hi * W_lo products are skipped (they add exact zeros)
+  int one_term;               // f16 mode: A_hi * W_hi only; no lo plane is read, a split output is written as its hi plane only
   int tiles_m, tiles_n;
   int gm;      // M-tiles per tile group (L2 blocking of the resident tile set)
   float* part;   // split-K (ping-pong kernel, grid.y = ksplit): raw partial sums [ksplit][M][N]; bias / act / residual are
@@ -144,7 +145,7 @@ __device__ __forceinline__ void x3_store_block(const Args& g, const f32x4 acc, i
         lo4[e] = ll;
       }
       *(f16x4*)(g.Ch + off) = hi4;
-      *(f16x4*)(g.Cl + off) = lo4;
+      if (!g.one_term) *(f16x4*)(g.Cl + off) = lo4;
     }
   } else {
     if (row >= g.M) return;
@@ -162,7 +163,7 @@ __device__ __forceinline__ void x3_store_block(const Args& g, const f32x4 acc, i
           _Float16 hh, ll;
           hgl_split_hi_lo(v, hh, ll, amax);
           g.Ch[off] = hh;
-          g.Cl[off] = ll;
+          if (!g.one_term) g.Cl[off] = ll;
         }
       }
     }
@@ -174,7 +175,8 @@ __device__ __forceinline__ void x3_store_block(const Args& g, const f32x4 acc, i
 // global -> registers -> LDS with 16-byte accesses.  An LDS row holds the hi and the lo halves of one operand row for
 // BK = 64 (128 B + 128 B) plus one 16-byte pad (row stride 272 B = 17 x 16 B: at most one two-way conflict per
 // ds_read_b128 lane group).
-template <int ACT, int BK, int OCC>
+// NT = 1 (f16 mode): only the hi halves are loaded and staged, one MFMA per accumulator and k-step.
+template <int ACT, int BK, int OCC, int NT>
 __global__ __launch_bounds__(NTHREADS, OCC) void gemm_f16x3_kernel(Args g) {
   extern __shared__ __attribute__((aligned(16))) _Float16 smem[];  // [A: BM rows | W: BN rows] x ROW_H
   constexpr int ROW_H = 2 * BK + 8;   // halfs per LDS row: hi | lo | pad
@@ -221,8 +223,9 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gemm_f16x3_kernel(Args g) {
     const int k = kt * BK;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      pah[i] = *(const u32x4*)(pa_h[i] + k); pal[i] = *(const u32x4*)(pa_l[i] + k);
-      pwh[i] = *(const u32x4*)(pw_h[i] + k); pwl[i] = *(const u32x4*)(pw_l[i] + k);
+      pah[i] = *(const u32x4*)(pa_h[i] + k);
+      pwh[i] = *(const u32x4*)(pw_h[i] + k);
+      if constexpr (NT != 1) { pal[i] = *(const u32x4*)(pa_l[i] + k); pwl[i] = *(const u32x4*)(pw_l[i] + k); }
     }
   };
   auto store_tile = [&]() {
@@ -230,8 +233,9 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gemm_f16x3_kernel(Args g) {
     for (int i = 0; i < NLD; ++i) {
       _Float16* ar = smem + (ld_row + RSTEP * i) * ROW_H + ld_c * 8;
       _Float16* wr = smem + (BM + ld_row + RSTEP * i) * ROW_H + ld_c * 8;
-      *(u32x4*)ar = pah[i]; *(u32x4*)(ar + BK) = pal[i];
-      *(u32x4*)wr = pwh[i]; *(u32x4*)(wr + BK) = pwl[i];
+      *(u32x4*)ar = pah[i];
+      *(u32x4*)wr = pwh[i];
+      if constexpr (NT != 1) { *(u32x4*)(ar + BK) = pal[i]; *(u32x4*)(wr + BK) = pwl[i]; }
     }
   };
 
@@ -254,12 +258,16 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gemm_f16x3_kernel(Args g) {
       f16x8 ah[4], al[4], bh[4], bl[4];
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        ah[b] = *(const f16x8*)(As + b * 16 * ROW_H + 32 * s); al[b] = *(const f16x8*)(As + b * 16 * ROW_H + BK + 32 * s);
-        bh[b] = *(const f16x8*)(Ws + b * 16 * ROW_H + 32 * s); bl[b] = *(const f16x8*)(Ws + b * 16 * ROW_H + BK + 32 * s);
+        ah[b] = *(const f16x8*)(As + b * 16 * ROW_H + 32 * s);
+        bh[b] = *(const f16x8*)(Ws + b * 16 * ROW_H + 32 * s);
+        if constexpr (NT != 1) {
+          al[b] = *(const f16x8*)(As + b * 16 * ROW_H + BK + 32 * s);
+          bl[b] = *(const f16x8*)(Ws + b * 16 * ROW_H + BK + 32 * s);
+        }
       }
       // small cross terms first, then the hi*hi term; W fragment first = transposed accumulator
 #pragma unroll
-      for (int term = 0; term < 3; ++term)
+      for (int term = NT == 1 ? 2 : 0; term < 3; ++term)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -360,9 +368,12 @@ __device__ __forceinline__ void x3p_wait() {
 // fp16-valued weight (NT = 2) the W_lo plane is all zero and is NOT STAGED: the two W units of a K tile are one piece each
 // (U1 = 2, U2 = 1, U3 = 1, U4 = 2 pieces).  "All but the five youngest units" is then 8, 8, 7, 7 pieces in the four phases
 // (7 everywhere is stricter, hence safe); the drained tail 8, 6, 4, 2, 0 becomes 6, 4, 3, 2, 0; the 32 stores of a full
-// write-out are added as before; the four units a K tile issues are 6 pieces.
+// write-out are added as before; the four units a K tile issues are 6 pieces.  With NT = 1 (f16 mode) no lo plane is staged:
+// every unit is ONE piece and every count halves (the 32 stores of a full write-out stay: 42 -> 32 + 5).
 constexpr int x3p_cnt(int nt, int c) {
-  return nt == 3 ? c : (c == 42 ? 39 : c == 10 ? 7 : c == 8 ? 6 : c == 6 ? 4 : c == 4 ? 3 : c);
+  return nt == 3 ? c
+         : nt == 1 ? (c == 42 ? 37 : c / 2)
+                   : (c == 42 ? 39 : c == 10 ? 7 : c == 8 ? 6 : c == 6 ? 4 : c == 4 ? 3 : c);
 }
 
 template <int ACT, int WLOADS, int NT>
@@ -449,7 +460,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x3p_kernel(Args g) {
     if (u == 0) {
       const unsigned off = wrap ? nx[0] : o0.oa0;
       glds16(bAh + ko, off, sb + rgA0 * 1024);
-      glds16(bAl + ko, off, sb + PLANE + rgA0 * 1024);
+      if (NT != 1) glds16(bAl + ko, off, sb + PLANE + rgA0 * 1024);     // NT = 1: hi planes only
     } else if (u == 1) {
       const unsigned off = wrap ? nx[2] : o0.ow0;
       glds16(bWh + ko, off, sb + 2 * PLANE + cgW0 * 1024);
@@ -461,7 +472,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x3p_kernel(Args g) {
     } else {
       const unsigned off = wrap ? nx[1] : o0.oa1;
       glds16(bAh + ko, off, sb + rgA1 * 1024);
-      glds16(bAl + ko, off, sb + PLANE + rgA1 * 1024);
+      if (NT != 1) glds16(bAl + ko, off, sb + PLANE + rgA1 * 1024);
     }
   };
   auto issue_prologue = [&](const TileOff& o) {   // seven units ahead
@@ -483,7 +494,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x3p_kernel(Args g) {
     for (int ib = 0; ib < 4; ++ib) {
       const unsigned char* p = Ab + stage * STAGE + (4 * ih + ib) * 1024;
       ah[ib] = *(const f16x8*)p;
-      al[ib] = *(const f16x8*)(p + PLANE);
+      if constexpr (NT != 1) al[ib] = *(const f16x8*)(p + PLANE);
     }
   };
   auto read_B = [&](int j, int stage) {
@@ -491,12 +502,12 @@ __global__ __launch_bounds__(512, 1) void gemm_x3p_kernel(Args g) {
     for (int jb = 0; jb < 2; ++jb) {
       const unsigned char* p = Wb + stage * STAGE + (2 * j + jb) * 1024;
       bh[j][jb] = *(const f16x8*)p;
-      bl[j][jb] = *(const f16x8*)(p + PLANE);
+      if constexpr (NT != 1) bl[j][jb] = *(const f16x8*)(p + PLANE);
     }
   };
   // the 24 MFMAs of quadrant (ih, j): per accumulator lo*hi, hi*lo, hi*hi over the whole K tile; W fragment first =
   // transposed accumulator (lane: output row r, four consecutive columns).  NT == 2: the weight is fp16-valued (W_lo == 0),
-  // the hi*lo products would add exact zeros and are not issued (16 MFMAs; same accumulators bit for bit)
+  // the hi*lo products would add exact zeros and are not issued (16 MFMAs; same accumulators bit for bit).  NT == 1: hi*hi only (8)
   auto quad = [&](int ih, int j) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -505,7 +516,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x3p_kernel(Args g) {
       for (int ib = 0; ib < 4; ++ib)
 #pragma unroll
         for (int jb = 0; jb < 2; ++jb) {
-          if (NT == 2 && term == 1) continue;
+          if ((NT == 2 && term == 1) || (NT == 1 && term != 2)) continue;
           const f16x8 a = term == 0 ? al[ib] : ah[ib];
           const f16x8 b = term == 1 ? bl[j][jb] : bh[j][jb];
           acc[4 * ih + ib][2 * j + jb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, a, acc[4 * ih + ib][2 * j + jb], 0, 0, 0);
@@ -745,7 +756,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x3p_kernel(Args g) {
                   lo4[e] = ll;
                 }
                 *(f16x4*)(g.Ch + off) = hi4;
-                *(f16x4*)(g.Cl + off) = lo4;
+                if constexpr (NT != 1) *(f16x4*)(g.Cl + off) = lo4;
               }
             }
           }
@@ -773,7 +784,8 @@ struct SkinnyArgs {
   float out_scale;
 };
 
-template <int ACT>
+// NT = 1 (f16 mode): A rounded to fp16 in registers, W_hi only, one MFMA per k-step
+template <int ACT, int NT>
 __global__ __launch_bounds__(256) void gemm_x3_skinny_kernel(SkinnyArgs g) {
   __shared__ float red[3][16][64];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -797,8 +809,10 @@ __global__ __launch_bounds__(256) void gemm_x3_skinny_kernel(SkinnyArgs g) {
       ah[e] = h0; ah[4 + e] = h1;
       al[e] = l0; al[4 + e] = l1;
     }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl, acc, 0, 0, 0);
+    if constexpr (NT != 1) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wl, acc, 0, 0, 0);
+    }
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wh, acc, 0, 0, 0);
   };
   int ks = wave;
@@ -809,14 +823,18 @@ __global__ __launch_bounds__(256) void gemm_x3_skinny_kernel(SkinnyArgs g) {
     for (int u = 0; u < 4; ++u) {
       const int k = 16 * (ks + 4 * u);
       a0[u] = *(const f32x4*)(ap + k); a1[u] = *(const f32x4*)(ap + k + 4);
-      wh[u] = *(const f16x8*)(whp + k); wl[u] = *(const f16x8*)(wlp + k);
+      wh[u] = *(const f16x8*)(whp + k);
+      if constexpr (NT != 1) wl[u] = *(const f16x8*)(wlp + k);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) step(a0[u], a1[u], wh[u], wl[u]);
   }
   for (; ks < nks; ks += 4) {
     const int k = 16 * ks;
-    step(*(const f32x4*)(ap + k), *(const f32x4*)(ap + k + 4), *(const f16x8*)(whp + k), *(const f16x8*)(wlp + k));
+    const f16x8 w1 = *(const f16x8*)(whp + k);
+    f16x8 w2 = w1;
+    if constexpr (NT != 1) w2 = *(const f16x8*)(wlp + k);
+    step(*(const f32x4*)(ap + k), *(const f32x4*)(ap + k + 4), w1, w2);
   }
   hgl_split_commit(amax);
   if (wave > 0) {
@@ -897,7 +915,7 @@ __global__ __launch_bounds__(256) void split_f16_kernel(const float* __restrict_
       b[e] = l0;
     }
     ((f16x4*)hi)[i] = a;
-    ((f16x4*)lo)[i] = b;
+    if (lo) ((f16x4*)lo)[i] = b;   // nullptr: f16 mode, hi plane only
   }
   hgl_split_commit(amax);
 }
@@ -940,7 +958,7 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __res
     }
   const float rstd = rsqrtf(wsum(q) * (1.0f / D) + eps);
   f16x4* hr = (f16x4*)(hi + (long long)drow * D);
-  f16x4* lr = (f16x4*)(lo + (long long)drow * D);
+  f16x4* lr = lo ? (f16x4*)(lo + (long long)drow * D) : nullptr;   // nullptr: f16 mode, hi plane only
 #pragma unroll
   for (int i = 0; i < VEC; ++i) {
     const f32x4 wv = ((const f32x4*)w)[lane + 64 * i];
@@ -955,7 +973,7 @@ __global__ __launch_bounds__(256) void layernorm_split_kernel(const float* __res
       c[e] = l0;
     }
     hr[lane + 64 * i] = a;
-    lr[lane + 64 * i] = c;
+    if (lr) lr[lane + 64 * i] = c;
   }
 }
 
@@ -980,7 +998,7 @@ __global__ __launch_bounds__(256) void win_partition_split_kernel(const float* _
     b[e] = l0;
   }
   ((f16x4*)hi)[i] = a;
-  ((f16x4*)lo)[i] = b;
+  if (lo) ((f16x4*)lo)[i] = b;   // nullptr: f16 mode, hi plane only
 }
 
 }  // namespace
@@ -988,11 +1006,20 @@ __global__ __launch_bounds__(256) void win_partition_split_kernel(const float* _
 int hgl_launch_win_partition_split(const float* H, int g, int ws, int nw, int D, void* hi, void* lo, hipStream_t st) {
   const long long total4 = (long long)nw * nw * ws * ws * (D / 4);
   hipLaunchKernelGGL(win_partition_split_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, H, g, ws,
-                     nw, D / 4, (_Float16*)hi, (_Float16*)lo, total4);
+                     nw, D / 4, (_Float16*)hi, hgl_split_terms() == 1 ? nullptr : (_Float16*)lo, total4);
   return hgl_check_launch("win_partition_split");
 }
 
 int hgl_precision() { return g_precision; }
+
+bool hgl_split_layout() { return g_precision == HGL_PREC_F16X3 || g_precision == HGL_PREC_F16; }
+
+namespace {
+thread_local int g_terms_pin = 0;   // HglSplitTermsScope: 0 = follow the mode
+}
+int hgl_split_terms() { return g_terms_pin ? g_terms_pin : g_precision == HGL_PREC_F16 ? 1 : 3; }
+HglSplitTermsScope::HglSplitTermsScope(int terms) : prev(g_terms_pin) { g_terms_pin = terms; }
+HglSplitTermsScope::~HglSplitTermsScope() { g_terms_pin = prev; }
 
 bool hgl_has_split_weight(const float* W) { return find_split((const void*)W, nullptr); }
 
@@ -1004,12 +1031,20 @@ bool hgl_get_split_weight(const float* W, const void** hi, const void** lo, int*
   return true;
 }
 
-int hgl_launch_split_f16(const float* x, float scale, void* hi, void* lo, long long n, hipStream_t st) {
+namespace {
+int launch_split_f16(const float* x, float scale, void* hi, void* lo, long long n, bool with_lo, hipStream_t st) {
   HGL_REQUIRE(x && hi && lo && n > 0 && (n & 3) == 0, "split_f16: bad arguments (n %% 4 != 0?)");
   long long blocks = (n / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(split_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, scale, (_Float16*)hi, (_Float16*)lo, n / 4);
+  hipLaunchKernelGGL(split_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, scale, (_Float16*)hi,
+                     with_lo ? (_Float16*)lo : nullptr, n / 4);
   return hgl_check_launch("split_f16");
+}
+}  // namespace
+
+// activations: the lo plane is written unless the mode multiplies hi halves only
+int hgl_launch_split_f16(const float* x, float scale, void* hi, void* lo, long long n, hipStream_t st) {
+  return launch_split_f16(x, scale, hi, lo, n, hgl_split_terms() != 1, st);
 }
 
 int hgl_launch_layernorm_split(const float* x, const float* w, const float* b, void* hi, void* lo, int rows, int D,
@@ -1020,7 +1055,7 @@ int hgl_launch_layernorm_split(const float* x, const float* w, const float* b, v
 int hgl_launch_layernorm_split_maps(const float* x, const float* w, const float* b, void* hi, void* lo, int rows, int D,
                                     float eps, const int* smap, const int* dmap, hipStream_t st) {
   const unsigned grid = (unsigned)((rows + 3) / 4);
-  _Float16 *h = (_Float16*)hi, *l = (_Float16*)lo;
+  _Float16 *h = (_Float16*)hi, *l = hgl_split_terms() == 1 ? nullptr : (_Float16*)lo;
   switch (D) {
     case 256: hipLaunchKernelGGL(layernorm_split_kernel<1>, dim3(grid), dim3(256), 0, st, x, w, b, h, l, rows, eps, smap, dmap); break;
     case 512: hipLaunchKernelGGL(layernorm_split_kernel<2>, dim3(grid), dim3(256), 0, st, x, w, b, h, l, rows, eps, smap, dmap); break;
@@ -1060,8 +1095,13 @@ int launch_x3_v1(Args& g, hipStream_t st) {
   const long long nwg = (long long)g.tiles_m * g.tiles_n;
   HGL_REQUIRE(nwg < (1ll << 31), "gemm_f16x3: grid too large");
   const size_t lds = (size_t)(BM + BN) * (2 * BK + 8) * sizeof(_Float16);
-  HGL_RESERVE_LDS((gemm_f16x3_kernel<ACT, BK, 2>), lds, "gemm_f16x3");
-  hipLaunchKernelGGL((gemm_f16x3_kernel<ACT, BK, 2>), dim3((unsigned)nwg), dim3(NTHREADS), lds, st, g);
+  if (g.one_term) {
+    HGL_RESERVE_LDS((gemm_f16x3_kernel<ACT, BK, 2, 1>), lds, "gemm_f16x3");
+    hipLaunchKernelGGL((gemm_f16x3_kernel<ACT, BK, 2, 1>), dim3((unsigned)nwg), dim3(NTHREADS), lds, st, g);
+    return HGL_OK;
+  }
+  HGL_RESERVE_LDS((gemm_f16x3_kernel<ACT, BK, 2, 3>), lds, "gemm_f16x3");
+  hipLaunchKernelGGL((gemm_f16x3_kernel<ACT, BK, 2, 3>), dim3((unsigned)nwg), dim3(NTHREADS), lds, st, g);
   return HGL_OK;
 }
 
@@ -1080,6 +1120,7 @@ int launch_x3_p3(Args& g, hipStream_t st) {
 
 template <int ACT, int WLOADS>
 int launch_x3_p2(Args& g, hipStream_t st) {
+  if (g.one_term) return launch_x3_p3<ACT, WLOADS, 1>(g, st);
   return g.lo_zero ? launch_x3_p3<ACT, WLOADS, 2>(g, st) : launch_x3_p3<ACT, WLOADS, 3>(g, st);
 }
 
@@ -1151,6 +1192,8 @@ int hgl_launch_gemm_f16x3_maps(const void* Ah, const void* Al, int lda, const in
   g.part = nullptr; g.ksplit = 1;
   g.out_scale = ldexpf(1.0f, -sw.scale_log2);
   g.lo_zero = x3_two_terms(sw) ? 1 : 0;
+  g.one_term = hgl_split_terms() == 1 ? 1 : 0;
+  if (g.one_term) g.Cl = nullptr;   // a split output is its hi plane only
   g.gm = x3_gm();
   g.vec4 = x3_vec4_ok(bias, R, ldr, C, Ch, Cl, ldc, N) ? 1 : 0;
   // kernel selection (hgl_gemm_f16x3_select); both tilings accumulate in the same order
@@ -1180,7 +1223,7 @@ int hgl_launch_gemm_f16x3_maps(const void* Ah, const void* Al, int lda, const in
 
 // fp32-A entry for small M (called from hgl_launch_gemm): true when the GEMM was taken
 bool hgl_gemm_skinny_applicable(const float* W32, int M, int N, int K, int lda, int ldw, int batch, int max_m) {
-  if (g_precision != HGL_PREC_F16X3 || batch != 1 || M > max_m || (K & 15) || (lda & 3) || ldw != K) return false;
+  if (!hgl_split_layout() || batch != 1 || M > max_m || (K & 15) || (lda & 3) || ldw != K) return false;
   SplitW sw;
   return find_split((const void*)W32, &sw) && sw.N == N && sw.K == K;
 }
@@ -1195,12 +1238,19 @@ int hgl_launch_gemm_x3_skinny(const float* A, int lda, const float* W32, const f
   g.out_scale = ldexpf(1.0f, -sw.scale_log2);
   const dim3 grid((unsigned)((N + 31) / 32), (unsigned)((M + 31) / 32));
   HglProfScope prof(HGL_PROF_OTHER, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), st);
+#define HGL_SKINNY(ACT_)                                                                                  \
+  do {                                                                                                    \
+    if (one) hipLaunchKernelGGL((gemm_x3_skinny_kernel<ACT_, 1>), grid, dim3(256), 0, st, g);             \
+    else hipLaunchKernelGGL((gemm_x3_skinny_kernel<ACT_, 3>), grid, dim3(256), 0, st, g);                 \
+  } while (0)
+  const bool one = hgl_split_terms() == 1;
   switch (act) {
-    case HGL_ACT_QUICKGELU: hipLaunchKernelGGL(gemm_x3_skinny_kernel<HGL_ACT_QUICKGELU>, grid, dim3(256), 0, st, g); break;
-    case HGL_ACT_GELU: hipLaunchKernelGGL(gemm_x3_skinny_kernel<HGL_ACT_GELU>, grid, dim3(256), 0, st, g); break;
-    case HGL_ACT_RELU: hipLaunchKernelGGL(gemm_x3_skinny_kernel<HGL_ACT_RELU>, grid, dim3(256), 0, st, g); break;
-    default: hipLaunchKernelGGL(gemm_x3_skinny_kernel<HGL_ACT_NONE>, grid, dim3(256), 0, st, g); break;
+    case HGL_ACT_QUICKGELU: HGL_SKINNY(HGL_ACT_QUICKGELU); break;
+    case HGL_ACT_GELU: HGL_SKINNY(HGL_ACT_GELU); break;
+    case HGL_ACT_RELU: HGL_SKINNY(HGL_ACT_RELU); break;
+    default: HGL_SKINNY(HGL_ACT_NONE); break;
   }
+#undef HGL_SKINNY
   return hgl_check_launch("gemm_x3_skinny");
 }
 
@@ -1235,6 +1285,7 @@ int hgl_launch_gemm_f16x3_splitk(const void* Ah, const void* Al, int lda, const 
   g.rmod = 0; g.rp_p = g.rp_t = 0; g.amap = amap; g.cmap = nullptr; g.part = part; g.ksplit = ksplit; g.vec4 = 1;
   g.out_scale = ldexpf(1.0f, -sw.scale_log2);
   g.lo_zero = x3_two_terms(sw) ? 1 : 0;
+  g.one_term = hgl_split_terms() == 1 ? 1 : 0;
   g.gm = 8;
   {
     const long long few_tiles = (long long)((M + 127) / 128) * ((N + 127) / 128);
@@ -1310,7 +1361,7 @@ int hgl_launch_gemm_f16x3_balanced(const void* Ah, const void* Al, int lda, cons
 extern "C" {
 
 int hgl_set_precision(int mode) {
-  HGL_REQUIRE(mode == HGL_PREC_F32 || mode == HGL_PREC_F16X3, "set_precision: unknown mode %d", mode);
+  HGL_REQUIRE(mode == HGL_PREC_F32 || mode == HGL_PREC_F16X3 || mode == HGL_PREC_F16, "set_precision: unknown mode %d", mode);
   g_precision = mode;
   return HGL_OK;
 }
@@ -1327,7 +1378,8 @@ int hgl_register_split_weight(const float* w_fp32, int N, int K, int scale_log2,
   HGL_TRY(hgl_require_device());
   HGL_REQUIRE(w_fp32 && hi && lo && N > 0 && K > 0 && (K & 7) == 0, "register_split_weight: bad arguments (K %% 8)");
   HGL_REQUIRE(scale_log2 >= -24 && scale_log2 <= 24, "register_split_weight: scale_log2 out of range");
-  HGL_TRY(hgl_launch_split_f16(w_fp32, ldexpf(1.0f, scale_log2), hi, lo, (long long)N * K, (hipStream_t)stream));
+  // (both halves in every mode: a model built in f16 mode still runs its decoder in f16x3 arithmetic)
+  HGL_TRY(launch_split_f16(w_fp32, ldexpf(1.0f, scale_log2), hi, lo, (long long)N * K, true, (hipStream_t)stream));
   // fp16-valued weights (the OpenAI CLIP archives store fp16; clip/model.py:509 is commented out in the reference, so the
   // model holds those values as fp32): every lo half is zero and the GEMMs drop the A_hi * W_lo products.  One read-back
   // per weight at model construction.

@@ -302,6 +302,17 @@ int hgl_launch_dec_i2t(const float* q, int ldq, long long q_bstride, const float
 
 // split-fp16 GEMM path (gemm_f16x3.hip)
 int hgl_precision();
+// the fp16 hi | lo plane layout is in use (HGL_PREC_F16X3 and HGL_PREC_F16): split weights registered, split producers and
+// consumers on the encoder path
+bool hgl_split_layout();
+// products per split-operand product: 3 (f16x3: lo*hi + hi*lo + hi*hi) or 1 (f16: hi*hi; no lo plane is written or read).
+// HglSplitTermsScope pins 3 for the host code in its scope (the SAM decoder keeps its f16x3 arithmetic in f16 mode).
+int hgl_split_terms();
+struct HglSplitTermsScope {
+  explicit HglSplitTermsScope(int terms);
+  ~HglSplitTermsScope();
+  int prev;
+};
 bool hgl_has_split_weight(const float* W);
 bool hgl_get_split_weight(const float* W, const void** hi, const void** lo, int* scale_log2, int* N, int* K);
 int hgl_launch_split_f16(const float* x, float scale, void* hi, void* lo, long long n, hipStream_t st);
@@ -329,4 +340,4 @@ int hgl_launch_gemm_f16x3(const void* Ah, const void* Al, int lda, const float* 
                           int ldr, float* C, void* Ch, void* Cl, int ldc, int M, int N, int K, int act, hipStream_t st);
 int hgl_launch_win_partition_split(const float* H, int g, int ws, int nw, int D, void* hi, void* lo, hipStream_t st);
 // true when the split-fp16 path applies to a GEMM with this weight and reduction length
-static inline bool hgl_use_x3(const float* W, int K) { return hgl_precision() == HGL_PREC_F16X3 && (K % 64) == 0 && hgl_has_split_weight(W); }
+static inline bool hgl_use_x3(const float* W, int K) { return hgl_split_layout() && (K % 64) == 0 && hgl_has_split_weight(W); }

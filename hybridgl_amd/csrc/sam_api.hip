@@ -371,7 +371,7 @@ struct SplitPair { uint16_t *hi, *lo; };
 inline SplitPair split_view(float* buf, size_t elems) { return SplitPair{(uint16_t*)buf, (uint16_t*)buf + elems}; }
 
 bool dec_x3_ready(const HglSamDecoderW* w) {
-  if (hgl_precision() != HGL_PREC_F16X3 || w->C != 256) return false;
+  if (!hgl_split_layout() || w->C != 256) return false;   // (f16 mode: the entry points pin three terms)
   const float* need[] = {w->layer[0].i2t.out.w, w->layer[1].i2t.out.w, w->layer[1].i2t.q.w, w->layer[1].t2i.k.w,
                          w->layer[1].t2i.v.w, w->final_t2i.k.w, w->final_t2i.v.w, w->up0_w, w->up3_w};
   for (const float* x : need) if (!hgl_has_split_weight(x)) return false;
@@ -603,6 +603,8 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
                        const int32_t* labels, int n_sparse, const float* dense, int first_mask, int P, float* low_res,
                        float* iou_pred, void* workspace, size_t workspace_bytes, void* stream, bool gated = false,
                        float iou_gate = 0.f) {
+  // the decoder keeps the f16x3 arithmetic in f16 mode: its split producers write both planes, its GEMMs issue three terms
+  const HglSplitTermsScope three_terms(3);
   HGL_TRY(hgl_require_device());
   HGL_REQUIRE(valid_dec(w) && w->dense_pe, "sam_decode: invalid weight struct (dense_pe missing?)");
   HGL_REQUIRE(emb && (points01 || (coords01 && labels)) && low_res && iou_pred && P > 0, "sam_decode: null input");

@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void fill_rows_split_kernel(_Float16* __restri
       l[e] = l0;
     }
     *(fr_h4*)(hi + ro + 4 * c) = a;
-    *(fr_h4*)(lo + ro + 4 * c) = l;
+    if (lo) *(fr_h4*)(lo + ro + 4 * c) = l;   // nullptr: f16 mode, hi plane only
   }
 }
 
@@ -1409,7 +1409,7 @@ int hgl_launch_relpos_direct(const float* qkv, int ldq, int B, int heads, int S,
   HGL_REQUIRE(hd == 80 || hd == 64, "relpos_direct: head dim %d unsupported", hd);
   HGL_REQUIRE((size & 1) == 0 && size > 0 && size <= 64, "relpos_direct: window size %d unsupported (even, <= 64)", size);
   // f16x3 mode: the matrix-core version (table of 2*size-1 rows padded to 32 / 128)
-  if (hgl_precision() == HGL_PREC_F16X3 && (size == 14 || size == 64)) {
+  if (hgl_split_layout() && (size == 14 || size == 64)) {
     const int NT = size == 14 ? 1 : 4;
     const dim3 gridm((unsigned)((S + 127) / 128), (unsigned)(B * heads), 1);   // both axes in one workgroup: q is read once
     const size_t ldsm = (size_t)2 * NT * 32 * (hd + 8) * sizeof(_Float16) + (size_t)4 * 32 * (NT * 32 + 1) * sizeof(float);
@@ -1471,7 +1471,8 @@ int hgl_launch_fill_rows(float* dst, int ld, const int* rows, const int* nrows, 
 int hgl_launch_fill_rows_split(void* hi, void* lo, int ld, const int* rows, const int* nrows, int max_rows, const float* v,
                                int N, hipStream_t st) {
   HGL_REQUIRE((N & 3) == 0 && (ld & 3) == 0 && max_rows > 0 && hi && lo, "fill_rows_split: bad arguments");
-  hipLaunchKernelGGL(fill_rows_split_kernel, dim3(4, (unsigned)max_rows), dim3(256), 0, st, (_Float16*)hi, (_Float16*)lo, ld, rows,
+  hipLaunchKernelGGL(fill_rows_split_kernel, dim3(4, (unsigned)max_rows), dim3(256), 0, st, (_Float16*)hi,
+                     hgl_split_terms() == 1 ? nullptr : (_Float16*)lo, ld, rows,
                      nrows, v, N / 4);
   return hgl_check_launch("fill_rows_split");
 }

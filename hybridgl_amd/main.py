@@ -73,6 +73,9 @@ def default_argument_parser():
     p.add_argument("--host_transforms", action="store_true",
                    help="ToTensor/Normalize and the GEM transform on the loader threads' CPU (numpy / PIL) as the reference's "
                         "DataLoader workers do, instead of bit-identical device kernels (hybridgl_amd/transforms.py)")
+    p.add_argument("--precision", default=None, choices=["f16x3", "f32", "f16"],
+                   help="arithmetic of the encoders (default: HYBRIDGL_PRECISION, else f16x3); f16 = fp16 GEMM operands with fp32 "
+                        "accumulation, opt-in and not fp32-class")
     p.add_argument("--stats_json", default="", help="rank 0 writes {stats, metrics} of the run here (throughput, loader wait)")
     p.add_argument("--k_clamp", default="auto", choices=["auto", "persistent", "per_ref"],
                    help="the k1 / k2 clamp of Hybridgl_main.py:178-181: persistent = the reference's quirk (once an image yields "
@@ -336,11 +339,14 @@ def build_models(args, dev):
     """(CLIPViTFM, SamAutomaticMaskGenerator | None, GEM model | None) as Hybridgl_main.py:36-38,47-48,66-74 builds them"""
     from .backbone import CLIPViTFM
     resolve_defaults(args)
-    model = CLIPViTFM(model_name=args.clip_model, device=dev).eval()
+    if getattr(args, "precision", None) is None:
+        from . import ops
+        args.precision = ops.default_precision()
+    model = CLIPViTFM(model_name=args.clip_model, device=dev, precision=args.precision).eval()
     gen = None
     if args.sam or args.real:
         from .sam import SamAutomaticMaskGenerator, sam_model_registry
-        sam = sam_model_registry[args.sam_model](device=dev)
+        sam = sam_model_registry[args.sam_model](device=dev, precision=args.precision)
         # Hybridgl_main.py:67-73
         gen = SamAutomaticMaskGenerator(sam, points_per_side=args.points_per_side, points_per_batch=args.points_per_batch,
                                         pred_iou_thresh=args.pred_iou_thresh, stability_score_thresh=args.stability_score_thresh,
@@ -443,6 +449,7 @@ def main(args):
         import json
         stats["refs_per_s"] = stats["refs"] / stats["seconds"] if stats["seconds"] > 0 else 0.0
         stats["world"] = world
+        stats["precision"] = args.precision
         stats["host_cores_per_rank"] = len(cores) if cores else len(os.sched_getaffinity(0))
         json.dump({"stats": stats, "metrics": m}, open(args.stats_json, "w"))
     pc = args.dataset == "phrasecut"
@@ -450,7 +457,8 @@ def main(args):
             + (f"\nDataset: PhraseCut / {args.split}" if pc else f"\nDataset: {args.dataset} / {args.split} / {splitBy}") +
             f"\nOverall IoU / mean IoU"
             f"\npure hybridgl: {m['oIoU']:.2f} / {m['mIoU']:.2f}"
-            f"\nhybridgl w/ spatial guidance: {m['oIoU_final']:.2f} / {m['mIoU_final']:.2f}")
+            f"\nhybridgl w/ spatial guidance: {m['oIoU_final']:.2f} / {m['mIoU_final']:.2f}"
+            f"\nprecision: {args.precision}")
     os.makedirs(args.result_dir, exist_ok=True)                         # Hybridgl_main.py:233-248
     # Hybridgl_main.py:233-248 / Hybridgl_main_PhraseCut.py:224-238
     with open(os.path.join(args.result_dir, "result_log_PhraseCut.txt" if pc else f"result_log_{args.dataset}_{args.split}.txt"), "a") as f:

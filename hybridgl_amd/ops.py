@@ -98,21 +98,36 @@ def split_weight_keys_since(before):
     return [k for k in _split_cache if k not in before]
 
 
+PRECISIONS = {"f32": 0, "f16x3": 1, "f16": 2}
+
+
 def default_precision():
-    """'f16x3' unless HYBRIDGL_PRECISION=f32: both meet the parity bar (tests run both)."""
+    """'f16x3' unless HYBRIDGL_PRECISION says otherwise: 'f32' and 'f16x3' meet the parity bar (tests run both); 'f16' is
+    the opt-in half-precision mode (fp16 operands, fp32 accumulation)."""
     import os
-    return os.environ.get("HYBRIDGL_PRECISION", "f16x3")
+    mode = os.environ.get("HYBRIDGL_PRECISION", "f16x3")
+    if mode not in PRECISIONS:
+        raise ValueError(f"HYBRIDGL_PRECISION={mode!r}: expected one of {sorted(PRECISIONS)}")
+    return mode
+
+
+def split_mode(mode):
+    """True for the modes that keep fp16 hi | lo planes of weights and activations ('f16x3' and 'f16')"""
+    return mode in ("f16x3", "f16")
 
 
 _precision_now = None
 
 
 def set_precision(mode):
-    """'f32' (exact fp32 MFMA) or 'f16x3' (split-fp16 MFMA, fp32-class accuracy).  The library keeps ONE current mode;
+    """'f32' (exact fp32 MFMA), 'f16x3' (split-fp16 MFMA, fp32-class accuracy) or 'f16' (fp16 operands, one MFMA per
+    product, fp32 accumulation: opt-in, not fp32-class).  The library keeps ONE current mode;
     every model carries its own and re-asserts it on entry (use_precision), so models of different precision can live
     in one process."""
     global _precision_now
-    check(_lib.load().hgl_set_precision({"f32": 0, "f16x3": 1}[mode]), "hgl_set_precision")
+    if mode not in PRECISIONS:
+        raise ValueError(f"precision {mode!r}: expected one of {sorted(PRECISIONS)}")
+    check(_lib.load().hgl_set_precision(PRECISIONS[mode]), "hgl_set_precision")
     _precision_now = mode
 
 
@@ -140,15 +155,15 @@ def split_overflow_peek(buf):
 
 
 class SplitOverflow(_lib.HybridGLError):
-    """an activation left the fp16 range in f16x3 mode: the results since the last clean check contain inf / NaN"""
+    """an activation left the fp16 range in f16x3 or f16 mode: the results since the last clean check contain inf / NaN"""
 
 
 def check_split_overflow():
-    """raise if the f16x3 path met a value it cannot represent (the results since the last check are then not
-    fp32-class); the cure is HYBRIDGL_PRECISION=f32"""
+    """raise if the f16x3 / f16 path met a value it cannot represent (the results since the last check then contain inf /
+    NaN); the cure is HYBRIDGL_PRECISION=f32"""
     n = split_overflow_count(reset=True)
     if n:
-        raise SplitOverflow(f"activations exceeded the fp16 range (|x| > 65504) in f16x3 mode ({n} GPU threads saw one): "
+        raise SplitOverflow(f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode ({n} GPU threads saw one): "
                             "the results contain inf / NaN; rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
 
 

@@ -530,7 +530,7 @@ class HybridGLPipeline:
                             # recommends included -- would trip over the same count at its first group
                             ops.split_overflow_count(reset=True)
                             raise ops.SplitOverflow(
-                                f"activations exceeded the fp16 range (|x| > 65504) in f16x3 mode by group {self.groups_run} of the "
+                                f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode by group {self.groups_run} of the "
                                 f"loop ({stc.overflow} GPU threads saw one; refs up to dataset position {units[-1][-1].index}): the "
                                 "results from the previous group on contain inf / NaN; rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
                         got = [p[:2] for p in gen.group_finish(stc)]
@@ -539,7 +539,7 @@ class HybridGLPipeline:
                         if stc.overflow:
                             ops.split_overflow_count(reset=True)
                             raise ops.SplitOverflow(
-                                f"activations exceeded the fp16 range (|x| > 65504) in f16x3 mode by group {self.groups_run} of the "
+                                f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode by group {self.groups_run} of the "
                                 f"loop ({stc.overflow} GPU threads saw one): rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
                         got = [tuple(t[:proposal_cap] if proposal_cap is not None else t for t in p[:2])
                                for p in gen.crops_finish(gen.crops_post(stc))]
@@ -727,7 +727,7 @@ class HybridGLPipeline:
         from . import dist as D
         rows = self.partial_rows()
         overflow = 0
-        if getattr(self.model.model, "precision", "f32") == "f16x3":
+        if ops.split_mode(getattr(self.model.model, "precision", "f32")):
             overflow = ops.split_overflow_count(reset=True)
         # exchange first, raise afterwards and on EVERY rank: a rank that raised before the all-gather would leave the others
         # waiting in the collective
@@ -735,7 +735,7 @@ class HybridGLPipeline:
         overflow = int(D.max_over_ranks(float(overflow), dist, self.model.device))
         if overflow:     # an activation beyond the fp16 range voids the run: raise, do not report
             from ._lib import HybridGLError
-            raise HybridGLError(f"activations exceeded the fp16 range (|x| > 65504) in f16x3 mode ({overflow} GPU threads saw one on "
+            raise HybridGLError(f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode ({overflow} GPU threads saw one on "
                                 "some rank): the results contain inf / NaN; rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
         return m
 

@@ -73,9 +73,9 @@ class Sam:
                          ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias"), ("lin1_w", "mlp.lin1.weight"),
                          ("lin1_b", "mlp.lin1.bias"), ("lin2_w", "mlp.lin2.weight"), ("lin2_b", "mlp.lin2.bias")]:
                 setattr(b, f, t(sd[f"{p}.{k}"]))
-                if precision == "f16x3" and f in ("qkv_w", "proj_w", "lin1_w", "lin2_w"):
+                if ops.split_mode(precision) and f in ("qkv_w", "proj_w", "lin1_w", "lin2_w"):
                     ops.register_split_weight(self._t[-1])
-                if precision == "f16x3" and f in ("rel_pos_h", "rel_pos_w") and b.window == 14 and self._t[-1].shape == (27, 80):
+                if ops.split_mode(precision) and f in ("rel_pos_h", "rel_pos_w") and b.window == 14 and self._t[-1].shape == (27, 80):
                     # the windowed attention multiplies with these tables on the matrix cores: split once here (unscaled)
                     # instead of per wave and item in the kernel
                     ops.register_split_weight(self._t[-1], scale_log2=0)
@@ -89,7 +89,7 @@ class Sam:
         enc.neck1_w, enc.neck1_b = t(sd[f"{e}.neck.1.weight"]), t(sd[f"{e}.neck.1.bias"])
         enc.neck2_w = t(np.asarray(sd[f"{e}.neck.2.weight"]).reshape(Cc, Cc * 9))
         enc.neck3_w, enc.neck3_b = t(sd[f"{e}.neck.3.weight"]), t(sd[f"{e}.neck.3.bias"])
-        if precision == "f16x3":     # patch embedding and neck convolutions as split-fp16 GEMMs (K % 64 == 0 permitting)
+        if ops.split_mode(precision):     # patch embedding and neck convolutions as split-fp16 GEMMs (K % 64 == 0 permitting)
             for x in self._t:
                 if x.data_ptr() in (enc.patch_w, enc.neck0_w, enc.neck2_w) and x.shape[1] % 64 == 0:
                     ops.register_split_weight(x)
@@ -118,7 +118,7 @@ class Sam:
         def lin(dst, key):
             dst.w, dst.b = t(sd[f"{key}.weight"]), t(sd[f"{key}.bias"])
             wshape = np.asarray(sd[f"{key}.weight"]).shape
-            if precision == "f16x3" and len(wshape) == 2 and wshape[1] % 16 == 0:
+            if ops.split_mode(precision) and len(wshape) == 2 and wshape[1] % 16 == 0:
                 ops.register_split_weight(self._t[-2])     # small-M GEMMs of the decoder (token MLPs, hyper-nets, IoU head)
 
         def attn(dst, key):
@@ -140,13 +140,13 @@ class Sam:
         # ConvTranspose2d(k=2,s=2) weights [Cin,Cout,2,2] -> GEMM rows ordered (ky,kx,cout)
         w0 = np.asarray(sd[f"{m}.output_upscaling.0.weight"])
         dec.up0_w = t(np.transpose(w0, (2, 3, 1, 0)).reshape(-1, w0.shape[0]))
-        if precision == "f16x3":
+        if ops.split_mode(precision):
             ops.register_split_weight(self._t[-1])
         dec.up0_b = t(np.tile(np.asarray(sd[f"{m}.output_upscaling.0.bias"]), 4))
         lin(dec.up1, f"{m}.output_upscaling.1")
         w3 = np.asarray(sd[f"{m}.output_upscaling.3.weight"])
         dec.up3_w = t(np.transpose(w3, (2, 3, 1, 0)).reshape(-1, w3.shape[0]))
-        if precision == "f16x3":
+        if ops.split_mode(precision):
             ops.register_split_weight(self._t[-1])
         dec.up3_b = t(np.tile(np.asarray(sd[f"{m}.output_upscaling.3.bias"]), 4))
         for i in range(4):
@@ -163,7 +163,7 @@ class Sam:
         check(_lib.load().hgl_sam_dense_pe(C.byref(dec), cd.data_ptr(), self.dense_pe.data_ptr(), ops._stream()),
               "hgl_sam_dense_pe")
         torch.cuda.current_stream().synchronize()
-        if precision == "f16x3" and Cc == 256:
+        if ops.split_mode(precision) and Cc == 256:
             # merged image-side projections of the decoder (HglSamDecoderW.kvq1 / kvf): concatenated weights, and the
             # positional-encoding part of k and q as per-position tables: (keys + pe) W^T = keys W^T + pe W^T
             def cat_w(keys):

@@ -73,19 +73,25 @@ int hgl_prof_enable(int on);
 int hgl_prof_read(int cls, long long* launches, double* ms, double* flops, double* bytes);
 
 /* GEMM precision mode of the encoders.  HGL_PREC_F32: v_mfma_f32_32x32x2_f32 (exact fp32 products).
- * HGL_PREC_F16X3: every fp32 operand split into fp16 hi+lo, three v_mfma_f32_32x32x16_f16 per
+ * HGL_PREC_F16X3: every fp32 operand split into fp16 hi+lo, three v_mfma_f32_16x16x32_f16 per
  * step into one fp32 accumulator (a_hi*b_hi + a_hi*b_lo + a_lo*b_hi; ~2^-22 relative error per
  * term, i.e. fp32-class accuracy at 16/3 of the fp32 matrix rate).  It applies to GEMMs whose
- * weight has been registered with hgl_register_split_weight; all others stay on the fp32 path. */
+ * weight has been registered with hgl_register_split_weight; all others stay on the fp32 path.
+ * HGL_PREC_F16 (opt-in): the same GEMMs with fp16 operands -- the activation rounded to fp16, the
+ * registered weight's (power-of-two scaled) hi half -- ONE v_mfma_f32_16x16x32_f16 per step, fp32
+ * accumulation; no lo plane is written or read.  About 2^-11 relative error per operand: NOT the
+ * fp32 parity of the other two modes.  The attention kernels of the encoders and the SAM mask
+ * decoder keep their f16x3 arithmetic in this mode; the fp16 range guard below applies unchanged. */
 #define HGL_PREC_F32 0
 #define HGL_PREC_F16X3 1
+#define HGL_PREC_F16 2
 int hgl_set_precision(int mode);
 int hgl_get_precision(void);
 /* Pins the tiling of the f16x3 GEMM: -1 = cost model (default), 0 = register-staged 128x128 (two workgroups per
  * CU), 1 = LDS-DMA 256x256 ping-pong (persistent).  Both tilings give bit-identical results; the switch exists for
  * the parity tests and micro-benchmarks. */
 int hgl_gemm_f16x3_select(int kind);
-/* f16x3 mode splits every fp32 operand into fp16 hi + lo; an activation beyond the fp16 range (|x| > 65504) cannot be
+/* f16x3 (and f16) mode splits every fp32 operand into fp16 hi + lo; an activation beyond the fp16 range (|x| > 65504) cannot be
  * split (inf - inf).  The kernels that split GEMM outputs track the largest |x| they meet; *count = GPU threads that met
  * such a value since the last reset (a blocking device read: synchronise the producing streams first).  Non-zero means
  * the results of that run contain inf / NaN: rerun with hgl_set_precision(HGL_PREC_F32). */
