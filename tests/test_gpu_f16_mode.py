@@ -4,12 +4,11 @@ The GEMMs are pinned EXACTLY: with both operands rounded to fp16 on the host (th
 the result equals the float64 product of the rounded operands within fp32-accumulation error.  The models are compared
 with the f32 mode within bounds derived from the fp16 operand error (2^-11 relative per operand), and
 against the f16x3 mode to show that the mode really multiplies hi halves only."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
+from abi_ref import gemm_f16_reference
 from hybridgl_amd import ops, weights
 
 pytestmark = pytest.mark.gpu
@@ -17,31 +16,6 @@ pytestmark = pytest.mark.gpu
 
 def T(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _scale_log2(w):
-    amax = float(np.abs(w).max())
-    return 0 if amax == 0 else max(-24, min(24, 14 - math.ceil(math.log2(amax))))
-
-
-def _reference(a, w, bias, res, act, rows=None):
-    """float64 GEMM of the fp16-rounded operands (+ the fp32-accumulation error bound of each output)"""
-    s = _scale_log2(w)
-    a16 = a.astype(np.float16).astype(np.float64)
-    w16 = (w.astype(np.float64) * 2.0 ** s).astype(np.float16).astype(np.float64)
-    if rows is not None:
-        a16 = a16[rows]
-    acc = (a16 @ w16.T) * 2.0 ** -s
-    mag = (np.abs(a16) @ np.abs(w16).T) * 2.0 ** -s
-    K = a.shape[1]
-    y = acc + (bias.astype(np.float64) if bias is not None else 0.0)
-    if act == "gelu":      # (|gelu'| <= 1.13: the accumulation error passes through at most 1.2x)
-        y = 0.5 * y * (1.0 + np.vectorize(math.erf)(y / math.sqrt(2.0)))
-    if res is not None:
-        y = y + (res[rows] if rows is not None else res).astype(np.float64)
-    # fp32 accumulation (K terms, each product exact) + the fp32 epilogue (scale, bias, activation, residual)
-    bound = 1.2 * 2.0 * K * 2.0 ** -24 * mag + 8.0 * 2.0 ** -24 * (np.abs(acc) + np.abs(y) + 1.0)
-    return y, bound
 
 
 GEMM_CASES = [
@@ -61,7 +35,7 @@ def test_gemm_f16_is_the_fp16_operand_product(cuda, M, N, K, has_b, has_r, act, 
     w = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
     b = rng.standard_normal(N).astype(np.float32) if has_b else None
     r = rng.standard_normal((M, N)).astype(np.float32) if has_r else None
-    ref, bound = _reference(a, w, b, r, act)
+    ref, bound = gemm_f16_reference(a, w, b, r, act)
     W = T(w, cuda)
     args = (T(a, cuda), W, T(b, cuda) if has_b else None, T(r, cuda) if has_r else None, act)
     try:
@@ -92,7 +66,7 @@ def test_gemm_f16_row_balanced_split_k_tail(cuda):
     y = ops.gemm_f16x3(T(a, cuda), T(w, cuda), T(b, cuda), T(r, cuda), balanced=True).cpu().numpy().astype(np.float64)
     assert ops.split_overflow_count() == 0
     rows = np.r_[0:300, M - 1100:M]
-    ref, bound = _reference(a, w, b, r, "none", rows=rows)
+    ref, bound = gemm_f16_reference(a, w, b, r, "none", rows=rows)
     ratio = np.abs(y[rows] - ref) / bound
     assert ratio.max() <= 1.0, ratio.max()
 
@@ -109,7 +83,7 @@ def test_skinny_gemm_f16(cuda, M, N, K, has_r):
     ops.register_split_weight(W)
     ops.set_precision("f16")
     y = ops.gemm(T(a, cuda), W, T(b, cuda), T(r, cuda) if has_r else None).cpu().numpy().astype(np.float64)
-    ref, bound = _reference(a, w, b, r, "none")
+    ref, bound = gemm_f16_reference(a, w, b, r, "none")
     assert (np.abs(y - ref) / bound).max() <= 1.0
     ops.set_precision("f16x3")
     y3 = ops.gemm(T(a, cuda), W, T(b, cuda), T(r, cuda) if has_r else None).cpu().numpy().astype(np.float64)

@@ -224,7 +224,7 @@ def test_gemm_inplace_residual_and_asymmetry(cuda):
     np.testing.assert_allclose(c.cpu().numpy(), w.T + 1, rtol=0, atol=1e-6)
 
 
-@pytest.mark.parametrize("D", [256, 512, 768, 1280, 96, 128])
+@pytest.mark.parametrize("D", [256, 512, 768, 1024, 1280, 96, 128])
 def test_layernorm(cuda, D):
     rng = np.random.default_rng(D)
     x = (rng.standard_normal((301, D)) * 3 + 1).astype(np.float32)
@@ -233,6 +233,34 @@ def test_layernorm(cuda, D):
     for eps in (1e-5, 1e-6):
         y = ops.layernorm(T(x, cuda), T(w, cuda), T(b, cuda), eps).cpu().numpy()
         np.testing.assert_allclose(y, O.layer_norm(x, w, b, eps), rtol=0, atol=2e-5)
+
+
+@pytest.mark.parametrize("D", [256, 512, 768, 1024, 1280, 96])
+@pytest.mark.parametrize("misaligned", [False, True], ids=["aligned", "misaligned"])
+def test_layernorm_vec_widths_misalignment_and_offset_mean(cuda, D, misaligned):
+    """hgl_layernorm_f32 against float64 on the register-resident widths (layernorm_vec_kernel<D / 256>) and, with x and y
+    one float off 16-byte alignment, on the same widths through layernorm_any_kernel; rows 0..3 sit at |mean| ~ 1e3 with a
+    spread of 3, where a one-pass variance (E[x^2] - mean^2 in fp32) loses ~1e-2 of the result, and the two-pass variance
+    of both kernels keeps the error at the fp32 rounding of the mean (~1e-7 |mean| / std relative)."""
+    import abi_ref as R
+    rows, off = 301, int(misaligned)
+    g = torch.Generator(device=cuda).manual_seed(D + off)
+    x = torch.randn((rows, D), device=cuda, generator=g) * 3 + 1
+    x[:4] += torch.tensor([1.0e3, -1.0e3, 2.0e3, 7.5e2], device=cuda)[:, None]
+    w = torch.randn((D,), device=cuda, generator=g)
+    b = torch.randn((D,), device=cuda, generator=g)
+    xb = torch.empty((rows * D + 4,), device=cuda)
+    xb[off:off + rows * D] = x.reshape(-1)
+    yb = torch.full((rows * D + 4,), -7.25e30, device=cuda)
+    names = R.launched_kernels(lambda: R.layernorm(xb, w, b, yb, rows, D, 1e-6, ox=off, oy=off))
+    vec = D % 256 == 0 and D <= 1280 and not misaligned
+    assert names == [f"layernorm_vec_kernel<{D // 256}>" if vec else "layernorm_any_kernel"], names
+    y = yb[off:off + rows * D].reshape(rows, D).double()
+    ref = R.layernorm_reference(x, w, b, 1e-6)
+    std = x.double().std(-1, keepdim=True)
+    bound = 2e-5 + 8e-7 * x.double().mean(-1, keepdim=True).abs() / std * float(w.abs().max())
+    assert ((y - ref).abs() <= bound).all(), float(((y - ref).abs() - bound).max())
+    assert (yb[:off] == -7.25e30).all() and (yb[off + rows * D:] == -7.25e30).all()
 
 
 def _attn_ref(q, k, v, heads, scale, add_mask=None, bias=None):
@@ -643,26 +671,39 @@ def test_gemm_f16x3_fp16_valued_weights_drop_the_zero_products(cuda):
 def test_ping_pong_attention_is_bit_identical_to_the_tile_kernel(cuda, tmp_path, B, H, S, hd, rel):
     """attn_x3pp_kernel (one 8-wave workgroup per 256 queries, two wave groups one barrier interval apart, K / V chunks
     double-buffered) against attn_x3_kernel (HGL_ATTN_PP=0, a child process): same arithmetic per (query tile, key tile)
-    pair -> identical bits; with the rel-pos tensors of SAM's global blocks, a 64-wide head, a ragged last key tile."""
+    pair -> identical bits; with the rel-pos tensors of SAM's global blocks (a 36 x 64 key grid: kw and Sk multiples of 32,
+    as the ping-pong kernel's rel-pos path needs), a 64-wide head, a ragged last key tile.  Each child reports the kernels
+    it launched: the HGL_ATTN_PP=1 child must have run the ping-pong kernel, the other the tile kernel."""
+    import json
     import subprocess
     import sys
+    grid = (36, 64) if rel else None        # rel-pos key grid (kh, kw)
+    assert grid is None or grid[0] * grid[1] == S
     code = f"""
-import sys, numpy as np, torch
+import json, sys, numpy as np, torch
 sys.path.insert(0, {ROOT!r})
+sys.path.insert(0, {os.path.join(ROOT, "tests")!r})
+import abi_ref
 from hybridgl_amd import ops
 ops.set_precision('f16x3')
 g = torch.Generator().manual_seed({S + hd})
 q, k, v = (torch.randn({B}, {S}, {H * hd}, generator=g).cuda() for _ in range(3))
 kw = {{}}
-if {rel}:
-    side = int(round({S} ** 0.5))
-    kw = dict(rel_h=torch.randn({B * H}, {S}, side, generator=g).cuda(), rel_w=torch.randn({B * H}, {S}, side, generator=g).cuda())
-np.save(sys.argv[1], ops.attention(q, k, v, {H}, **kw).cpu().numpy())
+rel = {grid!r}
+if rel:
+    kw = dict(rel_h=torch.randn({B * H}, {S}, rel[0], generator=g).cuda(), rel_w=torch.randn({B * H}, {S}, rel[1], generator=g).cuda())
+out = []
+names = abi_ref.launched_kernels(lambda: out.append(ops.attention(q, k, v, {H}, **kw)))
+np.save(sys.argv[1], out[0].cpu().numpy())
+json.dump(names, open(sys.argv[1] + '.json', 'w'))
 """
-    outs = []
+    outs, kernels = [], []
     for pp in ("1", "0"):
         path = str(tmp_path / f"hgl_pp_{pp}_{S}_{hd}.npy")
         r = subprocess.run([sys.executable, "-c", code, path], env=dict(os.environ, HGL_ATTN_PP=pp), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-1500:]
         outs.append(np.load(path))
+        kernels.append(json.load(open(path + ".json")))
+    assert kernels[0] == [f"attn_x3pp_kernel<{hd},3>"], kernels
+    assert kernels[1] == [f"attn_x3_kernel<{hd},0,4,3>"], kernels
     assert np.isfinite(outs[0]).all() and np.array_equal(outs[0], outs[1])
