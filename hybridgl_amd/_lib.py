@@ -170,6 +170,9 @@ PROTOTYPES = {
     "hgl_sam_decode_workspace_bytes": (_SZ, [C.POINTER(HglSamDecoderW), _I]),
     "hgl_sam_decode_points": (_I, [C.POINTER(HglSamDecoderW), _VP, _VP, _I, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_sam_decode_points_gated": (_I, [C.POINTER(HglSamDecoderW), _VP, _VP, _I, C.c_float, _VP, _VP, _VP, _SZ, _VP]),
+    "hgl_sam_decode_multi_workspace_bytes": (_SZ, [C.POINTER(HglSamDecoderW), _I, _I]),
+    "hgl_sam_decode_points_multi": (_I, [C.POINTER(HglSamDecoderW), _VP, _VP, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "hgl_sam_decode_points_multi_gated": (_I, [C.POINTER(HglSamDecoderW), _VP, _VP, _I, _I, C.c_float, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_sam_decode_prompts": (_I, [C.POINTER(HglSamDecoderW), _VP, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_sam_embed_masks": (_I, [C.POINTER(HglSamDecoderW), _VP, _I, _VP, _VP]),
     "hgl_sam_decoder_fusion": (_I, [_I]),
@@ -179,6 +182,7 @@ PROTOTYPES = {
     "hgl_sam_postprocess": (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _VP, _VP, _VP, _VP, _VP,
                                  _VP, _SZ, _VP]),
     "hgl_nms": (_I, [_VP, _VP, _VP, _I, _F, _VP, _VP, _VP]),
+    "hgl_nms_segments": (_I, [_VP, _VP, _VP, _VP, _I, _I, _F, _VP, _VP, _VP]),
     "hgl_nms_large_workspace_bytes": (_SZ, [_I]),
     "hgl_nms_large": (_I, [_VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_box_near_crop_edge": (_I, [_VP, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, _VP, _VP]),

@@ -1480,6 +1480,7 @@ struct FewQArgs {
   int B, H, Sq, Sk, ldq, ldk, ldv, ldo;
   long long sqb, skb, svb, sob;
   float scale;
+  int kvdiv;      // chunked kernel: batches b that share keys / values (those of set b / kvdiv, skb / svb apart); else 1
 };
 
 constexpr int FEWQ_MAX = 8;
@@ -1622,8 +1623,8 @@ __global__ __launch_bounds__(256, 4) void attn_fewq_chunk_kernel(FewQArgs a, flo
     o[qi][0] = f32x4{0.f, 0.f, 0.f, 0.f};
     o[qi][1] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const float* kp = a.k + b * a.skb + hh * 16 + c2 * 8;
-  const float* vp = a.v + b * a.svb + hh * 16 + c2 * 8;
+  const float* kp = a.k + (b / a.kvdiv) * a.skb + hh * 16 + c2 * 8;
+  const float* vp = a.v + (b / a.kvdiv) * a.svb + hh * 16 + c2 * 8;
   const float* qs = q_s + hh * FQC_QS + c2 * 8;
   const int k0 = chunk * FQC_KEYS + ks;
   f32x4 kn[2], vn[2];
@@ -1857,6 +1858,7 @@ int hgl_launch_attention_fewq(const float* q, const float* k, const float* v, fl
   HGL_REQUIRE(hd == 16 && Sq >= 1 && Sq <= FEWQ_MAX, "attention_fewq: unsupported shape (hd %d, Sq %d)", hd, Sq);
   HGL_REQUIRE(((ldk | ldv) & 3) == 0 && ((skb | svb) & 3) == 0, "attention_fewq: K/V strides must be multiples of 4");
   FewQArgs a;
+  a.kvdiv = 1;
   a.q = q; a.k = k; a.v = v; a.out = out; a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.sqb = sqb; a.skb = skb; a.svb = svb; a.sob = sob; a.scale = scale;
   HglProfScope prof(HGL_PROF_ATTN, 4.0 * B * (double)H * Sq * Sk * hd, 0.0, st);
@@ -1871,14 +1873,16 @@ size_t hgl_attention_fewq_part_bytes(int B, int Sk) {
 
 int hgl_launch_attention_fewq_chunked(const float* q, const float* k, const float* v, float* out, int B, int H, int Sq, int Sk,
                                       int hd, int ldq, int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb,
-                                      long long sob, float scale, float* part, size_t part_bytes, hipStream_t st) {
+                                      long long sob, float scale, float* part, size_t part_bytes, hipStream_t st, int kv_group) {
   HGL_REQUIRE(q && k && v && out && part, "attention_fewq_chunked: null operand");
+  HGL_REQUIRE(kv_group >= 1 && B % kv_group == 0, "attention_fewq_chunked: %d batches in groups of %d", B, kv_group);
   HGL_REQUIRE(hd == 16 && H == 8 && Sq >= 1 && Sq <= 7 && Sk >= 1 && B >= 1 && B <= 65535,
               "attention_fewq_chunked: unsupported shape (hd %d, H %d, Sq %d)", hd, H, Sq);
   HGL_REQUIRE(((ldk | ldv) & 3) == 0 && ((skb | svb) & 3) == 0 && (((uintptr_t)k | (uintptr_t)v) & 15) == 0,
               "attention_fewq_chunked: K/V strides must be multiples of 4");
   HGL_REQUIRE(part_bytes >= hgl_attention_fewq_part_bytes(B, Sk), "attention_fewq_chunked: partial buffer too small");
   FewQArgs a;
+  a.kvdiv = kv_group;
   a.q = q; a.k = k; a.v = v; a.out = out; a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.sqb = sqb; a.skb = skb; a.svb = svb; a.sob = sob; a.scale = scale;
   const int nchunk = (Sk + FQC_KEYS - 1) / FQC_KEYS;

@@ -193,7 +193,8 @@ int hgl_launch_attention_smallk(const float* q, const float* k, const float* v, 
 size_t hgl_attention_fewq_part_bytes(int B, int Sk);
 int hgl_launch_attention_fewq_chunked(const float* q, const float* k, const float* v, float* out, int B, int H, int Sq, int Sk,
                                       int hd, int ldq, int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb,
-                                      long long sob, float scale, float* part, size_t part_bytes, hipStream_t st);
+                                      long long sob, float scale, float* part, size_t part_bytes, hipStream_t st,
+                                      int kv_group = 1);   // > 1: batches b of one group share the keys / values of set b / kv_group
 int hgl_launch_attention(const float* q, const float* k, const float* v, float* out, int B, int H,
                          int Sq, int Sk, int hd, int ldq, int ldk, int ldv, int ldo, long long sqb,
                          long long skb, long long svb, long long sob, float scale, int mask_kind,
@@ -298,7 +299,8 @@ int hgl_launch_dec_tail(const void* src_hi, const void* src_lo, const float* up0
                         float eps, float* low_res, const uint8_t* skip, hipStream_t st);
 int hgl_launch_dec_i2t(const float* q, int ldq, long long q_bstride, const float* k1, const float* v1, const float* out_w,
                        const float* out_b, const float* R, long long r_bstride, const float* ln_w, const float* ln_b, float eps,
-                       float scale, int P, int HW, float* out32, void* out_hi, void* out_lo, hipStream_t st);
+                       float scale, int P, int HW, float* out32, void* out_hi, void* out_lo, hipStream_t st,
+                       int per_set = 1);   // > 1: prompts p of one set share the queries / residual rows of set p / per_set
 
 // split-fp16 GEMM path (gemm_f16x3.hip)
 int hgl_precision();

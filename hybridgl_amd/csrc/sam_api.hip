@@ -254,7 +254,8 @@ struct DecPlan {
   uint8_t* skip;      // IoU gate: prompts whose upscaling is skipped
 };
 
-bool carve_dec(HglArena& ar, const HglSamDecoderW* w, int P, DecPlan& p) {
+// n_img > 1: the P prompts belong to n_img images (P / n_img each): one set of shared layer-0 image tokens per image
+bool carve_dec(HglArena& ar, const HglSamDecoderW* w, int P, DecPlan& p, int n_img = 1) {
   const size_t C = w->C, HW = (size_t)w->grid * w->grid, T = 16;   // 5 output tokens + up to 11 sparse prompt tokens
   p.sparse = ar.take<float>((size_t)P * (T - 5) * C);
   p.tokens = ar.take<float>(P * T * C);
@@ -264,8 +265,8 @@ bool carve_dec(HglArena& ar, const HglSamDecoderW* w, int P, DecPlan& p) {
   p.k1 = ar.take<float>(P * T * C);
   p.v1 = ar.take<float>(P * T * C);
   p.att = ar.take<float>(P * T * C);
-  p.keys0 = ar.take<float>(HW * C);
-  p.kpe0 = ar.take<float>(HW * C);
+  p.keys0 = ar.take<float>(n_img * HW * C);
+  p.kpe0 = ar.take<float>(n_img * HW * C);
   p.keys = ar.take<float>(P * HW * C);
   p.kpe = ar.take<float>(P * HW * C);
   // k / v / q projections of the image tokens: three [P*HW, C/2] matrices, or -- merged projections -- ONE [P*HW, 3C/2]
@@ -314,6 +315,18 @@ inline int lin(const float* A, int lda, const HglLinearW& l, const float* R, int
   return hgl_launch_gemm(A, l.w, l.b, R, Cc, M, N, K, lda, K, ldr, ldc, 1, 0, 0, 0, 0, act, st);
 }
 
+// lin() over the rows of n sets of M rows each (the shared image tokens of n images), every row as lin() over ONE set gives
+// it: the kernel lin() picks for M rows is a small-tile one whose rows do not depend on the row count -> one launch over
+// n * M rows; any other choice (fp32 tiles, whose dispatch looks at M) -> set by set.
+inline int lin_sets(const float* A, int lda, const HglLinearW& l, float* Cc, int ldc, int M, int n, int N, int K, hipStream_t st) {
+  if (n == 1) return lin(A, lda, l, nullptr, 0, Cc, ldc, M, N, K, HGL_ACT_NONE, st);
+  if (hgl_gemm_skinny_applicable(l.w, M, N, K, lda, K, 1, 8192))
+    return hgl_launch_gemm_x3_skinny(A, lda, l.w, l.b, nullptr, 0, Cc, ldc, n * M, N, K, HGL_ACT_NONE, st);
+  for (int i = 0; i < n; ++i)
+    HGL_TRY(lin(A + (size_t)i * M * lda, lda, l, nullptr, 0, Cc + (size_t)i * M * ldc, ldc, M, N, K, HGL_ACT_NONE, st));
+  return HGL_OK;
+}
+
 // which fused decoder stages are in use (bit 0: upscaling + hyper-network products, bit 1: merged image-side projections,
 // bit 2: image -> token attention + out-projection + norm4, bit 3: unused, bit 4: chunked token -> image attention);
 // default: all stages fused
@@ -327,7 +340,7 @@ int dec_fusion_mask() {
 // partials in `scratch` (the image -> token buffer, idle at that point)
 int dec_fewq(const float* q, const float* k, const float* v, float* att, int B, int heads, int Nq, int Nk, int hd, int ldq,
              int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb, long long sob, float* scratch,
-             size_t scratch_bytes, hipStream_t st) {
+             size_t scratch_bytes, hipStream_t st, int kv_group = 1) {
   const float scale = 1.0f / sqrtf((float)hd);
   if ((dec_fusion_mask() & 16) && scratch && heads == 8 && hd == 16 && Nk >= 256 && B <= 65535 &&
       scratch_bytes >= hgl_attention_fewq_part_bytes(B, Nk)) {
@@ -335,9 +348,10 @@ int dec_fewq(const float* q, const float* k, const float* v, float* att, int B, 
     for (int q0 = 0; q0 < Nq; q0 += 7)
       HGL_TRY(hgl_launch_attention_fewq_chunked(q + (long long)q0 * ldq, k, v, att + (long long)q0 * ldo, B, heads,
                                                 Nq - q0 < 7 ? Nq - q0 : 7, Nk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb, sob, scale,
-                                                scratch, scratch_bytes, st));
+                                                scratch, scratch_bytes, st, kv_group));
     return HGL_OK;
   }
+  HGL_REQUIRE(kv_group == 1, "sam_decode: keys shared by groups of %d prompts need the chunked attention", kv_group);
   return hgl_launch_attention(q, k, v, att, B, heads, Nq, Nk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb, sob, scale, HGL_MASK_NONE,
                               nullptr, 0, 0, nullptr, nullptr, 0, 0, st);
 }
@@ -346,15 +360,24 @@ int dec_fewq(const float* q, const float* k, const float* v, float* att, int B, 
 // Nq rows serve every batch (batch stride 0).  out: [B, Nq, C] (+ residual R, may alias out).
 int dec_attn(const HglSamDecoderW* w, const HglSamAttnW& a, const float* q, bool q_shared, int Nq, const float* k,
              const float* v, bool kv_shared, int Nk, int B, float* qp, float* kp, float* vp, float* att,
-             const float* R, long long sR, float* out, hipStream_t st, float* scratch = nullptr, size_t scratch_bytes = 0) {
+             const float* R, long long sR, float* out, hipStream_t st, float* scratch = nullptr, size_t scratch_bytes = 0,
+             int kv_sets = 1) {
   const int C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
   const int Bq = q_shared ? 1 : B, Bk = kv_shared ? 1 : B;
   HGL_TRY(lin(q, C, a.q, nullptr, 0, qp, I, Bq * Nq, I, C, HGL_ACT_NONE, st));
-  HGL_TRY(lin(k, C, a.k, nullptr, 0, kp, I, Bk * Nk, I, C, HGL_ACT_NONE, st));
-  HGL_TRY(lin(v, C, a.v, nullptr, 0, vp, I, Bk * Nk, I, C, HGL_ACT_NONE, st));
-  HGL_TRY(dec_fewq(qp, kp, vp, att, B, heads, Nq, Nk, hd, I, I, I, I, q_shared ? 0 : (long long)Nq * I,
-                   kv_shared ? 0 : (long long)Nk * I, kv_shared ? 0 : (long long)Nk * I, (long long)Nq * I, scratch,
-                   scratch_bytes, st));
+  if (kv_shared && kv_sets > 1) {
+    // the prompts of kv_sets images in one launch: prompt b attends to the keys / values of image b / (B / kv_sets)
+    HGL_TRY(lin_sets(k, C, a.k, kp, I, Nk, kv_sets, I, C, st));
+    HGL_TRY(lin_sets(v, C, a.v, vp, I, Nk, kv_sets, I, C, st));
+    HGL_TRY(dec_fewq(qp, kp, vp, att, B, heads, Nq, Nk, hd, I, I, I, I, (long long)Nq * I, (long long)Nk * I, (long long)Nk * I,
+                     (long long)Nq * I, scratch, scratch_bytes, st, B / kv_sets));
+  } else {
+    HGL_TRY(lin(k, C, a.k, nullptr, 0, kp, I, Bk * Nk, I, C, HGL_ACT_NONE, st));
+    HGL_TRY(lin(v, C, a.v, nullptr, 0, vp, I, Bk * Nk, I, C, HGL_ACT_NONE, st));
+    HGL_TRY(dec_fewq(qp, kp, vp, att, B, heads, Nq, Nk, hd, I, I, I, I, q_shared ? 0 : (long long)Nq * I,
+                     kv_shared ? 0 : (long long)Nk * I, kv_shared ? 0 : (long long)Nk * I, (long long)Nq * I, scratch,
+                     scratch_bytes, st));
+  }
   // out_proj (+ residual): one GEMM over all B*Nq rows when the residual is laid out like the output (small row
   // counts then take the small-tile kernel); batched when a shared residual (stride 0) has to be broadcast
   if (!R || sR == (long long)Nq * C)
@@ -442,8 +465,8 @@ int dec_t2i_merged(const HglSamDecoderW* w, const HglSamAttnW& a, const float* q
 // token -> image attention on the RAW image-token planes (sam_decoder_t2i.hip): the 7 tokens are projected through W_k / W_v
 // instead of the HW image tokens.  Scratch: `small` (>= P * 56 * 256 * 8 bytes: the folded queries' planes + the attended
 // rows), `bias` (P * 56 * HW floats).
-int dec_t2i_raw(const HglSamDecoderW* w, const HglSamAttnW& a, const float* qpe, const SplitPair& keysS, int P, int HW, int T,
-                float* q1, float* small, float* bias, float* att, float* queries, hipStream_t st) {
+int dec_t2i_raw(const HglSamDecoderW* w, const HglSamAttnW& a, const float* qpe, const SplitPair& keysS, int P, int ppi, int HW,
+                int T, float* q1, float* small, float* bias, float* att, float* queries, hipStream_t st) {
   const int C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
   HGL_TRY(lin(qpe, C, a.q, nullptr, 0, q1, I, P * T, I, C, HGL_ACT_NONE, st));
   uint16_t* Qh = (uint16_t*)small;
@@ -454,8 +477,10 @@ int dec_t2i_raw(const HglSamDecoderW* w, const HglSamAttnW& a, const float* qpe,
   // bias[p*56 + r, key] = Qk[p*56 + r, :] . pe[key, :]: pe is the "weight" [HW, C] of a split-fp16 GEMM
   HGL_TRY(hgl_launch_gemm_f16x3(Qh, Ql, C, w->dense_pe, nullptr, nullptr, 0, bias, nullptr, nullptr, HW, P * 56, HW, C,
                                 HGL_ACT_NONE, st));
-  // (prompt batches of <= 128: eight key ranges per prompt, their partial rows behind the folded queries; see the kernel)
-  const int ns = hgl_t2i_key_ranges(P, HW);
+  // (prompt batches of <= 128: eight key ranges per prompt, their partial rows behind the folded queries; see the kernel.
+  // The batch that decides is the image's own, ppi, not the launch's total: a prompt's sums keep their order whether its
+  // image is decoded alone or with others)
+  const int ns = hgl_t2i_key_ranges(ppi, HW);
   float* const rows = ns > 1 ? A + (size_t)P * 56 * C : A;
   HGL_TRY(hgl_launch_t2i_raw_attn(Qh, Ql, bias, keysS.hi, keysS.lo, P, HW, rows, ns, st));
   HGL_TRY(hgl_launch_t2i_unfold_v(rows, ns, a.v.w, a.v.b, att, P, st));
@@ -602,7 +627,7 @@ __global__ void iou_gate_kernel(const float* __restrict__ iou, int P, float gate
 static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* points01, const float* coords01,
                        const int32_t* labels, int n_sparse, const float* dense, int first_mask, int P, float* low_res,
                        float* iou_pred, void* workspace, size_t workspace_bytes, void* stream, bool gated = false,
-                       float iou_gate = 0.f) {
+                       float iou_gate = 0.f, int n_img = 1) {
   // the decoder keeps the f16x3 arithmetic in f16 mode: its split producers write both planes, its GEMMs issue three terms
   const HglSplitTermsScope three_terms(3);
   HGL_TRY(hgl_require_device());
@@ -611,9 +636,11 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
   HGL_REQUIRE(first_mask == 0 || first_mask == 1, "sam_decode: first_mask must be 0 or 1");
   HGL_REQUIRE(n_sparse >= 2 && n_sparse <= 11, "sam_decode: %d sparse tokens per prompt (2 .. 11 supported)", n_sparse);
   HGL_REQUIRE(n_sparse <= 3 || (long long)P * w->heads <= 65535, "sam_decode: %d prompts of more than 3 sparse tokens in one call", P);
+  HGL_REQUIRE(n_img >= 1 && P % n_img == 0 && (n_img == 1 || (points01 && !dense)), "sam_decode: %d prompts for %d images", P, n_img);
+  const int ppi = P / n_img;   // prompts per image: emb holds n_img embeddings, prompt p belongs to image p / ppi
   HglArena ar(workspace, workspace_bytes);
   DecPlan p;
-  if (!workspace || !carve_dec(ar, w, P, p)) {
+  if (!workspace || !carve_dec(ar, w, P, p, n_img)) {
     hgl_set_error("sam_decode: workspace too small (%zu bytes given)", workspace_bytes);
     return HGL_EWORKSPACE;
   }
@@ -638,8 +665,9 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
     HGL_TRY(hgl_launch_add_rows_bcast(p.keys, sK, w->dense_pe, sK, P, p.kpe, st));
   } else {
     // src = image_embedding + no_mask_embed (dense prompt) ; shared by all prompts until the first update
-    HGL_TRY(hgl_launch_add_rows_bcast(emb, C, w->no_mask, C, HW, p.keys0, st));   // rows of C, "pe" = no_mask [C]
-    HGL_TRY(hgl_launch_add_rows_bcast(p.keys0, 0, w->dense_pe, (long long)HW * C, 1, p.kpe0, st));
+    // (n_img images: one such set per image, sK apart)
+    HGL_TRY(hgl_launch_add_rows_bcast(emb, C, w->no_mask, C, n_img * HW, p.keys0, st));   // rows of C, "pe" = no_mask [C]
+    HGL_TRY(hgl_launch_add_rows_bcast(p.keys0, n_img > 1 ? sK : 0, w->dense_pe, (long long)HW * C, n_img, p.kpe0, st));
   }
   (void)hipMemcpyAsync(p.queries, p.tokens, sizeof(float) * P * sQ, hipMemcpyDeviceToDevice, st);
 
@@ -652,7 +680,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
   // through W_k / W_v instead of the HW image tokens: no k | v projection GEMM; layer 1 projects q alone for its step 4)
   const bool raw_t2i = merged && (dec_fusion_mask() & 32) && (dec_fusion_mask() & 4) && T == 7 && I1 == 128 && w->heads == 8 &&
                        C == 256 && HW % 128 == 0 && P <= 65535 && !perprompt && hgl_has_split_weight(w->dense_pe) &&
-                       (size_t)P * (56 * C * 8) + hgl_t2i_part_bytes(P, HW) <= atti_bytes &&   // dec_t2i_raw: Q' planes + attended rows (+ partials)
+                       (size_t)P * (56 * C * 8) + n_img * hgl_t2i_part_bytes(ppi, HW) <= atti_bytes &&   // dec_t2i_raw: Q' planes + attended rows (+ partials)
                        (size_t)P * (56 * C * 4 + 16384 * 4 + 256) <= atti_bytes;      // step (4): K' and U planes + cb
   for (int li = 0; li < 2; ++li) {
     const auto& L = w->layer[li];
@@ -677,7 +705,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
     if (raw_t2i && !shared && !plain0) {
       // no projection of the image tokens at all: this attention reads the raw planes (its positional term in p.kp), and
       // step (4) below folds W_q into the 7 token keys as well
-      HGL_TRY(dec_t2i_raw(w, L.t2i, p.qpe, keysS, P, HW, T, p.q1, p.atti, p.kp, p.att, p.queries, st));
+      HGL_TRY(dec_t2i_raw(w, L.t2i, p.qpe, keysS, P, ppi, HW, T, p.q1, p.atti, p.kp, p.att, p.queries, st));
     } else if (merged && !shared && !plain0) {
       // k, v of this step and q of step (4) read the same rows: one GEMM, the positional encoding as a per-position table
       HGL_TRY(dec_project_merged(keysS, w->kvq1_w, w->kvq1_b, w->kvq1_pe, P, HW, C, 3 * I1, p.kp, st));
@@ -686,7 +714,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
       HGL_TRY(dec_t2i_x3(w, L.t2i, p.qpe, kpeS, keysS, P, HW, T, p.q1, p.kp, p.vp, p.att, p.queries, p.atti, atti_bytes, st));
     } else {
       HGL_TRY(dec_attn(w, L.t2i, p.qpe, false, T, kpe, keys, shared, HW, P, p.q1, p.kp, p.vp, p.att, p.queries, sQ,
-                       p.queries, st, p.atti, atti_bytes));
+                       p.queries, st, p.atti, atti_bytes, shared ? n_img : 1));
     }
     HGL_TRY(hgl_launch_layernorm(p.queries, L.n2.w, L.n2.b, p.queries, P * T, C, 1e-5f, st));
     // (3) MLP on the tokens
@@ -718,11 +746,17 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
       // split planes the next projections read (and, in layer 0, as the fp32 rows layer 1 adds its update to)
       HGL_TRY(lin(p.qpe, C, L.i2t.k, nullptr, 0, p.k1, I1, P * T, I1, C, HGL_ACT_NONE, st));
       HGL_TRY(lin(p.queries, C, L.i2t.v, nullptr, 0, p.v1, I1, P * T, I1, C, HGL_ACT_NONE, st));
-      if (shared) HGL_TRY(lin(p.kpe0, C, L.i2t.q, nullptr, 0, p.qi, I1, HW, I1, C, HGL_ACT_NONE, st));
-      HGL_TRY(hgl_launch_dec_i2t(shared ? p.qi : p.kp + 2 * I1, shared ? I1 : 3 * I1, shared ? 0 : (long long)HW * 3 * I1, p.k1,
-                                 p.v1, L.i2t.out.w, L.i2t.out.b, keys, shared ? 0 : sK, L.n4.w, L.n4.b, 1e-5f,
+      if (shared) HGL_TRY(lin_sets(p.kpe0, C, L.i2t.q, p.qi, I1, HW, n_img, I1, C, st));
+      // (shared rows: stride 0 for one image; n_img images: the rows of image p / ppi, one image's rows apart)
+      const bool sets = shared && n_img > 1;
+      HGL_TRY(hgl_launch_dec_i2t(shared ? p.qi : p.kp + 2 * I1, shared ? I1 : 3 * I1,
+                                 sets ? (long long)HW * I1 : shared ? 0 : (long long)HW * 3 * I1, p.k1,
+                                 p.v1, L.i2t.out.w, L.i2t.out.b, keys, sets ? sK : shared ? 0 : sK, L.n4.w, L.n4.b, 1e-5f,
                                  1.0f / sqrtf((float)(I1 / w->heads)), P, HW, (li == 0 && !raw_t2i) ? p.keys : nullptr, keysS.hi,
-                                 keysS.lo, st));
+                                 keysS.lo, st, sets ? ppi : 1));
+    } else if (shared && n_img > 1) {
+      hgl_set_error("sam_decode: several images in one launch need the fused image -> token step");
+      return HGL_EINVAL;
     } else if (x3 && plain0) {
       HGL_TRY(dec_attn(w, L.i2t, kpe, false, HW, p.qpe, p.queries, false, T, P, p.qi, p.k1, p.v1, p.atti, keys, sK, p.keys, st));
       HGL_TRY(hgl_launch_ln256_pe_split(p.keys, L.n4.w, L.n4.b, w->dense_pe, HW, (long long)P * HW, 1e-5f, 1, keysS.hi, keysS.lo,
@@ -748,7 +782,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
   // final token -> image attention
   HGL_TRY(hgl_launch_add_rows_bcast(p.queries, P * sQ, p.tokens, P * sQ, 1, p.qpe, st));
   if (raw_t2i) {
-    HGL_TRY(dec_t2i_raw(w, w->final_t2i, p.qpe, keysS, P, HW, T, p.q1, p.atti, p.kp, p.att, p.queries, st));
+    HGL_TRY(dec_t2i_raw(w, w->final_t2i, p.qpe, keysS, P, ppi, HW, T, p.q1, p.atti, p.kp, p.att, p.queries, st));
   } else if (merged) {
     HGL_TRY(dec_project_merged(keysS, w->kvf_w, w->kvf_b, w->kvf_pe, P, HW, C, 2 * I1, p.kp, st));
     HGL_TRY(dec_t2i_merged(w, w->final_t2i, p.qpe, p.kp, 2 * I1, P, HW, T, p.q1, p.att, p.queries, p.atti, atti_bytes, st));
@@ -771,6 +805,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
   const uint8_t* skip = nullptr;
   if (gated) {
     hipLaunchKernelGGL(iou_gate_kernel, dim3((P + 255) / 256), dim3(256), 0, st, (const float*)iou_pred, P, iou_gate, p.skip);
+    HGL_TRY(hgl_check_launch("iou_gate"));
     skip = p.skip;
   }
 
@@ -823,6 +858,72 @@ int hgl_sam_decode_points_gated(const HglSamDecoderW* w, const float* emb, const
   HGL_REQUIRE(points01, "sam_decode: null input");
   return decode_impl(w, emb, points01, nullptr, nullptr, 2, nullptr, 1, P, low_res, iou_pred, workspace, workspace_bytes, stream, true,
                      iou_gate);
+}
+
+// Can decode_impl take the prompts of several images in ONE launch sequence?  Only layer 0 knows that prompts share image
+// tokens; its two shared steps then need the kernels that address "the rows of image p / ppi": the chunked token -> image
+// attention (fusion bit 4) and the fused image -> token step (bits 1, 2).  The conditions are decode_impl's own.
+static bool dec_multi_fused(const HglSamDecoderW* w, int n_img, int ppi) {
+  const int C = w->C, HW = w->grid * w->grid, I1 = w->layer[1].t2i.internal, heads = w->heads;
+  const long long P = (long long)n_img * ppi;
+  const auto& L0 = w->layer[0];
+  const bool merged = dec_x3_ready(w) && dec_merged_ready(w) && I1 == w->layer[1].i2t.internal && I1 == w->final_t2i.internal &&
+                      2 * w->final_t2i.internal == C;
+  const bool fuse_i2t = merged && (dec_fusion_mask() & 4) && L0.i2t.internal == I1 && I1 == 128 && heads == 8 && HW % 64 == 0;
+  const size_t atti_bytes = (size_t)P * HW * (C / 2) * sizeof(float);
+  const bool chunked = (dec_fusion_mask() & 16) && heads == 8 && L0.t2i.internal == 128 && HW >= 256 &&
+                       atti_bytes >= hgl_attention_fewq_part_bytes((int)P, HW);
+  return P <= 65535 && fuse_i2t && chunked;
+}
+
+// Images per launch sequence: whole images, at most 1024 prompts.  The token-side GEMMs of up to 8192 rows (1170 prompts of 7
+// tokens) run on the small-tile kernel whatever their row count (lin()), larger ones on fp32 tiles with other sums: within
+// the bound a prompt's rows do not depend on how many images share the launch.
+static int dec_multi_images(int n_img, int ppi) {
+  const int per = ppi >= 1024 ? 1 : 1024 / ppi;
+  return per < n_img ? per : n_img;
+}
+
+// n_img images x ppi prompts.  One image: exactly hgl_sam_decode_points(_gated).  Several: launch sequences over
+// dec_multi_images() images each where the fused stages serve (dec_multi_fused), else image by image through the one-image
+// path; either way every prompt's rows are those of its image's own call.
+static int decode_multi(const HglSamDecoderW* w, const float* emb, const float* points01, int n_img, int ppi, float* low_res,
+                        float* iou_pred, void* workspace, size_t workspace_bytes, void* stream, bool gated, float iou_gate) {
+  HGL_REQUIRE(points01, "sam_decode: null input");
+  HGL_REQUIRE(valid_dec(w) && w->dense_pe, "sam_decode: invalid weight struct (dense_pe missing?)");
+  HGL_REQUIRE(n_img >= 1 && ppi >= 1 && (long long)n_img * ppi <= 65535, "sam_decode_multi: %d images x %d prompts", n_img, ppi);
+  if (n_img == 1)
+    return decode_impl(w, emb, points01, nullptr, nullptr, 2, nullptr, 1, ppi, low_res, iou_pred, workspace, workspace_bytes, stream,
+                       gated, iou_gate);
+  const int per = dec_multi_fused(w, dec_multi_images(n_img, ppi), ppi) ? dec_multi_images(n_img, ppi) : 1;
+  const size_t HW = (size_t)w->grid * w->grid, lowsz = (size_t)3 * 16 * HW;
+  for (int i = 0; i < n_img; i += per) {
+    const int k = n_img - i < per ? n_img - i : per;
+    HGL_TRY(decode_impl(w, emb + i * HW * w->C, points01 + (size_t)i * ppi * 2, nullptr, nullptr, 2, nullptr, 1, k * ppi,
+                        low_res + (size_t)i * ppi * lowsz, iou_pred + (size_t)i * ppi * 3, workspace, workspace_bytes, stream, gated,
+                        iou_gate, k));
+  }
+  return HGL_OK;
+}
+
+size_t hgl_sam_decode_multi_workspace_bytes(const HglSamDecoderW* w, int n_img, int ppi) {
+  if (!valid_dec(w) || n_img <= 0 || ppi <= 0 || (long long)n_img * ppi > 65535) return 0;
+  const int per = n_img > 1 && dec_multi_fused(w, dec_multi_images(n_img, ppi), ppi) ? dec_multi_images(n_img, ppi) : 1;
+  HglArena ar(nullptr, 0);
+  DecPlan p;
+  carve_dec(ar, w, per * ppi, p, per);
+  return ar.off;
+}
+
+int hgl_sam_decode_points_multi(const HglSamDecoderW* w, const float* emb, const float* points01, int n_img, int ppi,
+                                float* low_res, float* iou_pred, void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_multi(w, emb, points01, n_img, ppi, low_res, iou_pred, workspace, workspace_bytes, stream, false, 0.f);
+}
+
+int hgl_sam_decode_points_multi_gated(const HglSamDecoderW* w, const float* emb, const float* points01, int n_img, int ppi,
+                                      float iou_gate, float* low_res, float* iou_pred, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return decode_multi(w, emb, points01, n_img, ppi, low_res, iou_pred, workspace, workspace_bytes, stream, true, iou_gate);
 }
 
 int hgl_sam_decode_prompts(const HglSamDecoderW* w, const float* emb, const float* coords01, const int32_t* labels, int n_sparse,

@@ -362,13 +362,14 @@ __global__ __launch_bounds__(512, 4) void dec_tail_kernel(TailArgs a) {
 //                        (reads 268, writes 268 / 536 MB).  Fused: reads q (and the per-prompt residual), writes the split planes
 //                        (and, while a later layer needs them as a residual, the fp32 rows).
 struct I2TArgs {
-  const float* q;             // image-side queries: row (p, n) at q + p * sqb + n * ldq, 128 floats (8 heads x 16)
+  const float* q;             // image-side queries: row (p, n) at q + (p / pdiv) * sqb + n * ldq, 128 floats (8 heads x 16)
   long long sqb;
+  int pdiv;                   // prompts that share one set of queries / residual rows (several images in one launch); else 1
   int ldq;
   const float *k1, *v1;       // projected prompt tokens [P, 7, 128]
   const _Float16 *Wh, *Wl;    // out_proj weight [256, 128] split
   const float* bo;
-  const float* R;             // residual rows of 256 floats: R + p * srb + n * 256   (srb = 0: the same rows for every prompt)
+  const float* R;             // residual rows of 256 floats: R + (p / pdiv) * srb + n * 256   (srb = 0: the same rows for every prompt)
   long long srb;
   const float *ln_w, *ln_b;
   float so, eps, scale;
@@ -419,7 +420,7 @@ __global__ __launch_bounds__(512, 2) void dec_i2t_kernel(I2TArgs a) {
   const int hh = t & 7, arow = t >> 3;
   f32x4 qv[4];
   {
-    const float* qp = a.q + p * a.sqb + (long long)(n0 + arow) * a.ldq + hh * 16;
+    const float* qp = a.q + (p / a.pdiv) * a.sqb + (long long)(n0 + arow) * a.ldq + hh * 16;
 #pragma unroll
     for (int c = 0; c < 4; ++c) qv[c] = *(const f32x4*)(qp + 4 * c);
   }
@@ -525,7 +526,7 @@ __global__ __launch_bounds__(512, 2) void dec_i2t_kernel(I2TArgs a) {
     lw[j] = *(const f32x4*)(a.ln_w + colw + 16 * j);
     lb[j] = *(const f32x4*)(a.ln_b + colw + 16 * j);
   }
-  const float* Rp = a.R + p * a.srb + (long long)n0 * 256 + colw;
+  const float* Rp = a.R + (p / a.pdiv) * a.srb + (long long)n0 * 256 + colw;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -639,10 +640,12 @@ int hgl_launch_dec_tail(const void* src_hi, const void* src_lo, const float* up0
 // Image -> token attention + out-projection + residual + norm4 of a TwoWayAttentionBlock in one launch (dec_i2t_kernel).
 // q: image-side queries (row (p, n) at q + p * q_bstride + n * ldq; q_bstride = 0: one set for every prompt), k1 / v1 the
 // projected prompt tokens [P, 7, 128], R the residual rows (r_bstride = 0: shared), out32 (may be null) / out_hi / out_lo the
-// normalised rows.  HGL_EINVAL when the geometry or the weight does not fit.
+// normalised rows.  per_set > 1 (prompts of several images in one launch): prompts p of one image, per_set in a row, share
+// queries and residual rows; the strides then step from image to image (set p / per_set).  HGL_EINVAL when the geometry or
+// the weight does not fit.
 int hgl_launch_dec_i2t(const float* q, int ldq, long long q_bstride, const float* k1, const float* v1, const float* out_w,
                        const float* out_b, const float* R, long long r_bstride, const float* ln_w, const float* ln_b, float eps,
-                       float scale, int P, int HW, float* out32, void* out_hi, void* out_lo, hipStream_t st) {
+                       float scale, int P, int HW, float* out32, void* out_hi, void* out_lo, hipStream_t st, int per_set) {
   const void *wh, *wl;
   int s = 0, n = 0, k = 0;
   HGL_REQUIRE(hgl_get_split_weight(out_w, &wh, &wl, &s, &n, &k), "dec_i2t: the out-projection weight has no registered fp16 split");
@@ -650,7 +653,9 @@ int hgl_launch_dec_i2t(const float* q, int ldq, long long q_bstride, const float
   HGL_REQUIRE(q && k1 && v1 && R && out_hi && out_lo, "dec_i2t: null operand");
   HGL_REQUIRE(HW % I2T_ROWS == 0 && P > 0 && P <= 65535 && (ldq & 3) == 0 && (q_bstride & 3) == 0 && (r_bstride & 3) == 0,
               "dec_i2t: %d tokens / %d prompts / strides unsupported", HW, P);
+  HGL_REQUIRE(per_set >= 1 && P % per_set == 0, "dec_i2t: %d prompts in sets of %d", P, per_set);
   I2TArgs a;
+  a.pdiv = per_set;
   a.q = q; a.sqb = q_bstride; a.ldq = ldq; a.k1 = k1; a.v1 = v1;
   a.Wh = (const _Float16*)wh; a.Wl = (const _Float16*)wl; a.bo = out_b; a.R = R; a.srb = r_bstride;
   a.ln_w = ln_w; a.ln_b = ln_b; a.so = ldexpf(1.0f, -s); a.eps = eps; a.scale = scale;

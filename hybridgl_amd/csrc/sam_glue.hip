@@ -1114,10 +1114,9 @@ __device__ __forceinline__ bool nms_before(float sj, int j, float si, int i) {
 
 // Greedy NMS in one workgroup (K <= 1024): candidates with keep[k]!=0, descending score with the
 // original index as tie-break (stable sort), suppress IoU > thr.  out_idx[0..n) in kept order.
-__global__ __launch_bounds__(1024) void nms_kernel(const int* __restrict__ boxes,
-                                                   const float* __restrict__ scores,
-                                                   const uint8_t* __restrict__ keep, int K, float thr,
-                                                   int* __restrict__ out_idx, int* __restrict__ out_n) {
+__device__ __forceinline__ void nms_body(const int* __restrict__ boxes, const float* __restrict__ scores,
+                                         const uint8_t* __restrict__ keep, int K, float thr,
+                                         int* __restrict__ out_idx, int* __restrict__ out_n) {
   __shared__ int order[1024];
   __shared__ unsigned char alive[1024];
   __shared__ int cur, nkept;
@@ -1165,6 +1164,13 @@ __global__ __launch_bounds__(1024) void nms_kernel(const int* __restrict__ boxes
   if (t == 0) *out_n = nkept;
 }
 
+__global__ __launch_bounds__(1024) void nms_kernel(const int* __restrict__ boxes,
+                                                   const float* __restrict__ scores,
+                                                   const uint8_t* __restrict__ keep, int K, float thr,
+                                                   int* __restrict__ out_idx, int* __restrict__ out_n) {
+  nms_body(boxes, scores, keep, K, thr, out_idx, out_n);
+}
+
 // ---- NMS for any K (crop layers / dense point grids, automatic_mask_generator.py:209-220,259-266) ----------
 // Same semantics as nms_kernel (descending score, original index breaks ties, suppress IoU > thr), in three passes:
 // rank by counting -> 64x64-bit suppression words of the sorted boxes -> one workgroup walks the row blocks,
@@ -1198,9 +1204,9 @@ __device__ __forceinline__ bool nms_overlap(const int4 a, const int4 b, float th
 // box: 82 us for the 192 candidates of an image): ranks by counting, the boxes in rank order in LDS, every thread the
 // suppression words of its row (the same IoU expression: nms_overlap), then ONE thread walks the rows OR-ing the kept ones
 // into the removed set -- the scheme of the any-K path below in one workgroup.
-__global__ __launch_bounds__(512) void nms_bits_kernel(const int* __restrict__ boxes, const float* __restrict__ scores,
-                                                       const uint8_t* __restrict__ keep, int K, float thr,
-                                                       int* __restrict__ out_idx, int* __restrict__ out_n) {
+__device__ __forceinline__ void nms_bits_body(const int* __restrict__ boxes, const float* __restrict__ scores,
+                                              const uint8_t* __restrict__ keep, int K, float thr,
+                                              int* __restrict__ out_idx, int* __restrict__ out_n) {
   __shared__ int4 sbox[512];
   __shared__ int order[512];
   __shared__ float ssc[512];
@@ -1283,6 +1289,38 @@ __global__ __launch_bounds__(512) void nms_bits_kernel(const int* __restrict__ b
     __syncthreads();
   }
   if (t == 0) *out_n = nkept_s;
+}
+
+__global__ __launch_bounds__(512) void nms_bits_kernel(const int* __restrict__ boxes, const float* __restrict__ scores,
+                                                       const uint8_t* __restrict__ keep, int K, float thr,
+                                                       int* __restrict__ out_idx, int* __restrict__ out_n) {
+  nms_bits_body(boxes, scores, keep, K, thr, out_idx, out_n);
+}
+
+// Several candidate lists in one launch: workgroup s runs the greedy NMS of segment s = candidates offsets[s] .. offsets[s+1]
+// exactly as hgl_nms runs it on that list alone (the same bodies): out_idx[offsets[s] + 0 .. out_n[s]) holds the kept
+// candidates as indices INTO the segment.  BITS: this launch serves the segments of up to 512 candidates (nms_bits_body),
+// else those of 513 .. 1024 (nms_body); a workgroup whose segment belongs to the other launch returns at once, and an
+// empty segment gets its out_n[s] = 0 from the BITS launch.
+template <bool BITS>
+__global__ __launch_bounds__(BITS ? 512 : 1024) void nms_segments_kernel(const int* __restrict__ boxes,
+                                                                         const float* __restrict__ scores,
+                                                                         const uint8_t* __restrict__ keep,
+                                                                         const int* __restrict__ offsets, float thr,
+                                                                         int* __restrict__ out_idx, int* __restrict__ out_n) {
+  const int s = blockIdx.x, o = offsets[s], K = offsets[s + 1] - o;
+  // (a list that is empty, or longer than the caller's max_len admits, keeps nothing: out_n[s] = 0 from the BITS launch,
+  // which runs first; the other launch then overwrites the count of the lists it serves)
+  if (K <= 0 || K > 512) {
+    if (BITS && threadIdx.x == 0) out_n[s] = 0;
+    if (BITS || K <= 0 || K > 1024) return;
+  } else if (!BITS) {
+    return;
+  }
+  if (BITS)
+    nms_bits_body(boxes + 4ll * o, scores + o, keep + o, K, thr, out_idx + o, out_n + s);
+  else
+    nms_body(boxes + 4ll * o, scores + o, keep + o, K, thr, out_idx + o, out_n + s);
 }
 
 // grid (W, W), 64 threads: word (row a = 64*by + t, column block bx) of the upper triangle
@@ -1615,6 +1653,22 @@ int hgl_nms(const int32_t* boxes_xyxy, const float* scores, const uint8_t* keep,
   else
     hipLaunchKernelGGL(nms_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const int*)boxes_xyxy, scores, keep, K, iou_threshold, (int*)out_idx, (int*)out_n);
   return hgl_check_launch("nms");
+}
+
+int hgl_nms_segments(const int32_t* boxes_xyxy, const float* scores, const uint8_t* keep, const int32_t* offsets, int n_seg,
+                     int max_len, float iou_threshold, int32_t* out_idx, int32_t* out_n, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(boxes_xyxy && scores && keep && offsets && out_idx && out_n, "nms_segments: null argument");
+  HGL_REQUIRE(n_seg > 0 && n_seg <= 65535, "nms_segments: n_seg must be in [1,65535] (got %d)", n_seg);
+  HGL_REQUIRE(max_len >= 0 && max_len <= 1024, "nms_segments: segments hold up to 1024 candidates (max_len %d)", max_len);
+  HGL_REQUIRE(((uintptr_t)boxes_xyxy & 15) == 0, "nms_segments: boxes must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(nms_segments_kernel<true>, dim3(n_seg), dim3(512), 0, st, (const int*)boxes_xyxy, scores, keep,
+                     (const int*)offsets, iou_threshold, (int*)out_idx, (int*)out_n);
+  if (max_len > 512)
+    hipLaunchKernelGGL(nms_segments_kernel<false>, dim3(n_seg), dim3(1024), 0, st, (const int*)boxes_xyxy, scores, keep,
+                       (const int*)offsets, iou_threshold, (int*)out_idx, (int*)out_n);
+  return hgl_check_launch("nms_segments");
 }
 
 size_t hgl_nms_large_workspace_bytes(int K) {

@@ -263,6 +263,34 @@ class Sam:
               "hgl_sam_decode_points")
         return low, iou
 
+    def decode_points_multi(self, emb, points01, n_img, iou_gate=None):
+        """decode_points for the prompts of SEVERAL images in one call: emb [n_img, g*g, C], points01 [n_img * ppi, 2], prompt p
+        belongs to image p // ppi -> (low_res [n_img*ppi,3,4g,4g], iou [n_img*ppi,3]); every prompt's rows are bit for bit
+        those of decode_points on its image's own ppi prompts (hgl_sam_decode_points_multi)."""
+        lib = _lib.load()
+        ops.use_precision(self.precision)
+        P = int(points01.shape[0])
+        n_img = int(n_img)
+        if n_img < 1 or P % n_img or tuple(emb.shape[:1]) != (n_img,):
+            raise ValueError(f"{P} prompts / embeddings {tuple(emb.shape)} for {n_img} images")
+        ppi = P // n_img
+        need = lib.hgl_sam_decode_multi_workspace_bytes(C.byref(self.dec_w), n_img, ppi)
+        ws = ops.workspace(need, self.device, "sam_decode")
+        g4 = 4 * self.grid
+        low = torch.empty((P, 3, g4, g4), dtype=torch.float32, device=self.device)
+        iou = torch.empty((P, 3), dtype=torch.float32, device=self.device)
+        if iou_gate is not None:
+            check(lib.hgl_sam_decode_points_multi_gated(C.byref(self.dec_w), ops._dev(emb, torch.float32, "emb"),
+                                                        ops._dev(points01, torch.float32, "points01"), n_img, ppi, float(iou_gate),
+                                                        low.data_ptr(), iou.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
+                  "hgl_sam_decode_points_multi_gated")
+            return low, iou
+        check(lib.hgl_sam_decode_points_multi(C.byref(self.dec_w), ops._dev(emb, torch.float32, "emb"),
+                                              ops._dev(points01, torch.float32, "points01"), n_img, ppi, low.data_ptr(),
+                                              iou.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
+              "hgl_sam_decode_points_multi")
+        return low, iou
+
     def decode_prompts(self, emb, coords01, labels, first_mask=1, dense=None):
         """prompts of two or three sparse tokens (prompt_encoder.py:73-101): coords01 [P,n,2] fp32 device
         ((coordinate + 0.5) / img_size), labels [P,n] int32 (-1 padding, 0 / 1 background / foreground point, 2 / 3 box
@@ -336,6 +364,20 @@ def nms(boxes_xyxy, scores, keep, iou_threshold):
         check(lib.hgl_nms_large(ops._dev(boxes_xyxy, torch.int32, "boxes"), ops._dev(scores, torch.float32, "scores"),
                                 ops._dev(keep, torch.uint8, "keep"), K, float(iou_threshold), idx.data_ptr(),
                                 n.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "hgl_nms_large")
+    return idx, n
+
+
+def nms_segments(boxes_xyxy, scores, keep, offsets, max_len, iou_threshold):
+    """nms() for several candidate lists in one launch (hgl_nms_segments): list s = candidates offsets[s] .. offsets[s+1]
+    (offsets: int32 device tensor [n_seg + 1], ascending from 0; max_len: the longest list, <= 1024) -> (idx [K] int32: from
+    position offsets[s] on, the kept candidates of list s as indices INTO the list; n [n_seg] int32)."""
+    lib = _lib.load()
+    K, n_seg = boxes_xyxy.shape[0], offsets.shape[0] - 1
+    idx = torch.empty((K,), dtype=torch.int32, device=boxes_xyxy.device)
+    n = torch.empty((n_seg,), dtype=torch.int32, device=boxes_xyxy.device)
+    check(lib.hgl_nms_segments(ops._dev(boxes_xyxy, torch.int32, "boxes"), ops._dev(scores, torch.float32, "scores"),
+                               ops._dev(keep, torch.uint8, "keep"), ops._dev(offsets, torch.int32, "offsets"), n_seg, int(max_len),
+                               float(iou_threshold), idx.data_ptr(), n.data_ptr(), ops._stream()), "hgl_nms_segments")
     return idx, n
 
 
@@ -640,6 +682,10 @@ class SamAutomaticMaskGenerator:
         assert len(self.point_grids) >= crop_n_layers + 1, "one point grid per crop layer"
         self.crop_n_layers = crop_n_layers
         self.crop_overlap_ratio = crop_overlap_ratio
+        # The prompts of ONE image that go through the decoder together.  A group of images decodes many such batches in one
+        # launch (_propose_classes), but every batch-dependent choice of the decoder -- the key-range split of its token ->
+        # image attention (eight partial sums per prompt for batches of up to 128) -- follows this per-image batch, never the
+        # launch's total: a candidate does not depend on how many images share its launch.
         self.points_per_batch = points_per_batch
         self.pred_iou_thresh = pred_iou_thresh
         self.stability_score_thresh = stability_score_thresh
@@ -667,22 +713,74 @@ class SamAutomaticMaskGenerator:
         return self._propose_from_embedding(emb, H, W, nh, nw, layer_idx, crop_box, orig_size)
 
     def propose_batch(self, images, encoded_event=None):
-        """propose() for several whole images with ONE encoder pass over all of them (Sam.encode_batch); decoder,
-        post-processing and NMS per image.  Returns the list of propose() tuples.  encoded_event: a torch.cuda.Event that
-        is recorded behind the encoder pass (the boundary between the GEMM-bound and the latency-bound part of the stage)."""
+        """propose() for several whole images with ONE encoder pass over all of them (Sam.encode_batch) and, per class of
+        images of one size, ONE decoder call, ONE post-processing call and ONE NMS launch (_propose_classes).  Returns the
+        list of propose() tuples, bit for bit what propose() gives for each image alone up to the encoder's batching.
+        encoded_event: a torch.cuda.Event that is recorded behind the encoder pass (the boundary between the GEMM-bound
+        and the latency-bound part of the stage)."""
+        out = [None] * len(images)
+        pts_of = {}
+        for idxs, (masks, boxes, iou, stab, order, cnt), k3, (H, W) in self._propose_classes(images, encoded_event):
+            pts = pts_of.get((H, W))
+            if pts is None:
+                pts = pts_of[(H, W)] = np.repeat(self.point_grids[0] * np.array([[W, H]], dtype=np.float64), 3, axis=0)
+            for j, i in enumerate(idxs):
+                sl = slice(j * k3, (j + 1) * k3)
+                out[i] = (masks[sl], boxes[sl], iou[sl], stab[sl], order[sl], cnt[j:j + 1], pts)
+        return out
+
+    def _propose_classes(self, images, encoded_event=None):
+        """The proposal stage of a group up to the first NMS, by size class: the images are partitioned into classes of equal
+        (H, W) -- whose resized shape, prompt grid and post-processing geometry agree --, and a class goes through ONE decoder
+        call over all its prompts (Sam.decode_points_multi: whole images, at most 1024 prompts per launch sequence), ONE
+        post-processing call over its candidates and ONE segmented NMS launch (one workgroup per image).
+        points_per_batch keeps its meaning per IMAGE: it is the prompt batch the decoder's batch-dependent choices see (the
+        key-range split of the token -> image attention is taken from the prompts per image, never from the launch's
+        total), so every candidate is bit for bit what the image's own decoder call gives; an image whose grid needs
+        several such batches goes through the decoder alone, as in propose().
+        Returns [(image indices, (masks [n*k3,H,W] u8, boxes [n*k3,4] i32, iou [n*k3], stab [n*k3], order [n*k3] i32 -- per
+        image, indices into the image's k3 candidates --, counts [n] i32), k3, (H, W))]."""
         m = self.model
         sizes, resized = [], []
         for image in images:
             H, W = image.shape[:2]
             dev_img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image)).to(m.device)
-            sizes.append((H, W) + get_preprocess_shape(H, W, m.img_size))
+            sizes.append((int(H), int(W)) + get_preprocess_shape(H, W, m.img_size))
             resized.append(resize_longest_side(dev_img.contiguous(), m.img_size))
         emb = m.encode_batch(resized)
         if encoded_event is not None:
             encoded_event.record(torch.cuda.current_stream(m.device))
-        return [self._propose_from_embedding(emb[i], *sizes[i], 0, None, None) for i in range(len(images))]
+        npts = len(self.point_grids[0])
+        k3 = 3 * npts
+        classes = {}
+        for i, sz in enumerate(sizes):
+            classes.setdefault(sz, []).append(i)
+        out = []
+        for (H, W, nh, nw), idxs in classes.items():
+            # (the clean-up's and the post-processing's 32-bit pixel offsets bound the candidates of one call)
+            n_max = min(max(1, (2 ** 31 - 1) // (k3 * H * W)), 65535 // k3) if k3 <= 1024 and npts <= self.points_per_batch else 1
+            for c0 in range(0, len(idxs), n_max):
+                part = idxs[c0:c0 + n_max]
+                if len(part) == 1:
+                    c = self._propose_from_embedding(emb[part[0]], H, W, nh, nw, 0, None, None)
+                    out.append((part, c[:6], k3, (H, W)))
+                else:
+                    out.append((part, self._propose_class(emb, part, H, W, nh, nw), k3, (H, W)))
+        return out
 
-    def _propose_from_embedding(self, emb, H, W, nh, nw, layer_idx, crop_box, orig_size):
+    def _dev_const(self, key, make):
+        """small device tensors that depend on a group's shape only (index lists, offsets, tiled prompt grids): uploaded once"""
+        cache = self.__dict__.setdefault("_const_cache", {})
+        t = cache.get(key)
+        if t is None:
+            if len(cache) >= 256:
+                cache.clear()
+            t = cache[key] = make()
+        return t
+
+    def _prompt_grid(self, H, W, nh, nw, layer_idx):
+        """the point grid of a crop of H x W in crop coordinates (float64, host) and as the decoder's [npts, 2] fp32 device
+        tensor ((point in the resized frame + 0.5) / img_size)"""
         m = self.model
         pts = self.point_grids[layer_idx] * np.array([[W, H]], dtype=np.float64)   # automatic_mask_generator.py:240-241
         tp = pts.copy()
@@ -695,6 +793,34 @@ class SamAutomaticMaskGenerator:
             if len(cache) >= 64:
                 cache.clear()
             p01 = cache[key] = torch.from_numpy(((tp + 0.5) / float(m.img_size)).astype(np.float32)).to(m.device)
+        return pts, p01
+
+    def _propose_class(self, emb, idxs, H, W, nh, nw):
+        """decoder, post-processing and first NMS of the images idxs (rows of emb), all of size H x W, in one call each"""
+        m = self.model
+        dev = m.device
+        n = len(idxs)
+        pts, p01 = self._prompt_grid(H, W, nh, nw, 0)
+        npts = len(pts)
+        k3 = 3 * npts
+        if idxs == list(range(idxs[0], idxs[0] + n)):
+            e = emb[idxs[0]:idxs[0] + n]
+        else:
+            e = emb.index_select(0, self._dev_const(("rows",) + tuple(idxs), lambda: torch.tensor(idxs, dtype=torch.int64, device=dev)))
+        gate = float(self.pred_iou_thresh) if self.pred_iou_thresh > 0 and getattr(self, "iou_gate", True) else None
+        # (the call itself goes through whole images, at most 1024 prompts per launch sequence)
+        pk = self._dev_const(("p01", H, W, n), lambda: p01.repeat(n, 1).contiguous())
+        low, iou = m.decode_points_multi(e, pk, n, iou_gate=gate)
+        low, iou = low.flatten(0, 1), iou.flatten()
+        masks, boxes, stab, keep, _ = m.postprocess(low, iou, (nh, nw), (H, W), self.pred_iou_thresh,
+                                                    self.stability_score_thresh, self.stability_score_offset)
+        offs = self._dev_const(("offs", n, k3), lambda: torch.arange(0, (n + 1) * k3, k3, dtype=torch.int32, device=dev))
+        order, cnt = nms_segments(boxes, iou, keep, offs, k3, self.box_nms_thresh)
+        return masks, boxes, iou, stab, order, cnt
+
+    def _propose_from_embedding(self, emb, H, W, nh, nw, layer_idx, crop_box, orig_size):
+        m = self.model
+        pts, p01 = self._prompt_grid(H, W, nh, nw, layer_idx)
         lows, ious = [], []
         # the post-processing below drops every candidate whose prediction does not exceed pred_iou_thresh (when that is > 0:
         # automatic_mask_generator.py:287-291): prompts that fail with all three masks skip the decoder's upscaling
@@ -974,9 +1100,18 @@ class SamAutomaticMaskGenerator:
         st = _GroupState()
         st.cap = cap
         st.sizes = [tuple(int(v) for v in im.shape[:2]) for im in images]
-        st.cand = self.propose_batch(images, encoded_event)
+        st.cand = self._propose_classes(images, encoded_event)
         dev = self.model.device
-        st.n1_dev = torch.cat([c[5] for c in st.cand])
+        # (counts in image order: a class holds its images' counts side by side)
+        cnts = [c[1][5] for c in st.cand]
+        st.n1_dev = cnts[0] if len(cnts) == 1 else torch.cat(cnts)
+        perm = [i for c in st.cand for i in c[0]]
+        if perm != list(range(len(images))):
+            inv = [0] * len(perm)
+            for pos, i in enumerate(perm):
+                inv[i] = pos
+            st.n1_dev = st.n1_dev.index_select(0, self._dev_const(("rows",) + tuple(inv),
+                                                                  lambda: torch.tensor(inv, dtype=torch.int64, device=dev)))
         st.n1 = torch.empty(len(images), dtype=torch.int32).pin_memory()
         st.n1.copy_(st.n1_dev, non_blocking=True)
         # the fp16 range guard of the f16x3 mode rides on the same read-back: what the device had counted (any stream) when
@@ -988,10 +1123,32 @@ class SamAutomaticMaskGenerator:
         st.ev1.record(torch.cuda.current_stream(dev))
         return st
 
+    def _segment_index(self, counts, stride):
+        """Device index lists for "the first counts[j] entries of segment j" of a flat array whose segments lie `stride`
+        apart, from ONE pinned upload: (positions [total] i64, segment starts of every entry [total] i64, offsets of the
+        packed result [n + 1] i32)."""
+        total, n = int(sum(counts)), len(counts)
+        host = torch.empty(2 * total + n + 1, dtype=torch.int64, pin_memory=True)
+        h = host.numpy()
+        o = 0
+        h[2 * total] = 0
+        for j, c in enumerate(counts):
+            h[o:o + c] = np.arange(j * stride, j * stride + c)
+            h[total + o:total + o + c] = j * stride
+            o += c
+            h[2 * total + j + 1] = o
+        d = host.to(self.model.device, non_blocking=True)
+        return d[:total], d[total:2 * total], d[2 * total:].to(torch.int32)
+
     def group_cleanup(self, st):
-        """Stage B: waits for the counts of group_begin (host sync 1 of 2), gathers each image's survivors and runs
-        postprocess_small_regions' kernels on them (holes, islands, boxes, second NMS; automatic_mask_generator.py:324-372).
-        The second NMS counts leave in one copy again."""
+        """Stage B: waits for the counts of group_begin (host sync 1 of 2); per size class ONE gather of the survivors of all
+        its images, postprocess_small_regions' kernels on them (holes, islands, boxes: image by image, see below; the second
+        NMS: one segmented launch; automatic_mask_generator.py:324-372).  The second NMS counts leave in one copy again.
+        The clean-up passes stay one image per call, by measurement (profiles/group_tail_ab.json): alone on the device the two
+        passes over a group's 16 x 64 masks of 640 x 640 take 13.12 ms at one image per call, 11.44 at 2, 10.95 at 4 and
+        10.16 at 16, but beside the CLIP stream the step is SLOWER with the whole class per call (0.980 of the parent's time
+        against 0.975): its launches then hold the whole chip for milliseconds while the persistent GEMMs of the other stream
+        wait, and its union-find planes (8 bytes per pixel: 3.4 GB against one image's 210 MB) leave the last-level cache."""
         st.ev1.synchronize()
         if st.ovf is not None:
             st.overflow = int(st.ovf[0]) + int(st.ovf[1])
@@ -1002,60 +1159,99 @@ class SamAutomaticMaskGenerator:
         st.n1_list = n1
         st.stage = []
         n2_dev = []
-        for (masks, boxes, iou, stab, order, _n, _pts), n in zip(st.cand, n1):
-            if n == 0:
+        area = self.min_mask_region_area
+        for idxs, (masks, boxes, iou, stab, order, _cnt), k3, _hw in st.cand:
+            counts = [n1[i] for i in idxs]
+            total = sum(counts)
+            if total == 0:
                 st.stage.append(None)
-                n2_dev.append(torch.zeros(1, dtype=torch.int32, device=dev))
+                if area > 0:
+                    n2_dev.append(torch.zeros(len(idxs), dtype=torch.int32, device=dev))
                 continue
-            idx = order[:n].long()
-            m = masks.index_select(0, idx)
-            bx = boxes.index_select(0, idx)
-            if self.min_mask_region_area > 0:
-                m1, c1 = remove_small_regions(m, self.min_mask_region_area, "holes")
-                m2, c2, nb = remove_small_regions_boxes(m1, self.min_mask_region_area, "islands")
+            pos, base, offs = self._segment_index(counts, k3)
+            idx = order.index_select(0, pos).long()          # per image: indices into its k3 candidates, first NMS order
+            gidx = idx + base                                # the same as rows of the class's tensors
+            m = masks.index_select(0, gidx)
+            bx = boxes.index_select(0, gidx)
+            if area > 0:
+                m1, c1 = torch.empty_like(m), torch.empty((total,), dtype=torch.uint8, device=dev)
+                m2, c2 = torch.empty_like(m), torch.empty((total,), dtype=torch.uint8, device=dev)
+                nb = torch.empty((total, 4), dtype=torch.int32, device=dev)
+                o = 0
+                for c in counts:
+                    if c > 0:
+                        sl = slice(o, o + c)
+                        remove_small_regions(m[sl], area, "holes", out=(m1[sl], c1[sl]))
+                        remove_small_regions_boxes(m1[sl], area, "islands", out=(m2[sl], c2[sl], nb[sl]))
+                    o += c
                 unchanged = ((c1 | c2) == 0).to(torch.float32)           # score 1 for untouched masks
-                order2, n2 = nms(nb, unchanged, torch.ones(n, dtype=torch.uint8, device=dev),
-                                 max(self.box_nms_thresh, self.crop_nms_thresh))
-                st.stage.append((m2, nb, idx, order2, iou, stab))
+                order2, n2 = nms_segments(nb, unchanged, torch.ones(total, dtype=torch.uint8, device=dev), offs, max(counts),
+                                          max(self.box_nms_thresh, self.crop_nms_thresh))
+                st.stage.append((m2, nb, idx, gidx, order2, iou, stab, counts))
                 n2_dev.append(n2)
             else:
-                st.stage.append((m, bx, idx, None, iou, stab))
-                n2_dev.append(torch.full((1,), n, dtype=torch.int32, device=dev))
-        st.cand = None     # the candidate tensors (192 full-size masks per image) can go back to the allocator
+                st.stage.append((m, bx, idx, gidx, None, iou, stab, counts))
         st.n2 = None
-        if self.min_mask_region_area > 0:
+        if area > 0:
+            # (class order; group_finish reads them the same way)
             st.n2 = torch.empty(len(n1), dtype=torch.int32).pin_memory()
-            st.n2.copy_(torch.cat(n2_dev), non_blocking=True)
+            st.n2.copy_(n2_dev[0] if len(n2_dev) == 1 else torch.cat(n2_dev), non_blocking=True)
             st.ev2 = torch.cuda.Event()
             st.ev2.record(torch.cuda.current_stream(dev))
+        st.cand = [c[0] for c in st.cand]     # the candidate tensors (192 full-size masks per image) can go back to the allocator
         return st
 
     def group_finish(self, st):
-        """Stage C: host sync 2 of 2 (none without the small-region clean-up), the final gathers.  Returns per image what
-        generate_device returns: (masks [n,H,W] uint8, boxes_xywh [n,4] int64, iou [n], stability [n], cand [n] int64);
-        n may be 0."""
+        """Stage C: host sync 2 of 2 (none without the small-region clean-up), the final gathers, one per size class.  Returns
+        per image what generate_device returns: (masks [n,H,W] uint8, boxes_xywh [n,4] int64, iou [n], stability [n],
+        cand [n] int64); n may be 0."""
+        n2_all = None
         if st.n2 is not None:
             st.ev2.synchronize()
-            n2 = [int(v) for v in st.n2.tolist()]
-        else:
-            n2 = list(st.n1_list)
-        out = []
+            n2_all = [int(v) for v in st.n2.tolist()]
+        out = [None] * len(st.sizes)
         dev = self.model.device
-        for stg, n, hw in zip(st.stage, n2, st.sizes):
-            if stg is None or n == 0:
-                e = torch.empty
-                out.append((e((0,) + hw, dtype=torch.uint8, device=dev), e((0, 4), dtype=torch.int64, device=dev),
-                            e((0,), device=dev), e((0,), device=dev), e((0,), dtype=torch.int64, device=dev)))
-                continue
-            m, bx, idx, order2, iou, stab = stg
-            if order2 is not None:
-                k = order2[:n].long()
-                m, bx, idx = m.index_select(0, k), bx.index_select(0, k), idx.index_select(0, k)
-            b = bx.long()
-            xywh = torch.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1)
-            out.append((m, xywh, iou.index_select(0, idx), stab.index_select(0, idx), idx))
+        e = torch.empty
+        k0 = 0
+        for idxs, stg in zip(st.cand, st.stage):
+            n2 = n2_all[k0:k0 + len(idxs)] if n2_all is not None else [st.n1_list[i] for i in idxs]
+            k0 += len(idxs)
+            if stg is not None and sum(n2) > 0:
+                m, bx, idx, gidx, order2, iou, stab, counts = stg
+                if order2 is not None:
+                    pos, base, _ = self._packed_index(n2, counts)
+                    k = order2.index_select(0, pos).long() + base
+                    m, bx, idx, gidx = m.index_select(0, k), bx.index_select(0, k), idx.index_select(0, k), gidx.index_select(0, k)
+                b = bx.long()
+                xywh = torch.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1)
+                iou, stab = iou.index_select(0, gidx), stab.index_select(0, gidx)
+            o = 0
+            for i, n in zip(idxs, n2):
+                if stg is None or n == 0:
+                    hw = st.sizes[i]
+                    out[i] = (e((0,) + hw, dtype=torch.uint8, device=dev), e((0, 4), dtype=torch.int64, device=dev),
+                              e((0,), device=dev), e((0,), device=dev), e((0,), dtype=torch.int64, device=dev))
+                    continue
+                sl = slice(o, o + n)
+                out[i] = (m[sl], xywh[sl], iou[sl], stab[sl], idx[sl])
+                o += n
         st.stage = None
         return out
+
+    def _packed_index(self, counts, seg_lens):
+        """_segment_index for segments packed back to back (segment j starts at sum(seg_lens[:j])): the first counts[j]
+        entries of each -> (positions [total] i64, segment starts [total] i64, None)"""
+        total = int(sum(counts))
+        host = torch.empty(2 * total, dtype=torch.int64, pin_memory=True)
+        h = host.numpy()
+        o = s0 = 0
+        for c, ln in zip(counts, seg_lens):
+            h[o:o + c] = np.arange(s0, s0 + c)
+            h[total + o:total + o + c] = s0
+            o += c
+            s0 += ln
+        d = host.to(self.model.device, non_blocking=True)
+        return d[:total], d[total:], None
 
     def generate_group(self, images, cap=None):
         """generate_device() for several images with one encoder pass and two host syncs in all (one without clean-up)."""
@@ -1148,12 +1344,17 @@ def coco_encode_rle(uncompressed_rle):
     return {"size": [h, w], "counts": buf.raw[:n.value].decode("utf-8")}
 
 
-def remove_small_regions(masks, area_thresh, mode):
-    """utils/amg.py:267-291 for a batch [n,H,W] uint8 on the device -> (new masks, changed [n] uint8)."""
+def remove_small_regions(masks, area_thresh, mode, out=None):
+    """utils/amg.py:267-291 for a batch [n,H,W] uint8 on the device -> (new masks, changed [n] uint8).
+    out: (masks, changed) to write into (contiguous slices of a group's tensors) instead of fresh ones."""
     lib = _lib.load()
     n, H, W = masks.shape
-    out = torch.empty_like(masks)
-    changed = torch.empty((n,), dtype=torch.uint8, device=masks.device)
+    if out is not None:
+        out, changed = out
+        ops._dev(out, torch.uint8, "out"), ops._dev(changed, torch.uint8, "changed")
+    else:
+        out = torch.empty_like(masks)
+        changed = torch.empty((n,), dtype=torch.uint8, device=masks.device)
     need = lib.hgl_remove_small_regions_workspace_bytes(n, H, W)
     ws = ops.workspace(need, masks.device, "sam_ccl")
     check(lib.hgl_remove_small_regions(ops._dev(masks, torch.uint8, "masks"), n, H, W, int(area_thresh),
@@ -1162,14 +1363,18 @@ def remove_small_regions(masks, area_thresh, mode):
     return out, changed
 
 
-def remove_small_regions_boxes(masks, area_thresh, mode):
+def remove_small_regions_boxes(masks, area_thresh, mode, out=None):
     """remove_small_regions with the boxes of the masks it writes (batched_mask_to_box, utils/amg.py:303-346) out of the
-    same pass -> (new masks, changed [n] uint8, int32 XYXY [n,4])."""
+    same pass -> (new masks, changed [n] uint8, int32 XYXY [n,4]).  out: (masks, changed, boxes) to write into."""
     lib = _lib.load()
     n, H, W = masks.shape
-    out = torch.empty_like(masks)
-    changed = torch.empty((n,), dtype=torch.uint8, device=masks.device)
-    boxes = torch.empty((n, 4), dtype=torch.int32, device=masks.device)
+    if out is not None:
+        out, changed, boxes = out
+        ops._dev(out, torch.uint8, "out"), ops._dev(changed, torch.uint8, "changed"), ops._dev(boxes, torch.int32, "boxes")
+    else:
+        out = torch.empty_like(masks)
+        changed = torch.empty((n,), dtype=torch.uint8, device=masks.device)
+        boxes = torch.empty((n, 4), dtype=torch.int32, device=masks.device)
     need = lib.hgl_remove_small_regions_workspace_bytes(n, H, W)
     ws = ops.workspace(need, masks.device, "sam_ccl")
     check(lib.hgl_remove_small_regions_boxes(ops._dev(masks, torch.uint8, "masks"), n, H, W, int(area_thresh),

@@ -516,6 +516,21 @@ int hgl_sam_decode_points(const HglSamDecoderW* w, const float* emb, const float
  * acts in the fused upscaling of the split-fp16 mode; elsewhere every prompt is upscaled. */
 int hgl_sam_decode_points_gated(const HglSamDecoderW* w, const float* emb, const float* points01, int P, float iou_gate,
                                 float* low_res, float* iou_pred, void* workspace, size_t workspace_bytes, void* stream);
+/* The prompts of SEVERAL images in one call (a group of images through the automatic generator): emb [n_img, grid*grid, C],
+ * points01 [n_img * ppi, 2], prompt p belongs to image p / ppi -> low_res [n_img*ppi,3,4*grid,4*grid], iou [n_img*ppi,3].
+ * Every prompt's rows are bit for bit those of hgl_sam_decode_points(_gated) on its image's own ppi prompts: only the first
+ * decoder layer knows that prompts share image tokens (it addresses the rows of image p / ppi), and every choice that
+ * depends on the batch -- the key-range split of the token -> image attention -- is taken from ppi, never from the
+ * launch's total.  With the fused decoder stages (split-fp16 mode, the ViT decoder geometry) the prompts go through one
+ * launch sequence per 1024 prompts (whole images: within that bound no kernel choice on the token side depends on the row
+ * count); elsewhere the call runs the one-image path image by image.  n_img * ppi <= 65535;
+ * workspace >= hgl_sam_decode_multi_workspace_bytes(w, n_img, ppi).  n_img = 1 is hgl_sam_decode_points(_gated). */
+size_t hgl_sam_decode_multi_workspace_bytes(const HglSamDecoderW* w, int n_img, int ppi);
+int hgl_sam_decode_points_multi(const HglSamDecoderW* w, const float* emb, const float* points01, int n_img, int ppi,
+                                float* low_res, float* iou_pred, void* workspace, size_t workspace_bytes, void* stream);
+int hgl_sam_decode_points_multi_gated(const HglSamDecoderW* w, const float* emb, const float* points01, int n_img, int ppi,
+                                      float iou_gate, float* low_res, float* iou_pred, void* workspace, size_t workspace_bytes,
+                                      void* stream);
 /* The same for the other prompt kinds of SamPredictor.predict_torch (predictor.py:169-243; PromptEncoder._embed_points /
  * _embed_boxes / _embed_masks, prompt_encoder.py:73-127): n_sparse = 2 .. 11 sparse tokens per prompt, coords01
  * [P,n_sparse,2] ((coordinate + 0.5) / img_size, computed by the caller in the dtype the reference would use), labels
@@ -577,6 +592,14 @@ int hgl_sam_postprocess(const float* low_res, const float* iou_pred, int K, int 
  * out_idx [K] receives the kept candidate indices in order, *out_n their count (device memory). */
 int hgl_nms(const int32_t* boxes_xyxy, const float* scores, const uint8_t* keep, int K, float iou_threshold,
             int32_t* out_idx, int32_t* out_n, void* stream);
+
+/* hgl_nms for n_seg candidate lists in one launch (the images of a group): list s = candidates offsets[s] .. offsets[s+1]
+ * (offsets [n_seg + 1] int32, device memory, ascending from 0; a list may be empty), one workgroup per list, each list
+ * exactly as hgl_nms treats it alone.  out_idx [offsets[n_seg]] receives, from position offsets[s] on, the kept candidates
+ * of list s in order as indices INTO the list; out_n [n_seg] their counts.  max_len: the longest list, <= 1024 (lists of
+ * more than 512 candidates add a second launch).  boxes_xyxy 16-byte aligned. */
+int hgl_nms_segments(const int32_t* boxes_xyxy, const float* scores, const uint8_t* keep, const int32_t* offsets, int n_seg,
+                     int max_len, float iou_threshold, int32_t* out_idx, int32_t* out_n, void* stream);
 
 /* remove_small_regions (utils/amg.py:267-291) for a batch of masks on the device: 8-connected
  * components of the mask (holes=0: "islands") or of its complement (holes=1), components with
