@@ -497,20 +497,15 @@ class HybridGLPipeline:
                     self._stage_mark("sam_begin")
                     imgs = [units[i][0].sam_img for i in fresh]
                     if self.use_sam_masks:
-                        if getattr(gen, "crop_n_layers", 0) > 0:
-                            # PhraseCut configuration (crop layers): the same begin / finish split -- every crop of every image
-                            # of the group is enqueued here without a wait, the three count read-backs come after the CLIP
-                            # stage of the previous group has been enqueued
-                            if self.stagger == "decoder" and not serial:
-                                ev_enc = torch.cuda.Event()
-                            state = ("crops", gen.crops_begin(imgs, ev_enc))
-                        else:
-                            # stagger = "decoder": the CLIP stage of the previous group starts when THIS group's encoder pass
-                            # is through, so its large GEMMs run beside the latency-bound rest of the proposal stage (decoder,
-                            # post-processing, NMS, clean-up) instead of beside the encoder's equally matrix-bound GEMMs
-                            if self.stagger == "decoder" and not serial:
-                                ev_enc = torch.cuda.Event()
-                            state = ("group", gen.group_begin(imgs, proposal_cap, ev_enc))
+                        # stagger = "decoder": the CLIP stage of the previous group starts when THIS group's encoder pass
+                        # is through, so its large GEMMs run beside the latency-bound rest of the proposal stage (decoder,
+                        # post-processing, NMS, clean-up) instead of beside the encoder's equally matrix-bound GEMMs
+                        if self.stagger == "decoder" and not serial:
+                            ev_enc = torch.cuda.Event()
+                        # everything of the group up to its first count read-back is enqueued here without a wait (with crop
+                        # layers, the PhraseCut configuration: every crop of every image); the read-backs come after the CLIP
+                        # stage of the previous group has been enqueued
+                        state = gen.group_begin(imgs, proposal_cap, ev_enc)
                     else:    # proposal kernels only; their output is not consumed (synthetic benchmark, seeded masks)
                         self.last_proposals = gen.propose_batch(imgs)[-1]
             if pending is not None:
@@ -521,28 +516,18 @@ class HybridGLPipeline:
             props, ready = None, None
             if state is not None:
                 with torch.cuda.stream(s_sam):
-                    if state[0] == "group":
-                        stc = gen.group_cleanup(state[1])
-                        if stc.overflow:
-                            # fail at THIS group, not in metrics() after the whole dataset: the counter rode on the group's
-                            # count read-back (everything the device had finished by then, on any stream).  The counters are
-                            # process-global: cleared here, or every later run() of the process -- the f32 rerun this message
-                            # recommends included -- would trip over the same count at its first group
-                            ops.split_overflow_count(reset=True)
-                            raise ops.SplitOverflow(
-                                f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode by group {self.groups_run} of the "
-                                f"loop ({stc.overflow} GPU threads saw one; refs up to dataset position {units[-1][-1].index}): the "
-                                "results from the previous group on contain inf / NaN; rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
-                        got = [p[:2] for p in gen.group_finish(stc)]
-                    else:
-                        stc = gen.crops_mid(state[1])
-                        if stc.overflow:
-                            ops.split_overflow_count(reset=True)
-                            raise ops.SplitOverflow(
-                                f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode by group {self.groups_run} of the "
-                                f"loop ({stc.overflow} GPU threads saw one): rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
-                        got = [tuple(t[:proposal_cap] if proposal_cap is not None else t for t in p[:2])
-                               for p in gen.crops_finish(gen.crops_post(stc))]
+                    stc = gen.group_cleanup(state)
+                    if stc.overflow:
+                        # fail at THIS group, not in metrics() after the whole dataset: the counter rode on the group's
+                        # count read-back (everything the device had finished by then, on any stream).  The counters are
+                        # process-global: cleared here, or every later run() of the process -- the f32 rerun this message
+                        # recommends included -- would trip over the same count at its first group
+                        ops.split_overflow_count(reset=True)
+                        raise ops.SplitOverflow(
+                            f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode by group {self.groups_run} of the "
+                            f"loop ({stc.overflow} GPU threads saw one; refs up to dataset position {units[-1][-1].index}): the "
+                            "results from the previous group on contain inf / NaN; rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
+                    got = [p[:2] for p in gen.group_finish(stc)]
                     ready = torch.cuda.Event()
                     ready.record(s_sam)
                     self._stage_mark("sam_end")

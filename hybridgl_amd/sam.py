@@ -28,6 +28,17 @@ def _dev(a, device):
     return t.contiguous().to(device)
 
 
+def _image_on(image, device):
+    """an image [H,W,3] uint8, numpy or tensor, as a tensor on the device"""
+    return image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image)).to(device)
+
+
+def _xywh(boxes_xyxy):
+    """box_xyxy_to_xywh (utils/amg.py:255-259) as int64"""
+    b = boxes_xyxy.long()
+    return torch.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1)
+
+
 def load_sam_state_dict(path):
     """`torch.load` of the released checkpoint (build_sam.py:103-106)."""
     sd = torch.load(path, map_location="cpu")
@@ -238,78 +249,55 @@ class Sam:
                                        ops._stream()), "hgl_sam_encode_batch")
         return emb
 
+    def _decode(self, entry, P, ws_query, ws_args, *args):
+        """The outputs and the workspace of P prompts, and the call of one decoder entry point, all of which end in
+        (..., low_res, iou, workspace, workspace_bytes, stream) behind their own arguments args; ws_query(dec_w, *ws_args):
+        the entry point's workspace size -> (low_res [P,3,4g,4g], iou [P,3])."""
+        lib = _lib.load()
+        ops.use_precision(self.precision)
+        ws = ops.workspace(getattr(lib, ws_query)(C.byref(self.dec_w), *ws_args), self.device, "sam_decode")
+        g4 = 4 * self.grid
+        low = torch.empty((P, 3, g4, g4), dtype=torch.float32, device=self.device)
+        iou = torch.empty((P, 3), dtype=torch.float32, device=self.device)
+        check(getattr(lib, entry)(C.byref(self.dec_w), *args, low.data_ptr(), iou.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  ops._stream()), entry)
+        return low, iou
+
     def decode_points(self, emb, points01, iou_gate=None):
         """points01: [P,2] fp32 device ((point+0.5)/img_size) -> (low_res [P,3,4g,4g], iou [P,3]).
         iou_gate: a pred_iou_thresh the caller will filter with (automatic_mask_generator.py:287-291): prompts none of whose
         three predictions exceeds it skip the output upscaling -- their rows of low_res are unwritten memory, which the caller's
         filter never reads (hgl_sam_decode_points_gated)."""
-        lib = _lib.load()
-        ops.use_precision(self.precision)
-        P = points01.shape[0]
-        need = lib.hgl_sam_decode_workspace_bytes(C.byref(self.dec_w), P)
-        ws = ops.workspace(need, self.device, "sam_decode")
-        g4 = 4 * self.grid
-        low = torch.empty((P, 3, g4, g4), dtype=torch.float32, device=self.device)
-        iou = torch.empty((P, 3), dtype=torch.float32, device=self.device)
-        if iou_gate is not None:
-            check(lib.hgl_sam_decode_points_gated(C.byref(self.dec_w), ops._dev(emb, torch.float32, "emb"),
-                                                  ops._dev(points01, torch.float32, "points01"), P, float(iou_gate), low.data_ptr(),
-                                                  iou.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
-                  "hgl_sam_decode_points_gated")
-            return low, iou
-        check(lib.hgl_sam_decode_points(C.byref(self.dec_w), ops._dev(emb, torch.float32, "emb"),
-                                        ops._dev(points01, torch.float32, "points01"), P, low.data_ptr(),
-                                        iou.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
-              "hgl_sam_decode_points")
-        return low, iou
+        P = int(points01.shape[0])
+        gated = iou_gate is not None
+        return self._decode("hgl_sam_decode_points_gated" if gated else "hgl_sam_decode_points", P,
+                            "hgl_sam_decode_workspace_bytes", (P,), ops._dev(emb, torch.float32, "emb"),
+                            ops._dev(points01, torch.float32, "points01"), P, *((float(iou_gate),) if gated else ()))
 
     def decode_points_multi(self, emb, points01, n_img, iou_gate=None):
         """decode_points for the prompts of SEVERAL images in one call: emb [n_img, g*g, C], points01 [n_img * ppi, 2], prompt p
         belongs to image p // ppi -> (low_res [n_img*ppi,3,4g,4g], iou [n_img*ppi,3]); every prompt's rows are bit for bit
         those of decode_points on its image's own ppi prompts (hgl_sam_decode_points_multi)."""
-        lib = _lib.load()
-        ops.use_precision(self.precision)
         P = int(points01.shape[0])
         n_img = int(n_img)
         if n_img < 1 or P % n_img or tuple(emb.shape[:1]) != (n_img,):
             raise ValueError(f"{P} prompts / embeddings {tuple(emb.shape)} for {n_img} images")
         ppi = P // n_img
-        need = lib.hgl_sam_decode_multi_workspace_bytes(C.byref(self.dec_w), n_img, ppi)
-        ws = ops.workspace(need, self.device, "sam_decode")
-        g4 = 4 * self.grid
-        low = torch.empty((P, 3, g4, g4), dtype=torch.float32, device=self.device)
-        iou = torch.empty((P, 3), dtype=torch.float32, device=self.device)
-        if iou_gate is not None:
-            check(lib.hgl_sam_decode_points_multi_gated(C.byref(self.dec_w), ops._dev(emb, torch.float32, "emb"),
-                                                        ops._dev(points01, torch.float32, "points01"), n_img, ppi, float(iou_gate),
-                                                        low.data_ptr(), iou.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
-                  "hgl_sam_decode_points_multi_gated")
-            return low, iou
-        check(lib.hgl_sam_decode_points_multi(C.byref(self.dec_w), ops._dev(emb, torch.float32, "emb"),
-                                              ops._dev(points01, torch.float32, "points01"), n_img, ppi, low.data_ptr(),
-                                              iou.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
-              "hgl_sam_decode_points_multi")
-        return low, iou
+        gated = iou_gate is not None
+        return self._decode("hgl_sam_decode_points_multi_gated" if gated else "hgl_sam_decode_points_multi", P,
+                            "hgl_sam_decode_multi_workspace_bytes", (n_img, ppi), ops._dev(emb, torch.float32, "emb"),
+                            ops._dev(points01, torch.float32, "points01"), n_img, ppi, *((float(iou_gate),) if gated else ()))
 
     def decode_prompts(self, emb, coords01, labels, first_mask=1, dense=None):
         """prompts of two or three sparse tokens (prompt_encoder.py:73-101): coords01 [P,n,2] fp32 device
         ((coordinate + 0.5) / img_size), labels [P,n] int32 (-1 padding, 0 / 1 background / foreground point, 2 / 3 box
         corners); dense: None or [P, g*g, C] from embed_masks; first_mask 1 -> mask tokens 1..3 (multimask), 0 -> tokens 0..2
         (column 0 = the single-mask output) -> (low_res [P,3,4g,4g], iou [P,3])."""
-        lib = _lib.load()
-        ops.use_precision(self.precision)
         P, n = int(coords01.shape[0]), int(coords01.shape[1])
-        need = lib.hgl_sam_decode_workspace_bytes(C.byref(self.dec_w), P)
-        ws = ops.workspace(need, self.device, "sam_decode")
-        g4 = 4 * self.grid
-        low = torch.empty((P, 3, g4, g4), dtype=torch.float32, device=self.device)
-        iou = torch.empty((P, 3), dtype=torch.float32, device=self.device)
-        check(lib.hgl_sam_decode_prompts(C.byref(self.dec_w), ops._dev(emb, torch.float32, "emb"),
-                                         ops._dev(coords01, torch.float32, "coords01"), ops._dev(labels, torch.int32, "labels"), n,
-                                         None if dense is None else ops._dev(dense, torch.float32, "dense"),
-                                         int(first_mask), P, low.data_ptr(), iou.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         ops._stream()), "hgl_sam_decode_prompts")
-        return low, iou
+        return self._decode("hgl_sam_decode_prompts", P, "hgl_sam_decode_workspace_bytes", (P,),
+                            ops._dev(emb, torch.float32, "emb"), ops._dev(coords01, torch.float32, "coords01"),
+                            ops._dev(labels, torch.int32, "labels"), n,
+                            None if dense is None else ops._dev(dense, torch.float32, "dense"), int(first_mask), P)
 
     def embed_masks(self, mask_input):
         """PromptEncoder._embed_masks (prompt_encoder.py:103-106): [P,1,4g,4g] fp32 device -> dense rows [P, g*g, C]"""
@@ -349,21 +337,16 @@ class Sam:
 
 def nms(boxes_xyxy, scores, keep, iou_threshold):
     """Device NMS -> (idx [K] int32, n [1] int32), both on the device.  K <= 1024: one workgroup; larger K
-    (dense grids, crop layers): the three-pass bit-matrix kernels, same semantics."""
+    (dense grids, crop layers): the three-pass bit-matrix kernels (nms_large), same semantics."""
     lib = _lib.load()
     K = boxes_xyxy.shape[0]
+    if K > 1024:
+        return nms_large(boxes_xyxy, scores, keep, iou_threshold)
     idx = torch.empty((K,), dtype=torch.int32, device=boxes_xyxy.device)
     n = torch.empty((1,), dtype=torch.int32, device=boxes_xyxy.device)
-    if K <= 1024:
-        check(lib.hgl_nms(ops._dev(boxes_xyxy, torch.int32, "boxes"), ops._dev(scores, torch.float32, "scores"),
-                          ops._dev(keep, torch.uint8, "keep"), K, float(iou_threshold), idx.data_ptr(), n.data_ptr(),
-                          ops._stream()), "hgl_nms")
-    else:
-        need = lib.hgl_nms_large_workspace_bytes(K)
-        ws = ops.workspace(need, boxes_xyxy.device, "nms_large")
-        check(lib.hgl_nms_large(ops._dev(boxes_xyxy, torch.int32, "boxes"), ops._dev(scores, torch.float32, "scores"),
-                                ops._dev(keep, torch.uint8, "keep"), K, float(iou_threshold), idx.data_ptr(),
-                                n.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "hgl_nms_large")
+    check(lib.hgl_nms(ops._dev(boxes_xyxy, torch.int32, "boxes"), ops._dev(scores, torch.float32, "scores"),
+                      ops._dev(keep, torch.uint8, "keep"), K, float(iou_threshold), idx.data_ptr(), n.data_ptr(),
+                      ops._stream()), "hgl_nms")
     return idx, n
 
 
@@ -382,7 +365,7 @@ def nms_segments(boxes_xyxy, scores, keep, offsets, max_len, iou_threshold):
 
 
 def nms_large(boxes_xyxy, scores, keep, iou_threshold):
-    """hgl_nms_large regardless of K (tests)."""
+    """hgl_nms_large regardless of K: nms() above 1024 candidates (and the tests below that)."""
     lib = _lib.load()
     K = boxes_xyxy.shape[0]
     idx = torch.empty((K,), dtype=torch.int32, device=boxes_xyxy.device)
@@ -522,8 +505,7 @@ class ResizeLongestSide:
         self.target_length = target_length
 
     def apply_image(self, image):
-        dev = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image)).cuda()
-        return resize_longest_side(dev.contiguous(), self.target_length)
+        return resize_longest_side(_image_on(image, "cuda").contiguous(), self.target_length)
 
     def apply_coords(self, coords, original_size):
         """utils/transforms.py:33-45 (float64, as numpy)."""
@@ -561,7 +543,7 @@ class SamPredictor:
 
     def set_image(self, image, image_format="RGB"):
         assert image_format in ("RGB", "BGR"), f"image_format must be in ['RGB', 'BGR'], is {image_format}."
-        img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image)).to(self.device)
+        img = _image_on(image, self.device)
         if image_format != self.model.image_format:
             img = img.flip(-1)
         self.reset_image()
@@ -657,13 +639,15 @@ class SamPredictor:
 
 class _GroupState:
     """a group of images on its way through SamAutomaticMaskGenerator.group_begin / group_cleanup / group_finish"""
-    __slots__ = ("sizes", "cap", "cand", "n1_dev", "n1", "ev1", "n1_list", "stage", "n2", "ev2", "ovf", "overflow")
+    __slots__ = ("sizes", "crops", "cap", "cand", "n1", "ev1", "ovf", "overflow", "n1_list", "stage", "n2", "ev2")
 
 
 class SamAutomaticMaskGenerator:
-    """automatic_mask_generator.py:35-372: the Hybridgl_main.py:67-73 configuration (one crop, 8x8 points) runs
-    entirely on the device with two host syncs; crop layers / dense grids (Hybridgl_main_PhraseCut.py) add one
-    sync per crop (its survivor count) and the cross-crop NMS."""
+    """automatic_mask_generator.py:35-372.  Proposals go from the decoder's candidates to the final records through ONE tail,
+    that of a group of images (group_begin / group_cleanup / group_finish); an image with crop layers is a group of one,
+    generate_device the same steps with its two counts read where they are needed.  The Hybridgl_main.py:67-73
+    configuration (one crop, 8x8 points) reads two counts per GROUP back (one without the small-region clean-up), crop
+    layers / dense grids (Hybridgl_main_PhraseCut.py) three."""
 
     def __init__(self, model, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.88,
                  stability_score_thresh=0.95, stability_score_offset=1.0, box_nms_thresh=0.7, crop_n_layers=0,
@@ -693,6 +677,74 @@ class SamAutomaticMaskGenerator:
         self.box_nms_thresh = box_nms_thresh
         self.crop_nms_thresh = crop_nms_thresh
         self.min_mask_region_area = min_mask_region_area
+        # the fifth tensor of a finished image names every survivor's origin: crop * source_stride + candidate of that crop
+        self.source_stride = 3 * max(len(g) for g in self.point_grids)
+
+    # ---- small pieces every path shares ---------------------------------------------------------
+    def _points(self, H, W, layer_idx=0):
+        """the prompt point of every candidate of a crop of H x W, in crop coordinates: [3 * points, 2] float64 (host)"""
+        return np.repeat(self.point_grids[layer_idx] * np.array([[W, H]], dtype=np.float64), 3, axis=0)
+
+    def _gate(self):
+        """The post-processing drops every candidate whose prediction does not exceed pred_iou_thresh (when that is > 0:
+        automatic_mask_generator.py:287-291): prompts that fail with all three masks skip the decoder's upscaling."""
+        return float(self.pred_iou_thresh) if self.pred_iou_thresh > 0 and getattr(self, "iou_gate", True) else None
+
+    def _empty(self, H, W):
+        """the tensors of an image without a survivor"""
+        dev, e = self.model.device, torch.empty
+        return (e((0, H, W), dtype=torch.uint8, device=dev), e((0, 4), dtype=torch.int64, device=dev),
+                e((0,), device=dev), e((0,), device=dev), e((0,), dtype=torch.int64, device=dev))
+
+    def _read_back(self, counts, overflow=False):
+        """A device tensor of counts on its way to the host, nothing waited for: (pinned copy, the event behind it, None).
+        overflow: the fp16 range guard of the f16x3 mode rides on the same read-back -- the third element is the pinned pair
+        of counters, what the device had counted (any stream) when this stream got here: the caller stops at this group
+        instead of finding out at the end of the dataset."""
+        host = torch.empty(counts.shape[0], dtype=torch.int32).pin_memory()
+        host.copy_(counts, non_blocking=True)
+        ovf = None
+        if overflow:
+            ovf = torch.zeros(2, dtype=torch.int32).pin_memory()
+            ops.split_overflow_peek(ovf)     # (the counters are process-wide: the CLIP / GEM models of the loop may be f16x3 when this one is not)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.model.device))
+        return host, ev, ovf
+
+    def _cleanup(self, m, counts, offs=None):
+        """postprocess_small_regions (automatic_mask_generator.py:324-372) on the device, without its read-back: m [total,H,W]
+        uint8, the masks of one or several images packed image by image, counts their number per image.  Holes, then islands
+        with the boxes of what remains, one image per call into slices of the outputs (by measurement, see group_cleanup);
+        untouched masks score 1 in the NMS at max(box_nms_thresh, crop_nms_thresh) that follows.  offs (int32 device tensor
+        [len(counts) + 1], the packed offsets): ONE segmented launch, a list per image of at most 1024; None: the masks are ONE
+        list of any length.  -> (masks, boxes XYXY i32, order [total] i32, n [len(counts)] i32)"""
+        area, total, dev = self.min_mask_region_area, m.shape[0], m.device
+        m1, c1 = torch.empty_like(m), torch.empty((total,), dtype=torch.uint8, device=dev)
+        m2, c2 = torch.empty_like(m), torch.empty((total,), dtype=torch.uint8, device=dev)
+        nb = torch.empty((total, 4), dtype=torch.int32, device=dev)
+        o = 0
+        for c in counts:
+            if c > 0:
+                sl = slice(o, o + c)
+                remove_small_regions(m[sl], area, "holes", out=(m1[sl], c1[sl]))
+                remove_small_regions_boxes(m1[sl], area, "islands", out=(m2[sl], c2[sl], nb[sl]))
+            o += c
+        unchanged = ((c1 | c2) == 0).to(torch.float32)           # score 1 for untouched masks
+        keep = torch.ones(total, dtype=torch.uint8, device=dev)
+        thresh = max(self.box_nms_thresh, self.crop_nms_thresh)
+        if offs is not None and max(counts) <= 1024:
+            order, n = nms_segments(nb, unchanged, keep, offs, max(counts), thresh)
+        else:
+            assert len(counts) == 1, "more than 1024 survivors of one image: the segmented NMS does not take them"
+            order, n = nms(nb, unchanged, keep, thresh)
+        return m2, nb, order, n
+
+    def cleanup_fixed(self, m):
+        """postprocess_small_regions kernels on a fixed batch of masks [n,H,W] uint8 without reading any
+        count back: holes, islands, boxes, second NMS (its order is left on the device)."""
+        if self.min_mask_region_area <= 0:
+            return m, mask_boxes(m)
+        return self._cleanup(m, [m.shape[0]])[:2]
 
     # ---- device part: everything up to and including the first NMS, no host sync -----------
     def propose(self, image, resized=None, layer_idx=0, crop_box=None, orig_size=None):
@@ -707,8 +759,7 @@ class SamAutomaticMaskGenerator:
         nh, nw = get_preprocess_shape(H, W, m.img_size)
         if resized is None:
             # ResizeLongestSide.apply_image (utils/transforms.py:26-31): Pillow's bilinear resampler, bit-exact, on the device
-            dev_img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image)).to(m.device)
-            resized = resize_longest_side(dev_img.contiguous(), m.img_size)
+            resized = resize_longest_side(_image_on(image, m.device).contiguous(), m.img_size)
         emb = m.encode(resized)
         return self._propose_from_embedding(emb, H, W, nh, nw, layer_idx, crop_box, orig_size)
 
@@ -719,11 +770,8 @@ class SamAutomaticMaskGenerator:
         encoded_event: a torch.cuda.Event that is recorded behind the encoder pass (the boundary between the GEMM-bound
         and the latency-bound part of the stage)."""
         out = [None] * len(images)
-        pts_of = {}
         for idxs, (masks, boxes, iou, stab, order, cnt), k3, (H, W) in self._propose_classes(images, encoded_event):
-            pts = pts_of.get((H, W))
-            if pts is None:
-                pts = pts_of[(H, W)] = np.repeat(self.point_grids[0] * np.array([[W, H]], dtype=np.float64), 3, axis=0)
+            pts = self._points(H, W)
             for j, i in enumerate(idxs):
                 sl = slice(j * k3, (j + 1) * k3)
                 out[i] = (masks[sl], boxes[sl], iou[sl], stab[sl], order[sl], cnt[j:j + 1], pts)
@@ -744,9 +792,8 @@ class SamAutomaticMaskGenerator:
         sizes, resized = [], []
         for image in images:
             H, W = image.shape[:2]
-            dev_img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image)).to(m.device)
             sizes.append((int(H), int(W)) + get_preprocess_shape(H, W, m.img_size))
-            resized.append(resize_longest_side(dev_img.contiguous(), m.img_size))
+            resized.append(resize_longest_side(_image_on(image, m.device).contiguous(), m.img_size))
         emb = m.encode_batch(resized)
         if encoded_event is not None:
             encoded_event.record(torch.cuda.current_stream(m.device))
@@ -807,10 +854,9 @@ class SamAutomaticMaskGenerator:
             e = emb[idxs[0]:idxs[0] + n]
         else:
             e = emb.index_select(0, self._dev_const(("rows",) + tuple(idxs), lambda: torch.tensor(idxs, dtype=torch.int64, device=dev)))
-        gate = float(self.pred_iou_thresh) if self.pred_iou_thresh > 0 and getattr(self, "iou_gate", True) else None
         # (the call itself goes through whole images, at most 1024 prompts per launch sequence)
         pk = self._dev_const(("p01", H, W, n), lambda: p01.repeat(n, 1).contiguous())
-        low, iou = m.decode_points_multi(e, pk, n, iou_gate=gate)
+        low, iou = m.decode_points_multi(e, pk, n, iou_gate=self._gate())
         low, iou = low.flatten(0, 1), iou.flatten()
         masks, boxes, stab, keep, _ = m.postprocess(low, iou, (nh, nw), (H, W), self.pred_iou_thresh,
                                                     self.stability_score_thresh, self.stability_score_offset)
@@ -822,9 +868,7 @@ class SamAutomaticMaskGenerator:
         m = self.model
         pts, p01 = self._prompt_grid(H, W, nh, nw, layer_idx)
         lows, ious = [], []
-        # the post-processing below drops every candidate whose prediction does not exceed pred_iou_thresh (when that is > 0:
-        # automatic_mask_generator.py:287-291): prompts that fail with all three masks skip the decoder's upscaling
-        gate = float(self.pred_iou_thresh) if self.pred_iou_thresh > 0 and getattr(self, "iou_gate", True) else None
+        gate = self._gate()
         for s in range(0, len(pts), self.points_per_batch):
             low, iou = m.decode_points(emb, p01[s:s + self.points_per_batch].contiguous(), iou_gate=gate)
             lows.append(low.flatten(0, 1))
@@ -836,293 +880,123 @@ class SamAutomaticMaskGenerator:
         if crop_box is not None and orig_size is not None and list(crop_box) != [0, 0, orig_size[1], orig_size[0]]:
             box_near_crop_edge(boxes, keep, crop_box, [0, 0, orig_size[1], orig_size[0]])
         order, n = nms(boxes, iou, keep, self.box_nms_thresh)
-        return masks, boxes, iou, stab, order, n, np.repeat(pts, 3, axis=0)
+        return masks, boxes, iou, stab, order, n, self._points(H, W, layer_idx)
 
-    def generate_device_crops(self, image):
-        """_generate_masks with crop layers (automatic_mask_generator.py:197-220) + postprocess_small_regions.
-        Returns device tensors (masks [n,H,W] u8, boxes_xywh [n,4] i64, iou [n], stability [n]) and host arrays
-        (points [n,2] f64, crop_boxes [n,4] i64), in the reference's output order."""
-        m = self.model
-        dev_img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image)).to(m.device)
-        H, W = dev_img.shape[:2]
-        crop_boxes, layer_idxs = generate_crop_boxes((H, W), self.crop_n_layers, self.crop_overlap_ratio)
-        all_m, all_b, all_iou, all_stab, all_pts, all_cb = [], [], [], [], [], []
-        # the crops are known from the image size alone: their encoder passes run as batches of up to 8 (better-filled GEMMs,
-        # weights read once: 13.5 -> 11 ms per crop at ViT-H), the decoder / filters / NMS then crop by crop as in the reference
-        embs = []
-        for c0 in range(0, len(crop_boxes), 8):
-            res = [resize_longest_side(dev_img[y0:y1, x0:x1, :].contiguous(), m.img_size) for x0, y0, x1, y1 in crop_boxes[c0:c0 + 8]]
-            e = m.encode_batch(res) if len(res) > 1 else [m.encode(res[0])]
-            embs.extend(e[i] for i in range(len(res)))
-        for ci, (crop_box, layer_idx) in enumerate(zip(crop_boxes, layer_idxs)):
-            x0, y0, x1, y1 = crop_box
-            ch, cw = y1 - y0, x1 - x0
-            masks, boxes, iou, stab, order, n, pts = self._propose_from_embedding(embs[ci], ch, cw, *get_preprocess_shape(ch, cw, m.img_size),
-                                                                                   layer_idx, crop_box, (H, W))
-            n = int(n.item())                                    # host sync: survivors of this crop
-            if n == 0:
-                continue
-            idx = order[:n].long()
-            full = torch.zeros((n, H, W), dtype=torch.uint8, device=m.device)     # uncrop_masks (amg.py:241-252)
-            full[:, y0:y1, x0:x1] = masks.index_select(0, idx)
-            off = torch.tensor([x0, y0, x0, y0], dtype=torch.int32, device=m.device)
-            all_m.append(full)
-            all_b.append(boxes.index_select(0, idx) + off)       # uncrop_boxes_xyxy (amg.py:225-231)
-            all_iou.append(iou.index_select(0, idx))
-            all_stab.append(stab.index_select(0, idx))
-            all_pts.append(pts[idx.cpu().numpy()] + np.array([[x0, y0]], dtype=np.float64))   # uncrop_points
-            all_cb.append(np.tile(np.array([crop_box], dtype=np.int64), (n, 1)))
-        if not all_m:
-            e = torch.empty
-            return (e((0, H, W), dtype=torch.uint8, device=m.device), e((0, 4), dtype=torch.int64, device=m.device),
-                    e((0,), device=m.device), e((0,), device=m.device), np.zeros((0, 2)), np.zeros((0, 4), np.int64))
-        mk, bx = torch.cat(all_m), torch.cat(all_b).contiguous()
-        iou, stab = torch.cat(all_iou), torch.cat(all_stab)
-        pts, cbs = np.concatenate(all_pts), np.concatenate(all_cb)
-        if len(crop_boxes) > 1:
-            # duplicates between crops: prefer masks from smaller crops (automatic_mask_generator.py:209-220)
-            area = (cbs[:, 2] - cbs[:, 0]) * (cbs[:, 3] - cbs[:, 1])
-            scores = torch.from_numpy((1.0 / torch.from_numpy(area)).to(torch.float32).numpy()).to(m.device)
-            order, n = nms(bx, scores, torch.ones(len(bx), dtype=torch.uint8, device=m.device), self.crop_nms_thresh)
-            k = order[: int(n.item())].long()
-            kc = k.cpu().numpy()
-            mk, bx, iou, stab, pts, cbs = mk.index_select(0, k), bx.index_select(0, k).contiguous(), iou[k], stab[k], pts[kc], cbs[kc]
-        if self.min_mask_region_area > 0 and len(bx) > 0:
-            m1, c1 = remove_small_regions(mk.contiguous(), self.min_mask_region_area, "holes")
-            m2, c2, nb = remove_small_regions_boxes(m1, self.min_mask_region_area, "islands")
-            unchanged = ((c1 | c2) == 0).to(torch.float32)
-            order2, n2 = nms(nb, unchanged, torch.ones(len(nb), dtype=torch.uint8, device=m.device),
-                             max(self.box_nms_thresh, self.crop_nms_thresh))
-            k = order2[: int(n2.item())].long()
-            kc = k.cpu().numpy()
-            mk, bx, iou, stab, pts, cbs = m2.index_select(0, k), nb.index_select(0, k), iou[k], stab[k], pts[kc], cbs[kc]
-        b = bx.long()
-        xywh = torch.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1)
-        return mk, xywh, iou, stab, pts, cbs
+    # ---- the tail: a GROUP of images from the candidates to the final tensors --------------------------------------
+    def group_begin(self, images, cap=None, encoded_event=None):
+        """Stage A of generate() for several images on the current stream: Pillow-exact resize, the encoder, then decoder +
+        fused post-processing + first NMS.  Without crop layers ONE encoder pass takes all images and every size class one
+        decoder call (_propose_classes); with crop layers the crops of all images go through the encoder in batches of up to
+        16, then decoder, crop-edge filter and NMS crop by crop (_crops_begin).
+        The survivor counts of the whole group leave in ONE device->host copy (pinned), marked by an event, with the fp16
+        range counters: nothing is waited for here, so the caller can enqueue other work (the CLIP stage of the previous
+        group) before group_cleanup().
+        cap: keep at most this many proposals per image (not in the reference -- synthetic benchmark: 'AMG forced to keep a
+        fixed 64').  Without crop layers it bounds the survivors of the first NMS, before the clean-up; with crop layers it
+        truncates the finished lists."""
+        return self._begin(images, cap, encoded_event, 16)
 
-    # ---- crop layers for a GROUP of images: three host syncs for the whole group instead of 1 per crop + 2 per image ----
-    def crops_begin(self, images, encoded_event=None):
-        """Stage A of generate_device_crops for several images on the current stream, nothing waited for: the crops of all
-        images through the encoder in batches of up to 16, then decoder + fused post-processing + crop-edge filter + first
-        NMS crop by crop; the survivor counts of ALL crops leave in one pinned copy behind an event (with the fp16 range
-        counters).  The caller enqueues other work (the CLIP stage of the previous group) before crops_mid()."""
-        m = self.model
+    def _begin(self, images, cap, encoded_event, encoder_chunk):
         st = _GroupState()
-        st.sizes, st.cand = [], []
-        res, owner = [], []
-        imgs = []
-        for image in images:
-            dev_img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image)).to(m.device)
-            H, W = dev_img.shape[:2]
-            crop_boxes, layer_idxs = generate_crop_boxes((H, W), self.crop_n_layers, self.crop_overlap_ratio)
-            st.sizes.append((int(H), int(W), crop_boxes, layer_idxs))
-            imgs.append(dev_img)
-            for x0, y0, x1, y1 in crop_boxes:
-                res.append(resize_longest_side(dev_img[y0:y1, x0:x1, :].contiguous(), m.img_size))
-                owner.append(len(imgs) - 1)
-        embs = []
-        for c0 in range(0, len(res), 16):
-            chunk = res[c0:c0 + 16]
-            e = m.encode_batch(chunk) if len(chunk) > 1 else [m.encode(chunk[0])]
-            embs.extend(e[i] for i in range(len(chunk)))
-        if encoded_event is not None:
-            encoded_event.record(torch.cuda.current_stream(m.device))
-        k, counts = 0, []
-        for (H, W, crop_boxes, layer_idxs) in st.sizes:
-            per = []
-            for crop_box, layer_idx in zip(crop_boxes, layer_idxs):
-                x0, y0, x1, y1 = crop_box
-                ch, cw = y1 - y0, x1 - x0
-                c = self._propose_from_embedding(embs[k], ch, cw, *get_preprocess_shape(ch, cw, m.img_size), layer_idx, crop_box, (H, W))
-                k += 1
-                per.append(c[:5])
-                counts.append(c[5])
-            st.cand.append(per)
-        st.n1_dev = torch.cat(counts)
-        st.n1 = torch.empty(len(counts), dtype=torch.int32).pin_memory()
-        st.n1.copy_(st.n1_dev, non_blocking=True)
-        st.overflow = 0
-        st.ovf = torch.zeros(2, dtype=torch.int32).pin_memory()
-        ops.split_overflow_peek(st.ovf)     # (the counters are process-wide: the CLIP / GEM models of the loop may be f16x3 when this one is not)
-        st.ev1 = torch.cuda.Event()
-        st.ev1.record(torch.cuda.current_stream(m.device))
+        st.cap, st.overflow = cap, 0
+        st.sizes = [tuple(int(v) for v in im.shape[:2]) for im in images]
+        if self.crop_n_layers > 0:
+            counts = self._crops_begin(st, images, encoded_event, encoder_chunk)
+        else:
+            st.cand = self._propose_classes(images, encoded_event)
+            # (counts in image order: a class holds its images' counts side by side)
+            cnts = [c[1][5] for c in st.cand]
+            counts = cnts[0] if len(cnts) == 1 else torch.cat(cnts)
+            perm = [i for c in st.cand for i in c[0]]
+            if perm != list(range(len(images))):
+                inv = [0] * len(perm)
+                for pos, i in enumerate(perm):
+                    inv[i] = pos
+                counts = counts.index_select(0, self._dev_const(("rows",) + tuple(inv), lambda: torch.tensor(
+                    inv, dtype=torch.int64, device=self.model.device)))
+        st.n1, st.ev1, st.ovf = self._read_back(counts, overflow=True)
         return st
 
-    def crops_mid(self, st):
-        """Stage B (host sync 1 of 3): every crop's survivors pasted into full-size masks (uncrop_masks / uncrop_boxes_xyxy,
-        amg.py:225-252), the crops of an image concatenated in the reference's order, the cross-crop NMS that prefers
-        masks of smaller crops (automatic_mask_generator.py:209-220); its counts leave in one copy."""
+    def group_cleanup(self, st):
+        """Stage B: waits for the counts of group_begin (the first host sync) and enqueues what they decide.  Without crop
+        layers: the survivors' gather and the small-region clean-up with its NMS (_classes_cleanup); with crop layers:
+        every crop's survivors in its image's frame and the cross-crop NMS (_crops_merge).  The next counts leave in one
+        copy again (none without crop layers and without clean-up).  st.overflow: the fp16 range counters of group_begin."""
         st.ev1.synchronize()
         st.overflow = int(st.ovf[0]) + int(st.ovf[1])
-        m = self.model
-        dev = m.device
         n1 = [int(v) for v in st.n1.tolist()]
-        k = 0
-        st.stage, n_dev = [], []
-        for (H, W, crop_boxes, layer_idxs), per in zip(st.sizes, st.cand):
-            all_m, all_b, all_iou, all_stab, areas = [], [], [], [], []
-            for crop_box, (masks, boxes, iou, stab, order) in zip(crop_boxes, per):
-                n = n1[k]
-                k += 1
-                if n == 0:
-                    continue
-                x0, y0, x1, y1 = crop_box
-                idx = order[:n].long()
-                if (x0, y0, x1, y1) == (0, 0, W, H):
-                    full = masks.index_select(0, idx)
-                else:
-                    full = torch.zeros((n, H, W), dtype=torch.uint8, device=dev)
-                    full[:, y0:y1, x0:x1] = masks.index_select(0, idx)
-                all_m.append(full)
-                all_b.append(boxes.index_select(0, idx) + torch.tensor([x0, y0, x0, y0], dtype=torch.int32, device=dev))
-                all_iou.append(iou.index_select(0, idx))
-                all_stab.append(stab.index_select(0, idx))
-                areas.append(np.full(n, (x1 - x0) * (y1 - y0), dtype=np.int64))
-            if not all_m:
-                st.stage.append(None)
-                n_dev.append(torch.zeros(1, dtype=torch.int32, device=dev))
-                continue
-            mk, bx = torch.cat(all_m), torch.cat(all_b).contiguous()
-            iou, stab = torch.cat(all_iou), torch.cat(all_stab)
-            order, n = None, torch.full((1,), len(bx), dtype=torch.int32, device=dev)
-            if len(crop_boxes) > 1:
-                area = np.concatenate(areas)
-                scores = torch.from_numpy((1.0 / torch.from_numpy(area)).to(torch.float32).numpy()).to(dev)
-                order, n = nms(bx, scores, torch.ones(len(bx), dtype=torch.uint8, device=dev), self.crop_nms_thresh)
-            st.stage.append((mk, bx, iou, stab, order))
-            n_dev.append(n.reshape(1))
-        st.cand = None
-        st.n2 = torch.empty(len(n_dev), dtype=torch.int32).pin_memory()
-        st.n2.copy_(torch.cat(n_dev), non_blocking=True)
-        st.ev2 = torch.cuda.Event()
-        st.ev2.record(torch.cuda.current_stream(dev))
+        counts = self._crops_merge(st, n1) if self.crop_n_layers > 0 else self._classes_cleanup(st, n1)
+        st.n2 = st.ev2 = None
+        if counts is not None:
+            st.n2, st.ev2, _ = self._read_back(counts)
         return st
 
-    def crops_post(self, st):
-        """Stage C (host sync 2 of 3): the survivors of the cross-crop NMS through postprocess_small_regions' kernels (holes,
-        islands, boxes, the NMS that prefers untouched masks; automatic_mask_generator.py:324-372); counts in one copy."""
-        st.ev2.synchronize()
-        dev = self.model.device
-        n2 = [int(v) for v in st.n2.tolist()]
-        stage, n_dev = [], []
-        for stg, n in zip(st.stage, n2):
-            if stg is None or n == 0:
-                stage.append(None)
-                n_dev.append(torch.zeros(1, dtype=torch.int32, device=dev))
-                continue
-            mk, bx, iou, stab, order = stg
-            if order is not None:
-                k = order[:n].long()
-                mk, bx, iou, stab = mk.index_select(0, k), bx.index_select(0, k).contiguous(), iou[k], stab[k]
-            if self.min_mask_region_area > 0:
-                m1, c1 = remove_small_regions(mk.contiguous(), self.min_mask_region_area, "holes")
-                m2, c2, nb = remove_small_regions_boxes(m1, self.min_mask_region_area, "islands")
-                unchanged = ((c1 | c2) == 0).to(torch.float32)
-                order2, nn = nms(nb, unchanged, torch.ones(len(nb), dtype=torch.uint8, device=dev),
-                                 max(self.box_nms_thresh, self.crop_nms_thresh))
-                stage.append((m2, nb, iou, stab, order2))
-                n_dev.append(nn.reshape(1))
-            else:
-                stage.append((mk, bx, iou, stab, None))
-                n_dev.append(torch.full((1,), n, dtype=torch.int32, device=dev))
-        st.stage = stage
-        st.n1 = torch.empty(len(n_dev), dtype=torch.int32).pin_memory()
-        st.n1.copy_(torch.cat(n_dev), non_blocking=True)
-        st.ev1 = torch.cuda.Event()
-        st.ev1.record(torch.cuda.current_stream(dev))
-        return st
-
-    def crops_finish(self, st):
-        """Stage D (host sync 3 of 3): the final gathers.  Per image (masks [n,H,W] u8, boxes_xywh [n,4] i64, iou [n],
-        stability [n]) -- the first four outputs of generate_device_crops, same order; n may be 0."""
-        st.ev1.synchronize()
-        dev = self.model.device
-        n3 = [int(v) for v in st.n1.tolist()]
-        out = []
-        for stg, n, (H, W, _cb, _li) in zip(st.stage, n3, st.sizes):
-            if stg is None or n == 0:
-                e = torch.empty
-                out.append((e((0, H, W), dtype=torch.uint8, device=dev), e((0, 4), dtype=torch.int64, device=dev),
-                            e((0,), device=dev), e((0,), device=dev)))
-                continue
-            mk, bx, iou, stab, order2 = stg
-            if order2 is not None:
-                k = order2[:n].long()
-                mk, bx, iou, stab = mk.index_select(0, k), bx.index_select(0, k), iou[k], stab[k]
-            b = bx.long()
-            out.append((mk, torch.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1), iou, stab))
+    def group_finish(self, st):
+        """Stage C: the second host sync (none without crop layers and without clean-up) and the final gathers; with crop
+        layers the clean-up and a third sync lie between them (_crops_finish).  Returns per image (masks [n,H,W] uint8,
+        boxes_xywh [n,4] int64, iou [n], stability [n], source [n] int64), in the reference's output order; n may be 0.
+        source: crop index * source_stride + index into that crop's 3 * points candidates (no crop layers: the candidate)."""
+        n2 = None
+        if st.n2 is not None:
+            st.ev2.synchronize()
+            n2 = [int(v) for v in st.n2.tolist()]
+        out = self._crops_finish(st, n2) if self.crop_n_layers > 0 else self._classes_finish(st, n2)
         st.stage = None
         return out
 
+    def generate_group(self, images, cap=None):
+        """generate_device() for several images with one encoder pass and two host syncs in all (one without clean-up)."""
+        return self.group_finish(self.group_cleanup(self.group_begin(images, cap)))
+
     def generate_crops_group(self, images):
         """generate_device_crops (masks, boxes, iou, stability) for several images with three host syncs in all"""
-        return self.crops_finish(self.crops_post(self.crops_mid(self.crops_begin(images))))
+        return [p[:4] for p in self.group_finish(self.group_cleanup(self.group_begin(images)))]
 
     def generate_device(self, image, resized=None, fixed_n=None):
         """Whole `generate` on the device.  Returns (masks [n,H,W] uint8, boxes_xywh [n,4] int64,
         iou [n], stability [n], cand [n] int64 indices into the 3*points candidates), all device
-        tensors, in the reference's output order.  Two host syncs (the two proposal counts).
+        tensors, in the reference's output order.  Two host syncs (the two proposal counts), read where they are needed: by
+        measurement one image is faster this way than as a group of one, whose pinned read-backs cost it 0.3 ms.
         fixed_n (benchmark only): take the first fixed_n survivors of the first NMS without reading
         the count back (the caller guarantees that many survive), run the clean-up kernels on them
         and skip the final gather -- no host sync at all."""
         masks, boxes, iou, stab, order, n, points = self.propose(image, resized)
         if fixed_n is not None:
             idx = order[:fixed_n].long()
-            m = masks.index_select(0, idx).contiguous()
-            m, nb = self.cleanup_fixed(m)
+            m, nb = self.cleanup_fixed(masks.index_select(0, idx).contiguous())
             return m, nb, iou.index_select(0, idx), stab.index_select(0, idx), idx
         n = int(n.item())                       # host sync: number of survivors of the first NMS
         idx = order[:n].long()
         m = masks.index_select(0, idx).contiguous()
         bx = boxes.index_select(0, idx).contiguous()
         if self.min_mask_region_area > 0 and n > 0:
-            # postprocess_small_regions (automatic_mask_generator.py:324-372) on the device
-            m1, c1 = remove_small_regions(m, self.min_mask_region_area, "holes")
-            m2, c2, nb = remove_small_regions_boxes(m1, self.min_mask_region_area, "islands")
-            unchanged = ((c1 | c2) == 0).to(torch.float32)           # score 1 for untouched masks
-            keep_all = torch.ones(n, dtype=torch.uint8, device=m.device)
-            order2, n2 = nms(nb, unchanged, keep_all, max(self.box_nms_thresh, self.crop_nms_thresh))
-            k = order2[: int(n2.item())].long()
-            m, bx, idx = m2.index_select(0, k), nb.index_select(0, k), idx.index_select(0, k)
-        b = bx.long()
-        xywh = torch.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1) if n > 0 else b
-        return m, xywh, iou.index_select(0, idx), stab.index_select(0, idx), idx
+            m, bx, order2, n2 = self._cleanup(m, [n])
+            k = order2[: int(n2.item())].long()     # host sync: survivors of the second NMS
+            m, bx, idx = m.index_select(0, k), bx.index_select(0, k), idx.index_select(0, k)
+        return m, _xywh(bx), iou.index_select(0, idx), stab.index_select(0, idx), idx
 
-    # ---- a GROUP of images through the generator: one encoder pass, two host syncs for the whole group ------------
-    def group_begin(self, images, cap=None, encoded_event=None):
-        """Stage A of generate() for several whole images (no crop layers) on the current stream: Pillow-exact resize,
-        ONE encoder pass over all of them (Sam.encode_batch), then per image decoder + fused post-processing + first NMS.
-        The survivor counts of all images leave in ONE device->host copy (pinned), marked by an event: nothing is waited for
-        here, so the caller can enqueue other work (the CLIP stage of the previous group) before group_cleanup().
-        cap: keep at most this many survivors per image (first NMS order; not in the reference -- synthetic benchmark:
-        'AMG forced to keep a fixed 64')."""
-        assert self.crop_n_layers == 0, "crop layers take generate_device_crops (one crop at a time)"
-        st = _GroupState()
-        st.cap = cap
-        st.sizes = [tuple(int(v) for v in im.shape[:2]) for im in images]
-        st.cand = self._propose_classes(images, encoded_event)
-        dev = self.model.device
-        # (counts in image order: a class holds its images' counts side by side)
-        cnts = [c[1][5] for c in st.cand]
-        st.n1_dev = cnts[0] if len(cnts) == 1 else torch.cat(cnts)
-        perm = [i for c in st.cand for i in c[0]]
-        if perm != list(range(len(images))):
-            inv = [0] * len(perm)
-            for pos, i in enumerate(perm):
-                inv[i] = pos
-            st.n1_dev = st.n1_dev.index_select(0, self._dev_const(("rows",) + tuple(inv),
-                                                                  lambda: torch.tensor(inv, dtype=torch.int64, device=dev)))
-        st.n1 = torch.empty(len(images), dtype=torch.int32).pin_memory()
-        st.n1.copy_(st.n1_dev, non_blocking=True)
-        # the fp16 range guard of the f16x3 mode rides on the same read-back: what the device had counted (any stream) when
-        # this stream got here -- the caller stops at this group instead of finding out at the end of the dataset
-        st.overflow = 0
-        st.ovf = torch.zeros(2, dtype=torch.int32).pin_memory()
-        ops.split_overflow_peek(st.ovf)     # (the counters are process-wide: the CLIP / GEM models of the loop may be f16x3 when this one is not)
-        st.ev1 = torch.cuda.Event()
-        st.ev1.record(torch.cuda.current_stream(dev))
-        return st
+    def generate_device_crops(self, image):
+        """_generate_masks with crop layers (automatic_mask_generator.py:197-220) + postprocess_small_regions: the crop group
+        of one (its encoder batches hold up to 8 crops).  Returns device tensors (masks [n,H,W] u8, boxes_xywh [n,4] i64,
+        iou [n], stability [n]) and host arrays (points [n,2] f64, crop_boxes [n,4] i64), in the reference's output order.
+        Four host syncs: the group's three and the read-back of the survivors' sources."""
+        st = self._begin([image], None, None, 8)
+        m, xywh, iou, stab, src = self.group_finish(self.group_cleanup(st))[0]
+        return (m, xywh, iou, stab) + self._sources(src, *st.sizes[0])
 
+    def _sources(self, src, H, W):
+        """the source indices of an image's survivors on the host: (prompt points [n,2] f64 in image coordinates, crop boxes
+        XYXY [n,4] i64)"""
+        crop_boxes, layer_idxs = generate_crop_boxes((H, W), self.crop_n_layers, self.crop_overlap_ratio)
+        crop, cand = np.divmod(src.cpu().numpy(), self.source_stride)
+        pts = np.zeros((len(crop), 2))
+        for c in np.unique(crop):
+            x0, y0, x1, y1 = crop_boxes[c]
+            sel = crop == c
+            pts[sel] = self._points(y1 - y0, x1 - x0, layer_idxs[c])[cand[sel]] + np.array([[x0, y0]], dtype=np.float64)   # uncrop_points
+        return pts, np.asarray(crop_boxes, dtype=np.int64)[crop]
+
+    # ---- the tail without crop layers: by size class ------------------------------------------------------------
     def _segment_index(self, counts, stride):
         """Device index lists for "the first counts[j] entries of segment j" of a flat array whose segments lie `stride`
         apart, from ONE pinned upload: (positions [total] i64, segment starts of every entry [total] i64, offsets of the
@@ -1140,104 +1014,6 @@ class SamAutomaticMaskGenerator:
         d = host.to(self.model.device, non_blocking=True)
         return d[:total], d[total:2 * total], d[2 * total:].to(torch.int32)
 
-    def group_cleanup(self, st):
-        """Stage B: waits for the counts of group_begin (host sync 1 of 2); per size class ONE gather of the survivors of all
-        its images, postprocess_small_regions' kernels on them (holes, islands, boxes: image by image, see below; the second
-        NMS: one segmented launch; automatic_mask_generator.py:324-372).  The second NMS counts leave in one copy again.
-        The clean-up passes stay one image per call, by measurement (profiles/group_tail_ab.json): alone on the device the two
-        passes over a group's 16 x 64 masks of 640 x 640 take 13.12 ms at one image per call, 11.44 at 2, 10.95 at 4 and
-        10.16 at 16, but beside the CLIP stream the step is SLOWER with the whole class per call (0.980 of the parent's time
-        against 0.975): its launches then hold the whole chip for milliseconds while the persistent GEMMs of the other stream
-        wait, and its union-find planes (8 bytes per pixel: 3.4 GB against one image's 210 MB) leave the last-level cache."""
-        st.ev1.synchronize()
-        if st.ovf is not None:
-            st.overflow = int(st.ovf[0]) + int(st.ovf[1])
-        dev = self.model.device
-        n1 = [int(v) for v in st.n1.tolist()]
-        if st.cap is not None:
-            n1 = [min(v, st.cap) for v in n1]
-        st.n1_list = n1
-        st.stage = []
-        n2_dev = []
-        area = self.min_mask_region_area
-        for idxs, (masks, boxes, iou, stab, order, _cnt), k3, _hw in st.cand:
-            counts = [n1[i] for i in idxs]
-            total = sum(counts)
-            if total == 0:
-                st.stage.append(None)
-                if area > 0:
-                    n2_dev.append(torch.zeros(len(idxs), dtype=torch.int32, device=dev))
-                continue
-            pos, base, offs = self._segment_index(counts, k3)
-            idx = order.index_select(0, pos).long()          # per image: indices into its k3 candidates, first NMS order
-            gidx = idx + base                                # the same as rows of the class's tensors
-            m = masks.index_select(0, gidx)
-            bx = boxes.index_select(0, gidx)
-            if area > 0:
-                m1, c1 = torch.empty_like(m), torch.empty((total,), dtype=torch.uint8, device=dev)
-                m2, c2 = torch.empty_like(m), torch.empty((total,), dtype=torch.uint8, device=dev)
-                nb = torch.empty((total, 4), dtype=torch.int32, device=dev)
-                o = 0
-                for c in counts:
-                    if c > 0:
-                        sl = slice(o, o + c)
-                        remove_small_regions(m[sl], area, "holes", out=(m1[sl], c1[sl]))
-                        remove_small_regions_boxes(m1[sl], area, "islands", out=(m2[sl], c2[sl], nb[sl]))
-                    o += c
-                unchanged = ((c1 | c2) == 0).to(torch.float32)           # score 1 for untouched masks
-                order2, n2 = nms_segments(nb, unchanged, torch.ones(total, dtype=torch.uint8, device=dev), offs, max(counts),
-                                          max(self.box_nms_thresh, self.crop_nms_thresh))
-                st.stage.append((m2, nb, idx, gidx, order2, iou, stab, counts))
-                n2_dev.append(n2)
-            else:
-                st.stage.append((m, bx, idx, gidx, None, iou, stab, counts))
-        st.n2 = None
-        if area > 0:
-            # (class order; group_finish reads them the same way)
-            st.n2 = torch.empty(len(n1), dtype=torch.int32).pin_memory()
-            st.n2.copy_(n2_dev[0] if len(n2_dev) == 1 else torch.cat(n2_dev), non_blocking=True)
-            st.ev2 = torch.cuda.Event()
-            st.ev2.record(torch.cuda.current_stream(dev))
-        st.cand = [c[0] for c in st.cand]     # the candidate tensors (192 full-size masks per image) can go back to the allocator
-        return st
-
-    def group_finish(self, st):
-        """Stage C: host sync 2 of 2 (none without the small-region clean-up), the final gathers, one per size class.  Returns
-        per image what generate_device returns: (masks [n,H,W] uint8, boxes_xywh [n,4] int64, iou [n], stability [n],
-        cand [n] int64); n may be 0."""
-        n2_all = None
-        if st.n2 is not None:
-            st.ev2.synchronize()
-            n2_all = [int(v) for v in st.n2.tolist()]
-        out = [None] * len(st.sizes)
-        dev = self.model.device
-        e = torch.empty
-        k0 = 0
-        for idxs, stg in zip(st.cand, st.stage):
-            n2 = n2_all[k0:k0 + len(idxs)] if n2_all is not None else [st.n1_list[i] for i in idxs]
-            k0 += len(idxs)
-            if stg is not None and sum(n2) > 0:
-                m, bx, idx, gidx, order2, iou, stab, counts = stg
-                if order2 is not None:
-                    pos, base, _ = self._packed_index(n2, counts)
-                    k = order2.index_select(0, pos).long() + base
-                    m, bx, idx, gidx = m.index_select(0, k), bx.index_select(0, k), idx.index_select(0, k), gidx.index_select(0, k)
-                b = bx.long()
-                xywh = torch.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], 1)
-                iou, stab = iou.index_select(0, gidx), stab.index_select(0, gidx)
-            o = 0
-            for i, n in zip(idxs, n2):
-                if stg is None or n == 0:
-                    hw = st.sizes[i]
-                    out[i] = (e((0,) + hw, dtype=torch.uint8, device=dev), e((0, 4), dtype=torch.int64, device=dev),
-                              e((0,), device=dev), e((0,), device=dev), e((0,), dtype=torch.int64, device=dev))
-                    continue
-                sl = slice(o, o + n)
-                out[i] = (m[sl], xywh[sl], iou[sl], stab[sl], idx[sl])
-                o += n
-        st.stage = None
-        return out
-
     def _packed_index(self, counts, seg_lens):
         """_segment_index for segments packed back to back (segment j starts at sum(seg_lens[:j])): the first counts[j]
         entries of each -> (positions [total] i64, segment starts [total] i64, None)"""
@@ -1253,21 +1029,189 @@ class SamAutomaticMaskGenerator:
         d = host.to(self.model.device, non_blocking=True)
         return d[:total], d[total:], None
 
-    def generate_group(self, images, cap=None):
-        """generate_device() for several images with one encoder pass and two host syncs in all (one without clean-up)."""
-        return self.group_finish(self.group_cleanup(self.group_begin(images, cap)))
+    def _classes_cleanup(self, st, n1):
+        """group_cleanup without crop layers: per size class ONE gather of the survivors of all its images and _cleanup on
+        them (its passes image by image, its NMS one segmented launch) -> the second NMS counts in class order, or None.
+        The clean-up passes stay one image per call, by measurement (profiles/group_tail_ab.json): alone on the device the two
+        passes over a group's 16 x 64 masks of 640 x 640 take 13.12 ms at one image per call, 11.44 at 2, 10.95 at 4 and
+        10.16 at 16, but beside the CLIP stream the step is SLOWER with the whole class per call (0.980 of the parent's time
+        against 0.975): its launches then hold the whole chip for milliseconds while the persistent GEMMs of the other stream
+        wait, and its union-find planes (8 bytes per pixel: 3.4 GB against one image's 210 MB) leave the last-level cache."""
+        dev = self.model.device
+        if st.cap is not None:
+            n1 = [min(v, st.cap) for v in n1]
+        st.n1_list = n1
+        st.stage = []
+        n2_dev = []
+        area = self.min_mask_region_area
+        for idxs, (masks, boxes, iou, stab, order, _cnt), k3, _hw in st.cand:
+            counts = [n1[i] for i in idxs]
+            if sum(counts) == 0:
+                st.stage.append(None)
+                if area > 0:
+                    n2_dev.append(torch.zeros(len(idxs), dtype=torch.int32, device=dev))
+                continue
+            pos, base, offs = self._segment_index(counts, k3)
+            idx = order.index_select(0, pos).long()          # per image: indices into its k3 candidates, first NMS order
+            gidx = idx + base                                # the same as rows of the class's tensors
+            m = masks.index_select(0, gidx)
+            bx = boxes.index_select(0, gidx)
+            order2 = None
+            if area > 0:
+                m, bx, order2, n2 = self._cleanup(m, counts, offs)
+                n2_dev.append(n2)
+            st.stage.append((m, bx, idx, gidx, order2, iou, stab, counts))
+        # (class order; _classes_finish reads them the same way)
+        counts = (n2_dev[0] if len(n2_dev) == 1 else torch.cat(n2_dev)) if area > 0 else None
+        st.cand = [c[0] for c in st.cand]     # the candidate tensors (192 full-size masks per image) can go back to the allocator
+        return counts
 
-    def cleanup_fixed(self, m):
-        """postprocess_small_regions kernels on a fixed batch of masks [n,H,W] uint8 without reading any
-        count back: holes, islands, boxes, second NMS (its order is left on the device)."""
-        if self.min_mask_region_area <= 0:
-            return m, mask_boxes(m)
-        m1, c1 = remove_small_regions(m, self.min_mask_region_area, "holes")
-        m2, c2, nb = remove_small_regions_boxes(m1, self.min_mask_region_area, "islands")
-        nms(nb, ((c1 | c2) == 0).to(torch.float32), torch.ones(m.shape[0], dtype=torch.uint8, device=m.device),
-            max(self.box_nms_thresh, self.crop_nms_thresh))
-        return m2, nb
+    def _classes_finish(self, st, n2_all):
+        """group_finish without crop layers: the final gathers, one per size class"""
+        out = [None] * len(st.sizes)
+        k0 = 0
+        for idxs, stg in zip(st.cand, st.stage):
+            n2 = n2_all[k0:k0 + len(idxs)] if n2_all is not None else [st.n1_list[i] for i in idxs]
+            k0 += len(idxs)
+            if stg is not None and sum(n2) > 0:
+                m, bx, idx, gidx, order2, iou, stab, counts = stg
+                if order2 is not None:
+                    pos, base, _ = self._packed_index(n2, counts)
+                    k = order2.index_select(0, pos).long() + base
+                    m, bx, idx, gidx = m.index_select(0, k), bx.index_select(0, k), idx.index_select(0, k), gidx.index_select(0, k)
+                xywh = _xywh(bx)
+                iou, stab = iou.index_select(0, gidx), stab.index_select(0, gidx)
+            o = 0
+            for i, n in zip(idxs, n2):
+                if stg is None or n == 0:
+                    out[i] = self._empty(*st.sizes[i])
+                    continue
+                sl = slice(o, o + n)
+                out[i] = (m[sl], xywh[sl], iou[sl], stab[sl], idx[sl])
+                o += n
+        return out
 
+    # ---- the tail with crop layers: image by image, crop by crop --------------------------------------------------
+    def _encode_crops(self, resized, chunk):
+        """the embeddings of a list of resized crops, through the encoder in batches of up to `chunk` (better-filled GEMMs,
+        weights read once: 13.5 -> 11 ms per crop at ViT-H in batches of 8)"""
+        embs = []
+        for c0 in range(0, len(resized), chunk):
+            e = self.model.encode_batch(resized[c0:c0 + chunk])
+            embs.extend(e[i] for i in range(e.shape[0]))
+        return embs
+
+    def _crops_begin(self, st, images, encoded_event, chunk):
+        """group_begin with crop layers -> the first NMS counts of ALL crops, image by image.  The crops are known from the
+        image sizes alone, so the encoder takes them across images; decoder / filters / NMS crop by crop as in the reference."""
+        m = self.model
+        st.crops, res = [], []
+        for image, hw in zip(images, st.sizes):
+            dev_img = _image_on(image, m.device)
+            crop_boxes, layer_idxs = generate_crop_boxes(hw, self.crop_n_layers, self.crop_overlap_ratio)
+            st.crops.append((crop_boxes, layer_idxs))
+            res += [resize_longest_side(dev_img[y0:y1, x0:x1, :].contiguous(), m.img_size) for x0, y0, x1, y1 in crop_boxes]
+        embs = self._encode_crops(res, chunk)
+        if encoded_event is not None:
+            encoded_event.record(torch.cuda.current_stream(m.device))
+        st.cand, counts, k = [], [], 0
+        for hw, (crop_boxes, layer_idxs) in zip(st.sizes, st.crops):
+            per = []
+            for crop_box, layer_idx in zip(crop_boxes, layer_idxs):
+                x0, y0, x1, y1 = crop_box
+                ch, cw = y1 - y0, x1 - x0
+                c = self._propose_from_embedding(embs[k], ch, cw, *get_preprocess_shape(ch, cw, m.img_size), layer_idx, crop_box, hw)
+                k += 1
+                per.append(c[:5])
+                counts.append(c[5])
+            st.cand.append(per)
+        return torch.cat(counts)
+
+    def _uncrop(self, cand, n, crop_box, H, W):
+        """the n survivors of one crop in the image's frame (uncrop_masks / uncrop_boxes_xyxy, amg.py:225-252) -> (masks
+        [n,H,W], boxes XYXY, iou, stability, their indices into the crop's candidates [n] i64)"""
+        masks, boxes, iou, stab, order = cand
+        x0, y0, x1, y1 = crop_box
+        dev = masks.device
+        idx = order[:n].long()
+        if (x0, y0, x1, y1) == (0, 0, W, H):
+            full = masks.index_select(0, idx)
+        else:
+            full = torch.zeros((n, H, W), dtype=torch.uint8, device=dev)
+            full[:, y0:y1, x0:x1] = masks.index_select(0, idx)
+        off = torch.tensor([x0, y0, x0, y0], dtype=torch.int32, device=dev)
+        return full, boxes.index_select(0, idx) + off, iou.index_select(0, idx), stab.index_select(0, idx), idx
+
+    def _cross_crop_nms(self, boxes, areas):
+        """duplicates between crops: prefer masks from smaller crops (automatic_mask_generator.py:209-220); areas: the crop
+        area of every box (host, int64) -> nms() order and count"""
+        scores = torch.from_numpy((1.0 / torch.from_numpy(areas)).to(torch.float32).numpy()).to(boxes.device)
+        return nms(boxes, scores, torch.ones(len(boxes), dtype=torch.uint8, device=boxes.device), self.crop_nms_thresh)
+
+    def _crops_merge(self, st, n1):
+        """group_cleanup with crop layers: every crop's survivors uncropped, the crops of an image concatenated in the
+        reference's order, the cross-crop NMS -> its counts, one per image"""
+        dev = self.model.device
+        k = 0
+        st.stage, n_dev = [], []
+        for (H, W), (crop_boxes, _layers), per in zip(st.sizes, st.crops, st.cand):
+            parts, areas = [], []
+            for ci, (crop_box, cand) in enumerate(zip(crop_boxes, per)):
+                n = n1[k]
+                k += 1
+                if n == 0:
+                    continue
+                part = self._uncrop(cand, n, crop_box, H, W)
+                parts.append(part[:4] + (part[4] + ci * self.source_stride,))
+                areas.append(np.full(n, (crop_box[2] - crop_box[0]) * (crop_box[3] - crop_box[1]), dtype=np.int64))
+            if not parts:
+                st.stage.append(None)
+                n_dev.append(torch.zeros(1, dtype=torch.int32, device=dev))
+                continue
+            mk, bx, iou, stab, src = (torch.cat(t) for t in zip(*parts))
+            bx = bx.contiguous()
+            order, n = None, torch.full((1,), len(bx), dtype=torch.int32, device=dev)
+            if len(crop_boxes) > 1:
+                order, n = self._cross_crop_nms(bx, np.concatenate(areas))
+            st.stage.append((mk, bx, iou, stab, src, order))
+            n_dev.append(n.reshape(1))
+        st.cand = None
+        return torch.cat(n_dev)
+
+    def _crops_finish(self, st, n2):
+        """group_finish with crop layers: the survivors of the cross-crop NMS through _cleanup, image by image (a crop
+        configuration can leave more than 1024 of them), its counts in one copy (host sync 3 of 3), the final gathers"""
+        dev = self.model.device
+        stage, n_dev = [], []
+        for stg, n in zip(st.stage, n2):
+            if stg is None or n == 0:
+                stage.append(None)
+                n_dev.append(torch.zeros(1, dtype=torch.int32, device=dev))
+                continue
+            mk, bx, iou, stab, src, order = stg
+            if order is not None:
+                k = order[:n].long()
+                mk, bx, iou, stab, src = mk.index_select(0, k), bx.index_select(0, k).contiguous(), iou[k], stab[k], src[k]
+            order2, nn = None, torch.full((1,), n, dtype=torch.int32, device=dev)
+            if self.min_mask_region_area > 0:
+                mk, bx, order2, nn = self._cleanup(mk.contiguous(), [n])
+            stage.append((mk, bx, iou, stab, src, order2))
+            n_dev.append(nn.reshape(1))
+        n3, ev3, _ = self._read_back(torch.cat(n_dev))
+        ev3.synchronize()
+        out = []
+        for stg, n, hw in zip(stage, n3.tolist(), st.sizes):
+            if stg is None or n == 0:
+                out.append(self._empty(*hw))
+                continue
+            mk, bx, iou, stab, src, order2 = stg
+            if order2 is not None:
+                k = order2[:n].long()
+                mk, bx, iou, stab, src = mk.index_select(0, k), bx.index_select(0, k), iou[k], stab[k], src[k]
+            out.append(tuple(t[:st.cap] for t in (mk, _xywh(bx), iou, stab, src)))
+        return out
+
+    # ---- host records ---------------------------------------------------------------------------------------------
     def _segmentation(self, mask):
         """automatic_mask_generator.py:176-182: the record's `segmentation` in the configured output mode (binary mask,
         uncompressed RLE dict, COCO RLE dict with the compressed counts string)."""
@@ -1278,29 +1222,21 @@ class SamAutomaticMaskGenerator:
 
     def generate(self, image):
         """automatic_mask_generator.py:137-195 -> list of records."""
+        H, W = image.shape[:2]
         if self.crop_n_layers > 0:
             m, xywh, iou, stab, pts, cbs = self.generate_device_crops(image)
-            masks = m.bool().cpu().numpy()
-            xywh, iou, stab = xywh.cpu().numpy(), iou.cpu().numpy(), stab.cpu().numpy()
-            out = []
-            for i in range(len(masks)):
-                cb = cbs[i]
-                out.append({"segmentation": self._segmentation(masks[i]), "area": int(masks[i].sum()), "bbox": [int(v) for v in xywh[i]],
-                            "predicted_iou": float(iou[i]), "point_coords": [pts[i].tolist()],
-                            "stability_score": float(stab[i]),
-                            "crop_box": [int(cb[0]), int(cb[1]), int(cb[2] - cb[0]), int(cb[3] - cb[1])]})   # XYWH
-            return out
-        m, xywh, iou, stab, idx = self.generate_device(image)
+        else:
+            m, xywh, iou, stab, src = self.generate_device(image)
+            pts, cbs = self._sources(src, H, W)
         masks = m.bool().cpu().numpy()
-        xywh, iou, stab, idx = xywh.cpu().numpy(), iou.cpu().numpy(), stab.cpu().numpy(), idx.cpu().numpy()
-        H, W = image.shape[:2]
-        points = np.repeat(self.point_grids[0] * np.array([[W, H]], dtype=np.float64), 3, axis=0)
+        xywh, iou, stab = xywh.cpu().numpy(), iou.cpu().numpy(), stab.cpu().numpy()
         out = []
         for i in range(len(masks)):
-            out.append({"segmentation": self._segmentation(masks[i]), "area": int(masks[i].sum()),
-                        "bbox": [int(v) for v in xywh[i]], "predicted_iou": float(iou[i]),
-                        "point_coords": [points[idx[i]].tolist()], "stability_score": float(stab[i]),
-                        "crop_box": [0, 0, W, H]})
+            cb = cbs[i]
+            out.append({"segmentation": self._segmentation(masks[i]), "area": int(masks[i].sum()), "bbox": [int(v) for v in xywh[i]],
+                        "predicted_iou": float(iou[i]), "point_coords": [pts[i].tolist()],
+                        "stability_score": float(stab[i]),
+                        "crop_box": [int(cb[0]), int(cb[1]), int(cb[2] - cb[0]), int(cb[3] - cb[1])]})   # XYWH
         return out
 
 

@@ -317,10 +317,11 @@ def test_phrasecut_configuration_at_full_size(cuda, full):
 
 
 def test_crop_layers_in_groups_equal_image_by_image(cuda, models):
-    """SamAutomaticMaskGenerator.crops_begin / crops_mid / crops_post / crops_finish (three host syncs per GROUP of images)
-    against generate_device_crops (one per crop + two per image): identical masks, boxes, scores, for images of different
-    sizes, with thresholds that decide."""
-    from hybridgl_amd.sam import SamAutomaticMaskGenerator, sam_model_registry
+    """SamAutomaticMaskGenerator.group_begin / group_cleanup / group_finish with crop layers (three host syncs per GROUP of
+    images) against generate_device_crops (every image a group of its own): identical masks, boxes, scores, for images of
+    different sizes, with thresholds that decide; and the host arrays of generate_device_crops (prompt points, crop boxes)
+    against what the source index of the group names, worked out here from the crop list and the point grids."""
+    from hybridgl_amd.sam import SamAutomaticMaskGenerator, generate_crop_boxes
     from hybridgl_amd.synth import synth_image
     sam = models[2].model      # the tiny SAM whose mask threshold leaves sparse masks: boxes differ, the NMS passes decide
     imgs = [torch.from_numpy(synth_image(h, w, 11 + i)).to(cuda) for i, (h, w) in enumerate(((150, 200), (200, 150), (120, 120)))]
@@ -337,10 +338,32 @@ def test_crop_layers_in_groups_equal_image_by_image(cuda, models):
         assert a[0].shape == b[0].shape
         for x, y in zip(a[:4], b[:4]):      # stability of an empty mask is 0 / 0: NaN in both
             assert torch.equal(torch.nan_to_num(x, nan=-7.0), torch.nan_to_num(y, nan=-7.0)) if x.is_floating_point() else torch.equal(x, y)
+    # the three stages one by one give the one-call form, and a fifth tensor: crop * source_stride + candidate of that crop
+    full = gen.group_finish(gen.group_cleanup(gen.group_begin(imgs)))
+    seen = set()
+    for a, b, f, im in zip(one, grp, full, imgs):
+        assert len(f) == 5 and all(torch.equal(torch.nan_to_num(x, nan=-7.0), torch.nan_to_num(y, nan=-7.0)) for x, y in zip(b, f[:4]))
+        src = f[4].cpu().numpy()
+        assert src.dtype == np.int64 and src.shape == (a[0].shape[0],)
+        crop_list, layers = generate_crop_boxes(tuple(im.shape[:2]), 1, 512 / 1500)
+        pts, cbs = np.zeros((len(src), 2)), np.zeros((len(src), 4), np.int64)
+        for i, s in enumerate(src):
+            ci, cand = divmod(int(s), gen.source_stride)
+            x0, y0, x1, y1 = crop_list[ci]
+            grid = gen.point_grids[layers[ci]]
+            assert cand < 3 * len(grid)
+            pts[i] = grid[cand // 3] * np.array([x1 - x0, y1 - y0], dtype=np.float64) + np.array([x0, y0], dtype=np.float64)
+            cbs[i] = crop_list[ci]
+            seen.add(ci)
+        assert a[4].dtype == np.float64 and a[5].dtype == np.int64
+        assert np.array_equal(a[4], pts) and np.array_equal(a[5], cbs)
+    assert len(seen) > 1, "the survivors come from more than one crop"
     # an IoU threshold nothing passes: empty outputs of the right shapes, no failure
     gen.pred_iou_thresh = 1e9
     for (m, bx, iou, stab), im in zip(gen.generate_crops_group(imgs), imgs):
         assert m.shape == (0,) + tuple(im.shape[:2]) and bx.shape == (0, 4) and iou.shape == stab.shape == (0,)
+    a = gen.generate_device_crops(imgs[0])
+    assert a[0].shape == (0, 150, 200) and a[4].shape == (0, 2) and a[5].shape == (0, 4) and a[5].dtype == np.int64
 
 
 def test_phrasecut_from_disk_groups_equal_image_by_image(cuda, tmp_path):
