@@ -1,9 +1,13 @@
 // Host orchestration of the SAM image encoder and prompt/mask decoder behind the C ABI.
-//   hgl_sam_encode         == Sam.preprocess + ImageEncoderViT.forward
-//                             (modeling/sam.py:164-174, modeling/image_encoder.py:106-116)
-//   hgl_sam_decode_points  == PromptEncoder(points) + MaskDecoder(multimask_output=True)
-//                             (predictor.py:222-235, modeling/mask_decoder.py:71-149)
-// Every contraction is the fp32 MFMA GEMM / fused attention of gemm.hip / attention.hip.
+//   hgl_sam_encode(_batch)  == Sam.preprocess + ImageEncoderViT.forward
+//                              (modeling/sam.py:164-174, modeling/image_encoder.py:106-116)
+//   hgl_sam_decode_*        == PromptEncoder(points / labelled points and boxes / mask inputs) + MaskDecoder
+//                              (predictor.py:222-235, modeling/mask_decoder.py:71-149), for the prompts of one or several images
+// This file decides and launches.  In the split-fp16 modes the contractions are the GEMMs of gemm_f16x3.hip, the attention of
+// attention_ps.hip / attention.hip and the fused decoder stages of sam_decoder_fused.hip / sam_decoder_t2i.hip; in f32 mode, and
+// wherever a weight has no registered split halves, the fp32 MFMA GEMM / attention of gemm.hip / attention.hip.  Which of them a
+// call takes is decided ONCE, before anything is enqueued: per encoder block by enc_block_route, per decoder call by dec_route
+// (DecRoute); the code below those two reads their fields and re-derives nothing.
 // Tokens stay NHWC ([g*g, C] rows) end to end; the reference's NCHW permutes disappear.
 #include "hgl_common.h"
 #include <stdlib.h>
@@ -64,113 +68,89 @@ bool valid_enc(const HglSamEncoderW* w) {
          w->neck1_w && w->neck1_b && w->neck2_w && w->neck3_w && w->neck3_b;
 }
 
-// Block.forward (modeling/image_encoder.py:166-182)
-int enc_block(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPlan& p, hipStream_t st) {
-  const int D = w->embed_dim, g = w->img_size / w->patch, heads = w->heads, hd = D / heads;
-  const int T1 = g * g;                   // tokens of one image
-  const int T = p.nb * T1;                // token rows of the batch (images stacked along the rows)
-  const int ws = b.window;
-  const int size = ws > 0 ? ws : g;       // attention grid side
-  const int nw = ws > 0 ? (g + ws - 1) / ws : 1;
-  const int B1 = nw * nw;                 // windows of one image (1 for global attention)
-  const int B = p.nb * B1;
-  const int S = size * size;              // tokens per window
-  const int M1 = B1 * S;                  // padded rows of one image
-  const int M = B * S;
-  const int L = b.rel_len;
-  HGL_REQUIRE(L == 2 * size - 1, "sam_encode: rel_pos length %d does not match attention size %d", L, size);
+// ---- one encoder block: Block.forward (modeling/image_encoder.py:166-182) ----
+enum EncAttn {
+  ENC_ATTN_PS_WIN,      // q | k | v as fp16 hi / lo planes, 14 x 14 windows: the kernel takes the rel-pos terms from the registered tables
+  ENC_ATTN_PS_GLOBAL,   // the same planes, the whole 64 x 64 grid: the rel-pos terms as tensors, from the split q
+  ENC_ATTN_WIN14,       // fp32 qkv, 14 x 14 windows at head dim 80: the kernel computes the decomposed rel-pos terms itself
+  ENC_ATTN_TABLES       // fp32 qkv, decomposed rel-pos tables first, then the generic attention
+};
 
-  const bool x3 = hgl_use_x3(b.qkv_w, D) && hgl_use_x3(b.proj_w, D) && hgl_use_x3(b.lin1_w, D) &&
-                  hgl_use_x3(b.lin2_w, 4 * D) && (D % 256) == 0;
-  static int padskip = -1;   // HGL_SAM_PADSKIP=0: run the windowed GEMMs over the padded rows as well (A/B timing)
-  if (padskip < 0) padskip = HGL_DIAG_SWITCH("HGL_SAM_PADSKIP", 1) ? 1 : 0;
-  uint16_t* Ah = (uint16_t*)p.Hw;                   // split GEMM input (aliases the window buffer)
-  uint16_t* Al = Ah + (size_t)M * D;
-  uint16_t* Hh = (uint16_t*)p.H;
-  uint16_t* Hl = Hh + (size_t)T * D;
-  uint16_t* Fh = (uint16_t*)p.F;
-  uint16_t* Fl = Fh + (size_t)T * 4 * D;
-  uint16_t* Qh = (uint16_t*)p.QKV;                  // split qkv (aliases the fp32 tensor)
-  uint16_t* Ql = Qh + (size_t)M * 3 * D;
-  // global blocks (the whole 64 x 64 grid, rel-pos terms as tensors): the same split planes, the terms from the split q
-  static int ps_glob_on = -1;     // HGL_ATTN_PS_GLOBAL=0: the global blocks keep the fp32-input kernels (A/B timing)
-  if (ps_glob_on < 0) ps_glob_on = HGL_DIAG_SWITCH("HGL_ATTN_PS_GLOBAL", 1) ? 1 : 0;
-  // both decisions are hgl_attention_ps_serves' (the predicate the launch itself applies: plane distance + one item's rows
-  // within 32 bits, shapes, registered tables), taken here because the in-projection below writes split planes only
-  const long long plane_delta = (long long)M * 3 * D * 2;
-  const bool ps_glob = x3 && ws == 0 && size == 64 && ps_glob_on &&
-                       hgl_attention_ps_serves(plane_delta, 3 * D, B, heads, S, hd, HGL_MASK_NONE, size, size, nullptr, nullptr) != 0;
-  const bool ps_win = x3 && ws == 14 &&
-                      hgl_attention_ps_serves(plane_delta, 3 * D, B, heads, S, hd, HGL_MASK_NONE, 0, 0, b.rel_pos_h, b.rel_pos_w) != 0;
-  if (x3) {
-    if (ws > 0 && M > T && padskip) {
-      // norm1 of the real tokens written straight to their rows of the padded window layout (the pad rows are never
-      // read: the GEMMs below gather the real tokens only)
-      HGL_TRY(hgl_launch_layernorm_split_maps(p.X, b.norm1_w, b.norm1_b, Ah, Al, T, D, 1e-6f, p.tok_of, p.pad_of, st));
-    } else if (ws > 0) {
-      HGL_TRY(hgl_launch_layernorm(p.X, b.norm1_w, b.norm1_b, p.H, T, D, 1e-6f, st));
-      for (int i = 0; i < p.nb; ++i)
-        HGL_TRY(hgl_launch_win_partition_split(p.H + (size_t)i * T1 * D, g, ws, nw, D, Ah + (size_t)i * M1 * D,
-                                               Al + (size_t)i * M1 * D, st));
-    } else {
-      HGL_TRY(hgl_launch_layernorm_split(p.X, b.norm1_w, b.norm1_b, Ah, Al, T, D, 1e-6f, st));
+// The geometry of a block and everything that is decided about its launches
+struct EncBlockRoute {
+  int D, g, heads, hd;
+  int T1, T;            // tokens of one image; token rows of the batch (images stacked along the rows)
+  int ws, size, nw;     // window (0: global attention), attention grid side, windows per grid side
+  int B1, B;            // windows of one image (1 for global attention), of the batch
+  int S, M1, M;         // tokens per window; padded rows of one image, of the batch
+  int L;                // rel-pos table length
+  bool x3;              // the split-fp16 path: every GEMM operand activation exists only as fp16 hi | lo planes
+  EncAttn attn;
+  bool gather;          // the windowed GEMMs read and write the real tokens only (the window does not divide the grid)
+  bool planes;          // the in-projection writes q | k | v as fp16 hi / lo planes (same bytes as the fp32 tensor)
+};
+
+int enc_block_route(const HglSamEncoderW* w, const HglSamBlockW& b, int nb, EncBlockRoute& r) {
+  r.D = w->embed_dim, r.g = w->img_size / w->patch, r.heads = w->heads, r.hd = r.D / r.heads;
+  r.T1 = r.g * r.g, r.T = nb * r.T1;
+  r.ws = b.window, r.size = r.ws > 0 ? r.ws : r.g, r.nw = r.ws > 0 ? (r.g + r.ws - 1) / r.ws : 1;
+  r.B1 = r.nw * r.nw, r.B = nb * r.B1;
+  r.S = r.size * r.size, r.M1 = r.B1 * r.S, r.M = r.B * r.S;
+  r.L = b.rel_len;
+  HGL_REQUIRE(r.L == 2 * r.size - 1, "sam_encode: rel_pos length %d does not match attention size %d", r.L, r.size);
+  const int D = r.D;
+  r.x3 = hgl_use_x3(b.qkv_w, D) && hgl_use_x3(b.proj_w, D) && hgl_use_x3(b.lin1_w, D) && hgl_use_x3(b.lin2_w, 4 * D) &&
+         (D % 256) == 0;
+  static const int padskip = HGL_DIAG_SWITCH("HGL_SAM_PADSKIP", 1);   // 0: the windowed GEMMs run over the padded rows as well (A/B timing)
+  // only the real tokens go through the windowed GEMMs (16 % fewer rows at 64x64 / 14x14)
+  r.gather = r.x3 && r.ws > 0 && r.M > r.T && padskip;
+  static const int ps_glob_on = HGL_DIAG_SWITCH("HGL_ATTN_PS_GLOBAL", 1);   // 0: the global blocks keep the fp32-input kernels (A/B timing)
+  // both pre-split decisions are hgl_attention_ps_serves' (the predicate the launch itself applies: plane distance + one item's
+  // rows within 32 bits, shapes, registered tables), taken here because the in-projection writes split planes only
+  const long long plane_delta = (long long)r.M * 3 * D * 2;
+  const bool ps_glob = r.x3 && r.ws == 0 && r.size == 64 && ps_glob_on &&
+                       hgl_attention_ps_serves(plane_delta, 3 * D, r.B, r.heads, r.S, r.hd, HGL_MASK_NONE, r.size, r.size, nullptr, nullptr) != 0;
+  const bool ps_win = r.x3 && r.ws == 14 &&
+                      hgl_attention_ps_serves(plane_delta, 3 * D, r.B, r.heads, r.S, r.hd, HGL_MASK_NONE, 0, 0, b.rel_pos_h, b.rel_pos_w) != 0;
+  r.attn = ps_win ? ENC_ATTN_PS_WIN : ps_glob ? ENC_ATTN_PS_GLOBAL : (r.x3 && r.ws == 14 && r.hd == 80) ? ENC_ATTN_WIN14 : ENC_ATTN_TABLES;
+  r.planes = r.attn == ENC_ATTN_PS_WIN || r.attn == ENC_ATTN_PS_GLOBAL;
+  return HGL_OK;
+}
+
+// the fp16 hi | lo planes of the split path: each pair aliases an fp32 buffer of the plan (same bytes)
+struct EncPlanes {
+  uint16_t *Ah, *Al;    // GEMM input in window order, later the attention's output (the window buffer)
+  uint16_t *Hh, *Hl;    // norm2 (H)
+  uint16_t *Fh, *Fl;    // mlp.lin1 (F)
+  uint16_t *Qh, *Ql;    // split qkv (QKV)
+  EncPlanes(const EncPlan& p, const EncBlockRoute& r)
+      : Ah((uint16_t*)p.Hw), Al(Ah + (size_t)r.M * r.D), Hh((uint16_t*)p.H), Hl(Hh + (size_t)r.T * r.D), Fh((uint16_t*)p.F),
+        Fl(Fh + (size_t)r.T * 4 * r.D), Qh((uint16_t*)p.QKV), Ql(Qh + (size_t)r.M * 3 * r.D) {}
+};
+
+// attention of the B windows (or whole grids) on p.QKV -> the planes Ah | Al (x3) or p.O (fp32)
+int enc_attention(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, hipStream_t st) {
+  const int D = r.D, B = r.B, S = r.S, M = r.M, L = r.L, heads = r.heads, hd = r.hd, size = r.size;
+  const EncPlanes s(p, r);
+  const float scale = 1.0f / sqrtf((float)hd);
+  if (r.planes) {
+    const float *rel_h = nullptr, *rel_w = nullptr, *tab_h = b.rel_pos_h, *tab_w = b.rel_pos_w;
+    int rel_k = 0;
+    if (r.attn == ENC_ATTN_PS_GLOBAL) {
+      HGL_TRY(hgl_launch_relpos_split(s.Qh, s.Ql, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
+      rel_h = p.relh, rel_w = p.relw, rel_k = size, tab_h = tab_w = nullptr;
     }
-    // q | k | v as fp16 hi / lo planes (the in-projection's write-out splits; same bytes as the fp32 tensor) for the attention
-    // kernel that stages them by LDS-DMA without converting (attention_ps.hip): the 14 x 14 windows at head dim 80
-    if (ps_glob) {
-      HGL_TRY(hgl_launch_gemm_f16x3(Ah, Al, D, b.qkv_w, b.qkv_b, nullptr, 0, nullptr, Qh, Ql, 3 * D, M, 3 * D, D, HGL_ACT_NONE, st));
-    } else if (ps_win) {
-      if (M > T && padskip) {
-        HGL_TRY(hgl_launch_fill_rows_split(Qh, Ql, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st));
-        HGL_TRY(hgl_launch_gemm_f16x3_maps(Ah, Al, D, p.pad_of, b.qkv_w, b.qkv_b, nullptr, 0, 0, p.pad_of, nullptr, Qh, Ql, 3 * D,
-                                           T, 3 * D, D, HGL_ACT_NONE, st));
-      } else {
-        HGL_TRY(hgl_launch_gemm_f16x3(Ah, Al, D, b.qkv_w, b.qkv_b, nullptr, 0, nullptr, Qh, Ql, 3 * D, M, 3 * D, D, HGL_ACT_NONE, st));
-      }
-    } else if (ws > 0 && M > T && padskip) {
-      // only the real tokens go through the GEMM (16 % fewer rows at 64x64 / 14x14); a padded row of qkv is the bias
-      HGL_TRY(hgl_launch_fill_rows(p.QKV, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st));
-      HGL_TRY(hgl_launch_gemm_f16x3_maps(Ah, Al, D, p.pad_of, b.qkv_w, b.qkv_b, nullptr, 0, 0, p.pad_of, p.QKV, nullptr,
-                                         nullptr, 3 * D, T, 3 * D, D, HGL_ACT_NONE, st));
-    } else {
-      HGL_TRY(hgl_launch_gemm_f16x3(Ah, Al, D, b.qkv_w, b.qkv_b, nullptr, 0, p.QKV, nullptr, nullptr, 3 * D, M, 3 * D, D,
-                                    HGL_ACT_NONE, st));
-    }
-  } else {
-    HGL_TRY(hgl_launch_layernorm(p.X, b.norm1_w, b.norm1_b, p.H, T, D, 1e-6f, st));
-    const float* A = p.H;
-    if (ws > 0) {
-      for (int i = 0; i < p.nb; ++i)
-        HGL_TRY(hgl_launch_win_partition(p.H + (size_t)i * T1 * D, g, ws, nw, D, p.Hw + (size_t)i * M1 * D, st));
-      A = p.Hw;
-    }
-    HGL_TRY(hgl_launch_gemm(A, b.qkv_w, b.qkv_b, nullptr, p.QKV, M, 3 * D, D, D, D, 0, 3 * D, 1, 0, 0, 0, 0,
-                            HGL_ACT_NONE, st));
-  }
-  if (ps_win) {
-    const int rc = hgl_launch_attention_ps(Qh, Ql, 3 * D, 0, D, 2 * D, S, B, heads, S, hd, nullptr, Ah, Al, D, (long long)S * D,
-                                           1.0f / sqrtf((float)hd), HGL_MASK_NONE, nullptr, 0, 0, nullptr, nullptr, 0, 0,
-                                           b.rel_pos_h, b.rel_pos_w, st);
+    const int rc = hgl_launch_attention_ps(s.Qh, s.Ql, 3 * D, 0, D, 2 * D, S, B, heads, S, hd, nullptr, s.Ah, s.Al, D, (long long)S * D,
+                                           scale, HGL_MASK_NONE, nullptr, 0, 0, rel_h, rel_w, rel_k, rel_k, tab_h, tab_w, st);
     if (rc < 0) return rc;
     HGL_REQUIRE(rc == 0, "sam_encode: the pre-split attention refused a shape its caller had checked");
-    goto attention_done;
+    return HGL_OK;
   }
-  if (ps_glob) {
-    HGL_TRY(hgl_launch_relpos_split(Qh, Ql, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
-    const int rc = hgl_launch_attention_ps(Qh, Ql, 3 * D, 0, D, 2 * D, S, B, heads, S, hd, nullptr, Ah, Al, D, (long long)S * D,
-                                           1.0f / sqrtf((float)hd), HGL_MASK_NONE, nullptr, 0, 0, p.relh, p.relw, size, size,
-                                           nullptr, nullptr, st);
-    if (rc < 0) return rc;
-    HGL_REQUIRE(rc == 0, "sam_encode: the pre-split attention refused a shape its caller had checked");
-    goto attention_done;
-  }
-  // 14 x 14 windows at head dim 80 in f16x3 mode: the attention kernel computes the decomposed rel-pos terms itself
-  if (x3 && ws == 14 && hd == 80) {
-    const int rc = hgl_launch_attention_win14(p.QKV, p.QKV + D, p.QKV + 2 * D, Ah, Al, B, heads, hd, 3 * D, 3 * D, 3 * D, D,
+  if (r.attn == ENC_ATTN_WIN14) {
+    const int rc = hgl_launch_attention_win14(p.QKV, p.QKV + D, p.QKV + 2 * D, s.Ah, s.Al, B, heads, hd, 3 * D, 3 * D, 3 * D, D,
                                               (long long)S * 3 * D, (long long)S * 3 * D, (long long)S * 3 * D, (long long)S * D,
-                                              1.0f / sqrtf((float)hd), b.rel_pos_h, b.rel_pos_w, st);
-    if (rc < 0) return rc;
-    if (rc == 0) goto attention_done;
+                                              scale, b.rel_pos_h, b.rel_pos_w, st);
+    if (rc <= 0) return rc;   // (> 0: the kernel declines, e.g. tables that are not registered -> the rel-pos tables below)
   }
   // decomposed rel-pos tables rel_h/rel_w [B*heads, S, size] from the UNSCALED q (image_encoder.py:351-354)
   if (hd == 80 || hd == 64) {
@@ -184,57 +164,82 @@ int enc_block(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPlan& p, 
     HGL_TRY(hgl_launch_relpos_gather(p.Tw, B, heads, S, size, L, 1, p.relw, st));
   }
   // f16x3: the attention writes its output as the fp16 hi+lo pair the projection reads
-  HGL_TRY(hgl_launch_attention_split(p.QKV, p.QKV + D, p.QKV + 2 * D, x3 ? nullptr : p.O, Ah, Al, B, heads, S, S, hd, 3 * D,
-                                     3 * D, 3 * D, D, (long long)S * 3 * D, (long long)S * 3 * D, (long long)S * 3 * D,
-                                     (long long)S * D, 1.0f / sqrtf((float)hd), HGL_MASK_NONE, nullptr, 0, 0, p.relh,
-                                     p.relw, size, size, st));
-attention_done:
-  if (x3) {
-    static int splitk_proj = -1;   // HGL_SAM_SPLITK_PROJ=1 enables split-K for the projection too (measured neutral: K is short)
-    if (splitk_proj < 0) splitk_proj = HGL_DIAG_SWITCH("HGL_SAM_SPLITK_PROJ", 0) ? 1 : 0;
-    const int ksp = splitk_proj ? hgl_gemm_f16x3_splitk_factor(T, D, D) : 1;
-    const size_t qkv_cap = (size_t)M * 3 * D * sizeof(float);     // q, k, v are dead after the attention
-    const bool proj_splitk = ksp > 1 && (size_t)ksp * T * D * sizeof(float) <= qkv_cap && (ws == 0 || (M > T && padskip));
-    if (proj_splitk) {
-      // few 256x256 tiles: split-K over the idle CUs; real tokens only, written to token order with the residual
-      HGL_TRY(hgl_launch_gemm_f16x3_splitk(Ah, Al, D, ws > 0 ? p.pad_of : nullptr, b.proj_w, b.proj_b, p.X, D,
-                                           ws > 0 ? p.tok_of : nullptr, p.X, D, T, D, D, HGL_ACT_NONE, ksp, p.QKV, qkv_cap, st));
-    } else if (ws > 0 && M > T && padskip) {
-      // projection of the real tokens only, written straight back to token order with the residual added
-      // (window_unpartition + shortcut, image_encoder.py:178-180)
-      HGL_TRY(hgl_launch_gemm_f16x3_balanced(Ah, Al, D, p.pad_of, b.proj_w, b.proj_b, p.X, D, p.tok_of, p.X, D, T, D, D, HGL_ACT_NONE,
-                                             p.QKV, qkv_cap, st));
-    } else if (ws > 0) {
-      HGL_TRY(hgl_launch_gemm_f16x3(Ah, Al, D, b.proj_w, b.proj_b, nullptr, 0, p.P, nullptr, nullptr, D, M, D, D,
-                                    HGL_ACT_NONE, st));
-      for (int i = 0; i < p.nb; ++i)
-        HGL_TRY(hgl_launch_win_unpartition_add(p.X + (size_t)i * T1 * D, g, ws, nw, D, p.P + (size_t)i * M1 * D, st));
-    } else {
-      HGL_TRY(hgl_launch_gemm_f16x3_balanced(Ah, Al, D, nullptr, b.proj_w, b.proj_b, p.X, D, nullptr, p.X, D, T, D, D, HGL_ACT_NONE,
-                                             p.QKV, qkv_cap, st));
-    }
-    HGL_TRY(hgl_launch_layernorm_split(p.X, b.norm2_w, b.norm2_b, Hh, Hl, T, D, 1e-6f, st));
-    HGL_TRY(hgl_launch_gemm_f16x3(Hh, Hl, D, b.lin1_w, b.lin1_b, nullptr, 0, nullptr, Fh, Fl, 4 * D, T, 4 * D, D,
-                                  HGL_ACT_GELU, st));
-    // mlp.lin2: few output tiles, K = 4D -> split-K over the idle CUs; the partial sums borrow the qkv buffer
-    static int splitk_on = -1;   // HGL_SAM_SPLITK=0 disables (A/B timing)
-    if (splitk_on < 0) splitk_on = HGL_DIAG_SWITCH("HGL_SAM_SPLITK", 1) ? 1 : 0;
-    const int ks = splitk_on ? hgl_gemm_f16x3_splitk_factor(T, D, 4 * D) : 1;
-    const size_t qkv_bytes = (size_t)M * 3 * D * sizeof(float);
-    if (ks > 1 && (size_t)ks * T * D * sizeof(float) <= qkv_bytes) {
-      HGL_TRY(hgl_launch_gemm_f16x3_splitk(Fh, Fl, 4 * D, nullptr, b.lin2_w, b.lin2_b, p.X, D, nullptr, p.X, D, T, D, 4 * D,
-                                           HGL_ACT_NONE, ks, p.QKV, qkv_bytes, st));
-    } else {
-      HGL_TRY(hgl_launch_gemm_f16x3_balanced(Fh, Fl, 4 * D, nullptr, b.lin2_w, b.lin2_b, p.X, D, nullptr, p.X, D, T, D, 4 * D, HGL_ACT_NONE,
-                                             p.QKV, qkv_bytes, st));
-    }
-    return HGL_OK;
+  return hgl_launch_attention_split(p.QKV, p.QKV + D, p.QKV + 2 * D, r.x3 ? nullptr : p.O, s.Ah, s.Al, B, heads, S, S, hd, 3 * D,
+                                    3 * D, 3 * D, D, (long long)S * 3 * D, (long long)S * 3 * D, (long long)S * 3 * D,
+                                    (long long)S * D, scale, HGL_MASK_NONE, nullptr, 0, 0, p.relh, p.relw, size, size, st);
+}
+
+// the block on the split-fp16 path
+int enc_block_x3(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, hipStream_t st) {
+  const int D = r.D, T = r.T, M = r.M, ws = r.ws;
+  const EncPlanes s(p, r);
+  // norm1 -> the split GEMM input in window order
+  if (r.gather) {
+    // the real tokens written straight to their rows of the padded window layout (the pad rows are never read: the GEMMs
+    // below gather the real tokens only)
+    HGL_TRY(hgl_launch_layernorm_split_maps(p.X, b.norm1_w, b.norm1_b, s.Ah, s.Al, T, D, 1e-6f, p.tok_of, p.pad_of, st));
+  } else if (ws > 0) {
+    HGL_TRY(hgl_launch_layernorm(p.X, b.norm1_w, b.norm1_b, p.H, T, D, 1e-6f, st));
+    for (int i = 0; i < p.nb; ++i)
+      HGL_TRY(hgl_launch_win_partition_split(p.H + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, s.Ah + (size_t)i * r.M1 * D,
+                                             s.Al + (size_t)i * r.M1 * D, st));
+  } else {
+    HGL_TRY(hgl_launch_layernorm_split(p.X, b.norm1_w, b.norm1_b, s.Ah, s.Al, T, D, 1e-6f, st));
   }
+  // in-projection, (fp32 qkv | planes) x (every row | the real tokens gathered: a padded row of qkv is the bias).  Planes:
+  // q | k | v as fp16 hi / lo planes (the write-out splits; same bytes as the fp32 tensor) for the attention kernel that stages
+  // them by LDS-DMA without converting (attention_ps.hip)
+  float* const Cf = r.planes ? nullptr : p.QKV;
+  uint16_t* const Ch = r.planes ? s.Qh : nullptr;
+  uint16_t* const Cl = r.planes ? s.Ql : nullptr;
+  if (r.gather) {
+    HGL_TRY(r.planes ? hgl_launch_fill_rows_split(s.Qh, s.Ql, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st)
+                     : hgl_launch_fill_rows(p.QKV, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st));
+    HGL_TRY(hgl_launch_gemm_f16x3_maps(s.Ah, s.Al, D, p.pad_of, b.qkv_w, b.qkv_b, nullptr, 0, 0, p.pad_of, Cf, Ch, Cl, 3 * D, T,
+                                       3 * D, D, HGL_ACT_NONE, st));
+  } else {
+    HGL_TRY(hgl_launch_gemm_f16x3(s.Ah, s.Al, D, b.qkv_w, b.qkv_b, nullptr, 0, Cf, Ch, Cl, 3 * D, M, 3 * D, D, HGL_ACT_NONE, st));
+  }
+  HGL_TRY(enc_attention(b, p, r, st));
+  const size_t qkv_bytes = (size_t)M * 3 * D * sizeof(float);     // q, k, v are dead after the attention
+  if (ws > 0 && !r.gather) {
+    HGL_TRY(hgl_launch_gemm_f16x3(s.Ah, s.Al, D, b.proj_w, b.proj_b, nullptr, 0, p.P, nullptr, nullptr, D, M, D, D, HGL_ACT_NONE, st));
+    for (int i = 0; i < p.nb; ++i)
+      HGL_TRY(hgl_launch_win_unpartition_add(p.X + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.P + (size_t)i * r.M1 * D, st));
+  } else {
+    // windows: the projection of the real tokens only, written straight back to token order with the residual added
+    // (window_unpartition + shortcut, image_encoder.py:178-180); global: every row where it is
+    HGL_TRY(hgl_launch_gemm_f16x3_balanced(s.Ah, s.Al, D, r.gather ? p.pad_of : nullptr, b.proj_w, b.proj_b, p.X, D,
+                                           r.gather ? p.tok_of : nullptr, p.X, D, T, D, D, HGL_ACT_NONE, p.QKV, qkv_bytes, st));
+  }
+  HGL_TRY(hgl_launch_layernorm_split(p.X, b.norm2_w, b.norm2_b, s.Hh, s.Hl, T, D, 1e-6f, st));
+  HGL_TRY(hgl_launch_gemm_f16x3(s.Hh, s.Hl, D, b.lin1_w, b.lin1_b, nullptr, 0, nullptr, s.Fh, s.Fl, 4 * D, T, 4 * D, D,
+                                HGL_ACT_GELU, st));
+  // mlp.lin2: few output tiles, K = 4D -> split-K over the idle CUs; the partial sums borrow the qkv buffer
+  static const int splitk_on = HGL_DIAG_SWITCH("HGL_SAM_SPLITK", 1);   // 0 disables (A/B timing)
+  const int ks = splitk_on ? hgl_gemm_f16x3_splitk_factor(T, D, 4 * D) : 1;
+  if (ks > 1 && (size_t)ks * T * D * sizeof(float) <= qkv_bytes)
+    return hgl_launch_gemm_f16x3_splitk(s.Fh, s.Fl, 4 * D, nullptr, b.lin2_w, b.lin2_b, p.X, D, nullptr, p.X, D, T, D, 4 * D,
+                                        HGL_ACT_NONE, ks, p.QKV, qkv_bytes, st);
+  return hgl_launch_gemm_f16x3_balanced(s.Fh, s.Fl, 4 * D, nullptr, b.lin2_w, b.lin2_b, p.X, D, nullptr, p.X, D, T, D, 4 * D,
+                                        HGL_ACT_NONE, p.QKV, qkv_bytes, st);
+}
+
+// the block on the fp32 kernels
+int enc_block_f32(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, hipStream_t st) {
+  const int D = r.D, T = r.T, M = r.M, ws = r.ws;
+  HGL_TRY(hgl_launch_layernorm(p.X, b.norm1_w, b.norm1_b, p.H, T, D, 1e-6f, st));
+  if (ws > 0)
+    for (int i = 0; i < p.nb; ++i)
+      HGL_TRY(hgl_launch_win_partition(p.H + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.Hw + (size_t)i * r.M1 * D, st));
+  HGL_TRY(hgl_launch_gemm(ws > 0 ? p.Hw : p.H, b.qkv_w, b.qkv_b, nullptr, p.QKV, M, 3 * D, D, D, D, 0, 3 * D, 1, 0, 0, 0, 0,
+                          HGL_ACT_NONE, st));
+  HGL_TRY(enc_attention(b, p, r, st));
   if (ws > 0) {
     HGL_TRY(hgl_launch_gemm(p.O, b.proj_w, b.proj_b, nullptr, p.P, M, D, D, D, D, 0, D, 1, 0, 0, 0, 0,
                             HGL_ACT_NONE, st));
     for (int i = 0; i < p.nb; ++i)
-      HGL_TRY(hgl_launch_win_unpartition_add(p.X + (size_t)i * T1 * D, g, ws, nw, D, p.P + (size_t)i * M1 * D, st));
+      HGL_TRY(hgl_launch_win_unpartition_add(p.X + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.P + (size_t)i * r.M1 * D, st));
   } else {
     HGL_TRY(hgl_launch_gemm(p.O, b.proj_w, b.proj_b, p.X, p.X, T, D, D, D, D, D, D, 1, 0, 0, 0, 0,
                             HGL_ACT_NONE, st));
@@ -242,17 +247,28 @@ attention_done:
   HGL_TRY(hgl_launch_layernorm(p.X, b.norm2_w, b.norm2_b, p.H, T, D, 1e-6f, st));
   HGL_TRY(hgl_launch_gemm(p.H, b.lin1_w, b.lin1_b, nullptr, p.F, T, 4 * D, D, D, D, 0, 4 * D, 1, 0, 0, 0, 0,
                           HGL_ACT_GELU, st));
-  HGL_TRY(hgl_launch_gemm(p.F, b.lin2_w, b.lin2_b, p.X, p.X, T, D, 4 * D, 4 * D, 4 * D, D, D, 1, 0, 0, 0, 0,
-                          HGL_ACT_NONE, st));
-  return HGL_OK;
+  return hgl_launch_gemm(p.F, b.lin2_w, b.lin2_b, p.X, p.X, T, D, 4 * D, 4 * D, 4 * D, D, D, 1, 0, 0, 0, 0,
+                         HGL_ACT_NONE, st);
+}
+
+int enc_block(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPlan& p, hipStream_t st) {
+  EncBlockRoute r;
+  HGL_TRY(enc_block_route(w, b, p.nb, r));
+  return r.x3 ? enc_block_x3(b, p, r, st) : enc_block_f32(b, p, r, st);
 }
 
 // ------------------------------------------------------------------------------ decoder
 struct DecPlan {
-  float *coords, *sparse, *tokens, *queries, *qpe, *q1, *k1, *v1, *att, *keys0, *kpe0, *keys, *kpe, *kp, *vp,
+  float *sparse, *tokens, *queries, *qpe, *q1, *k1, *v1, *att, *keys0, *kpe0, *keys, *kpe, *kp, *vp,
       *qi, *atti, *mlp, *u1, *u2, *hy_a, *hy_b, *hyper, *iou_a, *iou_b, *keysS;
   uint8_t* skip;      // IoU gate: prompts whose upscaling is skipped
 };
+
+// the two buffers that also serve as scratch (layouts below): their sizes, for carve_dec and for the route's capacity conditions
+// kp: k / v / q projections of the image tokens: three [P*HW, C/2] matrices, or -- merged projections -- ONE [P*HW, 3C/2]
+inline size_t dec_kp_floats(const HglSamDecoderW* w, size_t P) { return 3 * (P * ((size_t)w->grid * w->grid) * w->C / 2); }
+// atti: the image -> token attention's output [P*HW, C/2]
+inline size_t dec_atti_floats(const HglSamDecoderW* w, size_t P) { return P * ((size_t)w->grid * w->grid) * w->C / 2; }
 
 // n_img > 1: the P prompts belong to n_img images (P / n_img each): one set of shared layer-0 image tokens per image
 bool carve_dec(HglArena& ar, const HglSamDecoderW* w, int P, DecPlan& p, int n_img = 1) {
@@ -269,11 +285,10 @@ bool carve_dec(HglArena& ar, const HglSamDecoderW* w, int P, DecPlan& p, int n_i
   p.kpe0 = ar.take<float>(n_img * HW * C);
   p.keys = ar.take<float>(P * HW * C);
   p.kpe = ar.take<float>(P * HW * C);
-  // k / v / q projections of the image tokens: three [P*HW, C/2] matrices, or -- merged projections -- ONE [P*HW, 3C/2]
-  p.kp = ar.take<float>(3 * (P * HW * C / 2));
+  p.kp = ar.take<float>(dec_kp_floats(w, P));
   p.vp = p.kp ? p.kp + P * HW * C / 2 : nullptr;
   p.qi = p.kp ? p.kp + 2 * (P * HW * C / 2) : nullptr;
-  p.atti = ar.take<float>(P * HW * C / 2);
+  p.atti = ar.take<float>(dec_atti_floats(w, P));
   p.mlp = ar.take<float>(P * T * w->mlp_dim);
   p.u1 = ar.take<float>(P * HW * C);           // [P*HW*4, C/4]
   p.u2 = ar.take<float>(P * HW * 16 * (C / 8)); // [P*HW*16, C/8]
@@ -328,27 +343,52 @@ inline int lin_sets(const float* A, int lda, const HglLinearW& l, float* Cc, int
 }
 
 // which fused decoder stages are in use (bit 0: upscaling + hyper-network products, bit 1: merged image-side projections,
-// bit 2: image -> token attention + out-projection + norm4, bit 3: unused, bit 4: chunked token -> image attention);
-// default: all stages fused
+// bit 2: image -> token attention + out-projection + norm4, bit 3: unused, bit 4: chunked token -> image attention,
+// bit 5: token -> image attention on the raw image-token planes); default: all stages fused
 int g_dec_fusion = -1;
 int dec_fusion_mask() {
   if (g_dec_fusion < 0) g_dec_fusion = HGL_DIAG_SWITCH("HGL_SAM_DEC_FUSED", 0x7fffffff);   // product: hgl_sam_decoder_fusion()
   return g_dec_fusion;
 }
 
-// token -> image attention (7 queries, thousands of keys): the chunked kernel when the shape fits (fusion bit 4), with the
-// partials in `scratch` (the image -> token buffer, idle at that point)
+// ---- scratch layouts: DecPlan::atti, idle whenever tokens attend to the image, serves three other purposes and DecPlan::kp
+// one; each layout gives its pointers and its byte count side by side, and dec_route's capacity conditions call bytes() ----
+// (1) the partials of the chunked few-query attention: hgl_attention_fewq_part_bytes(B, Nk), see dec_fewq
+// (2) the raw token -> image attention: the folded queries Q' [P*56, C] as fp16 hi | lo planes, then [P*56, C] floats that hold Q' in fp32 first and
+// the attended rows afterwards, then the key-range partial rows (counted for one key range as well, where nothing is written
+// there: the attended rows leave the kernel directly)
+struct RawT2iScratch {
+  uint16_t *Qh, *Ql;
+  float *A, *part;
+  RawT2iScratch(float* atti, int P, int C)
+      : Qh((uint16_t*)atti), Ql(Qh + (size_t)P * 56 * C), A((float*)(Ql + (size_t)P * 56 * C)), part(A + (size_t)P * 56 * C) {}
+  static size_t bytes(int P, int n_img, int ppi, int HW, int C) { return (size_t)P * (56 * C * 8) + n_img * hgl_t2i_part_bytes(ppi, HW); }
+};
+// (3) the folded image -> token step: K' [P*56, C] hi | lo, the U fragments [P, 16, 2, 64, 8] hi | lo, cb [P*56] floats (256
+// bytes a prompt)
+struct I2tFoldScratch {
+  uint16_t *Kh, *Kl, *Uh, *Ul;
+  float* cb;
+  I2tFoldScratch(float* atti, int P, int C)
+      : Kh((uint16_t*)atti), Kl(Kh + (size_t)P * 56 * C), Uh(Kl + (size_t)P * 56 * C), Ul(Uh + (size_t)P * 16384),
+        cb((float*)(Ul + (size_t)P * 16384)) {}
+  static size_t bytes(int P, int C) { return (size_t)P * (56 * C * 4 + 16384 * 4 + 256); }
+};
+// kp as the positional bias [P*56, HW] of (2) and (3): the folded rows against dense_pe
+inline size_t dec_bias_bytes(int P, int HW) { return (size_t)P * 56 * HW * sizeof(float); }
+
+// token -> image attention (7 queries, thousands of keys): the chunked kernel where the route says it serves (DecRoute::chunked:
+// part != null), with the partials in `part` (the image -> token buffer, idle at that point)
 int dec_fewq(const float* q, const float* k, const float* v, float* att, int B, int heads, int Nq, int Nk, int hd, int ldq,
-             int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb, long long sob, float* scratch,
-             size_t scratch_bytes, hipStream_t st, int kv_group = 1) {
+             int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb, long long sob, float* part,
+             size_t part_bytes, hipStream_t st, int kv_group = 1) {
   const float scale = 1.0f / sqrtf((float)hd);
-  if ((dec_fusion_mask() & 16) && scratch && heads == 8 && hd == 16 && Nk >= 256 && B <= 65535 &&
-      scratch_bytes >= hgl_attention_fewq_part_bytes(B, Nk)) {
+  if (part) {
     // the chunked kernel holds up to 7 queries: longer prompts (more sparse tokens) go through it 7 queries at a time
     for (int q0 = 0; q0 < Nq; q0 += 7)
       HGL_TRY(hgl_launch_attention_fewq_chunked(q + (long long)q0 * ldq, k, v, att + (long long)q0 * ldo, B, heads,
                                                 Nq - q0 < 7 ? Nq - q0 : 7, Nk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb, sob, scale,
-                                                scratch, scratch_bytes, st, kv_group));
+                                                part, part_bytes, st, kv_group));
     return HGL_OK;
   }
   HGL_REQUIRE(kv_group == 1, "sam_decode: keys shared by groups of %d prompts need the chunked attention", kv_group);
@@ -360,7 +400,7 @@ int dec_fewq(const float* q, const float* k, const float* v, float* att, int B, 
 // Nq rows serve every batch (batch stride 0).  out: [B, Nq, C] (+ residual R, may alias out).
 int dec_attn(const HglSamDecoderW* w, const HglSamAttnW& a, const float* q, bool q_shared, int Nq, const float* k,
              const float* v, bool kv_shared, int Nk, int B, float* qp, float* kp, float* vp, float* att,
-             const float* R, long long sR, float* out, hipStream_t st, float* scratch = nullptr, size_t scratch_bytes = 0,
+             const float* R, long long sR, float* out, hipStream_t st, float* part = nullptr, size_t part_bytes = 0,
              int kv_sets = 1) {
   const int C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
   const int Bq = q_shared ? 1 : B, Bk = kv_shared ? 1 : B;
@@ -370,13 +410,12 @@ int dec_attn(const HglSamDecoderW* w, const HglSamAttnW& a, const float* q, bool
     HGL_TRY(lin_sets(k, C, a.k, kp, I, Nk, kv_sets, I, C, st));
     HGL_TRY(lin_sets(v, C, a.v, vp, I, Nk, kv_sets, I, C, st));
     HGL_TRY(dec_fewq(qp, kp, vp, att, B, heads, Nq, Nk, hd, I, I, I, I, (long long)Nq * I, (long long)Nk * I, (long long)Nk * I,
-                     (long long)Nq * I, scratch, scratch_bytes, st, B / kv_sets));
+                     (long long)Nq * I, part, part_bytes, st, B / kv_sets));
   } else {
     HGL_TRY(lin(k, C, a.k, nullptr, 0, kp, I, Bk * Nk, I, C, HGL_ACT_NONE, st));
     HGL_TRY(lin(v, C, a.v, nullptr, 0, vp, I, Bk * Nk, I, C, HGL_ACT_NONE, st));
     HGL_TRY(dec_fewq(qp, kp, vp, att, B, heads, Nq, Nk, hd, I, I, I, I, q_shared ? 0 : (long long)Nq * I,
-                     kv_shared ? 0 : (long long)Nk * I, kv_shared ? 0 : (long long)Nk * I, (long long)Nq * I, scratch,
-                     scratch_bytes, st));
+                     kv_shared ? 0 : (long long)Nk * I, kv_shared ? 0 : (long long)Nk * I, (long long)Nq * I, part, part_bytes, st));
   }
   // out_proj (+ residual): one GEMM over all B*Nq rows when the residual is laid out like the output (small row
   // counts then take the small-tile kernel); batched when a shared residual (stride 0) has to be broadcast
@@ -401,104 +440,181 @@ bool dec_x3_ready(const HglSamDecoderW* w) {
   return true;
 }
 
-// image -> token attention of one layer (transformer.py:139-150): q = (keys + pe) Wq, 7 token keys / values,
-// keys' = keys + out_proj(attn)   (LayerNorm follows in the caller)
-int dec_i2t_x3(const HglSamDecoderW* w, const HglSamAttnW& a, bool shared, const float* kpe0, const SplitPair& kpeS,
-               const float* tok_k, const float* tok_v, int P, int HW, int T, float* qi, float* k1, float* v1, float* atti,
-               const float* R, int rmod, float* keys_out, hipStream_t st) {
-  const int C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
-  if (shared) {
-    HGL_TRY(lin(kpe0, C, a.q, nullptr, 0, qi, I, HW, I, C, HGL_ACT_NONE, st));
-  } else {
-    HGL_TRY(hgl_launch_gemm_f16x3(kpeS.hi, kpeS.lo, C, a.q.w, a.q.b, nullptr, 0, qi, nullptr, nullptr, I, P * HW, I, C,
-                                  HGL_ACT_NONE, st));
-  }
-  HGL_TRY(lin(tok_k, C, a.k, nullptr, 0, k1, I, P * T, I, C, HGL_ACT_NONE, st));
-  HGL_TRY(lin(tok_v, C, a.v, nullptr, 0, v1, I, P * T, I, C, HGL_ACT_NONE, st));
-  const SplitPair at = split_view(atti, (size_t)P * HW * I);
-  // (the few-key kernel for up to 8 tokens, the general one beyond)
-  HGL_TRY(hgl_launch_attention_split(qi, k1, v1, nullptr, at.hi, at.lo, P, heads, HW, T, hd, I, I, I, I,
-                                     shared ? 0 : (long long)HW * I, (long long)T * I, (long long)T * I, (long long)HW * I,
-                                     1.0f / sqrtf((float)hd), HGL_MASK_NONE, nullptr, 0, 0, nullptr, nullptr, 0, 0, st));
-  return hgl_launch_gemm_f16x3_rmod(at.hi, at.lo, I, a.out.w, a.out.b, R, C, rmod, keys_out, nullptr, nullptr, C, P * HW, C,
-                                    I, HGL_ACT_NONE, st);
-}
-
-// token -> image attention with per-prompt image tokens (transformer.py:126-131): K/V projections read the split planes
-int dec_t2i_x3(const HglSamDecoderW* w, const HglSamAttnW& a, const float* qpe, const SplitPair& kpeS, const SplitPair& keysS,
-               int P, int HW, int T, float* q1, float* kp, float* vp, float* att, float* queries, float* scratch,
-               size_t scratch_bytes, hipStream_t st) {
-  const int C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
-  HGL_TRY(lin(qpe, C, a.q, nullptr, 0, q1, I, P * T, I, C, HGL_ACT_NONE, st));
-  HGL_TRY(hgl_launch_gemm_f16x3(kpeS.hi, kpeS.lo, C, a.k.w, a.k.b, nullptr, 0, kp, nullptr, nullptr, I, P * HW, I, C,
-                                HGL_ACT_NONE, st));
-  HGL_TRY(hgl_launch_gemm_f16x3(keysS.hi, keysS.lo, C, a.v.w, a.v.b, nullptr, 0, vp, nullptr, nullptr, I, P * HW, I, C,
-                                HGL_ACT_NONE, st));
-  HGL_TRY(dec_fewq(q1, kp, vp, att, P, heads, T, HW, hd, I, I, I, I, (long long)T * I, (long long)HW * I, (long long)HW * I,
-                   (long long)T * I, scratch, scratch_bytes, st));
-  return lin(att, I, a.out, queries, C, queries, C, P * T, C, I, HGL_ACT_NONE, st);
-}
-
-// ---- merged image-side projections (HglSamDecoderW.kvq1 / kvf) ------------------------------------------------------
+// merged image-side projections (HglSamDecoderW.kvq1 / kvf): present and registered
 bool dec_merged_ready(const HglSamDecoderW* w) {
-  return (dec_fusion_mask() & 2) && w->kvq1_w && w->kvq1_b && w->kvq1_pe && w->kvf_w && w->kvf_b && w->kvf_pe &&
-         hgl_has_split_weight(w->kvq1_w) && hgl_has_split_weight(w->kvf_w);
+  return w->kvq1_w && w->kvq1_b && w->kvq1_pe && w->kvf_w && w->kvf_b && w->kvf_pe && hgl_has_split_weight(w->kvq1_w) &&
+         hgl_has_split_weight(w->kvf_w);
 }
 
-// kvq [P*HW, N] = keys W^T + b + pe_table[row % HW]   (N = 3I: k | v | q of layer 1;  N = 2I: k | v of the final attention)
-int dec_project_merged(const SplitPair& keysS, const float* W, const float* b, const float* pe_tab, int P, int HW, int C, int N,
-                       float* kvq, hipStream_t st) {
-  return hgl_launch_gemm_f16x3_rmod(keysS.hi, keysS.lo, C, W, b, pe_tab, N, HW, kvq, nullptr, nullptr, N, P * HW, N, C,
-                                    HGL_ACT_NONE, st);
+// ---- the route of one decoder call: every decision about its launches, taken by dec_route() from the weights, the shape of
+// the call and the fusion mask before anything is enqueued.  decode_impl and its helpers read these fields. ----
+struct DecRoute {
+  int P, n_img, ppi;     // prompts; images they belong to; prompts per image (prompt p belongs to image p / ppi)
+  int T, HW;             // tokens per prompt, image tokens
+  size_t atti_bytes;     // capacity of DecPlan::atti
+  bool x3;               // the image-token side on split planes
+  bool merged;           // merged image-side projections (fusion bit 1)
+  bool raw_t2i;          // token -> image attention of layer 1 and the final one on the raw planes (fusion bit 5)
+  bool shared[2];        // per layer: the image tokens are identical for every prompt of an image (layer 0 without dense prompts)
+  bool plain[2];         // per layer: per-prompt image tokens in layer 0 -> the plain fp32 launches
+  bool fuse_i2t[2];      // per layer: attention over the 7 tokens + out-projection + residual + norm4 in one launch (fusion bit 2)
+  bool chunked[3];       // token -> image attention of layer 0, layer 1, the final one: the chunked few-query kernel serves (fusion bit 4)
+  bool fused_tail;       // upscaling + hyper-network products in one launch (fusion bit 0)
+  int ns;                // key ranges per prompt of the raw attention
+  bool multi;            // the prompts of several images can share this launch sequence
+};
+
+DecRoute dec_route(const HglSamDecoderW* w, int P, int n_img, int n_sparse, bool dense, int fusion) {
+  DecRoute r;
+  const int C = w->C, g = w->grid, HW = g * g, T = 5 + n_sparse, heads = w->heads, I1 = w->layer[1].t2i.internal, ppi = P / n_img;
+  r.P = P, r.n_img = n_img, r.ppi = ppi, r.T = T, r.HW = HW;
+  r.atti_bytes = dec_atti_floats(w, P) * sizeof(float);
+  r.x3 = dec_x3_ready(w);
+  r.merged = r.x3 && (fusion & 2) && dec_merged_ready(w) && w->layer[1].t2i.internal == w->layer[1].i2t.internal &&
+             w->layer[1].t2i.internal == w->final_t2i.internal && 2 * w->final_t2i.internal == C;
+  // fusion bit 5: the token -> image attention of layer 1 and the final one on the raw image-token planes (the 7 tokens go
+  // through W_k / W_v instead of the HW image tokens: no k | v projection GEMM; layer 1 projects q alone for its step 4).
+  // Capacity: both reuses of atti, and kp as the bias of either
+  r.raw_t2i = r.merged && (fusion & 32) && (fusion & 4) && T == 7 && I1 == 128 && heads == 8 && C == 256 && HW % 128 == 0 &&
+              P <= 65535 && !dense && hgl_has_split_weight(w->dense_pe) &&
+              RawT2iScratch::bytes(P, n_img, ppi, HW, C) <= r.atti_bytes && I2tFoldScratch::bytes(P, C) <= r.atti_bytes &&
+              dec_bias_bytes(P, HW) <= dec_kp_floats(w, P) * sizeof(float);
+  // (prompt batches of <= 128: eight key ranges per prompt, see the kernel.  The batch that decides is the image's own, ppi,
+  // not the launch's total: a prompt's sums keep their order whether its image is decoded alone or with others)
+  r.ns = hgl_t2i_key_ranges(ppi, HW);
+  for (int li = 0; li < 2; ++li) {
+    r.shared[li] = li == 0 && !dense;   // keys identical for every prompt in layer 0
+    // layer 0 on per-prompt image tokens: the plain fp32 launches (the split planes / merged weights belong to layer 1's input)
+    r.plain[li] = li == 0 && dense;
+    r.fuse_i2t[li] = r.merged && (fusion & 4) && w->layer[li].i2t.internal == I1 && I1 == 128 && heads == 8 && HW % 64 == 0 &&
+                     P <= 65535 && T == 7 && !r.plain[li];
+  }
+  const HglSamAttnW* t2i[3] = {&w->layer[0].t2i, &w->layer[1].t2i, &w->final_t2i};
+  // the chunked kernel: 8 heads of 16, at least one chunk of keys, its partials in atti
+  for (int s = 0; s < 3; ++s)
+    r.chunked[s] = (fusion & 16) && heads == 8 && t2i[s]->internal / heads == 16 && HW >= 256 && P <= 65535 &&
+                   r.atti_bytes >= hgl_attention_fewq_part_bytes(P, HW);
+  // fused upscaling + hyper-network products (one launch, the 256-channel rows read once)
+  r.fused_tail = r.x3 && (fusion & 1) && (HW % 64) == 0 && (g % 64 == 0 || 64 % g == 0) && P <= 65535;
+  // Several images in ONE launch sequence: only layer 0 knows that prompts share image tokens; its two shared steps then need
+  // the kernels that address "the rows of image p / ppi": the chunked token -> image attention and the fused image -> token step
+  r.multi = r.shared[0] && r.fuse_i2t[0] && r.chunked[0];
+  return r;
 }
 
-// token -> image attention on merged projections: k = kvq[:, 0:I], v = kvq[:, I:2I], row stride ld
-int dec_t2i_merged(const HglSamDecoderW* w, const HglSamAttnW& a, const float* qpe, const float* kvq, int ld, int P, int HW,
-                   int T, float* q1, float* att, float* queries, float* scratch, size_t scratch_bytes, hipStream_t st) {
-  const int C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
-  HGL_TRY(lin(qpe, C, a.q, nullptr, 0, q1, I, P * T, I, C, HGL_ACT_NONE, st));
-  HGL_TRY(dec_fewq(q1, kvq, kvq + I, att, P, heads, T, HW, hd, I, ld, ld, I, (long long)T * I, (long long)HW * ld,
-                   (long long)HW * ld, (long long)T * I, scratch, scratch_bytes, st));
-  return lin(att, I, a.out, queries, C, queries, C, P * T, C, I, HGL_ACT_NONE, st);
+// steps (2) of a layer (step 0 / 1) and the final attention (step 2): the tokens attend to the image (transformer.py:126-131,
+// :98-104), queries += out_proj(attn): plain, or -- layer 1 and the final attention of the split path -- raw, merged or split
+int dec_t2i(const DecRoute& r, const HglSamDecoderW* w, const HglSamAttnW& a, int step, const DecPlan& p, const SplitPair& keysS,
+            const SplitPair& kpeS, hipStream_t st) {
+  const int P = r.P, HW = r.HW, T = r.T, C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
+  float* const part = r.chunked[step] ? p.atti : nullptr;   // the chunked attention's partials
+  const long long sq = (long long)T * I, sk = (long long)HW * I;   // batch strides of the projected tokens / image tokens
+  if (step == 0 || !r.x3) {   // fp32 projections of the image tokens; the only form for layer 0
+    const bool shared = step < 2 && r.shared[step];
+    return dec_attn(w, a, p.qpe, false, T, shared ? p.kpe0 : p.kpe, shared ? p.keys0 : p.keys, shared, HW, P, p.q1, p.kp, p.vp, p.att,
+                    p.queries, (long long)T * C, p.queries, st, part, r.atti_bytes, shared ? r.n_img : 1);
+  }
+  const bool merged = r.merged && !r.raw_t2i, fin = step == 2;
+  const int N = fin ? 2 * I : 3 * I;
+  if (merged)
+    // k, v of this step and (layer 1) q of step (4) read the same rows: one GEMM, the positional encoding as a per-position
+    // table.  kvq [P*HW, N] = keys W^T + b + pe_table[row % HW]; N = 3I: k | v | q of layer 1 (kvq1), N = 2I: k | v of the final
+    // attention (kvf)
+    HGL_TRY(hgl_launch_gemm_f16x3_rmod(keysS.hi, keysS.lo, C, fin ? w->kvf_w : w->kvq1_w, fin ? w->kvf_b : w->kvq1_b,
+                                       fin ? w->kvf_pe : w->kvq1_pe, N, HW, p.kp, nullptr, nullptr, N, P * HW, N, C, HGL_ACT_NONE, st));
+  HGL_TRY(lin(p.qpe, C, a.q, nullptr, 0, p.q1, I, P * T, I, C, HGL_ACT_NONE, st));
+  if (r.raw_t2i) {
+    // no projection of the image tokens at all (sam_decoder_t2i.hip): the 7 tokens are projected through W_k / W_v instead of
+    // the HW image tokens, the attention reads the raw planes, its positional term in p.kp
+    const RawT2iScratch s(p.atti, P, C);
+    HGL_TRY(hgl_launch_t2i_fold_q(p.q1, a.k.w, 1.0f / sqrtf((float)hd), s.A, P, st));
+    HGL_TRY(hgl_launch_split_f16(s.A, 1.0f, s.Qh, s.Ql, (long long)P * 56 * C, st));
+    // bias[p*56 + r, key] = Qk[p*56 + r, :] . pe[key, :]: pe is the "weight" [HW, C] of a split-fp16 GEMM
+    HGL_TRY(hgl_launch_gemm_f16x3(s.Qh, s.Ql, C, w->dense_pe, nullptr, nullptr, 0, p.kp, nullptr, nullptr, HW, P * 56, HW, C,
+                                  HGL_ACT_NONE, st));
+    // several key ranges: their partial rows behind the folded queries; one: the attended rows over the folded queries
+    float* const rows = r.ns > 1 ? s.part : s.A;
+    HGL_TRY(hgl_launch_t2i_raw_attn(s.Qh, s.Ql, p.kp, keysS.hi, keysS.lo, P, HW, rows, r.ns, st));
+    HGL_TRY(hgl_launch_t2i_unfold_v(rows, r.ns, a.v.w, a.v.b, p.att, P, st));
+  } else if (merged) {   // k = kvq[:, 0:I], v = kvq[:, I:2I], row stride N
+    HGL_TRY(dec_fewq(p.q1, p.kp, p.kp + I, p.att, P, heads, T, HW, hd, I, N, N, I, sq, (long long)HW * N, (long long)HW * N, sq, part,
+                     r.atti_bytes, st));
+  } else {
+    // per-prompt image tokens (transformer.py:126-131): the K / V projections read the split planes
+    HGL_TRY(hgl_launch_gemm_f16x3(kpeS.hi, kpeS.lo, C, a.k.w, a.k.b, nullptr, 0, p.kp, nullptr, nullptr, I, P * HW, I, C,
+                                  HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm_f16x3(keysS.hi, keysS.lo, C, a.v.w, a.v.b, nullptr, 0, p.vp, nullptr, nullptr, I, P * HW, I, C,
+                                  HGL_ACT_NONE, st));
+    HGL_TRY(dec_fewq(p.q1, p.kp, p.vp, p.att, P, heads, T, HW, hd, I, I, I, I, sq, sk, sk, sq, part, r.atti_bytes, st));
+  }
+  return lin(p.att, I, a.out, p.queries, C, p.queries, C, P * T, C, I, HGL_ACT_NONE, st);
 }
 
-// token -> image attention on the RAW image-token planes (sam_decoder_t2i.hip): the 7 tokens are projected through W_k / W_v
-// instead of the HW image tokens.  Scratch: `small` (>= P * 56 * 256 * 8 bytes: the folded queries' planes + the attended
-// rows), `bias` (P * 56 * HW floats).
-int dec_t2i_raw(const HglSamDecoderW* w, const HglSamAttnW& a, const float* qpe, const SplitPair& keysS, int P, int ppi, int HW,
-                int T, float* q1, float* small, float* bias, float* att, float* queries, hipStream_t st) {
-  const int C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
-  HGL_TRY(lin(qpe, C, a.q, nullptr, 0, q1, I, P * T, I, C, HGL_ACT_NONE, st));
-  uint16_t* Qh = (uint16_t*)small;
-  uint16_t* Ql = Qh + (size_t)P * 56 * C;
-  float* A = (float*)(Ql + (size_t)P * 56 * C);      // first the folded queries in fp32, then the attended rows
-  HGL_TRY(hgl_launch_t2i_fold_q(q1, a.k.w, 1.0f / sqrtf((float)hd), A, P, st));
-  HGL_TRY(hgl_launch_split_f16(A, 1.0f, Qh, Ql, (long long)P * 56 * C, st));
-  // bias[p*56 + r, key] = Qk[p*56 + r, :] . pe[key, :]: pe is the "weight" [HW, C] of a split-fp16 GEMM
-  HGL_TRY(hgl_launch_gemm_f16x3(Qh, Ql, C, w->dense_pe, nullptr, nullptr, 0, bias, nullptr, nullptr, HW, P * 56, HW, C,
-                                HGL_ACT_NONE, st));
-  // (prompt batches of <= 128: eight key ranges per prompt, their partial rows behind the folded queries; see the kernel.
-  // The batch that decides is the image's own, ppi, not the launch's total: a prompt's sums keep their order whether its
-  // image is decoded alone or with others)
-  const int ns = hgl_t2i_key_ranges(ppi, HW);
-  float* const rows = ns > 1 ? A + (size_t)P * 56 * C : A;
-  HGL_TRY(hgl_launch_t2i_raw_attn(Qh, Ql, bias, keysS.hi, keysS.lo, P, HW, rows, ns, st));
-  HGL_TRY(hgl_launch_t2i_unfold_v(rows, ns, a.v.w, a.v.b, att, P, st));
-  return lin(att, I, a.out, queries, C, queries, C, P * T, C, I, HGL_ACT_NONE, st);
-}
-
-// image -> token attention on merged projections: q = kvq[:, 2I:3I]
-int dec_i2t_merged(const HglSamDecoderW* w, const HglSamAttnW& a, const float* kvq, int ld, const float* tok_k, const float* tok_v,
-                   int P, int HW, int T, float* k1, float* v1, float* atti, const float* R, float* keys_out, hipStream_t st) {
-  const int C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
-  HGL_TRY(lin(tok_k, C, a.k, nullptr, 0, k1, I, P * T, I, C, HGL_ACT_NONE, st));
-  HGL_TRY(lin(tok_v, C, a.v, nullptr, 0, v1, I, P * T, I, C, HGL_ACT_NONE, st));
-  const SplitPair at = split_view(atti, (size_t)P * HW * I);
-  HGL_TRY(hgl_launch_attention_split(kvq + 2 * I, k1, v1, nullptr, at.hi, at.lo, P, heads, HW, T, hd, ld, I, I, I,
-                                     (long long)HW * ld, (long long)T * I, (long long)T * I, (long long)HW * I,
-                                     1.0f / sqrtf((float)hd), HGL_MASK_NONE, nullptr, 0, 0, nullptr, nullptr, 0, 0, st));
-  return hgl_launch_gemm_f16x3_rmod(at.hi, at.lo, I, a.out.w, a.out.b, R, C, 0, keys_out, nullptr, nullptr, C, P * HW, C, I,
-                                    HGL_ACT_NONE, st);
+// step (4) of layer li: the image attends to the tokens: q = keys+pe, k = queries+pe, v = queries ; keys += out, then norm4
+// (transformer.py:139-150); the image tokens leave it in the form the next step of the route reads
+int dec_i2t(const DecRoute& r, const HglSamDecoderW* w, int li, const DecPlan& p, const SplitPair& keysS, const SplitPair& kpeS,
+            hipStream_t st) {
+  const auto& L = w->layer[li];
+  const auto& a = L.i2t;
+  const int P = r.P, HW = r.HW, T = r.T, C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
+  const long long sK = (long long)HW * C;
+  const bool shared = r.shared[li];
+  const float* keys = shared ? p.keys0 : p.keys;
+  const float* kpe = shared ? p.kpe0 : p.kpe;
+  if (r.fuse_i2t[li]) {
+    HGL_TRY(lin(p.qpe, C, a.k, nullptr, 0, p.k1, I, P * T, I, C, HGL_ACT_NONE, st));
+    HGL_TRY(lin(p.queries, C, a.v, nullptr, 0, p.v1, I, P * T, I, C, HGL_ACT_NONE, st));
+    if (r.raw_t2i && !shared) {
+      // layer 1 on per-prompt image tokens: scores = (keys + pe) . (W_q^T k_tok) and update = P (W_o v_tok) by MFMA against
+      // per-prompt 56 x 256 matrices (sam_decoder_t2i.hip: dec_i2t_fold_kernel); the planes are updated in place
+      const I2tFoldScratch s(p.atti, P, C);
+      HGL_TRY(hgl_launch_i2t_prep(p.k1, p.v1, a.q.w, a.q.b, a.out.w, 1.0f / sqrtf((float)hd), s.Kh, s.Kl, s.cb, s.Uh, s.Ul, P, st));
+      HGL_TRY(hgl_launch_gemm_f16x3(s.Kh, s.Kl, C, w->dense_pe, nullptr, nullptr, 0, p.kp, nullptr, nullptr, HW, P * 56, HW, C,
+                                    HGL_ACT_NONE, st));
+      return hgl_launch_dec_i2t_fold(keysS.hi, keysS.lo, s.Kh, s.Kl, p.kp, s.cb, s.Uh, s.Ul, a.out.b, L.n4.w, L.n4.b, 1e-5f, P, HW,
+                                     keysS.hi, keysS.lo, st);
+    }
+    // attention over the 7 tokens, out-projection, residual and norm4 in one launch: the image tokens leave it as the
+    // split planes the next projections read (and, in layer 0, as the fp32 rows layer 1 adds its update to)
+    if (shared) HGL_TRY(lin_sets(p.kpe0, C, a.q, p.qi, I, HW, r.n_img, I, C, st));
+    // (shared rows: stride 0 for one image; n_img images: the rows of image p / ppi, one image's rows apart)
+    const bool sets = shared && r.n_img > 1;
+    return hgl_launch_dec_i2t(shared ? p.qi : p.kp + 2 * I, shared ? I : 3 * I, sets ? (long long)HW * I : shared ? 0 : (long long)HW * 3 * I,
+                              p.k1, p.v1, a.out.w, a.out.b, keys, sets ? sK : shared ? 0 : sK, L.n4.w, L.n4.b, 1e-5f,
+                              1.0f / sqrtf((float)hd), P, HW, (li == 0 && !r.raw_t2i) ? p.keys : nullptr, keysS.hi, keysS.lo, st,
+                              sets ? r.ppi : 1);
+  }
+  if (!r.x3 || r.plain[li]) {   // the plain fp32 launches
+    HGL_TRY(dec_attn(w, a, kpe, shared, HW, p.qpe, p.queries, false, T, P, p.qi, p.k1, p.v1, p.atti, keys, shared ? 0 : sK, p.keys, st));
+    if (!r.x3) {
+      HGL_TRY(hgl_launch_layernorm(p.keys, L.n4.w, L.n4.b, p.keys, P * HW, C, 1e-5f, st));
+      return hgl_launch_add_rows_bcast(p.keys, sK, w->dense_pe, sK, P, p.kpe, st);
+    }
+  } else {
+    // q = (keys + pe) Wq: of the shared rows, from the merged projection of step (2) (kvq[:, 2I:3I]), or from the split planes;
+    // 7 token keys / values (the few-key kernel for up to 8 tokens, the general one beyond), its output split;
+    // keys' = keys + out_proj(attn)
+    const bool from_kvq = r.merged && !shared;
+    const int ldq = from_kvq ? 3 * I : I;
+    if (shared) {
+      HGL_TRY(lin(p.kpe0, C, a.q, nullptr, 0, p.qi, I, HW, I, C, HGL_ACT_NONE, st));
+    } else if (!from_kvq) {
+      HGL_TRY(hgl_launch_gemm_f16x3(kpeS.hi, kpeS.lo, C, a.q.w, a.q.b, nullptr, 0, p.qi, nullptr, nullptr, I, P * HW, I, C,
+                                    HGL_ACT_NONE, st));
+    }
+    HGL_TRY(lin(p.qpe, C, a.k, nullptr, 0, p.k1, I, P * T, I, C, HGL_ACT_NONE, st));
+    HGL_TRY(lin(p.queries, C, a.v, nullptr, 0, p.v1, I, P * T, I, C, HGL_ACT_NONE, st));
+    const SplitPair at = split_view(p.atti, (size_t)P * HW * I);
+    HGL_TRY(hgl_launch_attention_split(from_kvq ? p.kp + 2 * I : p.qi, p.k1, p.v1, nullptr, at.hi, at.lo, P, heads, HW, T, hd, ldq, I,
+                                       I, I, shared ? 0 : (long long)HW * ldq, (long long)T * I, (long long)T * I, (long long)HW * I,
+                                       1.0f / sqrtf((float)hd), HGL_MASK_NONE, nullptr, 0, 0, nullptr, nullptr, 0, 0, st));
+    HGL_TRY(hgl_launch_gemm_f16x3_rmod(at.hi, at.lo, I, a.out.w, a.out.b, keys, C, shared ? HW : 0, p.keys, nullptr, nullptr, C,
+                                       P * HW, C, I, HGL_ACT_NONE, st));
+  }
+  // norm4, then keys (and, unmerged, keys + dense_pe) as split planes; the fp32 rows are kept only while a later layer
+  // needs them as a residual
+  return hgl_launch_ln256_pe_split(p.keys, L.n4.w, L.n4.b, w->dense_pe, HW, (long long)P * HW, 1e-5f, li == 0 ? 1 : 0, keysS.hi,
+                                   keysS.lo, r.merged ? nullptr : kpeS.hi, r.merged ? nullptr : kpeS.lo, st);
 }
 
 }  // namespace
@@ -637,7 +753,10 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
   HGL_REQUIRE(n_sparse >= 2 && n_sparse <= 11, "sam_decode: %d sparse tokens per prompt (2 .. 11 supported)", n_sparse);
   HGL_REQUIRE(n_sparse <= 3 || (long long)P * w->heads <= 65535, "sam_decode: %d prompts of more than 3 sparse tokens in one call", P);
   HGL_REQUIRE(n_img >= 1 && P % n_img == 0 && (n_img == 1 || (points01 && !dense)), "sam_decode: %d prompts for %d images", P, n_img);
-  const int ppi = P / n_img;   // prompts per image: emb holds n_img embeddings, prompt p belongs to image p / ppi
+  // emb holds n_img embeddings, prompt p belongs to image p / (P / n_img)
+  const DecRoute r = dec_route(w, P, n_img, n_sparse, dense != nullptr, dec_fusion_mask());
+  HGL_REQUIRE(n_img == 1 || r.multi, "sam_decode: %d images in one launch sequence need the fused image -> token step and the "
+              "chunked token -> image attention", n_img);
   HglArena ar(workspace, workspace_bytes);
   DecPlan p;
   if (!workspace || !carve_dec(ar, w, P, p, n_img)) {
@@ -646,9 +765,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
   }
   hipStream_t st = (hipStream_t)stream;
   const int C = w->C, g = w->grid, HW = g * g, T = 5 + n_sparse;
-  const bool perprompt = dense != nullptr;     // the image tokens differ from prompt to prompt already in layer 0
   const long long sQ = (long long)T * C, sK = (long long)HW * C;
-  const size_t atti_bytes = (size_t)P * HW * (C / 2) * sizeof(float);
 
   // ---- prompt encoder + token assembly ----
   if (points01) {
@@ -659,7 +776,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
     HGL_TRY(hgl_launch_pe_labeled(coords01, labels, w->pe_gauss, n_sparse * P, C / 2, w->not_a_point, pe4, p.sparse, st));
   }
   HGL_TRY(hgl_launch_build_tokens(w->iou_token, w->mask_tokens, p.sparse, P, C, T, p.tokens, st));
-  if (perprompt) {
+  if (dense) {   // the image tokens differ from prompt to prompt already in layer 0
     // src[p] = image_embedding + dense[p] (mask_decoder.py:121-123 with dense_prompt_embeddings from mask inputs)
     HGL_TRY(hgl_launch_add_rows_bcast(dense, sK, emb, sK, P, p.keys, st));
     HGL_TRY(hgl_launch_add_rows_bcast(p.keys, sK, w->dense_pe, sK, P, p.kpe, st));
@@ -671,24 +788,10 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
   }
   (void)hipMemcpyAsync(p.queries, p.tokens, sizeof(float) * P * sQ, hipMemcpyDeviceToDevice, st);
 
-  const bool x3 = dec_x3_ready(w);
-  const bool merged = x3 && dec_merged_ready(w) && w->layer[1].t2i.internal == w->layer[1].i2t.internal &&
-                      w->layer[1].t2i.internal == w->final_t2i.internal && 2 * w->final_t2i.internal == C;
-  const int I1 = w->layer[1].t2i.internal;
   const SplitPair keysS = split_view(p.keysS, (size_t)P * HW * C), kpeS = split_view(p.kpe, (size_t)P * HW * C);
-  // fusion bit 5: the token -> image attention of layer 1 and the final one on the raw image-token planes (the 7 tokens go
-  // through W_k / W_v instead of the HW image tokens: no k | v projection GEMM; layer 1 projects q alone for its step 4)
-  const bool raw_t2i = merged && (dec_fusion_mask() & 32) && (dec_fusion_mask() & 4) && T == 7 && I1 == 128 && w->heads == 8 &&
-                       C == 256 && HW % 128 == 0 && P <= 65535 && !perprompt && hgl_has_split_weight(w->dense_pe) &&
-                       (size_t)P * (56 * C * 8) + n_img * hgl_t2i_part_bytes(ppi, HW) <= atti_bytes &&   // dec_t2i_raw: Q' planes + attended rows (+ partials)
-                       (size_t)P * (56 * C * 4 + 16384 * 4 + 256) <= atti_bytes;      // step (4): K' and U planes + cb
+  // TwoWayAttentionBlock (transformer.py:109-150) x 2
   for (int li = 0; li < 2; ++li) {
     const auto& L = w->layer[li];
-    const bool shared = li == 0 && !perprompt;   // keys identical for every prompt in layer 0
-    // layer 0 on per-prompt image tokens: the plain fp32 launches (the split planes / merged weights belong to layer 1's input)
-    const bool plain0 = li == 0 && perprompt;
-    const float* keys = shared ? p.keys0 : p.keys;
-    const float* kpe = shared ? p.kpe0 : p.kpe;
     // (1) self attention of the tokens
     if (li == 0) {  // skip_first_layer_pe: queries = self_attn(q,q,q), no residual
       HGL_TRY(dec_attn(w, L.self_attn, p.queries, false, T, p.queries, p.queries, false, T, P, p.q1, p.k1, p.v1, p.att,
@@ -702,96 +805,19 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
     HGL_TRY(hgl_launch_layernorm(p.queries, L.n1.w, L.n1.b, p.queries, P * T, C, 1e-5f, st));
     // (2) tokens attend to the image
     HGL_TRY(hgl_launch_add_rows_bcast(p.queries, P * sQ, p.tokens, P * sQ, 1, p.qpe, st));
-    if (raw_t2i && !shared && !plain0) {
-      // no projection of the image tokens at all: this attention reads the raw planes (its positional term in p.kp), and
-      // step (4) below folds W_q into the 7 token keys as well
-      HGL_TRY(dec_t2i_raw(w, L.t2i, p.qpe, keysS, P, ppi, HW, T, p.q1, p.atti, p.kp, p.att, p.queries, st));
-    } else if (merged && !shared && !plain0) {
-      // k, v of this step and q of step (4) read the same rows: one GEMM, the positional encoding as a per-position table
-      HGL_TRY(dec_project_merged(keysS, w->kvq1_w, w->kvq1_b, w->kvq1_pe, P, HW, C, 3 * I1, p.kp, st));
-      HGL_TRY(dec_t2i_merged(w, L.t2i, p.qpe, p.kp, 3 * I1, P, HW, T, p.q1, p.att, p.queries, p.atti, atti_bytes, st));
-    } else if (x3 && !shared && !plain0) {
-      HGL_TRY(dec_t2i_x3(w, L.t2i, p.qpe, kpeS, keysS, P, HW, T, p.q1, p.kp, p.vp, p.att, p.queries, p.atti, atti_bytes, st));
-    } else {
-      HGL_TRY(dec_attn(w, L.t2i, p.qpe, false, T, kpe, keys, shared, HW, P, p.q1, p.kp, p.vp, p.att, p.queries, sQ,
-                       p.queries, st, p.atti, atti_bytes, shared ? n_img : 1));
-    }
+    HGL_TRY(dec_t2i(r, w, L.t2i, li, p, keysS, kpeS, st));
     HGL_TRY(hgl_launch_layernorm(p.queries, L.n2.w, L.n2.b, p.queries, P * T, C, 1e-5f, st));
     // (3) MLP on the tokens
     HGL_TRY(lin(p.queries, C, L.lin1, nullptr, 0, p.mlp, w->mlp_dim, P * T, w->mlp_dim, C, HGL_ACT_RELU, st));
     HGL_TRY(lin(p.mlp, w->mlp_dim, L.lin2, p.queries, C, p.queries, C, P * T, C, w->mlp_dim, HGL_ACT_NONE, st));
     HGL_TRY(hgl_launch_layernorm(p.queries, L.n3.w, L.n3.b, p.queries, P * T, C, 1e-5f, st));
-    // (4) image attends to the tokens: q = keys+pe, k = queries+pe, v = queries ; keys += out
+    // (4) image attends to the tokens
     HGL_TRY(hgl_launch_add_rows_bcast(p.queries, P * sQ, p.tokens, P * sQ, 1, p.qpe, st));
-    const bool fuse_i2t = merged && (dec_fusion_mask() & 4) && L.i2t.internal == I1 && I1 == 128 && w->heads == 8 &&
-                          HW % 64 == 0 && P <= 65535 && T == 7 && !plain0;
-    if (fuse_i2t && raw_t2i && !shared) {
-      // layer 1 on per-prompt image tokens: scores = (keys + pe) . (W_q^T k_tok) and update = P (W_o v_tok) by MFMA against
-      // per-prompt 56 x 256 matrices (sam_decoder_t2i.hip: dec_i2t_fold_kernel); the planes are updated in place
-      HGL_TRY(lin(p.qpe, C, L.i2t.k, nullptr, 0, p.k1, I1, P * T, I1, C, HGL_ACT_NONE, st));
-      HGL_TRY(lin(p.queries, C, L.i2t.v, nullptr, 0, p.v1, I1, P * T, I1, C, HGL_ACT_NONE, st));
-      uint16_t* Kh = (uint16_t*)p.atti;                            // [P*56, 256] K' hi / lo
-      uint16_t* Kl = Kh + (size_t)P * 56 * C;
-      uint16_t* Uh = Kl + (size_t)P * 56 * C;                      // [P, 16, 2, 64, 8] U fragments hi / lo
-      uint16_t* Ul = Uh + (size_t)P * 16384;
-      float* cbv = (float*)(Ul + (size_t)P * 16384);               // [P*56]
-      HGL_TRY(hgl_launch_i2t_prep(p.k1, p.v1, L.i2t.q.w, L.i2t.q.b, L.i2t.out.w, 1.0f / sqrtf((float)(I1 / w->heads)), Kh, Kl, cbv, Uh,
-                                  Ul, P, st));
-      HGL_TRY(hgl_launch_gemm_f16x3(Kh, Kl, C, w->dense_pe, nullptr, nullptr, 0, p.kp, nullptr, nullptr, HW, P * 56, HW, C,
-                                    HGL_ACT_NONE, st));
-      HGL_TRY(hgl_launch_dec_i2t_fold(keysS.hi, keysS.lo, Kh, Kl, p.kp, cbv, Uh, Ul, L.i2t.out.b, L.n4.w, L.n4.b, 1e-5f, P, HW,
-                                      keysS.hi, keysS.lo, st));
-    } else if (fuse_i2t) {
-      // attention over the 7 tokens, out-projection, residual and norm4 in one launch: the image tokens leave it as the
-      // split planes the next projections read (and, in layer 0, as the fp32 rows layer 1 adds its update to)
-      HGL_TRY(lin(p.qpe, C, L.i2t.k, nullptr, 0, p.k1, I1, P * T, I1, C, HGL_ACT_NONE, st));
-      HGL_TRY(lin(p.queries, C, L.i2t.v, nullptr, 0, p.v1, I1, P * T, I1, C, HGL_ACT_NONE, st));
-      if (shared) HGL_TRY(lin_sets(p.kpe0, C, L.i2t.q, p.qi, I1, HW, n_img, I1, C, st));
-      // (shared rows: stride 0 for one image; n_img images: the rows of image p / ppi, one image's rows apart)
-      const bool sets = shared && n_img > 1;
-      HGL_TRY(hgl_launch_dec_i2t(shared ? p.qi : p.kp + 2 * I1, shared ? I1 : 3 * I1,
-                                 sets ? (long long)HW * I1 : shared ? 0 : (long long)HW * 3 * I1, p.k1,
-                                 p.v1, L.i2t.out.w, L.i2t.out.b, keys, sets ? sK : shared ? 0 : sK, L.n4.w, L.n4.b, 1e-5f,
-                                 1.0f / sqrtf((float)(I1 / w->heads)), P, HW, (li == 0 && !raw_t2i) ? p.keys : nullptr, keysS.hi,
-                                 keysS.lo, st, sets ? ppi : 1));
-    } else if (shared && n_img > 1) {
-      hgl_set_error("sam_decode: several images in one launch need the fused image -> token step");
-      return HGL_EINVAL;
-    } else if (x3 && plain0) {
-      HGL_TRY(dec_attn(w, L.i2t, kpe, false, HW, p.qpe, p.queries, false, T, P, p.qi, p.k1, p.v1, p.atti, keys, sK, p.keys, st));
-      HGL_TRY(hgl_launch_ln256_pe_split(p.keys, L.n4.w, L.n4.b, w->dense_pe, HW, (long long)P * HW, 1e-5f, 1, keysS.hi, keysS.lo,
-                                        merged ? nullptr : kpeS.hi, merged ? nullptr : kpeS.lo, st));
-    } else if (x3) {
-      if (merged && !shared) {
-        HGL_TRY(dec_i2t_merged(w, L.i2t, p.kp, 3 * I1, p.qpe, p.queries, P, HW, T, p.k1, p.v1, p.atti, keys, p.keys, st));
-      } else {
-        HGL_TRY(dec_i2t_x3(w, L.i2t, shared, p.kpe0, kpeS, p.qpe, p.queries, P, HW, T, p.qi, p.k1, p.v1, p.atti, keys,
-                           shared ? HW : 0, p.keys, st));
-      }
-      // norm4, then keys (and, unmerged, keys + dense_pe) as split planes; the fp32 rows are kept only while a later layer
-      // needs them as a residual
-      HGL_TRY(hgl_launch_ln256_pe_split(p.keys, L.n4.w, L.n4.b, w->dense_pe, HW, (long long)P * HW, 1e-5f, li == 0 ? 1 : 0,
-                                        keysS.hi, keysS.lo, merged ? nullptr : kpeS.hi, merged ? nullptr : kpeS.lo, st));
-    } else {
-      HGL_TRY(dec_attn(w, L.i2t, kpe, shared, HW, p.qpe, p.queries, false, T, P, p.qi, p.k1, p.v1, p.atti, keys,
-                       shared ? 0 : sK, p.keys, st));
-      HGL_TRY(hgl_launch_layernorm(p.keys, L.n4.w, L.n4.b, p.keys, P * HW, C, 1e-5f, st));
-      HGL_TRY(hgl_launch_add_rows_bcast(p.keys, sK, w->dense_pe, sK, P, p.kpe, st));
-    }
+    HGL_TRY(dec_i2t(r, w, li, p, keysS, kpeS, st));
   }
   // final token -> image attention
   HGL_TRY(hgl_launch_add_rows_bcast(p.queries, P * sQ, p.tokens, P * sQ, 1, p.qpe, st));
-  if (raw_t2i) {
-    HGL_TRY(dec_t2i_raw(w, w->final_t2i, p.qpe, keysS, P, ppi, HW, T, p.q1, p.atti, p.kp, p.att, p.queries, st));
-  } else if (merged) {
-    HGL_TRY(dec_project_merged(keysS, w->kvf_w, w->kvf_b, w->kvf_pe, P, HW, C, 2 * I1, p.kp, st));
-    HGL_TRY(dec_t2i_merged(w, w->final_t2i, p.qpe, p.kp, 2 * I1, P, HW, T, p.q1, p.att, p.queries, p.atti, atti_bytes, st));
-  } else if (x3) {
-    HGL_TRY(dec_t2i_x3(w, w->final_t2i, p.qpe, kpeS, keysS, P, HW, T, p.q1, p.kp, p.vp, p.att, p.queries, p.atti, atti_bytes, st));
-  } else {
-    HGL_TRY(dec_attn(w, w->final_t2i, p.qpe, false, T, p.kpe, p.keys, false, HW, P, p.q1, p.kp, p.vp, p.att, p.queries,
-                     sQ, p.queries, st, p.atti, atti_bytes));
-  }
+  HGL_TRY(dec_t2i(r, w, w->final_t2i, 2, p, keysS, kpeS, st));
   HGL_TRY(hgl_launch_layernorm(p.queries, w->norm_final.w, w->norm_final.b, p.queries, P * T, C, 1e-5f, st));
 
   // ---- IoU head on the iou token (row 0); multimask output = columns 1..3.  BEFORE the upscaling: the predictions depend on
@@ -819,14 +845,13 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
     HGL_TRY(lin(p.hy_a, C, w->hyper[i][1], nullptr, 0, p.hy_b, C, P, C, C, HGL_ACT_RELU, st));
     HGL_TRY(lin(p.hy_b, C, w->hyper[i][2], nullptr, 0, p.hyper + i * C8, 4 * C8, P, C8, C, HGL_ACT_NONE, st));
   }
-  // fused upscaling + hyper-network products (one launch, the 256-channel rows read once); hgl_sam_decoder_fusion(0) /
-  // HGL_SAM_DEC_FUSED=0 keep the four launches below (same products, sums associated differently: tests compare the two)
-  const bool fused_tail = x3 && (dec_fusion_mask() & 1) && (HW % 64) == 0 && (g % 64 == 0 || 64 % g == 0) && P <= 65535;
-  if (fused_tail) {
+  // fused upscaling + hyper-network products; hgl_sam_decoder_fusion(0) / HGL_SAM_DEC_FUSED=0 keep the four launches below
+  // (same products, sums associated differently: tests compare the two)
+  if (r.fused_tail) {
     HGL_TRY(hgl_launch_dec_tail(keysS.hi, keysS.lo, w->up0_w, w->up0_b, w->up1.w, w->up1.b, w->up3_w, w->up3_b, p.hyper, first_mask,
                                 P, g, 1e-6f, low_res, skip, st));
   } else {
-    if (x3) {
+    if (r.x3) {
       HGL_TRY(hgl_launch_gemm_f16x3(keysS.hi, keysS.lo, C, w->up0_w, w->up0_b, nullptr, 0, p.u1, nullptr, nullptr, 4 * C4,
                                     P * HW, 4 * C4, C, HGL_ACT_NONE, st));
       const SplitPair u1S = split_view(p.kpe, (size_t)P * HW * 4 * C4);   // kpeS is dead from here on
@@ -860,33 +885,18 @@ int hgl_sam_decode_points_gated(const HglSamDecoderW* w, const float* emb, const
                      iou_gate);
 }
 
-// Can decode_impl take the prompts of several images in ONE launch sequence?  Only layer 0 knows that prompts share image
-// tokens; its two shared steps then need the kernels that address "the rows of image p / ppi": the chunked token -> image
-// attention (fusion bit 4) and the fused image -> token step (bits 1, 2).  The conditions are decode_impl's own.
-static bool dec_multi_fused(const HglSamDecoderW* w, int n_img, int ppi) {
-  const int C = w->C, HW = w->grid * w->grid, I1 = w->layer[1].t2i.internal, heads = w->heads;
-  const long long P = (long long)n_img * ppi;
-  const auto& L0 = w->layer[0];
-  const bool merged = dec_x3_ready(w) && dec_merged_ready(w) && I1 == w->layer[1].i2t.internal && I1 == w->final_t2i.internal &&
-                      2 * w->final_t2i.internal == C;
-  const bool fuse_i2t = merged && (dec_fusion_mask() & 4) && L0.i2t.internal == I1 && I1 == 128 && heads == 8 && HW % 64 == 0;
-  const size_t atti_bytes = (size_t)P * HW * (C / 2) * sizeof(float);
-  const bool chunked = (dec_fusion_mask() & 16) && heads == 8 && L0.t2i.internal == 128 && HW >= 256 &&
-                       atti_bytes >= hgl_attention_fewq_part_bytes((int)P, HW);
-  return P <= 65535 && fuse_i2t && chunked;
-}
-
 // Images per launch sequence: whole images, at most 1024 prompts.  The token-side GEMMs of up to 8192 rows (1170 prompts of 7
 // tokens) run on the small-tile kernel whatever their row count (lin()), larger ones on fp32 tiles with other sums: within
 // the bound a prompt's rows do not depend on how many images share the launch.
-static int dec_multi_images(int n_img, int ppi) {
-  const int per = ppi >= 1024 ? 1 : 1024 / ppi;
-  return per < n_img ? per : n_img;
+// Where the route of such a launch sequence does not serve several images (DecRoute::multi): 1.
+static int dec_multi_images(const HglSamDecoderW* w, int n_img, int ppi) {
+  const int most = ppi >= 1024 ? 1 : 1024 / ppi, per = most < n_img ? most : n_img;
+  return per > 1 && dec_route(w, per * ppi, per, 2, false, dec_fusion_mask()).multi ? per : 1;
 }
 
 // n_img images x ppi prompts.  One image: exactly hgl_sam_decode_points(_gated).  Several: launch sequences over
-// dec_multi_images() images each where the fused stages serve (dec_multi_fused), else image by image through the one-image
-// path; either way every prompt's rows are those of its image's own call.
+// dec_multi_images() images each (1: image by image through the one-image path); either way every prompt's rows are those of
+// its image's own call.
 static int decode_multi(const HglSamDecoderW* w, const float* emb, const float* points01, int n_img, int ppi, float* low_res,
                         float* iou_pred, void* workspace, size_t workspace_bytes, void* stream, bool gated, float iou_gate) {
   HGL_REQUIRE(points01, "sam_decode: null input");
@@ -895,7 +905,7 @@ static int decode_multi(const HglSamDecoderW* w, const float* emb, const float* 
   if (n_img == 1)
     return decode_impl(w, emb, points01, nullptr, nullptr, 2, nullptr, 1, ppi, low_res, iou_pred, workspace, workspace_bytes, stream,
                        gated, iou_gate);
-  const int per = dec_multi_fused(w, dec_multi_images(n_img, ppi), ppi) ? dec_multi_images(n_img, ppi) : 1;
+  const int per = dec_multi_images(w, n_img, ppi);
   const size_t HW = (size_t)w->grid * w->grid, lowsz = (size_t)3 * 16 * HW;
   for (int i = 0; i < n_img; i += per) {
     const int k = n_img - i < per ? n_img - i : per;
@@ -908,7 +918,7 @@ static int decode_multi(const HglSamDecoderW* w, const float* emb, const float* 
 
 size_t hgl_sam_decode_multi_workspace_bytes(const HglSamDecoderW* w, int n_img, int ppi) {
   if (!valid_dec(w) || n_img <= 0 || ppi <= 0 || (long long)n_img * ppi > 65535) return 0;
-  const int per = n_img > 1 && dec_multi_fused(w, dec_multi_images(n_img, ppi), ppi) ? dec_multi_images(n_img, ppi) : 1;
+  const int per = dec_multi_images(w, n_img, ppi);
   HglArena ar(nullptr, 0);
   DecPlan p;
   carve_dec(ar, w, per * ppi, p, per);

@@ -131,6 +131,10 @@ SAM_CONFIGS = {
     # number of 64-token tiles per grid row): the ragged paths of the decoder kernels
     "tiny24": dict(embed_dim=160, depth=2, num_heads=2, global_attn_indexes=(1,),
                    img_size=384, patch_size=16, window_size=14, out_chans=256),
+    # 28x28 tokens = 2 x 2 windows of 14 (no padded rows) at a width that takes the split-fp16 encoder (4 heads of 64): the
+    # window partition / unpartition launches of a grid the window divides
+    "tiny28": dict(embed_dim=256, depth=2, num_heads=4, global_attn_indexes=(1,),
+                   img_size=448, patch_size=16, window_size=14, out_chans=256),
 }
 
 

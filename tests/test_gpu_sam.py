@@ -669,6 +669,32 @@ def test_vit_b_two_blocks_full_width(cuda):
     np.testing.assert_allclose(emb, ref, rtol=0, atol=2e-4)
 
 
+@pytest.mark.parametrize("precision", [None, "f32"])
+def test_encoder_window_divides_grid_vs_oracle(cuda, precision):
+    """28x28 tokens = 2 x 2 windows of 14 x 14 with no padded rows, width 256 (4 heads of 64): the only geometry in the suite
+    where the windowed block partitions and un-partitions whole windows (win_partition_split / win_unpartition_add in the
+    default precision, win_partition / win_unpartition_add in f32) instead of gathering the real tokens of a padded grid.
+    One windowed + one global block + neck against the oracle, at the bar of the other two-block encoders.
+    The bar comes from those tests (the oracle's embedding here is finite, max |x| 4.39, std 1.00), not from a run: when
+    the test was written no GPU could be had, so the max |error| of this geometry is NOT measured, neither before nor after
+    the encoder block was restructured; the test prints it before it asserts."""
+    from hybridgl_amd import ops
+    from hybridgl_amd.synth import synth_image
+    cfg = weights.SAM_CONFIGS["tiny28"]
+    sd = weights.sam_state_dict("tiny28", 0)
+    try:
+        m = hsam.Sam(sd, cfg, cuda, precision=precision)
+        img = synth_image(336, 448, 11)      # 336 x 448: exercises the zero padding
+        emb = m.encode(T(img, cuda)).cpu().numpy().reshape(28, 28, 256)
+        ref = S.image_encoder(sd, S.preprocess(img, 448), cfg)
+        print(f"tiny28 encoder ({precision or ops.default_precision()}): max |error| {np.abs(emb - ref).max():.3e}")
+        np.testing.assert_allclose(emb, ref, rtol=0, atol=2e-4)
+        emb2 = m.encode(T(img, cuda)).cpu().numpy().reshape(28, 28, 256)
+        assert np.array_equal(emb, emb2)      # run-to-run bit reproducible
+    finally:
+        ops.set_precision(ops.default_precision())
+
+
 def test_full_size_decoder_properties(cuda):
     """64 prompts x 64x64 embedding (BASELINE size): finite, deterministic, prompt-batch independent."""
     cfg = weights.SAM_CONFIGS["vit_h_d2"]
