@@ -149,9 +149,14 @@ int hgl_attention_f32(const float* q, const float* k, const float* v, float* out
                       const uint8_t* keep, int keep_b0, int keep_n, const float* rel_h,
                       const float* rel_w, int kh, int kw, void* stream) {
   HGL_TRY(hgl_require_device());
-  return hgl_launch_attention(q, k, v, out, B, H, Sq, Sk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb, sob,
-                              scale, mask_kind, keep, keep_b0, keep_n, rel_h, rel_w, kh, kw,
-                              (hipStream_t)stream);
+  HglAttn d;
+  d.B = B, d.H = H, d.Sq = Sq, d.Sk = Sk, d.hd = hd, d.scale = scale;
+  d.q = q, d.k = k, d.v = v, d.out = out;
+  d.ldq = ldq, d.ldk = ldk, d.ldv = ldv, d.ldo = ldo;
+  d.sqb = sqb, d.skb = skb, d.svb = svb, d.sob = sob;
+  d.mask_kind = mask_kind, d.keep = keep, d.keep_b0 = keep_b0, d.keep_n = keep_n;
+  d.rel_h = rel_h, d.rel_w = rel_w, d.kh = kh, d.kw = kw;
+  return hgl_launch_attention(d, (hipStream_t)stream);
 }
 
 int hgl_mask_resize(const uint8_t* masks, int N, int Hm, int Wm, int g, float* pm, void* stream) {

@@ -1747,201 +1747,221 @@ __global__ __launch_bounds__(128) void attn_fewq_combine_kernel(const float* __r
   out[b * sob + (long long)qi * ldo + ll * 8 + d] = acc / lsum;
 }
 
-// TERMS: 3 (f16x3) or 1 (f16 mode: the one-term flavours)
+// ---- host side: the route (which kernel family serves a descriptor) and the launch ---------------------------------------------
+
+// the switches of the route, each read once
+int sw_wide() { static const int v = HGL_DIAG_SWITCH("HGL_ATTN_WIDE", 1); return v; }
+int sw_dual() { static const int v = HGL_DIAG_SWITCH("HGL_ATTN_DUAL", 1); return v; }
+int sw_relpos_fused() { static const int v = HGL_DIAG_SWITCH("HGL_ATTN_RELPOS_FUSED", 1); return v; }
+int sw_pp() { static const int v = hgl_env_int("HGL_ATTN_PP", 1); return v; }
+
+// the split-fp16 tile kernels at head dim 16 / 32 / 64 / 80, in the order the conditions are asked
+HglAttnRoute route_x3(const HglAttn& d) {
+  const int HD = d.hd;
+  // sequences of 129..256 queries (a 14 x 14 window, a 197-token CLIP sequence): one 8-wave workgroup per (batch, head)
+  // (longer sequences measured neutral for 785 queries, slower for the 4096-query global blocks: two independent
+  // 4-wave workgroups per CU interleave their phases, one 8-wave workgroup meets at every barrier)
+  // the persistent kernel parks the CLS-keep row of an item in a 256-byte LDS tail: keys beyond 257 do not fit there
+  const bool w8 = sw_wide() && HD >= 64 && d.Sq > 128 && d.Sq <= 256 && d.mask_kind != HGL_MASK_CAUSAL &&
+                  (d.mask_kind != HGL_MASK_CLS_KEEP || d.Sk <= 257);
+  // long unmasked sequences (SAM's global blocks, GEM's 785 tokens): the ping-pong kernel, one 8-wave workgroup per 256 queries
+  // (measured, tools/attn_pp_ab.py: 4096 x 4096 x 80 with rel-pos 1690 against 1745 us; 785- and 1000-token sequences
+  // 15-25 % SLOWER than two 4-wave workgroups per CU -- few query blocks per head, and the co-execution the schedule
+  // is built for did not appear: SQ_VALU_MFMA_COEXEC stayed at 23 % of the matrix-busy cycles)
+  if ((HD == 64 || HD == 80) && sw_pp() && d.Sq >= 2048 && d.Sk >= 2048 && d.mask_kind == HGL_MASK_NONE &&
+      (!d.rel_h || (d.kw & 31) == 0) && ((d.Sk & 31) == 0 || !d.rel_h))
+    return HGL_ATTN_PINGPONG;
+  if (HD == 80 && d.rel_h && d.kh == 14 && d.kw == 14 && d.Sk == 196 && d.mask_kind == HGL_MASK_NONE) return HGL_ATTN_REL14;
+  // head dim 64 (the CLIP sequences): two items per CU -- one 4-wave workgroup per item, two query tiles per wave.
+  // 868 against 976 us on 1024 x 12 x 197 x 64 (141 against 125 TF/s), -0.4 ms per benchmark step (HGL_ATTN_DUAL=0: the
+  // persistent 8-wave kernel)
+  if (w8 && !d.rel_h && sw_dual() && HD == 64 && (d.mask_kind != HGL_MASK_CLS_KEEP || d.Sk <= 257)) return HGL_ATTN_DUAL;
+  if (w8 && !d.rel_h) return HGL_ATTN_WIDE;   // K / V staged once
+  return HGL_ATTN_TILE;
+}
+
+// TERMS: 3 (f16x3) or 1 (f16 mode: the one-term flavours; q, k, v arrive as fp32 and are rounded to fp16 in the kernel)
 template <int HD, int TERMS>
-int launch_hd(const AttnArgs& a, hipStream_t st) {
+int launch_hd(const AttnArgs& a, HglAttnRoute route, hipStream_t st) {
   dim3 grid((a.Sq + 127) / 128, a.B * a.H);
   HglProfScope prof(HGL_PROF_ATTN, 4.0 * a.B * a.H * (double)a.Sq * a.Sk * HD,
                     4.0 * a.B * a.H * HD * (2.0 * a.Sq + 2.0 * a.Sk), st);
-  if (hgl_split_layout()) {   // (f16 mode: q, k, v arrive as fp32; the TERMS = 1 flavours round them to fp16 in the kernel)
-    // sequences of 129..256 queries (a 14 x 14 window, a 197-token CLIP sequence): one 8-wave workgroup per (batch, head)
-    static const int wide = HGL_DIAG_SWITCH("HGL_ATTN_WIDE", 1);
-    static const int dual = HGL_DIAG_SWITCH("HGL_ATTN_DUAL", 1);
-    // (longer sequences measured neutral for 785 queries, slower for the 4096-query global blocks: two independent
-    // 4-wave workgroups per CU interleave their phases, one 8-wave workgroup meets at every barrier)
-    // the persistent kernel parks the CLS-keep row of an item in a 256-byte LDS tail: keys beyond 257 do not fit there
-    const bool w8 = wide && HD >= 64 && a.Sq > 128 && a.Sq <= 256 && a.mask_kind != HGL_MASK_CAUSAL &&
-                    (a.mask_kind != HGL_MASK_CLS_KEEP || a.Sk <= 257);
-    // long unmasked sequences (SAM's global blocks, GEM's 785 tokens): the ping-pong kernel, one 8-wave workgroup per 256 queries
-    static const int pp = hgl_env_int("HGL_ATTN_PP", 1);
-    if constexpr (HD == 64 || HD == 80) {
-      // (measured, tools/attn_pp_ab.py: 4096 x 4096 x 80 with rel-pos 1690 against 1745 us; 785- and 1000-token sequences
-      // 15-25 % SLOWER than two 4-wave workgroups per CU -- few query blocks per head, and the co-execution the schedule
-      // is built for did not appear: SQ_VALU_MFMA_COEXEC stayed at 23 % of the matrix-busy cycles)
-      if (pp && a.Sq >= 2048 && a.Sk >= 2048 && a.mask_kind == HGL_MASK_NONE && (!a.rel_h || (a.kw & 31) == 0) &&
-          ((a.Sk & 31) == 0 || !a.rel_h)) {
-        constexpr int KROW_ = 2 * HD + 8, VP_ = 96;
-        constexpr size_t lds = (size_t)2 * KV_CHUNK * (KROW_ + 2 * VP_) * sizeof(_Float16);
-        HGL_RESERVE_LDS((attn_x3pp_kernel<HD, TERMS>), lds, "attention (ping-pong kernel)");
-        hipLaunchKernelGGL((attn_x3pp_kernel<HD, TERMS>), dim3((a.Sq + 255) / 256, a.B * a.H), dim3(512), lds, st, a);
-        return hgl_check_launch("attention");
-      }
-    }
-    if (HD == 80 && a.rel_h && a.kh == 14 && a.kw == 14 && a.Sk == 196 && a.mask_kind == HGL_MASK_NONE) {
-      hipLaunchKernelGGL((attn_x3_kernel<HD, HD == 80 ? 14 : 0, 4, TERMS>), grid, dim3(256), 0, st, a);   // rel_h / rel_w given as tensors
-    } else if (w8 && !a.rel_h && dual && HD == 64 && (a.mask_kind != HGL_MASK_CLS_KEEP || a.Sk <= 257)) {
-      // head dim 64 (the CLIP sequences): two items per CU -- one 4-wave workgroup per item, two query tiles per wave.
-      // 868 against 976 us on 1024 x 12 x 197 x 64 (141 against 125 TF/s), -0.4 ms per benchmark step (HGL_ATTN_DUAL=0: the
-      // persistent 8-wave kernel)
-      hipLaunchKernelGGL((attn_x3q_kernel<HD == 64 ? 64 : 16, 2, TERMS>), dim3((unsigned)(a.B * a.H)), dim3(256), 0, st, a);
-    } else if (w8 && !a.rel_h) {   // one 8-wave workgroup per item (K / V staged once)
-      hipLaunchKernelGGL((attn_x3_kernel<HD, 0, 8, TERMS>), dim3((a.Sq + 255) / 256, a.B * a.H), dim3(512), 0, st, a);
-    } else {
-      hipLaunchKernelGGL((attn_x3_kernel<HD, 0, 4, TERMS>), grid, dim3(256), 0, st, a);
+  if constexpr (HD == 64 || HD == 80) {
+    if (route == HGL_ATTN_PINGPONG) {
+      constexpr int KROW_ = 2 * HD + 8, VP_ = 96;
+      constexpr size_t lds = (size_t)2 * KV_CHUNK * (KROW_ + 2 * VP_) * sizeof(_Float16);
+      HGL_RESERVE_LDS((attn_x3pp_kernel<HD, TERMS>), lds, "attention (ping-pong kernel)");
+      hipLaunchKernelGGL((attn_x3pp_kernel<HD, TERMS>), dim3((a.Sq + 255) / 256, a.B * a.H), dim3(512), lds, st, a);
+      return hgl_check_launch("attention");
     }
   }
-  else hipLaunchKernelGGL(attn_f32_kernel<HD>, grid, dim3(256), 0, st, a);
+  switch (route) {
+    case HGL_ATTN_REL14:   // rel_h / rel_w given as tensors
+      hipLaunchKernelGGL((attn_x3_kernel<HD, HD == 80 ? 14 : 0, 4, TERMS>), grid, dim3(256), 0, st, a);
+      break;
+    case HGL_ATTN_DUAL:
+      hipLaunchKernelGGL((attn_x3q_kernel<HD == 64 ? 64 : 16, 2, TERMS>), dim3((unsigned)(a.B * a.H)), dim3(256), 0, st, a);
+      break;
+    case HGL_ATTN_WIDE:
+      hipLaunchKernelGGL((attn_x3_kernel<HD, 0, 8, TERMS>), dim3((a.Sq + 255) / 256, a.B * a.H), dim3(512), 0, st, a);
+      break;
+    case HGL_ATTN_TILE:
+      hipLaunchKernelGGL((attn_x3_kernel<HD, 0, 4, TERMS>), grid, dim3(256), 0, st, a);
+      break;
+    default:               // HGL_ATTN_F32
+      hipLaunchKernelGGL(attn_f32_kernel<HD>, grid, dim3(256), 0, st, a);
+  }
   return hgl_check_launch("attention");
 }
 
-}  // namespace
-
-
-// Windowed attention of the SAM encoder (14 x 14 windows, head dim 80, f16x3 mode) with the decomposed rel-pos terms
-// computed INSIDE the kernel from the tables Rh / Rw [27, 80] (no rel_h / rel_w tensors, no separate table kernel).
-// Returns HGL_EINVAL-free "not applicable" (1) when the shape is not the one this path serves.
-int hgl_launch_attention_win14(const float* q, const float* k, const float* v, void* out_hi, void* out_lo, int B, int H, int hd,
-                               int ldq, int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb, long long sob,
-                               float scale, const float* Rh, const float* Rw, hipStream_t st) {
-  static const int wide = HGL_DIAG_SWITCH("HGL_ATTN_WIDE", 1);
-  static const int fused = HGL_DIAG_SWITCH("HGL_ATTN_RELPOS_FUSED", 1);
-  if (!wide || !fused || hd != 80 || !hgl_split_layout() || !out_hi || !out_lo || !Rh || !Rw) return 1;
-  HGL_REQUIRE(q && k && v && B > 0 && H > 0 && (long long)B * H <= 65535, "attention_win14: bad arguments");
-  AttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.out = nullptr;
-  a.B = B; a.H = H; a.Sq = 196; a.Sk = 196;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-  a.sqb = sqb; a.skb = skb; a.svb = svb; a.sob = sob;
-  a.scale = scale; a.mask_kind = HGL_MASK_NONE; a.keep = nullptr; a.keep_b0 = 0; a.keep_n = B;
-  a.rel_h = nullptr; a.rel_w = nullptr; a.kh = 14; a.kw = 14;
-  a.tab_h = Rh; a.tab_w = Rw;
-  {   // the tables' fp16 halves when the model registered them (unscaled: scale 2^0)
-    const void *hh = nullptr, *hl = nullptr, *wh = nullptr, *wl = nullptr;
-    int sh = 1, sw = 1, n1 = 0, k1 = 0, n2 = 0, k2 = 0;
-    if (hgl_get_split_weight(Rh, &hh, &hl, &sh, &n1, &k1) && hgl_get_split_weight(Rw, &wh, &wl, &sw, &n2, &k2) && sh == 0 && sw == 0 &&
-        n1 == 27 && n2 == 27 && k1 == 80 && k2 == 80) {
-      a.tabh_hi = (const _Float16*)hh; a.tabh_lo = (const _Float16*)hl;
-      a.tabw_hi = (const _Float16*)wh; a.tabw_lo = (const _Float16*)wl;
-    }
+// Windowed attention of the SAM encoder (14 x 14 windows, head dim 80, split-fp16 modes) with the decomposed rel-pos terms
+// computed INSIDE the kernel from the tables [27, 80] (no rel_h / rel_w tensors, no separate table kernel)
+int launch_win14(AttnArgs& a, const HglAttn& d, hipStream_t st) {
+  HGL_REQUIRE(d.q && d.k && d.v && d.B > 0 && d.H > 0 && (long long)d.B * d.H <= 65535, "attention_win14: bad arguments");
+  a.out = nullptr;
+  a.keep = nullptr, a.keep_b0 = 0, a.keep_n = d.B;
+  a.kh = 14, a.kw = 14;
+  a.tab_h = d.tab_h, a.tab_w = d.tab_w;
+  const void* t[4];   // the tables' fp16 halves when the model registered them
+  if (hgl_attention_rel_tables(d.tab_h, d.tab_w, t)) {
+    a.tabh_hi = (const _Float16*)t[0], a.tabh_lo = (const _Float16*)t[1];
+    a.tabw_hi = (const _Float16*)t[2], a.tabw_lo = (const _Float16*)t[3];
   }
-  a.out_hi = (_Float16*)out_hi; a.out_lo = hgl_split_terms() == 1 ? nullptr : (_Float16*)out_lo;   // f16 mode: hi plane only
-  HglProfScope prof(HGL_PROF_ATTN, 4.0 * B * H * 196.0 * 196.0 * 80, 0.0, st);
-  if (hgl_split_terms() == 1) hipLaunchKernelGGL((attn_x3_kernel<80, 14, 8, 1>), dim3(1, (unsigned)(B * H)), dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((attn_x3_kernel<80, 14, 8>), dim3(1, (unsigned)(B * H)), dim3(512), 0, st, a);
+  HglProfScope prof(HGL_PROF_ATTN, 4.0 * d.B * d.H * 196.0 * 196.0 * 80, 0.0, st);
+  if (hgl_split_terms() == 1) hipLaunchKernelGGL((attn_x3_kernel<80, 14, 8, 1>), dim3(1, (unsigned)(d.B * d.H)), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((attn_x3_kernel<80, 14, 8>), dim3(1, (unsigned)(d.B * d.H)), dim3(512), 0, st, a);
   return hgl_check_launch("attention_win14");
 }
 
 // few-key attention (Sk <= 8, head dim 16): output fp32 (out) or the fp16 split pair (out == nullptr)
-int hgl_launch_attention_smallk(const float* q, const float* k, const float* v, float* out, void* out_hi, void* out_lo,
-                                int B, int H, int Sq, int Sk, int hd, int ldq, int ldk, int ldv, int ldo, long long sqb,
-                                long long skb, long long svb, long long sob, float scale, hipStream_t st) {
-  HGL_REQUIRE(q && k && v && (out || (out_hi && out_lo)), "attention_smallk: null operand");
-  HGL_REQUIRE(hd == 16 && Sk >= 1 && Sk <= SMALLK_MAX && H >= 1 && 256 % H == 0, "attention_smallk: unsupported shape (hd %d, Sk %d, H %d)", hd, Sk, H);
-  HGL_REQUIRE(((ldq | ldk | ldv | ldo) & 3) == 0 && ((sqb | skb | svb | sob) & 3) == 0, "attention_smallk: strides must be multiples of 4");
-  HGL_REQUIRE(B <= 65535, "attention_smallk: B too large");
+int launch_smallk(const HglAttn& d, hipStream_t st) {
+  HGL_REQUIRE(d.q && d.k && d.v && (d.out || (d.out_hi && d.out_lo)), "attention_smallk: null operand");
+  HGL_REQUIRE(d.hd == 16 && d.Sk >= 1 && d.Sk <= SMALLK_MAX && d.H >= 1 && 256 % d.H == 0,
+              "attention_smallk: unsupported shape (hd %d, Sk %d, H %d)", d.hd, d.Sk, d.H);
+  HGL_REQUIRE(((d.ldq | d.ldk | d.ldv | d.ldo) & 3) == 0 && ((d.sqb | d.skb | d.svb | d.sob) & 3) == 0,
+              "attention_smallk: strides must be multiples of 4");
+  HGL_REQUIRE(d.B <= 65535, "attention_smallk: B too large");
   SmallKArgs a;
-  a.q = q; a.k = k; a.v = v; a.out = out; a.out_hi = (_Float16*)out_hi;
-  a.out_lo = hgl_split_terms() == 1 ? nullptr : (_Float16*)out_lo;   // f16 mode: hi plane only
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-  a.sqb = sqb; a.skb = skb; a.svb = svb; a.sob = sob; a.scale = scale;
-  const int qpb = 256 / H;
-  HglProfScope prof(HGL_PROF_ATTN, 4.0 * B * (double)H * Sq * Sk * hd, 0.0, st);
-  hipLaunchKernelGGL(attn_smallk_kernel, dim3((unsigned)((Sq + qpb - 1) / qpb), (unsigned)B), dim3(256),
-                     (size_t)2 * Sk * H * 16 * sizeof(float), st, a);
+  a.q = d.q; a.k = d.k; a.v = d.v; a.out = d.out; a.out_hi = (_Float16*)d.out_hi;
+  a.out_lo = hgl_split_terms() == 1 ? nullptr : (_Float16*)d.out_lo;   // f16 mode: hi plane only
+  a.B = d.B; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk; a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
+  a.sqb = d.sqb; a.skb = d.skb; a.svb = d.svb; a.sob = d.sob; a.scale = d.scale;
+  const int qpb = 256 / d.H;
+  HglProfScope prof(HGL_PROF_ATTN, 4.0 * d.B * (double)d.H * d.Sq * d.Sk * d.hd, 0.0, st);
+  hipLaunchKernelGGL(attn_smallk_kernel, dim3((unsigned)((d.Sq + qpb - 1) / qpb), (unsigned)d.B), dim3(256),
+                     (size_t)2 * d.Sk * d.H * 16 * sizeof(float), st, a);
   return hgl_check_launch("attention_smallk");
 }
 
-int hgl_launch_attention_fewq(const float* q, const float* k, const float* v, float* out, int B, int H, int Sq, int Sk,
-                              int hd, int ldq, int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb,
-                              long long sob, float scale, hipStream_t st) {
-  HGL_REQUIRE(q && k && v && out, "attention_fewq: null operand");
-  HGL_REQUIRE(hd == 16 && Sq >= 1 && Sq <= FEWQ_MAX, "attention_fewq: unsupported shape (hd %d, Sq %d)", hd, Sq);
-  HGL_REQUIRE(((ldk | ldv) & 3) == 0 && ((skb | svb) & 3) == 0, "attention_fewq: K/V strides must be multiples of 4");
+// few queries over many keys: one workgroup per (batch, head), or (HGL_ATTN_FEWQ_CHUNKED, the decoder's sizes: 8 heads of 16,
+// up to 7 queries) the chunked kernel and its combine
+int launch_fewq(const HglAttn& d, bool chunked, hipStream_t st) {
+  if (chunked) {
+    HGL_REQUIRE(d.q && d.k && d.v && d.out && d.part, "attention_fewq_chunked: null operand");
+    HGL_REQUIRE(d.kv_group >= 1 && d.B % d.kv_group == 0, "attention_fewq_chunked: %d batches in groups of %d", d.B, d.kv_group);
+    HGL_REQUIRE(d.hd == 16 && d.H == 8 && d.Sq >= 1 && d.Sq <= 7 && d.Sk >= 1 && d.B >= 1 && d.B <= 65535,
+                "attention_fewq_chunked: unsupported shape (hd %d, H %d, Sq %d)", d.hd, d.H, d.Sq);
+    HGL_REQUIRE(((d.ldk | d.ldv) & 3) == 0 && ((d.skb | d.svb) & 3) == 0 && (((uintptr_t)d.k | (uintptr_t)d.v) & 15) == 0,
+                "attention_fewq_chunked: K/V strides must be multiples of 4");
+    HGL_REQUIRE(d.part_bytes >= hgl_attention_fewq_part_bytes(d.B, d.Sk), "attention_fewq_chunked: partial buffer too small");
+  } else {
+    HGL_REQUIRE(d.q && d.k && d.v && d.out, "attention_fewq: null operand");
+    HGL_REQUIRE(d.hd == 16 && d.Sq >= 1 && d.Sq <= FEWQ_MAX, "attention_fewq: unsupported shape (hd %d, Sq %d)", d.hd, d.Sq);
+    HGL_REQUIRE(((d.ldk | d.ldv) & 3) == 0 && ((d.skb | d.svb) & 3) == 0, "attention_fewq: K/V strides must be multiples of 4");
+  }
   FewQArgs a;
-  a.kvdiv = 1;
-  a.q = q; a.k = k; a.v = v; a.out = out; a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.sqb = sqb; a.skb = skb; a.svb = svb; a.sob = sob; a.scale = scale;
-  HglProfScope prof(HGL_PROF_ATTN, 4.0 * B * (double)H * Sq * Sk * hd, 0.0, st);
-  hipLaunchKernelGGL(attn_fewq_kernel, dim3((unsigned)(B * H)), dim3(256), 0, st, a);
-  return hgl_check_launch("attention_fewq");
+  a.kvdiv = chunked ? d.kv_group : 1;
+  a.q = d.q; a.k = d.k; a.v = d.v; a.out = d.out; a.B = d.B; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk;
+  a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo; a.sqb = d.sqb; a.skb = d.skb; a.svb = d.svb; a.sob = d.sob;
+  a.scale = d.scale;
+  HglProfScope prof(HGL_PROF_ATTN, 4.0 * d.B * (double)d.H * d.Sq * d.Sk * d.hd, 0.0, st);
+  if (!chunked) {
+    hipLaunchKernelGGL(attn_fewq_kernel, dim3((unsigned)(d.B * d.H)), dim3(256), 0, st, a);
+    return hgl_check_launch("attention_fewq");
+  }
+  const int nchunk = (d.Sk + FQC_KEYS - 1) / FQC_KEYS;
+  hipLaunchKernelGGL(attn_fewq_chunk_kernel, dim3((unsigned)nchunk, (unsigned)d.B), dim3(256), 0, st, a, d.part);
+  hipLaunchKernelGGL(attn_fewq_combine_kernel, dim3(7, (unsigned)d.B), dim3(128), 0, st, (const float*)d.part, nchunk, d.Sq, d.out,
+                     d.ldo, d.sob);
+  return hgl_check_launch("attention_fewq_chunked");
 }
 
-// chunked form for the decoder's sizes (8 heads of 16, up to 7 queries): `part` >= hgl_attention_fewq_part_bytes(B, Sk) bytes
+}  // namespace
+
+// `part` >= this many bytes for the chunked few-query form
 size_t hgl_attention_fewq_part_bytes(int B, int Sk) {
   return (size_t)B * ((Sk + FQC_KEYS - 1) / FQC_KEYS) * 16 * 7 * FQC_PART * sizeof(float);
 }
 
-int hgl_launch_attention_fewq_chunked(const float* q, const float* k, const float* v, float* out, int B, int H, int Sq, int Sk,
-                                      int hd, int ldq, int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb,
-                                      long long sob, float scale, float* part, size_t part_bytes, hipStream_t st, int kv_group) {
-  HGL_REQUIRE(q && k && v && out && part, "attention_fewq_chunked: null operand");
-  HGL_REQUIRE(kv_group >= 1 && B % kv_group == 0, "attention_fewq_chunked: %d batches in groups of %d", B, kv_group);
-  HGL_REQUIRE(hd == 16 && H == 8 && Sq >= 1 && Sq <= 7 && Sk >= 1 && B >= 1 && B <= 65535,
-              "attention_fewq_chunked: unsupported shape (hd %d, H %d, Sq %d)", hd, H, Sq);
-  HGL_REQUIRE(((ldk | ldv) & 3) == 0 && ((skb | svb) & 3) == 0 && (((uintptr_t)k | (uintptr_t)v) & 15) == 0,
-              "attention_fewq_chunked: K/V strides must be multiples of 4");
-  HGL_REQUIRE(part_bytes >= hgl_attention_fewq_part_bytes(B, Sk), "attention_fewq_chunked: partial buffer too small");
-  FewQArgs a;
-  a.kvdiv = kv_group;
-  a.q = q; a.k = k; a.v = v; a.out = out; a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.sqb = sqb; a.skb = skb; a.svb = svb; a.sob = sob; a.scale = scale;
-  const int nchunk = (Sk + FQC_KEYS - 1) / FQC_KEYS;
-  HglProfScope prof(HGL_PROF_ATTN, 4.0 * B * (double)H * Sq * Sk * hd, 0.0, st);
-  hipLaunchKernelGGL(attn_fewq_chunk_kernel, dim3((unsigned)nchunk, (unsigned)B), dim3(256), 0, st, a, part);
-  hipLaunchKernelGGL(attn_fewq_combine_kernel, dim3(7, (unsigned)B), dim3(128), 0, st, (const float*)part, nchunk, Sq, out, ldo, sob);
-  return hgl_check_launch("attention_fewq_chunked");
+bool hgl_attention_rel_tables(const float* tab_h, const float* tab_w, const void* t[4]) {
+  int sh = 1, sw = 1, n1 = 0, k1 = 0, n2 = 0, k2 = 0;
+  t[0] = t[1] = t[2] = t[3] = nullptr;
+  return tab_h && tab_w && hgl_get_split_weight(tab_h, &t[0], &t[1], &sh, &n1, &k1) &&
+         hgl_get_split_weight(tab_w, &t[2], &t[3], &sw, &n2, &k2) && sh == 0 && sw == 0 && n1 == 27 && n2 == 27 &&
+         k1 == 80 && k2 == 80;
 }
 
-int hgl_launch_attention(const float* q, const float* k, const float* v, float* out, int B, int H,
-                         int Sq, int Sk, int hd, int ldq, int ldk, int ldv, int ldo, long long sqb,
-                         long long skb, long long svb, long long sob, float scale, int mask_kind,
-                         const uint8_t* keep, int keep_b0, int keep_n, const float* rel_h,
-                         const float* rel_w, int kh, int kw, hipStream_t st) {
-  return hgl_launch_attention_split(q, k, v, out, nullptr, nullptr, B, H, Sq, Sk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb, sob,
-                                    scale, mask_kind, keep, keep_b0, keep_n, rel_h, rel_w, kh, kw, st);
+HglAttnRoute hgl_attention_route(const HglAttn& d) {
+  if (d.qkv_hi || d.qkv_lo) return hgl_attention_route_planes(d);
+  if (d.part) return HGL_ATTN_FEWQ_CHUNKED;     // the caller's choice (sam_api.hip: DecRoute::chunked); the launch validates
+  if (d.tab_h || d.tab_w)                       // registered halves or not: the kernel splits the tables itself without them
+    return sw_wide() && sw_relpos_fused() && d.hd == 80 && hgl_split_layout() && d.out_hi && d.out_lo && d.tab_h && d.tab_w &&
+                   d.Sq == 196 && d.Sk == 196 && d.mask_kind == HGL_MASK_NONE && !d.rel_h && !d.rel_w
+               ? HGL_ATTN_WIN14
+               : HGL_ATTN_NONE;
+  const bool plain = d.mask_kind == HGL_MASK_NONE && !d.rel_h;
+  if (d.out && d.hd == 16 && d.Sq <= FEWQ_MAX && d.Sk >= 1024 && plain) return HGL_ATTN_FEWQ;
+  if (d.hd == 16 && d.Sk <= SMALLK_MAX && d.Sq >= 256 && plain && d.H > 0 && 256 % d.H == 0) return HGL_ATTN_SMALLK;
+  if (d.hd != 16 && d.hd != 32 && d.hd != 64 && d.hd != 80) return HGL_ATTN_NONE;
+  return hgl_split_layout() ? route_x3(d) : HGL_ATTN_F32;
 }
 
-// out != nullptr: fp32 output; out == nullptr (f16x3 mode only): the fp16 hi+lo pair (out_hi, out_lo), same strides
-int hgl_launch_attention_split(const float* q, const float* k, const float* v, float* out, void* out_hi, void* out_lo, int B,
-                               int H, int Sq, int Sk, int hd, int ldq, int ldk, int ldv, int ldo, long long sqb,
-                               long long skb, long long svb, long long sob, float scale, int mask_kind,
-                               const uint8_t* keep, int keep_b0, int keep_n, const float* rel_h,
-                               const float* rel_w, int kh, int kw, hipStream_t st) {
-  HGL_REQUIRE(q && k && v && (out || (out_hi && out_lo)), "attention: null operand");
-  HGL_REQUIRE(out || hgl_split_layout(), "attention: split output exists in the split-fp16 modes only");
-  HGL_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "attention: bad shape");
-  HGL_REQUIRE((ldq & 3) == 0 && (ldk & 3) == 0 && (ldv & 3) == 0 && (ldo & 3) == 0, "attention: leading dims must be multiples of 4");
-  HGL_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15) == 0,
-              "attention: operands must be 16-byte aligned");
-  HGL_REQUIRE(((sqb | skb | svb | sob) & 3) == 0, "attention: batch strides must be multiples of 4");
-  HGL_REQUIRE(mask_kind >= 0 && mask_kind <= 2, "attention: bad mask kind %d", mask_kind);
-  HGL_REQUIRE(mask_kind != HGL_MASK_CLS_KEEP || keep, "attention: HGL_MASK_CLS_KEEP needs keep bytes");
-  HGL_REQUIRE((rel_h == nullptr) == (rel_w == nullptr), "attention: rel_h and rel_w go together");
-  HGL_REQUIRE(!rel_h || (kh > 0 && kw > 0 && kh * kw == Sk), "attention: kh*kw must equal Sk");
-  HGL_REQUIRE((long long)B * H <= 65535, "attention: B*H too large for grid.y");
-  if (out && hd == 16 && Sq <= FEWQ_MAX && Sk >= 1024 && mask_kind == HGL_MASK_NONE && !rel_h)
-    return hgl_launch_attention_fewq(q, k, v, out, B, H, Sq, Sk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb, sob, scale, st);
-  if (hd == 16 && Sk <= SMALLK_MAX && Sq >= 256 && mask_kind == HGL_MASK_NONE && !rel_h && 256 % H == 0)
-    return hgl_launch_attention_smallk(q, k, v, out, out_hi, out_lo, B, H, Sq, Sk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb,
-                                       sob, scale, st);
+int hgl_launch_attention(const HglAttn& d, hipStream_t st) {
+  const HglAttnRoute route = hgl_attention_route(d);
+  if (d.qkv_hi || d.qkv_lo) {
+    HGL_REQUIRE(route != HGL_ATTN_NONE, "attention: no pre-split kernel serves B %d, H %d, S %d x %d, hd %d, mask %d", d.B, d.H,
+                d.Sq, d.Sk, d.hd, d.mask_kind);
+    return hgl_launch_attention_planes(d, route, st);
+  }
+  if (route == HGL_ATTN_FEWQ_CHUNKED) return launch_fewq(d, true, st);
+  const bool win14 = d.tab_h || d.tab_w;
+  if (win14) {
+    HGL_REQUIRE(route == HGL_ATTN_WIN14, "attention: no kernel takes rel-pos tables at S %d x %d, hd %d, mask %d", d.Sq, d.Sk, d.hd,
+                d.mask_kind);
+  } else {
+    HGL_REQUIRE(d.q && d.k && d.v && (d.out || (d.out_hi && d.out_lo)), "attention: null operand");
+    HGL_REQUIRE(d.out || hgl_split_layout(), "attention: split output exists in the split-fp16 modes only");
+    HGL_REQUIRE(d.B > 0 && d.H > 0 && d.Sq > 0 && d.Sk > 0, "attention: bad shape");
+    HGL_REQUIRE((d.ldq & 3) == 0 && (d.ldk & 3) == 0 && (d.ldv & 3) == 0 && (d.ldo & 3) == 0,
+                "attention: leading dims must be multiples of 4");
+    HGL_REQUIRE((((uintptr_t)d.q | (uintptr_t)d.k | (uintptr_t)d.v | (uintptr_t)d.out | (uintptr_t)d.out_hi | (uintptr_t)d.out_lo) & 15) == 0,
+                "attention: operands must be 16-byte aligned");
+    HGL_REQUIRE(((d.sqb | d.skb | d.svb | d.sob) & 3) == 0, "attention: batch strides must be multiples of 4");
+    HGL_REQUIRE(d.mask_kind >= 0 && d.mask_kind <= 2, "attention: bad mask kind %d", d.mask_kind);
+    HGL_REQUIRE(d.mask_kind != HGL_MASK_CLS_KEEP || d.keep, "attention: HGL_MASK_CLS_KEEP needs keep bytes");
+    HGL_REQUIRE((d.rel_h == nullptr) == (d.rel_w == nullptr), "attention: rel_h and rel_w go together");
+    HGL_REQUIRE(!d.rel_h || (d.kh > 0 && d.kw > 0 && d.kh * d.kw == d.Sk), "attention: kh*kw must equal Sk");
+    HGL_REQUIRE((long long)d.B * d.H <= 65535, "attention: B*H too large for grid.y");
+    if (route == HGL_ATTN_FEWQ) return launch_fewq(d, false, st);
+    if (route == HGL_ATTN_SMALLK) return launch_smallk(d, st);
+    HGL_REQUIRE(route != HGL_ATTN_NONE, "attention: unsupported head dim %d (16,32,64,80)", d.hd);
+  }
   AttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.out = out;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk;
-  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-  a.sqb = sqb; a.skb = skb; a.svb = svb; a.sob = sob;
-  a.scale = scale; a.mask_kind = mask_kind; a.keep = keep; a.keep_b0 = keep_b0; a.keep_n = keep_n > 0 ? keep_n : B;
-  a.rel_h = rel_h; a.rel_w = rel_w; a.kh = kh; a.kw = kw;
+  a.q = d.q; a.k = d.k; a.v = d.v; a.out = d.out;
+  a.B = d.B; a.H = d.H; a.Sq = d.Sq; a.Sk = d.Sk;
+  a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.ldo = d.ldo;
+  a.sqb = d.sqb; a.skb = d.skb; a.svb = d.svb; a.sob = d.sob;
+  a.scale = d.scale; a.mask_kind = d.mask_kind; a.keep = d.keep; a.keep_b0 = d.keep_b0; a.keep_n = d.keep_n > 0 ? d.keep_n : d.B;
+  a.rel_h = d.rel_h; a.rel_w = d.rel_w; a.kh = d.kh; a.kw = d.kw;
   a.tab_h = nullptr; a.tab_w = nullptr;
-  a.out_hi = (_Float16*)out_hi; a.out_lo = hgl_split_terms() == 1 ? nullptr : (_Float16*)out_lo;   // f16 mode: hi plane only
+  a.out_hi = (_Float16*)d.out_hi; a.out_lo = hgl_split_terms() == 1 ? nullptr : (_Float16*)d.out_lo;   // f16 mode: hi plane only
+  if (win14) return launch_win14(a, d, st);
   const bool one = hgl_split_terms() == 1;
-  switch (hd) {
-    case 16: return one ? launch_hd<16, 1>(a, st) : launch_hd<16, 3>(a, st);
-    case 32: return one ? launch_hd<32, 1>(a, st) : launch_hd<32, 3>(a, st);
-    case 64: return one ? launch_hd<64, 1>(a, st) : launch_hd<64, 3>(a, st);
-    case 80: return one ? launch_hd<80, 1>(a, st) : launch_hd<80, 3>(a, st);
-    default:
-      hgl_set_error("attention: unsupported head dim %d (16,32,64,80)", hd);
-      return HGL_EINVAL;
+  switch (d.hd) {
+    case 16: return one ? launch_hd<16, 1>(a, route, st) : launch_hd<16, 3>(a, route, st);
+    case 32: return one ? launch_hd<32, 1>(a, route, st) : launch_hd<32, 3>(a, route, st);
+    case 64: return one ? launch_hd<64, 1>(a, route, st) : launch_hd<64, 3>(a, route, st);
+    default: return one ? launch_hd<80, 1>(a, route, st) : launch_hd<80, 3>(a, route, st);
   }
 }
 

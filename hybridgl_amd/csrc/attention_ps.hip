@@ -1056,101 +1056,85 @@ extern "C" int hgl_debug_ps_stamps(unsigned long long* out, int n, int block, in
 }
 #endif
 
-// the kernels here read the lo planes the qkv GEMM writes: three-term mode only (f16 mode takes the fp32-input kernels)
-bool hgl_attention_ps_enabled() { return attn_ps_flag() != 0 && hgl_split_layout() && hgl_split_terms() == 3; }
-
 extern "C" int hgl_attention_presplit(int on) {
   const int prev = attn_ps_flag();
   if (on >= 0) g_attn_ps = on != 0;
   return prev;
 }
 
-// THE predicate of this file: does hgl_launch_attention_ps serve this call?  The callers that must decide BEFORE the
-// in-projection whether it writes split planes (sam_api.hip, clip_api.hip: afterwards there is no fp32 qkv to fall back to) ask
-// exactly what the launch asks.  plane_delta = byte distance from the hi to the lo plane; rel_kh / rel_kw != 0: rel-pos terms
-// given as tensors; tab_h / tab_w: the windowed blocks' tables.  Returns the kernel kind (> 0) or 0.
-enum { PS_K_NONE = 0, PS_K_WIN, PS_K_RELT80, PS_K_RELT64, PS_K_CLIP, PS_K_PLAIN80, PS_K_PLAIN64 };
-int hgl_attention_ps_serves(long long plane_delta, int ld, int B, int H, int S, int hd, int mask_kind, int rel_kh, int rel_kw,
-                            const float* tab_h, const float* tab_w) {
-  if (!hgl_attention_ps_enabled()) return PS_K_NONE;
-  if (!(hd == 80 || hd == 64) || mask_kind == HGL_MASK_CAUSAL || B <= 0 || H <= 0 || S <= 0) return PS_K_NONE;
+// The plane-form half of hgl_attention_route.  The callers that must decide BEFORE the in-projection whether it writes split
+// planes (sam_api.hip, clip_api.hip: afterwards there is no fp32 qkv to fall back to) ask with the descriptor they launch with.
+HglAttnRoute hgl_attention_route_planes(const HglAttn& d) {
+  const int S = d.Sq, hd = d.hd;
+  // the kernels here read the lo planes the qkv GEMM writes: three-term mode only (f16 mode takes the fp32-input kernels)
+  if (!(attn_ps_flag() != 0 && hgl_split_layout() && hgl_split_terms() == 3) || d.Sk != S) return HGL_ATTN_NONE;
+  if (!(hd == 80 || hd == 64) || d.mask_kind == HGL_MASK_CAUSAL || d.B <= 0 || d.H <= 0 || S <= 0) return HGL_ATTN_NONE;
   // the DMA addresses one item's K / V rows with a 32-bit offset from the item's base in the hi plane, lo plane included
-  const long long span = (long long)S * ld * 2 + (long long)ld * 2;
-  if (plane_delta < 0 || plane_delta + span >= (1ll << 32)) return PS_K_NONE;
+  const long long plane_delta = (const char*)d.qkv_lo - (const char*)d.qkv_hi;
+  const long long span = (long long)S * d.ld * 2 + (long long)d.ld * 2;
+  if (plane_delta < 0 || plane_delta + span >= (1ll << 32)) return HGL_ATTN_NONE;
   // the 197-token CLIP sequences: 1 = one workgroup per item with two query tiles per wave (K / V staged once),
   // 2 = the pipelined persistent kernel with two workgroups per item.  (The pipelined kernel with two query tiles per wave
   // -- attn_psp_kernel<64, PS_PLAIN, 2>, which the template still admits -- needs 256 VGPRs + 19 spilled dwords whose scratch
   // reloads wait on vmcnt in the middle of the DMA stream: 855 us against 742 for (1) on 1024 x 12 x 197 x 64; not instantiated.)
   static const int clip_kernel = HGL_DIAG_SWITCH("HGL_ATTN_PS_CLIP", 1);
-  if (tab_h || tab_w) {
-    const void *hh = nullptr, *hl = nullptr;
-    int sh = 1, n1 = 0, k1 = 0;
-    if (tab_h && tab_w && hd == 80 && S == 196 && mask_kind == HGL_MASK_NONE && !rel_kh &&
-        hgl_get_split_weight(tab_h, &hh, &hl, &sh, &n1, &k1) && sh == 0 && n1 == 27 && k1 == 80 &&
-        hgl_get_split_weight(tab_w, &hh, &hl, &sh, &n1, &k1) && sh == 0 && n1 == 27 && k1 == 80)
-      return PS_K_WIN;
-    return PS_K_NONE;
+  const int rel_kh = d.rel_h ? d.kh : 0, rel_kw = d.rel_h ? d.kw : 0;
+  if (d.tab_h || d.tab_w) {
+    const void* t[4];
+    return hd == 80 && S == 196 && d.mask_kind == HGL_MASK_NONE && !rel_kh && hgl_attention_rel_tables(d.tab_h, d.tab_w, t)
+               ? HGL_ATTN_PS_WIN
+               : HGL_ATTN_NONE;
   }
   if (rel_kh || rel_kw) {
     // 32-bit element offsets into the rel-pos tensors
-    if (mask_kind == HGL_MASK_NONE && (rel_kw & 31) == 0 && (S & 31) == 0 && rel_kh * rel_kw == S &&
-        (long long)B * H * S * (long long)(rel_kh > rel_kw ? rel_kh : rel_kw) < (1ll << 32))
-      return hd == 80 ? PS_K_RELT80 : PS_K_RELT64;
-    return PS_K_NONE;
+    return d.mask_kind == HGL_MASK_NONE && (rel_kw & 31) == 0 && (S & 31) == 0 && rel_kh * rel_kw == S &&
+                   (long long)d.B * d.H * S * (long long)(rel_kh > rel_kw ? rel_kh : rel_kw) < (1ll << 32)
+               ? HGL_ATTN_PS_RELT
+               : HGL_ATTN_NONE;
   }
-  if (hd == 64 && S > 128 && S <= 256 && clip_kernel == 1 && (mask_kind != HGL_MASK_CLS_KEEP || S <= 257)) return PS_K_CLIP;
-  if (mask_kind == HGL_MASK_NONE || (mask_kind == HGL_MASK_CLS_KEEP && S <= 257)) return hd == 80 ? PS_K_PLAIN80 : PS_K_PLAIN64;
-  return PS_K_NONE;
+  if (hd == 64 && S > 128 && S <= 256 && clip_kernel == 1 && (d.mask_kind != HGL_MASK_CLS_KEEP || S <= 257)) return HGL_ATTN_PS_CLIP;
+  if (d.mask_kind == HGL_MASK_NONE || (d.mask_kind == HGL_MASK_CLS_KEEP && S <= 257)) return HGL_ATTN_PS_PLAIN;
+  return HGL_ATTN_NONE;
 }
 
-// Attention on the split qkv planes.  Returns 1 ("not applicable": the caller takes the fp32-input path) when the shape is
-// not one this kernel serves, 0 on success, < 0 on error.
+// The plane-form half of hgl_launch_attention; `route` is hgl_attention_route_planes' answer for d (not HGL_ATTN_NONE).
 //   qkv_hi / qkv_lo : fp16 planes, row (b * sb + s), columns qcol / kcol / vcol + head * hd, leading dimension ld (halfs)
 //   tab_h / tab_w   : SAM's windowed blocks (S == 196, hd == 80): the rel-pos tables (fp32 pointers registered with
 //                     hgl_register_split_weight at scale 2^0); rel_h / rel_w: the terms as tensors (global blocks)
-int hgl_launch_attention_ps(const void* qkv_hi, const void* qkv_lo, int ld, int qcol, int kcol, int vcol, long long sb, int B,
-                            int H, int S, int hd, float* out, void* out_hi, void* out_lo, int ldo, long long sob, float scale,
-                            int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, const float* rel_h, const float* rel_w,
-                            int kh, int kw, const float* tab_h, const float* tab_w, hipStream_t st) {
-  const long long delta = (const char*)qkv_lo - (const char*)qkv_hi;
-  const int kind = hgl_attention_ps_serves(delta, ld, B, H, S, hd, mask_kind, rel_h ? kh : 0, rel_h ? kw : 0, tab_h, tab_w);
-  if (kind == PS_K_NONE) return 1;
-  HGL_REQUIRE(qkv_hi && qkv_lo && (out || (out_hi && out_lo)) && B > 0 && H > 0 && S > 0, "attention_ps: bad arguments");
-  HGL_REQUIRE((ld & 7) == 0 && (qcol & 7) == 0 && (kcol & 7) == 0 && (vcol & 7) == 0 && (ldo & 3) == 0 && (sob & 3) == 0 &&
-                  (((uintptr_t)qkv_hi | (uintptr_t)qkv_lo | (uintptr_t)out | (uintptr_t)out_hi | (uintptr_t)out_lo) & 15) == 0,
+int hgl_launch_attention_planes(const HglAttn& d, HglAttnRoute route, hipStream_t st) {
+  const int S = d.Sq;
+  HGL_REQUIRE(d.qkv_hi && d.qkv_lo && (d.out || (d.out_hi && d.out_lo)) && d.B > 0 && d.H > 0 && S > 0, "attention_ps: bad arguments");
+  HGL_REQUIRE((d.ld & 7) == 0 && (d.qcol & 7) == 0 && (d.kcol & 7) == 0 && (d.vcol & 7) == 0 && (d.ldo & 3) == 0 && (d.sob & 3) == 0 &&
+                  (((uintptr_t)d.qkv_hi | (uintptr_t)d.qkv_lo | (uintptr_t)d.out | (uintptr_t)d.out_hi | (uintptr_t)d.out_lo) & 15) == 0,
               "attention_ps: operands must be 16-byte aligned");
-  HGL_REQUIRE(mask_kind != HGL_MASK_CLS_KEEP || keep, "attention_ps: HGL_MASK_CLS_KEEP needs keep bytes");
-  HGL_REQUIRE(vcol >= kcol, "attention_ps: the V columns must not lie before the K columns (32-bit offsets from the K base)");
-  HGL_REQUIRE((rel_h == nullptr) == (rel_w == nullptr) && (tab_h == nullptr) == (tab_w == nullptr), "attention_ps: rel-pos operands go in pairs");
+  HGL_REQUIRE(d.mask_kind != HGL_MASK_CLS_KEEP || d.keep, "attention_ps: HGL_MASK_CLS_KEEP needs keep bytes");
+  HGL_REQUIRE(d.vcol >= d.kcol, "attention_ps: the V columns must not lie before the K columns (32-bit offsets from the K base)");
+  HGL_REQUIRE((d.rel_h == nullptr) == (d.rel_w == nullptr) && (d.tab_h == nullptr) == (d.tab_w == nullptr), "attention_ps: rel-pos operands go in pairs");
   PsArgs a;
-  a.hi = (const _Float16*)qkv_hi; a.lo = (const _Float16*)qkv_lo;
-  a.ld = ld; a.qcol = qcol; a.kcol = kcol; a.vcol = vcol; a.sb = sb;
-  a.B = B; a.H = H; a.S = S;
-  a.out = out; a.out_hi = (_Float16*)out_hi; a.out_lo = (_Float16*)out_lo; a.ldo = ldo; a.sob = sob;
-  a.scale = scale; a.mask_kind = mask_kind; a.keep = keep; a.keep_b0 = keep_b0; a.keep_n = keep_n > 0 ? keep_n : B;
-  a.rel_h = rel_h; a.rel_w = rel_w; a.kh = kh; a.kw = kw;
+  a.hi = (const _Float16*)d.qkv_hi; a.lo = (const _Float16*)d.qkv_lo;
+  a.ld = d.ld; a.qcol = d.qcol; a.kcol = d.kcol; a.vcol = d.vcol; a.sb = d.sb;
+  a.B = d.B; a.H = d.H; a.S = S;
+  a.out = d.out; a.out_hi = (_Float16*)d.out_hi; a.out_lo = (_Float16*)d.out_lo; a.ldo = d.ldo; a.sob = d.sob;
+  a.scale = d.scale; a.mask_kind = d.mask_kind; a.keep = d.keep; a.keep_b0 = d.keep_b0; a.keep_n = d.keep_n > 0 ? d.keep_n : d.B;
+  a.rel_h = d.rel_h; a.rel_w = d.rel_w; a.kh = d.kh; a.kw = d.kw;
   a.tabh_hi = a.tabh_lo = a.tabw_hi = a.tabw_lo = nullptr;
   a.nqb = 1;
   a.dbg = HGL_DIAG_SWITCH("HGL_ATTN_PS_DBG", 0);
-  if (kind == PS_K_WIN) {
-    const void *hh = nullptr, *hl = nullptr, *wh = nullptr, *wl = nullptr;
-    int sh = 1, sw = 1, n1 = 0, k1 = 0, n2 = 0, k2 = 0;
-    (void)hgl_get_split_weight(tab_h, &hh, &hl, &sh, &n1, &k1);
-    (void)hgl_get_split_weight(tab_w, &wh, &wl, &sw, &n2, &k2);
-    a.tabh_hi = (const _Float16*)hh; a.tabh_lo = (const _Float16*)hl;
-    a.tabw_hi = (const _Float16*)wh; a.tabw_lo = (const _Float16*)wl;
+  if (route == HGL_ATTN_PS_WIN) {
+    const void* t[4];
+    (void)hgl_attention_rel_tables(d.tab_h, d.tab_w, t);
+    a.tabh_hi = (const _Float16*)t[0]; a.tabh_lo = (const _Float16*)t[1];
+    a.tabw_hi = (const _Float16*)t[2]; a.tabw_lo = (const _Float16*)t[3];
     a.nqb = 2;
-  } else if (kind != PS_K_CLIP) {
+  } else if (route != HGL_ATTN_PS_CLIP) {
     a.nqb = (S + 127) / 128;   // blocks of 128 queries (the CLS keep row of an item sits in 256 bytes of LDS)
   }
-  HglProfScope prof(HGL_PROF_ATTN, 4.0 * B * H * (double)S * S * hd, 0.0, st);
-  switch (kind) {
-    case PS_K_WIN: return psp_launch<80, PS_WIN14>(a, st);
-    case PS_K_RELT80: return psp_launch<80, PS_RELT>(a, st);
-    case PS_K_RELT64: return psp_launch<64, PS_RELT>(a, st);
-    case PS_K_PLAIN80: return psp_launch<80, PS_PLAIN>(a, st);
-    case PS_K_PLAIN64: return psp_launch<64, PS_PLAIN>(a, st);
-    default: return ps_launch<64, PS_PLAIN, 2>(a, st);     // PS_K_CLIP: the un-pipelined kernel, two query tiles per wave
+  HglProfScope prof(HGL_PROF_ATTN, 4.0 * d.B * d.H * (double)S * S * d.hd, 0.0, st);
+  switch (route) {
+    case HGL_ATTN_PS_WIN: return psp_launch<80, PS_WIN14>(a, st);
+    case HGL_ATTN_PS_RELT: return d.hd == 80 ? psp_launch<80, PS_RELT>(a, st) : psp_launch<64, PS_RELT>(a, st);
+    case HGL_ATTN_PS_PLAIN: return d.hd == 80 ? psp_launch<80, PS_PLAIN>(a, st) : psp_launch<64, PS_PLAIN>(a, st);
+    default: return ps_launch<64, PS_PLAIN, 2>(a, st);     // HGL_ATTN_PS_CLIP: the un-pipelined kernel, two query tiles per wave
   }
 }
 
@@ -1169,10 +1153,14 @@ extern "C" int hgl_attention_presplit_f32(const float* qkv, int ld, int B, int H
   uint16_t* hi = (uint16_t*)scratch;
   uint16_t* lo = hi + n;
   HGL_TRY(hgl_launch_split_f16(qkv, 1.0f, hi, lo, (long long)n, st));
+  HglAttn d = hgl_attn_packed_planes(hi, lo, B, H, S, hd);
+  d.ld = ld, d.scale = scale;
+  d.out = out, d.ldo = ldo, d.sob = (long long)S * ldo;
+  d.mask_kind = mask_kind, d.keep = keep, d.keep_b0 = keep_b0, d.keep_n = keep_n;
   const int prev = hgl_attention_presplit(1);
-  const int rc = hgl_launch_attention_ps(hi, lo, ld, 0, H * hd, 2 * H * hd, S, B, H, S, hd, out, nullptr, nullptr, ldo, (long long)S * ldo,
-                                         scale, mask_kind, keep, keep_b0, keep_n, nullptr, nullptr, 0, 0, nullptr, nullptr, st);
+  const bool served = hgl_attention_route(d) != HGL_ATTN_NONE;
+  const int rc = served ? hgl_launch_attention(d, st) : HGL_OK;
   hgl_attention_presplit(prev);
-  HGL_REQUIRE(rc <= 0, "attention_presplit: shape not served (B %d, H %d, S %d, hd %d, mask %d)", B, H, S, hd, mask_kind);
+  HGL_REQUIRE(served, "attention_presplit: shape not served (B %d, H %d, S %d, hd %d, mask %d)", B, H, S, hd, mask_kind);
   return rc;
 }

@@ -19,32 +19,56 @@ typedef HglBlockBufs BlockBufs;
 // tile per CU), but they cost a third of the small-tile kernel's CU-time, which is what matters for work that runs
 // on a side stream underneath the SAM / CLIP kernels (text encoder: 12 x 77 rows, GEM: 785 rows): measured
 // 49.05 -> 47.8 ms per benchmark step.
-bool hgl_clip_block_uses_x3(const HglResBlockW& w, int M, int D) {
+static bool block_uses_x3(const HglResBlockW& w, int M, int D) {
   static const int min_m = HGL_DIAG_SWITCH("HGL_X3_MIN_M", 512);
   return M > min_m && hgl_use_x3(w.in_proj_w, D) && hgl_use_x3(w.out_proj_w, D) && hgl_use_x3(w.fc_w, D) &&
          hgl_use_x3(w.proj_w, 4 * D) && (D % 256) == 0;
 }
 
-// the attention of a block runs on q | k | v as fp16 hi / lo planes (attention_ps.hip): head dim 64, no causal mask -- GEM's
-// 785-token blocks.  CLIP's 197-token sequences stay on attn_x3q_kernel: alone (1024 sequences) the pre-split kernel takes 742
-// against 868 us, but in the pipeline's launches (2048 sequences of a group) it is no faster (1771 against 1761 us) while the
+// the attention of a block on the split path, with q | k | v as fp16 hi | lo planes aliasing bf.QKV; its output is the fp16
+// hi | lo pair aliasing bf.H that the out-projection reads
+static HglAttn block_attn_planes(const HglBlockBufs& bf, int B, int S, int D, int heads) {
+  const uint16_t* Qh = (const uint16_t*)bf.QKV;
+  uint16_t* Hh = (uint16_t*)bf.H;
+  HglAttn d = hgl_attn_packed_planes(Qh, Qh + (size_t)B * S * 3 * D, B, heads, S, D / heads);
+  d.out_hi = Hh, d.out_lo = Hh + (size_t)B * S * D;
+  return d;
+}
+
+// planes: the attention of a block runs on q | k | v as fp16 hi / lo planes (attention_ps.hip): head dim 64, no causal mask --
+// GEM's 785-token blocks.  CLIP's 197-token sequences stay on attn_x3q_kernel: alone (1024 sequences) the pre-split kernel takes
+// 742 against 868 us, but in the pipeline's launches (2048 sequences of a group) it is no faster (1771 against 1761 us) while the
 // in-projection's split write-out costs 3 % of that GEMM (tools/clip_ps_ab.sh: 31.77 against 31.79 ms of kernel time per ref);
 // HGL_ATTN_PS_CLIPBLOCKS=2 routes them here as well (A/B timing, the parity test)
-bool hgl_clip_block_presplit(const HglResBlockW& w, int B, int S, int D, int heads, int mask_kind) {
-  const int hd = D / heads;
+HglClipBlockRoute hgl_clip_block_route(const HglResBlockW& w, const HglBlockBufs& bf, int B, int S, int D, int heads, int mask_kind,
+                                       HglClipBlockUse use) {
+  const int M = B * S, hd = D / heads;
   static const int on = hgl_env_int("HGL_ATTN_PS_CLIPBLOCKS", 1);   // 0: never, 2: also S <= 256
-  return on && (S > 256 || on == 2) && hgl_clip_block_uses_x3(w, B * S, D) && hd == 64 && S > 128 &&
-         hgl_attention_ps_serves((long long)B * S * 3 * D * 2, 3 * D, B, heads, S, hd, mask_kind, 0, 0, nullptr, nullptr) != 0;
+  HglClipBlockRoute r;
+  r.x3 = block_uses_x3(w, M, D);
+  r.planes = false;
+  if (r.x3 && use == HGL_BLOCK_WHOLE && on && (S > 256 || on == 2) && hd == 64 && S > 128) {
+    HglAttn d = block_attn_planes(bf, B, S, D, heads);
+    d.mask_kind = mask_kind;
+    r.planes = hgl_attention_route(d) != HGL_ATTN_NONE;
+  }
+  // mlp.c_proj with few output tiles and K = 4D (GEM at 785 rows, the text encoder, small batches): split-K over the
+  // idle CUs; the partial sums borrow the qkv buffer (dead after the attention; it holds three slices)
+  static const int splitk_on = HGL_DIAG_SWITCH("HGL_CLIP_SPLITK", 1);
+  r.ks = r.x3 && use != HGL_BLOCK_QKV_ONLY && splitk_on ? hgl_gemm_f16x3_splitk_factor(M, D, 4 * D) : 1;
+  if (r.ks > 3) r.ks = 3;
+  return r;
 }
 
 // first half of a block: H = ln_1(X) (fp32, or the fp16 hi+lo pair aliasing bf.H on the split path), QKV = H W_in + b
-// (split_out: q | k | v as fp16 hi / lo planes aliasing bf.QKV, for hgl_clip_block_rest(..., qkv_split = true))
-int hgl_clip_block_qkv(const HglResBlockW& w, const float* X, int M, int D, const HglBlockBufs& bf, hipStream_t st, bool split_out) {
-  if (hgl_clip_block_uses_x3(w, M, D)) {
+// (r.planes: q | k | v as fp16 hi / lo planes aliasing bf.QKV)
+int hgl_clip_block_qkv(const HglResBlockW& w, const HglClipBlockRoute& r, const float* X, int M, int D, const HglBlockBufs& bf,
+                       hipStream_t st) {
+  if (r.x3) {
     uint16_t* Hh = (uint16_t*)bf.H;
     uint16_t* Hl = Hh + (size_t)M * D;
     HGL_TRY(hgl_launch_layernorm_split(X, w.ln1_w, w.ln1_b, Hh, Hl, M, D, 1e-5f, st));
-    if (split_out) {
+    if (r.planes) {
       uint16_t* Qh = (uint16_t*)bf.QKV;
       return hgl_launch_gemm_f16x3(Hh, Hl, D, w.in_proj_w, w.in_proj_b, nullptr, 0, nullptr, Qh, Qh + (size_t)M * 3 * D, 3 * D, M,
                                    3 * D, D, HGL_ACT_NONE, st);
@@ -52,37 +76,26 @@ int hgl_clip_block_qkv(const HglResBlockW& w, const float* X, int M, int D, cons
     return hgl_launch_gemm_f16x3(Hh, Hl, D, w.in_proj_w, w.in_proj_b, nullptr, 0, bf.QKV, nullptr, nullptr, 3 * D, M, 3 * D, D,
                                  HGL_ACT_NONE, st);
   }
-  HGL_REQUIRE(!split_out, "clip_block_qkv: split output exists on the split-fp16 path only");
   HGL_TRY(hgl_launch_layernorm(X, w.ln1_w, w.ln1_b, bf.H, M, D, 1e-5f, st));
   return hgl_launch_gemm(bf.H, w.in_proj_w, w.in_proj_b, nullptr, bf.QKV, M, 3 * D, D, D, D, 0, 3 * D, 1, 0, 0, 0, 0,
                          HGL_ACT_NONE, st);
 }
 
 // second half: x <- x + out_proj(attention(QKV)) ; x <- x + mlp(ln_2 x)
-int hgl_clip_block_rest(const HglResBlockW& w, float* X, int B, int S, int D, int heads, const HglBlockBufs& bf,
-                        int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st, bool qkv_split) {
+int hgl_clip_block_rest(const HglResBlockW& w, const HglClipBlockRoute& r, float* X, int B, int S, int D, int heads,
+                        const HglBlockBufs& bf, int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st) {
   const int M = B * S;
-  const int hd = D / heads;
-  const long long sQKV = (long long)S * 3 * D;
-  if (hgl_clip_block_uses_x3(w, M, D)) {
+  HglAttn at = r.planes ? block_attn_planes(bf, B, S, D, heads) : hgl_attn_packed(bf.QKV, B, heads, S, D / heads);
+  at.mask_kind = mask_kind, at.keep = keep, at.keep_b0 = keep_b0, at.keep_n = keep_n;
+  if (r.x3) {
     // activations feeding a GEMM alias the fp32 scratch buffers (same byte size)
     uint16_t* Hh = (uint16_t*)bf.H;
     uint16_t* Hl = Hh + (size_t)M * D;
     uint16_t* Fh = (uint16_t*)bf.F;
     uint16_t* Fl = Fh + (size_t)M * 4 * D;
     // the attention writes its output as the fp16 hi+lo pair the out-projection reads
-    if (qkv_split) {
-      const uint16_t* Qh = (const uint16_t*)bf.QKV;
-      const int rc = hgl_launch_attention_ps(Qh, Qh + (size_t)M * 3 * D, 3 * D, 0, D, 2 * D, S, B, heads, S, hd, nullptr, Hh, Hl, D,
-                                             (long long)S * D, 1.0f / sqrtf((float)hd), mask_kind, keep, keep_b0, keep_n, nullptr,
-                                             nullptr, 0, 0, nullptr, nullptr, st);
-      if (rc < 0) return rc;
-      HGL_REQUIRE(rc == 0, "clip_block: the pre-split attention refused a shape its caller had checked");
-    } else {
-    HGL_TRY(hgl_launch_attention_split(bf.QKV, bf.QKV + D, bf.QKV + 2 * D, nullptr, Hh, Hl, B, heads, S, S, hd, 3 * D, 3 * D,
-                                       3 * D, D, sQKV, sQKV, sQKV, (long long)S * D, 1.0f / sqrtf((float)hd), mask_kind, keep,
-                                       keep_b0, keep_n, nullptr, nullptr, 0, 0, st));
-    }
+    at.out_hi = Hh, at.out_lo = Hl;
+    HGL_TRY(hgl_launch_attention(at, st));
     // (balanced: whole rounds of the persistent tiling + a split-K tail when the last round would be mostly empty; the
     // partial sums borrow the qkv buffer, dead after the attention)
     HGL_TRY(hgl_launch_gemm_f16x3_balanced(Hh, Hl, D, nullptr, w.out_proj_w, w.out_proj_b, X, D, nullptr, X, D, M, D, D, HGL_ACT_NONE,
@@ -90,24 +103,17 @@ int hgl_clip_block_rest(const HglResBlockW& w, float* X, int B, int S, int D, in
     HGL_TRY(hgl_launch_layernorm_split(X, w.ln2_w, w.ln2_b, Hh, Hl, M, D, 1e-5f, st));
     HGL_TRY(hgl_launch_gemm_f16x3(Hh, Hl, D, w.fc_w, w.fc_b, nullptr, 0, nullptr, Fh, Fl, 4 * D, M, 4 * D, D,
                                   HGL_ACT_QUICKGELU, st));
-    // mlp.c_proj with few output tiles and K = 4D (GEM at 785 rows, the text encoder, small batches): split-K over the
-    // idle CUs; the partial sums borrow the qkv buffer (dead after the attention; it holds three slices)
-    static const int splitk_on = HGL_DIAG_SWITCH("HGL_CLIP_SPLITK", 1);
-    int ks = splitk_on ? hgl_gemm_f16x3_splitk_factor(M, D, 4 * D) : 1;
-    if (ks > 3) ks = 3;
-    if (ks > 1) {
+    if (r.ks > 1) {
       HGL_TRY(hgl_launch_gemm_f16x3_splitk(Fh, Fl, 4 * D, nullptr, w.proj_w, w.proj_b, X, D, nullptr, X, D, M, D, 4 * D,
-                                           HGL_ACT_NONE, ks, bf.QKV, (size_t)M * 3 * D * sizeof(float), st));
+                                           HGL_ACT_NONE, r.ks, bf.QKV, (size_t)M * 3 * D * sizeof(float), st));
     } else {
       HGL_TRY(hgl_launch_gemm_f16x3_balanced(Fh, Fl, 4 * D, nullptr, w.proj_w, w.proj_b, X, D, nullptr, X, D, M, D, 4 * D, HGL_ACT_NONE,
                                              bf.QKV, (size_t)M * 3 * D * sizeof(float), st));
     }
     return HGL_OK;
   }
-  HGL_REQUIRE(!qkv_split, "clip_block_rest: split qkv exists on the split-fp16 path only");
-  HGL_TRY(hgl_launch_attention(bf.QKV, bf.QKV + D, bf.QKV + 2 * D, bf.H, B, heads, S, S, hd, 3 * D,
-                               3 * D, 3 * D, D, sQKV, sQKV, sQKV, (long long)S * D, 1.0f / sqrtf((float)hd),
-                               mask_kind, keep, keep_b0, keep_n, nullptr, nullptr, 0, 0, st));
+  at.out = bf.H;
+  HGL_TRY(hgl_launch_attention(at, st));
   HGL_TRY(hgl_launch_gemm(bf.H, w.out_proj_w, w.out_proj_b, X, X, M, D, D, D, D, D, D, 1, 0, 0, 0, 0,
                           HGL_ACT_NONE, st));
   HGL_TRY(hgl_launch_layernorm(X, w.ln2_w, w.ln2_b, bf.H, M, D, 1e-5f, st));
@@ -121,9 +127,9 @@ int hgl_clip_block_rest(const HglResBlockW& w, float* X, int B, int S, int D, in
 // x <- x + attn(ln_1 x) ; x <- x + mlp(ln_2 x)      (clip/model.py:244-257)
 int hgl_clip_run_block(const HglResBlockW& w, float* X, int B, int S, int D, int heads, const HglBlockBufs& bf,
                        int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st) {
-  const bool ps = hgl_clip_block_presplit(w, B, S, D, heads, mask_kind);
-  HGL_TRY(hgl_clip_block_qkv(w, X, B * S, D, bf, st, ps));
-  return hgl_clip_block_rest(w, X, B, S, D, heads, bf, mask_kind, keep, keep_b0, keep_n, st, ps);
+  const HglClipBlockRoute r = hgl_clip_block_route(w, bf, B, S, D, heads, mask_kind, HGL_BLOCK_WHOLE);
+  HGL_TRY(hgl_clip_block_qkv(w, r, X, B * S, D, bf, st));
+  return hgl_clip_block_rest(w, r, X, B, S, D, heads, bf, mask_kind, keep, keep_b0, keep_n, st);
 }
 
 // patch embedding + cls + pos + ln_pre for `n_img` images -> X [n_img, S, D]; cols holds the im2col matrix
@@ -149,11 +155,6 @@ int hgl_clip_embed_images(const HglClipVisionW* w, const float* imgs, int n_img,
 }
 
 namespace {
-
-inline int run_block(const HglResBlockW& w, float* X, int B, int S, int D, int heads, const BlockBufs& bf,
-                     int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st) {
-  return hgl_clip_run_block(w, X, B, S, D, heads, bf, mask_kind, keep, keep_b0, keep_n, st);
-}
 
 int n_streams(int mode) {
   switch (mode) {
@@ -199,15 +200,16 @@ int embed_images(const HglClipVisionW* w, const float* imgs, int n_img, float* X
 // sequence.  2.2 of the block's 2.9 GFLOP per sequence are dead rows.  Leaves the CLS rows [B, D] in p.cls_rows.
 int run_block_cls(const HglResBlockW& w, const float* X, int B, int S, int D, int heads, const BlockBufs& bf, int mask_kind,
                   const uint8_t* keep, int keep_b0, int keep_n, const ClipPlan& p, hipStream_t st) {
-  const int M = B * S, hd = D / heads;
-  const long long sQKV = (long long)S * 3 * D;
-  HGL_TRY(hgl_clip_block_qkv(w, X, M, D, bf, st));
+  const int M = B * S;
+  const HglClipBlockRoute r = hgl_clip_block_route(w, bf, B, S, D, heads, mask_kind, HGL_BLOCK_QKV_ONLY);
+  HGL_TRY(hgl_clip_block_qkv(w, r, X, M, D, bf, st));
   float* att = bf.H;            // [B, D]: the ln_1 output is dead after the qkv projection
   float* xcls = p.cls_rows;     // [B, D]
   float* h = p.cls_ln;          // [B, D]
-  HGL_TRY(hgl_launch_attention(bf.QKV, bf.QKV + D, bf.QKV + 2 * D, att, B, heads, 1, S, hd, 3 * D, 3 * D, 3 * D, D, sQKV, sQKV,
-                               sQKV, (long long)D, 1.0f / sqrtf((float)hd), mask_kind, keep, keep_b0, keep_n, nullptr, nullptr,
-                               0, 0, st));
+  HglAttn at = hgl_attn_packed(bf.QKV, B, heads, S, D / heads);
+  at.Sq = 1, at.out = att, at.sob = D;   // one query per sequence
+  at.mask_kind = mask_kind, at.keep = keep, at.keep_b0 = keep_b0, at.keep_n = keep_n;
+  HGL_TRY(hgl_launch_attention(at, st));
   HGL_TRY(hgl_launch_gather_rows(X, (long long)S * D, B, D, xcls, st));
   HGL_TRY(hgl_launch_gemm(att, w.out_proj_w, w.out_proj_b, xcls, xcls, B, D, D, D, D, D, D, 1, 0, 0, 0, 0, HGL_ACT_NONE, st));
   HGL_TRY(hgl_launch_layernorm(xcls, w.ln2_w, w.ln2_b, h, B, D, 1e-5f, st));
@@ -306,14 +308,14 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
 
   if (fusion_mode == HGL_FUSION_CROP) {
     for (int l = 0; l + 1 < w->layers; ++l)
-      HGL_TRY(run_block(w->blocks[l], p.X, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st));
+      HGL_TRY(hgl_clip_run_block(w->blocks[l], p.X, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st));
     HGL_TRY(run_block_cls(w->blocks[w->layers - 1], p.X, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, p, st));
     return head_rows(w, N, out, nullptr, p, st);
   }
 
   const int nb0 = two_stream ? 2 * N : N;
   for (int l = 0; l < masking_block; ++l)
-    HGL_TRY(run_block(w->blocks[l], p.X, nb0, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st));
+    HGL_TRY(hgl_clip_run_block(w->blocks[l], p.X, nb0, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st));
 
   float* X = p.X;
   float* Y = p.Y;
@@ -322,14 +324,14 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
       for (int l = masking_block; l <= ret_block; ++l) {
         // x = cat(cls, x*pm)  (model/backbone.py:163-176)
         HGL_TRY(hgl_launch_mix(X, nullptr, 0.f, X, 1.f, p.pm, N, S, D, st));
-        if (l < ret_block) HGL_TRY(run_block(w->blocks[l], X, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st));
+        if (l < ret_block) HGL_TRY(hgl_clip_run_block(w->blocks[l], X, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st));
         else HGL_TRY(run_block_cls(w->blocks[l], X, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, p, st));
       }
       return head_rows(w, N, out, nullptr, p, st);
     }
     case HGL_FUSION_ATTN_MASKING: {
       for (int l = masking_block; l < ret_block; ++l)
-        HGL_TRY(run_block(w->blocks[l], X, N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, 0, N, st));
+        HGL_TRY(hgl_clip_run_block(w->blocks[l], X, N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, 0, N, st));
       HGL_TRY(run_block_cls(w->blocks[ret_block], X, N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, 0, N, p, st));
       return head_rows(w, N, out, nullptr, p, st);
     }
@@ -339,7 +341,7 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
         HGL_TRY(hgl_launch_mix(Y, X, 1.f, X + sN, 2.f, p.pm, N, S, D, st));
         if (l < ret_block) {
           (void)hipMemcpyAsync(Y + sN, X + sN, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
-          HGL_TRY(run_block(w->blocks[l], Y, 2 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, N, N, st));
+          HGL_TRY(hgl_clip_run_block(w->blocks[l], Y, 2 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, N, N, st));
         } else {  // the global stream of the returning block is dead, and so are the non-CLS rows of the local one
           HGL_TRY(run_block_cls(w->blocks[l], Y, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, p, st));
         }
@@ -353,7 +355,7 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
         HGL_TRY(hgl_launch_mix(Y + sN, X, 1.f, X + sN, 2.f, nullptr, N, S, D, st));
         if (l < ret_block) {
           (void)hipMemcpyAsync(Y, X, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
-          HGL_TRY(run_block(w->blocks[l], Y, 2 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, N, N, st));
+          HGL_TRY(hgl_clip_run_block(w->blocks[l], Y, 2 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, N, N, st));
         } else {  // the local stream of the returning block is dead, and so are the non-CLS rows of the global one
           HGL_TRY(run_block_cls(w->blocks[l], Y + sN, N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, 0, N, p, st));
         }
@@ -374,7 +376,7 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
         if (l < ret_block) {
           (void)hipMemcpyAsync(Y, X, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
           (void)hipMemcpyAsync(Y + 2 * sN, X + 2 * sN, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
-          HGL_TRY(run_block(w->blocks[l], Y, 4 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, 2 * N, N, st));
+          HGL_TRY(hgl_clip_run_block(w->blocks[l], Y, 4 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, 2 * N, N, st));
         } else {  // plain xl / xg streams of the returning block are dead; of hl / hg only the CLS rows are consumed
           HGL_TRY(run_block_cls(w->blocks[l], Y + sN, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, p, st));
           HGL_TRY(head_rows(w, N, out, nullptr, p, st));
@@ -468,7 +470,7 @@ int hgl_clip_encode_text_ex(const HglClipTextW* w, const int32_t* tokens, int B,
   BlockBufs bf{p.H, p.QKV, p.F};
   for (int l = 0; l < w->layers; ++l) {
     if (n_zero > 0 && l >= masking_block) HGL_TRY(hgl_launch_zero_positions(p.X, B, S, D, zero_pos, n_zero, st));   // backbone.py:44-46
-    HGL_TRY(run_block(w->blocks[l], p.X, B, S, D, w->heads, bf, HGL_MASK_CAUSAL, nullptr, 0, 0, st));
+    HGL_TRY(hgl_clip_run_block(w->blocks[l], p.X, B, S, D, w->heads, bf, HGL_MASK_CAUSAL, nullptr, 0, 0, st));
   }
   // ln_final is row-wise: normalise only the pooled rows, then project (clip/model.py:424-429)
   HGL_TRY(hgl_launch_gather_eot(p.X, p.eot, B, S, D, p.rows, st));

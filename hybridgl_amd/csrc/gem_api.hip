@@ -307,8 +307,10 @@ int gem_block(const HglResBlockW& w, const GemPlan& p, int S, int D, int heads, 
   const float scale = 1.0f / sqrtf((float)hd);
   const long long SD = (long long)S * D, MD = (long long)M * D;
   const HglBlockBufs bf{p.H, p.QKV, p.F};
-  const bool x3 = hgl_clip_block_uses_x3(w, M, D);
-  HGL_TRY(hgl_clip_block_qkv(w, p.X, M, D, bf, st));          // p.H = ln_1(x) (fp32 or the hi+lo pair), p.QKV
+  // (the self-self attention below reads q | k | v as fp32)
+  const HglClipBlockRoute r = hgl_clip_block_route(w, bf, nb, S, D, heads, HGL_MASK_NONE, need_ori ? HGL_BLOCK_FP32_QKV : HGL_BLOCK_QKV_ONLY);
+  const bool x3 = r.x3;
+  HGL_TRY(hgl_clip_block_qkv(w, r, p.X, M, D, bf, st));       // p.H = ln_1(x) (fp32 or the hi+lo pair), p.QKV
   if (ss_temp > 0.f) {
     hipLaunchKernelGGL(set_scalar_kernel, dim3(1), dim3(64), 0, st, p.t, ss_temp, nb);
   } else {
@@ -323,20 +325,28 @@ int gem_block(const HglResBlockW& w, const GemPlan& p, int S, int D, int heads, 
   // sets in the order (v, k, q): QKV + 2D, + D, + 0.  Attention batches = (set, image): 3 * nb sequences of S tokens.
   const float* V = p.QKV + 2 * D;
   HGL_TRY(normalize_heads(V, -(long long)D, 3 * D, M, S, heads, hd, p, st));
+  // q = the normalised rows times the temperature (N3s), k = the normalised rows (N3): [3 * nb, S, D], scale 1
+  HglAttn at;
+  at.B = 3 * nb, at.H = heads, at.Sq = S, at.Sk = S, at.hd = hd, at.scale = 1.0f;
+  at.q = p.N3s, at.k = p.N3, at.v = p.N3, at.out = p.X1;
+  at.ldq = at.ldk = at.ldv = at.ldo = D;
+  at.sqb = at.skb = at.svb = at.sob = SD;
   for (int it = 0; it < ss_iter; ++it) {
-    HGL_TRY(hgl_launch_attention(p.N3s, p.N3, p.N3, p.X1, 3 * nb, heads, S, S, hd, D, D, D, D, SD, SD, SD, SD, 1.0f,
-                                 HGL_MASK_NONE, nullptr, 0, 0, nullptr, nullptr, 0, 0, st));
+    HGL_TRY(hgl_launch_attention(at, st));
     HGL_TRY(normalize_heads(p.X1, MD, D, M, S, heads, hd, p, st));
   }
   // assignment to v: the value operand is the block's v for all three sets -- one launch when a batch stride of 0
   // expresses that (one image), else one launch per set over the images
+  at.v = V, at.ldv = 3 * D;
   if (nb == 1) {
-    HGL_TRY(hgl_launch_attention(p.N3s, p.N3, V, p.X1, 3, heads, S, S, hd, D, D, 3 * D, D, SD, SD, 0, SD, 1.0f, HGL_MASK_NONE,
-                                 nullptr, 0, 0, nullptr, nullptr, 0, 0, st));
+    at.svb = 0;
+    HGL_TRY(hgl_launch_attention(at, st));
   } else {
-    for (int set = 0; set < 3; ++set)
-      HGL_TRY(hgl_launch_attention(p.N3s + set * MD, p.N3 + set * MD, V, p.X1 + set * MD, nb, heads, S, S, hd, D, D, 3 * D, D,
-                                   SD, SD, 3 * SD, SD, 1.0f, HGL_MASK_NONE, nullptr, 0, 0, nullptr, nullptr, 0, 0, st));
+    at.B = nb, at.svb = 3 * SD;
+    for (int set = 0; set < 3; ++set) {
+      at.q = p.N3s + set * MD, at.k = p.N3 + set * MD, at.out = p.X1 + set * MD;
+      HGL_TRY(hgl_launch_attention(at, st));
+    }
   }
   if (x3) {
     _Float16* Mh = (_Float16*)p.N3;
@@ -353,7 +363,7 @@ int gem_block(const HglResBlockW& w, const GemPlan& p, int S, int D, int heads, 
   }
   if (!need_ori) return HGL_OK;
   // original stream (clip/model.py:244-257): the plain block on the same QKV
-  return hgl_clip_block_rest(w, p.X, nb, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st);
+  return hgl_clip_block_rest(w, r, p.X, nb, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st);
 }
 
 bool valid_vision(const HglClipVisionW* w) {

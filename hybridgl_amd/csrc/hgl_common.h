@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <math.h>
 #include <atomic>
 #include "../../include/hybridgl.h"
 
@@ -170,36 +171,92 @@ int hgl_launch_gemm(const float* A, const float* W, const float* bias, const flo
                     hipStream_t st);
 int hgl_launch_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D,
                          float eps, hipStream_t st);
-int hgl_launch_attention_split(const float* q, const float* k, const float* v, float* out, void* out_hi, void* out_lo, int B,
-                               int H, int Sq, int Sk, int hd, int ldq, int ldk, int ldv, int ldo, long long sqb,
-                               long long skb, long long svb, long long sob, float scale, int mask_kind,
-                               const uint8_t* keep, int keep_b0, int keep_n, const float* rel_h,
-                               const float* rel_w, int kh, int kw, hipStream_t st);
-int hgl_launch_attention_win14(const float* q, const float* k, const float* v, void* out_hi, void* out_lo, int B, int H, int hd,
-                               int ldq, int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb, long long sob,
-                               float scale, const float* Rh, const float* Rw, hipStream_t st);
-// attention on the split qkv planes the in-projection GEMM emits (attention_ps.hip); returns 1 when the shape is not served
-bool hgl_attention_ps_enabled();
-// would hgl_launch_attention_ps serve this call (0 = no)?  For callers that choose the in-projection's output form first
-int hgl_attention_ps_serves(long long plane_delta, int ld, int B, int H, int S, int hd, int mask_kind, int rel_kh, int rel_kw,
-                            const float* tab_h, const float* tab_w);
-int hgl_launch_attention_ps(const void* qkv_hi, const void* qkv_lo, int ld, int qcol, int kcol, int vcol, long long sb, int B,
-                            int H, int S, int hd, float* out, void* out_hi, void* out_lo, int ldo, long long sob, float scale,
-                            int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, const float* rel_h, const float* rel_w,
-                            int kh, int kw, const float* tab_h, const float* tab_w, hipStream_t st);
-int hgl_launch_attention_smallk(const float* q, const float* k, const float* v, float* out, void* out_hi, void* out_lo,
-                                int B, int H, int Sq, int Sk, int hd, int ldq, int ldk, int ldv, int ldo, long long sqb,
-                                long long skb, long long svb, long long sob, float scale, hipStream_t st);
+// ---- attention: one call descriptor, one route, one launch (attention.hip; the plane-form kernels live in attention_ps.hip) ----
+// A caller says WHAT attention it wants in named fields; hgl_attention_route says WHICH kernel family serves it.
+struct HglAttn {
+  int B = 0, H = 0, Sq = 0, Sk = 0, hd = 0;
+  float scale = 1.0f;
+  // operands, one of two forms.  fp32 q / k / v: rows of ldq / ldk / ldv floats, batch strides sqb / skb / svb ...
+  const float *q = nullptr, *k = nullptr, *v = nullptr;
+  int ldq = 0, ldk = 0, ldv = 0;
+  long long sqb = 0, skb = 0, svb = 0;
+  // ... or the fp16 hi | lo planes of a packed qkv (Sq == Sk): row (b * sb + s), columns qcol / kcol / vcol + head * hd, rows of
+  // ld halfs
+  const void *qkv_hi = nullptr, *qkv_lo = nullptr;
+  int ld = 0, qcol = 0, kcol = 0, vcol = 0;
+  long long sb = 0;
+  // output: fp32 `out`, or (out == nullptr, split-fp16 modes) the fp16 hi | lo pair; rows of ldo, batch stride sob
+  float* out = nullptr;
+  void *out_hi = nullptr, *out_lo = nullptr;
+  int ldo = 0;
+  long long sob = 0;
+  int mask_kind = HGL_MASK_NONE;
+  const uint8_t* keep = nullptr;    // HGL_MASK_CLS_KEEP: keep bytes of batches keep_b0 .. keep_b0 + keep_n (keep_n 0: all B)
+  int keep_b0 = 0, keep_n = 0;
+  // decomposed rel-pos bias: the terms as tensors [B*H, Sq, kh] / [B*H, Sq, kw] ...
+  const float *rel_h = nullptr, *rel_w = nullptr;
+  int kh = 0, kw = 0;
+  // ... or the windowed blocks' tables [27, 80] (14 x 14 windows at head dim 80: the kernel computes the terms itself)
+  const float *tab_h = nullptr, *tab_w = nullptr;
+  // part != nullptr: the chunked few-query form (the decoder's token -> image attention).  part: scratch of at least
+  // hgl_attention_fewq_part_bytes(B, Sk) bytes; kv_group > 1: batches b of one group share the keys / values of set b / kv_group
+  float* part = nullptr;
+  size_t part_bytes = 0;
+  int kv_group = 1;
+};
+// the packed [B, S, 3D] qkv of a transformer block (q | k | v at columns 0, D, 2D; D = H * hd) as fp32, scale 1 / sqrt(hd),
+// output rows of D floats.  The caller names the output (out, or out_hi / out_lo) and what else differs.
+inline HglAttn hgl_attn_packed(const float* qkv, int B, int H, int S, int hd) {
+  const int D = H * hd;
+  HglAttn d;
+  d.B = B, d.H = H, d.Sq = S, d.Sk = S, d.hd = hd, d.scale = 1.0f / sqrtf((float)hd);
+  d.q = qkv, d.k = qkv + D, d.v = qkv + 2 * D;
+  d.ldq = d.ldk = d.ldv = 3 * D;
+  d.sqb = d.skb = d.svb = (long long)S * 3 * D;
+  d.ldo = D, d.sob = (long long)S * D;
+  return d;
+}
+// the same tensor as the fp16 hi | lo planes the in-projection's write-out emits
+inline HglAttn hgl_attn_packed_planes(const void* hi, const void* lo, int B, int H, int S, int hd) {
+  const int D = H * hd;
+  HglAttn d;
+  d.B = B, d.H = H, d.Sq = S, d.Sk = S, d.hd = hd, d.scale = 1.0f / sqrtf((float)hd);
+  d.qkv_hi = hi, d.qkv_lo = lo;
+  d.ld = 3 * D, d.qcol = 0, d.kcol = D, d.vcol = 2 * D, d.sb = S;
+  d.ldo = D, d.sob = (long long)S * D;
+  return d;
+}
+// The kernel family that serves a descriptor.  A pure function of the descriptor, the precision state (hgl_split_layout(),
+// hgl_split_terms()), the split-weight registry (the windowed tables) and the switches; it enqueues nothing and sets no error.
+enum HglAttnRoute {
+  HGL_ATTN_NONE = 0,       // no kernel serves the descriptor
+  // fp32 q / k / v (attention.hip)
+  HGL_ATTN_FEWQ_CHUNKED,   // `part` given: 8 heads of 16, up to 7 queries, keys in chunks of 256
+  HGL_ATTN_WIN14,          // tables given: 14 x 14 windows at head dim 80, the rel-pos terms computed in the kernel
+  HGL_ATTN_FEWQ,           // head dim 16, up to 8 queries over >= 1024 keys
+  HGL_ATTN_SMALLK,         // head dim 16, up to 8 keys
+  HGL_ATTN_F32,            // fp32 mode: the fp32 tile kernel
+  HGL_ATTN_PINGPONG,       // long unmasked sequences: one 8-wave workgroup per 256 queries
+  HGL_ATTN_REL14,          // head dim 80, 14 x 14 rel-pos terms as tensors
+  HGL_ATTN_DUAL,           // head dim 64, 129..256 queries: one 4-wave workgroup per item, two query tiles per wave
+  HGL_ATTN_WIDE,           // 129..256 queries: one 8-wave workgroup per item
+  HGL_ATTN_TILE,           // one 4-wave workgroup per 128 queries
+  // q | k | v as fp16 hi | lo planes (attention_ps.hip)
+  HGL_ATTN_PS_WIN,         // 14 x 14 windows at head dim 80, the registered tables
+  HGL_ATTN_PS_RELT,        // rel-pos terms as tensors
+  HGL_ATTN_PS_CLIP,        // head dim 64, 129..256 tokens: the un-pipelined kernel, two query tiles per wave
+  HGL_ATTN_PS_PLAIN        // the pipelined persistent kernel
+};
+HglAttnRoute hgl_attention_route(const HglAttn& d);
+// validates (the requirements of the family the route chose) and launches; "no kernel serves the descriptor" is an error
+int hgl_launch_attention(const HglAttn& d, hipStream_t st);
 size_t hgl_attention_fewq_part_bytes(int B, int Sk);
-int hgl_launch_attention_fewq_chunked(const float* q, const float* k, const float* v, float* out, int B, int H, int Sq, int Sk,
-                                      int hd, int ldq, int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb,
-                                      long long sob, float scale, float* part, size_t part_bytes, hipStream_t st,
-                                      int kv_group = 1);   // > 1: batches b of one group share the keys / values of set b / kv_group
-int hgl_launch_attention(const float* q, const float* k, const float* v, float* out, int B, int H,
-                         int Sq, int Sk, int hd, int ldq, int ldk, int ldv, int ldo, long long sqb,
-                         long long skb, long long svb, long long sob, float scale, int mask_kind,
-                         const uint8_t* keep, int keep_b0, int keep_n, const float* rel_h,
-                         const float* rel_w, int kh, int kw, hipStream_t st);
+// between attention.hip and attention_ps.hip only: the plane-form half of the route and of the launch, and the ONE lookup of the
+// windowed blocks' tables in the split-weight registry (both [27, 80], registered at scale 2^0: the halves the kernels' own
+// split gives, bit for bit; t = h hi, h lo, w hi, w lo)
+bool hgl_attention_rel_tables(const float* tab_h, const float* tab_w, const void* t[4]);
+HglAttnRoute hgl_attention_route_planes(const HglAttn& d);
+int hgl_launch_attention_planes(const HglAttn& d, HglAttnRoute route, hipStream_t st);
 
 // CLIP glue (clip_glue.hip)
 int hgl_launch_im2col_patch(const float* img, int N, int res, int patch, float* cols, hipStream_t st);
@@ -226,14 +283,24 @@ struct HglBlockBufs {
   float* QKV;  // [M, 3D]
   float* F;    // [M, 4D]
 };
+// Everything that is decided about the launches of one residual block, once per block call
+struct HglClipBlockRoute {
+  bool x3;       // the split-fp16 path: every GEMM operand activation exists only as fp16 hi | lo planes
+  bool planes;   // the in-projection writes q | k | v as planes and the attention runs on them (attention_ps.hip)
+  int ks;        // split-K factor of mlp.c_proj (1: the row-balanced launch)
+};
+// what the caller runs of the block: all of it (planes where the route serves them); all of it, reading q | k | v as fp32
+// after the in-projection (GEM's self-self attention: no planes); or the in-projection alone (the CLS-row block, GEM without
+// its original stream: no planes, and mlp.c_proj is not the block's: ks stays 1)
+enum HglClipBlockUse { HGL_BLOCK_WHOLE, HGL_BLOCK_FP32_QKV, HGL_BLOCK_QKV_ONLY };
+HglClipBlockRoute hgl_clip_block_route(const HglResBlockW& w, const HglBlockBufs& bf, int B, int S, int D, int heads, int mask_kind,
+                                       HglClipBlockUse use);
 int hgl_clip_run_block(const HglResBlockW& w, float* X, int B, int S, int D, int heads, const HglBlockBufs& bf,
                        int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st);
-bool hgl_clip_block_uses_x3(const HglResBlockW& w, int M, int D);
-bool hgl_clip_block_presplit(const HglResBlockW& w, int B, int S, int D, int heads, int mask_kind);
-int hgl_clip_block_qkv(const HglResBlockW& w, const float* X, int M, int D, const HglBlockBufs& bf, hipStream_t st,
-                       bool split_out = false);
-int hgl_clip_block_rest(const HglResBlockW& w, float* X, int B, int S, int D, int heads, const HglBlockBufs& bf,
-                        int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st, bool qkv_split = false);
+int hgl_clip_block_qkv(const HglResBlockW& w, const HglClipBlockRoute& r, const float* X, int M, int D, const HglBlockBufs& bf,
+                       hipStream_t st);
+int hgl_clip_block_rest(const HglResBlockW& w, const HglClipBlockRoute& r, float* X, int B, int S, int D, int heads,
+                        const HglBlockBufs& bf, int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st);
 int hgl_clip_embed_images(const HglClipVisionW* w, const float* imgs, int n_img, float* X, float* cols, float* tok,
                           hipStream_t st);
 

@@ -90,7 +90,31 @@ struct EncBlockRoute {
   bool planes;          // the in-projection writes q | k | v as fp16 hi / lo planes (same bytes as the fp32 tensor)
 };
 
-int enc_block_route(const HglSamEncoderW* w, const HglSamBlockW& b, int nb, EncBlockRoute& r) {
+// the fp16 hi | lo planes of the split path: each pair aliases an fp32 buffer of the plan (same bytes)
+struct EncPlanes {
+  uint16_t *Ah, *Al;    // GEMM input in window order, later the attention's output (the window buffer)
+  uint16_t *Hh, *Hl;    // norm2 (H)
+  uint16_t *Fh, *Fl;    // mlp.lin1 (F)
+  uint16_t *Qh, *Ql;    // split qkv (QKV)
+  EncPlanes(const EncPlan& p, const EncBlockRoute& r)
+      : Ah((uint16_t*)p.Hw), Al(Ah + (size_t)r.M * r.D), Hh((uint16_t*)p.H), Hl(Hh + (size_t)r.T * r.D), Fh((uint16_t*)p.F),
+        Fl(Fh + (size_t)r.T * 4 * r.D), Qh((uint16_t*)p.QKV), Ql(Qh + (size_t)r.M * 3 * r.D) {}
+};
+
+// the attention of the B windows (or whole grids) as `kind` runs it: on p.QKV as planes or as fp32 -> the planes Ah | Al (x3) or
+// p.O (fp32); the rel-pos terms from the block's tables or as the tensors p.relh / p.relw that enc_attention computes first
+HglAttn enc_attn(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, EncAttn kind) {
+  const EncPlanes s(p, r);
+  const bool planes = kind == ENC_ATTN_PS_WIN || kind == ENC_ATTN_PS_GLOBAL;
+  HglAttn d = planes ? hgl_attn_packed_planes(s.Qh, s.Ql, r.B, r.heads, r.S, r.hd) : hgl_attn_packed(p.QKV, r.B, r.heads, r.S, r.hd);
+  d.out = r.x3 ? nullptr : p.O, d.out_hi = s.Ah, d.out_lo = s.Al;
+  if (kind == ENC_ATTN_PS_WIN || kind == ENC_ATTN_WIN14) d.tab_h = b.rel_pos_h, d.tab_w = b.rel_pos_w;
+  else d.rel_h = p.relh, d.rel_w = p.relw, d.kh = d.kw = r.size;
+  return d;
+}
+
+int enc_block_route(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPlan& p, EncBlockRoute& r) {
+  const int nb = p.nb;
   r.D = w->embed_dim, r.g = w->img_size / w->patch, r.heads = w->heads, r.hd = r.D / r.heads;
   r.T1 = r.g * r.g, r.T = nb * r.T1;
   r.ws = b.window, r.size = r.ws > 0 ? r.ws : r.g, r.nw = r.ws > 0 ? (r.g + r.ws - 1) / r.ws : 1;
@@ -105,68 +129,38 @@ int enc_block_route(const HglSamEncoderW* w, const HglSamBlockW& b, int nb, EncB
   // only the real tokens go through the windowed GEMMs (16 % fewer rows at 64x64 / 14x14)
   r.gather = r.x3 && r.ws > 0 && r.M > r.T && padskip;
   static const int ps_glob_on = HGL_DIAG_SWITCH("HGL_ATTN_PS_GLOBAL", 1);   // 0: the global blocks keep the fp32-input kernels (A/B timing)
-  // both pre-split decisions are hgl_attention_ps_serves' (the predicate the launch itself applies: plane distance + one item's
-  // rows within 32 bits, shapes, registered tables), taken here because the in-projection writes split planes only
-  const long long plane_delta = (long long)r.M * 3 * D * 2;
-  const bool ps_glob = r.x3 && r.ws == 0 && r.size == 64 && ps_glob_on &&
-                       hgl_attention_ps_serves(plane_delta, 3 * D, r.B, r.heads, r.S, r.hd, HGL_MASK_NONE, r.size, r.size, nullptr, nullptr) != 0;
-  const bool ps_win = r.x3 && r.ws == 14 &&
-                      hgl_attention_ps_serves(plane_delta, 3 * D, r.B, r.heads, r.S, r.hd, HGL_MASK_NONE, 0, 0, b.rel_pos_h, b.rel_pos_w) != 0;
-  r.attn = ps_win ? ENC_ATTN_PS_WIN : ps_glob ? ENC_ATTN_PS_GLOBAL : (r.x3 && r.ws == 14 && r.hd == 80) ? ENC_ATTN_WIN14 : ENC_ATTN_TABLES;
+  // each candidate is hgl_attention_route's answer for the descriptor the block would launch with (plane distance + one item's
+  // rows within 32 bits, shapes, registered tables, switches), taken here because the in-projection writes planes OR fp32
+  const auto serves = [&](EncAttn kind, HglAttnRoute family) { return hgl_attention_route(enc_attn(b, p, r, kind)) == family; };
+  r.attn = ENC_ATTN_TABLES;
+  if (r.x3 && r.ws == 14 && serves(ENC_ATTN_PS_WIN, HGL_ATTN_PS_WIN)) r.attn = ENC_ATTN_PS_WIN;
+  else if (r.x3 && r.ws == 0 && r.size == 64 && ps_glob_on && serves(ENC_ATTN_PS_GLOBAL, HGL_ATTN_PS_RELT)) r.attn = ENC_ATTN_PS_GLOBAL;
+  else if (r.x3 && r.ws == 14 && serves(ENC_ATTN_WIN14, HGL_ATTN_WIN14)) r.attn = ENC_ATTN_WIN14;
   r.planes = r.attn == ENC_ATTN_PS_WIN || r.attn == ENC_ATTN_PS_GLOBAL;
   return HGL_OK;
 }
 
-// the fp16 hi | lo planes of the split path: each pair aliases an fp32 buffer of the plan (same bytes)
-struct EncPlanes {
-  uint16_t *Ah, *Al;    // GEMM input in window order, later the attention's output (the window buffer)
-  uint16_t *Hh, *Hl;    // norm2 (H)
-  uint16_t *Fh, *Fl;    // mlp.lin1 (F)
-  uint16_t *Qh, *Ql;    // split qkv (QKV)
-  EncPlanes(const EncPlan& p, const EncBlockRoute& r)
-      : Ah((uint16_t*)p.Hw), Al(Ah + (size_t)r.M * r.D), Hh((uint16_t*)p.H), Hl(Hh + (size_t)r.T * r.D), Fh((uint16_t*)p.F),
-        Fl(Fh + (size_t)r.T * 4 * r.D), Qh((uint16_t*)p.QKV), Ql(Qh + (size_t)r.M * 3 * r.D) {}
-};
-
-// attention of the B windows (or whole grids) on p.QKV -> the planes Ah | Al (x3) or p.O (fp32)
+// attention of the B windows (or whole grids): the rel-pos producer of r.attn, then the kernel the route named
 int enc_attention(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, hipStream_t st) {
   const int D = r.D, B = r.B, S = r.S, M = r.M, L = r.L, heads = r.heads, hd = r.hd, size = r.size;
-  const EncPlanes s(p, r);
-  const float scale = 1.0f / sqrtf((float)hd);
-  if (r.planes) {
-    const float *rel_h = nullptr, *rel_w = nullptr, *tab_h = b.rel_pos_h, *tab_w = b.rel_pos_w;
-    int rel_k = 0;
-    if (r.attn == ENC_ATTN_PS_GLOBAL) {
-      HGL_TRY(hgl_launch_relpos_split(s.Qh, s.Ql, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
-      rel_h = p.relh, rel_w = p.relw, rel_k = size, tab_h = tab_w = nullptr;
+  if (r.attn == ENC_ATTN_PS_GLOBAL) {
+    const EncPlanes s(p, r);
+    HGL_TRY(hgl_launch_relpos_split(s.Qh, s.Ql, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
+  } else if (r.attn == ENC_ATTN_TABLES) {
+    // decomposed rel-pos tables rel_h/rel_w [B*heads, S, size] from the UNSCALED q (image_encoder.py:351-354)
+    if (hd == 80 || hd == 64) {
+      HGL_TRY(hgl_launch_relpos_direct(p.QKV, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
+    } else {  // generic head dims: q . rel_pos[r] for every r as a batched GEMM, then gathered per (q,k)
+      HGL_TRY(hgl_launch_gemm(p.QKV, b.rel_pos_h, nullptr, nullptr, p.Th, M, L, hd, 3 * D, hd, 0, L, heads, hd, 0,
+                              0, (long long)M * L, HGL_ACT_NONE, st));
+      HGL_TRY(hgl_launch_gemm(p.QKV, b.rel_pos_w, nullptr, nullptr, p.Tw, M, L, hd, 3 * D, hd, 0, L, heads, hd, 0,
+                              0, (long long)M * L, HGL_ACT_NONE, st));
+      HGL_TRY(hgl_launch_relpos_gather(p.Th, B, heads, S, size, L, 0, p.relh, st));
+      HGL_TRY(hgl_launch_relpos_gather(p.Tw, B, heads, S, size, L, 1, p.relw, st));
     }
-    const int rc = hgl_launch_attention_ps(s.Qh, s.Ql, 3 * D, 0, D, 2 * D, S, B, heads, S, hd, nullptr, s.Ah, s.Al, D, (long long)S * D,
-                                           scale, HGL_MASK_NONE, nullptr, 0, 0, rel_h, rel_w, rel_k, rel_k, tab_h, tab_w, st);
-    if (rc < 0) return rc;
-    HGL_REQUIRE(rc == 0, "sam_encode: the pre-split attention refused a shape its caller had checked");
-    return HGL_OK;
-  }
-  if (r.attn == ENC_ATTN_WIN14) {
-    const int rc = hgl_launch_attention_win14(p.QKV, p.QKV + D, p.QKV + 2 * D, s.Ah, s.Al, B, heads, hd, 3 * D, 3 * D, 3 * D, D,
-                                              (long long)S * 3 * D, (long long)S * 3 * D, (long long)S * 3 * D, (long long)S * D,
-                                              scale, b.rel_pos_h, b.rel_pos_w, st);
-    if (rc <= 0) return rc;   // (> 0: the kernel declines, e.g. tables that are not registered -> the rel-pos tables below)
-  }
-  // decomposed rel-pos tables rel_h/rel_w [B*heads, S, size] from the UNSCALED q (image_encoder.py:351-354)
-  if (hd == 80 || hd == 64) {
-    HGL_TRY(hgl_launch_relpos_direct(p.QKV, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
-  } else {  // generic head dims: q . rel_pos[r] for every r as a batched GEMM, then gathered per (q,k)
-    HGL_TRY(hgl_launch_gemm(p.QKV, b.rel_pos_h, nullptr, nullptr, p.Th, M, L, hd, 3 * D, hd, 0, L, heads, hd, 0,
-                            0, (long long)M * L, HGL_ACT_NONE, st));
-    HGL_TRY(hgl_launch_gemm(p.QKV, b.rel_pos_w, nullptr, nullptr, p.Tw, M, L, hd, 3 * D, hd, 0, L, heads, hd, 0,
-                            0, (long long)M * L, HGL_ACT_NONE, st));
-    HGL_TRY(hgl_launch_relpos_gather(p.Th, B, heads, S, size, L, 0, p.relh, st));
-    HGL_TRY(hgl_launch_relpos_gather(p.Tw, B, heads, S, size, L, 1, p.relw, st));
   }
   // f16x3: the attention writes its output as the fp16 hi+lo pair the projection reads
-  return hgl_launch_attention_split(p.QKV, p.QKV + D, p.QKV + 2 * D, r.x3 ? nullptr : p.O, s.Ah, s.Al, B, heads, S, S, hd, 3 * D,
-                                    3 * D, 3 * D, D, (long long)S * 3 * D, (long long)S * 3 * D, (long long)S * 3 * D,
-                                    (long long)S * D, scale, HGL_MASK_NONE, nullptr, 0, 0, p.relh, p.relw, size, size, st);
+  return hgl_launch_attention(enc_attn(b, p, r, r.attn), st);
 }
 
 // the block on the split-fp16 path
@@ -253,7 +247,7 @@ int enc_block_f32(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& 
 
 int enc_block(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPlan& p, hipStream_t st) {
   EncBlockRoute r;
-  HGL_TRY(enc_block_route(w, b, p.nb, r));
+  HGL_TRY(enc_block_route(w, b, p, r));
   return r.x3 ? enc_block_x3(b, p, r, st) : enc_block_f32(b, p, r, st);
 }
 
@@ -382,18 +376,22 @@ inline size_t dec_bias_bytes(int P, int HW) { return (size_t)P * 56 * HW * sizeo
 int dec_fewq(const float* q, const float* k, const float* v, float* att, int B, int heads, int Nq, int Nk, int hd, int ldq,
              int ldk, int ldv, int ldo, long long sqb, long long skb, long long svb, long long sob, float* part,
              size_t part_bytes, hipStream_t st, int kv_group = 1) {
-  const float scale = 1.0f / sqrtf((float)hd);
+  HglAttn d;
+  d.B = B, d.H = heads, d.Sq = Nq, d.Sk = Nk, d.hd = hd, d.scale = 1.0f / sqrtf((float)hd);
+  d.q = q, d.k = k, d.v = v, d.out = att;
+  d.ldq = ldq, d.ldk = ldk, d.ldv = ldv, d.ldo = ldo;
+  d.sqb = sqb, d.skb = skb, d.svb = svb, d.sob = sob;
   if (part) {
+    d.part = part, d.part_bytes = part_bytes, d.kv_group = kv_group;
     // the chunked kernel holds up to 7 queries: longer prompts (more sparse tokens) go through it 7 queries at a time
-    for (int q0 = 0; q0 < Nq; q0 += 7)
-      HGL_TRY(hgl_launch_attention_fewq_chunked(q + (long long)q0 * ldq, k, v, att + (long long)q0 * ldo, B, heads,
-                                                Nq - q0 < 7 ? Nq - q0 : 7, Nk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb, sob, scale,
-                                                part, part_bytes, st, kv_group));
+    for (int q0 = 0; q0 < Nq; q0 += 7) {
+      d.q = q + (long long)q0 * ldq, d.out = att + (long long)q0 * ldo, d.Sq = Nq - q0 < 7 ? Nq - q0 : 7;
+      HGL_TRY(hgl_launch_attention(d, st));
+    }
     return HGL_OK;
   }
   HGL_REQUIRE(kv_group == 1, "sam_decode: keys shared by groups of %d prompts need the chunked attention", kv_group);
-  return hgl_launch_attention(q, k, v, att, B, heads, Nq, Nk, hd, ldq, ldk, ldv, ldo, sqb, skb, svb, sob, scale, HGL_MASK_NONE,
-                              nullptr, 0, 0, nullptr, nullptr, 0, 0, st);
+  return hgl_launch_attention(d, st);
 }
 
 // Attention.forward (modeling/transformer.py:218-240).  q: [Bq? , Nq, C] rows; when q_shared the same
@@ -605,9 +603,12 @@ int dec_i2t(const DecRoute& r, const HglSamDecoderW* w, int li, const DecPlan& p
     HGL_TRY(lin(p.qpe, C, a.k, nullptr, 0, p.k1, I, P * T, I, C, HGL_ACT_NONE, st));
     HGL_TRY(lin(p.queries, C, a.v, nullptr, 0, p.v1, I, P * T, I, C, HGL_ACT_NONE, st));
     const SplitPair at = split_view(p.atti, (size_t)P * HW * I);
-    HGL_TRY(hgl_launch_attention_split(from_kvq ? p.kp + 2 * I : p.qi, p.k1, p.v1, nullptr, at.hi, at.lo, P, heads, HW, T, hd, ldq, I,
-                                       I, I, shared ? 0 : (long long)HW * ldq, (long long)T * I, (long long)T * I, (long long)HW * I,
-                                       1.0f / sqrtf((float)hd), HGL_MASK_NONE, nullptr, 0, 0, nullptr, nullptr, 0, 0, st));
+    HglAttn d;
+    d.B = P, d.H = heads, d.Sq = HW, d.Sk = T, d.hd = hd, d.scale = 1.0f / sqrtf((float)hd);
+    d.q = from_kvq ? p.kp + 2 * I : p.qi, d.k = p.k1, d.v = p.v1;
+    d.ldq = ldq, d.ldk = d.ldv = I, d.sqb = shared ? 0 : (long long)HW * ldq, d.skb = d.svb = (long long)T * I;
+    d.out_hi = at.hi, d.out_lo = at.lo, d.ldo = I, d.sob = (long long)HW * I;
+    HGL_TRY(hgl_launch_attention(d, st));
     HGL_TRY(hgl_launch_gemm_f16x3_rmod(at.hi, at.lo, I, a.out.w, a.out.b, keys, C, shared ? HW : 0, p.keys, nullptr, nullptr, C,
                                        P * HW, C, I, HGL_ACT_NONE, st));
   }

@@ -1,4 +1,4 @@
-"""GPU: every branch of the attention dispatcher (hgl_launch_attention_split / launch_hd, csrc/attention.hip) against a
+"""GPU: every branch of the attention dispatcher (hgl_attention_route / hgl_launch_attention, csrc/attention.hip) against a
 float64 reference, at the layouts the model code hands it and at the lengths where tiles end.
 
 Each row of CASES names the kernel it must reach in the split-fp16 modes ({T}: TERMS = 3 in f16x3, 1 in f16); in f32 mode

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_ref as R
 from hybridgl_amd import _lib, ops, weights
 from hybridgl_amd import sam as hsam
 from hybridgl_amd.synth import synth_image
@@ -29,6 +30,11 @@ def _ab(fn):
     return a, b
 
 
+def _attn_kernels(fn):
+    """the attention kernels fn() launches, in launch order (the profiler's names, as abi_ref.kernel_key gives them)"""
+    return [n for n in R.launched_kernels(fn) if n.startswith("attn_")]
+
+
 @pytest.mark.parametrize("nb", [1, 3])
 def test_sam_encoder_blocks_presplit_equal_fp32_input_kernels(cuda, nb):
     """ViT-H width, one windowed (14 x 14, head dim 80, rel-pos tables in the kernel, pad rows) and one global block
@@ -38,14 +44,32 @@ def test_sam_encoder_blocks_presplit_equal_fp32_input_kernels(cuda, nb):
     cfg = weights.SAM_CONFIGS["vit_h_d2"]
     m = hsam.Sam(weights.sam_state_dict("vit_h_d2", 0), cfg, cuda)
     imgs = [torch.from_numpy(synth_image(1024, 1024 - 64 * i, 20 + i)).to(cuda) for i in range(nb)]
-    e0, e1 = _ab(lambda: m.encode_batch(imgs).clone())
+    ran = []
+
+    def encode():
+        out = []
+        ran.append(_attn_kernels(lambda: out.append(m.encode_batch(imgs).clone())))
+        return out[0]
+
+    e0, e1 = _ab(encode)
+    # block 0 is windowed, block 1 global: the kernels that split the fp32 qkv themselves (rel-pos tables in the kernel, the
+    # ping-pong kernel with the terms as tensors), then the pre-split windowed and rel-pos-tensor kernels
+    assert ran == [["attn_x3_kernel<80,14,8,3>", "attn_x3pp_kernel<80,3>"],
+                   ["attn_psp_kernel<80,1,1>", "attn_psp_kernel<80,2,1>"]], ran
     assert torch.isfinite(e0).all() and float(e0.abs().max()) > 0
     assert torch.equal(e0, e1), float((e0 - e1).abs().max())
 
 
-@pytest.mark.parametrize("B,H,S,hd,mask", [(40, 12, 197, 64, "none"), (40, 12, 197, 64, "cls_keep"), (3, 12, 197, 64, "cls_keep"),
-                                           (5, 12, 785, 64, "none"), (8, 16, 196, 80, "none"), (2, 16, 1024, 80, "none"),
-                                           (16, 12, 257, 64, "cls_keep"), (9, 12, 130, 64, "none")])
+ROWS = [(40, 12, 197, 64, "none"), (40, 12, 197, 64, "cls_keep"), (3, 12, 197, 64, "cls_keep"), (5, 12, 785, 64, "none"),
+        (8, 16, 196, 80, "none"), (2, 16, 1024, 80, "none"), (16, 12, 257, 64, "cls_keep"), (9, 12, 130, 64, "none"),
+        (6, 16, 197, 80, "cls_keep")]
+# the kernel each row reaches: the 197-token kernel (un-pipelined, two query tiles per wave) for 129..256 tokens at head dim 64,
+# else the pipelined persistent kernel at head dim 64 / 80 (mode PS_PLAIN = 0), with and without the CLS keep row
+PS_CLIP, PS_PLAIN64, PS_PLAIN80 = "attn_ps_kernel<64,0,2>", "attn_psp_kernel<64,0,1>", "attn_psp_kernel<80,0,1>"
+KERNEL = dict(zip(ROWS, [PS_CLIP, PS_CLIP, PS_CLIP, PS_PLAIN64, PS_PLAIN80, PS_PLAIN80, PS_PLAIN64, PS_CLIP, PS_PLAIN80]))
+
+
+@pytest.mark.parametrize("B,H,S,hd,mask", ROWS)
 def test_presplit_kernels_equal_the_fp32_input_kernels(cuda, B, H, S, hd, mask):
     """hgl_attention_presplit_f32 (split planes, LDS-DMA staging, pipelined persistent kernel) against hgl_attention_f32 (the
     kernels that split q / k / v themselves) on CLIP's 197-token sequences with and without the CLS keep row of
@@ -66,7 +90,10 @@ def test_presplit_kernels_equal_the_fp32_input_kernels(cuda, B, H, S, hd, mask):
     D = H * hd
     q, k, v = (qkv[..., i * D:(i + 1) * D].contiguous() for i in range(3))
     ref = ops.attention(q, k, v, H, mask=mask, **kw)
-    got = ops.attention_presplit(qkv, H, mask=mask, **kw)
+    out = []
+    names = _attn_kernels(lambda: out.append(ops.attention_presplit(qkv, H, mask=mask, **kw)))
+    got = out[0]
+    assert names == [KERNEL[B, H, S, hd, mask]], names
     assert torch.isfinite(got).all()
     err = float((got - ref).abs().max())
     assert err <= 4e-6 * max(1.0, float(ref.abs().max())), err
