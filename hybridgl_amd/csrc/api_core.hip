@@ -133,8 +133,10 @@ int hgl_gemm_f32(const float* A, const float* W, const float* bias, const float*
                  int N, int K, int lda, int ldw, int ldr, int ldc, int batch, long long sA,
                  long long sW, long long sR, long long sC, int act, void* stream) {
   HGL_TRY(hgl_require_device());
-  return hgl_launch_gemm(A, W, bias, R, C, M, N, K, lda, ldw, ldr, ldc, batch, sA, sW, sR, sC, act,
-                         (hipStream_t)stream);
+  HglGemm d = hgl_gemm_linear(A, W, bias, C, M, N, K, act, R);
+  d.lda = lda, d.ldw = ldw, d.ldr = ldr, d.ldc = ldc;
+  d.batch = batch, d.sA = sA, d.sW = sW, d.sR = sR, d.sC = sC;
+  return hgl_launch_gemm(d, (hipStream_t)stream);
 }
 
 int hgl_layernorm_f32(const float* x, const float* w, const float* b, float* y, int rows, int D,

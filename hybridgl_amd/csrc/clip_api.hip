@@ -68,17 +68,13 @@ int hgl_clip_block_qkv(const HglResBlockW& w, const HglClipBlockRoute& r, const 
     uint16_t* Hh = (uint16_t*)bf.H;
     uint16_t* Hl = Hh + (size_t)M * D;
     HGL_TRY(hgl_launch_layernorm_split(X, w.ln1_w, w.ln1_b, Hh, Hl, M, D, 1e-5f, st));
-    if (r.planes) {
-      uint16_t* Qh = (uint16_t*)bf.QKV;
-      return hgl_launch_gemm_f16x3(Hh, Hl, D, w.in_proj_w, w.in_proj_b, nullptr, 0, nullptr, Qh, Qh + (size_t)M * 3 * D, 3 * D, M,
-                                   3 * D, D, HGL_ACT_NONE, st);
-    }
-    return hgl_launch_gemm_f16x3(Hh, Hl, D, w.in_proj_w, w.in_proj_b, nullptr, 0, bf.QKV, nullptr, nullptr, 3 * D, M, 3 * D, D,
-                                 HGL_ACT_NONE, st);
+    uint16_t* Qh = (uint16_t*)bf.QKV;
+    if (r.planes)
+      return hgl_launch_gemm(hgl_gemm_planes_split(Hh, Hl, w.in_proj_w, w.in_proj_b, Qh, Qh + (size_t)M * 3 * D, M, 3 * D, D), st);
+    return hgl_launch_gemm(hgl_gemm_planes(Hh, Hl, w.in_proj_w, w.in_proj_b, bf.QKV, M, 3 * D, D), st);
   }
   HGL_TRY(hgl_launch_layernorm(X, w.ln1_w, w.ln1_b, bf.H, M, D, 1e-5f, st));
-  return hgl_launch_gemm(bf.H, w.in_proj_w, w.in_proj_b, nullptr, bf.QKV, M, 3 * D, D, D, D, 0, 3 * D, 1, 0, 0, 0, 0,
-                         HGL_ACT_NONE, st);
+  return hgl_launch_gemm(hgl_gemm_linear(bf.H, w.in_proj_w, w.in_proj_b, bf.QKV, M, 3 * D, D), st);
 }
 
 // second half: x <- x + out_proj(attention(QKV)) ; x <- x + mlp(ln_2 x)
@@ -98,30 +94,21 @@ int hgl_clip_block_rest(const HglResBlockW& w, const HglClipBlockRoute& r, float
     HGL_TRY(hgl_launch_attention(at, st));
     // (balanced: whole rounds of the persistent tiling + a split-K tail when the last round would be mostly empty; the
     // partial sums borrow the qkv buffer, dead after the attention)
-    HGL_TRY(hgl_launch_gemm_f16x3_balanced(Hh, Hl, D, nullptr, w.out_proj_w, w.out_proj_b, X, D, nullptr, X, D, M, D, D, HGL_ACT_NONE,
-                                           bf.QKV, (size_t)M * 3 * D * sizeof(float), st));
+    HglGemm out = hgl_gemm_planes(Hh, Hl, w.out_proj_w, w.out_proj_b, X, M, D, D, HGL_ACT_NONE, X);
+    out.part = bf.QKV, out.part_bytes = (size_t)M * 3 * D * sizeof(float);
+    HGL_TRY(hgl_launch_gemm(out, st));
     HGL_TRY(hgl_launch_layernorm_split(X, w.ln2_w, w.ln2_b, Hh, Hl, M, D, 1e-5f, st));
-    HGL_TRY(hgl_launch_gemm_f16x3(Hh, Hl, D, w.fc_w, w.fc_b, nullptr, 0, nullptr, Fh, Fl, 4 * D, M, 4 * D, D,
-                                  HGL_ACT_QUICKGELU, st));
-    if (r.ks > 1) {
-      HGL_TRY(hgl_launch_gemm_f16x3_splitk(Fh, Fl, 4 * D, nullptr, w.proj_w, w.proj_b, X, D, nullptr, X, D, M, D, 4 * D,
-                                           HGL_ACT_NONE, r.ks, bf.QKV, (size_t)M * 3 * D * sizeof(float), st));
-    } else {
-      HGL_TRY(hgl_launch_gemm_f16x3_balanced(Fh, Fl, 4 * D, nullptr, w.proj_w, w.proj_b, X, D, nullptr, X, D, M, D, 4 * D, HGL_ACT_NONE,
-                                             bf.QKV, (size_t)M * 3 * D * sizeof(float), st));
-    }
-    return HGL_OK;
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes_split(Hh, Hl, w.fc_w, w.fc_b, Fh, Fl, M, 4 * D, D, HGL_ACT_QUICKGELU), st));
+    HglGemm proj = hgl_gemm_planes(Fh, Fl, w.proj_w, w.proj_b, X, M, D, 4 * D, HGL_ACT_NONE, X);
+    proj.part = out.part, proj.part_bytes = out.part_bytes, proj.ksplit = r.ks;   // r.ks 1: whole rounds + a tail where that pays
+    return hgl_launch_gemm(proj, st);
   }
   at.out = bf.H;
   HGL_TRY(hgl_launch_attention(at, st));
-  HGL_TRY(hgl_launch_gemm(bf.H, w.out_proj_w, w.out_proj_b, X, X, M, D, D, D, D, D, D, 1, 0, 0, 0, 0,
-                          HGL_ACT_NONE, st));
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(bf.H, w.out_proj_w, w.out_proj_b, X, M, D, D, HGL_ACT_NONE, X), st));
   HGL_TRY(hgl_launch_layernorm(X, w.ln2_w, w.ln2_b, bf.H, M, D, 1e-5f, st));
-  HGL_TRY(hgl_launch_gemm(bf.H, w.fc_w, w.fc_b, nullptr, bf.F, M, 4 * D, D, D, D, 0, 4 * D, 1, 0, 0,
-                          0, 0, HGL_ACT_QUICKGELU, st));
-  HGL_TRY(hgl_launch_gemm(bf.F, w.proj_w, w.proj_b, X, X, M, D, 4 * D, 4 * D, 4 * D, D, D, 1, 0, 0,
-                          0, 0, HGL_ACT_NONE, st));
-  return HGL_OK;
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(bf.H, w.fc_w, w.fc_b, bf.F, M, 4 * D, D, HGL_ACT_QUICKGELU), st));
+  return hgl_launch_gemm(hgl_gemm_linear(bf.F, w.proj_w, w.proj_b, X, M, D, 4 * D, HGL_ACT_NONE, X), st);
 }
 
 // x <- x + attn(ln_1 x) ; x <- x + mlp(ln_2 x)      (clip/model.py:244-257)
@@ -142,12 +129,10 @@ int hgl_clip_embed_images(const HglClipVisionW* w, const float* imgs, int n_img,
     uint16_t* ch = (uint16_t*)cols;
     uint16_t* cl = ch + (size_t)n_img * P * kd;
     HGL_TRY(hgl_launch_im2col_patch_split(imgs, n_img, g * w->patch, w->patch, ch, cl, st));
-    HGL_TRY(hgl_launch_gemm_f16x3(ch, cl, kd, w->conv1_w, nullptr, nullptr, 0, tok, nullptr, nullptr, D, n_img * P, D, kd,
-                                  HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(ch, cl, w->conv1_w, nullptr, tok, n_img * P, D, kd), st));
   } else {
     HGL_TRY(hgl_launch_im2col_patch(imgs, n_img, g * w->patch, w->patch, cols, st));
-    HGL_TRY(hgl_launch_gemm(cols, w->conv1_w, nullptr, nullptr, tok, n_img * P, D, kd, kd, kd, 0, D, 1,
-                            0, 0, 0, 0, HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(cols, w->conv1_w, nullptr, tok, n_img * P, D, kd), st));
   }
   HGL_TRY(hgl_launch_assemble_lnpre(tok, w->class_embedding, w->positional_embedding, w->ln_pre_w,
                                     w->ln_pre_b, X, n_img, S, D, st));
@@ -211,20 +196,19 @@ int run_block_cls(const HglResBlockW& w, const float* X, int B, int S, int D, in
   at.mask_kind = mask_kind, at.keep = keep, at.keep_b0 = keep_b0, at.keep_n = keep_n;
   HGL_TRY(hgl_launch_attention(at, st));
   HGL_TRY(hgl_launch_gather_rows(X, (long long)S * D, B, D, xcls, st));
-  HGL_TRY(hgl_launch_gemm(att, w.out_proj_w, w.out_proj_b, xcls, xcls, B, D, D, D, D, D, D, 1, 0, 0, 0, 0, HGL_ACT_NONE, st));
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(att, w.out_proj_w, w.out_proj_b, xcls, B, D, D, HGL_ACT_NONE, xcls), st));
   HGL_TRY(hgl_launch_layernorm(xcls, w.ln2_w, w.ln2_b, h, B, D, 1e-5f, st));
-  HGL_TRY(hgl_launch_gemm(h, w.fc_w, w.fc_b, nullptr, bf.F, B, 4 * D, D, D, D, 0, 4 * D, 1, 0, 0, 0, 0, HGL_ACT_QUICKGELU, st));
-  HGL_TRY(hgl_launch_gemm(bf.F, w.proj_w, w.proj_b, xcls, xcls, B, D, 4 * D, 4 * D, 4 * D, D, D, 1, 0, 0, 0, 0, HGL_ACT_NONE,
-                          st));
-  return HGL_OK;
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(h, w.fc_w, w.fc_b, bf.F, B, 4 * D, D, HGL_ACT_QUICKGELU), st));
+  return hgl_launch_gemm(hgl_gemm_linear(bf.F, w.proj_w, w.proj_b, xcls, B, D, 4 * D, HGL_ACT_NONE, xcls), st);
 }
 
 // ln_post(rows) @ proj (+ R) on CLS rows that are already gathered (p.cls_rows)
 int head_rows(const HglClipVisionW* w, int N, float* out, const float* R, const ClipPlan& p, hipStream_t st) {
   const int D = w->width, E = w->embed;
   HGL_TRY(hgl_launch_layernorm(p.cls_rows, w->ln_post_w, w->ln_post_b, p.cls_ln, N, D, 1e-5f, st));
-  HGL_TRY(hgl_launch_gemm(p.cls_ln, w->proj_t, nullptr, R, out, N, E, D, D, D, E, E, 1, 0, 0, 0, 0, HGL_ACT_NONE, st));
-  return HGL_OK;
+  HglGemm head = hgl_gemm_linear(p.cls_ln, w->proj_t, nullptr, out, N, E, D, HGL_ACT_NONE, R);
+  head.ldr = E;
+  return hgl_launch_gemm(head, st);
 }
 
 bool valid_vision(const HglClipVisionW* w) {
@@ -475,9 +459,7 @@ int hgl_clip_encode_text_ex(const HglClipTextW* w, const int32_t* tokens, int B,
   // ln_final is row-wise: normalise only the pooled rows, then project (clip/model.py:424-429)
   HGL_TRY(hgl_launch_gather_eot(p.X, p.eot, B, S, D, p.rows, st));
   HGL_TRY(hgl_launch_layernorm(p.rows, w->ln_final_w, w->ln_final_b, p.rows_ln, B, D, 1e-5f, st));
-  HGL_TRY(hgl_launch_gemm(p.rows_ln, w->text_projection_t, nullptr, nullptr, out, B, w->embed, D, D, D,
-                          0, w->embed, 1, 0, 0, 0, 0, HGL_ACT_NONE, st));
-  return HGL_OK;
+  return hgl_launch_gemm(hgl_gemm_linear(p.rows_ln, w->text_projection_t, nullptr, out, B, w->embed, D), st);
 }
 
 int hgl_clip_encode_text_prefix(const HglClipTextW* w, const int32_t* tokens, int B, int seq_len, float* out,

@@ -354,12 +354,11 @@ int gem_block(const HglResBlockW& w, const GemPlan& p, int S, int D, int heads, 
     hipLaunchKernelGGL(mean3_split_kernel, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, p.X1, MD, MD, Mh,
                        hgl_split_terms() == 1 ? nullptr : Ml);
     HGL_TRY(hgl_check_launch("gem_mean3"));
-    HGL_TRY(hgl_launch_gemm_f16x3(Mh, Ml, D, w.out_proj_w, w.out_proj_b, p.Xg, D, p.Xg, nullptr, nullptr, D, M, D, D,
-                                  HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(Mh, Ml, w.out_proj_w, w.out_proj_b, p.Xg, M, D, D, HGL_ACT_NONE, p.Xg), st));
   } else {
     hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, p.X1, MD, MD, p.N3);
     HGL_TRY(hgl_check_launch("gem_mean3"));
-    HGL_TRY(hgl_launch_gemm(p.N3, w.out_proj_w, w.out_proj_b, p.Xg, p.Xg, M, D, D, D, D, D, D, 1, 0, 0, 0, 0, HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.N3, w.out_proj_w, w.out_proj_b, p.Xg, M, D, D, HGL_ACT_NONE, p.Xg), st));
   }
   if (!need_ori) return HGL_OK;
   // original stream (clip/model.py:244-257): the plain block on the same QKV
@@ -419,10 +418,10 @@ int hgl_gem_image_features_batch(const HglClipVisionW* w, const float* imgs, int
   }
   // ln_post + proj on every token of the stream(s)
   HGL_TRY(hgl_launch_layernorm(gem_stream, w->ln_post_w, w->ln_post_b, p.H, M, D, 1e-5f, st));
-  HGL_TRY(hgl_launch_gemm(p.H, w->proj_t, nullptr, nullptr, feat_gem, M, E, D, D, D, 0, E, 1, 0, 0, 0, 0, HGL_ACT_NONE, st));
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.H, w->proj_t, nullptr, feat_gem, M, E, D), st));
   if (feat_ori) {
     HGL_TRY(hgl_launch_layernorm(p.X, w->ln_post_w, w->ln_post_b, p.H, M, D, 1e-5f, st));
-    HGL_TRY(hgl_launch_gemm(p.H, w->proj_t, nullptr, nullptr, feat_ori, M, E, D, D, D, 0, E, 1, 0, 0, 0, 0, HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.H, w->proj_t, nullptr, feat_ori, M, E, D), st));
   }
   return HGL_OK;
 }

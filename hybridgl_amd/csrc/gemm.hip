@@ -216,38 +216,24 @@ __global__ __launch_bounds__(NTHREADS, OCC) void gemm_f32_kernel(GemmArgs g) {
 
 }  // namespace
 
-int hgl_launch_gemm(const float* A, const float* W, const float* bias, const float* R, float* C,
-                    int M, int N, int K, int lda, int ldw, int ldr, int ldc, int batch,
-                    long long sA, long long sW, long long sR, long long sC, int act,
-                    hipStream_t st) {
-  HGL_REQUIRE(A && W && C, "gemm: null operand");
-  HGL_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0, "gemm: bad shape M=%d N=%d K=%d batch=%d", M, N, K, batch);
-  HGL_REQUIRE((K & 3) == 0 && (lda & 3) == 0 && (ldw & 3) == 0, "gemm: K, lda, ldw must be multiples of 4 (K=%d lda=%d ldw=%d)", K, lda, ldw);
-  HGL_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0, "gemm: A and W must be 16-byte aligned");
-  HGL_REQUIRE((sA & 3) == 0 && (sW & 3) == 0, "gemm: batch strides of A and W must be multiples of 4");
-  HGL_REQUIRE(act >= 0 && act <= 3, "gemm: bad activation %d", act);
-  // f16x3 mode, small M, registered weight: the split-fp16 small-tile kernel (gemm_f16x3.hip)
-  if (hgl_gemm_skinny_applicable(W, M, N, K, lda, ldw, batch))
-    return hgl_launch_gemm_x3_skinny(A, lda, W, bias, R, ldr, C, ldc, M, N, K, act, st);
+// the fp32 tile launch of a descriptor hgl_launch_gemm (gemm_f16x3.hip) has validated and routed here
+int hgl_launch_gemm_f32_tiles(const HglGemm& d, hipStream_t st) {
   GemmArgs g;
-  g.A = A; g.W = W; g.bias = bias; g.R = R; g.C = C;
-  g.M = M; g.N = N; g.K = K;
-  g.lda = lda; g.ldw = ldw; g.ldr = ldr; g.ldc = ldc;
-  g.sA = sA; g.sW = sW; g.sR = sR; g.sC = sC;
-  g.act = act;
-  g.tiles_m = (M + BM - 1) / BM;
-  g.tiles_n = (N + BN - 1) / BN;
-  const long long nwg = (long long)g.tiles_m * g.tiles_n * batch;
+  g.A = d.A; g.W = d.W; g.bias = d.bias; g.R = d.R; g.C = d.C;
+  g.M = d.M; g.N = d.N; g.K = d.K;
+  g.lda = d.lda; g.ldw = d.ldw; g.ldr = d.ldr; g.ldc = d.ldc;
+  g.sA = d.sA; g.sW = d.sW; g.sR = d.sR; g.sC = d.sC;
+  g.act = d.act;
+  g.tiles_m = (d.M + BM - 1) / BM;
+  g.tiles_n = (d.N + BN - 1) / BN;
+  const long long nwg = (long long)g.tiles_m * g.tiles_n * d.batch;
   HGL_REQUIRE(nwg < (1ll << 31), "gemm: grid too large");
   // default: single LDS buffer (36.9 KB) -> 3 workgroups per CU (3 waves/SIMD); measured on MI355X
   // 104-121 TF/s on the CLIP shapes vs 87-108 for the double-buffered 2-workgroup variant, which
   // HGL_GEMM_BK32X2=1 keeps selectable in the diagnostic build (make diag).
-  static int variant = -1;
-  if (variant < 0) {
-    variant = HGL_DIAG_SWITCH("HGL_GEMM_BK32X2", 0) ? 1 : 0;
-  }
-  HglProfScope prof(HGL_PROF_GEMM, 2.0 * M * (double)N * K * batch,
-                    4.0 * batch * ((double)M * K + (double)N * K + (double)M * N * (R ? 2 : 1)), st);
+  static const int variant = HGL_DIAG_SWITCH("HGL_GEMM_BK32X2", 0) ? 1 : 0;
+  HglProfScope prof(HGL_PROF_GEMM, 2.0 * d.M * (double)d.N * d.K * d.batch,
+                    4.0 * d.batch * ((double)d.M * d.K + (double)d.N * d.K + (double)d.M * d.N * (d.R ? 2 : 1)), st);
 #define HGL_GEMM_LAUNCH(ACT_, BK_, NBUF_, OCC_)                                                            \
   do {                                                                                                  \
     const size_t lds_ = (size_t)NBUF_ * (BM + BN) * (BK_ + 4) * sizeof(float);                          \
@@ -255,16 +241,12 @@ int hgl_launch_gemm(const float* A, const float* W, const float* bias, const flo
     hipLaunchKernelGGL((gemm_f32_kernel<ACT_, BK_, NBUF_, OCC_>), dim3((unsigned)nwg), dim3(NTHREADS), lds_,  \
                        st, g);                                                                          \
   } while (0)
-#define HGL_GEMM_VARIANTS(ACT_)                               \
-  do {                                                        \
-    if (variant == 1) HGL_GEMM_LAUNCH(ACT_, 32, 2, 2);        \
-    else HGL_GEMM_LAUNCH(ACT_, 32, 1, 3);                     \
-  } while (0)
-  switch (act) {
-    case HGL_ACT_QUICKGELU: HGL_GEMM_VARIANTS(HGL_ACT_QUICKGELU); break;
-    case HGL_ACT_GELU: HGL_GEMM_VARIANTS(HGL_ACT_GELU); break;
-    case HGL_ACT_RELU: HGL_GEMM_VARIANTS(HGL_ACT_RELU); break;
-    default: HGL_GEMM_VARIANTS(HGL_ACT_NONE); break;
-  }
+  HGL_TRY(hgl_with_act(d.act, [&](auto act) -> int {
+    constexpr int ACT = decltype(act)::value;
+    if (variant == 1) HGL_GEMM_LAUNCH(ACT, 32, 2, 2);
+    else HGL_GEMM_LAUNCH(ACT, 32, 1, 3);
+    return HGL_OK;
+  }));
+#undef HGL_GEMM_LAUNCH
   return hgl_check_launch("gemm_f32");
 }

@@ -73,7 +73,7 @@ struct Args {
   int vec4;    // N, ldc, ldr multiples of 4 and 16-byte aligned bases: the write-out moves 16-byte vectors
 };
 
-int g_x3_kernel = -2;   // -2: not yet chosen (-> -1); -1: cost model; >= 0: forced by hgl_gemm_f16x3_select
+int g_x3_kernel = -1;   // -1: the cost model; >= 0: a tiling pinned by hgl_gemm_f16x3_select
 
 // grid of the persistent ping-pong kernel: one workgroup per CU (HGL_X3_PERSIST=0: one per tile)
 int x3_num_cus() {
@@ -1067,24 +1067,12 @@ int hgl_launch_layernorm_split_maps(const float* x, const float* w, const float*
   return hgl_check_launch("layernorm_split");
 }
 
-// A given as split halves (Ah, Al) [M,K] lda (in halfs); W looked up in the registry by its fp32 pointer.
-// Output: C fp32 (ldc) or, when C == nullptr, the split pair (Ch, Cl).
-int hgl_launch_gemm_f16x3(const void* Ah, const void* Al, int lda, const float* W32, const float* bias, const float* R,
-                          int ldr, float* C, void* Ch, void* Cl, int ldc, int M, int N, int K, int act, hipStream_t st) {
-  return hgl_launch_gemm_f16x3_rmod(Ah, Al, lda, W32, bias, R, ldr, 0, C, Ch, Cl, ldc, M, N, K, act, st);
-}
-
-int hgl_launch_gemm_f16x3_rmod(const void* Ah, const void* Al, int lda, const float* W32, const float* bias, const float* R,
-                               int ldr, int rmod, float* C, void* Ch, void* Cl, int ldc, int M, int N, int K, int act,
-                               hipStream_t st) {
-  return hgl_launch_gemm_f16x3_maps(Ah, Al, lda, nullptr, W32, bias, R, ldr, rmod, nullptr, C, Ch, Cl, ldc, M, N, K, act, st);
-}
-
 namespace {
 
-bool x3_vec4_ok(const float* bias, const float* R, int ldr, const float* C, const void* Ch, const void* Cl, int ldc, int N) {
-  return (N & 3) == 0 && (ldc & 3) == 0 && (!R || (ldr & 3) == 0) && (((size_t)bias | (size_t)R | (size_t)C) & 15) == 0 &&
-         (((size_t)Ch | (size_t)Cl) & 7) == 0;
+// N, ldc, ldr multiples of 4 and 16-byte aligned bases: the write-out can move 16-byte vectors
+bool x3_vec4_ok(const HglGemm& d) {
+  return (d.N & 3) == 0 && (d.ldc & 3) == 0 && (!d.R || (d.ldr & 3) == 0) &&
+         (((size_t)d.bias | (size_t)d.R | (size_t)d.C) & 15) == 0 && (((size_t)d.Ch | (size_t)d.Cl) & 7) == 0;
 }
 
 template <int ACT>
@@ -1148,35 +1136,44 @@ int x3_gm() {
   return gmv;
 }
 
-}  // namespace
+// The LDS-DMA kernel addresses an operand plane with 32-bit byte offsets: a plane of 4 GB or more (CLIP ViT-L/14 fc2 over a
+// group of 16 refs: 526 336 rows x 4096 halves) would fall back to the register-staged kernel at half the rate.  Rows are
+// independent: such a launch runs as row chunks that fit (same tiles, same sums per row).  The rows of one chunk of `rows` rows:
+int x3_row_chunk(const HglGemm& d, int rows) {
+  if (!d.amap && !d.cmap && d.rmod == 0 && (double)rows * d.lda * 2.0 >= 4.0e9 && (double)256 * d.lda * 2.0 < 2.0e9)
+    return (int)(3.9e9 / ((double)d.lda * 2.0)) / 256 * 256;
+  return rows;
+}
 
-int hgl_launch_gemm_f16x3_maps(const void* Ah, const void* Al, int lda, const int* amap, const float* W32, const float* bias,
-                               const float* R, int ldr, int rmod, const int* cmap, float* C, void* Ch, void* Cl, int ldc,
-                               int M, int N, int K, int act, hipStream_t st) {
-  SplitW sw;
-  HGL_REQUIRE(find_split((const void*)W32, &sw), "gemm_f16x3: weight %p has no registered fp16 split", (const void*)W32);
-  HGL_REQUIRE(sw.N == N && sw.K == K, "gemm_f16x3: registered split is [%d,%d], GEMM wants [%d,%d]", sw.N, sw.K, N, K);
-  HGL_REQUIRE(Ah && Al && (C || (Ch && Cl)) && M > 0 && N > 0 && K > 0, "gemm_f16x3: bad arguments");
-  HGL_REQUIRE((K % 64) == 0 && (lda & 7) == 0, "gemm_f16x3: K must be a multiple of 64 and lda of 8 (K=%d lda=%d)", K, lda);
-  // The LDS-DMA kernel addresses an operand plane with 32-bit byte offsets: a plane of 4 GB or more (CLIP ViT-L/14 fc2 over a
-  // group of 16 refs: 526 336 rows x 4096 halves) would fall back to the register-staged kernel at half the rate.  Rows are
-  // independent: run it as row chunks that fit (same tiles, same sums per row).
-  if (!amap && !cmap && rmod == 0 && (double)M * lda * 2.0 >= 4.0e9 && (double)256 * lda * 2.0 < 2.0e9) {
-    const int chunk = (int)(3.9e9 / ((double)lda * 2.0)) / 256 * 256;
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-      const int mc = M - m0 < chunk ? M - m0 : chunk;
-      HGL_TRY(hgl_launch_gemm_f16x3_maps((const _Float16*)Ah + (long long)m0 * lda, (const _Float16*)Al + (long long)m0 * lda, lda,
-                                         nullptr, W32, bias, R ? R + (long long)m0 * ldr : nullptr, ldr, 0, nullptr,
-                                         C ? C + (long long)m0 * ldc : nullptr, Ch ? (_Float16*)Ch + (long long)m0 * ldc : nullptr,
-                                         Cl ? (_Float16*)Cl + (long long)m0 * ldc : nullptr, ldc, mc, N, K, act, st));
-    }
-    return HGL_OK;
-  }
+// the tiling of ONE launch over `rows` rows of d (hgl_gemm_f16x3_select pins it; both tilings accumulate in the same order and
+// give bit-identical results)
+int x3_kind(const HglGemm& d, int rows) {
+  // the LDS-DMA kernel addresses the operands with 32-bit byte offsets from the plane bases and writes 16-byte vectors
+  const bool small_offsets = (double)rows * d.lda * (d.amap ? 4.0 : 2.0) < 4.0e9 && (double)d.N * d.K * 2.0 < 4.0e9;   // gathered rows: <= 2M
+  if (!small_offsets || !x3_vec4_ok(d)) return HGL_X3_V1;
+  // a row-modulo residual (positional table) of a few MB stays in L2: it does not cost what a streamed residual costs
+  // (decoder k|v|q projection, 262144 x 384 x 256 with a 6 MB table: ping-pong 233 us, register-staged 308 -- the model said 346 / 302)
+  const bool streamed_r = d.R != nullptr && (d.rmod == 0 || (double)d.rmod * d.N * 4.0 > 8.0e6);
+  return g_x3_kernel >= 0 ? g_x3_kernel : pick_x3_kernel(rows, d.N, d.K, streamed_r);
+}
+
+// launches that cannot fill the 256 CUs once (GEM at 785 rows, text encoder: a 128x128 tile per CU is latency-bound
+// when run alone) are accounted separately from the throughput-bound ones
+int x3_prof_class(int M, int N, int kind) {
+  const long long few_tiles = (long long)((M + 127) / 128) * ((N + 127) / 128);
+  return few_tiles < 256 ? HGL_PROF_GEMM_X3_FEW : kind == HGL_X3_V1 ? HGL_PROF_GEMM_X3 : HGL_PROF_GEMM_X3G;
+}
+
+// the tilings' arguments for rows [m0, m0 + m) of d: through the maps when there are any (their entries are absolute rows), by
+// pointer offset otherwise
+Args x3_args(const HglGemm& d, const SplitW& sw, int m0, int m) {
+  const long long ao = d.amap ? 0 : (long long)m0 * d.lda, ro = d.cmap ? 0 : (long long)m0 * d.ldr, co = d.cmap ? 0 : (long long)m0 * d.ldc;
   Args g;
-  g.Ah = (const _Float16*)Ah; g.Al = (const _Float16*)Al; g.Wh = sw.hi; g.Wl = sw.lo;
-  g.bias = bias; g.R = R; g.C = C; g.Ch = (_Float16*)Ch; g.Cl = (_Float16*)Cl;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = K; g.ldr = ldr; g.ldc = ldc;
-  g.rmod = rmod; g.amap = amap; g.cmap = cmap;
+  g.Ah = (const _Float16*)d.Ah + ao; g.Al = (const _Float16*)d.Al + ao; g.Wh = sw.hi; g.Wl = sw.lo;
+  g.bias = d.bias; g.R = d.R ? d.R + ro : nullptr; g.C = d.C ? d.C + co : nullptr;
+  g.Ch = d.Ch ? (_Float16*)d.Ch + co : nullptr; g.Cl = d.Cl ? (_Float16*)d.Cl + co : nullptr;
+  g.M = m; g.N = d.N; g.K = d.K; g.lda = d.lda; g.ldw = d.K; g.ldr = d.ldr; g.ldc = d.ldc;
+  g.rmod = d.rmod; g.amap = d.amap ? d.amap + m0 : nullptr; g.cmap = d.cmap ? d.cmap + m0 : nullptr;
   g.rp_p = g.rp_t = 0;
   {
     // The decoder's k | v | q projections add a positional table of rmod rows to P batches of rmod rows: in row order an
@@ -1184,9 +1181,9 @@ int hgl_launch_gemm_f16x3_maps(const void* Ah, const void* Al, int lda, const in
     // tile -- as many bytes as the A operand itself (profiles/r05b_decoder_traffic.json: 18.8 MB fetched per prompt for
     // 8.4 MB of operands).  HGL_X3_RPERM=0 keeps the row order.
     static const int rperm = HGL_DIAG_SWITCH("HGL_X3_RPERM", 1);
-    if (rperm && R && rmod > 0 && (rmod % 256) == 0 && (M % rmod) == 0 && M / rmod > 1 && !amap && !cmap) {
-      g.rp_p = M / rmod;
-      g.rp_t = rmod / 256;
+    if (rperm && d.R && d.rmod > 0 && (d.rmod % 256) == 0 && (m % d.rmod) == 0 && m / d.rmod > 1 && !d.amap && !d.cmap) {
+      g.rp_p = m / d.rmod;
+      g.rp_t = d.rmod / 256;
     }
   }
   g.part = nullptr; g.ksplit = 1;
@@ -1195,114 +1192,68 @@ int hgl_launch_gemm_f16x3_maps(const void* Ah, const void* Al, int lda, const in
   g.one_term = hgl_split_terms() == 1 ? 1 : 0;
   if (g.one_term) g.Cl = nullptr;   // a split output is its hi plane only
   g.gm = x3_gm();
-  g.vec4 = x3_vec4_ok(bias, R, ldr, C, Ch, Cl, ldc, N) ? 1 : 0;
-  // kernel selection (hgl_gemm_f16x3_select); both tilings accumulate in the same order
-  // and give bit-identical results
-  if (g_x3_kernel == -2) {
-    g_x3_kernel = -1;      // automatic (the cost model); hgl_gemm_f16x3_select() pins a tiling
-  }
-  // the LDS-DMA kernel addresses the operands with 32-bit byte offsets from the plane bases and writes 16-byte vectors
-  const bool small_offsets = (double)M * lda * (amap ? 4.0 : 2.0) < 4.0e9 && (double)N * K * 2.0 < 4.0e9;   // gathered rows: <= 2M
-  // a row-modulo residual (positional table) of a few MB stays in L2: it does not cost what a streamed residual costs
-  // (decoder k|v|q projection, 262144 x 384 x 256 with a 6 MB table: ping-pong 233 us, register-staged 308 -- the model said 346 / 302)
-  const bool streamed_r = R != nullptr && (rmod == 0 || (double)rmod * N * 4.0 > 8.0e6);
-  int kind = g_x3_kernel >= 0 ? g_x3_kernel : pick_x3_kernel(M, N, K, streamed_r);
-  if (!small_offsets || !g.vec4) kind = HGL_X3_V1;
-  // launches that cannot fill the 256 CUs once (GEM at 785 rows, text encoder: a 128x128 tile per CU is latency-bound
-  // when run alone) are accounted separately from the throughput-bound ones
-  const long long few_tiles = (long long)((M + 127) / 128) * ((N + 127) / 128);
-  HglProfScope prof(few_tiles < 256 ? HGL_PROF_GEMM_X3_FEW : kind == HGL_X3_V1 ? HGL_PROF_GEMM_X3 : HGL_PROF_GEMM_X3G, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N * (R ? 2 : 1)), st);
-  switch (act) {
-    case HGL_ACT_QUICKGELU: HGL_TRY(launch_x3<HGL_ACT_QUICKGELU>(kind, g, st)); break;
-    case HGL_ACT_GELU: HGL_TRY(launch_x3<HGL_ACT_GELU>(kind, g, st)); break;
-    case HGL_ACT_RELU: HGL_TRY(launch_x3<HGL_ACT_RELU>(kind, g, st)); break;
-    default: HGL_TRY(launch_x3<HGL_ACT_NONE>(kind, g, st)); break;
-  }
-  return hgl_check_launch("gemm_f16x3");
+  g.vec4 = x3_vec4_ok(d) ? 1 : 0;
+  return g;
 }
 
-// fp32-A entry for small M (called from hgl_launch_gemm): true when the GEMM was taken
-bool hgl_gemm_skinny_applicable(const float* W32, int M, int N, int K, int lda, int ldw, int batch, int max_m) {
-  if (!hgl_split_layout() || batch != 1 || M > max_m || (K & 15) || (lda & 3) || ldw != K) return false;
-  SplitW sw;
-  return find_split((const void*)W32, &sw) && sw.N == N && sw.K == K;
+// rows [m0, m0 + m) of d on the tiling x3_kind names, chunk by chunk
+int launch_x3_rows(const HglGemm& d, const SplitW& sw, int m0, int m, hipStream_t st) {
+  const int chunk = x3_row_chunk(d, m);
+  for (int c0 = 0; c0 < m; c0 += chunk) {
+    const int mc = m - c0 < chunk ? m - c0 : chunk;
+    Args g = x3_args(d, sw, m0 + c0, mc);
+    const int kind = x3_kind(d, mc);
+    HglProfScope prof(x3_prof_class(mc, d.N, kind), 2.0 * mc * (double)d.N * d.K,
+                      4.0 * ((double)mc * d.K + (double)d.N * d.K + (double)mc * d.N * (d.R ? 2 : 1)), st);
+    HGL_TRY(hgl_with_act(d.act, [&](auto act) -> int { return launch_x3<decltype(act)::value>(kind, g, st); }));
+    HGL_TRY(hgl_check_launch("gemm_f16x3"));
+  }
+  return HGL_OK;
 }
 
-int hgl_launch_gemm_x3_skinny(const float* A, int lda, const float* W32, const float* bias, const float* R, int ldr,
-                              float* C, int ldc, int M, int N, int K, int act, hipStream_t st) {
-  SplitW sw;
-  HGL_REQUIRE(find_split((const void*)W32, &sw), "gemm_x3_skinny: weight has no registered split");
+int launch_x3_skinny(const HglGemm& d, const SplitW& sw, hipStream_t st) {
   SkinnyArgs g;
-  g.A = A; g.Wh = sw.hi; g.Wl = sw.lo; g.bias = bias; g.R = R; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldr = ldr; g.ldc = ldc;
+  g.A = d.A; g.Wh = sw.hi; g.Wl = sw.lo; g.bias = d.bias; g.R = d.R; g.C = d.C;
+  g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.lda; g.ldr = d.ldr; g.ldc = d.ldc;
   g.out_scale = ldexpf(1.0f, -sw.scale_log2);
-  const dim3 grid((unsigned)((N + 31) / 32), (unsigned)((M + 31) / 32));
-  HglProfScope prof(HGL_PROF_OTHER, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), st);
-#define HGL_SKINNY(ACT_)                                                                                  \
-  do {                                                                                                    \
-    if (one) hipLaunchKernelGGL((gemm_x3_skinny_kernel<ACT_, 1>), grid, dim3(256), 0, st, g);             \
-    else hipLaunchKernelGGL((gemm_x3_skinny_kernel<ACT_, 3>), grid, dim3(256), 0, st, g);                 \
-  } while (0)
+  const dim3 grid((unsigned)((d.N + 31) / 32), (unsigned)((d.M + 31) / 32));
+  HglProfScope prof(HGL_PROF_OTHER, 2.0 * d.M * (double)d.N * d.K, 4.0 * ((double)d.M * d.K + (double)d.N * d.K + (double)d.M * d.N), st);
   const bool one = hgl_split_terms() == 1;
-  switch (act) {
-    case HGL_ACT_QUICKGELU: HGL_SKINNY(HGL_ACT_QUICKGELU); break;
-    case HGL_ACT_GELU: HGL_SKINNY(HGL_ACT_GELU); break;
-    case HGL_ACT_RELU: HGL_SKINNY(HGL_ACT_RELU); break;
-    default: HGL_SKINNY(HGL_ACT_NONE); break;
-  }
-#undef HGL_SKINNY
-  return hgl_check_launch("gemm_x3_skinny");
+  return hgl_with_act(d.act, [&](auto act) -> int {
+    constexpr int ACT = decltype(act)::value;
+    if (one) hipLaunchKernelGGL((gemm_x3_skinny_kernel<ACT, 1>), grid, dim3(256), 0, st, g);
+    else hipLaunchKernelGGL((gemm_x3_skinny_kernel<ACT, 3>), grid, dim3(256), 0, st, g);
+    return hgl_check_launch("gemm_x3_skinny");
+  });
 }
 
 // Split-K on the ping-pong tiling for GEMMs with few output tiles and a long K (SAM's mlp.lin2: 80 tiles,
-// K = 5120): ksplit slices of K run as independent workgroups (grid.y), raw partial sums go through `part`
-// (>= ksplit*M*N floats), splitk_reduce adds them in index order and applies bias / activation / residual.
-int hgl_gemm_f16x3_splitk_factor(int M, int N, int K) {
-  const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256);
-  if ((N & 3) || K < 1024 || tiles * 2 > 256) return 1;
-  int ks = (int)(256 / tiles);
-  if (ks > 4) ks = 4;
-  while (ks > 1 && ((K / 32 / ks) & ~1) < 8) --ks;   // keep every slice at least 8 K tiles long
-  return ks;
-}
-
-int hgl_launch_gemm_f16x3_splitk(const void* Ah, const void* Al, int lda, const int* amap, const float* W32, const float* bias,
-                                 const float* R, int ldr, const int* cmap, float* C, int ldc, int M, int N, int K, int act,
-                                 int ksplit, float* part, size_t part_bytes, hipStream_t st) {
-  SplitW sw;
-  HGL_REQUIRE(find_split((const void*)W32, &sw), "gemm_f16x3_splitk: weight %p has no registered fp16 split", (const void*)W32);
-  HGL_REQUIRE(sw.N == N && sw.K == K && Ah && Al && C && part, "gemm_f16x3_splitk: bad arguments");
-  HGL_REQUIRE(ksplit >= 2 && ksplit <= 8 && (K % 64) == 0 && (lda & 7) == 0 && (N & 3) == 0 && (ldc & 3) == 0 && (ldr & 3) == 0,
+// K = 5120): ksplit slices of K run as independent workgroups (grid.y), raw partial sums go through d.part
+// (>= ksplit*M*N floats), splitk_reduce adds them in index order and applies bias / activation / residual.  Rows [m0, m0 + M) of d.
+int launch_x3_splitk(const HglGemm& d, const SplitW& sw, int m0, int M, int ksplit, hipStream_t st) {
+  const int N = d.N, K = d.K;
+  HGL_REQUIRE(d.Ah && d.Al && d.C && d.part && d.rmod == 0, "gemm_f16x3_splitk: bad arguments");
+  HGL_REQUIRE(ksplit >= 2 && ksplit <= 8 && (K % 64) == 0 && (d.lda & 7) == 0 && (N & 3) == 0 && (d.ldc & 3) == 0 && (d.ldr & 3) == 0,
               "gemm_f16x3_splitk: unsupported shape (K %d, N %d, ksplit %d)", K, N, ksplit);
   HGL_REQUIRE(((K / 32 / ksplit) & ~1) >= 2, "gemm_f16x3_splitk: K too short for %d slices", ksplit);
-  HGL_REQUIRE(part_bytes >= (size_t)ksplit * M * N * sizeof(float), "gemm_f16x3_splitk: partial-sum workspace too small");
-  HGL_REQUIRE(((size_t)part & 15) == 0, "gemm_f16x3_splitk: partial-sum workspace must be 16-byte aligned");
-  HGL_REQUIRE((double)M * lda * (amap ? 4.0 : 2.0) < 4.0e9 && (double)N * K * 2.0 < 4.0e9, "gemm_f16x3_splitk: operand too large");
-  Args g;
-  g.Ah = (const _Float16*)Ah; g.Al = (const _Float16*)Al; g.Wh = sw.hi; g.Wl = sw.lo;
+  HGL_REQUIRE(d.part_bytes >= (size_t)ksplit * M * N * sizeof(float), "gemm_f16x3_splitk: partial-sum workspace too small");
+  HGL_REQUIRE(((size_t)d.part & 15) == 0, "gemm_f16x3_splitk: partial-sum workspace must be 16-byte aligned");
+  HGL_REQUIRE((double)M * d.lda * (d.amap ? 4.0 : 2.0) < 4.0e9 && (double)N * K * 2.0 < 4.0e9, "gemm_f16x3_splitk: operand too large");
+  const Args out = x3_args(d, sw, m0, M);      // where the reduce pass reads the residual and writes
+  Args g = out;                                // the slices: raw partial sums [ksplit][M][N], no epilogue
   g.bias = nullptr; g.R = nullptr; g.C = nullptr; g.Ch = nullptr; g.Cl = nullptr;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = K; g.ldr = 0; g.ldc = N;
-  g.rmod = 0; g.rp_p = g.rp_t = 0; g.amap = amap; g.cmap = nullptr; g.part = part; g.ksplit = ksplit; g.vec4 = 1;
-  g.out_scale = ldexpf(1.0f, -sw.scale_log2);
-  g.lo_zero = x3_two_terms(sw) ? 1 : 0;
-  g.one_term = hgl_split_terms() == 1 ? 1 : 0;
-  g.gm = 8;
-  {
-    const long long few_tiles = (long long)((M + 127) / 128) * ((N + 127) / 128);
-    HglProfScope prof(few_tiles < 256 ? HGL_PROF_GEMM_X3_FEW : HGL_PROF_GEMM_X3G, 2.0 * M * (double)N * K,
-                      4.0 * ((double)M * K + (double)N * K + (double)M * N * (R ? 2 : 1)), st);
-    HGL_TRY(launch_x3_p<HGL_ACT_NONE>(g, st));
-    const long long MN4 = (long long)M * N / 4;
-    const unsigned blocks = (unsigned)((MN4 + 255) / 256 > 4096 ? 4096 : (MN4 + 255) / 256);
-#define HGL_SPLITK_REDUCE(ACT_) hipLaunchKernelGGL(splitk_reduce_kernel<ACT_>, dim3(blocks), dim3(256), 0, st, part, ksplit, MN4, N / 4, bias, R, ldr / 4, C, ldc / 4, cmap)
-    switch (act) {
-      case HGL_ACT_QUICKGELU: HGL_SPLITK_REDUCE(HGL_ACT_QUICKGELU); break;
-      case HGL_ACT_GELU: HGL_SPLITK_REDUCE(HGL_ACT_GELU); break;
-      case HGL_ACT_RELU: HGL_SPLITK_REDUCE(HGL_ACT_RELU); break;
-      default: HGL_SPLITK_REDUCE(HGL_ACT_NONE); break;
-    }
-  }
-  return hgl_check_launch("gemm_f16x3_splitk");
+  g.ldr = 0; g.ldc = N; g.cmap = nullptr; g.rp_p = g.rp_t = 0;
+  g.part = d.part; g.ksplit = ksplit; g.vec4 = 1; g.gm = 8;
+  HglProfScope prof(x3_prof_class(M, N, HGL_X3_P), 2.0 * M * (double)N * K,
+                    4.0 * ((double)M * K + (double)N * K + (double)M * N * (d.R ? 2 : 1)), st);
+  HGL_TRY(launch_x3_p<HGL_ACT_NONE>(g, st));
+  const long long MN4 = (long long)M * N / 4;
+  const unsigned blocks = (unsigned)((MN4 + 255) / 256 > 4096 ? 4096 : (MN4 + 255) / 256);
+  return hgl_with_act(d.act, [&](auto act) -> int {
+    hipLaunchKernelGGL(splitk_reduce_kernel<decltype(act)::value>, dim3(blocks), dim3(256), 0, st, d.part, ksplit, MN4, N / 4,
+                       d.bias, out.R, d.ldr / 4, out.C, d.ldc / 4, out.cmap);
+    return hgl_check_launch("gemm_f16x3_splitk");
+  });
 }
 
 // A GEMM whose LAST round of the persistent 256 x 256 tiling is mostly empty (CLIP's out / fc2 over a group of 16 refs: 2364
@@ -1311,7 +1262,7 @@ int hgl_launch_gemm_f16x3_splitk(const void* Ah, const void* Al, int lda, const 
 // a tail of a few row tiles that runs split-K over all CUs (the existing split-K path: K slices as grid.y, partial sums through
 // `part`, summed in index order with bias / activation / residual by splitk_reduce_kernel: deterministic).  A tail row's sum
 // is associated differently from a main row's (K slices), as any split-K row's is: equal to fp32 rounding, not bit for bit
-// -- which rows form the tail depends on M alone.  Falls through to the plain launch when the plan does not pay.
+// -- which rows form the tail depends on M alone.  False when the plan does not pay: the plain launch.
 bool x3_tail_plan(int M, int N, int K, bool has_r, size_t part_bytes, int* m_main, int* ksplit) {
   if ((N & 3) || K < 1024 || (K % 64)) return false;      // (K = 768, CLIP's out-projection: measured no gain -- six-K-tile slices cost what the round costs)
   const int ncu = x3_num_cus();
@@ -1339,23 +1290,72 @@ bool x3_tail_plan(int M, int N, int K, bool has_r, size_t part_bytes, int* m_mai
   return true;
 }
 
-int hgl_launch_gemm_f16x3_balanced(const void* Ah, const void* Al, int lda, const int* amap, const float* W32, const float* bias,
-                                   const float* R, int ldr, const int* cmap, float* C, int ldc, int M, int N, int K, int act,
-                                   float* part, size_t part_bytes, hipStream_t st) {
-  int m_main = 0, ks = 1;
-  static const int on = HGL_DIAG_SWITCH("HGL_X3_TAIL", 1);
-  const bool p_kernel = g_x3_kernel < 0 ? pick_x3_kernel(M, N, K, R != nullptr) == HGL_X3_P : g_x3_kernel == HGL_X3_P;
-  if (!on || !C || !part || !p_kernel || (((size_t)part) & 15) || !x3_tail_plan(M, N, K, R != nullptr, part_bytes, &m_main, &ks))
-    return hgl_launch_gemm_f16x3_maps(Ah, Al, lda, amap, W32, bias, R, ldr, 0, cmap, C, nullptr, nullptr, ldc, M, N, K, act, st);
-  HGL_TRY(hgl_launch_gemm_f16x3_maps(Ah, Al, lda, amap, W32, bias, R, ldr, 0, cmap, C, nullptr, nullptr, ldc, m_main, N, K, act, st));
-  const int m_tail = M - m_main;
-  // the tail's rows: through the maps when there are any (their entries are absolute rows), by pointer offset otherwise
-  const _Float16* th = (const _Float16*)Ah + (amap ? 0 : (long long)m_main * lda);
-  const _Float16* tl = (const _Float16*)Al + (amap ? 0 : (long long)m_main * lda);
-  const float* tr = R ? R + (cmap ? 0 : (long long)m_main * ldr) : nullptr;
-  float* tc = C + (cmap ? 0 : (long long)m_main * ldc);
-  return hgl_launch_gemm_f16x3_splitk(th, tl, lda, amap ? amap + m_main : nullptr, W32, bias, tr, ldr, cmap ? cmap + m_main : nullptr,
-                                      tc, ldc, m_tail, N, K, act, ks, part, part_bytes, st);
+// everything that is decided about one GEMM, once: the route, the ONE lookup of the weight's split, the row-balanced cut
+struct GemmPlan {
+  HglGemmRoute route = HGL_GEMM_NONE;
+  SplitW sw;                  // every route but HGL_GEMM_NONE / HGL_GEMM_F32
+  int m_main = 0, ks = 1;     // HGL_GEMM_X3_BALANCED: rows of the whole rounds, slices of the tail
+};
+
+GemmPlan gemm_plan(const HglGemm& d) {
+  GemmPlan p;
+  if (d.A) {
+    // split modes, small M, registered weight: the split-fp16 small-tile kernel
+    const bool skinny = hgl_split_layout() && d.batch == 1 && d.M <= d.skinny_max_m && !(d.K & 15) && !(d.lda & 3) && d.ldw == d.K &&
+                        find_split((const void*)d.W, &p.sw) && p.sw.N == d.N && p.sw.K == d.K;
+    p.route = skinny ? HGL_GEMM_SKINNY : HGL_GEMM_F32;
+  } else if (d.Ah && find_split((const void*)d.W, &p.sw)) {
+    static const int tail_on = HGL_DIAG_SWITCH("HGL_X3_TAIL", 1);
+    const int kind = x3_kind(d, x3_row_chunk(d, d.M));   // (planes of 4 GB and more: the first chunk's)
+    if (d.ksplit > 1) p.route = HGL_GEMM_X3_SPLITK;
+    else if (kind == HGL_X3_P && tail_on && d.C && d.part && !((size_t)d.part & 15) && d.rmod == 0 &&
+             x3_tail_plan(d.M, d.N, d.K, d.R != nullptr, d.part_bytes, &p.m_main, &p.ks))
+      p.route = HGL_GEMM_X3_BALANCED;
+    else p.route = kind == HGL_X3_P ? HGL_GEMM_X3_PINGPONG : HGL_GEMM_X3_STAGED;
+  }
+  return p;
+}
+
+}  // namespace
+
+int hgl_gemm_f16x3_splitk_factor(int M, int N, int K) {
+  const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256);
+  if ((N & 3) || K < 1024 || tiles * 2 > 256) return 1;
+  int ks = (int)(256 / tiles);
+  if (ks > 4) ks = 4;
+  while (ks > 1 && ((K / 32 / ks) & ~1) < 8) --ks;   // keep every slice at least 8 K tiles long
+  return ks;
+}
+
+HglGemmRoute hgl_gemm_route(const HglGemm& d) { return gemm_plan(d).route; }
+
+int hgl_launch_gemm(const HglGemm& d, hipStream_t st) {
+  const int M = d.M, N = d.N, K = d.K;
+  HGL_REQUIRE(d.W && (d.A ? d.C != nullptr : d.Ah != nullptr), "gemm: null operand");
+  if (d.A) {
+    HGL_REQUIRE(M > 0 && N > 0 && K > 0 && d.batch > 0, "gemm: bad shape M=%d N=%d K=%d batch=%d", M, N, K, d.batch);
+    HGL_REQUIRE((K & 3) == 0 && (d.lda & 3) == 0 && (d.ldw & 3) == 0, "gemm: K, lda, ldw must be multiples of 4 (K=%d lda=%d ldw=%d)", K, d.lda, d.ldw);
+    HGL_REQUIRE(((uintptr_t)d.A & 15) == 0 && ((uintptr_t)d.W & 15) == 0, "gemm: A and W must be 16-byte aligned");
+    HGL_REQUIRE((d.sA & 3) == 0 && (d.sW & 3) == 0, "gemm: batch strides of A and W must be multiples of 4");
+    HGL_REQUIRE(d.act >= 0 && d.act <= 3, "gemm: bad activation %d", d.act);
+  }
+  const GemmPlan p = gemm_plan(d);
+  switch (p.route) {
+    case HGL_GEMM_F32: return hgl_launch_gemm_f32_tiles(d, st);
+    case HGL_GEMM_SKINNY: return launch_x3_skinny(d, p.sw, st);
+    case HGL_GEMM_NONE:
+      hgl_set_error("gemm_f16x3: weight %p has no registered fp16 split", (const void*)d.W);
+      return HGL_EINVAL;
+    default: break;
+  }
+  // A given as split halves (Ah, Al) [M, K], lda in halfs; output: C fp32 or, when C == nullptr, the split pair (Ch, Cl)
+  HGL_REQUIRE(p.sw.N == N && p.sw.K == K, "gemm_f16x3: registered split is [%d,%d], GEMM wants [%d,%d]", p.sw.N, p.sw.K, N, K);
+  if (p.route == HGL_GEMM_X3_SPLITK) return launch_x3_splitk(d, p.sw, 0, M, d.ksplit, st);
+  HGL_REQUIRE(d.Ah && d.Al && (d.C || (d.Ch && d.Cl)) && M > 0 && N > 0 && K > 0, "gemm_f16x3: bad arguments");
+  HGL_REQUIRE((K % 64) == 0 && (d.lda & 7) == 0, "gemm_f16x3: K must be a multiple of 64 and lda of 8 (K=%d lda=%d)", K, d.lda);
+  if (p.route != HGL_GEMM_X3_BALANCED) return launch_x3_rows(d, p.sw, 0, M, st);
+  HGL_TRY(launch_x3_rows(d, p.sw, 0, p.m_main, st));
+  return launch_x3_splitk(d, p.sw, p.m_main, M - p.m_main, p.ks, st);
 }
 
 extern "C" {
@@ -1429,10 +1429,10 @@ int hgl_gemm_f16x3(const float* A, const float* W, const float* bias, const floa
   // scratch beyond the split A: room for the partial sums of the row-balanced launch (whole rounds + split-K tail), which the
   // model code uses for its residual GEMMs; without it, the plain launch
   const size_t a_bytes = hgl_align_up((size_t)M * K * 4, 256);
-  if (scratch_bytes > a_bytes + 256)
-    return hgl_launch_gemm_f16x3_balanced(ah, al, K, nullptr, W, bias, R, N, nullptr, C, N, M, N, K, act,
-                                          (float*)((char*)scratch + a_bytes), scratch_bytes - a_bytes, st);
-  return hgl_launch_gemm_f16x3(ah, al, K, W, bias, R, N, C, nullptr, nullptr, N, M, N, K, act, st);
+  HglGemm d = hgl_gemm_planes(ah, al, W, bias, C, M, N, K, act, R);
+  d.ldr = N;
+  if (scratch_bytes > a_bytes + 256) d.part = (float*)((char*)scratch + a_bytes), d.part_bytes = scratch_bytes - a_bytes;
+  return hgl_launch_gemm(d, st);
 }
 
 }  // extern "C"

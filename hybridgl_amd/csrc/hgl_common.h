@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <math.h>
 #include <atomic>
+#include <type_traits>
 #include "../../include/hybridgl.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -165,12 +166,97 @@ struct HglArena {
 };
 
 // ---- internal launchers (each returns HGL_*) -------------------------------
-int hgl_launch_gemm(const float* A, const float* W, const float* bias, const float* R, float* C,
-                    int M, int N, int K, int lda, int ldw, int ldr, int ldc, int batch,
-                    long long sA, long long sW, long long sR, long long sC, int act,
-                    hipStream_t st);
 int hgl_launch_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int D,
                          float eps, hipStream_t st);
+// ---- GEMM: one call descriptor, one route, one launch (gemm_f16x3.hip; the fp32 tile kernel lives in gemm.hip) ----
+// C = act(A @ W^T + bias) + R.  A caller says WHAT product it wants in named fields; hgl_gemm_route says WHICH kernel family
+// serves it.
+struct HglGemm {
+  int M = 0, N = 0, K = 0, act = HGL_ACT_NONE;
+  // A, one of two forms.  fp32 rows of lda floats, `batch` matrices sA apart ...
+  const float* A = nullptr;
+  int lda = 0, batch = 1;
+  long long sA = 0;
+  // ... or the fp16 hi | lo planes (lda in halfs; amap: row m is read from row amap[m])
+  const void *Ah = nullptr, *Al = nullptr;
+  const int* amap = nullptr;
+  // the weight [N, K] as fp32 (rows of ldw floats, batch stride sW); the pointer is also the key of its registered fp16 split
+  const float* W = nullptr;
+  int ldw = 0;
+  long long sW = 0;
+  const float* bias = nullptr;
+  // residual (may alias the output): rows of ldr floats, batch stride sR; rmod > 0: row m adds row m % rmod (a table shared
+  // by every batch of rmod rows)
+  const float* R = nullptr;
+  int ldr = 0, rmod = 0;
+  long long sR = 0;
+  // output: fp32 C, or (C == nullptr, plane-form A) the fp16 hi | lo pair; rows of ldc, batch stride sC; cmap: output and
+  // residual row m live at row cmap[m]
+  float* C = nullptr;
+  void *Ch = nullptr, *Cl = nullptr;
+  int ldc = 0;
+  long long sC = 0;
+  const int* cmap = nullptr;
+  // plane-form A: scratch for partial sums (16-byte aligned).  ksplit > 1: split-K in that many slices (needs ksplit * M * N
+  // floats); ksplit 0 / 1: the launcher may cut the rows into whole rounds of the persistent tiling + a split-K tail
+  float* part = nullptr;
+  size_t part_bytes = 0;
+  int ksplit = 0;
+  // fp32 A with a registered weight in the split-fp16 modes: up to this many rows take the small-tile kernel
+  int skinny_max_m = 1024;
+};
+// a dense nn.Linear on fp32 rows: C [M, N] = act(A [M, K] W^T + bias) (+ R, rows of N floats)
+inline HglGemm hgl_gemm_linear(const float* A, const float* W, const float* bias, float* C, int M, int N, int K,
+                               int act = HGL_ACT_NONE, const float* R = nullptr) {
+  HglGemm d;
+  d.M = M, d.N = N, d.K = K, d.act = act;
+  d.A = A, d.lda = K, d.W = W, d.ldw = K, d.bias = bias;
+  d.R = R, d.ldr = R ? N : 0, d.C = C, d.ldc = N;
+  return d;
+}
+// the same with A as dense fp16 hi | lo planes (rows of K halfs) and a registered W
+inline HglGemm hgl_gemm_planes(const void* Ah, const void* Al, const float* W, const float* bias, float* C, int M, int N, int K,
+                               int act = HGL_ACT_NONE, const float* R = nullptr) {
+  HglGemm d = hgl_gemm_linear(nullptr, W, bias, C, M, N, K, act, R);
+  d.Ah = Ah, d.Al = Al;
+  return d;
+}
+// planes in, planes out: the write-out splits (the next GEMM or the attention reads the pair)
+inline HglGemm hgl_gemm_planes_split(const void* Ah, const void* Al, const float* W, const float* bias, void* Ch, void* Cl, int M,
+                                     int N, int K, int act = HGL_ACT_NONE) {
+  HglGemm d = hgl_gemm_planes(Ah, Al, W, bias, nullptr, M, N, K, act);
+  d.Ch = Ch, d.Cl = Cl;
+  return d;
+}
+// The kernel family that serves a descriptor.  A pure function of the descriptor, the precision state, the split-weight
+// registry, hgl_gemm_f16x3_select and the switches; it enqueues nothing and sets no error.
+enum HglGemmRoute {
+  HGL_GEMM_NONE = 0,       // no kernel serves the descriptor (no operand; plane-form A without a registered weight)
+  // fp32 A
+  HGL_GEMM_F32,            // the fp32 MFMA tile kernel (gemm.hip)
+  HGL_GEMM_SKINNY,         // split modes, registered weight, one batch of <= skinny_max_m rows: 32 x 32 tiles, K over four waves
+  // A as fp16 hi | lo planes
+  HGL_GEMM_X3_STAGED,      // register-staged 128 x 128 tiles: few tiles, any N / leading dimensions, planes of 4 GB and more
+  HGL_GEMM_X3_PINGPONG,    // persistent 256 x 256 ping-pong tiles (planes of 4 GB and more: in row chunks, named by the first)
+  HGL_GEMM_X3_BALANCED,    // ping-pong over the rows that fill whole rounds + split-K over the last row tiles
+  HGL_GEMM_X3_SPLITK       // ksplit > 1: K slices of the ping-pong tiling + the reduce pass
+};
+HglGemmRoute hgl_gemm_route(const HglGemm& d);
+// validates (the requirements of the family the route chose), looks the weight up once and launches; "no kernel serves the
+// descriptor" is an error
+int hgl_launch_gemm(const HglGemm& d, hipStream_t st);
+// between gemm_f16x3.hip and gemm.hip only: the fp32 tile launch of a validated descriptor
+int hgl_launch_gemm_f32_tiles(const HglGemm& d, hipStream_t st);
+// the activation of an epilogue as a compile-time constant: f(std::integral_constant<int, HGL_ACT_*>{}) -> an hgl status
+template <class F>
+inline int hgl_with_act(int act, F&& f) {
+  switch (act) {
+    case HGL_ACT_QUICKGELU: return f(std::integral_constant<int, HGL_ACT_QUICKGELU>{});
+    case HGL_ACT_GELU: return f(std::integral_constant<int, HGL_ACT_GELU>{});
+    case HGL_ACT_RELU: return f(std::integral_constant<int, HGL_ACT_RELU>{});
+    default: return f(std::integral_constant<int, HGL_ACT_NONE>{});
+  }
+}
 // ---- attention: one call descriptor, one route, one launch (attention.hip; the plane-form kernels live in attention_ps.hip) ----
 // A caller says WHAT attention it wants in named fields; hgl_attention_route says WHICH kernel family serves it.
 struct HglAttn {
@@ -389,24 +475,7 @@ int hgl_launch_layernorm_split(const float* x, const float* w, const float* b, v
                                float eps, hipStream_t st);
 int hgl_launch_layernorm_split_maps(const float* x, const float* w, const float* b, void* hi, void* lo, int rows, int D,
                                     float eps, const int* smap, const int* dmap, hipStream_t st);
-bool hgl_gemm_skinny_applicable(const float* W32, int M, int N, int K, int lda, int ldw, int batch, int max_m = 1024);
-int hgl_launch_gemm_x3_skinny(const float* A, int lda, const float* W32, const float* bias, const float* R, int ldr,
-                              float* C, int ldc, int M, int N, int K, int act, hipStream_t st);
 int hgl_gemm_f16x3_splitk_factor(int M, int N, int K);
-int hgl_launch_gemm_f16x3_splitk(const void* Ah, const void* Al, int lda, const int* amap, const float* W32, const float* bias,
-                                 const float* R, int ldr, const int* cmap, float* C, int ldc, int M, int N, int K, int act,
-                                 int ksplit, float* part, size_t part_bytes, hipStream_t st);
-// row-balanced launch: whole rounds of the persistent tiling + a split-K tail (gemm_f16x3.hip); `part`: scratch for the tail's partial sums
-int hgl_launch_gemm_f16x3_balanced(const void* Ah, const void* Al, int lda, const int* amap, const float* W32, const float* bias,
-                                   const float* R, int ldr, const int* cmap, float* C, int ldc, int M, int N, int K, int act,
-                                   float* part, size_t part_bytes, hipStream_t st);
-int hgl_launch_gemm_f16x3_maps(const void* Ah, const void* Al, int lda, const int* amap, const float* W32, const float* bias,
-                               const float* R, int ldr, int rmod, const int* cmap, float* C, void* Ch, void* Cl, int ldc,
-                               int M, int N, int K, int act, hipStream_t st);
-int hgl_launch_gemm_f16x3_rmod(const void* Ah, const void* Al, int lda, const float* W32, const float* bias, const float* R,
-                               int ldr, int rmod, float* C, void* Ch, void* Cl, int ldc, int M, int N, int K, int act, hipStream_t st);
-int hgl_launch_gemm_f16x3(const void* Ah, const void* Al, int lda, const float* W32, const float* bias, const float* R,
-                          int ldr, float* C, void* Ch, void* Cl, int ldc, int M, int N, int K, int act, hipStream_t st);
 int hgl_launch_win_partition_split(const float* H, int g, int ws, int nw, int D, void* hi, void* lo, hipStream_t st);
 // true when the split-fp16 path applies to a GEMM with this weight and reduction length
 static inline bool hgl_use_x3(const float* W, int K) { return hgl_split_layout() && (K % 64) == 0 && hgl_has_split_weight(W); }

@@ -151,10 +151,11 @@ int enc_attention(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& 
     if (hd == 80 || hd == 64) {
       HGL_TRY(hgl_launch_relpos_direct(p.QKV, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
     } else {  // generic head dims: q . rel_pos[r] for every r as a batched GEMM, then gathered per (q,k)
-      HGL_TRY(hgl_launch_gemm(p.QKV, b.rel_pos_h, nullptr, nullptr, p.Th, M, L, hd, 3 * D, hd, 0, L, heads, hd, 0,
-                              0, (long long)M * L, HGL_ACT_NONE, st));
-      HGL_TRY(hgl_launch_gemm(p.QKV, b.rel_pos_w, nullptr, nullptr, p.Tw, M, L, hd, 3 * D, hd, 0, L, heads, hd, 0,
-                              0, (long long)M * L, HGL_ACT_NONE, st));
+      HglGemm rel = hgl_gemm_linear(p.QKV, b.rel_pos_h, nullptr, p.Th, M, L, hd);    // one batch per head: q's columns of that head
+      rel.lda = 3 * D, rel.batch = heads, rel.sA = hd, rel.sC = (long long)M * L;
+      HGL_TRY(hgl_launch_gemm(rel, st));
+      rel.W = b.rel_pos_w, rel.C = p.Tw;
+      HGL_TRY(hgl_launch_gemm(rel, st));
       HGL_TRY(hgl_launch_relpos_gather(p.Th, B, heads, S, size, L, 0, p.relh, st));
       HGL_TRY(hgl_launch_relpos_gather(p.Tw, B, heads, S, size, L, 1, p.relw, st));
     }
@@ -183,40 +184,37 @@ int enc_block_x3(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r
   // in-projection, (fp32 qkv | planes) x (every row | the real tokens gathered: a padded row of qkv is the bias).  Planes:
   // q | k | v as fp16 hi / lo planes (the write-out splits; same bytes as the fp32 tensor) for the attention kernel that stages
   // them by LDS-DMA without converting (attention_ps.hip)
-  float* const Cf = r.planes ? nullptr : p.QKV;
-  uint16_t* const Ch = r.planes ? s.Qh : nullptr;
-  uint16_t* const Cl = r.planes ? s.Ql : nullptr;
+  HglGemm qkv = r.planes ? hgl_gemm_planes_split(s.Ah, s.Al, b.qkv_w, b.qkv_b, s.Qh, s.Ql, M, 3 * D, D)
+                         : hgl_gemm_planes(s.Ah, s.Al, b.qkv_w, b.qkv_b, p.QKV, M, 3 * D, D);
   if (r.gather) {
     HGL_TRY(r.planes ? hgl_launch_fill_rows_split(s.Qh, s.Ql, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st)
                      : hgl_launch_fill_rows(p.QKV, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st));
-    HGL_TRY(hgl_launch_gemm_f16x3_maps(s.Ah, s.Al, D, p.pad_of, b.qkv_w, b.qkv_b, nullptr, 0, 0, p.pad_of, Cf, Ch, Cl, 3 * D, T,
-                                       3 * D, D, HGL_ACT_NONE, st));
-  } else {
-    HGL_TRY(hgl_launch_gemm_f16x3(s.Ah, s.Al, D, b.qkv_w, b.qkv_b, nullptr, 0, Cf, Ch, Cl, 3 * D, M, 3 * D, D, HGL_ACT_NONE, st));
+    qkv.M = T, qkv.amap = qkv.cmap = p.pad_of;
   }
+  HGL_TRY(hgl_launch_gemm(qkv, st));
   HGL_TRY(enc_attention(b, p, r, st));
   const size_t qkv_bytes = (size_t)M * 3 * D * sizeof(float);     // q, k, v are dead after the attention
   if (ws > 0 && !r.gather) {
-    HGL_TRY(hgl_launch_gemm_f16x3(s.Ah, s.Al, D, b.proj_w, b.proj_b, nullptr, 0, p.P, nullptr, nullptr, D, M, D, D, HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(s.Ah, s.Al, b.proj_w, b.proj_b, p.P, M, D, D), st));
     for (int i = 0; i < p.nb; ++i)
       HGL_TRY(hgl_launch_win_unpartition_add(p.X + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.P + (size_t)i * r.M1 * D, st));
   } else {
     // windows: the projection of the real tokens only, written straight back to token order with the residual added
     // (window_unpartition + shortcut, image_encoder.py:178-180); global: every row where it is
-    HGL_TRY(hgl_launch_gemm_f16x3_balanced(s.Ah, s.Al, D, r.gather ? p.pad_of : nullptr, b.proj_w, b.proj_b, p.X, D,
-                                           r.gather ? p.tok_of : nullptr, p.X, D, T, D, D, HGL_ACT_NONE, p.QKV, qkv_bytes, st));
+    HglGemm proj = hgl_gemm_planes(s.Ah, s.Al, b.proj_w, b.proj_b, p.X, T, D, D, HGL_ACT_NONE, p.X);
+    if (r.gather) proj.amap = p.pad_of, proj.cmap = p.tok_of;
+    proj.part = p.QKV, proj.part_bytes = qkv_bytes;
+    HGL_TRY(hgl_launch_gemm(proj, st));
   }
   HGL_TRY(hgl_launch_layernorm_split(p.X, b.norm2_w, b.norm2_b, s.Hh, s.Hl, T, D, 1e-6f, st));
-  HGL_TRY(hgl_launch_gemm_f16x3(s.Hh, s.Hl, D, b.lin1_w, b.lin1_b, nullptr, 0, nullptr, s.Fh, s.Fl, 4 * D, T, 4 * D, D,
-                                HGL_ACT_GELU, st));
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_planes_split(s.Hh, s.Hl, b.lin1_w, b.lin1_b, s.Fh, s.Fl, T, 4 * D, D, HGL_ACT_GELU), st));
   // mlp.lin2: few output tiles, K = 4D -> split-K over the idle CUs; the partial sums borrow the qkv buffer
   static const int splitk_on = HGL_DIAG_SWITCH("HGL_SAM_SPLITK", 1);   // 0 disables (A/B timing)
   const int ks = splitk_on ? hgl_gemm_f16x3_splitk_factor(T, D, 4 * D) : 1;
-  if (ks > 1 && (size_t)ks * T * D * sizeof(float) <= qkv_bytes)
-    return hgl_launch_gemm_f16x3_splitk(s.Fh, s.Fl, 4 * D, nullptr, b.lin2_w, b.lin2_b, p.X, D, nullptr, p.X, D, T, D, 4 * D,
-                                        HGL_ACT_NONE, ks, p.QKV, qkv_bytes, st);
-  return hgl_launch_gemm_f16x3_balanced(s.Fh, s.Fl, 4 * D, nullptr, b.lin2_w, b.lin2_b, p.X, D, nullptr, p.X, D, T, D, 4 * D,
-                                        HGL_ACT_NONE, p.QKV, qkv_bytes, st);
+  HglGemm lin2 = hgl_gemm_planes(s.Fh, s.Fl, b.lin2_w, b.lin2_b, p.X, T, D, 4 * D, HGL_ACT_NONE, p.X);
+  lin2.part = p.QKV, lin2.part_bytes = qkv_bytes;
+  if (ks > 1 && (size_t)ks * T * D * sizeof(float) <= qkv_bytes) lin2.ksplit = ks;   // else: whole rounds + a tail where that pays
+  return hgl_launch_gemm(lin2, st);
 }
 
 // the block on the fp32 kernels
@@ -226,23 +224,18 @@ int enc_block_f32(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& 
   if (ws > 0)
     for (int i = 0; i < p.nb; ++i)
       HGL_TRY(hgl_launch_win_partition(p.H + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.Hw + (size_t)i * r.M1 * D, st));
-  HGL_TRY(hgl_launch_gemm(ws > 0 ? p.Hw : p.H, b.qkv_w, b.qkv_b, nullptr, p.QKV, M, 3 * D, D, D, D, 0, 3 * D, 1, 0, 0, 0, 0,
-                          HGL_ACT_NONE, st));
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(ws > 0 ? p.Hw : p.H, b.qkv_w, b.qkv_b, p.QKV, M, 3 * D, D), st));
   HGL_TRY(enc_attention(b, p, r, st));
   if (ws > 0) {
-    HGL_TRY(hgl_launch_gemm(p.O, b.proj_w, b.proj_b, nullptr, p.P, M, D, D, D, D, 0, D, 1, 0, 0, 0, 0,
-                            HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.O, b.proj_w, b.proj_b, p.P, M, D, D), st));
     for (int i = 0; i < p.nb; ++i)
       HGL_TRY(hgl_launch_win_unpartition_add(p.X + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.P + (size_t)i * r.M1 * D, st));
   } else {
-    HGL_TRY(hgl_launch_gemm(p.O, b.proj_w, b.proj_b, p.X, p.X, T, D, D, D, D, D, D, 1, 0, 0, 0, 0,
-                            HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.O, b.proj_w, b.proj_b, p.X, T, D, D, HGL_ACT_NONE, p.X), st));
   }
   HGL_TRY(hgl_launch_layernorm(p.X, b.norm2_w, b.norm2_b, p.H, T, D, 1e-6f, st));
-  HGL_TRY(hgl_launch_gemm(p.H, b.lin1_w, b.lin1_b, nullptr, p.F, T, 4 * D, D, D, D, 0, 4 * D, 1, 0, 0, 0, 0,
-                          HGL_ACT_GELU, st));
-  return hgl_launch_gemm(p.F, b.lin2_w, b.lin2_b, p.X, p.X, T, D, 4 * D, 4 * D, 4 * D, D, D, 1, 0, 0, 0, 0,
-                         HGL_ACT_NONE, st);
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.H, b.lin1_w, b.lin1_b, p.F, T, 4 * D, D, HGL_ACT_GELU), st));
+  return hgl_launch_gemm(hgl_gemm_linear(p.F, b.lin2_w, b.lin2_b, p.X, T, D, 4 * D, HGL_ACT_NONE, p.X), st);
 }
 
 int enc_block(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPlan& p, hipStream_t st) {
@@ -314,23 +307,31 @@ bool valid_dec(const HglSamDecoderW* w) {
   return true;
 }
 
-inline int lin(const float* A, int lda, const HglLinearW& l, const float* R, int ldr, float* Cc, int ldc, int M,
-               int N, int K, int act, hipStream_t st) {
+inline HglGemm lin_desc(const float* A, int lda, const HglLinearW& l, const float* R, int ldr, float* Cc, int ldc, int M,
+                        int N, int K, int act) {
+  HglGemm d = hgl_gemm_linear(A, l.w, l.b, Cc, M, N, K, act, R);
+  d.lda = lda, d.ldr = ldr, d.ldc = ldc;
   // the token side of a large prompt batch (512 prompts: 3584 rows) and the image-side projections shared by all prompts
   // (4096 rows) are still small-tile work: 8 x 116 workgroups of 32 x 32 instead of the fp32 kernel (35 -> 12 us each,
   // 23 launches per decoder call)
-  if (M > 1024 && hgl_gemm_skinny_applicable(l.w, M, N, K, lda, K, 1, 8192))
-    return hgl_launch_gemm_x3_skinny(A, lda, l.w, l.b, R, ldr, Cc, ldc, M, N, K, act, st);
-  return hgl_launch_gemm(A, l.w, l.b, R, Cc, M, N, K, lda, K, ldr, ldc, 1, 0, 0, 0, 0, act, st);
+  d.skinny_max_m = 8192;
+  return d;
+}
+inline int lin(const float* A, int lda, const HglLinearW& l, const float* R, int ldr, float* Cc, int ldc, int M,
+               int N, int K, int act, hipStream_t st) {
+  return hgl_launch_gemm(lin_desc(A, lda, l, R, ldr, Cc, ldc, M, N, K, act), st);
 }
 
 // lin() over the rows of n sets of M rows each (the shared image tokens of n images), every row as lin() over ONE set gives
 // it: the kernel lin() picks for M rows is a small-tile one whose rows do not depend on the row count -> one launch over
 // n * M rows; any other choice (fp32 tiles, whose dispatch looks at M) -> set by set.
 inline int lin_sets(const float* A, int lda, const HglLinearW& l, float* Cc, int ldc, int M, int n, int N, int K, hipStream_t st) {
-  if (n == 1) return lin(A, lda, l, nullptr, 0, Cc, ldc, M, N, K, HGL_ACT_NONE, st);
-  if (hgl_gemm_skinny_applicable(l.w, M, N, K, lda, K, 1, 8192))
-    return hgl_launch_gemm_x3_skinny(A, lda, l.w, l.b, nullptr, 0, Cc, ldc, n * M, N, K, HGL_ACT_NONE, st);
+  HglGemm d = lin_desc(A, lda, l, nullptr, 0, Cc, ldc, M, N, K, HGL_ACT_NONE);
+  if (n == 1) return hgl_launch_gemm(d, st);
+  if (hgl_gemm_route(d) == HGL_GEMM_SKINNY) {
+    d.M = d.skinny_max_m = n * M;   // the row bound held for ONE set
+    return hgl_launch_gemm(d, st);
+  }
   for (int i = 0; i < n; ++i)
     HGL_TRY(lin(A + (size_t)i * M * lda, lda, l, nullptr, 0, Cc + (size_t)i * M * ldc, ldc, M, N, K, HGL_ACT_NONE, st));
   return HGL_OK;
@@ -419,8 +420,9 @@ int dec_attn(const HglSamDecoderW* w, const HglSamAttnW& a, const float* q, bool
   // counts then take the small-tile kernel); batched when a shared residual (stride 0) has to be broadcast
   if (!R || sR == (long long)Nq * C)
     return lin(att, I, a.out, R, C, out, C, B * Nq, C, I, HGL_ACT_NONE, st);
-  return hgl_launch_gemm(att, a.out.w, a.out.b, R, out, Nq, C, I, I, I, C, C, B, (long long)Nq * I, 0, sR,
-                         (long long)Nq * C, HGL_ACT_NONE, st);
+  HglGemm d = hgl_gemm_linear(att, a.out.w, a.out.b, out, Nq, C, I, HGL_ACT_NONE, R);
+  d.batch = B, d.sA = (long long)Nq * I, d.sR = sR, d.sC = (long long)Nq * C;
+  return hgl_launch_gemm(d, st);
 }
 
 // ---- f16x3 path of the decoder's image-token side (M = P*HW rows) -------------------------------------------
@@ -514,12 +516,15 @@ int dec_t2i(const DecRoute& r, const HglSamDecoderW* w, const HglSamAttnW& a, in
   }
   const bool merged = r.merged && !r.raw_t2i, fin = step == 2;
   const int N = fin ? 2 * I : 3 * I;
-  if (merged)
+  if (merged) {
     // k, v of this step and (layer 1) q of step (4) read the same rows: one GEMM, the positional encoding as a per-position
     // table.  kvq [P*HW, N] = keys W^T + b + pe_table[row % HW]; N = 3I: k | v | q of layer 1 (kvq1), N = 2I: k | v of the final
     // attention (kvf)
-    HGL_TRY(hgl_launch_gemm_f16x3_rmod(keysS.hi, keysS.lo, C, fin ? w->kvf_w : w->kvq1_w, fin ? w->kvf_b : w->kvq1_b,
-                                       fin ? w->kvf_pe : w->kvq1_pe, N, HW, p.kp, nullptr, nullptr, N, P * HW, N, C, HGL_ACT_NONE, st));
+    HglGemm kvq = hgl_gemm_planes(keysS.hi, keysS.lo, fin ? w->kvf_w : w->kvq1_w, fin ? w->kvf_b : w->kvq1_b, p.kp, P * HW, N, C,
+                                  HGL_ACT_NONE, fin ? w->kvf_pe : w->kvq1_pe);
+    kvq.rmod = HW;
+    HGL_TRY(hgl_launch_gemm(kvq, st));
+  }
   HGL_TRY(lin(p.qpe, C, a.q, nullptr, 0, p.q1, I, P * T, I, C, HGL_ACT_NONE, st));
   if (r.raw_t2i) {
     // no projection of the image tokens at all (sam_decoder_t2i.hip): the 7 tokens are projected through W_k / W_v instead of
@@ -528,8 +533,7 @@ int dec_t2i(const DecRoute& r, const HglSamDecoderW* w, const HglSamAttnW& a, in
     HGL_TRY(hgl_launch_t2i_fold_q(p.q1, a.k.w, 1.0f / sqrtf((float)hd), s.A, P, st));
     HGL_TRY(hgl_launch_split_f16(s.A, 1.0f, s.Qh, s.Ql, (long long)P * 56 * C, st));
     // bias[p*56 + r, key] = Qk[p*56 + r, :] . pe[key, :]: pe is the "weight" [HW, C] of a split-fp16 GEMM
-    HGL_TRY(hgl_launch_gemm_f16x3(s.Qh, s.Ql, C, w->dense_pe, nullptr, nullptr, 0, p.kp, nullptr, nullptr, HW, P * 56, HW, C,
-                                  HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(s.Qh, s.Ql, w->dense_pe, nullptr, p.kp, P * 56, HW, C), st));
     // several key ranges: their partial rows behind the folded queries; one: the attended rows over the folded queries
     float* const rows = r.ns > 1 ? s.part : s.A;
     HGL_TRY(hgl_launch_t2i_raw_attn(s.Qh, s.Ql, p.kp, keysS.hi, keysS.lo, P, HW, rows, r.ns, st));
@@ -539,10 +543,8 @@ int dec_t2i(const DecRoute& r, const HglSamDecoderW* w, const HglSamAttnW& a, in
                      r.atti_bytes, st));
   } else {
     // per-prompt image tokens (transformer.py:126-131): the K / V projections read the split planes
-    HGL_TRY(hgl_launch_gemm_f16x3(kpeS.hi, kpeS.lo, C, a.k.w, a.k.b, nullptr, 0, p.kp, nullptr, nullptr, I, P * HW, I, C,
-                                  HGL_ACT_NONE, st));
-    HGL_TRY(hgl_launch_gemm_f16x3(keysS.hi, keysS.lo, C, a.v.w, a.v.b, nullptr, 0, p.vp, nullptr, nullptr, I, P * HW, I, C,
-                                  HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(kpeS.hi, kpeS.lo, a.k.w, a.k.b, p.kp, P * HW, I, C), st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(keysS.hi, keysS.lo, a.v.w, a.v.b, p.vp, P * HW, I, C), st));
     HGL_TRY(dec_fewq(p.q1, p.kp, p.vp, p.att, P, heads, T, HW, hd, I, I, I, I, sq, sk, sk, sq, part, r.atti_bytes, st));
   }
   return lin(p.att, I, a.out, p.queries, C, p.queries, C, P * T, C, I, HGL_ACT_NONE, st);
@@ -567,8 +569,7 @@ int dec_i2t(const DecRoute& r, const HglSamDecoderW* w, int li, const DecPlan& p
       // per-prompt 56 x 256 matrices (sam_decoder_t2i.hip: dec_i2t_fold_kernel); the planes are updated in place
       const I2tFoldScratch s(p.atti, P, C);
       HGL_TRY(hgl_launch_i2t_prep(p.k1, p.v1, a.q.w, a.q.b, a.out.w, 1.0f / sqrtf((float)hd), s.Kh, s.Kl, s.cb, s.Uh, s.Ul, P, st));
-      HGL_TRY(hgl_launch_gemm_f16x3(s.Kh, s.Kl, C, w->dense_pe, nullptr, nullptr, 0, p.kp, nullptr, nullptr, HW, P * 56, HW, C,
-                                    HGL_ACT_NONE, st));
+      HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(s.Kh, s.Kl, w->dense_pe, nullptr, p.kp, P * 56, HW, C), st));
       return hgl_launch_dec_i2t_fold(keysS.hi, keysS.lo, s.Kh, s.Kl, p.kp, s.cb, s.Uh, s.Ul, a.out.b, L.n4.w, L.n4.b, 1e-5f, P, HW,
                                      keysS.hi, keysS.lo, st);
     }
@@ -597,8 +598,7 @@ int dec_i2t(const DecRoute& r, const HglSamDecoderW* w, int li, const DecPlan& p
     if (shared) {
       HGL_TRY(lin(p.kpe0, C, a.q, nullptr, 0, p.qi, I, HW, I, C, HGL_ACT_NONE, st));
     } else if (!from_kvq) {
-      HGL_TRY(hgl_launch_gemm_f16x3(kpeS.hi, kpeS.lo, C, a.q.w, a.q.b, nullptr, 0, p.qi, nullptr, nullptr, I, P * HW, I, C,
-                                    HGL_ACT_NONE, st));
+      HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(kpeS.hi, kpeS.lo, a.q.w, a.q.b, p.qi, P * HW, I, C), st));
     }
     HGL_TRY(lin(p.qpe, C, a.k, nullptr, 0, p.k1, I, P * T, I, C, HGL_ACT_NONE, st));
     HGL_TRY(lin(p.queries, C, a.v, nullptr, 0, p.v1, I, P * T, I, C, HGL_ACT_NONE, st));
@@ -609,8 +609,9 @@ int dec_i2t(const DecRoute& r, const HglSamDecoderW* w, int li, const DecPlan& p
     d.ldq = ldq, d.ldk = d.ldv = I, d.sqb = shared ? 0 : (long long)HW * ldq, d.skb = d.svb = (long long)T * I;
     d.out_hi = at.hi, d.out_lo = at.lo, d.ldo = I, d.sob = (long long)HW * I;
     HGL_TRY(hgl_launch_attention(d, st));
-    HGL_TRY(hgl_launch_gemm_f16x3_rmod(at.hi, at.lo, I, a.out.w, a.out.b, keys, C, shared ? HW : 0, p.keys, nullptr, nullptr, C,
-                                       P * HW, C, I, HGL_ACT_NONE, st));
+    HglGemm out = hgl_gemm_planes(at.hi, at.lo, a.out.w, a.out.b, p.keys, P * HW, C, I, HGL_ACT_NONE, keys);
+    out.rmod = shared ? HW : 0;
+    HGL_TRY(hgl_launch_gemm(out, st));
   }
   // norm4, then keys (and, unmerged, keys + dense_pe) as split planes; the fp32 rows are kept only while a later layer
   // needs them as a residual
@@ -659,12 +660,14 @@ int hgl_sam_encode_batch(const HglSamEncoderW* w, const uint8_t* const* resized_
     uint16_t* ch = (uint16_t*)p.cols;            // im2col written as fp16 hi | lo planes (same bytes as fp32)
     uint16_t* cl = ch + (size_t)T * kd;
     HGL_TRY(hgl_launch_im2col_patch_split(p.img, nb, S, w->patch, ch, cl, st));
-    HGL_TRY(hgl_launch_gemm_f16x3_rmod(ch, cl, kd, w->patch_w, w->patch_b, w->pos_embed, D, nb > 1 ? T1 : 0, p.X, nullptr,
-                                       nullptr, D, T, D, kd, HGL_ACT_NONE, st));
+    HglGemm embed = hgl_gemm_planes(ch, cl, w->patch_w, w->patch_b, p.X, T, D, kd, HGL_ACT_NONE, w->pos_embed);
+    embed.rmod = nb > 1 ? T1 : 0;
+    HGL_TRY(hgl_launch_gemm(embed, st));
   } else {
     HGL_TRY(hgl_launch_im2col_patch(p.img, nb, S, w->patch, p.cols, st));
-    HGL_TRY(hgl_launch_gemm(p.cols, w->patch_w, w->patch_b, w->pos_embed, p.X, T1, D, kd, kd, kd, D, D, nb,
-                            (long long)T1 * kd, 0, 0, (long long)T1 * D, HGL_ACT_NONE, st));
+    HglGemm embed = hgl_gemm_linear(p.cols, w->patch_w, w->patch_b, p.X, T1, D, kd, HGL_ACT_NONE, w->pos_embed);
+    embed.batch = nb, embed.sA = (long long)T1 * kd, embed.sC = (long long)T1 * D;    // one batch per image, the table shared
+    HGL_TRY(hgl_launch_gemm(embed, st));
   }
   for (int i = 0; i < w->depth; ++i) {
     const int ws = w->blocks[i].window;
@@ -680,11 +683,9 @@ int hgl_sam_encode_batch(const HglSamEncoderW* w, const uint8_t* const* resized_
     uint16_t* xh = (uint16_t*)p.H;
     uint16_t* xl = xh + (size_t)T * D;
     HGL_TRY(hgl_launch_split_f16(p.X, 1.0f, xh, xl, (long long)T * D, st));
-    HGL_TRY(hgl_launch_gemm_f16x3(xh, xl, D, w->neck0_w, nullptr, nullptr, 0, p.neckA, nullptr, nullptr, C, T, C, D,
-                                  HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(xh, xl, w->neck0_w, nullptr, p.neckA, T, C, D), st));
   } else {
-    HGL_TRY(hgl_launch_gemm(p.X, w->neck0_w, nullptr, nullptr, p.neckA, T, C, D, D, D, 0, C, 1, 0, 0, 0, 0,
-                            HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.X, w->neck0_w, nullptr, p.neckA, T, C, D), st));
   }
   HGL_TRY(hgl_launch_layernorm(p.neckA, w->neck1_w, w->neck1_b, p.neckB, T, C, 1e-6f, st));
   for (int i = 0; i < nb; ++i)
@@ -693,11 +694,9 @@ int hgl_sam_encode_batch(const HglSamEncoderW* w, const uint8_t* const* resized_
     uint16_t* ch = (uint16_t*)p.F;
     uint16_t* cl = ch + (size_t)T * C * 9;
     HGL_TRY(hgl_launch_split_f16(p.cols3, 1.0f, ch, cl, (long long)T * C * 9, st));
-    HGL_TRY(hgl_launch_gemm_f16x3(ch, cl, C * 9, w->neck2_w, nullptr, nullptr, 0, p.neckA, nullptr, nullptr, C, T, C, C * 9,
-                                  HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(ch, cl, w->neck2_w, nullptr, p.neckA, T, C, C * 9), st));
   } else {
-    HGL_TRY(hgl_launch_gemm(p.cols3, w->neck2_w, nullptr, nullptr, p.neckA, T, C, C * 9, C * 9, C * 9, 0, C, 1, 0, 0,
-                            0, 0, HGL_ACT_NONE, st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.cols3, w->neck2_w, nullptr, p.neckA, T, C, C * 9), st));
   }
   HGL_TRY(hgl_launch_layernorm(p.neckA, w->neck3_w, w->neck3_b, emb, T, C, 1e-6f, st));
   return HGL_OK;
@@ -853,18 +852,14 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
                                 P, g, 1e-6f, low_res, skip, st));
   } else {
     if (r.x3) {
-      HGL_TRY(hgl_launch_gemm_f16x3(keysS.hi, keysS.lo, C, w->up0_w, w->up0_b, nullptr, 0, p.u1, nullptr, nullptr, 4 * C4,
-                                    P * HW, 4 * C4, C, HGL_ACT_NONE, st));
+      HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(keysS.hi, keysS.lo, w->up0_w, w->up0_b, p.u1, P * HW, 4 * C4, C), st));
       const SplitPair u1S = split_view(p.kpe, (size_t)P * HW * 4 * C4);   // kpeS is dead from here on
       HGL_TRY(hgl_launch_ln_gelu64(p.u1, w->up1.w, w->up1.b, (long long)P * HW * 4, 1e-6f, u1S.hi, u1S.lo, st));
-      HGL_TRY(hgl_launch_gemm_f16x3(u1S.hi, u1S.lo, C4, w->up3_w, w->up3_b, nullptr, 0, p.u2, nullptr, nullptr, 4 * C8,
-                                    P * HW * 4, 4 * C8, C4, HGL_ACT_GELU, st));
+      HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(u1S.hi, u1S.lo, w->up3_w, w->up3_b, p.u2, P * HW * 4, 4 * C8, C4, HGL_ACT_GELU), st));
     } else {
-      HGL_TRY(hgl_launch_gemm(p.keys, w->up0_w, w->up0_b, nullptr, p.u1, P * HW, 4 * C4, C, C, C, 0, 4 * C4, 1, 0, 0, 0, 0,
-                              HGL_ACT_NONE, st));
+      HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.keys, w->up0_w, w->up0_b, p.u1, P * HW, 4 * C4, C), st));
       HGL_TRY(hgl_launch_ln_gelu64(p.u1, w->up1.w, w->up1.b, (long long)P * HW * 4, 1e-6f, nullptr, nullptr, st));
-      HGL_TRY(hgl_launch_gemm(p.u1, w->up3_w, w->up3_b, nullptr, p.u2, P * HW * 4, 4 * C8, C4, C4, C4, 0, 4 * C8, 1, 0, 0,
-                              0, 0, HGL_ACT_GELU, st));
+      HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.u1, w->up3_w, w->up3_b, p.u2, P * HW * 4, 4 * C8, C4, HGL_ACT_GELU), st));
     }
     // masks[p, t, pix] = hyper[p, t, :] . upscaled[p, pix, :] for the three multimask tokens, un-shuffled into
     // [P,3,4g,4g] by the same kernel

@@ -152,7 +152,7 @@ def test_gemm_f16x3_inplace_residual(cuda):
                                         (160 * 256, 1280, 5120, "gelu"),               # lin2's shape (with an activation, for the reduce pass)
                                         (256 * 256, 1280, 1280, "none")])              # 1280 tiles = 5 rounds exactly: the plain launch
 def test_gemm_f16x3_row_balanced_launch(cuda, M, N, K, act):
-    """hgl_launch_gemm_f16x3_balanced (the residual GEMMs of the CLIP / SAM blocks): a GEMM whose last round of the persistent
+    """the row-balanced route of hgl_launch_gemm (the residual GEMMs of the CLIP / SAM blocks): a GEMM whose last round of the persistent
     256 x 256 tiling would be mostly empty runs as whole rounds + a split-K tail over the last row tiles.  Against the plain
     launch: the main rows bit for bit, the tail rows (K slices summed in index order) to fp32 rounding; in place on the
     residual, as the blocks call it; and against a float64 product on a sample of rows."""
