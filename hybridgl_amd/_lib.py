@@ -208,6 +208,8 @@ PROTOTYPES = {
     "hgl_gt_mask_from_rle_string": (_I, [C.c_char_p, _I, _I, _VP, _VP]),
     "hgl_rle_encode_mask": (_I, [_VP, _I, _I, _VP, _LL, C.POINTER(C.c_longlong)]),
     "hgl_rle_to_string": (_I, [_VP, _LL, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
+    "hgl_rle_encode_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "hgl_rle_encode_device": (_I, [_VP, _I, _I, _I, _VP, _I, _VP, _LL, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

@@ -82,6 +82,9 @@ def default_argument_parser():
                         "fewer than 3 / 6 proposals the clamp stays for every later item OF THE PROCESS: depends on the number of "
                         "ranks); per_ref = that item only (order- and sharding-independent); auto = persistent on one rank, "
                         "per_ref under sharding")
+    p.add_argument("--save_masks", default="", metavar="DIR",
+                   help="every rank writes DIR/masks.rank{rank}.jsonl: one line per sentence with its two winning masks as COCO "
+                        "RLE strings and its IoU counts (INTEGRATION.md); the files of all ranks together are the job's predictions")
     return p
 
 
@@ -360,6 +363,26 @@ def build_models(args, dev):
     return model, gen, gem_model
 
 
+def save_masks(pipe, directory, rank=0):
+    """--save_masks: DIR/masks.rank{rank}.jsonl, one JSON line per sentence this rank scored, keyed like dist.ROW_FIELDS:
+    {"index": dataset position, "sentence": sentence number, "size": [H, W], "pure", "final": the winning masks (pure CLIP /
+    with spatial guidance) as COCO compressed RLE strings (sam.coco_encode_rle), "I", "U", "I_final", "U_final": the metric
+    row's counts}.  Returns the path."""
+    import json
+    from .sam import coco_encode_rle
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, f"masks.rank{rank}.jsonl")
+    rows = pipe.partial_rows()
+    with open(path, "w") as f:
+        for rec, row in zip(pipe.predictions(), rows):
+            assert (rec["index"], rec["sentence"]) == (int(row[0]), int(row[1]))
+            enc = lambda counts: coco_encode_rle({"size": rec["size"], "counts": counts})["counts"]
+            f.write(json.dumps({"index": rec["index"], "sentence": rec["sentence"], "size": rec["size"], "pure": enc(rec["pure"]),
+                                "final": enc(rec["final"]), "I": int(row[2]), "U": int(row[3]), "I_final": int(row[4]),
+                                "U_final": int(row[5])}) + "\n")
+    return path
+
+
 def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
     """The loop of Hybridgl_main.py:79-247 over this rank's share of the dataset: loader threads -> HybridGLPipeline.run ->
     one exchange of the metric rows.  Returns (metrics of the whole job, stats of this rank: refs, seconds of the loop,
@@ -371,8 +394,9 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
     from . import dist as D
     resolve_defaults(args)
     k_clamp = args.k_clamp if args.k_clamp != "auto" else ("persistent" if world == 1 else "per_ref")
+    save_dir = getattr(args, "save_masks", "")
     pipe = HybridGLPipeline(model, fusion_mode=args.fusion_mode, masking_block=getattr(args, "masking_block", 9), mask_generator=gen,
-                            use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp)
+                            use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir))
     rr = None
     if args.real and args.dataset == "phrasecut":
         from .weights import CLIP_CONFIGS
@@ -409,6 +433,8 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
         n = pipe.run(loader, group=args.group, proposal_cap=cap)
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
+    if save_dir:
+        save_masks(pipe, save_dir, rank)      # this rank's own sentences: no collective
     m = pipe.metrics(dist)      # one all-gather of the metric rows; identical on every rank
     stats = {"refs": n, "seconds": dt, "seconds_job": D.max_over_ranks(dt, dist, dev), "loader_wait_s": loader.wait_s, "loader_make_s": loader.make_s,
              "images_decoded": rr.decoded if rr is not None else None, "image_cache_hits": pipe.cache_hits,

@@ -331,6 +331,51 @@ def iou_select(masks, idx, which, gt):
     return out
 
 
+def rle_slot_words(H, W):
+    """the slot size at which hgl_rle_encode_device never loses a mask: the words of its bit plane, ceil(H*W/32)"""
+    return (int(H) * int(W) + 31) // 32
+
+
+def rle_split(flat, S, slot_words):
+    """(slots [S, slot_words], table [S, 4]) as views of the flat int32 buffer rle_encode fills (device tensor, host tensor
+    or numpy array alike): the table first, then the slots"""
+    return flat[4 * S:4 * S + S * slot_words].reshape(S, slot_words), flat[:4 * S].reshape(S, 4)
+
+
+def rle_encode(masks, sel=None, slot_words=None, out=None):
+    """Column-major run lengths (utils/amg.py:107-136) of masks[sel] on the device: hgl_rle_encode_device on the current
+    stream, no synchronisation.  masks [N,H,W] bool / uint8; sel: integer device tensor [S] (converted on the device) or
+    None for every mask; slot_words: int32 words per entry (default ceil(H*W/32): nothing is ever lost).
+    Returns (slots [S, slot_words] int32, table [S,4] int32 = n_counts, form, area, 0), two views of one flat buffer
+    (`out`: a contiguous int32 device tensor of S * (4 + slot_words) elements to use for it); form 0: the slot holds the
+    counts, 1: the column-major bit plane, 2: neither fits, 3: index out of range (include/hybridgl.h).  The words are
+    unsigned: view them as uint32 on the host."""
+    lib = _lib.load()
+    N, H, W = masks.shape
+    mp, masks = _u8(masks, "masks")
+    sp = None
+    S = N
+    if sel is not None:
+        if not sel.is_cuda or sel.is_floating_point() or sel.dtype == torch.bool:
+            raise TypeError("sel: expected an integer device tensor")
+        sel = sel.reshape(-1).to(torch.int64).contiguous()
+        sp, S = sel.data_ptr(), int(sel.numel())
+    slot_words = rle_slot_words(H, W) if slot_words is None else int(slot_words)
+    if out is None:
+        out = torch.empty(S * (4 + slot_words), dtype=torch.int32, device=masks.device)
+    elif out.numel() != S * (4 + slot_words):
+        raise ValueError(f"out: expected {S * (4 + slot_words)} int32 elements, got {out.numel()}")
+    slots, table = rle_split(out, S, slot_words)
+    if S == 0:
+        return slots, table
+    need = lib.hgl_rle_encode_workspace_bytes(S, H, W)
+    ws = workspace(need, masks.device, "rle")
+    base = _dev(out, torch.int32, "out")
+    check(lib.hgl_rle_encode_device(mp, N, H, W, sp, S, base + 16 * S, slot_words, base, ws.data_ptr(), ws.numel(), _stream()),
+          "hgl_rle_encode_device")
+    return slots, table
+
+
 def score_sentence(hybrid, sentence_feat, noun_phrase_feat, other_noun_feats, boxes, gem_score,
                    logit_scale=100.0, r=0.5, k1=3, k2=6, alpha=0.6, relaword="none", has_other_nouns=False):
     """Per-sentence tail (Hybridgl_main.py:153-196,225-228).

@@ -117,7 +117,7 @@ def _side_streams(device):
 class HybridGLPipeline:
     def __init__(self, model, fusion_mode="G2L", masking_block=9, r=0.5, alpha=0.6, k1=3, k2=6, res=224,
                  mask_generator=None, use_sam_masks=False, fixed_proposals=None, cleanup_given_masks=False,
-                 gem_model=None, k_clamp="persistent", image_cache=32):
+                 gem_model=None, k_clamp="persistent", image_cache=32, record_predictions=False):
         """mask_generator: a hybridgl_amd.sam.SamAutomaticMaskGenerator; when given, every step runs the
         SAM proposal stage (encoder, decoder, post-processing, NMS) on ref.sam_img first.
         use_sam_masks=False keeps ref.masks for the CLIP stage (fixed N; synthetic benchmark, where
@@ -125,7 +125,10 @@ class HybridGLPipeline:
         k_clamp: "persistent" = the reference's quirk (Hybridgl_main.py:178-181: once an image yields fewer than k1 / k2
         proposals, k1 / k2 stay clamped for every LATER item of the process -- under sharding "later" means later on the
         same rank, so a run that meets such an image depends on the number of ranks); "per_ref" = the clamp applies
-        to that item only (order- and sharding-independent; differs from the reference after such an image)."""
+        to that item only (order- and sharding-independent; differs from the reference after such an image).
+        record_predictions: keep every sentence's two winning masks as run lengths (predictions()): each tail is followed
+        by one ops.rle_encode of the winners, selected by the tail's own device indices, and an asynchronous copy of the
+        runs to pinned host memory -- no read-back of an index or a pixel, no synchronisation in the loop."""
         if k_clamp not in ("persistent", "per_ref"):
             raise ValueError("k_clamp must be 'persistent' or 'per_ref'")
         # run(): proposals, hybrid features and GEM features of the last `image_cache` images with an image_id (the dataset
@@ -159,6 +162,10 @@ class HybridGLPipeline:
         self.iu_owner = []  # per sentence (dataset position of its ref, sentence number)
         self.idx_log = []   # per sentence: device int32 [2] = (index of the pure-CLIP winner, index with spatial guidance)
         self._n_refs = 0
+        self.record_predictions = bool(record_predictions)
+        self._pred_pending = []   # copies in flight: (ref position, sentences, H, W, slot words, pinned buffer, event), in log order
+        self._pred_done = []      # per sentence, in log order: ((H, W), counts of the pure winner, counts of the final one)
+        self._pred_free = []      # pinned staging buffers whose copies have completed
 
     def _join_side_streams(self, cur, outs):
         """The caller's stream waits for both side streams; every tensor that leaves them is recorded on the caller's
@@ -256,11 +263,71 @@ class HybridGLPipeline:
 
     _DEFERRED = object()
 
-    def _log_tail(self, ref_index, n, idx, iu):
+    def _log_tail(self, ref_index, n, idx, iu, masks=None):
         for j in range(n):
             self.iu_log.append((iu[j, 0:2], iu[j, 2:4]))
             self.iu_owner.append((ref_index, j))
             self.idx_log.append(idx[j])
+        if self.record_predictions:
+            self._record_tail(ref_index, n, masks, idx)
+
+    # ---- predictions: the winning masks of every sentence as run lengths (record_predictions=True) --------------------------
+    def _record_tail(self, ref_index, n, masks, idx):
+        """One ops.rle_encode of the 2n winners of a tail (idx [n,2]: the device tensor the tail wrote) and one asynchronous
+        copy of table and slots into a pinned buffer, both on the current stream; nothing here waits for the device."""
+        _, H, W = masks.shape
+        sw = ops.rle_slot_words(H, W)
+        flat = torch.empty(2 * n * (4 + sw), dtype=torch.int32, device=masks.device)
+        ops.rle_encode(masks, idx.reshape(-1), sw, out=flat)
+        self._harvest_predictions()
+        host = None
+        for i, b in enumerate(self._pred_free):
+            if b.numel() >= flat.numel():
+                host = self._pred_free.pop(i)
+                break
+        if host is None:
+            host = torch.empty(flat.numel(), dtype=torch.int32, pin_memory=True)
+        host[:flat.numel()].copy_(flat, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._pred_pending.append((ref_index, n, H, W, sw, host, ev))
+
+    def _harvest_predictions(self, wait=False):
+        """The copies that have completed (wait=True: all of them), oldest first, reduced to their counts arrays; their
+        staging buffers return to the pool.  Host memory grows with the number of runs, not with pixels."""
+        from .sam import rle_from_slot
+        while self._pred_pending:
+            ref_index, n, H, W, sw, host, ev = self._pred_pending[0]
+            if wait:
+                ev.synchronize()
+            elif not ev.query():
+                break
+            self._pred_pending.pop(0)
+            slots, table = ops.rle_split(host.numpy(), 2 * n, sw)
+            rows = []
+            for e in range(2 * n):
+                nc, form = int(table[e, 0]), int(table[e, 1])
+                if form == 0:
+                    rows.append(slots[e, :nc].astype(np.uint32))      # a copy: the buffer is reused
+                else:
+                    rows.append(np.asarray(rle_from_slot(slots[e], nc, form, H, W), dtype=np.uint32))
+            for j in range(n):
+                self._pred_done.append(((H, W), rows[2 * j], rows[2 * j + 1]))
+            self._pred_free.append(host)
+
+    def predictions(self):
+        """The winning masks of every sentence scored so far, ordered and keyed like partial_rows(): a list of
+        {"index": dataset position, "sentence": sentence number, "pure_index", "final_index": the proposal indices of
+        winning_indices(), "size": [H, W], "pure", "final": column-major run lengths (the `counts` of sam.mask_to_rle)}.
+        Waits for the copies still in flight."""
+        if not self.record_predictions:
+            raise RuntimeError("predictions(): this pipeline does not record them; build it with record_predictions=True")
+        self._harvest_predictions(wait=True)
+        win = self.winning_indices()
+        assert len(self._pred_done) == len(self.iu_owner) == len(win)
+        return [{"index": int(o[0]), "sentence": int(o[1]), "pure_index": int(w[0]), "final_index": int(w[1]),
+                 "size": [int(hw[0]), int(hw[1])], "pure": [int(v) for v in a], "final": [int(v) for v in b]}
+                for o, w, (hw, a, b) in zip(self.iu_owner, win, self._pred_done)]
 
     def _flush_tails(self, defer):
         """the deferred tails of a group's refs in one hgl_score_group call; returns each ref's last-sentence tensors, in order"""
@@ -269,7 +336,7 @@ class HybridGLPipeline:
         outs = ops.score_group(defer, self.model.model._logit_scale_exp, self.r, self.alpha, cum=self.cum, want_scores=True)
         last = []
         for q, (idx, iu, sc, sn, gm) in zip(defer, outs):
-            self._log_tail(q["ref_index"], len(q["sentences"]), idx, iu)
+            self._log_tail(q["ref_index"], len(q["sentences"]), idx, iu, q["masks"])
             last.append((idx[-1], sc[-1], sn[-1], gm[-1]))
         defer.clear()
         return last
@@ -306,7 +373,7 @@ class HybridGLPipeline:
                 return self._DEFERRED
             idx, iu, sc, sn, gm = ops.score_ref(hybrid, text, ref.boxes, ref.masks, recs, m.model._logit_scale_exp, self.r, self.k1,
                                                 self.k2, self.alpha, cum=self.cum, want_scores=True)
-            self._log_tail(ref_index, len(recs), idx, iu)
+            self._log_tail(ref_index, len(recs), idx, iu, ref.masks)
             return (idx[-1], sc[-1], sn[-1], gm[-1]) if recs else None
         last = None
         for sent_no, (s, imgattn) in enumerate(zip(ref.sentences, attn)):
@@ -324,6 +391,9 @@ class HybridGLPipeline:
             self.iu_owner.append((ref_index, sent_no))
             self.idx_log.append(idx)
             last = (idx, sc, sn, gem)
+        if self.record_predictions:
+            n = len(ref.sentences)
+            self._record_tail(ref_index, n, ref.masks, torch.stack(self.idx_log[-n:]))
         return last
 
     # ---- the evaluation loop at the grouped rate ----------------------------------------------------------------------
@@ -383,9 +453,11 @@ class HybridGLPipeline:
         use_gem = self.gem_model is not None
         items = [synthetic_ref(90000 + j, dev, N=proposals, H=H, W=W, n_sent=n_sent, sam_img_size=1024 if gen is not None else 0,
                                gem=use_gem, device_blur=True)[0] for j in range(min(group, 4))]
+        if self.record_predictions:      # what the loop has recorded so far is filed before the rehearsal's records are dropped
+            self._harvest_predictions(wait=True)
         keep = (self.cum.clone(), list(self.iu_log), list(self.iu_owner), list(self.idx_log), self._n_refs,
                 getattr(self, "skipped", 0), getattr(self, "groups_run", 0), dict(self._img_cache), self.cache_hits,
-                (self.k1, self.k2), getattr(self, "group_marks", None), getattr(self, "stage_marks", None))
+                (self.k1, self.k2), getattr(self, "group_marks", None), getattr(self, "stage_marks", None), len(self._pred_done))
         self.group_marks = self.stage_marks = None
         cap = proposals if (gen is not None and self.use_sam_masks) else None
         try:
@@ -421,6 +493,9 @@ class HybridGLPipeline:
             self._img_cache, self.cache_hits = keep[7], keep[8]
             self.k1, self.k2 = keep[9]
             self.group_marks, self.stage_marks = keep[10], keep[11]
+            if self.record_predictions:      # the staging buffers stay (sized for this geometry), the records go
+                self._harvest_predictions(wait=True)
+                del self._pred_done[keep[12]:]
         return self
 
     def run(self, loader, group=16, proposal_cap=None, collect=False, serial=False, total=None):

@@ -1228,12 +1228,19 @@ class SamAutomaticMaskGenerator:
         else:
             m, xywh, iou, stab, src = self.generate_device(image)
             pts, cbs = self._sources(src, H, W)
-        masks = m.bool().cpu().numpy()
+        if self.output_mode == "binary_mask":
+            masks = m.bool().cpu().numpy()
+            segs, areas = masks, [int(k.sum()) for k in masks]
+        else:
+            # the RLE modes: runs encoded on the device, only runs cross to the host (no [n,H,W] byte copy, no host codec)
+            segs, areas = _masks_to_rle(m)
+            if self.output_mode == "coco_rle":
+                segs = [coco_encode_rle(r) for r in segs]
         xywh, iou, stab = xywh.cpu().numpy(), iou.cpu().numpy(), stab.cpu().numpy()
         out = []
-        for i in range(len(masks)):
+        for i in range(len(segs)):
             cb = cbs[i]
-            out.append({"segmentation": self._segmentation(masks[i]), "area": int(masks[i].sum()), "bbox": [int(v) for v in xywh[i]],
+            out.append({"segmentation": segs[i], "area": areas[i], "bbox": [int(v) for v in xywh[i]],
                         "predicted_iou": float(iou[i]), "point_coords": [pts[i].tolist()],
                         "stability_score": float(stab[i]),
                         "crop_box": [int(cb[0]), int(cb[1]), int(cb[2] - cb[0]), int(cb[3] - cb[1])]})   # XYWH
@@ -1251,6 +1258,47 @@ def mask_to_rle(mask):
     counts = np.empty(m.value, dtype=np.uint32)
     check(lib.hgl_rle_encode_mask(mk.ctypes.data, H, W, counts.ctypes.data, m.value, C.byref(m)), "hgl_rle_encode_mask")
     return {"size": [H, W], "counts": [int(v) for v in counts]}
+
+
+def rle_from_slot(slot, n_counts, form, H, W):
+    """The counts of one entry of ops.rle_encode from its slot on the HOST (`slot`: the entry's words as a numpy array, at
+    least as many as its form defines).  Form 0: the slot holds the n_counts counts.  Form 1 (more runs than the slot
+    holds): the slot is the column-major bit plane, bit p % 32 of word p / 32 with p = x*H + y; it is unpacked and the
+    host codec finishes the job.  Forms 2 / 3 carry no mask."""
+    slot = np.ascontiguousarray(np.asarray(slot)).view(np.uint32).reshape(-1)
+    if form == 0:
+        return [int(v) for v in slot[:n_counts]]
+    if form != 1:
+        raise ValueError("rle_from_slot: " + ("the entry's index was out of range" if form == 3 else
+                                              f"neither the {n_counts} counts nor the bit plane fit the slot"))
+    words = (H * W + 31) // 32
+    bits = np.unpackbits(slot[:words].astype("<u4").view(np.uint8), bitorder="little")[:H * W]
+    counts = mask_to_rle(bits.reshape(W, H).T)["counts"]
+    assert len(counts) == n_counts, (len(counts), n_counts)
+    return counts
+
+
+def _masks_to_rle(masks, sel=None):
+    """masks_to_rle plus the areas of the table: (list of RLE dicts, list of int)"""
+    n, H, W = masks.shape
+    S = n if sel is None else int(sel.numel())
+    if S == 0:
+        return [], []
+    if not masks.is_contiguous():
+        masks = masks.contiguous()
+    sw = ops.rle_slot_words(H, W)
+    flat = torch.empty(S * (4 + sw), dtype=torch.int32, device=masks.device)
+    ops.rle_encode(masks, sel, sw, out=flat)
+    slots, table = ops.rle_split(flat.cpu().numpy(), S, sw)      # the one device -> host copy
+    rles = [{"size": [H, W], "counts": rle_from_slot(slots[i], int(table[i, 0]), int(table[i, 1]), H, W)} for i in range(S)]
+    return rles, [int(a) for a in table[:, 2]]
+
+
+def masks_to_rle(masks, sel=None):
+    """mask_to_rle for device masks [n,H,W] (bool / uint8), all of them or masks[sel] (sel: integer device tensor): the runs
+    are formed on the device (ops.rle_encode) and one device -> host copy brings table and slots over -- runs, not pixels.
+    Returns a list of {"size": [H, W], "counts": [...]}, identical to mask_to_rle of every mask."""
+    return _masks_to_rle(masks, sel)[0]
 
 
 def rle_to_mask(rle):

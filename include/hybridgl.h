@@ -651,6 +651,21 @@ int hgl_gt_mask_from_rle_string(const char* s, int H, int W, uint8_t* mask, int6
  * hgl_rle_to_string: the compressed ASCII string of COCO; out needs at most 7*m+1 bytes; *len = strlen(out). */
 int hgl_rle_encode_mask(const uint8_t* mask, int H, int W, uint32_t* counts, long long cap, long long* m);
 int hgl_rle_to_string(const uint32_t* counts, long long m, char* out, size_t cap, size_t* len);
+/* The same run lengths for masks that live on the DEVICE, selected by a device index tensor (csrc/rle.hip): the mask
+ * generator's RLE modes and the evaluator's winning masks without a pixel read-back.  Asynchronous on `stream`; no host
+ * synchronisation, allocation or atomics; every entry owns its slot and its table row.
+ * masks: device [N,H,W] row-major, nonzero = foreground (N*H*W < 2^31).  sel: device [S] indices into masks, or NULL for
+ * masks 0..S-1 (then S <= N).  slots: device [S, slot_words].  table: device [S,4] = (n_counts, form, area, 0); n_counts
+ * is always the true number of counts and area the number of foreground pixels.  form says what the slot holds:
+ *   0  the n_counts counts (whenever n_counts <= slot_words)
+ *   1  the column-major bit plane, bit p % 32 of word p / 32 with p = x*H + y, ceil(H*W/32) words (the counts do not fit
+ *      but the plane does: with slot_words = ceil(H*W/32) no mask is ever lost, whatever its run count)
+ *   2  neither fits: nothing written
+ *   3  sel[s] is outside [0, N): nothing read or written
+ * Words of a slot beyond what its form defines are not written.  ws: the size the workspace query returns for (S, H, W). */
+size_t hgl_rle_encode_workspace_bytes(int S, int H, int W);
+int hgl_rle_encode_device(const uint8_t* masks, int N, int H, int W, const int64_t* sel, int S, uint32_t* slots,
+                          long long slot_words, int32_t* table, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
