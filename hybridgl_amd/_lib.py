@@ -210,6 +210,11 @@ PROTOTYPES = {
     "hgl_rle_to_string": (_I, [_VP, _LL, C.c_char_p, _SZ, C.POINTER(C.c_size_t)]),
     "hgl_rle_encode_workspace_bytes": (_SZ, [_I, _I, _I]),
     "hgl_rle_encode_device": (_I, [_VP, _I, _I, _I, _VP, _I, _VP, _LL, _VP, _VP, _SZ, _VP]),
+    "hgl_rle_from_string": (_I, [C.c_char_p, _VP, _LL, C.POINTER(C.c_longlong)]),
+    "hgl_rle_decode_workspace_bytes": (_SZ, [_I, _I, _I, _LL]),
+    "hgl_rle_decode_device": (_I, [_VP, _LL, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "hgl_rle_iou_workspace_bytes": (_SZ, [_I, _I, _I, _LL, _LL]),
+    "hgl_rle_iou_device": (_I, [_VP, _LL, _VP, _VP, _LL, _VP, _I, _I, _I, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

@@ -111,6 +111,34 @@ long long fill_counts(const unsigned* cnts, long long m, int H, int W, uint8_t* 
   return area;
 }
 
+// The counts of a compressed string (maskApi.c:217-230 rleFrString): LEB128-like, 5 payload bits + continuation bit per
+// character (offset 48), every count after the third stored as a difference to the count two places earlier.
+// The string comes from an annotation file: every shift below is on unsigned 64-bit values with a bounded count
+// (a count takes at most 7 characters = 35 bits; maskApi.c itself shifts 32-bit ints, so longer groups never occur in
+// valid data), a group cut off by the end of the string or longer than that is an error, never undefined behaviour.
+int parse_rle_string(const char* s, const char* who, std::vector<unsigned>& cnts) {
+  size_t p = 0;
+  while (s[p]) {
+    unsigned long long ux = 0;
+    int k = 0;
+    bool more = true;
+    while (more) {
+      HGL_REQUIRE(s[p] != 0, "%s: truncated string", who);
+      HGL_REQUIRE(k < 7, "%s: malformed count (more than 7 characters)", who);
+      const unsigned c = (unsigned)(unsigned char)(s[p] - 48);
+      ux |= (unsigned long long)(c & 0x1fu) << (5 * k);
+      more = (c & 0x20u) != 0;
+      ++p;
+      ++k;
+      if (!more && (c & 0x10u)) ux |= ~0ULL << (5 * k);      // sign extension (maskApi.c: x |= -1 << 5*k)
+    }
+    long long x = (long long)ux;
+    if (cnts.size() > 2) x += (long long)cnts[cnts.size() - 2];
+    cnts.push_back((unsigned)(unsigned long long)x);
+  }
+  return HGL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -147,34 +175,24 @@ int hgl_gt_mask_from_rle_counts(const uint32_t* counts, int m, int H, int W, uin
 
 int hgl_gt_mask_from_rle_string(const char* s, int H, int W, uint8_t* mask, int64_t* area) {
   HGL_REQUIRE(s && mask && H > 0 && W > 0, "gt_mask_from_rle_string: bad arguments");
-  // LEB128-like, 5 payload bits + continuation bit per character (offset 48), every count after the third stored
-  // as a difference to the count two places earlier (maskApi.c:217-230)
-  // The string comes from an annotation file: every shift below is on unsigned 64-bit values with a bounded count
-  // (a count takes at most 7 characters = 35 bits; maskApi.c itself shifts 32-bit ints, so longer groups never occur in
-  // valid data), a group cut off by the end of the string or longer than that is an error, never undefined behaviour.
   std::vector<unsigned> cnts;
-  size_t p = 0;
-  while (s[p]) {
-    unsigned long long ux = 0;
-    int k = 0;
-    bool more = true;
-    while (more) {
-      HGL_REQUIRE(s[p] != 0, "gt_mask_from_rle_string: truncated string");
-      HGL_REQUIRE(k < 7, "gt_mask_from_rle_string: malformed count (more than 7 characters)");
-      const unsigned c = (unsigned)(unsigned char)(s[p] - 48);
-      ux |= (unsigned long long)(c & 0x1fu) << (5 * k);
-      more = (c & 0x20u) != 0;
-      ++p;
-      ++k;
-      if (!more && (c & 0x10u)) ux |= ~0ULL << (5 * k);      // sign extension (maskApi.c: x |= -1 << 5*k)
-    }
-    long long x = (long long)ux;
-    if (cnts.size() > 2) x += (long long)cnts[cnts.size() - 2];
-    cnts.push_back((unsigned)(unsigned long long)x);
-  }
+  HGL_TRY(parse_rle_string(s, "gt_mask_from_rle_string", cnts));
   std::fill(mask, mask + (size_t)H * W, (uint8_t)0);
   const long long a = fill_counts(cnts.data(), (long long)cnts.size(), H, W, mask);
   if (area) *area = a;
+  return HGL_OK;
+}
+
+// maskApi.c:217-230 rleFrString without the decode: the counts of a compressed string.  *m receives the number of counts;
+// with counts == nullptr or cap too small nothing is written beyond cap and the needed length is still reported.
+int hgl_rle_from_string(const char* s, uint32_t* counts, long long cap, long long* m) {
+  HGL_REQUIRE(s && m && cap >= 0, "rle_from_string: bad arguments");
+  std::vector<unsigned> cnts;
+  HGL_TRY(parse_rle_string(s, "rle_from_string", cnts));
+  const long long n = (long long)cnts.size();
+  if (counts)
+    for (long long i = 0; i < n && i < cap; ++i) counts[i] = cnts[i];
+  *m = n;
   return HGL_OK;
 }
 

@@ -196,6 +196,220 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned lo
   if (t == 0) slot[trans] = HW - last_base;
 }
 
+// ---- the way back: slots + table -> masks (hgl_rle_decode_device) and intersection / union of two encoded sets
+// (hgl_rle_iou_device).  The mirror image of the launches above:
+//
+//   A. rle_starts_kernel   one workgroup per entry decides what the slot holds (the status code) and, for form 0, sum-scans
+//      the counts 256 at a time with a 64-bit carry into run starts E_k (E_0 = 0, saturated at H*W, so a count of 0xFFFFFFFF
+//      cannot wrap).  The area is the clipped length of the odd runs (form 0) or the pop-count of the plane's valid bits (form 1).
+//   B. rle_plane_word      any 64-bit column word -- rows 64j .. 64j+63 of column x, the encoder's own layout -- from its
+//      entry alone.  Form 0: an upper-bound search in E finds the last run that starts at or before the word's first pixel,
+//      then the runs that touch the word are walked: no atomics, no scatter, O(words * log n + n) over an entry.  Form 1: the
+//      32-bit run-order words are re-packed (the inverse of the encoder's form-1 branch).  An entry of code 2 gives 0.
+//   C. rle_rows_kernel     the inverse of rle_columns_kernel: lane x forms the column word(s) of its 64 rows with B and every
+//      row is one coalesced store across the lanes (1 or 4 bytes per lane).  Every byte of every entry is written exactly once;
+//      the decoder keeps no plane anywhere.
+//   D. rle_plane_kernel / rle_iou_kernel   for the IoU the words of both sets go to the workspace, one thread per word, and one
+//      workgroup per entry pop-counts a & b and a | b: padding bits are 0 on both sides, no mask is expanded to bytes.
+
+// the slot of an entry holds a mask (include/hybridgl.h: anything else is code 2)
+__device__ __forceinline__ bool rle_entry_usable(int n, int form, long long slot_words, unsigned plane_words) {
+  if (n < 0) return false;
+  if (form == 0) return (long long)n <= slot_words;
+  if (form == 1) return (long long)plane_words <= slot_words;      // a plane that the slot cannot hold is never read
+  return false;
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_starts_kernel(const uint32_t* __restrict__ slots, long long slot_words,
+                                                                 const int32_t* __restrict__ table, int H, int W,
+                                                                 uint32_t* __restrict__ E, long long e_stride,
+                                                                 int32_t* __restrict__ status) {
+  __shared__ unsigned red[4];
+  __shared__ unsigned long long wtot[4];
+  const int s = blockIdx.x, t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const int n = table[(size_t)s * 4], form = table[(size_t)s * 4 + 1];
+  const unsigned HW = (unsigned)H * (unsigned)W;      // < 2^31 (checked by the host entry)
+  const unsigned plane_words = (HW + 31u) / 32u;
+  int32_t* row = status + (size_t)s * 4;
+  if (!rle_entry_usable(n, form, slot_words, plane_words)) {      // uniform over the workgroup
+    if (t == 0) { row[0] = 2; row[1] = 0; row[2] = 0; row[3] = 0; }
+    return;
+  }
+  const uint32_t* slot = slots + (size_t)s * (size_t)slot_words;
+  unsigned area = 0;
+  int code = 0;
+  if (form == 1) {
+    const unsigned tail = HW - 32u * (plane_words - 1u);      // 1 .. 32 valid bits in the last word
+    for (unsigned w = t; w < plane_words; w += RLE_THREADS) {
+      uint32_t v = slot[w];
+      if (w == plane_words - 1u && tail < 32u) v &= (1u << tail) - 1u;
+      area += __popc(v);
+    }
+  } else {
+    uint32_t* Es = E + (size_t)s * (size_t)e_stride;      // n + 1 <= slot_words + 1 <= e_stride entries
+    // E[k] = min(H*W, counts[0] + .. + counts[k-1]); the sums are exact in 64 bits (n < 2^31 counts < 2^32)
+    unsigned long long carry = 0;
+    if (t == 0) Es[0] = 0;
+    for (unsigned base = 0; base < (unsigned)n; base += RLE_THREADS) {
+      const unsigned i = base + t;
+      const unsigned long long own = i < (unsigned)n ? (unsigned long long)slot[i] : 0ull;
+      unsigned long long v = own;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long a = __shfl_up(v, d, 64);
+        if (lane >= d) v += a;
+      }
+      __syncthreads();      // the previous chunk's reads of wtot are over
+      if (lane == 63) wtot[wave] = v;
+      __syncthreads();
+      unsigned long long sum = carry + v, tot = 0;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        if (w < wave) sum += wtot[w];
+        tot += wtot[w];
+      }
+      if (i < (unsigned)n) {
+        const unsigned end = sum < (unsigned long long)HW ? (unsigned)sum : HW;
+        const unsigned start = sum - own < (unsigned long long)HW ? (unsigned)(sum - own) : HW;
+        Es[i + 1] = end;
+        if (i & 1u) area += end - start;
+      }
+      carry += tot;
+    }
+    code = carry == (unsigned long long)HW ? 0 : 1;
+  }
+  area = rle_block_sum(area, red);
+  if (t == 0) { row[0] = code; row[1] = (int32_t)area; row[2] = 0; row[3] = 0; }
+}
+
+// rows 64j .. 64j+63 of column x of an entry that holds a mask (bits beyond H are 0); Es: the entry's run starts (form 0)
+__device__ __forceinline__ unsigned long long rle_plane_word(const uint32_t* __restrict__ slot, int form, int n,
+                                                             const uint32_t* __restrict__ Es, unsigned plane_words, int H, int x,
+                                                             int j) {
+  const int nb = H - 64 * j < 64 ? H - 64 * j : 64;
+  const unsigned p0 = (unsigned)x * (unsigned)H + 64u * (unsigned)j, p1 = p0 + (unsigned)nb;      // p1 <= H*W
+  unsigned long long c = 0;
+  if (form == 1) {
+    // the nb <= 64 bits from p0 on live in at most three 32-bit words
+    const unsigned w = p0 >> 5, o = p0 & 31u;
+    const unsigned long long w0 = slot[w];
+    const unsigned long long w1 = w + 1 < plane_words ? slot[w + 1] : 0u;
+    const unsigned long long w2 = w + 2 < plane_words ? slot[w + 2] : 0u;
+    c = (w0 | (w1 << 32)) >> o;
+    if (o) c |= w2 << (64 - o);
+    if (nb < 64) c &= (1ull << nb) - 1ull;
+  } else if (n > 0) {
+    unsigned lo = 0, hi = (unsigned)n - 1u;      // the last run k in [0, n) with E[k] <= p0 (E[0] = 0)
+    while (lo < hi) {
+      const unsigned mid = (lo + hi + 1u) >> 1;
+      if (Es[mid] <= p0) lo = mid; else hi = mid - 1u;
+    }
+    unsigned k = lo, pos = p0;
+    while (pos < p1 && k < (unsigned)n) {
+      const unsigned e = Es[k + 1];
+      const unsigned end = e < p1 ? e : p1;
+      if (end > pos) {
+        if (k & 1u) {
+          const unsigned len = end - pos;      // 1 .. 64
+          c |= (len == 64u ? ~0ull : ((1ull << len) - 1ull)) << (pos - p0);
+        }
+        pos = end;
+      }
+      ++k;
+    }
+  }
+  return c;
+}
+
+// V columns per lane (4: one aligned 32-bit store per row when W % 4 == 0), 64 rows per wave, 4 waves = 4 row tiles per block
+template <int V>
+__global__ __launch_bounds__(RLE_THREADS) void rle_rows_kernel(const uint32_t* __restrict__ slots, long long slot_words,
+                                                               const int32_t* __restrict__ table, const uint32_t* __restrict__ E,
+                                                               long long e_stride, const int32_t* __restrict__ status, int H,
+                                                               int W, int HW64, int col_tiles, int row_tiles,
+                                                               uint8_t* __restrict__ masks) {
+  const unsigned tile = blockIdx.x;
+  const int s = (int)(tile / (unsigned)(col_tiles * row_tiles));
+  const int rem = (int)(tile % (unsigned)(col_tiles * row_tiles));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = (rem / col_tiles) * 4 + wave;
+  const int x = ((rem % col_tiles) * 64 + lane) * V;
+  if (j >= HW64 || x >= W) return;      // no barrier and no cross-lane operation below
+  const int y0 = j * 64;
+  const int rows = H - y0 < 64 ? H - y0 : 64;
+  unsigned long long c[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) c[k] = 0;
+  if (status[(size_t)s * 4] != 2) {
+    const int n = table[(size_t)s * 4], form = table[(size_t)s * 4 + 1];
+    const unsigned plane_words = ((unsigned)H * (unsigned)W + 31u) / 32u;
+#pragma unroll
+    for (int k = 0; k < V; ++k)      // x + k < W: W % 4 == 0 on the 4-column path
+      c[k] = rle_plane_word(slots + (size_t)s * (size_t)slot_words, form, n, E + (size_t)s * (size_t)e_stride, plane_words, H, x + k, j);
+  }
+  uint8_t* dst = masks + (size_t)s * H * W + (size_t)y0 * W + x;      // (y0 + r) * W + x (+ 3) < H * W
+#pragma unroll 8
+  for (int r = 0; r < rows; ++r) {
+    if (V == 4) {
+      uint32_t v = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) v |= (uint32_t)((c[k] >> r) & 1ull) << (8 * k);
+      *reinterpret_cast<uint32_t*>(dst + (size_t)r * W) = v;
+    } else {
+      dst[(size_t)r * W] = (uint8_t)((c[0] >> r) & 1ull);
+    }
+  }
+}
+
+// one thread per plane word: word q = x*HW64 + j of entry s, q_tiles workgroups per entry
+__global__ __launch_bounds__(RLE_THREADS) void rle_plane_kernel(const uint32_t* __restrict__ slots, long long slot_words,
+                                                                const int32_t* __restrict__ table, const uint32_t* __restrict__ E,
+                                                                long long e_stride, const int32_t* __restrict__ status, int H,
+                                                                int W, int HW64, int q_tiles, unsigned long long* __restrict__ plane) {
+  const int s = (int)(blockIdx.x / (unsigned)q_tiles);
+  const unsigned q = (blockIdx.x % (unsigned)q_tiles) * RLE_THREADS + threadIdx.x;
+  const unsigned Q = (unsigned)W * (unsigned)HW64;
+  if (q >= Q) return;
+  unsigned long long c = 0;
+  if (status[(size_t)s * 4] != 2) {
+    const unsigned plane_words = ((unsigned)H * (unsigned)W + 31u) / 32u;
+    c = rle_plane_word(slots + (size_t)s * (size_t)slot_words, table[(size_t)s * 4 + 1], table[(size_t)s * 4],
+                       E + (size_t)s * (size_t)e_stride, plane_words, H, (int)(q / (unsigned)HW64), (int)(q % (unsigned)HW64));
+  }
+  plane[(size_t)s * Q + q] = c;
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_iou_kernel(const unsigned long long* __restrict__ pa,
+                                                              const unsigned long long* __restrict__ pb,
+                                                              const int32_t* __restrict__ sa, const int32_t* __restrict__ sb,
+                                                              unsigned Q, long long* __restrict__ iu) {
+  __shared__ unsigned red[4];
+  const int s = blockIdx.x, t = threadIdx.x;
+  if (sa[(size_t)s * 4] == 2 || sb[(size_t)s * 4] == 2) {      // uniform over the workgroup
+    if (t == 0) { iu[(size_t)s * 2] = -1; iu[(size_t)s * 2 + 1] = -1; }
+    return;
+  }
+  const unsigned long long* A = pa + (size_t)s * Q;
+  const unsigned long long* B = pb + (size_t)s * Q;
+  unsigned inter = 0, uni = 0;      // <= H*W < 2^31
+  for (unsigned q = t; q < Q; q += RLE_THREADS) {
+    const unsigned long long a = A[q], b = B[q];
+    inter += __popcll(a & b);
+    uni += __popcll(a | b);
+  }
+  inter = rle_block_sum(inter, red);
+  uni = rle_block_sum(uni, red);
+  if (t == 0) { iu[(size_t)s * 2] = (long long)inter; iu[(size_t)s * 2 + 1] = (long long)uni; }
+}
+
+// run starts of one set: [S] arrays of slot_words + 1 words
+size_t rle_starts_bytes(int S, long long slot_words) { return hgl_align_up((size_t)S * (size_t)(slot_words + 1) * sizeof(uint32_t), 256); }
+size_t rle_planes_bytes(int S, int H, int W) {
+  return hgl_align_up((size_t)S * (size_t)W * (size_t)((H + 63) / 64) * sizeof(unsigned long long), 256);
+}
+size_t rle_status_bytes(int S) { return hgl_align_up((size_t)S * 4 * sizeof(int32_t), 256); }
+
 }  // namespace
 
 extern "C" {
@@ -232,6 +446,89 @@ int hgl_rle_encode_device(const uint8_t* masks, int N, int H, int W, const int64
   hipLaunchKernelGGL(rle_runs_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)plane, N, H, W,
                      sel64, HW64, slots, slot_words, table);
   return hgl_check_launch("rle_encode_device");
+}
+
+size_t hgl_rle_decode_workspace_bytes(int S, int H, int W, long long slot_words) {
+  if (S <= 0 || H <= 0 || W <= 0 || slot_words < 0) return 0;
+  return rle_starts_bytes(S, slot_words);
+}
+
+int hgl_rle_decode_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S, int H, int W, uint8_t* masks,
+                          int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(slots && table && masks && status && S > 0 && H > 0 && W > 0 && slot_words >= 0, "rle_decode_device: bad arguments");
+  HGL_REQUIRE((long long)H * W < (1ll << 31), "rle_decode_device: image too large (H*W must be < 2^31)");
+  HGL_REQUIRE((long long)S * H * W < (1ll << 31), "rle_decode_device: batch too large (S*H*W must be < 2^31)");
+  const int HW64 = (H + 63) / 64;
+  const bool wide = (W % 4 == 0) && (((uintptr_t)masks & 3u) == 0);
+  const int col_tiles = (W + (wide ? 255 : 63)) / (wide ? 256 : 64), row_tiles = (HW64 + 3) / 4;
+  const long long tiles = (long long)S * col_tiles * row_tiles;
+  HGL_REQUIRE(tiles < (1ll << 31), "rle_decode_device: too many entries (%d) for one launch", S);
+  if (!ws || ws_bytes < hgl_rle_decode_workspace_bytes(S, H, W, slot_words)) {
+    hgl_set_error("rle_decode_device: workspace too small");
+    return HGL_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* E = (uint32_t*)ws;
+  const long long e_stride = slot_words + 1;
+  hipLaunchKernelGGL(rle_starts_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots, slot_words, table, H, W, E, e_stride,
+                     status);
+  if (wide)
+    hipLaunchKernelGGL(rle_rows_kernel<4>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
+                       (const uint32_t*)E, e_stride, (const int32_t*)status, H, W, HW64, col_tiles, row_tiles, masks);
+  else
+    hipLaunchKernelGGL(rle_rows_kernel<1>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
+                       (const uint32_t*)E, e_stride, (const int32_t*)status, H, W, HW64, col_tiles, row_tiles, masks);
+  return hgl_check_launch("rle_decode_device");
+}
+
+size_t hgl_rle_iou_workspace_bytes(int S, int H, int W, long long slot_words_a, long long slot_words_b) {
+  if (S <= 0 || H <= 0 || W <= 0 || slot_words_a < 0 || slot_words_b < 0) return 0;
+  // per side: the planes, the run starts, the status table
+  return 2 * rle_planes_bytes(S, H, W) + rle_starts_bytes(S, slot_words_a) + rle_starts_bytes(S, slot_words_b) + 2 * rle_status_bytes(S);
+}
+
+int hgl_rle_iou_device(const uint32_t* slots_a, long long slot_words_a, const int32_t* table_a, const uint32_t* slots_b,
+                       long long slot_words_b, const int32_t* table_b, int S, int H, int W, int64_t* iu, void* ws, size_t ws_bytes,
+                       void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(slots_a && table_a && slots_b && table_b && iu && S > 0 && H > 0 && W > 0 && slot_words_a >= 0 && slot_words_b >= 0,
+              "rle_iou_device: bad arguments");
+  HGL_REQUIRE((long long)H * W < (1ll << 31), "rle_iou_device: image too large (H*W must be < 2^31)");
+  HGL_REQUIRE((long long)S * H * W < (1ll << 31), "rle_iou_device: batch too large (S*H*W must be < 2^31)");
+  const int HW64 = (H + 63) / 64;
+  const unsigned Q = (unsigned)W * (unsigned)HW64;
+  const int q_tiles = (int)((Q + RLE_THREADS - 1) / RLE_THREADS);
+  HGL_REQUIRE((long long)S * q_tiles < (1ll << 31), "rle_iou_device: too many entries (%d) for one launch", S);
+  if (!ws || ws_bytes < hgl_rle_iou_workspace_bytes(S, H, W, slot_words_a, slot_words_b)) {
+    hgl_set_error("rle_iou_device: workspace too small");
+    return HGL_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* p = (char*)ws;
+  unsigned long long* plane[2];
+  uint32_t* E[2];
+  int32_t* status[2];
+  const uint32_t* slots[2] = {slots_a, slots_b};
+  const int32_t* table[2] = {table_a, table_b};
+  const long long sw[2] = {slot_words_a, slot_words_b};
+  for (int i = 0; i < 2; ++i) {
+    plane[i] = (unsigned long long*)p;
+    p += rle_planes_bytes(S, H, W);
+    E[i] = (uint32_t*)p;
+    p += rle_starts_bytes(S, sw[i]);
+    status[i] = (int32_t*)p;
+    p += rle_status_bytes(S);
+  }
+  for (int i = 0; i < 2; ++i) {
+    hipLaunchKernelGGL(rle_starts_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i], H, W, E[i], sw[i] + 1,
+                       status[i]);
+    hipLaunchKernelGGL(rle_plane_kernel, dim3((unsigned)(S * q_tiles)), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
+                       (const uint32_t*)E[i], sw[i] + 1, (const int32_t*)status[i], H, W, HW64, q_tiles, plane[i]);
+  }
+  hipLaunchKernelGGL(rle_iou_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)plane[0],
+                     (const unsigned long long*)plane[1], (const int32_t*)status[0], (const int32_t*)status[1], Q, (long long*)iu);
+  return hgl_check_launch("rle_iou_device");
 }
 
 }  // extern "C"

@@ -15,6 +15,8 @@ background is OpenCV's fixed-point GaussianBlur restated on the device (Hybridgl
     python -m hybridgl_amd.main --dataset refcocog --split val --fusion_mode G2L --synthetic 8
     python -m hybridgl_amd.main --dataset refcoco --split testA --real --refer_data_root ./refer/data
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m hybridgl_amd.main --real ...
+    python -m hybridgl_amd.main --synthetic 8 --save_masks out      # ... and later, with no model or checkpoint:
+    python -m hybridgl_amd.main --synthetic 8 --score_masks out     # the same report from the saved masks and the ground truth
 
 Under a launcher (WORLD_SIZE > 1) rank r evaluates the items i = r (mod R) of the loader's order and the metric rows
 are gathered once at the end (hybridgl_amd/dist.py); rank 0 writes the report.
@@ -85,6 +87,9 @@ def default_argument_parser():
     p.add_argument("--save_masks", default="", metavar="DIR",
                    help="every rank writes DIR/masks.rank{rank}.jsonl: one line per sentence with its two winning masks as COCO "
                         "RLE strings and its IoU counts (INTEGRATION.md); the files of all ranks together are the job's predictions")
+    p.add_argument("--score_masks", default="", metavar="DIR",
+                   help="score the predictions a run saved with --save_masks DIR against the dataset's ground truth, without any "
+                        "model or checkpoint (the dataset flags as in that run); exits non-zero when a stored count differs")
     return p
 
 
@@ -363,6 +368,88 @@ def build_models(args, dev):
     return model, gen, gem_model
 
 
+def dataset_items(args, dev, rank=0, world=1, sam_img_size=0, gem=False):
+    """(dataset object | None, this rank's job list, item maker i -> RefBatch | None) of the run that `args` describes:
+    PhraseCut, REFER or the seeded synthetic refs.  What evaluate() loops over and what --score_masks takes the ground truth from."""
+    from . import dist as D
+    if args.real and args.dataset == "phrasecut":
+        from .weights import CLIP_CONFIGS
+        rr = RealPhraseCut(args, dev, CLIP_CONFIGS[args.clip_model]["context_length"])
+        return rr, rr.jobs(rank, world), rr.load
+    if args.real:
+        from .weights import CLIP_CONFIGS
+        rr = RealRefs(args, dev, split_by(args.dataset), CLIP_CONFIGS[args.clip_model]["context_length"],
+                      device_transforms=not getattr(args, "host_transforms", False))
+        return rr, rr.jobs(rank, world), rr.load
+    from .pipeline import synthetic_ref
+    make = lambda i: synthetic_ref(i, dev, N=args.proposals, sam_img_size=sam_img_size, gem=gem, device_blur=True)[0]
+    return None, D.shard_indices(args.synthetic, rank, world), make
+
+
+def report_text(args, m, precision=None):
+    """the result lines of Hybridgl_main.py:233-248 / Hybridgl_main_PhraseCut.py:224-238"""
+    pc = args.dataset == "phrasecut"
+    return (f"\n\n fusion_mode={args.fusion_mode} "
+            + (f"\nDataset: PhraseCut / {args.split}" if pc else f"\nDataset: {args.dataset} / {args.split} / {split_by(args.dataset)}") +
+            f"\nOverall IoU / mean IoU"
+            f"\npure hybridgl: {m['oIoU']:.2f} / {m['mIoU']:.2f}"
+            f"\nhybridgl w/ spatial guidance: {m['oIoU_final']:.2f} / {m['mIoU_final']:.2f}"
+            + (f"\nprecision: {precision}" if precision is not None else ""))
+
+
+def write_report(args, text):
+    """append the result lines to the run's result log (Hybridgl_main.py:233-248) and print them"""
+    os.makedirs(args.result_dir, exist_ok=True)                         # Hybridgl_main.py:233-248
+    name = "result_log_PhraseCut.txt" if args.dataset == "phrasecut" else f"result_log_{args.dataset}_{args.split}.txt"
+    with open(os.path.join(args.result_dir, name), "a") as f:
+        f.write(text)
+    print(text)
+
+
+def score_masks(args, dev, directory=None):
+    """--score_masks DIR: the metrics of a saved run (--save_masks) from its files and the dataset's ground truth alone -- no
+    model is built, no checkpoint read.  The job list and the item makers are evaluate()'s; the target of a sentence is
+    Sentence.target when set, else RefBatch.target.  The saved strings are decoded and met with the targets on the device
+    (predictions.score: integer counts, exact), and every recomputed row is compared with the one the file stores.
+    Returns (metrics as dist.metrics_from_rows reports them, {"rows": [n,6] int64, "mismatches": keys whose stored counts
+    differ from the recomputed ones, "missing": dataset sentences without a record, "extra": records without a sentence})."""
+    from . import dist as D
+    from . import predictions as P
+    resolve_defaults(args)
+    records = P.load(directory or args.score_masks)
+    # the items as a run builds them, minus what only the models read: same indices, same targets
+    _, jobs, make = dataset_items(args, dev, 0, 1, sam_img_size=0, gem=False)
+
+    def targets():
+        for i in jobs:
+            ref = make(i)
+            if ref is None:
+                continue
+            index = ref.index if ref.index is not None else i
+            for j, sent in enumerate(ref.sentences):
+                yield (index, j), (sent.target if sent.target is not None else ref.target)
+
+    rows, missing, extra = P.score(records, targets())
+    stored = {(r["index"], r["sentence"]): [r["I"], r["U"], r["I_final"], r["U_final"]] for r in records}
+    mismatches = [(int(r[0]), int(r[1])) for r in rows if stored[(int(r[0]), int(r[1]))] != [int(v) for v in r[2:6]]]
+    return D.metrics_from_rows(rows), {"rows": rows, "mismatches": mismatches, "missing": missing, "extra": extra}
+
+
+def score_masks_main(args, dev):
+    """the --score_masks branch of main(): report, result log, exit status"""
+    m, rep = score_masks(args, dev)
+    for name, what in (("missing", "dataset sentence without a saved record"), ("extra", "saved record without a dataset sentence"),
+                       ("mismatches", "stored counts differ from the recomputed ones")):
+        for k in rep[name]:
+            print(f"{what}: index {k[0]} sentence {k[1]}")
+    print(f"scored {len(rep['rows'])} saved sentences from {args.score_masks}: {len(rep['mismatches'])} mismatching, "
+          f"{len(rep['missing'])} without a record, {len(rep['extra'])} without a sentence")
+    write_report(args, report_text(args, m))
+    if rep["mismatches"]:
+        raise SystemExit(1)
+    return m
+
+
 def save_masks(pipe, directory, rank=0):
     """--save_masks: DIR/masks.rank{rank}.jsonl, one JSON line per sentence this rank scored, keyed like dist.ROW_FIELDS:
     {"index": dataset position, "sentence": sentence number, "size": [H, W], "pure", "final": the winning masks (pure CLIP /
@@ -390,27 +477,14 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
     refs skipped)."""
     import time
     from .loader import Prefetcher
-    from .pipeline import EmptyProposals, HybridGLPipeline, synthetic_ref
+    from .pipeline import EmptyProposals, HybridGLPipeline
     from . import dist as D
     resolve_defaults(args)
     k_clamp = args.k_clamp if args.k_clamp != "auto" else ("persistent" if world == 1 else "per_ref")
     save_dir = getattr(args, "save_masks", "")
     pipe = HybridGLPipeline(model, fusion_mode=args.fusion_mode, masking_block=getattr(args, "masking_block", 9), mask_generator=gen,
                             use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir))
-    rr = None
-    if args.real and args.dataset == "phrasecut":
-        from .weights import CLIP_CONFIGS
-        rr = RealPhraseCut(args, dev, CLIP_CONFIGS[args.clip_model]["context_length"])
-        jobs, make = rr.jobs(rank, world), rr.load
-    elif args.real:
-        from .weights import CLIP_CONFIGS
-        rr = RealRefs(args, dev, split_by(args.dataset), CLIP_CONFIGS[args.clip_model]["context_length"],
-                      device_transforms=not getattr(args, "host_transforms", False))
-        jobs, make = rr.jobs(rank, world), rr.load
-    else:
-        jobs = D.shard_indices(args.synthetic, rank, world)
-        make = lambda i: synthetic_ref(i, dev, N=args.proposals, sam_img_size=1024 if gen else 0, gem=gem_model is not None,
-                                       device_blur=True)[0]
+    rr, jobs, make = dataset_items(args, dev, rank, world, sam_img_size=1024 if gen else 0, gem=gem_model is not None)
     # Hybridgl_main.py:45,79: DataLoader(num_workers=4) feeding the loop; here loader threads feed the grouped loop
     loader = Prefetcher(jobs, make, workers=args.workers, depth=2 * args.group + 2, device=dev)
     cap = getattr(args, "proposal_cap", 0) or None
@@ -453,11 +527,15 @@ def main(args):
                          "configs[0]) is covered by the oracle tests: python -m pytest tests -m 'not gpu'")
     rank, local_rank, world = D.env_rank()
     dev = torch.device("cuda", local_rank % torch.cuda.device_count())
+    if getattr(args, "score_masks", ""):      # before any model exists: files and ground truth only
+        if world > 1:
+            raise SystemExit("--score_masks runs on one rank: start it without a launcher (world size 1)")
+        torch.cuda.set_device(dev)
+        return score_masks_main(args, dev)
     cores = D.pin_rank_to_cores(local_rank, int(os.environ.get("LOCAL_WORLD_SIZE", world)))   # launch + loader threads of a rank on its own cores
     D.size_host_threads(cores, args.workers)
     torch.cuda.set_device(dev)
     dist = D.init_process_group(os.environ.get("HYBRIDGL_DIST_BACKEND", "nccl"), dev) if world > 1 else None
-    splitBy = split_by(args.dataset)
     model, gen, gem_model = build_models(args, dev)
     if rank == 0:
         print(f"fusion mode={args.fusion_mode}")
@@ -478,18 +556,7 @@ def main(args):
         stats["precision"] = args.precision
         stats["host_cores_per_rank"] = len(cores) if cores else len(os.sched_getaffinity(0))
         json.dump({"stats": stats, "metrics": m}, open(args.stats_json, "w"))
-    pc = args.dataset == "phrasecut"
-    text = (f"\n\n fusion_mode={args.fusion_mode} "
-            + (f"\nDataset: PhraseCut / {args.split}" if pc else f"\nDataset: {args.dataset} / {args.split} / {splitBy}") +
-            f"\nOverall IoU / mean IoU"
-            f"\npure hybridgl: {m['oIoU']:.2f} / {m['mIoU']:.2f}"
-            f"\nhybridgl w/ spatial guidance: {m['oIoU_final']:.2f} / {m['mIoU_final']:.2f}"
-            f"\nprecision: {args.precision}")
-    os.makedirs(args.result_dir, exist_ok=True)                         # Hybridgl_main.py:233-248
-    # Hybridgl_main.py:233-248 / Hybridgl_main_PhraseCut.py:224-238
-    with open(os.path.join(args.result_dir, "result_log_PhraseCut.txt" if pc else f"result_log_{args.dataset}_{args.split}.txt"), "a") as f:
-        f.write(text)
-    print(text)
+    write_report(args, report_text(args, m, args.precision))
     return m
 
 

@@ -376,6 +376,85 @@ def rle_encode(masks, sel=None, slot_words=None, out=None):
     return slots, table
 
 
+def rle_pack(counts_list, H, W, slot_words=None, device=None):
+    """Host run lengths -> what ops.rle_encode would hand out for them: (slots [S, slot_words] int32, table [S,4] int32) on
+    the device, every row in form 0.  counts_list: ragged lists / arrays of uint32 counts (column-major runs of H x W masks,
+    zeros first); slot_words: default the longest list (at least 1), so runs cross the bus and not ceil(H*W/32) words per
+    mask; a list longer than an explicit slot_words raises ValueError.  One pinned staging buffer, one host -> device copy
+    on the current stream; table columns 2 and 3 are 0 (the decoder does not read them)."""
+    import numpy as np
+    if int(H) <= 0 or int(W) <= 0:
+        raise ValueError(f"rle_pack: bad size {H} x {W}")
+    rows = [np.asarray(c, dtype=np.uint32).reshape(-1) for c in counts_list]
+    S = len(rows)
+    longest = max([len(r) for r in rows], default=0)
+    if slot_words is None:
+        slot_words = max(longest, 1)
+    slot_words = int(slot_words)
+    if longest > slot_words:
+        k = next(i for i, r in enumerate(rows) if len(r) > slot_words)
+        raise ValueError(f"rle_pack: entry {k} has {len(rows[k])} counts, slot_words is {slot_words}")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    stage = torch.zeros(S * (4 + slot_words), dtype=torch.int32, pin_memory=True)
+    slots, table = rle_split(stage.numpy(), S, slot_words)
+    for i, r in enumerate(rows):
+        table[i, 0] = len(r)
+        slots[i, :len(r)] = r.view(np.int32)
+    flat = stage.to(device, non_blocking=True)
+    return rle_split(flat, S, slot_words)
+
+
+def _rle_set(slots, table, name):
+    """(slots pointer, slot_words, table pointer, S) of one encoded set: int32 device tensors [S, slot_words] and [S, 4]"""
+    if slots.dim() != 2 or table.dim() != 2 or table.shape[1] != 4 or table.shape[0] != slots.shape[0]:
+        raise ValueError(f"{name}: expected slots [S, slot_words] and table [S, 4], got {tuple(slots.shape)} and {tuple(table.shape)}")
+    return _dev(slots, torch.int32, name + " slots"), int(slots.shape[1]), _dev(table, torch.int32, name + " table"), int(slots.shape[0])
+
+
+def rle_decode(slots, table, H, W, out=None):
+    """The inverse of rle_encode on the device: hgl_rle_decode_device on the current stream, no synchronisation.  slots /
+    table: what rle_encode or rle_pack returns (form 0: counts, form 1: the bit plane).  Returns (masks [S,H,W] uint8 0 / 1,
+    status [S,4] int32 = code, area, 0, 0): code 0 = decoded, 1 = decoded but the counts do not sum to H*W (clipped as the
+    host codec clips), 2 = the slot holds no mask (zeros) (include/hybridgl.h).  `out`: a contiguous uint8 device tensor of
+    exactly S*H*W elements to decode into; every byte of it is written."""
+    lib = _lib.load()
+    H, W = int(H), int(W)
+    sp, sw, tp, S = _rle_set(slots, table, "rle_decode")
+    if out is None:
+        out = torch.empty(S * H * W, dtype=torch.uint8, device=slots.device)
+    elif out.numel() != S * H * W:
+        raise ValueError(f"out: expected {S * H * W} uint8 elements, got {out.numel()}")
+    status = torch.empty((S, 4), dtype=torch.int32, device=slots.device)
+    masks = out.view(S, H, W)
+    if S == 0:
+        return masks, status
+    op = _dev(out, torch.uint8, "out")
+    need = lib.hgl_rle_decode_workspace_bytes(S, H, W, sw)
+    ws = workspace(need, slots.device, "rle")
+    check(lib.hgl_rle_decode_device(sp, sw, tp, S, H, W, op, status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "hgl_rle_decode_device")
+    return masks, status
+
+
+def rle_iou(slots_a, table_a, slots_b, table_b, H, W):
+    """(|A & B|, |A | B|) of entry s of one encoded set against entry s of another, int64 [S,2] on the device, computed on
+    bit planes (hgl_rle_iou_device; no mask is expanded to bytes).  (-1, -1) where either slot holds no mask."""
+    lib = _lib.load()
+    H, W = int(H), int(W)
+    ap, asw, atp, S = _rle_set(slots_a, table_a, "rle_iou a")
+    bp, bsw, btp, Sb = _rle_set(slots_b, table_b, "rle_iou b")
+    if S != Sb:
+        raise ValueError(f"rle_iou: the sets have {S} and {Sb} entries")
+    iu = torch.empty((S, 2), dtype=torch.int64, device=slots_a.device)
+    if S == 0:
+        return iu
+    need = lib.hgl_rle_iou_workspace_bytes(S, H, W, asw, bsw)
+    ws = workspace(need, slots_a.device, "rle")
+    check(lib.hgl_rle_iou_device(ap, asw, atp, bp, bsw, btp, S, H, W, iu.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "hgl_rle_iou_device")
+    return iu
+
+
 def score_sentence(hybrid, sentence_feat, noun_phrase_feat, other_noun_feats, boxes, gem_score,
                    logit_scale=100.0, r=0.5, k1=3, k2=6, alpha=0.6, relaword="none", has_other_nouns=False):
     """Per-sentence tail (Hybridgl_main.py:153-196,225-228).

@@ -1311,6 +1311,46 @@ def rle_to_mask(rle):
     return out.astype(bool)
 
 
+def rle_counts_from_string(s):
+    """The counts of a COCO compressed RLE string (str / bytes) as a uint32 array: the native restatement of
+    maskApi.c:217-230 rleFrString without the decode (hgl_rle_from_string).  Raises on a malformed string."""
+    lib = _lib.load()
+    b = s.encode("ascii") if isinstance(s, str) else bytes(s)
+    counts = np.empty(max(len(b), 1), dtype=np.uint32)      # every count takes at least one character
+    m = C.c_longlong(0)
+    check(lib.hgl_rle_from_string(C.c_char_p(b), counts.ctypes.data, len(counts), C.byref(m)), "hgl_rle_from_string")
+    return counts[:m.value]
+
+
+def rle_counts(rle):
+    """the counts of an RLE dict as a uint32 array, whichever form it carries them in (list / array, or COCO string / bytes)"""
+    c = rle["counts"]
+    if isinstance(c, (str, bytes, bytearray)):
+        return rle_counts_from_string(c)
+    return np.ascontiguousarray(np.asarray(c, dtype=np.uint32)).reshape(-1)
+
+
+def rles_to_masks(rles, device=None):
+    """rle_to_mask for a list of RLE dicts {"size": [h, w], "counts": list | COCO string / bytes} of ONE size, decoded on the
+    device: the runs cross the bus (ops.rle_pack: one copy), the pixels are formed there (ops.rle_decode).  Returns a bool
+    [n,H,W] device tensor.  Raises ValueError naming the first entry whose counts do not sum to H*W (one read-back of the
+    status table)."""
+    if len(rles) == 0:
+        raise ValueError("rles_to_masks: no entries (the size of the result is the entries')")
+    h, w = (int(v) for v in rles[0]["size"])
+    for i, r in enumerate(rles):
+        if [int(v) for v in r["size"]] != [h, w]:
+            raise ValueError(f"rles_to_masks: entry {i} has size {list(r['size'])}, entry 0 has {[h, w]}")
+    slots, table = ops.rle_pack([rle_counts(r) for r in rles], h, w, device=device)
+    masks, status = ops.rle_decode(slots, table, h, w)
+    code = status[:, 0].cpu().numpy()
+    bad = np.flatnonzero(code != 0)
+    if len(bad):
+        raise ValueError(f"rles_to_masks: entry {int(bad[0])} does not decode to a {h} x {w} mask (status {int(code[bad[0]])}: "
+                         "its counts do not sum to H*W)")
+    return masks.view(torch.bool)
+
+
 def area_from_rle(rle):
     """utils/amg.py:154-155."""
     return sum(rle["counts"][1::2])

@@ -666,6 +666,34 @@ int hgl_rle_to_string(const uint32_t* counts, long long m, char* out, size_t cap
 size_t hgl_rle_encode_workspace_bytes(int S, int H, int W);
 int hgl_rle_encode_device(const uint8_t* masks, int N, int H, int W, const int64_t* sel, int S, uint32_t* slots,
                           long long slot_words, int32_t* table, void* ws, size_t ws_bytes, void* stream);
+/* The counts of a compressed COCO RLE string (maskApi.c:217-230 rleFrString without the decode).  HOST memory.  *m = the
+ * true number of counts, always; with counts == NULL or cap too small nothing is written beyond cap (size query, as
+ * hgl_rle_encode_mask).  A group cut off by the end of the string, or longer than 7 characters, is an error. */
+int hgl_rle_from_string(const char* s, uint32_t* counts, long long cap, long long* m);
+/* The way back on the DEVICE (csrc/rle.hip): masks out of exactly what hgl_rle_encode_device writes, so that encode ->
+ * decode composes with no host in between, and intersection / union of two encoded sets without expanding either.
+ * Asynchronous on `stream`; no host synchronisation, allocation or atomics; two calls give the same bytes.
+ * slots: device [S, slot_words]; table: device [S,4] = (n_counts, form, ., .), columns 2 and 3 are not read.
+ *   form 0  the slot holds n_counts counts (column-major runs, zeros first; zero-length runs anywhere are legal)
+ *   form 1  the slot holds the column-major bit plane, bit p % 32 of word p / 32 with p = x*H + y; bits beyond H*W ignored
+ * masks: device [S,H,W] row-major uint8, values 0 / 1; every byte of every entry is written (no need to clear), none
+ * outside [0, S*H*W).  status: device [S,4] = (code, area, 0, 0), area = foreground pixels written.
+ *   code 0  decoded, and (form 0) the counts sum to exactly H*W
+ *   code 1  form 0 whose counts do not sum to H*W: decoded as the host codec decodes it (hgl_gt_mask_from_rle_counts):
+ *           runs clipped at H*W (positions are summed in 64 bits: [0xFFFFFFFF, 5] does not wrap), pixels past the last
+ *           run are 0
+ *   code 2  the slot holds no mask: form 2 or 3 or any other form value, n_counts < 0, n_counts > slot_words in form 0,
+ *           ceil(H*W/32) > slot_words in form 1; the mask is all zeros
+ * hgl_rle_iou_device: iu device [S,2] int64 = (|A & B|, |A | B|) of entry s of A against entry s of B, on bit planes in
+ * the workspace; (-1, -1) when either entry would have code 2; code-1 entries count as decoded.
+ * Limits: H*W < 2^31 and S*H*W < 2^31.  ws: the size the matching workspace query returns (HGL_EWORKSPACE when smaller). */
+size_t hgl_rle_decode_workspace_bytes(int S, int H, int W, long long slot_words);
+int hgl_rle_decode_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S, int H, int W,
+                          uint8_t* masks, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+size_t hgl_rle_iou_workspace_bytes(int S, int H, int W, long long slot_words_a, long long slot_words_b);
+int hgl_rle_iou_device(const uint32_t* slots_a, long long slot_words_a, const int32_t* table_a,
+                       const uint32_t* slots_b, long long slot_words_b, const int32_t* table_b,
+                       int S, int H, int W, int64_t* iu, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

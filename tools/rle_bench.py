@@ -11,7 +11,14 @@
   evaluator  (--evaluator) HybridGLPipeline.run at the benchmark's configuration (ViT-B/16, SAM ViT-H feeding CLIP, GEM
              heat-maps, 64 proposals, groups of 16) with record_predictions off and on, alternating, refs/s each
 
+  decode     (--decode, instead of the legs above) the way back: ops.rle_decode for 64 and for 6 blob masks of 640 x 640 and
+             ops.rle_iou for 64 pairs (HIP events, median of --reps after warm-up), the decoder's time against ONE streaming
+             write of the S*H*W output bytes (a fill of the same buffer, timed the same way), and the host wall time of the
+             path it replaces: sam.rle_to_mask per mask plus the upload, both sides ending in a synchronise; writes
+             profiles/rle_decode_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
+    python tools/rle_bench.py --decode [--reps 30]
 """
 import argparse
 import json
@@ -127,14 +134,78 @@ def evaluator_leg(dev, steps, group=16, proposals=64, rounds=3):
             "sentences_recorded": n_pred, "host_bytes_of_counts": 4 * runs, "staging_buffers": len(pipes["on"]._pred_free)}
 
 
+def decode_leg(masks, reps):
+    """masks: [64,H,W] uint8 blobs on the device.  The inputs of the decoder are the runs as a saved set holds them: packed
+    counts (ops.rle_pack), form 0."""
+    N, H, W = masks.shape
+    dev = masks.device
+    rles = hsam.masks_to_rle(masks)
+    host = masks.cpu().numpy()
+    rec = {"H": H, "W": W, "counts_per_mask_max": max(len(r["counts"]) for r in rles)}
+    for name, S in (("64_masks", 64), ("6_masks", 6)):
+        part = rles[:S]
+        slots, table = ops.rle_pack([r["counts"] for r in part], H, W, device=dev)
+        out = torch.empty(S * H * W, dtype=torch.uint8, device=dev)
+        got, status = ops.rle_decode(slots, table, H, W, out=out)
+        assert np.array_equal(got.cpu().numpy(), host[:S]) and not status[:, 0].any()
+        us = device_us(lambda: ops.rle_decode(slots, table, H, W, out=out), reps)
+        us_fill = device_us(lambda: out.fill_(1), reps)      # the yardstick: one streaming write of the output bytes
+        nbytes = S * H * W
+
+        def host_path():
+            up = [torch.from_numpy(hsam.rle_to_mask(r)).to(dev) for r in part]
+            torch.cuda.synchronize()
+            return up
+
+        def device_path():
+            m = hsam.rles_to_masks(part, device=dev)      # pack + copy + decode + the status read-back (a synchronise)
+            torch.cuda.synchronize()
+            return m
+
+        h, d = host_ms(host_path, max(3, reps // 3)), host_ms(device_path, max(3, reps // 3))
+        rec[name] = {"entries": S, "output_bytes": nbytes, "slot_words": int(slots.shape[1]), "input_bytes": int(slots.numel() * 4),
+                     "rle_decode_us": round(us, 1), "TBps_of_one_write": round(nbytes / us / 1e6, 3), "fill_same_bytes_us": round(us_fill, 1),
+                     "fill_TBps": round(nbytes / us_fill / 1e6, 3), "time_over_streaming_write": round(us / us_fill, 2),
+                     "host_decode_and_upload_ms": round(h, 2), "rles_to_masks_ms": round(d, 2), "host_over_device_wall": round(h / d, 2),
+                     "host_over_decode_kernels": round(h * 1e3 / us, 1)}
+    a_s, a_t = ops.rle_pack([r["counts"] for r in rles], H, W, device=dev)
+    b_s, b_t = ops.rle_pack([r["counts"] for r in rles[1:] + rles[:1]], H, W, device=dev)
+    iu = ops.rle_iou(a_s, a_t, b_s, b_t, H, W).cpu().numpy()
+    hb = np.roll(host, -1, axis=0)
+    assert iu.tolist() == [[int((x & y).sum()), int((x | y).sum())] for x, y in zip(host, hb)]
+    us = device_us(lambda: ops.rle_iou(a_s, a_t, b_s, b_t, H, W), reps)
+    da, db = masks, torch.roll(masks, -1, 0).contiguous()
+    us_bytes = device_us(lambda: [ops.iou_counts(da[i], db[i]) for i in range(N)], reps)
+    rec["iou_64_pairs"] = {"entries": N, "rle_iou_us": round(us, 1), "hgl_iou_on_bytes_64_launches_us": round(us_bytes, 1),
+                           "mask_bytes_never_formed": 2 * N * H * W}
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
     ap.add_argument("--steps", type=int, default=64)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rle_bench.py needs a GPU"
     dev = torch.device("cuda:0")
+    if args.decode:
+        rng = np.random.default_rng(7)
+        yy, xx = np.mgrid[0:640, 0:640]
+        blob = np.zeros((64, 640, 640), np.uint8)
+        for i in range(64):      # seeded unions of ellipses, as the tests' blobs
+            for _ in range(int(rng.integers(1, 4))):
+                cy, cx, ry, rx = rng.random() * 640, rng.random() * 640, (0.05 + 0.3 * rng.random()) * 640, (0.05 + 0.3 * rng.random()) * 640
+                blob[i] |= (((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1).astype(np.uint8)
+        out = {"decode": decode_leg(torch.from_numpy(blob).to(dev), args.reps), "reps": args.reps,
+               "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_decode_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
     masks = torch.from_numpy(np.ascontiguousarray(synth.synth_masks(64, 640, 640, 2000))).to(dev).view(torch.uint8)
     out = {"kernel": kernel_leg(masks, args.reps), "generator": generator_leg(masks, args.reps)}
     if args.evaluator:
