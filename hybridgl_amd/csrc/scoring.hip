@@ -6,8 +6,10 @@
 //   synthesize_views     Hybridgl_main.py:93-125
 #include "hgl_common.h"
 #include <mutex>
+#include <vector>
 #include <condition_variable>
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 namespace {
@@ -106,20 +108,22 @@ __device__ __forceinline__ float dir_weight(int dirflag, int x, int W) {
 constexpr int PX_LANE = 16;
 constexpr int PIX_PER_BLOCK = 256 * PX_LANE;  // 4096
 
-constexpr int MASK_GROUP = 8;  // masks per blockIdx.y
-// the per-group pooling (three sentences of up to sixteen refs per launch: enough workgroups without splitting the masks
-// eight ways; a single ref's launch keeps eight: 139 against 130 us with 32): the normalised heat-map values of a block's pixels -- a division and a direction weight per pixel -- are
-// computed once per 32 masks instead of once per 8.  The partial sums per (mask, part) do not depend on the grouping.
+// masks per pooling workgroup (blockIdx.y), both by measurement: 8 for the per-sentence pooling and for hgl_score_ref (the
+// launch of a single ref needs the workgroups: 130 against 139 us with 32), 32 for hgl_score_group (three sentences of up to
+// sixteen refs per launch are enough workgroups without splitting the masks eight ways, and the normalised heat-map values of a
+// block's pixels -- a division and a direction weight per pixel -- are computed once per 32 masks instead of once per 8).  The
+// partial sums per (mask, part) do not depend on the grouping.
+constexpr int MASK_GROUP = 8;
 constexpr int REF_MASK_GROUP = 32;
 
-// ---- the pooling of a block, shared by the three pooling kernels (one heat-map / the maps of a ref / of a group of refs) -----
+// ---- the pooling of a block, shared by the pooling kernels (one heat-map / the maps of the rows of a table) --------------------
 // One workgroup = PIX_PER_BLOCK consecutive pixels x a group of masks x UP TO FOUR heat-maps at once: the normalised values of
 // the maps at the lane's 16 pixels live in registers (16 VGPRs per map), and a mask's 16 bytes are loaded ONCE, turned into
 // sixteen 0.0 / 1.0 floats once, and multiplied into all the maps: cvt + one fma per (pixel, map) instead of a 64-bit select
 // and a double-precision add per (pixel, map) and a re-read of the bytes per map.  (Until round 5 every (block, group, map) was
 // its own workgroup with a double-precision sum per pixel: 130 vector instructions per KiB of mask bytes and map, the bytes
 // fetched S times -- 1.37 TB/s on the algorithmic bytes, instruction-bound.)
-// Arithmetic of one (map, mask, wave) partial -- THE definition all three kernels share, so their results are the same bits:
+// Arithmetic of one (map, mask, wave) partial -- THE definition the pooling kernels share, so their results are the same bits:
 //   lane: a = 0; for e = 0..15 in order: a = fma(m_e, v_e, a) in fp32 (m_e is 0 or 1: the products are exact, the 16-term sum
 //   carries at most a few 1e-8 of relative error); the 64 lane sums folded in fp32 by pool_sum_f's fixed DPP tree; the wave's
 //   sum widened to double; partials over a mask's waves are added in double by the scoring kernels as before.
@@ -170,7 +174,7 @@ struct DirRamp {
 // per step (v_add_f32 with a DPP operand).  (__shfl_xor compiles to ds_bpermute_b32: a double-precision butterfly was twelve
 // LDS-crossbar operations and six adds per (mask, map), as much of the loop as its arithmetic; the DPP form in double costs three
 // instructions per step.)  The wave's 1024 products are thus summed in fp32 -- as the reference sums ALL its products
-// (Hybridgl_main.py:221, torch.sum of an fp32 tensor) -- in a fixed tree: deterministic, and the same function in all three
+// (Hybridgl_main.py:221, torch.sum of an fp32 tensor) -- in a fixed tree: deterministic, and the same function in all
 // pooling kernels; partials of different waves are added in double by the scoring kernels.
 template <int CTRL, int ROWS>
 __device__ __forceinline__ float pool_dpp_f(float v) {
@@ -342,57 +346,16 @@ __global__ __launch_bounds__(256) void coherence_final_kernel(const double* __re
 }
 
 // ---- IoU ----
-__global__ __launch_bounds__(256) void iou_kernel(const uint8_t* __restrict__ p,
-                                                  const uint8_t* __restrict__ g, long long n,
-                                                  unsigned long long* __restrict__ out) {
-  unsigned I = 0, U = 0;
-  const long long n16 = n / 16;
-  const bool al = (((uintptr_t)p | (uintptr_t)g) & 15) == 0;
-  if (al) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n16;
-         i += (long long)gridDim.x * blockDim.x) {
-      const uint4 a = ((const uint4*)p)[i], b = ((const uint4*)g)[i];
-      const unsigned aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        // nonzero byte -> 0x01 per byte
-        unsigned x = aw[w], y = bw[w];
-        x |= x >> 4; x |= x >> 2; x |= x >> 1; x &= 0x01010101u;
-        y |= y >> 4; y |= y >> 2; y |= y >> 1; y &= 0x01010101u;
-        I += __popc(x & y);
-        U += __popc(x | y);
-      }
-    }
-  }
-  const long long tail0 = al ? n16 * 16 : 0;
-  for (long long i = tail0 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    const bool a = p[i] != 0, b = g[i] != 0;
-    I += (a && b);
-    U += (a || b);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    I += __shfl_xor(I, o);
-    U += __shfl_xor(U, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicAdd(&out[0], (unsigned long long)I);
-    atomicAdd(&out[1], (unsigned long long)U);
-  }
-}
-
-// same with pred = masks[idx[which]] resolved on the device
-__global__ __launch_bounds__(256) void iou_select_kernel(const uint8_t* __restrict__ masks,
-                                                         const int* __restrict__ idx, int which,
-                                                         const uint8_t* __restrict__ g, long long n,
-                                                         unsigned long long* __restrict__ out) {
-  const uint8_t* p = masks + (long long)idx[which] * n;
+// |p & g| and |p | g| (a byte counts when it is not zero) over ONE BLOCK's share of two planes of n bytes, folded over each wave
+// (valid in every lane): the blocks of the grid's x dimension stride over the planes, 16 bytes per thread and trip when both
+// planes start on a 16-byte boundary (nonzero byte -> 0x01 per byte, popcount), byte by byte otherwise and for the last n % 16.
+// THE count of hgl_iou, hgl_iou_select and the fused tail (integers: no order to keep).
+__device__ __forceinline__ void iou_count_wave(const uint8_t* __restrict__ p, const uint8_t* __restrict__ g, long long n, unsigned& Iout,
+                                               unsigned& Uout) {
   unsigned I = 0, U = 0;
   const bool al = ((((uintptr_t)p) | ((uintptr_t)g)) & 15) == 0;
   const long long n16 = al ? n / 16 : 0;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n16;
-       i += (long long)gridDim.x * blockDim.x) {
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n16; i += (long long)gridDim.x * 256) {
     const uint4 a = ((const uint4*)p)[i], b = ((const uint4*)g)[i];
     const unsigned aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
@@ -404,8 +367,7 @@ __global__ __launch_bounds__(256) void iou_select_kernel(const uint8_t* __restri
       U += __popc(x | y);
     }
   }
-  for (long long i = n16 * 16 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
+  for (long long i = n16 * 16 + blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const bool a = p[i] != 0, b = g[i] != 0;
     I += (a && b);
     U += (a || b);
@@ -415,6 +377,28 @@ __global__ __launch_bounds__(256) void iou_select_kernel(const uint8_t* __restri
     I += __shfl_xor(I, o);
     U += __shfl_xor(U, o);
   }
+  Iout = I;
+  Uout = U;
+}
+
+__global__ __launch_bounds__(256) void iou_kernel(const uint8_t* __restrict__ p,
+                                                  const uint8_t* __restrict__ g, long long n,
+                                                  unsigned long long* __restrict__ out) {
+  unsigned I, U;
+  iou_count_wave(p, g, n, I, U);
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&out[0], (unsigned long long)I);
+    atomicAdd(&out[1], (unsigned long long)U);
+  }
+}
+
+// same with pred = masks[idx[which]] resolved on the device
+__global__ __launch_bounds__(256) void iou_select_kernel(const uint8_t* __restrict__ masks,
+                                                         const int* __restrict__ idx, int which,
+                                                         const uint8_t* __restrict__ g, long long n,
+                                                         unsigned long long* __restrict__ out) {
+  unsigned I, U;
+  iou_count_wave(masks + (long long)idx[which] * n, g, n, I, U);
   if ((threadIdx.x & 63) == 0) {
     atomicAdd(&out[0], (unsigned long long)I);
     atomicAdd(&out[1], (unsigned long long)U);
@@ -661,14 +645,15 @@ __global__ __launch_bounds__(256) void score_sentence_kernel(
                       idx, score_clip, score_neg, soft_scratch);
 }
 
-// ---- the tail of a whole REF (all its sentences) in four launches: Hybridgl_main.py:153-230 -------------------------------
+// ---- the tail of whole REFS (all their sentences) in four launches: Hybridgl_main.py:153-230 ------------------------------
+// (the device bodies; the kernels that run them over a table of refs follow, the host path is tail_launch below)
 // The per-sentence launches above re-read the N mask planes for every sentence (83.6 MB per ref at N = 64, 640 x 640, three
 // sentences) and cost ~15 launches per sentence with torch glue between them.  Here the pooling of ALL sentences' heat-maps is
 // one launch (the mask planes come from HBM once: the other maps' workgroups find them in L2 / the Infinity Cache), the
 // scoring of the sentences runs as one workgroup each in one launch, the IoU of
 // both winners of every sentence in one launch, and the four accumulators of Hybridgl_main.py:52-55 are updated by the
 // last block of that launch.  Arithmetic and reduction orders are those of the per-sentence kernels (bit-identical results).
-constexpr int REF_MAXS = 16;       // sentences per launch (the host loops over chunks)
+constexpr int REF_MAXS = 16;       // sentences per row of a launch (a ref with more takes several rows: tail_push_rows)
 constexpr int REF_MM_BLOCKS = 64;  // min / max partials per heat-map
 
 struct RefSentences {
@@ -703,10 +688,6 @@ __device__ __forceinline__ void ref_minmax_body(const float* __restrict__ a, int
     p[1] = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
   }
 }
-__global__ __launch_bounds__(256) void ref_minmax_kernel(RefSentences rs, long long n, float* __restrict__ part_mm) {
-  ref_minmax_body(rs.attn[blockIdx.y], blockIdx.y, n, part_mm);
-}
-
 // min / max are exact in any order: every wave folds the 64 partial pairs of a map itself (one pair per lane)
 __device__ __forceinline__ void ref_fold_minmax(const float* __restrict__ part_mm, int s, int lane, float& mn, float& mx) {
   const float* p = part_mm + ((long long)s * REF_MM_BLOCKS + lane) * 2;
@@ -774,20 +755,6 @@ __device__ __forceinline__ void ref_masked_pool_last(int blk, const float* const
     const PoolMap pm[1] = {{attn[sj], dirflag[sj], sj, mn, mx - mn}};
     pool_block<1, false>(blk, pm, n0, n1, masks, N, H, W, mask_group == 0, part_sum, part_cnt, part_tot, nparts);
   }
-}
-
-template <int CH>
-__global__ __launch_bounds__(256) void ref_masked_pool_kernel(RefSentences rs, int S, const uint8_t* __restrict__ masks, int N, int H,
-                                                              int W, const float* __restrict__ part_mm, double* __restrict__ part_sum,
-                                                              unsigned* __restrict__ part_cnt, double* __restrict__ part_tot,
-                                                              int nparts) {
-  ref_masked_pool_body<MASK_GROUP, CH>(blockIdx.x, rs.attn, rs.dirflag, S, blockIdx.y, masks, N, H, W, part_mm, part_sum, part_cnt, part_tot, nparts);
-}
-__global__ __launch_bounds__(256) void ref_masked_pool_last_kernel(RefSentences rs, int S, const uint8_t* __restrict__ masks, int N, int H,
-                                                                   int W, const float* __restrict__ part_mm, double* __restrict__ part_sum,
-                                                                   unsigned* __restrict__ part_cnt, double* __restrict__ part_tot,
-                                                                   int nparts, int blk) {
-  ref_masked_pool_last<MASK_GROUP>(blk, rs.attn, rs.dirflag, S, blockIdx.y, masks, N, H, W, part_mm, part_sum, part_cnt, part_tot, nparts);
 }
 
 // one workgroup per sentence: coherence_final_kernel's reduction for its N masks, then the sentence's scoring
@@ -868,48 +835,11 @@ __device__ __forceinline__ void ref_score_body(const RefSentences& rs, int s, bo
                       soft_all + (long long)s * (2 * N + 2 * E));
 }
 
-__global__ __launch_bounds__(256) void ref_score_kernel(RefSentences rs, const float* __restrict__ hybrid, const float* __restrict__ text,
-                                                        const long long* __restrict__ boxes, int N, int E, int H, int W,
-                                                        float logit_scale, float r_mix, int k1, int k2, float alpha,
-                                                        const double* __restrict__ part_sum, const unsigned* __restrict__ part_cnt,
-                                                        const double* __restrict__ part_tot, int nparts, float* __restrict__ gem_all,
-                                                        float* __restrict__ clip_all, float* __restrict__ neg_all,
-                                                        float* __restrict__ soft_all, int* __restrict__ idx_all,
-                                                        unsigned long long* __restrict__ iu_all, unsigned* __restrict__ done) {
-  ref_score_body(rs, blockIdx.x, blockIdx.x == 0, hybrid, text, boxes, N, E, H, W, logit_scale, r_mix, k1, k2, alpha, part_sum, part_cnt,
-                 part_tot, nparts, gem_all, clip_all, neg_all, soft_all, idx_all, iu_all, done);
-}
-
-// Compute_IoU of both winners of every sentence: grid (blocks, 2 S); the last block to finish adds the ref's counts to
-// the running accumulators cum_I, cum_U, cum_I_final, cum_U_final (integers: order-free)
-// I / U of one block's share of a (mask, target) pair, reduced over the block: valid in thread 0
+// Compute_IoU of both winners of every sentence: I / U of one block's share of a (mask, target) pair, reduced over the block
 __device__ __forceinline__ void ref_iou_block(const uint8_t* __restrict__ p, const uint8_t* __restrict__ g, long long n, unsigned& Iout,
                                               unsigned& Uout) {
-  unsigned I = 0, U = 0;
-  const bool al = ((((uintptr_t)p) | ((uintptr_t)g)) & 15) == 0;
-  const long long n16 = al ? n / 16 : 0;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n16; i += (long long)gridDim.x * 256) {
-    const uint4 a = ((const uint4*)p)[i], b = ((const uint4*)g)[i];
-    const unsigned aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      unsigned x = aw[w], y = bw[w];
-      x |= x >> 4; x |= x >> 2; x |= x >> 1; x &= 0x01010101u;
-      y |= y >> 4; y |= y >> 2; y |= y >> 1; y &= 0x01010101u;
-      I += __popc(x & y);
-      U += __popc(x | y);
-    }
-  }
-  for (long long i = n16 * 16 + blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const bool a = p[i] != 0, b = g[i] != 0;
-    I += (a && b);
-    U += (a || b);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    I += __shfl_xor(I, o);
-    U += __shfl_xor(U, o);
-  }
+  unsigned I, U;
+  iou_count_wave(p, g, n, I, U);
   __shared__ unsigned sI[4], sU[4];
   if ((threadIdx.x & 63) == 0) {
     sI[threadIdx.x >> 6] = I;
@@ -920,35 +850,14 @@ __device__ __forceinline__ void ref_iou_block(const uint8_t* __restrict__ p, con
   Uout = (sU[0] + sU[1]) + (sU[2] + sU[3]);
 }
 
-__global__ __launch_bounds__(256) void ref_iou_kernel(RefSentences rs, int S, const uint8_t* __restrict__ masks, long long n,
-                                                      const int* __restrict__ idx_all, unsigned long long* __restrict__ iu_all,
-                                                      unsigned long long* __restrict__ cum, unsigned* __restrict__ done) {
-  const int s = blockIdx.y >> 1, which = blockIdx.y & 1;
-  unsigned I, U;
-  ref_iou_block(masks + (long long)idx_all[2 * s + which] * n, rs.target[s], n, I, U);
-  // one pair of atomics per BLOCK (thousands of 64-bit atomics on two dozen addresses serialise in L2: 68 us for six IoUs)
-  __shared__ int last;
-  if (threadIdx.x == 0) {
-    atomicAdd(&iu_all[4 * s + 2 * which], (unsigned long long)I);
-    atomicAdd(&iu_all[4 * s + 2 * which + 1], (unsigned long long)U);
-    __threadfence();
-    last = atomicAdd(done, 1u) == gridDim.x * gridDim.y - 1;
-  }
-  __syncthreads();
-  if (last && cum != nullptr && threadIdx.x < 4) {
-    unsigned long long a = 0;
-    for (int j = 0; j < S; ++j) a += atomicAdd(&iu_all[4 * j + threadIdx.x], 0ull);   // coherent read of the other blocks' sums
-    cum[threadIdx.x] += a;
-  }
-}
-
-// ---- the tail of a whole GROUP of refs in the same four launches (hgl_score_group) -------------------------------------------
-// hgl_score_ref is four launches per ref of ~31 MB each: latency-bound by construction (pooling 33 us per ref = 0.9 TB/s on
-// its algorithmic bytes).  The grouped loop scores the refs of a group (16 images) back to back, so the same kernels run over
-// ALL of them at once: a table of per-ref descriptors in device memory (shapes differ from ref to ref), grids sized by the
-// largest ref with the others' surplus blocks leaving at once, ~0.5 GB per pooling launch.  A block executes the per-ref
-// kernels' bodies on its ref's operands: identical arithmetic and reduction order, identical rows.
-constexpr int GRP_MAXR = 16;       // refs per launch (the host loops over chunks)
+// ---- the kernels of the fused tail: the bodies above over a TABLE of rows (hgl_score_ref: the rows of one ref; hgl_score_group:
+// of a group of refs) ---------------------------------------------------------------------------------------------------------
+// Four launches per ref of ~31 MB each are latency-bound by construction (pooling 33 us per ref = 0.9 TB/s on its algorithmic
+// bytes).  The grouped loop scores the refs of a group (16 images) back to back, so the kernels run over ALL of them at once: a
+// table of per-row descriptors in device memory (shapes differ from ref to ref), grids sized by the largest row with the
+// others' surplus blocks leaving at once, ~0.5 GB per pooling launch.  A block executes the bodies on its row's operands: the
+// rows of a ref do not depend on what else the table holds.
+constexpr int GRP_MAXR = 16;       // rows per launch (the host loops over chunks)
 struct GroupRefDev {
   RefSentences rs;
   int S, N, H, W, k1, k2, nparts, nblk;
@@ -971,20 +880,22 @@ __global__ __launch_bounds__(256) void grp_minmax_kernel(const GroupRefDev* __re
   ref_minmax_body(g.rs.attn[s], s, (long long)g.H * g.W, g.part_mm);
 }
 
-template <int CH>
+// MG: masks per pooling workgroup (MASK_GROUP for hgl_score_ref, REF_MASK_GROUP for hgl_score_group: see above)
+template <int MG, int CH>
 __global__ __launch_bounds__(256) void grp_masked_pool_kernel(const GroupRefDev* __restrict__ tab) {
   const GroupRefDev& g = tab[blockIdx.z];
   const int nfull = (int)(((long long)g.H * g.W) / PIX_PER_BLOCK);
-  if ((int)blockIdx.x >= nfull || (int)blockIdx.y * REF_MASK_GROUP >= g.N) return;
-  ref_masked_pool_body<REF_MASK_GROUP, CH>(blockIdx.x, g.rs.attn, g.rs.dirflag, g.S, blockIdx.y, g.masks, g.N, g.H, g.W, g.part_mm, g.part_sum,
-                                       g.part_cnt, g.part_tot, g.nparts);
+  if ((int)blockIdx.x >= nfull || (int)blockIdx.y * MG >= g.N) return;
+  ref_masked_pool_body<MG, CH>(blockIdx.x, g.rs.attn, g.rs.dirflag, g.S, blockIdx.y, g.masks, g.N, g.H, g.W, g.part_mm, g.part_sum,
+                               g.part_cnt, g.part_tot, g.nparts);
 }
+template <int MG>
 __global__ __launch_bounds__(256) void grp_masked_pool_last_kernel(const GroupRefDev* __restrict__ tab) {
   const GroupRefDev& g = tab[blockIdx.z];
   const long long HW = (long long)g.H * g.W;
-  if (HW % PIX_PER_BLOCK == 0 || (int)blockIdx.y * REF_MASK_GROUP >= g.N) return;
-  ref_masked_pool_last<REF_MASK_GROUP>((int)(HW / PIX_PER_BLOCK), g.rs.attn, g.rs.dirflag, g.S, blockIdx.y, g.masks, g.N, g.H, g.W, g.part_mm,
-                                       g.part_sum, g.part_cnt, g.part_tot, g.nparts);
+  if (HW % PIX_PER_BLOCK == 0 || (int)blockIdx.y * MG >= g.N) return;
+  ref_masked_pool_last<MG>((int)(HW / PIX_PER_BLOCK), g.rs.attn, g.rs.dirflag, g.S, blockIdx.y, g.masks, g.N, g.H, g.W, g.part_mm,
+                           g.part_sum, g.part_cnt, g.part_tot, g.nparts);
 }
 
 __global__ __launch_bounds__(256) void grp_score_kernel(const GroupRefDev* __restrict__ tab, int E, float logit_scale, float r_mix,
@@ -996,8 +907,8 @@ __global__ __launch_bounds__(256) void grp_score_kernel(const GroupRefDev* __res
                  alpha, g.part_sum, g.part_cnt, g.part_tot, g.nparts, g.gem, g.clip, g.neg, g.soft, g.idx, g.iu, done);
 }
 
-// grid (blocks, 2 maxS, R): every block counts on `done` (those beyond their ref's sentences do nothing else); the last one adds
-// all sentences' sums of all refs to the running accumulators (integers: order-free)
+// grid (blocks, 2 maxS, R): every block counts on `done` (those beyond their row's sentences do nothing else); the last one adds
+// all sentences' sums of all rows to the running accumulators cum_I, cum_U, cum_I_final, cum_U_final (integers: order-free)
 __global__ __launch_bounds__(256) void grp_iou_kernel(const GroupRefDev* __restrict__ tab, int R, unsigned long long* __restrict__ cum,
                                                       unsigned* __restrict__ done) {
   const GroupRefDev& g = tab[blockIdx.z];
@@ -1358,95 +1269,87 @@ static size_t ref_ws_layout(int S, int N, int E, int H, int W, size_t* off) {
   return o;
 }
 
-size_t hgl_score_ref_workspace_bytes(int S, int N, int E, int H, int W) {
-  size_t off[7];
-  return ref_ws_layout(S < REF_MAXS ? S : REF_MAXS, N, E, H, W, off);
-}
-
-int hgl_score_ref(const float* hybrid, const float* text, int T, const int64_t* boxes, const uint8_t* masks, int N, int E,
-                  int H, int W, const HglSentence* sentences, int S, float logit_scale, float r, int k1, int k2, float alpha,
-                  int32_t* idx, int64_t* iu, int64_t* cum, float* score_clip, float* score_neg, float* gem_score,
-                  void* workspace, size_t workspace_bytes, void* stream) {
-  HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(hybrid && text && boxes && masks && sentences && idx && iu, "score_ref: null argument");
-  HGL_REQUIRE(N > 0 && E > 0 && H > 0 && W > 0 && S > 0 && T > 0, "score_ref: bad shape");
-  if (k1 > N) k1 = N;       // Hybridgl_main.py:178-181
-  if (k2 > N) k2 = N;
-  HGL_REQUIRE(k1 >= 1 && k1 <= MAXK && k2 >= 1 && k2 <= MAXK, "score_ref: k1,k2 must be in [1,%d]", MAXK);
-  for (int s = 0; s < S; ++s) {
-    const HglSentence& q = sentences[s];
-    HGL_REQUIRE(q.imgattn && q.target, "score_ref: sentence %d has no heat-map / target", s);
-    HGL_REQUIRE(q.sentence_row >= 0 && q.sentence_row < T && q.noun_phrase_row >= 0 && q.noun_phrase_row < T, "score_ref: sentence %d: text row out of range", s);
-    HGL_REQUIRE(q.n_other >= 0 && (q.n_other == 0 || (q.other_row0 >= 0 && q.other_row0 + q.n_other <= T)), "score_ref: sentence %d: other-noun rows out of range", s);
-    HGL_REQUIRE(q.dirflag >= 0 && q.dirflag <= 3 && q.relaword >= 0 && q.relaword <= 7, "score_ref: sentence %d: bad dirflag / relaword", s);
-  }
-  if (!workspace || workspace_bytes < hgl_score_ref_workspace_bytes(S, N, E, H, W)) {
-    hgl_set_error("score_ref: workspace too small (%zu < %zu)", workspace_bytes, hgl_score_ref_workspace_bytes(S, N, E, H, W));
-    return HGL_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const long long HW = (long long)H * W;
-  const int nparts = coh_nparts(H, W);
-  for (int s0 = 0; s0 < S; s0 += REF_MAXS) {
-    const int sc = S - s0 < REF_MAXS ? S - s0 : REF_MAXS;
-    size_t off[7];
-    ref_ws_layout(sc, N, E, H, W, off);
-    char* base = (char*)workspace;
-    RefSentences rs;
-    memset(&rs, 0, sizeof(rs));
-    for (int j = 0; j < sc; ++j) {
-      const HglSentence& q = sentences[s0 + j];
-      rs.attn[j] = q.imgattn; rs.target[j] = q.target;
-      rs.sent_row[j] = q.sentence_row; rs.nphr_row[j] = q.noun_phrase_row;
-      rs.other_row0[j] = q.n_other > 0 ? q.other_row0 : 0; rs.n_other[j] = q.n_other;
-      rs.dirflag[j] = q.dirflag; rs.rela[j] = q.relaword; rs.has_other[j] = q.has_other_nouns; rs.black[j] = q.black;
-    }
-    float* part_mm = (float*)(base + off[0]);
-    double* psum = (double*)(base + off[1]);
-    unsigned* pcnt = (unsigned*)(base + off[2]);
-    double* ptot = (double*)(base + off[3]);
-    float* soft = (float*)(base + off[4]);
-    float* spare = (float*)(base + off[5]);
-    unsigned* done = (unsigned*)(base + off[6]);
-    float* gem = gem_score ? gem_score + (long long)s0 * N : spare;
-    float* clip = score_clip ? score_clip + (long long)s0 * N : spare + (long long)sc * N;
-    float* neg = score_neg ? score_neg + (long long)s0 * N : spare + 2ll * sc * N;
-    hipLaunchKernelGGL(ref_minmax_kernel, dim3(REF_MM_BLOCKS, sc), dim3(256), 0, st, rs, HW, part_mm);
-    {
-      const int nfull = (int)(HW / PIX_PER_BLOCK), ngrp = (N + MASK_GROUP - 1) / MASK_GROUP;
-      if (nfull > 0 && sc <= 3)
-        hipLaunchKernelGGL(ref_masked_pool_kernel<3>, dim3(nfull, ngrp), dim3(256), 0, st, rs, sc, masks, N, H, W, part_mm, psum, pcnt, ptot, nparts);
-      else if (nfull > 0)
-        hipLaunchKernelGGL(ref_masked_pool_kernel<4>, dim3(nfull, ngrp), dim3(256), 0, st, rs, sc, masks, N, H, W, part_mm, psum, pcnt, ptot, nparts);
-      if (coh_nblk(H, W) > nfull)
-        hipLaunchKernelGGL(ref_masked_pool_last_kernel, dim3(1, ngrp), dim3(256), 0, st, rs, sc, masks, N, H, W, part_mm, psum, pcnt, ptot, nparts, nfull);
-    }
-    hipLaunchKernelGGL(ref_score_kernel, dim3(sc), dim3(256), 0, st, rs, hybrid, text, (const long long*)boxes, N, E, H, W, logit_scale,
-                       r, k1, k2, alpha, psum, pcnt, ptot, nparts, gem, clip, neg, soft, (int*)idx + 2 * s0,
-                       (unsigned long long*)iu + 4 * s0, done);
-    long long blocks = (HW / 16 + 1023) / 1024;      // four 16-byte words per thread
-    if (blocks < 1) blocks = 1;
-    if (blocks > 32) blocks = 32;
-    hipLaunchKernelGGL(ref_iou_kernel, dim3((unsigned)blocks, 2 * sc), dim3(256), 0, st, rs, sc, masks, HW, (const int*)idx + 2 * s0,
-                       (unsigned long long*)iu + 4 * s0, (unsigned long long*)cum, done);
-  }
-  return hgl_check_launch("score_ref");
-}
-
-// ---- hgl_score_group: the refs of a group through ONE set of launches -------------------------------------------------------
+// ---- the one host path of the fused tail: hgl_score_ref and hgl_score_group ---------------------------------------------------
+// Both entries hand over a list of ROWS.  A row is an HglGroupRef that holds at most REF_MAXS sentences: a ref of S <= 16
+// sentences as it is, a ref of more as ceil(S / 16) rows that share its hybrid / text / boxes / masks, each with its chunk of the
+// sentences and the output pointers moved to that chunk.  Up to GRP_MAXR rows go through one set of launches.
+}  // extern "C"
 namespace {
-// workspace of one ref inside the group's workspace (the layout of hgl_score_ref's) + the descriptor table in front
-size_t grp_ws_layout(const HglGroupRef* refs, int R, int E, size_t* ref_off) {
-  size_t o = hgl_align_up((size_t)GRP_MAXR * sizeof(GroupRefDev), 256) + 256;     // table + the done counter
-  for (int i = 0; i < R; ++i) {
+struct TailCall {
+  std::vector<HglGroupRef> rows;
+  int E;
+  float logit_scale, r, alpha;
+  int64_t* cum;
+  hipStream_t st;
+  int mask_group;      // masks per pooling workgroup: MASK_GROUP (hgl_score_ref) or REF_MASK_GROUP (hgl_score_group)
+};
+
+// everything an entry requires of a ref; clamps k1 / k2 to the number of masks in place (Hybridgl_main.py:178-181).
+// who: "score_ref" or "score_group: ref 3"
+int tail_check_ref(HglGroupRef& q, int E, const char* who) {
+  HGL_REQUIRE(q.hybrid && q.text && q.boxes && q.masks && q.sentences && q.idx && q.iu, "%s: null argument", who);
+  HGL_REQUIRE(q.N > 0 && E > 0 && q.H > 0 && q.W > 0 && q.S > 0 && q.T > 0, "%s: bad shape", who);
+  if (q.k1 > q.N) q.k1 = q.N;
+  if (q.k2 > q.N) q.k2 = q.N;
+  HGL_REQUIRE(q.k1 >= 1 && q.k1 <= MAXK && q.k2 >= 1 && q.k2 <= MAXK, "%s: k1,k2 must be in [1,%d]", who, MAXK);
+  for (int s = 0; s < q.S; ++s) {
+    const HglSentence& t = q.sentences[s];
+    HGL_REQUIRE(t.imgattn && t.target, "%s: sentence %d has no heat-map / target", who, s);
+    HGL_REQUIRE(t.sentence_row >= 0 && t.sentence_row < q.T && t.noun_phrase_row >= 0 && t.noun_phrase_row < q.T,
+                "%s: sentence %d: text row out of range", who, s);
+    HGL_REQUIRE(t.n_other >= 0 && (t.n_other == 0 || (t.other_row0 >= 0 && t.other_row0 + t.n_other <= q.T)),
+                "%s: sentence %d: other-noun rows out of range", who, s);
+    HGL_REQUIRE(t.dirflag >= 0 && t.dirflag <= 3 && t.relaword >= 0 && t.relaword <= 7, "%s: sentence %d: bad dirflag / relaword", who, s);
+  }
+  return HGL_OK;
+}
+
+void tail_fill_sentences(RefSentences& rs, const HglSentence* sent, int S) {
+  for (int j = 0; j < S; ++j) {
+    const HglSentence& t = sent[j];
+    rs.attn[j] = t.imgattn; rs.target[j] = t.target;
+    rs.sent_row[j] = t.sentence_row; rs.nphr_row[j] = t.noun_phrase_row;
+    rs.other_row0[j] = t.n_other > 0 ? t.other_row0 : 0; rs.n_other[j] = t.n_other;
+    rs.dirflag[j] = t.dirflag; rs.rela[j] = t.relaword; rs.has_other[j] = t.has_other_nouns; rs.black[j] = t.black;
+  }
+}
+
+// the rows of a ref
+void tail_push_rows(std::vector<HglGroupRef>& rows, const HglGroupRef& q) {
+  for (int s0 = 0; s0 < q.S; s0 += REF_MAXS) {
+    HglGroupRef row = q;
+    row.sentences = q.sentences + s0;
+    row.S = q.S - s0 < REF_MAXS ? q.S - s0 : REF_MAXS;
+    row.idx = q.idx ? q.idx + 2 * s0 : nullptr;
+    row.iu = q.iu ? q.iu + 4 * s0 : nullptr;
+    row.score_clip = q.score_clip ? q.score_clip + (long long)s0 * q.N : nullptr;
+    row.score_neg = q.score_neg ? q.score_neg + (long long)s0 * q.N : nullptr;
+    row.gem_score = q.gem_score ? q.gem_score + (long long)s0 * q.N : nullptr;
+    rows.push_back(row);
+  }
+}
+
+// workspace of one launch: the descriptor table and the done counter, then one ref_ws_layout per row
+size_t tail_ws_layout(const HglGroupRef* rows, int n, int E, size_t* row_off) {
+  size_t o = hgl_align_up((size_t)GRP_MAXR * sizeof(GroupRefDev), 256) + 256;
+  for (int i = 0; i < n; ++i) {
     size_t off[7];
-    if (ref_off) ref_off[i] = o;
-    o += ref_ws_layout(refs[i].S, refs[i].N, E, refs[i].H, refs[i].W, off);
+    if (row_off) row_off[i] = o;
+    o += ref_ws_layout(rows[i].S, rows[i].N, E, rows[i].H, rows[i].W, off);
   }
   return o;
 }
-// pinned staging of the descriptor table: a ring of slots, a slot is reused only after the copy out of it has completed
-// Pinned staging slots of hgl_score_group's descriptor table: one ring PER DEVICE (an event belongs to the device it was
+// ... and of a call: its launches run one after the other on the stream and share it
+size_t tail_ws_bytes(const std::vector<HglGroupRef>& rows, int E) {
+  size_t total = 0;
+  for (size_t r0 = 0; r0 < rows.size(); r0 += GRP_MAXR) {
+    const size_t n = tail_ws_layout(rows.data() + r0, (int)(rows.size() - r0 < GRP_MAXR ? rows.size() - r0 : GRP_MAXR), E, nullptr);
+    total = n > total ? n : total;
+  }
+  return total;
+}
+
+// Pinned staging slots of the descriptor table (a slot is reused only after the copy out of it has completed): one ring PER DEVICE (an event belongs to the device it was
 // created on), a slot is held (busy) by one host thread from the moment it is picked until its event has been recorded behind
 // the upload, and every event call is checked -- a failed record must not leave a slot looking reusable.
 struct GrpStage {
@@ -1468,7 +1371,7 @@ GrpStage g_grp_stage;
 int grp_stage_acquire(int* dev_out, void** host) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= GrpStage::DEVS) {
-    hgl_set_error("score_group: cannot tell the current device");
+    hgl_set_error("scoring tail: cannot tell the current device");
     return -1;
   }
   GrpStage::Ring& rg = g_grp_stage.ring[dev];
@@ -1494,10 +1397,10 @@ int grp_stage_acquire(int* dev_out, void** host) {
       rg.buf[slot] = nullptr;
       ok = false;
     }
-    if (!ok) hgl_set_error("score_group: cannot allocate the pinned descriptor slot");
+    if (!ok) hgl_set_error("scoring tail: cannot allocate the pinned descriptor slot");
   } else if (rg.used[slot]) {
     ok = hipEventSynchronize(rg.ev[slot]) == hipSuccess;      // the upload that last read this slot: eight calls ago
-    if (!ok) hgl_set_error("score_group: waiting for a descriptor slot failed");
+    if (!ok) hgl_set_error("scoring tail: waiting for a descriptor slot failed");
   }
   if (!ok) {
     (void)hipGetLastError();
@@ -1526,78 +1429,52 @@ bool grp_stage_release(int dev, int slot, hipStream_t st) {
   g_grp_stage.freed.notify_one();
   return ok;
 }
-}  // namespace
-
-size_t hgl_score_group_workspace_bytes(const HglGroupRef* refs, int R, int E) {
-  if (!refs || R <= 0 || E <= 0) return 0;
-  size_t total = 0;
-  for (int r0 = 0; r0 < R; r0 += GRP_MAXR) {
-    const size_t n = grp_ws_layout(refs + r0, R - r0 < GRP_MAXR ? R - r0 : GRP_MAXR, E, nullptr);
-    total = n > total ? n : total;
-  }
-  return total;
+// the pooling launches of the rows of a table, MG masks per workgroup; CH = 3 when no row has more than three sentences
+template <int MG>
+void tail_launch_pool(const GroupRefDev* tab, int rc, int maxS, int max_nblk, int maxN, bool any_partial, hipStream_t st) {
+  const int max_groups = (maxN + MG - 1) / MG;
+  if (maxS <= 3)
+    hipLaunchKernelGGL((grp_masked_pool_kernel<MG, 3>), dim3(max_nblk, max_groups, rc), dim3(256), 0, st, tab);
+  else
+    hipLaunchKernelGGL((grp_masked_pool_kernel<MG, 4>), dim3(max_nblk, max_groups, rc), dim3(256), 0, st, tab);
+  if (any_partial)
+    hipLaunchKernelGGL(grp_masked_pool_last_kernel<MG>, dim3(1, max_groups, rc), dim3(256), 0, st, tab);
 }
 
-int hgl_score_group(const HglGroupRef* refs, int R, int E, float logit_scale, float r, float alpha, int64_t* cum, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-  HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(refs && R > 0 && E > 0, "score_group: bad arguments");
-  for (int i = 0; i < R; ++i) {
-    const HglGroupRef& q = refs[i];
-    HGL_REQUIRE(q.hybrid && q.text && q.boxes && q.masks && q.sentences && q.idx && q.iu, "score_group: ref %d: null argument", i);
-    HGL_REQUIRE(q.N > 0 && q.H > 0 && q.W > 0 && q.T > 0 && q.S > 0 && q.S <= REF_MAXS, "score_group: ref %d: bad shape (S %d: 1 .. %d)", i,
-                q.S, REF_MAXS);
-    HGL_REQUIRE((q.k1 < q.N ? q.k1 : q.N) >= 1 && q.k1 <= MAXK && (q.k2 < q.N ? q.k2 : q.N) >= 1 && q.k2 <= MAXK,
-                "score_group: ref %d: k1,k2 must be in [1,%d]", i, MAXK);
-    for (int s = 0; s < q.S; ++s) {
-      const HglSentence& t = q.sentences[s];
-      HGL_REQUIRE(t.imgattn && t.target, "score_group: ref %d sentence %d has no heat-map / target", i, s);
-      HGL_REQUIRE(t.sentence_row >= 0 && t.sentence_row < q.T && t.noun_phrase_row >= 0 && t.noun_phrase_row < q.T,
-                  "score_group: ref %d sentence %d: text row out of range", i, s);
-      HGL_REQUIRE(t.n_other >= 0 && (t.n_other == 0 || (t.other_row0 >= 0 && t.other_row0 + t.n_other <= q.T)),
-                  "score_group: ref %d sentence %d: other-noun rows out of range", i, s);
-      HGL_REQUIRE(t.dirflag >= 0 && t.dirflag <= 3 && t.relaword >= 0 && t.relaword <= 7, "score_group: ref %d sentence %d: bad dirflag / relaword", i, s);
-    }
-  }
-  if (!workspace || workspace_bytes < hgl_score_group_workspace_bytes(refs, R, E)) {
-    hgl_set_error("score_group: workspace too small (%zu < %zu)", workspace_bytes, hgl_score_group_workspace_bytes(refs, R, E));
+// checked rows -> launches.  who: the entry's name, for its messages
+int tail_launch(const TailCall& c, void* workspace, size_t workspace_bytes, const char* who) {
+  const size_t need = tail_ws_bytes(c.rows, c.E);
+  if (!workspace || workspace_bytes < need) {
+    hgl_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
     return HGL_EWORKSPACE;
   }
-  hipStream_t st = (hipStream_t)stream;
   char* base = (char*)workspace;
+  const int R = (int)c.rows.size();
   for (int r0 = 0; r0 < R; r0 += GRP_MAXR) {
     const int rc = R - r0 < GRP_MAXR ? R - r0 : GRP_MAXR;
-    size_t ref_off[GRP_MAXR];
-    grp_ws_layout(refs + r0, rc, E, ref_off);
+    size_t row_off[GRP_MAXR];
+    tail_ws_layout(c.rows.data() + r0, rc, c.E, row_off);
     // the descriptor table, built in a pinned slot and copied in front of the workspace on the stream
     void* host_v = nullptr;
     int stage_dev = 0;
     const int slot = grp_stage_acquire(&stage_dev, &host_v);
     if (slot < 0) return HGL_ELAUNCH;
     GroupRefDev* host = (GroupRefDev*)host_v;
-    int maxS = 0, max_nblk = 0, max_groups = 0;
-    bool any_partial = false;      // a ref whose plane does not end on a block boundary: the pooling's second, small launch
+    int maxS = 0, max_nblk = 0, maxN = 0;
+    bool any_partial = false;      // a row whose plane does not end on a block boundary: the pooling's second, small launch
     long long max_iou_blocks = 1;
     for (int i = 0; i < rc; ++i) {
-      const HglGroupRef& q = refs[r0 + i];
+      const HglGroupRef& q = c.rows[r0 + i];
       GroupRefDev& d = host[i];
       memset(&d, 0, sizeof(d));
-      for (int j = 0; j < q.S; ++j) {
-        const HglSentence& t = q.sentences[j];
-        d.rs.attn[j] = t.imgattn; d.rs.target[j] = t.target;
-        d.rs.sent_row[j] = t.sentence_row; d.rs.nphr_row[j] = t.noun_phrase_row;
-        d.rs.other_row0[j] = t.n_other > 0 ? t.other_row0 : 0; d.rs.n_other[j] = t.n_other;
-        d.rs.dirflag[j] = t.dirflag; d.rs.rela[j] = t.relaword; d.rs.has_other[j] = t.has_other_nouns; d.rs.black[j] = t.black;
-      }
-      d.S = q.S; d.N = q.N; d.H = q.H; d.W = q.W;
-      d.k1 = q.k1 < q.N ? q.k1 : q.N;       // Hybridgl_main.py:178-181
-      d.k2 = q.k2 < q.N ? q.k2 : q.N;
+      tail_fill_sentences(d.rs, q.sentences, q.S);
+      d.S = q.S; d.N = q.N; d.H = q.H; d.W = q.W; d.k1 = q.k1; d.k2 = q.k2;
       d.nparts = coh_nparts(q.H, q.W);
       d.nblk = coh_nblk(q.H, q.W);
       d.hybrid = q.hybrid; d.text = q.text; d.boxes = (const long long*)q.boxes; d.masks = q.masks;
       size_t off[7];
-      ref_ws_layout(q.S, q.N, E, q.H, q.W, off);
-      char* rb = base + ref_off[i];
+      ref_ws_layout(q.S, q.N, c.E, q.H, q.W, off);
+      char* rb = base + row_off[i];
       d.part_mm = (float*)(rb + off[0]);
       d.part_sum = (double*)(rb + off[1]);
       d.part_cnt = (unsigned*)(rb + off[2]);
@@ -1610,33 +1487,76 @@ int hgl_score_group(const HglGroupRef* refs, int R, int E, float logit_scale, fl
       d.idx = (int*)q.idx;
       d.iu = (unsigned long long*)q.iu;
       maxS = q.S > maxS ? q.S : maxS;
+      maxN = q.N > maxN ? q.N : maxN;
       max_nblk = d.nblk > max_nblk ? d.nblk : max_nblk;
       any_partial = any_partial || ((long long)q.H * q.W) % PIX_PER_BLOCK != 0;
-      const int groups = (q.N + REF_MASK_GROUP - 1) / REF_MASK_GROUP;
-      max_groups = groups > max_groups ? groups : max_groups;
-      long long blocks = ((long long)q.H * q.W / 16 + 1023) / 1024;
+      long long blocks = ((long long)q.H * q.W / 16 + 1023) / 1024;      // four 16-byte words per thread
       blocks = blocks < 1 ? 1 : (blocks > 32 ? 32 : blocks);
       max_iou_blocks = blocks > max_iou_blocks ? blocks : max_iou_blocks;
     }
-    GroupRefDev* tab = (GroupRefDev*)base;
+    const GroupRefDev* tab = (const GroupRefDev*)base;
     unsigned* done = (unsigned*)(base + hgl_align_up((size_t)GRP_MAXR * sizeof(GroupRefDev), 256));
-    const bool uploaded = hipMemcpyAsync(tab, host, (size_t)rc * sizeof(GroupRefDev), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!grp_stage_release(stage_dev, slot, st) || !uploaded) {
-      hgl_set_error("score_group: descriptor upload failed");
+    const bool uploaded = hipMemcpyAsync(base, host, (size_t)rc * sizeof(GroupRefDev), hipMemcpyHostToDevice, c.st) == hipSuccess;
+    if (!grp_stage_release(stage_dev, slot, c.st) || !uploaded) {
+      hgl_set_error("%s: descriptor upload failed", who);
       return HGL_ELAUNCH;
     }
-    hipLaunchKernelGGL(grp_minmax_kernel, dim3(REF_MM_BLOCKS, maxS, rc), dim3(256), 0, st, (const GroupRefDev*)tab);
-    if (maxS <= 3)
-      hipLaunchKernelGGL(grp_masked_pool_kernel<3>, dim3(max_nblk, max_groups, rc), dim3(256), 0, st, (const GroupRefDev*)tab);
+    hipLaunchKernelGGL(grp_minmax_kernel, dim3(REF_MM_BLOCKS, maxS, rc), dim3(256), 0, c.st, tab);
+    if (c.mask_group == MASK_GROUP)
+      tail_launch_pool<MASK_GROUP>(tab, rc, maxS, max_nblk, maxN, any_partial, c.st);
     else
-      hipLaunchKernelGGL(grp_masked_pool_kernel<4>, dim3(max_nblk, max_groups, rc), dim3(256), 0, st, (const GroupRefDev*)tab);
-    if (any_partial)
-      hipLaunchKernelGGL(grp_masked_pool_last_kernel, dim3(1, max_groups, rc), dim3(256), 0, st, (const GroupRefDev*)tab);
-    hipLaunchKernelGGL(grp_score_kernel, dim3(maxS, rc), dim3(256), 0, st, (const GroupRefDev*)tab, E, logit_scale, r, alpha, done);
-    hipLaunchKernelGGL(grp_iou_kernel, dim3((unsigned)max_iou_blocks, 2 * maxS, rc), dim3(256), 0, st, (const GroupRefDev*)tab, rc,
-                       (unsigned long long*)cum, done);
+      tail_launch_pool<REF_MASK_GROUP>(tab, rc, maxS, max_nblk, maxN, any_partial, c.st);
+    hipLaunchKernelGGL(grp_score_kernel, dim3(maxS, rc), dim3(256), 0, c.st, tab, c.E, c.logit_scale, c.r, c.alpha, done);
+    hipLaunchKernelGGL(grp_iou_kernel, dim3((unsigned)max_iou_blocks, 2 * maxS, rc), dim3(256), 0, c.st, tab, rc,
+                       (unsigned long long*)c.cum, done);
   }
-  return hgl_check_launch("score_group");
+  return hgl_check_launch(who);
+}
+}  // namespace
+
+extern "C" {
+
+size_t hgl_score_ref_workspace_bytes(int S, int N, int E, int H, int W) {
+  HglGroupRef q;
+  memset(&q, 0, sizeof(q));
+  q.S = S; q.N = N; q.H = H; q.W = W;
+  std::vector<HglGroupRef> rows;
+  tail_push_rows(rows, q);
+  return tail_ws_bytes(rows, E);
+}
+
+int hgl_score_ref(const float* hybrid, const float* text, int T, const int64_t* boxes, const uint8_t* masks, int N, int E,
+                  int H, int W, const HglSentence* sentences, int S, float logit_scale, float r, int k1, int k2, float alpha,
+                  int32_t* idx, int64_t* iu, int64_t* cum, float* score_clip, float* score_neg, float* gem_score,
+                  void* workspace, size_t workspace_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HglGroupRef q = {hybrid, text, T, boxes, masks, N, H, W, sentences, S, k1, k2, idx, iu, score_clip, score_neg, gem_score};
+  HGL_TRY(tail_check_ref(q, E, "score_ref"));
+  TailCall c = {{}, E, logit_scale, r, alpha, cum, (hipStream_t)stream, MASK_GROUP};
+  tail_push_rows(c.rows, q);
+  return tail_launch(c, workspace, workspace_bytes, "score_ref");
+}
+
+size_t hgl_score_group_workspace_bytes(const HglGroupRef* refs, int R, int E) {
+  if (!refs || R <= 0 || E <= 0) return 0;
+  std::vector<HglGroupRef> rows;
+  for (int i = 0; i < R; ++i) tail_push_rows(rows, refs[i]);
+  return tail_ws_bytes(rows, E);
+}
+
+int hgl_score_group(const HglGroupRef* refs, int R, int E, float logit_scale, float r, float alpha, int64_t* cum, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(refs && R > 0 && E > 0, "score_group: bad arguments");
+  TailCall c = {{}, E, logit_scale, r, alpha, cum, (hipStream_t)stream, REF_MASK_GROUP};
+  for (int i = 0; i < R; ++i) {
+    char who[40];
+    snprintf(who, sizeof(who), "score_group: ref %d", i);
+    HglGroupRef q = refs[i];
+    HGL_TRY(tail_check_ref(q, E, who));
+    tail_push_rows(c.rows, q);
+  }
+  return tail_launch(c, workspace, workspace_bytes, "score_group");
 }
 
 int hgl_gen_dir_mask(int dirflag, int H, int W, float* out, void* stream) {

@@ -485,6 +485,32 @@ def score_sentence(hybrid, sentence_feat, noun_phrase_feat, other_noun_feats, bo
     return idx, sc, sn
 
 
+def _pack_sentences(sentences, H, W, keep, what="sentence"):
+    """list of sentence dicts (score_ref's docstring) -> HglSentence array; the tensors behind its pointers go to `keep`"""
+    recs = (_lib.HglSentence * len(sentences))()
+    for j, q in enumerate(sentences):
+        a = q["imgattn"]
+        if tuple(a.shape) != (H, W):
+            raise ValueError(f"{what} {j}: imgattn {tuple(a.shape)} != masks {(H, W)}")
+        tp, tt = _u8(q["target"], "target")
+        if tuple(tt.shape) != (H, W):
+            raise ValueError(f"{what} {j}: target {tuple(tt.shape)} != masks {(H, W)}")
+        keep += [a, tt]
+        recs[j] = _lib.HglSentence(int(q["sentence_row"]), int(q["noun_phrase_row"]), int(q.get("other_row0", 0)), int(q.get("n_other", 0)),
+                                   DIRFLAG.get(q.get("dirflag", "none"), 0), RELAWORD.get(q.get("relaword", "none"), 0),
+                                   int(bool(q.get("has_other_nouns", False))), float(q.get("black", 1.8)),
+                                   _dev(a, torch.float32, "imgattn"), tp)
+    return recs
+
+
+def _tail_outputs(S, N, dev, want_scores):
+    """(idx [S,2] int32, iu [S,4] int64, score_clip, score_neg, gem [S,N] or None) and the pointers of the last three"""
+    idx = torch.empty((S, 2), dtype=torch.int32, device=dev)
+    iu = torch.empty((S, 4), dtype=torch.int64, device=dev)
+    scores = tuple(torch.empty((S, N), dtype=torch.float32, device=dev) if want_scores else None for _ in range(3))
+    return (idx, iu) + scores, [t.data_ptr() if t is not None else None for t in scores]
+
+
 def score_ref(hybrid, text, boxes, masks, sentences, logit_scale=100.0, r=0.5, k1=3, k2=6, alpha=0.6, cum=None, want_scores=False):
     """The whole tail of one dataset item (Hybridgl_main.py:153-230) in four launches: hgl_score_ref.
 
@@ -500,43 +526,23 @@ def score_ref(hybrid, text, boxes, masks, sentences, logit_scale=100.0, r=0.5, k
     mp, masks = _u8(masks, "masks")
     _, H, W = masks.shape
     dev = hybrid.device
-    recs = (_lib.HglSentence * S)()
-    keep = []       # tensors whose pointers sit in the records
-    for j, q in enumerate(sentences):
-        a = q["imgattn"]
-        if tuple(a.shape) != (H, W):
-            raise ValueError(f"sentence {j}: imgattn {tuple(a.shape)} != masks {(H, W)}")
-        tp, tt = _u8(q["target"], "target")
-        if tuple(tt.shape) != (H, W):
-            raise ValueError(f"sentence {j}: target {tuple(tt.shape)} != masks {(H, W)}")
-        keep += [a, tt]
-        recs[j] = _lib.HglSentence(int(q["sentence_row"]), int(q["noun_phrase_row"]), int(q.get("other_row0", 0)), int(q.get("n_other", 0)),
-                                   DIRFLAG.get(q.get("dirflag", "none"), 0), RELAWORD.get(q.get("relaword", "none"), 0),
-                                   int(bool(q.get("has_other_nouns", False))), float(q.get("black", 1.8)),
-                                   _dev(a, torch.float32, "imgattn"), tp)
-    idx = torch.empty((S, 2), dtype=torch.int32, device=dev)
-    iu = torch.empty((S, 4), dtype=torch.int64, device=dev)
-    sc = sn = gm = None
-    if want_scores:
-        sc, sn, gm = (torch.empty((S, N), dtype=torch.float32, device=dev) for _ in range(3))
+    keep = []
+    recs = _pack_sentences(sentences, H, W, keep)
+    out, (scp, snp, gmp) = _tail_outputs(S, N, dev, want_scores)
     need = lib.hgl_score_ref_workspace_bytes(S, N, E, H, W)
     ws = workspace(need, dev, "score_ref")
     check(lib.hgl_score_ref(_dev(hybrid, torch.float32, "hybrid"), _dev(text, torch.float32, "text"), T,
                             _dev(boxes, torch.int64, "boxes"), mp, N, E, H, W, recs, S, float(logit_scale), float(r), int(k1), int(k2),
-                            float(alpha), idx.data_ptr(), iu.data_ptr(), _dev(cum, torch.int64, "cum") if cum is not None else None,
-                            sc.data_ptr() if sc is not None else None, sn.data_ptr() if sn is not None else None,
-                            gm.data_ptr() if gm is not None else None, ws.data_ptr(), ws.numel(), _stream()), "hgl_score_ref")
-    return (idx, iu, sc, sn, gm) if want_scores else (idx, iu)
-
-
-SCORE_GROUP_MAX_SENTENCES = 16      # per ref and call (csrc/scoring.hip REF_MAXS)
+                            float(alpha), out[0].data_ptr(), out[1].data_ptr(), _dev(cum, torch.int64, "cum") if cum is not None else None,
+                            scp, snp, gmp, ws.data_ptr(), ws.numel(), _stream()), "hgl_score_ref")
+    return out if want_scores else out[:2]
 
 
 def score_group(refs, logit_scale=100.0, r=0.5, alpha=0.6, cum=None, want_scores=False):
     """The tails of the R refs of a group (Hybridgl_main.py:153-230 each) in ONE set of four launches: hgl_score_group.
-    refs: list of dicts {hybrid [N,E], text [T,E], boxes [N,4] int64, masks [N,H,W], sentences (as for score_ref, at most
-    16), k1, k2}; shapes may differ from ref to ref.  cum as for score_ref.  Returns one tuple per ref, as score_ref would
-    (rows identical to its rows)."""
+    refs: list of dicts {hybrid [N,E], text [T,E], boxes [N,4] int64, masks [N,H,W], sentences (as for score_ref), k1, k2};
+    shapes may differ from ref to ref.  cum as for score_ref.  Returns one tuple per ref, as score_ref would (rows identical
+    to its rows)."""
     lib = _lib.load()
     R = len(refs)
     recs = (_lib.HglGroupRef * R)()
@@ -549,32 +555,13 @@ def score_group(refs, logit_scale=100.0, r=0.5, alpha=0.6, cum=None, want_scores
         mp, masks = _u8(q["masks"], "masks")
         _, H, W = masks.shape
         S = len(q["sentences"])
-        if not 1 <= S <= SCORE_GROUP_MAX_SENTENCES:
-            raise ValueError(f"ref {i}: {S} sentences (1 .. {SCORE_GROUP_MAX_SENTENCES} per call)")
-        sent = (_lib.HglSentence * S)()
-        for j, t in enumerate(q["sentences"]):
-            a = t["imgattn"]
-            if tuple(a.shape) != (H, W):
-                raise ValueError(f"ref {i} sentence {j}: imgattn {tuple(a.shape)} != masks {(H, W)}")
-            tp, tt = _u8(t["target"], "target")
-            if tuple(tt.shape) != (H, W):
-                raise ValueError(f"ref {i} sentence {j}: target {tuple(tt.shape)} != masks {(H, W)}")
-            keep += [a, tt]
-            sent[j] = _lib.HglSentence(int(t["sentence_row"]), int(t["noun_phrase_row"]), int(t.get("other_row0", 0)), int(t.get("n_other", 0)),
-                                       DIRFLAG.get(t.get("dirflag", "none"), 0), RELAWORD.get(t.get("relaword", "none"), 0),
-                                       int(bool(t.get("has_other_nouns", False))), float(t.get("black", 1.8)),
-                                       _dev(a, torch.float32, "imgattn"), tp)
-        idx = torch.empty((S, 2), dtype=torch.int32, device=dev)
-        iu = torch.empty((S, 4), dtype=torch.int64, device=dev)
-        sc = sn = gm = None
-        if want_scores:
-            sc, sn, gm = (torch.empty((S, N), dtype=torch.float32, device=dev) for _ in range(3))
+        sent = _pack_sentences(q["sentences"], H, W, keep, f"ref {i} sentence")
+        out, (scp, snp, gmp) = _tail_outputs(S, N, dev, want_scores)
         keep += [sent, masks]
         recs[i] = _lib.HglGroupRef(_dev(hybrid, torch.float32, "hybrid"), _dev(text, torch.float32, "text"), T,
                                    _dev(q["boxes"], torch.int64, "boxes"), mp, N, H, W, sent, S, int(q["k1"]), int(q["k2"]),
-                                   idx.data_ptr(), iu.data_ptr(), sc.data_ptr() if sc is not None else None,
-                                   sn.data_ptr() if sn is not None else None, gm.data_ptr() if gm is not None else None)
-        outs.append((idx, iu, sc, sn, gm) if want_scores else (idx, iu))
+                                   out[0].data_ptr(), out[1].data_ptr(), scp, snp, gmp)
+        outs.append(out if want_scores else out[:2])
     need = lib.hgl_score_group_workspace_bytes(recs, R, E)
     ws = workspace(need, dev, "score_group")
     check(lib.hgl_score_group(recs, R, E, float(logit_scale), float(r), float(alpha),

@@ -367,7 +367,7 @@ class HybridGLPipeline:
                          dirflag=s.dirflag, relaword=s.relaflag, has_other_nouns=s.n_nouns != 0, black=black_for(s.relaflag),
                          imgattn=a if a.is_contiguous() else a.contiguous(), target=s.target if s.target is not None else ref.target)
                     for s, a in zip(ref.sentences, attn)]
-            if defer is not None and 1 <= len(recs) <= ops.SCORE_GROUP_MAX_SENTENCES:
+            if defer is not None:
                 defer.append(dict(hybrid=hybrid, text=text, boxes=ref.boxes, masks=ref.masks, sentences=recs, k1=self.k1, k2=self.k2,
                                   ref_index=ref_index))
                 return self._DEFERRED

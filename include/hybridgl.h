@@ -324,7 +324,11 @@ int hgl_score_sentence(const float* hybrid, const float* sentence_feat, const fl
  * (I, U, I_final, U_final); cum [4] int64 (may be NULL) is INCREMENTED by the column sums of iu on the device
  * (cum_I, cum_U, cum_I_final, cum_U_final of Hybridgl_main.py:52-55); score_clip / score_neg / gem_score [S,N] are optional
  * (NULL) copies of the per-sentence logits and coherence scores.  Results are those of hgl_coherence_scores +
- * hgl_score_sentence + hgl_iou_select per sentence, bit for bit. */
+ * hgl_score_sentence + hgl_iou_select per sentence, bit for bit.  The call is hgl_score_group's of a group of this one ref
+ * (one host path; the pooling keeps 8 masks per workgroup here, the group's keeps 32: the partial sums are the same).  S is not
+ * limited: sixteen sentences make one row of the launch's descriptor table, a ref with more takes ceil(S / 16) rows in the same
+ * launches.  Workspace: hgl_score_ref_workspace_bytes holds the descriptor table, the counter of finished blocks and ONE
+ * workspace per row (the rows run in the same launches), so query it rather than assume a size. */
 typedef struct {
   int sentence_row, noun_phrase_row;  /* rows of text: clip.tokenize(sentence), clip.tokenize(noun_phrase) (:146-152) */
   int other_row0, n_other;            /* n_other consecutive rows from other_row0: 'a photo of ' + other noun (:157-164) */
@@ -343,10 +347,11 @@ int hgl_score_ref(const float* hybrid, const float* text, int T, const int64_t* 
 
 /* The same tail for the R refs of a group in ONE set of launches (the grouped evaluation loop scores a group's refs back to
  * back; four launches of ~31 MB per ref are latency-bound, one launch over the group streams ~0.5 GB).  Shapes may differ from
- * ref to ref.  Per ref: the arguments of hgl_score_ref (S <= 16 sentences; k1 / k2 are this ref's values of the clamp of
+ * ref to ref.  Per ref: the arguments of hgl_score_ref (any number of sentences; k1 / k2 are this ref's values of the clamp of
  * Hybridgl_main.py:178-181, which the caller carries from ref to ref) and its outputs idx [S,2], iu [S,4] and, optionally,
  * score_clip / score_neg / gem_score [S,N].  cum as for hgl_score_ref (the sums of all refs' sentences are added once).
- * Rows identical to hgl_score_ref's (same kernels' bodies on a per-ref descriptor table). */
+ * Rows identical to hgl_score_ref's (the same host path and kernels: every ref contributes its rows of at most sixteen
+ * sentences to the descriptor table, sixteen rows per set of launches). */
 typedef struct HglGroupRef {
   const float* hybrid;                /* [N,E] */
   const float* text;                  /* [T,E] */

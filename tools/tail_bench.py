@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Timing of the scoring tail on the benchmark's shape (64 proposals, 640 x 640, 3 sentences, E = 512): hgl_score_ref (one call per
-ref) against the per-sentence launches; HIP events around 20 calls each."""
+"""Timing of the scoring tail on the benchmark's shape (64 proposals, 640 x 640, 3 sentences, E = 512): hgl_score_group (sixteen
+refs per call) and hgl_score_ref (one call per ref: the same host path and kernels over a table of one row, after a descriptor
+upload of its own) against the per-sentence launches; HIP events around 20 calls each."""
 import os
 import sys
 
