@@ -35,6 +35,16 @@ class HglGroupRef(C.Structure):
                 ("score_neg", C.c_void_p), ("gem_score", C.c_void_p)]
 
 
+class HglSweepConfig(C.Structure):
+    """include/hybridgl.h HglSweepConfig: (r, alpha) of one configuration of hgl_score_group_sweep"""
+    _fields_ = [("r", C.c_float), ("alpha", C.c_float)]
+
+
+class HglSweepRef(C.Structure):
+    """include/hybridgl.h HglSweepRef: one ref's k table (host) and outputs for hgl_score_group_sweep"""
+    _fields_ = [("k", C.POINTER(C.c_int32)), ("idx", C.c_void_p), ("iu", C.c_void_p), ("ceiling", C.c_void_p)]
+
+
 class HglResBlockW(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "ln1_w", "ln1_b", "in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b",
@@ -202,6 +212,9 @@ PROTOTYPES = {
                            _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_score_group_workspace_bytes": (_SZ, [C.POINTER(HglGroupRef), _I, _I]),
     "hgl_score_group": (_I, [C.POINTER(HglGroupRef), _I, _I, C.c_float, C.c_float, C.c_float, _VP, _VP, _SZ, _VP]),
+    "hgl_score_group_sweep_workspace_bytes": (_SZ, [C.POINTER(HglGroupRef), _I, _I, C.POINTER(HglSweepConfig), _I]),
+    "hgl_score_group_sweep": (_I, [C.POINTER(HglGroupRef), C.POINTER(HglSweepRef), _I, _I, C.c_float, C.POINTER(HglSweepConfig), _I,
+                                   _VP, _VP, _VP, _SZ, _VP]),
     "hgl_u8_to_chw_lut": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP]),
     "hgl_gt_mask_from_polygons": (_I, [_VP, _VP, _I, _I, _I, _VP, _VP]),
     "hgl_gt_mask_from_rle_counts": (_I, [_VP, _I, _I, _I, _VP, _VP]),

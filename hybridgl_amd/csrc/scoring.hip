@@ -429,12 +429,17 @@ __device__ float relation_boxes_dev(const long long* bi, const long long* bj, fl
   }
 }
 
-__device__ __forceinline__ void score_sentence_body(
+// The body of a sentence comes in two parts, so that the sweep over (r, alpha, k1, k2) (grp_sweep_score_kernel) runs the very
+// same code: score_lists_body -- everything that depends on r alone: text ensemble, logits, both soft-maxes, the pure arg-max
+// (idx[0]) and the two top-k lists top1 / top2 (LDS, MAXK entries each) to k1 / k2 -- and score_blend_body, the single-thread
+// end that depends on k1, k2 and alpha.  A list built by repeated arg-max for a smaller k is a prefix of the list for a larger
+// one: a caller may build the lists once to the largest k and run score_blend_body per (k1, k2, alpha).
+__device__ __forceinline__ void score_lists_body(
     const float* __restrict__ hybrid, const float* __restrict__ sent, const float* __restrict__ nphr,
-    const float* __restrict__ others, int n_other, float r_mix,
-    const long long* __restrict__ boxes, const float* __restrict__ gem, int N, int E,
-    float logit_scale, int k1, int k2, float alpha, int rela, int has_other, int* __restrict__ idx,
-    float* __restrict__ score_clip, float* __restrict__ score_neg, float* __restrict__ soft_scratch) {
+    const float* __restrict__ others, int n_other, float r_mix, int N, int E,
+    float logit_scale, int k1, int k2, int* __restrict__ idx,
+    float* __restrict__ score_clip, float* __restrict__ score_neg, float* __restrict__ soft_scratch,
+    int* __restrict__ top1, int* __restrict__ top2) {
   // soft_scratch: [2*N] softmax values + [2*E] text vectors (global scratch so N, E are unbounded)
   float* tpos = soft_scratch + 2 * N;
   float* tneg = tpos + E;
@@ -450,7 +455,6 @@ __device__ __forceinline__ void score_sentence_body(
   __threadfence_block();
   __shared__ float red[8];
   __shared__ int redi[8];
-  __shared__ int top1[MAXK], top2[MAXK];
   __shared__ float nrm[2];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
 
@@ -594,9 +598,14 @@ __device__ __forceinline__ void score_sentence_body(
     }
   }
   __syncthreads();
+}
 
-  if (t == 0) {
-    // Hybridgl_main.py:183-196 relation sums, softmax, blend with the coherence score, argmax
+// one THREAD: Hybridgl_main.py:183-196 relation sums over the first k1 / k2 entries of the lists, softmax, blend with the
+// coherence score, argmax -> the final index
+__device__ __forceinline__ int score_blend_body(const long long* __restrict__ boxes, const float* __restrict__ gem, int N, int k1, int k2,
+                                                float alpha, int rela, int has_other, const float* __restrict__ soft_scratch,
+                                                const int* __restrict__ top1, const int* __restrict__ top2) {
+  {
     const float* sc = soft_scratch;
     const float* sn = soft_scratch + N;
     // partial sums are fp32 in the reference (np.float64 + Tensor -> Tensor.__radd__ -> fp32)
@@ -631,8 +640,20 @@ __device__ __forceinline__ void score_sentence_body(
       const float v = (tf[i] / den) * (1.f - alpha) + alpha * gem[top1[i]];
       if (i == 0 || v > bv || (v != v && bv == bv)) { bv = v; best = i; }
     }
-    idx[1] = top1[best];
+    return top1[best];
   }
+}
+
+__device__ __forceinline__ void score_sentence_body(
+    const float* __restrict__ hybrid, const float* __restrict__ sent, const float* __restrict__ nphr,
+    const float* __restrict__ others, int n_other, float r_mix,
+    const long long* __restrict__ boxes, const float* __restrict__ gem, int N, int E,
+    float logit_scale, int k1, int k2, float alpha, int rela, int has_other, int* __restrict__ idx,
+    float* __restrict__ score_clip, float* __restrict__ score_neg, float* __restrict__ soft_scratch) {
+  __shared__ int top1[MAXK], top2[MAXK];
+  score_lists_body(hybrid, sent, nphr, others, n_other, r_mix, N, E, logit_scale, k1, k2, idx, score_clip, score_neg, soft_scratch,
+                   top1, top2);
+  if (threadIdx.x == 0) idx[1] = score_blend_body(boxes, gem, N, k1, k2, alpha, rela, has_other, soft_scratch, top1, top2);
 }
 
 __global__ __launch_bounds__(256) void score_sentence_kernel(
@@ -757,19 +778,13 @@ __device__ __forceinline__ void ref_masked_pool_last(int blk, const float* const
   }
 }
 
-// one workgroup per sentence: coherence_final_kernel's reduction for its N masks, then the sentence's scoring
-__device__ __forceinline__ void ref_score_body(const RefSentences& rs, int s, bool first, const float* __restrict__ hybrid,
-                                               const float* __restrict__ text, const long long* __restrict__ boxes, int N, int E, int H,
-                                               int W, float logit_scale, float r_mix, int k1, int k2, float alpha,
-                                               const double* __restrict__ part_sum, const unsigned* __restrict__ part_cnt,
-                                               const double* __restrict__ part_tot, int nparts, float* __restrict__ gem_all,
-                                               float* __restrict__ clip_all, float* __restrict__ neg_all, float* __restrict__ soft_all,
-                                               int* __restrict__ idx_all, unsigned long long* __restrict__ iu_all,
-                                               unsigned* __restrict__ done) {
+// the coherence scores gem [N] of sentence s of a row from the pooling partials (one workgroup; shared by ref_score_body and the
+// sweep's scoring kernel: the same sums in the same order)
+__device__ __forceinline__ void ref_coherence_body(float black, int s, int N, int H, int W, const double* __restrict__ part_sum,
+                                                   const unsigned* __restrict__ part_cnt, const double* __restrict__ part_tot, int nparts,
+                                                   float* __restrict__ gem) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long HW = (long long)H * W;
-  float* gem = gem_all + (long long)s * N;
-  const float black = rs.black[s];
   // coherence_final_kernel's reduction for this sentence's N masks.  One wave per mask, lanes stride over the per-wave
   // partials -- but a plain `for (b = lane; b < nparts; b += 64)` is one memory round trip per trip, and sixteen masks per
   // wave one after the other made this workgroup the longest kernel of the tail (130 us).  The total is summed ONCE per wave
@@ -825,6 +840,19 @@ __device__ __forceinline__ void ref_score_body(const RefSentences& rs, int s, bo
       }
     }
   }
+}
+
+// one workgroup per sentence: coherence_final_kernel's reduction for its N masks, then the sentence's scoring
+__device__ __forceinline__ void ref_score_body(const RefSentences& rs, int s, bool first, const float* __restrict__ hybrid,
+                                               const float* __restrict__ text, const long long* __restrict__ boxes, int N, int E, int H,
+                                               int W, float logit_scale, float r_mix, int k1, int k2, float alpha,
+                                               const double* __restrict__ part_sum, const unsigned* __restrict__ part_cnt,
+                                               const double* __restrict__ part_tot, int nparts, float* __restrict__ gem_all,
+                                               float* __restrict__ clip_all, float* __restrict__ neg_all, float* __restrict__ soft_all,
+                                               int* __restrict__ idx_all, unsigned long long* __restrict__ iu_all,
+                                               unsigned* __restrict__ done) {
+  float* gem = gem_all + (long long)s * N;
+  ref_coherence_body(rs.black[s], s, N, H, W, part_sum, part_cnt, part_tot, nparts, gem);
   if (threadIdx.x < 4) iu_all[4 * s + threadIdx.x] = 0ull;
   if (first && threadIdx.x == 0) *done = 0u;
   __syncthreads();
@@ -940,6 +968,225 @@ __global__ __launch_bounds__(256) void grp_iou_kernel(const GroupRefDev* __restr
     }
     __syncthreads();
     if (threadIdx.x < 4) cum[threadIdx.x] += acc[threadIdx.x];
+  }
+}
+
+// ---- the sweep: the tail of the same rows under C configurations (r, alpha, k1, k2) at once: hgl_score_group_sweep -----------
+// Min / max and pooling do not depend on the configuration: they run once, through the launches above.  What replaces
+// grp_score_kernel + grp_iou_kernel:
+//   grp_iou_table_kernel     |mask_n & target_t| of EVERY proposal with every distinct target of the row, the areas of the
+//                            proposals and of the targets, in one pass over the mask planes: a configuration's (I, U) is then a
+//                            look-up (grp_iou_kernel reads a plane per (sentence, winner): C x S x 2 planes per ref for C
+//                            configurations), and the best proposal of a sentence -- the ceiling -- comes with it;
+//   grp_sweep_score_kernel   one workgroup per (sentence, distinct r): score_lists_body once, to the largest k1 / k2 any
+//                            configuration of that r asks for, then one thread per configuration runs score_blend_body over its
+//                            own prefixes of the lists.
+constexpr int SWP_MAXC = 256;      // configurations per call: one thread of a scoring workgroup each
+constexpr int SWP_MAXR = 32;       // distinct r among them: workgroups per sentence
+constexpr int TAB_MG = 32;         // masks per workgroup of the table kernel
+struct SweepRowDev {
+  unsigned char k[SWP_MAXC][2];         // this ref's k1, k2 per configuration, clamped to N
+  unsigned char kmax[SWP_MAXR][2];      // the largest of them per distinct r
+  int tslot[REF_MAXS];                  // sentence -> index of its target among the row's distinct target pointers
+  const uint8_t* tptr[REF_MAXS];        // the distinct targets
+  int nt, cstride;                      // their number; sentences of the WHOLE ref (the stride of a configuration in idx / iu)
+  int* idx;                             // [C, cstride, 2], at the row's first sentence
+  unsigned long long* iu;               // [C, cstride, 4], likewise
+  long long* ceiling;                   // [S,3] of the row
+  // table (zeroed before the launch): I [nt][N], then area [N] (slot nt), and at (REF_MAXS + 1) * N the areas of the targets
+  unsigned long long* tab;
+  float* scratch;                       // per (sentence, r): gem, clip, neg [N] each and score_lists_body's 2 N + 2 E
+};
+struct SweepTab {
+  SweepRowDev row[GRP_MAXR];
+  float r[SWP_MAXR], alpha[SWP_MAXC];
+  unsigned char rgrp[SWP_MAXC];         // configuration -> index of its r
+  int C, nr;
+};
+
+// sixteen bytes of a plane at pixel p0 -> sixteen bits (byte != 0, as iou_count_wave counts); pixels beyond the plane are 0.
+// full (wave-uniform): all sixteen lie inside -- one 16-byte load at any alignment, as pool_block's
+__device__ __forceinline__ unsigned tab_bits(const uint8_t* __restrict__ plane, long long p0, long long HW, bool full) {
+  unsigned w4[4] = {0u, 0u, 0u, 0u};
+  if (full) {
+    const pool_u32x4 mv = *(const pool_u32x4_u*)(plane + p0);
+    w4[0] = mv.x; w4[1] = mv.y; w4[2] = mv.z; w4[3] = mv.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < PX_LANE; ++e) {
+      const unsigned byte = p0 + e < HW ? (unsigned)plane[min(p0 + e, HW - 1)] : 0u;
+      w4[e >> 2] |= byte << (8 * (e & 3));
+    }
+  }
+  unsigned bits = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const unsigned w = w4[q];
+    const unsigned nz = ((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) >> 7) & 0x01010101u;      // as pool_block
+    bits |= (((nz * 0x01020408u) >> 24) & 0xfu) << (4 * q);      // bits 0, 8, 16, 24 gathered into 24..27 (no two terms meet)
+  }
+  return bits;
+}
+
+// grid (pixel blocks, groups of TAB_MG masks, rows).  A workgroup holds PIX_PER_BLOCK pixels of its masks as bits (one VGPR
+// per mask and lane), walks the row's distinct targets (and, as one more, the plane of all ones: the masks' areas) and adds its
+// counts to the row's table: every mask byte is fetched once, whatever the number of sentences.  Integers: any order.
+__global__ __launch_bounds__(256) void grp_iou_table_kernel(const GroupRefDev* __restrict__ tab, const SweepTab* __restrict__ swp) {
+  const GroupRefDev& g = tab[blockIdx.z];
+  const SweepRowDev& q = swp->row[blockIdx.z];
+  const long long HW = (long long)g.H * g.W;
+  const long long b0 = (long long)blockIdx.x * PIX_PER_BLOCK;
+  const int n0 = blockIdx.y * TAB_MG, N = g.N;
+  if (b0 >= HW || n0 >= N) return;      // (uniform; before any barrier)
+  const int n1 = min(N, n0 + TAB_MG);
+  const long long p0 = b0 + threadIdx.x * PX_LANE;
+  const bool full = b0 + PIX_PER_BLOCK <= HW;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned mb[TAB_MG];
+#pragma unroll
+  for (int j = 0; j < TAB_MG; ++j) {
+    const unsigned b = tab_bits(g.masks + (long long)min(n0 + j, n1 - 1) * HW, p0, HW, full);
+    mb[j] = n0 + j < n1 ? b : 0u;
+  }
+  __shared__ unsigned sm[4][TAB_MG + 1];
+  const int nt = q.nt;
+  for (int t = 0; t <= nt; ++t) {
+    const unsigned tb = t < nt ? tab_bits(q.tptr[t], p0, HW, full) : 0xffffu;
+    unsigned c[TAB_MG];
+#pragma unroll
+    for (int j = 0; j < TAB_MG; ++j) c[j] = (unsigned)__popc(mb[j] & tb);
+#pragma unroll
+    for (int j = 0; j < TAB_MG; ++j) c[j] = pool_sum_u(c[j]);
+    const unsigned ta = pool_sum_u((unsigned)__popc(tb));
+    if (lane == 63) {
+#pragma unroll
+      for (int j = 0; j < TAB_MG; ++j) sm[wave][j] = c[j];
+      sm[wave][TAB_MG] = ta;
+    }
+    __syncthreads();
+    const int x = threadIdx.x;
+    if (x <= TAB_MG) {
+      const unsigned v = (sm[0][x] + sm[1][x]) + (sm[2][x] + sm[3][x]);
+      if (x < TAB_MG) {
+        if (n0 + x < n1 && v != 0u) atomicAdd(&q.tab[(long long)t * N + n0 + x], (unsigned long long)v);
+      } else if (t < nt && blockIdx.y == 0 && v != 0u) {
+        atomicAdd(&q.tab[(REF_MAXS + 1ll) * N + t], (unsigned long long)v);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the order of the ceiling: a's I / U above b's, compared exactly as I_a U_b > I_b U_a; the lower index wins a tie (U = 0 has
+// been replaced by 1 by the caller: I is 0 then and the pair ranks as ratio 0)
+__device__ __forceinline__ bool ceil_better(unsigned long long Ia, unsigned long long Ua, int na, unsigned long long Ib,
+                                            unsigned long long Ub, int nb) {
+  const unsigned long long l = Ia * Ub, r = Ib * Ua;
+  return l > r || (l == r && na < nb);
+}
+
+// grid (maxS, distinct r, rows), after grp_iou_table_kernel on the stream.  Every block counts on `done` (zeroed before the
+// launch); the last one adds the column sums of all rows' iu [C, S, 4] to cum [C, 4] and the ceilings' (I, U) to cum_ceiling.
+__global__ __launch_bounds__(256) void grp_sweep_score_kernel(const GroupRefDev* __restrict__ tab, const SweepTab* __restrict__ swp, int R,
+                                                              int E, float logit_scale, unsigned long long* __restrict__ cum,
+                                                              unsigned long long* __restrict__ cum_ceiling,
+                                                              unsigned* __restrict__ done) {
+  const GroupRefDev& g = tab[blockIdx.z];
+  const SweepRowDev& q = swp->row[blockIdx.z];
+  const int s = blockIdx.x, rg = blockIdx.y, t = threadIdx.x, C = swp->C;
+  __shared__ int top1[MAXK], top2[MAXK];
+  __shared__ int pure;
+  __shared__ unsigned long long cI[4], cU[4];
+  __shared__ int cn[4];
+  if (s < g.S) {
+    const int N = g.N;
+    float* gem = q.scratch + ((long long)s * gridDim.y + rg) * (5ll * N + 2ll * E);
+    float* clip = gem + N;
+    float* neg = clip + N;
+    float* soft = neg + N;
+    ref_coherence_body(g.rs.black[s], s, N, g.H, g.W, g.part_sum, g.part_cnt, g.part_tot, g.nparts, gem);
+    __syncthreads();
+    __threadfence_block();
+    score_lists_body(g.hybrid, g.text + (long long)g.rs.sent_row[s] * E, g.text + (long long)g.rs.nphr_row[s] * E,
+                     g.text + (long long)g.rs.other_row0[s] * E, g.rs.n_other[s], swp->r[rg], N, E, logit_scale, q.kmax[rg][0],
+                     q.kmax[rg][1], &pure, clip, neg, soft, top1, top2);
+    const unsigned long long* Itab = q.tab + (long long)q.tslot[s] * N;
+    const unsigned long long* area = q.tab + (long long)q.nt * N;
+    const unsigned long long tarea = q.tab[(REF_MAXS + 1ll) * N + q.tslot[s]];
+    if (t < C && swp->rgrp[t] == rg) {      // one thread per configuration of this r
+      const int fin = score_blend_body(g.boxes, gem, N, q.k[t][0], q.k[t][1], swp->alpha[t], g.rs.rela[s], g.rs.has_other[s], soft,
+                                       top1, top2);
+      const int pu = pure;
+      int* io = q.idx + ((long long)t * q.cstride + s) * 2;
+      io[0] = pu;
+      io[1] = fin;
+      unsigned long long* uo = q.iu + ((long long)t * q.cstride + s) * 4;
+      const unsigned long long Ip = Itab[pu], If = Itab[fin];
+      uo[0] = Ip;
+      uo[1] = area[pu] + tarea - Ip;
+      uo[2] = If;
+      uo[3] = area[fin] + tarea - If;
+    }
+    if (rg == 0) {      // the ceiling of the sentence: the proposal of the largest I / U
+      unsigned long long bI = 0ull, bU = 1ull;
+      int bn = 0x7fffffff;
+      for (int n = t; n < N; n += 256) {
+        const unsigned long long I = Itab[n], U = area[n] + tarea - I, Uc = U != 0ull ? U : 1ull;
+        if (ceil_better(I, Uc, n, bI, bU, bn)) { bI = I; bU = Uc; bn = n; }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long oI = __shfl_xor(bI, o), oU = __shfl_xor(bU, o);
+        const int on = __shfl_xor(bn, o);
+        if (ceil_better(oI, oU, on, bI, bU, bn)) { bI = oI; bU = oU; bn = on; }
+      }
+      if ((t & 63) == 0) { cI[t >> 6] = bI; cU[t >> 6] = bU; cn[t >> 6] = bn; }
+      __syncthreads();
+      if (t == 0) {
+        for (int w = 1; w < 4; ++w)
+          if (ceil_better(cI[w], cU[w], cn[w], bI, bU, bn)) { bI = cI[w]; bU = cU[w]; bn = cn[w]; }
+        q.ceiling[3 * s + 0] = bn;
+        q.ceiling[3 * s + 1] = (long long)bI;
+        q.ceiling[3 * s + 2] = (long long)(area[bn] + tarea - bI);
+      }
+    }
+  }
+  __shared__ int last;
+  __threadfence();
+  __syncthreads();
+  if (t == 0) last = atomicAdd(done, 1u) == gridDim.x * gridDim.y * gridDim.z - 1;
+  __syncthreads();
+  if (!last) return;
+  // the last block: every other block's stores came before its count on `done` (fence, then the atomic); read them behind a
+  // fence of our own, with device-scope loads.  One thread per configuration walks the (row, sentence) entries: independent loads
+  __threadfence();
+  if (cum != nullptr && t < C) {
+    unsigned long long a[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int r = 0; r < R; ++r) {
+      const SweepRowDev& w = swp->row[r];
+      const int S = tab[r].S;
+      for (int j = 0; j < S; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          a[k] += __hip_atomic_load(&w.iu[((long long)t * w.cstride + j) * 4 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cum[4 * t + k] += a[k];
+  }
+  if (cum_ceiling != nullptr) {
+    __shared__ unsigned long long acc[2];
+    if (t < 2) acc[t] = 0ull;
+    __syncthreads();
+    for (int e = t; e < R * REF_MAXS; e += 256) {
+      const int r = e / REF_MAXS, j = e % REF_MAXS;
+      if (j < tab[r].S) {
+        const long long* cl = swp->row[r].ceiling + 3 * j;
+        atomicAdd(&acc[0], (unsigned long long)__hip_atomic_load(cl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        atomicAdd(&acc[1], (unsigned long long)__hip_atomic_load(cl + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      }
+    }
+    __syncthreads();
+    if (t < 2) cum_ceiling[t] += acc[t];
   }
 }
 
@@ -1284,6 +1531,38 @@ struct TailCall {
   int mask_group;      // masks per pooling workgroup: MASK_GROUP (hgl_score_ref) or REF_MASK_GROUP (hgl_score_group)
 };
 
+// hgl_score_group_sweep: what the rows of a TailCall carry besides (rows[i] belongs to TailCall::rows[i]; the rows' idx / iu
+// are the sweep's [C,S,2] / [C,S,4] arrays at the row's first sentence)
+struct SweepRowHost {
+  const int32_t* k;       // HOST [C,2]: the ref's k1, k2 per configuration
+  int S_total;            // sentences of the whole ref
+  int64_t* ceiling;       // [S,3] of the row
+};
+struct SweepCall {
+  const HglSweepConfig* cfg;
+  int C, nr;
+  float r[SWP_MAXR];                    // the distinct r (by bit pattern), in order of first appearance
+  unsigned char rgrp[SWP_MAXC];
+  std::vector<SweepRowHost> rows;
+  int64_t* cum_ceiling;
+};
+
+// the sweep's part of a launch's workspace, behind the tail's own: SweepTab, then what is zeroed before every launch (the
+// counter of finished blocks and the rows' tables), then the rows' scoring scratch
+size_t sweep_ws_layout(const HglGroupRef* rows, int n, int E, int nr, size_t* tab_off, size_t* scratch_off, size_t* zero_end) {
+  size_t o = hgl_align_up(sizeof(SweepTab), 256) + 256;
+  for (int i = 0; i < n; ++i) {
+    if (tab_off) tab_off[i] = o;
+    o += hgl_align_up(((REF_MAXS + 1) * (size_t)rows[i].N + REF_MAXS) * sizeof(unsigned long long), 256);
+  }
+  if (zero_end) *zero_end = o;
+  for (int i = 0; i < n; ++i) {
+    if (scratch_off) scratch_off[i] = o;
+    o += hgl_align_up((size_t)rows[i].S * nr * (5 * (size_t)rows[i].N + 2 * (size_t)E) * sizeof(float), 256);
+  }
+  return o;
+}
+
 // everything an entry requires of a ref; clamps k1 / k2 to the number of masks in place (Hybridgl_main.py:178-181).
 // who: "score_ref" or "score_group: ref 3"
 int tail_check_ref(HglGroupRef& q, int E, const char* who) {
@@ -1340,10 +1619,13 @@ size_t tail_ws_layout(const HglGroupRef* rows, int n, int E, size_t* row_off) {
   return o;
 }
 // ... and of a call: its launches run one after the other on the stream and share it
-size_t tail_ws_bytes(const std::vector<HglGroupRef>& rows, int E) {
+// (sweep_nr > 0: a sweep over that many distinct r -- every launch's sweep_ws_layout behind its tail_ws_layout)
+size_t tail_ws_bytes(const std::vector<HglGroupRef>& rows, int E, int sweep_nr = 0) {
   size_t total = 0;
   for (size_t r0 = 0; r0 < rows.size(); r0 += GRP_MAXR) {
-    const size_t n = tail_ws_layout(rows.data() + r0, (int)(rows.size() - r0 < GRP_MAXR ? rows.size() - r0 : GRP_MAXR), E, nullptr);
+    const int rc = (int)(rows.size() - r0 < GRP_MAXR ? rows.size() - r0 : GRP_MAXR);
+    size_t n = tail_ws_layout(rows.data() + r0, rc, E, nullptr);
+    if (sweep_nr > 0) n = hgl_align_up(n, 256) + sweep_ws_layout(rows.data() + r0, rc, E, sweep_nr, nullptr, nullptr, nullptr);
     total = n > total ? n : total;
   }
   return total;
@@ -1391,7 +1673,7 @@ int grp_stage_acquire(int* dev_out, void** host) {
   }
   bool ok = true;
   if (!rg.buf[slot]) {       // only the holder of a busy slot touches its buffer and event
-    ok = hipHostMalloc(&rg.buf[slot], GRP_MAXR * sizeof(GroupRefDev), hipHostMallocDefault) == hipSuccess;
+    ok = hipHostMalloc(&rg.buf[slot], GRP_MAXR * sizeof(GroupRefDev) + sizeof(SweepTab), hipHostMallocDefault) == hipSuccess;      // (a sweep's table rides behind the rows')
     if (ok && hipEventCreateWithFlags(&rg.ev[slot], hipEventDisableTiming) != hipSuccess) {
       (void)hipHostFree(rg.buf[slot]);
       rg.buf[slot] = nullptr;
@@ -1442,8 +1724,9 @@ void tail_launch_pool(const GroupRefDev* tab, int rc, int maxS, int max_nblk, in
 }
 
 // checked rows -> launches.  who: the entry's name, for its messages
-int tail_launch(const TailCall& c, void* workspace, size_t workspace_bytes, const char* who) {
-  const size_t need = tail_ws_bytes(c.rows, c.E);
+// sw: the call is a sweep -- after the pooling, the IoU table and the sweep's scoring instead of grp_score_kernel / grp_iou_kernel
+int tail_launch(const TailCall& c, void* workspace, size_t workspace_bytes, const char* who, const SweepCall* sw = nullptr) {
+  const size_t need = tail_ws_bytes(c.rows, c.E, sw ? sw->nr : 0);
   if (!workspace || workspace_bytes < need) {
     hgl_set_error("%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
     return HGL_EWORKSPACE;
@@ -1496,7 +1779,45 @@ int tail_launch(const TailCall& c, void* workspace, size_t workspace_bytes, cons
     }
     const GroupRefDev* tab = (const GroupRefDev*)base;
     unsigned* done = (unsigned*)(base + hgl_align_up((size_t)GRP_MAXR * sizeof(GroupRefDev), 256));
-    const bool uploaded = hipMemcpyAsync(base, host, (size_t)rc * sizeof(GroupRefDev), hipMemcpyHostToDevice, c.st) == hipSuccess;
+    bool uploaded = hipMemcpyAsync(base, host, (size_t)rc * sizeof(GroupRefDev), hipMemcpyHostToDevice, c.st) == hipSuccess;
+    char* sbase = nullptr;        // the sweep's part of the workspace, its table built in the same pinned slot
+    size_t zero_end = 0;
+    if (sw) {
+      SweepTab* ht = (SweepTab*)(host + GRP_MAXR);
+      memset(ht, 0, sizeof(*ht));
+      ht->C = sw->C; ht->nr = sw->nr;
+      memcpy(ht->r, sw->r, sizeof(ht->r));
+      memcpy(ht->rgrp, sw->rgrp, sizeof(ht->rgrp));
+      for (int j = 0; j < sw->C; ++j) ht->alpha[j] = sw->cfg[j].alpha;
+      sbase = base + hgl_align_up(tail_ws_layout(c.rows.data() + r0, rc, c.E, nullptr), 256);
+      size_t tab_off[GRP_MAXR], scratch_off[GRP_MAXR];
+      sweep_ws_layout(c.rows.data() + r0, rc, c.E, sw->nr, tab_off, scratch_off, &zero_end);
+      for (int i = 0; i < rc; ++i) {
+        const HglGroupRef& q = c.rows[r0 + i];
+        const SweepRowHost& h = sw->rows[r0 + i];
+        SweepRowDev& d = ht->row[i];
+        for (int j = 0; j < sw->C; ++j)
+          for (int e = 0; e < 2; ++e) {
+            const int k = h.k[2 * j + e] > q.N ? q.N : h.k[2 * j + e];      // validated by the entry
+            d.k[j][e] = (unsigned char)k;
+            unsigned char& m = d.kmax[sw->rgrp[j]][e];
+            m = m > k ? m : (unsigned char)k;
+          }
+        for (int j = 0; j < q.S; ++j) {      // a target pointer is counted once
+          int at = 0;
+          while (at < d.nt && d.tptr[at] != q.sentences[j].target) ++at;
+          if (at == d.nt) d.tptr[d.nt++] = q.sentences[j].target;
+          d.tslot[j] = at;
+        }
+        d.cstride = h.S_total;
+        d.idx = (int*)q.idx;
+        d.iu = (unsigned long long*)q.iu;
+        d.ceiling = (long long*)h.ceiling;
+        d.tab = (unsigned long long*)(sbase + tab_off[i]);
+        d.scratch = (float*)(sbase + scratch_off[i]);
+      }
+      uploaded = uploaded && hipMemcpyAsync(sbase, ht, sizeof(SweepTab), hipMemcpyHostToDevice, c.st) == hipSuccess;
+    }
     if (!grp_stage_release(stage_dev, slot, c.st) || !uploaded) {
       hgl_set_error("%s: descriptor upload failed", who);
       return HGL_ELAUNCH;
@@ -1506,6 +1827,18 @@ int tail_launch(const TailCall& c, void* workspace, size_t workspace_bytes, cons
       tail_launch_pool<MASK_GROUP>(tab, rc, maxS, max_nblk, maxN, any_partial, c.st);
     else
       tail_launch_pool<REF_MASK_GROUP>(tab, rc, maxS, max_nblk, maxN, any_partial, c.st);
+    if (sw) {
+      const size_t zero0 = hgl_align_up(sizeof(SweepTab), 256);
+      if (hipMemsetAsync(sbase + zero0, 0, zero_end - zero0, c.st) != hipSuccess) {
+        hgl_set_error("%s: memset failed", who);
+        return HGL_ELAUNCH;
+      }
+      const SweepTab* stab = (const SweepTab*)sbase;
+      hipLaunchKernelGGL(grp_iou_table_kernel, dim3(max_nblk, (maxN + TAB_MG - 1) / TAB_MG, rc), dim3(256), 0, c.st, tab, stab);
+      hipLaunchKernelGGL(grp_sweep_score_kernel, dim3(maxS, sw->nr, rc), dim3(256), 0, c.st, tab, stab, rc, c.E, c.logit_scale,
+                         (unsigned long long*)c.cum, (unsigned long long*)sw->cum_ceiling, (unsigned*)(sbase + zero0));
+      continue;
+    }
     hipLaunchKernelGGL(grp_score_kernel, dim3(maxS, rc), dim3(256), 0, c.st, tab, c.E, c.logit_scale, c.r, c.alpha, done);
     hipLaunchKernelGGL(grp_iou_kernel, dim3((unsigned)max_iou_blocks, 2 * maxS, rc), dim3(256), 0, c.st, tab, rc,
                        (unsigned long long*)c.cum, done);
@@ -1557,6 +1890,71 @@ int hgl_score_group(const HglGroupRef* refs, int R, int E, float logit_scale, fl
     tail_push_rows(c.rows, q);
   }
   return tail_launch(c, workspace, workspace_bytes, "score_group");
+}
+
+}  // extern "C"
+namespace {
+// the checks of the sweep entry on its configurations; fills the distinct r and every configuration's group
+int sweep_check_configs(SweepCall& sw) {
+  HGL_REQUIRE(sw.C >= 1 && sw.C <= SWP_MAXC, "score_group_sweep: %d configurations (1 .. %d)", sw.C, SWP_MAXC);
+  HGL_REQUIRE(sw.cfg, "score_group_sweep: null argument");
+  sw.nr = 0;
+  for (int j = 0; j < sw.C; ++j) {
+    int at = 0;
+    while (at < sw.nr && memcmp(&sw.r[at], &sw.cfg[j].r, sizeof(float)) != 0) ++at;
+    if (at == sw.nr) {
+      HGL_REQUIRE(sw.nr < SWP_MAXR, "score_group_sweep: more than %d distinct r", SWP_MAXR);
+      sw.r[sw.nr++] = sw.cfg[j].r;
+    }
+    sw.rgrp[j] = (unsigned char)at;
+  }
+  return HGL_OK;
+}
+}  // namespace
+extern "C" {
+
+size_t hgl_score_group_sweep_workspace_bytes(const HglGroupRef* refs, int R, int E, const HglSweepConfig* configs, int C) {
+  if (!refs || R <= 0 || E <= 0) return 0;
+  SweepCall sw = {};
+  sw.cfg = configs; sw.C = C;
+  if (sweep_check_configs(sw) != HGL_OK) return 0;
+  std::vector<HglGroupRef> rows;
+  for (int i = 0; i < R; ++i) tail_push_rows(rows, refs[i]);
+  return tail_ws_bytes(rows, E, sw.nr);
+}
+
+int hgl_score_group_sweep(const HglGroupRef* refs, const HglSweepRef* sweep, int R, int E, float logit_scale,
+                          const HglSweepConfig* configs, int C, int64_t* cum, int64_t* cum_ceiling, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(refs && sweep && R > 0 && E > 0, "score_group_sweep: bad arguments");
+  SweepCall sw = {};
+  sw.cfg = configs; sw.C = C; sw.cum_ceiling = cum_ceiling;
+  HGL_TRY(sweep_check_configs(sw));
+  TailCall c = {{}, E, logit_scale, 0.f, 0.f, cum, (hipStream_t)stream, REF_MASK_GROUP};
+  for (int i = 0; i < R; ++i) {
+    char who[48];
+    snprintf(who, sizeof(who), "score_group_sweep: ref %d", i);
+    HglGroupRef q = refs[i];
+    // the ref's own k1 / k2 / idx / iu / score rows are not part of this entry: the sweep's outputs stand in their place
+    q.idx = sweep[i].idx; q.iu = sweep[i].iu; q.k1 = q.k2 = 1;
+    q.score_clip = q.score_neg = q.gem_score = nullptr;
+    HGL_REQUIRE(sweep[i].k && sweep[i].ceiling, "%s: null argument", who);
+    HGL_TRY(tail_check_ref(q, E, who));
+    for (int j = 0; j < 2 * C; ++j) {
+      const int k = sweep[i].k[j] > q.N ? q.N : sweep[i].k[j];
+      HGL_REQUIRE(k >= 1 && k <= MAXK, "%s: configuration %d: k1,k2 must be in [1,%d]", who, j / 2, MAXK);
+    }
+    const size_t first = c.rows.size();
+    tail_push_rows(c.rows, q);
+    for (size_t rix = first; rix < c.rows.size(); ++rix) {
+      HglGroupRef& row = c.rows[rix];
+      const long long s0 = row.sentences - q.sentences;
+      // tail_push_rows moved idx / iu by the row's first sentence within ONE configuration: what the sweep's layout needs too
+      sw.rows.push_back({sweep[i].k, q.S, sweep[i].ceiling + 3 * s0});
+    }
+  }
+  return tail_launch(c, workspace, workspace_bytes, "score_group_sweep", &sw);
 }
 
 int hgl_gen_dir_mask(int dirflag, int H, int W, float* out, void* stream) {

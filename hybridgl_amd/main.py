@@ -90,7 +90,25 @@ def default_argument_parser():
     p.add_argument("--score_masks", default="", metavar="DIR",
                    help="score the predictions a run saved with --save_masks DIR against the dataset's ground truth, without any "
                         "model or checkpoint (the dataset flags as in that run); exits non-zero when a stored count differs")
+    p.add_argument("--sweep", default="", metavar="SPEC",
+                   help="score every ref under a grid of the tail's hyper-parameters in the same pass, e.g. "
+                        "'r=0.3,0.5,0.7;alpha=0:1:0.1;k1=3;k2=6': an axis is a value list or lo:hi:step (hi included), an axis "
+                        "left out keeps the run's value; the grid is the product, r slowest and k2 fastest (at most 256 "
+                        "configurations, 32 distinct r).  The run's own result is unchanged; see --sweep_json")
+    p.add_argument("--sweep_json", default="", metavar="OUT",
+                   help="with --sweep: rank 0 writes the configurations, their oIoU / mIoU (pure and with guidance), the proposal "
+                        "ceiling and the best configuration by final oIoU here (INTEGRATION.md)")
     return p
+
+
+def sweep_report(configs, sm):
+    """what --sweep_json holds, from HybridGLPipeline.sweep_metrics()"""
+    keys = ("r", "alpha", "k1", "k2", "oIoU", "mIoU", "oIoU_final", "mIoU_final", "n_sentences")
+    best = sm["best"]
+    return {"configs": [dict(zip(("r", "alpha", "k1", "k2"), t)) for t in configs],
+            "metrics": [{k: m[k] for k in keys} for m in sm["configs"]],
+            "ceiling": sm["ceiling"],
+            "best": None if best is None else dict({k: sm["configs"][best][k] for k in keys}, index=best)}
 
 
 OTHER_NOUN_PREFIX = "a photo of "   # Hybridgl_main.py:160: clip.tokenize('a photo of ' + other_noun)
@@ -482,8 +500,14 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
     resolve_defaults(args)
     k_clamp = args.k_clamp if args.k_clamp != "auto" else ("persistent" if world == 1 else "per_ref")
     save_dir = getattr(args, "save_masks", "")
+    sweep = None
+    if getattr(args, "sweep", ""):
+        import inspect
+        from .sweep import parse_sweep_spec
+        own = inspect.signature(HybridGLPipeline.__init__).parameters      # the run's values: the pipeline's defaults
+        sweep = parse_sweep_spec(args.sweep, *(own[n].default for n in ("r", "alpha", "k1", "k2")))
     pipe = HybridGLPipeline(model, fusion_mode=args.fusion_mode, masking_block=getattr(args, "masking_block", 9), mask_generator=gen,
-                            use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir))
+                            use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir), sweep=sweep)
     rr, jobs, make = dataset_items(args, dev, rank, world, sam_img_size=1024 if gen else 0, gem=gem_model is not None)
     # Hybridgl_main.py:45,79: DataLoader(num_workers=4) feeding the loop; here loader threads feed the grouped loop
     loader = Prefetcher(jobs, make, workers=args.workers, depth=2 * args.group + 2, device=dev)
@@ -514,6 +538,8 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
              "images_decoded": rr.decoded if rr is not None else None, "image_cache_hits": pipe.cache_hits,
              "skipped": getattr(pipe, "skipped", 0), "groups": getattr(pipe, "groups_run", None),
              "workers": args.workers, "group": args.group}
+    if sweep is not None:      # one more exchange of rows, on every rank
+        stats["sweep"] = sweep_report(sweep, pipe.sweep_metrics(dist))
     return m, stats
 
 
@@ -547,8 +573,16 @@ def main(args):
         print(f"{stats['skipped']} refs skipped: the proposal stage returned no mask")
     if dist is not None:
         dist.destroy_process_group()
+    sweep = stats.pop("sweep", None)
     if rank != 0:
         return m
+    if sweep is not None:
+        import json
+        b = sweep["best"]
+        print(f"sweep: {len(sweep['configs'])} configurations; proposal ceiling oIoU {sweep['ceiling']['oIoU']:.2f} mIoU "
+              f"{sweep['ceiling']['mIoU']:.2f}; best final oIoU {b['oIoU_final']:.2f} at r={b['r']} alpha={b['alpha']} k1={b['k1']} k2={b['k2']}")
+        if getattr(args, "sweep_json", ""):
+            json.dump(sweep, open(args.sweep_json, "w"), indent=1)
     if getattr(args, "stats_json", ""):
         import json
         stats["refs_per_s"] = stats["refs"] / stats["seconds"] if stats["seconds"] > 0 else 0.0

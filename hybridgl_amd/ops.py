@@ -538,6 +538,19 @@ def score_ref(hybrid, text, boxes, masks, sentences, logit_scale=100.0, r=0.5, k
     return out if want_scores else out[:2]
 
 
+def _group_ref(i, q, keep, k1, k2, idx, iu, scores=(None, None, None)):
+    """one ref dict of score_group -> its HglGroupRef record with the given k1 / k2 and output pointers; what the record points
+    to goes to `keep`"""
+    hybrid, text = q["hybrid"], q["text"]
+    mp, masks = _u8(q["masks"], "masks")
+    _, H, W = masks.shape
+    sent = _pack_sentences(q["sentences"], H, W, keep, f"ref {i} sentence")
+    keep += [sent, masks]
+    return _lib.HglGroupRef(_dev(hybrid, torch.float32, "hybrid"), _dev(text, torch.float32, "text"), text.shape[0],
+                            _dev(q["boxes"], torch.int64, "boxes"), mp, hybrid.shape[0], H, W, sent, len(q["sentences"]), int(k1), int(k2),
+                            idx, iu, *scores)
+
+
 def score_group(refs, logit_scale=100.0, r=0.5, alpha=0.6, cum=None, want_scores=False):
     """The tails of the R refs of a group (Hybridgl_main.py:153-230 each) in ONE set of four launches: hgl_score_group.
     refs: list of dicts {hybrid [N,E], text [T,E], boxes [N,4] int64, masks [N,H,W], sentences (as for score_ref), k1, k2};
@@ -550,23 +563,68 @@ def score_group(refs, logit_scale=100.0, r=0.5, alpha=0.6, cum=None, want_scores
     E = refs[0]["hybrid"].shape[1]
     dev = refs[0]["hybrid"].device
     for i, q in enumerate(refs):
-        hybrid, text = q["hybrid"], q["text"]
-        N, T = hybrid.shape[0], text.shape[0]
-        mp, masks = _u8(q["masks"], "masks")
-        _, H, W = masks.shape
-        S = len(q["sentences"])
-        sent = _pack_sentences(q["sentences"], H, W, keep, f"ref {i} sentence")
-        out, (scp, snp, gmp) = _tail_outputs(S, N, dev, want_scores)
-        keep += [sent, masks]
-        recs[i] = _lib.HglGroupRef(_dev(hybrid, torch.float32, "hybrid"), _dev(text, torch.float32, "text"), T,
-                                   _dev(q["boxes"], torch.int64, "boxes"), mp, N, H, W, sent, S, int(q["k1"]), int(q["k2"]),
-                                   out[0].data_ptr(), out[1].data_ptr(), scp, snp, gmp)
+        out, scores = _tail_outputs(len(q["sentences"]), q["hybrid"].shape[0], dev, want_scores)
+        recs[i] = _group_ref(i, q, keep, q["k1"], q["k2"], out[0].data_ptr(), out[1].data_ptr(), scores)
         outs.append(out if want_scores else out[:2])
     need = lib.hgl_score_group_workspace_bytes(recs, R, E)
     ws = workspace(need, dev, "score_group")
     check(lib.hgl_score_group(recs, R, E, float(logit_scale), float(r), float(alpha),
                               _dev(cum, torch.int64, "cum") if cum is not None else None, ws.data_ptr(), ws.numel(), _stream()),
           "hgl_score_group")
+    return outs
+
+
+def _sweep_k(q, configs, name):
+    """the C values of k1 / k2 (`name`) of one ref: the ref's own sequence of C (a caller that carries a clamp per
+    configuration), else the configuration's (r, alpha, k1, k2), else the ref's int"""
+    own = q.get(name)
+    if own is not None and not isinstance(own, int):
+        own = [int(v) for v in own]
+        if len(own) != len(configs):
+            raise ValueError(f"{name}: {len(own)} values for {len(configs)} configurations")
+        return own
+    at = 2 if name == "k1" else 3
+    if any(len(t) < 4 for t in configs) and own is None:
+        raise ValueError(f"a configuration without k1 / k2 needs the ref's own {name}")
+    return [int(t[at]) if len(t) >= 4 else int(own) for t in configs]
+
+
+def score_group_sweep(refs, configs, logit_scale=100.0, cum=None, cum_ceiling=None):
+    """score_group under C configurations of (r, alpha, k1, k2) in one pass: hgl_score_group_sweep (min / max and pooling once,
+    one pass over the mask planes for the IoU of every proposal with every target, one scoring workgroup per sentence and
+    distinct r).  refs as for score_group; configs: list of (r, alpha) or (r, alpha, k1, k2), at most 256 with at most 32
+    distinct r.  A ref's k1 / k2 per configuration: the ref's own k1 / k2 when that is a sequence of C, else the
+    configuration's, else the ref's int.  cum: int64 [C,4] device tensor, incremented by every configuration's column sums;
+    cum_ceiling: int64 [2], incremented by the (I, U) of every sentence's best proposal.
+    Returns per ref (idx [C,S,2] int32, iu [C,S,4] int64, ceiling [S,3] int64 = best proposal, its I, its U); row c equals
+    score_group's rows under configuration c bit for bit."""
+    import ctypes as C_
+    lib = _lib.load()
+    R, C = len(refs), len(configs)
+    cfg = (_lib.HglSweepConfig * max(C, 1))()
+    for c, t in enumerate(configs):
+        cfg[c] = _lib.HglSweepConfig(float(t[0]), float(t[1]))
+    recs = (_lib.HglGroupRef * R)()
+    swp = (_lib.HglSweepRef * R)()
+    keep, outs = [], []
+    E = refs[0]["hybrid"].shape[1]
+    dev = refs[0]["hybrid"].device
+    for i, q in enumerate(refs):
+        S = len(q["sentences"])
+        k1, k2 = _sweep_k(q, configs, "k1"), _sweep_k(q, configs, "k2")
+        ks = (C_.c_int32 * max(2 * C, 1))(*[v for pair in zip(k1, k2) for v in pair])
+        out = (torch.empty((C, S, 2), dtype=torch.int32, device=dev), torch.empty((C, S, 4), dtype=torch.int64, device=dev),
+               torch.empty((S, 3), dtype=torch.int64, device=dev))
+        recs[i] = _group_ref(i, q, keep, 1, 1, None, None)
+        swp[i] = _lib.HglSweepRef(ks, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        keep.append(ks)
+        outs.append(out)
+    need = lib.hgl_score_group_sweep_workspace_bytes(recs, R, E, cfg, C)
+    ws = workspace(need, dev, "score_group_sweep")
+    check(lib.hgl_score_group_sweep(recs, swp, R, E, float(logit_scale), cfg, C,
+                                    _dev(cum, torch.int64, "cum") if cum is not None else None,
+                                    _dev(cum_ceiling, torch.int64, "cum_ceiling") if cum_ceiling is not None else None,
+                                    ws.data_ptr(), ws.numel(), _stream()), "hgl_score_group_sweep")
     return outs
 
 

@@ -117,7 +117,7 @@ def _side_streams(device):
 class HybridGLPipeline:
     def __init__(self, model, fusion_mode="G2L", masking_block=9, r=0.5, alpha=0.6, k1=3, k2=6, res=224,
                  mask_generator=None, use_sam_masks=False, fixed_proposals=None, cleanup_given_masks=False,
-                 gem_model=None, k_clamp="persistent", image_cache=32, record_predictions=False):
+                 gem_model=None, k_clamp="persistent", image_cache=32, record_predictions=False, sweep=None):
         """mask_generator: a hybridgl_amd.sam.SamAutomaticMaskGenerator; when given, every step runs the
         SAM proposal stage (encoder, decoder, post-processing, NMS) on ref.sam_img first.
         use_sam_masks=False keeps ref.masks for the CLIP stage (fixed N; synthetic benchmark, where
@@ -128,7 +128,11 @@ class HybridGLPipeline:
         to that item only (order- and sharding-independent; differs from the reference after such an image).
         record_predictions: keep every sentence's two winning masks as run lengths (predictions()): each tail is followed
         by one ops.rle_encode of the winners, selected by the tail's own device indices, and an asynchronous copy of the
-        runs to pinned host memory -- no read-back of an index or a pixel, no synchronisation in the loop."""
+        runs to pinned host memory -- no read-back of an index or a pixel, no synchronisation in the loop.
+        sweep: a list of (r, alpha, k1, k2): every fused tail is followed by ONE ops.score_group_sweep call on the same operands
+        that scores them under all these configurations (each with its own k1 / k2 under the k_clamp rule) and counts the
+        proposal ceiling; sweep_rows() / ceiling_rows() / sweep_metrics() report them.  The pipeline's own configuration runs
+        exactly as without a sweep.  A ref the fused tail cannot serve raises ValueError then."""
         if k_clamp not in ("persistent", "per_ref"):
             raise ValueError("k_clamp must be 'persistent' or 'per_ref'")
         # run(): proposals, hybrid features and GEM features of the last `image_cache` images with an image_id (the dataset
@@ -166,6 +170,16 @@ class HybridGLPipeline:
         self._pred_pending = []   # copies in flight: (ref position, sentences, H, W, slot words, pinned buffer, event), in log order
         self._pred_done = []      # per sentence, in log order: ((H, W), counts of the pure winner, counts of the final one)
         self._pred_free = []      # pinned staging buffers whose copies have completed
+        self.sweep = None
+        if sweep is not None:
+            self.sweep = [(float(t[0]), float(t[1]), int(t[2]), int(t[3])) for t in sweep]
+            if not self.sweep:
+                raise ValueError("sweep: no configuration")
+            self._sweep_k0 = [[t[2], t[3]] for t in self.sweep]
+            self._sweep_k = [list(k) for k in self._sweep_k0]      # the clamp of Hybridgl_main.py:178-181, per configuration
+            self.sweep_cum = torch.zeros((len(self.sweep), 4), dtype=torch.int64, device=dev)
+            self.sweep_cum_ceiling = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._sweep_log = []      # per tail: (idx [C,S,2], iu [C,S,4], ceiling [S,3]) device tensors, in the order of iu_log
 
     def _join_side_streams(self, cur, outs):
         """The caller's stream waits for both side streams; every tensor that leaves them is recorded on the caller's
@@ -334,12 +348,21 @@ class HybridGLPipeline:
         if not defer:
             return []
         outs = ops.score_group(defer, self.model.model._logit_scale_exp, self.r, self.alpha, cum=self.cum, want_scores=True)
+        if self.sweep is not None:
+            self._sweep_tails(defer)
         last = []
         for q, (idx, iu, sc, sn, gm) in zip(defer, outs):
             self._log_tail(q["ref_index"], len(q["sentences"]), idx, iu, q["masks"])
             last.append((idx[-1], sc[-1], sn[-1], gm[-1]))
         defer.clear()
         return last
+
+    def _sweep_tails(self, refs):
+        """the same tails (the dicts handed to ops.score_group, each with its sweep_k) under every configuration of the sweep"""
+        outs = ops.score_group_sweep([dict(q, k1=[k[0] for k in q["sweep_k"]], k2=[k[1] for k in q["sweep_k"]]) for q in refs],
+                                     [t[:2] for t in self.sweep], self.model.model._logit_scale_exp, cum=self.sweep_cum,
+                                     cum_ceiling=self.sweep_cum_ceiling)
+        self._sweep_log.extend(outs)
 
     def _score_ref(self, ref, hybrid, text, heat, defer=None):
         """the per-sentence tail of Hybridgl_main.py:153-230 for one ref; returns the tensors of its last sentence.  defer (a
@@ -350,6 +373,10 @@ class HybridGLPipeline:
             self.k1, self.k2 = self._k0
         self.k1 = min(self.k1, hybrid.shape[0])
         self.k2 = min(self.k2, hybrid.shape[0])
+        if self.sweep is not None:      # the same rule for every configuration's own pair
+            if self.k_clamp == "per_ref":
+                self._sweep_k = [list(k) for k in self._sweep_k0]
+            self._sweep_k = [[min(k[0], hybrid.shape[0]), min(k[1], hybrid.shape[0])] for k in self._sweep_k]
         ref_index = ref.index if ref.index is not None else self._n_refs
         self._n_refs += 1
         if not ref.sentences:        # an item without a sentence scores nothing (the reference's inner loop does not run)
@@ -359,6 +386,9 @@ class HybridGLPipeline:
         fused = self.fused_tail and text.is_contiguous() and all(
             list(s.other_noun_rows) == list(range(s.other_noun_rows[0], s.other_noun_rows[0] + len(s.other_noun_rows)))
             for s in ref.sentences if s.other_noun_rows)
+        if self.sweep is not None and not fused:
+            raise ValueError(f"sweep: the fused tail cannot serve ref {ref_index} (other-noun rows that are not consecutive, text "
+                             "that is not contiguous, or HYBRIDGL_FUSED_TAIL=0), and the sweep runs on the fused tail's operands")
         if fused:
             # hgl_score_ref: every mask byte read once for all sentences' heat-maps, one scoring workgroup per sentence,
             # both IoUs of every sentence and the accumulators of Hybridgl_main.py:52-55 in the same four launches
@@ -370,9 +400,14 @@ class HybridGLPipeline:
             if defer is not None:
                 defer.append(dict(hybrid=hybrid, text=text, boxes=ref.boxes, masks=ref.masks, sentences=recs, k1=self.k1, k2=self.k2,
                                   ref_index=ref_index))
+                if self.sweep is not None:
+                    defer[-1]["sweep_k"] = self._sweep_k
                 return self._DEFERRED
             idx, iu, sc, sn, gm = ops.score_ref(hybrid, text, ref.boxes, ref.masks, recs, m.model._logit_scale_exp, self.r, self.k1,
                                                 self.k2, self.alpha, cum=self.cum, want_scores=True)
+            if self.sweep is not None:
+                self._sweep_tails([dict(hybrid=hybrid, text=text, boxes=ref.boxes, masks=ref.masks, sentences=recs,
+                                        sweep_k=self._sweep_k)])
             self._log_tail(ref_index, len(recs), idx, iu, ref.masks)
             return (idx[-1], sc[-1], sn[-1], gm[-1]) if recs else None
         last = None
@@ -458,6 +493,8 @@ class HybridGLPipeline:
         keep = (self.cum.clone(), list(self.iu_log), list(self.iu_owner), list(self.idx_log), self._n_refs,
                 getattr(self, "skipped", 0), getattr(self, "groups_run", 0), dict(self._img_cache), self.cache_hits,
                 (self.k1, self.k2), getattr(self, "group_marks", None), getattr(self, "stage_marks", None), len(self._pred_done))
+        if self.sweep is not None:
+            keep_sweep = (self.sweep_cum.clone(), self.sweep_cum_ceiling.clone(), list(self._sweep_log), self._sweep_k)
         self.group_marks = self.stage_marks = None
         cap = proposals if (gen is not None and self.use_sam_masks) else None
         try:
@@ -493,6 +530,10 @@ class HybridGLPipeline:
             self._img_cache, self.cache_hits = keep[7], keep[8]
             self.k1, self.k2 = keep[9]
             self.group_marks, self.stage_marks = keep[10], keep[11]
+            if self.sweep is not None:
+                self.sweep_cum.copy_(keep_sweep[0])
+                self.sweep_cum_ceiling.copy_(keep_sweep[1])
+                self._sweep_log[:], self._sweep_k = keep_sweep[2], keep_sweep[3]
             if self.record_predictions:      # the staging buffers stay (sized for this geometry), the records go
                 self._harvest_predictions(wait=True)
                 del self._pred_done[keep[12]:]
@@ -780,6 +821,50 @@ class HybridGLPipeline:
         if not self.idx_log:
             return np.zeros((0, 2), dtype=np.int64)
         return torch.stack(self.idx_log).cpu().numpy().astype(np.int64)
+
+    # ---- the sweep's reports (sweep=...) --------------------------------------------------------------------------------------
+    def _sweep_on(self, what):
+        if self.sweep is None:
+            raise RuntimeError(f"{what}: this pipeline runs no sweep; build it with sweep=[(r, alpha, k1, k2), ...]")
+
+    def sweep_rows(self):
+        """[C, n, 6] int64: partial_rows() of every configuration of the sweep (dist.ROW_FIELDS), sentences in the order of
+        partial_rows().  One device->host copy."""
+        self._sweep_on("sweep_rows()")
+        C, n = len(self.sweep), len(self.iu_owner)
+        out = np.zeros((C, n, 6), dtype=np.int64)
+        if n:
+            out[:, :, 0:2] = np.asarray(self.iu_owner, dtype=np.int64).reshape(1, n, 2)
+            out[:, :, 2:6] = torch.cat([iu for _, iu, _ in self._sweep_log], dim=1).cpu().numpy()
+        return out
+
+    def sweep_indices(self):
+        """[C, n, 2] int64: winning_indices() of every configuration"""
+        self._sweep_on("sweep_indices()")
+        if not self._sweep_log:
+            return np.zeros((len(self.sweep), 0, 2), dtype=np.int64)
+        return torch.cat([idx for idx, _, _ in self._sweep_log], dim=1).cpu().numpy().astype(np.int64)
+
+    def ceiling_rows(self):
+        """[n, 5] int64 = (dataset position, sentence, proposal, I, U): per sentence the proposal with the largest IoU against
+        its target -- the bound no scoring of these proposals exceeds.  One device->host copy."""
+        self._sweep_on("ceiling_rows()")
+        n = len(self.iu_owner)
+        out = np.zeros((n, 5), dtype=np.int64)
+        if n:
+            out[:, 0:2] = np.asarray(self.iu_owner, dtype=np.int64).reshape(n, 2)
+            out[:, 2:5] = torch.cat([cl for _, _, cl in self._sweep_log], dim=0).cpu().numpy()
+        return out
+
+    def sweep_metrics(self, dist=None):
+        """sweep.sweep_metrics_from_rows of the job: {"configs": one metrics() dict per configuration (with its r, alpha, k1,
+        k2), "ceiling": {oIoU, mIoU, cum, n_sentences}, "best": index of the largest oIoU_final}; with an initialised
+        torch.distributed the rows of all ranks are gathered first (ONE dist.gather_rows exchange for all configurations)."""
+        from . import dist as D, sweep as SW
+        self._sweep_on("sweep_metrics()")
+        packed = D.gather_rows(SW.pack_rows(self.sweep_rows(), self.ceiling_rows()), dist, self.model.device)
+        rows, ceil6 = SW.unpack_rows(packed, len(self.sweep))
+        return SW.sweep_metrics_from_rows(rows, ceil6, self.sweep)
 
     def metrics(self, dist=None):
         """Hybridgl_main.py:240-247: overall IoU and mean IoU, pure and with spatial guidance; with an initialised

@@ -369,6 +369,34 @@ size_t hgl_score_group_workspace_bytes(const HglGroupRef* refs, int R, int E);
 int hgl_score_group(const HglGroupRef* refs, int R, int E, float logit_scale, float r, float alpha, int64_t* cum, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* hgl_score_group under C configurations (r, alpha, k1, k2) in ONE pass: the sweep of the tail's hyper-parameters
+ * (Hybridgl_main.py:57-63).  Min / max and pooling run once (they do not depend on the configuration), one pass over the mask
+ * planes counts |mask_n & target| of EVERY proposal with every distinct target pointer of a ref (a configuration's I / U is then
+ * a look-up), and one workgroup per (sentence, distinct r) builds the soft-maxes and the top-k lists to the largest k of that
+ * r -- a list for a smaller k is its prefix -- before one thread per configuration runs the relation sums and the blend.
+ * refs: as for hgl_score_group, with the same checks; their k1, k2, idx, iu and score rows are NOT used -- per ref the sweep
+ * record stands in: k HOST [C,2] = (k1, k2) of every configuration for THIS ref (the caller carries the clamp of
+ * Hybridgl_main.py:178-181 per configuration; clamped to N here as there), idx [C,S,2] int32, iu [C,S,4] int64 and
+ * ceiling [S,3] int64 = (n, I, U) of the proposal with the largest I / U against the sentence's target -- the bound no scoring
+ * exceeds -- compared exactly (I_a U_b > I_b U_a in 64 bits), lowest index on ties, a pair with U = 0 ranking as ratio 0.
+ * configs: HOST [C], 1 <= C <= 256, at most 32 distinct r (by bit pattern); every k in [1, 16] after the clamp: HGL_EINVAL
+ * otherwise, before anything is written.  cum [C,4] int64 (may be NULL) is INCREMENTED by the column sums of every ref's iu[c],
+ * cum_ceiling [2] int64 (may be NULL) by the sums of the ceilings' I and U, on the device.
+ * CONTRACT: row c of idx, iu and cum equals, bit for bit, what hgl_score_group returns for the same refs with r = configs[c].r,
+ * alpha = configs[c].alpha and each ref's k1, k2 = k[c] -- NaN logits and NaN coherence scores included (the same device code
+ * in the same order).  The workspace depends on the number of distinct r: query it with the call's own configs. */
+typedef struct { float r, alpha; } HglSweepConfig;
+typedef struct HglSweepRef {
+  const int32_t* k;                   /* HOST [C,2] */
+  int32_t* idx;                       /* [C,S,2] */
+  int64_t* iu;                        /* [C,S,4] */
+  int64_t* ceiling;                   /* [S,3] */
+} HglSweepRef;
+size_t hgl_score_group_sweep_workspace_bytes(const HglGroupRef* refs, int R, int E, const HglSweepConfig* configs, int C);
+int hgl_score_group_sweep(const HglGroupRef* refs, const HglSweepRef* sweep, int R, int E, float logit_scale,
+                          const HglSweepConfig* configs, int C, int64_t* cum, int64_t* cum_ceiling, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* Compute_IoU on a mask selected on the device: pred = masks[idx[which]] ([N,HW] uint8),
  * so the winning index never travels to the host (Hybridgl_main.py:169-171,227-230). */
 int hgl_iou_select(const uint8_t* masks, const int32_t* idx, int which, const uint8_t* gt,

@@ -1,9 +1,20 @@
 #!/usr/bin/env python3
 """Timing of the scoring tail on the benchmark's shape (64 proposals, 640 x 640, 3 sentences, E = 512): hgl_score_group (sixteen
 refs per call) and hgl_score_ref (one call per ref: the same host path and kernels over a table of one row, after a descriptor
-upload of its own) against the per-sentence launches; HIP events around 20 calls each."""
+upload of its own) against the per-sentence launches; HIP events around 20 calls each.
+
+--sweep C: instead, the hyper-parameter sweep on the same sixteen refs -- ONE hgl_score_group_sweep call over C configurations
+(r x alpha grid, k1 = 3, k2 = 6) against C hgl_score_group calls and against one such call, alternated --rounds times, the
+medians reported (and written to --json OUT)."""
+import argparse
 import os
 import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--sweep", type=int, default=0, metavar="C")
+ap.add_argument("--rounds", type=int, default=7)
+ap.add_argument("--json", default="")
+opt = ap.parse_args()
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -66,6 +77,51 @@ def per_ref16():
     for q in grp:
         ops.score_ref(q["hybrid"], q["text"], q["boxes"], q["masks"], q["sentences"], 100.0, 0.5, 3, 6, 0.6, cum=cum)
 
+
+def sweep_bench(C, rounds):
+    import json
+    import statistics
+    nr = max(1, int(round(C ** 0.5)))
+    configs = [((c % nr) / max(nr - 1, 1), (c // nr) / max((C - 1) // nr, 1), 3, 6) for c in range(C)]
+    cumC = torch.zeros((C, 4), dtype=torch.int64, device=dev)
+    cumc = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def sweep():
+        ops.score_group_sweep(grp, configs, 100.0, cum=cumC, cum_ceiling=cumc)
+
+    def loop():
+        for r, a, k1, k2 in configs:
+            ops.score_group(grp, 100.0, r, a, cum=cum)
+
+    def once(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n * 1e3
+
+    t = {"sweep": [], "loop": [], "single": []}
+    for _ in range(rounds):      # alternated
+        t["single"].append(once(group16, 10))
+        t["sweep"].append(once(sweep, 5))
+        t["loop"].append(once(loop, 1))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    out = {"shape": "16 refs x 64 proposals x 640 x 640 x 3 sentences, E = 512", "configurations": C, "distinct_r": len({c[0] for c in configs}),
+           "rounds": rounds, "us_sweep_call": med["sweep"], "us_C_score_group_calls": med["loop"], "us_one_score_group_call": med["single"],
+           "sweep_over_C_calls": med["sweep"] / med["loop"], "extra_us_per_group_with_sweep_on": med["sweep"],
+           "us_all_rounds": t}
+    print(json.dumps(out))
+    if opt.json:
+        json.dump(out, open(opt.json, "w"), indent=1)
+
+
+if opt.sweep > 0:
+    sweep_bench(opt.sweep, opt.rounds)
+    sys.exit(0)
 
 timed(group16, "hgl_score_group, 16 distinct refs (4 launches)", refs=16)
 timed(per_ref16, "hgl_score_ref x 16 distinct refs (64 launches)", refs=16)
