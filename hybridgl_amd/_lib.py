@@ -226,6 +226,8 @@ PROTOTYPES = {
     "hgl_rle_from_string": (_I, [C.c_char_p, _VP, _LL, C.POINTER(C.c_longlong)]),
     "hgl_rle_decode_workspace_bytes": (_SZ, [_I, _I, _I, _LL]),
     "hgl_rle_decode_device": (_I, [_VP, _LL, _VP, _I, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
+    "hgl_rle_decode_group_workspace_bytes": (_SZ, [_I, _LL]),
+    "hgl_rle_decode_group_device": (_I, [_VP, _LL, _VP, _I, _VP, _I, _VP, _LL, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_rle_iou_workspace_bytes": (_SZ, [_I, _I, _I, _LL, _LL]),
     "hgl_rle_iou_device": (_I, [_VP, _LL, _VP, _VP, _LL, _VP, _I, _I, _I, _VP, _VP, _SZ, _VP]),
 }

@@ -24,6 +24,7 @@
 // plane (bit p % 32 of word p / 32; whenever the counts do not fit but ceil(H*W/32) words do), 2 = neither fits, nothing
 // written, 3 = the index is outside [0, N), nothing read or written.  Words beyond what the form defines keep their bytes.
 #include "hgl_common.h"
+#include "rle_group.h"      // RleGroup, rle_group_plan: plain C++, shared with the sanitizer harness
 
 namespace {
 
@@ -362,6 +363,218 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_rows_kernel(const uint32_t* _
   }
 }
 
+// ---- a whole group's proposals in one call (hgl_rle_decode_group_device): S entries that belong to G <= 64 images of their own
+// sizes.  The geometry rides in the kernel arguments (RleGroup, by value: no descriptor memory, nothing to keep alive), and the
+// two launches are those of hgl_rle_decode_device whatever G is: rle_group_starts_kernel is rle_starts_kernel with the entry's
+// image looked up and the mask's box read off the runs; rle_group_rows_kernel finds (image, entry, tile) of a block in the
+// host's tile prefix sums and takes the 4-column or the byte path as its image's width and base address allow.  Both searches
+// (<= 6 steps over <= 64 rows of the arguments) are uniform over the block.
+
+// the last g with v[g] <= key (v non-decreasing, v[0] <= key): the image that owns entry / tile `key`; images without entries
+// share their successor's value and are passed over
+template <typename T>
+__device__ __forceinline__ int rle_group_find(const T* v, int G, T key) {
+  int lo = 0, hi = G - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (v[mid] <= key) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the workgroup-wide maximum of v (rle_block_sum's shape)
+__device__ __forceinline__ unsigned rle_block_max(unsigned v, unsigned* lds) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const unsigned o = __shfl_xor(v, d, 64);
+    v = v > o ? v : o;
+  }
+  __syncthreads();      // the previous use of lds is over
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const unsigned a = lds[0] > lds[1] ? lds[0] : lds[1], b = lds[2] > lds[3] ? lds[2] : lds[3];
+  return a > b ? a : b;
+}
+
+// The box of the pixels [a, b) of run order (a < b <= H*W) joined into (x0, y0, x1, y1): x in [a / H, (b-1) / H]; within one
+// column y in [a % H, (b-1) % H], and a stretch that crosses a column boundary holds a pixel of row H-1 and one of row 0.
+__device__ __forceinline__ void rle_box_join(unsigned a, unsigned b, unsigned H, unsigned& x0, unsigned& y0, unsigned& x1,
+                                             unsigned& y1) {
+  const unsigned xa = a / H, xb = (b - 1u) / H;
+  unsigned ya = a - xa * H, yb = (b - 1u) - xb * H;
+  if (xa != xb) { ya = 0; yb = H - 1u; }
+  x0 = x0 < xa ? x0 : xa;
+  x1 = x1 > xb ? x1 : xb;
+  y0 = y0 < ya ? y0 : ya;
+  y1 = y1 > yb ? y1 : yb;
+}
+
+// rle_starts_kernel's pass with the entry's image looked up and the box: boxes [S,4] receives the inclusive XYXY box of the mask
+// the entry decodes to (batched_mask_to_box, utils/amg.py:303-346; zeros for an empty mask and for code 2), read off the runs
+// (form 0) or the plane words (form 1) in the pass that scans them.  (A body shared with rle_starts_kernel changed that
+// kernel's register allocation and schedule, so the pass is written out here.)
+__global__ __launch_bounds__(RLE_THREADS) void rle_group_starts_kernel(const uint32_t* __restrict__ slots, long long slot_words,
+                                                                       const int32_t* __restrict__ table, const RleGroup grp,
+                                                                       uint32_t* __restrict__ E, long long e_stride,
+                                                                       int32_t* __restrict__ status, int32_t* __restrict__ boxes) {
+  __shared__ unsigned red[4];
+  __shared__ unsigned long long wtot[4];
+  const int s = blockIdx.x;
+  const int g = rle_group_find(grp.first, grp.G, s);
+  const int H = grp.H[g], W = grp.W[g];
+  int32_t* box = boxes + (size_t)s * 4;
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const int n = table[(size_t)s * 4], form = table[(size_t)s * 4 + 1];
+  const unsigned HW = (unsigned)H * (unsigned)W;      // < 2^31 (checked by the host entry)
+  const unsigned plane_words = (HW + 31u) / 32u;
+  int32_t* row = status + (size_t)s * 4;
+  if (!rle_entry_usable(n, form, slot_words, plane_words)) {      // uniform over the workgroup
+    if (t == 0) {
+      row[0] = 2; row[1] = 0; row[2] = 0; row[3] = 0;
+      box[0] = 0; box[1] = 0; box[2] = 0; box[3] = 0;
+    }
+    return;
+  }
+  const uint32_t* slot = slots + (size_t)s * (size_t)slot_words;
+  unsigned area = 0;
+  unsigned bx0 = 0x7fffffffu, by0 = 0x7fffffffu, bx1 = 0, by1 = 0;      // the box of this thread's pixels
+  int code = 0;
+  if (form == 1) {
+    const unsigned tail = HW - 32u * (plane_words - 1u);      // 1 .. 32 valid bits in the last word
+    for (unsigned w = t; w < plane_words; w += RLE_THREADS) {
+      uint32_t v = slot[w];
+      if (w == plane_words - 1u && tail < 32u) v &= (1u << tail) - 1u;
+      area += __popc(v);
+      if (v) {
+        // the word's set pixels column by column (a word spans several columns when H < 32)
+        const unsigned p = 32u * w;
+        unsigned x = p / (unsigned)H, y = p - x * (unsigned)H, filled = 0;
+        while (filled < 32u && x < (unsigned)W) {
+          const unsigned m = 32u - filled < (unsigned)H - y ? 32u - filled : (unsigned)H - y;
+          const uint32_t seg = (v >> filled) & (m == 32u ? 0xffffffffu : ((1u << m) - 1u));
+          if (seg) {
+            const unsigned ya = y + (unsigned)__builtin_ctz(seg), yb = y + 31u - (unsigned)__builtin_clz(seg);
+            bx0 = bx0 < x ? bx0 : x;
+            bx1 = bx1 > x ? bx1 : x;
+            by0 = by0 < ya ? by0 : ya;
+            by1 = by1 > yb ? by1 : yb;
+          }
+          filled += m;
+          y += m;
+          if (y == (unsigned)H) { y = 0; ++x; }
+        }
+      }
+    }
+  } else {
+    uint32_t* Es = E + (size_t)s * (size_t)e_stride;      // n + 1 <= slot_words + 1 <= e_stride entries
+    // E[k] = min(H*W, counts[0] + .. + counts[k-1]); the sums are exact in 64 bits (n < 2^31 counts < 2^32)
+    unsigned long long carry = 0;
+    if (t == 0) Es[0] = 0;
+    for (unsigned base = 0; base < (unsigned)n; base += RLE_THREADS) {
+      const unsigned i = base + t;
+      const unsigned long long own = i < (unsigned)n ? (unsigned long long)slot[i] : 0ull;
+      unsigned long long v = own;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long a = __shfl_up(v, d, 64);
+        if (lane >= d) v += a;
+      }
+      __syncthreads();      // the previous chunk's reads of wtot are over
+      if (lane == 63) wtot[wave] = v;
+      __syncthreads();
+      unsigned long long sum = carry + v, tot = 0;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        if (w < wave) sum += wtot[w];
+        tot += wtot[w];
+      }
+      if (i < (unsigned)n) {
+        const unsigned end = sum < (unsigned long long)HW ? (unsigned)sum : HW;
+        const unsigned start = sum - own < (unsigned long long)HW ? (unsigned)(sum - own) : HW;
+        Es[i + 1] = end;
+        if (i & 1u) area += end - start;
+        if ((i & 1u) && end > start) rle_box_join(start, end, (unsigned)H, bx0, by0, bx1, by1);
+      }
+      carry += tot;
+    }
+    code = carry == (unsigned long long)HW ? 0 : 1;
+  }
+  area = rle_block_sum(area, red);
+  if (t == 0) { row[0] = code; row[1] = (int32_t)area; row[2] = 0; row[3] = 0; }
+  // minima as maxima of the complement; an empty mask keeps the zeros of batched_mask_to_box
+  bx0 = 0x7fffffffu - rle_block_max(0x7fffffffu - bx0, red);
+  by0 = 0x7fffffffu - rle_block_max(0x7fffffffu - by0, red);
+  bx1 = rle_block_max(bx1, red);
+  by1 = rle_block_max(by1, red);
+  if (t == 0) {
+    box[0] = area ? (int32_t)bx0 : 0;
+    box[1] = area ? (int32_t)by0 : 0;
+    box[2] = area ? (int32_t)bx1 : 0;
+    box[3] = area ? (int32_t)by1 : 0;
+  }
+}
+
+// rle_rows_kernel's tile: rows 64j .. 64j+63 of columns x .. x+V-1 of entry s (j < HW64, x < W) into the entry's mask at dst
+// [H,W]; V columns per lane (4: one aligned 32-bit store per row when W % 4 == 0 and dst is 4-byte aligned).  No barrier, no cross-lane operation.
+template <int V>
+__device__ __forceinline__ void rle_rows_tile(const uint32_t* __restrict__ slots, long long slot_words,
+                                              const int32_t* __restrict__ table, const uint32_t* __restrict__ E, long long e_stride,
+                                              const int32_t* __restrict__ status, int s, int H, int W, int j, int x,
+                                              uint8_t* __restrict__ dst) {
+  const int y0 = j * 64;
+  const int rows = H - y0 < 64 ? H - y0 : 64;
+  unsigned long long c[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) c[k] = 0;
+  if (status[(size_t)s * 4] != 2) {
+    const int n = table[(size_t)s * 4], form = table[(size_t)s * 4 + 1];
+    const unsigned plane_words = ((unsigned)H * (unsigned)W + 31u) / 32u;
+#pragma unroll
+    for (int k = 0; k < V; ++k)      // x + k < W: W % 4 == 0 on the 4-column path
+      c[k] = rle_plane_word(slots + (size_t)s * (size_t)slot_words, form, n, E + (size_t)s * (size_t)e_stride, plane_words, H, x + k, j);
+  }
+  dst = dst + (size_t)y0 * W + x;      // (y0 + r) * W + x (+ 3) < H * W
+#pragma unroll 8
+  for (int r = 0; r < rows; ++r) {
+    if (V == 4) {
+      uint32_t v = 0;
+#pragma unroll
+      for (int k = 0; k < V; ++k) v |= (uint32_t)((c[k] >> r) & 1ull) << (8 * k);
+      *reinterpret_cast<uint32_t*>(dst + (size_t)r * W) = v;
+    } else {
+      dst[(size_t)r * W] = (uint8_t)((c[0] >> r) & 1ull);
+    }
+  }
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_group_rows_kernel(const uint32_t* __restrict__ slots, long long slot_words,
+                                                                     const int32_t* __restrict__ table,
+                                                                     const uint32_t* __restrict__ E, long long e_stride,
+                                                                     const int32_t* __restrict__ status, const RleGroup grp,
+                                                                     uint8_t* __restrict__ masks) {
+  const unsigned tile = blockIdx.x;
+  const int g = rle_group_find(grp.tile0, grp.G, tile);
+  const int H = grp.H[g], W = grp.W[g];
+  const bool wide = (grp.wide >> g) & 1ull;
+  const int HW64 = (H + 63) / 64;
+  const int col_tiles = (W + (wide ? 255 : 63)) / (wide ? 256 : 64), row_tiles = (HW64 + 3) / 4;
+  const unsigned local = tile - grp.tile0[g];
+  const int k = (int)(local / (unsigned)(col_tiles * row_tiles));      // the entry within its image
+  const int rem = (int)(local % (unsigned)(col_tiles * row_tiles));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int j = (rem / col_tiles) * 4 + wave;
+  uint8_t* dst = masks + grp.off[g] + (size_t)k * H * W;
+  const int s = grp.first[g] + k;
+  if (wide) {
+    const int x = ((rem % col_tiles) * 64 + lane) * 4;
+    if (j < HW64 && x < W) rle_rows_tile<4>(slots, slot_words, table, E, e_stride, status, s, H, W, j, x, dst);
+  } else {
+    const int x = (rem % col_tiles) * 64 + lane;
+    if (j < HW64 && x < W) rle_rows_tile<1>(slots, slot_words, table, E, e_stride, status, s, H, W, j, x, dst);
+  }
+}
+
 // one thread per plane word: word q = x*HW64 + j of entry s, q_tiles workgroups per entry
 __global__ __launch_bounds__(RLE_THREADS) void rle_plane_kernel(const uint32_t* __restrict__ slots, long long slot_words,
                                                                 const int32_t* __restrict__ table, const uint32_t* __restrict__ E,
@@ -480,6 +693,38 @@ int hgl_rle_decode_device(const uint32_t* slots, long long slot_words, const int
     hipLaunchKernelGGL(rle_rows_kernel<1>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
                        (const uint32_t*)E, e_stride, (const int32_t*)status, H, W, HW64, col_tiles, row_tiles, masks);
   return hgl_check_launch("rle_decode_device");
+}
+
+size_t hgl_rle_decode_group_workspace_bytes(int S, long long slot_words) {
+  if (S <= 0 || slot_words < 0) return 0;
+  return rle_starts_bytes(S, slot_words);
+}
+
+int hgl_rle_decode_group_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S,
+                                const int64_t* images_host, int G, uint8_t* masks, long long masks_bytes, int32_t* boxes_xyxy,
+                                int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(slots && table && images_host && masks && boxes_xyxy && status && S > 0 && slot_words >= 0 && masks_bytes >= 0,
+              "rle_decode_group_device: bad arguments");
+  RleGroup grp;
+  long long tiles = 0;
+  char why[200];
+  if (rle_group_plan(images_host, G, S, (uintptr_t)masks, masks_bytes, &grp, &tiles, why, sizeof(why)) != 0) {
+    hgl_set_error("rle_decode_group_device: %s", why);
+    return HGL_EINVAL;
+  }
+  if (!ws || ws_bytes < hgl_rle_decode_group_workspace_bytes(S, slot_words)) {
+    hgl_set_error("rle_decode_group_device: workspace too small");
+    return HGL_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* E = (uint32_t*)ws;
+  const long long e_stride = slot_words + 1;
+  hipLaunchKernelGGL(rle_group_starts_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots, slot_words, table, grp, E, e_stride,
+                     status, boxes_xyxy);
+  hipLaunchKernelGGL(rle_group_rows_kernel, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
+                     (const uint32_t*)E, e_stride, (const int32_t*)status, grp, masks);
+  return hgl_check_launch("rle_decode_group_device");
 }
 
 size_t hgl_rle_iou_workspace_bytes(int S, int H, int W, long long slot_words_a, long long slot_words_b) {

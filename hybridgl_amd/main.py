@@ -17,6 +17,8 @@ background is OpenCV's fixed-point GaussianBlur restated on the device (Hybridgl
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m hybridgl_amd.main --real ...
     python -m hybridgl_amd.main --synthetic 8 --save_masks out      # ... and later, with no model or checkpoint:
     python -m hybridgl_amd.main --synthetic 8 --score_masks out     # the same report from the saved masks and the ground truth
+    python -m hybridgl_amd.main --real ... --save_proposals props   # SAM's proposals kept per image (hybridgl_amd/proposals.py) ...
+    python -m hybridgl_amd.main --real ... --proposals_dir props --fusion_mode L2G     # ... and evaluated from, with no SAM
 
 Under a launcher (WORLD_SIZE > 1) rank r evaluates the items i = r (mod R) of the loader's order and the metric rows
 are gathered once at the end (hybridgl_amd/dist.py); rank 0 writes the report.
@@ -90,6 +92,12 @@ def default_argument_parser():
     p.add_argument("--score_masks", default="", metavar="DIR",
                    help="score the predictions a run saved with --save_masks DIR against the dataset's ground truth, without any "
                         "model or checkpoint (the dataset flags as in that run); exits non-zero when a stored count differs")
+    p.add_argument("--save_proposals", default="", metavar="DIR",
+                   help="with --real: keep the mask generator's proposals beside the run, DIR/<image_id>.json in the format of "
+                        "SAM's scripts/amg.py --convert-to-rle plus DIR/meta.json (INTEGRATION.md); the run itself is unchanged")
+    p.add_argument("--proposals_dir", default="", metavar="DIR",
+                   help="with --real: take every image's proposals from a store --save_proposals (or SAM's amg.py) wrote instead of "
+                        "running SAM: no SAM model is built, no checkpoint read; an image the store lacks is an error")
     p.add_argument("--sweep", default="", metavar="SPEC",
                    help="score every ref under a grid of the tail's hyper-parameters in the same pass, e.g. "
                         "'r=0.3,0.5,0.7;alpha=0:1:0.1;k1=3;k2=6': an axis is a value list or lo:hi:step (hi included), an axis "
@@ -166,6 +174,7 @@ class RealRefs:
         self._imgs = collections.OrderedDict()
         self._lock = threading.Lock()
         self.decoded = 0        # images decoded / uploaded (<= items loaded)
+        self.proposals = None   # a proposals.StoredProposals: its files are read and packed here, on the loader threads
 
     def jobs(self, rank=0, world=1):
         from .dist import shard_by_groups
@@ -231,6 +240,8 @@ class RealRefs:
         H, W = sam_img.shape[:2]
         rid = self.ds.ref_ids[i]
         ref = self.ds.refer.Refs[rid]
+        if self.proposals is not None:
+            self.proposals.prefetch(int(ref["image_id"]), (H, W))
         annot, sentences = self.ds.target(i), self.ds.sentence_raws[i]
         strings, sents = [], []
         t = lambda a: pin_upload(a, dev)
@@ -311,6 +322,7 @@ class RealPhraseCut:
         self.parse = json.load(open(args.parse_json)) if args.parse_json else {}
         self.n = len(self.ds) if args.max_refs <= 0 else min(len(self.ds), args.max_refs)
         self.decoded = 0
+        self.proposals = None   # as RealRefs.proposals
 
     def jobs(self, rank=0, world=1):
         from .dist import shard_indices
@@ -327,6 +339,8 @@ class RealPhraseCut:
             return None
         dev = self.dev
         H, W = item["height"], item["width"]
+        if self.proposals is not None:
+            self.proposals.prefetch(int(item["image_id"]), (H, W))
         sam_img = pin_upload(item["sam_img"], dev)
         file_img = sam_img if item["file_img"] is None else pin_upload(item["file_img"], dev)
         image_norm = T.phrasecut_image_norm(file_img, H, W)             # dataset_phrasecut.py:49-51 + Hybridgl_main_PhraseCut.py:69-70
@@ -361,6 +375,17 @@ def split_by(dataset):
     return "umd" if dataset == "refcocog" else "unc"          # Hybridgl_main.py:26-29
 
 
+def check_proposal_flags(args):
+    save, read = getattr(args, "save_proposals", ""), getattr(args, "proposals_dir", "")
+    if save and read:
+        raise SystemExit("--save_proposals and --proposals_dir exclude each other: a run either writes a store or reads one")
+    if (save or read) and not args.real:
+        raise SystemExit("--save_proposals / --proposals_dir need --real: a store is keyed by the dataset's image ids")
+    if read and getattr(args, "prepare", False):
+        raise SystemExit("--prepare rehearses the loop on synthetic images, which a proposal store does not hold: drop one of "
+                         "--prepare and --proposals_dir")
+
+
 def build_models(args, dev):
     """(CLIPViTFM, SamAutomaticMaskGenerator | None, GEM model | None) as Hybridgl_main.py:36-38,47-48,66-74 builds them"""
     from .backbone import CLIPViTFM
@@ -370,7 +395,11 @@ def build_models(args, dev):
         args.precision = ops.default_precision()
     model = CLIPViTFM(model_name=args.clip_model, device=dev, precision=args.precision).eval()
     gen = None
-    if args.sam or args.real:
+    check_proposal_flags(args)
+    if getattr(args, "proposals_dir", ""):      # the store stands in for the generator: no SAM model, no checkpoint
+        from .proposals import StoredProposals
+        gen = StoredProposals(args.proposals_dir, dev)
+    elif args.sam or args.real:
         from .sam import SamAutomaticMaskGenerator, sam_model_registry
         sam = sam_model_registry[args.sam_model](device=dev, precision=args.precision)
         # Hybridgl_main.py:67-73
@@ -506,15 +535,27 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
         from .sweep import parse_sweep_spec
         own = inspect.signature(HybridGLPipeline.__init__).parameters      # the run's values: the pipeline's defaults
         sweep = parse_sweep_spec(args.sweep, *(own[n].default for n in ("r", "alpha", "k1", "k2")))
+    check_proposal_flags(args)
+    recorder = None
+    if getattr(args, "save_proposals", ""):
+        from .proposals import ProposalRecorder, generator_settings
+        recorder = gen = ProposalRecorder(gen, args.save_proposals, generator_settings(
+            gen, sam_model=args.sam_model, precision=getattr(args, "precision", None), proposal_cap=getattr(args, "proposal_cap", 0)))
     pipe = HybridGLPipeline(model, fusion_mode=args.fusion_mode, masking_block=getattr(args, "masking_block", 9), mask_generator=gen,
                             use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir), sweep=sweep)
     rr, jobs, make = dataset_items(args, dev, rank, world, sam_img_size=1024 if gen else 0, gem=gem_model is not None)
+    if rr is not None and getattr(gen, "prefetch", None) is not None:
+        rr.proposals = gen      # files, JSON and run lengths are the loader threads' work
     # Hybridgl_main.py:45,79: DataLoader(num_workers=4) feeding the loop; here loader threads feed the grouped loop
     loader = Prefetcher(jobs, make, workers=args.workers, depth=2 * args.group + 2, device=dev)
     cap = getattr(args, "proposal_cap", 0) or None
     if getattr(args, "prepare", False) and args.group > 1:
         # workspaces, allocator blocks and kernel instantiations of a full group, before the first item arrives
+        if recorder is not None:
+            recorder.recording = False      # the rehearsal's synthetic images are not the dataset's
         pipe.prepare(group=args.group, H=640, W=640, proposals=cap or args.proposals)
+        if recorder is not None:
+            recorder.recording = True
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     if args.group <= 1:      # ref by ref on one stream (Hybridgl_main.py:79-230 as written)
@@ -533,11 +574,17 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
     dt = time.perf_counter() - t0
     if save_dir:
         save_masks(pipe, save_dir, rank)      # this rank's own sentences: no collective
+    if recorder is not None:
+        recorder.flush()      # this rank's own images (shard_by_groups): no collective
     m = pipe.metrics(dist)      # one all-gather of the metric rows; identical on every rank
     stats = {"refs": n, "seconds": dt, "seconds_job": D.max_over_ranks(dt, dist, dev), "loader_wait_s": loader.wait_s, "loader_make_s": loader.make_s,
              "images_decoded": rr.decoded if rr is not None else None, "image_cache_hits": pipe.cache_hits,
              "skipped": getattr(pipe, "skipped", 0), "groups": getattr(pipe, "groups_run", None),
              "workers": args.workers, "group": args.group}
+    if recorder is not None:
+        stats["proposals_saved"] = recorder.written
+    if getattr(args, "proposals_dir", ""):
+        stats["proposal_store"] = gen.settings()
     if sweep is not None:      # one more exchange of rows, on every rank
         stats["sweep"] = sweep_report(sweep, pipe.sweep_metrics(dist))
     return m, stats
@@ -576,6 +623,9 @@ def main(args):
     sweep = stats.pop("sweep", None)
     if rank != 0:
         return m
+    if "proposal_store" in stats:
+        print(f"proposals from {args.proposals_dir} (no SAM model built); generator settings of the store: "
+              + (", ".join(f"{k}={v}" for k, v in stats["proposal_store"].items()) or "none recorded (no meta.json)"))
     if sweep is not None:
         import json
         b = sweep["best"]

@@ -436,6 +436,60 @@ def rle_decode(slots, table, H, W, out=None):
     return masks, status
 
 
+def rle_group_layout(sizes, counts):
+    """(images [G,4] int64 = H, W, first entry, byte offset; total bytes) of a group decoded back to back: image g's
+    counts[g] masks of sizes[g] = (H, W) follow those of image g-1 with no padding"""
+    import numpy as np
+    if len(sizes) != len(counts):
+        raise ValueError(f"rle_group_layout: {len(sizes)} sizes and {len(counts)} counts")
+    images = np.zeros((len(sizes), 4), dtype=np.int64)
+    e = o = 0
+    for g, ((H, W), n) in enumerate(zip(sizes, counts)):
+        if int(n) < 0:
+            raise ValueError(f"rle_group_layout: image {g} has {n} entries")
+        images[g] = (int(H), int(W), e, o)
+        e += int(n)
+        o += int(n) * int(H) * int(W)
+    return images, o
+
+
+def rle_decode_group(slots, table, sizes, counts, out=None, aux=None):
+    """A whole group's proposals in one call (hgl_rle_decode_group_device on the current stream, no synchronisation): the
+    S = sum(counts) entries of slots / table (what rle_encode or rle_pack returns) belong to G = len(sizes) <= 64 images,
+    counts[g] consecutive entries of sizes[g] = (H, W) each; an image may own none.  Returns (masks: a list of G uint8 views
+    [counts[g], H, W], values 0 / 1, packed back to back in one buffer; boxes [S,4] int32: inclusive XYXY of every mask as
+    sam.mask_boxes gives it, derived from the runs; status [S,4] int32 as rle_decode).  `out`: a contiguous uint8 device
+    tensor of exactly the packed size to decode into; every byte of it is written.  boxes and status are the two halves of
+    ONE int32 buffer [2,S,4] (`aux`: such a contiguous device tensor to use for it), so a caller that wants both on the host
+    copies one tensor.  The number of launches depends neither on G nor on the sizes."""
+    lib = _lib.load()
+    sp, sw, tp, S = _rle_set(slots, table, "rle_decode_group")
+    images, total = rle_group_layout(sizes, counts)
+    G = len(images)
+    if int(sum(int(n) for n in counts)) != S:
+        raise ValueError(f"rle_decode_group: counts sum to {sum(counts)}, the set has {S} entries")
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=slots.device)
+    elif out.numel() != total:
+        raise ValueError(f"out: expected {total} uint8 elements, got {out.numel()}")
+    if aux is None:
+        aux = torch.empty((2, S, 4), dtype=torch.int32, device=slots.device)
+    elif tuple(aux.shape) != (2, S, 4) or aux.dtype != torch.int32 or not aux.is_contiguous():
+        raise ValueError(f"aux: expected a contiguous int32 tensor [2, {S}, 4], got {tuple(aux.shape)} {aux.dtype}")
+    boxes, status = aux[0], aux[1]
+    flat = out.view(-1)
+    masks = [flat[int(o):int(o) + int(n) * int(H) * int(W)].view(int(n), int(H), int(W))
+             for (H, W, _, o), n in zip(images, counts)]
+    if S == 0:
+        return masks, boxes, status
+    op = _dev(out, torch.uint8, "out")
+    need = lib.hgl_rle_decode_group_workspace_bytes(S, sw)
+    ws = workspace(need, slots.device, "rle")
+    check(lib.hgl_rle_decode_group_device(sp, sw, tp, S, images.ctypes.data, G, op, total, boxes.data_ptr(), status.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream()), "hgl_rle_decode_group_device")
+    return masks, boxes, status
+
+
 def rle_iou(slots_a, table_a, slots_b, table_b, H, W):
     """(|A & B|, |A | B|) of entry s of one encoded set against entry s of another, int64 [S,2] on the device, computed on
     bit planes (hgl_rle_iou_device; no mask is expanded to bytes).  (-1, -1) where either slot holds no mask."""

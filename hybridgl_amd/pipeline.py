@@ -248,12 +248,14 @@ class HybridGLPipeline:
         else:
             if gen_here is not None:
                 # Hybridgl_main.py:85 mask_generator.generate(sam_img), kept on the device
+                # a proposal store (hybridgl_amd/proposals.py) is keyed by the image id; SAM's own generator is called as ever
+                by_id = {"image_id": ref.image_id} if getattr(gen_here, "wants_image_ids", False) else {}
                 if self.use_sam_masks and getattr(gen_here, "crop_n_layers", 0) > 0:
                     # PhraseCut configuration (Hybridgl_main_PhraseCut.py:56-62): crop layers, cross-crop NMS
-                    prop = gen_here.generate_device_crops(ref.sam_img)[:4]
+                    prop = gen_here.generate_device_crops(ref.sam_img, **by_id)[:4]
                 elif self.use_sam_masks or self.fixed_proposals is not None:
                     prop = gen_here.generate_device(ref.sam_img, resized=ref.sam_resized,
-                                                    fixed_n=self.fixed_proposals)
+                                                    fixed_n=self.fixed_proposals, **by_id)
                 else:  # proposal kernels only, nothing read back
                     prop = gen_here.propose(ref.sam_img, resized=ref.sam_resized)
                 if self.use_sam_masks:
@@ -621,7 +623,10 @@ class HybridGLPipeline:
                         # everything of the group up to its first count read-back is enqueued here without a wait (with crop
                         # layers, the PhraseCut configuration: every crop of every image); the read-backs come after the CLIP
                         # stage of the previous group has been enqueued
-                        state = gen.group_begin(imgs, proposal_cap, ev_enc)
+                        if getattr(gen, "wants_image_ids", False):      # a store is keyed by the image, not by its pixels
+                            state = gen.group_begin(imgs, proposal_cap, ev_enc, image_ids=[units[i][0].image_id for i in fresh])
+                        else:
+                            state = gen.group_begin(imgs, proposal_cap, ev_enc)
                     else:    # proposal kernels only; their output is not consumed (synthetic benchmark, seeded masks)
                         self.last_proposals = gen.propose_batch(imgs)[-1]
             if pending is not None:

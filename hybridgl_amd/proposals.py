@@ -1,0 +1,438 @@
+"""SAM proposals as an artefact on disk: written beside a normal run, read back in place of the mask generator.
+
+The proposals of an image are a function of the image and the generator's settings alone, and every axis of an experiment
+that lies behind them (fusion mode, masking block, CLIP model, precision of the CLIP stage, the GEM heat-map) re-runs SAM for
+nothing.  A store is a directory in the file format of the reference's scripts/amg.py:229-232 with --convert-to-rle:
+
+    <image_id>.json   the list SamAutomaticMaskGenerator.generate() returns in "coco_rle" mode (automatic_mask_generator.py:
+                      137-195): records {"segmentation": {"size": [H, W], "counts": COCO string}, "area", "bbox" XYWH,
+                      "predicted_iou", "point_coords", "stability_score", "crop_box"}; an image without a proposal is []
+    meta.json         the generator's settings (generator_settings), for the reader's report
+
+ProposalStore     the directory: atomic writes (temporary name, then rename), reads that name the image when a file is bad
+ProposalRecorder  wraps a generator that speaks group_begin / group_cleanup / group_finish: after group_finish one
+                  ops.rle_encode per image over its survivors and asynchronous copies into pinned staging; the files are
+                  written once the copies have completed, at later group boundaries and in flush().  Nothing waits in the loop.
+StoredProposals   answers the same three calls (and generate_device for HybridGLPipeline.step) from a store: the runs are
+                  parsed and packed on the loader threads (prefetch), one upload and one ops.rle_decode_group per group bring
+                  them back as pixels with their boxes.  It never runs SAM: a missing or inconsistent file is a ValueError."""
+import collections
+import json
+import os
+import threading
+
+import numpy as np
+import torch
+
+from . import ops
+
+RECORD_KEYS = ("segmentation", "area", "bbox", "predicted_iou", "point_coords", "stability_score", "crop_box")
+
+
+def generator_settings(gen, **extra):
+    """what meta.json records of a SamAutomaticMaskGenerator: grid, thresholds and NMS, crop layers, clean-up area and the
+    model's mask threshold; `extra`: what only the caller knows (SAM variant, precision, proposal_cap)"""
+    meta = {"points_per_side": [int(round(len(g) ** 0.5)) for g in gen.point_grids], "points_per_batch": int(gen.points_per_batch),
+            "pred_iou_thresh": float(gen.pred_iou_thresh), "stability_score_thresh": float(gen.stability_score_thresh),
+            "stability_score_offset": float(gen.stability_score_offset), "box_nms_thresh": float(gen.box_nms_thresh),
+            "crop_nms_thresh": float(gen.crop_nms_thresh), "crop_n_layers": int(gen.crop_n_layers),
+            "crop_overlap_ratio": float(gen.crop_overlap_ratio), "min_mask_region_area": int(gen.min_mask_region_area),
+            "mask_threshold": float(getattr(gen.model, "mask_threshold", 0.0))}
+    meta.update(extra)
+    return meta
+
+
+class ProposalStore:
+    """a directory of <image_id>.json record lists and one meta.json"""
+
+    def __init__(self, directory):
+        self.directory = os.fspath(directory)
+
+    def path(self, image_id):
+        return os.path.join(self.directory, f"{image_id}.json")
+
+    def _write(self, path, obj):
+        os.makedirs(self.directory, exist_ok=True)
+        tmp = f"{path}.tmp.{os.getpid()}.{threading.get_ident()}"
+        try:
+            with open(tmp, "w") as f:
+                json.dump(obj, f)
+            os.replace(tmp, path)      # the final name never holds a partial file
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+
+    def write(self, image_id, records):
+        self._write(self.path(image_id), list(records))
+
+    def write_meta(self, meta):
+        self._write(os.path.join(self.directory, "meta.json"), dict(meta))
+
+    def meta(self):
+        """the settings the writer recorded ({} for a store the upstream script produced)"""
+        path = os.path.join(self.directory, "meta.json")
+        if not os.path.exists(path):
+            return {}
+        with open(path) as f:
+            return json.load(f)
+
+    def has(self, image_id):
+        return os.path.exists(self.path(image_id))
+
+    def records(self, image_id):
+        """the stored list, as generate() returned it in coco_rle mode; ValueError naming the image for a missing or garbled file"""
+        path = self.path(image_id)
+        if not os.path.exists(path):
+            raise ValueError(f"proposal store {self.directory}: image {image_id} has no file ({os.path.basename(path)})")
+        try:
+            with open(path) as f:
+                recs = json.load(f)
+        except (json.JSONDecodeError, UnicodeDecodeError) as e:
+            raise ValueError(f"proposal store {self.directory}: image {image_id}: {os.path.basename(path)} is not valid JSON ({e})") from None
+        if not isinstance(recs, list):
+            raise ValueError(f"proposal store {self.directory}: image {image_id}: expected a list of records")
+        for k, r in enumerate(recs):
+            seg = r.get("segmentation") if isinstance(r, dict) else None
+            if (not isinstance(seg, dict) or not isinstance(seg.get("counts"), str) or not isinstance(seg.get("size"), list)
+                    or len(seg["size"]) != 2 or any(key not in r for key in RECORD_KEYS)
+                    or not isinstance(r["bbox"], list) or len(r["bbox"]) != 4):
+                raise ValueError(f"proposal store {self.directory}: image {image_id} entry {k}: not a coco_rle record "
+                                 f"(keys {sorted(RECORD_KEYS)}, segmentation {{size, counts string}})")
+        return recs
+
+
+def build_records(H, W, counts, areas, xywh, iou, stab, points, crop_boxes):
+    """the record list of one image from its survivors' host arrays, field for field what generate() builds in coco_rle mode"""
+    from .sam import coco_encode_rle
+    out = []
+    for i in range(len(counts)):
+        cb = crop_boxes[i]
+        out.append({"segmentation": coco_encode_rle({"size": [int(H), int(W)], "counts": counts[i]}), "area": int(areas[i]),
+                    "bbox": [int(v) for v in xywh[i]], "predicted_iou": float(iou[i]), "point_coords": [points[i].tolist()],
+                    "stability_score": float(stab[i]),
+                    "crop_box": [int(cb[0]), int(cb[1]), int(cb[2] - cb[0]), int(cb[3] - cb[1])]})   # XYWH
+    return out
+
+
+class _Recorded:
+    """a group on its way through a ProposalRecorder: the wrapped generator's state and the images' ids"""
+    __slots__ = ("inner", "ids", "overflow")
+
+
+class ProposalRecorder:
+    """A generator that writes what it hands out.  Every call goes to the wrapped generator unchanged -- the run's rows and
+    report are those of an unwrapped run -- and the survivors of every image with an id are encoded (ops.rle_encode: runs,
+    not pixels) and copied to pinned staging behind it.  A staging buffer is reused only after its copy's event; the files
+    are written when the events have completed: at later group boundaries, and in flush()."""
+    wants_image_ids = True
+
+    def __init__(self, generator, store, meta=None):
+        self.generator = generator
+        self.store = store if isinstance(store, ProposalStore) else ProposalStore(store)
+        self.recording = True       # False: calls pass through unrecorded (a rehearsal on images that are not the dataset's)
+        self.written = 0
+        self._pending = collections.deque()      # (image_id, H, W, n, sw, runs host, scalars host, event)
+        self._free = []                          # pinned buffers whose copies have completed
+        self._seen = set()
+        if meta is not None:
+            self.store.write_meta(meta)
+
+    def __getattr__(self, name):      # thresholds, crop_n_layers, model, ...: the wrapped generator's
+        if name == "generator":
+            raise AttributeError(name)
+        return getattr(self.generator, name)
+
+    # ---- the three calls of HybridGLPipeline.run
+    def group_begin(self, images, cap=None, encoded_event=None, image_ids=None):
+        st = _Recorded()
+        st.ids = list(image_ids) if image_ids is not None else [None] * len(images)
+        st.inner = self.generator.group_begin(images, cap, encoded_event)
+        st.overflow = 0
+        return st
+
+    def group_cleanup(self, st):
+        st.inner = self.generator.group_cleanup(st.inner)
+        st.overflow = st.inner.overflow
+        return st
+
+    def group_finish(self, st):
+        out = self.generator.group_finish(st.inner)
+        self._harvest()
+        for iid, p in zip(st.ids, out):
+            self._record(iid, p[0], p[1], p[2], p[3], p[4])
+        return out
+
+    # ---- the calls of HybridGLPipeline.step
+    def generate_device(self, image, resized=None, fixed_n=None, image_id=None):
+        out = self.generator.generate_device(image, resized=resized, fixed_n=fixed_n)
+        self._harvest()
+        self._record(image_id, *out[:5])
+        return out
+
+    def generate_device_crops(self, image, image_id=None):
+        gen = self.generator
+        st = gen._begin([image], None, None, 8)      # generate_device_crops, with the sources kept for the record
+        m, xywh, iou, stab, src = gen.group_finish(gen.group_cleanup(st))[0]
+        self._harvest()
+        self._record(image_id, m, xywh, iou, stab, src)
+        return (m, xywh, iou, stab) + gen._sources(src, *st.sizes[0])
+
+    # ---- staging
+    def _take(self, numel, dtype):
+        for i, b in enumerate(self._free):
+            if b.dtype == dtype and b.numel() >= numel:
+                return self._free.pop(i)
+        return torch.empty(max(int(numel), 1), dtype=dtype, pin_memory=True)
+
+    def _record(self, image_id, masks, xywh, iou, stab, src):
+        if not self.recording:
+            return
+        if image_id is None:
+            raise ValueError("ProposalRecorder: an item without an image_id cannot be stored")
+        if image_id in self._seen:      # the image came back after the loop's image cache had dropped it: the same proposals
+            return
+        self._seen.add(image_id)
+        n, H, W = (int(v) for v in masks.shape)
+        if n == 0:
+            self._pending.append((image_id, H, W, 0, 0, None, None, None))
+            return
+        sw = ops.rle_slot_words(H, W)
+        flat = torch.empty(n * (4 + sw), dtype=torch.int32, device=masks.device)
+        ops.rle_encode(masks if masks.is_contiguous() else masks.contiguous(), None, sw, out=flat)
+        runs = self._take(flat.numel(), torch.int32)
+        runs[:flat.numel()].copy_(flat, non_blocking=True)
+        # the few scalars per proposal ride along: rows iou, stability, source, x, y, w, h (all exact in float64)
+        sc = torch.cat([iou.double()[None], stab.double()[None], src.double()[None], xywh.double().t()])
+        scal = self._take(7 * n, torch.float64)
+        scal[:7 * n].copy_(sc.reshape(-1), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._pending.append((image_id, H, W, n, sw, runs, scal, ev))
+
+    def _harvest(self, wait=False):
+        """write the files of the copies that have completed (wait=True: of all), oldest first; their buffers return to the pool"""
+        from .sam import rle_from_slot
+        while self._pending:
+            image_id, H, W, n, sw, runs, scal, ev = self._pending[0]
+            if ev is not None:
+                if wait:
+                    ev.synchronize()
+                elif not ev.query():
+                    break
+            self._pending.popleft()
+            if n == 0:
+                self.store.write(image_id, [])
+            else:
+                slots, table = ops.rle_split(runs.numpy(), n, sw)
+                counts = [rle_from_slot(slots[e], int(table[e, 0]), int(table[e, 1]), H, W) for e in range(n)]
+                s = scal.numpy()[:7 * n].reshape(7, n)
+                pts, cbs = self.generator._sources(torch.from_numpy(s[2].astype(np.int64)), H, W)
+                self.store.write(image_id, build_records(H, W, counts, table[:, 2], s[3:7].T.astype(np.int64), s[0].astype(np.float32),
+                                                         s[1].astype(np.float32), pts, cbs))
+                self._free += [runs, scal]
+            self.written += 1
+
+    def forget(self):
+        """record every image again when it next comes by (a second pass over the same images rewrites their files)"""
+        self._seen.clear()
+
+    def flush(self):
+        """wait for the copies still in flight and write their files; returns the number of images written so far"""
+        self._harvest(wait=True)
+        return self.written
+
+
+class _Rows:
+    """the proposals of one stored image, packed on a loader thread: ONE pinned int32 buffer = table [n,4] | slots [n,sw] |
+    the bits of predicted_iou [n] | of stability_score [n], and the stored boxes for the check"""
+    __slots__ = ("n", "H", "W", "sw", "buf", "bbox")
+
+
+class _Stored:
+    __slots__ = ("ids", "sizes", "counts", "first", "rows", "masks", "boxes", "iou", "stab", "host", "ev", "overflow")
+
+
+class StoredProposals:
+    """The mask generator's place in HybridGLPipeline taken by a ProposalStore.  No SAM model, no checkpoint.
+
+    prefetch(image_id, size) is the host half -- file, JSON, sam.rle_counts_from_string, packing into one pinned buffer -- and
+    belongs on the loader threads (RealRefs.load / RealPhraseCut.load call it); an image nobody prefetched is read where it
+    is first asked for.  Per group the loop's thread concatenates the staged rows, issues one upload and one
+    ops.rle_decode_group, and reads status and boxes back once, in group_cleanup.  cap: the first `cap` entries of an image."""
+    wants_image_ids = True
+    crop_n_layers = 0      # HybridGLPipeline.step: one generate_device call, whatever produced the store
+
+    def __init__(self, store, device, cap=None, keep=256):
+        self.store = store if isinstance(store, ProposalStore) else ProposalStore(store)
+        self.device = torch.device(device)
+        self.cap = cap
+        self.keep = int(keep)
+        self._rows = collections.OrderedDict()      # image id -> _Rows, the last `keep` images
+        self._lock = threading.Lock()
+        self._free = collections.deque()            # (pinned buffer, the event behind its upload)
+        self._back = []                             # pinned read-back buffers group_cleanup has finished with
+        self.loaded = 0                             # images parsed (<= images asked for)
+
+    def records(self, image_id):
+        return self.store.records(image_id)
+
+    def settings(self):
+        return self.store.meta()
+
+    # ---- host half (loader threads)
+    def prefetch(self, image_id, size=None):
+        """parse and pack image `image_id` unless it is staged already; size (H, W): the image's, checked against every record"""
+        if image_id is None:
+            raise ValueError("StoredProposals: an item without an image_id has no stored proposals")
+        with self._lock:
+            rows = self._rows.get(image_id)
+            if rows is not None:
+                self._rows.move_to_end(image_id)
+        if rows is None:
+            rows = self._load(image_id, size)
+            with self._lock:
+                self._rows[image_id] = rows
+                self.loaded += 1
+                while len(self._rows) > self.keep:
+                    self._rows.popitem(last=False)
+        if size is not None and rows.n and (rows.H, rows.W) != tuple(int(v) for v in size):
+            raise ValueError(f"proposal store {self.store.directory}: image {image_id} entry 0: size {[rows.H, rows.W]} differs "
+                             f"from the image's {[int(v) for v in size]}")
+        return rows
+
+    def _load(self, image_id, size):
+        from .sam import rle_counts_from_string
+        recs = self.store.records(image_id)
+        rows = _Rows()
+        rows.n = len(recs)
+        rows.H, rows.W = (int(v) for v in (size if size is not None else (recs[0]["segmentation"]["size"] if recs else (0, 0))))
+        counts = []
+        for k, r in enumerate(recs):
+            if [int(v) for v in r["segmentation"]["size"]] != [rows.H, rows.W]:
+                raise ValueError(f"proposal store {self.store.directory}: image {image_id} entry {k}: size "
+                                 f"{r['segmentation']['size']} differs from the image's {[rows.H, rows.W]}")
+            try:
+                counts.append(rle_counts_from_string(r["segmentation"]["counts"]))
+            except Exception as e:
+                raise ValueError(f"proposal store {self.store.directory}: image {image_id} entry {k}: bad counts string ({e})") from None
+        n = rows.n
+        rows.sw = max([len(c) for c in counts] + [1])
+        rows.buf = torch.zeros(n * (6 + rows.sw), dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        h = rows.buf.numpy()
+        slots, table = ops.rle_split(h, n, rows.sw)
+        for k, c in enumerate(counts):
+            table[k, 0] = len(c)
+            slots[k, :len(c)] = np.asarray(c, dtype=np.uint32).view(np.int32)
+        tail = h[n * (4 + rows.sw):].view(np.float32)
+        tail[:n] = [r["predicted_iou"] for r in recs]
+        tail[n:] = [r["stability_score"] for r in recs]
+        rows.bbox = np.asarray([r["bbox"] for r in recs], dtype=np.int64).reshape(n, 4)
+        return rows
+
+    # ---- device half (the loop's thread)
+    def _staging(self, numel):
+        """a pinned buffer whose last upload has completed, or a new one"""
+        for _ in range(len(self._free)):
+            buf, ev = self._free.popleft()
+            if buf.numel() >= numel and ev.query():
+                return buf
+            self._free.append((buf, ev))
+        return torch.empty(max(int(numel), 1), dtype=torch.int32, pin_memory=True)
+
+    def group_begin(self, images, cap=None, encoded_event=None, image_ids=None):
+        if image_ids is None or len(image_ids) != len(images):
+            raise ValueError("StoredProposals: the image ids of the group are needed (RefBatch.image_id)")
+        st = _Stored()
+        st.overflow = 0
+        st.ids = list(image_ids)
+        st.sizes = [tuple(int(v) for v in im.shape[:2]) for im in images]
+        st.rows = [self.prefetch(iid, size) for iid, size in zip(st.ids, st.sizes)]
+        caps = [c for c in (cap, self.cap) if c]
+        st.counts = [min([r.n] + caps) for r in st.rows]
+        st.first = np.cumsum([0] + st.counts)
+        S = int(st.first[-1])
+        if encoded_event is not None:      # there is no encoder pass to wait for
+            encoded_event.record(torch.cuda.current_stream(self.device))
+        st.ev = None
+        if S == 0:
+            return st
+        sw = max(r.sw for r, n in zip(st.rows, st.counts) if n)
+        numel = S * (6 + sw)
+        host = self._staging(numel)
+        h = host.numpy()[:numel]
+        slots, table = ops.rle_split(h, S, sw)
+        tail = h[S * (4 + sw):]
+        for r, n, e in zip(st.rows, st.counts, st.first):
+            if n == 0:
+                continue
+            rs, rt = ops.rle_split(r.buf.numpy(), r.n, r.sw)
+            table[e:e + n] = rt[:n]
+            slots[e:e + n, :r.sw] = rs[:n]      # words beyond an entry's n_counts are never read
+            rtail = r.buf.numpy()[r.n * (4 + r.sw):]
+            tail[e:e + n] = rtail[:n]
+            tail[S + e:S + e + n] = rtail[r.n:r.n + n]
+        dev = torch.empty(numel, dtype=torch.int32, device=self.device)
+        dev.copy_(host[:numel], non_blocking=True)
+        up = torch.cuda.Event()
+        up.record()
+        self._free.append((host, up))
+        dslots, dtable = ops.rle_split(dev, S, sw)
+        st.iou = dev[S * (4 + sw):S * (5 + sw)].view(torch.float32)
+        st.stab = dev[S * (5 + sw):].view(torch.float32)
+        # boxes and status share one buffer and leave in one copy into pooled pinned memory; group_cleanup reads it, where
+        # SAM reads its first counts, and hands the buffer back
+        aux = torch.empty((2, S, 4), dtype=torch.int32, device=self.device)
+        st.masks, st.boxes = self._decode(dslots, dtable, st.sizes, st.counts, aux)[:2]
+        fits = self._back and self._back[-1].numel() >= 8 * S
+        st.host = self._back.pop() if fits else torch.empty(max(8 * S, 4096), dtype=torch.int32, pin_memory=True)
+        st.host[:8 * S].copy_(aux.view(-1), non_blocking=True)
+        st.ev = torch.cuda.Event()
+        st.ev.record()
+        return st
+
+    def _decode(self, slots, table, sizes, counts, aux):
+        """the group's pixels, boxes (aux[0]) and status (aux[1]): two launches whatever the group holds"""
+        return ops.rle_decode_group(slots, table, sizes, counts, aux=aux)
+
+    def group_cleanup(self, st):
+        if st.ev is None:
+            return st
+        st.ev.synchronize()
+        S = int(st.first[-1])
+        boxes, status = st.host.numpy()[:8 * S].reshape(2, S, 4).copy()
+        self._back.append(st.host)
+        st.host = None
+        for g, (iid, r, n, e) in enumerate(zip(st.ids, st.rows, st.counts, st.first)):
+            for k in range(n):
+                code = int(status[e + k, 0])
+                if code != 0:
+                    raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {k}: its counts do not decode to a "
+                                     f"{r.H} x {r.W} mask (status {code})")
+                x0, y0, x1, y1 = (int(v) for v in boxes[e + k])
+                # (an empty mask has no box: the reference stores its zero box moved by the crop's origin, whatever that is)
+                if int(status[e + k, 1]) > 0 and [x0, y0, x1 - x0, y1 - y0] != r.bbox[k].tolist():
+                    raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {k}: the stored bbox "
+                                     f"{r.bbox[k].tolist()} is not the box of its mask {[x0, y0, x1 - x0, y1 - y0]}")
+        return st
+
+    def group_finish(self, st):
+        """per image (masks u8 [n,H,W], boxes_xywh int64 [n,4], iou [n], stability [n], None)"""
+        from .sam import _xywh
+        out = []
+        for g, ((H, W), n, e) in enumerate(zip(st.sizes, st.counts, st.first)):
+            if n == 0:
+                f32 = torch.empty((0,), dtype=torch.float32, device=self.device)
+                out.append((torch.empty((0, H, W), dtype=torch.uint8, device=self.device),
+                            torch.empty((0, 4), dtype=torch.int64, device=self.device), f32, f32, None))
+                continue
+            out.append((st.masks[g], _xywh(st.boxes[e:e + n]), st.iou[e:e + n], st.stab[e:e + n], None))
+        return out
+
+    def generate_group(self, images, image_ids, cap=None):
+        return self.group_finish(self.group_cleanup(self.group_begin(images, cap, None, image_ids)))
+
+    def generate_device(self, image, resized=None, fixed_n=None, image_id=None):
+        """HybridGLPipeline.step: the image's proposals as a group of one"""
+        if fixed_n is not None:
+            raise ValueError("StoredProposals: fixed_n is the synthetic benchmark's switch; a store hands out what it holds")
+        return self.generate_group([image], [image_id])[0]

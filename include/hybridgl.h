@@ -723,6 +723,25 @@ int hgl_rle_from_string(const char* s, uint32_t* counts, long long cap, long lon
 size_t hgl_rle_decode_workspace_bytes(int S, int H, int W, long long slot_words);
 int hgl_rle_decode_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S, int H, int W,
                           uint8_t* masks, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+/* A whole group's stored proposals in one call (csrc/rle.hip): hgl_rle_decode_device for S entries that belong to G <= 64
+ * images of their own sizes, with every mask's box -- what loading the per-image record lists of scripts/amg.py:229-232
+ * (generate() in coco_rle mode, automatic_mask_generator.py:176-182) needs in place of rle_to_mask (utils/amg.py:138-149)
+ * per record and batched_mask_to_box (utils/amg.py:303-346) per image.  Two launches whatever G and the sizes are.
+ * Asynchronous on `stream`; no host synchronisation, allocation or atomics; two calls give the same bytes.
+ * slots / table: as hgl_rle_decode_device (forms 0 and 1).  images_host: HOST [G,4] int64, row g = (H_g, W_g, first entry
+ * e_g, byte offset o_g into masks); image g owns the entries e_g .. e_(g+1)-1 (e_0 = 0, e_G = S, non-decreasing; an image may
+ * own none) and entry s of it is written at o_g + (s - e_g)*H_g*W_g.  The extents must lie inside [0, masks_bytes) and must
+ * not overlap, n_g*H_g*W_g < 2^31; anything else is HGL_EINVAL and nothing is enqueued.  The array is read before the call
+ * returns.  Every byte of every extent is written 0 / 1, none outside; an image whose W is a multiple of 4 and whose base
+ * address is 4-byte aligned takes the 4-column store path, any other the byte path.
+ * status: device [S,4] = (code, area, 0, 0) as hgl_rle_decode_device, against the entry's own H_g*W_g.
+ * boxes_xyxy: device [S,4] int32, the hgl_mask_boxes rule for the mask this call writes (inclusive XYXY, zeros for an empty
+ * mask and for code 2), derived from the runs / the plane words, not from the pixels.
+ * ws: hgl_rle_decode_group_workspace_bytes(S, slot_words) (HGL_EWORKSPACE when smaller). */
+size_t hgl_rle_decode_group_workspace_bytes(int S, long long slot_words);
+int hgl_rle_decode_group_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S,
+                                const int64_t* images_host, int G, uint8_t* masks, long long masks_bytes,
+                                int32_t* boxes_xyxy, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 size_t hgl_rle_iou_workspace_bytes(int S, int H, int W, long long slot_words_a, long long slot_words_b);
 int hgl_rle_iou_device(const uint32_t* slots_a, long long slot_words_a, const int32_t* table_a,
                        const uint32_t* slots_b, long long slot_words_b, const int32_t* table_b,

@@ -1,0 +1,218 @@
+"""CPU: the entries of the grouped RLE decoder (declared, bound, refusing without a device) and the proposal store on the
+host -- records built from the reference's generate() golden written, read back and packed for the device, [] images,
+meta.json, files that are missing, truncated or garbled, the atomic write, and the driver's flag rules."""
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+from hybridgl_amd import _lib
+from hybridgl_amd import proposals as P
+from hybridgl_amd import sam as hsam
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ["hgl_rle_decode_group_workspace_bytes", "hgl_rle_decode_group_device"]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load()
+
+
+def test_header_declares_and_binding_binds_the_new_entries(lib):
+    text = open(os.path.join(ROOT, "include", "hybridgl.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for name in NEW:
+        assert re.search(r"\b" + name + r"\s*\(", code), name
+        assert name in _lib.PROTOTYPES and hasattr(lib, name), name
+    assert re.search(r"#define\s+HGL_ABI_VERSION\s+7\b", text)
+    assert lib.hgl_abi_version() == _lib.ABI_VERSION == 7
+    # the export cites the reference lines it replaces, as every export does
+    doc = text[:text.index("size_t hgl_rle_decode_group_workspace_bytes")].rsplit("/*", 1)[1]
+    assert "scripts/amg.py:229-232" in doc and "utils/amg.py:303-346" in doc
+
+
+def test_group_entry_refuses_without_a_device(lib):
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is visible")
+    images = np.array([[4, 4, 0, 0]], np.int64)
+    assert lib.hgl_rle_decode_group_device(None, 4, None, 1, images.ctypes.data, 1, None, 16, None, None, None, 0, None) == -2
+    assert b"no HIP device" in lib.hgl_last_error()
+
+
+def test_group_workspace_query_is_host_arithmetic(lib):
+    # the run starts: slot_words + 1 words per entry, whatever the images' sizes are
+    assert lib.hgl_rle_decode_group_workspace_bytes(2, 10) >= 2 * 11 * 4
+    assert lib.hgl_rle_decode_group_workspace_bytes(2, 10) == lib.hgl_rle_decode_workspace_bytes(2, 65, 3, 10)
+    assert lib.hgl_rle_decode_group_workspace_bytes(1024, 12800) >= 1024 * 12801 * 4
+    assert lib.hgl_rle_decode_group_workspace_bytes(0, 4) == 0 and lib.hgl_rle_decode_group_workspace_bytes(3, -1) == 0
+
+
+def same(a, b):
+    """equal record lists; the stability of an empty mask is 0 / 0 = NaN on both sides, which == does not see as equal"""
+    return json.dumps(a) == json.dumps(b)
+
+
+@pytest.fixture(scope="module")
+def golden_records(golden_dir):
+    """records in coco_rle mode from the reference's generate() with crop layers (oracle/gen_golden.py, sam_crops.npz 'a_'):
+    every third of its 192 survivors, 240 x 320 (the fixture keeps the masks as packed bits)"""
+    z = np.load(os.path.join(golden_dir, "sam_crops.npz"))
+    sel = range(0, len(z["a_masks"]), 3)
+    masks = np.unpackbits(z["a_masks"][list(sel)], axis=-1)[..., :320]
+    recs = []
+    for i, m in zip(sel, masks):
+        assert int(m.sum()) == int(z["a_area"][i])
+        ys, xs = np.nonzero(m)      # the reference's bbox is the box of its mask: what StoredProposals holds a store to
+        assert z["a_bbox"][i].tolist() == ([0, 0, 0, 0] if not len(ys) else [xs.min(), ys.min(), xs.max() - xs.min(), ys.max() - ys.min()])
+        rle = hsam.coco_encode_rle(hsam.mask_to_rle(m))
+        recs.append({"segmentation": rle, "area": int(z["a_area"][i]), "bbox": [int(v) for v in z["a_bbox"][i]],
+                     "predicted_iou": float(z["a_iou"][i]), "point_coords": [z["a_points"][i].tolist()],
+                     "stability_score": float(z["a_stab"][i]), "crop_box": [int(v) for v in z["a_crop_box"][i]]})
+    return recs, masks
+
+
+def test_store_round_trip(tmp_path, golden_records):
+    recs, masks = golden_records
+    store = P.ProposalStore(tmp_path / "store")
+    store.write(581921, recs)
+    store.write(7, [])
+    meta = {"points_per_side": [8, 4], "pred_iou_thresh": 0.7, "crop_n_layers": 1, "sam_model": "tiny", "precision": "f16x3",
+            "proposal_cap": 0, "mask_threshold": 0.0, "min_mask_region_area": 800}
+    store.write_meta(meta)
+    assert sorted(os.listdir(store.directory)) == ["581921.json", "7.json", "meta.json"]      # no temporary file stays
+    again = P.ProposalStore(str(tmp_path / "store"))
+    got = again.records(581921)
+    assert same(got, recs) and any(r["stability_score"] != r["stability_score"] for r in got) and [type(v) for v in got[0].values()] == [type(v) for v in recs[0].values()]
+    assert list(got[0]) == list(P.RECORD_KEYS)
+    assert again.records(7) == [] and again.meta() == meta and again.has(7) and not again.has(8)
+    assert P.ProposalStore(tmp_path / "nowhere").meta() == {}
+    # the file is what anything that reads SAM's output reads: a JSON list whose strings decode to the masks
+    raw = json.load(open(store.path(581921)))
+    for r, m in zip(raw, masks):
+        assert r["segmentation"]["size"] == [240, 320] and np.array_equal(hsam.rle_to_mask(
+            {"size": [240, 320], "counts": hsam.rle_counts_from_string(r["segmentation"]["counts"]).tolist()}), m != 0)
+        assert r["area"] == int(m.sum())
+
+
+def test_bad_files_raise_and_name_the_image(tmp_path, golden_records):
+    recs, _ = golden_records
+    store = P.ProposalStore(tmp_path)
+    with pytest.raises(ValueError, match="image 12 has no file"):
+        store.records(12)
+    store.write(12, recs[:3])
+    text = open(store.path(12)).read()
+    open(store.path(12), "w").write(text[:len(text) // 2])      # truncated
+    with pytest.raises(ValueError, match="image 12"):
+        store.records(12)
+    open(store.path(12), "wb").write(b"\xff\xfe garbage {")      # garbled
+    with pytest.raises(ValueError, match="image 12"):
+        store.records(12)
+    open(store.path(12), "w").write(json.dumps({"not": "a list"}))
+    with pytest.raises(ValueError, match="image 12"):
+        store.records(12)
+    bad = [dict(recs[0]), {k: v for k, v in recs[1].items() if k != "bbox"}]
+    open(store.path(12), "w").write(json.dumps(bad))
+    with pytest.raises(ValueError, match="image 12 entry 1"):
+        store.records(12)
+    bad = [dict(recs[0], segmentation={"size": [240, 320], "counts": [1, 2, 3]})]      # uncompressed counts: another format
+    open(store.path(12), "w").write(json.dumps(bad))
+    with pytest.raises(ValueError, match="image 12 entry 0"):
+        store.records(12)
+
+
+def test_the_write_is_atomic(tmp_path, golden_records, monkeypatch):
+    """a write that fails half way leaves no file under the final name (a first write) or the previous file (a rewrite), and
+    no temporary file"""
+    recs, _ = golden_records
+    store = P.ProposalStore(tmp_path)
+    real = json.dump
+
+    def half(obj, f, **kw):
+        f.write(json.dumps(obj)[:40])
+        f.flush()
+        raise OSError("disk full")
+
+    monkeypatch.setattr(P.json, "dump", half)
+    with pytest.raises(OSError):
+        store.write(5, recs)
+    assert os.listdir(tmp_path) == []
+    monkeypatch.setattr(P.json, "dump", real)
+    store.write(5, recs[:2])
+    monkeypatch.setattr(P.json, "dump", half)
+    with pytest.raises(OSError):
+        store.write(5, recs)
+    monkeypatch.setattr(P.json, "dump", real)
+    assert os.listdir(tmp_path) == ["5.json"] and same(store.records(5), recs[:2])
+
+
+def test_prefetch_packs_one_buffer_per_image(tmp_path, golden_records):
+    """the host half of StoredProposals: table, counts and the two scores of an image in ONE int32 buffer"""
+    from hybridgl_amd import ops
+    recs, masks = golden_records
+    store = P.ProposalStore(tmp_path)
+    store.write(3, recs)
+    store.write(4, [])
+    sp = P.StoredProposals(store, "cpu")
+    rows = sp.prefetch(3, (240, 320))
+    counts = [hsam.mask_to_rle(m)["counts"] for m in masks]
+    n, sw = len(recs), max(len(c) for c in counts)
+    assert (rows.n, rows.H, rows.W, rows.sw) == (n, 240, 320, sw) and rows.buf.numel() == n * (6 + sw)
+    slots, table = ops.rle_split(rows.buf.numpy(), n, sw)
+    assert table[:, 0].tolist() == [len(c) for c in counts] and not table[:, 1:].any()
+    for k, c in enumerate(counts):
+        assert slots[k, :len(c)].view(np.uint32).tolist() == c
+    tail = rows.buf.numpy()[n * (4 + sw):].view(np.float32)
+    assert np.array_equal(tail[:n], np.array([r["predicted_iou"] for r in recs], np.float32))
+    assert np.array_equal(tail[n:], np.array([r["stability_score"] for r in recs], np.float32), equal_nan=True)
+    assert rows.bbox.tolist() == [r["bbox"] for r in recs]
+    assert sp.prefetch(3, (240, 320)) is rows and sp.loaded == 1      # staged once
+    empty = sp.prefetch(4, (17, 9))
+    assert empty.n == 0 and empty.buf.numel() == 0
+    assert same(sp.records(3), recs)
+    # errors name the image and the entry; nothing falls back to running SAM (there is no model to run)
+    with pytest.raises(ValueError, match="image 9 has no file"):
+        sp.prefetch(9, (240, 320))
+    with pytest.raises(ValueError, match="image 3 entry 0: size"):
+        P.StoredProposals(store, "cpu").prefetch(3, (240, 321))
+    with pytest.raises(ValueError, match="image_id"):
+        sp.prefetch(None, (240, 320))
+    bad = [dict(r) for r in recs[:4]]
+    bad[2] = dict(bad[2], segmentation={"size": [240, 320], "counts": bad[2]["segmentation"]["counts"] + "o"})      # cut off in a group
+    store.write(6, bad)
+    with pytest.raises(ValueError, match="image 6 entry 2"):
+        sp.prefetch(6, (240, 320))
+    bad[2] = dict(recs[2], segmentation={"size": [320, 240], "counts": recs[2]["segmentation"]["counts"]})
+    store.write(6, bad)
+    with pytest.raises(ValueError, match="image 6 entry 2: size"):
+        sp.prefetch(6, (240, 320))
+
+
+def test_generator_settings_and_the_flag_rules():
+    from hybridgl_amd import main as drv
+
+    class Model:
+        mask_threshold = 0.25
+
+    class Gen:
+        point_grids = [np.zeros((64, 2)), np.zeros((16, 2))]
+        points_per_batch, pred_iou_thresh, stability_score_thresh, stability_score_offset = 64, 0.7, 0.7, 1.0
+        box_nms_thresh, crop_nms_thresh, crop_n_layers, crop_overlap_ratio, min_mask_region_area = 0.7, 0.7, 1, 512 / 1500, 800
+        model = Model()
+
+    meta = P.generator_settings(Gen(), sam_model="default", precision="f16x3", proposal_cap=64)
+    for key in ("points_per_side", "pred_iou_thresh", "stability_score_thresh", "box_nms_thresh", "crop_nms_thresh", "crop_n_layers",
+                "min_mask_region_area", "mask_threshold", "sam_model", "precision", "proposal_cap"):
+        assert key in meta, key
+    assert meta["points_per_side"] == [8, 4] and meta["mask_threshold"] == 0.25 and json.loads(json.dumps(meta)) == meta
+    parse = drv.default_argument_parser().parse_args
+    for flags in (["--real", "--save_proposals", "a", "--proposals_dir", "b"], ["--save_proposals", "a"], ["--proposals_dir", "b"],
+                  ["--real", "--proposals_dir", "b", "--prepare"]):
+        with pytest.raises(SystemExit):
+            drv.check_proposal_flags(parse(flags))
+    for flags in (["--real", "--save_proposals", "a", "--save_masks", "m", "--sweep", "r=0.3,0.5"], ["--real", "--proposals_dir", "b"],
+                  ["--real"], []):
+        drv.check_proposal_flags(parse(flags))
