@@ -24,7 +24,7 @@
 // plane (bit p % 32 of word p / 32; whenever the counts do not fit but ceil(H*W/32) words do), 2 = neither fits, nothing
 // written, 3 = the index is outside [0, N), nothing read or written.  Words beyond what the form defines keep their bytes.
 #include "hgl_common.h"
-#include "rle_group.h"      // RleGroup, rle_group_plan: plain C++, shared with the sanitizer harness
+#include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan: plain C++, shared with the sanitizer harness
 
 namespace {
 
@@ -197,19 +197,26 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned lo
   if (t == 0) slot[trans] = HW - last_base;
 }
 
-// ---- the way back: slots + table -> masks (hgl_rle_decode_device) and intersection / union of two encoded sets
-// (hgl_rle_iou_device).  The mirror image of the launches above:
+// ---- the way back: slots + table -> masks (hgl_rle_decode_device, hgl_rle_decode_group_device) and intersection / union of two
+// encoded sets (hgl_rle_iou_device).  ONE decoder: the S entries of a call belong to G <= 64 images of their own sizes, and a
+// single-size set is a group of one.  The geometry rides in the kernel arguments, by value (no descriptor memory, nothing to keep
+// alive), in one of two shapes the kernels are compiled for: RleGroup, in which a block finds its image by a search of <= 6
+// steps over <= 64 rows of the arguments, uniform over the block; RleOne (a call of one image that starts at `masks`): H and W,
+// no search, nothing else to load.  The mirror image of the launches above, two per decode call whatever G is:
 //
-//   A. rle_starts_kernel   one workgroup per entry decides what the slot holds (the status code) and, for form 0, sum-scans
+//   A. rle_starts_kernel<BOX>   one workgroup per entry decides what the slot holds (the status code) and, for form 0, sum-scans
 //      the counts 256 at a time with a 64-bit carry into run starts E_k (E_0 = 0, saturated at H*W, so a count of 0xFFFFFFFF
 //      cannot wrap).  The area is the clipped length of the odd runs (form 0) or the pop-count of the plane's valid bits (form 1).
+//      BOX: the mask's box is read off the same runs / plane words (the group entry); without it no box is kept and none written.
 //   B. rle_plane_word      any 64-bit column word -- rows 64j .. 64j+63 of column x, the encoder's own layout -- from its
 //      entry alone.  Form 0: an upper-bound search in E finds the last run that starts at or before the word's first pixel,
 //      then the runs that touch the word are walked: no atomics, no scatter, O(words * log n + n) over an entry.  Form 1: the
 //      32-bit run-order words are re-packed (the inverse of the encoder's form-1 branch).  An entry of code 2 gives 0.
-//   C. rle_rows_kernel     the inverse of rle_columns_kernel: lane x forms the column word(s) of its 64 rows with B and every
-//      row is one coalesced store across the lanes (1 or 4 bytes per lane).  Every byte of every entry is written exactly once;
-//      the decoder keeps no plane anywhere.
+//   C. rle_rows_kernel<V>  the inverse of rle_columns_kernel: (image, entry, tile) of a block from the host's tile prefix sums;
+//      lane x forms the column word(s) of its 64 rows with B and every row is one coalesced store across the lanes (rle_rows_tile:
+//      1 or 4 bytes per lane).  V = 4 / 1: every image of the call takes that store path (a single image always does);
+//      V = 0: each image its own, a branch uniform over the block.  Every byte of every entry is written exactly once; the
+//      decoder keeps no plane anywhere.
 //   D. rle_plane_kernel / rle_iou_kernel   for the IoU the words of both sets go to the workspace, one thread per word, and one
 //      workgroup per entry pop-counts a & b and a | b: padding bits are 0 on both sides, no mask is expanded to bytes.
 
@@ -219,69 +226,6 @@ __device__ __forceinline__ bool rle_entry_usable(int n, int form, long long slot
   if (form == 0) return (long long)n <= slot_words;
   if (form == 1) return (long long)plane_words <= slot_words;      // a plane that the slot cannot hold is never read
   return false;
-}
-
-__global__ __launch_bounds__(RLE_THREADS) void rle_starts_kernel(const uint32_t* __restrict__ slots, long long slot_words,
-                                                                 const int32_t* __restrict__ table, int H, int W,
-                                                                 uint32_t* __restrict__ E, long long e_stride,
-                                                                 int32_t* __restrict__ status) {
-  __shared__ unsigned red[4];
-  __shared__ unsigned long long wtot[4];
-  const int s = blockIdx.x, t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
-  const int n = table[(size_t)s * 4], form = table[(size_t)s * 4 + 1];
-  const unsigned HW = (unsigned)H * (unsigned)W;      // < 2^31 (checked by the host entry)
-  const unsigned plane_words = (HW + 31u) / 32u;
-  int32_t* row = status + (size_t)s * 4;
-  if (!rle_entry_usable(n, form, slot_words, plane_words)) {      // uniform over the workgroup
-    if (t == 0) { row[0] = 2; row[1] = 0; row[2] = 0; row[3] = 0; }
-    return;
-  }
-  const uint32_t* slot = slots + (size_t)s * (size_t)slot_words;
-  unsigned area = 0;
-  int code = 0;
-  if (form == 1) {
-    const unsigned tail = HW - 32u * (plane_words - 1u);      // 1 .. 32 valid bits in the last word
-    for (unsigned w = t; w < plane_words; w += RLE_THREADS) {
-      uint32_t v = slot[w];
-      if (w == plane_words - 1u && tail < 32u) v &= (1u << tail) - 1u;
-      area += __popc(v);
-    }
-  } else {
-    uint32_t* Es = E + (size_t)s * (size_t)e_stride;      // n + 1 <= slot_words + 1 <= e_stride entries
-    // E[k] = min(H*W, counts[0] + .. + counts[k-1]); the sums are exact in 64 bits (n < 2^31 counts < 2^32)
-    unsigned long long carry = 0;
-    if (t == 0) Es[0] = 0;
-    for (unsigned base = 0; base < (unsigned)n; base += RLE_THREADS) {
-      const unsigned i = base + t;
-      const unsigned long long own = i < (unsigned)n ? (unsigned long long)slot[i] : 0ull;
-      unsigned long long v = own;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long a = __shfl_up(v, d, 64);
-        if (lane >= d) v += a;
-      }
-      __syncthreads();      // the previous chunk's reads of wtot are over
-      if (lane == 63) wtot[wave] = v;
-      __syncthreads();
-      unsigned long long sum = carry + v, tot = 0;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        if (w < wave) sum += wtot[w];
-        tot += wtot[w];
-      }
-      if (i < (unsigned)n) {
-        const unsigned end = sum < (unsigned long long)HW ? (unsigned)sum : HW;
-        const unsigned start = sum - own < (unsigned long long)HW ? (unsigned)(sum - own) : HW;
-        Es[i + 1] = end;
-        if (i & 1u) area += end - start;
-      }
-      carry += tot;
-    }
-    code = carry == (unsigned long long)HW ? 0 : 1;
-  }
-  area = rle_block_sum(area, red);
-  if (t == 0) { row[0] = code; row[1] = (int32_t)area; row[2] = 0; row[3] = 0; }
 }
 
 // rows 64j .. 64j+63 of column x of an entry that holds a mask (bits beyond H are 0); Es: the entry's run starts (form 0)
@@ -323,53 +267,6 @@ __device__ __forceinline__ unsigned long long rle_plane_word(const uint32_t* __r
   return c;
 }
 
-// V columns per lane (4: one aligned 32-bit store per row when W % 4 == 0), 64 rows per wave, 4 waves = 4 row tiles per block
-template <int V>
-__global__ __launch_bounds__(RLE_THREADS) void rle_rows_kernel(const uint32_t* __restrict__ slots, long long slot_words,
-                                                               const int32_t* __restrict__ table, const uint32_t* __restrict__ E,
-                                                               long long e_stride, const int32_t* __restrict__ status, int H,
-                                                               int W, int HW64, int col_tiles, int row_tiles,
-                                                               uint8_t* __restrict__ masks) {
-  const unsigned tile = blockIdx.x;
-  const int s = (int)(tile / (unsigned)(col_tiles * row_tiles));
-  const int rem = (int)(tile % (unsigned)(col_tiles * row_tiles));
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int j = (rem / col_tiles) * 4 + wave;
-  const int x = ((rem % col_tiles) * 64 + lane) * V;
-  if (j >= HW64 || x >= W) return;      // no barrier and no cross-lane operation below
-  const int y0 = j * 64;
-  const int rows = H - y0 < 64 ? H - y0 : 64;
-  unsigned long long c[V];
-#pragma unroll
-  for (int k = 0; k < V; ++k) c[k] = 0;
-  if (status[(size_t)s * 4] != 2) {
-    const int n = table[(size_t)s * 4], form = table[(size_t)s * 4 + 1];
-    const unsigned plane_words = ((unsigned)H * (unsigned)W + 31u) / 32u;
-#pragma unroll
-    for (int k = 0; k < V; ++k)      // x + k < W: W % 4 == 0 on the 4-column path
-      c[k] = rle_plane_word(slots + (size_t)s * (size_t)slot_words, form, n, E + (size_t)s * (size_t)e_stride, plane_words, H, x + k, j);
-  }
-  uint8_t* dst = masks + (size_t)s * H * W + (size_t)y0 * W + x;      // (y0 + r) * W + x (+ 3) < H * W
-#pragma unroll 8
-  for (int r = 0; r < rows; ++r) {
-    if (V == 4) {
-      uint32_t v = 0;
-#pragma unroll
-      for (int k = 0; k < V; ++k) v |= (uint32_t)((c[k] >> r) & 1ull) << (8 * k);
-      *reinterpret_cast<uint32_t*>(dst + (size_t)r * W) = v;
-    } else {
-      dst[(size_t)r * W] = (uint8_t)((c[0] >> r) & 1ull);
-    }
-  }
-}
-
-// ---- a whole group's proposals in one call (hgl_rle_decode_group_device): S entries that belong to G <= 64 images of their own
-// sizes.  The geometry rides in the kernel arguments (RleGroup, by value: no descriptor memory, nothing to keep alive), and the
-// two launches are those of hgl_rle_decode_device whatever G is: rle_group_starts_kernel is rle_starts_kernel with the entry's
-// image looked up and the mask's box read off the runs; rle_group_rows_kernel finds (image, entry, tile) of a block in the
-// host's tile prefix sums and takes the 4-column or the byte path as its image's width and base address allow.  Both searches
-// (<= 6 steps over <= 64 rows of the arguments) are uniform over the block.
-
 // the last g with v[g] <= key (v non-decreasing, v[0] <= key): the image that owns entry / tile `key`; images without entries
 // share their successor's value and are passed over
 template <typename T>
@@ -409,20 +306,47 @@ __device__ __forceinline__ void rle_box_join(unsigned a, unsigned b, unsigned H,
   y1 = y1 > yb ? y1 : yb;
 }
 
-// rle_starts_kernel's pass with the entry's image looked up and the box: boxes [S,4] receives the inclusive XYXY box of the mask
-// the entry decodes to (batched_mask_to_box, utils/amg.py:303-346; zeros for an empty mask and for code 2), read off the runs
-// (form 0) or the plane words (form 1) in the pass that scans them.  (A body shared with rle_starts_kernel changed that
-// kernel's register allocation and schedule, so the pass is written out here.)
-__global__ __launch_bounds__(RLE_THREADS) void rle_group_starts_kernel(const uint32_t* __restrict__ slots, long long slot_words,
-                                                                       const int32_t* __restrict__ table, const RleGroup grp,
-                                                                       uint32_t* __restrict__ E, long long e_stride,
-                                                                       int32_t* __restrict__ status, int32_t* __restrict__ boxes) {
+// The size of the image that owns entry s: looked up in a group, the image itself in a call of one.
+__device__ __forceinline__ void rle_entry_size(const RleGroup& grp, int s, int& H, int& W) {
+  const int g = rle_group_find(grp.first, grp.G, s);
+  H = grp.H[g], W = grp.W[g];
+}
+__device__ __forceinline__ void rle_entry_size(const RleOne& one, int, int& H, int& W) { H = one.H, W = one.W; }
+
+// What a block of the rows kernel needs of the image that owns its tile: size and tiling (rle_tiles' arithmetic; a call of one
+// brings the host's), first entry and tile, byte offset of the first entry, store path (V = 0: the image's own, else V's).
+struct RleImage {
+  int H, W, HW64, col_tiles, row_tiles, first;
+  unsigned tile0;
+  long long off;
+  bool wide;
+};
+template <int V>
+__device__ __forceinline__ RleImage rle_tile_image(const RleGroup& grp, unsigned tile) {
+  const int g = rle_group_find(grp.tile0, grp.G, tile);
+  const bool wide = V == 0 ? (bool)((grp.wide >> g) & 1ull) : V == 4;
+  const int H = grp.H[g], W = grp.W[g], HW64 = (H + 63) / 64;
+  return {H, W, HW64, (W + (wide ? 255 : 63)) / (wide ? 256 : 64), (HW64 + 3) / 4, grp.first[g], grp.tile0[g], grp.off[g], wide};
+}
+template <int V>
+__device__ __forceinline__ RleImage rle_tile_image(const RleOne& one, unsigned) {
+  return {one.H, one.W, one.HW64, one.col_tiles, one.row_tiles, 0, 0u, 0ll, V == 4};
+}
+
+// boxes [S,4] (BOX only) receives the inclusive XYXY box of the mask the entry decodes to (batched_mask_to_box,
+// utils/amg.py:303-346; zeros for an empty mask and for code 2), read off the runs (form 0) or the plane words (form 1) in the
+// pass that scans them.  GEO: RleGroup or RleOne.
+template <bool BOX, class GEO>
+__global__ __launch_bounds__(RLE_THREADS) void rle_starts_kernel(const uint32_t* __restrict__ slots, long long slot_words,
+                                                                 const int32_t* __restrict__ table, const GEO geo,
+                                                                 uint32_t* __restrict__ E, long long e_stride,
+                                                                 int32_t* __restrict__ status, int32_t* __restrict__ boxes) {
   __shared__ unsigned red[4];
   __shared__ unsigned long long wtot[4];
   const int s = blockIdx.x;
-  const int g = rle_group_find(grp.first, grp.G, s);
-  const int H = grp.H[g], W = grp.W[g];
-  int32_t* box = boxes + (size_t)s * 4;
+  int H, W;
+  rle_entry_size(geo, s, H, W);
+  int32_t* box = BOX ? boxes + (size_t)s * 4 : nullptr;
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
   const int n = table[(size_t)s * 4], form = table[(size_t)s * 4 + 1];
@@ -432,7 +356,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_group_starts_kernel(const uin
   if (!rle_entry_usable(n, form, slot_words, plane_words)) {      // uniform over the workgroup
     if (t == 0) {
       row[0] = 2; row[1] = 0; row[2] = 0; row[3] = 0;
-      box[0] = 0; box[1] = 0; box[2] = 0; box[3] = 0;
+      if (BOX) { box[0] = 0; box[1] = 0; box[2] = 0; box[3] = 0; }
     }
     return;
   }
@@ -446,7 +370,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_group_starts_kernel(const uin
       uint32_t v = slot[w];
       if (w == plane_words - 1u && tail < 32u) v &= (1u << tail) - 1u;
       area += __popc(v);
-      if (v) {
+      if (BOX && v) {
         // the word's set pixels column by column (a word spans several columns when H < 32)
         const unsigned p = 32u * w;
         unsigned x = p / (unsigned)H, y = p - x * (unsigned)H, filled = 0;
@@ -494,7 +418,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_group_starts_kernel(const uin
         const unsigned start = sum - own < (unsigned long long)HW ? (unsigned)(sum - own) : HW;
         Es[i + 1] = end;
         if (i & 1u) area += end - start;
-        if ((i & 1u) && end > start) rle_box_join(start, end, (unsigned)H, bx0, by0, bx1, by1);
+        if (BOX && (i & 1u) && end > start) rle_box_join(start, end, (unsigned)H, bx0, by0, bx1, by1);
       }
       carry += tot;
     }
@@ -502,6 +426,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_group_starts_kernel(const uin
   }
   area = rle_block_sum(area, red);
   if (t == 0) { row[0] = code; row[1] = (int32_t)area; row[2] = 0; row[3] = 0; }
+  if (!BOX) return;
   // minima as maxima of the complement; an empty mask keeps the zeros of batched_mask_to_box
   bx0 = 0x7fffffffu - rle_block_max(0x7fffffffu - bx0, red);
   by0 = 0x7fffffffu - rle_block_max(0x7fffffffu - by0, red);
@@ -515,8 +440,8 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_group_starts_kernel(const uin
   }
 }
 
-// rle_rows_kernel's tile: rows 64j .. 64j+63 of columns x .. x+V-1 of entry s (j < HW64, x < W) into the entry's mask at dst
-// [H,W]; V columns per lane (4: one aligned 32-bit store per row when W % 4 == 0 and dst is 4-byte aligned).  No barrier, no cross-lane operation.
+// rows 64j .. 64j+63 of columns x .. x+V-1 of entry s (j < HW64, x < W) into the entry's mask at dst [H,W]; V columns per lane
+// (4: one aligned 32-bit store per row when W % 4 == 0 and dst is 4-byte aligned).  No barrier, no cross-lane operation.
 template <int V>
 __device__ __forceinline__ void rle_rows_tile(const uint32_t* __restrict__ slots, long long slot_words,
                                               const int32_t* __restrict__ table, const uint32_t* __restrict__ E, long long e_stride,
@@ -548,31 +473,31 @@ __device__ __forceinline__ void rle_rows_tile(const uint32_t* __restrict__ slots
   }
 }
 
-__global__ __launch_bounds__(RLE_THREADS) void rle_group_rows_kernel(const uint32_t* __restrict__ slots, long long slot_words,
-                                                                     const int32_t* __restrict__ table,
-                                                                     const uint32_t* __restrict__ E, long long e_stride,
-                                                                     const int32_t* __restrict__ status, const RleGroup grp,
-                                                                     uint8_t* __restrict__ masks) {
+// 64 rows per wave, 4 waves = 4 row tiles per block; V as under C above, GEO: RleGroup or RleOne.  Waves per SIMD are asked for
+// (8 with one store path, 5 with both): left alone, the register allocator spreads V = 4 over a group over 94 VGPRs, occupancy 5.
+template <int V, class GEO>
+__global__ __launch_bounds__(RLE_THREADS, V ? 8 : 5) void rle_rows_kernel(const uint32_t* __restrict__ slots, long long slot_words,
+                                                                          const int32_t* __restrict__ table,
+                                                                          const uint32_t* __restrict__ E, long long e_stride,
+                                                                          const int32_t* __restrict__ status, const GEO geo,
+                                                                          uint8_t* __restrict__ masks) {
   const unsigned tile = blockIdx.x;
-  const int g = rle_group_find(grp.tile0, grp.G, tile);
-  const int H = grp.H[g], W = grp.W[g];
-  const bool wide = (grp.wide >> g) & 1ull;
-  const int HW64 = (H + 63) / 64;
-  const int col_tiles = (W + (wide ? 255 : 63)) / (wide ? 256 : 64), row_tiles = (HW64 + 3) / 4;
-  const unsigned local = tile - grp.tile0[g];
+  const RleImage im = rle_tile_image<V>(geo, tile);
+  const int H = im.H, W = im.W, HW64 = im.HW64, col_tiles = im.col_tiles, row_tiles = im.row_tiles;
+  const bool wide = im.wide;      // a constant unless V == 0: one store path is compiled
+  const unsigned local = tile - im.tile0;
   const int k = (int)(local / (unsigned)(col_tiles * row_tiles));      // the entry within its image
   const int rem = (int)(local % (unsigned)(col_tiles * row_tiles));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = (rem / col_tiles) * 4 + wave;
-  uint8_t* dst = masks + grp.off[g] + (size_t)k * H * W;
-  const int s = grp.first[g] + k;
-  if (wide) {
-    const int x = ((rem % col_tiles) * 64 + lane) * 4;
-    if (j < HW64 && x < W) rle_rows_tile<4>(slots, slot_words, table, E, e_stride, status, s, H, W, j, x, dst);
-  } else {
-    const int x = (rem % col_tiles) * 64 + lane;
-    if (j < HW64 && x < W) rle_rows_tile<1>(slots, slot_words, table, E, e_stride, status, s, H, W, j, x, dst);
-  }
+  uint8_t* dst = masks + im.off + (size_t)k * H * W;
+  const int s = im.first + k;
+  const int x = ((rem % col_tiles) * 64 + lane) * (wide ? 4 : 1);
+  if (j >= HW64 || x >= W) return;
+  if (wide)
+    rle_rows_tile<4>(slots, slot_words, table, E, e_stride, status, s, H, W, j, x, dst);
+  else
+    rle_rows_tile<1>(slots, slot_words, table, E, e_stride, status, s, H, W, j, x, dst);
 }
 
 // one thread per plane word: word q = x*HW64 + j of entry s, q_tiles workgroups per entry
@@ -623,6 +548,44 @@ size_t rle_planes_bytes(int S, int H, int W) {
 }
 size_t rle_status_bytes(int S) { return hgl_align_up((size_t)S * 4 * sizeof(int32_t), 256); }
 
+// the one decode: plan the images' geometry (-1), check the workspace (-3), two launches; boxes: null for none
+int rle_decode_launch(const char* name, const uint32_t* slots, long long slot_words, const int32_t* table, int S,
+                      const int64_t* images, int G, uint8_t* masks, long long masks_bytes, int32_t* boxes, int32_t* status, void* ws,
+                      size_t ws_bytes, void* stream) {
+  RleGroup grp;
+  long long tiles = 0;
+  char why[200];
+  if (rle_group_plan(images, G, S, (uintptr_t)masks, masks_bytes, &grp, &tiles, why, sizeof(why)) != 0) {
+    hgl_set_error("%s: %s", name, why);
+    return HGL_EINVAL;
+  }
+  if (!ws || ws_bytes < rle_starts_bytes(S, slot_words)) {
+    hgl_set_error("%s: workspace too small", name);
+    return HGL_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t* E = (uint32_t*)ws;
+  const long long e_stride = slot_words + 1;
+  const unsigned long long all = G == RLE_GROUP_MAX ? ~0ull : (1ull << G) - 1ull;
+  // V: one store path for all G images -> the kernel that holds only that path; the choice per image otherwise
+  auto launch = [&](auto geo, uint8_t* base) {
+    using GEO = decltype(geo);
+    auto starts = boxes ? rle_starts_kernel<true, GEO> : rle_starts_kernel<false, GEO>;
+    hipLaunchKernelGGL(starts, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots, slot_words, table, geo, E, e_stride, status, boxes);
+    auto rows = grp.wide == all ? rle_rows_kernel<4, GEO> : rle_rows_kernel<1, GEO>;
+    if constexpr (std::is_same<GEO, RleGroup>::value)
+      if (grp.wide != all && grp.wide != 0) rows = rle_rows_kernel<0, GEO>;
+    hipLaunchKernelGGL(rows, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, slots, slot_words, table, (const uint32_t*)E, e_stride,
+                       (const int32_t*)status, geo, base);
+  };
+  const RleTiles one = rle_tiles(grp.H[0], grp.W[0], (uintptr_t)masks + (uintptr_t)grp.off[0]);
+  if (G == 1)
+    launch(RleOne{grp.H[0], grp.W[0], one.HW64, one.col_tiles, one.row_tiles}, masks + grp.off[0]);
+  else
+    launch(grp, masks);
+  return hgl_check_launch(name);
+}
+
 }  // namespace
 
 extern "C" {
@@ -638,10 +601,8 @@ int hgl_rle_encode_device(const uint8_t* masks, int N, int H, int W, const int64
   HGL_REQUIRE(masks && slots && table && N > 0 && H > 0 && W > 0 && S > 0 && slot_words >= 0, "rle_encode_device: bad arguments");
   HGL_REQUIRE(sel || S <= N, "rle_encode_device: without an index tensor S (%d) must not exceed N (%d)", S, N);
   HGL_REQUIRE((long long)N * H * W < (1ll << 31), "rle_encode_device: batch too large (N*H*W must be < 2^31)");
-  const int HW64 = (H + 63) / 64;
-  const bool wide = (W % 4 == 0) && (((uintptr_t)masks & 3u) == 0);
-  const int col_tiles = (W + (wide ? 255 : 63)) / (wide ? 256 : 64), row_tiles = (HW64 + 3) / 4;
-  const long long tiles = (long long)S * col_tiles * row_tiles;
+  const RleTiles t = rle_tiles(H, W, (uintptr_t)masks);
+  const long long tiles = (long long)S * t.col_tiles * t.row_tiles;
   HGL_REQUIRE(tiles < (1ll << 31), "rle_encode_device: too many entries (%d) for one launch", S);
   if (!ws || ws_bytes < hgl_rle_encode_workspace_bytes(S, H, W)) {
     hgl_set_error("rle_encode_device: workspace too small");
@@ -650,14 +611,14 @@ int hgl_rle_encode_device(const uint8_t* masks, int N, int H, int W, const int64
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* plane = (unsigned long long*)ws;
   const long long* sel64 = (const long long*)sel;
-  if (wide)
-    hipLaunchKernelGGL(rle_columns_kernel<4>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, masks, N, H, W, sel64, HW64,
-                       col_tiles, row_tiles, plane);
+  if (t.wide)
+    hipLaunchKernelGGL(rle_columns_kernel<4>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, masks, N, H, W, sel64, t.HW64,
+                       t.col_tiles, t.row_tiles, plane);
   else
-    hipLaunchKernelGGL(rle_columns_kernel<1>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, masks, N, H, W, sel64, HW64,
-                       col_tiles, row_tiles, plane);
+    hipLaunchKernelGGL(rle_columns_kernel<1>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, masks, N, H, W, sel64, t.HW64,
+                       t.col_tiles, t.row_tiles, plane);
   hipLaunchKernelGGL(rle_runs_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)plane, N, H, W,
-                     sel64, HW64, slots, slot_words, table);
+                     sel64, t.HW64, slots, slot_words, table);
   return hgl_check_launch("rle_encode_device");
 }
 
@@ -672,27 +633,9 @@ int hgl_rle_decode_device(const uint32_t* slots, long long slot_words, const int
   HGL_REQUIRE(slots && table && masks && status && S > 0 && H > 0 && W > 0 && slot_words >= 0, "rle_decode_device: bad arguments");
   HGL_REQUIRE((long long)H * W < (1ll << 31), "rle_decode_device: image too large (H*W must be < 2^31)");
   HGL_REQUIRE((long long)S * H * W < (1ll << 31), "rle_decode_device: batch too large (S*H*W must be < 2^31)");
-  const int HW64 = (H + 63) / 64;
-  const bool wide = (W % 4 == 0) && (((uintptr_t)masks & 3u) == 0);
-  const int col_tiles = (W + (wide ? 255 : 63)) / (wide ? 256 : 64), row_tiles = (HW64 + 3) / 4;
-  const long long tiles = (long long)S * col_tiles * row_tiles;
-  HGL_REQUIRE(tiles < (1ll << 31), "rle_decode_device: too many entries (%d) for one launch", S);
-  if (!ws || ws_bytes < hgl_rle_decode_workspace_bytes(S, H, W, slot_words)) {
-    hgl_set_error("rle_decode_device: workspace too small");
-    return HGL_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t* E = (uint32_t*)ws;
-  const long long e_stride = slot_words + 1;
-  hipLaunchKernelGGL(rle_starts_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots, slot_words, table, H, W, E, e_stride,
-                     status);
-  if (wide)
-    hipLaunchKernelGGL(rle_rows_kernel<4>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
-                       (const uint32_t*)E, e_stride, (const int32_t*)status, H, W, HW64, col_tiles, row_tiles, masks);
-  else
-    hipLaunchKernelGGL(rle_rows_kernel<1>, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
-                       (const uint32_t*)E, e_stride, (const int32_t*)status, H, W, HW64, col_tiles, row_tiles, masks);
-  return hgl_check_launch("rle_decode_device");
+  const int64_t image[4] = {H, W, 0, 0};      // a group of one: every entry is this image's, from byte 0 on
+  return rle_decode_launch("rle_decode_device", slots, slot_words, table, S, image, 1, masks, (long long)S * H * W, nullptr, status,
+                           ws, ws_bytes, stream);
 }
 
 size_t hgl_rle_decode_group_workspace_bytes(int S, long long slot_words) {
@@ -706,25 +649,8 @@ int hgl_rle_decode_group_device(const uint32_t* slots, long long slot_words, con
   HGL_TRY(hgl_require_device());
   HGL_REQUIRE(slots && table && images_host && masks && boxes_xyxy && status && S > 0 && slot_words >= 0 && masks_bytes >= 0,
               "rle_decode_group_device: bad arguments");
-  RleGroup grp;
-  long long tiles = 0;
-  char why[200];
-  if (rle_group_plan(images_host, G, S, (uintptr_t)masks, masks_bytes, &grp, &tiles, why, sizeof(why)) != 0) {
-    hgl_set_error("rle_decode_group_device: %s", why);
-    return HGL_EINVAL;
-  }
-  if (!ws || ws_bytes < hgl_rle_decode_group_workspace_bytes(S, slot_words)) {
-    hgl_set_error("rle_decode_group_device: workspace too small");
-    return HGL_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t* E = (uint32_t*)ws;
-  const long long e_stride = slot_words + 1;
-  hipLaunchKernelGGL(rle_group_starts_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots, slot_words, table, grp, E, e_stride,
-                     status, boxes_xyxy);
-  hipLaunchKernelGGL(rle_group_rows_kernel, dim3((unsigned)tiles), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
-                     (const uint32_t*)E, e_stride, (const int32_t*)status, grp, masks);
-  return hgl_check_launch("rle_decode_group_device");
+  return rle_decode_launch("rle_decode_group_device", slots, slot_words, table, S, images_host, G, masks, masks_bytes, boxes_xyxy,
+                           status, ws, ws_bytes, stream);
 }
 
 size_t hgl_rle_iou_workspace_bytes(int S, int H, int W, long long slot_words_a, long long slot_words_b) {
@@ -766,8 +692,8 @@ int hgl_rle_iou_device(const uint32_t* slots_a, long long slot_words_a, const in
     p += rle_status_bytes(S);
   }
   for (int i = 0; i < 2; ++i) {
-    hipLaunchKernelGGL(rle_starts_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i], H, W, E[i], sw[i] + 1,
-                       status[i]);
+    hipLaunchKernelGGL((rle_starts_kernel<false, RleOne>), dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
+                       RleOne{H, W, HW64, 0, 0}, E[i], sw[i] + 1, status[i], (int32_t*)nullptr);
     hipLaunchKernelGGL(rle_plane_kernel, dim3((unsigned)(S * q_tiles)), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
                        (const uint32_t*)E[i], sw[i] + 1, (const int32_t*)status[i], H, W, HW64, q_tiles, plane[i]);
   }

@@ -1,6 +1,6 @@
-// The geometry of hgl_rle_decode_group_device (csrc/rle.hip): what the host works out of the caller's image rows and hands to the
-// two kernels by value.  Plain C++ without a HIP construct: rle.hip includes it, and so does the sanitizer harness
-// tests/native/rle_group_sanitize.cpp.
+// The geometry of the RLE entries (csrc/rle.hip): the tiling of an image, shared by the encoder and the decoder, and what the host
+// works out of a decode call's image rows and hands to the two decoder kernels by value.  Plain C++ without a HIP construct:
+// rle.hip includes it, and so does the sanitizer harness tests/native/rle_group_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
 #include <stdint.h>
@@ -8,13 +8,26 @@
 #include <stdio.h>
 #include <string.h>
 
+// The tiles of one H x W mask whose first byte lies at address `base` (rle_columns_kernel and rle_rows_kernel alike): a block is
+// 4 waves = 4 row tiles of 64 rows, by 64 lanes of one column each or, on the 4-column path (W % 4 == 0 and base 4-byte aligned:
+// one aligned 32-bit access per row and lane), of four.
+struct RleTiles {
+  bool wide;
+  int HW64, col_tiles, row_tiles;      // 64-row words per column; blocks across; blocks down
+};
+static inline RleTiles rle_tiles(long long H, long long W, uintptr_t base) {
+  const bool wide = (W % 4 == 0) && ((base & 3u) == 0);
+  const int HW64 = (int)((H + 63) / 64);
+  return {wide, HW64, (int)((W + (wide ? 255 : 63)) / (wide ? 256 : 64)), (HW64 + 3) / 4};
+}
+
 constexpr int RLE_GROUP_MAX = 64;
 
 struct RleGroup {
   long long off[RLE_GROUP_MAX];                 // byte offset of the image's first entry in masks
   int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
   int first[RLE_GROUP_MAX];                     // the image's first entry (non-decreasing, first[0] = 0)
-  unsigned tile0[RLE_GROUP_MAX];                // the image's first tile of rle_group_rows_kernel (non-decreasing, tile0[0] = 0)
+  unsigned tile0[RLE_GROUP_MAX];                // the image's first tile of rle_rows_kernel (non-decreasing, tile0[0] = 0)
   unsigned long long wide;                      // bit g: image g takes the 4-column store path
   int G;
 };
@@ -53,21 +66,25 @@ static inline int rle_group_plan(const int64_t* images, int G, int S, uintptr_t 
     for (int f = 0; f < g; ++f)
       RLE_GROUP_REQUIRE(lo[g] == hi[g] || lo[f] == hi[f] || hi[f] <= lo[g] || hi[g] <= lo[f],
                         "the extents of images %d and %d overlap", f, g);
-    const bool wide = (W % 4 == 0) && (((masks + (uintptr_t)o) & 3u) == 0);
-    const long long HW64 = (H + 63) / 64;
-    const long long col_tiles = (W + (wide ? 255 : 63)) / (wide ? 256 : 64), row_tiles = (HW64 + 3) / 4;
+    const RleTiles t = rle_tiles(H, W, masks + (uintptr_t)o);
     grp->off[g] = o;
     grp->H[g] = (int)H;
     grp->W[g] = (int)W;
     grp->first[g] = (int)e;
     grp->tile0[g] = (unsigned)tiles;
-    if (wide) grp->wide |= 1ull << g;
-    tiles += n * col_tiles * row_tiles;
+    if (t.wide) grp->wide |= 1ull << g;
+    tiles += n * t.col_tiles * t.row_tiles;
     RLE_GROUP_REQUIRE(tiles < (1ll << 31), "too many entries (%d) for one launch", S);
   }
   *tiles_out = tiles;
   return 0;
 #undef RLE_GROUP_REQUIRE
 }
+
+// A call of one image whose first entry lies at `masks` and which owns every entry: what the kernels take in place of RleGroup
+// then -- nothing to look up, five scalars in the arguments.
+struct RleOne {
+  int H, W, HW64, col_tiles, row_tiles;      // rle_tiles' (the rows kernel reads the last two; 0 for a caller of the starts kernel alone)
+};
 
 #endif  // HGL_RLE_GROUP_H

@@ -221,3 +221,14 @@ def launched_kernels(fn):
     evs.sort(key=lambda e: e.time_range.start)
     names = [e.name for e in evs if not e.name.lower().startswith(("memcpy", "memset"))]
     return [kernel_key(n) or n for n in names]
+
+
+def rle_kernels(fn):
+    """launched_kernels(fn) for the kernels of csrc/rle.hip: [(function name, first template argument or None)] in launch order, from
+    a demangled ('rle_rows_kernel<4>(...)') or an Itanium-mangled ('15rle_rows_kernelILi4EEEv...') name; any other kernel
+    keeps its raw name"""
+    out = []
+    for n in launched_kernels(fn):
+        m = re.search(r"(rle_[a-z]+_kernel)(?:<(\w+)[,>]|IL[ib](\d+)E)?", n)
+        out.append((m.group(1), m.group(2) or m.group(3)) if m else (n, None))
+    return out

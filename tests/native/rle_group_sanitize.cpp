@@ -1,8 +1,9 @@
-// Sanitizer harness for rle_group_plan (csrc/rle_group.h: the host side of hgl_rle_decode_group_device), built by
+// Sanitizer harness for rle_group_plan and rle_tiles (csrc/rle_group.h: the host side of the RLE entries), built by
 // tests/test_sanitize_rle_group.py with g++ -fsanitize=address,undefined.  Reads a case file written by the test, one case per
 // line:   <G> <S> <base address> <masks_bytes> <4*G numbers: H W first offset per image>
 // and prints one line per case: the return code, then for an accepted case the number of tiles, the wide bits and per image
 // "H W first tile0 off".  The image rows live in a heap buffer of exactly 4*G words, so a read beyond them is a report.
+// A line   T <H> <W> <base address>   is a case of rle_tiles and prints "T wide HW64 col_tiles row_tiles".
 #include <cinttypes>
 #include <cstdint>
 #include <cstdio>
@@ -20,6 +21,14 @@ int main(int argc, char** argv) {
   std::string line;
   while (std::getline(in, line)) {
     std::istringstream ss(line);
+    if (line.rfind("T ", 0) == 0) {
+      char tag;
+      long long H, W, base;
+      ss >> tag >> H >> W >> base;
+      const RleTiles t = rle_tiles(H, W, (uintptr_t)base);
+      printf("T %d %d %d %d\n", (int)t.wide, t.HW64, t.col_tiles, t.row_tiles);
+      continue;
+    }
     long long G, S, base, bytes;
     if (!(ss >> G >> S >> base >> bytes)) continue;
     const long long rows = G < 0 ? 0 : (G > 70 ? 70 : G);      // what the caller owns

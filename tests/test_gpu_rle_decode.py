@@ -235,6 +235,21 @@ def test_unaligned_output_takes_the_narrow_path(cuda):
         assert status[:, 1].tolist() == batch.reshape(3, -1).sum(1).tolist()
 
 
+def test_launch_counts(cuda):
+    """a single-size decode is the group decode of one image: the same two kernel functions and the same instantiation of the
+    rows kernel (the starts kernels differ by design: only the group entry's keeps the box); the IoU launches five"""
+    import abi_ref
+    H, W = 65, 63
+    batch = blobs(10, H, W, seed=51)
+    slots, table = ops.rle_pack([hsam.mask_to_rle(m)["counts"] for m in batch], H, W, device=cuda)
+    single = abi_ref.rle_kernels(lambda: ops.rle_decode(slots, table, H, W))
+    group = abi_ref.rle_kernels(lambda: ops.rle_decode_group(slots, table, [(H, W)], [10]))
+    assert [k for k, _ in single] == ["rle_starts_kernel", "rle_rows_kernel"], single
+    assert [k for k, _ in group] == [k for k, _ in single] and group[1] == single[1] == ("rle_rows_kernel", "1"), (single, group)
+    iou = abi_ref.rle_kernels(lambda: ops.rle_iou(slots, table, slots, table, H, W))
+    assert [k for k, _ in iou] == ["rle_starts_kernel", "rle_plane_kernel"] * 2 + ["rle_iou_kernel"], iou
+
+
 def test_two_calls_give_identical_bytes(cuda):
     H, W = 130, 70
     batch = blobs(4, H, W, seed=31)

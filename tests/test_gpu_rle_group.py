@@ -1,6 +1,7 @@
 """hgl_rle_decode_group_device (csrc/rle.hip) through ops.rle_decode_group: one call for a group of images of several sizes
-against ops.rle_decode + sam.mask_boxes per image -- masks, boxes, status and area with torch.equal -- on the sizes at which
-the row tiling, the two store paths and the image lookup change, on every kind of entry the decoder knows, and the contract of
+against a host oracle built from the slots and the table (masks, status, boxes: exact) and against ops.rle_decode +
+sam.mask_boxes per image (a group of one equals a group of many; mask_boxes is a kernel of its own) -- on the sizes at which
+the row tiling, the store paths and the image lookup change, on every kind of entry the decoder knows, and the contract of
 the entry (containment with guard bytes, determinism, refused geometry, a launch count that does not depend on the group)."""
 import numpy as np
 import pytest
@@ -9,6 +10,7 @@ import torch
 from hybridgl_amd import _lib, ops
 from hybridgl_amd import sam as hsam
 from oracle import gen_gtmask_golden as GG
+from oracle import gtmask_oracle as G
 
 import abi_ref
 
@@ -79,10 +81,44 @@ def reference(slots, table, sizes, counts):
     return masks, torch.cat(boxes), torch.cat(status)
 
 
+def host_oracle(slots, table, sizes, counts):
+    """the decoder's contract on the host, from the slots and the table as the device holds them -> per image masks [n,H,W]
+    uint8, and for all entries status rows (code, area, 0, 0) and inclusive XYXY boxes (zeros for an empty mask)"""
+    words = slots.cpu().numpy().view(np.uint32)
+    tab = table.cpu().numpy()
+    sw = words.shape[1]
+    masks, status, boxes, e = [], [], [], 0
+    for (H, W), n in zip(sizes, counts):
+        out = np.zeros((n, H, W), np.uint8)
+        for i in range(n):
+            cnt, form = int(tab[e + i, 0]), int(tab[e + i, 1])
+            plane_words = (H * W + 31) // 32
+            code = 2
+            if form == 0 and 0 <= cnt <= sw:
+                c = [int(v) for v in words[e + i, :cnt]]
+                out[i] = G.counts_to_mask(c, H, W)
+                code = 0 if sum(c) == H * W else 1
+            elif form == 1 and cnt >= 0 and plane_words <= sw:      # n_counts < 0 is no mask in either form (include/hybridgl.h)
+                bits = np.unpackbits(words[e + i, :plane_words].astype("<u4").view(np.uint8), bitorder="little")
+                out[i] = bits[:H * W].reshape(W, H).T
+                code = 0
+            ys, xs = np.nonzero(out[i])
+            boxes.append([xs.min(), ys.min(), xs.max(), ys.max()] if len(ys) else [0, 0, 0, 0])
+            status.append([code, int(out[i].sum()), 0, 0])
+        masks.append(out)
+        e += n
+    return masks, np.array(status, np.int32).reshape(-1, 4), np.array(boxes, np.int32).reshape(-1, 4)
+
+
 def check_group(slots, table, sizes, counts):
     got_m, got_b, got_s = ops.rle_decode_group(slots, table, sizes, counts)
-    ref_m, ref_b, ref_s = reference(slots, table, sizes, counts)
+    want_m, want_s, want_b = host_oracle(slots, table, sizes, counts)
     assert len(got_m) == len(sizes)
+    for g, (a, b) in enumerate(zip(got_m, want_m)):
+        assert np.array_equal(a.cpu().numpy(), b), (g, sizes[g])
+    assert np.array_equal(got_s.cpu().numpy(), want_s), (got_s.cpu().numpy() != want_s).any(1).nonzero()[0].tolist()
+    assert np.array_equal(got_b.cpu().numpy(), want_b), (got_b.cpu().numpy() != want_b).any(1).nonzero()[0].tolist()
+    ref_m, ref_b, ref_s = reference(slots, table, sizes, counts)
     for g, (a, b) in enumerate(zip(got_m, ref_m)):
         assert tuple(a.shape) == (counts[g],) + tuple(sizes[g]) and a.dtype == torch.uint8
         assert torch.equal(a, b), (g, sizes[g])
@@ -284,14 +320,64 @@ def test_bad_geometry_is_refused_and_nothing_is_enqueued(cuda):
 
 
 def test_the_launches_do_not_depend_on_the_group(cuda):
-    """six images of six sizes launch the kernel list of a group of one"""
+    """six images of six sizes, and a group whose images take different store paths, launch the two kernels of a group of one
+    (which instantiation of the rows kernel: test_every_rows_kernel_writes_the_same_bytes)"""
     sizes = [(1, 1), (64, 64), (65, 63), (63, 260), (130, 4), (3, 5)]
     sets = [ops.rle_pack(image_counts(H, W)[:10], H, W, device=cuda) for H, W in sizes]
     slots, table = join(sets)
-    one = abi_ref.launched_kernels(lambda: ops.rle_decode_group(*sets[1], sizes[1:2], [10]))
-    six = abi_ref.launched_kernels(lambda: ops.rle_decode_group(slots, table, sizes, [10] * 6))
-    assert len(one) == 2 and six == one, (one, six)
-    assert "rle_group_starts_kernel" in one[0] and "rle_group_rows_kernel" in one[1]
+    one = abi_ref.rle_kernels(lambda: ops.rle_decode_group(*sets[1], sizes[1:2], [10]))
+    six = abi_ref.rle_kernels(lambda: ops.rle_decode_group(slots, table, sizes, [10] * 6))
+    # 3 x 5 with 8 entries is narrow, 64 x 64 behind it at byte 120 is wide
+    m_slots, m_table = join([ops.rle_pack(image_counts(3, 5)[:8], 3, 5, device=cuda), sets[1]])
+    mixed = abi_ref.rle_kernels(lambda: ops.rle_decode_group(m_slots, m_table, [(3, 5), (64, 64)], [8, 10]))
+    assert len(one) == 2 and len(six) == 2 and len(mixed) == 2, (one, six, mixed)
+    for got in (one, six, mixed):
+        assert [k for k, _ in got] == ["rle_starts_kernel", "rle_rows_kernel"], got
+    assert mixed[1][1] == "0", mixed
+
+
+def test_every_rows_kernel_writes_the_same_bytes(cuda):
+    """65 x 260 entries of every kind through rle_rows_kernel<4>, <1> and <0>: ops.rle_decode into an aligned and into an odd
+    address, and as the second image of a group behind a 3 x 5 image whose 8 (7) entries leave it at byte 120 (105) -- the
+    bytes, the status rows and (group calls) the boxes equal the host oracle"""
+    H, W = 65, 260
+    yy, xx = np.mgrid[0:H, 0:W]
+    dense = np.stack([(yy + xx) & 1, np.random.default_rng(5).random((H, W)) < 0.5]).astype(np.uint8)
+    planes = ops.rle_encode(torch.from_numpy(dense).to(cuda))
+    assert planes[1].cpu().numpy()[:, 1].tolist() == [1, 1]
+    slots, table = join([ops.rle_pack(image_counts(H, W), H, W, device=cuda), planes])
+    S = int(slots.shape[0])
+    n = S * H * W
+    (want_m,), want_s, want_b = host_oracle(slots, table, [(H, W)], [S])
+    assert np.array_equal(want_m[-2:], dense) and set(want_s[:, 0].tolist()) == {0, 1}
+
+    def single(offset, V):
+        buf = torch.full((offset + n + 64,), SENT, dtype=torch.uint8, device=cuda)
+        assert buf.data_ptr() % 4 == 0
+        res = []
+        names = abi_ref.rle_kernels(lambda: res.append(ops.rle_decode(slots, table, H, W, out=buf[offset:offset + n])))
+        assert names == [("rle_starts_kernel", names[0][1]), ("rle_rows_kernel", V)], names
+        host = buf.cpu().numpy()
+        assert (host[:offset] == SENT).all() and (host[offset + n:] == SENT).all(), "wrote outside the output"
+        return host[offset:offset + n].reshape(S, H, W), res[0][1].cpu().numpy(), None
+
+    def behind(k, V):
+        first = ops.rle_pack(image_counts(3, 5)[:k], 3, 5, device=cuda)
+        g_slots, g_table = join([first, (slots, table)])
+        images, _ = ops.rle_group_layout([(3, 5), (H, W)], [k, S])
+        assert images[1, 3] == 15 * k
+        res = []
+        names = abi_ref.rle_kernels(lambda: res.append(ops.rle_decode_group(g_slots, g_table, [(3, 5), (H, W)], [k, S])))
+        assert names == [("rle_starts_kernel", names[0][1]), ("rle_rows_kernel", V)], names
+        masks, boxes, status = res[0]
+        assert masks[0].data_ptr() % 4 == 0
+        return masks[1].cpu().numpy(), status[k:].cpu().numpy(), boxes[k:].cpu().numpy()
+
+    for name, (m, st, b) in (("aligned: <4>", single(0, "4")), ("odd address: <1>", single(1, "1")),
+                             ("behind 120 bytes: <0>, wide branch", behind(8, "0")), ("behind 105 bytes: <1>", behind(7, "1"))):
+        assert m.max() <= 1 and np.array_equal(m, want_m), name
+        assert np.array_equal(st, want_s), name
+        assert b is None or np.array_equal(b, want_b), name
 
 
 def test_front_end_checks(cuda):

@@ -1,7 +1,8 @@
-"""The host side of hgl_rle_decode_group_device -- rle_group_plan (csrc/rle_group.h): validation of the caller's image rows, tile
-prefix sums, the choice of the store path per image -- under AddressSanitizer + UndefinedBehaviorSanitizer, as a stand-alone
-program (tests/native/rle_group_sanitize.cpp) built with g++ -fsanitize=address,undefined -fno-sanitize-recover: accepted
-geometries against the same arithmetic in Python, every refusal of the contract, seeded random rows."""
+"""The host side of the RLE decode entries -- rle_group_plan (csrc/rle_group.h): validation of the caller's image rows, tile
+prefix sums, the choice of the store path per image -- and the tiling all RLE entries share (rle_tiles) under AddressSanitizer
++ UndefinedBehaviorSanitizer, as a stand-alone program (tests/native/rle_group_sanitize.cpp) built with g++
+-fsanitize=address,undefined -fno-sanitize-recover: accepted geometries against the same arithmetic in Python, every refusal of
+the contract, seeded random rows, the one-image rows of the single-size entries."""
 import os
 import shutil
 import subprocess
@@ -25,6 +26,13 @@ def harness(tmp_path_factory):
     return str(out)
 
 
+def tiles_of(H, W, base):
+    """rle_tiles in Python: (wide, 64-row words per column, blocks across, blocks down)"""
+    wide = W % 4 == 0 and base % 4 == 0
+    HW64 = (H + 63) // 64
+    return wide, HW64, (W + (255 if wide else 63)) // (256 if wide else 64), (HW64 + 3) // 4
+
+
 def plan(images, S, base, nbytes):
     """rle_group_plan in Python: None when the geometry is refused, else (tiles, wide bits, rows of H W first tile0 off)"""
     G = len(images)
@@ -44,9 +52,7 @@ def plan(images, S, base, nbytes):
         if any(lo != hi and a != b and not (b <= lo or hi <= a) for a, b in ext):
             return None
         ext.append((lo, hi))
-        wide = W % 4 == 0 and (base + o) % 4 == 0
-        col = (W + (255 if wide else 63)) // (256 if wide else 64)
-        row = ((H + 63) // 64 + 3) // 4
+        wide, _, col, row = tiles_of(H, W, base + o)
         rows.append((H, W, e, tiles, o))
         wide_bits |= int(wide) << g
         tiles += n * col * row
@@ -98,7 +104,18 @@ def cases():
             g, col = int(rng.integers(0, G)), int(rng.integers(0, 4))
             im[g][col] += int(rng.integers(-40, 41))
         out.append((im, s, int(rng.integers(0, 8)), tot + int(rng.integers(-3, 4))))
+    # what hgl_rle_decode_device makes of (S, H, W, masks): one row (H, W, 0, 0) and S*H*W bytes, at any address
+    for H, W in ONE_IMAGE_SIZES:
+        for base in (0, 1, 4096, 4099):
+            out.append(([[H, W, 0, 0]], 3, base, 3 * H * W))
+    out.append(([[1 << 16, 1 << 15, 0, 0]], 1, 0, 1 << 31))      # H*W = 2^31
+    out.append(([[1 << 15, 1 << 15, 0, 0]], 2, 0, 1 << 31))      # S*H*W = 2^31
     return out
+
+
+ONE_IMAGE_SIZES = [(65, 63), (65, 260), (640, 640), (1, 1), (3, 5), (130, 4)]
+TILE_CASES = [(H, W, base) for H, W in ONE_IMAGE_SIZES + [(63, 256), (64, 257), (257, 64), ((1 << 31) - 1, 1), (1, (1 << 31) - 4),
+                                                           (1, (1 << 31) - 1)] for base in (0, 1, 2, 4096, (1 << 48) + 4)]
 
 
 def test_plan_under_asan_ubsan(harness, tmp_path):
@@ -107,11 +124,17 @@ def test_plan_under_asan_ubsan(harness, tmp_path):
     with open(path, "w") as f:
         for images, S, base, nbytes in todo:
             f.write(" ".join(str(v) for v in [len(images), S, base, nbytes] + [x for row in images for x in row]) + "\n")
+        for H, W, base in TILE_CASES:
+            f.write(f"T {H} {W} {base}\n")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([harness, str(path)], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     lines = r.stdout.strip().split("\n")
-    assert len(lines) == len(todo)
+    assert len(lines) == len(todo) + len(TILE_CASES)
+    for (H, W, base), line in zip(TILE_CASES, lines[len(todo):]):
+        wide, HW64, col, row = tiles_of(H, W, base)
+        assert line == f"T {int(wide)} {HW64} {col} {row}", (H, W, base, line)
+    lines = lines[:len(todo)]
     accepted = 0
     for k, ((images, S, base, nbytes), line) in enumerate(zip(todo, lines)):
         want = plan(images, S, base, nbytes)
@@ -127,3 +150,10 @@ def test_plan_under_asan_ubsan(harness, tmp_path):
     # 3 x 5 in front of 64 x 64 at an aligned base: the latter's first byte is odd, it takes the byte path
     images, S, base, nbytes = todo[0]
     assert (plan(images, S, base, nbytes)[1] >> 6) & 1 == 0 and (plan(images, S, base, nbytes)[1] >> 1) & 1 == 1
+    # the one-image rows: accepted with the store path of (W, address) and S * tiles of one mask; 2^31 pixels or bytes refused
+    one = todo[-(4 * len(ONE_IMAGE_SIZES) + 2):]
+    for (images, S, base, nbytes), line in zip(one[:-2], lines[-len(one):-2]):
+        H, W = images[0][:2]
+        wide, _, col, row = tiles_of(H, W, base)
+        assert wide == (W % 4 == 0 and base % 4 == 0) and line.startswith(f"0 {S * col * row} {int(wide)} |"), line
+    assert all(l.startswith("-1 ") and "2^31" in l for l in lines[-2:]), lines[-2:]
