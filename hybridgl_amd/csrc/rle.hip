@@ -24,7 +24,7 @@
 // plane (bit p % 32 of word p / 32; whenever the counts do not fit but ceil(H*W/32) words do), 2 = neither fits, nothing
 // written, 3 = the index is outside [0, N), nothing read or written.  Words beyond what the form defines keep their bytes.
 #include "hgl_common.h"
-#include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan: plain C++, shared with the sanitizer harness
+#include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan, rle_match_plan: plain C++, shared with the sanitizer harnesses
 
 namespace {
 
@@ -217,8 +217,9 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned lo
 //      1 or 4 bytes per lane).  V = 4 / 1: every image of the call takes that store path (a single image always does);
 //      V = 0: each image its own, a branch uniform over the block.  Every byte of every entry is written exactly once; the
 //      decoder keeps no plane anywhere.
-//   D. rle_plane_kernel / rle_iou_kernel   for the IoU the words of both sets go to the workspace, one thread per word, and one
-//      workgroup per entry pop-counts a & b and a | b: padding bits are 0 on both sides, no mask is expanded to bytes.
+//   D. rle_plane_kernel<GEO> / rle_iou_kernel   for the IoU the words of both sets go to the workspace, one thread per word, and
+//      one workgroup per entry pop-counts a & b and a | b: padding bits are 0 on both sides, no mask is expanded to bytes.  GEO:
+//      RlePlaneOne (the pairwise IoU: one size) or RlePlaneGroup (the match below: the block finds its image by a search).
 
 // the slot of an entry holds a mask (include/hybridgl.h: anything else is code 2)
 __device__ __forceinline__ bool rle_entry_usable(int n, int form, long long slot_words, unsigned plane_words) {
@@ -500,13 +501,34 @@ __global__ __launch_bounds__(RLE_THREADS, V ? 8 : 5) void rle_rows_kernel(const 
     rle_rows_tile<1>(slots, slot_words, table, E, e_stride, status, s, H, W, j, x, dst);
 }
 
-// one thread per plane word: word q = x*HW64 + j of entry s, q_tiles workgroups per entry
+// The entry and the size of the image that own block `blk` of the plane kernel, the block's rank among the entry's q_tiles
+// blocks and the plane word the entry starts at: looked up in a group, plain arithmetic in a call of one.
+struct RlePlaneBlock {
+  int s, H, W, HW64;
+  unsigned tile;
+  size_t word0;
+};
+__device__ __forceinline__ RlePlaneBlock rle_plane_block(const RlePlaneOne& one, unsigned blk) {
+  const int s = (int)(blk / (unsigned)one.q_tiles);
+  return {s, one.H, one.W, one.HW64, blk % (unsigned)one.q_tiles, (size_t)s * (size_t)one.W * (size_t)one.HW64};
+}
+__device__ __forceinline__ RlePlaneBlock rle_plane_block(const RlePlaneGroup& grp, unsigned blk) {
+  const int g = rle_group_find(grp.blk0, grp.G, blk);
+  const int H = grp.H[g], W = grp.W[g], HW64 = (H + 63) / 64;
+  const unsigned Q = (unsigned)W * (unsigned)HW64, q_tiles = (Q + RLE_THREADS - 1) / RLE_THREADS;
+  const unsigned local = blk - grp.blk0[g], k = local / q_tiles;
+  return {grp.first[g] + (int)k, H, W, HW64, local % q_tiles, (size_t)grp.word0[g] + (size_t)k * Q};
+}
+
+// one thread per plane word: word q = x*HW64 + j of an entry, ceil(Q / 256) workgroups per entry.  GEO: RlePlaneOne or RlePlaneGroup.
+template <class GEO>
 __global__ __launch_bounds__(RLE_THREADS) void rle_plane_kernel(const uint32_t* __restrict__ slots, long long slot_words,
                                                                 const int32_t* __restrict__ table, const uint32_t* __restrict__ E,
-                                                                long long e_stride, const int32_t* __restrict__ status, int H,
-                                                                int W, int HW64, int q_tiles, unsigned long long* __restrict__ plane) {
-  const int s = (int)(blockIdx.x / (unsigned)q_tiles);
-  const unsigned q = (blockIdx.x % (unsigned)q_tiles) * RLE_THREADS + threadIdx.x;
+                                                                long long e_stride, const int32_t* __restrict__ status, const GEO geo,
+                                                                unsigned long long* __restrict__ plane) {
+  const RlePlaneBlock b = rle_plane_block(geo, blockIdx.x);
+  const int s = b.s, H = b.H, W = b.W, HW64 = b.HW64;
+  const unsigned q = b.tile * RLE_THREADS + threadIdx.x;
   const unsigned Q = (unsigned)W * (unsigned)HW64;
   if (q >= Q) return;
   unsigned long long c = 0;
@@ -515,7 +537,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_plane_kernel(const uint32_t* 
     c = rle_plane_word(slots + (size_t)s * (size_t)slot_words, table[(size_t)s * 4 + 1], table[(size_t)s * 4],
                        E + (size_t)s * (size_t)e_stride, plane_words, H, (int)(q / (unsigned)HW64), (int)(q % (unsigned)HW64));
   }
-  plane[(size_t)s * Q + q] = c;
+  plane[b.word0 + q] = c;
 }
 
 __global__ __launch_bounds__(RLE_THREADS) void rle_iou_kernel(const unsigned long long* __restrict__ pa,
@@ -541,12 +563,221 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_iou_kernel(const unsigned lon
   if (t == 0) { iu[(size_t)s * 2] = (long long)inter; iu[(size_t)s * 2 + 1] = (long long)uni; }
 }
 
+// ---- every mask of one set against every mask of another, image by image (hgl_rle_match_device).
+//
+//   E. rle_match_tile_kernel   a workgroup owns TA x TB = 32 x 64 pairs of one image.  Both sets' planes are in the workspace
+//      (A .. D above, the starts kernel with boxes); the tile's words are walked CHUNK = 32 at a time through LDS: As[32][32] and
+//      Bs[64][34] 64-bit words.  Lane l of a wave owns B row l and the wave 8 A rows, two words per read (ds_read_b128): the B
+//      rows are padded to a stride of 34 words = 68 banks, so the 16 lanes of every lane group of the read (their l mod 16 are all
+//      different) start on 16 different 4-bank slots -- unpadded, every lane would start on bank 0 -- and the A words are one
+//      address for the whole wave (a broadcast).  A plane word is read from memory once per tile; a pair costs two ANDs and two
+//      pop-counts per word.  The columns outside the intersection of (the union of the tile's A boxes) and (the
+//      union of its B boxes) are not walked: one side is all zeros there.
+//      A call of few tiles (64 x 64 masks are 2) splits every tile's word range over `splits` workgroups, each with a plane of
+//      partial counts of its own in the workspace: no atomics, and the sum below does not depend on who finished first.
+//   F. rle_match_best_kernel   one wave per entry of either set walks its row / column of the image's matrix, sums the partial
+//      counts, and keeps the partner with the largest I / D, ratios compared exactly (I1*D2 > I2*D1 in 64 bits), the lowest
+//      index on a tie.  The waves of set A write the caller's matrix on the way, every element once.
+struct RleBest {
+  long long I, D;
+  int idx;      // -1: none
+};
+__device__ __forceinline__ bool rle_best_better(const RleBest& a, const RleBest& b) {      // a takes b's place
+  if (a.idx < 0) return false;
+  if (b.idx < 0) return true;
+  const long long l = a.I * b.D, r = b.I * a.D;      // I < 2^31, D < 2^32
+  return l > r || (l == r && a.idx < b.idx);
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_match_tile_kernel(const unsigned long long* __restrict__ pa,
+                                                                     const unsigned long long* __restrict__ pb,
+                                                                     const int32_t* __restrict__ sa, const int32_t* __restrict__ sb,
+                                                                     const int32_t* __restrict__ boxa, const int32_t* __restrict__ boxb,
+                                                                     const RleMatch geo, int splits, long long pairs,
+                                                                     int32_t* __restrict__ partial) {
+  constexpr int TA = RLE_MATCH_TA, TB = RLE_MATCH_TB, CH = RLE_MATCH_CHUNK, PER = TA / 4;      // PER A rows per wave
+  __shared__ alignas(16) unsigned long long As[TA][CH];
+  __shared__ alignas(16) unsigned long long Bs[TB][CH + 2];      // + 2: rows stay 16-byte aligned and start 4 banks apart
+  __shared__ int xr[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const unsigned tile = blockIdx.x / (unsigned)splits, z = blockIdx.x % (unsigned)splits;
+  const int g = rle_group_find(geo.tile0, geo.G, tile);
+  const int fa = geo.first_a[g], fb = geo.first_b[g];
+  const int na = geo.first_a[g + 1] - fa, nb = geo.first_b[g + 1] - fb;
+  const unsigned tiles_b = ((unsigned)nb + TB - 1) / TB, local = tile - geo.tile0[g];
+  const int a0 = (int)(local / tiles_b) * TA, b0 = (int)(local % tiles_b) * TB;
+  const int HW64 = (geo.H[g] + 63) / 64;
+  const unsigned Q = (unsigned)geo.W[g] * (unsigned)HW64;
+  // the columns that hold a pixel of one of the tile's A masks and of one of its B masks
+  if (wave < 2) {
+    const int32_t* st = wave ? sb : sa;
+    const int32_t* bx = wave ? boxb : boxa;
+    const int e = wave ? b0 + lane : a0 + lane;
+    const bool in = wave ? e < nb : (lane < TA && e < na);
+    int x0 = 0x7fffffff, x1 = -1;
+    if (in) {
+      const size_t s = (size_t)(wave ? fb : fa) + e;
+      if (st[s * 4] != 2 && st[s * 4 + 1] > 0) { x0 = bx[s * 4]; x1 = bx[s * 4 + 2]; }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      const int o0 = __shfl_xor(x0, d, 64), o1 = __shfl_xor(x1, d, 64);
+      x0 = x0 < o0 ? x0 : o0;
+      x1 = x1 > o1 ? x1 : o1;
+    }
+    if (lane == 0) { xr[2 * wave] = x0; xr[2 * wave + 1] = x1; }
+  }
+  __syncthreads();
+  const int x0 = xr[0] > xr[2] ? xr[0] : xr[2], x1 = xr[1] < xr[3] ? xr[1] : xr[3];
+  const unsigned c_lo = x0 <= x1 ? (unsigned)x0 * HW64 : 0u, c_hi = x0 <= x1 ? (unsigned)(x1 + 1) * HW64 : 0u;      // <= Q
+  // this workgroup's share of them: whole chunks, the z-th of `splits` equal parts
+  const unsigned per = (((c_hi - c_lo + CH - 1) / CH + (unsigned)splits - 1) / (unsigned)splits) * CH;
+  const unsigned w_lo = c_lo + z * per < c_hi ? c_lo + z * per : c_hi, w_hi = c_hi - w_lo < per ? c_hi : w_lo + per;
+  const unsigned long long* PA = pa + (size_t)geo.word0_a[g];
+  const unsigned long long* PB = pb + (size_t)geo.word0_b[g];
+  unsigned acc[PER];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) acc[i] = 0;
+  // Staging: 8 rows of 32 words per pass, a row is 256 contiguous bytes.  The twelve loads of a chunk go to registers at clamped
+  // (always valid) addresses with nothing between them, so they are in flight together, and a chunk is loaded while the one
+  // before it is pop-counted; what lies outside the tile or the word range becomes 0 afterwards.
+  const int sr = t >> 5, sw = t & 31;
+  unsigned long long ra[TA / 8], rb[TB / 8];
+  auto fetch = [&](unsigned w0) {      // w0 < w_hi; a0 < na and b0 < nb: the tile exists
+    const unsigned w = w0 + sw;
+    const bool ok = w < w_hi;
+    const unsigned wc = ok ? w : w_hi - 1u;
+#pragma unroll
+    for (int i = 0; i < TA / 8; ++i) {
+      const int r = a0 + sr + 8 * i;
+      ra[i] = PA[(size_t)(r < na ? r : a0) * Q + wc];
+    }
+#pragma unroll
+    for (int i = 0; i < TB / 8; ++i) {
+      const int r = b0 + sr + 8 * i;
+      rb[i] = PB[(size_t)(r < nb ? r : b0) * Q + wc];
+    }
+  };
+  // The values are pinned in their registers, all twelve at once, where they are needed (after the pop-count of the chunk before):
+  // left to itself the compiler turns "outside ? 0 : load" back into a branch around every load and waits for each before it
+  // issues the next.
+  auto settle = [&](unsigned w0) {
+    const bool ok = w0 + sw < w_hi;
+#pragma unroll
+    for (int i = 0; i < TA / 8; ++i) asm volatile("" : "+v"(ra[i]));
+#pragma unroll
+    for (int i = 0; i < TB / 8; ++i) asm volatile("" : "+v"(rb[i]));
+#pragma unroll
+    for (int i = 0; i < TA / 8; ++i) ra[i] = (ok && a0 + sr + 8 * i < na) ? ra[i] : 0ull;
+#pragma unroll
+    for (int i = 0; i < TB / 8; ++i) rb[i] = (ok && b0 + sr + 8 * i < nb) ? rb[i] : 0ull;
+  };
+  if (w_lo < w_hi) fetch(w_lo);
+  for (unsigned w0 = w_lo; w0 < w_hi; w0 += CH) {
+    settle(w0);
+#pragma unroll
+    for (int i = 0; i < TA / 8; ++i) As[sr + 8 * i][sw] = ra[i];
+#pragma unroll
+    for (int i = 0; i < TB / 8; ++i) Bs[sr + 8 * i][sw] = rb[i];
+    __syncthreads();
+    if (w0 + CH < w_hi) fetch(w0 + CH);      // uniform over the workgroup; settled and stored after the barrier below
+#pragma unroll 4
+    for (int k = 0; k < CH; ++k) {
+      const unsigned long long b = Bs[lane][k];
+#pragma unroll
+      for (int i = 0; i < PER; ++i) acc[i] += __popcll(As[wave * PER + i][k] & b);
+    }
+    __syncthreads();      // the next chunk overwrites As / Bs
+  }
+  const int b = b0 + lane;
+  if (b >= nb) return;
+  int32_t* P = partial + (size_t)z * (size_t)pairs + geo.pair0[g];
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const int a = a0 + wave * PER + i;
+    if (a < na) P[(size_t)a * nb + b] = (int32_t)acc[i];      // <= H*W < 2^31; every element of every plane is written
+  }
+}
+
+// blocks 0 .. Sa-1: the entries of A over their rows; Sa .. Sa+Sb-1: the entries of B over their columns.  One wave each.
+// inter: the caller's matrices (null: not wanted), written by the waves of A: -1 in the row / column of an entry of code 2.
+__global__ __launch_bounds__(64) void rle_match_best_kernel(const int32_t* __restrict__ sa, const int32_t* __restrict__ sb,
+                                                            const uint8_t* __restrict__ crowd_b, const RleMatch geo, int splits,
+                                                            long long pairs, const int32_t* __restrict__ partial,
+                                                            int32_t* __restrict__ inter, int32_t* __restrict__ match_a,
+                                                            int32_t* __restrict__ match_b) {
+  const int Sa = geo.first_a[geo.G], lane = threadIdx.x;
+  const bool side_b = (int)blockIdx.x >= Sa;
+  const int s = side_b ? (int)blockIdx.x - Sa : (int)blockIdx.x;
+  const int g = rle_group_find(side_b ? geo.first_b : geo.first_a, geo.G, s);
+  const int fa = geo.first_a[g], fb = geo.first_b[g];
+  const int na = geo.first_a[g + 1] - fa, nb = geo.first_b[g + 1] - fb;
+  const int32_t* self = (side_b ? sb : sa) + (size_t)s * 4;
+  int32_t* out = (side_b ? match_b : match_a) + (size_t)s * 4;
+  const int code = self[0], area = self[1];
+  const int k = s - (side_b ? fb : fa), n = side_b ? na : nb;
+  int32_t* row = (!side_b && inter) ? inter + geo.off[g] + (size_t)k * nb : nullptr;
+  if (code == 2) {      // uniform over the wave
+    if (row)
+      for (int j = lane; j < n; j += 64) row[j] = -1;
+    if (lane == 0) { out[0] = 2; out[1] = 0; out[2] = -1; out[3] = 0; }
+    return;
+  }
+  const int32_t* P = partial + geo.pair0[g];
+  const bool crowd_self = side_b && crowd_b && crowd_b[s];
+  RleBest best = {0, 1, -1};
+  for (int j = lane; j < n; j += 64) {
+    const int32_t* other = side_b ? sa + (size_t)(fa + j) * 4 : sb + (size_t)(fb + j) * 4;
+    const bool dead = other[0] == 2;
+    const size_t e = side_b ? (size_t)j * nb + k : (size_t)k * nb + j;
+    long long I = 0;
+    for (int z = 0; z < splits; ++z) I += P[(size_t)z * (size_t)pairs + e];
+    if (row) row[j] = dead ? -1 : (int32_t)I;
+    if (dead || I <= 0) continue;      // a partner that holds no mask, or no common pixel
+    const long long area_a = side_b ? other[1] : area, area_b = side_b ? area : other[1];
+    const bool crowd = side_b ? crowd_self : (crowd_b && crowd_b[fb + j]);
+    const RleBest c = {I, crowd ? area_a : area_a + area_b - I, j};
+    if (rle_best_better(c, best)) best = c;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const RleBest o = {__shfl_xor(best.I, d, 64), __shfl_xor(best.D, d, 64), __shfl_xor(best.idx, d, 64)};
+    if (rle_best_better(o, best)) best = o;
+  }
+  if (lane == 0) { out[0] = code; out[1] = area; out[2] = best.idx; out[3] = (int32_t)best.I; }
+}
+
 // run starts of one set: [S] arrays of slot_words + 1 words
 size_t rle_starts_bytes(int S, long long slot_words) { return hgl_align_up((size_t)S * (size_t)(slot_words + 1) * sizeof(uint32_t), 256); }
 size_t rle_planes_bytes(int S, int H, int W) {
   return hgl_align_up((size_t)S * (size_t)W * (size_t)((H + 63) / 64) * sizeof(unsigned long long), 256);
 }
 size_t rle_status_bytes(int S) { return hgl_align_up((size_t)S * 4 * sizeof(int32_t), 256); }
+
+// the workspace of a match: per side run starts, status, boxes and planes; the planes of partial counts, one per split
+struct RleMatchWs {
+  size_t E[2], status[2], boxes[2], plane[2], partial, total;
+};
+RleMatchWs rle_match_ws(const RleMatchPlan& plan, int Sa, long long swa, int Sb, long long swb) {
+  RleMatchWs w;
+  size_t p = 0;
+  const int S[2] = {Sa, Sb};
+  const long long sw[2] = {swa, swb}, words[2] = {plan.words_a, plan.words_b};
+  for (int i = 0; i < 2; ++i) {
+    w.E[i] = p;
+    p += rle_starts_bytes(S[i], sw[i]);
+    w.status[i] = p;
+    p += rle_status_bytes(S[i]);
+    w.boxes[i] = p;
+    p += rle_status_bytes(S[i]);
+    w.plane[i] = p;
+    p += hgl_align_up((size_t)words[i] * sizeof(unsigned long long), 256);
+  }
+  w.partial = p;
+  p += hgl_align_up((size_t)plan.splits * (size_t)plan.pairs * sizeof(int32_t), 256);
+  w.total = p;
+  return w;
+}
 
 // the one decode: plan the images' geometry (-1), check the workspace (-3), two launches; boxes: null for none
 int rle_decode_launch(const char* name, const uint32_t* slots, long long slot_words, const int32_t* table, int S,
@@ -694,12 +925,81 @@ int hgl_rle_iou_device(const uint32_t* slots_a, long long slot_words_a, const in
   for (int i = 0; i < 2; ++i) {
     hipLaunchKernelGGL((rle_starts_kernel<false, RleOne>), dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
                        RleOne{H, W, HW64, 0, 0}, E[i], sw[i] + 1, status[i], (int32_t*)nullptr);
-    hipLaunchKernelGGL(rle_plane_kernel, dim3((unsigned)(S * q_tiles)), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
-                       (const uint32_t*)E[i], sw[i] + 1, (const int32_t*)status[i], H, W, HW64, q_tiles, plane[i]);
+    hipLaunchKernelGGL(rle_plane_kernel<RlePlaneOne>, dim3((unsigned)(S * q_tiles)), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
+                       (const uint32_t*)E[i], sw[i] + 1, (const int32_t*)status[i], RlePlaneOne{H, W, HW64, q_tiles}, plane[i]);
   }
   hipLaunchKernelGGL(rle_iou_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)plane[0],
                      (const unsigned long long*)plane[1], (const int32_t*)status[0], (const int32_t*)status[1], Q, (long long*)iu);
   return hgl_check_launch("rle_iou_device");
+}
+
+size_t hgl_rle_match_workspace_bytes(const int64_t* images_host, int G, int Sa, long long slot_words_a, int Sb, long long slot_words_b,
+                                     int want_inter) {
+  if (!images_host || slot_words_a < 0 || slot_words_b < 0) return 0;
+  RleMatchPlan plan;
+  char why[200];
+  // the caller's extents are the call's business: here only the geometry counts
+  if (rle_match_plan(images_host, G, Sa, Sb, -1, &plan, why, sizeof(why)) != 0) return 0;
+  (void)want_inter;      // the partial counts live in the workspace either way
+  return rle_match_ws(plan, Sa, slot_words_a, Sb, slot_words_b).total;
+}
+
+int hgl_rle_match_device(const uint32_t* slots_a, long long slot_words_a, const int32_t* table_a, int Sa, const uint32_t* slots_b,
+                         long long slot_words_b, const int32_t* table_b, int Sb, const int64_t* images_host, int G,
+                         const uint8_t* crowd_b, int32_t* inter, long long inter_elems, int32_t* match_a, int32_t* match_b, void* ws,
+                         size_t ws_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(images_host && Sa >= 0 && Sb >= 0 && slot_words_a >= 0 && slot_words_b >= 0 && (Sa == 0 || (slots_a && table_a && match_a)) &&
+                  (Sb == 0 || (slots_b && table_b && match_b)) && (!inter || inter_elems >= 0),
+              "rle_match_device: bad arguments");
+  RleMatchPlan plan;
+  char why[200];
+  if (rle_match_plan(images_host, G, Sa, Sb, inter ? inter_elems : -1, &plan, why, sizeof(why)) != 0) {
+    hgl_set_error("rle_match_device: %s", why);
+    return HGL_EINVAL;
+  }
+  const RleMatchWs w = rle_match_ws(plan, Sa, slot_words_a, Sb, slot_words_b);
+  if (w.total > 0 && (!ws || ws_bytes < w.total)) {
+    hgl_set_error("rle_match_device: workspace too small");
+    return HGL_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)ws;
+  const uint32_t* slots[2] = {slots_a, slots_b};
+  const int32_t* table[2] = {table_a, table_b};
+  const long long sw[2] = {slot_words_a, slot_words_b}, blocks[2] = {plan.blocks_a, plan.blocks_b};
+  const int S[2] = {Sa, Sb};
+  const RlePlaneGroup* pg[2] = {&plan.pa, &plan.pb};
+  uint32_t* E[2];
+  int32_t *status[2], *boxes[2];
+  unsigned long long* plane[2];
+  // a side, a kernel or a matrix without an element has no launch; otherwise six launches whatever G and the sizes are
+  for (int i = 0; i < 2; ++i) {
+    E[i] = (uint32_t*)(base + w.E[i]);
+    status[i] = (int32_t*)(base + w.status[i]);
+    boxes[i] = (int32_t*)(base + w.boxes[i]);
+    plane[i] = (unsigned long long*)(base + w.plane[i]);
+    if (S[i] == 0) continue;
+    RleGroup grp;      // what the starts kernel reads of it: the sizes and the first entries
+    memset(&grp, 0, sizeof(grp));
+    grp.G = G;
+    for (int g = 0; g < G; ++g) { grp.H[g] = pg[i]->H[g]; grp.W[g] = pg[i]->W[g]; grp.first[g] = pg[i]->first[g]; }
+    hipLaunchKernelGGL((rle_starts_kernel<true, RleGroup>), dim3((unsigned)S[i]), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
+                       grp, E[i], sw[i] + 1, status[i], boxes[i]);
+    hipLaunchKernelGGL(rle_plane_kernel<RlePlaneGroup>, dim3((unsigned)blocks[i]), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
+                       (const uint32_t*)E[i], sw[i] + 1, (const int32_t*)status[i], *pg[i], plane[i]);
+  }
+  int32_t* partial = (int32_t*)(base + w.partial);
+  if (plan.tiles > 0)      // tiles * splits <= max(tiles, RLE_MATCH_BLOCKS + tiles) < 2^31 + 1024
+    hipLaunchKernelGGL(rle_match_tile_kernel, dim3((unsigned)(plan.tiles * plan.splits)), dim3(RLE_THREADS), 0, st,
+                       (const unsigned long long*)plane[0], (const unsigned long long*)plane[1], (const int32_t*)status[0],
+                       (const int32_t*)status[1], (const int32_t*)boxes[0], (const int32_t*)boxes[1], plan.m, plan.splits, plan.pairs,
+                       partial);
+  if (Sa + Sb > 0)
+    hipLaunchKernelGGL(rle_match_best_kernel, dim3((unsigned)Sa + (unsigned)Sb), dim3(64), 0, st, (const int32_t*)status[0],
+                       (const int32_t*)status[1], crowd_b, plan.m, plan.splits, plan.pairs, (const int32_t*)partial, inter, match_a,
+                       match_b);
+  return hgl_check_launch("rle_match_device");
 }
 
 }  // extern "C"

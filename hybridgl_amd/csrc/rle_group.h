@@ -1,6 +1,7 @@
 // The geometry of the RLE entries (csrc/rle.hip): the tiling of an image, shared by the encoder and the decoder, and what the host
-// works out of a decode call's image rows and hands to the two decoder kernels by value.  Plain C++ without a HIP construct:
-// rle.hip includes it, and so does the sanitizer harness tests/native/rle_group_sanitize.cpp.
+// works out of a decode call's image rows (rle_group_plan) and of a match call's (rle_match_plan) and hands to the kernels by
+// value.  Plain C++ without a HIP construct: rle.hip includes it, and so do the sanitizer harnesses
+// tests/native/rle_group_sanitize.cpp and tests/native/rle_match_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
 #include <stdint.h>
@@ -86,5 +87,117 @@ static inline int rle_group_plan(const int64_t* images, int G, int S, uintptr_t 
 struct RleOne {
   int H, W, HW64, col_tiles, row_tiles;      // rle_tiles' (the rows kernel reads the last two; 0 for a caller of the starts kernel alone)
 };
+
+// What a block of the plane kernel needs of the image that owns it (hgl_rle_iou_device: one image, hgl_rle_match_device: a
+// group): the entries of an image lie back to back in the plane buffer, W * HW64 words each, 256 words per block.
+struct RlePlaneOne {
+  int H, W, HW64, q_tiles;
+};
+struct RlePlaneGroup {
+  int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
+  int first[RLE_GROUP_MAX];                     // the image's first entry
+  unsigned blk0[RLE_GROUP_MAX];                 // its first block of the plane kernel (non-decreasing, blk0[0] = 0)
+  unsigned word0[RLE_GROUP_MAX];                // the plane word its first entry starts at
+  int G;
+};
+
+// ---- hgl_rle_match_device: every mask of set A against every mask of set B, image by image.  A workgroup of the tile kernel
+// owns RLE_MATCH_TA x RLE_MATCH_TB pairs of one image and walks the plane words RLE_MATCH_CHUNK at a time.
+constexpr int RLE_MATCH_TA = 32, RLE_MATCH_TB = 64, RLE_MATCH_CHUNK = 32;
+// A call with few tiles splits every tile's word range over `splits` workgroups (a 64 x 64 match is 2 tiles: alone they would
+// walk 200 chunks each, one after the other, on 2 of the device's CUs); each writes its partial counts to a plane of its own.
+constexpr int RLE_MATCH_BLOCKS = 1024, RLE_MATCH_SPLITS_MAX = 32;
+
+struct RleMatch {
+  long long off[RLE_GROUP_MAX];                           // element offset of the image's [na, nb] matrix
+  int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
+  int first_a[RLE_GROUP_MAX + 1], first_b[RLE_GROUP_MAX + 1];      // first entries; [G] = Sa / Sb
+  unsigned word0_a[RLE_GROUP_MAX], word0_b[RLE_GROUP_MAX];         // the plane word the image's first entry starts at
+  unsigned tile0[RLE_GROUP_MAX];                          // the image's first tile (non-decreasing, tile0[0] = 0)
+  long long pair0[RLE_GROUP_MAX];                         // the image's first element in a plane of partial counts
+  int G;
+};
+
+struct RleMatchPlan {
+  RleMatch m;
+  RlePlaneGroup pa, pb;
+  long long tiles, blocks_a, blocks_b;      // grid sizes: tile kernel, plane kernel of either side
+  long long words_a, words_b;               // 64-bit plane words of either side
+  long long pairs;                          // sum of na*nb: the elements of one plane of partial counts
+  int splits;                               // workgroups per tile, 1 .. RLE_MATCH_SPLITS_MAX: ceil(RLE_MATCH_BLOCKS / tiles)
+};
+
+// images [G,5] = (H, W, first A entry, first B entry, element offset of the image's matrix) -> *plan; 0, or -1 with the reason
+// in why.  inter_elems >= 0: the caller's matrix buffer holds that many elements, every extent [off, off + na*nb) must lie inside
+// and no two may overlap.  inter_elems < 0: no matrix is wanted and column 4 is not read.  The partial counts of the tile kernel
+// are always packed image after image (pair0, plan->pairs elements per split).  Checked besides: 1 <= G <= 64; Sa, Sb >= 0; H*W < 2^31; entries from 0 to Sa / Sb without
+// a step back; Sa + Sb < 2^31; fewer than 2^31 tiles and plane blocks, fewer than 2^32 plane words per side.
+static inline int rle_match_plan(const int64_t* images, int G, int Sa, int Sb, long long inter_elems, RleMatchPlan* plan, char* why,
+                                 size_t why_cap) {
+#define RLE_MATCH_REQUIRE(cond, ...)        \
+  do {                                      \
+    if (!(cond)) {                          \
+      snprintf(why, why_cap, __VA_ARGS__);  \
+      return -1;                            \
+    }                                       \
+  } while (0)
+  RLE_MATCH_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
+  RLE_MATCH_REQUIRE(Sa >= 0 && Sb >= 0 && (long long)Sa + Sb < (1ll << 31), "bad set sizes %d, %d (Sa + Sb must be < 2^31)", Sa, Sb);
+  memset(plan, 0, sizeof(*plan));
+  RleMatch* m = &plan->m;
+  m->G = plan->pa.G = plan->pb.G = G;
+  const bool packed = inter_elems < 0;
+  long long lo[RLE_GROUP_MAX], hi[RLE_GROUP_MAX];      // the element extent [lo, hi) of every image's matrix
+  for (int g = 0; g < G; ++g) {
+    const int64_t* r = images + 5 * g;
+    const long long H = r[0], W = r[1], ea = r[2], eb = r[3];
+    const long long ea_next = g + 1 < G ? r[5 + 2] : (long long)Sa, eb_next = g + 1 < G ? r[5 + 3] : (long long)Sb;
+    RLE_MATCH_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
+                      "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
+    RLE_MATCH_REQUIRE(ea >= 0 && ea <= ea_next && ea_next <= (long long)Sa && (g > 0 || ea == 0),
+                      "image %d: A entries %lld .. %lld (rows must not decrease, from 0 to Sa = %d)", g, ea, ea_next, Sa);
+    RLE_MATCH_REQUIRE(eb >= 0 && eb <= eb_next && eb_next <= (long long)Sb && (g > 0 || eb == 0),
+                      "image %d: B entries %lld .. %lld (rows must not decrease, from 0 to Sb = %d)", g, eb, eb_next, Sb);
+    const long long na = ea_next - ea, nb = eb_next - eb, n = na * nb;      // < 2^62
+    const long long o = packed ? 0 : r[4];
+    if (!packed) {
+      RLE_MATCH_REQUIRE(o >= 0 && o <= inter_elems && n <= inter_elems - o,
+                        "image %d: elements %lld .. +%lld lie outside the %lld of inter", g, o, n, inter_elems);
+      lo[g] = o;
+      hi[g] = o + n;
+      for (int f = 0; f < g; ++f)
+        RLE_MATCH_REQUIRE(lo[g] == hi[g] || lo[f] == hi[f] || hi[f] <= lo[g] || hi[g] <= lo[f],
+                          "the matrices of images %d and %d overlap", f, g);
+    }
+    const long long HW64 = (H + 63) / 64, Q = W * HW64, q_tiles = (Q + 255) / 256;      // Q <= H*W < 2^31
+    m->off[g] = o;
+    m->H[g] = plan->pa.H[g] = plan->pb.H[g] = (int)H;
+    m->W[g] = plan->pa.W[g] = plan->pb.W[g] = (int)W;
+    m->first_a[g] = plan->pa.first[g] = (int)ea;
+    m->first_b[g] = plan->pb.first[g] = (int)eb;
+    m->word0_a[g] = plan->pa.word0[g] = (unsigned)plan->words_a;
+    m->word0_b[g] = plan->pb.word0[g] = (unsigned)plan->words_b;
+    m->tile0[g] = (unsigned)plan->tiles;
+    m->pair0[g] = plan->pairs;
+    plan->pa.blk0[g] = (unsigned)plan->blocks_a;
+    plan->pb.blk0[g] = (unsigned)plan->blocks_b;
+    plan->pairs += n;
+    plan->words_a += na * Q;
+    plan->words_b += nb * Q;
+    plan->blocks_a += na * q_tiles;
+    plan->blocks_b += nb * q_tiles;
+    plan->tiles += ((na + RLE_MATCH_TA - 1) / RLE_MATCH_TA) * ((nb + RLE_MATCH_TB - 1) / RLE_MATCH_TB);
+    RLE_MATCH_REQUIRE(plan->words_a < (1ll << 32) && plan->words_b < (1ll << 32),
+                      "too many plane words for one call (sum of n*W*ceil(H/64) must be < 2^32 per side)");
+    RLE_MATCH_REQUIRE(plan->blocks_a < (1ll << 31) && plan->blocks_b < (1ll << 31) && plan->tiles < (1ll << 31),
+                      "too many entries (%d, %d) for one launch", Sa, Sb);
+  }
+  m->first_a[G] = Sa;
+  m->first_b[G] = Sb;
+  const long long want = plan->tiles > 0 ? (RLE_MATCH_BLOCKS + plan->tiles - 1) / plan->tiles : 1;
+  plan->splits = (int)(want < 1 ? 1 : (want > RLE_MATCH_SPLITS_MAX ? RLE_MATCH_SPLITS_MAX : want));
+  return 0;
+#undef RLE_MATCH_REQUIRE
+}
 
 #endif  // HGL_RLE_GROUP_H

@@ -98,6 +98,10 @@ def default_argument_parser():
     p.add_argument("--proposals_dir", default="", metavar="DIR",
                    help="with --real: take every image's proposals from a store --save_proposals (or SAM's amg.py) wrote instead of "
                         "running SAM: no SAM model is built, no checkpoint read; an image the store lacks is an error")
+    p.add_argument("--proposal_ceiling", default="", metavar="OUT",
+                   help="with --proposals_dir: write the proposal ceiling of the store -- per sentence the stored proposal of the "
+                        "largest IoU against the ground truth, {oIoU, mIoU, cum, n_sentences} as the sweep reports it -- here and "
+                        "exit; no SAM, CLIP or GEM model is built (the dataset flags and --proposal_cap as in the run)")
     p.add_argument("--sweep", default="", metavar="SPEC",
                    help="score every ref under a grid of the tail's hyper-parameters in the same pass, e.g. "
                         "'r=0.3,0.5,0.7;alpha=0:1:0.1;k1=3;k2=6': an axis is a value list or lo:hi:step (hi included), an axis "
@@ -290,15 +294,16 @@ AMG_DEFAULTS = {   # Hybridgl_main.py:67-73 / Hybridgl_main_PhraseCut.py:56-62
 }
 
 
-def resolve_defaults(args):
-    """fill the flags left at None with the configuration of the reference script that --dataset selects"""
+def resolve_defaults(args, loop=True):
+    """fill the flags left at None with the configuration of the reference script that --dataset selects; loop=False: for a
+    branch that runs no evaluation loop (the loop's own flag combinations are not checked)"""
     for k, v in AMG_DEFAULTS["phrasecut" if args.dataset == "phrasecut" else "refer"].items():
         if getattr(args, k, None) is None:
             setattr(args, k, v)
     if getattr(args, "split", None) is None:
         # Hybridgl_main_PhraseCut.py:42 evaluates PhraseCutDataset(split='test'); the REFER scripts their val split
         args.split = "test" if args.dataset == "phrasecut" else "val"
-    if getattr(args, "group", None) is not None and args.group <= 1 and getattr(args, "proposal_cap", 0):
+    if loop and getattr(args, "group", None) is not None and args.group <= 1 and getattr(args, "proposal_cap", 0):
         # the ref-by-ref path (HybridGLPipeline.step) keeps every proposal: silently ignoring the cap would give other results
         # than the grouped loop whenever the cap binds
         raise SystemExit("--proposal_cap applies to the grouped loop only: use --group >= 2 with it (or drop the cap)")
@@ -497,6 +502,48 @@ def score_masks_main(args, dev):
     return m
 
 
+def proposal_ceiling(args, dev):
+    """--proposals_dir DIR --proposal_ceiling OUT: the ceiling of a proposal store against the dataset's ground truth from the
+    files alone -- no model is built, no checkpoint read.  Jobs, items and targets are those of score_masks(); the stored runs
+    meet the encoded targets on the device (proposals.ceiling: integer counts, exact).  Returns ({"oIoU", "mIoU", "cum",
+    "n_sentences"}: the "ceiling" block of HybridGLPipeline.sweep_metrics() for a run fed from the same store, rows [n,5])."""
+    from . import dist as D
+    from . import proposals as P
+    resolve_defaults(args, loop=False)
+    check_proposal_flags(args)
+    _, jobs, make = dataset_items(args, dev, 0, 1, sam_img_size=0, gem=False)
+
+    def targets():
+        for i in jobs:
+            ref = make(i)
+            if ref is None:
+                continue
+            index = ref.index if ref.index is not None else i
+            for j, sent in enumerate(ref.sentences):
+                yield (index, j), ref.image_id, (sent.target if sent.target is not None else ref.target)
+
+    rows = P.ceiling(args.proposals_dir, targets(), cap=getattr(args, "proposal_cap", 0) or None, device=dev,
+                     group=max(int(getattr(args, "group", 16) or 16), 1))
+    cm = D.metrics_from_rows(rows[:, [0, 1, 3, 4, 3, 4]])
+    return {"oIoU": cm["oIoU"], "mIoU": cm["mIoU"], "cum": cm["cum"][:2], "n_sentences": cm["n_sentences"]}, rows
+
+
+def proposal_ceiling_main(args, dev):
+    """the --proposal_ceiling branch of main(): the file and one line"""
+    import json
+    if not getattr(args, "proposals_dir", ""):
+        raise SystemExit("--proposal_ceiling needs --proposals_dir: the store whose ceiling is asked for")
+    try:
+        c, rows = proposal_ceiling(args, dev)
+    except ValueError as e:
+        raise SystemExit(f"hybridgl_amd.main: {e}")
+    with open(args.proposal_ceiling, "w") as f:
+        json.dump(c, f, indent=1)
+    print(f"proposal ceiling of {args.proposals_dir} over {c['n_sentences']} sentences (no model built): oIoU {c['oIoU']:.2f} "
+          f"mIoU {c['mIoU']:.2f}")
+    return c
+
+
 def save_masks(pipe, directory, rank=0):
     """--save_masks: DIR/masks.rank{rank}.jsonl, one JSON line per sentence this rank scored, keyed like dist.ROW_FIELDS:
     {"index": dataset position, "sentence": sentence number, "size": [H, W], "pure", "final": the winning masks (pure CLIP /
@@ -605,6 +652,11 @@ def main(args):
             raise SystemExit("--score_masks runs on one rank: start it without a launcher (world size 1)")
         torch.cuda.set_device(dev)
         return score_masks_main(args, dev)
+    if getattr(args, "proposal_ceiling", ""):      # likewise: the store's files and ground truth only
+        if world > 1:
+            raise SystemExit("--proposal_ceiling runs on one rank: start it without a launcher (world size 1)")
+        torch.cuda.set_device(dev)
+        return proposal_ceiling_main(args, dev)
     cores = D.pin_rank_to_cores(local_rank, int(os.environ.get("LOCAL_WORLD_SIZE", world)))   # launch + loader threads of a rank on its own cores
     D.size_host_threads(cores, args.workers)
     torch.cuda.set_device(dev)

@@ -509,6 +509,63 @@ def rle_iou(slots_a, table_a, slots_b, table_b, H, W):
     return iu
 
 
+def rle_match_layout(sizes, counts_a, counts_b):
+    """(images [G,5] int64 = H, W, first A entry, first B entry, element offset; total elements) of a group's [na, nb] matrices
+    packed back to back"""
+    import numpy as np
+    if not (len(sizes) == len(counts_a) == len(counts_b)):
+        raise ValueError(f"rle_match_layout: {len(sizes)} sizes, {len(counts_a)} and {len(counts_b)} counts")
+    images = np.zeros((len(sizes), 5), dtype=np.int64)
+    ea = eb = o = 0
+    for g, ((H, W), na, nb) in enumerate(zip(sizes, counts_a, counts_b)):
+        if int(na) < 0 or int(nb) < 0:
+            raise ValueError(f"rle_match_layout: image {g} has {na} and {nb} entries")
+        images[g] = (int(H), int(W), ea, eb, o)
+        ea += int(na)
+        eb += int(nb)
+        o += int(na) * int(nb)
+    return images, o
+
+
+def rle_match(slots_a, table_a, slots_b, table_b, sizes, counts_a, counts_b, crowd_b=None, matrix=True):
+    """Every mask of set A against every mask of set B, image by image (hgl_rle_match_device on the current stream, no
+    synchronisation): the entries of either set (what rle_encode or rle_pack returns) belong to G = len(sizes) <= 64 images,
+    counts_a[g] / counts_b[g] consecutive entries of sizes[g] = (H, W); an image may own none on either side.  Returns
+    (inter: a list of G int32 views [na_g, nb_g] of one buffer, |a & b| of every pair, -1 in the row / column of an entry that
+    holds no mask -- or None with matrix=False; match_a [Sa,4] int32 = (code, area, best, I_best); match_b [Sb,4] likewise).
+    best: the index within the image's other set of the partner with the largest I / D, D = area(a) where crowd_b[b] is set
+    and the union elsewhere, compared exactly, the lowest index on a tie, -1 when nothing intersects (include/hybridgl.h).
+    crowd_b: bool / uint8 device tensor [Sb] or None.  No mask becomes pixels."""
+    lib = _lib.load()
+    ap, asw, atp, Sa = _rle_set(slots_a, table_a, "rle_match a")
+    bp, bsw, btp, Sb = _rle_set(slots_b, table_b, "rle_match b")
+    if slots_a.device != slots_b.device:
+        raise ValueError("rle_match: the two sets live on different devices")
+    images, total = rle_match_layout(sizes, counts_a, counts_b)
+    G = len(images)
+    if int(sum(int(n) for n in counts_a)) != Sa or int(sum(int(n) for n in counts_b)) != Sb:
+        raise ValueError(f"rle_match: counts sum to {sum(counts_a)} and {sum(counts_b)}, the sets have {Sa} and {Sb} entries")
+    dev = slots_a.device
+    cp = None
+    if crowd_b is not None:
+        if crowd_b.numel() != Sb:
+            raise ValueError(f"crowd_b: expected {Sb} flags, got {crowd_b.numel()}")
+        cp, crowd_b = _u8(crowd_b, "crowd_b")
+    match = torch.empty((Sa + Sb, 4), dtype=torch.int32, device=dev)
+    match_a, match_b = match[:Sa], match[Sa:]
+    flat = torch.empty(total, dtype=torch.int32, device=dev) if matrix else None
+    inter = [flat[int(o):int(o) + int(na) * int(nb)].view(int(na), int(nb))
+             for (_, _, _, _, o), na, nb in zip(images, counts_a, counts_b)] if matrix else None
+    if Sa + Sb == 0:
+        return inter, match_a, match_b
+    need = lib.hgl_rle_match_workspace_bytes(images.ctypes.data, G, Sa, asw, Sb, bsw, int(matrix))
+    ws = workspace(need, dev, "rle")
+    check(lib.hgl_rle_match_device(ap, asw, atp, Sa, bp, bsw, btp, Sb, images.ctypes.data, G, cp,
+                                   flat.data_ptr() if matrix else None, total, match_a.data_ptr(), match_b.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), _stream()), "hgl_rle_match_device")
+    return inter, match_a, match_b
+
+
 def score_sentence(hybrid, sentence_feat, noun_phrase_feat, other_noun_feats, boxes, gem_score,
                    logit_scale=100.0, r=0.5, k1=3, k2=6, alpha=0.6, relaword="none", has_other_nouns=False):
     """Per-sentence tail (Hybridgl_main.py:153-196,225-228).

@@ -15,7 +15,11 @@ ProposalRecorder  wraps a generator that speaks group_begin / group_cleanup / gr
                   written once the copies have completed, at later group boundaries and in flush().  Nothing waits in the loop.
 StoredProposals   answers the same three calls (and generate_device for HybridGLPipeline.step) from a store: the runs are
                   parsed and packed on the loader threads (prefetch), one upload and one ops.rle_decode_group per group bring
-                  them back as pixels with their boxes.  It never runs SAM: a missing or inconsistent file is a ValueError."""
+                  them back as pixels with their boxes.  It never runs SAM: a missing or inconsistent file is a ValueError.
+compare           two stores image by image, every mask of one against every mask of the other (ops.rle_match on the runs: no
+                  mask becomes pixels): did SAM's set move, or only the scoring?
+                      python -m hybridgl_amd.proposals compare DIR_A DIR_B [--iou LIST] [--json OUT]
+ceiling           the best proposal of a store per target -- the bound no scoring of these proposals exceeds -- without CLIP."""
 import collections
 import json
 import os
@@ -78,6 +82,13 @@ class ProposalStore:
 
     def has(self, image_id):
         return os.path.exists(self.path(image_id))
+
+    def image_ids(self):
+        """the ids of the images the directory holds a file for, sorted: integers where the name is a number (the datasets'
+        ids), the name itself otherwise (a store the upstream script wrote from file names)"""
+        names = [n[:-5] for n in os.listdir(self.directory) if n.endswith(".json") and n != "meta.json"]
+        ids = [int(n) if n.isdigit() and str(int(n)) == n else n for n in names]
+        return sorted(ids, key=lambda v: (isinstance(v, str), v))
 
     def records(self, image_id):
         """the stored list, as generate() returned it in coco_rle mode; ValueError naming the image for a missing or garbled file"""
@@ -436,3 +447,237 @@ class StoredProposals:
         if fixed_n is not None:
             raise ValueError("StoredProposals: fixed_n is the synthetic benchmark's switch; a store hands out what it holds")
         return self.generate_group([image], [image_id])[0]
+
+
+def _store(x):
+    return x if isinstance(x, ProposalStore) else ProposalStore(x)
+
+
+def _image_runs(store, image_id, cap=None):
+    """(size (H, W) or None for an image without a record, the run lists of its first `cap` records)"""
+    from .sam import rle_counts_from_string
+    recs = store.records(image_id)
+    if cap:
+        recs = recs[:int(cap)]
+    size, runs = None, []
+    for k, r in enumerate(recs):
+        hw = tuple(int(v) for v in r["segmentation"]["size"])
+        if size is None:
+            size = hw
+        if hw != size or hw[0] <= 0 or hw[1] <= 0 or hw[0] * hw[1] >= 1 << 31:
+            raise ValueError(f"proposal store {store.directory}: image {image_id} entry {k}: size {list(hw)} "
+                             + (f"differs from entry 0's {list(size)}" if hw != size else "is no image size"))
+        try:
+            runs.append(rle_counts_from_string(r["segmentation"]["counts"]))
+        except Exception as e:
+            raise ValueError(f"proposal store {store.directory}: image {image_id} entry {k}: bad counts string ({e})") from None
+    return size, runs
+
+
+def _pack(runs, device):
+    """run lists -> (slots, table) on the device, as predictions._pack packs a set's strings (the sizes ride in the call)"""
+    return ops.rle_pack(runs, 1, 1, device=device)
+
+
+def _check_decoded(store, ids, counts, match):
+    """every entry of `match` [S,4] (host) must have decoded with code 0"""
+    e = 0
+    for iid, n in zip(ids, counts):
+        bad = np.flatnonzero(match[e:e + n, 0] != 0)
+        if len(bad):
+            raise ValueError(f"proposal store {store.directory}: image {iid} entry {int(bad[0])}: its counts do not decode to a mask "
+                             f"of the stated size (status {int(match[e + bad[0], 0])})")
+        e += n
+
+
+def compare(a, b, thresholds=(0.5, 0.75, 0.9), device=None, group=16):
+    """Two proposal stores (ProposalStore objects or directories), image by image: every mask of A's list against every mask of
+    B's (ops.rle_match, `group` images per call; the strings' runs cross the bus, no mask becomes pixels).  The lists may differ
+    in length and order.  Returns {"summary": ..., "per_image": {image_id: ...}}; per image: n_a, n_b; identical = the masks of A
+    whose best partner in B is the same mask (I == area_a == area_b); at_iou = {t: [masks of A, masks of B with a partner at IoU
+    >= t]} per threshold; mean_iou_a / min_iou_a / mean_iou_b / min_iou_b over each side's best IoU (None for an empty list; a
+    mask without an intersecting partner, an empty mask included, counts 0).  The summary sums the counts, takes mean and
+    minimum over all masks, and lists only_in_a, only_in_b (images one store lacks) and size_mismatch (images whose stores
+    state different sizes: listed, not compared)."""
+    a, b = _store(a), _store(b)
+    thresholds = [float(t) for t in thresholds]
+    ids_a, ids_b = a.image_ids(), b.image_ids()
+    in_b = set(ids_b)
+    in_a = set(ids_a)
+    common = [i for i in ids_a if i in in_b]
+    per_image, size_mismatch = {}, []
+
+    def chunks():
+        """the common images whose sizes agree, `group` at a time: only a chunk's run lists are held at once"""
+        chunk = []
+        for iid in common:
+            (size_a, runs_a), (size_b, runs_b) = _image_runs(a, iid), _image_runs(b, iid)
+            if size_a is not None and size_b is not None and size_a != size_b:
+                size_mismatch.append(iid)
+                continue
+            chunk.append((iid, size_a or size_b or (1, 1), runs_a, runs_b))
+            if len(chunk) >= max(int(group), 1):
+                yield chunk
+                chunk = []
+        if chunk:
+            yield chunk
+
+    def side(best_iou):
+        n = len(best_iou)
+        return {"n": n, "at": [int((best_iou >= t).sum()) for t in thresholds], "sum": float(best_iou.sum()),
+                "min": float(best_iou.min()) if n else None}
+
+    for chunk in chunks():
+        ca, cb = [len(c[2]) for c in chunk], [len(c[3]) for c in chunk]
+        sa, ta = _pack([r for c in chunk for r in c[2]], device)
+        sb, tb = _pack([r for c in chunk for r in c[3]], device)
+        _, ma, mb = ops.rle_match(sa, ta, sb, tb, [c[1] for c in chunk], ca, cb, matrix=False)
+        ma, mb = ma.cpu().numpy().astype(np.int64), mb.cpu().numpy().astype(np.int64)
+        _check_decoded(a, [c[0] for c in chunk], ca, ma)
+        _check_decoded(b, [c[0] for c in chunk], cb, mb)
+        ea = eb = 0
+        for (iid, _, _, _), na, nb in zip(chunk, ca, cb):
+            xa, xb = ma[ea:ea + na], mb[eb:eb + nb]
+
+            def best_iou(x, other):
+                has = x[:, 2] >= 0
+                partner = other[np.where(has, x[:, 2], 0), 1] if len(other) else np.zeros(len(x), np.int64)
+                union = x[:, 1] + partner - x[:, 3]
+                return np.where(has, x[:, 3] / np.maximum(union, 1), 0.0), has & (x[:, 3] == x[:, 1]) & (x[:, 3] == partner)
+
+            iou_a, same = best_iou(xa, xb)
+            iou_b, _ = best_iou(xb, xa)
+            per_image[iid] = {"a": side(iou_a), "b": side(iou_b), "identical": int(same.sum())}
+            ea += na
+            eb += nb
+
+    def report(rows):
+        """the public shape of one image's (or all images') figures from the sides' sums"""
+        na, nb = sum(r["a"]["n"] for r in rows), sum(r["b"]["n"] for r in rows)
+        mins = {s: [r[s]["min"] for r in rows if r[s]["n"]] for s in "ab"}
+        return {"n_a": na, "n_b": nb, "identical": sum(r["identical"] for r in rows),
+                "at_iou": {t: [sum(r["a"]["at"][k] for r in rows), sum(r["b"]["at"][k] for r in rows)] for k, t in enumerate(thresholds)},
+                "mean_iou_a": sum(r["a"]["sum"] for r in rows) / na if na else None, "min_iou_a": min(mins["a"]) if mins["a"] else None,
+                "mean_iou_b": sum(r["b"]["sum"] for r in rows) / nb if nb else None, "min_iou_b": min(mins["b"]) if mins["b"] else None}
+
+    summary = report(list(per_image.values()))
+    summary.update({"n_images": len(per_image), "only_in_a": [i for i in ids_a if i not in in_b],
+                    "only_in_b": [i for i in ids_b if i not in in_a], "size_mismatch": size_mismatch})
+    return {"summary": summary, "per_image": {iid: report([r]) for iid, r in per_image.items()}}
+
+
+def ceiling(store, targets, cap=None, device=None, group=16):
+    """The best proposal of a store per target, without CLIP or GEM: rows [n,5] int64 = (index, sentence, proposal, I, U), the
+    format and the rule of HybridGLPipeline.ceiling_rows() -- per target the proposal of its image with the largest I / U,
+    compared exactly, the lowest index on a tie (proposal 0 with I = 0 when none intersects); an image without a proposal
+    contributes no row, as the loop skips its refs.  targets: an iterable of ((index, sentence), image_id, mask [H,W] bool /
+    uint8 device tensor) in any order; they are encoded on the device (ops.rle_encode, as predictions.score encodes them) and
+    met by the stored runs in ops.rle_match, `group` images per call.  device: where to (None: where the targets are).  cap:
+    the first `cap` records of every image, as StoredProposals(cap=).  Rows are sorted by (index, sentence)."""
+    store = _store(store)
+    rows, runs_of, seen = [], {}, set()
+
+    def flush(items):
+        by_image = collections.OrderedDict()
+        for key, iid, t in items:
+            by_image.setdefault(iid, []).append((key, t))
+        ids, sizes, ca, cb, runs, enc = [], [], [], [], [], []
+        for iid, its in by_image.items():
+            H, W = (int(v) for v in its[0][1].shape[-2:])
+            size, r = runs_of[iid]
+            if not r:
+                continue
+            if size != (H, W) or any(tuple(int(v) for v in t.shape[-2:]) != (H, W) for _, t in its):
+                raise ValueError(f"proposal store {store.directory}: image {iid}: size {list(size)} differs from its target's {[H, W]}")
+            gt = torch.stack([t.reshape(H, W).to(torch.uint8) if t.dtype != torch.bool else t.reshape(H, W).view(torch.uint8)
+                              for _, t in its])
+            enc.append(ops.rle_encode(gt if device is None else gt.to(device)))
+            ids.append(iid)
+            sizes.append((H, W))
+            ca.append(len(r))
+            cb.append(len(its))
+            runs += r
+        if not ids:
+            return
+        dev = enc[0][0].device
+        sw = max(int(s.shape[1]) for s, _ in enc)
+        sb = torch.cat([torch.cat([s, s.new_zeros((s.shape[0], sw - s.shape[1]))], 1) for s, _ in enc]).contiguous()
+        tb = torch.cat([t for _, t in enc]).contiguous()
+        sa, ta = _pack(runs, dev)
+        _, ma, mb = ops.rle_match(sa, ta, sb, tb, sizes, ca, cb, matrix=False)
+        ma, mb = ma.cpu().numpy().astype(np.int64), mb.cpu().numpy().astype(np.int64)
+        _check_decoded(store, ids, ca, ma)
+        if (mb[:, 0] != 0).any():      # ops.rle_encode with its default slot never loses a mask
+            raise RuntimeError(f"ceiling: target {int(np.flatnonzero(mb[:, 0] != 0)[0])} of the call did not encode (status "
+                               f"{int(mb[mb[:, 0] != 0][0, 0])})")
+        ea = eb = 0
+        for iid, na, nb in zip(ids, ca, cb):
+            for j, (key, _) in enumerate(by_image[iid]):
+                _, area_t, best, inter = mb[eb + j]
+                best = max(int(best), 0)
+                rows.append([key[0], key[1], best, int(inter), int(ma[ea + best, 1] + area_t - inter)])
+            ea += na
+            eb += nb
+
+    pending, images = [], set()
+    for key, iid, t in targets:
+        key = (int(key[0]), int(key[1]))
+        if key in seen:
+            raise ValueError(f"ceiling: two targets for {key}")
+        seen.add(key)
+        if iid not in runs_of:
+            runs_of[iid] = _image_runs(store, iid, cap)
+        if iid not in images and len(images) >= max(int(group), 1):      # a group is full: the images met so far go in one call
+            flush(pending)
+            pending, images = [], set()
+            runs_of = {iid: runs_of[iid]}
+        images.add(iid)
+        pending.append((key, iid, t))
+    flush(pending)
+    return np.asarray(sorted(rows), dtype=np.int64).reshape(-1, 5)
+
+
+def _jsonable(report):
+    return {"summary": report["summary"], "per_image": [dict(v, image_id=k) for k, v in report["per_image"].items()]}
+
+
+def main(argv=None):
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m hybridgl_amd.proposals", description="stored SAM proposals (main.py --save_proposals)")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    c = sub.add_parser("compare", help="two stores, image by image, every mask against every mask")
+    c.add_argument("dir_a")
+    c.add_argument("dir_b")
+    c.add_argument("--iou", default="0.5,0.75,0.9", metavar="LIST", help="the IoU thresholds of the report, comma-separated")
+    c.add_argument("--json", default="", metavar="OUT", help="also write the summary and the per-image figures here")
+    args = p.parse_args(argv)
+    try:
+        thresholds = [float(v) for v in args.iou.split(",") if v.strip()]
+        for d in (args.dir_a, args.dir_b):
+            if not os.path.isdir(d):
+                raise FileNotFoundError(f"{d}: no such directory")
+        report = compare(args.dir_a, args.dir_b, thresholds)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"hybridgl_amd.proposals: {e}")
+    s = report["summary"]
+    fmt = lambda v: "-" if v is None else format(v, ".6f")
+    print(f"images: {s['n_images']}   only in A: {len(s['only_in_a'])}   only in B: {len(s['only_in_b'])}"
+          + (f"   size mismatch: {len(s['size_mismatch'])}" if s["size_mismatch"] else ""))
+    print(f"masks: A {s['n_a']}, B {s['n_b']}, identical {s['identical']}")
+    for t, (ka, kb) in s["at_iou"].items():
+        print(f"IoU >= {t:g}: {ka} of A, {kb} of B have a partner")
+    print(f"best IoU of A: mean {fmt(s['mean_iou_a'])}, min {fmt(s['min_iou_a'])};  of B: mean {fmt(s['mean_iou_b'])}, min {fmt(s['min_iou_b'])}")
+    for iid, r in report["per_image"].items():
+        if r["identical"] != r["n_a"] or r["n_a"] != r["n_b"]:
+            print(f"  image {iid}: A {r['n_a']}, B {r['n_b']}, identical {r['identical']}, min best IoU {fmt(r['min_iou_a'])} / {fmt(r['min_iou_b'])}")
+    for name in ("only_in_a", "only_in_b", "size_mismatch"):
+        for iid in s[name]:
+            print(f"  {name.replace('_', ' ')}: image {iid}")
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(_jsonable(report), f)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -746,6 +746,35 @@ size_t hgl_rle_iou_workspace_bytes(int S, int H, int W, long long slot_words_a, 
 int hgl_rle_iou_device(const uint32_t* slots_a, long long slot_words_a, const int32_t* table_a,
                        const uint32_t* slots_b, long long slot_words_b, const int32_t* table_b,
                        int S, int H, int W, int64_t* iu, void* ws, size_t ws_bytes, void* stream);
+/* Every mask of set A against every mask of set B, image by image (csrc/rle.hip): the m x n form of the reference's
+ * rleIou(dt, gt, m, n, iscrowd, o) (refer/external/maskApi.c:77-96, pycocotools' iou) as exact integers, with the best partner
+ * of every mask.  Grouped from the start: one image is a group of one.  Asynchronous on `stream`; no host synchronisation,
+ * allocation or atomics; two calls give the same bytes; at most six launches, whatever G and the sizes are.
+ * Set A = (slots_a, slot_words_a, table_a, Sa), set B likewise: what hgl_rle_encode_device hands out, forms 0 and 1, with the
+ * code 0 / 1 / 2 rules of hgl_rle_decode_device.  Sa or Sb may be 0 (the set's pointers are then not read).
+ * images_host: HOST [G,5] int64, G <= 64, row g = (H_g, W_g, first A entry, first B entry, element offset of the image's
+ * matrix in inter); entries run from 0 to Sa / Sb and do not decrease, an image may own none on either side; H*W < 2^31.
+ * The array is read before the call returns.  Image g's matrix is [na_g, nb_g] int32, row-major; the extents must lie inside
+ * [0, inter_elems) and must not overlap.  Anything else is HGL_EINVAL and nothing is enqueued.
+ * crowd_b: device [Sb] uint8 (nonzero = crowd), or NULL for none.
+ * inter: |a & b| of every pair of an image, -1 in the row / column of an entry of code 2; nothing outside the extents is
+ * written.  NULL: no matrix is wanted (column 4 of images_host and inter_elems are not read).
+ * match_a: device [Sa,4] int32 = (code, area, best, I_best), match_b [Sb,4] likewise.  code and area as the decoder's status;
+ * best = the index, within the image's other set, of the partner with the largest I / D, where D(a, b) = area(a) when
+ * crowd_b[b] is set and area(a) + area(b) - I otherwise; ratios are compared exactly (I1*D2 > I2*D1 in 64 bits) and the lowest
+ * index wins a tie; best = -1 and I_best = 0 when no partner intersects.  An entry of code 2 has area 0 and best = -1 and is
+ * nobody's best.
+ * Limits: Sa + Sb < 2^31; per side the sum of n_g * W_g * ceil(H_g / 64) < 2^32.
+ * ws: hgl_rle_match_workspace_bytes for the same geometry, want_inter = (inter != NULL).  The query returns 0 for a geometry
+ * the call refuses and also for a valid call without an entry (Sa = Sb = 0), which needs no workspace and takes ws = NULL.
+ * The workspace holds both sets' bit planes and the partial counts: a call of fewer than 1024 tiles of 32 x 64 pairs splits
+ * every tile's plane words over up to 32 workgroups, each with a plane of sum(na_g * nb_g) counts of its own. */
+size_t hgl_rle_match_workspace_bytes(const int64_t* images_host, int G, int Sa, long long slot_words_a, int Sb,
+                                     long long slot_words_b, int want_inter);
+int hgl_rle_match_device(const uint32_t* slots_a, long long slot_words_a, const int32_t* table_a, int Sa,
+                         const uint32_t* slots_b, long long slot_words_b, const int32_t* table_b, int Sb,
+                         const int64_t* images_host, int G, const uint8_t* crowd_b, int32_t* inter, long long inter_elems,
+                         int32_t* match_a, int32_t* match_b, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,8 +17,15 @@
              path it replaces: sam.rle_to_mask per mask plus the upload, both sides ending in a synchronise; writes
              profiles/rle_decode_bench.json as well
 
+  match      (--match, instead of the legs above) every mask of one set against every mask of another: ops.rle_match for
+             64 x 64 masks of 640 x 640 (a RefCOCO image) and for 512 x 512 (a heavy-AMG image), against what a caller had to
+             do before the entry existed: replicate both sets into the Sa*Sb-long pair list and run ops.rle_iou over it, in
+             chunks within its S*H*W < 2^31 limit (HIP events, median of --reps after warm-up; the pair list's time with and
+             without the replication); writes profiles/rle_match_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
     python tools/rle_bench.py --decode [--reps 30]
+    python tools/rle_bench.py --match [--reps 30]
 """
 import argparse
 import json
@@ -181,8 +188,69 @@ def decode_leg(masks, reps):
     return rec
 
 
+def blobs(n, H, W, seed):
+    """seeded unions of ellipses, as the tests' blobs"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    out = np.zeros((n, H, W), np.uint8)
+    for i in range(n):
+        for _ in range(int(rng.integers(1, 4))):
+            cy, cx, ry, rx = rng.random() * H, rng.random() * W, (0.05 + 0.3 * rng.random()) * H, (0.05 + 0.3 * rng.random()) * W
+            out[i] |= (((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1).astype(np.uint8)
+    return out
+
+
+def match_leg(dev, reps, H=640, W=640):
+    """both sets are runs as a store holds them: packed counts (ops.rle_pack), form 0"""
+    rec = {"H": H, "W": W}
+    limit = ((1 << 31) - 1) // (H * W)      # entries per ops.rle_iou call
+    for name, n in (("64x64", 64), ("512x512", 512)):
+        sets = []
+        for seed in (11, 12):
+            runs = []
+            for at in range(0, n, 64):      # 64 masks at a time through the device encoder
+                m = torch.from_numpy(blobs(min(64, n - at), H, W, 1000 * seed + at)).to(dev)
+                runs += [r["counts"] for r in hsam.masks_to_rle(m)]
+            sets.append(ops.rle_pack(runs, H, W, device=dev))
+        (sa, ta), (sb, tb) = sets
+        inter, ma, mb = ops.rle_match(sa, ta, sb, tb, [(H, W)], [n], [n])
+        us = device_us(lambda: ops.rle_match(sa, ta, sb, tb, [(H, W)], [n], [n]), reps)
+        us_nomatrix = device_us(lambda: ops.rle_match(sa, ta, sb, tb, [(H, W)], [n], [n], matrix=False), reps)
+        rows = max(1, min(n, limit // n))      # rows of the matrix per pair-list chunk
+        ib = torch.arange(n, device=dev).repeat(rows)
+
+        def pair_list(keep=None, held=None):
+            """held: a dict that keeps the replicated chunks from call to call (the rle_iou calls alone); None: replicate anew"""
+            for a0 in range(0, n, rows):
+                k = min(rows, n - a0)
+                part = None if held is None else held.get(a0)
+                if part is None:
+                    ia = torch.arange(a0, a0 + k, device=dev).repeat_interleave(n)
+                    part = (sa[ia].contiguous(), ta[ia].contiguous(), sb[ib[:k * n]].contiguous(), tb[ib[:k * n]].contiguous())
+                    if held is not None:
+                        held[a0] = part
+                iu = ops.rle_iou(*part, H, W)
+                if keep is not None:
+                    keep.append(iu[:, 0].reshape(k, n))
+
+        got = []
+        pair_list(got)
+        assert torch.equal(torch.cat(got).to(torch.int32), inter[0]), "the pair list and the entry disagree"
+        r2 = max(3, reps // 5)
+        us_pairs = device_us(lambda: pair_list(), r2, warm=2)
+        held = {}
+        us_pairs_kernels = device_us(lambda: pair_list(held=held), r2, warm=2)
+        rec[name] = {"masks_a": n, "masks_b": n, "pairs": n * n, "slot_words": [int(sa.shape[1]), int(sb.shape[1])],
+                     "rle_match_us": round(us, 1), "rle_match_no_matrix_us": round(us_nomatrix, 1),
+                     "pair_list_chunks": (n + rows - 1) // rows, "pair_list_us": round(us_pairs, 1),
+                     "pair_list_rle_iou_only_us": round(us_pairs_kernels, 1), "pair_list_over_match": round(us_pairs / us, 1),
+                     "rle_iou_only_over_match": round(us_pairs_kernels / us, 1)}
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--match", action="store_true", help="measure rle_match against the pair list; writes profiles/rle_match_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
@@ -190,6 +258,14 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rle_bench.py needs a GPU"
     dev = torch.device("cuda:0")
+    if args.match:
+        out = {"match": match_leg(dev, args.reps), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_match_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
     if args.decode:
         rng = np.random.default_rng(7)
         yy, xx = np.mgrid[0:640, 0:640]
