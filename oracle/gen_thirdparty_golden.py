@@ -32,6 +32,7 @@ from hybridgl_amd.synth import synth_image, synth_masks  # noqa: E402
 
 BLUR_SIZES = [(97, 130), (480, 640), (33, 17)]
 CC_CASES = [(0, 60, 80, 30), (1, 97, 131, 10), (2, 64, 64, 800)]       # (seed, H, W, area threshold)
+TIE_CASE = (19, 80, 20)             # (H, W, area threshold) of the block-order case: every component is below the threshold
 
 
 def speckle(seed, H, W, n=4):
@@ -43,6 +44,24 @@ def speckle(seed, H, W, n=4):
     m[1] = rng.random((H, W)) < 0.45
     m[2] = rng.random((H, W)) < 0.08
     return m
+
+
+def cc_masks(ci):
+    """-> (masks [n,H,W] uint8, area threshold) of case ci: the speckle cases, then the BLOCK-ORDER case -- the `tie` patterns
+    of tests/ccl_cases.py: equal-area small components where the first in raster order starts in row 0 at a LATER column and
+    the other in row 1 at column 0, and the reverse.  remove_small_regions keeps `argmax(sizes)`, the FIRST largest label, so
+    the output says how the labeller numbers such a pair; OpenCV's 8-way labeller scans 2 x 2 blocks, the kernel and scipy
+    number by first pixel in raster order."""
+    if ci < len(CC_CASES):
+        seed, H, W, thr = CC_CASES[ci]
+        return speckle(seed, H, W), thr
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from ccl_cases import tie_masks
+    H, W, thr = TIE_CASE
+    return np.stack(tie_masks(H, W)).astype(np.uint8), thr
+
+
+N_CC = len(CC_CASES) + 1
 
 
 def nms_case(seed, n=200, n_idx=3):
@@ -80,8 +99,8 @@ def gen_cv2(out, cv2):
     np.savez_compressed(os.path.join(out, "cv_comp.npz"), img=img, masks=masks, blurred=blurred, out=np.stack(comp),
                         version=np.array(cv2.__version__))
     cc = {}
-    for ci, (seed, H, W, thr) in enumerate(CC_CASES):
-        m = speckle(seed, H, W)
+    for ci in range(N_CC):
+        m, thr = cc_masks(ci)
         cc[f"m{ci}"] = m
         cc[f"thr{ci}"] = np.array(thr)
         for mode in ("holes", "islands"):
@@ -176,8 +195,8 @@ def selftest(out):
     blur["version"] = np.array("oracle-selftest")
     np.savez_compressed(os.path.join(out, "cv_blur.npz"), **blur)
     cc = {}
-    for ci, (seed, H, W, thr) in enumerate(CC_CASES):
-        m = speckle(seed, H, W)
+    for ci in range(N_CC):
+        m, thr = cc_masks(ci)
         cc[f"m{ci}"], cc[f"thr{ci}"] = m, np.array(thr)
         for mode in ("holes", "islands"):
             res = [S.remove_small_regions(m[k].astype(bool), thr, mode) for k in range(len(m))]
