@@ -1335,13 +1335,12 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const int* __restrict__ bo
   colbox[t] = b < n ? ((const int4*)boxes)[order[b]] : make_int4(0, 0, 0, 0);
   __syncthreads();
   const int a = rb * 64 + t;
+  if (a >= n) return;       // the mask has K rows, not 64 W: rows from n on are neither written nor read (nms_scan_kernel)
+  const int4 me = ((const int4*)boxes)[order[a]];
+  const int jmax = min(64, n - cb * 64);
   unsigned long long w = 0;
-  if (a < n) {
-    const int4 me = ((const int4*)boxes)[order[a]];
-    const int jmax = min(64, n - cb * 64);
-    for (int j = 0; j < jmax; ++j) {
-      if (cb * 64 + j > a && nms_overlap(me, colbox[j], thr)) w |= 1ull << j;
-    }
+  for (int j = 0; j < jmax; ++j) {
+    if (cb * 64 + j > a && nms_overlap(me, colbox[j], thr)) w |= 1ull << j;
   }
   mask[(long long)a * W + cb] = w;
 }

@@ -622,7 +622,12 @@ int hgl_sam_postprocess(const float* low_res, const float* iou_pred, int K, int 
 
 /* torchvision.ops.batched_nms with one category (automatic_mask_generator.py:251-257): greedy,
  * descending score, suppress IoU > iou_threshold among candidates with keep!=0; K <= 1024.
- * out_idx [K] receives the kept candidate indices in order, *out_n their count (device memory). */
+ * out_idx [K] receives the kept candidate indices in order, *out_n their count (device memory).
+ * Exact against torchvision's float32 arithmetic for coordinates in [0, 2896]: there every area and every sum of two areas
+ * is an integer below 2^24.  Beyond that the union `wa * ha + wb * hb - inter` rounds, and the kernels evaluate it as
+ * fma(wa, ha, wb * hb) - inter, where torchvision rounds both products: with coordinates up to 32768, 5 to 7 of 4800 pairs
+ * built to lie within a few float32 steps of the threshold are decided the other way (tools/nms_contraction_probe.py).
+ * The same holds for hgl_nms_segments and hgl_nms_large. */
 int hgl_nms(const int32_t* boxes_xyxy, const float* scores, const uint8_t* keep, int K, float iou_threshold,
             int32_t* out_idx, int32_t* out_n, void* stream);
 
