@@ -8,7 +8,8 @@
 //   ln_gelu_rows          LayerNorm2d + GELU of output_upscaling, modeling/mask_decoder.py:53-59
 //   hyper_logits          hyper-network x upscaled embedding, written in the [P,3,4g,4g] pixel order
 //   sam_postprocess       modeling/sam.py:133-162 + utils/amg.py:156-176,303-346 fused
-//   sam_select / nms      automatic_mask_generator.py:251-257,287-319
+//   sam_finalize          the filters of automatic_mask_generator.py:287-298 (the selection after them -- NMS, crop
+//                         edges, gather -- is sam_nms.hip)
 #include "hgl_common.h"
 #include <math.h>
 
@@ -1102,322 +1103,6 @@ __global__ void sam_finalize_kernel(const unsigned* __restrict__ c, const float*
   keep[k] = (pass_iou && (!(stab_thresh > 0.f) || s >= stab_thresh)) ? 1 : 0;  // NaN >= x is false
 }
 
-// The ranking order of every NMS kernel below: descending score, the original index breaks ties, and a NaN score ranks ABOVE
-// every number (where torch.sort(descending=True) -- batched_nms's argsort, automatic_mask_generator.py:251-257 -- puts it).
-// A total order: ranks by counting never collide, order[] has no holes below the number of valid candidates.  (With a plain
-// `sj > sc || (sj == sc && j < i)` two NaN scores -- an f16x3 overflow with the thresholds open -- both got rank 0.)
-__device__ __forceinline__ bool nms_before(float sj, int j, float si, int i) {
-  const bool nj = sj != sj, ni = si != si;
-  if (nj || ni) return nj && (!ni || j < i);
-  return sj > si || (sj == si && j < i);
-}
-
-// Greedy NMS in one workgroup (K <= 1024): candidates with keep[k]!=0, descending score with the
-// original index as tie-break (stable sort), suppress IoU > thr.  out_idx[0..n) in kept order.
-__device__ __forceinline__ void nms_body(const int* __restrict__ boxes, const float* __restrict__ scores,
-                                         const uint8_t* __restrict__ keep, int K, float thr,
-                                         int* __restrict__ out_idx, int* __restrict__ out_n) {
-  __shared__ int order[1024];
-  __shared__ unsigned char alive[1024];
-  __shared__ int cur, nkept;
-  const int t = threadIdx.x;
-  int valid = 0;
-  float sc = 0.f;
-  if (t < K && keep[t]) { valid = 1; sc = scores[t]; }
-  // rank by counting (K small): position among valid candidates
-  if (t < 1024) order[t] = -1;
-  __syncthreads();
-  if (valid) {
-    int rank = 0;
-    for (int j = 0; j < K; ++j) {
-      if (!keep[j]) continue;
-      const float sj = scores[j];
-      if (nms_before(sj, j, sc, t)) ++rank;
-    }
-    order[rank] = t;
-  }
-  if (t < 1024) alive[t] = 1;
-  if (t == 0) nkept = 0;
-  __syncthreads();
-  int nvalid = 0;
-  for (int j = 0; j < K; ++j) nvalid += keep[j] ? 1 : 0;  // uniform
-  for (int r = 0; r < nvalid; ++r) {
-    if (t == 0) cur = alive[r] ? order[r] : -1;
-    __syncthreads();
-    const int ci = cur;
-    if (ci >= 0) {
-      if (t == 0) { out_idx[nkept] = ci; ++nkept; }
-      // suppress lower-ranked boxes overlapping ci
-      const int me = (t > r && t < nvalid) ? order[t] : -1;
-      if (me >= 0 && alive[t]) {
-        const float ax0 = boxes[ci * 4], ay0 = boxes[ci * 4 + 1], ax1 = boxes[ci * 4 + 2], ay1 = boxes[ci * 4 + 3];
-        const float bx0 = boxes[me * 4], by0 = boxes[me * 4 + 1], bx1 = boxes[me * 4 + 2], by1 = boxes[me * 4 + 3];
-        const float iw = fmaxf(fminf(ax1, bx1) - fmaxf(ax0, bx0), 0.f);
-        const float ih = fmaxf(fminf(ay1, by1) - fmaxf(ay0, by0), 0.f);
-        const float inter = iw * ih;
-        const float iou = inter / ((ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0) - inter);
-        if (iou > thr) alive[t] = 0;
-      }
-    }
-    __syncthreads();
-  }
-  if (t == 0) *out_n = nkept;
-}
-
-__global__ __launch_bounds__(1024) void nms_kernel(const int* __restrict__ boxes,
-                                                   const float* __restrict__ scores,
-                                                   const uint8_t* __restrict__ keep, int K, float thr,
-                                                   int* __restrict__ out_idx, int* __restrict__ out_n) {
-  nms_body(boxes, scores, keep, K, thr, out_idx, out_n);
-}
-
-// ---- NMS for any K (crop layers / dense point grids, automatic_mask_generator.py:209-220,259-266) ----------
-// Same semantics as nms_kernel (descending score, original index breaks ties, suppress IoU > thr), in three passes:
-// rank by counting -> 64x64-bit suppression words of the sorted boxes -> one workgroup walks the row blocks,
-// resolving each 64-row block with wave shuffles and OR-ing the kept rows into the running "removed" bit set.
-__global__ __launch_bounds__(256) void nms_rank_kernel(const float* __restrict__ scores, const uint8_t* __restrict__ keep,
-                                                       int K, int* __restrict__ order, int* __restrict__ nvalid) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= K || !keep[i]) return;
-  const float sc = scores[i];
-  int rank = 0;
-  for (int j = 0; j < K; ++j) {
-    if (!keep[j]) continue;
-    const float sj = scores[j];
-    rank += nms_before(sj, j, sc, i) ? 1 : 0;
-  }
-  order[rank] = i;
-  atomicAdd(nvalid, 1);
-}
-
-__device__ __forceinline__ bool nms_overlap(const int4 a, const int4 b, float thr) {
-  const float ax0 = (float)a.x, ay0 = (float)a.y, ax1 = (float)a.z, ay1 = (float)a.w;
-  const float bx0 = (float)b.x, by0 = (float)b.y, bx1 = (float)b.z, by1 = (float)b.w;
-  const float iw = fmaxf(fminf(ax1, bx1) - fmaxf(ax0, bx0), 0.f);
-  const float ih = fmaxf(fminf(ay1, by1) - fmaxf(ay0, by0), 0.f);
-  const float inter = iw * ih;
-  const float iou = inter / ((ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0) - inter);
-  return iou > thr;
-}
-
-// nms_kernel's semantics for K <= 512 without its serial loop of K iterations x (two barriers + global loads of the current
-// box: 82 us for the 192 candidates of an image): ranks by counting, the boxes in rank order in LDS, every thread the
-// suppression words of its row (the same IoU expression: nms_overlap), then ONE thread walks the rows OR-ing the kept ones
-// into the removed set -- the scheme of the any-K path below in one workgroup.
-__device__ __forceinline__ void nms_bits_body(const int* __restrict__ boxes, const float* __restrict__ scores,
-                                              const uint8_t* __restrict__ keep, int K, float thr,
-                                              int* __restrict__ out_idx, int* __restrict__ out_n) {
-  __shared__ int4 sbox[512];
-  __shared__ int order[512];
-  __shared__ float ssc[512];
-  __shared__ unsigned char skeep[512];
-  __shared__ unsigned long long mask[512][8];
-  __shared__ unsigned long long removed[8];
-  __shared__ unsigned long long kept_word;
-  __shared__ int nv, nkept_s;
-  const int t = threadIdx.x, lane = t & 63;
-  const bool valid = t < K && keep[t];
-  const float sc = valid ? scores[t] : 0.f;
-  ssc[t] = sc;
-  skeep[t] = valid ? 1 : 0;
-  order[t] = -1;
-  if (t < 8) removed[t] = 0;
-  if (t == 0) { nv = 0; nkept_s = 0; }
-  __syncthreads();
-  if (valid) {      // rank by counting: position among the valid candidates (descending score, the index breaks ties)
-    int rank = 0;
-#pragma unroll 8
-    for (int j = 0; j < K; ++j) {
-      const float sj = ssc[j];
-      rank += (skeep[j] && nms_before(sj, j, sc, t)) ? 1 : 0;
-    }
-    order[rank] = t;
-    atomicAdd(&nv, 1);
-  }
-  __syncthreads();
-  const int n = nv;
-  if (t < n) sbox[t] = ((const int4*)boxes)[order[t]];
-  __syncthreads();
-  const int nw = (n + 63) >> 6;
-  // word w is needed of rows 0 .. min(n, 64 (w + 1)) - 1 (words left of a row's diagonal block are never read): the (word, row)
-  // pairs are dealt to all 512 threads -- 384 pairs of 64 IoUs for 192 boxes, not three words for each of 192 threads
-  for (int w = 0, q0 = 0; w < nw; ++w) {
-    const int rows = min(n, 64 * (w + 1));
-    for (int q = t - (q0 & 511); q < rows; q += 512) {
-      if (q < 0) continue;
-      const int4 me = sbox[q];
-      unsigned long long word = 0;
-      const int b0 = 64 * w, jn = min(64, n - b0);
-#pragma unroll 4
-      for (int j = 0; j < jn; ++j)
-        if (b0 + j > q && nms_overlap(me, sbox[b0 + j], thr)) word |= 1ull << j;
-      mask[q][w] = word;
-    }
-    q0 += rows;
-  }
-  __syncthreads();
-  // nms_scan_kernel's walk on the LDS-resident words: wave 0 resolves a block of 64 rows with shuffles, then every later word
-  // takes the OR of the kept rows
-  for (int rb = 0; rb < nw; ++rb) {
-    if (t < 64) {
-      const int a = rb * 64 + lane;
-      const unsigned long long d = a < n ? mask[a][rb] : 0ull;
-      unsigned long long rem = removed[rb], km = 0;
-      for (int s2 = 0; s2 < 64; ++s2) {
-        const unsigned lo = __shfl((unsigned)(d & 0xffffffffull), s2), hi = __shfl((unsigned)(d >> 32), s2);
-        if (rb * 64 + s2 < n && !((rem >> s2) & 1ull)) {
-          km |= 1ull << s2;
-          rem |= ((unsigned long long)hi << 32) | lo;
-        }
-      }
-      const int base = nkept_s;
-      if ((km >> lane) & 1ull) out_idx[base + __popcll(km & ((1ull << lane) - 1ull))] = order[a];
-      if (lane == 0) { kept_word = km; nkept_s = base + __popcll(km); }
-    }
-    __syncthreads();
-    const unsigned long long km = kept_word;
-    if (t > rb && t < nw) {
-      unsigned long long acc = removed[t];
-      unsigned long long bits = km;
-      while (bits) {
-        const int s2 = __ffsll((long long)bits) - 1;
-        bits &= bits - 1;
-        acc |= mask[rb * 64 + s2][t];
-      }
-      removed[t] = acc;
-    }
-    __syncthreads();
-  }
-  if (t == 0) *out_n = nkept_s;
-}
-
-__global__ __launch_bounds__(512) void nms_bits_kernel(const int* __restrict__ boxes, const float* __restrict__ scores,
-                                                       const uint8_t* __restrict__ keep, int K, float thr,
-                                                       int* __restrict__ out_idx, int* __restrict__ out_n) {
-  nms_bits_body(boxes, scores, keep, K, thr, out_idx, out_n);
-}
-
-// Several candidate lists in one launch: workgroup s runs the greedy NMS of segment s = candidates offsets[s] .. offsets[s+1]
-// exactly as hgl_nms runs it on that list alone (the same bodies): out_idx[offsets[s] + 0 .. out_n[s]) holds the kept
-// candidates as indices INTO the segment.  BITS: this launch serves the segments of up to 512 candidates (nms_bits_body),
-// else those of 513 .. 1024 (nms_body); a workgroup whose segment belongs to the other launch returns at once, and an
-// empty segment gets its out_n[s] = 0 from the BITS launch.
-template <bool BITS>
-__global__ __launch_bounds__(BITS ? 512 : 1024) void nms_segments_kernel(const int* __restrict__ boxes,
-                                                                         const float* __restrict__ scores,
-                                                                         const uint8_t* __restrict__ keep,
-                                                                         const int* __restrict__ offsets, float thr,
-                                                                         int* __restrict__ out_idx, int* __restrict__ out_n) {
-  const int s = blockIdx.x, o = offsets[s], K = offsets[s + 1] - o;
-  // (a list that is empty, or longer than the caller's max_len admits, keeps nothing: out_n[s] = 0 from the BITS launch,
-  // which runs first; the other launch then overwrites the count of the lists it serves)
-  if (K <= 0 || K > 512) {
-    if (BITS && threadIdx.x == 0) out_n[s] = 0;
-    if (BITS || K <= 0 || K > 1024) return;
-  } else if (!BITS) {
-    return;
-  }
-  if (BITS)
-    nms_bits_body(boxes + 4ll * o, scores + o, keep + o, K, thr, out_idx + o, out_n + s);
-  else
-    nms_body(boxes + 4ll * o, scores + o, keep + o, K, thr, out_idx + o, out_n + s);
-}
-
-// grid (W, W), 64 threads: word (row a = 64*by + t, column block bx) of the upper triangle
-__global__ __launch_bounds__(64) void nms_mask_kernel(const int* __restrict__ boxes, const int* __restrict__ order,
-                                                      const int* __restrict__ nvalid, int W, float thr,
-                                                      unsigned long long* __restrict__ mask) {
-  const int cb = blockIdx.x, rb = blockIdx.y, t = threadIdx.x;
-  const int n = *nvalid;
-  if (cb < rb || rb * 64 >= n) return;
-  __shared__ int4 colbox[64];
-  const int b = cb * 64 + t;
-  colbox[t] = b < n ? ((const int4*)boxes)[order[b]] : make_int4(0, 0, 0, 0);
-  __syncthreads();
-  const int a = rb * 64 + t;
-  if (a >= n) return;       // the mask has K rows, not 64 W: rows from n on are neither written nor read (nms_scan_kernel)
-  const int4 me = ((const int4*)boxes)[order[a]];
-  const int jmax = min(64, n - cb * 64);
-  unsigned long long w = 0;
-  for (int j = 0; j < jmax; ++j) {
-    if (cb * 64 + j > a && nms_overlap(me, colbox[j], thr)) w |= 1ull << j;
-  }
-  mask[(long long)a * W + cb] = w;
-}
-
-__global__ __launch_bounds__(256) void nms_scan_kernel(const unsigned long long* __restrict__ mask,
-                                                       const int* __restrict__ order, const int* __restrict__ nvalid,
-                                                       int W, int* __restrict__ out_idx, int* __restrict__ out_n) {
-  __shared__ unsigned long long removed[1024];
-  __shared__ unsigned long long kept_word;
-  __shared__ int nkept_s;
-  const int t = threadIdx.x, lane = t & 63;
-  const int n = *nvalid;
-  for (int w = t; w < W; w += 256) removed[w] = 0;
-  if (t == 0) nkept_s = 0;
-  __syncthreads();
-  const int nblk = (n + 63) / 64;
-  for (int rb = 0; rb < nblk; ++rb) {
-    if (t < 64) {
-      const int a = rb * 64 + lane;
-      const unsigned long long d = a < n ? mask[(long long)a * W + rb] : 0ull;
-      unsigned long long rem = removed[rb], km = 0;
-      for (int s2 = 0; s2 < 64; ++s2) {
-        const unsigned lo = __shfl((unsigned)(d & 0xffffffffull), s2), hi = __shfl((unsigned)(d >> 32), s2);
-        if (rb * 64 + s2 < n && !((rem >> s2) & 1ull)) {
-          km |= 1ull << s2;
-          rem |= ((unsigned long long)hi << 32) | lo;
-        }
-      }
-      const int base = nkept_s;
-      if ((km >> lane) & 1ull) out_idx[base + __popcll(km & ((1ull << lane) - 1ull))] = order[a];
-      if (lane == 0) { kept_word = km; nkept_s = base + __popcll(km); }
-    }
-    __syncthreads();
-    const unsigned long long km = kept_word;
-    for (int w = rb + 1 + t; w < W; w += 256) {
-      unsigned long long acc = removed[w];
-      unsigned long long bits = km;
-      while (bits) {
-        const int s2 = __ffsll((long long)bits) - 1;
-        bits &= bits - 1;
-        acc |= mask[(long long)(rb * 64 + s2) * W + w];
-      }
-      removed[w] = acc;
-    }
-    __syncthreads();
-  }
-  if (t == 0) *out_n = nkept_s;
-}
-
-// is_box_near_crop_edge (utils/amg.py:78-88) applied to keep flags: boxes are in crop coordinates
-__global__ __launch_bounds__(256) void crop_edge_kernel(const int* __restrict__ boxes, int K, int cx0, int cy0, int cx1,
-                                                        int cy1, int ox0, int oy0, int ox1, int oy1, float atol,
-                                                        uint8_t* __restrict__ keep) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= K) return;
-  const float b[4] = {(float)(boxes[i * 4] + cx0), (float)(boxes[i * 4 + 1] + cy0), (float)(boxes[i * 4 + 2] + cx0),
-                      (float)(boxes[i * 4 + 3] + cy0)};
-  const float c[4] = {(float)cx0, (float)cy0, (float)cx1, (float)cy1};
-  const float o[4] = {(float)ox0, (float)oy0, (float)ox1, (float)oy1};
-  bool near = false;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) near |= (fabsf(b[e] - c[e]) <= atol) && !(fabsf(b[e] - o[e]) <= atol);
-  if (near) keep[i] = 0;
-}
-
-// dst[i] = src[idx[i]] for i < *n (rows of row_bytes bytes, 16-byte multiples)
-__global__ __launch_bounds__(256) void gather_masks_kernel(const uint8_t* __restrict__ src,
-                                                           const int* __restrict__ idx,
-                                                           const int* __restrict__ n, long long row16,
-                                                           uint8_t* __restrict__ dst) {
-  const int i = blockIdx.y;
-  if (i >= *n) return;
-  const uint4* s = (const uint4*)(src + (long long)idx[i] * row16 * 16);
-  uint4* d = (uint4*)(dst + (long long)i * row16 * 16);
-  for (long long j = blockIdx.x * 256ll + threadIdx.x; j < row16; j += (long long)gridDim.x * 256) d[j] = s[j];
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------ launchers
@@ -1640,83 +1325,6 @@ int hgl_sam_postprocess(const float* low_res, const float* iou_pred, int K, int 
   hipLaunchKernelGGL(sam_finalize_kernel, dim3((K + 255) / 256), dim3(256), 0, st, counters, iou_pred, K,
                      pred_iou_thresh, stability_thresh, stability, (int*)boxes_xyxy, keep);
   return hgl_check_launch("sam_postprocess");
-}
-
-int hgl_nms(const int32_t* boxes_xyxy, const float* scores, const uint8_t* keep, int K, float iou_threshold,
-            int32_t* out_idx, int32_t* out_n, void* stream) {
-  HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(boxes_xyxy && scores && keep && out_idx && out_n, "nms: null argument");
-  HGL_REQUIRE(K > 0 && K <= 1024, "nms: K must be in [1,1024] (got %d)", K);
-  if (K <= 512 && ((uintptr_t)boxes_xyxy & 15) == 0)
-    hipLaunchKernelGGL(nms_bits_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, (const int*)boxes_xyxy, scores, keep, K, iou_threshold, (int*)out_idx, (int*)out_n);
-  else
-    hipLaunchKernelGGL(nms_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const int*)boxes_xyxy, scores, keep, K, iou_threshold, (int*)out_idx, (int*)out_n);
-  return hgl_check_launch("nms");
-}
-
-int hgl_nms_segments(const int32_t* boxes_xyxy, const float* scores, const uint8_t* keep, const int32_t* offsets, int n_seg,
-                     int max_len, float iou_threshold, int32_t* out_idx, int32_t* out_n, void* stream) {
-  HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(boxes_xyxy && scores && keep && offsets && out_idx && out_n, "nms_segments: null argument");
-  HGL_REQUIRE(n_seg > 0 && n_seg <= 65535, "nms_segments: n_seg must be in [1,65535] (got %d)", n_seg);
-  HGL_REQUIRE(max_len >= 0 && max_len <= 1024, "nms_segments: segments hold up to 1024 candidates (max_len %d)", max_len);
-  HGL_REQUIRE(((uintptr_t)boxes_xyxy & 15) == 0, "nms_segments: boxes must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(nms_segments_kernel<true>, dim3(n_seg), dim3(512), 0, st, (const int*)boxes_xyxy, scores, keep,
-                     (const int*)offsets, iou_threshold, (int*)out_idx, (int*)out_n);
-  if (max_len > 512)
-    hipLaunchKernelGGL(nms_segments_kernel<false>, dim3(n_seg), dim3(1024), 0, st, (const int*)boxes_xyxy, scores, keep,
-                       (const int*)offsets, iou_threshold, (int*)out_idx, (int*)out_n);
-  return hgl_check_launch("nms_segments");
-}
-
-size_t hgl_nms_large_workspace_bytes(int K) {
-  const size_t W = ((size_t)K + 63) / 64;
-  return hgl_align_up((size_t)K * sizeof(int), 256) + hgl_align_up(sizeof(int), 256) + hgl_align_up((size_t)K * W * 8, 256);
-}
-
-int hgl_nms_large(const int32_t* boxes_xyxy, const float* scores, const uint8_t* keep, int K, float iou_threshold,
-                  int32_t* out_idx, int32_t* out_n, void* workspace, size_t workspace_bytes, void* stream) {
-  HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(boxes_xyxy && scores && keep && out_idx && out_n, "nms_large: null argument");
-  HGL_REQUIRE(K > 0 && K <= 32768, "nms_large: K must be in [1,32768] (got %d)", K);
-  HGL_REQUIRE(((uintptr_t)boxes_xyxy & 15) == 0, "nms_large: boxes must be 16-byte aligned");
-  if (!workspace || workspace_bytes < hgl_nms_large_workspace_bytes(K)) {
-    hgl_set_error("nms_large: workspace too small");
-    return HGL_EWORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int W = (K + 63) / 64;
-  HglArena ar(workspace, workspace_bytes);
-  int* order = ar.take<int>((size_t)K);
-  int* nvalid = ar.take<int>(1);
-  unsigned long long* mask = ar.take<unsigned long long>((size_t)K * W);
-  if (hipMemsetAsync(nvalid, 0, sizeof(int), st) != hipSuccess) {
-    hgl_set_error("nms_large: memset failed");
-    return HGL_ELAUNCH;
-  }
-  hipLaunchKernelGGL(nms_rank_kernel, dim3((K + 255) / 256), dim3(256), 0, st, scores, keep, K, order, nvalid);
-  hipLaunchKernelGGL(nms_mask_kernel, dim3(W, W), dim3(64), 0, st, (const int*)boxes_xyxy, order, nvalid, W, iou_threshold, mask);
-  hipLaunchKernelGGL(nms_scan_kernel, dim3(1), dim3(256), 0, st, mask, order, nvalid, W, (int*)out_idx, (int*)out_n);
-  return hgl_check_launch("nms_large");
-}
-
-int hgl_box_near_crop_edge(const int32_t* boxes_xyxy, int K, const int32_t* crop_box_xyxy, const int32_t* orig_box_xyxy,
-                           float atol, uint8_t* keep, void* stream) {
-  HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(boxes_xyxy && crop_box_xyxy && orig_box_xyxy && keep && K > 0, "box_near_crop_edge: bad arguments");
-  hipLaunchKernelGGL(crop_edge_kernel, dim3((K + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const int*)boxes_xyxy, K,
-                     crop_box_xyxy[0], crop_box_xyxy[1], crop_box_xyxy[2], crop_box_xyxy[3], orig_box_xyxy[0],
-                     orig_box_xyxy[1], orig_box_xyxy[2], orig_box_xyxy[3], atol, keep);
-  return hgl_check_launch("box_near_crop_edge");
-}
-
-int hgl_gather_masks(const uint8_t* masks, const int32_t* idx, const int32_t* n, int max_n, long long HW,
-                     uint8_t* out, void* stream) {
-  HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(masks && idx && n && out && max_n > 0 && HW > 0 && (HW & 15) == 0, "gather_masks: bad arguments (HW must be a multiple of 16)");
-  hipLaunchKernelGGL(gather_masks_kernel, dim3(64, max_n), dim3(256), 0, (hipStream_t)stream, masks, (const int*)idx, (const int*)n, HW / 16, out);
-  return hgl_check_launch("gather_masks");
 }
 
 }  // extern "C"

@@ -232,3 +232,15 @@ def rle_kernels(fn):
         m = re.search(r"(rle_[a-z]+_kernel)(?:<(\w+)[,>]|IL[ib](\d+)E)?", n)
         out.append((m.group(1), m.group(2) or m.group(3)) if m else (n, None))
     return out
+
+
+def nms_kernels(fn):
+    """launched_kernels(fn) for the kernels of csrc/sam_nms.hip: [(function name, template argument or None)] in launch order,
+    from a demangled ('nms_segments_kernel<true>(...)') or an Itanium-mangled ('19nms_segments_kernelILb1EEEv...') name, the
+    argument as the mangled form spells it ('1' for true); any other kernel keeps its raw name"""
+    out = []
+    for n in launched_kernels(fn):
+        m = re.search(r"(nms_(?:[a-z]+_)?kernel)(?:<(\w+)[,>]|IL[ib](\d+)E)?", n)
+        arg = m and (m.group(2) or m.group(3))
+        out.append((m.group(1), {"true": "1", "false": "0"}.get(arg, arg)) if m else (n, None))
+    return out

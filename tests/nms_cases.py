@@ -1,4 +1,4 @@
-"""Deterministic candidate lists for the greedy box NMS (csrc/sam_glue.hip: nms_kernel, nms_bits_kernel, nms_segments_kernel,
+"""Deterministic candidate lists for the greedy box NMS (csrc/sam_nms.hip: nms_segments_kernel with its LDS and serial bodies,
 nms_rank / nms_mask / nms_scan_kernel) and the reference they are judged by, plain numpy, no GPU code.
 
 `greedy_nms` is the reference: a loop over the ranked candidates that computes, for every kept one, ONE row of IoUs in float32,
@@ -342,6 +342,6 @@ def cases_for(K, thr=None):
 
 
 # the K of the device grid, by the route that serves them
-K_BITS = [1, 2, 63, 64, 65, 127, 128, 129, 448, 449, 511, 512]      # hgl_nms: nms_bits_kernel
-K_SERIAL = [513, 1023, 1024]                                        # hgl_nms: nms_kernel
+K_BITS = [1, 2, 63, 64, 65, 127, 128, 129, 448, 449, 511, 512]      # hgl_nms: nms_segments_kernel<true>, the LDS body
+K_SERIAL = [513, 1023, 1024]                                        # hgl_nms: nms_segments_kernel<false>, the serial body
 K_LARGE = [1025, 4097, 16390]                                       # hgl_nms_large alone; the last: W = 257 words a row

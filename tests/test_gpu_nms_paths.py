@@ -1,6 +1,7 @@
-"""The greedy box NMS (csrc/sam_glue.hip) on every kernel route against the float32 reference of tests/nms_cases.py, on dense,
-chained inputs: hgl_nms (nms_bits_kernel up to 512 candidates, nms_kernel for 513 .. 1024 and for an unaligned box pointer),
-hgl_nms_segments (both bodies, one workgroup a list) and hgl_nms_large (rank / mask / scan, any K up to 32768).
+"""The greedy box NMS (csrc/sam_nms.hip) on every kernel route against the float32 reference of tests/nms_cases.py, on dense,
+chained inputs: hgl_nms (the segment kernel on one list: its LDS body up to 512 candidates, its serial body for 513 .. 1024 and
+for an unaligned box pointer), hgl_nms_segments (both bodies, one workgroup a list) and hgl_nms_large (rank / mask / scan, any K
+up to 32768).
 
 K: 1, 2, around every multiple of 64 that starts a new word of the LDS kernel up to its eighth (448 | 449, 511 | 512), 513 /
 1023 / 1024 (serial kernel), 1025 / 4097 / 16390 (W = 17, 65 and 257 words a row: the 256-thread stride loops over removed[]
@@ -72,7 +73,7 @@ def test_every_route_equals_the_reference(cuda, K):
 
 @pytest.mark.parametrize("K", [1, 2, 64, 65, 192, 449, 512])
 def test_serial_kernel_below_513_through_an_unaligned_box_pointer(cuda, K):
-    """hgl_nms sends boxes that are not 16-byte aligned (nms_bits_kernel loads them as int4) to nms_kernel: the same lists as
+    """hgl_nms sends boxes that are not 16-byte aligned (the LDS body loads them as int4) to the serial body: the same lists as
     the aligned call.  hgl_nms_segments and hgl_nms_large refuse such a pointer and launch nothing."""
     lib = _lib.load()
     for c, ref in refs(K):
@@ -231,6 +232,54 @@ def test_the_second_nms_as_the_generator_composes_it(cuda):
     s = (rng.random(1500) < 0.8).astype(np.float32)
     assert twice(hsam.nms, T(b, cuda), T(s, cuda), torch.ones(1500, dtype=torch.uint8, device=cuda), thr) \
         == N.greedy_nms(b, s, np.ones(1500, np.uint8), thr)
+
+
+def test_launches(cuda):
+    """a single list is one segment: hgl_nms launches the segment kernel of hgl_nms_segments, the same function and
+    instantiation, once -- the LDS body for up to 512 aligned candidates, the serial body above and for an unaligned box
+    pointer; hgl_nms_large launches its three passes.  No kernel of a single list's own exists."""
+    import abi_ref
+    thr = 0.7
+    case = {K: N.clusters(K, thr) for K in (2, 3, 65, 513)}
+    ref = {K: N.run(c) for K, c in case.items()}
+    dev = {K: (T(c.boxes, cuda), T(c.scores, cuda), T(c.keep, cuda)) for K, c in case.items()}
+    flat = torch.zeros(4 * 3 + 1, dtype=torch.int32, device=cuda)
+    flat[1:] = dev[3][0].reshape(-1)
+    off4 = flat[1:].view(3, 4)
+    assert off4.data_ptr() % 16 == 4
+    seen = []
+
+    def launches(call, lens):
+        """the kernels of one call (made once before, so that nothing is allocated under the profiler); every list's kept
+        candidates must equal the reference"""
+        call()
+        got = []
+        ks = abi_ref.nms_kernels(lambda: got.append(call()))
+        idx, n = (x.cpu().numpy() for x in got[0])
+        for i, L in enumerate(lens):
+            o = sum(lens[:i])
+            assert idx[o:o + n[i]].tolist() == ref[L], (lens, i)
+        seen.extend(ks)
+        return ks
+
+    def single(fn, K, boxes=None):
+        b, s, k = dev[K]
+        return launches(lambda: fn(b if boxes is None else boxes, s, k, thr), [K])
+
+    def segments(lens, max_len):
+        b, s, k = (torch.cat([dev[L][j] for L in lens]) for j in range(3))
+        offs = T(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), cuda)
+        return launches(lambda: hsam.nms_segments(b, s, k, offs, max_len, thr), lens)
+
+    lds = single(hsam.nms, 3)
+    assert len(lds) == 1 and lds == segments([3, 2], 3), lds
+    both = segments([3, 513], 513)
+    assert len(both) == 2 and both[0] == lds[0] and both[1] != lds[0], (lds, both)
+    assert single(hsam.nms, 513) == both[1:] and single(hsam.nms, 3, off4) == both[1:]
+    assert lds[0][0] == both[1][0] and {lds[0][1], both[1][1]} == {"0", "1"}, (lds, both)     # one function, its two bodies
+    large = single(hsam.nms_large, 65)
+    assert len(large) == 3 and len({k for k, _ in large}) == 3 and all(k.startswith("nms_") for k, _ in large), large
+    assert not [k for k in seen if k[0] in ("nms_kernel", "nms_bits_kernel")], seen
 
 
 # ------------------------------------------------------------------------------------------- the NMS's small neighbours

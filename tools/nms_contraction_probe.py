@@ -5,7 +5,8 @@ Beyond it `wa * ha + wb * hb - inter` rounds, and the library's -ffp-contract=on
 sum, which torchvision's CPU kernel (the reference's NMS) does not do.  This builds box pairs with coordinates up to 32768
 whose IoU lies within a few float32 steps of the threshold, predicts on the host the decision of the stepwise float32
 expression and of both possible fusions, and runs the pairs on the device: lists of two through hgl_nms_segments
-(nms_bits_body -> nms_overlap) and a sample through hgl_nms with an unaligned pointer (nms_kernel -> nms_body).
+(the LDS body, nms_bits_body) and a sample through hgl_nms with an unaligned pointer (the serial body, nms_serial_body): two
+inlinings of the one IoU expression, nms_overlap of csrc/sam_nms.hip.
 
     python tools/nms_contraction_probe.py [--out FILE.json]
 """
