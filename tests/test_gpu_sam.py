@@ -188,9 +188,11 @@ def test_predictor_prompt_kinds_vs_reference(cuda, tiny, golden_dir):
 def test_postprocess_shared_table_kernel_is_bit_identical(cuda, tiny, orig, inp, img, low):
     """sam_postprocess_sep_kernel (per-tile column tables + the horizontally interpolated patch in LDS) against the per-pixel
     kernel (HGL_SAM_POST_SEP=0): logits, masks, boxes and stability counters bit for bit, over down- and up-scaling size
-    ratios (the fifth geometry exceeds the shared tables, and so do the last three -- crops of a crop layer at 2.6 : 1: both
-    calls take the per-pixel kernel there.  A 32-column tile variant of the shared-table kernel fits those crops and was
-    measured: 3.1 ms per crop against the per-pixel kernel's 2.1)"""
+    ratios.  The fifth geometry exceeds the shared tables, and so do the last three -- crops of a crop layer at 2.6 : 1: both
+    calls take the per-pixel kernel there, so for those four the comparison is the per-pixel kernel with itself; what pins them
+    -- and every other route of the two kernels -- against a reference is tests/test_gpu_postprocess_paths.py.  (A 32-column
+    tile variant of the shared-table kernel fits those crops and was measured: 3.1 ms per crop against the per-pixel kernel's
+    2.1)"""
     m = tiny[1]
     rng = np.random.default_rng(orig[0])
     K = 7
@@ -753,6 +755,7 @@ def test_full_size_decoder_all_prompts_vs_torch_cpu_restatement(cuda):
     same = diff == 0
     assert same.sum() >= 150                       # nearly all of the 192 candidates agree in every pixel
     np.testing.assert_allclose(stab.cpu().numpy()[same], rstab.numpy()[same], rtol=0, atol=1e-3)
+    assert np.array_equal(boxes.cpu().numpy()[same].astype(np.int64), rbox.numpy()[same])      # the box is a function of the mask
 
 
 @pytest.mark.parametrize("mode", ["holes", "islands"])
