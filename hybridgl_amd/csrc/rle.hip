@@ -18,17 +18,17 @@
 //      counts[0] = 0).  A first sweep pop-counts T (the number of counts is transitions + 1) and C (the area) and so decides
 //      what the slot holds; the second sweep takes the words 256 at a time: an exclusive sum-scan of the pop-counts gives the
 //      rank of every word's first transition, an exclusive max-scan of "position of my last transition" the position of the
-//      last earlier one, both carried from chunk to chunk, and every transition writes its own counts[k] = p_k - p_(k-1).
+//      last earlier one, both carried from chunk to chunk, and every transition writes its own counts[k] = p_k - p_(k-1)
+//      (rle_counts_chunk in rle_scan.h: the polygon rasteriser of rle_poly.hip ends in the same scan).
 //
 // Slot forms (table row = n_counts, form, area, 0): 0 = the n_counts counts (whenever they fit), 1 = the column-major bit
 // plane (bit p % 32 of word p / 32; whenever the counts do not fit but ceil(H*W/32) words do), 2 = neither fits, nothing
 // written, 3 = the index is outside [0, N), nothing read or written.  Words beyond what the form defines keep their bytes.
 #include "hgl_common.h"
 #include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan, rle_match_plan: plain C++, shared with the sanitizer harnesses
+#include "rle_scan.h"       // RLE_THREADS, rle_block_sum, rle_group_find, rle_counts_chunk: shared with rle_poly.hip
 
 namespace {
-
-constexpr int RLE_THREADS = 256;
 
 // the mask of entry s, or -1 when its index is outside [0, N) (the host never sees the indices)
 __device__ __forceinline__ long long rle_pick(const long long* sel, int s, int N) {
@@ -88,15 +88,6 @@ __device__ __forceinline__ unsigned long long rle_transitions(const unsigned lon
   return (c ^ ((c << 1) | carry)) & valid;
 }
 
-__device__ __forceinline__ unsigned rle_block_sum(unsigned v, unsigned* lds) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-  __syncthreads();      // the previous use of lds is over
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return lds[0] + lds[1] + lds[2] + lds[3];
-}
-
 // n <= 32 pixels of column x from row y on, out of the column's 64-bit words (y + n <= H)
 __device__ __forceinline__ uint32_t rle_column_bits(const unsigned long long* col, int y, int n) {
   const int j = y >> 6, o = y & 63;
@@ -112,7 +103,6 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned lo
   __shared__ unsigned red[4];
   __shared__ unsigned wsum[4], wmax[4];
   const int s = blockIdx.x, t = threadIdx.x;
-  const int lane = t & 63, wave = t >> 6;
   int32_t* row = table + (size_t)s * 4;
   if (rle_pick(sel, s, N) < 0) {
     if (t == 0) { row[0] = 0; row[1] = 3; row[2] = 0; row[3] = 0; }
@@ -164,35 +154,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned lo
       T = rle_transitions(P, q, H, HW64, &c);
       p0 = (q / (unsigned)HW64) * (unsigned)H + 64u * (q % (unsigned)HW64);
     }
-    const unsigned cnt = __popcll(T);
-    const unsigned mine = T ? p0 + (63u - (unsigned)__clzll((long long)T)) : 0u;
-    unsigned isum = cnt, imax = mine;      // inclusive scans within the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const unsigned a = __shfl_up(isum, d, 64), b = __shfl_up(imax, d, 64);
-      if (lane >= d) { isum += a; imax = imax > b ? imax : b; }
-    }
-    unsigned emax = __shfl_up(imax, 1, 64);
-    if (lane == 0) emax = 0;
-    __syncthreads();      // the previous chunk's reads of wsum / wmax are over
-    if (lane == 63) { wsum[wave] = isum; wmax[wave] = imax; }
-    __syncthreads();
-    unsigned k = rank_base + isum - cnt, prev = last_base > emax ? last_base : emax;
-    unsigned tot = 0, top = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w < wave) { k += wsum[w]; prev = prev > wmax[w] ? prev : wmax[w]; }
-      tot += wsum[w];
-      top = top > wmax[w] ? top : wmax[w];
-    }
-    while (T) {
-      const unsigned p = p0 + (unsigned)__builtin_ctzll(T);
-      T &= T - 1ull;
-      slot[k++] = p - prev;      // k < trans < n_counts <= slot_words
-      prev = p;
-    }
-    rank_base += tot;
-    last_base = last_base > top ? last_base : top;
+    rle_counts_chunk(T, p0, slot, rank_base, last_base, wsum, wmax);      // rle_scan.h; k < trans < n_counts <= slot_words
   }
   if (t == 0) slot[trans] = HW - last_base;
 }
@@ -266,18 +228,6 @@ __device__ __forceinline__ unsigned long long rle_plane_word(const uint32_t* __r
     }
   }
   return c;
-}
-
-// the last g with v[g] <= key (v non-decreasing, v[0] <= key): the image that owns entry / tile `key`; images without entries
-// share their successor's value and are passed over
-template <typename T>
-__device__ __forceinline__ int rle_group_find(const T* v, int G, T key) {
-  int lo = 0, hi = G - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (v[mid] <= key) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 // the workgroup-wide maximum of v (rle_block_sum's shape)

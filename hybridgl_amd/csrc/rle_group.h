@@ -1,6 +1,7 @@
 // The geometry of the RLE entries (csrc/rle.hip): the tiling of an image, shared by the encoder and the decoder, and what the host
 // works out of a decode call's image rows (rle_group_plan) and of a match call's (rle_match_plan) and hands to the kernels by
-// value.  Plain C++ without a HIP construct: rle.hip includes it, and so do the sanitizer harnesses
+// value, and likewise of a polygon call's (rle_poly_plan, csrc/rle_poly.hip).  Plain C++ without a HIP construct: the .hip files
+// include it, and so do the sanitizer harnesses
 // tests/native/rle_group_sanitize.cpp and tests/native/rle_match_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
@@ -198,6 +199,59 @@ static inline int rle_match_plan(const int64_t* images, int G, int Sa, int Sb, l
   plan->splits = (int)(want < 1 ? 1 : (want > RLE_MATCH_SPLITS_MAX ? RLE_MATCH_SPLITS_MAX : want));
   return 0;
 #undef RLE_MATCH_REQUIRE
+}
+
+// ---- hgl_rle_from_polygons_device (csrc/rle_poly.hip): polygons -> RLE, one workgroup per entry.  A polygon's toggle plane --
+// one bit per run-order position 0 .. H*W, H*W / 32 + 1 words -- lives in LDS when it has at most RLE_POLY_LDS_WORDS words
+// (40 KB: 480 x 640 is 9601) and in the workspace otherwise; the entry's two coverage planes always live in the workspace.
+constexpr int RLE_POLY_LDS_WORDS = 10240;
+
+struct RlePoly {
+  unsigned long long word0[RLE_GROUP_MAX];      // the 32-bit workspace word the image's first entry starts at
+  int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
+  int first[RLE_GROUP_MAX];                     // the image's first entry (non-decreasing, first[0] = 0)
+  int G;
+};
+
+// the words of one plane of an H x W entry, and the workspace words of the entry: two planes, a third when LDS cannot hold it
+static inline unsigned long long rle_poly_plane_words(long long H, long long W) { return (unsigned long long)(H * W) / 32u + 1u; }
+static inline unsigned long long rle_poly_entry_words(long long H, long long W) {
+  const unsigned long long nw = rle_poly_plane_words(H, W);
+  return nw * (nw > (unsigned long long)RLE_POLY_LDS_WORDS ? 3u : 2u);
+}
+
+// images [G,3] = (H, W, first entry) -> *geo and the 32-bit words of workspace the call needs; 0, or -1 with the reason in why.
+// Checked: 1 <= G <= 64; S >= 0; sizes with H*W < 2^31; entries from 0 to S without a step back.
+static inline int rle_poly_plan(const int64_t* images, int G, int S, RlePoly* geo, unsigned long long* words_out, char* why,
+                                size_t why_cap) {
+#define RLE_POLY_REQUIRE(cond, ...)         \
+  do {                                      \
+    if (!(cond)) {                          \
+      snprintf(why, why_cap, __VA_ARGS__);  \
+      return -1;                            \
+    }                                       \
+  } while (0)
+  RLE_POLY_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
+  RLE_POLY_REQUIRE(S >= 0, "%d entries", S);
+  memset(geo, 0, sizeof(*geo));
+  geo->G = G;
+  unsigned long long words = 0;
+  for (int g = 0; g < G; ++g) {
+    const long long H = images[3 * g], W = images[3 * g + 1], e = images[3 * g + 2];
+    const long long e_next = g + 1 < G ? images[3 * (g + 1) + 2] : (long long)S;
+    RLE_POLY_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
+                     "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
+    RLE_POLY_REQUIRE(e >= 0 && e <= e_next && e_next <= (long long)S && (g > 0 || e == 0),
+                     "image %d: entries %lld .. %lld (rows must not decrease, from 0 to S = %d)", g, e, e_next, S);
+    geo->word0[g] = words;
+    geo->H[g] = (int)H;
+    geo->W[g] = (int)W;
+    geo->first[g] = (int)e;
+    words += (unsigned long long)(e_next - e) * rle_poly_entry_words(H, W);      // < 2^31 * 3 * 2^26
+  }
+  *words_out = words;
+  return 0;
+#undef RLE_POLY_REQUIRE
 }
 
 #endif  // HGL_RLE_GROUP_H

@@ -102,6 +102,10 @@ def default_argument_parser():
                    help="with --proposals_dir: write the proposal ceiling of the store -- per sentence the stored proposal of the "
                         "largest IoU against the ground truth, {oIoU, mIoU, cum, n_sentences} as the sweep reports it -- here and "
                         "exit; no SAM, CLIP or GEM model is built (the dataset flags and --proposal_cap as in the run)")
+    p.add_argument("--device_targets", action="store_true",
+                   help="with --score_masks or --proposal_ceiling on --real REFER data: take every target's size and polygons from "
+                        "the annotations alone and rasterise them on the device, straight into run lengths "
+                        "(ops.rle_from_polygons); no image file is opened, nothing is rasterised on the host; same rows and metrics")
     p.add_argument("--sweep", default="", metavar="SPEC",
                    help="score every ref under a grid of the tail's hyper-parameters in the same pass, e.g. "
                         "'r=0.3,0.5,0.7;alpha=0:1:0.1;k1=3;k2=6': an axis is a value list or lo:hi:step (hi included), an axis "
@@ -458,6 +462,48 @@ def write_report(args, text):
     print(text)
 
 
+def check_device_targets(args):
+    """--device_targets belongs to the two branches that build no model, on REFER annotations"""
+    if not getattr(args, "device_targets", False):
+        return
+    if not (getattr(args, "score_masks", "") or getattr(args, "proposal_ceiling", "")):
+        raise SystemExit("--device_targets applies to --score_masks and --proposal_ceiling only: a run's own targets ride with its "
+                         "items")
+    if not args.real or args.dataset == "phrasecut":
+        raise SystemExit("--device_targets needs --real REFER data: the polygons come from the REFER annotations (PhraseCut's "
+                         "targets are Pillow's rasterisation of truncated vertices, the synthetic refs have no polygons)")
+
+
+def offline_targets(args, dev):
+    """((index, sentence), image id, target) of every sentence of the run that `args` describes, for the two branches that
+    build no model.  Default: the items as a run builds them, minus what only the models read -- same indices, same targets;
+    the target of a sentence is Sentence.target when set, else RefBatch.target.  --device_targets: index, sentence, image id,
+    size and polygons from the REFER annotations alone (refer_io.PolygonTarget: no image file is opened, nothing is
+    rasterised on the host); a ref whose annotation is an RLE dict keeps its pixel target."""
+    if getattr(args, "device_targets", False):
+        from .dist import shard_by_groups
+        from .loader import pin_upload
+        from .refer_io import ReferDataset
+        ds = ReferDataset(args.refer_data_root, args.dataset, split_by(args.dataset), args.split)
+        n = len(ds) if args.max_refs <= 0 else min(len(ds), args.max_refs)
+        for i in shard_by_groups([ds.image_id(k) for k in range(n)], 0, 1):      # RealRefs.jobs
+            ref = ds.refer.Refs[ds.ref_ids[i]]
+            target = ds.target_polygons(i)
+            if target is None:
+                target = pin_upload(ds.target(i), dev)
+            for j in range(min(len(ref["sent_ids"]), len(ds.sentence_raws[i]))):      # RealRefs.load's sentences
+                yield (i, j), int(ref["image_id"]), target
+        return
+    _, jobs, make = dataset_items(args, dev, 0, 1, sam_img_size=0, gem=False)
+    for i in jobs:
+        ref = make(i)
+        if ref is None:
+            continue
+        index = ref.index if ref.index is not None else i
+        for j, sent in enumerate(ref.sentences):
+            yield (index, j), ref.image_id, (sent.target if sent.target is not None else ref.target)
+
+
 def score_masks(args, dev, directory=None):
     """--score_masks DIR: the metrics of a saved run (--save_masks) from its files and the dataset's ground truth alone -- no
     model is built, no checkpoint read.  The job list and the item makers are evaluate()'s; the target of a sentence is
@@ -468,20 +514,9 @@ def score_masks(args, dev, directory=None):
     from . import dist as D
     from . import predictions as P
     resolve_defaults(args)
+    check_device_targets(args)
     records = P.load(directory or args.score_masks)
-    # the items as a run builds them, minus what only the models read: same indices, same targets
-    _, jobs, make = dataset_items(args, dev, 0, 1, sam_img_size=0, gem=False)
-
-    def targets():
-        for i in jobs:
-            ref = make(i)
-            if ref is None:
-                continue
-            index = ref.index if ref.index is not None else i
-            for j, sent in enumerate(ref.sentences):
-                yield (index, j), (sent.target if sent.target is not None else ref.target)
-
-    rows, missing, extra = P.score(records, targets())
+    rows, missing, extra = P.score(records, ((key, t) for key, _, t in offline_targets(args, dev)))
     stored = {(r["index"], r["sentence"]): [r["I"], r["U"], r["I_final"], r["U_final"]] for r in records}
     mismatches = [(int(r[0]), int(r[1])) for r in rows if stored[(int(r[0]), int(r[1]))] != [int(v) for v in r[2:6]]]
     return D.metrics_from_rows(rows), {"rows": rows, "mismatches": mismatches, "missing": missing, "extra": extra}
@@ -511,18 +546,8 @@ def proposal_ceiling(args, dev):
     from . import proposals as P
     resolve_defaults(args, loop=False)
     check_proposal_flags(args)
-    _, jobs, make = dataset_items(args, dev, 0, 1, sam_img_size=0, gem=False)
-
-    def targets():
-        for i in jobs:
-            ref = make(i)
-            if ref is None:
-                continue
-            index = ref.index if ref.index is not None else i
-            for j, sent in enumerate(ref.sentences):
-                yield (index, j), ref.image_id, (sent.target if sent.target is not None else ref.target)
-
-    rows = P.ceiling(args.proposals_dir, targets(), cap=getattr(args, "proposal_cap", 0) or None, device=dev,
+    check_device_targets(args)
+    rows = P.ceiling(args.proposals_dir, offline_targets(args, dev), cap=getattr(args, "proposal_cap", 0) or None, device=dev,
                      group=max(int(getattr(args, "group", 16) or 16), 1))
     cm = D.metrics_from_rows(rows[:, [0, 1, 3, 4, 3, 4]])
     return {"oIoU": cm["oIoU"], "mIoU": cm["mIoU"], "cum": cm["cum"][:2], "n_sentences": cm["n_sentences"]}, rows
@@ -647,6 +672,7 @@ def main(args):
                          "configs[0]) is covered by the oracle tests: python -m pytest tests -m 'not gpu'")
     rank, local_rank, world = D.env_rank()
     dev = torch.device("cuda", local_rank % torch.cuda.device_count())
+    check_device_targets(args)
     if getattr(args, "score_masks", ""):      # before any model exists: files and ground truth only
         if world > 1:
             raise SystemExit("--score_masks runs on one rank: start it without a launcher (world size 1)")

@@ -566,6 +566,77 @@ def rle_match(slots_a, table_a, slots_b, table_b, sizes, counts_a, counts_b, cro
     return inter, match_a, match_b
 
 
+POLY_RULE = {"once": 0, "any": 1}
+
+
+def rle_from_polygons(entries, sizes, counts, rule="once", slot_words=None, device=None, out=None):
+    """Polygons rasterised on the device, straight into RLE (hgl_rle_from_polygons_device on the current stream, no
+    synchronisation): what rle_encode would return for the masks refer_io.gt_mask_from_polygons gives, without the pixels.
+    entries: per entry a list of flat polygons [x0, y0, x1, y1, ...] (an entry may own none: the empty mask); the S entries
+    belong to G = len(sizes) <= 64 images, counts[g] consecutive entries of sizes[g] = (H, W), as in rle_decode_group.
+    rule: "once" = the pixels covered by exactly one polygon (the REFER target), "any" = by at least one.  slot_words: int32
+    words per entry (default the largest ceil(H*W/32) of the call: nothing is ever lost).  One pinned staging buffer holds the
+    coordinates and both offset arrays; one host -> device copy.  Returns (slots [S, slot_words] int32, table [S,4] int32 =
+    n_counts, form, area, 0 as rle_encode writes them, status [S,4] int32 = code, sum of the polygons' own areas, 0, 0; code 0
+    = rasterised, 2 = refused): three views of one flat buffer, table, slots, status in this order (`out`: a contiguous int32
+    device tensor of S * (8 + slot_words) elements to use for it).  Raises ValueError before the upload for what the host codec refuses: a coordinate that is NaN
+    or outside (-1e5, 1e5), a polygon without a vertex."""
+    import numpy as np
+    lib = _lib.load()
+    if rule not in POLY_RULE:
+        raise ValueError(f"rle_from_polygons: rule {rule!r} (one of {sorted(POLY_RULE)})")
+    if len(sizes) != len(counts):
+        raise ValueError(f"rle_from_polygons: {len(sizes)} sizes and {len(counts)} counts")
+    S, G = len(entries), len(sizes)
+    if any(int(n) < 0 for n in counts) or int(sum(int(n) for n in counts)) != S:
+        raise ValueError(f"rle_from_polygons: counts sum to {sum(counts)}, there are {S} entries")
+    polys, entry_polys = [], [0]
+    for e, entry in enumerate(entries):
+        for k, poly in enumerate(entry):
+            xy = np.asarray(poly, dtype=np.float64).reshape(-1)
+            if len(xy) < 2 or len(xy) % 2:
+                raise ValueError(f"rle_from_polygons: entry {e} polygon {k} has {len(xy)} coordinates (x, y pairs, at least one)")
+            if not bool(np.all((xy > -1.0e5) & (xy < 1.0e5))):      # false for a NaN
+                raise ValueError(f"rle_from_polygons: entry {e} polygon {k}: a coordinate is NaN or outside (-1e5, 1e5)")
+            polys.append(xy)
+        entry_polys.append(len(polys))
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    images = np.zeros((max(G, 1), 3), dtype=np.int64)
+    first = 0
+    for g, ((H, W), n) in enumerate(zip(sizes, counts)):
+        images[g] = (int(H), int(W), first)
+        first += int(n)
+    if slot_words is None:
+        slot_words = max([rle_slot_words(H, W) for H, W in sizes], default=1)
+    slot_words = int(slot_words)
+    if out is None:
+        out = torch.empty(S * (8 + slot_words), dtype=torch.int32, device=device)
+    elif out.numel() != S * (8 + slot_words):
+        raise ValueError(f"out: expected {S * (8 + slot_words)} int32 elements, got {out.numel()}")
+    slots, table = rle_split(out, S, slot_words)
+    status = out[S * (4 + slot_words):].reshape(S, 4)
+    if S == 0:
+        return slots, table, status
+    P, n_xy = len(polys), int(sum(len(p) for p in polys))
+    stage = torch.empty(8 * n_xy + 4 * (P + 1) + 4 * (S + 1), dtype=torch.uint8, pin_memory=True)
+    host = stage.numpy()
+    if P:
+        host[:8 * n_xy].view(np.float64)[:] = np.concatenate(polys)
+    off = host[8 * n_xy:].view(np.int32)
+    off[0] = 0
+    off[1:P + 1] = np.cumsum([len(p) // 2 for p in polys], dtype=np.int64)
+    off[P + 1:] = entry_polys
+    buf = stage.to(device, non_blocking=True)
+    xy_p = buf.data_ptr()
+    need = lib.hgl_rle_from_polygons_workspace_bytes(images.ctypes.data, G, S, P)
+    ws = workspace(need, device, "rle")
+    base = _dev(out, torch.int32, "out")
+    check(lib.hgl_rle_from_polygons_device(xy_p, xy_p + 8 * n_xy, P, xy_p + 8 * n_xy + 4 * (P + 1), S, images.ctypes.data, G,
+                                           POLY_RULE[rule], base + 16 * S, slot_words, base, status.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), _stream()), "hgl_rle_from_polygons_device")
+    return slots, table, status
+
+
 def score_sentence(hybrid, sentence_feat, noun_phrase_feat, other_noun_feats, boxes, gem_score,
                    logit_scale=100.0, r=0.5, k1=3, k2=6, alpha=0.6, relaword="none", has_other_nouns=False):
     """Per-sentence tail (Hybridgl_main.py:153-196,225-228).

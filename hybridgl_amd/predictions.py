@@ -111,22 +111,35 @@ def compare(a, b, device=None, batch=256):
 
 def score(records, targets, batch=32):
     """The metric rows of saved predictions against ground truth.  records: a loaded set; targets: an iterable of
-    ((index, sentence), mask [H,W] bool / uint8 device tensor) in any order.  The targets are encoded on the device
-    (ops.rle_encode) and met by the saved strings' runs in ops.rle_iou: integer counts, exact.  Returns (rows [n,6] int64 =
+    ((index, sentence), target) in any order, a target being a mask [H,W] bool / uint8 device tensor or a
+    refer_io.PolygonTarget.  Mask targets are encoded on the device (ops.rle_encode); the polygon targets of a flush are
+    rasterised on the device, straight into run lengths, by ONE ops.rle_from_polygons call and never become pixels.  Either
+    way they are met by the saved strings' runs in ops.rle_iou: integer counts, exact.  Returns (rows [n,6] int64 =
     dist.ROW_FIELDS sorted by key, missing: target keys without a record, extra: record keys without a target)."""
     import torch
     from . import ops
+    from .refer_io import PolygonTarget
     recs = _by_key(records)
     rows, missing, seen = [], [], set()
 
     def flush(H, W, items):
         keys = [k for k, _ in items]
         n = len(keys)
-        gt = torch.stack([t.reshape(H, W).to(torch.uint8) if t.dtype != torch.bool else t.reshape(H, W).view(torch.uint8)
-                          for _, t in items])
-        sel = torch.arange(n, device=gt.device).repeat(len(MASKS))
-        sg, tg = ops.rle_encode(gt, sel)
-        sp, tp = _pack([recs[k][m] for m in MASKS for k in keys], H, W, gt.device)
+        if isinstance(items[0][1], PolygonTarget):      # a flush holds one kind of target
+            s1, t1, status = ops.rle_from_polygons([t.polygons for _, t in items], [(H, W)], [n], rule="once")
+            dev = s1.device
+            status = status.cpu().numpy()
+            if (status[:, 0] != 0).any():
+                raise ValueError(f"score: the polygons of {keys[int(np.flatnonzero(status[:, 0] != 0)[0])]} are refused "
+                                 f"(status {int(status[status[:, 0] != 0][0, 0])})")
+            sg, tg = s1.repeat(len(MASKS), 1), t1.repeat(len(MASKS), 1)
+        else:
+            gt = torch.stack([t.reshape(H, W).to(torch.uint8) if t.dtype != torch.bool else t.reshape(H, W).view(torch.uint8)
+                              for _, t in items])
+            dev = gt.device
+            sel = torch.arange(n, device=dev).repeat(len(MASKS))
+            sg, tg = ops.rle_encode(gt, sel)
+        sp, tp = _pack([recs[k][m] for m in MASKS for k in keys], H, W, dev)
         iu = ops.rle_iou(sp, tp, sg, tg, H, W).cpu().numpy().reshape(len(MASKS), n, 2)
         if (iu < 0).any():
             raise ValueError(f"score: a saved mask of {keys[int(np.argwhere(iu < 0)[0][1])]} does not decode")
@@ -145,11 +158,12 @@ def score(records, targets, batch=32):
         H, W = (int(v) for v in t.shape[-2:])
         if recs[key]["size"] != [H, W]:
             raise ValueError(f"score: the record of {key} states size {recs[key]['size']}, its target is {[H, W]}")
-        q = pending.setdefault((H, W), [])
+        kind = (H, W, isinstance(t, PolygonTarget))
+        q = pending.setdefault(kind, [])
         q.append((key, t))
         if len(q) >= batch:
-            flush(H, W, pending.pop((H, W)))
-    for (H, W), q in sorted(pending.items()):
+            flush(H, W, pending.pop(kind))
+    for (H, W, _), q in sorted(pending.items()):
         flush(H, W, q)
     rows = np.asarray(sorted(rows), dtype=np.int64).reshape(-1, 6)
     return rows, sorted(missing), sorted(set(recs) - seen)

@@ -570,10 +570,13 @@ def ceiling(store, targets, cap=None, device=None, group=16):
     """The best proposal of a store per target, without CLIP or GEM: rows [n,5] int64 = (index, sentence, proposal, I, U), the
     format and the rule of HybridGLPipeline.ceiling_rows() -- per target the proposal of its image with the largest I / U,
     compared exactly, the lowest index on a tie (proposal 0 with I = 0 when none intersects); an image without a proposal
-    contributes no row, as the loop skips its refs.  targets: an iterable of ((index, sentence), image_id, mask [H,W] bool /
-    uint8 device tensor) in any order; they are encoded on the device (ops.rle_encode, as predictions.score encodes them) and
+    contributes no row, as the loop skips its refs.  targets: an iterable of ((index, sentence), image_id, target) in any order,
+    a target being a mask [H,W] bool / uint8 device tensor or a refer_io.PolygonTarget; masks are encoded on the device
+    (ops.rle_encode, as predictions.score encodes them), the polygon targets of a call are rasterised on the device, straight
+    into run lengths, by ONE ops.rle_from_polygons call and never become pixels; either way they are
     met by the stored runs in ops.rle_match, `group` images per call.  device: where to (None: where the targets are).  cap:
     the first `cap` records of every image, as StoredProposals(cap=).  Rows are sorted by (index, sentence)."""
+    from .refer_io import PolygonTarget
     store = _store(store)
     rows, runs_of, seen = [], {}, set()
 
@@ -582,6 +585,7 @@ def ceiling(store, targets, cap=None, device=None, group=16):
         for key, iid, t in items:
             by_image.setdefault(iid, []).append((key, t))
         ids, sizes, ca, cb, runs, enc = [], [], [], [], [], []
+        poly_keys, poly_entries, poly_counts = [], [], []      # the call's polygon targets, image by image
         for iid, its in by_image.items():
             H, W = (int(v) for v in its[0][1].shape[-2:])
             size, r = runs_of[iid]
@@ -589,9 +593,19 @@ def ceiling(store, targets, cap=None, device=None, group=16):
                 continue
             if size != (H, W) or any(tuple(int(v) for v in t.shape[-2:]) != (H, W) for _, t in its):
                 raise ValueError(f"proposal store {store.directory}: image {iid}: size {list(size)} differs from its target's {[H, W]}")
-            gt = torch.stack([t.reshape(H, W).to(torch.uint8) if t.dtype != torch.bool else t.reshape(H, W).view(torch.uint8)
-                              for _, t in its])
-            enc.append(ops.rle_encode(gt if device is None else gt.to(device)))
+            # an image's mask targets first, then its polygon targets: the rows carry their keys, the order is free
+            pix = [it for it in its if not isinstance(it[1], PolygonTarget)]
+            pol = [it for it in its if isinstance(it[1], PolygonTarget)]
+            by_image[iid] = its = pix + pol
+            if pix:
+                gt = torch.stack([t.reshape(H, W).to(torch.uint8) if t.dtype != torch.bool else t.reshape(H, W).view(torch.uint8)
+                                  for _, t in pix])
+                enc.append(ops.rle_encode(gt if device is None else gt.to(device)))
+            else:
+                enc.append(None)
+            poly_keys += [k for k, _ in pol]
+            poly_entries += [t.polygons for _, t in pol]
+            poly_counts.append(len(pol))
             ids.append(iid)
             sizes.append((H, W))
             ca.append(len(r))
@@ -599,7 +613,22 @@ def ceiling(store, targets, cap=None, device=None, group=16):
             runs += r
         if not ids:
             return
-        dev = enc[0][0].device
+        dev = next((e[0].device for e in enc if e is not None), device)
+        if poly_entries:
+            ps, pt, pst = ops.rle_from_polygons(poly_entries, sizes, poly_counts, rule="once", device=dev)
+            dev = ps.device
+            pst = pst.cpu().numpy()
+            if (pst[:, 0] != 0).any():
+                raise ValueError(f"ceiling: the polygons of target {poly_keys[int(np.flatnonzero(pst[:, 0] != 0)[0])]} are refused "
+                                 f"(status {int(pst[pst[:, 0] != 0][0, 0])})")
+            e, parts = 0, []
+            for own, n in zip(enc, poly_counts):      # per image: its encoded masks, then its share of the polygon set
+                if own is not None:
+                    parts.append(own)
+                if n:
+                    parts.append((ps[e:e + n], pt[e:e + n]))
+                e += n
+            enc = parts
         sw = max(int(s.shape[1]) for s, _ in enc)
         sb = torch.cat([torch.cat([s, s.new_zeros((s.shape[0], sw - s.shape[1]))], 1) for s, _ in enc]).contiguous()
         tb = torch.cat([t for _, t in enc]).contiguous()

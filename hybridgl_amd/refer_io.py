@@ -48,6 +48,21 @@ def gt_mask_from_rle(rle):
     return out, int(area.value)
 
 
+class PolygonTarget:
+    """A ground-truth target that stays its polygons: what predictions.score and proposals.ceiling take in place of a mask
+    tensor and rasterise on the device, straight into run lengths (ops.rle_from_polygons, rule "once": the pixels covered by
+    exactly one polygon, as ReferDataset.target keeps them).  A host object; `shape` is (H, W) as a mask's would be."""
+    __slots__ = ("H", "W", "polygons")
+
+    def __init__(self, H, W, polygons):
+        self.H, self.W = int(H), int(W)
+        self.polygons = [list(p) for p in polygons]
+
+    @property
+    def shape(self):
+        return (self.H, self.W)
+
+
 class REFER:
     """refer/refer.py:40-291 (the subset the evaluation loop uses)."""
 
@@ -161,6 +176,17 @@ class ReferDataset:
     def target(self, index):
         """ground truth of item `index`: the pixels covered by exactly one polygon (:112-121), uint8 [H, W]"""
         return (self.refer.getMask(self.refer.Refs[self.ref_ids[index]])["mask"] == 1).astype(np.uint8)
+
+    def target_polygons(self, index):
+        """ground truth of item `index` as a PolygonTarget -- size and polygons from the annotations alone, no image file is
+        opened and nothing is rasterised -- or None when the annotation's segmentation is an RLE dict: such a ref keeps the
+        pixel target (target())"""
+        ref = self.refer.Refs[self.ref_ids[index]]
+        seg = self.refer.refToAnn[ref["ref_id"]]["segmentation"]
+        if not (isinstance(seg, list) and len(seg) > 0 and isinstance(seg[0], list)):      # getMask's own test
+            return None
+        image = self.refer.Imgs[ref["image_id"]]
+        return PolygonTarget(image["height"], image["width"], seg)
 
     def __getitem__(self, index, sam_img=None):
         rid = self.ref_ids[index]

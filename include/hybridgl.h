@@ -780,6 +780,37 @@ int hgl_rle_match_device(const uint32_t* slots_a, long long slot_words_a, const 
                          const uint32_t* slots_b, long long slot_words_b, const int32_t* table_b, int Sb,
                          const int64_t* images_host, int G, const uint8_t* crowd_b, int32_t* inter, long long inter_elems,
                          int32_t* match_a, int32_t* match_b, void* ws, size_t ws_bytes, void* stream);
+/* Ground-truth polygons rasterised on the DEVICE, straight into RLE (csrc/rle_poly.hip): the device form of
+ * refer/external/maskApi.c:161-201 rleFrPoly and of the polygon count that refer/refer.py:283-291 takes of its masks --
+ * hgl_gt_mask_from_polygons without the pixels.  What it writes is what hgl_rle_encode_device would write for the finished
+ * masks, so the targets of an evaluation meet hgl_rle_iou_device / hgl_rle_match_device without ever being an image.
+ * Asynchronous on `stream`; no host synchronisation, no allocation; ONE launch whatever G, S, P and the sizes are (none for
+ * S = 0); two calls give the same bytes.  This is the one entry of the RLE family that uses an atomic: every crossing of the
+ * boundary walk XORs one bit, and an integer XOR does not depend on the order.
+ * xy: device doubles, the polygons' x0,y0,x1,y1,... concatenated.  point_offsets: device [P+1], polygon i owns the vertices
+ * point_offsets[i] .. point_offsets[i+1]-1.  entry_polys: device [S+1], entry s owns the polygons entry_polys[s] ..
+ * entry_polys[s+1]-1; an entry may own none and is then the empty mask (one count, H*W).
+ * images_host: HOST [G,3] int64, G <= 64, row g = (H_g, W_g, first entry) with the rules of hgl_rle_decode_group_device: entries
+ * run from 0 to S and do not decrease, an image may own none, H*W < 2^31; read before the call returns.  A bad geometry,
+ * slot_words < 1 or a rule other than 0 / 1 is HGL_EINVAL and nothing is enqueued.
+ * rule 0: the pixels covered by exactly one polygon (the REFER target, data/dataset_refer_bert.py:118-121); rule 1: the pixels
+ * covered by at least one (mask.merge / annToMask of a multi-polygon object).
+ * slots / table: hgl_rle_encode_device's contract against the entry's own H_g x W_g -- form 0 (the counts) whenever
+ * n_counts <= slot_words, form 1 (the column-major bit plane) when ceil(H*W/32) <= slot_words, form 2 otherwise;
+ * table = (true n_counts, form, area of the final mask, 0); words beyond what the form defines are not written.
+ * status: device [S,4] = (code, sum of the areas of the entry's polygons each on its own -- what hgl_gt_mask_from_polygons
+ * returns as area -- saturated at 2^31-1, 0, 0).  code 0: rasterised.  code 2: the entry is refused -- a polygon without a
+ * vertex, a coordinate that is NaN or outside (-1e5, 1e5) (the host codec's guard), polygon indices outside [0, P], or a walk
+ * of 2^31 steps or more; its table row is (0, 3, 0, 0), its area sum 0 and its slot untouched.
+ * ws: hgl_rle_from_polygons_workspace_bytes for the same geometry (HGL_EWORKSPACE when smaller): two bit planes per entry, a
+ * third for an entry whose plane of H*W + 1 bits does not fit into 40 KB of LDS.  The query returns 0 for a geometry the call
+ * refuses and for S = 0, which needs no workspace and takes ws = NULL. */
+size_t hgl_rle_from_polygons_workspace_bytes(const int64_t* images_host, int G, int S, int P);
+int hgl_rle_from_polygons_device(const double* xy, const int32_t* point_offsets, int P,
+                                 const int32_t* entry_polys, int S,
+                                 const int64_t* images_host, int G, int rule,
+                                 uint32_t* slots, long long slot_words, int32_t* table, int32_t* status,
+                                 void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

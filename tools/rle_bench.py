@@ -23,9 +23,18 @@
              chunks within its S*H*W < 2^31 limit (HIP events, median of --reps after warm-up; the pair list's time with and
              without the replication); writes profiles/rle_match_bench.json as well
 
+  polygons   (--polygons, instead of the legs above) ground truth from polygons: ONE ops.rle_from_polygons call for 64 entries of
+             480 x 640 -- the golden 40-gon scaled and shifted per entry, plus a small triangle -- as host wall time (pack, copy,
+             kernel, synchronise) and as the kernel alone (HIP events), against the path it replaces: refer_io.gt_mask_from_polygons
+             per entry + loader.pin_upload + ops.rle_encode, wall time to the synchronise; and the wall time of
+             `python -m hybridgl_amd.main --proposal_ceiling` with and without --device_targets on a synthetic on-disk REFER
+             tree (hybridgl_amd.synth.write_refer_tree, as tools/evaluator_ranks.py) with a seeded proposal store; writes
+             profiles/rle_polygons_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
     python tools/rle_bench.py --decode [--reps 30]
     python tools/rle_bench.py --match [--reps 30]
+    python tools/rle_bench.py --polygons [--reps 30] [--cli_images 100]
 """
 import argparse
 import json
@@ -248,8 +257,104 @@ def match_leg(dev, reps, H=640, W=640):
     return rec
 
 
+def polygons_leg(dev, reps, cli_images):
+    import shutil
+    import subprocess
+    import tempfile
+    from hybridgl_amd import _lib, proposals as P, refer_io
+    from hybridgl_amd.loader import pin_upload
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gold = np.load(os.path.join(root, "tests", "golden", "gtmask.npz"))
+    i = next(i for i in range(int(gold["n_cases"][0])) if tuple(gold[f"c{i}_size"]) == (480, 640))
+    H, W = 480, 640
+    xy, npts = gold[f"c{i}_xy"], gold[f"c{i}_npts"]
+    gon, tri = xy[:2 * npts[0]].reshape(-1, 2), xy[2 * npts[0]:].reshape(-1, 2)
+    rng = np.random.default_rng(1)
+    entries = []
+    for _ in range(64):
+        s, d = rng.uniform(0.5, 1.0), rng.uniform(-60, 60, 2)
+        entries.append([((gon - (320, 240)) * s + (320, 240) + d).ravel().tolist(), (tri + rng.uniform(-5, 5, 2)).ravel().tolist()])
+    sizes, counts = [(H, W)], [64]
+
+    def device_path():
+        ops.rle_from_polygons(entries, sizes, counts, device=dev)
+        torch.cuda.synchronize()
+
+    def host_path():
+        gt = torch.stack([pin_upload((refer_io.gt_mask_from_polygons(e, H, W)[0] == 1).astype(np.uint8), dev) for e in entries])
+        ops.rle_encode(gt)
+        torch.cuda.synchronize()
+
+    # the two paths agree, bit for bit
+    slots, table, status = ops.rle_from_polygons(entries, sizes, counts, device=dev)
+    gt = torch.stack([pin_upload((refer_io.gt_mask_from_polygons(e, H, W)[0] == 1).astype(np.uint8), dev) for e in entries])
+    es, et = ops.rle_encode(gt)
+    n = int(table[:, 0].max())
+    assert torch.equal(table, et) and torch.equal(slots[:, :n], es[:, :n]) and int(status[:, 0].abs().sum()) == 0
+    # the kernel alone: the ABI on buffers already on the device
+    lib = _lib.load()
+    polys = [np.asarray(p, np.float64) for e in entries for p in e]
+    d = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    xy_d = d(np.concatenate(polys), np.float64)
+    po_d = d(np.concatenate([[0], np.cumsum([len(p) // 2 for p in polys])]), np.int32)
+    ep_d = d(np.arange(0, 2 * 64 + 1, 2), np.int32)
+    images = np.asarray([[H, W, 0]], dtype=np.int64)
+    sw = ops.rle_slot_words(H, W)
+    out = torch.empty(64 * (8 + sw), dtype=torch.int32, device=dev)
+    ws = ops.workspace(lib.hgl_rle_from_polygons_workspace_bytes(images.ctypes.data, 1, 64, len(polys)), dev, "rle")
+    base = out.data_ptr()
+
+    def kernel():
+        rc = lib.hgl_rle_from_polygons_device(xy_d.data_ptr(), po_d.data_ptr(), len(polys), ep_d.data_ptr(), 64, images.ctypes.data, 1, 0,
+                                              base + 16 * 64, sw, base, base + 4 * 64 * (4 + sw), ws.data_ptr(), ws.numel(),
+                                              torch.cuda.current_stream().cuda_stream)
+        assert rc == 0
+
+    rec = {"entries": 64, "size": [H, W], "vertices_per_entry": int(npts.sum()), "counts_per_entry_max": n,
+           "device_path_wall_ms": host_ms(device_path, reps), "device_kernel_us": device_us(kernel, reps),
+           "host_path_wall_ms": host_ms(host_path, reps)}
+    rec["wall_ratio_host_over_device"] = rec["host_path_wall_ms"] / rec["device_path_wall_ms"]
+    # the CLI leg: --proposal_ceiling on an on-disk tree, with and without --device_targets (fresh child processes)
+    tree = tempfile.mkdtemp(prefix="hgl_refer_")
+    try:
+        info = synth.write_refer_tree(tree, n_images=cli_images)
+        ds = refer_io.ReferDataset(tree, "refcoco", "unc", "val")
+        store = P.ProposalStore(os.path.join(tree, "store"))
+        for img in ds.refer.data["images"]:
+            h, w = img["height"], img["width"]
+            masks = np.zeros((8, h, w), bool)
+            for k in range(8):
+                y0, x0 = int(rng.integers(0, h // 2)), int(rng.integers(0, w // 2))
+                masks[k, y0:y0 + int(rng.integers(20, h // 2)), x0:x0 + int(rng.integers(20, w // 2))] = True
+            store.write(img["id"], P.build_records(h, w, [hsam.mask_to_rle(m)["counts"] for m in masks], [int(m.sum()) for m in masks],
+                                                   np.zeros((8, 4), np.int64), np.ones(8), np.ones(8), np.zeros((8, 2)),
+                                                   np.asarray([[0, 0, w, h]] * 8)))
+        store.write_meta({})
+        argv = [sys.executable, "-m", "hybridgl_amd.main", "--real", "--refer_data_root", tree, "--dataset", "refcoco", "--split", "val",
+                "--bpe_vocab", os.path.join(tree, "bpe.txt.gz"), "--parse_json", os.path.join(tree, "parse.json"), "--heatmap", "given",
+                "--proposals_dir", store.directory, "--result_dir", os.path.join(tree, "log")]
+        env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
+        cli = {"tree": info, "proposals_per_image": 8}
+        for name, more in (("host_targets", []), ("device_targets", ["--device_targets"]), ("host_targets_again", []),
+                           ("device_targets_again", ["--device_targets"])):
+            path = os.path.join(tree, name + ".json")
+            t0 = time.perf_counter()
+            r = subprocess.run(argv + ["--proposal_ceiling", path] + more, env=env, capture_output=True, text=True, timeout=900)
+            cli[name + "_wall_s"] = time.perf_counter() - t0
+            assert r.returncode == 0, r.stderr[-2000:]
+            cli[name] = json.load(open(path))
+        assert cli["host_targets"] == cli["device_targets"]
+        rec["cli_proposal_ceiling"] = cli
+    finally:
+        shutil.rmtree(tree, ignore_errors=True)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--polygons", action="store_true",
+                    help="measure rle_from_polygons against the host codec + upload + encode; writes profiles/rle_polygons_bench.json")
+    ap.add_argument("--cli_images", type=int, default=100, help="--polygons: images of the on-disk tree of the CLI leg")
     ap.add_argument("--match", action="store_true", help="measure rle_match against the pair list; writes profiles/rle_match_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
@@ -258,6 +363,14 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "rle_bench.py needs a GPU"
     dev = torch.device("cuda:0")
+    if args.polygons:
+        out = {"polygons": polygons_leg(dev, args.reps, args.cli_images), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_polygons_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
     if args.match:
         out = {"match": match_leg(dev, args.reps), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_match_bench.json")
