@@ -54,13 +54,12 @@ __device__ __forceinline__ void uf_union(int* L, int a, int b) {
 // pixels), area[root] = pixels of the component.  (A first version kept a label per pixel and spent ~700 us per call
 // at 64 x 640 x 640 moving 105 MB int arrays through six passes; the byte passes take a fifth of that.)
 constexpr int CCL_STEPS = 16;     // steps of 64 pixels whose bytes are fetched up front (independent loads: one latency)
-struct RowScan {
-  const uint8_t* row;     // mask bytes of this image row
-  int W, holes;
+// What a scan of a row keeps, whichever form the row has (bytes: RowScan, bits: BitScan), and the arithmetic both share.
+struct ScanState {
+  int W;
   int carry;              // last non-working column of the steps done so far
   bool prev_last;         // working bit of the column just left of the current step
   int prev_last_start;    // its run start (valid when prev_last)
-  uint8_t v[CCL_STEPS + 1];   // working flags of this lane's pixel in each step of the group (+ the first of the next group)
   unsigned lo_mask, hi_mask;  // bits of the lanes below this one, per 32-bit half of a ballot
   // per step
   bool work;              // this lane's pixel is a working pixel
@@ -68,10 +67,36 @@ struct RowScan {
   int start;              // run start column of this lane's pixel (valid when work)
   bool left, right;       // working bits of the columns just left / right of this lane's pixel
 
-  __device__ __forceinline__ void init(const uint8_t* r, int W_, int holes_, int lane) {
-    row = r; W = W_; holes = holes_; carry = -1; prev_last = false; prev_last_start = 0;
+  __device__ __forceinline__ void init_state(int W_, int lane) {
+    W = W_; carry = -1; prev_last = false; prev_last_start = 0;
     lo_mask = lane < 32 ? (1u << lane) - 1u : 0xffffffffu;
     hi_mask = lane < 32 ? 0u : (1u << (lane - 32)) - 1u;
+  }
+  // run start of this lane's pixel from the ballot wb of step x0: one past the last non-working column at or below the lane.
+  // 32-bit VALU work only -- the first version shifted 64-bit masks per lane and was bound by exactly that.
+  __device__ __forceinline__ void run_start(int x0) {
+    const unsigned blo = ~(unsigned)wb & lo_mask, bhi = ~(unsigned)(wb >> 32) & hi_mask;
+    int last = carry;
+    if (blo) last = x0 + 31 - __clz(blo);
+    if (bhi) last = x0 + 63 - __clz(bhi);
+    start = last + 1;
+  }
+  // leave step x0; start63 = lane 63's run start, fetched by the scan's own means
+  __device__ __forceinline__ void advance_state(int x0, int start63) {
+    const unsigned long long nb = ~wb;
+    prev_last = (wb >> 63) != 0;
+    prev_last_start = start63;
+    if (nb) carry = x0 + 63 - __clzll(nb);                 // (all 64 working: the carry stays)
+  }
+};
+struct RowScan : ScanState {
+  const uint8_t* row;     // mask bytes of this image row
+  int holes;
+  uint8_t v[CCL_STEPS + 1];   // working flags of this lane's pixel in each step of the group (+ the first of the next group)
+
+  __device__ __forceinline__ void init(const uint8_t* r, int W_, int holes_, int lane) {
+    row = r; holes = holes_;
+    init_state(W_, lane);
   }
   // fetch the group of steps that begins at column g0
   __device__ __forceinline__ void load(int g0, int lane) {
@@ -81,28 +106,18 @@ struct RowScan {
       v[k] = x < W ? row[x] : (uint8_t)(holes ? 1 : 0);       // beyond the row: a non-working value
     }
   }
-  // step k of the group (columns x0 .. x0+63).  Needs the whole wave (ballot, neighbour exchange): 32-bit VALU
-  // work only -- the first version shifted 64-bit masks per lane and was bound by exactly that.
+  // step k of the group (columns x0 .. x0+63).  Needs the whole wave (ballot, neighbour exchange).
   __device__ __forceinline__ void step(int k, int x0, int lane) {
     work = (v[k] != 0) != (holes != 0);
     wb = __ballot(work);
-    const unsigned blo = ~(unsigned)wb & lo_mask, bhi = ~(unsigned)(wb >> 32) & hi_mask;
-    int last = carry;
-    if (blo) last = x0 + 31 - __clz(blo);
-    if (bhi) last = x0 + 63 - __clz(bhi);
-    start = last + 1;
+    run_start(x0);
     const int wi = work ? 1 : 0;
     const int up = __shfl_up(wi, 1), dn = __shfl_down(wi, 1);
     const bool next0 = (__shfl((int)v[k + 1], 0) != 0) != (holes != 0);   // lane 0 of the next step (or the look-ahead byte)
     left = lane > 0 ? up != 0 : prev_last;
     right = lane < 63 ? dn != 0 : next0;
   }
-  __device__ __forceinline__ void advance(int x0) {
-    const unsigned long long nb = ~wb;
-    prev_last = (wb >> 63) != 0;
-    prev_last_start = __shfl(start, 63);
-    if (nb) carry = x0 + 63 - __clzll(nb);                 // (all 64 working: the carry stays)
-  }
+  __device__ __forceinline__ void advance(int x0) { advance_state(x0, __shfl(start, 63)); }      // (start comes out of a ballot: per lane)
 };
 #define CCL_FOR_STEPS(scan_load, ...)                                    \
   for (int g0 = 0; g0 < W; g0 += 64 * CCL_STEPS) {                        \
@@ -116,21 +131,12 @@ struct RowScan {
 
 // The same scan over a row of WORKING BITS (64 pixels per 8-byte word, written once by pass A): the passes after the first read
 // an eighth of the bytes, the wave fetches a step's word with one scalar load, and a lane's neighbours come out of the word
-// by shifts -- no ballot, no wave shuffles.  Bits beyond the row's width are 0 (not working).  Same fields as RowScan.
-struct BitScan {
+// by shifts -- no ballot, no wave shuffles.  Bits beyond the row's width are 0 (not working).
+struct BitScan : ScanState {
   const unsigned long long* bits;   // the row's words (wave-uniform pointer)
-  int W, carry;
-  bool prev_last;
-  int prev_last_start;
-  unsigned lo_mask, hi_mask;
-  bool work;
-  unsigned long long wb;
-  int start;
-  bool left, right;
   __device__ __forceinline__ void init(const unsigned long long* b, int W_, int lane) {
-    bits = b; W = W_; carry = -1; prev_last = false; prev_last_start = 0;
-    lo_mask = lane < 32 ? (1u << lane) - 1u : 0xffffffffu;
-    hi_mask = lane < 32 ? 0u : (1u << (lane - 32)) - 1u;
+    bits = b;
+    init_state(W_, lane);
   }
   __device__ __forceinline__ void load(int, int) {}
   __device__ __forceinline__ void step(int, int x0, int lane) {
@@ -138,22 +144,38 @@ struct BitScan {
     wb = bits[wi];
     const unsigned long long nextw = x0 + 64 < W ? bits[wi + 1] : 0ull;
     work = ((wb >> lane) & 1ull) != 0;
-    const unsigned blo = ~(unsigned)wb & lo_mask, bhi = ~(unsigned)(wb >> 32) & hi_mask;
-    int last = carry;
-    if (blo) last = x0 + 31 - __clz(blo);
-    if (bhi) last = x0 + 63 - __clz(bhi);
-    start = last + 1;
+    run_start(x0);
     left = lane > 0 ? ((wb >> (lane - 1)) & 1ull) != 0 : prev_last;
     right = lane < 63 ? ((wb >> (lane + 1)) & 1ull) != 0 : (nextw & 1ull) != 0;
   }
-  __device__ __forceinline__ void advance(int x0) {
-    const unsigned long long nb = ~wb;
-    prev_last = (wb >> 63) != 0;
-    prev_last_start = __builtin_amdgcn_readlane(start, 63);
-    if (nb) carry = x0 + 63 - __clzll(nb);
-  }
+  __device__ __forceinline__ void advance(int x0) { advance_state(x0, __builtin_amdgcn_readlane(start, 63)); }   // (the word is uniform)
 };
 __device__ __forceinline__ long long ccl_words(int W) { return (W + 63) >> 6; }
+
+// The row (or row pair) of this wave: four waves per workgroup, one row each, as a uniform value.  32-bit arithmetic: the
+// grids have at most (N*H + 3) / 4 workgroups and remove_small_regions_impl admits only N*H*W < 2^31, so every row that
+// exists is below 2^31.  A wider batch needs the 64-bit form of ccl_rows_kernel here as well.
+__device__ __forceinline__ long long ccl_wave_row() {
+  return __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+}
+
+// The 8-connectivity contact rule of a row (scan c, its pixels at L index base + column) against the row below (scan d, at
+// base + W + column), for the step x0 both scans stand at.  A link is issued only at the first column where two runs touch
+// (not implied by a contact one column to the left), so a blob costs O(1) unions per row.  Every lane takes part (the
+// shuffle).  L is the strip's plane in LDS or the global plane: the function inlines, and its accesses are the caller's.
+__device__ __forceinline__ void ccl_link_below(int* L, int base, int W, const BitScan& c, const BitScan& d, int x0, int lane) {
+  const int d_up = __shfl_up(d.start, 1);
+  const int d_left_start = lane > 0 ? d_up : d.prev_last_start;           // run start of the below-left pixel
+  if (c.work) {
+    const int me = base + c.start;
+    const bool s = d.work, sw = d.left, se = d.right, w = c.left, e = c.right;
+    if (s && !(w && sw)) uf_union(L, me, base + W + d.start);
+    if (!s) {
+      if (sw && !w) uf_union(L, me, base + W + d_left_start);
+      if (se && !e) uf_union(L, me, base + W + x0 + lane + 1);   // below is not working: the run starts there
+    }
+  }
+}
 
 // Pass A -- every run start becomes its own parent and gets a zero area; the row's working bits go to the bit plane.
 __global__ __launch_bounds__(256) void ccl_rows_kernel(const uint8_t* __restrict__ masks, int holes, int W,
@@ -195,7 +217,7 @@ __global__ __launch_bounds__(256) void ccl_strip_kernel(const unsigned long long
   const long long wq = ccl_words(W);
   for (int i = threadIdx.x; i < nr * W; i += 256) Ls[i] = i;      // every pixel its own parent (only run starts are ever read)
   __syncthreads();
-  // the row pairs inside the strip (pass B's contact rules)
+  // the row pairs inside the strip
   for (int r = wave; r + 1 < nr; r += 4) {
     const int base = r * W;
     BitScan c, d;
@@ -204,17 +226,7 @@ __global__ __launch_bounds__(256) void ccl_strip_kernel(const unsigned long long
     CCL_FOR_STEPS(c.load(g0, lane); d.load(g0, lane), {
       c.step(k, x0, lane);
       d.step(k, x0, lane);
-      const int d_up = __shfl_up(d.start, 1);
-      const int d_left_start = lane > 0 ? d_up : d.prev_last_start;
-      if (c.work) {
-        const int me = base + c.start;
-        const bool s = d.work, sw = d.left, se = d.right, w = c.left, e = c.right;
-        if (s && !(w && sw)) uf_union(Ls, me, base + W + d.start);
-        if (!s) {
-          if (sw && !w) uf_union(Ls, me, base + W + d_left_start);
-          if (se && !e) uf_union(Ls, me, base + W + x0 + lane + 1);
-        }
-      }
+      ccl_link_below(Ls, base, W, c, d, x0, lane);
       c.advance(x0);
       d.advance(x0);
     })
@@ -236,14 +248,13 @@ __global__ __launch_bounds__(256) void ccl_strip_kernel(const unsigned long long
   }
 }
 
-// Pass B -- links between the runs of adjacent rows (8-connectivity).  A link is issued only at the first column
-// where two runs touch (not implied by a contact one column to the left), so a blob costs O(1) unions per row.
+// Pass B -- links between the runs of adjacent rows (8-connectivity, ccl_link_below).
 // strip_rows > 0: the row pairs inside a strip were linked by ccl_strip_kernel; wave w takes the w-th pair that straddles two
 // strips (rows strip_rows - 1 | strip_rows, 2 strip_rows - 1 | 2 strip_rows, ... of every mask).
 __global__ __launch_bounds__(256) void ccl_merge_kernel(const unsigned long long* __restrict__ bits, int* __restrict__ L, int H,
                                                         int W, long long rows, int strip_rows) {
   const int lane = threadIdx.x & 63;
-  long long row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  long long row = ccl_wave_row();
   if (strip_rows > 0) {
     const int per_mask = (H - 1) / strip_rows;             // strip boundaries inside one mask
     if (per_mask <= 0) return;
@@ -260,17 +271,7 @@ __global__ __launch_bounds__(256) void ccl_merge_kernel(const unsigned long long
   CCL_FOR_STEPS(c.load(g0, lane); d.load(g0, lane), {
     c.step(k, x0, lane);
     d.step(k, x0, lane);
-    const int d_up = __shfl_up(d.start, 1);                                // (every lane takes part in the shuffle)
-    const int d_left_start = lane > 0 ? d_up : d.prev_last_start;           // run start of the below-left pixel
-    if (c.work) {
-      const int me = (int)(base + c.start);
-      const bool s = d.work, sw = d.left, se = d.right, w = c.left, e = c.right;
-      if (s && !(w && sw)) uf_union(L, me, (int)(base + W + d.start));
-      if (!s) {
-        if (sw && !w) uf_union(L, me, (int)(base + W + d_left_start));
-        if (se && !e) uf_union(L, me, (int)(base + W + x0 + lane + 1));   // below is not working: the run starts there
-      }
-    }
+    ccl_link_below(L, (int)base, W, c, d, x0, lane);
     c.advance(x0);
     d.advance(x0);
   })
@@ -294,7 +295,7 @@ __device__ __forceinline__ int wave_sum(int v) {
 __global__ __launch_bounds__(256) void ccl_count_kernel(const unsigned long long* __restrict__ bits, int* __restrict__ L,
                                                         int* __restrict__ area, int W, long long rows) {
   const int lane = threadIdx.x & 63;
-  const long long row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  const long long row = ccl_wave_row();
   if (row >= rows) return;
   const long long base = row * W;
   BitScan c;
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256) void ccl_stats_kernel(const unsigned long long
                                                         const int* __restrict__ area, int W, long long HW, long long rows,
                                                         int thresh, int* __restrict__ stats) {
   const int lane = threadIdx.x & 63;
-  const long long row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  const long long row = ccl_wave_row();
   if (row >= rows) return;
   const long long base = row * W;
   BitScan c;
@@ -380,11 +381,10 @@ __global__ __launch_bounds__(256) void ccl_stats_kernel(const unsigned long long
   }
 }
 
-__global__ void ccl_stats_init_kernel(int* stats, int N, int* boxes) {
+__global__ void ccl_stats_init_kernel(int* stats, int N) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   stats[n * 4 + 0] = 0; stats[n * 4 + 1] = 0; stats[n * 4 + 2] = 0; stats[n * 4 + 3] = 0;
-  (void)boxes;
 }
 
 // Pass F -- holes:   out = mask | (working && area < thresh)                      (fill small holes)
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void ccl_apply_kernel(const unsigned long long
                                                         uint8_t* __restrict__ out, uint8_t* __restrict__ changed,
                                                         int* __restrict__ boxes) {
   const int lane = threadIdx.x & 63;
-  const long long row = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  const long long row = ccl_wave_row();
   if (row >= rows) return;
   const long long base = row * W;
   const unsigned long long* brow = bits + row * ccl_words(W);
@@ -535,21 +535,6 @@ size_t hgl_remove_small_regions_workspace_bytes(int N, int H, int W) {
 }
 
 static int remove_small_regions_impl(const uint8_t* masks, int N, int H, int W, int area_thresh, int holes, uint8_t* out,
-                                     uint8_t* changed, int32_t* boxes_xyxy, void* workspace, size_t workspace_bytes, void* stream);
-
-int hgl_remove_small_regions(const uint8_t* masks, int N, int H, int W, int area_thresh, int holes, uint8_t* out,
-                             uint8_t* changed, void* workspace, size_t workspace_bytes, void* stream) {
-  return remove_small_regions_impl(masks, N, H, W, area_thresh, holes, out, changed, nullptr, workspace, workspace_bytes, stream);
-}
-
-int hgl_remove_small_regions_boxes(const uint8_t* masks, int N, int H, int W, int area_thresh, int holes, uint8_t* out,
-                                   uint8_t* changed, int32_t* boxes_xyxy, void* workspace, size_t workspace_bytes, void* stream) {
-  HGL_REQUIRE(boxes_xyxy, "remove_small_regions_boxes: null boxes");
-  HGL_REQUIRE(W <= 65535, "remove_small_regions_boxes: rows of more than 65535 pixels (the per-row box words hold 16-bit columns)");
-  return remove_small_regions_impl(masks, N, H, W, area_thresh, holes, out, changed, boxes_xyxy, workspace, workspace_bytes, stream);
-}
-
-static int remove_small_regions_impl(const uint8_t* masks, int N, int H, int W, int area_thresh, int holes, uint8_t* out,
                                      uint8_t* changed, int32_t* boxes_xyxy, void* workspace, size_t workspace_bytes, void* stream) {
   HGL_TRY(hgl_require_device());
   HGL_REQUIRE(masks && out && changed && N > 0 && H > 0 && W > 0, "remove_small_regions: bad arguments");
@@ -572,7 +557,7 @@ static int remove_small_regions_impl(const uint8_t* masks, int N, int H, int W, 
   const unsigned long long* cbits = bits;
   // strips of rows linked in LDS, then only the pairs between strips globally (rows too wide for the LDS plane: the global pass alone)
   const int strip_rows = W <= CCL_STRIP_PIX / 2 ? (CCL_STRIP_PIX / W < CCL_STRIP ? CCL_STRIP_PIX / W : CCL_STRIP) : 0;
-  hipLaunchKernelGGL(ccl_stats_init_kernel, dim3((N + 255) / 256), dim3(256), 0, st, stats, N, (int*)nullptr);
+  hipLaunchKernelGGL(ccl_stats_init_kernel, dim3((N + 255) / 256), dim3(256), 0, st, stats, N);
   if (strip_rows >= 2) {
     const int strips = (H + strip_rows - 1) / strip_rows;
     hipLaunchKernelGGL(ccl_rows_kernel, grid, dim3(256), 0, st, masks, holes, W, rows, (int*)nullptr, (int*)nullptr, bits);
@@ -591,6 +576,18 @@ static int remove_small_regions_impl(const uint8_t* masks, int N, int H, int W, 
                      H, W, rows, area_thresh, out, changed, boxes_xyxy ? (int*)rowbox : nullptr);
   if (boxes_xyxy) hipLaunchKernelGGL(box_rows_kernel, dim3(N), dim3(64), 0, st, (const unsigned*)rowbox, H, (int*)boxes_xyxy);
   return hgl_check_launch("remove_small_regions");
+}
+
+int hgl_remove_small_regions(const uint8_t* masks, int N, int H, int W, int area_thresh, int holes, uint8_t* out,
+                             uint8_t* changed, void* workspace, size_t workspace_bytes, void* stream) {
+  return remove_small_regions_impl(masks, N, H, W, area_thresh, holes, out, changed, nullptr, workspace, workspace_bytes, stream);
+}
+
+int hgl_remove_small_regions_boxes(const uint8_t* masks, int N, int H, int W, int area_thresh, int holes, uint8_t* out,
+                                   uint8_t* changed, int32_t* boxes_xyxy, void* workspace, size_t workspace_bytes, void* stream) {
+  HGL_REQUIRE(boxes_xyxy, "remove_small_regions_boxes: null boxes");
+  HGL_REQUIRE(W <= 65535, "remove_small_regions_boxes: rows of more than 65535 pixels (the per-row box words hold 16-bit columns)");
+  return remove_small_regions_impl(masks, N, H, W, area_thresh, holes, out, changed, boxes_xyxy, workspace, workspace_bytes, stream);
 }
 
 int hgl_mask_boxes(const uint8_t* masks, int N, int H, int W, int32_t* boxes_xyxy, void* stream) {

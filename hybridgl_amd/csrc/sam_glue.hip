@@ -11,6 +11,7 @@
 //   sam_finalize          the filters of automatic_mask_generator.py:287-298 (the selection after them -- NMS, crop
 //                         edges, gather -- is sam_nms.hip)
 #include "hgl_common.h"
+#include "post_geom.h"
 #include <math.h>
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -686,33 +687,18 @@ struct PostArgs {
   float* full_logits;    // optional [K, H, W] (tests only) or null
 };
 
-__device__ __forceinline__ void src_idx(float scale, int dst, int in_size, int& i0, int& i1, float& l0,
-                                        float& l1) {
-  float f = fmaf(scale, dst + 0.5f, -0.5f);
-  f = f < 0.f ? 0.f : f;
-  i0 = (int)f;
-  i0 = i0 < in_size - 1 ? i0 : in_size - 1;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l1 = f - i0;
-  l0 = 1.f - l1;
-}
+// ---- the steps both kernels share (the geometry -- table constants, src_idx, the bounds of a tile -- is post_geom.h).
+// Every floating-point statement keeps its shape (same products and sums per statement: -ffp-contract=on fuses per statement,
+// and the logits of the two kernels are bit-identical, tests/test_gpu_sam.py).
 
-// One workgroup = a 64x64 tile of output pixels of one candidate; a thread computes 16 consecutive pixels of one
-// row and stores them as one 16-byte word.  The low-res logits the tile touches (a <= 48x48 patch for every
-// realistic size ratio) are staged in LDS once, so the 16 taps per pixel are LDS reads instead of scattered global
-// loads.  (The first version used 16x16 tiles with one pixel per thread: 300k workgroups whose fixed cost -- bounds,
-// staging, two barriers, the reduction, atomics -- was 95 % of the 3.3 ms the kernel took.)
-constexpr int PTW = 64, PTH = 64;   // output tile
-constexpr int PPX = 16;             // pixels per thread (one row segment)
-constexpr int PR = 48;              // max staged low-res patch side
-
-__global__ __launch_bounds__(256) void sam_postprocess_kernel(PostArgs a) {
-  __shared__ float patch[PR * PR];
-  __shared__ unsigned red[6 * 4];
-  // XCD-aware tile map.  Workgroups go to the eight XCDs round-robin in linear order (x fastest), so the ~100 tiles of ONE
-  // candidate -- whose low-res patches overlap by their bilinear halos and share 128-byte lines -- sat on all eight L2s and
-  // every L2 fetched the lines for itself: 120.5 MB fetched for 50.3 MB of low-res logits (profiles/r04i_pmc_traffic.json).
-  // Remapped so that an XCD works through whole candidates: consecutive slots of one XCD are the tiles of one candidate.
+// A workgroup's place (uniform): candidate k, the 64 x 64 tile at (X0, Y0); a thread's: its 16-pixel segment of row Y from Xb on.
+struct PostTile { int k, X0, Y0; };
+struct PostSeg { int Xb, Y; };
+// XCD-aware tile map.  Workgroups go to the eight XCDs round-robin in linear order (x fastest), so the ~100 tiles of ONE
+// candidate -- whose low-res patches overlap by their bilinear halos and share 128-byte lines -- sat on all eight L2s and
+// every L2 fetched the lines for itself: 120.5 MB fetched for 50.3 MB of low-res logits (profiles/r04i_pmc_traffic.json).
+// Remapped so that an XCD works through whole candidates: consecutive slots of one XCD are the tiles of one candidate.
+__device__ __forceinline__ PostTile post_tile_of_block() {
   int bx = blockIdx.x, by = blockIdx.y, k = blockIdx.z;
   if ((gridDim.z & 7) == 0) {
     const unsigned nt = gridDim.x * gridDim.y;
@@ -723,44 +709,148 @@ __global__ __launch_bounds__(256) void sam_postprocess_kernel(PostArgs a) {
     by = (int)(t / gridDim.x);
     bx = (int)(t - (unsigned)by * gridDim.x);
   }
+  return PostTile{k, bx * PTW, by * PTH};
+}
+__device__ __forceinline__ PostSeg post_seg_of_thread(const PostTile& t) {
   const int tx = threadIdx.x & 3, ty = threadIdx.x >> 2;
-  const int X0 = bx * PTW, Y0 = by * PTH;
-  const int Xb = X0 + tx * PPX, Y = Y0 + ty;
-  if (a.iou && a.iou_thresh > 0.f && !(a.iou[k] > a.iou_thresh)) {   // the filter exists only for thresholds > 0 (:287)
-    // filtered before any pixel work (uniform): the candidate keeps an all-zero mask
-    if (Xb < a.W && Y < a.H) {
-      const int npx = min(PPX, a.W - Xb);
-      const long long pix0 = (long long)k * a.H * a.W + (long long)Y * a.W + Xb;
-      if (npx == PPX && (pix0 & 15) == 0) {
-        const u32x4g z = {0, 0, 0, 0};
-        *(u32x4g*)(a.masks + pix0) = z;
-      } else {
-        for (int p = 0; p < npx; ++p) a.masks[pix0 + p] = 0;
-      }
-    }
-    return;
+  return PostSeg{t.X0 + tx * PPX, t.Y0 + ty};
+}
+
+// the thread's segment: is there one, how many pixels it has, where its first mask byte lies
+__device__ __forceinline__ bool post_has_pixels(const PostArgs& a, const PostSeg& q) { return q.Xb < a.W && q.Y < a.H; }
+__device__ __forceinline__ int post_npx(const PostArgs& a, const PostSeg& q) { return min(PPX, a.W - q.Xb); }
+__device__ __forceinline__ long long post_pix0(const PostArgs& a, int k, const PostSeg& q) {
+  const long long HW = (long long)a.H * a.W;
+  return (long long)k * HW + (long long)q.Y * a.W + q.Xb;
+}
+
+// a segment's mask bytes from its bits (bit p = pixel p): one 16-byte store when it is whole and aligned, bytewise otherwise
+__device__ __forceinline__ void post_store_mask(uint8_t* masks, long long pix0, int npx, unsigned bits) {
+  if (npx == PPX && (pix0 & 15) == 0) {
+    u32x4g w;
+#pragma unroll
+    for (int i = 0; i < PPX / 4; ++i)      // four bits -> four bytes: the shifted copies do not overlap, no carries
+      w[i] = (((bits >> (4 * i)) & 0xfu) * 0x00204081u) & 0x01010101u;
+    *(u32x4g*)(masks + pix0) = w;
+  } else {
+    for (int p = 0; p < npx; ++p) masks[pix0 + p] = (uint8_t)((bits >> p) & 1u);
   }
-  const int Xl = min(X0 + PTW - 1, a.W - 1), Yl = min(Y0 + PTH - 1, a.H - 1);
-  const float* L = a.low + (long long)k * a.hl * a.wl;
-  const float sy1 = (float)a.hi / (float)a.H, sx1 = (float)a.wi / (float)a.W;
-  const float s2y = (float)a.hl / (float)a.S, s2x = (float)a.wl / (float)a.S;
-  // low-res patch bounds of the tile: taps are monotone in the output coordinate
-  int i0, i1, j0, j1;
-  float f0, f1;
-  src_idx(sy1, Y0, a.hi, i0, i1, f0, f1);
-  int vb, vdummy;
-  src_idx(s2y, i0, a.hl, vb, vdummy, f0, f1);
-  src_idx(sy1, Yl, a.hi, i0, i1, f0, f1);
-  int ve0, ve;
-  src_idx(s2y, i1, a.hl, ve0, ve, f0, f1);
-  src_idx(sx1, X0, a.wi, j0, j1, f0, f1);
-  int ub, udummy;
-  src_idx(s2x, j0, a.wl, ub, udummy, f0, f1);
-  src_idx(sx1, Xl, a.wi, j0, j1, f0, f1);
-  int ue0, ue;
-  src_idx(s2x, j1, a.wl, ue0, ue, f0, f1);
-  const int ph = ve - vb + 1, pw = ue - ub + 1;
-  const bool staged = ph <= PR && pw <= PR;      // uniform
+}
+
+// A candidate the IoU filter drops is filtered before any pixel work (uniform): it keeps an all-zero mask.  The filter
+// exists only for thresholds > 0 (:287).
+__device__ __forceinline__ bool post_filtered(const PostArgs& a, int k, const PostSeg& q) {
+  if (a.iou && a.iou_thresh > 0.f && !(a.iou[k] > a.iou_thresh)) {
+    if (post_has_pixels(a, q)) post_store_mask(a.masks, post_pix0(a, k, q), post_npx(a, q), 0u);
+    return true;
+  }
+  return false;
+}
+
+// the four scales and, per axis, what the tile touches
+struct PostBounds {
+  float sy1, sx1, s2y, s2x;
+  PostAxis y, x;
+};
+__device__ __forceinline__ PostBounds post_bounds(const PostArgs& a, const PostTile& t) {
+  PostBounds g;
+  g.sy1 = post_scale(a.hi, a.H); g.sx1 = post_scale(a.wi, a.W);
+  g.s2y = post_scale(a.hl, a.S); g.s2x = post_scale(a.wl, a.S);
+  g.y = post_axis(t.Y0, post_tile_last(t.Y0, a.H), g.sy1, g.s2y, a.hi, a.hl);
+  g.x = post_axis(t.X0, post_tile_last(t.X0, a.W), g.sx1, g.s2x, a.wi, a.wl);
+  return g;
+}
+
+// the row-dependent part, shared by the thread's pixels: stage-1 rows y0, y1 of output row Y and their low-res rows
+struct PostRow {
+  float ly0, ly1;
+  int v0[2], v1[2];
+  float m0[2], m1[2];
+};
+__device__ __forceinline__ PostRow post_row(const PostArgs& a, const PostBounds& g, int Y) {
+  PostRow r;
+  int y0, y1;
+  src_idx(g.sy1, Y, a.hi, y0, y1, r.ly0, r.ly1);
+  const int tyv[2] = {y0, y1};
+#pragma unroll
+  for (int iy = 0; iy < 2; ++iy) src_idx(g.s2y, tyv[iy], a.hl, r.v0[iy], r.v1[iy], r.m0[iy], r.m1[iy]);
+  return r;
+}
+
+// what a thread gathers for its candidate's counters
+struct PostSums {
+  unsigned inter = 0, uni = 0, minx = 0x7fffffff, miny = 0x7fffffff, maxx = 0, maxy = 0, any = 0;
+};
+
+// One pixel (number p of the segment, column X) from its four stage-1 values tap[iy][ix], which each kernel fetches its own
+// way: the two blends, the threshold (bit p of the segment's mask bits), the stability counts and the box.  (The mask travels
+// as one word of bits, by value: four words of bytes handed to the store by reference took the per-pixel kernel to 66
+// registers, two more than eight waves per SIMD leave it.)
+__device__ __forceinline__ void post_pixel(const PostArgs& a, PostSums& s, unsigned& bits, const float (&tap)[2][2],
+                                           float lx0, float lx1, float ly0, float ly1, long long pix0, int p, int X) {
+  const float top = tap[0][0] * lx0 + tap[0][1] * lx1;
+  const float bot = tap[1][0] * lx0 + tap[1][1] * lx1;
+  const float v = top * ly0 + bot * ly1;
+  const bool on = v > a.thr;
+  bits |= (on ? 1u : 0u) << p;
+  if (a.full_logits) a.full_logits[pix0 + p] = v;
+  s.inter += v > a.thr + a.off;
+  s.uni += v > a.thr - a.off;
+  if (on) { s.minx = min(s.minx, (unsigned)X); s.maxx = max(s.maxx, (unsigned)X); s.any = 1; }
+}
+// ... and the end of the segment: its row in the box, its mask bytes
+__device__ __forceinline__ void post_segment_done(const PostArgs& a, PostSums& s, unsigned bits, long long pix0, int npx, int Y) {
+  if (s.any) s.miny = s.maxy = Y;
+  post_store_mask(a.masks, pix0, npx, bits);
+}
+
+// wave reduction, then one set of atomics per workgroup
+__device__ __forceinline__ void post_reduce(unsigned* counters, int k, PostSums& s) {
+  __shared__ unsigned red[6 * 4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s.inter += __shfl_xor(s.inter, o);
+    s.uni += __shfl_xor(s.uni, o);
+    s.minx = min(s.minx, (unsigned)__shfl_xor(s.minx, o));
+    s.miny = min(s.miny, (unsigned)__shfl_xor(s.miny, o));
+    s.maxx = max(s.maxx, (unsigned)__shfl_xor(s.maxx, o));
+    s.maxy = max(s.maxy, (unsigned)__shfl_xor(s.maxy, o));
+    s.any |= __shfl_xor(s.any, o);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[wave * 6 + 0] = s.inter; red[wave * 6 + 1] = s.uni;
+    red[wave * 6 + 2] = s.any ? s.minx : 0x7fffffffu; red[wave * 6 + 3] = s.any ? s.miny : 0x7fffffffu;
+    red[wave * 6 + 4] = s.any ? s.maxx : 0u; red[wave * 6 + 5] = s.any ? (s.maxy | 0x80000000u) : 0u;  // top bit: "has pixels"
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned I = 0, U = 0, mnx = 0x7fffffff, mny = 0x7fffffff, mxx = 0, mxy = 0, has = 0;
+    for (int w = 0; w < 4; ++w) {
+      I += red[w * 6]; U += red[w * 6 + 1];
+      mnx = min(mnx, red[w * 6 + 2]); mny = min(mny, red[w * 6 + 3]);
+      if (red[w * 6 + 5] & 0x80000000u) { has = 1; mxx = max(mxx, red[w * 6 + 4]); mxy = max(mxy, red[w * 6 + 5] & 0x7fffffffu); }
+    }
+    unsigned* c = counters + (long long)k * 6;
+    if (I) atomicAdd(&c[0], I);
+    if (U) atomicAdd(&c[1], U);
+    if (has) {
+      atomicMin(&c[2], mnx); atomicMin(&c[3], mny);
+      atomicMax(&c[4], mxx); atomicMax(&c[5], mxy);
+    }
+  }
+}
+
+// The per-pixel kernel: a tile stages its low-res patch (when it fits) and every pixel evaluates its sixteen taps from it.
+__global__ __launch_bounds__(256) void sam_postprocess_kernel(PostArgs a) {
+  __shared__ float patch[PR * PR];
+  const PostTile t = post_tile_of_block();
+  const PostSeg q = post_seg_of_thread(t);
+  if (post_filtered(a, t.k, q)) return;
+  const float* L = a.low + (long long)t.k * a.hl * a.wl;
+  const PostBounds g = post_bounds(a, t);
+  const int vb = g.y.low_first, ub = g.x.low_first, ph = g.y.patch, pw = g.x.patch;
+  const bool staged = post_staged(g.y, g.x);      // uniform
   if (staged) {
     for (int v = threadIdx.x >> 6; v < ph; v += 4) {       // (row, column) by shifts: no integer division per element
       const int u = threadIdx.x & 63;
@@ -772,94 +862,39 @@ __global__ __launch_bounds__(256) void sam_postprocess_kernel(PostArgs a) {
     return staged ? patch[(v - vb) * PR + (u - ub)] : L[(long long)v * a.wl + u];
   };
 
-  const long long HW = (long long)a.H * a.W;
-  unsigned inter = 0, uni = 0, minx = 0x7fffffff, miny = 0x7fffffff, maxx = 0, maxy = 0, any = 0;
-  if (Xb < a.W && Y < a.H) {
-    // row-dependent part, shared by the thread's pixels
-    int y0, y1;
-    float ly0, ly1;
-    src_idx(sy1, Y, a.hi, y0, y1, ly0, ly1);
-    const int tyv[2] = {y0, y1};
-    int v0[2], v1[2];
-    float m0[2], m1[2];
-#pragma unroll
-    for (int iy = 0; iy < 2; ++iy) src_idx(s2y, tyv[iy], a.hl, v0[iy], v1[iy], m0[iy], m1[iy]);
-    unsigned bytes[PPX / 4] = {0, 0, 0, 0};
-    const int npx = min(PPX, a.W - Xb);
-    const long long pix0 = (long long)k * HW + (long long)Y * a.W + Xb;
+  PostSums s;
+  if (post_has_pixels(a, q)) {
+    const PostRow r = post_row(a, g, q.Y);
+    unsigned bits = 0;
+    const int npx = post_npx(a, q);
+    const long long pix0 = post_pix0(a, t.k, q);
 #pragma unroll
     for (int p = 0; p < PPX; ++p) {
       if (p < npx) {
-        const int X = Xb + p;
+        const int X = q.Xb + p;
         int x0, x1;
         float lx0, lx1;
-        src_idx(sx1, X, a.wi, x0, x1, lx0, lx1);
+        src_idx(g.sx1, X, a.wi, x0, x1, lx0, lx1);
         float tap[2][2];
         const int txv[2] = {x0, x1};
 #pragma unroll
         for (int ix = 0; ix < 2; ++ix) {
           int u0, u1;
           float n0, n1;
-          src_idx(s2x, txv[ix], a.wl, u0, u1, n0, n1);
+          src_idx(g.s2x, txv[ix], a.wl, u0, u1, n0, n1);
 #pragma unroll
           for (int iy = 0; iy < 2; ++iy) {
-            const float top = ld(v0[iy], u0) * n0 + ld(v0[iy], u1) * n1;
-            const float bot = ld(v1[iy], u0) * n0 + ld(v1[iy], u1) * n1;
-            tap[iy][ix] = top * m0[iy] + bot * m1[iy];
+            const float top = ld(r.v0[iy], u0) * n0 + ld(r.v0[iy], u1) * n1;
+            const float bot = ld(r.v1[iy], u0) * n0 + ld(r.v1[iy], u1) * n1;
+            tap[iy][ix] = top * r.m0[iy] + bot * r.m1[iy];
           }
         }
-        const float top = tap[0][0] * lx0 + tap[0][1] * lx1;
-        const float bot = tap[1][0] * lx0 + tap[1][1] * lx1;
-        const float v = top * ly0 + bot * ly1;
-        const bool on = v > a.thr;
-        bytes[p >> 2] |= (on ? 1u : 0u) << (8 * (p & 3));
-        if (a.full_logits) a.full_logits[pix0 + p] = v;
-        inter += v > a.thr + a.off;
-        uni += v > a.thr - a.off;
-        if (on) { minx = min(minx, (unsigned)X); maxx = max(maxx, (unsigned)X); any = 1; }
+        post_pixel(a, s, bits, tap, lx0, lx1, r.ly0, r.ly1, pix0, p, X);
       }
     }
-    if (any) miny = maxy = Y;
-    if (npx == PPX && (pix0 & 15) == 0) {
-      u32x4g w; w[0] = bytes[0]; w[1] = bytes[1]; w[2] = bytes[2]; w[3] = bytes[3];
-      *(u32x4g*)(a.masks + pix0) = w;
-    } else {
-      for (int p = 0; p < npx; ++p) a.masks[pix0 + p] = (uint8_t)((bytes[p >> 2] >> (8 * (p & 3))) & 1u);
-    }
+    post_segment_done(a, s, bits, pix0, npx, q.Y);
   }
-  // wave reduction, then one set of atomics per workgroup
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    inter += __shfl_xor(inter, o);
-    uni += __shfl_xor(uni, o);
-    minx = min(minx, (unsigned)__shfl_xor(minx, o));
-    miny = min(miny, (unsigned)__shfl_xor(miny, o));
-    maxx = max(maxx, (unsigned)__shfl_xor(maxx, o));
-    maxy = max(maxy, (unsigned)__shfl_xor(maxy, o));
-    any |= __shfl_xor(any, o);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave * 6 + 0] = inter; red[wave * 6 + 1] = uni;
-    red[wave * 6 + 2] = any ? minx : 0x7fffffffu; red[wave * 6 + 3] = any ? miny : 0x7fffffffu;
-    red[wave * 6 + 4] = any ? maxx : 0u; red[wave * 6 + 5] = any ? (maxy | 0x80000000u) : 0u;  // top bit: "has pixels"
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned I = 0, U = 0, mnx = 0x7fffffff, mny = 0x7fffffff, mxx = 0, mxy = 0, has = 0;
-    for (int w = 0; w < 4; ++w) {
-      I += red[w * 6]; U += red[w * 6 + 1];
-      mnx = min(mnx, red[w * 6 + 2]); mny = min(mny, red[w * 6 + 3]);
-      if (red[w * 6 + 5] & 0x80000000u) { has = 1; mxx = max(mxx, red[w * 6 + 4]); mxy = max(mxy, red[w * 6 + 5] & 0x7fffffffu); }
-    }
-    unsigned* c = a.counters + (long long)k * 6;
-    if (I) atomicAdd(&c[0], I);
-    if (U) atomicAdd(&c[1], U);
-    if (has) {
-      atomicMin(&c[2], mnx); atomicMin(&c[3], mny);
-      atomicMax(&c[4], mxx); atomicMax(&c[5], mxy);
-    }
-  }
+  post_reduce(a.counters, t.k, s);
 }
 
 // The same arithmetic with the work shared inside a tile.  Stage 1 (low-res -> S x S) interpolates horizontally first:
@@ -869,70 +904,23 @@ __global__ __launch_bounds__(256) void sam_postprocess_kernel(PostArgs a) {
 // table of its stage-1 columns (u0, u1, weights) and h over (low-res rows of the patch) x (stage-1 columns of the tile) in
 // LDS; an output pixel is then 8 LDS reads and the two vertical / one horizontal blends, expression for expression those
 // of the kernel above (same products, same order, same contraction: the logits are bit-identical, tests/test_gpu_sam.py).
-// ~40 instead of ~90 instructions per pixel.  The host picks this kernel when every tile's patch / column count fits.
-constexpr int PX1 = 112;            // max stage-1 columns of a tile (64 output columns at a 1.6 : 1 size ratio: 104).  Wider
-                                    // tables (192 columns = 47 KB of LDS, for the 2.7 : 1 crops of a crop layer) measured SLOWER
-                                    // than the per-pixel kernel there (3.1 against 2.0 ms per crop): three workgroups per CU
-                                    // do not hide the load -> build -> interpolate chain of a tile.  Round 6: 32-column tiles
-                                    // (88 stage-1 columns: these tables, 128 threads) on the same crops: 3.1 ms again -- the
-                                    // table of a tile costs what its 2048 pixels save
-
+// ~40 instead of ~90 instructions per pixel.  The host picks this kernel when every tile's patch / column count fits
+// (post_sep_fits: the bounds the kernel itself computes).
 __global__ __launch_bounds__(256) void sam_postprocess_sep_kernel(PostArgs a) {
   __shared__ float patch[PR * PR];
   __shared__ float H1[PR * PX1];
   __shared__ int xc0[PTW], xc1[PTW];
   __shared__ float xl0[PTW], xl1[PTW];
-  __shared__ unsigned red[6 * 4];
-  // XCD-aware tile map (see sam_postprocess_kernel): an XCD works through whole candidates
-  int bx = blockIdx.x, by = blockIdx.y, k = blockIdx.z;
-  if ((gridDim.z & 7) == 0) {
-    const unsigned nt = gridDim.x * gridDim.y;
-    const unsigned Lb = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const unsigned c = Lb & 7u, j = Lb >> 3;
-    const unsigned t = j % nt;
-    k = (int)((j / nt) * 8u + c);
-    by = (int)(t / gridDim.x);
-    bx = (int)(t - (unsigned)by * gridDim.x);
-  }
-  const int tx = threadIdx.x & 3, ty = threadIdx.x >> 2;
-  const int X0 = bx * PTW, Y0 = by * PTH;
-  const int Xb = X0 + tx * PPX, Y = Y0 + ty;
-  if (a.iou && a.iou_thresh > 0.f && !(a.iou[k] > a.iou_thresh)) {
-    if (Xb < a.W && Y < a.H) {
-      const int npx = min(PPX, a.W - Xb);
-      const long long pix0 = (long long)k * a.H * a.W + (long long)Y * a.W + Xb;
-      if (npx == PPX && (pix0 & 15) == 0) {
-        const u32x4g z = {0, 0, 0, 0};
-        *(u32x4g*)(a.masks + pix0) = z;
-      } else {
-        for (int p = 0; p < npx; ++p) a.masks[pix0 + p] = 0;
-      }
-    }
-    return;
-  }
-  const int Xl = min(X0 + PTW - 1, a.W - 1), Yl = min(Y0 + PTH - 1, a.H - 1);
-  const float* L = a.low + (long long)k * a.hl * a.wl;
-  const float sy1 = (float)a.hi / (float)a.H, sx1 = (float)a.wi / (float)a.W;
-  const float s2y = (float)a.hl / (float)a.S, s2x = (float)a.wl / (float)a.S;
-  int i0, i1, j0, j1;
-  float f0, f1;
-  src_idx(sy1, Y0, a.hi, i0, i1, f0, f1);
-  int vb, vdummy;
-  src_idx(s2y, i0, a.hl, vb, vdummy, f0, f1);
-  src_idx(sy1, Yl, a.hi, i0, i1, f0, f1);
-  int ve0, ve;
-  src_idx(s2y, i1, a.hl, ve0, ve, f0, f1);
-  src_idx(sx1, X0, a.wi, j0, j1, f0, f1);
-  const int X1b = j0;                                    // first stage-1 column of the tile
-  int ub, udummy;
-  src_idx(s2x, j0, a.wl, ub, udummy, f0, f1);
-  src_idx(sx1, Xl, a.wi, j0, j1, f0, f1);
-  // (the host launches this kernel only when these fit, with the same IEEE arithmetic; the clamps keep a disagreement -- which
-  // cannot happen -- inside the tables)
-  const int R1w = min(j1 - X1b + 1, PX1);                // stage-1 columns of the tile
-  int ue0, ue;
-  src_idx(s2x, j1, a.wl, ue0, ue, f0, f1);
-  const int ph = min(ve - vb + 1, PR), pw = min(ue - ub + 1, PR);   // low-res patch
+  const PostTile t = post_tile_of_block();
+  const PostSeg q = post_seg_of_thread(t);
+  if (post_filtered(a, t.k, q)) return;
+  const float* L = a.low + (long long)t.k * a.hl * a.wl;
+  const PostBounds g = post_bounds(a, t);
+  // (the host launches this kernel only when these fit, by the same function; the clamps keep a disagreement -- which cannot
+  // happen -- inside the tables)
+  const int X1b = g.x.s1_first, R1w = min(g.x.s1_count, PX1);       // stage-1 columns of the tile
+  const int vb = g.y.low_first, ub = g.x.low_first;
+  const int ph = min(g.y.patch, PR), pw = min(g.x.patch, PR);       // low-res patch
   // (thread -> (row, column) by shifts: an integer division per element cost more than the element)
   for (int v = threadIdx.x >> 6; v < ph; v += 4) {
     const int u = threadIdx.x & 63;
@@ -941,7 +929,7 @@ __global__ __launch_bounds__(256) void sam_postprocess_sep_kernel(PostArgs a) {
   if (threadIdx.x < PTW) {
     int x0, x1;
     float lx0, lx1;
-    src_idx(sx1, min(X0 + (int)threadIdx.x, a.W - 1), a.wi, x0, x1, lx0, lx1);
+    src_idx(g.sx1, min(t.X0 + (int)threadIdx.x, a.W - 1), a.wi, x0, x1, lx0, lx1);
     xc0[threadIdx.x] = x0 - X1b; xc1[threadIdx.x] = x1 - X1b;
     xl0[threadIdx.x] = lx0; xl1[threadIdx.x] = lx1;
   }
@@ -954,7 +942,7 @@ __global__ __launch_bounds__(256) void sam_postprocess_sep_kernel(PostArgs a) {
     if (c < R1w) {
       int u0, u1;
       float n0, n1;
-      src_idx(s2x, X1b + c, a.wl, u0, u1, n0, n1);
+      src_idx(g.s2x, X1b + c, a.wl, u0, u1, n0, n1);
       u0 -= ub; u1 -= ub;
       for (int v = threadIdx.x >> cshift; v < ph; v += vstep) {
         const float h1 = patch[v * PR + u0] * n0 + patch[v * PR + u1] * n1;
@@ -964,30 +952,23 @@ __global__ __launch_bounds__(256) void sam_postprocess_sep_kernel(PostArgs a) {
   }
   __syncthreads();
 
-  const long long HW = (long long)a.H * a.W;
-  unsigned inter = 0, uni = 0, minx = 0x7fffffff, miny = 0x7fffffff, maxx = 0, maxy = 0, any = 0;
-  if (Xb < a.W && Y < a.H) {
-    int y0, y1;
-    float ly0, ly1;
-    src_idx(sy1, Y, a.hi, y0, y1, ly0, ly1);
-    const int tyv[2] = {y0, y1};
-    float m0[2], m1[2];
+  PostSums s;
+  if (post_has_pixels(a, q)) {
+    const PostRow r = post_row(a, g, q.Y);
     const float* r0[2];
     const float* r1[2];
 #pragma unroll
     for (int iy = 0; iy < 2; ++iy) {
-      int v0, v1;
-      src_idx(s2y, tyv[iy], a.hl, v0, v1, m0[iy], m1[iy]);
-      r0[iy] = H1 + (v0 - vb) * PX1;
-      r1[iy] = H1 + (v1 - vb) * PX1;
+      r0[iy] = H1 + (r.v0[iy] - vb) * PX1;
+      r1[iy] = H1 + (r.v1[iy] - vb) * PX1;
     }
-    unsigned bytes[PPX / 4] = {0, 0, 0, 0};
-    const int npx = min(PPX, a.W - Xb);
-    const long long pix0 = (long long)k * HW + (long long)Y * a.W + Xb;
+    unsigned bits = 0;
+    const int npx = post_npx(a, q);
+    const long long pix0 = post_pix0(a, t.k, q);
 #pragma unroll
     for (int p = 0; p < PPX; ++p) {
       if (p < npx) {
-        const int X = Xb + p, xi = tx * PPX + p;
+        const int X = q.Xb + p, xi = X - t.X0;
         const float lx0 = xl0[xi], lx1 = xl1[xi];
         const int txc[2] = {xc0[xi], xc1[xi]};
         float tap[2][2];
@@ -997,83 +978,15 @@ __global__ __launch_bounds__(256) void sam_postprocess_sep_kernel(PostArgs a) {
           for (int iy = 0; iy < 2; ++iy) {
             const float top = r0[iy][txc[ix]];
             const float bot = r1[iy][txc[ix]];
-            tap[iy][ix] = top * m0[iy] + bot * m1[iy];
+            tap[iy][ix] = top * r.m0[iy] + bot * r.m1[iy];
           }
         }
-        const float top = tap[0][0] * lx0 + tap[0][1] * lx1;
-        const float bot = tap[1][0] * lx0 + tap[1][1] * lx1;
-        const float v = top * ly0 + bot * ly1;
-        const bool on = v > a.thr;
-        bytes[p >> 2] |= (on ? 1u : 0u) << (8 * (p & 3));
-        if (a.full_logits) a.full_logits[pix0 + p] = v;
-        inter += v > a.thr + a.off;
-        uni += v > a.thr - a.off;
-        if (on) { minx = min(minx, (unsigned)X); maxx = max(maxx, (unsigned)X); any = 1; }
+        post_pixel(a, s, bits, tap, lx0, lx1, r.ly0, r.ly1, pix0, p, X);
       }
     }
-    if (any) miny = maxy = Y;
-    if (npx == PPX && (pix0 & 15) == 0) {
-      u32x4g w; w[0] = bytes[0]; w[1] = bytes[1]; w[2] = bytes[2]; w[3] = bytes[3];
-      *(u32x4g*)(a.masks + pix0) = w;
-    } else {
-      for (int p = 0; p < npx; ++p) a.masks[pix0 + p] = (uint8_t)((bytes[p >> 2] >> (8 * (p & 3))) & 1u);
-    }
+    post_segment_done(a, s, bits, pix0, npx, q.Y);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    inter += __shfl_xor(inter, o);
-    uni += __shfl_xor(uni, o);
-    minx = min(minx, (unsigned)__shfl_xor(minx, o));
-    miny = min(miny, (unsigned)__shfl_xor(miny, o));
-    maxx = max(maxx, (unsigned)__shfl_xor(maxx, o));
-    maxy = max(maxy, (unsigned)__shfl_xor(maxy, o));
-    any |= __shfl_xor(any, o);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave * 6 + 0] = inter; red[wave * 6 + 1] = uni;
-    red[wave * 6 + 2] = any ? minx : 0x7fffffffu; red[wave * 6 + 3] = any ? miny : 0x7fffffffu;
-    red[wave * 6 + 4] = any ? maxx : 0u; red[wave * 6 + 5] = any ? (maxy | 0x80000000u) : 0u;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned I = 0, U = 0, mnx = 0x7fffffff, mny = 0x7fffffff, mxx = 0, mxy = 0, has = 0;
-    for (int w = 0; w < 4; ++w) {
-      I += red[w * 6]; U += red[w * 6 + 1];
-      mnx = min(mnx, red[w * 6 + 2]); mny = min(mny, red[w * 6 + 3]);
-      if (red[w * 6 + 5] & 0x80000000u) { has = 1; mxx = max(mxx, red[w * 6 + 4]); mxy = max(mxy, red[w * 6 + 5] & 0x7fffffffu); }
-    }
-    unsigned* c = a.counters + (long long)k * 6;
-    if (I) atomicAdd(&c[0], I);
-    if (U) atomicAdd(&c[1], U);
-    if (has) {
-      atomicMin(&c[2], mnx); atomicMin(&c[3], mny);
-      atomicMax(&c[4], mxx); atomicMax(&c[5], mxy);
-    }
-  }
-}
-
-// host twin of src_idx (the same IEEE operations) and the test "does every tile of this geometry fit the shared tables"
-static void src_idx_host(float scale, int dst, int in_size, int& i0, int& i1) {
-  float f = fmaf(scale, dst + 0.5f, -0.5f);
-  f = f < 0.f ? 0.f : f;
-  i0 = (int)f;
-  i0 = i0 < in_size - 1 ? i0 : in_size - 1;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-}
-static bool postprocess_sep_fits(int out, int in1, int low, int S) {
-  const float s1 = (float)in1 / (float)out, s2 = (float)low / (float)S;
-  for (int o0 = 0; o0 < out; o0 += PTW) {
-    const int ol = (o0 + PTW - 1 < out ? o0 + PTW - 1 : out - 1);
-    int a0, a1, b0, b1, u0, u1, e0, e1;
-    src_idx_host(s1, o0, in1, a0, a1);
-    src_idx_host(s1, ol, in1, b0, b1);
-    if (b1 - a0 + 1 > PX1) return false;
-    src_idx_host(s2, a0, low, u0, u1);
-    src_idx_host(s2, b1, low, e0, e1);
-    if (e1 - u0 + 1 > PR) return false;
-  }
-  return true;
+  post_reduce(a.counters, t.k, s);
 }
 
 __global__ void init_counters_kernel(unsigned* c, int K) {
@@ -1318,7 +1231,7 @@ int hgl_sam_postprocess(const float* low_res, const float* iou_pred, int K, int 
   const char* sep_env = hgl_env_str("HGL_SAM_POST_SEP");     // "0": the per-pixel kernel (A/B in tests: bit-identical outputs)
   const bool sep_on = !(sep_env && sep_env[0] == '0');
   const dim3 grid((W + PTW - 1) / PTW, (H + PTH - 1) / PTH, K);
-  if (sep_on && postprocess_sep_fits(W, in_w, wl, img_size) && postprocess_sep_fits(H, in_h, hl, img_size))
+  if (sep_on && post_geometry_fits_sep(H, W, in_h, in_w, hl, wl, img_size))
     hipLaunchKernelGGL(sam_postprocess_sep_kernel, grid, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(sam_postprocess_kernel, grid, dim3(256), 0, st, a);

@@ -9,10 +9,11 @@ batched_mask_to_box (utils/amg.py:303-346) and the two filters of automatic_mask
 semantics with one fma: they are part of the operation's definition, pure-float64 indices differ by up to 1e-3 in logit at
 S = 1024), the four blends in float64.
 
-`classify` restates the kernels' src_idx and the host's postprocess_sep_fits in Python and says, per geometry, which kernel a
-call takes and, per 64 x 64 tile, whether the per-pixel kernel stages the tile's low-res patch in LDS or reads global memory.
-The table constants are read from sam_glue.hip, so a retune moves the expectations of tests/test_post_cases_host.py instead of
-silently moving the cases to other routes.
+`classify` restates csrc/post_geom.h (src_idx, the bounds of a tile, the fit test behind the host's choice) in Python and says,
+per geometry, which kernel a call takes and, per 64 x 64 tile, whether the per-pixel kernel stages the tile's low-res patch in
+LDS or reads global memory.  The table constants are read from post_geom.h, so a retune moves the expectations of
+tests/test_post_cases_host.py instead of silently moving the cases to other routes; the restatement itself is held against
+the header by tests/native/post_geom_routes.cpp (tests/test_post_cases_host.py).
 
 `check_outputs` judges the four production outputs (masks, boxes, stability, keep) WITHOUT the kernel's logits, so it judges
 the production configuration (full_logits == nullptr).  Tolerance: tol = 2^-20 max|low_res|.  A pixel is four nested convex
@@ -33,7 +34,7 @@ from oracle.clip_oracle import _src_index
 
 F32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAM_GLUE = os.path.join(ROOT, "hybridgl_amd", "csrc", "sam_glue.hip")
+POST_GEOM = os.path.join(ROOT, "hybridgl_amd", "csrc", "post_geom.h")
 
 MASK_THRESHOLD = 0.0            # the model's value (Sam.mask_threshold)
 UNDECIDED_CAP = 1e-3            # share of a candidate's pixels that may lie within tol of one of the three thresholds
@@ -71,8 +72,8 @@ def geom_id(g):
 
 
 # ----------------------------------------------------------------------------------------------------------- path classifier
-def table_constants(path=SAM_GLUE):
-    """PTW, PTH, PR, PX1 as csrc/sam_glue.hip declares them"""
+def table_constants(path=POST_GEOM):
+    """PTW, PTH, PR, PX1 as csrc/post_geom.h declares them"""
     src = open(path).read()
     out = {}
     for name in ("PTW", "PTH", "PR", "PX1"):
@@ -84,47 +85,34 @@ def table_constants(path=SAM_GLUE):
 
 
 def src_idx(scale, dst, in_size):
-    """src_idx / src_idx_host of sam_glue.hip for one destination index: fmaf(scale, dst + 0.5f, -0.5f) (the float64 product of
-    two float32 values is exact, so one rounding of it is the fma), clamped -> (i0, i1)"""
-    f = F32(np.float64(F32(scale)) * np.float64(F32(dst) + F32(0.5)) - 0.5)
-    f = F32(0) if f < 0 else f
-    i0 = min(int(f), in_size - 1)
-    return i0, i0 + (1 if i0 < in_size - 1 else 0)
+    """src_idx of post_geom.h for one destination index or an array of them: fmaf(scale, dst + 0.5f, -0.5f) (the float64
+    product of two float32 values is exact, so one rounding of it is the fma), clamped -> (i0, i1)"""
+    f = (np.float64(F32(scale)) * (np.asarray(dst).astype(F32) + F32(0.5)).astype(np.float64) - 0.5).astype(F32)
+    f = np.where(f < 0, F32(0), f)
+    i0 = np.minimum(f.astype(np.int64), in_size - 1)
+    return i0, i0 + (i0 < in_size - 1)
 
 
 def _scale(a, b):
     return F32(a) / F32(b)
 
 
-def sep_fits(out, in1, low, S, c=None):
-    """postprocess_sep_fits: every 64-wide strip of one axis fits the shared tables"""
-    c = c or table_constants()
-    s1, s2 = _scale(in1, out), _scale(low, S)
-    for o0 in range(0, out, c["PTW"]):
-        ol = min(o0 + c["PTW"] - 1, out - 1)
-        a0, _ = src_idx(s1, o0, in1)
-        _, b1 = src_idx(s1, ol, in1)
-        if b1 - a0 + 1 > c["PX1"]:
-            return False
-        u0, _ = src_idx(s2, a0, low)
-        _, e1 = src_idx(s2, b1, low)
-        if e1 - u0 + 1 > c["PR"]:
-            return False
-    return True
-
-
 def _axis(out, in1, low, S, tile):
     """per 64-wide strip of one axis: (stage-1 count, low-res patch side), as both kernels compute them"""
     s1, s2 = _scale(in1, out), _scale(low, S)
-    res = []
-    for o0 in range(0, out, tile):
-        ol = min(o0 + tile - 1, out - 1)
-        a0, _ = src_idx(s1, o0, in1)
-        _, b1 = src_idx(s1, ol, in1)
-        u0, _ = src_idx(s2, a0, low)
-        _, e1 = src_idx(s2, b1, low)
-        res.append((b1 - a0 + 1, e1 - u0 + 1))
-    return res
+    o0 = np.arange(0, out, tile)
+    ol = np.minimum(o0 + tile - 1, out - 1)
+    a0, _ = src_idx(s1, o0, in1)
+    _, b1 = src_idx(s1, ol, in1)
+    u0, _ = src_idx(s2, a0, low)
+    _, e1 = src_idx(s2, b1, low)
+    return [(int(n), int(m)) for n, m in zip(b1 - a0 + 1, e1 - u0 + 1)]
+
+
+def sep_fits(out, in1, low, S, c=None):
+    """post_sep_fits: every 64-wide strip of one axis fits the shared tables"""
+    c = c or table_constants()
+    return all(cols <= c["PX1"] and patch <= c["PR"] for cols, patch in _axis(out, in1, low, S, c["PTW"]))
 
 
 Tile = namedtuple("Tile", "by bx ph pw cols staged")

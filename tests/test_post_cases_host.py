@@ -1,9 +1,11 @@
 """CPU checks of the post-processing cases (tests/post_cases.py): the routes, the reference and the checker.
 
-* every geometry reaches the kernel and the tile route named beside it (the classifier restates src_idx and postprocess_sep_fits
-  of csrc/sam_glue.hip and reads the table constants from that file: a retune fails here instead of silently moving the cases),
-  and together the cases reach every route of the list: two kernels x remap on / off, staged, unstaged and mixed tiles, vector
-  and bytewise stores;
+* every geometry reaches the kernel and the tile route named beside it (the classifier restates csrc/post_geom.h and reads the
+  table constants from it: a retune fails here instead of silently moving the cases), and together the cases reach every
+  route of the list: two kernels x remap on / off, staged, unstaged and mixed tiles, vector and bytewise stores;
+* the restatement equals the header: tests/native/post_geom_routes.cpp, a stand-alone program over post_geom.h built with g++
+  under AddressSanitizer + UndefinedBehaviorSanitizer, gives the same kernel and the same tiles for all 18 geometries, and the
+  same fit decision, strip counts and source indices for every output extent from 1 to 1100 on each axis combination in use;
 * the float64-blend reference agrees within tol = 2^-20 max|low_res| with the two float32 CPU implementations of the operation,
   torch's F.interpolate and oracle/sam_oracle.py:postprocess_masks, on every geometry (printed with -s);
 * the checker accepts, on every case, the outputs derived from the torch float32 result -- a correct implementation passes --
@@ -12,6 +14,9 @@
 * the share of undecided pixels stays below the cap for the committed seeds.
 """
 import functools
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -65,6 +70,79 @@ def test_geometry_reaches_its_route(gid):
         assert r.max_cols <= c["PX1"] and r.max_patch <= c["PR"] and r.n_unstaged == 0
     assert len(r.tiles) == -(-g.orig[0] // c["PTH"]) * -(-g.orig[1] // c["PTW"])
     assert g.inp[0] <= g.S and g.inp[1] <= g.S
+
+
+# ------------------------------------------------------------------------------- the restatement against csrc/post_geom.h
+SWEEP = range(1, 1101)
+
+
+@pytest.fixture(scope="module")
+def routes(tmp_path_factory):
+    """-> run(requests) -> (lines of text, int16 array of index pairs): the stand-alone program over post_geom.h"""
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    d = tmp_path_factory.mktemp("post_geom_routes")
+    exe = d / "post_geom_routes"
+    # -ffp-contract=off: src_idx's one fma is written as fmaf; nothing else may fuse
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           os.path.join(P.ROOT, "tests", "native", "post_geom_routes.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+    def run(requests):
+        src, dst = d / "requests.txt", d / "indices.bin"
+        src.write_text("".join(q + "\n" for q in requests))
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+        r = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, (r.returncode, r.stderr[-3000:])
+        lines = r.stdout.splitlines()
+        c = P.table_constants()
+        assert lines[0].split() == ["C", str(c["PTW"]), str(c["PTH"]), "16", str(c["PR"]), str(c["PX1"])]
+        assert len(lines) == 1 + len(requests)
+        return lines[1:], np.fromfile(dst, dtype=np.int16)
+    return run
+
+
+def test_the_header_chooses_the_kernel_and_bounds_the_tiles_as_classify_says(routes):
+    c = P.table_constants()
+    lines, _ = routes([f"G {g.orig[0]} {g.orig[1]} {g.inp[0]} {g.inp[1]} {g.S} {g.low}" for g in P.GEOMS])
+    assert len(lines) == len(P.GEOMS) == 18
+    for g, line in zip(P.GEOMS, lines):
+        r = P.classify(g, c)
+        want = ["G", int(r.sep), len(r.tiles)] + [int(v) for t in r.tiles for v in t]
+        assert line.split() == [str(v) for v in want], (P.geom_id(g), line[:200])
+
+
+def test_the_header_agrees_on_every_extent_from_1_to_1100(routes):
+    """per axis: the (crop, low-res, plane) combinations of GEOMS against every output extent -- the fit decision, the stage-1
+    count and the patch side of every strip, and src_idx index for index (output -> stage 1 and stage 1 -> low-res)"""
+    c = P.table_constants()
+    combos = sorted({(g.inp[ax], g.low, g.S) for g in P.GEOMS for ax in (0, 1)})
+    assert len(combos) >= 10 and {g.orig[ax] for g in P.GEOMS for ax in (0, 1)} <= set(SWEEP)
+    req = [f"L {crop} {low} {S}" for crop, low, S in combos]
+    req += [f"A {out} {crop} {low} {S}" for crop, low, S in combos for out in SWEEP]
+    lines, idx = routes(req)
+    o, fits = 0, 0
+    for (crop, low, S), line in zip(combos, lines):
+        assert line.split() == ["L", str(crop)]
+        i0, i1 = P.src_idx(P._scale(low, S), np.arange(crop), low)
+        assert np.array_equal(idx[o:o + 2 * crop].reshape(crop, 2), np.stack([i0, i1], 1)), (crop, low, S)
+        o += 2 * crop
+    k = len(combos)
+    for crop, low, S in combos:
+        for out in SWEEP:
+            strips = P._axis(out, crop, low, S, c["PTW"])
+            fit = P.sep_fits(out, crop, low, S, c)
+            want = ["A", int(fit), len(strips)] + [v for s in strips for v in s]
+            assert lines[k].split() == [str(v) for v in want], (out, crop, low, S, lines[k][:200])
+            i0, i1 = P.src_idx(P._scale(crop, out), np.arange(out), crop)
+            assert np.array_equal(idx[o:o + 2 * out].reshape(out, 2), np.stack([i0, i1], 1)), (out, crop, low, S)
+            o += 2 * out
+            k += 1
+            fits += fit
+    assert o == len(idx) and k == len(lines)
+    assert 0 < fits < len(combos) * len(SWEEP)              # both decisions occur
 
 
 def test_the_boundaries_and_tile_counts_are_the_named_ones():
