@@ -134,6 +134,7 @@ PROTOTYPES = {
     "hgl_gemm_f16x3_select": (_I, [_I]),
     "hgl_split_overflow_count": (_I, [_I, C.POINTER(C.c_ulonglong)]),
     "hgl_split_overflow_peek_async": (_I, [_VP, _VP]),
+    "hgl_split_overflow_snapshot_async": (_I, [_VP, _VP]),
     "hgl_register_split_weight": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP]),
     "hgl_unregister_split_weight": (_I, [_VP]),
     "hgl_split_weight_is_fp16_valued": (_I, [_VP]),

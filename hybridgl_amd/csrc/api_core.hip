@@ -117,6 +117,21 @@ int hgl_split_overflow_peek_async(unsigned int* host2, void* stream) {
   return HGL_OK;
 }
 
+// All three counters (GEMM, attention, SAM decoder) in stream order into three words of PINNED host memory: no wait, no
+// reset.  The peek above leaves the decoder unit's counter out (i2t_prep_kernel's guarded split, sam_decoder_t2i.hip); a
+// caller that re-runs work on a moved total needs every unit, or a decoder overflow surfaces at the blocking count only.
+int hgl_split_overflow_snapshot_async(unsigned int* host3, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(host3 != nullptr, "split_overflow_snapshot_async: null argument");
+  if (hgl_split_overflow_gemm_peek(host3, (hipStream_t)stream) != 0 ||
+      hgl_split_overflow_attention_peek(host3 + 1, (hipStream_t)stream) != 0 ||
+      hgl_split_overflow_decoder_peek(host3 + 2, (hipStream_t)stream) != 0) {
+    hgl_set_error("split_overflow_snapshot_async: hipMemcpyFromSymbolAsync failed");
+    return HGL_ELAUNCH;
+  }
+  return HGL_OK;
+}
+
 int hgl_abi_version(void) { return HGL_ABI_VERSION; }
 const char* hgl_last_error(void) { return g_err; }
 

@@ -443,6 +443,7 @@ int hgl_launch_t2i_raw_attn(const void* Qh, const void* Ql, const float* bias, c
 int hgl_launch_i2t_prep(const float* k1, const float* v1, const float* Wq, const float* bq, const float* Wo, float scale, void* Kh,
                         void* Kl, float* cb, void* Uh, void* Ul, int P, hipStream_t st);
 unsigned long long hgl_split_overflow_decoder(int reset);
+int hgl_split_overflow_decoder_peek(unsigned int* dst, hipStream_t st);
 int hgl_launch_dec_i2t_fold(const void* Xh, const void* Xl, const void* Kh, const void* Kl, const float* pek, const float* cb,
                             const void* Uh, const void* Ul, const float* bo, const float* ln_w, const float* ln_b, float eps, int P,
                             int HW, void* out_hi, void* out_lo, hipStream_t st);

@@ -642,6 +642,7 @@ int hgl_launch_i2t_prep(const float* k1, const float* v1, const float* Wq, const
   return hgl_check_launch("i2t_prep");
 }
 
+// (the blocking reader and hgl_split_overflow_decoder_peek, the stream-ordered one of hgl_split_overflow_snapshot_async)
 HGL_DEFINE_SPLIT_OVERFLOW_READER(hgl_split_overflow_decoder)
 
 int hgl_launch_dec_i2t_fold(const void* Xh, const void* Xl, const void* Kh, const void* Kl, const float* pek, const float* cb,

@@ -80,6 +80,9 @@ def default_argument_parser():
     p.add_argument("--precision", default=None, choices=["f16x3", "f32", "f16"],
                    help="arithmetic of the encoders (default: HYBRIDGL_PRECISION, else f16x3); f16 = fp16 GEMM operands with fp32 "
                         "accumulation, opt-in and not fp32-class")
+    p.add_argument("--on_overflow", default="raise", choices=["raise", "rescue"],
+                   help="an activation beyond the fp16 range in f16x3 / f16 mode: raise = stop at the offending group (rerun with "
+                        "--precision f32); rescue = run the groups that were in flight again in f32 and go on (grouped loop only)")
     p.add_argument("--stats_json", default="", help="rank 0 writes {stats, metrics} of the run here (throughput, loader wait)")
     p.add_argument("--k_clamp", default="auto", choices=["auto", "persistent", "per_ref"],
                    help="the k1 / k2 clamp of Hybridgl_main.py:178-181: persistent = the reference's quirk (once an image yields "
@@ -390,6 +393,9 @@ def check_proposal_flags(args):
         raise SystemExit("--save_proposals and --proposals_dir exclude each other: a run either writes a store or reads one")
     if (save or read) and not args.real:
         raise SystemExit("--save_proposals / --proposals_dir need --real: a store is keyed by the dataset's image ids")
+    if save and getattr(args, "on_overflow", "raise") == "rescue":
+        raise SystemExit("--save_proposals and --on_overflow rescue exclude each other: the store would keep the proposals of a pass "
+                         "that a rescue rolls back and runs again in f32; write the store with --on_overflow raise")
     if read and getattr(args, "prepare", False):
         raise SystemExit("--prepare rehearses the loop on synthetic images, which a proposal store does not hold: drop one of "
                          "--prepare and --proposals_dir")
@@ -442,15 +448,18 @@ def dataset_items(args, dev, rank=0, world=1, sam_img_size=0, gem=False):
     return None, D.shard_indices(args.synthetic, rank, world), make
 
 
-def report_text(args, m, precision=None):
-    """the result lines of Hybridgl_main.py:233-248 / Hybridgl_main_PhraseCut.py:224-238"""
+def report_text(args, m, precision=None, rescued=None):
+    """the result lines of Hybridgl_main.py:233-248 / Hybridgl_main_PhraseCut.py:224-238; rescued: HybridGLPipeline.rescue_stats,
+    a line of its own when a rescue happened"""
     pc = args.dataset == "phrasecut"
     return (f"\n\n fusion_mode={args.fusion_mode} "
             + (f"\nDataset: PhraseCut / {args.split}" if pc else f"\nDataset: {args.dataset} / {args.split} / {split_by(args.dataset)}") +
             f"\nOverall IoU / mean IoU"
             f"\npure hybridgl: {m['oIoU']:.2f} / {m['mIoU']:.2f}"
             f"\nhybridgl w/ spatial guidance: {m['oIoU_final']:.2f} / {m['mIoU_final']:.2f}"
-            + (f"\nprecision: {precision}" if precision is not None else ""))
+            + (f"\nprecision: {precision}" if precision is not None else "")
+            + (f"\nfp16 range: {rescued['events']} overflow(s) rescued, {rescued['refs']} refs in {rescued['groups']} groups re-run in f32"
+               if rescued and rescued.get("events", 0) > 0 else ""))
 
 
 def write_report(args, text):
@@ -614,7 +623,8 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
         recorder = gen = ProposalRecorder(gen, args.save_proposals, generator_settings(
             gen, sam_model=args.sam_model, precision=getattr(args, "precision", None), proposal_cap=getattr(args, "proposal_cap", 0)))
     pipe = HybridGLPipeline(model, fusion_mode=args.fusion_mode, masking_block=getattr(args, "masking_block", 9), mask_generator=gen,
-                            use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir), sweep=sweep)
+                            use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir), sweep=sweep,
+                            on_overflow=getattr(args, "on_overflow", "raise"))
     rr, jobs, make = dataset_items(args, dev, rank, world, sam_img_size=1024 if gen else 0, gem=gem_model is not None)
     if rr is not None and getattr(gen, "prefetch", None) is not None:
         rr.proposals = gen      # files, JSON and run lengths are the loader threads' work
@@ -652,7 +662,9 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
     stats = {"refs": n, "seconds": dt, "seconds_job": D.max_over_ranks(dt, dist, dev), "loader_wait_s": loader.wait_s, "loader_make_s": loader.make_s,
              "images_decoded": rr.decoded if rr is not None else None, "image_cache_hits": pipe.cache_hits,
              "skipped": getattr(pipe, "skipped", 0), "groups": getattr(pipe, "groups_run", None),
-             "workers": args.workers, "group": args.group}
+             "workers": args.workers, "group": args.group,
+             # this rank's own (ranks rescue independently); zeros without --on_overflow rescue
+             "split_overflow_rescued": dict(pipe.rescue_stats, positions=list(pipe.rescue_stats["positions"]))}
     if recorder is not None:
         stats["proposals_saved"] = recorder.written
     if getattr(args, "proposals_dir", ""):
@@ -718,7 +730,7 @@ def main(args):
         stats["precision"] = args.precision
         stats["host_cores_per_rank"] = len(cores) if cores else len(os.sched_getaffinity(0))
         json.dump({"stats": stats, "metrics": m}, open(args.stats_json, "w"))
-    write_report(args, report_text(args, m, args.precision))
+    write_report(args, report_text(args, m, args.precision, stats.get("split_overflow_rescued")))
     return m
 
 

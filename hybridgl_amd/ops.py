@@ -117,6 +117,40 @@ def split_mode(mode):
 
 
 _precision_now = None
+_precision_forced = None
+
+
+def effective_precision(mode):
+    """the precision a model that carries `mode` runs in right now: the forced one inside forced_precision, else its own
+    (use_precision's rule; no Python-side choice of buffers or entries depends on the mode, the library reads its own)"""
+    return mode if _precision_forced is None else _precision_forced
+
+
+class forced_precision:
+    """Context manager: while active, use_precision(m) sets `mode` whatever m is, so every model of the process runs in
+    `mode` whatever it was built in (the weights' fp16 splits stay registered and are simply not read in 'f32').  On exit the
+    library is back in the mode it was in on entry, so a bare ops.* call behind the context runs as one in front of it did; the
+    next model re-asserts its own as always.  Not re-entrant across threads: the library keeps ONE current mode."""
+
+    def __init__(self, mode):
+        if mode not in PRECISIONS:
+            raise ValueError(f"precision {mode!r}: expected one of {sorted(PRECISIONS)}")
+        self.mode = mode
+
+    def __enter__(self):
+        global _precision_forced
+        self._outer, self._was = _precision_forced, _precision_now
+        _precision_forced = self.mode
+        use_precision(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        global _precision_forced
+        _precision_forced = self._outer
+        back = self._outer if self._outer is not None else self._was
+        if back is not None:
+            use_precision(back)
+        return False
 
 
 def set_precision(mode):
@@ -132,7 +166,9 @@ def set_precision(mode):
 
 
 def use_precision(mode):
-    """make `mode` the library's current precision if it is not already (called on entry by every model method)"""
+    """make `mode` the library's current precision if it is not already (called on entry by every model method); inside
+    forced_precision the forced mode takes its place"""
+    mode = effective_precision(mode)
     if mode != _precision_now:
         set_precision(mode)
 
@@ -152,6 +188,14 @@ def split_overflow_peek(buf):
     wait, no reset.  Read buf after an event recorded behind this call has completed."""
     assert buf.is_pinned() and buf.dtype == torch.int32 and buf.numel() >= 2
     check(_lib.load().hgl_split_overflow_peek_async(buf.data_ptr(), _stream()), "hgl_split_overflow_peek_async")
+
+
+def split_overflow_snapshot(buf):
+    """Enqueue, on the current stream, a copy of ALL THREE overflow counters (GEMM, attention, SAM decoder) into `buf` (pinned
+    int32 [3] host tensor): no wait, no reset (hgl_split_overflow_snapshot_async).  Their sum is split_overflow_count(reset=
+    False) as of this point of the stream.  Read buf after an event recorded behind this call has completed."""
+    assert buf.is_pinned() and buf.dtype == torch.int32 and buf.numel() >= 3
+    check(_lib.load().hgl_split_overflow_snapshot_async(buf.data_ptr(), _stream()), "hgl_split_overflow_snapshot_async")
 
 
 class SplitOverflow(_lib.HybridGLError):

@@ -117,7 +117,8 @@ def _side_streams(device):
 class HybridGLPipeline:
     def __init__(self, model, fusion_mode="G2L", masking_block=9, r=0.5, alpha=0.6, k1=3, k2=6, res=224,
                  mask_generator=None, use_sam_masks=False, fixed_proposals=None, cleanup_given_masks=False,
-                 gem_model=None, k_clamp="persistent", image_cache=32, record_predictions=False, sweep=None):
+                 gem_model=None, k_clamp="persistent", image_cache=32, record_predictions=False, sweep=None,
+                 on_overflow="raise"):
         """mask_generator: a hybridgl_amd.sam.SamAutomaticMaskGenerator; when given, every step runs the
         SAM proposal stage (encoder, decoder, post-processing, NMS) on ref.sam_img first.
         use_sam_masks=False keeps ref.masks for the CLIP stage (fixed N; synthetic benchmark, where
@@ -132,9 +133,19 @@ class HybridGLPipeline:
         sweep: a list of (r, alpha, k1, k2): every fused tail is followed by ONE ops.score_group_sweep call on the same operands
         that scores them under all these configurations (each with its own k1 / k2 under the k_clamp rule) and counts the
         proposal ceiling; sweep_rows() / ceiling_rows() / sweep_metrics() report them.  The pipeline's own configuration runs
-        exactly as without a sweep.  A ref the fused tail cannot serve raises ValueError then."""
+        exactly as without a sweep.  A ref the fused tail cannot serve raises ValueError then.
+        on_overflow: what run() does when an activation leaves the fp16 range in f16x3 / f16 mode.  "raise" (default): it
+        raises ops.SplitOverflow at the offending group.  "rescue": the groups that were in flight are run again in f32 and
+        the loop goes on (run()'s docstring; rescue_stats); step() and metrics() are the same in both modes."""
         if k_clamp not in ("persistent", "per_ref"):
             raise ValueError("k_clamp must be 'persistent' or 'per_ref'")
+        if on_overflow not in ("raise", "rescue"):
+            raise ValueError("on_overflow must be 'raise' or 'rescue'")
+        self.on_overflow = on_overflow
+        # run(on_overflow="rescue"): moved totals met, groups / refs done again in f32, and those refs' dataset positions
+        self.rescue_stats = {"events": 0, "groups": 0, "refs": 0, "positions": []}
+        self._rescue_bufs = []    # pinned int32 [3] snapshot buffers that are free
+        self._rs = None           # the running loop's rescue state
         # run(): proposals, hybrid features and GEM features of the last `image_cache` images with an image_id (the dataset
         # yields one item per REF, Hybridgl_main.py:79, and the refs of an image are not always neighbours: RefCOCO has 2.6
         # refs per image).  0 = off.  Entries are device tensors: ~25 MB per 640 x 480 image with 64 proposals.
@@ -492,11 +503,9 @@ class HybridGLPipeline:
                                gem=use_gem, device_blur=True)[0] for j in range(min(group, 4))]
         if self.record_predictions:      # what the loop has recorded so far is filed before the rehearsal's records are dropped
             self._harvest_predictions(wait=True)
-        keep = (self.cum.clone(), list(self.iu_log), list(self.iu_owner), list(self.idx_log), self._n_refs,
-                getattr(self, "skipped", 0), getattr(self, "groups_run", 0), dict(self._img_cache), self.cache_hits,
-                (self.k1, self.k2), getattr(self, "group_marks", None), getattr(self, "stage_marks", None), len(self._pred_done))
-        if self.sweep is not None:
-            keep_sweep = (self.sweep_cum.clone(), self.sweep_cum_ceiling.clone(), list(self._sweep_log), self._sweep_k)
+        keep = self._checkpoint()
+        extras = (getattr(self, "groups_run", 0), getattr(self, "group_marks", None), getattr(self, "stage_marks", None),
+                  dict(self.rescue_stats, positions=list(self.rescue_stats["positions"])))
         self.group_marks = self.stage_marks = None
         cap = proposals if (gen is not None and self.use_sam_masks) else None
         try:
@@ -526,19 +535,8 @@ class HybridGLPipeline:
                         del blocks
             torch.cuda.synchronize(dev)
         finally:
-            self.cum.copy_(keep[0])
-            self.iu_log[:], self.iu_owner[:], self.idx_log[:] = keep[1], keep[2], keep[3]
-            self._n_refs, self.skipped, self.groups_run = keep[4], keep[5], keep[6]
-            self._img_cache, self.cache_hits = keep[7], keep[8]
-            self.k1, self.k2 = keep[9]
-            self.group_marks, self.stage_marks = keep[10], keep[11]
-            if self.sweep is not None:
-                self.sweep_cum.copy_(keep_sweep[0])
-                self.sweep_cum_ceiling.copy_(keep_sweep[1])
-                self._sweep_log[:], self._sweep_k = keep_sweep[2], keep_sweep[3]
-            if self.record_predictions:      # the staging buffers stay (sized for this geometry), the records go
-                self._harvest_predictions(wait=True)
-                del self._pred_done[keep[12]:]
+            self._rollback(keep)      # (the predictions' staging buffers stay, sized for this geometry; the records go)
+            self.groups_run, self.group_marks, self.stage_marks, self.rescue_stats = extras
         return self
 
     def run(self, loader, group=16, proposal_cap=None, collect=False, serial=False, total=None):
@@ -560,7 +558,19 @@ class HybridGLPipeline:
         reference would fail on them).  Returns the number of refs scored; collect=True also keeps step()'s per-ref
         return values in self.collected.  serial=True: the same work with every stage on the CURRENT stream, back to back
         (per-kernel timing with events on one stream).  total: the number of items the loader will yield, when known -- the
-        groups are then equally full (balanced_group) instead of full groups and a remainder."""
+        groups are then equally full (balanced_group) instead of full groups and a remainder.
+
+        on_overflow="rescue" (and a model in f16x3 / f16): every group is a transaction (hybridgl_amd/rescue.py).  Behind
+        each CLIP stage the CLIP stream waits for the proposal stage beside it and copies the three range counters to pinned
+        memory (ops.split_overflow_snapshot); the next proposal stage starts behind that copy, so the copy sees the same
+        work in every run.  The host reads it one group later.  An unchanged total commits the group; a moved one drains the
+        device, rolls the logs, accumulators, clamp and image cache back to the checkpoint before the oldest uncommitted
+        group (at most three are), clears the counters and runs those groups again under ops.forced_precision("f32"),
+        serially on the current stream, proposal stage included.  The loop then goes on in the models' own precision with an
+        empty pipeline.  What the f32 re-run files in the image cache is used by later groups like any other entry.
+        run() ends by waiting for the verdict on its last groups.  A ProposalRecorder as the generator is refused in this mode
+        (ValueError): its files are no part of the roll-back.  self.rescue_stats counts events, groups, refs and the
+        dataset positions done again; groups_run counts the loop's groups, not re-runs."""
         gen = self.mask_generator
         if total is not None:
             group = self.balanced_group(total, group)
@@ -570,100 +580,306 @@ class HybridGLPipeline:
             s_sam = s_clip = cur
         else:
             s_sam, s_clip = self._streams()
+        led = None
+        if self._rescue_wanted():
+            from .proposals import ProposalRecorder
+            from .rescue import RescueLedger
+            if isinstance(gen, ProposalRecorder):
+                # its files and its list of the images it has written are no part of _checkpoint / _rollback: the store would
+                # keep the proposals of the pass a rescue has just rejected
+                raise ValueError("on_overflow='rescue' cannot run with a ProposalRecorder (--save_proposals): a rolled-back group's "
+                                 "proposals would stay in the store; record the store with on_overflow='raise'")
+            led = RescueLedger()
+            # the total the loop starts from, in stream order before anything of this run
+            self._rs = dict(snaps=[], gate=None, base=self._snapshot(None, cur), cap=proposal_cap, group=group, cur=cur,
+                            s_sam=s_sam, s_clip=s_clip, serial=bool(serial))
+        if not serial:
             self._ev.record(cur)
             s_sam.wait_event(self._ev)
             s_clip.wait_event(self._ev)
         self.collected = [] if collect else None
         self.skipped = getattr(self, "skipped", 0)
-        done = 0
+        self._done = 0
         pending = None
         self.groups_run = getattr(self, "groups_run", 0)
         # items of one image are merged into a unit only when the proposals come from the generator (then they are a function
         # of the image); with given proposals every item keeps its own masks / boxes, as step() does
-        for units in self._units(loader, group, merge=gen is not None and self.use_sam_masks):
-            self.groups_run += 1
-            if getattr(self, "group_marks", None) is not None:      # host-side stamp of every group boundary (tools/first_use.py)
-                import time
-                self.group_marks.append(time.perf_counter())
-            produced = None
-            if not serial:      # items a lazy loader built on the caller's stream just now
-                produced = torch.cuda.Event()
-                produced.record(cur)
-            for u in units:
-                for r in u:
-                    _adopt(r, (s_sam, s_clip), produced)
-            state = None
-            ev_enc = None
-            # images seen lately (or in the group whose CLIP stage is about to be enqueued: it files them before this
-            # group's CLIP stage looks): no proposal stage, no hybrid forward for them
-            cached = [False] * len(units)
-            held = [None] * len(units)      # the cache entry itself, pinned at look-up (a later put may evict it from the dict)
-            if self.image_cache > 0 and gen is not None and self.use_sam_masks:
-                self._cache_cap = max(self.image_cache, 2 * group)
-                in_pending = {u[0].image_id for u in pending[0]} if pending is not None else set()
-                for i, u in enumerate(units):
-                    iid = u[0].image_id
-                    if iid is None:
-                        continue
-                    if iid in self._img_cache:
-                        cached[i], held[i] = True, ("entry", self._img_cache[iid])
-                    elif iid in in_pending:
-                        cached[i], held[i] = True, ("late",)
-            fresh = [i for i, c in enumerate(cached) if not c]
-            if gen is not None and fresh:
-                with torch.cuda.stream(s_sam):
-                    self._stage_mark("sam_begin")
-                    imgs = [units[i][0].sam_img for i in fresh]
-                    if self.use_sam_masks:
-                        # stagger = "decoder": the CLIP stage of the previous group starts when THIS group's encoder pass
-                        # is through, so its large GEMMs run beside the latency-bound rest of the proposal stage (decoder,
-                        # post-processing, NMS, clean-up) instead of beside the encoder's equally matrix-bound GEMMs
-                        if self.stagger == "decoder" and not serial:
-                            ev_enc = torch.cuda.Event()
-                        # everything of the group up to its first count read-back is enqueued here without a wait (with crop
-                        # layers, the PhraseCut configuration: every crop of every image); the read-backs come after the CLIP
-                        # stage of the previous group has been enqueued
-                        if getattr(gen, "wants_image_ids", False):      # a store is keyed by the image, not by its pixels
-                            state = gen.group_begin(imgs, proposal_cap, ev_enc, image_ids=[units[i][0].image_id for i in fresh])
-                        else:
-                            state = gen.group_begin(imgs, proposal_cap, ev_enc)
-                    else:    # proposal kernels only; their output is not consumed (synthetic benchmark, seeded masks)
-                        self.last_proposals = gen.propose_batch(imgs)[-1]
+        it = iter(self._units(loader, group, merge=gen is not None and self.use_sam_masks))
+        # the three-word read-back is switched on at the object that makes the read-back, and only there: a wrapper that hands
+        # attribute reads on to its generator would answer for it and keep the assignment to itself
+        snapshot_was = vars(gen).get("overflow_snapshot") if led is not None and hasattr(gen, "__dict__") else None
+        if snapshot_was is not None:
+            gen.overflow_snapshot = True
+        try:
+            for units in it:
+                self.groups_run += 1
+                if getattr(self, "group_marks", None) is not None:      # host-side stamp of every group boundary (tools/first_use.py)
+                    import time
+                    self.group_marks.append(time.perf_counter())
+                produced = None
+                if not serial:      # items a lazy loader built on the caller's stream just now
+                    produced = torch.cuda.Event()
+                    produced.record(cur)
+                for u in units:
+                    for r in u:
+                        _adopt(r, (s_sam, s_clip), produced)
+                if led is not None:
+                    led.open(self.groups_run, units)
+                    if self._rs["gate"] is not None and not serial:      # no proposal stage beside a snapshot
+                        s_sam.wait_event(self._rs["gate"])
+                state, ev_enc, cached, held, fresh = self._sam_begin(units, pending, s_sam, proposal_cap, serial, group)
+                if pending is not None:
+                    with torch.cuda.stream(s_clip):
+                        if ev_enc is not None:
+                            s_clip.wait_event(ev_enc)
+                        self._clip_stage(pending, led)
+                props, ready, seen = self._sam_end(units, state, cached, fresh, s_sam, led is not None)
+                enqueued = pending[4] if pending is not None else None      # the group whose CLIP stage went out just now
+                pending = (units, props, ready, held, self.groups_run)
+                if led is not None:
+                    if self._rescue_judge(led, it, seen):
+                        pending = None
+                    elif enqueued is not None:
+                        self._rescue_stage_end(enqueued, ready)
             if pending is not None:
                 with torch.cuda.stream(s_clip):
-                    if ev_enc is not None:
-                        s_clip.wait_event(ev_enc)
-                    done += self._clip_group(*pending)
-            props, ready = None, None
-            if state is not None:
-                with torch.cuda.stream(s_sam):
-                    stc = gen.group_cleanup(state)
-                    if stc.overflow:
-                        # fail at THIS group, not in metrics() after the whole dataset: the counter rode on the group's
-                        # count read-back (everything the device had finished by then, on any stream).  The counters are
-                        # process-global: cleared here, or every later run() of the process -- the f32 rerun this message
-                        # recommends included -- would trip over the same count at its first group
-                        ops.split_overflow_count(reset=True)
-                        raise ops.SplitOverflow(
-                            f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode by group {self.groups_run} of the "
-                            f"loop ({stc.overflow} GPU threads saw one; refs up to dataset position {units[-1][-1].index}): the "
-                            "results from the previous group on contain inf / NaN; rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
-                    got = [p[:2] for p in gen.group_finish(stc)]
-                    ready = torch.cuda.Event()
-                    ready.record(s_sam)
-                    self._stage_mark("sam_end")
-                props = [None] * len(units)          # None = take it from the image cache
-                for i, pr in zip(fresh, got):
-                    props[i] = pr
-            elif any(cached):
-                props = [None] * len(units)
-            pending = (units, props, ready, held)
-        if pending is not None:
-            with torch.cuda.stream(s_clip):
-                done += self._clip_group(*pending)
+                    self._clip_stage(pending, led)
+                if led is not None:
+                    self._rescue_stage_end(pending[4], None)
+            if led is not None:
+                self._rescue_judge(led, it, None)
+        finally:
+            if led is not None:
+                self._rs = None
+                if snapshot_was is not None:
+                    gen.overflow_snapshot = snapshot_was
         if not serial:
             self._join_side_streams(cur, self.collected)
-        return done
+        return self._done
+
+    def _sam_begin(self, units, pending, s_sam, proposal_cap, serial, group):
+        """The image-cache look-up of a group and everything of its proposal stage up to the first count read-back, enqueued on
+        s_sam without a wait -> (the generator's group state or None, the event behind its encoder pass or None, cached [n],
+        held [n], the units that go through the generator)."""
+        gen = self.mask_generator
+        state = None
+        ev_enc = None
+        # images seen lately (or in the group whose CLIP stage is about to be enqueued: it files them before this
+        # group's CLIP stage looks): no proposal stage, no hybrid forward for them
+        cached = [False] * len(units)
+        held = [None] * len(units)      # the cache entry itself, pinned at look-up (a later put may evict it from the dict)
+        if self.image_cache > 0 and gen is not None and self.use_sam_masks:
+            self._cache_cap = max(self.image_cache, 2 * group)
+            in_pending = {u[0].image_id for u in pending[0]} if pending is not None else set()
+            for i, u in enumerate(units):
+                iid = u[0].image_id
+                if iid is None:
+                    continue
+                if iid in self._img_cache:
+                    cached[i], held[i] = True, ("entry", self._img_cache[iid])
+                elif iid in in_pending:
+                    cached[i], held[i] = True, ("late",)
+        fresh = [i for i, c in enumerate(cached) if not c]
+        if gen is not None and fresh:
+            with torch.cuda.stream(s_sam):
+                self._stage_mark("sam_begin")
+                imgs = [units[i][0].sam_img for i in fresh]
+                if self.use_sam_masks:
+                    # stagger = "decoder": the CLIP stage of the previous group starts when THIS group's encoder pass
+                    # is through, so its large GEMMs run beside the latency-bound rest of the proposal stage (decoder,
+                    # post-processing, NMS, clean-up) instead of beside the encoder's equally matrix-bound GEMMs
+                    if self.stagger == "decoder" and not serial:
+                        ev_enc = torch.cuda.Event()
+                    # everything of the group up to its first count read-back is enqueued here without a wait (with crop
+                    # layers, the PhraseCut configuration: every crop of every image); the read-backs come after the CLIP
+                    # stage of the previous group has been enqueued
+                    if getattr(gen, "wants_image_ids", False):      # a store is keyed by the image, not by its pixels
+                        state = gen.group_begin(imgs, proposal_cap, ev_enc, image_ids=[units[i][0].image_id for i in fresh])
+                    else:
+                        state = gen.group_begin(imgs, proposal_cap, ev_enc)
+                else:    # proposal kernels only; their output is not consumed (synthetic benchmark, seeded masks)
+                    self.last_proposals = gen.propose_batch(imgs)[-1]
+                    if self._rs is not None and not serial:      # the stage-end snapshot beside it waits for this (no `ready` here)
+                        self._rs["beside"] = torch.cuda.Event()
+                        self._rs["beside"].record(s_sam)
+        return state, ev_enc, cached, held, fresh
+
+    def _sam_end(self, units, state, cached, fresh, s_sam, rescue=False):
+        """The rest of a group's proposal stage: waits for its counts and enqueues what they decide -> (props per unit or None,
+        the event behind the stage or None, the range counters' total that rode on the read-back -- rescue mode and a
+        generator that takes ops.split_overflow_snapshot there -- or None)."""
+        gen = self.mask_generator
+        props, ready, seen = None, None, None
+        if state is not None:
+            with torch.cuda.stream(s_sam):
+                stc = gen.group_cleanup(state)
+                if rescue:
+                    seen = int(stc.overflow) if getattr(gen, "__dict__", {}).get("overflow_snapshot", False) else None
+                elif stc.overflow:
+                    # fail at THIS group, not in metrics() after the whole dataset: the counter rode on the group's
+                    # count read-back (everything the device had finished by then, on any stream).  The counters are
+                    # process-global: cleared here, or every later run() of the process -- the f32 rerun this message
+                    # recommends included -- would trip over the same count at its first group
+                    ops.split_overflow_count(reset=True)
+                    raise ops.SplitOverflow(
+                        f"activations exceeded the fp16 range (|x| > 65504) in f16x3 / f16 mode by group {self.groups_run} of the "
+                        f"loop ({stc.overflow} GPU threads saw one; refs up to dataset position {units[-1][-1].index}): the "
+                        "results from the previous group on contain inf / NaN; rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
+                got = [p[:2] for p in gen.group_finish(stc)]
+                ready = torch.cuda.Event()
+                ready.record(s_sam)
+                self._stage_mark("sam_end")
+            props = [None] * len(units)          # None = take it from the image cache
+            for i, pr in zip(fresh, got):
+                props[i] = pr
+        elif any(cached):
+            props = [None] * len(units)
+        return props, ready, seen
+
+    def _clip_stage(self, pending, led=None):
+        """the CLIP stage of a pending group on the current stream; in rescue mode the checkpoint before it is taken first"""
+        units, props, ready, held, gid = pending
+        if led is not None:
+            led.checkpoint(gid, self._checkpoint())
+        self._done += self._clip_group(units, props, ready, held)
+
+    # ---- checkpoint and roll-back of everything a stage appends to or adds into (prepare(), on_overflow="rescue") -------------
+    def _checkpoint(self):
+        """The loop's state as of now; the accumulators are cloned on the current stream, the logs are append-only and kept as
+        lengths."""
+        cp = dict(cum=self.cum.clone(), n_log=len(self.iu_log), n_refs=self._n_refs, skipped=getattr(self, "skipped", 0),
+                  cache=dict(self._img_cache), cache_hits=self.cache_hits, k=(self.k1, self.k2), done=getattr(self, "_done", 0),
+                  collected=len(self.collected) if getattr(self, "collected", None) is not None else None,
+                  n_pred=len(self._pred_done) + sum(p[1] for p in self._pred_pending))      # sentences recorded, filed or in flight
+        if self.sweep is not None:
+            cp["sweep"] = (self.sweep_cum.clone(), self.sweep_cum_ceiling.clone(), len(self._sweep_log), [list(k) for k in self._sweep_k])
+        return cp
+
+    def _rollback(self, cp):
+        """Back to _checkpoint()'s state.  The caller has made sure that the device work since then has ended (or orders it before
+        the copies enqueued here on the current stream).  Image-cache entries put since then leave, those evicted since then
+        return; the staging buffers of the predictions stay, their records go."""
+        self.cum.copy_(cp["cum"])
+        n = cp["n_log"]
+        del self.iu_log[n:], self.iu_owner[n:], self.idx_log[n:]
+        self._n_refs, self.skipped, self._done = cp["n_refs"], cp["skipped"], cp["done"]
+        self._img_cache, self.cache_hits = cp["cache"], cp["cache_hits"]
+        self.k1, self.k2 = cp["k"]
+        if cp["collected"] is not None and getattr(self, "collected", None) is not None:
+            del self.collected[cp["collected"]:]
+        if self.sweep is not None:
+            self.sweep_cum.copy_(cp["sweep"][0])
+            self.sweep_cum_ceiling.copy_(cp["sweep"][1])
+            del self._sweep_log[cp["sweep"][2]:]
+            self._sweep_k = cp["sweep"][3]
+        if self.record_predictions:
+            self._harvest_predictions(wait=True)
+            del self._pred_done[cp["n_pred"]:]
+
+    # ---- on_overflow="rescue": the device side of hybridgl_amd/rescue.py --------------------------------------------------------
+    def _rescue_wanted(self):
+        """rescue mode, and a model of the loop that splits into fp16 planes (with f32 models the mode is a no-op)"""
+        if self.on_overflow != "rescue":
+            return False
+        owners = (getattr(self.model, "model", None), getattr(self.gem_model, "model", None), getattr(self.mask_generator, "model", None))
+        return any(ops.split_mode(getattr(o, "precision", "f32")) for o in owners if o is not None)
+
+    def _snapshot(self, gid, stream):
+        """(gid, pinned int32 [3], event): the three range counters as of this point of `stream`, nothing waited for"""
+        buf = self._rescue_bufs.pop() if self._rescue_bufs else torch.zeros(3, dtype=torch.int32).pin_memory()
+        with torch.cuda.stream(stream):
+            ops.split_overflow_snapshot(buf)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+        return gid, buf, ev
+
+    def _snapshot_total(self, snap):
+        _, buf, ev = snap
+        ev.synchronize()
+        total = sum(int(v) for v in buf.tolist())
+        self._rescue_bufs.append(buf)
+        return total
+
+    def _rescue_stage_end(self, gid, ready):
+        """The snapshot behind the CLIP stage of group gid (just enqueued), taken when the proposal stage beside it (`ready`) has
+        ended as well; the next proposal stage waits for it (run()), so it counts the same work in every run."""
+        rs = self._rs
+        beside = rs.pop("beside", None)      # proposal kernels whose output nobody consumes (use_sam_masks=False with a generator)
+        for ev in (ready, beside):
+            if ev is not None and not rs["serial"]:
+                rs["s_clip"].wait_event(ev)
+        snap = self._snapshot(gid, rs["s_clip"])
+        rs["snaps"].append(snap)
+        rs["gate"] = snap[2]
+
+    def _rescue_judge(self, led, it, seen):
+        """The verdicts that are due: the stage-end snapshots enqueued a group ago (at the end of run(): all of them), oldest
+        first, then the total `seen` on the newest group's read-back.  True: groups were re-run, the pipeline is empty."""
+        rs = self._rs
+        if rs["base"] is not None:
+            led.base, rs["base"] = self._snapshot_total(rs["base"]), None
+        while rs["snaps"]:
+            snap = rs["snaps"].pop(0)
+            d = led.stage_end(snap[0], self._snapshot_total(snap))
+            if d.kind == "rescue":
+                self._rescue(led, d, it)
+                return True
+        if seen is not None:
+            d = led.read_back(seen)
+            if d.kind == "rescue":
+                self._rescue(led, d, it)
+                return True
+        return False
+
+    def _rescue(self, led, d, it):
+        """A total moved: drain, roll back, clear the counters, run the groups in flight again in f32 on the current stream."""
+        rs = self._rs
+        cur, dev = rs["cur"], self.model.device
+        if d.pull_next:      # (rescue.py: the decision the next stage-end snapshot would have led to)
+            nxt = next(it, None)
+            if nxt is not None:
+                self.groups_run += 1
+                led.open(self.groups_run, nxt)
+        torch.cuda.synchronize(dev)
+        for snap in rs["snaps"]:
+            self._rescue_bufs.append(snap[1])
+        rs["snaps"], rs["gate"] = [], None
+        cp = led.oldest_checkpoint()
+        if cp is not None:
+            self._rollback(cp)
+        ops.split_overflow_count(reset=True, sync=False)      # the device is idle
+        gids = led.in_flight()
+        was_serial, self._serial = self._serial, True
+        stats = self.rescue_stats
+        stats["events"] += 1
+        try:
+            with torch.cuda.stream(cur), ops.forced_precision("f32"):
+                for gid in gids:
+                    units = led.payload(gid)
+                    here = torch.cuda.Event()
+                    here.record(cur)
+                    for u in units:
+                        for r in u:
+                            _adopt(r, (cur,), here)
+                    state, _, cached, held, fresh = self._sam_begin(units, None, cur, rs["cap"], True, rs["group"])
+                    props, ready, _ = self._sam_end(units, state, cached, fresh, cur, True)
+                    self._done += self._clip_group(units, props, ready, held)
+                    stats["groups"] += 1
+                    for u in units:
+                        stats["refs"] += len(u)
+                        stats["positions"] += [r.index for r in u]
+        finally:
+            self._serial = was_serial
+        led.rescued(0)
+        if not rs["serial"]:
+            # the loop's streams go on behind the re-run; what it filed in the image cache is read on the CLIP stream from now on
+            for entry in self._img_cache.values():
+                for t in entry or ():
+                    if isinstance(t, torch.Tensor):
+                        t.record_stream(rs["s_clip"])
+            self._ev.record(cur)
+            rs["s_sam"].wait_event(self._ev)
+            rs["s_clip"].wait_event(self._ev)
 
     def _clip_group(self, units, props, ready, held=None):
         """CLIP + scoring stage of one group on the current stream; props[i] = (masks u8 [n,H,W], boxes XYWH) of unit i from

@@ -679,6 +679,9 @@ class SamAutomaticMaskGenerator:
         self.min_mask_region_area = min_mask_region_area
         # the fifth tensor of a finished image names every survivor's origin: crop * source_stride + candidate of that crop
         self.source_stride = 3 * max(len(g) for g in self.point_grids)
+        # HybridGLPipeline.run(on_overflow="rescue") sets this for the length of a run: the range guard that rides on a
+        # group's count read-back is then ops.split_overflow_snapshot (all three counters) instead of the two-word peek
+        self.overflow_snapshot = False
 
     # ---- small pieces every path shares ---------------------------------------------------------
     def _points(self, H, W, layer_idx=0):
@@ -700,11 +703,15 @@ class SamAutomaticMaskGenerator:
         """A device tensor of counts on its way to the host, nothing waited for: (pinned copy, the event behind it, None).
         overflow: the fp16 range guard of the f16x3 mode rides on the same read-back -- the third element is the pinned pair
         of counters, what the device had counted (any stream) when this stream got here: the caller stops at this group
-        instead of finding out at the end of the dataset."""
+        instead of finding out at the end of the dataset.  With self.overflow_snapshot it is the pinned triple of
+        ops.split_overflow_snapshot, the SAM decoder's counter included."""
         host = torch.empty(counts.shape[0], dtype=torch.int32).pin_memory()
         host.copy_(counts, non_blocking=True)
         ovf = None
-        if overflow:
+        if overflow and self.overflow_snapshot:
+            ovf = torch.zeros(3, dtype=torch.int32).pin_memory()
+            ops.split_overflow_snapshot(ovf)
+        elif overflow:
             ovf = torch.zeros(2, dtype=torch.int32).pin_memory()
             ops.split_overflow_peek(ovf)     # (the counters are process-wide: the CLIP / GEM models of the loop may be f16x3 when this one is not)
         ev = torch.cuda.Event()
@@ -923,7 +930,7 @@ class SamAutomaticMaskGenerator:
         every crop's survivors in its image's frame and the cross-crop NMS (_crops_merge).  The next counts leave in one
         copy again (none without crop layers and without clean-up).  st.overflow: the fp16 range counters of group_begin."""
         st.ev1.synchronize()
-        st.overflow = int(st.ovf[0]) + int(st.ovf[1])
+        st.overflow = sum(int(v) for v in st.ovf.tolist())      # (two words, or three with self.overflow_snapshot)
         n1 = [int(v) for v in st.n1.tolist()]
         counts = self._crops_merge(st, n1) if self.crop_n_layers > 0 else self._classes_cleanup(st, n1)
         st.n2 = st.ev2 = None

@@ -101,6 +101,13 @@ int hgl_split_overflow_count(int reset, unsigned long long* count);
  * that reads something back per batch anyway (the evaluator's proposal counts, Hybridgl_main.py:85-87) rides this on the
  * same event and stops at the offending batch instead of voiding the run at its end. */
 int hgl_split_overflow_peek_async(unsigned int* host2, void* stream);
+/* ALL the counters hgl_split_overflow_count sums, copied in STREAM ORDER to host3[0..2] (pinned host memory; GEMM kernels,
+ * attention kernels, the SAM decoder's image -> token preparation) without waiting and without a reset: host3[0] + host3[1] +
+ * host3[2] is what hgl_split_overflow_count(0, ..) would have returned had the device stopped when `stream` reached this call.
+ * (hgl_split_overflow_peek_async does not see the decoder's counter.)  For a caller that compares totals between two points
+ * of a stream and redoes the work in between in HGL_PREC_F32 when they differ (HybridGLPipeline(on_overflow="rescue")).
+ * HGL_EINVAL for a null pointer; HGL_ELAUNCH when a copy could not be enqueued. */
+int hgl_split_overflow_snapshot_async(unsigned int* host3, void* stream);
 /* Splits w_fp32 [N,K] * 2^scale_log2 into caller-owned fp16 arrays hi, lo ([N,K] each) and
  * records them under the fp32 pointer (scale_log2 keeps the lo half in the fp16 normal range;
  * choose max|w| * 2^scale_log2 <= 2^14). */
