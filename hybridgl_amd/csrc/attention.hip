@@ -17,6 +17,7 @@
 //     ds_read_b128 fragment reads are conflict free; V read as ds_read_b32 rows).
 //   * everything fp32: exact products, fp32 accumulation -> matches the fp32 reference.
 #include "hgl_common.h"
+#include "attn_tile.h"
 #include <stdlib.h>
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -24,7 +25,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 namespace {
 
 constexpr int KV_CHUNK = 64;
-constexpr int NEG_BIG_BITS = 0xff800000;  // -inf
 
 struct AttnArgs {
   const float *q, *k, *v;
@@ -247,29 +247,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(AttnArgs a) {
 // and lo planes) because the P^T accumulator registers 8s..8s+7 of a lane form the B operand of
 // k-step s with the key order 16s + 8(j>>2) + 4h + (j&3): the matching A operand is then two
 // 8-byte reads of consecutive keys from a V^T row.
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split4(const f32x4 v, h16x4& hi, h16x4& lo, float& amax) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    _Float16 a, c;
-    hgl_split_hi_lo(v[e], a, c, amax);
-    hi[e] = a;
-    lo[e] = c;
-  }
-}
-
-// ds_read_b64_tr_b16: see attn_x3_kernel (EXEC must be all ones at the call)
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef __fp16 fp16x4v __attribute__((__vector_size__(4 * sizeof(__fp16))));
-__device__ __forceinline__ h16x4 lds_tr4(const _Float16* p) {
-  typedef __attribute__((address_space(3))) fp16x4v lds_v;
-  const fp16x4v v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v*)p);
-  h16x4 r;
-  __builtin_memcpy(&r, &v, 8);
-  return r;
-}
+// The steps of a (query tile, key tile) pair live ONCE in attn_tile.h; the kernels below are schedules around them.
 
 // RELW > 0: decomposed rel-pos bias of a RELW x RELW window (Sk == RELW*RELW, 2*RELW <= 32, e.g. SAM's 14 x 14)
 // evaluated ON THE MATRIX CORES: bias[q][key] = rel_h[q][key / RELW] + rel_w[q][key % RELW] = R[q][:] . E[key][:]
@@ -315,12 +293,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
   // (global blocks of a group of 16 images: 14 GB fetched for ~1.5 GB of q / k / v / rel-pos, profiles/r04b_sq_counters_attn_x3_global).
   // Remapped so that an XCD works through whole heads: consecutive slots of one XCD are the query blocks of one head.
   int bx = blockIdx.x, bh = blockIdx.y;
-  if (gridDim.x > 1 && (gridDim.y & 7) == 0) {
-    const unsigned G = gridDim.x, L = blockIdx.y * G + blockIdx.x;
-    const unsigned c = L & 7, j = L >> 3;
-    bh = (int)((j / G) * 8 + c);
-    bx = (int)(j % G);
-  }
+  if (gridDim.x > 1 && (gridDim.y & 7) == 0) attn_xcd_item(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, bh, bx);
   const int b = bh / a.H, hh = bh - b * a.H;
   const int q0 = (bx * NW + wave) * 32;
   const int qi = q0 + r;
@@ -361,31 +334,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
   // compiler from moving a load across it, so `load; split; load; split ...` compiled to one global round trip PER
   // 16-byte piece (10 here, 10 more for the unscaled copy, 20 for the rel-pos tables: 40 serial memory latencies at the
   // head of every 196-token item -- 56 % of the windowed kernel's wave cycles were spent waiting, tools/isa_serial_loads.py)
-  f32x4 qraw[KS][2];
-#pragma unroll
-  for (int s = 0; s < KS; ++s)
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-      qraw[s][half] = *(const f32x4*)(qp + 16 * s + 8 * h + 4 * half);   // qp is clamped to a valid row: unconditional, no branch
-  __builtin_amdgcn_sched_barrier(0);
-  if (!qvalid) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) qraw[s][0] = qraw[s][1] = f32x4{0, 0, 0, 0};
-  }
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const f32x4 v = qraw[s][half];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        _Float16 hi, lo;
-        hgl_split_hi_lo(v[e], hi, lo, amax);
-        qh[s][4 * half + e] = hi;
-        if constexpr (TERMS != 1) ql[s][4 * half + e] = lo;
-      }
-    }
-  }
+  attn_load_split_q<KS, TERMS, false>(qp, h, qvalid, 1.0f, qh, ql, amax);   // qp is clamped to a valid row
 
   f32x16 o[DT];
 #pragma unroll
@@ -579,10 +528,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
       Vl[row * VP + HD + c] = (_Float16)0.f;
     }
   }
-  // transposed-read addressing: lane = 16*grp + 4*q + p supplies row q, columns 4p..4p+3 of its group's block;
-  // groups 0/1 carry d columns 0-15 / 16-31 for h = 0, groups 2/3 the same for h = 1
-  const int tr_off = (((lane >> 2) & 3) + 4 * h) * VP + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-  store_chunk(0);      // chunk 0 was requested at the top of the kernel
+  const int tr_off = attn_tr_off<VP>(lane, h);
+  store_chunk(0);     // chunk 0 was requested at the top of the kernel
   __syncthreads();
   // Decomposed rel-pos terms given as tensors (SAM's global blocks: 64 x 64 keys): the 17 values a lane adds to the scores
   // of a key tile are fetched ONE TILE AHEAD.  Requested behind the tile's QK^T products and used at once they cost a
@@ -627,16 +574,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
         for (int e = 0; e < 16; ++e) s[e] = 0.f;
       }
       const _Float16* krow = Ks + (kt * 32 + r) * KROW + 8 * h;
-#pragma unroll
-      for (int c = 0; c < KS; ++c) {
-        const h16x8 kh8 = *(const h16x8*)(krow + 16 * c);
-        const h16x8 kl8 = *(const h16x8*)(krow + HD + 16 * c);
-        if constexpr (TERMS != 1) {
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[c], s, 0, 0, 0);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[c], s, 0, 0, 0);
-        }
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qh[c], s, 0, 0, 0);
-      }
+      attn_qk_tile<HD, TERMS>(krow, qh, ql, s);
       if constexpr (RELW > 0) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -675,67 +613,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
           mx = fmaxf(mx, sv);
         }
       } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[e]);
+        mx = attn_tile_max(s);
       }
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      // Lazy rescaling: the running maximum follows the scores only when some query of the wave would otherwise see
-      // probabilities above 2^8 (uniform branch).  Until then alpha == 1 and the 16*DT multiplies of O are skipped;
-      // p <= 256 keeps its full relative precision in fp32 and in the fp16 hi+lo pair.
-      const float m_cand = fmaxf(m_run, mx);
-      float m_new = m_run;
-      if (__builtin_amdgcn_ballot_w64(m_cand > m_run + rescale_thr)) {
-        m_new = m_cand;
-        const float m_use0 = (m_new == NEG_INF) ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use0) * sl2e);
-        l_run *= alpha;
-#pragma unroll
-        for (int d = 0; d < DT; ++d)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) o[d][e] *= alpha;
-        m_run = m_new;
-      }
-      const float mneg = -((m_new == NEG_INF) ? 0.f : m_new) * sl2e;
-      float rs = 0.f;
       h16x8 ph[2], pl[2];
-#pragma unroll
-      for (int e = 0; e < 16; e += 2) {
-        const float p0 = __builtin_amdgcn_exp2f(fmaf(s[e], sl2e, mneg));
-        const float p1 = __builtin_amdgcn_exp2f(fmaf(s[e + 1], sl2e, mneg));
-        rs += p0;
-        rs += p1;
-        // hi by one packed round-toward-zero conversion (any rounding works: lo is the exact remainder, rounded to nearest)
-        if constexpr (TERMS == 1) {   // P rounded to nearest, hi only
-          ph[e >> 3][e & 7] = (_Float16)p0; ph[e >> 3][(e & 7) + 1] = (_Float16)p1;
-        } else {
-          const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-          ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
-          pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
-          pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
-        }
-      }
-      l_run += rs;
+      attn_softmax_tile<DT, TERMS>(s, mx, sl2e, rescale_thr, m_run, l_run, o, ph, pl);
       // the scores are dead from here on: the next tile's rel-pos terms are requested now and travel under the P V products
       if (relfast) rel_prefetch(kbase + 32);
-      // O^T += V^T P^T ; A operand element j of lane (d, h) = V^T[d][kt*32 + 16*s2 + 8*(j>>2) + 4*h + (j&3)]
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        if (kbase + 16 * s2 >= sk_eff) break;   // uniform: the keys of this k-step are all beyond the sequence (P = 0)
-#pragma unroll
-        for (int d = 0; d < DT; ++d) {
-          const int off = (kt * 32 + 16 * s2) * VP + d * 32 + tr_off;
-          const h16x4 vh0 = lds_tr4(Vh + off), vh1 = lds_tr4(Vh + off + 8 * VP);
-          const h16x4 vl0 = lds_tr4(Vl + off), vl1 = lds_tr4(Vl + off + 8 * VP);
-          h16x8 vh8, vl8;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { vh8[e] = vh0[e]; vh8[4 + e] = vh1[e]; vl8[e] = vl0[e]; vl8[4 + e] = vl1[e]; }
-          if constexpr (TERMS != 1) {
-            o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[d], 0, 0, 0);
-            o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[d], 0, 0, 0);
-          }
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, ph[s2], o[d], 0, 0, 0);
-        }
-      }
+      attn_pv_tile<DT, VP, TERMS>(Vh, Vl, kt * 32 * VP + tr_off, kbase, sk_eff, ph, pl, o);
     }
     __syncthreads();
     if (has_next) {
@@ -745,37 +629,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
   }
 
   hgl_split_commit(amax);
-  const float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-  if (qvalid) {
-    const long long oo = b * a.sob + (long long)qi * a.ldo + hh * HD;
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = d * 32 + 8 * g + 4 * h;
-        if (dd < HD) {
-          f32x4 w;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) w[e] = o[d][4 * g + e] * inv;
-          if (a.out) {
-            *(f32x4*)(a.out + oo + dd) = w;
-          } else {   // the operand form of the following f16x3 projection
-            h16x4 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              _Float16 a2, c2;
-              hgl_split_hi_lo(w[e], a2, c2);
-              hi[e] = a2;
-              lo[e] = c2;
-            }
-            *(h16x4*)(a.out_hi + oo + dd) = hi;
-            if (a.out_lo) *(h16x4*)(a.out_lo + oo + dd) = lo;
-          }
-        }
-      }
-    }
-  }
+  attn_write_out<HD, DT>(o, l_run, qvalid, a.out, a.out_hi, a.out_lo, b, a.sob, qi, a.ldo, hh, h);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -795,7 +649,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_x3_kernel(AttnA
 // of 64 keys are double-buffered in LDS; chunk c is written by group B in interval 4c-2 and by group A in interval 4c-1
 // (each thread its own pieces, fetched four intervals earlier), after the last reader of the buffer's previous chunk
 // (group B's P V of tile 2c-3, interval 4c-3) and before its first reader (group A's Q K^T of tile 2c, interval 4c).
-// The arithmetic of a (query tile, key tile) pair is attn_x3_kernel's, instruction for instruction: identical results.
+// The arithmetic of a (query tile, key tile) pair is attn_x3_kernel's: both call the steps of attn_tile.h -- identical results.
 template <int HD, int TERMS = 3>   // TERMS = 1: see attn_x3_kernel
 __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
   constexpr int NT = 512;
@@ -818,12 +672,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
   const int grp = wave >> 2;
   const int r = lane & 31, h = lane >> 5;
   int bx = blockIdx.x, bh = blockIdx.y;
-  if (gridDim.x > 1 && (gridDim.y & 7) == 0) {   // an XCD works through whole heads (see attn_x3_kernel)
-    const unsigned G = gridDim.x, L = blockIdx.y * G + blockIdx.x;
-    const unsigned c = L & 7, j = L >> 3;
-    bh = (int)((j / G) * 8 + c);
-    bx = (int)(j % G);
-  }
+  if (gridDim.x > 1 && (gridDim.y & 7) == 0) attn_xcd_item(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, bh, bx);   // see attn_x3_kernel
   const int b = bh / a.H, hh = bh - b * a.H;
   const int q0 = (bx * 8 + wave) * 32;
   const int qi = q0 + r;
@@ -873,29 +722,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
   load_pieces(0);
   // Q fragments, unscaled (the scale lives in the exponent's constant): one batch of loads, then the splits
   h16x8 qh[KS], ql[KS];
-  {
-    f32x4 qraw[KS][2];
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int half = 0; half < 2; ++half) qraw[s][half] = *(const f32x4*)(qp + 16 * s + 8 * h + 4 * half);
-    __builtin_amdgcn_sched_barrier(0);
-    if (!qvalid) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) qraw[s][0] = qraw[s][1] = f32x4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int half = 0; half < 2; ++half)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          _Float16 hi, lo;
-          hgl_split_hi_lo(qraw[s][half][e], hi, lo, amax);
-          qh[s][4 * half + e] = hi;
-          if constexpr (TERMS != 1) ql[s][4 * half + e] = lo;
-        }
-  }
+  attn_load_split_q<KS, TERMS, false>(qp, h, qvalid, 1.0f, qh, ql, amax);
   if (VP > HD) {   // zero the d padding of both V buffers once
     constexpr int PADW = VP - HD > 0 ? VP - HD : 1;
     for (int i = t; i < 2 * KV_CHUNK * PADW; i += NT) {
@@ -919,7 +746,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
     for (int e = 0; e < 16; ++e) o[d][e] = 0.f;
   const float NEG_INF = __int_as_float(NEG_BIG_BITS);
   float m_run = NEG_INF, l_run = 0.f;
-  const int tr_off = (((lane >> 2) & 3) + 4 * h) * VP + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int tr_off = attn_tr_off<VP>(lane, h);
 
   // rel-pos terms of the NEXT tile (tensors [B*H, Sq, kh] / [B*H, Sq, kw], kw a multiple of 32)
   const bool rel = a.rel_h != nullptr;
@@ -947,24 +774,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
   h16x8 ph[2], pl[2];
   auto pv_step = [&](int tp) {      // O^T += V^T P^T for tile tp (its probabilities are in ph / pl)
     const int buf = (tp >> 1) & 1, kt = tp & 1, kbase = tp * 32;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      if (kbase + 16 * s2 >= a.Sk) break;
-#pragma unroll
-      for (int d = 0; d < DT; ++d) {
-        const int off = buf * VBUF + (kt * 32 + 16 * s2) * VP + d * 32 + tr_off;
-        const h16x4 vh0 = lds_tr4(Vh + off), vh1 = lds_tr4(Vh + off + 8 * VP);
-        const h16x4 vl0 = lds_tr4(Vl + off), vl1 = lds_tr4(Vl + off + 8 * VP);
-        h16x8 vh8, vl8;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { vh8[e] = vh0[e]; vh8[4 + e] = vh1[e]; vl8[e] = vl0[e]; vl8[4 + e] = vl1[e]; }
-        if constexpr (TERMS != 1) {
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[d], 0, 0, 0);
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[d], 0, 0, 0);
-        }
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, ph[s2], o[d], 0, 0, 0);
-      }
-    }
+    attn_pv_tile<DT, VP, TERMS>(Vh, Vl, buf * VBUF + kt * 32 * VP + tr_off, kbase, a.Sk, ph, pl, o);
   };
 
   if (grp == 1) bar();               // group B runs one interval behind group A
@@ -983,16 +793,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
         for (int e = 0; e < 16; ++e) s[e] = 0.f;
       }
       const _Float16* krow = Ks + ((tt >> 1) & 1) * KBUF + ((tt & 1) * 32 + r) * KROW + 8 * h;
-#pragma unroll
-      for (int c = 0; c < KS; ++c) {
-        const h16x8 kh8 = *(const h16x8*)(krow + 16 * c);
-        const h16x8 kl8 = *(const h16x8*)(krow + HD + 16 * c);
-        if constexpr (TERMS != 1) {
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[c], s, 0, 0, 0);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[c], s, 0, 0, 0);
-        }
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qh[c], s, 0, 0, 0);
-      }
+      attn_qk_tile<HD, TERMS>(krow, qh, ql, s);
       __builtin_amdgcn_s_setprio(0);
     }
     bar();
@@ -1009,51 +810,8 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
     }
     if (wave_active) {
       if (rel) rel_prefetch(kbase + 32);       // consumed at the next M step's start: a whole V step + a barrier away
-      float mx = NEG_INF;
-      if (kbase + 32 > a.Sk) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int kg = kbase + (e & 3) + 8 * (e >> 2) + 4 * h;
-          const float sv = kg >= a.Sk ? NEG_INF : s[e];
-          s[e] = sv;
-          mx = fmaxf(mx, sv);
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[e]);
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float m_cand = fmaxf(m_run, mx);
-      float m_new = m_run;
-      if (__builtin_amdgcn_ballot_w64(m_cand > m_run + rescale_thr)) {
-        m_new = m_cand;
-        const float m_use0 = (m_new == NEG_INF) ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use0) * sl2e);
-        l_run *= alpha;
-#pragma unroll
-        for (int d = 0; d < DT; ++d)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) o[d][e] *= alpha;
-        m_run = m_new;
-      }
-      const float mneg = -((m_new == NEG_INF) ? 0.f : m_new) * sl2e;
-      float rs = 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; e += 2) {
-        const float p0 = __builtin_amdgcn_exp2f(fmaf(s[e], sl2e, mneg));
-        const float p1 = __builtin_amdgcn_exp2f(fmaf(s[e + 1], sl2e, mneg));
-        rs += p0;
-        rs += p1;
-        if constexpr (TERMS == 1) {   // P rounded to nearest, hi only
-          ph[e >> 3][e & 7] = (_Float16)p0; ph[e >> 3][(e & 7) + 1] = (_Float16)p1;
-        } else {
-          const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-          ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
-          pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
-          pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
-        }
-      }
-      l_run += rs;
+      attn_mask_tail(s, kbase, a.Sk, h);
+      attn_softmax_tile<DT, TERMS>(s, attn_tile_max(s), sl2e, rescale_thr, m_run, l_run, o, ph, pl);
     }
     bar();
   }
@@ -1065,37 +823,7 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
   if (grp == 0) bar();               // group A's last interval: group B is still one behind
 
   hgl_split_commit(amax);
-  const float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-  if (qvalid) {
-    const long long oo = b * a.sob + (long long)qi * a.ldo + hh * HD;
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = d * 32 + 8 * g + 4 * h;
-        if (dd < HD) {
-          f32x4 w;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) w[e] = o[d][4 * g + e] * inv;
-          if (a.out) {
-            *(f32x4*)(a.out + oo + dd) = w;
-          } else {
-            h16x4 hi, lo;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              _Float16 a2, c2;
-              hgl_split_hi_lo(w[e], a2, c2);
-              hi[e] = a2;
-              lo[e] = c2;
-            }
-            *(h16x4*)(a.out_hi + oo + dd) = hi;
-            if (a.out_lo) *(h16x4*)(a.out_lo + oo + dd) = lo;
-          }
-        }
-      }
-    }
-  }
+  attn_write_out<HD, DT>(o, l_run, qvalid, a.out, a.out_hi, a.out_lo, b, a.sob, qi, a.ldo, hh, h);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1104,7 +832,8 @@ __global__ __launch_bounds__(512, 1) void attn_x3pp_kernel(AttnArgs a) {
 // staged once (as in the 8-wave kernels) but a CU holds two workgroups = two items whose phases are independent: while one
 // waits for its loads, splits a chunk or stores its output rows, the other multiplies.  (The 8-wave workgroups put both
 // waves of a SIMD on the SAME item: they meet at every chunk barrier and wait for the same loads.)  Arithmetic per
-// (query tile, key tile) is that of attn_x3_kernel, operation for operation.
+// (query tile, key tile): the steps of attn_tile.h, as in attn_x3_kernel; q is scaled BEFORE its split here (the scores are in
+// nats, the exponent's constant is log2 e), there in the exponent.
 template <int HD, int QT, int TERMS = 3>   // TERMS = 1: see attn_x3_kernel
 __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
   constexpr int NW = 4, NT = NW * 64;
@@ -1146,30 +875,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
     qvalid[qt] = qi[qt] < a.Sq;
     tile_active[qt] = q0 < a.Sq;
     const float* qp = a.q + b * a.sqb + (long long)(qvalid[qt] ? qi[qt] : 0) * a.ldq + hh * HD;
-    f32x4 qraw[KS][2];      // one batch of loads, then the splits (see attn_x3_kernel: a split right behind its load serialises them)
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int half = 0; half < 2; ++half)
-        qraw[s][half] = *(const f32x4*)(qp + 16 * s + 8 * h + 4 * half);     // qp is clamped to a valid row
-    __builtin_amdgcn_sched_barrier(0);
-    if (!qvalid[qt]) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) qraw[s][0] = qraw[s][1] = f32x4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const f32x4 v = qraw[s][half];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          _Float16 hi, lo;
-          hgl_split_hi_lo(v[e] * a.scale, hi, lo, amax);
-          qh[qt][s][4 * half + e] = hi;
-          if constexpr (TERMS != 1) ql[qt][s][4 * half + e] = lo;
-        }
-      }
+    attn_load_split_q<KS, TERMS, true>(qp, h, qvalid[qt], a.scale, qh[qt], ql[qt], amax);   // qp is clamped to a valid row
   }
   f32x16 o[QT][DT];
   float m_run[QT], l_run[QT];
@@ -1224,7 +930,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
       Vl[row * VP + HD + c] = (_Float16)0.f;
     }
   }
-  const int tr_off = (((lane >> 2) & 3) + 4 * h) * VP + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int tr_off = attn_tr_off<VP>(lane, h);
   load_chunk(0);
   store_chunk(0);
   __syncthreads();
@@ -1243,87 +949,14 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) s[e] = 0.f;
         const _Float16* krow = Ks + (kt * 32 + r) * KROW + 8 * h;
-#pragma unroll
-        for (int c = 0; c < KS; ++c) {
-          const h16x8 kh8 = *(const h16x8*)(krow + 16 * c);
-          const h16x8 kl8 = *(const h16x8*)(krow + HD + 16 * c);
-          if constexpr (TERMS != 1) {
-            s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[qt][c], s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[qt][c], s, 0, 0, 0);
-          }
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qh[qt][c], s, 0, 0, 0);
-        }
-        if (kbase + 32 > a.Sk) {   // uniform: the tile that crosses the end of the sequence
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int kg = kbase + (e & 3) + 8 * (e >> 2) + 4 * h;
-            s[e] = kg >= a.Sk ? NEG_INF : s[e];
-          }
-        }
-        if (keep_row && wave == 0 && qt == 0) {   // uniform: the wave and tile that own query 0 of a CLS-keep batch
-          const int kk = kbase + (lane & 31);
-          const unsigned kb = kk >= 1 && kk < a.Sk ? keepL[kk - 1] : 1u;
-          const unsigned bits = (unsigned)__builtin_amdgcn_ballot_w64(kb != 0) >> (4 * h);
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const bool kept = (bits >> ((e & 3) + 8 * (e >> 2))) & 1u;
-            s[e] = (qi[0] == 0 && !kept) ? NEG_INF : s[e];
-          }
-        }
-        float mx = NEG_INF;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[e]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_cand = fmaxf(m_run[qt], mx);
-        float m_new = m_run[qt];
-        if (__builtin_amdgcn_ballot_w64(m_cand > m_run[qt] + 5.5f)) {   // lazy rescaling (attn_x3_kernel)
-          m_new = m_cand;
-          const float m_use0 = (m_new == NEG_INF) ? 0.f : m_new;
-          const float alpha = __builtin_amdgcn_exp2f((m_run[qt] - m_use0) * LOG2E);
-          l_run[qt] *= alpha;
-#pragma unroll
-          for (int d = 0; d < DT; ++d)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) o[qt][d][e] *= alpha;
-          m_run[qt] = m_new;
-        }
-        const float mneg = -((m_new == NEG_INF) ? 0.f : m_new) * LOG2E;
-        float rs = 0.f;
+        attn_qk_tile<HD, TERMS>(krow, qh[qt], ql[qt], s);
+        attn_mask_tail(s, kbase, a.Sk, h);
+        if (keep_row && wave == 0 && qt == 0)   // uniform: the wave and tile that own query 0 of a CLS-keep batch
+          attn_mask_cls_keep(s, keepL, kbase, a.Sk, lane, h, qi[0]);
         h16x8 ph[2], pl[2];
-#pragma unroll
-        for (int e = 0; e < 16; e += 2) {
-          const float p0 = __builtin_amdgcn_exp2f(fmaf(s[e], LOG2E, mneg));
-          const float p1 = __builtin_amdgcn_exp2f(fmaf(s[e + 1], LOG2E, mneg));
-          rs += p0;
-          rs += p1;
-          if constexpr (TERMS == 1) {   // P rounded to nearest, hi only
-            ph[e >> 3][e & 7] = (_Float16)p0; ph[e >> 3][(e & 7) + 1] = (_Float16)p1;
-          } else {
-            const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-            ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
-            pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
-            pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
-          }
-        }
-        l_run[qt] += rs;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          if (kbase + 16 * s2 >= a.Sk) break;   // uniform
-#pragma unroll
-          for (int d = 0; d < DT; ++d) {
-            const int off = (kt * 32 + 16 * s2) * VP + d * 32 + tr_off;
-            const h16x4 vh0 = lds_tr4(Vh + off), vh1 = lds_tr4(Vh + off + 8 * VP);
-            const h16x4 vl0 = lds_tr4(Vl + off), vl1 = lds_tr4(Vl + off + 8 * VP);
-            h16x8 vh8, vl8;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { vh8[e] = vh0[e]; vh8[4 + e] = vh1[e]; vl8[e] = vl0[e]; vl8[4 + e] = vl1[e]; }
-            if constexpr (TERMS != 1) {
-              o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[qt][d], 0, 0, 0);
-              o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[qt][d], 0, 0, 0);
-            }
-            o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, ph[s2], o[qt][d], 0, 0, 0);
-          }
-        }
+        // q is pre-scaled here: the scores are in nats
+        attn_softmax_tile<DT, TERMS>(s, attn_tile_max(s), LOG2E, 5.5f, m_run[qt], l_run[qt], o[qt], ph, pl);
+        attn_pv_tile<DT, VP, TERMS>(Vh, Vl, kt * 32 * VP + tr_off, kbase, a.Sk, ph, pl, o[qt]);
       }
     }
     __syncthreads();
@@ -1335,38 +968,8 @@ __global__ __launch_bounds__(256, 2) void attn_x3q_kernel(AttnArgs a) {
 
   hgl_split_commit(amax);
 #pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    const float l_tot = l_run[qt] + __shfl_xor(l_run[qt], 32);
-    const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-    if (qvalid[qt]) {
-      const long long oo = b * a.sob + (long long)qi[qt] * a.ldo + hh * HD;
-#pragma unroll
-      for (int d = 0; d < DT; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int dd = d * 32 + 8 * g + 4 * h;
-          if (dd < HD) {
-            f32x4 w;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = o[qt][d][4 * g + e] * inv;
-            if (a.out) {
-              *(f32x4*)(a.out + oo + dd) = w;
-            } else {
-              h16x4 hi, lo;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                _Float16 a2, c2;
-                hgl_split_hi_lo(w[e], a2, c2);
-                hi[e] = a2;
-                lo[e] = c2;
-              }
-              *(h16x4*)(a.out_hi + oo + dd) = hi;
-              if (a.out_lo) *(h16x4*)(a.out_lo + oo + dd) = lo;
-            }
-          }
-        }
-    }
-  }
+  for (int qt = 0; qt < QT; ++qt)
+    attn_write_out<HD, DT>(o[qt], l_run[qt], qvalid[qt], a.out, a.out_hi, a.out_lo, b, a.sob, qi[qt], a.ldo, hh, h);
 }
 
 // ---------------------------------------------------------------------------------------------

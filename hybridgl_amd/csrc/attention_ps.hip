@@ -17,24 +17,22 @@
 //     waits and write-out run beside the other's MFMAs);
 //   * windows: two workgroups per (window, head) (query tiles 0-3 / 4-6), placed on the same XCD so that the second finds the
 //     item's K / V planes in L2; staging twice costs DMA bytes only.
-// The arithmetic of a (query tile, key tile) pair is attn_x3_kernel's, operation for operation (swapped QK^T, scale in the
-// exponent, lazy rescaling, P split by a packed round-toward-zero conversion, P^T accumulators as the B operand of P V through
-// the transposing LDS read): results are bit-identical to that kernel on the same hi / lo planes.
+// The arithmetic of a (query tile, key tile) pair is attn_x3_kernel's (swapped QK^T, scale in the exponent, lazy rescaling, P
+// split by a packed round-toward-zero conversion, P^T accumulators as the B operand of P V through the transposing LDS read):
+// attn_ps_kernel calls the same steps of attn_tile.h, so its results are bit-identical to that kernel on the same hi / lo
+// planes.  attn_psp_kernel takes the tile map, the masks, QK^T of its first tile and P V from there; its soft-max is the same
+// operations written out as the groups of its hand-interleaved segment (see there), its write-out pairs lanes for 16-byte stores.
 #include "hgl_common.h"
+#include "attn_tile.h"
 #include <stdlib.h>
 #include <mutex>
 #include <type_traits>
 
 namespace {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef __fp16 fp16x4v __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef __attribute__((address_space(3))) void lds_void_t;
 
-constexpr int PS_NEG_BIG_BITS = 0xff800000;  // -inf
-constexpr int PS_CHUNK = 32;                 // keys per staged chunk = one key tile
+constexpr int PS_CHUNK = 32;                // keys per staged chunk = one key tile
 
 enum { PS_PLAIN = 0, PS_WIN14 = 1, PS_RELT = 2 };
 
@@ -64,15 +62,6 @@ struct PsArgs {
 #else
 #define PS_DBG(a) 0
 #endif
-
-// ds_read_b64_tr_b16 (EXEC must be all ones at the call)
-__device__ __forceinline__ h16x4 ps_tr4(const _Float16* p) {
-  typedef __attribute__((address_space(3))) fp16x4v lds_v;
-  const fp16x4v v = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_v*)p);
-  h16x4 r;
-  __builtin_memcpy(&r, &v, 8);
-  return r;
-}
 
 // One LDS-DMA wave-instruction: lane i copies 16 B from sbase + voff(i) to LDS byte lds_addr + 16 * i (see gemm_f16x3.hip).
 // Not counted by the compiler on vmcnt: the consumer waits with an explicit s_waitcnt.
@@ -137,16 +126,14 @@ __global__ __launch_bounds__(256, 2) void attn_ps_kernel(PsArgs a) {
   {
     const unsigned L = blockIdx.x, nqb = (unsigned)a.nqb, items = (unsigned)(a.B * a.H);
     if ((items & 7u) == 0) {
-      const unsigned c = L & 7u, j = L >> 3;
-      item = (int)((j / nqb) * 8u + c);
-      bx = (int)(j % nqb);
+      attn_xcd_item(L, nqb, item, bx);
     } else {
       item = (int)(L / nqb);
       bx = (int)(L % nqb);
     }
   }
   const int b = item / a.H, hh = item - b * a.H;
-  const float NEG_INF = __int_as_float(PS_NEG_BIG_BITS);
+  const float NEG_INF = __int_as_float(NEG_BIG_BITS);
   constexpr float LOG2E = 1.4426950408889634f;
   const float sl2e = a.scale * LOG2E;
   const float inv_scale = 1.0f / a.scale;
@@ -253,8 +240,7 @@ __global__ __launch_bounds__(256, 2) void attn_ps_kernel(PsArgs a) {
 #pragma unroll
     for (int sx = 0; sx < KS; ++sx) asm volatile("" : "+v"(qh[qt][sx]), "+v"(ql[qt][sx]));
 
-  // transposed-read addressing (attn_x3_kernel): lane = 16*grp + 4*q + p supplies row q, columns 4p..4p+3 of its group's block
-  const int tr_off = (((lane >> 2) & 3) + 4 * h) * VP + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+  const int tr_off = attn_tr_off<VP>(lane, h);
 
   const int nchunk = (a.S + PS_CHUNK - 1) / PS_CHUNK;
   for (int ci = 0; ci < nchunk; ++ci) {
@@ -280,125 +266,24 @@ __global__ __launch_bounds__(256, 2) void attn_ps_kernel(PsArgs a) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) s[e] = 0.f;
       const _Float16* krow = Ks + r * KP + 8 * h;
-#pragma unroll
-      for (int c = 0; c < KS; ++c) {
-        const h16x8 kh8 = *(const h16x8*)(krow + 16 * c);
-        const h16x8 kl8 = *(const h16x8*)(krow + HD + 16 * c);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qh[qt][c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, ql[qt][c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qh[qt][c], s, 0, 0, 0);
-      }
+      attn_qk_tile<HD, 3>(krow, qh[qt], ql[qt], s);
       // s[e] = S^T[key = kbase + (e&3) + 8*(e>>2) + 4*h][query], unscaled; scale and log2(e) are folded into the exponent's fma
       PS_STAMP(14);
-      float mx = NEG_INF;
-      if (kbase + 32 > a.S) {   // uniform: the tile that crosses the end of the sequence
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int kg = kbase + (e & 3) + 8 * (e >> 2) + 4 * h;
-          s[e] = kg >= a.S ? NEG_INF : s[e];
-        }
-      }
-      if (MODE == PS_PLAIN && keep_row && bx == 0 && wave == 0 && qt == 0) {   // uniform: the tile that owns query 0
-        const int kk = kbase + (lane & 31);
-        const unsigned kb = kk >= 1 && kk < a.S ? keepL[kk - 1] : 1u;
-        const unsigned bits = (unsigned)__builtin_amdgcn_ballot_w64(kb != 0) >> (4 * h);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const bool kept = (bits >> ((e & 3) + 8 * (e >> 2))) & 1u;
-          s[e] = (qi[0] == 0 && !kept) ? NEG_INF : s[e];
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 16; ++e) mx = fmaxf(mx, s[e]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      // lazy rescaling (attn_x3_kernel): the running maximum follows the scores only when some query of the wave would
-      // otherwise see probabilities above 2^8 (uniform branch)
-      const float m_cand = fmaxf(m_run[qt], mx);
-      float m_new = m_run[qt];
-      if (__builtin_amdgcn_ballot_w64(m_cand > m_run[qt] + rescale_thr)) {
-        m_new = m_cand;
-        const float m_use0 = (m_new == NEG_INF) ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f((m_run[qt] - m_use0) * sl2e);
-        l_run[qt] *= alpha;
-#pragma unroll
-        for (int d = 0; d < DT; ++d)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) o[qt][d][e] *= alpha;
-        m_run[qt] = m_new;
-      }
-      const float mneg = -((m_new == NEG_INF) ? 0.f : m_new) * sl2e;
-      float rs = 0.f;
+      attn_mask_tail(s, kbase, a.S, h);
+      if (MODE == PS_PLAIN && keep_row && bx == 0 && wave == 0 && qt == 0)   // uniform: the tile that owns query 0
+        attn_mask_cls_keep(s, keepL, kbase, a.S, lane, h, qi[0]);
       h16x8 ph[2], pl[2];
-#pragma unroll
-      for (int e = 0; e < 16; e += 2) {
-        const float p0 = __builtin_amdgcn_exp2f(fmaf(s[e], sl2e, mneg));
-        const float p1 = __builtin_amdgcn_exp2f(fmaf(s[e + 1], sl2e, mneg));
-        rs += p0;
-        rs += p1;
-        // hi by one packed round-toward-zero conversion (any rounding works: lo is the exact remainder, rounded to nearest)
-        const h16x2 hi2 = __builtin_bit_cast(h16x2, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-        ph[e >> 3][e & 7] = hi2[0]; ph[e >> 3][(e & 7) + 1] = hi2[1];
-        pl[e >> 3][e & 7] = (_Float16)(p0 - (float)hi2[0]);
-        pl[e >> 3][(e & 7) + 1] = (_Float16)(p1 - (float)hi2[1]);
-      }
-      l_run[qt] += rs;
+      attn_softmax_tile<DT, 3>(s, attn_tile_max(s), sl2e, rescale_thr, m_run[qt], l_run[qt], o[qt], ph, pl);
       PS_STAMP(15);
-      // the scores are dead from here on: the next tile's rel-pos terms travel under the P V products
-      // O^T += V^T P^T ; A operand element j of lane (d, h) = V^T[d][16*s2 + 8*(j>>2) + 4*h + (j&3)]
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        if (kbase + 16 * s2 >= a.S) break;   // uniform: the keys of this k-step are all beyond the sequence (P = 0)
-#pragma unroll
-        for (int d = 0; d < DT; ++d) {
-          const int off = (16 * s2) * VP + d * 32 + tr_off;
-          const h16x4 vh0 = ps_tr4(Vh + off), vh1 = ps_tr4(Vh + off + 8 * VP);
-          const h16x4 vl0 = ps_tr4(Vl + off), vl1 = ps_tr4(Vl + off + 8 * VP);
-          h16x8 vh8, vl8;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { vh8[e] = vh0[e]; vh8[4 + e] = vh1[e]; vl8[e] = vl0[e]; vl8[4 + e] = vl1[e]; }
-          o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[qt][d], 0, 0, 0);
-          o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[qt][d], 0, 0, 0);
-          o[qt][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, ph[s2], o[qt][d], 0, 0, 0);
-        }
-      }
+      attn_pv_tile<DT, VP, 3>(Vh, Vl, tr_off, kbase, a.S, ph, pl, o[qt]);
       PS_STAMP(16);
     }
   }
   PS_STAMP(20);
 
 #pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    const float l_tot = l_run[qt] + __shfl_xor(l_run[qt], 32);
-    const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-    if (qvalid[qt]) {
-      const long long oo = b * a.sob + (long long)qi[qt] * a.ldo + hh * HD;
-#pragma unroll
-      for (int d = 0; d < DT; ++d)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int dd = d * 32 + 8 * g + 4 * h;
-          if (dd < HD) {
-            f32x4 w;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) w[e] = o[qt][d][4 * g + e] * inv;
-            if (a.out) {
-              *(f32x4*)(a.out + oo + dd) = w;
-            } else {   // the operand form of the following f16x3 projection
-              h16x4 hi, lo;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                _Float16 a2, c2;
-                hgl_split_hi_lo(w[e], a2, c2);
-                hi[e] = a2;
-                lo[e] = c2;
-              }
-              *(h16x4*)(a.out_hi + oo + dd) = hi;
-              *(h16x4*)(a.out_lo + oo + dd) = lo;
-            }
-          }
-        }
-    }
-  }
+  for (int qt = 0; qt < QT; ++qt)
+    attn_write_out<HD, DT>(o[qt], l_run[qt], qvalid[qt], a.out, a.out_hi, a.out_lo, b, a.sob, qi[qt], a.ldo, hh, h);
   PS_STAMP(21);
 }
 
@@ -459,7 +344,7 @@ __global__ __launch_bounds__(256, 2) void attn_psp_kernel(PsArgs a, const unsign
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int r = lane & 31, h = lane >> 5;
-  const float NEG_INF = __int_as_float(PS_NEG_BIG_BITS);
+  const float NEG_INF = __int_as_float(NEG_BIG_BITS);
   constexpr float LOG2E = 1.4426950408889634f;
   const float sl2e = a.scale * LOG2E;
   const float inv_scale = 1.0f / a.scale;
@@ -515,8 +400,8 @@ __global__ __launch_bounds__(256, 2) void attn_psp_kernel(PsArgs a, const unsign
   if constexpr (MODE == PS_WIN14) {   // the indicator table, once per workgroup: a linear copy of the (already swizzled) global image
     for (int i = wave; i < PSP_EBYTES / 1024; i += 4) ps_glds16(etab, (unsigned)(i * 1024 + lane * 16), lds0 + G::E_OFF + (unsigned)i * 1024u);
   }
-  const int tr_off = (((lane >> 2) & 3) + 4 * h) * VP + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-  const int k_off = r * KP + 8 * h;                                   // halfs, within a K stage
+  const int tr_off = attn_tr_off<VP>(lane, h);
+  const int k_off = r * KP + 8 * h;                                  // halfs, within a K stage
   int e_off[2];                                                       // bytes, within the table, of key row r (kbase % 32 == 0)
 #pragma unroll
   for (int c = 0; c < 2; ++c) e_off[c] = r * 64 + (((2 * c + h) ^ ((r >> 2) & 3)) * 16);
@@ -537,11 +422,10 @@ __global__ __launch_bounds__(256, 2) void attn_psp_kernel(PsArgs a, const unsign
   {
     const unsigned nqb = (unsigned)a.nqb;
     if ((a.B & 7) == 0) {
-      const unsigned c = L & 7u, j = L >> 3;
-      const unsigned per_b = (unsigned)a.H * nqb;
-      const unsigned bl = j / per_b, rem = j - bl * per_b;
-      item = (int)((bl * 8u + c) * (unsigned)a.H + rem / nqb);
-      bx = (int)(rem % nqb);
+      int be, rem;      // batch element, slot within it = head * nqb + query block
+      attn_xcd_item(L, (unsigned)a.H * nqb, be, rem);
+      item = (int)((unsigned)be * (unsigned)a.H + (unsigned)rem / nqb);
+      bx = (int)((unsigned)rem % nqb);
     } else {
       item = (int)(L / nqb);
       bx = (int)(L % nqb);
@@ -695,14 +579,7 @@ __global__ __launch_bounds__(256, 2) void attn_psp_kernel(PsArgs a, const unsign
   // QK^T of key chunk ci into a fresh accumulator (PS_RELT: started at the prefetched rel-pos terms)
   auto qk = [&](int ci, f32x16& s, const h16x8 (&QH)[KS], const h16x8 (&QL)[KS]) {
     const _Float16* krow = (const _Float16*)(ps_smem + G::K_RING + (ci % 3) * G::KSTAGE) + k_off;
-#pragma unroll
-    for (int c = 0; c < KS; ++c) {
-      const h16x8 kh8 = *(const h16x8*)(krow + 16 * c);
-      const h16x8 kl8 = *(const h16x8*)(krow + HD + 16 * c);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, QH[c], s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, QL[c], s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, QH[c], s, 0, 0, 0);
-    }
+    attn_qk_tile<HD, 3>(krow, QH, QL, s);
     if constexpr (MODE == PS_WIN14) {
       const unsigned char* eb = ps_smem + G::E_OFF + ci * (PS_CHUNK * 64);
 #pragma unroll
@@ -755,24 +632,11 @@ __global__ __launch_bounds__(256, 2) void attn_psp_kernel(PsArgs a, const unsign
     //   with_next: there is a next pair; nci its key chunk
     auto tile = [&](auto cur_c, auto nxt_c, bool wn, int nci) {
       constexpr int CUR = decltype(cur_c)::value, NXT = decltype(nxt_c)::value;
-      if (kbase + 32 > a.S) {   // uniform: the tile that crosses the end of the sequence
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int kg = kbase + (e & 3) + 8 * (e >> 2) + 4 * h;
-          s_cur[e] = kg >= a.S ? NEG_INF : s_cur[e];
-        }
-      }
-      if (MODE == PS_PLAIN && CUR == 0 && keep_row && bx == 0 && wave == 0) {   // uniform: the tile that owns query 0
-        const int kk = kbase + (lane & 31);
-        const unsigned kb = kk >= 1 && kk < a.S ? keepL[kk - 1] : 1u;
-        const unsigned bits = (unsigned)__builtin_amdgcn_ballot_w64(kb != 0) >> (4 * h);
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const bool kept = (bits >> ((e & 3) + 8 * (e >> 2))) & 1u;
-          s_cur[e] = (qi[0] == 0 && !kept) ? NEG_INF : s_cur[e];
-        }
-      }
-      // ---- segment A (one basic block).  The interleave is written out by hand: 19 groups of soft-max work (U: the max chain,
+      attn_mask_tail(s_cur, kbase, a.S, h);
+      if (MODE == PS_PLAIN && CUR == 0 && keep_row && bx == 0 && wave == 0)   // uniform: the tile that owns query 0
+        attn_mask_cls_keep(s_cur, keepL, kbase, a.S, lane, h, qi[0]);
+      // ---- segment A (one basic block): the operations of attn_softmax_tile (attn_tile.h; keep the two in step) beside the next
+      // tile's QK^T chain.  The interleave is written out by hand: 19 groups of soft-max work (U: the max chain,
       // the rescaling decision; E_k: two exponentials; F_k / G_k: the hi / lo split of a pair), each behind its share of the
       // QK^T chain's matrix instructions, with __builtin_amdgcn_sched_barrier(0) between the groups -- sched_group_barrier
       // pipelines are not honoured by this compiler for this block (it emits the dependent MFMAs first and the soft-max behind
@@ -889,22 +753,7 @@ __global__ __launch_bounds__(256, 2) void attn_psp_kernel(PsArgs a, const unsign
       if (!(PS_DBG(a) & 2)) {
         const _Float16* Vh = (const _Float16*)(ps_smem + G::V_RING + (ci & 1) * G::VSTAGE);
         const _Float16* Vl = (const _Float16*)(ps_smem + G::V_RING + (ci & 1) * G::VSTAGE + G::VL_OFF);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          if (kbase + 16 * s2 >= a.S) break;   // uniform
-#pragma unroll
-          for (int d = 0; d < DT; ++d) {
-            const int off = (16 * s2) * VP + d * 32 + tr_off;
-            const h16x4 vh0 = ps_tr4(Vh + off), vh1 = ps_tr4(Vh + off + 8 * VP);
-            const h16x4 vl0 = ps_tr4(Vl + off), vl1 = ps_tr4(Vl + off + 8 * VP);
-            h16x8 vh8, vl8;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { vh8[e] = vh0[e]; vh8[4 + e] = vh1[e]; vl8[e] = vl0[e]; vl8[4 + e] = vl1[e]; }
-            o[CUR][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl8, ph[s2], o[CUR][d], 0, 0, 0);
-            o[CUR][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, pl[s2], o[CUR][d], 0, 0, 0);
-            o[CUR][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh8, ph[s2], o[CUR][d], 0, 0, 0);
-          }
-        }
+        attn_pv_tile<DT, VP, 3>(Vh, Vl, tr_off, kbase, a.S, ph, pl, o[CUR]);
       }
       if (wn) s_cur = s_next;
     };

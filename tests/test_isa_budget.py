@@ -22,6 +22,17 @@ BUDGETS = {
         "dec_tail_kernel": (128, 0),          # sixteen waves per CU
         "dec_i2t_kernel": (128, 0),
     },
+    # the split-fp16 attention kernels (their tile steps are shared through attn_tile.h): two waves per SIMD in every
+    # instantiation -- two 4-wave workgroups per CU, or one 8-wave workgroup -- and nothing spilled
+    "attention.hip": {
+        "attn_x3_kernel": (256, 0),
+        "attn_x3pp_kernel": (256, 0),         # one 8-wave workgroup per CU = two waves per SIMD
+        "attn_x3q_kernel": (256, 0),
+    },
+    "attention_ps.hip": {
+        "attn_ps_kernel": (256, 0),
+        "attn_psp_kernel": (256, 0),
+    },
 }
 
 
