@@ -235,6 +235,8 @@ PROTOTYPES = {
     "hgl_rle_match_device": (_I, [_VP, _LL, _VP, _I, _VP, _LL, _VP, _I, _VP, _I, _VP, _VP, _LL, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_rle_from_polygons_workspace_bytes": (_SZ, [_VP, _I, _I, _I]),
     "hgl_rle_from_polygons_device": (_I, [_VP, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _LL, _VP, _VP, _VP, _SZ, _VP]),
+    "hgl_rle_merge_workspace_bytes": (_SZ, [_VP, _I, _I, _LL, _I, _I]),
+    "hgl_rle_merge_device": (_I, [_VP, _LL, _VP, _I, _VP, _I, _VP, _I, _VP, _VP, _VP, _LL, _VP, _I, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

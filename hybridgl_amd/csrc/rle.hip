@@ -19,13 +19,14 @@
 //      what the slot holds; the second sweep takes the words 256 at a time: an exclusive sum-scan of the pop-counts gives the
 //      rank of every word's first transition, an exclusive max-scan of "position of my last transition" the position of the
 //      last earlier one, both carried from chunk to chunk, and every transition writes its own counts[k] = p_k - p_(k-1)
-//      (rle_counts_chunk in rle_scan.h: the polygon rasteriser of rle_poly.hip ends in the same scan).
+//      (rle_counts_chunk in rle_scan.h: the polygon rasteriser of rle_poly.hip ends in the same scan).  Both sweeps are
+//      rle_write_runs, a device function over any column plane: the merge kernel further down ends in it too.
 //
 // Slot forms (table row = n_counts, form, area, 0): 0 = the n_counts counts (whenever they fit), 1 = the column-major bit
 // plane (bit p % 32 of word p / 32; whenever the counts do not fit but ceil(H*W/32) words do), 2 = neither fits, nothing
 // written, 3 = the index is outside [0, N), nothing read or written.  Words beyond what the form defines keep their bytes.
 #include "hgl_common.h"
-#include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan, rle_match_plan: plain C++, shared with the sanitizer harnesses
+#include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan, rle_match_plan, rle_merge_plan: plain C++, shared with the sanitizer harnesses
 #include "rle_scan.h"       // RLE_THREADS, rle_block_sum, rle_group_find, rle_counts_chunk: shared with rle_poly.hip
 
 namespace {
@@ -96,19 +97,12 @@ __device__ __forceinline__ uint32_t rle_column_bits(const unsigned long long* co
   return (uint32_t)v & (n == 32 ? 0xffffffffu : ((1u << n) - 1u));
 }
 
-__global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned long long* __restrict__ plane, int N, int H, int W,
-                                                               const long long* __restrict__ sel, int HW64,
-                                                               uint32_t* __restrict__ slots, long long slot_words,
-                                                               int32_t* __restrict__ table) {
-  __shared__ unsigned red[4];
-  __shared__ unsigned wsum[4], wmax[4];
-  const int s = blockIdx.x, t = threadIdx.x;
-  int32_t* row = table + (size_t)s * 4;
-  if (rle_pick(sel, s, N) < 0) {
-    if (t == 0) { row[0] = 0; row[1] = 3; row[2] = 0; row[3] = 0; }
-    return;
-  }
-  const unsigned long long* P = plane + (size_t)s * W * HW64;
+// The run writer: what the slot and the table row of one H x W mask hold, out of its column plane P (W * HW64 words, padding bits
+// 0).  The whole workgroup calls it; red, wsum, wmax: 4 words of LDS each.  ONE copy: the encoder's plane comes from
+// rle_columns_kernel, the merge's from the vote of its own workgroup (rle_merge_kernel below).
+__device__ __forceinline__ void rle_write_runs(const unsigned long long* P, int H, int W, int HW64, uint32_t* slot, long long slot_words,
+                                               int32_t* row, unsigned* red, unsigned* wsum, unsigned* wmax) {
+  const int t = threadIdx.x;
   const unsigned Q = (unsigned)W * (unsigned)HW64;
   const unsigned HW = (unsigned)H * (unsigned)W;      // < 2^31 (checked by the host entry)
 
@@ -125,7 +119,6 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned lo
   const unsigned plane_words = (HW + 31u) / 32u;
   const int form = (long long)n_counts <= slot_words ? 0 : ((long long)plane_words <= slot_words ? 1 : 2);
   if (t == 0) { row[0] = (int32_t)n_counts; row[1] = form; row[2] = (int32_t)area; row[3] = 0; }
-  uint32_t* slot = slots + (size_t)s * (size_t)slot_words;
   if (form == 2) return;
   if (form == 1) {
     // the bit plane in run order: 32 pixels per word, LSB first; a word may span several columns when H < 32
@@ -157,6 +150,21 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned lo
     rle_counts_chunk(T, p0, slot, rank_base, last_base, wsum, wmax);      // rle_scan.h; k < trans < n_counts <= slot_words
   }
   if (t == 0) slot[trans] = HW - last_base;
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned long long* __restrict__ plane, int N, int H, int W,
+                                                               const long long* __restrict__ sel, int HW64,
+                                                               uint32_t* __restrict__ slots, long long slot_words,
+                                                               int32_t* __restrict__ table) {
+  __shared__ unsigned red[4];
+  __shared__ unsigned wsum[4], wmax[4];
+  const int s = blockIdx.x, t = threadIdx.x;
+  int32_t* row = table + (size_t)s * 4;
+  if (rle_pick(sel, s, N) < 0) {
+    if (t == 0) { row[0] = 0; row[1] = 3; row[2] = 0; row[3] = 0; }
+    return;
+  }
+  rle_write_runs(plane + (size_t)s * W * HW64, H, W, HW64, slots + (size_t)s * (size_t)slot_words, slot_words, row, red, wsum, wmax);
 }
 
 // ---- the way back: slots + table -> masks (hgl_rle_decode_device, hgl_rle_decode_group_device) and intersection / union of two
@@ -511,6 +519,135 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_iou_kernel(const unsigned lon
   inter = rle_block_sum(inter, red);
   uni = rle_block_sum(uni, red);
   if (t == 0) { iu[(size_t)s * 2] = (long long)inter; iu[(size_t)s * 2 + 1] = (long long)uni; }
+}
+
+// ---- new masks out of encoded masks (hgl_rle_merge_device): output entry s is a vote over k_s source entries of its own image,
+// a pixel is set iff lo_s <= (members that cover it) <= hi_s -- rleMerge (refer/external/maskApi.c:49-70) is lo = 1 (union) or
+// lo = k (intersection) with hi = k.  Three launches whatever G, S, M and the sizes are: A and D above put the source set's column
+// words into the workspace; then
+//
+//   G. rle_merge_kernel   one workgroup per output entry.  It checks the entry's members (a block-wide maximum of their codes),
+//      then a thread owns plane word q = x*HW64 + j and walks the members: a member's word is one 8-byte load, coalesced over the
+//      workgroup (the words of an entry are contiguous); the member index is the same for every thread (a scalar load).  The
+//      count of every one of the word's 64 pixels is kept bit-sliced: slice b holds bit b of all 64 counts, ceil(log2(k+1)) <= 16
+//      slices, and a member is added by a ripple of AND / XOR through them (count <= k never carries out of the top slice).
+//      lo <= count and count <= hi are two bit-serial comparisons from the top slice down (hi clamped to k; lo > k sets nothing).
+//      All loop bounds are uniform over the workgroup; no pixel is ever a byte.  The padding bits beyond H are masked (the rule
+//      (0, 0) would set them).  The merged word goes to the entry's plane in the workspace -- materialised once: both sweeps of
+//      the run writer read it, and a re-vote per sweep would read k words for each -- and after a barrier the workgroup runs
+//      rle_write_runs on it: the encoder's own slot and table row.
+// One plane word of a vote: the counts of its 64 pixels over the k members mem[0 .. k) (absolute source indices; the word of
+// member m lies at P[(m - src_lo) * Q]), bit-sliced into NB slices (k < 2^NB), and the pixels whose count lies in [lo, hi]
+// (0 <= lo, hi <= k).  All loop bounds are uniform over the workgroup.
+template <int NB>
+__device__ __forceinline__ unsigned long long rle_vote_word(const unsigned long long* __restrict__ P, unsigned Q,
+                                                            const int32_t* __restrict__ mem, int k, int src_lo, int lo, int hi) {
+  unsigned long long c[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) c[b] = 0;
+#pragma unroll 4
+  for (int i = 0; i < k; ++i) {
+    unsigned long long carry = P[(size_t)(mem[i] - src_lo) * Q];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {      // a ripple add of one bit per pixel; count <= k never carries out of the top slice
+      const unsigned long long both = c[b] & carry;
+      c[b] ^= carry;
+      carry = both;
+    }
+  }
+  unsigned long long gt = 0, lt = 0, eq_lo = ~0ull, eq_hi = ~0ull;      // count > lo, count < hi, equal so far
+#pragma unroll
+  for (int b = NB - 1; b >= 0; --b) {
+    const unsigned long long lb = ((lo >> b) & 1) ? ~0ull : 0ull, hb = ((hi >> b) & 1) ? ~0ull : 0ull;
+    gt |= eq_lo & c[b] & ~lb;
+    eq_lo &= ~(c[b] ^ lb);
+    lt |= eq_hi & ~c[b] & hb;
+    eq_hi &= ~(c[b] ^ hb);
+  }
+  return (gt | eq_lo) & (lt | eq_hi);
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_merge_kernel(const unsigned long long* __restrict__ src_plane,
+                                                                const int32_t* __restrict__ src_status, const RleMerge geo,
+                                                                const int32_t* __restrict__ members, int M,
+                                                                const int32_t* __restrict__ member_offsets,
+                                                                const int32_t* __restrict__ bounds, unsigned long long* merged,
+                                                                uint32_t* __restrict__ slots, long long slot_words,
+                                                                int32_t* __restrict__ table, int32_t* __restrict__ status) {
+  __shared__ unsigned red[4];
+  __shared__ unsigned wsum[4], wmax[4];
+  const int s = blockIdx.x, t = threadIdx.x;
+  const int g = rle_group_find(geo.first_out, geo.G, s);
+  const int H = geo.H[g], W = geo.W[g], HW64 = (H + 63) / 64;
+  const unsigned Q = (unsigned)W * (unsigned)HW64;
+  const int src_lo = geo.first_src[g], src_hi = geo.first_src[g + 1];
+  const long long o0 = member_offsets[s], o1 = member_offsets[s + 1];
+  const int lo = bounds[(size_t)s * 2], hi = bounds[(size_t)s * 2 + 1];
+  int32_t* row = table + (size_t)s * 4;
+  int32_t* st = status + (size_t)s * 4;
+  // everything up to the vote is uniform over the workgroup
+  bool ok = o0 >= 0 && o0 <= o1 && o1 <= (long long)M;
+  const int k = ok ? (int)(o1 - o0) : 0;
+  ok = ok && k <= 65535 && lo >= 0 && lo <= hi;
+  unsigned worst = 0;      // the largest code among the members; 2 for a member outside the image's own source entries
+  if (ok) {
+    for (int i = t; i < k; i += RLE_THREADS) {
+      const int m = members[o0 + i];
+      unsigned code = 2;
+      if (m >= src_lo && m < src_hi) {
+        const int c = src_status[(size_t)m * 4];
+        code = c == 0 ? 0u : (c == 1 ? 1u : 2u);
+      }
+      worst = worst > code ? worst : code;
+    }
+    worst = rle_block_max(worst, red);
+  }
+  if (!ok || worst == 2u) {
+    if (t == 0) {
+      row[0] = 0; row[1] = 3; row[2] = 0; row[3] = 0;
+      st[0] = 2; st[1] = k; st[2] = 0; st[3] = 0;
+    }
+    return;
+  }
+  if (t == 0) { st[0] = (int32_t)worst; st[1] = k; st[2] = 0; st[3] = 0; }
+  int nb = 0;      // slices: count <= k < 2^nb
+  while ((k >> nb) != 0) ++nb;
+  const int hic = hi < k ? hi : k;
+  const bool none = lo > k;
+  const unsigned long long* Ps = src_plane + (size_t)geo.word0_src[g];
+  unsigned long long* Pm = merged + (size_t)geo.word0_out[g] + (size_t)(s - geo.first_out[g]) * Q;
+  for (unsigned q = t; q < Q; q += RLE_THREADS) {
+    unsigned long long in;      // lo <= count <= hi, 64 pixels at once; NB: nb rounded up, the slices above nb stay 0
+    if (nb <= 2) in = rle_vote_word<2>(Ps + q, Q, members + o0, k, src_lo, lo, hic);
+    else if (nb <= 4) in = rle_vote_word<4>(Ps + q, Q, members + o0, k, src_lo, lo, hic);
+    else if (nb <= 8) in = rle_vote_word<8>(Ps + q, Q, members + o0, k, src_lo, lo, hic);
+    else in = rle_vote_word<16>(Ps + q, Q, members + o0, k, src_lo, lo, hic);
+    const int j = (int)(q % (unsigned)HW64);
+    const int nv = H - 64 * j < 64 ? H - 64 * j : 64;
+    const unsigned long long valid = nv == 64 ? ~0ull : ((1ull << nv) - 1ull);      // rle_transitions' valid bits
+    Pm[q] = none ? 0ull : (in & valid);
+  }
+  __syncthreads();      // the workgroup's own plane words are written: every thread may read any of them
+  rle_write_runs(Pm, H, W, HW64, slots + (size_t)s * (size_t)slot_words, slot_words, row, red, wsum, wmax);
+}
+
+// the workspace of a merge: the source set's run starts, status and planes, then the merged planes
+struct RleMergeWs {
+  size_t E, status, plane, merged, total;
+};
+RleMergeWs rle_merge_ws(const RleMergePlan& plan, int Ssrc, long long sw) {
+  RleMergeWs w;
+  size_t p = 0;
+  w.E = p;
+  p += hgl_align_up((size_t)Ssrc * (size_t)(sw + 1) * sizeof(uint32_t), 256);
+  w.status = p;
+  p += hgl_align_up((size_t)Ssrc * 4 * sizeof(int32_t), 256);
+  w.plane = p;
+  p += hgl_align_up((size_t)plan.words_src * sizeof(unsigned long long), 256);
+  w.merged = p;
+  p += hgl_align_up((size_t)plan.words_out * sizeof(unsigned long long), 256);
+  w.total = p;
+  return w;
 }
 
 // ---- every mask of one set against every mask of another, image by image (hgl_rle_match_device).
@@ -950,6 +1087,58 @@ int hgl_rle_match_device(const uint32_t* slots_a, long long slot_words_a, const 
                        (const int32_t*)status[1], crowd_b, plan.m, plan.splits, plan.pairs, (const int32_t*)partial, inter, match_a,
                        match_b);
   return hgl_check_launch("rle_match_device");
+}
+
+size_t hgl_rle_merge_workspace_bytes(const int64_t* images_host, int G, int Ssrc, long long slot_words_src, int S, int M) {
+  if (!images_host || slot_words_src < 0 || S == 0) return 0;
+  RleMergePlan plan;
+  char why[200];
+  if (rle_merge_plan(images_host, G, Ssrc, S, M, &plan, why, sizeof(why)) != 0) return 0;
+  return rle_merge_ws(plan, Ssrc, slot_words_src).total;
+}
+
+int hgl_rle_merge_device(const uint32_t* slots_src, long long slot_words_src, const int32_t* table_src, int Ssrc,
+                         const int64_t* images_host, int G, const int32_t* members, int M, const int32_t* member_offsets,
+                         const int32_t* bounds, uint32_t* slots, long long slot_words, int32_t* table, int S, int32_t* status, void* ws,
+                         size_t ws_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(images_host && Ssrc >= 0 && S >= 0 && M >= 0 && slot_words_src >= 0 && slot_words >= 0 &&
+                  (Ssrc == 0 || (slots_src && table_src)) && (M == 0 || members) &&
+                  (S == 0 || (member_offsets && bounds && slots && table && status)),
+              "rle_merge_device: bad arguments");
+  RleMergePlan plan;
+  char why[200];
+  if (rle_merge_plan(images_host, G, Ssrc, S, M, &plan, why, sizeof(why)) != 0) {
+    hgl_set_error("rle_merge_device: %s", why);
+    return HGL_EINVAL;
+  }
+  if (S == 0) return HGL_OK;      // nothing to write: no launch, no workspace
+  const RleMergeWs w = rle_merge_ws(plan, Ssrc, slot_words_src);
+  if (!ws || ws_bytes < w.total) {
+    hgl_set_error("rle_merge_device: workspace too small");
+    return HGL_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)ws;
+  uint32_t* E = (uint32_t*)(base + w.E);
+  int32_t* status_src = (int32_t*)(base + w.status);
+  unsigned long long* plane = (unsigned long long*)(base + w.plane);
+  unsigned long long* merged = (unsigned long long*)(base + w.merged);
+  if (Ssrc > 0) {
+    RleGroup grp;      // what the starts kernel reads of it: the sizes and the first entries
+    memset(&grp, 0, sizeof(grp));
+    grp.G = G;
+    for (int g = 0; g < G; ++g) { grp.H[g] = plan.src.H[g]; grp.W[g] = plan.src.W[g]; grp.first[g] = plan.src.first[g]; }
+    hipLaunchKernelGGL((rle_starts_kernel<false, RleGroup>), dim3((unsigned)Ssrc), dim3(RLE_THREADS), 0, st, slots_src, slot_words_src,
+                       table_src, grp, E, slot_words_src + 1, status_src, (int32_t*)nullptr);
+    HGL_TRY(hgl_check_launch("rle_merge_device"));
+    hipLaunchKernelGGL(rle_plane_kernel<RlePlaneGroup>, dim3((unsigned)plan.blocks_src), dim3(RLE_THREADS), 0, st, slots_src,
+                       slot_words_src, table_src, (const uint32_t*)E, slot_words_src + 1, (const int32_t*)status_src, plan.src, plane);
+    HGL_TRY(hgl_check_launch("rle_merge_device"));
+  }
+  hipLaunchKernelGGL(rle_merge_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)plane,
+                     (const int32_t*)status_src, plan.m, members, M, member_offsets, bounds, merged, slots, slot_words, table, status);
+  return hgl_check_launch("rle_merge_device");
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // The geometry of the RLE entries (csrc/rle.hip): the tiling of an image, shared by the encoder and the decoder, and what the host
-// works out of a decode call's image rows (rle_group_plan) and of a match call's (rle_match_plan) and hands to the kernels by
-// value, and likewise of a polygon call's (rle_poly_plan, csrc/rle_poly.hip).  Plain C++ without a HIP construct: the .hip files
-// include it, and so do the sanitizer harnesses
-// tests/native/rle_group_sanitize.cpp and tests/native/rle_match_sanitize.cpp.
+// works out of a decode call's image rows (rle_group_plan), of a match call's (rle_match_plan) and of a merge call's
+// (rle_merge_plan) and hands to the kernels by value, and likewise of a polygon call's (rle_poly_plan, csrc/rle_poly.hip).  Plain
+// C++ without a HIP construct: the .hip files include it, and so do the sanitizer harnesses
+// tests/native/rle_group_sanitize.cpp, tests/native/rle_match_sanitize.cpp and tests/native/rle_merge_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
 #include <stdint.h>
@@ -199,6 +199,72 @@ static inline int rle_match_plan(const int64_t* images, int G, int Sa, int Sb, l
   plan->splits = (int)(want < 1 ? 1 : (want > RLE_MATCH_SPLITS_MAX ? RLE_MATCH_SPLITS_MAX : want));
   return 0;
 #undef RLE_MATCH_REQUIRE
+}
+
+// ---- hgl_rle_merge_device: every output entry is a vote over source entries of its own image.  The source set goes through the
+// plane kernel (RlePlaneGroup, as a side of the match does); a workgroup of the merge kernel owns one output entry, finds its
+// image by its first output entry and writes the merged plane into the workspace before it writes the runs.
+struct RleMerge {
+  unsigned long long word0_out[RLE_GROUP_MAX];      // the plane word the image's first output entry starts at
+  unsigned word0_src[RLE_GROUP_MAX];                // the plane word its first source entry starts at
+  int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
+  int first_src[RLE_GROUP_MAX + 1], first_out[RLE_GROUP_MAX + 1];      // first entries; [G] = Ssrc / S
+  int G;
+};
+
+struct RleMergePlan {
+  RleMerge m;
+  RlePlaneGroup src;
+  long long blocks_src;                 // grid size of the plane kernel
+  long long words_src, words_out;       // 64-bit plane words of the source set and of the merged set
+};
+
+// images [G,4] = (H, W, first source entry, first output entry) -> *plan; 0, or -1 with the reason in why.  Checked: 1 <= G <= 64;
+// Ssrc, S, M >= 0; H*W < 2^31; entries from 0 to Ssrc / S without a step back; fewer than 2^31 plane blocks, fewer than 2^32 plane
+// words on either side.
+static inline int rle_merge_plan(const int64_t* images, int G, int Ssrc, int S, int M, RleMergePlan* plan, char* why, size_t why_cap) {
+#define RLE_MERGE_REQUIRE(cond, ...)        \
+  do {                                      \
+    if (!(cond)) {                          \
+      snprintf(why, why_cap, __VA_ARGS__);  \
+      return -1;                            \
+    }                                       \
+  } while (0)
+  RLE_MERGE_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
+  RLE_MERGE_REQUIRE(Ssrc >= 0 && S >= 0 && M >= 0, "bad set sizes %d, %d and %d members", Ssrc, S, M);
+  memset(plan, 0, sizeof(*plan));
+  RleMerge* m = &plan->m;
+  m->G = plan->src.G = G;
+  for (int g = 0; g < G; ++g) {
+    const int64_t* r = images + 4 * g;
+    const long long H = r[0], W = r[1], es = r[2], eo = r[3];
+    const long long es_next = g + 1 < G ? r[4 + 2] : (long long)Ssrc, eo_next = g + 1 < G ? r[4 + 3] : (long long)S;
+    RLE_MERGE_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
+                      "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
+    RLE_MERGE_REQUIRE(es >= 0 && es <= es_next && es_next <= (long long)Ssrc && (g > 0 || es == 0),
+                      "image %d: source entries %lld .. %lld (rows must not decrease, from 0 to Ssrc = %d)", g, es, es_next, Ssrc);
+    RLE_MERGE_REQUIRE(eo >= 0 && eo <= eo_next && eo_next <= (long long)S && (g > 0 || eo == 0),
+                      "image %d: output entries %lld .. %lld (rows must not decrease, from 0 to S = %d)", g, eo, eo_next, S);
+    const long long ns = es_next - es, no = eo_next - eo;
+    const long long HW64 = (H + 63) / 64, Q = W * HW64, q_tiles = (Q + 255) / 256;      // Q <= H*W < 2^31
+    m->H[g] = plan->src.H[g] = (int)H;
+    m->W[g] = plan->src.W[g] = (int)W;
+    m->first_src[g] = plan->src.first[g] = (int)es;
+    m->first_out[g] = (int)eo;
+    m->word0_src[g] = plan->src.word0[g] = (unsigned)plan->words_src;
+    m->word0_out[g] = (unsigned long long)plan->words_out;
+    plan->src.blk0[g] = (unsigned)plan->blocks_src;
+    plan->words_src += ns * Q;
+    plan->words_out += no * Q;
+    plan->blocks_src += ns * q_tiles;
+    RLE_MERGE_REQUIRE(plan->words_src < (1ll << 32) && plan->words_out < (1ll << 32),
+                      "too many plane words for one call (sum of n*W*ceil(H/64) must be < 2^32 per side)");
+    RLE_MERGE_REQUIRE(plan->blocks_src < (1ll << 31), "too many entries (%d) for one launch", Ssrc);
+  }
+  m->first_src[G] = Ssrc;
+  m->first_out[G] = S;
+  return 0;
+#undef RLE_MERGE_REQUIRE
 }
 
 // ---- hgl_rle_from_polygons_device (csrc/rle_poly.hip): polygons -> RLE, one workgroup per entry.  A polygon's toggle plane --

@@ -17,6 +17,7 @@ background is OpenCV's fixed-point GaussianBlur restated on the device (Hybridgl
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m hybridgl_amd.main --real ...
     python -m hybridgl_amd.main --synthetic 8 --save_masks out      # ... and later, with no model or checkpoint:
     python -m hybridgl_amd.main --synthetic 8 --score_masks out     # the same report from the saved masks and the ground truth
+    python -m hybridgl_amd.main --synthetic 8 --ensemble_masks a b c --ensemble_out voted   # saved runs voted into one, scored, saved
     python -m hybridgl_amd.main --real ... --save_proposals props   # SAM's proposals kept per image (hybridgl_amd/proposals.py) ...
     python -m hybridgl_amd.main --real ... --proposals_dir props --fusion_mode L2G     # ... and evaluated from, with no SAM
 
@@ -95,6 +96,16 @@ def default_argument_parser():
     p.add_argument("--score_masks", default="", metavar="DIR",
                    help="score the predictions a run saved with --save_masks DIR against the dataset's ground truth, without any "
                         "model or checkpoint (the dataset flags as in that run); exits non-zero when a stored count differs")
+    p.add_argument("--ensemble_masks", nargs="+", default=[], metavar="DIR",
+                   help="vote two or more runs saved with --save_masks into one prediction, mask by mask on the device "
+                        "(predictions.ensemble: ops.rle_merge on the strings' runs), score it against the dataset's ground truth "
+                        "and write it to --ensemble_out; no model is built, no checkpoint read (the dataset flags as in those runs)")
+    p.add_argument("--ensemble_rule", default="majority", metavar="RULE",
+                   help="with --ensemble_masks: majority, union, intersect, at_least:T or exactly:T over the (weighted) votes")
+    p.add_argument("--ensemble_weights", nargs="+", type=int, default=None, metavar="W",
+                   help="with --ensemble_masks: one non-negative integer per directory; a run of weight 2 votes twice")
+    p.add_argument("--ensemble_out", default="", metavar="OUT",
+                   help="with --ensemble_masks: the directory that receives the voted masks.rank0.jsonl (readable by --score_masks)")
     p.add_argument("--save_proposals", default="", metavar="DIR",
                    help="with --real: keep the mask generator's proposals beside the run, DIR/<image_id>.json in the format of "
                         "SAM's scripts/amg.py --convert-to-rle plus DIR/meta.json (INTEGRATION.md); the run itself is unchanged")
@@ -475,7 +486,7 @@ def check_device_targets(args):
     """--device_targets belongs to the two branches that build no model, on REFER annotations"""
     if not getattr(args, "device_targets", False):
         return
-    if not (getattr(args, "score_masks", "") or getattr(args, "proposal_ceiling", "")):
+    if not (getattr(args, "score_masks", "") or getattr(args, "proposal_ceiling", "") or getattr(args, "ensemble_masks", None)):
         raise SystemExit("--device_targets applies to --score_masks and --proposal_ceiling only: a run's own targets ride with its "
                          "items")
     if not args.real or args.dataset == "phrasecut":
@@ -546,6 +557,58 @@ def score_masks_main(args, dev):
     return m
 
 
+def check_ensemble_flags(args):
+    """what --ensemble_masks needs and what it does not go with"""
+    dirs = list(getattr(args, "ensemble_masks", None) or [])
+    if len(dirs) < 2:
+        raise SystemExit(f"--ensemble_masks takes two or more directories, got {len(dirs)}: one run is its own ensemble")
+    w = getattr(args, "ensemble_weights", None)
+    if w is not None and len(w) != len(dirs):
+        raise SystemExit(f"--ensemble_weights has {len(w)} values for {len(dirs)} directories: one weight per directory")
+    if getattr(args, "score_masks", "") or getattr(args, "proposal_ceiling", ""):
+        raise SystemExit("--ensemble_masks does not combine with --score_masks or --proposal_ceiling: score the ensemble's own "
+                         "--ensemble_out afterwards")
+    if not getattr(args, "ensemble_out", ""):
+        raise SystemExit("--ensemble_masks needs --ensemble_out: the directory that receives the voted predictions")
+
+
+def ensemble_masks(args, dev):
+    """--ensemble_masks DIR DIR [DIR ...] --ensemble_out OUT: the saved runs voted into one prediction (predictions.ensemble),
+    scored against the dataset's ground truth as --score_masks scores a run (predictions.score over offline_targets) and saved
+    to OUT with the counts filled in -- no model is built, no checkpoint read.  Returns (metrics, {"rows", "missing", "extra",
+    "path"})."""
+    from . import dist as D
+    from . import predictions as P
+    resolve_defaults(args)
+    check_ensemble_flags(args)
+    check_device_targets(args)
+    records = P.ensemble(list(args.ensemble_masks), rule=args.ensemble_rule, weights=args.ensemble_weights, device=dev)
+    rows, missing, extra = P.score(records, ((key, t) for key, _, t in offline_targets(args, dev)))
+    counts = {(int(r[0]), int(r[1])): [int(v) for v in r[2:6]] for r in rows}
+    for rec in records:      # a record without a target keeps zeros: --score_masks on OUT will name it as extra
+        rec["I"], rec["U"], rec["I_final"], rec["U_final"] = counts.get((rec["index"], rec["sentence"]), [0, 0, 0, 0])
+    path = P.save(records, args.ensemble_out, 0)
+    return D.metrics_from_rows(rows), {"rows": rows, "missing": missing, "extra": extra, "path": path}
+
+
+def ensemble_masks_main(args, dev):
+    """the --ensemble_masks branch of main(): report, result log, one line that names the rule and the sets"""
+    check_ensemble_flags(args)
+    try:
+        m, rep = ensemble_masks(args, dev)
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"hybridgl_amd.main: {e}")
+    for name, what in (("missing", "dataset sentence without a saved record"), ("extra", "saved record without a dataset sentence")):
+        for k in rep[name]:
+            print(f"{what}: index {k[0]} sentence {k[1]}")
+    write_report(args, report_text(args, m))
+    w = args.ensemble_weights
+    print(f"ensemble of {len(args.ensemble_masks)} saved runs by {args.ensemble_rule}"
+          + (f" with weights {' '.join(str(v) for v in w)}" if w else "")
+          + f" ({', '.join(args.ensemble_masks)}): {len(rep['rows'])} sentences written to {rep['path']} (no model built)")
+    return m
+
+
 def proposal_ceiling(args, dev):
     """--proposals_dir DIR --proposal_ceiling OUT: the ceiling of a proposal store against the dataset's ground truth from the
     files alone -- no model is built, no checkpoint read.  Jobs, items and targets are those of score_masks(); the stored runs
@@ -583,19 +646,16 @@ def save_masks(pipe, directory, rank=0):
     {"index": dataset position, "sentence": sentence number, "size": [H, W], "pure", "final": the winning masks (pure CLIP /
     with spatial guidance) as COCO compressed RLE strings (sam.coco_encode_rle), "I", "U", "I_final", "U_final": the metric
     row's counts}.  Returns the path."""
-    import json
+    from . import predictions as P
     from .sam import coco_encode_rle
-    os.makedirs(directory, exist_ok=True)
-    path = os.path.join(directory, f"masks.rank{rank}.jsonl")
-    rows = pipe.partial_rows()
-    with open(path, "w") as f:
-        for rec, row in zip(pipe.predictions(), rows):
-            assert (rec["index"], rec["sentence"]) == (int(row[0]), int(row[1]))
-            enc = lambda counts: coco_encode_rle({"size": rec["size"], "counts": counts})["counts"]
-            f.write(json.dumps({"index": rec["index"], "sentence": rec["sentence"], "size": rec["size"], "pure": enc(rec["pure"]),
-                                "final": enc(rec["final"]), "I": int(row[2]), "U": int(row[3]), "I_final": int(row[4]),
-                                "U_final": int(row[5])}) + "\n")
-    return path
+    records = []
+    for rec, row in zip(pipe.predictions(), pipe.partial_rows()):
+        assert (rec["index"], rec["sentence"]) == (int(row[0]), int(row[1]))
+        enc = lambda counts: coco_encode_rle({"size": rec["size"], "counts": counts})["counts"]
+        records.append({"index": rec["index"], "sentence": rec["sentence"], "size": rec["size"], "pure": enc(rec["pure"]),
+                        "final": enc(rec["final"]), "I": int(row[2]), "U": int(row[3]), "I_final": int(row[4]),
+                        "U_final": int(row[5])})
+    return P.save(records, directory, rank)
 
 
 def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
@@ -684,6 +744,13 @@ def main(args):
                          "configs[0]) is covered by the oracle tests: python -m pytest tests -m 'not gpu'")
     rank, local_rank, world = D.env_rank()
     dev = torch.device("cuda", local_rank % torch.cuda.device_count())
+    if getattr(args, "ensemble_masks", None) or getattr(args, "ensemble_out", "") or getattr(args, "ensemble_weights", None):
+        check_ensemble_flags(args)      # before any model exists, like the two branches below
+        check_device_targets(args)
+        if world > 1:
+            raise SystemExit("--ensemble_masks runs on one rank: start it without a launcher (world size 1)")
+        torch.cuda.set_device(dev)
+        return ensemble_masks_main(args, dev)
     check_device_targets(args)
     if getattr(args, "score_masks", ""):      # before any model exists: files and ground truth only
         if world > 1:

@@ -681,6 +681,107 @@ def rle_from_polygons(entries, sizes, counts, rule="once", slot_words=None, devi
     return slots, table, status
 
 
+def rle_merge_rule(name, k):
+    """(lo, hi) of a named vote over k members: a pixel is set iff lo <= (members that cover it) <= hi.  "union" (1, k),
+    "intersect" (k, k), "majority" (k // 2 + 1, k), "at_least:T" (T, max(T, k)), "exactly:T" (T, T) with T >= 0.  ValueError on
+    anything else.  Pure Python."""
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"rle_merge_rule: {k} members")
+    if name == "union":
+        return 1, max(k, 1)
+    if name == "intersect":
+        return k, k
+    if name == "majority":
+        return k // 2 + 1, max(k, k // 2 + 1)
+    if isinstance(name, str) and ":" in name:
+        kind, _, arg = name.partition(":")
+        if kind in ("at_least", "exactly") and arg.isdigit():
+            t = int(arg)
+            return (t, max(t, k)) if kind == "at_least" else (t, t)
+    raise ValueError(f"rle_merge_rule: rule {name!r} (union, intersect, majority, at_least:T, exactly:T)")
+
+
+def rle_merge_layout(sizes, counts_src, counts_out):
+    """images [G,4] int64 = (H, W, first source entry, first output entry) of a merge over G images: image g owns
+    counts_src[g] consecutive source entries and counts_out[g] consecutive output entries of sizes[g] = (H, W)"""
+    import numpy as np
+    if not (len(sizes) == len(counts_src) == len(counts_out)):
+        raise ValueError(f"rle_merge_layout: {len(sizes)} sizes, {len(counts_src)} and {len(counts_out)} counts")
+    images = np.zeros((len(sizes), 4), dtype=np.int64)
+    es = eo = 0
+    for g, ((H, W), ns, no) in enumerate(zip(sizes, counts_src, counts_out)):
+        if int(ns) < 0 or int(no) < 0:
+            raise ValueError(f"rle_merge_layout: image {g} has {ns} and {no} entries")
+        images[g] = (int(H), int(W), es, eo)
+        es += int(ns)
+        eo += int(no)
+    return images
+
+
+def rle_merge(slots, table, sizes, counts_src, members, member_offsets, bounds, counts_out, slot_words=None, out=None):
+    """New masks out of encoded masks, by vote (hgl_rle_merge_device on the current stream, no synchronisation): the source
+    entries (slots / table: what rle_encode or rle_pack returns) belong to G = len(sizes) <= 64 images, counts_src[g]
+    consecutive entries of sizes[g] = (H, W); image g owns counts_out[g] consecutive output entries.  Output entry s merges the
+    source entries members[member_offsets[s] : member_offsets[s+1]] (absolute indices, all of its own image; one listed twice
+    counts twice) and a pixel of it is set iff bounds[s] = (lo, hi) holds for the number of members that cover it
+    (rle_merge_rule names the usual ones).  members: a list of per-entry lists (member_offsets is then None) or a flat int32
+    sequence / device tensor with member_offsets [S+1]; bounds: [S,2].  slot_words: int32 words per output entry (default the
+    largest ceil(H*W/32) of the call: nothing is ever lost).  Returns (slots [S, slot_words] int32, table [S,4] int32 as
+    rle_encode writes them, status [S,4] int32 = code, k, 0, 0; code 0 = merged, 1 = merged with a clipped member, 2 = refused):
+    three views of one flat buffer, table, slots, status in this order (`out`: a contiguous int32 device tensor of
+    S * (8 + slot_words) elements to use for it).  No mask becomes pixels."""
+    import numpy as np
+    lib = _lib.load()
+    sp, sw, tp, Ssrc = _rle_set(slots, table, "rle_merge")
+    dev = slots.device
+    images = rle_merge_layout(sizes, counts_src, counts_out)
+    G = len(images)
+    if int(sum(int(n) for n in counts_src)) != Ssrc:
+        raise ValueError(f"rle_merge: counts_src sum to {sum(counts_src)}, the set has {Ssrc} entries")
+    S = int(sum(int(n) for n in counts_out))
+    if member_offsets is None:
+        lists = [np.asarray(m, dtype=np.int64).reshape(-1) for m in members]
+        member_offsets = np.concatenate([[0], np.cumsum([len(m) for m in lists], dtype=np.int64)])
+        members = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
+
+    def i32(x, shape, name):
+        if not torch.is_tensor(x):
+            a = np.asarray(x, dtype=np.int64).reshape(shape)
+            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError(f"rle_merge: {name} does not fit int32")
+            x = torch.from_numpy(a.astype(np.int32))
+        x = x.to(device=dev, dtype=torch.int32).reshape(shape).contiguous()
+        return x
+
+    members = i32(members, (-1,), "members")
+    member_offsets = i32(member_offsets, (-1,), "member_offsets")
+    bounds = i32(bounds, (-1, 2), "bounds")
+    M = int(members.numel())
+    if member_offsets.numel() != S + 1 or bounds.shape[0] != S:
+        raise ValueError(f"rle_merge: {S} output entries need {S + 1} member offsets and {S} bounds, got {member_offsets.numel()} "
+                         f"and {bounds.shape[0]}")
+    if slot_words is None:
+        slot_words = max([rle_slot_words(H, W) for H, W in sizes], default=1)
+    slot_words = int(slot_words)
+    if out is None:
+        out = torch.empty(S * (8 + slot_words), dtype=torch.int32, device=dev)
+    elif out.numel() != S * (8 + slot_words):
+        raise ValueError(f"out: expected {S * (8 + slot_words)} int32 elements, got {out.numel()}")
+    oslots, otable = rle_split(out, S, slot_words)
+    status = out[S * (4 + slot_words):].reshape(S, 4)
+    if S == 0:
+        return oslots, otable, status
+    need = lib.hgl_rle_merge_workspace_bytes(images.ctypes.data, G, Ssrc, sw, S, M)
+    ws = workspace(need, dev, "rle")
+    base = _dev(out, torch.int32, "out")
+    check(lib.hgl_rle_merge_device(sp if Ssrc else None, sw, tp if Ssrc else None, Ssrc, images.ctypes.data, G,
+                                   members.data_ptr() if M else None, M, member_offsets.data_ptr(), bounds.data_ptr(),
+                                   base + 16 * S, slot_words, base, S, status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "hgl_rle_merge_device")
+    return oslots, otable, status
+
+
 def score_sentence(hybrid, sentence_feat, noun_phrase_feat, other_noun_feats, boxes, gem_score,
                    logit_scale=100.0, r=0.5, k1=3, k2=6, alpha=0.6, relaword="none", has_other_nouns=False):
     """Per-sentence tail (Hybridgl_main.py:153-196,225-228).

@@ -5,6 +5,8 @@ strings' counts cross the bus, no mask is expanded to bytes).
     records = predictions.load("runA")                        # [{"index", "sentence", "size", "pure", "final", "I", ...}]
     report = predictions.compare("runA", "runB")              # or two loaded sets
     python -m hybridgl_amd.predictions compare runA runB [--json OUT]
+    voted = predictions.ensemble(["runA", "runB", "runC"], rule="majority")   # [{"index", "sentence", "size", "pure", "final"}]
+    python -m hybridgl_amd.main <dataset flags> --ensemble_masks runA runB runC --ensemble_out OUT   # voted, scored and saved
 
 Any producer that writes the same lines (the reference's own winners included) can be compared in the same way.
 """
@@ -167,6 +169,80 @@ def score(records, targets, batch=32):
         flush(H, W, q)
     rows = np.asarray(sorted(rows), dtype=np.int64).reshape(-1, 6)
     return rows, sorted(missing), sorted(set(recs) - seen)
+
+
+def ensemble(sets, rule="majority", weights=None, device=None, batch=64):
+    """Two or more saved runs voted into one prediction.  sets: loaded record lists or directories; every set must hold the same
+    (index, sentence) keys and state the same size for each -- an ensemble over different sentences is not a run (ValueError).
+    For every key the `pure` masks of all sets are voted into one mask and the `final` masks into another: rule is a name of
+    ops.rle_merge_rule ("majority", "union", "intersect", "at_least:T", "exactly:T") over k = sum(weights) votes; weights: one
+    non-negative integer per set (default 1 each), expressed by listing a set's mask that many times.  The strings' runs cross
+    the bus (ops.rle_pack), the vote happens on bit planes (ops.rle_merge: one call per `batch` <= 64 image sizes, every size an
+    image of the call) and runs come back: no mask becomes pixels, and the output slots hold ceil(H*W/32) words, so no mask is
+    ever lost.  Returns records {"index", "sentence", "size", "pure", "final"} (COCO strings) sorted by key; score() fills in
+    the counts that save() writes."""
+    from . import ops
+    from .sam import coco_encode_rle, rle_counts_from_string, rle_from_slot
+    sets = [_by_key(load(s) if isinstance(s, (str, os.PathLike)) else s) for s in sets]
+    if len(sets) < 2:
+        raise ValueError(f"ensemble: {len(sets)} set(s); a vote takes at least two")
+    weights = [1] * len(sets) if weights is None else list(weights)
+    if len(weights) != len(sets) or any(isinstance(w, bool) or not isinstance(w, int) or w < 0 for w in weights):
+        raise ValueError(f"ensemble: weights {weights!r} (one non-negative integer per set, {len(sets)} sets)")
+    if not 1 <= int(batch) <= 64:
+        raise ValueError(f"ensemble: batch {batch} (1 .. 64 image sizes per call)")
+    keys = sorted(sets[0])
+    for i, s in enumerate(sets[1:], 1):
+        if set(s) != set(keys):
+            odd = sorted(set(s) ^ set(keys))[0]
+            raise ValueError(f"ensemble: set {i} and set 0 do not hold the same keys (index {odd[0]} sentence {odd[1]} is in one only)")
+        for k in keys:
+            if s[k]["size"] != sets[0][k]["size"]:
+                raise ValueError(f"ensemble: index {k[0]} sentence {k[1]} has size {s[k]['size']} in set {i} and "
+                                 f"{sets[0][k]['size']} in set 0")
+    votes = int(sum(weights))
+    bounds = ops.rle_merge_rule(rule, votes)
+    by_size = {}
+    for k in keys:
+        by_size.setdefault(tuple(sets[0][k]["size"]), []).append(k)
+    sizes = sorted(by_size)
+    out = {}
+    for c in range(0, len(sizes), int(batch)):
+        chunk = sizes[c:c + int(batch)]
+        strings, members, order = [], [], []
+        for hw in chunk:
+            for k in by_size[hw]:
+                for m in MASKS:
+                    first = len(strings)
+                    strings += [s[k][m] for s in sets]
+                    members.append([first + i for i, w in enumerate(weights) for _ in range(w)])
+                    order.append((k, m, hw))
+        n_src = [len(by_size[hw]) * len(MASKS) * len(sets) for hw in chunk]
+        n_out = [len(by_size[hw]) * len(MASKS) for hw in chunk]
+        # one packed set for all sizes of the call: rle_pack's size only guards its own arguments, the table rows carry none
+        slots, table = ops.rle_pack([rle_counts_from_string(s) for s in strings], chunk[0][0], chunk[0][1], device=device)
+        res = ops.rle_merge(slots, table, chunk, n_src, members, None, [bounds] * len(members), n_out)
+        s_out, t_out, status = (x.cpu().numpy() for x in res)
+        for e, (k, m, (H, W)) in enumerate(order):
+            if status[e, 0] == 2:
+                raise ValueError(f"ensemble: a saved {m!r} mask of index {k[0]} sentence {k[1]} does not decode")
+            counts = rle_from_slot(s_out[e], int(t_out[e, 0]), int(t_out[e, 1]), H, W)
+            out.setdefault(k, {})[m] = coco_encode_rle({"size": [H, W], "counts": counts})["counts"]
+    return [{"index": k[0], "sentence": k[1], "size": list(sets[0][k]["size"]), **out[k]} for k in keys]
+
+
+def save(records, directory, rank=0):
+    """DIR/masks.rank{rank}.jsonl, one JSON line per record with the keys load() reads back (KEYS, in that order): what
+    main.py --save_masks writes for a run and --ensemble_out for a vote.  Returns the path."""
+    records = list(records)
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(os.fspath(directory), f"masks.rank{rank}.jsonl")
+    for i, rec in enumerate(records):
+        _check_record(rec, f"save: record {i}")
+    with open(path, "w") as f:
+        for rec in records:
+            f.write(json.dumps({k: rec[k] for k in KEYS}) + "\n")
+    return path
 
 
 def _jsonable(report):

@@ -1375,6 +1375,30 @@ def coco_encode_rle(uncompressed_rle):
     return {"size": [h, w], "counts": buf.raw[:n.value].decode("utf-8")}
 
 
+def merge_rles(rles, intersect=False, device=None):
+    """mask.merge of refer/external/mask.py (maskApi.c:49-70 rleMerge) for a list of RLE dicts of ONE size, on the device: the
+    runs cross the bus (ops.rle_pack), the union -- or, with intersect, the intersection -- is formed on bit planes
+    (ops.rle_merge) and comes back as runs; no mask becomes pixels.  The dicts carry their counts as lists / arrays or as COCO
+    strings; the result is an RLE dict in the form of the first.  Raises ValueError on an empty list, on sizes that differ and
+    on an entry that does not decode."""
+    if len(rles) == 0:
+        raise ValueError("merge_rles: no entries (the size of the result is the entries')")
+    h, w = (int(v) for v in rles[0]["size"])
+    for i, r in enumerate(rles):
+        if [int(v) for v in r["size"]] != [h, w]:
+            raise ValueError(f"merge_rles: entry {i} has size {list(r['size'])}, entry 0 has {[h, w]}")
+    n = len(rles)
+    slots, table = ops.rle_pack([rle_counts(r) for r in rles], h, w, device=device)
+    out = ops.rle_merge(slots, table, [(h, w)], [n], [list(range(n))], None, [ops.rle_merge_rule("intersect" if intersect else "union", n)],
+                        [1])
+    s, t, st = (x.cpu().numpy() for x in out)
+    if st[0, 0] == 2:
+        raise ValueError("merge_rles: an entry holds no mask")
+    counts = rle_from_slot(s[0], int(t[0, 0]), int(t[0, 1]), h, w)
+    merged = {"size": [h, w], "counts": counts}
+    return coco_encode_rle(merged) if isinstance(rles[0]["counts"], (str, bytes, bytearray)) else merged
+
+
 def remove_small_regions(masks, area_thresh, mode, out=None):
     """utils/amg.py:267-291 for a batch [n,H,W] uint8 on the device -> (new masks, changed [n] uint8).
     out: (masks, changed) to write into (contiguous slices of a group's tensors) instead of fresh ones."""

@@ -818,6 +818,43 @@ int hgl_rle_from_polygons_device(const double* xy, const int32_t* point_offsets,
                                  const int64_t* images_host, int G, int rule,
                                  uint32_t* slots, long long slot_words, int32_t* table, int32_t* status,
                                  void* ws, size_t ws_bytes, void* stream);
+/* New masks out of masks that are already encoded (csrc/rle.hip): the device form of rleMerge(R, M, n, intersect)
+ * (refer/external/maskApi.c:49-70, mask.merge of refer/external/mask.py) generalised to a vote -- every output entry is a rule
+ * over the per-pixel count of its members.  No mask becomes pixels.  Asynchronous on `stream`; no host synchronisation,
+ * allocation or atomics; two calls give the same bytes; at most three launches whatever G, S, M and the sizes are, none for S = 0.
+ * Source set = (slots_src, slot_words_src, table_src, Ssrc): what hgl_rle_encode_device hands out, forms 0 and 1, with the
+ * code 0 / 1 / 2 rules of hgl_rle_decode_device.  Ssrc may be 0 (the set's pointers are then not read).
+ * images_host: HOST [G,4] int64, G <= 64, row g = (H_g, W_g, first source entry, first output entry); both entry columns run
+ * from 0 to Ssrc / S and do not decrease, an image may own none on either side; H*W < 2^31.  The array is read before the call
+ * returns.  Anything else is HGL_EINVAL and nothing is enqueued.
+ * members: device [M] int32, absolute source indices (not read when M = 0).  member_offsets: device [S+1] int32; output entry s
+ * merges the source entries members[member_offsets[s] .. member_offsets[s+1]-1], k_s of them; a source listed twice counts
+ * twice (integer weights).  bounds: device [S,2] int32 = (lo_s, hi_s): a pixel of output s is set iff
+ * lo_s <= (number of its members that cover the pixel) <= hi_s.
+ *   union         (1, k)          rleMerge(.., 0)
+ *   intersection  (k, k)          rleMerge(.., 1)
+ *   majority      (k/2 + 1, k)
+ *   exactly one   (1, 1)          the REFER target rule of hgl_rle_from_polygons_device
+ * (0, 0) gives the complement of the union; k = 0 follows from the formula: all pixels when lo = 0, none otherwise.
+ * slots [S, slot_words] / table [S,4]: what hgl_rle_encode_device would write for the merged mask against the entry's own
+ * H_g x W_g -- form 0 (the counts) whenever n_counts <= slot_words, form 1 (the column-major bit plane) when they do not fit but
+ * ceil(H*W/32) words do, form 2 otherwise; table = (true n_counts, form, area, 0); words beyond what the form defines are
+ * not written.
+ * status: device [S,4] int32 = (code, k_s, 0, 0).  code 0: merged.  code 1: merged, and at least one member had the decoder's
+ * code 1; such a member is used as the decoder decodes it.  code 2: refused -- a member index outside the source entries of the
+ * entry's own image, a member of code 2, offsets that step back or leave [0, M] (k_s is then reported as 0), lo < 0 or lo > hi,
+ * k_s > 65535; the table row is (0, 3, 0, 0) and the slot is untouched.
+ * Limits: M, S, Ssrc < 2^31; the source plane words, sum of n_g * W_g * ceil(H_g / 64), < 2^32, and the merged plane words
+ * likewise; fewer than 2^31 blocks.  The outputs must not alias the sources.
+ * ws: hgl_rle_merge_workspace_bytes for the same geometry (HGL_EWORKSPACE when smaller): the source set's run starts, status
+ * and bit planes, and one bit plane per output entry (the merged plane is written once and read by both sweeps of the run
+ * writer).  The query returns 0 for a geometry the call refuses and for S = 0, which needs no workspace and takes ws = NULL. */
+size_t hgl_rle_merge_workspace_bytes(const int64_t* images_host, int G, int Ssrc, long long slot_words_src, int S, int M);
+int hgl_rle_merge_device(const uint32_t* slots_src, long long slot_words_src, const int32_t* table_src, int Ssrc,
+                         const int64_t* images_host, int G, const int32_t* members, int M,
+                         const int32_t* member_offsets, const int32_t* bounds,
+                         uint32_t* slots, long long slot_words, int32_t* table, int S, int32_t* status,
+                         void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

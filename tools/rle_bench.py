@@ -31,10 +31,17 @@
              tree (hybridgl_amd.synth.write_refer_tree, as tools/evaluator_ranks.py) with a seeded proposal store; writes
              profiles/rle_polygons_bench.json as well
 
+  merge      (--merge, instead of the legs above) new masks out of encoded masks: ONE ops.rle_merge call against the pixel path
+             built from the existing entries (ops.rle_decode -> torch sum and compare -> ops.rle_encode), both from packed runs
+             to the encoder's slots, HIP events: the majority of 3 runs x 2 masks x 128 sentences of 640 x 640, and the union of
+             64 proposals per image for 16 images of 640 x 640; equality of the two paths is checked before any timing; writes
+             profiles/rle_merge_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
     python tools/rle_bench.py --decode [--reps 30]
     python tools/rle_bench.py --match [--reps 30]
     python tools/rle_bench.py --polygons [--reps 30] [--cli_images 100]
+    python tools/rle_bench.py --merge [--reps 30]
 """
 import argparse
 import json
@@ -257,6 +264,65 @@ def match_leg(dev, reps, H=640, W=640):
     return rec
 
 
+def device_spread(fn, reps, warm=5):
+    """median, fastest and slowest of `reps` HIP-event timings in microseconds, after `warm` calls"""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) * 1e3)
+    return {"median_us": round(statistics.median(out), 1), "min_us": round(min(out), 1), "max_us": round(max(out), 1)}
+
+
+def merge_leg(dev, reps, H=640, W=640):
+    """sources are runs as saved predictions and stores hold them: packed counts (ops.rle_pack), form 0"""
+    reps = max(reps, 20)
+    base = torch.from_numpy(blobs(64, H, W, 4100)).to(dev)
+    runs = [r["counts"] for r in hsam.masks_to_rle(base)]
+    sw = ops.rle_slot_words(H, W)
+    rec = {"H": H, "W": W, "reps": reps, "merged_plane": "materialised once in the workspace"}
+    shapes = {
+        # 128 sentences x (pure, final), three runs each: output e votes sources 3e .. 3e+2 (neighbouring blobs: runs that mostly agree)
+        "majority_3_runs_2_masks_128_sentences": (256, 3, "majority", lambda e, i: (e + 7 * i) % 64),
+        # 16 images, the union of each one's 64 proposals
+        "union_64_proposals_16_images": (16, 64, "union", lambda e, i: (5 * e + i) % 64),
+    }
+    for name, (S, k, rule, pick) in shapes.items():
+        slots, table = ops.rle_pack([runs[pick(e, i)] for e in range(S) for i in range(k)], H, W, device=dev)
+        members = torch.arange(S * k, dtype=torch.int32, device=dev)
+        offsets = torch.arange(0, S * k + 1, k, dtype=torch.int32, device=dev)
+        lo, hi = ops.rle_merge_rule(rule, k)
+        bounds = torch.tensor([[lo, hi]] * S, dtype=torch.int32, device=dev)
+        out_m = torch.empty(S * (8 + sw), dtype=torch.int32, device=dev)
+        out_p = torch.empty(S * (4 + sw), dtype=torch.int32, device=dev)
+        pix = torch.empty(S * k * H * W, dtype=torch.uint8, device=dev)
+
+        def entry():
+            return ops.rle_merge(slots, table, [(H, W)], [S * k], members, offsets, bounds, [S], slot_words=sw, out=out_m)
+
+        def pixels():
+            dec, _ = ops.rle_decode(slots, table, H, W, out=pix)
+            count = dec.view(S, k, H, W).sum(dim=1, dtype=torch.int32)
+            return ops.rle_encode(((count >= lo) & (count <= hi)).to(torch.uint8), slot_words=sw, out=out_p)
+
+        ms, mt, st = entry()
+        ps, pt = pixels()
+        n = int(pt[:, 0].max())
+        assert int(st[:, 0].abs().sum()) == 0 and torch.equal(mt, pt) and int(pt[:, 1].abs().sum()) == 0 and torch.equal(ms[:, :n], ps[:, :n]), \
+            "the entry and the pixel path disagree"
+        a, b = device_spread(entry, reps), device_spread(pixels, reps)
+        rec[name] = {"sources": S * k, "outputs": S, "members_per_output": k, "rule": rule, "source_slot_words": int(slots.shape[1]),
+                     "counts_per_output_max": n, "rle_merge": a, "decode_vote_encode": b,
+                     "pixel_path_over_entry": round(b["median_us"] / a["median_us"], 2)}
+    return rec
+
+
 def polygons_leg(dev, reps, cli_images):
     import shutil
     import subprocess
@@ -356,6 +422,8 @@ def main():
                     help="measure rle_from_polygons against the host codec + upload + encode; writes profiles/rle_polygons_bench.json")
     ap.add_argument("--cli_images", type=int, default=100, help="--polygons: images of the on-disk tree of the CLI leg")
     ap.add_argument("--match", action="store_true", help="measure rle_match against the pair list; writes profiles/rle_match_bench.json")
+    ap.add_argument("--merge", action="store_true",
+                    help="measure rle_merge against decode -> vote -> encode; writes profiles/rle_merge_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
@@ -366,6 +434,14 @@ def main():
     if args.polygons:
         out = {"polygons": polygons_leg(dev, args.reps, args.cli_images), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_polygons_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
+    if args.merge:
+        out = {"merge": merge_leg(dev, args.reps), "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_merge_bench.json")
         with open(path, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
