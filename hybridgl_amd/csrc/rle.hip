@@ -26,8 +26,9 @@
 // plane (bit p % 32 of word p / 32; whenever the counts do not fit but ceil(H*W/32) words do), 2 = neither fits, nothing
 // written, 3 = the index is outside [0, N), nothing read or written.  Words beyond what the form defines keep their bytes.
 #include "hgl_common.h"
-#include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan, rle_match_plan, rle_merge_plan: plain C++, shared with the sanitizer harnesses
+#include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan, rle_match_plan, rle_merge_plan, rle_nms_plan: plain C++, shared with the sanitizer harnesses
 #include "rle_scan.h"       // RLE_THREADS, rle_block_sum, rle_group_find, rle_counts_chunk: shared with rle_poly.hip
+#include "nms_walk.h"       // nms_before, nms_resolve_block, nms_emit_block: shared with sam_nms.hip
 
 namespace {
 
@@ -662,6 +663,7 @@ RleMergeWs rle_merge_ws(const RleMergePlan& plan, int Ssrc, long long sw) {
 //      union of its B boxes) are not walked: one side is all zeros there.
 //      A call of few tiles (64 x 64 masks are 2) splits every tile's word range over `splits` workgroups, each with a plane of
 //      partial counts of its own in the workspace: no atomics, and the sum below does not depend on who finished first.
+//      `upper`: both sides are the same set and only the pairs a < b are wanted (G below): a tile that holds none returns at once.
 //   F. rle_match_best_kernel   one wave per entry of either set walks its row / column of the image's matrix, sums the partial
 //      counts, and keeps the partner with the largest I / D, ratios compared exactly (I1*D2 > I2*D1 in 64 bits), the lowest
 //      index on a tie.  The waves of set A write the caller's matrix on the way, every element once.
@@ -681,7 +683,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_match_tile_kernel(const unsig
                                                                      const int32_t* __restrict__ sa, const int32_t* __restrict__ sb,
                                                                      const int32_t* __restrict__ boxa, const int32_t* __restrict__ boxb,
                                                                      const RleMatch geo, int splits, long long pairs,
-                                                                     int32_t* __restrict__ partial) {
+                                                                     int upper, int32_t* __restrict__ partial) {
   constexpr int TA = RLE_MATCH_TA, TB = RLE_MATCH_TB, CH = RLE_MATCH_CHUNK, PER = TA / 4;      // PER A rows per wave
   __shared__ alignas(16) unsigned long long As[TA][CH];
   __shared__ alignas(16) unsigned long long Bs[TB][CH + 2];      // + 2: rows stay 16-byte aligned and start 4 banks apart
@@ -693,6 +695,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_match_tile_kernel(const unsig
   const int na = geo.first_a[g + 1] - fa, nb = geo.first_b[g + 1] - fb;
   const unsigned tiles_b = ((unsigned)nb + TB - 1) / TB, local = tile - geo.tile0[g];
   const int a0 = (int)(local / tiles_b) * TA, b0 = (int)(local % tiles_b) * TB;
+  if (upper && a0 >= b0 + TB) return;      // a set against itself (the mask NMS): no pair a < b in this tile, its counts are never read
   const int HW64 = (geo.H[g] + 63) / 64;
   const unsigned Q = (unsigned)geo.W[g] * (unsigned)HW64;
   // the columns that hold a pixel of one of the tile's A masks and of one of its B masks
@@ -834,6 +837,147 @@ __global__ __launch_bounds__(64) void rle_match_best_kernel(const int32_t* __res
   if (lane == 0) { out[0] = code; out[1] = area; out[2] = best.idx; out[3] = (int32_t)best.I; }
 }
 
+// ---- greedy suppression by mask overlap inside one set, image by image (hgl_rle_nms_device): rleNms of maskApi.c:98-107 on the
+// planes, with the box NMS's order (nms_walk.h).  The set goes through A, B, D and E once (pa == pb, the tiles above the
+// diagonal), then:
+//
+//   G. rle_nms_rank_kernel    one thread per entry counts the entries of its image that come before it (nms_before; without
+//      scores every score is equal and the index decides: the given order).  An entry of code 2 takes a place behind every
+//      entry that holds a mask, so order[] is a permutation of the image's list and nothing downstream reads an unwritten index.
+//   H. rle_nms_words_kernel   one wave per suppression word: lane j decides column rank 64 w + j against row rank q from the
+//      summed partial counts and the two areas, in double; the word is the wave's ballot.  Words left of a row's diagonal block
+//      are neither written nor read.
+//   I. rle_nms_walk_kernel    one workgroup per image walks the 64-row blocks: wave 0 resolves the diagonal block
+//      (nms_resolve_block, nms_emit_block), then every later word of removed[] takes the OR of the block's kept rows, one wave per
+//      word with a lane per kept row; the column's first suppressor is the lowest lane whose word names it.
+struct RleNmsEntry {
+  int g, f, n;      // image, its first entry, its entries
+};
+__device__ __forceinline__ RleNmsEntry rle_nms_image(const RleNms& geo, int g) { return {g, geo.first[g], geo.first[g + 1] - geo.first[g]}; }
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_nms_rank_kernel(const int32_t* __restrict__ status, const float* __restrict__ scores,
+                                                                   const RleNms geo, int32_t* __restrict__ order,
+                                                                   int32_t* __restrict__ result) {
+  const int s = blockIdx.x * RLE_THREADS + threadIdx.x;
+  if (s >= geo.first[geo.G]) return;
+  const RleNmsEntry im = rle_nms_image(geo, rle_group_find(geo.first, geo.G, s));
+  const int i = s - im.f;
+  const int code = status[(size_t)s * 4], area = status[(size_t)s * 4 + 1];
+  const float si = scores ? scores[s] : 0.f;
+  int before = 0, valid = 0, dead_lower = 0;
+  for (int j = 0; j < im.n; ++j) {
+    const bool ok = status[(size_t)(im.f + j) * 4] != 2;
+    const float sj = scores ? scores[im.f + j] : 0.f;
+    valid += ok ? 1 : 0;
+    before += (ok && nms_before(sj, j, si, i)) ? 1 : 0;
+    dead_lower += (!ok && j < i) ? 1 : 0;
+  }
+  order[im.f + (code != 2 ? before : valid + dead_lower)] = i;
+  int32_t* row = result + (size_t)s * 4;
+  row[0] = code; row[1] = area; row[2] = code != 2 ? before : -1; row[3] = -1;
+}
+
+// does the pair of I common pixels and these areas (both > 0) exceed thr?  metric 0: I / union, 1: I / the smaller area
+__device__ __forceinline__ bool rle_nms_exceeds(long long I, long long area_a, long long area_b, double thr, int metric) {
+  const long long D = metric == 0 ? area_a + area_b - I : (area_a < area_b ? area_a : area_b);
+  const double ratio = I == 0 ? 0.0 : (double)I / (double)D;
+  return ratio > thr;
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_nms_words_kernel(const int32_t* __restrict__ status, const int32_t* __restrict__ order,
+                                                                    const int32_t* __restrict__ partial, const RleNms geo, int splits,
+                                                                    long long pairs, long long sup_words, double thr, int metric,
+                                                                    unsigned long long* __restrict__ sup) {
+  const int lane = threadIdx.x & 63;
+  const long long u = (long long)blockIdx.x * (RLE_THREADS / 64) + (threadIdx.x >> 6);
+  if (u >= sup_words) return;      // uniform over the wave, as everything up to the ballot
+  const RleNmsEntry im = rle_nms_image(geo, rle_group_find(geo.sup0, geo.G, u));
+  const int nw = (im.n + 63) >> 6;
+  const long long local = u - geo.sup0[im.g];
+  const int q = (int)(local / nw), w = (int)(local % nw);
+  if (w < (q >> 6)) return;
+  const int a = order[im.f + q];
+  const int32_t* sa = status + (size_t)(im.f + a) * 4;
+  const bool row_ok = sa[0] != 2 && sa[1] > 0;
+  const int c = 64 * w + lane;
+  bool bit = false;
+  if (row_ok && c > q && c < im.n) {
+    const int b = order[im.f + c];
+    const int32_t* sb = status + (size_t)(im.f + b) * 4;
+    if (sb[0] != 2 && sb[1] > 0) {
+      const int lo = a < b ? a : b, hi = a < b ? b : a;      // the tile kernel counted the pairs lo < hi
+      const int32_t* P = partial + geo.pair0[im.g] + (size_t)lo * im.n + hi;
+      long long I = 0;
+      for (int z = 0; z < splits; ++z) I += P[(size_t)z * (size_t)pairs];
+      bit = rle_nms_exceeds(I, sa[1], sb[1], thr, metric);
+    }
+  }
+  const unsigned long long word = __ballot(bit);
+  if (lane == 0) sup[u] = word;
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_nms_walk_kernel(const int32_t* __restrict__ status, const int32_t* __restrict__ order,
+                                                                   const unsigned long long* __restrict__ sup, const RleNms geo,
+                                                                   int32_t* __restrict__ out_idx, int32_t* __restrict__ out_n,
+                                                                   int32_t* __restrict__ result) {
+  __shared__ int by_rank[RLE_NMS_MAX];                       // the rank of the column's first suppressor, -1: none
+  __shared__ unsigned long long removed[RLE_NMS_MAX / 64];
+  __shared__ unsigned long long kept_word;
+  __shared__ int nkept_s;
+  __shared__ int red[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const RleNmsEntry im = rle_nms_image(geo, (int)blockIdx.x);
+  if (im.n == 0) {      // uniform over the workgroup
+    if (t == 0) out_n[im.g] = 0;
+    return;
+  }
+  // the entries that hold a mask take the ranks 0 .. nv-1
+  int mine = 0;
+  for (int j = t; j < im.n; j += RLE_THREADS) mine += status[(size_t)(im.f + j) * 4] != 2 ? 1 : 0;
+  const int nv = rle_block_sum(mine, red);
+  const int nw = (im.n + 63) >> 6, nblk = (nv + 63) >> 6;
+  for (int c = t; c < im.n; c += RLE_THREADS) by_rank[c] = -1;
+  if (t < nw) removed[t] = 0;
+  if (t == 0) nkept_s = 0;
+  __syncthreads();
+  const int* ord = order + im.f;
+  const unsigned long long* words = sup + geo.sup0[im.g];
+  for (int rb = 0; rb < nblk; ++rb) {
+    if (wave == 0) {
+      const int a = rb * 64 + lane;
+      const unsigned long long d = a < nv ? words[(size_t)a * nw + rb] : 0ull, rem = removed[rb];
+      const unsigned long long km = nms_resolve_block(d, rem, rb, nv);
+      nms_emit_block(km, rb, lane, ord, out_idx + im.f, nkept_s, kept_word);
+      // a column of this block that falls here: the first kept row whose diagonal word names it
+      int first = -1;
+      for (int s2 = 0; s2 < 64; ++s2) {
+        const unsigned lo = __shfl((unsigned)(d & 0xffffffffull), s2), hi = __shfl((unsigned)(d >> 32), s2);
+        const unsigned long long row = ((unsigned long long)hi << 32) | lo;
+        if (first < 0 && ((km >> s2) & 1ull) && ((row >> lane) & 1ull)) first = rb * 64 + s2;
+      }
+      if (a < nv && !((rem >> lane) & 1ull) && first >= 0) by_rank[a] = first;
+    }
+    __syncthreads();
+    const unsigned long long km = kept_word;
+    for (int w = rb + 1 + wave; w < nblk; w += RLE_THREADS / 64) {      // uniform over the wave
+      const unsigned long long v = ((km >> lane) & 1ull) ? words[(size_t)(rb * 64 + lane) * nw + w] : 0ull;
+      unsigned long long who = 0;      // lane j: the kept rows of the block that name column 64 w + j
+      for (int j = 0; j < 64; ++j) {
+        const unsigned long long b = __ballot((v >> j) & 1ull);
+        if (lane == j) who = b;
+      }
+      const unsigned long long old = removed[w];
+      if (who && !((old >> lane) & 1ull)) by_rank[64 * w + lane] = rb * 64 + (__ffsll((long long)who) - 1);
+      const unsigned long long fresh = __ballot(who != 0);
+      if (lane == 0) removed[w] = old | fresh;
+    }
+    __syncthreads();
+  }
+  for (int c = t; c < nv; c += RLE_THREADS)
+    if (by_rank[c] >= 0) result[(size_t)(im.f + ord[c]) * 4 + 3] = ord[by_rank[c]];
+  if (t == 0) out_n[im.g] = nkept_s;
+}
+
 // run starts of one set: [S] arrays of slot_words + 1 words
 size_t rle_starts_bytes(int S, long long slot_words) { return hgl_align_up((size_t)S * (size_t)(slot_words + 1) * sizeof(uint32_t), 256); }
 size_t rle_planes_bytes(int S, int H, int W) {
@@ -862,6 +1006,31 @@ RleMatchWs rle_match_ws(const RleMatchPlan& plan, int Sa, long long swa, int Sb,
   }
   w.partial = p;
   p += hgl_align_up((size_t)plan.splits * (size_t)plan.pairs * sizeof(int32_t), 256);
+  w.total = p;
+  return w;
+}
+
+// the workspace of a mask NMS: run starts, status, boxes and planes of the one set; the planes of partial counts; order; words
+struct RleNmsWs {
+  size_t E, status, boxes, plane, partial, order, sup, total;
+};
+RleNmsWs rle_nms_ws(const RleNmsPlan& plan, int S, long long sw) {
+  RleNmsWs w;
+  size_t p = 0;
+  w.E = p;
+  p += rle_starts_bytes(S, sw);
+  w.status = p;
+  p += rle_status_bytes(S);
+  w.boxes = p;
+  p += rle_status_bytes(S);
+  w.plane = p;
+  p += hgl_align_up((size_t)plan.mp.words_a * sizeof(unsigned long long), 256);
+  w.partial = p;
+  p += hgl_align_up((size_t)plan.mp.splits * (size_t)plan.mp.pairs * sizeof(int32_t), 256);
+  w.order = p;
+  p += hgl_align_up((size_t)S * sizeof(int32_t), 256);
+  w.sup = p;
+  p += hgl_align_up((size_t)plan.sup_words * sizeof(unsigned long long), 256);
   w.total = p;
   return w;
 }
@@ -1081,12 +1250,73 @@ int hgl_rle_match_device(const uint32_t* slots_a, long long slot_words_a, const 
     hipLaunchKernelGGL(rle_match_tile_kernel, dim3((unsigned)(plan.tiles * plan.splits)), dim3(RLE_THREADS), 0, st,
                        (const unsigned long long*)plane[0], (const unsigned long long*)plane[1], (const int32_t*)status[0],
                        (const int32_t*)status[1], (const int32_t*)boxes[0], (const int32_t*)boxes[1], plan.m, plan.splits, plan.pairs,
-                       partial);
+                       0, partial);
   if (Sa + Sb > 0)
     hipLaunchKernelGGL(rle_match_best_kernel, dim3((unsigned)Sa + (unsigned)Sb), dim3(64), 0, st, (const int32_t*)status[0],
                        (const int32_t*)status[1], crowd_b, plan.m, plan.splits, plan.pairs, (const int32_t*)partial, inter, match_a,
                        match_b);
   return hgl_check_launch("rle_match_device");
+}
+
+size_t hgl_rle_nms_workspace_bytes(const int64_t* images_host, int G, int S, long long slot_words) {
+  if (!images_host || slot_words < 0 || S <= 0) return 0;
+  RleNmsPlan plan;
+  char why[200];
+  if (rle_nms_plan(images_host, G, S, &plan, why, sizeof(why)) != 0) return 0;
+  return rle_nms_ws(plan, S, slot_words).total;
+}
+
+int hgl_rle_nms_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S, const int64_t* images_host, int G,
+                       const float* scores, double thr, int metric, int32_t* out_idx, int32_t* out_n, int32_t* result, void* ws,
+                       size_t ws_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(images_host && S >= 0 && slot_words >= 0 && (S == 0 || (slots && table && out_idx && out_n && result)),
+              "rle_nms_device: bad arguments");
+  HGL_REQUIRE(thr == thr, "rle_nms_device: the threshold is NaN");
+  HGL_REQUIRE(metric == 0 || metric == 1, "rle_nms_device: metric %d (0 = IoU, 1 = containment)", metric);
+  RleNmsPlan plan;
+  char why[200];
+  if (rle_nms_plan(images_host, G, S, &plan, why, sizeof(why)) != 0) {
+    hgl_set_error("rle_nms_device: %s", why);
+    return HGL_EINVAL;
+  }
+  if (S == 0) return HGL_OK;      // nothing to rank: no launch, out_n is the caller's
+  const RleNmsWs w = rle_nms_ws(plan, S, slot_words);
+  if (!ws || ws_bytes < w.total) {
+    hgl_set_error("rle_nms_device: workspace too small");
+    return HGL_EWORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* base = (char*)ws;
+  uint32_t* E = (uint32_t*)(base + w.E);
+  int32_t* status = (int32_t*)(base + w.status);
+  int32_t* boxes = (int32_t*)(base + w.boxes);
+  unsigned long long* plane = (unsigned long long*)(base + w.plane);
+  int32_t* partial = (int32_t*)(base + w.partial);
+  int32_t* order = (int32_t*)(base + w.order);
+  unsigned long long* sup = (unsigned long long*)(base + w.sup);
+  const RleMatchPlan& mp = plan.mp;
+  RleGroup grp;      // what the starts kernel reads of it: the sizes and the first entries
+  memset(&grp, 0, sizeof(grp));
+  grp.G = G;
+  for (int g = 0; g < G; ++g) { grp.H[g] = mp.pa.H[g]; grp.W[g] = mp.pa.W[g]; grp.first[g] = mp.pa.first[g]; }
+  // six launches whatever G and the sizes are (S > 0: every one of them has a block)
+  hipLaunchKernelGGL((rle_starts_kernel<true, RleGroup>), dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots, slot_words, table, grp, E,
+                     slot_words + 1, status, boxes);
+  hipLaunchKernelGGL(rle_plane_kernel<RlePlaneGroup>, dim3((unsigned)mp.blocks_a), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
+                     (const uint32_t*)E, slot_words + 1, (const int32_t*)status, mp.pa, plane);
+  hipLaunchKernelGGL(rle_match_tile_kernel, dim3((unsigned)(mp.tiles * mp.splits)), dim3(RLE_THREADS), 0, st,
+                     (const unsigned long long*)plane, (const unsigned long long*)plane, (const int32_t*)status, (const int32_t*)status,
+                     (const int32_t*)boxes, (const int32_t*)boxes, mp.m, mp.splits, mp.pairs, 1, partial);
+  hipLaunchKernelGGL(rle_nms_rank_kernel, dim3((unsigned)((S + RLE_THREADS - 1) / RLE_THREADS)), dim3(RLE_THREADS), 0, st,
+                     (const int32_t*)status, scores, plan.n, order, result);
+  const long long waves = RLE_THREADS / 64;
+  hipLaunchKernelGGL(rle_nms_words_kernel, dim3((unsigned)((plan.sup_words + waves - 1) / waves)), dim3(RLE_THREADS), 0, st,
+                     (const int32_t*)status, (const int32_t*)order, (const int32_t*)partial, plan.n, mp.splits, mp.pairs, plan.sup_words,
+                     thr, metric, sup);
+  hipLaunchKernelGGL(rle_nms_walk_kernel, dim3((unsigned)G), dim3(RLE_THREADS), 0, st, (const int32_t*)status, (const int32_t*)order,
+                     (const unsigned long long*)sup, plan.n, out_idx, out_n, result);
+  return hgl_check_launch("rle_nms_device");
 }
 
 size_t hgl_rle_merge_workspace_bytes(const int64_t* images_host, int G, int Ssrc, long long slot_words_src, int S, int M) {

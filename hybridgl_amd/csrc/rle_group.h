@@ -1,8 +1,8 @@
 // The geometry of the RLE entries (csrc/rle.hip): the tiling of an image, shared by the encoder and the decoder, and what the host
 // works out of a decode call's image rows (rle_group_plan), of a match call's (rle_match_plan) and of a merge call's
-// (rle_merge_plan) and hands to the kernels by value, and likewise of a polygon call's (rle_poly_plan, csrc/rle_poly.hip).  Plain
-// C++ without a HIP construct: the .hip files include it, and so do the sanitizer harnesses
-// tests/native/rle_group_sanitize.cpp, tests/native/rle_match_sanitize.cpp and tests/native/rle_merge_sanitize.cpp.
+// (rle_merge_plan) and of a mask NMS call's (rle_nms_plan) and hands to the kernels by value, and likewise of a polygon call's
+// (rle_poly_plan, csrc/rle_poly.hip).  Plain C++ without a HIP construct: the .hip files include it, and so do the sanitizer
+// harnesses tests/native/rle_group_sanitize.cpp, rle_match_sanitize.cpp, rle_merge_sanitize.cpp and rle_nms_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
 #include <stdint.h>
@@ -265,6 +265,65 @@ static inline int rle_merge_plan(const int64_t* images, int G, int Ssrc, int S, 
   m->first_out[G] = S;
   return 0;
 #undef RLE_MERGE_REQUIRE
+}
+
+// ---- hgl_rle_nms_device: greedy suppression by mask overlap of one set against itself, image by image.  The set goes through
+// the plane kernel once and the tile kernel of the match counts it against itself (an RleMatchPlan with both sides the same,
+// restricted to the tiles that hold a pair a < b); a row of an image's suppression words is ceil(n / 64) 64-bit words, one row
+// per rank.  An image owns at most RLE_NMS_MAX entries: its pair counts are n * n int32 per split.
+constexpr int RLE_NMS_MAX = 4096;
+
+struct RleNms {
+  long long pair0[RLE_GROUP_MAX];      // the image's first element in a plane of partial counts (RleMatch's)
+  long long sup0[RLE_GROUP_MAX];       // its first suppression word (non-decreasing, sup0[0] = 0)
+  int first[RLE_GROUP_MAX + 1];        // first entries; [G] = S
+  int G;
+};
+
+struct RleNmsPlan {
+  RleMatchPlan mp;           // the set against itself: m.first_a == m.first_b, pa == pb, tiles / splits / pairs of the full squares
+  RleNms n;
+  long long sup_words;       // 64-bit suppression words: sum of n_g * ceil(n_g / 64)
+};
+
+// images [G,3] = (H, W, first entry) -> *plan; 0, or -1 with the reason in why.  Checked: 1 <= G <= 64; S >= 0; H*W < 2^31; entries
+// from 0 to S without a step back; at most RLE_NMS_MAX entries per image; and what rle_match_plan checks of the set against
+// itself (fewer than 2^32 plane words, fewer than 2^31 blocks).
+static inline int rle_nms_plan(const int64_t* images, int G, int S, RleNmsPlan* plan, char* why, size_t why_cap) {
+#define RLE_NMS_REQUIRE(cond, ...)          \
+  do {                                      \
+    if (!(cond)) {                          \
+      snprintf(why, why_cap, __VA_ARGS__);  \
+      return -1;                            \
+    }                                       \
+  } while (0)
+  RLE_NMS_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
+  RLE_NMS_REQUIRE(S >= 0, "%d entries", S);
+  int64_t rows[5 * RLE_GROUP_MAX];      // the match's rows: both sides the same set, no matrix
+  for (int g = 0; g < G; ++g) {
+    const long long H = images[3 * g], W = images[3 * g + 1], e = images[3 * g + 2];
+    const long long e_next = g + 1 < G ? images[3 * (g + 1) + 2] : (long long)S;
+    RLE_NMS_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
+                    "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
+    RLE_NMS_REQUIRE(e >= 0 && e <= e_next && e_next <= (long long)S && (g > 0 || e == 0),
+                    "image %d: entries %lld .. %lld (rows must not decrease, from 0 to S = %d)", g, e, e_next, S);
+    RLE_NMS_REQUIRE(e_next - e <= RLE_NMS_MAX, "image %d owns %lld entries (at most %d)", g, e_next - e, RLE_NMS_MAX);
+    rows[5 * g] = H, rows[5 * g + 1] = W, rows[5 * g + 2] = rows[5 * g + 3] = e, rows[5 * g + 4] = 0;
+  }
+  if (rle_match_plan(rows, G, S, S, -1, &plan->mp, why, why_cap) != 0) return -1;      // S <= 64 * 4096: 2 S < 2^31
+  memset(&plan->n, 0, sizeof(plan->n));
+  plan->n.G = G;
+  plan->sup_words = 0;
+  for (int g = 0; g < G; ++g) {
+    const long long n = plan->mp.m.first_a[g + 1] - plan->mp.m.first_a[g];
+    plan->n.first[g] = plan->mp.m.first_a[g];
+    plan->n.pair0[g] = plan->mp.m.pair0[g];
+    plan->n.sup0[g] = plan->sup_words;
+    plan->sup_words += n * ((n + 63) / 64);      // <= 64 * 4096 * 64
+  }
+  plan->n.first[G] = S;
+  return 0;
+#undef RLE_NMS_REQUIRE
 }
 
 // ---- hgl_rle_from_polygons_device (csrc/rle_poly.hip): polygons -> RLE, one workgroup per entry.  A polygon's toggle plane --

@@ -4,21 +4,13 @@
 //   gather_masks                     the kept rows of a mask stack, by a device index list
 // Every decision of the greedy NMS is written once, as a __device__ function, and inlined into each kernel that takes it:
 // the ranking order (nms_before), the rank by counting (nms_rank), the IoU test (nms_overlap), the suppression word of a row
-// (nms_row_word) and the walk over the row blocks (nms_resolve_block, nms_emit_block, nms_or_kept_rows).
+// (nms_row_word) and the walk over the row blocks (nms_resolve_block, nms_emit_block, nms_or_kept_rows).  The order and the walk's
+// serial step live in nms_walk.h: the mask NMS on encoded sets (rle.hip) takes the same ones.
 #include "hgl_common.h"
+#include "nms_walk.h"       // nms_before, nms_resolve_block, nms_emit_block
 #include <math.h>
 
 namespace {
-
-// The ranking order of every NMS kernel below: descending score, the original index breaks ties, and a NaN score ranks ABOVE
-// every number (where torch.sort(descending=True) -- batched_nms's argsort, automatic_mask_generator.py:251-257 -- puts it).
-// A total order: ranks by counting never collide, order[] has no holes below the number of valid candidates.  (With a plain
-// `sj > sc || (sj == sc && j < i)` two NaN scores -- an f16x3 overflow with the thresholds open -- both got rank 0.)
-__device__ __forceinline__ bool nms_before(float sj, int j, float si, int i) {
-  const bool nj = sj != sj, ni = si != si;
-  if (nj || ni) return nj && (!ni || j < i);
-  return sj > si || (sj == si && j < i);
-}
 
 // rank by counting: how many of the K candidates are valid (keep[j] != 0) and come before candidate i of score si
 __device__ __forceinline__ int nms_rank(const float* scores, const unsigned char* keep, int K, float si, int i) {
@@ -48,30 +40,6 @@ __device__ __forceinline__ unsigned long long nms_row_word(int4 me, int q, const
   for (int j = 0; j < jn; ++j)
     if (c0 + j > q && nms_overlap(me, cols[j], thr)) word |= 1ull << j;
   return word;
-}
-
-// The walk's serial step, by one wave: lane l holds d, the diagonal word of row 64 rb + l (0 from row n on), and every lane
-// rem, the removed bits of the block so far.  Row by row, a row that is not removed is kept and removes what its word names.
-// -> the kept rows of the block
-__device__ __forceinline__ unsigned long long nms_resolve_block(unsigned long long d, unsigned long long rem, int rb, int n) {
-  unsigned long long km = 0;
-  for (int s2 = 0; s2 < 64; ++s2) {
-    const unsigned lo = __shfl((unsigned)(d & 0xffffffffull), s2), hi = __shfl((unsigned)(d >> 32), s2);
-    if (rb * 64 + s2 < n && !((rem >> s2) & 1ull)) {
-      km |= 1ull << s2;
-      rem |= ((unsigned long long)hi << 32) | lo;
-    }
-  }
-  return km;
-}
-
-// ... and its output, by the same wave: lane l appends candidate order[64 rb + l] if its row was kept; lane 0 hands the kept set
-// to the other waves and moves the count on.
-__device__ __forceinline__ void nms_emit_block(unsigned long long km, int rb, int lane, const int* order, int* out_idx,
-                                               int& nkept, unsigned long long& kept_word) {
-  const int base = nkept;
-  if ((km >> lane) & 1ull) out_idx[base + __popcll(km & ((1ull << lane) - 1ull))] = order[rb * 64 + lane];
-  if (lane == 0) { kept_word = km; nkept = base + __popcll(km); }
 }
 
 // The walk's parallel step for one later word of removed[]: acc | that word of every kept row of block rb.  word_of_row(r) is

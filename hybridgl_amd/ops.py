@@ -610,6 +610,65 @@ def rle_match(slots_a, table_a, slots_b, table_b, sizes, counts_a, counts_b, cro
     return inter, match_a, match_b
 
 
+NMS_METRIC = {"iou": 0, "containment": 1}
+
+
+def rle_nms_layout(sizes, counts):
+    """images [G,3] int64 = (H, W, first entry) of a mask NMS over G images: image g owns counts[g] consecutive entries of
+    sizes[g] = (H, W)"""
+    import numpy as np
+    if len(sizes) != len(counts):
+        raise ValueError(f"rle_nms_layout: {len(sizes)} sizes and {len(counts)} counts")
+    images = np.zeros((len(sizes), 3), dtype=np.int64)
+    e = 0
+    for g, ((H, W), n) in enumerate(zip(sizes, counts)):
+        if int(n) < 0:
+            raise ValueError(f"rle_nms_layout: image {g} has {n} entries")
+        images[g] = (int(H), int(W), e)
+        e += int(n)
+    return images
+
+
+def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou"):
+    """Greedy suppression by mask overlap inside one encoded set, image by image (hgl_rle_nms_device on the current stream, no
+    synchronisation): the S entries of slots / table (what rle_encode or rle_pack returns) belong to G = len(sizes) <= 64
+    images, counts[g] <= 4096 consecutive entries of sizes[g] = (H, W); an image may own none.  scores: float device tensor [S]
+    (the walk takes the box NMS's order: descending score, the index breaks ties, a NaN first) or None for the given order,
+    which is rleNms's.  An entry is kept iff no kept entry before it has ratio > thr with it; metric "iou": I / union,
+    "containment": I / the smaller area; an empty mask never suppresses and is never suppressed.
+    Returns (out_idx [S] int32: from image g's first entry on, its kept entries in walk order as indices into its list; out_n
+    [G] int32: how many; result [S,4] int32 = code, area, rank, by: the entry's position in the walk and the index of the kept
+    entry of lowest rank that suppressed it, -1 for a kept one and for code 2).  No mask becomes pixels."""
+    lib = _lib.load()
+    sp, sw, tp, S = _rle_set(slots, table, "rle_nms")
+    if metric not in NMS_METRIC:
+        raise ValueError(f"rle_nms: metric {metric!r} (one of {sorted(NMS_METRIC)})")
+    thr = float(thr)
+    if thr != thr:
+        raise ValueError("rle_nms: the threshold is NaN")
+    images = rle_nms_layout(sizes, counts)
+    G = len(images)
+    if int(sum(int(n) for n in counts)) != S:
+        raise ValueError(f"rle_nms: counts sum to {sum(counts)}, the set has {S} entries")
+    dev = slots.device
+    cp = None
+    if scores is not None:
+        if scores.numel() != S:
+            raise ValueError(f"scores: expected {S} values, got {scores.numel()}")
+        scores = scores.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+        cp = _dev(scores, torch.float32, "scores")
+    out = torch.empty(S * 5 + G, dtype=torch.int32, device=dev)      # one buffer: a caller that wants all three copies one tensor
+    out_idx, result, out_n = out[:S], out[S:5 * S].view(S, 4), out[5 * S:]
+    if S == 0:
+        out_n.zero_()
+        return out_idx, out_n, result
+    need = lib.hgl_rle_nms_workspace_bytes(images.ctypes.data, G, S, sw)
+    ws = workspace(need, dev, "rle")
+    check(lib.hgl_rle_nms_device(sp, sw, tp, S, images.ctypes.data, G, cp, thr, NMS_METRIC[metric], out_idx.data_ptr(),
+                                 out_n.data_ptr(), result.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "hgl_rle_nms_device")
+    return out_idx, out_n, result
+
+
 POLY_RULE = {"once": 0, "any": 1}
 
 

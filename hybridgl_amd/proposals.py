@@ -19,7 +19,10 @@ StoredProposals   answers the same three calls (and generate_device for HybridGL
 compare           two stores image by image, every mask of one against every mask of the other (ops.rle_match on the runs: no
                   mask becomes pixels): did SAM's set move, or only the scoring?
                       python -m hybridgl_amd.proposals compare DIR_A DIR_B [--iou LIST] [--json OUT]
-ceiling           the best proposal of a store per target -- the bound no scoring of these proposals exceeds -- without CLIP."""
+ceiling           the best proposal of a store per target -- the bound no scoring of these proposals exceeds -- without CLIP.
+thin              a store made smaller: per image the greedy suppression by MASK overlap (ops.rle_nms on the runs: no mask becomes
+                  pixels) that SAM's box NMS leaves undone; the result is a store like any other.
+                      python -m hybridgl_amd.proposals thin DIR_IN DIR_OUT --thr T [--metric iou|containment] [--score ...] [--json OUT]"""
 import collections
 import json
 import os
@@ -453,12 +456,9 @@ def _store(x):
     return x if isinstance(x, ProposalStore) else ProposalStore(x)
 
 
-def _image_runs(store, image_id, cap=None):
-    """(size (H, W) or None for an image without a record, the run lists of its first `cap` records)"""
+def _record_runs(store, image_id, recs):
+    """(size (H, W) or None for an empty list, the run lists of the records)"""
     from .sam import rle_counts_from_string
-    recs = store.records(image_id)
-    if cap:
-        recs = recs[:int(cap)]
     size, runs = None, []
     for k, r in enumerate(recs):
         hw = tuple(int(v) for v in r["segmentation"]["size"])
@@ -472,6 +472,14 @@ def _image_runs(store, image_id, cap=None):
         except Exception as e:
             raise ValueError(f"proposal store {store.directory}: image {image_id} entry {k}: bad counts string ({e})") from None
     return size, runs
+
+
+def _image_runs(store, image_id, cap=None):
+    """(size (H, W) or None for an image without a record, the run lists of its first `cap` records)"""
+    recs = store.records(image_id)
+    if cap:
+        recs = recs[:int(cap)]
+    return _record_runs(store, image_id, recs)
 
 
 def _pack(runs, device):
@@ -666,6 +674,62 @@ def ceiling(store, targets, cap=None, device=None, group=16):
     return np.asarray(sorted(rows), dtype=np.int64).reshape(-1, 5)
 
 
+THIN_SCORES = ("predicted_iou", "stability_score", "area", "stored")
+
+
+def thin(src, dst, thr, metric="iou", score="predicted_iou", group=16, device=None):
+    """A proposal store made smaller by mask NMS: for every image of `src` the records that ops.rle_nms keeps (`group` images
+    per call; the strings' runs cross the bus, no mask becomes pixels) are written to `dst`, unchanged and in their stored
+    order; an image without a proposal stays [].  An entry falls when a kept entry before it in the walk has ratio > thr with
+    it; metric "iou" or "containment" (I / the smaller area: a part nested in a whole, or the whole, whichever comes later).
+    score: the record field the walk is ordered by, descending, the stored index breaking ties -- "predicted_iou",
+    "stability_score" or "area" (compared as float32) -- or "stored": the stored order itself.  dst's meta is src's plus
+    {"thinned": {"thr", "metric", "score", "source"}}.  ValueError for dst == src, for a dst that already holds a store, for an
+    unknown score or metric and for a record that does not decode.  An image may hold at most 4096 records.
+    Returns {"per_image": {image_id: [before, after]}, "before": total, "after": total}."""
+    if metric not in ops.NMS_METRIC:
+        raise ValueError(f"thin: metric {metric!r} (one of {sorted(ops.NMS_METRIC)})")
+    if score not in THIN_SCORES:
+        raise ValueError(f"thin: score {score!r} (one of {list(THIN_SCORES)})")
+    thr = float(thr)
+    if thr != thr:
+        raise ValueError("thin: the threshold is NaN")
+    src, dst = _store(src), _store(dst)
+    if os.path.realpath(src.directory) == os.path.realpath(dst.directory):
+        raise ValueError(f"thin: the source and the destination are the same directory ({src.directory})")
+    if not os.path.isdir(src.directory):
+        raise ValueError(f"thin: {src.directory}: no such directory")
+    if os.path.isdir(dst.directory) and any(n.endswith(".json") for n in os.listdir(dst.directory)):
+        raise ValueError(f"thin: {dst.directory} already holds a store")
+    ids = src.image_ids()
+    per_image = {}
+    step = max(int(group), 1)
+    for c0 in range(0, len(ids), step):
+        chunk = [(iid, src.records(iid)) for iid in ids[c0:c0 + step]]
+        sized = [_record_runs(src, iid, recs) for iid, recs in chunk]
+        counts = [len(runs) for _, runs in sized]
+        kept = [[] for _ in chunk]
+        if sum(counts):
+            slots, table = _pack([r for _, runs in sized for r in runs], device)
+            scores = None
+            if score != "stored":
+                scores = torch.tensor([float(r[score]) for _, recs in chunk for r in recs], dtype=torch.float32).to(slots.device)
+            out_idx, out_n, result = ops.rle_nms(slots, table, [size or (1, 1) for size, _ in sized], counts, scores, thr, metric)
+            out_idx, out_n, result = (x.cpu().numpy().astype(np.int64) for x in (out_idx, out_n, result))
+            _check_decoded(src, [iid for iid, _ in chunk], counts, result)
+            e = 0
+            for k, n in enumerate(counts):
+                kept[k] = sorted(int(i) for i in out_idx[e:e + int(out_n[k])])
+                e += n
+        for (iid, recs), keep in zip(chunk, kept):
+            dst.write(iid, [recs[i] for i in keep])
+            per_image[iid] = [len(recs), len(keep)]
+    meta = dict(src.meta())
+    meta["thinned"] = {"thr": thr, "metric": metric, "score": score, "source": src.directory}
+    dst.write_meta(meta)
+    return {"per_image": per_image, "before": sum(v[0] for v in per_image.values()), "after": sum(v[1] for v in per_image.values())}
+
+
 def _jsonable(report):
     return {"summary": report["summary"], "per_image": [dict(v, image_id=k) for k, v in report["per_image"].items()]}
 
@@ -679,7 +743,25 @@ def main(argv=None):
     c.add_argument("dir_b")
     c.add_argument("--iou", default="0.5,0.75,0.9", metavar="LIST", help="the IoU thresholds of the report, comma-separated")
     c.add_argument("--json", default="", metavar="OUT", help="also write the summary and the per-image figures here")
+    t = sub.add_parser("thin", help="a store made smaller by mask NMS; evaluate the result with main.py --proposals_dir")
+    t.add_argument("dir_in")
+    t.add_argument("dir_out")
+    t.add_argument("--thr", type=float, required=True, help="an entry falls when a kept entry before it has ratio > THR with it")
+    t.add_argument("--metric", default="iou", choices=sorted(ops.NMS_METRIC))
+    t.add_argument("--score", default="predicted_iou", choices=list(THIN_SCORES), help="the order of the walk (stored: as stored)")
+    t.add_argument("--json", default="", metavar="OUT", help="also write the per-image counts here")
     args = p.parse_args(argv)
+    if args.cmd == "thin":
+        try:
+            rep = thin(args.dir_in, args.dir_out, args.thr, args.metric, args.score)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"hybridgl_amd.proposals: {e}")
+        print(f"images: {len(rep['per_image'])}   proposals: {rep['before']} -> {rep['after']}")
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump({"before": rep["before"], "after": rep["after"],
+                           "per_image": [{"image_id": k, "before": v[0], "after": v[1]} for k, v in rep["per_image"].items()]}, f)
+        return 0
     try:
         thresholds = [float(v) for v in args.iou.split(",") if v.strip()]
         for d in (args.dir_a, args.dir_b):

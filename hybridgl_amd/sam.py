@@ -1399,6 +1399,32 @@ def merge_rles(rles, intersect=False, device=None):
     return coco_encode_rle(merged) if isinstance(rles[0]["counts"], (str, bytes, bytearray)) else merged
 
 
+def nms_rles(rles, scores=None, thr=0.7, metric="iou", device=None):
+    """mask.nms of pycocotools (maskApi.c:98-107 rleNms) for a list of RLE dicts of ONE image, on the device: the runs cross the
+    bus (ops.rle_pack), the pairs are counted on bit planes and the walk runs there (ops.rle_nms); no mask becomes pixels.
+    Returns the kept indices in walk order: the given order without scores (rleNms's), else descending score with the index
+    breaking ties, a NaN first.  metric "iou", or "containment" (I / the smaller area).  The ratio is the exact one on every
+    pair; rleNms's differs only where rleIou's box pre-filter is not tight.  Raises ValueError on sizes that differ and on an
+    entry that does not decode."""
+    import numpy as np
+    if len(rles) == 0:
+        return []
+    h, w = (int(v) for v in rles[0]["size"])
+    for i, r in enumerate(rles):
+        if [int(v) for v in r["size"]] != [h, w]:
+            raise ValueError(f"nms_rles: entry {i} has size {list(r['size'])}, entry 0 has {[h, w]}")
+    n = len(rles)
+    if scores is not None and len(scores) != n:
+        raise ValueError(f"nms_rles: {len(scores)} scores for {n} entries")
+    slots, table = ops.rle_pack([rle_counts(r) for r in rles], h, w, device=device)
+    sc = None if scores is None else torch.as_tensor(np.asarray(scores, dtype=np.float32)).to(slots.device)
+    out_idx, out_n, result = (x.cpu().numpy() for x in ops.rle_nms(slots, table, [(h, w)], [n], sc, thr, metric))
+    bad = np.flatnonzero(result[:, 0] == 2)
+    if len(bad):
+        raise ValueError(f"nms_rles: entry {int(bad[0])} holds no mask")
+    return [int(i) for i in out_idx[:int(out_n[0])]]
+
+
 def remove_small_regions(masks, area_thresh, mode, out=None):
     """utils/amg.py:267-291 for a batch [n,H,W] uint8 on the device -> (new masks, changed [n] uint8).
     out: (masks, changed) to write into (contiguous slices of a group's tensors) instead of fresh ones."""

@@ -855,6 +855,39 @@ int hgl_rle_merge_device(const uint32_t* slots_src, long long slot_words_src, co
                          const int32_t* member_offsets, const int32_t* bounds,
                          uint32_t* slots, long long slot_words, int32_t* table, int S, int32_t* status,
                          void* ws, size_t ws_bytes, void* stream);
+/* Greedy suppression by MASK overlap inside one encoded set, image by image (csrc/rle.hip): the device form of
+ * rleNms(dt, n, keep, thr) (refer/external/maskApi.c:98-107, mask.nms of pycocotools) with the exact intersection of every pair
+ * in place of rleIou's box pre-filter, a second metric, and the order of the box NMS.  No mask becomes pixels.  Asynchronous on
+ * `stream`; no host synchronisation, allocation or atomics; two calls give the same bytes; SIX launches whatever G and the
+ * sizes are, none for S = 0 (out_n is then not written).
+ * Set = (slots, slot_words, table, S): what hgl_rle_encode_device hands out, forms 0 and 1, with the code 0 / 1 / 2 rules of
+ * hgl_rle_decode_device; an entry of code 1 counts as decoded.
+ * images_host: HOST [G,3] int64, G <= 64, row g = (H_g, W_g, first entry e_g) with the rules of hgl_rle_from_polygons_device:
+ * entries run from 0 to S and do not decrease, an image may own none, H*W < 2^31; read before the call returns.
+ * HGL_EINVAL, and nothing is enqueued: a bad geometry; an image that owns more than 4096 entries (its pair counts are n^2 int32
+ * per split in the workspace); a NaN thr; a metric other than 0 / 1.
+ * Order of the walk within an image.  scores == NULL: the given order, rleNms's.  Otherwise device [S] float and the order of
+ * hgl_nms: descending score, the original index breaks ties, a NaN ranks above every number.
+ * Ratio of a pair with I common pixels: 0 when I = 0; metric 0 (IoU): (double)I / (double)(area_i + area_j - I); metric 1
+ * (containment): (double)I / (double)min(area_i, area_j), which drops a part nested in a whole, or the whole, whichever ranks
+ * later.  An entry is kept iff no kept entry before it in the order has ratio > thr with it, compared in double as
+ * maskApi.c:104.  An empty mask never suppresses and is never suppressed.
+ * out_idx: device [S] int32; from position e_g on, the kept entries of image g in walk order, as indices into the image's list;
+ * the positions behind the out_n[g] kept ones are not written.  out_n: device [G] int32, the kept entries per image -- the shape
+ * hgl_nms_segments returns.
+ * result: device [S,4] int32 = (code, area, rank, by).  code and area as the decoder's status; rank = the entry's position in
+ * the walk; by = the index within the image of the kept entry of lowest rank that suppressed it, -1 for a kept entry.  An entry
+ * of code 2 has rank -1 and by -1, is not listed in out_idx and suppresses nobody.
+ * Limits: the plane words, sum of n_g * W_g * ceil(H_g / 64), < 2^32.
+ * ws: hgl_rle_nms_workspace_bytes for the same geometry (HGL_EWORKSPACE when smaller): the set's run starts, status, boxes and
+ * bit planes (built once, both sides of the pair count), the partial counts as in hgl_rle_match_device (only the tiles that hold
+ * a pair i < j are counted), the walk order and n_g * ceil(n_g / 64) 64-bit suppression words per image.  The query returns 0
+ * for a geometry the call refuses and for S = 0, which needs no workspace and takes ws = NULL. */
+size_t hgl_rle_nms_workspace_bytes(const int64_t* images_host, int G, int S, long long slot_words);
+int hgl_rle_nms_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S,
+                       const int64_t* images_host, int G, const float* scores, double thr, int metric,
+                       int32_t* out_idx, int32_t* out_n, int32_t* result,
+                       void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -37,11 +37,18 @@
              64 proposals per image for 16 images of 640 x 640; equality of the two paths is checked before any timing; writes
              profiles/rle_merge_bench.json as well
 
+  nms        (--nms, instead of the legs above) a proposal set thinned by mask overlap: ONE ops.rle_nms call for 16 images of
+             640 x 640 with 64 and with 256 proposals each (IoU, thr 0.7, scored), as the kernels alone (HIP events) and as host
+             wall time to the kept lists on the host, against what the product offered before the entry existed: the
+             ops.rle_match matrix of the set against itself read back and walked in numpy (wall time, and its device part
+             alone); equality of the two paths is checked before any timing; writes profiles/rle_nms_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
     python tools/rle_bench.py --decode [--reps 30]
     python tools/rle_bench.py --match [--reps 30]
     python tools/rle_bench.py --polygons [--reps 30] [--cli_images 100]
     python tools/rle_bench.py --merge [--reps 30]
+    python tools/rle_bench.py --nms [--reps 30]
 """
 import argparse
 import json
@@ -323,6 +330,63 @@ def merge_leg(dev, reps, H=640, W=640):
     return rec
 
 
+def nms_leg(dev, reps, H=640, W=640, G=16, thr=0.7):
+    """the lists are runs as a store holds them: packed counts (ops.rle_pack), form 0; image g holds the same 256 seeded blobs
+    in an order and with scores of its own"""
+    rec = {"H": H, "W": W, "images": G, "thr": thr, "metric": "iou", "reps": reps}
+    base = []
+    for at in range(0, 256, 64):
+        base += [r["counts"] for r in hsam.masks_to_rle(torch.from_numpy(blobs(64, H, W, 7000 + at)).to(dev))]
+    rng = np.random.default_rng(5)
+    for n in (64, 256):
+        picks = [rng.permutation(256)[:n] for _ in range(G)]
+        slots, table = ops.rle_pack([base[int(i)] for p in picks for i in p], H, W, device=dev)
+        scores_h = rng.random(G * n).astype(np.float32)
+        scores = torch.from_numpy(scores_h).to(dev)
+        sizes, counts = [(H, W)] * G, [n] * G
+
+        def entry():
+            return ops.rle_nms(slots, table, sizes, counts, scores, thr, "iou")
+
+        def entry_host():
+            out_idx, out_n, _ = entry()
+            out_idx, out_n = out_idx.cpu().numpy(), out_n.cpu().numpy()
+            return [out_idx[g * n:g * n + int(out_n[g])].tolist() for g in range(G)]
+
+        def matrix():
+            return ops.rle_match(slots, table, slots, table, sizes, counts, counts)
+
+        def matrix_walk():
+            inter, ma, _ = matrix()
+            area = ma[:, 1].cpu().numpy().astype(np.int64)
+            kept = []
+            for g in range(G):
+                I = inter[g].cpu().numpy().astype(np.int64)
+                a = area[g * n:(g + 1) * n]
+                order = np.lexsort((np.arange(n), -scores_h[g * n:(g + 1) * n].astype(np.float64)))
+                I, a = I[order][:, order], a[order]
+                U = a[:, None] + a[None, :] - I
+                over = (I > 0) & (I.astype(np.float64) / np.maximum(U, 1).astype(np.float64) > thr)
+                gone = np.zeros(n, bool)
+                mine = []
+                for i in range(n):
+                    if not gone[i]:
+                        mine.append(int(order[i]))
+                        gone[i + 1:] |= over[i, i + 1:]
+                kept.append(mine)
+            return kept
+
+        a, b = entry_host(), matrix_walk()
+        assert a == b, "the entry and the matrix walk disagree"
+        rec[f"{n}_proposals"] = {"entries": G * n, "kept": sum(len(k) for k in a), "slot_words": int(slots.shape[1]),
+                                 "rle_nms": device_spread(entry, reps), "rle_nms_to_host_ms": round(host_ms(entry_host, reps), 3),
+                                 "rle_match_matrix": device_spread(matrix, reps),
+                                 "matrix_read_back_and_numpy_walk_ms": round(host_ms(matrix_walk, max(3, reps // 3)), 3)}
+        r = rec[f"{n}_proposals"]
+        r["host_path_over_entry"] = round(r["matrix_read_back_and_numpy_walk_ms"] / r["rle_nms_to_host_ms"], 2)
+    return rec
+
+
 def polygons_leg(dev, reps, cli_images):
     import shutil
     import subprocess
@@ -424,6 +488,8 @@ def main():
     ap.add_argument("--match", action="store_true", help="measure rle_match against the pair list; writes profiles/rle_match_bench.json")
     ap.add_argument("--merge", action="store_true",
                     help="measure rle_merge against decode -> vote -> encode; writes profiles/rle_merge_bench.json")
+    ap.add_argument("--nms", action="store_true",
+                    help="measure rle_nms against the rle_match matrix walked in numpy; writes profiles/rle_nms_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
@@ -434,6 +500,14 @@ def main():
     if args.polygons:
         out = {"polygons": polygons_leg(dev, args.reps, args.cli_images), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_polygons_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
+    if args.nms:
+        out = {"nms": nms_leg(dev, args.reps), "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_nms_bench.json")
         with open(path, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
