@@ -27,7 +27,7 @@ bool carve_enc(HglArena& ar, const HglSamEncoderW* w, int nb, EncPlan& p) {
   const size_t T = (size_t)nb * g * g;
   // windowed blocks pad the grid up to a multiple of the window size
   size_t Tw_max = T;
-  int rl_max = 0;
+  int rl_max = 0, size_max = 0;   // longest rel-pos table; largest attention grid side (a window may be larger than the grid)
   for (int i = 0; i < w->depth; ++i) {
     const int ws = w->blocks[i].window;
     if (ws > 0) {
@@ -35,6 +35,7 @@ bool carve_enc(HglArena& ar, const HglSamEncoderW* w, int nb, EncPlan& p) {
       Tw_max = Tw_max > nb * nw * nw * ws * ws ? Tw_max : nb * nw * nw * ws * ws;
     }
     rl_max = rl_max > w->blocks[i].rel_len ? rl_max : w->blocks[i].rel_len;
+    size_max = size_max > (ws > 0 ? ws : g) ? size_max : (ws > 0 ? ws : g);
   }
   p.nb = nb;
   p.img = ar.take<float>((size_t)nb * 3 * S * S);
@@ -48,8 +49,8 @@ bool carve_enc(HglArena& ar, const HglSamEncoderW* w, int nb, EncPlan& p) {
   p.F = ar.take<float>(T * 4 * D);
   p.Th = ar.take<float>((size_t)w->heads * Tw_max * rl_max);
   p.Tw = ar.take<float>((size_t)w->heads * Tw_max * rl_max);
-  p.relh = ar.take<float>((size_t)w->heads * Tw_max * g);
-  p.relw = ar.take<float>((size_t)w->heads * Tw_max * g);
+  p.relh = ar.take<float>((size_t)w->heads * Tw_max * size_max);
+  p.relw = ar.take<float>((size_t)w->heads * Tw_max * size_max);
   p.neckA = ar.take<float>(T * C);
   p.neckB = ar.take<float>(T * C);
   p.cols3 = ar.take<float>(T * C * 9);
@@ -140,25 +141,37 @@ int enc_block_route(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPla
   return HGL_OK;
 }
 
-// attention of the B windows (or whole grids): the rel-pos producer of r.attn, then the kernel the route named
+// The rel-pos producer: the decomposed terms rel_h / rel_w [B*heads, S, size] from the UNSCALED q (image_encoder.py:351-354) of
+// B windows (or whole grids) of S = size * size tokens.  q as the fp16 hi | lo planes of the split in-projection (q_hi / q_lo,
+// ldq in halfs; qkv null) or as fp32 rows (qkv, ldq in floats).  The ONE place that picks the producer -- enc_attention and the
+// exported hgl_sam_relpos_tables both call it; which kernel a launcher below runs (matrix cores or VALU) is that launcher's.
+// Th / Tw: [heads][B*S][2*size-1] floats each, the products of the generic path.
+int enc_relpos_tables(const float* qkv, const void* q_hi, const void* q_lo, int ldq, int B, int heads, int S, int size, int hd,
+                      const float* Rh, const float* Rw, float* rel_h, float* rel_w, float* Th, float* Tw, hipStream_t st) {
+  if (q_hi || q_lo) return hgl_launch_relpos_split(q_hi, q_lo, ldq, B, heads, S, size, hd, Rh, Rw, rel_h, rel_w, st);
+  // the direct kernels hold a query's head in registers (head dim 64 / 80) and store its terms in pairs (even sizes) from a
+  // table of at most 127 rows in LDS
+  if ((hd == 80 || hd == 64) && (size & 1) == 0 && size <= 64)
+    return hgl_launch_relpos_direct(qkv, ldq, B, heads, S, size, hd, Rh, Rw, rel_h, rel_w, st);
+  // every other head dim and size: q . rel_pos[r] for every r as a batched GEMM, then gathered per (q, k)
+  const int M = B * S, L = 2 * size - 1;
+  HglGemm rel = hgl_gemm_linear(qkv, Rh, nullptr, Th, M, L, hd);    // one batch per head: q's columns of that head
+  rel.lda = ldq, rel.batch = heads, rel.sA = hd, rel.sC = (long long)M * L;
+  HGL_TRY(hgl_launch_gemm(rel, st));
+  rel.W = Rw, rel.C = Tw;
+  HGL_TRY(hgl_launch_gemm(rel, st));
+  HGL_TRY(hgl_launch_relpos_gather(Th, B, heads, S, size, L, 0, rel_h, st));
+  return hgl_launch_relpos_gather(Tw, B, heads, S, size, L, 1, rel_w, st);
+}
+
+// attention of the B windows (or whole grids): the rel-pos producer where r.attn takes the terms as tensors, then the kernel the
+// route named
 int enc_attention(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, hipStream_t st) {
-  const int D = r.D, B = r.B, S = r.S, M = r.M, L = r.L, heads = r.heads, hd = r.hd, size = r.size;
-  if (r.attn == ENC_ATTN_PS_GLOBAL) {
+  if (r.attn == ENC_ATTN_PS_GLOBAL || r.attn == ENC_ATTN_TABLES) {
     const EncPlanes s(p, r);
-    HGL_TRY(hgl_launch_relpos_split(s.Qh, s.Ql, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
-  } else if (r.attn == ENC_ATTN_TABLES) {
-    // decomposed rel-pos tables rel_h/rel_w [B*heads, S, size] from the UNSCALED q (image_encoder.py:351-354)
-    if (hd == 80 || hd == 64) {
-      HGL_TRY(hgl_launch_relpos_direct(p.QKV, 3 * D, B, heads, S, size, hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, st));
-    } else {  // generic head dims: q . rel_pos[r] for every r as a batched GEMM, then gathered per (q,k)
-      HglGemm rel = hgl_gemm_linear(p.QKV, b.rel_pos_h, nullptr, p.Th, M, L, hd);    // one batch per head: q's columns of that head
-      rel.lda = 3 * D, rel.batch = heads, rel.sA = hd, rel.sC = (long long)M * L;
-      HGL_TRY(hgl_launch_gemm(rel, st));
-      rel.W = b.rel_pos_w, rel.C = p.Tw;
-      HGL_TRY(hgl_launch_gemm(rel, st));
-      HGL_TRY(hgl_launch_relpos_gather(p.Th, B, heads, S, size, L, 0, p.relh, st));
-      HGL_TRY(hgl_launch_relpos_gather(p.Tw, B, heads, S, size, L, 1, p.relw, st));
-    }
+    const bool planes = r.attn == ENC_ATTN_PS_GLOBAL;
+    HGL_TRY(enc_relpos_tables(planes ? nullptr : p.QKV, planes ? s.Qh : nullptr, planes ? s.Ql : nullptr, 3 * r.D, r.B, r.heads, r.S,
+                              r.size, r.hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, p.Th, p.Tw, st));
   }
   // f16x3: the attention writes its output as the fp16 hi+lo pair the projection reads
   return hgl_launch_attention(enc_attn(b, p, r, r.attn), st);
@@ -705,6 +718,40 @@ int hgl_sam_encode_batch(const HglSamEncoderW* w, const uint8_t* const* resized_
 int hgl_sam_encode(const HglSamEncoderW* w, const uint8_t* resized_img, int in_h, int in_w, float* emb,
                    void* workspace, size_t workspace_bytes, void* stream) {
   return hgl_sam_encode_batch(w, &resized_img, &in_h, &in_w, 1, emb, workspace, workspace_bytes, stream);
+}
+
+// the generic path's products Th | Tw, [heads][B*S][2*size-1] floats each
+size_t hgl_sam_relpos_tables_workspace_bytes(int B, int heads, int S, int size) {
+  if (B < 1 || heads < 1 || S < 1 || size < 1) return 0;
+  HglArena ar(nullptr, 0);
+  ar.take<float>((size_t)heads * B * S * (2 * size - 1));
+  ar.take<float>((size_t)heads * B * S * (2 * size - 1));
+  return ar.off;
+}
+
+int hgl_sam_relpos_tables(const float* qkv, const void* q_hi, const void* q_lo, int ldq, int B, int heads, int S, int size, int hd,
+                          const float* rel_pos_h, const float* rel_pos_w, float* rel_h, float* rel_w, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  HGL_TRY(hgl_require_device());
+  const bool planes = q_hi || q_lo;
+  HGL_REQUIRE(rel_pos_h && rel_pos_w && rel_h && rel_w && (planes ? (q_hi && q_lo && !qkv) : qkv != nullptr),
+              "sam_relpos_tables: null argument (q as fp32 rows OR as both planes)");
+  HGL_REQUIRE(B > 0 && heads > 0 && size > 0 && S == size * size && (long long)B * heads <= 65535 && (long long)B * S < (1ll << 31),
+              "sam_relpos_tables: bad shape (B %d, heads %d, S %d, size %d)", B, heads, S, size);
+  HGL_REQUIRE(hd == 16 || hd == 32 || hd == 64 || hd == 80, "sam_relpos_tables: unsupported head dim %d (16,32,64,80)", hd);
+  HGL_REQUIRE(ldq >= heads * hd && (ldq & (planes ? 7 : 3)) == 0, "sam_relpos_tables: bad leading dim %d", ldq);
+  HGL_REQUIRE((((uintptr_t)qkv | (uintptr_t)q_hi | (uintptr_t)q_lo | (uintptr_t)rel_pos_h | (uintptr_t)rel_pos_w | (uintptr_t)rel_h |
+                (uintptr_t)rel_w) & 15) == 0, "sam_relpos_tables: operands must be 16-byte aligned");
+  // (the in-projection writes planes in f16x3 mode only: f16 mode keeps no lo plane, f32 mode no planes at all)
+  HGL_REQUIRE(!planes || (hgl_split_layout() && hgl_split_terms() == 3), "sam_relpos_tables: q as planes exists in f16x3 mode only");
+  HglArena ar(workspace, workspace_bytes);
+  float* Th = ar.take<float>((size_t)heads * B * S * (2 * size - 1));
+  float* Tw = ar.take<float>((size_t)heads * B * S * (2 * size - 1));
+  if (!workspace || !ar.ok()) {
+    hgl_set_error("sam_relpos_tables: workspace too small (%zu bytes given)", workspace_bytes);
+    return HGL_EWORKSPACE;
+  }
+  return enc_relpos_tables(qkv, q_hi, q_lo, ldq, B, heads, S, size, hd, rel_pos_h, rel_pos_w, rel_h, rel_w, Th, Tw, (hipStream_t)stream);
 }
 
 int hgl_sam_dense_pe(const HglSamDecoderW* w, const float* grid_coords01, float* dense_pe, void* stream) {

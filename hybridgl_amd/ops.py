@@ -299,6 +299,33 @@ def attention_presplit(qkv, heads, scale=None, mask="none", keep=None, keep_b0=0
     return out
 
 
+def sam_relpos_tables(q, rel_pos_h, rel_pos_w, B, heads, size, rel_h=None, rel_w=None):
+    """The rel-pos producer of the SAM encoder's attention (hgl_sam_relpos_tables): rel_h, rel_w [B*heads, size*size, size]
+    from the UNSCALED q of B windows of size x size tokens.  q: fp32 [B*size*size, ldq], or the pair (q_hi, q_lo) of fp16 planes
+    of that shape (f16x3 mode); the heads' q are the first heads*hd columns of a row.  rel_pos_h / rel_pos_w: [2*size-1, hd].
+    The library picks the kernels as the encoder does."""
+    lib = _lib.load()
+    S = size * size
+    hd = rel_pos_h.shape[1]
+    planes = isinstance(q, (tuple, list))
+    q0 = q[0] if planes else q
+    assert q0.shape[0] == B * S and tuple(rel_pos_h.shape) == tuple(rel_pos_w.shape) == (2 * size - 1, hd)
+    if rel_h is None:
+        rel_h = torch.empty((B * heads, S, size), dtype=torch.float32, device=q0.device)
+    if rel_w is None:
+        rel_w = torch.empty((B * heads, S, size), dtype=torch.float32, device=q0.device)
+    assert tuple(rel_h.shape) == tuple(rel_w.shape) == (B * heads, S, size)
+    need = lib.hgl_sam_relpos_tables_workspace_bytes(B, heads, S, size)
+    ws = workspace(need, q0.device, "sam_relpos")
+    check(lib.hgl_sam_relpos_tables(None if planes else _dev(q, torch.float32, "q"),
+                                    _dev(q[0], torch.float16, "q_hi") if planes else None,
+                                    _dev(q[1], torch.float16, "q_lo") if planes else None, q0.shape[1], B, heads, S, size, hd,
+                                    _dev(rel_pos_h, torch.float32, "rel_pos_h"), _dev(rel_pos_w, torch.float32, "rel_pos_w"),
+                                    _dev(rel_h, torch.float32, "rel_h"), _dev(rel_w, torch.float32, "rel_w"), ws.data_ptr(), need,
+                                    _stream()), "hgl_sam_relpos_tables")
+    return rel_h, rel_w
+
+
 def mask_resize(masks, g):
     """TF.resize(masks.float(), (g,g)) of model/backbone.py:160 -> [N, g*g] fp32."""
     lib = _lib.load()

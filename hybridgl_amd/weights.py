@@ -141,8 +141,9 @@ SAM_CONFIGS = {
 def sam_state_dict(name="vit_h", seed=0):
     """Seeded SAM state_dict (numpy fp32) with the reference's key names
     (segment_anything/modeling/*.py).  Linear/conv weights use std = fan_in^-0.5 so that
-    activations and mask logits stay O(1) with random weights."""
-    cfg = SAM_CONFIGS[name]
+    activations and mask logits stay O(1) with random weights.  `name`: a key of SAM_CONFIGS, or a config dict with the
+    same fields (a geometry that lives with its test)."""
+    cfg = SAM_CONFIGS[name] if isinstance(name, str) else name
     D, L, H = cfg["embed_dim"], cfg["depth"], cfg["num_heads"]
     ps, g = cfg["patch_size"], cfg["img_size"] // cfg["patch_size"]
     hd, C = D // H, cfg["out_chans"]

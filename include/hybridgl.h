@@ -537,6 +537,23 @@ size_t hgl_sam_encode_batch_workspace_bytes(const HglSamEncoderW* w, int nb);
 int hgl_sam_encode_batch(const HglSamEncoderW* w, const uint8_t* const* resized_imgs, const int* in_h, const int* in_w,
                          int nb, float* emb, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The rel-pos producer of one encoder attention launch, on its own: the decomposed terms of add_decomposed_rel_pos
+ * (image_encoder.py:325-361) from the UNSCALED q of B windows (or whole grids) of S = size * size tokens,
+ *   rel_h[b*heads + h, q, k] = q_vec . rel_pos_h[q / size - k + size - 1],
+ *   rel_w[b*heads + h, q, k] = q_vec . rel_pos_w[q % size - k + size - 1],      both [B*heads, S, size],
+ * with q_vec the hd columns of head h in row b*S + q of q.  q comes in one of two forms: fp32 rows of ldq floats (qkv: the
+ * packed in-projection output, q in the first heads*hd columns; q_hi = q_lo = NULL), or the fp16 hi / lo planes of the split
+ * in-projection (q_hi, q_lo, rows of ldq halfs; qkv = NULL; HGL_PREC_F16X3 only).  rel_pos_h / rel_pos_w: [2*size-1, hd].
+ * The kernels are the encoder's own, chosen by the function the encoder calls, from the library precision, hd, size and the
+ * form of q: planes -> the matrix-core kernel on planes (hd 64 / 80, size 14 / 64); hd 64 / 80 at an even size <= 64 -> the
+ * direct kernels (matrix cores in the split-fp16 modes at size 14 / 64, VALU otherwise); every other (hd, size) with hd in
+ * 16 / 32 / 64 / 80 -> two batched GEMMs q . rel_pos^T over all 2*size-1 rows + two gathers, through the workspace.
+ * Exported for the per-kernel tests (tests/test_gpu_relpos_tables.py). */
+size_t hgl_sam_relpos_tables_workspace_bytes(int B, int heads, int S, int size);
+int hgl_sam_relpos_tables(const float* qkv, const void* q_hi, const void* q_lo, int ldq, int B, int heads, int S, int size,
+                          int hd, const float* rel_pos_h, const float* rel_pos_w, float* rel_h, float* rel_w,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* get_dense_pe() (prompt_encoder.py:194-205): grid_coords01 [grid*grid,2] fp32 = ((x+1)-0.5)/grid,
  * ((y+1)-0.5)/grid; fills dense_pe [grid*grid, C]; call once per model. */
 int hgl_sam_dense_pe(const HglSamDecoderW* w, const float* grid_coords01, float* dense_pe, void* stream);
