@@ -978,6 +978,95 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_nms_walk_kernel(const int32_t
   if (t == 0) out_n[im.g] = nkept_s;
 }
 
+// ---- the kept entries of a set, compacted image by image into a second set (hgl_rle_select_device).  Nothing is decoded: an
+// entry moves as the words its table row defines.
+//
+//   J. rle_select_rank_kernel   one workgroup per image.  The image's entries are taken RLE_THREADS at a time in stored order:
+//      a wave's ballot of the keep flags gives every lane the kept entries before it in the wave (a pop-count below the lane),
+//      the four wave totals cross in LDS, the chunks' total is carried in a register.  A kept entry of rank r < max_keep writes
+//      out_src[e + r] = its index; the positions from k = min(kept, max_keep) on receive -1, out_n[g] = k.
+//   K. rle_select_move_kernel   one wave per (destination entry, chunk of RLE_SELECT_CHUNK slot words): the lanes share the
+//      entry's words, 16 bytes a lane and pass where the plan found both buffers aligned (WIDE), 4 otherwise; chunk 0 also
+//      carries the table row and the side columns.  A placeholder (out_src < 0) is the row (1, 0, 0, 0) and the one count H*W.
+__device__ __forceinline__ bool rle_select_kept(const uint8_t* __restrict__ keep, const int32_t* __restrict__ nms, int s) {
+  if (keep) return keep[s] != 0;
+  const int32_t* r = nms + (size_t)s * 4;
+  return (r[0] == 0 || r[0] == 1) && r[3] == -1;
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void rle_select_rank_kernel(const uint8_t* __restrict__ keep, const int32_t* __restrict__ nms,
+                                                                      const RleSelect geo, int32_t* __restrict__ out_src,
+                                                                      int32_t* __restrict__ out_n) {
+  __shared__ int wcnt[2][RLE_THREADS / 64];      // two sets: a chunk's totals are read while the next chunk's are written
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int g = (int)blockIdx.x, f = geo.first[g], n = geo.first[g + 1] - f, limit = geo.max_keep[g];
+  int base = 0;      // kept entries of the chunks before this one: the same in every thread
+  for (int c0 = 0, it = 0; c0 < n; c0 += RLE_THREADS, ++it) {      // uniform over the workgroup
+    const int i = c0 + t;
+    const bool k = i < n && rle_select_kept(keep, nms, f + i);
+    const unsigned long long b = __ballot(k);
+    if (lane == 0) wcnt[it & 1][wave] = __popcll(b);
+    __syncthreads();
+    int r = base + __popcll(b & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+    for (int w = 0; w < RLE_THREADS / 64; ++w) {
+      const int v = wcnt[it & 1][w];
+      r += w < wave ? v : 0;
+      total += v;
+    }
+    if (k && r < limit) out_src[f + r] = i;      // r < limit <= n
+    base += total;
+  }
+  const int kept = base < limit ? base : limit;
+  for (int p = kept + t; p < n; p += RLE_THREADS) out_src[f + p] = -1;
+  if (t == 0) out_n[g] = kept;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(64 * RLE_SELECT_WAVES) void rle_select_move_kernel(
+    const uint32_t* __restrict__ slots, long long slot_words, const int32_t* __restrict__ table, const uint32_t* __restrict__ cols, int C,
+    const RleSelect geo, long long chunks, const int32_t* __restrict__ out_src, uint32_t* __restrict__ out_slots,
+    int32_t* __restrict__ out_table, uint32_t* __restrict__ out_cols) {
+  const int lane = threadIdx.x & 63, S = geo.first[geo.G];
+  const long long blk = (long long)blockIdx.x;
+  const int d = (int)(blk / chunks) * RLE_SELECT_WAVES + (int)(threadIdx.x >> 6);      // the destination entry: uniform over the wave
+  const long long w0 = (blk % chunks) * RLE_SELECT_CHUNK;                               // the chunk's first word
+  if (d >= S) return;
+  const int g = rle_group_find(geo.first, geo.G, d);
+  const int src = out_src[d];
+  uint32_t* dst = out_slots + (size_t)d * (size_t)slot_words;
+  if (src < 0) {      // a placeholder: an empty mask of the image's size
+    if (w0 == 0 && lane == 0) {
+      int32_t* row = out_table + (size_t)d * 4;
+      row[0] = 1; row[1] = 0; row[2] = 0; row[3] = 0;
+      dst[0] = (uint32_t)geo.H[g] * (uint32_t)geo.W[g];      // slot_words >= 1 (the plan)
+    }
+    if (w0 == 0 && lane < C) out_cols[(size_t)lane * S + d] = 0u;
+    return;
+  }
+  const int s = geo.first[g] + src;      // src < n_g: the rank kernel wrote an index of the image's list
+  const int32_t* row = table + (size_t)s * 4;
+  const int n = row[0], form = row[1];
+  if (w0 == 0) {
+    if (lane < 4) out_table[(size_t)d * 4 + lane] = row[lane];
+    if (lane < C) out_cols[(size_t)lane * S + d] = cols[(size_t)lane * S + s];
+  }
+  const unsigned plane_words = ((unsigned)geo.H[g] * (unsigned)geo.W[g] + 31u) / 32u;
+  if (!rle_entry_usable(n, form, slot_words, plane_words)) return;      // the row describes no mask: no slot word moves
+  const long long words = form == 0 ? (long long)n : (long long)plane_words;      // <= slot_words
+  const long long w1 = words < w0 + RLE_SELECT_CHUNK ? words : w0 + RLE_SELECT_CHUNK;      // this chunk: [w0, w1)
+  const uint32_t* from = slots + (size_t)s * (size_t)slot_words;
+  long long w = w0;
+  if (WIDE) {      // both rows start 16-byte aligned and so does the chunk (RLE_SELECT_CHUNK % 4 == 0)
+    const long long quads = w1 > w0 ? (w1 - w0) / 4 : 0;
+    const uint4* from4 = reinterpret_cast<const uint4*>(from + w0);
+    uint4* dst4 = reinterpret_cast<uint4*>(dst + w0);
+    for (long long q = lane; q < quads; q += 64) dst4[q] = from4[q];
+    w = w0 + 4 * quads;      // up to 3 words remain
+  }
+  for (long long q = w + lane; q < w1; q += 64) dst[q] = from[q];
+}
+
 // run starts of one set: [S] arrays of slot_words + 1 words
 size_t rle_starts_bytes(int S, long long slot_words) { return hgl_align_up((size_t)S * (size_t)(slot_words + 1) * sizeof(uint32_t), 256); }
 size_t rle_planes_bytes(int S, int H, int W) {
@@ -1317,6 +1406,30 @@ int hgl_rle_nms_device(const uint32_t* slots, long long slot_words, const int32_
   hipLaunchKernelGGL(rle_nms_walk_kernel, dim3((unsigned)G), dim3(RLE_THREADS), 0, st, (const int32_t*)status, (const int32_t*)order,
                      (const unsigned long long*)sup, plan.n, out_idx, out_n, result);
   return hgl_check_launch("rle_nms_device");
+}
+
+int hgl_rle_select_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S, const int64_t* images_host, int G,
+                          const uint8_t* keep, const int32_t* nms_result, const uint32_t* cols, int C, uint32_t* out_slots,
+                          int32_t* out_table, uint32_t* out_cols, int32_t* out_src, int32_t* out_n, void* stream) {
+  HGL_TRY(hgl_require_device());
+  HGL_REQUIRE(images_host && S >= 0 && C >= 0 &&
+                  (S == 0 || (slots && table && out_slots && out_table && out_src && out_n && (C == 0 || (cols && out_cols)))),
+              "rle_select_device: bad arguments");
+  RleSelectPlan plan;
+  char why[200];
+  if (rle_select_plan(images_host, G, S, slot_words, C, keep != nullptr, nms_result != nullptr, (uintptr_t)slots, (uintptr_t)out_slots,
+                      (uintptr_t)table, (uintptr_t)out_table, &plan, why, sizeof(why)) != 0) {
+    hgl_set_error("rle_select_device: %s", why);
+    return HGL_EINVAL;
+  }
+  if (S == 0) return HGL_OK;      // nothing to move: no launch, out_n is the caller's
+  hipStream_t st = (hipStream_t)stream;
+  // two launches whatever G and the sizes are
+  hipLaunchKernelGGL(rle_select_rank_kernel, dim3((unsigned)G), dim3(RLE_THREADS), 0, st, keep, nms_result, plan.s, out_src, out_n);
+  auto move = plan.wide ? rle_select_move_kernel<true> : rle_select_move_kernel<false>;
+  hipLaunchKernelGGL(move, dim3((unsigned)plan.blocks), dim3(64 * RLE_SELECT_WAVES), 0, st, slots, slot_words, table, cols, C, plan.s,
+                     plan.chunks, (const int32_t*)out_src, out_slots, out_table, out_cols);
+  return hgl_check_launch("rle_select_device");
 }
 
 size_t hgl_rle_merge_workspace_bytes(const int64_t* images_host, int G, int Ssrc, long long slot_words_src, int S, int M) {

@@ -1,8 +1,9 @@
 // The geometry of the RLE entries (csrc/rle.hip): the tiling of an image, shared by the encoder and the decoder, and what the host
 // works out of a decode call's image rows (rle_group_plan), of a match call's (rle_match_plan) and of a merge call's
-// (rle_merge_plan) and of a mask NMS call's (rle_nms_plan) and hands to the kernels by value, and likewise of a polygon call's
-// (rle_poly_plan, csrc/rle_poly.hip).  Plain C++ without a HIP construct: the .hip files include it, and so do the sanitizer
-// harnesses tests/native/rle_group_sanitize.cpp, rle_match_sanitize.cpp, rle_merge_sanitize.cpp and rle_nms_sanitize.cpp.
+// (rle_merge_plan), of a mask NMS call's (rle_nms_plan) and of a compaction's (rle_select_plan) and hands to the kernels by value,
+// and likewise of a polygon call's (rle_poly_plan, csrc/rle_poly.hip).  Plain C++ without a HIP construct: the .hip files include
+// it, and so do the sanitizer harnesses tests/native/rle_group_sanitize.cpp, rle_match_sanitize.cpp, rle_merge_sanitize.cpp,
+// rle_nms_sanitize.cpp and rle_select_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
 #include <stdint.h>
@@ -324,6 +325,76 @@ static inline int rle_nms_plan(const int64_t* images, int G, int S, RleNmsPlan* 
   plan->n.first[G] = S;
   return 0;
 #undef RLE_NMS_REQUIRE
+}
+
+// ---- hgl_rle_select_device: the kept entries of every image moved to the front of the image's range of a second set, in stored
+// order, placeholders behind them.  One workgroup of the rank kernel per image; a wave of the move kernel owns one chunk of
+// RLE_SELECT_CHUNK words of one destination entry, RLE_SELECT_WAVES waves to a workgroup.
+constexpr int RLE_SELECT_COLS_MAX = 8, RLE_SELECT_WAVES = 4, RLE_SELECT_CHUNK = 2048;
+
+struct RleSelect {
+  int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
+  int first[RLE_GROUP_MAX + 1];        // first entries; [G] = S
+  int max_keep[RLE_GROUP_MAX];         // the survivors an image may have: its entries when the caller sets no limit
+  int G;
+};
+
+struct RleSelectPlan {
+  RleSelect s;
+  long long chunks;      // chunks of a slot: ceil(slot_words / RLE_SELECT_CHUNK), at least 1 (the table row and the columns ride in chunk 0)
+  long long blocks;      // grid size of the move kernel: ceil(S / RLE_SELECT_WAVES) * chunks
+  bool wide;             // the 16-byte path: slot_words % 4 == 0 and both slot buffers 16-byte aligned
+};
+
+// images [G,4] = (H, W, first entry, max_keep) -> *plan; 0, or -1 with the reason in why.  Checked: what rle_nms_plan checks of
+// (H, W, first entry) -- 1 <= G <= 64, S >= 0, H*W < 2^31, entries from 0 to S without a step back, at most RLE_NMS_MAX entries per
+// image, its plane-word limit -- and: 0 <= slot_words < 2^31, at least 1 when there is an entry (a placeholder is one count);
+// 0 <= C <= RLE_SELECT_COLS_MAX; exactly one of the keep flags and the NMS rows is given; the byte ranges of slots / out_slots and
+// of table / out_table do not overlap (addresses as numbers: nothing is read through them here); fewer than 2^31 blocks.
+static inline int rle_select_plan(const int64_t* images, int G, int S, long long slot_words, int C, bool has_keep, bool has_nms,
+                                  uintptr_t slots, uintptr_t out_slots, uintptr_t table, uintptr_t out_table, RleSelectPlan* plan,
+                                  char* why, size_t why_cap) {
+#define RLE_SELECT_REQUIRE(cond, ...)       \
+  do {                                      \
+    if (!(cond)) {                          \
+      snprintf(why, why_cap, __VA_ARGS__);  \
+      return -1;                            \
+    }                                       \
+  } while (0)
+  RLE_SELECT_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
+  RLE_SELECT_REQUIRE(slot_words >= 0 && slot_words < (1ll << 31), "slot_words %lld (0 .. 2^31 - 1)", slot_words);
+  RLE_SELECT_REQUIRE(C >= 0 && C <= RLE_SELECT_COLS_MAX, "%d side columns (0 .. %d)", C, RLE_SELECT_COLS_MAX);
+  RLE_SELECT_REQUIRE(has_keep != has_nms, "exactly one of keep and nms_result selects the entries (%s given)", has_keep ? "both" : "neither");
+  int64_t rows[3 * RLE_GROUP_MAX];
+  for (int g = 0; g < G; ++g) rows[3 * g] = images[4 * g], rows[3 * g + 1] = images[4 * g + 1], rows[3 * g + 2] = images[4 * g + 2];
+  RleNmsPlan nms;
+  if (rle_nms_plan(rows, G, S, &nms, why, why_cap) != 0) return -1;
+  RLE_SELECT_REQUIRE(S == 0 || slot_words >= 1, "slot_words 0: a placeholder needs one word");
+  memset(plan, 0, sizeof(*plan));
+  plan->s.G = G;
+  for (int g = 0; g < G; ++g) {
+    const int n = nms.n.first[g + 1] - nms.n.first[g];
+    const long long mk = images[4 * g + 3];
+    plan->s.H[g] = nms.mp.m.H[g];
+    plan->s.W[g] = nms.mp.m.W[g];
+    plan->s.first[g] = nms.n.first[g];
+    plan->s.max_keep[g] = (mk < 0 || mk > n) ? n : (int)mk;
+  }
+  plan->s.first[G] = S;
+  const unsigned long long slot_bytes = (unsigned long long)S * (unsigned long long)slot_words * 4ull;      // < 2^18 * 2^31 * 4
+  const unsigned long long table_bytes = (unsigned long long)S * 16ull;
+  RLE_SELECT_REQUIRE(slot_bytes == 0 || (unsigned long long)slots + slot_bytes <= (unsigned long long)out_slots ||
+                         (unsigned long long)out_slots + slot_bytes <= (unsigned long long)slots,
+                     "out_slots overlaps slots");
+  RLE_SELECT_REQUIRE(table_bytes == 0 || (unsigned long long)table + table_bytes <= (unsigned long long)out_table ||
+                         (unsigned long long)out_table + table_bytes <= (unsigned long long)table,
+                     "out_table overlaps table");
+  plan->chunks = slot_words > 0 ? (slot_words + RLE_SELECT_CHUNK - 1) / RLE_SELECT_CHUNK : 1;
+  plan->blocks = (((long long)S + RLE_SELECT_WAVES - 1) / RLE_SELECT_WAVES) * plan->chunks;      // <= 2^16 * 2^20
+  RLE_SELECT_REQUIRE(plan->blocks < (1ll << 31), "too many words (%d entries of %lld) for one launch", S, slot_words);
+  plan->wide = slot_words % 4 == 0 && ((slots | out_slots) & 15u) == 0;
+  return 0;
+#undef RLE_SELECT_REQUIRE
 }
 
 // ---- hgl_rle_from_polygons_device (csrc/rle_poly.hip): polygons -> RLE, one workgroup per entry.  A polygon's toggle plane --

@@ -112,6 +112,14 @@ def default_argument_parser():
     p.add_argument("--proposals_dir", default="", metavar="DIR",
                    help="with --real: take every image's proposals from a store --save_proposals (or SAM's amg.py) wrote instead of "
                         "running SAM: no SAM model is built, no checkpoint read; an image the store lacks is an error")
+    p.add_argument("--mask_nms_thresh", type=float, default=None, metavar="T",
+                   help="with --proposals_dir: thin every image's stored list by mask overlap as it loads, on the device -- an entry "
+                        "falls when a kept entry before it in the walk has ratio > T with it; what `python -m hybridgl_amd.proposals "
+                        "thin` would write to a second store, without the store; --proposal_cap then caps the survivors")
+    p.add_argument("--mask_nms_metric", default="iou", choices=["containment", "iou"],
+                   help="with --mask_nms_thresh: the ratio, I / union or I / the smaller area")
+    p.add_argument("--mask_nms_score", default="predicted_iou", choices=["predicted_iou", "stability_score", "area", "stored"],
+                   help="with --mask_nms_thresh: the record field the walk is ordered by, descending (stored: the stored order)")
     p.add_argument("--proposal_ceiling", default="", metavar="OUT",
                    help="with --proposals_dir: write the proposal ceiling of the store -- per sentence the stored proposal of the "
                         "largest IoU against the ground truth, {oIoU, mIoU, cum, n_sentences} as the sweep reports it -- here and "
@@ -398,7 +406,23 @@ def split_by(dataset):
     return "umd" if dataset == "refcocog" else "unc"          # Hybridgl_main.py:26-29
 
 
+def check_mask_nms_flags(args):
+    """--mask_nms_thresh thins a store as it loads: it needs the store, a number, and a run (the ceiling reads the files itself)"""
+    thr = getattr(args, "mask_nms_thresh", None)
+    if thr is None:
+        return
+    if not getattr(args, "proposals_dir", ""):
+        raise SystemExit("--mask_nms_thresh thins the proposals of a store as they load: it needs --proposals_dir (the generator's "
+                         "own proposals are thinned by writing a store and reading it back)")
+    if thr != thr:
+        raise SystemExit("--mask_nms_thresh is NaN")
+    if getattr(args, "proposal_ceiling", ""):
+        raise SystemExit("--mask_nms_thresh and --proposal_ceiling exclude each other: the ceiling reads the store's files as they "
+                         "are; write the thinner store with `python -m hybridgl_amd.proposals thin` and ask for its ceiling")
+
+
 def check_proposal_flags(args):
+    check_mask_nms_flags(args)
     save, read = getattr(args, "save_proposals", ""), getattr(args, "proposals_dir", "")
     if save and read:
         raise SystemExit("--save_proposals and --proposals_dir exclude each other: a run either writes a store or reads one")
@@ -424,7 +448,9 @@ def build_models(args, dev):
     check_proposal_flags(args)
     if getattr(args, "proposals_dir", ""):      # the store stands in for the generator: no SAM model, no checkpoint
         from .proposals import StoredProposals
-        gen = StoredProposals(args.proposals_dir, dev)
+        gen = StoredProposals(args.proposals_dir, dev, mask_nms_thresh=getattr(args, "mask_nms_thresh", None),
+                              mask_nms_metric=getattr(args, "mask_nms_metric", "iou"),
+                              mask_nms_score=getattr(args, "mask_nms_score", "predicted_iou"))
     elif args.sam or args.real:
         from .sam import SamAutomaticMaskGenerator, sam_model_registry
         sam = sam_model_registry[args.sam_model](device=dev, precision=args.precision)
@@ -729,6 +755,9 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
         stats["proposals_saved"] = recorder.written
     if getattr(args, "proposals_dir", ""):
         stats["proposal_store"] = gen.settings()
+        if getattr(gen, "mask_nms_thresh", None) is not None:      # this rank's own images
+            stats["proposals_thinned"] = {"thr": gen.mask_nms_thresh, "metric": gen.mask_nms_metric, "score": gen.mask_nms_score,
+                                          "before": int(gen.thinned[0]), "after": int(gen.thinned[1])}
     if sweep is not None:      # one more exchange of rows, on every rank
         stats["sweep"] = sweep_report(sweep, pipe.sweep_metrics(dist))
     return m, stats
@@ -752,6 +781,7 @@ def main(args):
         torch.cuda.set_device(dev)
         return ensemble_masks_main(args, dev)
     check_device_targets(args)
+    check_mask_nms_flags(args)
     if getattr(args, "score_masks", ""):      # before any model exists: files and ground truth only
         if world > 1:
             raise SystemExit("--score_masks runs on one rank: start it without a launcher (world size 1)")
@@ -782,7 +812,10 @@ def main(args):
         return m
     if "proposal_store" in stats:
         print(f"proposals from {args.proposals_dir} (no SAM model built); generator settings of the store: "
-              + (", ".join(f"{k}={v}" for k, v in stats["proposal_store"].items()) or "none recorded (no meta.json)"))
+              + (", ".join(f"{k}={v}" for k, v in stats["proposal_store"].items()) or "none recorded (no meta.json)")
+              + ("".join(f"; thinned on load by mask NMS: thr={t['thr']:g} metric={t['metric']} score={t['score']}, "
+                         f"{t['before']} -> {t['after']} proposals" for t in [stats["proposals_thinned"]])
+                 if "proposals_thinned" in stats else ""))
     if sweep is not None:
         import json
         b = sweep["best"]

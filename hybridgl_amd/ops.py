@@ -656,7 +656,7 @@ def rle_nms_layout(sizes, counts):
     return images
 
 
-def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou"):
+def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou", out=None):
     """Greedy suppression by mask overlap inside one encoded set, image by image (hgl_rle_nms_device on the current stream, no
     synchronisation): the S entries of slots / table (what rle_encode or rle_pack returns) belong to G = len(sizes) <= 64
     images, counts[g] <= 4096 consecutive entries of sizes[g] = (H, W); an image may own none.  scores: float device tensor [S]
@@ -665,7 +665,8 @@ def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou"):
     "containment": I / the smaller area; an empty mask never suppresses and is never suppressed.
     Returns (out_idx [S] int32: from image g's first entry on, its kept entries in walk order as indices into its list; out_n
     [G] int32: how many; result [S,4] int32 = code, area, rank, by: the entry's position in the walk and the index of the kept
-    entry of lowest rank that suppressed it, -1 for a kept one and for code 2).  No mask becomes pixels."""
+    entry of lowest rank that suppressed it, -1 for a kept one and for code 2).  No mask becomes pixels.  The three are views of
+    ONE int32 buffer, out_idx | result | out_n (`out`: a contiguous int32 device tensor of 5 S + G elements to use for it)."""
     lib = _lib.load()
     sp, sw, tp, S = _rle_set(slots, table, "rle_nms")
     if metric not in NMS_METRIC:
@@ -684,7 +685,10 @@ def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou"):
             raise ValueError(f"scores: expected {S} values, got {scores.numel()}")
         scores = scores.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
         cp = _dev(scores, torch.float32, "scores")
-    out = torch.empty(S * 5 + G, dtype=torch.int32, device=dev)      # one buffer: a caller that wants all three copies one tensor
+    if out is None:
+        out = torch.empty(S * 5 + G, dtype=torch.int32, device=dev)      # one buffer: a caller that wants all three copies one tensor
+    elif out.numel() != S * 5 + G or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out: expected a contiguous int32 tensor of {S * 5 + G} elements on {dev}, got {tuple(out.shape)} {out.dtype}")
     out_idx, result, out_n = out[:S], out[S:5 * S].view(S, 4), out[5 * S:]
     if S == 0:
         out_n.zero_()
@@ -694,6 +698,88 @@ def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou"):
     check(lib.hgl_rle_nms_device(sp, sw, tp, S, images.ctypes.data, G, cp, thr, NMS_METRIC[metric], out_idx.data_ptr(),
                                  out_n.data_ptr(), result.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "hgl_rle_nms_device")
     return out_idx, out_n, result
+
+
+def rle_select_layout(sizes, counts, max_keep=None):
+    """images [G,4] int64 = (H, W, first entry, max_keep) of a compaction over G images: image g owns counts[g] consecutive
+    entries of sizes[g] = (H, W).  max_keep: None (no limit: -1 in every row), one number for every image, or one per image (None
+    or a negative number: no limit for that image)"""
+    import numpy as np
+    if len(sizes) != len(counts):
+        raise ValueError(f"rle_select_layout: {len(sizes)} sizes and {len(counts)} counts")
+    if max_keep is None or not hasattr(max_keep, "__len__"):
+        max_keep = [max_keep] * len(sizes)
+    if len(max_keep) != len(sizes):
+        raise ValueError(f"rle_select_layout: {len(sizes)} sizes and {len(max_keep)} limits")
+    images = np.zeros((len(sizes), 4), dtype=np.int64)
+    e = 0
+    for g, ((H, W), n, mk) in enumerate(zip(sizes, counts, max_keep)):
+        if int(n) < 0:
+            raise ValueError(f"rle_select_layout: image {g} has {n} entries")
+        images[g] = (int(H), int(W), e, -1 if mk is None or int(mk) < 0 else int(mk))
+        e += int(n)
+    return images
+
+
+def rle_select(slots, table, sizes, counts, keep=None, nms_result=None, cols=None, max_keep=None, out=None, back=None):
+    """The kept entries of an encoded set, compacted image by image into a second, dense set (hgl_rle_select_device on the
+    current stream, no synchronisation): the S entries of slots / table belong to G = len(sizes) <= 64 images, counts[g] <= 4096
+    consecutive entries of sizes[g] = (H, W).  Exactly one of keep (bool / uint8 device tensor [S], nonzero = kept) and
+    nms_result (the result [S,4] of rle_nms: kept iff the code is 0 or 1 and by == -1) says who survives; max_keep (see
+    rle_select_layout) lets only the first max_keep kept entries of an image survive.  cols: a contiguous device tensor [C,S] of
+    a 4-byte dtype, C <= 8, or None: side columns that travel with the entries.
+    Returns (out_slots [S, slot_words], out_table [S,4], out_cols [C,S] in cols' dtype, out_src [S] int32, out_n [G] int32): from
+    image g's first entry on, its out_n[g] survivors in stored order -- row, the words the row defines, columns, and out_src =
+    the survivor's index within the image's list -- and behind them placeholders: an empty code-0 mask (row (1, 0, 0, 0), one
+    count H*W), out_src -1, columns 0.  So rle_decode_group(out_slots, out_table, sizes, counts) needs no count from the device.
+    Slot words beyond what an entry's form defines are not written.  The first three are views of ONE int32 buffer, table | slots
+    | cols (`out`: a contiguous int32 device tensor of S * (4 + slot_words + C) elements to use for it), the last two of another,
+    out_src | out_n (`back`: S + G elements)."""
+    lib = _lib.load()
+    sp, sw, tp, S = _rle_set(slots, table, "rle_select")
+    images = rle_select_layout(sizes, counts, max_keep)
+    G = len(images)
+    if int(sum(int(n) for n in counts)) != S:
+        raise ValueError(f"rle_select: counts sum to {sum(counts)}, the set has {S} entries")
+    if (keep is None) == (nms_result is None):
+        raise ValueError("rle_select: exactly one of keep and nms_result selects the entries")
+    dev = slots.device
+    kp = rp = cp = None
+    if keep is not None:
+        if keep.numel() != S:
+            raise ValueError(f"keep: expected {S} flags, got {keep.numel()}")
+        kp, keep = _u8(keep.reshape(-1), "keep")
+    else:
+        if tuple(nms_result.shape) != (S, 4):
+            raise ValueError(f"nms_result: expected [{S}, 4], got {tuple(nms_result.shape)}")
+        rp = _dev(nms_result, torch.int32, "nms_result")
+    C, cdtype = 0, torch.int32
+    if cols is not None:
+        if cols.dim() != 2 or cols.shape[1] != S or cols.element_size() != 4:
+            raise ValueError(f"cols: expected a [C, {S}] tensor of a 4-byte dtype, got {tuple(cols.shape)} {cols.dtype}")
+        C, cdtype = int(cols.shape[0]), cols.dtype
+        if C:
+            cp = _dev(cols, cdtype, "cols")
+
+    def take(buf, numel, name):
+        if buf is None:
+            return torch.empty(numel, dtype=torch.int32, device=dev)
+        if buf.numel() != numel or buf.dtype != torch.int32 or not buf.is_contiguous() or buf.device != dev:
+            raise ValueError(f"{name}: expected a contiguous int32 tensor of {numel} elements on {dev}, got {tuple(buf.shape)} {buf.dtype}")
+        return buf.view(-1)
+
+    out = take(out, S * (4 + sw + C), "out")
+    back = take(back, S + G, "back")
+    out_slots, out_table = rle_split(out, S, sw)
+    out_cols = out[S * (4 + sw):].view(C, S).view(cdtype)
+    out_src, out_n = back[:S], back[S:]
+    if S == 0:      # the entry launches nothing and leaves out_n alone
+        out_n.zero_()
+        return out_slots, out_table, out_cols, out_src, out_n
+    base = out.data_ptr()
+    check(lib.hgl_rle_select_device(sp, sw, tp, S, images.ctypes.data, G, kp, rp, cp, C, base + 16 * S, base, base + 4 * S * (4 + sw) if C else None,
+                                    out_src.data_ptr(), out_n.data_ptr(), _stream()), "hgl_rle_select_device")
+    return out_slots, out_table, out_cols, out_src, out_n
 
 
 POLY_RULE = {"once": 0, "any": 1}

@@ -259,11 +259,11 @@ class ProposalRecorder:
 class _Rows:
     """the proposals of one stored image, packed on a loader thread: ONE pinned int32 buffer = table [n,4] | slots [n,sw] |
     the bits of predicted_iou [n] | of stability_score [n], and the stored boxes for the check"""
-    __slots__ = ("n", "H", "W", "sw", "buf", "bbox")
+    __slots__ = ("n", "H", "W", "sw", "buf", "bbox", "area")
 
 
 class _Stored:
-    __slots__ = ("ids", "sizes", "counts", "first", "rows", "masks", "boxes", "iou", "stab", "host", "ev", "overflow")
+    __slots__ = ("ids", "sizes", "counts", "first", "rows", "masks", "boxes", "iou", "stab", "host", "ev", "overflow", "thinned")
 
 
 class StoredProposals:
@@ -272,15 +272,34 @@ class StoredProposals:
     prefetch(image_id, size) is the host half -- file, JSON, sam.rle_counts_from_string, packing into one pinned buffer -- and
     belongs on the loader threads (RealRefs.load / RealPhraseCut.load call it); an image nobody prefetched is read where it
     is first asked for.  Per group the loop's thread concatenates the staged rows, issues one upload and one
-    ops.rle_decode_group, and reads status and boxes back once, in group_cleanup.  cap: the first `cap` entries of an image."""
+    ops.rle_decode_group, and reads status and boxes back once, in group_cleanup.  cap: the first `cap` entries of an image.
+
+    mask_nms_thresh: thin every image's list by mask overlap as it loads -- what thin() would have written to a second store,
+    without the store.  All of an image's entries are uploaded; ops.rle_nms (mask_nms_metric, and mask_nms_score: one of
+    THIN_SCORES, the order of the walk) decides, ops.rle_select moves the survivors to the front of the image's range in stored
+    order with their IoU / stability columns, and the one ops.rle_decode_group runs over the compacted set with the original
+    counts: the positions behind the survivors decode to empty masks that nobody is handed.  The caps then apply to the
+    survivors.  The survivors' counts and source indices ride back in the read-back that carries boxes and status: still one
+    per group, no further synchronisation.  thinned = [entries read, entries handed out] over the images met so far, each image
+    counted once (noted in group_cleanup)."""
     wants_image_ids = True
     crop_n_layers = 0      # HybridGLPipeline.step: one generate_device call, whatever produced the store
 
-    def __init__(self, store, device, cap=None, keep=256):
+    def __init__(self, store, device, cap=None, keep=256, mask_nms_thresh=None, mask_nms_metric="iou", mask_nms_score="predicted_iou"):
         self.store = store if isinstance(store, ProposalStore) else ProposalStore(store)
         self.device = torch.device(device)
         self.cap = cap
         self.keep = int(keep)
+        self.mask_nms_thresh = None if mask_nms_thresh is None else float(mask_nms_thresh)
+        self.mask_nms_metric, self.mask_nms_score = mask_nms_metric, mask_nms_score
+        if self.mask_nms_thresh is not None:
+            if self.mask_nms_thresh != self.mask_nms_thresh:
+                raise ValueError("StoredProposals: mask_nms_thresh is NaN")
+            if mask_nms_metric not in ops.NMS_METRIC:
+                raise ValueError(f"StoredProposals: mask_nms_metric {mask_nms_metric!r} (one of {sorted(ops.NMS_METRIC)})")
+            if mask_nms_score not in THIN_SCORES:
+                raise ValueError(f"StoredProposals: mask_nms_score {mask_nms_score!r} (one of {list(THIN_SCORES)})")
+        self._thinned = {}      # image id -> (entries read, entries handed out)
         self._rows = collections.OrderedDict()      # image id -> _Rows, the last `keep` images
         self._lock = threading.Lock()
         self._free = collections.deque()            # (pinned buffer, the event behind its upload)
@@ -289,6 +308,10 @@ class StoredProposals:
 
     def records(self, image_id):
         return self.store.records(image_id)
+
+    @property
+    def thinned(self):
+        return [sum(v[0] for v in self._thinned.values()), sum(v[1] for v in self._thinned.values())]
 
     def settings(self):
         return self.store.meta()
@@ -341,6 +364,9 @@ class StoredProposals:
         tail[:n] = [r["predicted_iou"] for r in recs]
         tail[n:] = [r["stability_score"] for r in recs]
         rows.bbox = np.asarray([r["bbox"] for r in recs], dtype=np.int64).reshape(n, 4)
+        rows.area = None
+        if self.mask_nms_thresh is not None and self.mask_nms_score == "area":
+            rows.area = np.asarray([float(r["area"]) for r in recs], dtype=np.float32)
         return rows
 
     # ---- device half (the loop's thread)
@@ -358,10 +384,13 @@ class StoredProposals:
             raise ValueError("StoredProposals: the image ids of the group are needed (RefBatch.image_id)")
         st = _Stored()
         st.overflow = 0
+        st.thinned = None
         st.ids = list(image_ids)
         st.sizes = [tuple(int(v) for v in im.shape[:2]) for im in images]
         st.rows = [self.prefetch(iid, size) for iid, size in zip(st.ids, st.sizes)]
         caps = [c for c in (cap, self.cap) if c]
+        if self.mask_nms_thresh is not None:
+            return self._begin_thinned(st, min(caps) if caps else None, encoded_event)
         st.counts = [min([r.n] + caps) for r in st.rows]
         st.first = np.cumsum([0] + st.counts)
         S = int(st.first[-1])
@@ -408,9 +437,96 @@ class StoredProposals:
         """the group's pixels, boxes (aux[0]) and status (aux[1]): two launches whatever the group holds"""
         return ops.rle_decode_group(slots, table, sizes, counts, aux=aux)
 
+    # ---- thinning on load (mask_nms_thresh): the same three calls over nms -> select -> decode
+    def _begin_thinned(self, st, cap, encoded_event):
+        st.counts = [r.n for r in st.rows]      # every stored entry goes up: the caps apply to the survivors
+        st.first = np.cumsum([0] + st.counts)
+        S, G = int(st.first[-1]), len(st.rows)
+        if encoded_event is not None:
+            encoded_event.record(torch.cuda.current_stream(self.device))
+        st.ev = None
+        st.thinned = cap
+        if S == 0:
+            return st
+        by_area = self.mask_nms_score == "area"
+        sw = max(r.sw for r in st.rows if r.n)
+        numel = S * (6 + sw + (1 if by_area else 0))
+        host = self._staging(numel)
+        h = host.numpy()[:numel]
+        slots, table = ops.rle_split(h, S, sw)
+        tail = h[S * (4 + sw):]
+        for r, n, e in zip(st.rows, st.counts, st.first):
+            if n == 0:
+                continue
+            rs, rt = ops.rle_split(r.buf.numpy(), n, r.sw)
+            table[e:e + n] = rt
+            slots[e:e + n, :r.sw] = rs      # words beyond an entry's n_counts are never read
+            rtail = r.buf.numpy()[n * (4 + r.sw):]
+            tail[e:e + n] = rtail[:n]
+            tail[S + e:S + e + n] = rtail[n:]
+            if by_area:
+                tail[2 * S + e:2 * S + e + n] = r.area.view(np.int32)
+        dev = torch.empty(numel, dtype=torch.int32, device=self.device)
+        dev.copy_(host[:numel], non_blocking=True)
+        up = torch.cuda.Event()
+        up.record()
+        self._free.append((host, up))
+        dslots, dtable = ops.rle_split(dev, S, sw)
+        cols = dev[S * (4 + sw):S * (6 + sw)].view(2, S)      # predicted_iou | stability_score, as bits
+        scores = {"predicted_iou": cols[0], "stability_score": cols[1], "area": dev[S * (6 + sw):], "stored": None}[self.mask_nms_score]
+        if scores is not None:
+            scores = scores.view(torch.float32)
+        # ONE int32 buffer leaves in one copy: boxes | status | out_src | out_n | the NMS's out_idx, result, out_n
+        back = torch.empty(8 * S + (S + G) + (5 * S + G), dtype=torch.int32, device=self.device)
+        result = ops.rle_nms(dslots, dtable, st.sizes, st.counts, scores, self.mask_nms_thresh, self.mask_nms_metric,
+                             out=back[9 * S + G:])[2]
+        cslots, ctable, ccols, _, _ = ops.rle_select(dslots, dtable, st.sizes, st.counts, nms_result=result, cols=cols, max_keep=cap,
+                                                     back=back[8 * S:9 * S + G])
+        st.iou, st.stab = ccols[0].view(torch.float32), ccols[1].view(torch.float32)
+        st.masks, st.boxes = self._decode(cslots, ctable, st.sizes, st.counts, back[:8 * S].view(2, S, 4))[:2]
+        fits = self._back and self._back[-1].numel() >= back.numel()
+        st.host = self._back.pop() if fits else torch.empty(max(back.numel(), 4096), dtype=torch.int32, pin_memory=True)
+        st.host[:back.numel()].copy_(back, non_blocking=True)
+        st.ev = torch.cuda.Event()
+        st.ev.record()
+        return st
+
+    def _cleanup_thinned(self, st):
+        S, G = int(st.first[-1]), len(st.rows)
+        st.ev.synchronize()
+        h = st.host.numpy()[:14 * S + 2 * G].copy()
+        self._back.append(st.host)
+        st.host = None
+        boxes, status = h[:8 * S].reshape(2, S, 4)
+        out_src, out_n = h[8 * S:9 * S], h[9 * S:9 * S + G]
+        codes = h[10 * S + G:14 * S + G].reshape(S, 4)[:, 0]      # the NMS's result rows: every source entry's code
+        kept = []
+        for g, (iid, r, n, e) in enumerate(zip(st.ids, st.rows, st.counts, st.first)):
+            bad = np.flatnonzero(codes[e:e + n] != 0)
+            if len(bad):
+                raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {int(bad[0])}: its counts do not decode to a "
+                                 f"{r.H} x {r.W} mask (status {int(codes[e + bad[0]])})")
+            k = int(out_n[g])
+            for p in range(k):
+                src, code = int(out_src[e + p]), int(status[e + p, 0])
+                if code != 0:
+                    raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {src}: its counts do not decode to a "
+                                     f"{r.H} x {r.W} mask (status {code})")
+                x0, y0, x1, y1 = (int(v) for v in boxes[e + p])
+                if int(status[e + p, 1]) > 0 and [x0, y0, x1 - x0, y1 - y0] != r.bbox[src].tolist():
+                    raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {src}: the stored bbox "
+                                     f"{r.bbox[src].tolist()} is not the box of its mask {[x0, y0, x1 - x0, y1 - y0]}")
+            kept.append(k)
+            self._thinned[iid] = (n, k)
+        st.masks = [m[:k] for m, k in zip(st.masks, kept)]
+        st.counts = kept      # st.first keeps the uploaded layout: the survivors lead every image's range
+        return st
+
     def group_cleanup(self, st):
         if st.ev is None:
             return st
+        if self.mask_nms_thresh is not None:
+            return self._cleanup_thinned(st)
         st.ev.synchronize()
         S = int(st.first[-1])
         boxes, status = st.host.numpy()[:8 * S].reshape(2, S, 4).copy()

@@ -905,6 +905,36 @@ int hgl_rle_nms_device(const uint32_t* slots, long long slot_words, const int32_
                        const int64_t* images_host, int G, const float* scores, double thr, int metric,
                        int32_t* out_idx, int32_t* out_n, int32_t* result,
                        void* ws, size_t ws_bytes, void* stream);
+/* The kept entries of an encoded set, compacted image by image into a second, dense set (csrc/rle.hip): what stands between a
+ * stage that decides which entries survive (hgl_rle_nms_device, or any caller's flags) and a stage that takes a dense set (the
+ * decoders).  Stable: survivors keep their stored order.  Nothing is decoded; an entry moves as the words its table row defines.
+ * Asynchronous on `stream`; no host synchronisation, allocation, workspace or atomics; two calls give the same bytes; TWO
+ * launches whatever G and the sizes are, none for S = 0 (out_n is then not written).
+ * Set = (slots, slot_words, table, S): as everywhere in the family, forms 0 and 1, with the code 0 / 1 / 2 rules of
+ * hgl_rle_decode_device.
+ * images_host: HOST [G,4] int64, G <= 64, row g = (H_g, W_g, first entry e_g, max_keep_g); the first three columns with the
+ * rules (and the limits) of hgl_rle_nms_device, at most 4096 entries per image; max_keep_g < 0: no limit, otherwise only the
+ * first max_keep_g kept entries of the image, in stored order, survive.  Read before the call returns.
+ * Exactly one of keep and nms_result is non-NULL.  keep: device [S] bytes, nonzero = kept.  nms_result: the result [S,4] rows of
+ * hgl_rle_nms_device; an entry is kept iff its code is 0 or 1 and by == -1.
+ * cols: device [C,S] 4-byte words, 0 <= C <= 8 (NULL for C = 0): side columns that travel with the entries, moved as bits.
+ * HGL_EINVAL, and nothing is enqueued: a bad geometry; slot_words < 0 or >= 2^31, or 0 with S > 0 (a placeholder is one word); C
+ * outside 0 .. 8; both or neither of keep / nms_result; out_slots overlapping slots or out_table overlapping table (the other
+ * outputs must not overlap an input either; that is the caller's to keep).
+ * Outputs, with k_g survivors in image g.  Position e_g + p, p < k_g, holds the p-th survivor in stored order: out_table row =
+ * its row, whole; out_slots = exactly the words its form defines (n_counts in form 0, ceil(H*W/32) in form 1), nothing beyond
+ * them; a kept entry whose row describes no mask (code 2; reachable through keep only) has its row copied and no slot word
+ * written; out_src = its index within the image's list; out_cols[c] = cols[c] of it.  Positions p >= k_g of the image's range
+ * receive a PLACEHOLDER: row (1, 0, 0, 0), slot word 0 = H_g*W_g (nothing behind it), out_src = -1, columns 0 -- a legal, empty,
+ * code-0 mask for every consumer in the family, so a decode can run over the original layout with no count known on the host.
+ * out_n: device [G] int32 = k_g.  out_slots [S, slot_words], out_table [S,4], out_cols [C,S], out_src [S].
+ * The slots move 16 bytes a lane when slot_words % 4 == 0 and both slot buffers are 16-byte aligned, 4 bytes otherwise. */
+int hgl_rle_select_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S,
+                          const int64_t* images_host, int G,
+                          const uint8_t* keep, const int32_t* nms_result,
+                          const uint32_t* cols, int C,
+                          uint32_t* out_slots, int32_t* out_table, uint32_t* out_cols,
+                          int32_t* out_src, int32_t* out_n, void* stream);
 
 #ifdef __cplusplus
 }

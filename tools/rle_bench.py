@@ -43,12 +43,21 @@
              ops.rle_match matrix of the set against itself read back and walked in numpy (wall time, and its device part
              alone); equality of the two paths is checked before any timing; writes profiles/rle_nms_bench.json as well
 
+  select     (--select, instead of the legs above) the kept entries of that set compacted on the device: ONE ops.rle_select call
+             on the workload of --nms, driven by the NMS result with two side columns, (a) as the kernels alone (HIP events
+             behind a 256 MB copy that keeps the device busy while the host enqueues: two launches of a few microseconds are
+             otherwise timed at the host's pace) against a plain device-to-device copy of the set's bytes timed the same way, and (b) as wall time from the uploaded set to compacted
+             slots ready for the decode (ops.rle_nms + ops.rle_select) against what there was before the entry: ops.rle_nms,
+             the kept lists read back, the kept rows re-packed with numpy and uploaded; equality of the two paths is checked
+             before any timing; writes profiles/rle_select_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
     python tools/rle_bench.py --decode [--reps 30]
     python tools/rle_bench.py --match [--reps 30]
     python tools/rle_bench.py --polygons [--reps 30] [--cli_images 100]
     python tools/rle_bench.py --merge [--reps 30]
     python tools/rle_bench.py --nms [--reps 30]
+    python tools/rle_bench.py --select [--reps 20]
 """
 import argparse
 import json
@@ -387,6 +396,100 @@ def nms_leg(dev, reps, H=640, W=640, G=16, thr=0.7):
     return rec
 
 
+def device_spread_behind(fn, reps, head, warm=5):
+    """device_spread for a call of a few microseconds: `head` -- device work of some hundred microseconds -- is enqueued in front
+    of the first event, so the host has enqueued fn and the second event before the device reaches the first, and the interval
+    holds the kernels of fn back to back, not the host's pace of launching them"""
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        head()
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) * 1e3)
+    return {"median_us": round(statistics.median(out), 1), "min_us": round(min(out), 1), "max_us": round(max(out), 1)}
+
+
+def select_leg(dev, reps, H=640, W=640, G=16, thr=0.7):
+    """the workload of nms_leg; the NMS result of the set is computed once and held on the device for (a)"""
+    rec = {"H": H, "W": W, "images": G, "thr": thr, "metric": "iou", "reps": reps}
+    base = []
+    for at in range(0, 256, 64):
+        base += [r["counts"] for r in hsam.masks_to_rle(torch.from_numpy(blobs(64, H, W, 7000 + at)).to(dev))]
+    rng = np.random.default_rng(5)
+    ballast = torch.empty((2, 1 << 28), dtype=torch.uint8, device=dev)      # a 256 MB copy: the device's work while the host enqueues
+
+    def head():
+        ballast[1].copy_(ballast[0])
+
+    for n in (64, 256):
+        picks = [rng.permutation(256)[:n] for _ in range(G)]
+        slots, table = ops.rle_pack([base[int(i)] for p in picks for i in p], H, W, device=dev)
+        S, sw = int(slots.shape[0]), int(slots.shape[1])
+        scores = torch.from_numpy(rng.random(G * n).astype(np.float32)).to(dev)
+        cols = torch.stack([scores, 1 - scores]).contiguous()
+        sizes, counts = [(H, W)] * G, [n] * G
+        slots_h, table_h = slots.cpu().numpy(), table.cpu().numpy()      # the host's copy: it packed the set
+        result = ops.rle_nms(slots, table, sizes, counts, scores, thr, "iou")[2]
+        out = torch.empty(S * (4 + sw + 2), dtype=torch.int32, device=dev)
+        back = torch.empty(S + G, dtype=torch.int32, device=dev)
+
+        def select():
+            return ops.rle_select(slots, table, sizes, counts, nms_result=result, cols=cols, out=out, back=back)
+
+        whole = torch.cat([table.reshape(-1), slots.reshape(-1)])      # the set's bytes, table and slots
+        twin = torch.empty_like(whole)
+
+        def copy():
+            twin.copy_(whole)
+
+        def entry_path():
+            """uploaded set -> compacted slots ready for the decode, all on the device"""
+            res = ops.rle_nms(slots, table, sizes, counts, scores, thr, "iou")[2]
+            o = ops.rle_select(slots, table, sizes, counts, nms_result=res, cols=cols, out=out, back=back)
+            torch.cuda.synchronize()
+            return o
+
+        def host_path():
+            """what there was before the entry: the kept lists read back, the kept rows re-packed with numpy, uploaded"""
+            out_idx, out_n, _ = ops.rle_nms(slots, table, sizes, counts, scores, thr, "iou")
+            out_idx, out_n = out_idx.cpu().numpy(), out_n.cpu().numpy()
+            rows = np.concatenate([g * n + np.sort(out_idx[g * n:g * n + int(out_n[g])]) for g in range(G)])
+            flat = torch.from_numpy(np.concatenate([table_h[rows].reshape(-1), slots_h[rows].reshape(-1)])).pin_memory()
+            d = flat.to(dev, non_blocking=True)
+            torch.cuda.synchronize()
+            return rows, ops.rle_split(d, len(rows), sw), [int(v) for v in out_n]
+
+        cs, ct, cc, src, k = (x.cpu().numpy() for x in entry_path())
+        rows, (hs, ht), kept = host_path()
+        hs, ht = hs.cpu().numpy(), ht.cpu().numpy()
+        assert k.tolist() == kept, "the entry and the host path keep different counts"
+        at = 0
+        for g in range(G):      # the survivors' rows, and the words their rows define, are those of the host's gather
+            e, kg = g * n, kept[g]
+            assert np.array_equal(src[e:e + kg] + e, rows[at:at + kg]) and np.array_equal(ct[e:e + kg], ht[at:at + kg])
+            for p in range(kg):
+                w = int(ct[e + p, 0])
+                assert np.array_equal(cs[e + p, :w], hs[at + p, :w])
+            assert (src[e + kg:e + n] == -1).all() and (ct[e + kg:e + n] == (1, 0, 0, 0)).all() and (cs[e + kg:e + n, 0] == H * W).all()
+            at += kg
+        moved = int(ct[src >= 0][:, 0].sum()) + 4 * int((src >= 0).sum())
+        r = {"entries": S, "kept": int(k.sum()), "slot_words": sw, "set_bytes": int(whole.numel()) * 4, "words_moved": moved,
+             "rle_select": device_spread_behind(select, reps, head), "device_copy_of_the_set": device_spread_behind(copy, reps, head),
+             "rle_select_at_the_hosts_pace": device_spread(select, reps),
+             "nms_select_to_ready_ms": round(host_ms(entry_path, reps), 3),
+             "nms_read_back_numpy_repack_upload_ms": round(host_ms(host_path, reps), 3)}
+        r["select_over_copy"] = round(r["rle_select"]["median_us"] / r["device_copy_of_the_set"]["median_us"], 2)
+        r["host_path_over_entry"] = round(r["nms_read_back_numpy_repack_upload_ms"] / r["nms_select_to_ready_ms"], 2)
+        rec[f"{n}_proposals"] = r
+    return rec
+
+
 def polygons_leg(dev, reps, cli_images):
     import shutil
     import subprocess
@@ -490,6 +593,8 @@ def main():
                     help="measure rle_merge against decode -> vote -> encode; writes profiles/rle_merge_bench.json")
     ap.add_argument("--nms", action="store_true",
                     help="measure rle_nms against the rle_match matrix walked in numpy; writes profiles/rle_nms_bench.json")
+    ap.add_argument("--select", action="store_true",
+                    help="measure rle_select against a device copy and the host re-pack; writes profiles/rle_select_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
@@ -508,6 +613,14 @@ def main():
     if args.nms:
         out = {"nms": nms_leg(dev, args.reps), "device": torch.cuda.get_device_name(0)}
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_nms_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
+    if args.select:
+        out = {"select": select_leg(dev, args.reps), "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_select_bench.json")
         with open(path, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
