@@ -1160,7 +1160,9 @@ int hgl_launch_ln256_pe_split(float* x, const float* w, const float* b, const fl
   return hgl_check_launch("ln256_pe_split");
 }
 int hgl_launch_hyper_logits(const float* u2, const float* hyper, int P, int g, int row0, float* low_res, hipStream_t st) {
-  HGL_REQUIRE((4 * g) % 32 == 0, "hyper_logits: 4*grid must be a multiple of 32 (grid %d)", g);
+  // (a wave covers 8 consecutive X per step and the four waves stride by 32: any row length that is a multiple of 8 is covered
+  // exactly, the last step of a row by fewer waves)
+  HGL_REQUIRE((4 * g) % 8 == 0, "hyper_logits: 4*grid must be a multiple of 8 (grid %d)", g);
   hipLaunchKernelGGL(hyper_logits_kernel, dim3(4 * g, P), dim3(256), 0, st, u2, hyper, g, row0, low_res);
   return hgl_check_launch("hyper_logits");
 }
