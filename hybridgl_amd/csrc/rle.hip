@@ -26,7 +26,7 @@
 // plane (bit p % 32 of word p / 32; whenever the counts do not fit but ceil(H*W/32) words do), 2 = neither fits, nothing
 // written, 3 = the index is outside [0, N), nothing read or written.  Words beyond what the form defines keep their bytes.
 #include "hgl_common.h"
-#include "rle_group.h"      // RleTiles, RleGroup, RleOne, rle_group_plan, rle_match_plan, rle_merge_plan, rle_nms_plan: plain C++, shared with the sanitizer harnesses
+#include "rle_group.h"      // RleTiles, RleGroup, RleOne, RleSet and the rle_*_plan functions: plain C++, shared with the sanitizer harnesses
 #include "rle_scan.h"       // RLE_THREADS, rle_block_sum, rle_group_find, rle_counts_chunk: shared with rle_poly.hip
 #include "nms_walk.h"       // nms_before, nms_resolve_block, nms_emit_block: shared with sam_nms.hip
 
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned lo
 //      decoder keeps no plane anywhere.
 //   D. rle_plane_kernel<GEO> / rle_iou_kernel   for the IoU the words of both sets go to the workspace, one thread per word, and
 //      one workgroup per entry pop-counts a & b and a | b: padding bits are 0 on both sides, no mask is expanded to bytes.  GEO:
-//      RlePlaneOne (the pairwise IoU: one size) or RlePlaneGroup (the match below: the block finds its image by a search).
+//      RlePlaneOne (the pairwise IoU: one size) or RleSet (the match below: the block finds its image by a search).
 
 // the slot of an entry holds a mask (include/hybridgl.h: anything else is code 2)
 __device__ __forceinline__ bool rle_entry_usable(int n, int form, long long slot_words, unsigned plane_words) {
@@ -267,7 +267,8 @@ __device__ __forceinline__ void rle_box_join(unsigned a, unsigned b, unsigned H,
 }
 
 // The size of the image that owns entry s: looked up in a group, the image itself in a call of one.
-__device__ __forceinline__ void rle_entry_size(const RleGroup& grp, int s, int& H, int& W) {
+template <class GRP>      // RleGroup or RleSet
+__device__ __forceinline__ void rle_entry_size(const GRP& grp, int s, int& H, int& W) {
   const int g = rle_group_find(grp.first, grp.G, s);
   H = grp.H[g], W = grp.W[g];
 }
@@ -295,7 +296,7 @@ __device__ __forceinline__ RleImage rle_tile_image(const RleOne& one, unsigned) 
 
 // boxes [S,4] (BOX only) receives the inclusive XYXY box of the mask the entry decodes to (batched_mask_to_box,
 // utils/amg.py:303-346; zeros for an empty mask and for code 2), read off the runs (form 0) or the plane words (form 1) in the
-// pass that scans them.  GEO: RleGroup or RleOne.
+// pass that scans them.  GEO: RleGroup, RleSet or RleOne.
 template <bool BOX, class GEO>
 __global__ __launch_bounds__(RLE_THREADS) void rle_starts_kernel(const uint32_t* __restrict__ slots, long long slot_words,
                                                                  const int32_t* __restrict__ table, const GEO geo,
@@ -471,7 +472,7 @@ __device__ __forceinline__ RlePlaneBlock rle_plane_block(const RlePlaneOne& one,
   const int s = (int)(blk / (unsigned)one.q_tiles);
   return {s, one.H, one.W, one.HW64, blk % (unsigned)one.q_tiles, (size_t)s * (size_t)one.W * (size_t)one.HW64};
 }
-__device__ __forceinline__ RlePlaneBlock rle_plane_block(const RlePlaneGroup& grp, unsigned blk) {
+__device__ __forceinline__ RlePlaneBlock rle_plane_block(const RleSet& grp, unsigned blk) {
   const int g = rle_group_find(grp.blk0, grp.G, blk);
   const int H = grp.H[g], W = grp.W[g], HW64 = (H + 63) / 64;
   const unsigned Q = (unsigned)W * (unsigned)HW64, q_tiles = (Q + RLE_THREADS - 1) / RLE_THREADS;
@@ -479,7 +480,7 @@ __device__ __forceinline__ RlePlaneBlock rle_plane_block(const RlePlaneGroup& gr
   return {grp.first[g] + (int)k, H, W, HW64, local % q_tiles, (size_t)grp.word0[g] + (size_t)k * Q};
 }
 
-// one thread per plane word: word q = x*HW64 + j of an entry, ceil(Q / 256) workgroups per entry.  GEO: RlePlaneOne or RlePlaneGroup.
+// one thread per plane word: word q = x*HW64 + j of an entry, ceil(Q / 256) workgroups per entry.  GEO: RlePlaneOne or RleSet.
 template <class GEO>
 __global__ __launch_bounds__(RLE_THREADS) void rle_plane_kernel(const uint32_t* __restrict__ slots, long long slot_words,
                                                                 const int32_t* __restrict__ table, const uint32_t* __restrict__ E,
@@ -630,25 +631,6 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_merge_kernel(const unsigned l
   }
   __syncthreads();      // the workgroup's own plane words are written: every thread may read any of them
   rle_write_runs(Pm, H, W, HW64, slots + (size_t)s * (size_t)slot_words, slot_words, row, red, wsum, wmax);
-}
-
-// the workspace of a merge: the source set's run starts, status and planes, then the merged planes
-struct RleMergeWs {
-  size_t E, status, plane, merged, total;
-};
-RleMergeWs rle_merge_ws(const RleMergePlan& plan, int Ssrc, long long sw) {
-  RleMergeWs w;
-  size_t p = 0;
-  w.E = p;
-  p += hgl_align_up((size_t)Ssrc * (size_t)(sw + 1) * sizeof(uint32_t), 256);
-  w.status = p;
-  p += hgl_align_up((size_t)Ssrc * 4 * sizeof(int32_t), 256);
-  w.plane = p;
-  p += hgl_align_up((size_t)plan.words_src * sizeof(unsigned long long), 256);
-  w.merged = p;
-  p += hgl_align_up((size_t)plan.words_out * sizeof(unsigned long long), 256);
-  w.total = p;
-  return w;
 }
 
 // ---- every mask of one set against every mask of another, image by image (hgl_rle_match_device).
@@ -1069,58 +1051,107 @@ __global__ __launch_bounds__(64 * RLE_SELECT_WAVES) void rle_select_move_kernel(
 
 // run starts of one set: [S] arrays of slot_words + 1 words
 size_t rle_starts_bytes(int S, long long slot_words) { return hgl_align_up((size_t)S * (size_t)(slot_words + 1) * sizeof(uint32_t), 256); }
-size_t rle_planes_bytes(int S, int H, int W) {
-  return hgl_align_up((size_t)S * (size_t)W * (size_t)((H + 63) / 64) * sizeof(unsigned long long), 256);
-}
 size_t rle_status_bytes(int S) { return hgl_align_up((size_t)S * 4 * sizeof(int32_t), 256); }
 
-// the workspace of a match: per side run starts, status, boxes and planes; the planes of partial counts, one per split
-struct RleMatchWs {
-  size_t E[2], status[2], boxes[2], plane[2], partial, total;
+// A set staged for the kernels that read planes, in the workspace: run starts, status, boxes (when wanted) and the column words
+// of every entry (C and D above).  rle_stage_ws carves it at *p and moves *p behind it.
+constexpr size_t RLE_NO_BOXES = ~(size_t)0;
+struct RleStageWs {
+  size_t E, status, boxes, plane;      // boxes: RLE_NO_BOXES when not wanted
 };
-RleMatchWs rle_match_ws(const RleMatchPlan& plan, int Sa, long long swa, int Sb, long long swb) {
-  RleMatchWs w;
-  size_t p = 0;
-  const int S[2] = {Sa, Sb};
-  const long long sw[2] = {swa, swb}, words[2] = {plan.words_a, plan.words_b};
-  for (int i = 0; i < 2; ++i) {
-    w.E[i] = p;
-    p += rle_starts_bytes(S[i], sw[i]);
-    w.status[i] = p;
-    p += rle_status_bytes(S[i]);
-    w.boxes[i] = p;
-    p += rle_status_bytes(S[i]);
-    w.plane[i] = p;
-    p += hgl_align_up((size_t)words[i] * sizeof(unsigned long long), 256);
-  }
-  w.partial = p;
-  p += hgl_align_up((size_t)plan.splits * (size_t)plan.pairs * sizeof(int32_t), 256);
-  w.total = p;
+RleStageWs rle_stage_ws(size_t* p, int S, long long slot_words, long long plane_words, bool boxes) {
+  RleStageWs w;
+  w.E = *p;
+  *p += rle_starts_bytes(S, slot_words);
+  w.status = *p;
+  *p += rle_status_bytes(S);
+  w.boxes = boxes ? *p : RLE_NO_BOXES;
+  if (boxes) *p += rle_status_bytes(S);
+  w.plane = *p;
+  *p += hgl_align_up((size_t)plane_words * sizeof(unsigned long long), 256);
   return w;
 }
 
-// the workspace of a mask NMS: run starts, status, boxes and planes of the one set; the planes of partial counts; order; words
+// the staged set's arrays; the two launches that fill them when the set has an entry (`blocks`: the plane kernel's grid).  SG is
+// the starts kernel's geometry and PG the plane kernel's: RleSet for both, or RleOne and RlePlaneOne.
+struct RleStaged {
+  uint32_t* E;
+  int32_t *status, *boxes;      // boxes: null when the carve has none
+  unsigned long long* plane;
+};
+template <class SG, class PG>
+RleStaged rle_stage_launch(const uint32_t* slots, long long slot_words, const int32_t* table, int S, long long blocks, const SG& sgeo,
+                           const PG& pgeo, char* base, const RleStageWs& w, hipStream_t st) {
+  const RleStaged d = {(uint32_t*)(base + w.E), (int32_t*)(base + w.status), w.boxes != RLE_NO_BOXES ? (int32_t*)(base + w.boxes) : nullptr,
+                       (unsigned long long*)(base + w.plane)};
+  if (S == 0) return d;
+  auto starts = d.boxes ? rle_starts_kernel<true, SG> : rle_starts_kernel<false, SG>;
+  hipLaunchKernelGGL(starts, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots, slot_words, table, sgeo, d.E, slot_words + 1, d.status,
+                     d.boxes);
+  hipLaunchKernelGGL(rle_plane_kernel<PG>, dim3((unsigned)blocks), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
+                     (const uint32_t*)d.E, slot_words + 1, (const int32_t*)d.status, pgeo, d.plane);
+  return d;
+}
+
+// the workspace of a pairwise IoU: either side, S entries of one size, staged without boxes
+struct RleIouWs {
+  RleStageWs side[2];
+  size_t total;
+};
+RleIouWs rle_iou_ws(int S, int H, int W, long long swa, long long swb) {
+  RleIouWs w;
+  const long long words = (long long)S * W * ((H + 63) / 64);      // <= S*H*W
+  w.total = 0;
+  w.side[0] = rle_stage_ws(&w.total, S, swa, words, false);
+  w.side[1] = rle_stage_ws(&w.total, S, swb, words, false);
+  return w;
+}
+
+// the workspace of a match: either side staged with boxes; the planes of partial counts, one per split
+struct RleMatchWs {
+  RleStageWs side[2];
+  size_t partial, total;
+};
+size_t rle_partial_bytes(const RlePairs& p) { return hgl_align_up((size_t)p.splits * (size_t)p.pairs * sizeof(int32_t), 256); }
+RleMatchWs rle_match_ws(const RleMatchPlan& plan, int Sa, long long swa, int Sb, long long swb) {
+  RleMatchWs w;
+  size_t p = 0;
+  w.side[0] = rle_stage_ws(&p, Sa, swa, plan.a.words, true);
+  w.side[1] = rle_stage_ws(&p, Sb, swb, plan.b.words, true);
+  w.partial = p;
+  w.total = p + rle_partial_bytes(plan.p);
+  return w;
+}
+
+// the workspace of a mask NMS: the one set staged with boxes; the planes of partial counts; order; suppression words
 struct RleNmsWs {
-  size_t E, status, boxes, plane, partial, order, sup, total;
+  RleStageWs set;
+  size_t partial, order, sup, total;
 };
 RleNmsWs rle_nms_ws(const RleNmsPlan& plan, int S, long long sw) {
   RleNmsWs w;
   size_t p = 0;
-  w.E = p;
-  p += rle_starts_bytes(S, sw);
-  w.status = p;
-  p += rle_status_bytes(S);
-  w.boxes = p;
-  p += rle_status_bytes(S);
-  w.plane = p;
-  p += hgl_align_up((size_t)plan.mp.words_a * sizeof(unsigned long long), 256);
+  w.set = rle_stage_ws(&p, S, sw, plan.set.words, true);
   w.partial = p;
-  p += hgl_align_up((size_t)plan.mp.splits * (size_t)plan.mp.pairs * sizeof(int32_t), 256);
+  p += rle_partial_bytes(plan.p);
   w.order = p;
   p += hgl_align_up((size_t)S * sizeof(int32_t), 256);
   w.sup = p;
-  p += hgl_align_up((size_t)plan.sup_words * sizeof(unsigned long long), 256);
-  w.total = p;
+  w.total = p + hgl_align_up((size_t)plan.sup_words * sizeof(unsigned long long), 256);
+  return w;
+}
+
+// the workspace of a merge: the source set staged without boxes, then the merged planes
+struct RleMergeWs {
+  RleStageWs src;
+  size_t merged, total;
+};
+RleMergeWs rle_merge_ws(const RleMergePlan& plan, int Ssrc, long long sw) {
+  RleMergeWs w;
+  size_t p = 0;
+  w.src = rle_stage_ws(&p, Ssrc, sw, plan.src.words, false);
+  w.merged = p;
+  w.total = p + hgl_align_up((size_t)plan.words_out * sizeof(unsigned long long), 256);
   return w;
 }
 
@@ -1231,8 +1262,7 @@ int hgl_rle_decode_group_device(const uint32_t* slots, long long slot_words, con
 
 size_t hgl_rle_iou_workspace_bytes(int S, int H, int W, long long slot_words_a, long long slot_words_b) {
   if (S <= 0 || H <= 0 || W <= 0 || slot_words_a < 0 || slot_words_b < 0) return 0;
-  // per side: the planes, the run starts, the status table
-  return 2 * rle_planes_bytes(S, H, W) + rle_starts_bytes(S, slot_words_a) + rle_starts_bytes(S, slot_words_b) + 2 * rle_status_bytes(S);
+  return rle_iou_ws(S, H, W, slot_words_a, slot_words_b).total;
 }
 
 int hgl_rle_iou_device(const uint32_t* slots_a, long long slot_words_a, const int32_t* table_a, const uint32_t* slots_b,
@@ -1247,34 +1277,18 @@ int hgl_rle_iou_device(const uint32_t* slots_a, long long slot_words_a, const in
   const unsigned Q = (unsigned)W * (unsigned)HW64;
   const int q_tiles = (int)((Q + RLE_THREADS - 1) / RLE_THREADS);
   HGL_REQUIRE((long long)S * q_tiles < (1ll << 31), "rle_iou_device: too many entries (%d) for one launch", S);
-  if (!ws || ws_bytes < hgl_rle_iou_workspace_bytes(S, H, W, slot_words_a, slot_words_b)) {
+  const RleIouWs w = rle_iou_ws(S, H, W, slot_words_a, slot_words_b);
+  if (!ws || ws_bytes < w.total) {
     hgl_set_error("rle_iou_device: workspace too small");
     return HGL_EWORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)ws;
-  unsigned long long* plane[2];
-  uint32_t* E[2];
-  int32_t* status[2];
-  const uint32_t* slots[2] = {slots_a, slots_b};
-  const int32_t* table[2] = {table_a, table_b};
-  const long long sw[2] = {slot_words_a, slot_words_b};
-  for (int i = 0; i < 2; ++i) {
-    plane[i] = (unsigned long long*)p;
-    p += rle_planes_bytes(S, H, W);
-    E[i] = (uint32_t*)p;
-    p += rle_starts_bytes(S, sw[i]);
-    status[i] = (int32_t*)p;
-    p += rle_status_bytes(S);
-  }
-  for (int i = 0; i < 2; ++i) {
-    hipLaunchKernelGGL((rle_starts_kernel<false, RleOne>), dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
-                       RleOne{H, W, HW64, 0, 0}, E[i], sw[i] + 1, status[i], (int32_t*)nullptr);
-    hipLaunchKernelGGL(rle_plane_kernel<RlePlaneOne>, dim3((unsigned)(S * q_tiles)), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
-                       (const uint32_t*)E[i], sw[i] + 1, (const int32_t*)status[i], RlePlaneOne{H, W, HW64, q_tiles}, plane[i]);
-  }
-  hipLaunchKernelGGL(rle_iou_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)plane[0],
-                     (const unsigned long long*)plane[1], (const int32_t*)status[0], (const int32_t*)status[1], Q, (long long*)iu);
+  const RleOne one = {H, W, HW64, 0, 0};
+  const RlePlaneOne pone = {H, W, HW64, q_tiles};
+  const RleStaged a = rle_stage_launch(slots_a, slot_words_a, table_a, S, (long long)S * q_tiles, one, pone, (char*)ws, w.side[0], st);
+  const RleStaged b = rle_stage_launch(slots_b, slot_words_b, table_b, S, (long long)S * q_tiles, one, pone, (char*)ws, w.side[1], st);
+  hipLaunchKernelGGL(rle_iou_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)a.plane,
+                     (const unsigned long long*)b.plane, (const int32_t*)a.status, (const int32_t*)b.status, Q, (long long*)iu);
   return hgl_check_launch("rle_iou_device");
 }
 
@@ -1310,40 +1324,18 @@ int hgl_rle_match_device(const uint32_t* slots_a, long long slot_words_a, const 
   }
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)ws;
-  const uint32_t* slots[2] = {slots_a, slots_b};
-  const int32_t* table[2] = {table_a, table_b};
-  const long long sw[2] = {slot_words_a, slot_words_b}, blocks[2] = {plan.blocks_a, plan.blocks_b};
-  const int S[2] = {Sa, Sb};
-  const RlePlaneGroup* pg[2] = {&plan.pa, &plan.pb};
-  uint32_t* E[2];
-  int32_t *status[2], *boxes[2];
-  unsigned long long* plane[2];
   // a side, a kernel or a matrix without an element has no launch; otherwise six launches whatever G and the sizes are
-  for (int i = 0; i < 2; ++i) {
-    E[i] = (uint32_t*)(base + w.E[i]);
-    status[i] = (int32_t*)(base + w.status[i]);
-    boxes[i] = (int32_t*)(base + w.boxes[i]);
-    plane[i] = (unsigned long long*)(base + w.plane[i]);
-    if (S[i] == 0) continue;
-    RleGroup grp;      // what the starts kernel reads of it: the sizes and the first entries
-    memset(&grp, 0, sizeof(grp));
-    grp.G = G;
-    for (int g = 0; g < G; ++g) { grp.H[g] = pg[i]->H[g]; grp.W[g] = pg[i]->W[g]; grp.first[g] = pg[i]->first[g]; }
-    hipLaunchKernelGGL((rle_starts_kernel<true, RleGroup>), dim3((unsigned)S[i]), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
-                       grp, E[i], sw[i] + 1, status[i], boxes[i]);
-    hipLaunchKernelGGL(rle_plane_kernel<RlePlaneGroup>, dim3((unsigned)blocks[i]), dim3(RLE_THREADS), 0, st, slots[i], sw[i], table[i],
-                       (const uint32_t*)E[i], sw[i] + 1, (const int32_t*)status[i], *pg[i], plane[i]);
-  }
+  const RleStaged a = rle_stage_launch(slots_a, slot_words_a, table_a, Sa, plan.a.blocks, plan.a, plan.a, base, w.side[0], st);
+  const RleStaged b = rle_stage_launch(slots_b, slot_words_b, table_b, Sb, plan.b.blocks, plan.b, plan.b, base, w.side[1], st);
+  const RlePairs& pr = plan.p;
   int32_t* partial = (int32_t*)(base + w.partial);
-  if (plan.tiles > 0)      // tiles * splits <= max(tiles, RLE_MATCH_BLOCKS + tiles) < 2^31 + 1024
-    hipLaunchKernelGGL(rle_match_tile_kernel, dim3((unsigned)(plan.tiles * plan.splits)), dim3(RLE_THREADS), 0, st,
-                       (const unsigned long long*)plane[0], (const unsigned long long*)plane[1], (const int32_t*)status[0],
-                       (const int32_t*)status[1], (const int32_t*)boxes[0], (const int32_t*)boxes[1], plan.m, plan.splits, plan.pairs,
-                       0, partial);
+  if (pr.tiles > 0)      // tiles * splits <= max(tiles, RLE_MATCH_BLOCKS + tiles) < 2^31 + 1024
+    hipLaunchKernelGGL(rle_match_tile_kernel, dim3((unsigned)(pr.tiles * pr.splits)), dim3(RLE_THREADS), 0, st,
+                       (const unsigned long long*)a.plane, (const unsigned long long*)b.plane, (const int32_t*)a.status,
+                       (const int32_t*)b.status, (const int32_t*)a.boxes, (const int32_t*)b.boxes, pr.m, pr.splits, pr.pairs, 0, partial);
   if (Sa + Sb > 0)
-    hipLaunchKernelGGL(rle_match_best_kernel, dim3((unsigned)Sa + (unsigned)Sb), dim3(64), 0, st, (const int32_t*)status[0],
-                       (const int32_t*)status[1], crowd_b, plan.m, plan.splits, plan.pairs, (const int32_t*)partial, inter, match_a,
-                       match_b);
+    hipLaunchKernelGGL(rle_match_best_kernel, dim3((unsigned)Sa + (unsigned)Sb), dim3(64), 0, st, (const int32_t*)a.status,
+                       (const int32_t*)b.status, crowd_b, pr.m, pr.splits, pr.pairs, (const int32_t*)partial, inter, match_a, match_b);
   return hgl_check_launch("rle_match_device");
 }
 
@@ -1377,33 +1369,22 @@ int hgl_rle_nms_device(const uint32_t* slots, long long slot_words, const int32_
   }
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)ws;
-  uint32_t* E = (uint32_t*)(base + w.E);
-  int32_t* status = (int32_t*)(base + w.status);
-  int32_t* boxes = (int32_t*)(base + w.boxes);
-  unsigned long long* plane = (unsigned long long*)(base + w.plane);
   int32_t* partial = (int32_t*)(base + w.partial);
   int32_t* order = (int32_t*)(base + w.order);
   unsigned long long* sup = (unsigned long long*)(base + w.sup);
-  const RleMatchPlan& mp = plan.mp;
-  RleGroup grp;      // what the starts kernel reads of it: the sizes and the first entries
-  memset(&grp, 0, sizeof(grp));
-  grp.G = G;
-  for (int g = 0; g < G; ++g) { grp.H[g] = mp.pa.H[g]; grp.W[g] = mp.pa.W[g]; grp.first[g] = mp.pa.first[g]; }
+  const RlePairs& pr = plan.p;
   // six launches whatever G and the sizes are (S > 0: every one of them has a block)
-  hipLaunchKernelGGL((rle_starts_kernel<true, RleGroup>), dim3((unsigned)S), dim3(RLE_THREADS), 0, st, slots, slot_words, table, grp, E,
-                     slot_words + 1, status, boxes);
-  hipLaunchKernelGGL(rle_plane_kernel<RlePlaneGroup>, dim3((unsigned)mp.blocks_a), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
-                     (const uint32_t*)E, slot_words + 1, (const int32_t*)status, mp.pa, plane);
-  hipLaunchKernelGGL(rle_match_tile_kernel, dim3((unsigned)(mp.tiles * mp.splits)), dim3(RLE_THREADS), 0, st,
-                     (const unsigned long long*)plane, (const unsigned long long*)plane, (const int32_t*)status, (const int32_t*)status,
-                     (const int32_t*)boxes, (const int32_t*)boxes, mp.m, mp.splits, mp.pairs, 1, partial);
-  hipLaunchKernelGGL(rle_nms_rank_kernel, dim3((unsigned)((S + RLE_THREADS - 1) / RLE_THREADS)), dim3(RLE_THREADS), 0, st,
-                     (const int32_t*)status, scores, plan.n, order, result);
+  const RleStaged d = rle_stage_launch(slots, slot_words, table, S, plan.set.blocks, plan.set, plan.set, base, w.set, st);
+  const int32_t* status = d.status;
+  hipLaunchKernelGGL(rle_match_tile_kernel, dim3((unsigned)(pr.tiles * pr.splits)), dim3(RLE_THREADS), 0, st,
+                     (const unsigned long long*)d.plane, (const unsigned long long*)d.plane, status, status, (const int32_t*)d.boxes,
+                     (const int32_t*)d.boxes, pr.m, pr.splits, pr.pairs, 1, partial);
+  hipLaunchKernelGGL(rle_nms_rank_kernel, dim3((unsigned)((S + RLE_THREADS - 1) / RLE_THREADS)), dim3(RLE_THREADS), 0, st, status, scores,
+                     plan.n, order, result);
   const long long waves = RLE_THREADS / 64;
   hipLaunchKernelGGL(rle_nms_words_kernel, dim3((unsigned)((plan.sup_words + waves - 1) / waves)), dim3(RLE_THREADS), 0, st,
-                     (const int32_t*)status, (const int32_t*)order, (const int32_t*)partial, plan.n, mp.splits, mp.pairs, plan.sup_words,
-                     thr, metric, sup);
-  hipLaunchKernelGGL(rle_nms_walk_kernel, dim3((unsigned)G), dim3(RLE_THREADS), 0, st, (const int32_t*)status, (const int32_t*)order,
+                     status, (const int32_t*)order, (const int32_t*)partial, plan.n, pr.splits, pr.pairs, plan.sup_words, thr, metric, sup);
+  hipLaunchKernelGGL(rle_nms_walk_kernel, dim3((unsigned)G), dim3(RLE_THREADS), 0, st, status, (const int32_t*)order,
                      (const unsigned long long*)sup, plan.n, out_idx, out_n, result);
   return hgl_check_launch("rle_nms_device");
 }
@@ -1463,24 +1444,11 @@ int hgl_rle_merge_device(const uint32_t* slots_src, long long slot_words_src, co
   }
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)ws;
-  uint32_t* E = (uint32_t*)(base + w.E);
-  int32_t* status_src = (int32_t*)(base + w.status);
-  unsigned long long* plane = (unsigned long long*)(base + w.plane);
-  unsigned long long* merged = (unsigned long long*)(base + w.merged);
-  if (Ssrc > 0) {
-    RleGroup grp;      // what the starts kernel reads of it: the sizes and the first entries
-    memset(&grp, 0, sizeof(grp));
-    grp.G = G;
-    for (int g = 0; g < G; ++g) { grp.H[g] = plan.src.H[g]; grp.W[g] = plan.src.W[g]; grp.first[g] = plan.src.first[g]; }
-    hipLaunchKernelGGL((rle_starts_kernel<false, RleGroup>), dim3((unsigned)Ssrc), dim3(RLE_THREADS), 0, st, slots_src, slot_words_src,
-                       table_src, grp, E, slot_words_src + 1, status_src, (int32_t*)nullptr);
-    HGL_TRY(hgl_check_launch("rle_merge_device"));
-    hipLaunchKernelGGL(rle_plane_kernel<RlePlaneGroup>, dim3((unsigned)plan.blocks_src), dim3(RLE_THREADS), 0, st, slots_src,
-                       slot_words_src, table_src, (const uint32_t*)E, slot_words_src + 1, (const int32_t*)status_src, plan.src, plane);
-    HGL_TRY(hgl_check_launch("rle_merge_device"));
-  }
-  hipLaunchKernelGGL(rle_merge_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)plane,
-                     (const int32_t*)status_src, plan.m, members, M, member_offsets, bounds, merged, slots, slot_words, table, status);
+  // three launches whatever G, S, M and the sizes are; two fewer for a source set without an entry
+  const RleStaged src = rle_stage_launch(slots_src, slot_words_src, table_src, Ssrc, plan.src.blocks, plan.src, plan.src, base, w.src, st);
+  hipLaunchKernelGGL(rle_merge_kernel, dim3((unsigned)S), dim3(RLE_THREADS), 0, st, (const unsigned long long*)src.plane,
+                     (const int32_t*)src.status, plan.m, members, M, member_offsets, bounds, (unsigned long long*)(base + w.merged), slots,
+                     slot_words, table, status);
   return hgl_check_launch("rle_merge_device");
 }
 

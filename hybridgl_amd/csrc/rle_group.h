@@ -1,8 +1,12 @@
-// The geometry of the RLE entries (csrc/rle.hip): the tiling of an image, shared by the encoder and the decoder, and what the host
-// works out of a decode call's image rows (rle_group_plan), of a match call's (rle_match_plan) and of a merge call's
-// (rle_merge_plan), of a mask NMS call's (rle_nms_plan) and of a compaction's (rle_select_plan) and hands to the kernels by value,
-// and likewise of a polygon call's (rle_poly_plan, csrc/rle_poly.hip).  Plain C++ without a HIP construct: the .hip files include
-// it, and so do the sanitizer harnesses tests/native/rle_group_sanitize.cpp, rle_match_sanitize.cpp, rle_merge_sanitize.cpp,
+// The geometry of the RLE entries (csrc/rle.hip, csrc/rle_poly.hip): the tiling of an image, shared by the encoder and the
+// decoder; the checks every plan makes of its caller's image rows (rle_plan_count, rle_plan_size, rle_plan_entries); RleSet, the
+// one description of "a set of entries that belongs to G images" and of its bit planes in the workspace, built image by image
+// through rle_set_add; and the plans -- what the host works out of a decode call's rows (rle_group_plan), a match call's
+// (rle_match_plan), a merge call's (rle_merge_plan), a mask NMS call's (rle_nms_plan), a compaction's (rle_select_plan) and a
+// polygon call's (rle_poly_plan).  A plan holds the RleSets the plane kernel stages and the structs the other kernels take by
+// value (RleGroup, RleMatch, RleMerge, RleNms, RleSelect, RlePoly: their layout is the kernels' and stays); what such a struct
+// repeats of a set is copied out of the set in one place.  Plain C++ without a HIP construct: the .hip files include it, and so
+// do the sanitizer harnesses tests/native/rle_group_sanitize.cpp, rle_match_sanitize.cpp, rle_merge_sanitize.cpp,
 // rle_nms_sanitize.cpp and rle_select_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
@@ -26,6 +30,37 @@ static inline RleTiles rle_tiles(long long H, long long W, uintptr_t base) {
 
 constexpr int RLE_GROUP_MAX = 64;
 
+// ---- what every plan checks of its rows.  A plan and a check return 0, or -1 with the reason in why.
+#define RLE_PLAN_REQUIRE(cond, ...)         \
+  do {                                      \
+    if (!(cond)) {                          \
+      snprintf(why, why_cap, __VA_ARGS__);  \
+      return -1;                            \
+    }                                       \
+  } while (0)
+
+static inline int rle_plan_count(int G, char* why, size_t why_cap) {
+  RLE_PLAN_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
+  return 0;
+}
+static inline int rle_plan_size(int g, long long H, long long W, char* why, size_t why_cap) {
+  RLE_PLAN_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
+                   "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
+  return 0;
+}
+// the entries e .. e_next of image g in a set of S: from 0 to S without a step back.  `side` ("", "A ", "source " ..) and `total`
+// ("S", "Sa", "Ssrc" ..) are what the callers' messages differ in.
+static inline int rle_plan_entries(int g, long long e, long long e_next, int S, const char* side, const char* total, char* why,
+                                   size_t why_cap) {
+  RLE_PLAN_REQUIRE(e >= 0 && e <= e_next && e_next <= (long long)S && (g > 0 || e == 0),
+                   "image %d: %sentries %lld .. %lld (rows must not decrease, from 0 to %s = %d)", g, side, e, e_next, total, S);
+  return 0;
+}
+// column `col` of the row after `row` (image g of G, `stride` numbers to a row), or S behind the last row: where g's entries end
+static inline long long rle_row_next(const int64_t* row, int stride, int col, int g, int G, int S) {
+  return g + 1 < G ? row[stride + col] : (long long)S;
+}
+
 struct RleGroup {
   long long off[RLE_GROUP_MAX];                 // byte offset of the image's first entry in masks
   int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
@@ -41,34 +76,24 @@ struct RleGroup {
 // is a multiple of 4 and whose first byte (masks + offset) is 4-byte aligned: H*W is then a multiple of 4 and every entry is.
 static inline int rle_group_plan(const int64_t* images, int G, int S, uintptr_t masks, long long masks_bytes, RleGroup* grp,
                                  long long* tiles_out, char* why, size_t why_cap) {
-#define RLE_GROUP_REQUIRE(cond, ...)        \
-  do {                                      \
-    if (!(cond)) {                          \
-      snprintf(why, why_cap, __VA_ARGS__);  \
-      return -1;                            \
-    }                                       \
-  } while (0)
-  RLE_GROUP_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
+  if (rle_plan_count(G, why, why_cap)) return -1;
   memset(grp, 0, sizeof(*grp));
   grp->G = G;
   long long tiles = 0;
   long long lo[RLE_GROUP_MAX], hi[RLE_GROUP_MAX];      // the byte extent [lo, hi) of every image
   for (int g = 0; g < G; ++g) {
-    const long long H = images[4 * g], W = images[4 * g + 1], e = images[4 * g + 2], o = images[4 * g + 3];
-    const long long e_next = g + 1 < G ? images[4 * (g + 1) + 2] : (long long)S;
-    RLE_GROUP_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
-                      "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
-    RLE_GROUP_REQUIRE(e >= 0 && e <= e_next && e_next <= (long long)S && (g > 0 || e == 0),
-                      "image %d: entries %lld .. %lld (rows must not decrease, from 0 to S = %d)", g, e, e_next, S);
+    const int64_t* r = images + 4 * g;
+    const long long H = r[0], W = r[1], e = r[2], o = r[3], e_next = rle_row_next(r, 4, 2, g, G, S);
+    if (rle_plan_size(g, H, W, why, why_cap) || rle_plan_entries(g, e, e_next, S, "", "S", why, why_cap)) return -1;
     const long long n = e_next - e;
-    RLE_GROUP_REQUIRE(n * H * W < (1ll << 31), "image %d too large (n*H*W must be < 2^31)", g);
-    RLE_GROUP_REQUIRE(o >= 0 && o <= masks_bytes && n * H * W <= masks_bytes - o,
-                      "image %d: bytes %lld .. %lld lie outside the %lld of masks", g, o, o + n * H * W, masks_bytes);
+    RLE_PLAN_REQUIRE(n * H * W < (1ll << 31), "image %d too large (n*H*W must be < 2^31)", g);
+    RLE_PLAN_REQUIRE(o >= 0 && o <= masks_bytes && n * H * W <= masks_bytes - o,
+                     "image %d: bytes %lld .. %lld lie outside the %lld of masks", g, o, o + n * H * W, masks_bytes);
     lo[g] = o;
     hi[g] = o + n * H * W;
     for (int f = 0; f < g; ++f)
-      RLE_GROUP_REQUIRE(lo[g] == hi[g] || lo[f] == hi[f] || hi[f] <= lo[g] || hi[g] <= lo[f],
-                        "the extents of images %d and %d overlap", f, g);
+      RLE_PLAN_REQUIRE(lo[g] == hi[g] || lo[f] == hi[f] || hi[f] <= lo[g] || hi[g] <= lo[f],
+                       "the extents of images %d and %d overlap", f, g);
     const RleTiles t = rle_tiles(H, W, masks + (uintptr_t)o);
     grp->off[g] = o;
     grp->H[g] = (int)H;
@@ -77,11 +102,10 @@ static inline int rle_group_plan(const int64_t* images, int G, int S, uintptr_t 
     grp->tile0[g] = (unsigned)tiles;
     if (t.wide) grp->wide |= 1ull << g;
     tiles += n * t.col_tiles * t.row_tiles;
-    RLE_GROUP_REQUIRE(tiles < (1ll << 31), "too many entries (%d) for one launch", S);
+    RLE_PLAN_REQUIRE(tiles < (1ll << 31), "too many entries (%d) for one launch", S);
   }
   *tiles_out = tiles;
   return 0;
-#undef RLE_GROUP_REQUIRE
 }
 
 // A call of one image whose first entry lies at `masks` and which owns every entry: what the kernels take in place of RleGroup
@@ -90,18 +114,40 @@ struct RleOne {
   int H, W, HW64, col_tiles, row_tiles;      // rle_tiles' (the rows kernel reads the last two; 0 for a caller of the starts kernel alone)
 };
 
-// What a block of the plane kernel needs of the image that owns it (hgl_rle_iou_device: one image, hgl_rle_match_device: a
-// group): the entries of an image lie back to back in the plane buffer, W * HW64 words each, 256 words per block.
+// What a block of the plane kernel needs of the image that owns it: the entries of an image lie back to back in the plane
+// buffer, W * HW64 words each, 256 words per block.  One image of one size (hgl_rle_iou_device) is four scalars ..
 struct RlePlaneOne {
   int H, W, HW64, q_tiles;
 };
-struct RlePlaneGroup {
+// .. and a set over G images is an RleSet: a side of the match, the set of the mask NMS, the source set of the merge.  The
+// starts kernel and the plane kernel take it by value.
+struct RleSet {
   int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
-  int first[RLE_GROUP_MAX];                     // the image's first entry
+  int first[RLE_GROUP_MAX + 1];                 // the image's first entry (non-decreasing, first[0] = 0); [G] = S
   unsigned blk0[RLE_GROUP_MAX];                 // its first block of the plane kernel (non-decreasing, blk0[0] = 0)
   unsigned word0[RLE_GROUP_MAX];                // the plane word its first entry starts at
+  long long words, blocks;                      // 64-bit plane words of the set; grid size of the plane kernel
   int G;
 };
+
+// Image g (the images come in order, into a zeroed set) with the entries e .. e_next, checked by rle_plan_size and
+// rle_plan_entries.  Returns 0 or which of the set's two limits the image takes it beyond: fewer than 2^32 plane words, fewer than
+// 2^31 plane blocks.  A caller with several sets adds all of them and then refuses the words before the blocks.
+constexpr int RLE_SET_WORDS = 1, RLE_SET_BLOCKS = 2;
+constexpr const char* RLE_SET_WORDS_WHY = "too many plane words for one call (sum of n*W*ceil(H/64) must be < 2^32 per side)";
+static inline int rle_set_add(RleSet* set, int g, long long H, long long W, long long e, long long e_next) {
+  const long long Q = W * ((H + 63) / 64), q_tiles = (Q + 255) / 256;      // Q <= H*W < 2^31
+  set->H[g] = (int)H;
+  set->W[g] = (int)W;
+  set->first[g] = (int)e;
+  set->first[g + 1] = (int)e_next;      // S in the end
+  set->blk0[g] = (unsigned)set->blocks;
+  set->word0[g] = (unsigned)set->words;
+  set->words += (e_next - e) * Q;
+  set->blocks += (e_next - e) * q_tiles;
+  set->G = g + 1;
+  return (set->words < (1ll << 32) ? 0 : RLE_SET_WORDS) | (set->blocks < (1ll << 31) ? 0 : RLE_SET_BLOCKS);
+}
 
 // ---- hgl_rle_match_device: every mask of set A against every mask of set B, image by image.  A workgroup of the tile kernel
 // owns RLE_MATCH_TA x RLE_MATCH_TB pairs of one image and walks the plane words RLE_MATCH_CHUNK at a time.
@@ -120,90 +166,82 @@ struct RleMatch {
   int G;
 };
 
-struct RleMatchPlan {
+// The pairs of two sets over the same images (or of one set with itself): tiles and partial counts.
+struct RlePairs {
   RleMatch m;
-  RlePlaneGroup pa, pb;
-  long long tiles, blocks_a, blocks_b;      // grid sizes: tile kernel, plane kernel of either side
-  long long words_a, words_b;               // 64-bit plane words of either side
-  long long pairs;                          // sum of na*nb: the elements of one plane of partial counts
-  int splits;                               // workgroups per tile, 1 .. RLE_MATCH_SPLITS_MAX: ceil(RLE_MATCH_BLOCKS / tiles)
+  long long tiles;      // grid size of the tile kernel, per split
+  long long pairs;      // sum of na*nb: the elements of one plane of partial counts
+  int splits;           // workgroups per tile, 1 .. RLE_MATCH_SPLITS_MAX: ceil(RLE_MATCH_BLOCKS / tiles)
+};
+// image g brings na x nb pairs (into a zeroed *p, in order): its first tile and its first partial count
+static inline void rle_pairs_add(RlePairs* p, int g, long long na, long long nb) {
+  p->m.tile0[g] = (unsigned)p->tiles;
+  p->m.pair0[g] = p->pairs;
+  p->pairs += na * nb;      // < 2^62
+  p->tiles += ((na + RLE_MATCH_TA - 1) / RLE_MATCH_TA) * ((nb + RLE_MATCH_TB - 1) / RLE_MATCH_TB);
+}
+// every image is in: what the kernels' struct repeats of the two sets, and the splits
+static inline void rle_pairs_close(RlePairs* p, const RleSet& a, const RleSet& b) {
+  RleMatch* m = &p->m;
+  m->G = a.G;
+  for (int g = 0; g < a.G; ++g) {
+    m->H[g] = a.H[g], m->W[g] = a.W[g];
+    m->first_a[g] = a.first[g], m->first_b[g] = b.first[g];
+    m->word0_a[g] = a.word0[g], m->word0_b[g] = b.word0[g];
+  }
+  m->first_a[a.G] = a.first[a.G], m->first_b[a.G] = b.first[a.G];
+  const long long want = p->tiles > 0 ? (RLE_MATCH_BLOCKS + p->tiles - 1) / p->tiles : 1;
+  p->splits = (int)(want < 1 ? 1 : (want > RLE_MATCH_SPLITS_MAX ? RLE_MATCH_SPLITS_MAX : want));
+}
+
+struct RleMatchPlan {
+  RlePairs p;
+  RleSet a, b;
 };
 
 // images [G,5] = (H, W, first A entry, first B entry, element offset of the image's matrix) -> *plan; 0, or -1 with the reason
 // in why.  inter_elems >= 0: the caller's matrix buffer holds that many elements, every extent [off, off + na*nb) must lie inside
 // and no two may overlap.  inter_elems < 0: no matrix is wanted and column 4 is not read.  The partial counts of the tile kernel
-// are always packed image after image (pair0, plan->pairs elements per split).  Checked besides: 1 <= G <= 64; Sa, Sb >= 0; H*W < 2^31; entries from 0 to Sa / Sb without
-// a step back; Sa + Sb < 2^31; fewer than 2^31 tiles and plane blocks, fewer than 2^32 plane words per side.
+// are always packed image after image (pair0, p.pairs elements per split).  Checked besides: 1 <= G <= 64; Sa, Sb >= 0; H*W < 2^31;
+// entries from 0 to Sa / Sb without a step back; Sa + Sb < 2^31; fewer than 2^31 tiles and plane blocks, fewer than 2^32 plane
+// words per side.
 static inline int rle_match_plan(const int64_t* images, int G, int Sa, int Sb, long long inter_elems, RleMatchPlan* plan, char* why,
                                  size_t why_cap) {
-#define RLE_MATCH_REQUIRE(cond, ...)        \
-  do {                                      \
-    if (!(cond)) {                          \
-      snprintf(why, why_cap, __VA_ARGS__);  \
-      return -1;                            \
-    }                                       \
-  } while (0)
-  RLE_MATCH_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
-  RLE_MATCH_REQUIRE(Sa >= 0 && Sb >= 0 && (long long)Sa + Sb < (1ll << 31), "bad set sizes %d, %d (Sa + Sb must be < 2^31)", Sa, Sb);
+  if (rle_plan_count(G, why, why_cap)) return -1;
+  RLE_PLAN_REQUIRE(Sa >= 0 && Sb >= 0 && (long long)Sa + Sb < (1ll << 31), "bad set sizes %d, %d (Sa + Sb must be < 2^31)", Sa, Sb);
   memset(plan, 0, sizeof(*plan));
-  RleMatch* m = &plan->m;
-  m->G = plan->pa.G = plan->pb.G = G;
   const bool packed = inter_elems < 0;
   long long lo[RLE_GROUP_MAX], hi[RLE_GROUP_MAX];      // the element extent [lo, hi) of every image's matrix
   for (int g = 0; g < G; ++g) {
     const int64_t* r = images + 5 * g;
     const long long H = r[0], W = r[1], ea = r[2], eb = r[3];
-    const long long ea_next = g + 1 < G ? r[5 + 2] : (long long)Sa, eb_next = g + 1 < G ? r[5 + 3] : (long long)Sb;
-    RLE_MATCH_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
-                      "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
-    RLE_MATCH_REQUIRE(ea >= 0 && ea <= ea_next && ea_next <= (long long)Sa && (g > 0 || ea == 0),
-                      "image %d: A entries %lld .. %lld (rows must not decrease, from 0 to Sa = %d)", g, ea, ea_next, Sa);
-    RLE_MATCH_REQUIRE(eb >= 0 && eb <= eb_next && eb_next <= (long long)Sb && (g > 0 || eb == 0),
-                      "image %d: B entries %lld .. %lld (rows must not decrease, from 0 to Sb = %d)", g, eb, eb_next, Sb);
+    const long long ea_next = rle_row_next(r, 5, 2, g, G, Sa), eb_next = rle_row_next(r, 5, 3, g, G, Sb);
+    if (rle_plan_size(g, H, W, why, why_cap) || rle_plan_entries(g, ea, ea_next, Sa, "A ", "Sa", why, why_cap) ||
+        rle_plan_entries(g, eb, eb_next, Sb, "B ", "Sb", why, why_cap))
+      return -1;
     const long long na = ea_next - ea, nb = eb_next - eb, n = na * nb;      // < 2^62
     const long long o = packed ? 0 : r[4];
     if (!packed) {
-      RLE_MATCH_REQUIRE(o >= 0 && o <= inter_elems && n <= inter_elems - o,
-                        "image %d: elements %lld .. +%lld lie outside the %lld of inter", g, o, n, inter_elems);
+      RLE_PLAN_REQUIRE(o >= 0 && o <= inter_elems && n <= inter_elems - o,
+                       "image %d: elements %lld .. +%lld lie outside the %lld of inter", g, o, n, inter_elems);
       lo[g] = o;
       hi[g] = o + n;
       for (int f = 0; f < g; ++f)
-        RLE_MATCH_REQUIRE(lo[g] == hi[g] || lo[f] == hi[f] || hi[f] <= lo[g] || hi[g] <= lo[f],
-                          "the matrices of images %d and %d overlap", f, g);
+        RLE_PLAN_REQUIRE(lo[g] == hi[g] || lo[f] == hi[f] || hi[f] <= lo[g] || hi[g] <= lo[f],
+                         "the matrices of images %d and %d overlap", f, g);
     }
-    const long long HW64 = (H + 63) / 64, Q = W * HW64, q_tiles = (Q + 255) / 256;      // Q <= H*W < 2^31
-    m->off[g] = o;
-    m->H[g] = plan->pa.H[g] = plan->pb.H[g] = (int)H;
-    m->W[g] = plan->pa.W[g] = plan->pb.W[g] = (int)W;
-    m->first_a[g] = plan->pa.first[g] = (int)ea;
-    m->first_b[g] = plan->pb.first[g] = (int)eb;
-    m->word0_a[g] = plan->pa.word0[g] = (unsigned)plan->words_a;
-    m->word0_b[g] = plan->pb.word0[g] = (unsigned)plan->words_b;
-    m->tile0[g] = (unsigned)plan->tiles;
-    m->pair0[g] = plan->pairs;
-    plan->pa.blk0[g] = (unsigned)plan->blocks_a;
-    plan->pb.blk0[g] = (unsigned)plan->blocks_b;
-    plan->pairs += n;
-    plan->words_a += na * Q;
-    plan->words_b += nb * Q;
-    plan->blocks_a += na * q_tiles;
-    plan->blocks_b += nb * q_tiles;
-    plan->tiles += ((na + RLE_MATCH_TA - 1) / RLE_MATCH_TA) * ((nb + RLE_MATCH_TB - 1) / RLE_MATCH_TB);
-    RLE_MATCH_REQUIRE(plan->words_a < (1ll << 32) && plan->words_b < (1ll << 32),
-                      "too many plane words for one call (sum of n*W*ceil(H/64) must be < 2^32 per side)");
-    RLE_MATCH_REQUIRE(plan->blocks_a < (1ll << 31) && plan->blocks_b < (1ll << 31) && plan->tiles < (1ll << 31),
-                      "too many entries (%d, %d) for one launch", Sa, Sb);
+    plan->p.m.off[g] = o;
+    rle_pairs_add(&plan->p, g, na, nb);
+    const int over = rle_set_add(&plan->a, g, H, W, ea, ea_next) | rle_set_add(&plan->b, g, H, W, eb, eb_next);
+    RLE_PLAN_REQUIRE(!(over & RLE_SET_WORDS), "%s", RLE_SET_WORDS_WHY);
+    RLE_PLAN_REQUIRE(!(over & RLE_SET_BLOCKS) && plan->p.tiles < (1ll << 31), "too many entries (%d, %d) for one launch", Sa, Sb);
   }
-  m->first_a[G] = Sa;
-  m->first_b[G] = Sb;
-  const long long want = plan->tiles > 0 ? (RLE_MATCH_BLOCKS + plan->tiles - 1) / plan->tiles : 1;
-  plan->splits = (int)(want < 1 ? 1 : (want > RLE_MATCH_SPLITS_MAX ? RLE_MATCH_SPLITS_MAX : want));
+  rle_pairs_close(&plan->p, plan->a, plan->b);
   return 0;
-#undef RLE_MATCH_REQUIRE
 }
 
 // ---- hgl_rle_merge_device: every output entry is a vote over source entries of its own image.  The source set goes through the
-// plane kernel (RlePlaneGroup, as a side of the match does); a workgroup of the merge kernel owns one output entry, finds its
+// plane kernel (an RleSet, as a side of the match does); a workgroup of the merge kernel owns one output entry, finds its
 // image by its first output entry and writes the merged plane into the workspace before it writes the runs.
 struct RleMerge {
   unsigned long long word0_out[RLE_GROUP_MAX];      // the plane word the image's first output entry starts at
@@ -215,61 +253,41 @@ struct RleMerge {
 
 struct RleMergePlan {
   RleMerge m;
-  RlePlaneGroup src;
-  long long blocks_src;                 // grid size of the plane kernel
-  long long words_src, words_out;       // 64-bit plane words of the source set and of the merged set
+  RleSet src;
+  long long words_out;      // 64-bit plane words of the merged set
 };
 
 // images [G,4] = (H, W, first source entry, first output entry) -> *plan; 0, or -1 with the reason in why.  Checked: 1 <= G <= 64;
 // Ssrc, S, M >= 0; H*W < 2^31; entries from 0 to Ssrc / S without a step back; fewer than 2^31 plane blocks, fewer than 2^32 plane
 // words on either side.
 static inline int rle_merge_plan(const int64_t* images, int G, int Ssrc, int S, int M, RleMergePlan* plan, char* why, size_t why_cap) {
-#define RLE_MERGE_REQUIRE(cond, ...)        \
-  do {                                      \
-    if (!(cond)) {                          \
-      snprintf(why, why_cap, __VA_ARGS__);  \
-      return -1;                            \
-    }                                       \
-  } while (0)
-  RLE_MERGE_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
-  RLE_MERGE_REQUIRE(Ssrc >= 0 && S >= 0 && M >= 0, "bad set sizes %d, %d and %d members", Ssrc, S, M);
+  if (rle_plan_count(G, why, why_cap)) return -1;
+  RLE_PLAN_REQUIRE(Ssrc >= 0 && S >= 0 && M >= 0, "bad set sizes %d, %d and %d members", Ssrc, S, M);
   memset(plan, 0, sizeof(*plan));
   RleMerge* m = &plan->m;
-  m->G = plan->src.G = G;
   for (int g = 0; g < G; ++g) {
     const int64_t* r = images + 4 * g;
     const long long H = r[0], W = r[1], es = r[2], eo = r[3];
-    const long long es_next = g + 1 < G ? r[4 + 2] : (long long)Ssrc, eo_next = g + 1 < G ? r[4 + 3] : (long long)S;
-    RLE_MERGE_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
-                      "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
-    RLE_MERGE_REQUIRE(es >= 0 && es <= es_next && es_next <= (long long)Ssrc && (g > 0 || es == 0),
-                      "image %d: source entries %lld .. %lld (rows must not decrease, from 0 to Ssrc = %d)", g, es, es_next, Ssrc);
-    RLE_MERGE_REQUIRE(eo >= 0 && eo <= eo_next && eo_next <= (long long)S && (g > 0 || eo == 0),
-                      "image %d: output entries %lld .. %lld (rows must not decrease, from 0 to S = %d)", g, eo, eo_next, S);
-    const long long ns = es_next - es, no = eo_next - eo;
-    const long long HW64 = (H + 63) / 64, Q = W * HW64, q_tiles = (Q + 255) / 256;      // Q <= H*W < 2^31
-    m->H[g] = plan->src.H[g] = (int)H;
-    m->W[g] = plan->src.W[g] = (int)W;
-    m->first_src[g] = plan->src.first[g] = (int)es;
+    const long long es_next = rle_row_next(r, 4, 2, g, G, Ssrc), eo_next = rle_row_next(r, 4, 3, g, G, S);
+    if (rle_plan_size(g, H, W, why, why_cap) || rle_plan_entries(g, es, es_next, Ssrc, "source ", "Ssrc", why, why_cap) ||
+        rle_plan_entries(g, eo, eo_next, S, "output ", "S", why, why_cap))
+      return -1;
     m->first_out[g] = (int)eo;
-    m->word0_src[g] = plan->src.word0[g] = (unsigned)plan->words_src;
     m->word0_out[g] = (unsigned long long)plan->words_out;
-    plan->src.blk0[g] = (unsigned)plan->blocks_src;
-    plan->words_src += ns * Q;
-    plan->words_out += no * Q;
-    plan->blocks_src += ns * q_tiles;
-    RLE_MERGE_REQUIRE(plan->words_src < (1ll << 32) && plan->words_out < (1ll << 32),
-                      "too many plane words for one call (sum of n*W*ceil(H/64) must be < 2^32 per side)");
-    RLE_MERGE_REQUIRE(plan->blocks_src < (1ll << 31), "too many entries (%d) for one launch", Ssrc);
+    plan->words_out += (eo_next - eo) * (W * ((H + 63) / 64));      // as rle_set_add counts
+    const int over = rle_set_add(&plan->src, g, H, W, es, es_next);
+    RLE_PLAN_REQUIRE(!(over & RLE_SET_WORDS) && plan->words_out < (1ll << 32), "%s", RLE_SET_WORDS_WHY);
+    RLE_PLAN_REQUIRE(!(over & RLE_SET_BLOCKS), "too many entries (%d) for one launch", Ssrc);
   }
-  m->first_src[G] = Ssrc;
   m->first_out[G] = S;
+  m->G = G;      // what the kernel's struct repeats of the source set
+  for (int g = 0; g < G; ++g) m->H[g] = plan->src.H[g], m->W[g] = plan->src.W[g], m->word0_src[g] = plan->src.word0[g];
+  memcpy(m->first_src, plan->src.first, sizeof(int) * (size_t)(G + 1));
   return 0;
-#undef RLE_MERGE_REQUIRE
 }
 
 // ---- hgl_rle_nms_device: greedy suppression by mask overlap of one set against itself, image by image.  The set goes through
-// the plane kernel once and the tile kernel of the match counts it against itself (an RleMatchPlan with both sides the same,
+// the plane kernel once and the tile kernel of the match counts it against itself (RlePairs with both sides the same set,
 // restricted to the tiles that hold a pair a < b); a row of an image's suppression words is ceil(n / 64) 64-bit words, one row
 // per rank.  An image owns at most RLE_NMS_MAX entries: its pair counts are n * n int32 per split.
 constexpr int RLE_NMS_MAX = 4096;
@@ -281,50 +299,50 @@ struct RleNms {
   int G;
 };
 
+// The set of a mask NMS or of a compaction: rows of `stride` numbers that begin (H, W, first entry) -> *set.  Checked: S >= 0;
+// H*W < 2^31; entries from 0 to S without a step back; at most RLE_NMS_MAX entries per image -- of every image, before the set's
+// plane words (fewer than 2^32) are counted.  S <= 64 * 4096 then, so the set's blocks, at most words / 256 + S, need no check.
+static inline int rle_nms_set(const int64_t* images, int stride, int G, int S, RleSet* set, char* why, size_t why_cap) {
+  RLE_PLAN_REQUIRE(S >= 0, "%d entries", S);
+  for (int g = 0; g < G; ++g) {
+    const int64_t* r = images + stride * g;
+    const long long e = r[2], e_next = rle_row_next(r, stride, 2, g, G, S);
+    if (rle_plan_size(g, r[0], r[1], why, why_cap) || rle_plan_entries(g, e, e_next, S, "", "S", why, why_cap)) return -1;
+    RLE_PLAN_REQUIRE(e_next - e <= RLE_NMS_MAX, "image %d owns %lld entries (at most %d)", g, e_next - e, RLE_NMS_MAX);
+  }
+  memset(set, 0, sizeof(*set));
+  for (int g = 0; g < G; ++g) {
+    const int64_t* r = images + stride * g;
+    RLE_PLAN_REQUIRE(!(rle_set_add(set, g, r[0], r[1], r[2], rle_row_next(r, stride, 2, g, G, S)) & RLE_SET_WORDS), "%s", RLE_SET_WORDS_WHY);
+  }
+  return 0;
+}
+
 struct RleNmsPlan {
-  RleMatchPlan mp;           // the set against itself: m.first_a == m.first_b, pa == pb, tiles / splits / pairs of the full squares
+  RleSet set;
+  RlePairs p;                // the set against itself: m.first_a == m.first_b, tiles / splits / pairs of the full squares
   RleNms n;
   long long sup_words;       // 64-bit suppression words: sum of n_g * ceil(n_g / 64)
 };
 
-// images [G,3] = (H, W, first entry) -> *plan; 0, or -1 with the reason in why.  Checked: 1 <= G <= 64; S >= 0; H*W < 2^31; entries
-// from 0 to S without a step back; at most RLE_NMS_MAX entries per image; and what rle_match_plan checks of the set against
-// itself (fewer than 2^32 plane words, fewer than 2^31 blocks).
+// images [G,3] = (H, W, first entry) -> *plan; 0, or -1 with the reason in why.  Checked: 1 <= G <= 64 and what rle_nms_set checks.
 static inline int rle_nms_plan(const int64_t* images, int G, int S, RleNmsPlan* plan, char* why, size_t why_cap) {
-#define RLE_NMS_REQUIRE(cond, ...)          \
-  do {                                      \
-    if (!(cond)) {                          \
-      snprintf(why, why_cap, __VA_ARGS__);  \
-      return -1;                            \
-    }                                       \
-  } while (0)
-  RLE_NMS_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
-  RLE_NMS_REQUIRE(S >= 0, "%d entries", S);
-  int64_t rows[5 * RLE_GROUP_MAX];      // the match's rows: both sides the same set, no matrix
-  for (int g = 0; g < G; ++g) {
-    const long long H = images[3 * g], W = images[3 * g + 1], e = images[3 * g + 2];
-    const long long e_next = g + 1 < G ? images[3 * (g + 1) + 2] : (long long)S;
-    RLE_NMS_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
-                    "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
-    RLE_NMS_REQUIRE(e >= 0 && e <= e_next && e_next <= (long long)S && (g > 0 || e == 0),
-                    "image %d: entries %lld .. %lld (rows must not decrease, from 0 to S = %d)", g, e, e_next, S);
-    RLE_NMS_REQUIRE(e_next - e <= RLE_NMS_MAX, "image %d owns %lld entries (at most %d)", g, e_next - e, RLE_NMS_MAX);
-    rows[5 * g] = H, rows[5 * g + 1] = W, rows[5 * g + 2] = rows[5 * g + 3] = e, rows[5 * g + 4] = 0;
-  }
-  if (rle_match_plan(rows, G, S, S, -1, &plan->mp, why, why_cap) != 0) return -1;      // S <= 64 * 4096: 2 S < 2^31
+  if (rle_plan_count(G, why, why_cap) || rle_nms_set(images, 3, G, S, &plan->set, why, why_cap)) return -1;
+  memset(&plan->p, 0, sizeof(plan->p));
   memset(&plan->n, 0, sizeof(plan->n));
   plan->n.G = G;
   plan->sup_words = 0;
   for (int g = 0; g < G; ++g) {
-    const long long n = plan->mp.m.first_a[g + 1] - plan->mp.m.first_a[g];
-    plan->n.first[g] = plan->mp.m.first_a[g];
-    plan->n.pair0[g] = plan->mp.m.pair0[g];
+    const long long n = plan->set.first[g + 1] - plan->set.first[g];
+    rle_pairs_add(&plan->p, g, n, n);      // at most 64 * 128 * 64 tiles
+    plan->n.first[g] = plan->set.first[g];
+    plan->n.pair0[g] = plan->p.m.pair0[g];
     plan->n.sup0[g] = plan->sup_words;
     plan->sup_words += n * ((n + 63) / 64);      // <= 64 * 4096 * 64
   }
   plan->n.first[G] = S;
+  rle_pairs_close(&plan->p, plan->set, plan->set);
   return 0;
-#undef RLE_NMS_REQUIRE
 }
 
 // ---- hgl_rle_select_device: the kept entries of every image moved to the front of the image's range of a second set, in stored
@@ -354,47 +372,37 @@ struct RleSelectPlan {
 static inline int rle_select_plan(const int64_t* images, int G, int S, long long slot_words, int C, bool has_keep, bool has_nms,
                                   uintptr_t slots, uintptr_t out_slots, uintptr_t table, uintptr_t out_table, RleSelectPlan* plan,
                                   char* why, size_t why_cap) {
-#define RLE_SELECT_REQUIRE(cond, ...)       \
-  do {                                      \
-    if (!(cond)) {                          \
-      snprintf(why, why_cap, __VA_ARGS__);  \
-      return -1;                            \
-    }                                       \
-  } while (0)
-  RLE_SELECT_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
-  RLE_SELECT_REQUIRE(slot_words >= 0 && slot_words < (1ll << 31), "slot_words %lld (0 .. 2^31 - 1)", slot_words);
-  RLE_SELECT_REQUIRE(C >= 0 && C <= RLE_SELECT_COLS_MAX, "%d side columns (0 .. %d)", C, RLE_SELECT_COLS_MAX);
-  RLE_SELECT_REQUIRE(has_keep != has_nms, "exactly one of keep and nms_result selects the entries (%s given)", has_keep ? "both" : "neither");
-  int64_t rows[3 * RLE_GROUP_MAX];
-  for (int g = 0; g < G; ++g) rows[3 * g] = images[4 * g], rows[3 * g + 1] = images[4 * g + 1], rows[3 * g + 2] = images[4 * g + 2];
-  RleNmsPlan nms;
-  if (rle_nms_plan(rows, G, S, &nms, why, why_cap) != 0) return -1;
-  RLE_SELECT_REQUIRE(S == 0 || slot_words >= 1, "slot_words 0: a placeholder needs one word");
+  if (rle_plan_count(G, why, why_cap)) return -1;
+  RLE_PLAN_REQUIRE(slot_words >= 0 && slot_words < (1ll << 31), "slot_words %lld (0 .. 2^31 - 1)", slot_words);
+  RLE_PLAN_REQUIRE(C >= 0 && C <= RLE_SELECT_COLS_MAX, "%d side columns (0 .. %d)", C, RLE_SELECT_COLS_MAX);
+  RLE_PLAN_REQUIRE(has_keep != has_nms, "exactly one of keep and nms_result selects the entries (%s given)", has_keep ? "both" : "neither");
+  RleSet set;
+  if (rle_nms_set(images, 4, G, S, &set, why, why_cap)) return -1;
+  RLE_PLAN_REQUIRE(S == 0 || slot_words >= 1, "slot_words 0: a placeholder needs one word");
   memset(plan, 0, sizeof(*plan));
   plan->s.G = G;
   for (int g = 0; g < G; ++g) {
-    const int n = nms.n.first[g + 1] - nms.n.first[g];
+    const int n = set.first[g + 1] - set.first[g];
     const long long mk = images[4 * g + 3];
-    plan->s.H[g] = nms.mp.m.H[g];
-    plan->s.W[g] = nms.mp.m.W[g];
-    plan->s.first[g] = nms.n.first[g];
+    plan->s.H[g] = set.H[g];
+    plan->s.W[g] = set.W[g];
+    plan->s.first[g] = set.first[g];
     plan->s.max_keep[g] = (mk < 0 || mk > n) ? n : (int)mk;
   }
   plan->s.first[G] = S;
   const unsigned long long slot_bytes = (unsigned long long)S * (unsigned long long)slot_words * 4ull;      // < 2^18 * 2^31 * 4
   const unsigned long long table_bytes = (unsigned long long)S * 16ull;
-  RLE_SELECT_REQUIRE(slot_bytes == 0 || (unsigned long long)slots + slot_bytes <= (unsigned long long)out_slots ||
-                         (unsigned long long)out_slots + slot_bytes <= (unsigned long long)slots,
-                     "out_slots overlaps slots");
-  RLE_SELECT_REQUIRE(table_bytes == 0 || (unsigned long long)table + table_bytes <= (unsigned long long)out_table ||
-                         (unsigned long long)out_table + table_bytes <= (unsigned long long)table,
-                     "out_table overlaps table");
+  RLE_PLAN_REQUIRE(slot_bytes == 0 || (unsigned long long)slots + slot_bytes <= (unsigned long long)out_slots ||
+                       (unsigned long long)out_slots + slot_bytes <= (unsigned long long)slots,
+                   "out_slots overlaps slots");
+  RLE_PLAN_REQUIRE(table_bytes == 0 || (unsigned long long)table + table_bytes <= (unsigned long long)out_table ||
+                       (unsigned long long)out_table + table_bytes <= (unsigned long long)table,
+                   "out_table overlaps table");
   plan->chunks = slot_words > 0 ? (slot_words + RLE_SELECT_CHUNK - 1) / RLE_SELECT_CHUNK : 1;
   plan->blocks = (((long long)S + RLE_SELECT_WAVES - 1) / RLE_SELECT_WAVES) * plan->chunks;      // <= 2^16 * 2^20
-  RLE_SELECT_REQUIRE(plan->blocks < (1ll << 31), "too many words (%d entries of %lld) for one launch", S, slot_words);
+  RLE_PLAN_REQUIRE(plan->blocks < (1ll << 31), "too many words (%d entries of %lld) for one launch", S, slot_words);
   plan->wide = slot_words % 4 == 0 && ((slots | out_slots) & 15u) == 0;
   return 0;
-#undef RLE_SELECT_REQUIRE
 }
 
 // ---- hgl_rle_from_polygons_device (csrc/rle_poly.hip): polygons -> RLE, one workgroup per entry.  A polygon's toggle plane --
@@ -420,25 +428,15 @@ static inline unsigned long long rle_poly_entry_words(long long H, long long W) 
 // Checked: 1 <= G <= 64; S >= 0; sizes with H*W < 2^31; entries from 0 to S without a step back.
 static inline int rle_poly_plan(const int64_t* images, int G, int S, RlePoly* geo, unsigned long long* words_out, char* why,
                                 size_t why_cap) {
-#define RLE_POLY_REQUIRE(cond, ...)         \
-  do {                                      \
-    if (!(cond)) {                          \
-      snprintf(why, why_cap, __VA_ARGS__);  \
-      return -1;                            \
-    }                                       \
-  } while (0)
-  RLE_POLY_REQUIRE(G >= 1 && G <= RLE_GROUP_MAX, "%d images (1 .. %d in one call)", G, RLE_GROUP_MAX);
-  RLE_POLY_REQUIRE(S >= 0, "%d entries", S);
+  if (rle_plan_count(G, why, why_cap)) return -1;
+  RLE_PLAN_REQUIRE(S >= 0, "%d entries", S);
   memset(geo, 0, sizeof(*geo));
   geo->G = G;
   unsigned long long words = 0;
   for (int g = 0; g < G; ++g) {
-    const long long H = images[3 * g], W = images[3 * g + 1], e = images[3 * g + 2];
-    const long long e_next = g + 1 < G ? images[3 * (g + 1) + 2] : (long long)S;
-    RLE_POLY_REQUIRE(H > 0 && W > 0 && H < (1ll << 31) && W < (1ll << 31) && H * W < (1ll << 31),
-                     "image %d: bad size %lld x %lld (H*W must be < 2^31)", g, H, W);
-    RLE_POLY_REQUIRE(e >= 0 && e <= e_next && e_next <= (long long)S && (g > 0 || e == 0),
-                     "image %d: entries %lld .. %lld (rows must not decrease, from 0 to S = %d)", g, e, e_next, S);
+    const int64_t* r = images + 3 * g;
+    const long long H = r[0], W = r[1], e = r[2], e_next = rle_row_next(r, 3, 2, g, G, S);
+    if (rle_plan_size(g, H, W, why, why_cap) || rle_plan_entries(g, e, e_next, S, "", "S", why, why_cap)) return -1;
     geo->word0[g] = words;
     geo->H[g] = (int)H;
     geo->W[g] = (int)W;
@@ -447,7 +445,7 @@ static inline int rle_poly_plan(const int64_t* images, int G, int S, RlePoly* ge
   }
   *words_out = words;
   return 0;
-#undef RLE_POLY_REQUIRE
 }
 
+#undef RLE_PLAN_REQUIRE
 #endif  // HGL_RLE_GROUP_H

@@ -4,6 +4,7 @@ Every function validates device/dtype/contiguity, then passes raw pointers to
 libhybridgl.so.  Nothing here computes: a missing library or a CPU tensor raises.
 """
 import ctypes as C
+from itertools import repeat
 
 import torch
 
@@ -507,21 +508,35 @@ def rle_decode(slots, table, H, W, out=None):
     return masks, status
 
 
+def _rle_rows(name, sizes, counts_a, counts_b=None, tail=None, running=False):
+    """The [G, k] int64 image rows of the RLE group calls, for the rle_*_layout functions: H, W, the image's first entry in one
+    or two sets (the running sums of counts_a and counts_b) and -- with `tail` -- one more column: tail(g, H, W, na, nb) is its
+    value or, when `running`, what image g adds to a running offset, and the column is the offset before the image.  Returns
+    (rows, the offset behind the last image).  One flat list and one array: a row costs what it cost in the five loops before."""
+    import numpy as np
+    G, two = len(sizes), counts_b is not None
+    if len(counts_a) != G or (two and len(counts_b) != G):
+        raise ValueError(f"{name}: {G} sizes, {len(counts_a)} and {len(counts_b)} counts" if two else
+                         f"{name}: {G} sizes and {len(counts_a)} counts")
+    flat, ea, eb, off = [], 0, 0, 0
+    for g, ((H, W), na, nb) in enumerate(zip(sizes, counts_a, counts_b if two else repeat(0))):
+        if int(na) < 0 or int(nb) < 0:
+            raise ValueError(f"{name}: image {g} has {na} and {nb} entries" if two else f"{name}: image {g} has {na} entries")
+        H, W, na, nb = int(H), int(W), int(na), int(nb)
+        flat += (H, W, ea, eb) if two else (H, W, ea)
+        if tail is not None:
+            t = tail(g, H, W, na, nb)
+            flat.append(off if running else t)
+            off += t if running else 0
+        ea += na
+        eb += nb
+    return np.array(flat, dtype=np.int64).reshape(G, 3 + two + (tail is not None)), off
+
+
 def rle_group_layout(sizes, counts):
     """(images [G,4] int64 = H, W, first entry, byte offset; total bytes) of a group decoded back to back: image g's
     counts[g] masks of sizes[g] = (H, W) follow those of image g-1 with no padding"""
-    import numpy as np
-    if len(sizes) != len(counts):
-        raise ValueError(f"rle_group_layout: {len(sizes)} sizes and {len(counts)} counts")
-    images = np.zeros((len(sizes), 4), dtype=np.int64)
-    e = o = 0
-    for g, ((H, W), n) in enumerate(zip(sizes, counts)):
-        if int(n) < 0:
-            raise ValueError(f"rle_group_layout: image {g} has {n} entries")
-        images[g] = (int(H), int(W), e, o)
-        e += int(n)
-        o += int(n) * int(H) * int(W)
-    return images, o
+    return _rle_rows("rle_group_layout", sizes, counts, None, lambda g, H, W, n, _: n * H * W, running=True)
 
 
 def rle_decode_group(slots, table, sizes, counts, out=None, aux=None):
@@ -583,19 +598,7 @@ def rle_iou(slots_a, table_a, slots_b, table_b, H, W):
 def rle_match_layout(sizes, counts_a, counts_b):
     """(images [G,5] int64 = H, W, first A entry, first B entry, element offset; total elements) of a group's [na, nb] matrices
     packed back to back"""
-    import numpy as np
-    if not (len(sizes) == len(counts_a) == len(counts_b)):
-        raise ValueError(f"rle_match_layout: {len(sizes)} sizes, {len(counts_a)} and {len(counts_b)} counts")
-    images = np.zeros((len(sizes), 5), dtype=np.int64)
-    ea = eb = o = 0
-    for g, ((H, W), na, nb) in enumerate(zip(sizes, counts_a, counts_b)):
-        if int(na) < 0 or int(nb) < 0:
-            raise ValueError(f"rle_match_layout: image {g} has {na} and {nb} entries")
-        images[g] = (int(H), int(W), ea, eb, o)
-        ea += int(na)
-        eb += int(nb)
-        o += int(na) * int(nb)
-    return images, o
+    return _rle_rows("rle_match_layout", sizes, counts_a, counts_b, lambda g, H, W, na, nb: na * nb, running=True)
 
 
 def rle_match(slots_a, table_a, slots_b, table_b, sizes, counts_a, counts_b, crowd_b=None, matrix=True):
@@ -643,17 +646,7 @@ NMS_METRIC = {"iou": 0, "containment": 1}
 def rle_nms_layout(sizes, counts):
     """images [G,3] int64 = (H, W, first entry) of a mask NMS over G images: image g owns counts[g] consecutive entries of
     sizes[g] = (H, W)"""
-    import numpy as np
-    if len(sizes) != len(counts):
-        raise ValueError(f"rle_nms_layout: {len(sizes)} sizes and {len(counts)} counts")
-    images = np.zeros((len(sizes), 3), dtype=np.int64)
-    e = 0
-    for g, ((H, W), n) in enumerate(zip(sizes, counts)):
-        if int(n) < 0:
-            raise ValueError(f"rle_nms_layout: image {g} has {n} entries")
-        images[g] = (int(H), int(W), e)
-        e += int(n)
-    return images
+    return _rle_rows("rle_nms_layout", sizes, counts)[0]
 
 
 def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou", out=None):
@@ -704,21 +697,12 @@ def rle_select_layout(sizes, counts, max_keep=None):
     """images [G,4] int64 = (H, W, first entry, max_keep) of a compaction over G images: image g owns counts[g] consecutive
     entries of sizes[g] = (H, W).  max_keep: None (no limit: -1 in every row), one number for every image, or one per image (None
     or a negative number: no limit for that image)"""
-    import numpy as np
-    if len(sizes) != len(counts):
-        raise ValueError(f"rle_select_layout: {len(sizes)} sizes and {len(counts)} counts")
     if max_keep is None or not hasattr(max_keep, "__len__"):
         max_keep = [max_keep] * len(sizes)
-    if len(max_keep) != len(sizes):
+    if len(max_keep) != len(sizes) == len(counts):      # the counts' length is refused first
         raise ValueError(f"rle_select_layout: {len(sizes)} sizes and {len(max_keep)} limits")
-    images = np.zeros((len(sizes), 4), dtype=np.int64)
-    e = 0
-    for g, ((H, W), n, mk) in enumerate(zip(sizes, counts, max_keep)):
-        if int(n) < 0:
-            raise ValueError(f"rle_select_layout: image {g} has {n} entries")
-        images[g] = (int(H), int(W), e, -1 if mk is None or int(mk) < 0 else int(mk))
-        e += int(n)
-    return images
+    return _rle_rows("rle_select_layout", sizes, counts, None,
+                     lambda g, H, W, n, _: -1 if (mk := max_keep[g]) is None or (mk := int(mk)) < 0 else mk)[0]
 
 
 def rle_select(slots, table, sizes, counts, keep=None, nms_result=None, cols=None, max_keep=None, out=None, back=None):
@@ -877,18 +861,7 @@ def rle_merge_rule(name, k):
 def rle_merge_layout(sizes, counts_src, counts_out):
     """images [G,4] int64 = (H, W, first source entry, first output entry) of a merge over G images: image g owns
     counts_src[g] consecutive source entries and counts_out[g] consecutive output entries of sizes[g] = (H, W)"""
-    import numpy as np
-    if not (len(sizes) == len(counts_src) == len(counts_out)):
-        raise ValueError(f"rle_merge_layout: {len(sizes)} sizes, {len(counts_src)} and {len(counts_out)} counts")
-    images = np.zeros((len(sizes), 4), dtype=np.int64)
-    es = eo = 0
-    for g, ((H, W), ns, no) in enumerate(zip(sizes, counts_src, counts_out)):
-        if int(ns) < 0 or int(no) < 0:
-            raise ValueError(f"rle_merge_layout: image {g} has {ns} and {no} entries")
-        images[g] = (int(H), int(W), es, eo)
-        es += int(ns)
-        eo += int(no)
-    return images
+    return _rle_rows("rle_merge_layout", sizes, counts_src, counts_out)[0]
 
 
 def rle_merge(slots, table, sizes, counts_src, members, member_offsets, bounds, counts_out, slot_words=None, out=None):

@@ -36,12 +36,12 @@ int main(int argc, char** argv) {
     if (rc != 0) {
       printf("%d %s\n", rc, why);
     } else {
-      const RleMatch& m = plan->m;
-      printf("0 %lld %lld %lld %lld %lld %lld %d", plan->tiles, plan->blocks_a, plan->blocks_b, plan->words_a, plan->words_b, plan->pairs,
-             plan->splits);
+      const RleMatch& m = plan->p.m;
+      printf("0 %lld %lld %lld %lld %lld %lld %d", plan->p.tiles, plan->a.blocks, plan->b.blocks, plan->a.words, plan->b.words, plan->p.pairs,
+             plan->p.splits);
       for (int g = 0; g < m.G; ++g)
         printf(" | %d %d %d %d %lld %u %u %u %u %u %lld", m.H[g], m.W[g], m.first_a[g], m.first_b[g], m.off[g], m.word0_a[g], m.word0_b[g],
-               m.tile0[g], plan->pa.blk0[g], plan->pb.blk0[g], m.pair0[g]);
+               m.tile0[g], plan->a.blk0[g], plan->b.blk0[g], m.pair0[g]);
       printf(" | %d %d\n", m.first_a[m.G], m.first_b[m.G]);
     }
     free(plan);

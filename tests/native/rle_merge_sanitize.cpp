@@ -2,7 +2,7 @@
 // tests/test_sanitize_rle_merge.py with g++ -fsanitize=address,undefined.  Reads a case file written by the test, one case per
 // line:   <G> <Ssrc> <S> <M> <4*G numbers: H W first_src first_out per image>
 // and prints one line per case: the return code, then for an accepted case "blocks_src words_src words_out" and per image
-// "H W first_src first_out word0_src word0_out blk0" (the merge kernel's copy and the plane kernel's must agree, or the line says
+// "H W first_src first_out word0_src word0_out blk0" (the merge kernel's struct and the RleSet it was filled from must agree, or the line says
 // "split").  The image rows live in a heap buffer of exactly 4*G words, so a read beyond them is a report.
 #include <cinttypes>
 #include <cstdint>
@@ -37,8 +37,8 @@ int main(int argc, char** argv) {
       printf("%d %s\n", rc, why);
     } else {
       const RleMerge& m = plan->m;
-      const RlePlaneGroup& p = plan->src;
-      printf("0 %lld %lld %lld", plan->blocks_src, plan->words_src, plan->words_out);
+      const RleSet& p = plan->src;
+      printf("0 %lld %lld %lld", p.blocks, p.words, plan->words_out);
       bool split = p.G != m.G;
       for (int g = 0; g < m.G; ++g) {
         split = split || p.H[g] != m.H[g] || p.W[g] != m.W[g] || p.first[g] != m.first_src[g] || p.word0[g] != m.word0_src[g];

@@ -36,15 +36,17 @@ int main(int argc, char** argv) {
     if (rc != 0) {
       printf("%d %s\n", rc, why);
     } else {
-      const RleMatchPlan& mp = plan->mp;
-      printf("0 %lld %lld %lld %lld %d %lld", mp.tiles, mp.blocks_a, mp.words_a, mp.pairs, mp.splits, plan->sup_words);
+      const RlePairs& p = plan->p;
+      const RleSet& set = plan->set;
+      printf("0 %lld %lld %lld %lld %d %lld", p.tiles, set.blocks, set.words, p.pairs, p.splits, plan->sup_words);
       for (int g = 0; g < plan->n.G; ++g)
-        printf(" | %d %d %d %u %u %u %lld %lld", mp.m.H[g], mp.m.W[g], plan->n.first[g], mp.m.word0_a[g], mp.m.tile0[g], mp.pa.blk0[g],
+        printf(" | %d %d %d %u %u %u %lld %lld", p.m.H[g], p.m.W[g], plan->n.first[g], p.m.word0_a[g], p.m.tile0[g], set.blk0[g],
                plan->n.pair0[g], plan->n.sup0[g]);
       // both sides of the pair count are the one set
-      int same = mp.blocks_a == mp.blocks_b && mp.words_a == mp.words_b && mp.m.first_a[mp.m.G] == mp.m.first_b[mp.m.G];
+      int same = p.m.G == set.G && p.m.first_a[p.m.G] == set.first[set.G] && p.m.first_a[p.m.G] == p.m.first_b[p.m.G];
       for (int g = 0; g < plan->n.G; ++g)
-        same = same && mp.m.first_a[g] == mp.m.first_b[g] && mp.m.word0_a[g] == mp.m.word0_b[g] && mp.pa.blk0[g] == mp.pb.blk0[g];
+        same = same && p.m.first_a[g] == set.first[g] && p.m.first_a[g] == p.m.first_b[g] && p.m.word0_a[g] == set.word0[g] &&
+               p.m.word0_a[g] == p.m.word0_b[g];
       printf(" | %d %d\n", plan->n.first[plan->n.G], same);
     }
     free(plan);
