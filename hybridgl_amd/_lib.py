@@ -242,6 +242,8 @@ PROTOTYPES = {
     "hgl_rle_nms_workspace_bytes": (_SZ, [_VP, _I, _I, _LL]),
     "hgl_rle_nms_device": (_I, [_VP, _LL, _VP, _I, _VP, _I, _VP, C.c_double, _I, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_rle_select_device": (_I, [_VP, _LL, _VP, _I, _VP, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "hgl_rle_clean_workspace_bytes": (_SZ, [_VP, _I, _I, _LL, _LL]),
+    "hgl_rle_clean_device": (_I, [_VP, _LL, _VP, _I, _VP, _I, _I, _I, _LL, _VP, _LL, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

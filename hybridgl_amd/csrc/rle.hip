@@ -27,7 +27,7 @@
 // written, 3 = the index is outside [0, N), nothing read or written.  Words beyond what the form defines keep their bytes.
 #include "hgl_common.h"
 #include "rle_group.h"      // RleTiles, RleGroup, RleOne, RleSet and the rle_*_plan functions: plain C++, shared with the sanitizer harnesses
-#include "rle_scan.h"       // RLE_THREADS, rle_block_sum, rle_group_find, rle_counts_chunk: shared with rle_poly.hip
+#include "rle_scan.h"       // RLE_THREADS, the block reductions, rle_group_find, rle_counts_chunk, rle_write_runs, rle_stage_ws: shared with rle_poly.hip, rle_clean.hip
 #include "nms_walk.h"       // nms_before, nms_resolve_block, nms_emit_block: shared with sam_nms.hip
 
 namespace {
@@ -71,86 +71,6 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_columns_kernel(const uint8_t*
   unsigned long long* dst = plane + (size_t)s * W * HW64 + (size_t)x * HW64 + j;
 #pragma unroll
   for (int k = 0; k < V; ++k) dst[(size_t)k * HW64] = c[k];      // x + k < W: W % 4 == 0 on the 4-column path
-}
-
-// the transitions of word q of a mask's column plane P (q = x*HW64 + j); *C receives the word itself
-__device__ __forceinline__ unsigned long long rle_transitions(const unsigned long long* P, unsigned q, int H, int HW64,
-                                                              unsigned long long* C) {
-  const int j = (int)(q % (unsigned)HW64);
-  const int nb = H - 64 * j < 64 ? H - 64 * j : 64;
-  const unsigned long long valid = nb == 64 ? ~0ull : ((1ull << nb) - 1ull);
-  unsigned long long carry = 0;
-  if (q > 0) {
-    const int jp = j > 0 ? j - 1 : HW64 - 1;
-    const int nbp = H - 64 * jp < 64 ? H - 64 * jp : 64;
-    carry = (P[q - 1] >> (nbp - 1)) & 1ull;
-  }
-  const unsigned long long c = P[q];
-  *C = c;
-  return (c ^ ((c << 1) | carry)) & valid;
-}
-
-// n <= 32 pixels of column x from row y on, out of the column's 64-bit words (y + n <= H)
-__device__ __forceinline__ uint32_t rle_column_bits(const unsigned long long* col, int y, int n) {
-  const int j = y >> 6, o = y & 63;
-  unsigned long long v = col[j] >> o;
-  if (o + n > 64) v |= col[j + 1] << (64 - o);
-  return (uint32_t)v & (n == 32 ? 0xffffffffu : ((1u << n) - 1u));
-}
-
-// The run writer: what the slot and the table row of one H x W mask hold, out of its column plane P (W * HW64 words, padding bits
-// 0).  The whole workgroup calls it; red, wsum, wmax: 4 words of LDS each.  ONE copy: the encoder's plane comes from
-// rle_columns_kernel, the merge's from the vote of its own workgroup (rle_merge_kernel below).
-__device__ __forceinline__ void rle_write_runs(const unsigned long long* P, int H, int W, int HW64, uint32_t* slot, long long slot_words,
-                                               int32_t* row, unsigned* red, unsigned* wsum, unsigned* wmax) {
-  const int t = threadIdx.x;
-  const unsigned Q = (unsigned)W * (unsigned)HW64;
-  const unsigned HW = (unsigned)H * (unsigned)W;      // < 2^31 (checked by the host entry)
-
-  // ---- sweep 1: how many counts, how many foreground pixels -> what the slot holds
-  unsigned trans = 0, area = 0;
-  for (unsigned q = t; q < Q; q += RLE_THREADS) {
-    unsigned long long c;
-    trans += __popcll(rle_transitions(P, q, H, HW64, &c));
-    area += __popcll(c);
-  }
-  trans = rle_block_sum(trans, red);
-  area = rle_block_sum(area, red);
-  const unsigned n_counts = trans + 1u;
-  const unsigned plane_words = (HW + 31u) / 32u;
-  const int form = (long long)n_counts <= slot_words ? 0 : ((long long)plane_words <= slot_words ? 1 : 2);
-  if (t == 0) { row[0] = (int32_t)n_counts; row[1] = form; row[2] = (int32_t)area; row[3] = 0; }
-  if (form == 2) return;
-  if (form == 1) {
-    // the bit plane in run order: 32 pixels per word, LSB first; a word may span several columns when H < 32
-    for (unsigned w = t; w < plane_words; w += RLE_THREADS) {
-      const unsigned p = 32u * w;
-      int x = (int)(p / (unsigned)H), y = (int)(p % (unsigned)H), filled = 0;
-      uint32_t out = 0;
-      while (filled < 32 && x < W) {
-        const int n = 32 - filled < H - y ? 32 - filled : H - y;
-        out |= rle_column_bits(P + (size_t)x * HW64, y, n) << filled;
-        filled += n;
-        y += n;
-        if (y == H) { y = 0; ++x; }
-      }
-      slot[w] = out;
-    }
-    return;
-  }
-  // ---- sweep 2 (form 0): 256 words at a time, rank and previous position carried from chunk to chunk
-  unsigned rank_base = 0, last_base = 0;      // counts written so far; position of the last transition so far (0: none)
-  for (unsigned base = 0; base < Q; base += RLE_THREADS) {
-    const unsigned q = base + t;
-    unsigned long long T = 0, c;
-    unsigned p0 = 0;
-    if (q < Q) {
-      T = rle_transitions(P, q, H, HW64, &c);
-      p0 = (q / (unsigned)HW64) * (unsigned)H + 64u * (q % (unsigned)HW64);
-    }
-    rle_counts_chunk(T, p0, slot, rank_base, last_base, wsum, wmax);      // rle_scan.h; k < trans < n_counts <= slot_words
-  }
-  if (t == 0) slot[trans] = HW - last_base;
 }
 
 __global__ __launch_bounds__(RLE_THREADS) void rle_runs_kernel(const unsigned long long* __restrict__ plane, int N, int H, int W,
@@ -237,20 +157,6 @@ __device__ __forceinline__ unsigned long long rle_plane_word(const uint32_t* __r
     }
   }
   return c;
-}
-
-// the workgroup-wide maximum of v (rle_block_sum's shape)
-__device__ __forceinline__ unsigned rle_block_max(unsigned v, unsigned* lds) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const unsigned o = __shfl_xor(v, d, 64);
-    v = v > o ? v : o;
-  }
-  __syncthreads();      // the previous use of lds is over
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const unsigned a = lds[0] > lds[1] ? lds[0] : lds[1], b = lds[2] > lds[3] ? lds[2] : lds[3];
-  return a > b ? a : b;
 }
 
 // The box of the pixels [a, b) of run order (a < b <= H*W) joined into (x0, y0, x1, y1): x in [a / H, (b-1) / H]; within one
@@ -1049,29 +955,6 @@ __global__ __launch_bounds__(64 * RLE_SELECT_WAVES) void rle_select_move_kernel(
   for (long long q = w + lane; q < w1; q += 64) dst[q] = from[q];
 }
 
-// run starts of one set: [S] arrays of slot_words + 1 words
-size_t rle_starts_bytes(int S, long long slot_words) { return hgl_align_up((size_t)S * (size_t)(slot_words + 1) * sizeof(uint32_t), 256); }
-size_t rle_status_bytes(int S) { return hgl_align_up((size_t)S * 4 * sizeof(int32_t), 256); }
-
-// A set staged for the kernels that read planes, in the workspace: run starts, status, boxes (when wanted) and the column words
-// of every entry (C and D above).  rle_stage_ws carves it at *p and moves *p behind it.
-constexpr size_t RLE_NO_BOXES = ~(size_t)0;
-struct RleStageWs {
-  size_t E, status, boxes, plane;      // boxes: RLE_NO_BOXES when not wanted
-};
-RleStageWs rle_stage_ws(size_t* p, int S, long long slot_words, long long plane_words, bool boxes) {
-  RleStageWs w;
-  w.E = *p;
-  *p += rle_starts_bytes(S, slot_words);
-  w.status = *p;
-  *p += rle_status_bytes(S);
-  w.boxes = boxes ? *p : RLE_NO_BOXES;
-  if (boxes) *p += rle_status_bytes(S);
-  w.plane = *p;
-  *p += hgl_align_up((size_t)plane_words * sizeof(unsigned long long), 256);
-  return w;
-}
-
 // the staged set's arrays; the two launches that fill them when the set has an entry (`blocks`: the plane kernel's grid).  SG is
 // the starts kernel's geometry and PG the plane kernel's: RleSet for both, or RleOne and RlePlaneOne.
 struct RleStaged {
@@ -1194,6 +1077,15 @@ int rle_decode_launch(const char* name, const uint32_t* slots, long long slot_wo
 }
 
 }  // namespace
+
+// rle_scan.h: the staging of a set for a caller in another file (rle_clean.hip): rle_stage_launch on a carve without boxes,
+// its offsets taken from E
+void rle_stage_set(const uint32_t* slots, long long slot_words, const int32_t* table, int S, const RleSet& set, uint32_t* E,
+                   int32_t* status, unsigned long long* plane, void* stream) {
+  char* base = (char*)E;
+  const RleStageWs w = {0, (size_t)((char*)status - base), RLE_NO_BOXES, (size_t)((char*)plane - base)};
+  rle_stage_launch(slots, slot_words, table, S, set.blocks, set, set, base, w, (hipStream_t)stream);
+}
 
 extern "C" {
 

@@ -2,12 +2,12 @@
 // decoder; the checks every plan makes of its caller's image rows (rle_plan_count, rle_plan_size, rle_plan_entries); RleSet, the
 // one description of "a set of entries that belongs to G images" and of its bit planes in the workspace, built image by image
 // through rle_set_add; and the plans -- what the host works out of a decode call's rows (rle_group_plan), a match call's
-// (rle_match_plan), a merge call's (rle_merge_plan), a mask NMS call's (rle_nms_plan), a compaction's (rle_select_plan) and a
-// polygon call's (rle_poly_plan).  A plan holds the RleSets the plane kernel stages and the structs the other kernels take by
+// (rle_match_plan), a merge call's (rle_merge_plan), a mask NMS call's (rle_nms_plan), a compaction's (rle_select_plan), a
+// polygon call's (rle_poly_plan) and a clean-up's (rle_clean_plan).  A plan holds the RleSets the plane kernel stages and the structs the other kernels take by
 // value (RleGroup, RleMatch, RleMerge, RleNms, RleSelect, RlePoly: their layout is the kernels' and stays); what such a struct
 // repeats of a set is copied out of the set in one place.  Plain C++ without a HIP construct: the .hip files include it, and so
 // do the sanitizer harnesses tests/native/rle_group_sanitize.cpp, rle_match_sanitize.cpp, rle_merge_sanitize.cpp,
-// rle_nms_sanitize.cpp and rle_select_sanitize.cpp.
+// rle_nms_sanitize.cpp, rle_select_sanitize.cpp and rle_clean_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
 #include <stdint.h>
@@ -444,6 +444,37 @@ static inline int rle_poly_plan(const int64_t* images, int G, int S, RlePoly* ge
     words += (unsigned long long)(e_next - e) * rle_poly_entry_words(H, W);      // < 2^31 * 3 * 2^26
   }
   *words_out = words;
+  return 0;
+}
+
+// ---- hgl_rle_clean_device (csrc/rle_clean.hip): small holes filled and small islands dropped in every entry of a set, on
+// column segments (csrc/ccl_runs.h).  The set goes through the plane kernel; one workgroup per entry works on the entry's own
+// plane words, one 32-bit segment rank per plane word and RLE_CLEAN_ARRAYS arrays of `cap` 32-bit words.
+constexpr int RLE_CLEAN_ARRAYS = 5;      // first row, last row, parent link, area, raster key of a segment
+
+struct RleCleanPlan {
+  RleSet set;
+  long long cap;      // segments per entry and colour the workspace holds: seg_cap, or the most any entry of the set can have
+};
+
+// images [G,3] = (H, W, first entry) -> *plan; 0, or -1 with the reason in why.  Checked: what rle_nms_plan checks -- 1 <= G <= 64,
+// S >= 0, H*W < 2^31, entries from 0 to S without a step back, at most RLE_NMS_MAX entries per image, fewer than 2^32 plane words
+// -- and: 0 <= slot_words, out_slot_words < 2^31; area_thresh >= 0; modes 1 .. 3 (bit 0 holes, bit 1 islands); 1 <= seg_cap < 2^31.
+static inline int rle_clean_plan(const int64_t* images, int G, int S, long long slot_words, long long out_slot_words, int area_thresh,
+                                 int modes, long long seg_cap, RleCleanPlan* plan, char* why, size_t why_cap) {
+  if (rle_plan_count(G, why, why_cap)) return -1;
+  RLE_PLAN_REQUIRE(slot_words >= 0 && slot_words < (1ll << 31), "slot_words %lld (0 .. 2^31 - 1)", slot_words);
+  RLE_PLAN_REQUIRE(out_slot_words >= 0 && out_slot_words < (1ll << 31), "out_slot_words %lld (0 .. 2^31 - 1)", out_slot_words);
+  RLE_PLAN_REQUIRE(area_thresh >= 0, "area_thresh %d (must not be negative)", area_thresh);
+  RLE_PLAN_REQUIRE(modes >= 1 && modes <= 3, "modes %d (bit 0 = holes, bit 1 = islands: 1 .. 3)", modes);
+  RLE_PLAN_REQUIRE(seg_cap >= 1 && seg_cap < (1ll << 31), "seg_cap %lld (1 .. 2^31 - 1)", seg_cap);
+  if (rle_nms_set(images, 3, G, S, &plan->set, why, why_cap)) return -1;
+  long long most = 1;      // ccl_seg_bound of the largest image that owns an entry
+  for (int g = 0; g < G; ++g) {
+    const long long b = (long long)plan->set.W[g] * (((long long)plan->set.H[g] + 1) / 2);
+    if (plan->set.first[g + 1] > plan->set.first[g] && b > most) most = b;
+  }
+  plan->cap = seg_cap < most ? seg_cap : most;
   return 0;
 }
 

@@ -766,6 +766,60 @@ def rle_select(slots, table, sizes, counts, keep=None, nms_result=None, cols=Non
     return out_slots, out_table, out_cols, out_src, out_n
 
 
+CLEAN_MODES = {"holes": 1, "islands": 2, "both": 3}
+
+
+def rle_clean_layout(sizes, counts):
+    """images [G,3] int64 = (H, W, first entry) of a clean-up over G images: image g owns counts[g] consecutive entries of
+    sizes[g] = (H, W)"""
+    return _rle_rows("rle_clean_layout", sizes, counts)[0]
+
+
+def rle_remove_small_regions(slots, table, sizes, counts, area_thresh, mode="both", seg_cap=None, slot_words=None, out=None):
+    """remove_small_regions (utils/amg.py:267-291) on an encoded set, image by image (hgl_rle_clean_device on the current stream,
+    no synchronisation): the S entries of slots / table (what rle_encode or rle_pack returns) belong to G = len(sizes) <= 64
+    images, counts[g] <= 4096 consecutive entries of sizes[g] = (H, W); an image may own none.  mode "holes": 8-connected
+    components of the complement smaller than area_thresh are filled; "islands": components of the foreground smaller than it are
+    dropped (the first largest in raster order stays when all are small); "both": holes, then islands on the result -- SAM's order.
+    No mask becomes pixels and no pixel gets a label: the components are found on column segments.  seg_cap: the segments per
+    entry and colour the workspace is sized for (an entry with more gets code 3); default the bound that never refuses, the
+    set's largest W*ceil(H/2) + W; a caller who packed form-0 rows from strings passes slot_words // 2 + max W + 1.  slot_words:
+    int32 words per output entry (default the input's).
+    Returns (out_slots [S, slot_words], out_table [S,4]: the cleaned set as rle_encode would write it -- the canonical
+    re-encoding where nothing was removed; boxes [S,4] int32: inclusive XYXY as sam.mask_boxes gives it; result [S,4] int32 =
+    code, area after, changed (bit 0: the holes pass found a small component, bit 1: the islands pass did), area before).  Code 2
+    (no mask in the slot) and 3 (over seg_cap): table row (0, 3, 0, 0), slot untouched, box zeros.  The four are views of ONE
+    int32 buffer, table | slots | boxes | result (`out`: a contiguous int32 device tensor of S * (12 + slot_words) elements)."""
+    lib = _lib.load()
+    sp, sw, tp, S = _rle_set(slots, table, "rle_remove_small_regions")
+    if mode not in CLEAN_MODES:
+        raise ValueError(f"rle_remove_small_regions: mode {mode!r} (one of {sorted(CLEAN_MODES)})")
+    images = rle_clean_layout(sizes, counts)
+    G = len(images)
+    if int(sum(int(n) for n in counts)) != S:
+        raise ValueError(f"rle_remove_small_regions: counts sum to {sum(counts)}, the set has {S} entries")
+    osw = sw if slot_words is None else int(slot_words)
+    if seg_cap is None:
+        seg_cap = max([int(W) * ((int(H) + 1) // 2) + int(W) for H, W in sizes], default=1)
+    dev = slots.device
+    if out is None:
+        out = torch.empty(S * (12 + osw), dtype=torch.int32, device=dev)
+    elif out.numel() != S * (12 + osw) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out: expected a contiguous int32 tensor of {S * (12 + osw)} elements on {dev}, got {tuple(out.shape)} {out.dtype}")
+    out = out.view(-1)
+    out_slots, out_table = rle_split(out, S, osw)
+    boxes, result = out[S * (4 + osw):S * (8 + osw)].view(S, 4), out[S * (8 + osw):].view(S, 4)
+    if S == 0:
+        return out_slots, out_table, boxes, result
+    need = lib.hgl_rle_clean_workspace_bytes(images.ctypes.data, G, S, sw, int(seg_cap))
+    ws = workspace(need, dev, "rle")
+    base = out.data_ptr()
+    check(lib.hgl_rle_clean_device(sp, sw, tp, S, images.ctypes.data, G, int(area_thresh), CLEAN_MODES[mode], int(seg_cap), base + 16 * S, osw,
+                                   base, base + 4 * S * (4 + osw), base + 4 * S * (8 + osw), ws.data_ptr(), ws.numel(), _stream()),
+          "hgl_rle_clean_device")
+    return out_slots, out_table, boxes, result
+
+
 POLY_RULE = {"once": 0, "any": 1}
 
 

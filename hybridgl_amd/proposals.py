@@ -22,7 +22,11 @@ compare           two stores image by image, every mask of one against every mas
 ceiling           the best proposal of a store per target -- the bound no scoring of these proposals exceeds -- without CLIP.
 thin              a store made smaller: per image the greedy suppression by MASK overlap (ops.rle_nms on the runs: no mask becomes
                   pixels) that SAM's box NMS leaves undone; the result is a store like any other.
-                      python -m hybridgl_amd.proposals thin DIR_IN DIR_OUT --thr T [--metric iou|containment] [--score ...] [--json OUT]"""
+                      python -m hybridgl_amd.proposals thin DIR_IN DIR_OUT --thr T [--metric iou|containment] [--score ...] [--json OUT]
+clean             a store re-tuned: postprocess_small_regions at another min_mask_region_area -- small holes filled, small islands
+                  dropped (ops.rle_remove_small_regions on the runs: no mask becomes pixels), the boxes taken again, the second
+                  box NMS -- so a store saved at one value answers what another would have given without the ViT-H encoder.
+                      python -m hybridgl_amd.proposals clean DIR_IN DIR_OUT --min_area A [--nms_thresh T] [--json OUT]"""
 import collections
 import json
 import os
@@ -846,6 +850,90 @@ def thin(src, dst, thr, metric="iou", score="predicted_iou", group=16, device=No
     return {"per_image": per_image, "before": sum(v[0] for v in per_image.values()), "after": sum(v[1] for v in per_image.values())}
 
 
+def clean(src, dst, min_area, nms_thresh=0.7, group=16, device=None):
+    """postprocess_small_regions (automatic_mask_generator.py:324-372) on a proposal store: what the generator's
+    min_mask_region_area would have done to the records of `src`, written to `dst` without a SAM model.  Per chunk of `group`
+    images: holes smaller than min_area filled and islands smaller than it dropped in every record's mask
+    (ops.rle_remove_small_regions in mode both; the strings' runs cross the bus, no mask becomes pixels), then the box NMS over
+    the boxes of the cleaned masks at nms_thresh (the generator uses max(box_nms_thresh, crop_nms_thresh)), an untouched mask
+    scoring 1.0 and a changed one 0.0 (sam.nms_segments; sam.nms for an image of more than 1024 records).  The kept records are
+    written in the NMS's order, the order generate() hands them out in.  A kept record whose mask changed gets a new
+    `segmentation`, `area` and `bbox`; its other fields, and an unchanged record, stay as they stood.  dst's meta is src's plus
+    {"cleaned": {"min_area", "nms_thresh", "source"}}.  ValueError for dst == src, for a dst that already holds a store, for a
+    negative min_area or a NaN threshold and for a record that does not decode.  An image may hold at most 4096 records.
+    Returns {"per_image": {image_id: [before, after, changed among the kept]}, "before": total, "after": total, "changed": total}."""
+    from . import sam
+    min_area = int(min_area)
+    if min_area < 0:
+        raise ValueError(f"clean: min_area {min_area} (must not be negative)")
+    nms_thresh = float(nms_thresh)
+    if nms_thresh != nms_thresh:
+        raise ValueError("clean: the threshold is NaN")
+    src, dst = _store(src), _store(dst)
+    if os.path.realpath(src.directory) == os.path.realpath(dst.directory):
+        raise ValueError(f"clean: the source and the destination are the same directory ({src.directory})")
+    if not os.path.isdir(src.directory):
+        raise ValueError(f"clean: {src.directory}: no such directory")
+    if os.path.isdir(dst.directory) and any(n.endswith(".json") for n in os.listdir(dst.directory)):
+        raise ValueError(f"clean: {dst.directory} already holds a store")
+    ids = src.image_ids()
+    per_image = {}
+    step = max(int(group), 1)
+    for c0 in range(0, len(ids), step):
+        chunk = [(iid, src.records(iid)) for iid in ids[c0:c0 + step]]
+        sized = [_record_runs(src, iid, recs) for iid, recs in chunk]
+        counts = [len(runs) for _, runs in sized]
+        S = sum(counts)
+        out = [[] for _ in chunk]
+        if S:
+            sizes = [size or (1, 1) for size, _ in sized]
+            slots, table = _pack([r for _, runs in sized for r in runs], device)
+            dev, sw = slots.device, int(slots.shape[1])
+            # an output slot of the plane's size loses no mask: runs where they fit, the bit plane otherwise; rle_from_slot reads either
+            osw = max([sw] + [ops.rle_slot_words(H, W) for (H, W), n in zip(sizes, counts) if n])
+            flat = torch.empty(S * (12 + osw), dtype=torch.int32, device=dev)
+            _, _, boxes, result = ops.rle_remove_small_regions(slots, table, sizes, counts, min_area, "both",
+                                                               seg_cap=sw // 2 + max(W for _, W in sizes) + 1, slot_words=osw, out=flat)
+            boxes = boxes.clone()      # a buffer of its own: the NMS wants its boxes 16-byte aligned, the view lies where S * (4 + osw) words end
+            scores = (result[:, 2] == 0).to(torch.float32)
+            keep = torch.ones(S, dtype=torch.uint8, device=dev)
+            if max(counts) <= 1024:
+                offs = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32).to(dev)
+                order, n = sam.nms_segments(boxes, scores, keep, offs, max(counts), nms_thresh)
+                order, n = order.cpu().numpy().astype(np.int64), n.cpu().numpy().astype(np.int64)
+            else:      # a list of any length, image by image
+                order, n, e = np.zeros(S, np.int64), np.zeros(len(counts), np.int64), 0
+                for k, c in enumerate(counts):
+                    if c:
+                        o, nn = sam.nms(boxes[e:e + c].contiguous(), scores[e:e + c].contiguous(), keep[e:e + c].contiguous(), nms_thresh)
+                        order[e:e + c], n[k] = o.cpu().numpy(), int(nn.cpu()[0])
+                    e += c
+            host = flat.cpu().numpy()
+            h_slots, h_table = ops.rle_split(host, S, osw)
+            h_boxes, h_result = host[S * (4 + osw):].reshape(2, S, 4)
+            _check_decoded(src, [iid for iid, _ in chunk], counts, h_result)
+            e = 0
+            for k, ((iid, recs), (size, _), c) in enumerate(zip(chunk, sized, counts)):
+                for i in order[e:e + int(n[k])]:
+                    r, s = recs[int(i)], e + int(i)
+                    if h_result[s, 2]:
+                        H, W = size
+                        runs = sam.rle_from_slot(h_slots[s], int(h_table[s, 0]), int(h_table[s, 1]), H, W)
+                        x0, y0, x1, y1 = (int(v) for v in h_boxes[s])
+                        r = dict(r, segmentation=sam.coco_encode_rle({"size": [H, W], "counts": runs}), area=int(h_result[s, 1]),
+                                 bbox=[x0, y0, x1 - x0, y1 - y0])
+                    out[k].append((r, bool(h_result[s, 2])))
+                e += c
+        for (iid, recs), kept in zip(chunk, out):
+            dst.write(iid, [r for r, _ in kept])
+            per_image[iid] = [len(recs), len(kept), sum(1 for _, ch in kept if ch)]
+    meta = dict(src.meta())
+    meta["cleaned"] = {"min_area": min_area, "nms_thresh": nms_thresh, "source": src.directory}
+    dst.write_meta(meta)
+    return {"per_image": per_image, "before": sum(v[0] for v in per_image.values()), "after": sum(v[1] for v in per_image.values()),
+            "changed": sum(v[2] for v in per_image.values())}
+
+
 def _jsonable(report):
     return {"summary": report["summary"], "per_image": [dict(v, image_id=k) for k, v in report["per_image"].items()]}
 
@@ -866,7 +954,24 @@ def main(argv=None):
     t.add_argument("--metric", default="iou", choices=sorted(ops.NMS_METRIC))
     t.add_argument("--score", default="predicted_iou", choices=list(THIN_SCORES), help="the order of the walk (stored: as stored)")
     t.add_argument("--json", default="", metavar="OUT", help="also write the per-image counts here")
+    k = sub.add_parser("clean", help="a store with small holes filled and small islands dropped: the generator's min_mask_region_area, after the fact")
+    k.add_argument("dir_in")
+    k.add_argument("dir_out")
+    k.add_argument("--min_area", type=int, required=True, help="a hole or an island of fewer pixels is filled / dropped")
+    k.add_argument("--nms_thresh", type=float, default=0.7, help="the box NMS that follows (the generator's max(box_nms_thresh, crop_nms_thresh))")
+    k.add_argument("--json", default="", metavar="OUT", help="also write the per-image counts here")
     args = p.parse_args(argv)
+    if args.cmd == "clean":
+        try:
+            rep = clean(args.dir_in, args.dir_out, args.min_area, args.nms_thresh)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"hybridgl_amd.proposals: {e}")
+        print(f"images: {len(rep['per_image'])}   proposals: {rep['before']} -> {rep['after']}   changed among the kept: {rep['changed']}")
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump({"before": rep["before"], "after": rep["after"], "changed": rep["changed"],
+                           "per_image": [{"image_id": i, "before": v[0], "after": v[1], "changed": v[2]} for i, v in rep["per_image"].items()]}, f)
+        return 0
     if args.cmd == "thin":
         try:
             rep = thin(args.dir_in, args.dir_out, args.thr, args.metric, args.score)

@@ -1425,6 +1425,39 @@ def nms_rles(rles, scores=None, thr=0.7, metric="iou", device=None):
     return [int(i) for i in out_idx[:int(out_n[0])]]
 
 
+def remove_small_regions_rles(rles, area_thresh, mode):
+    """utils/amg.py:267-291 for a list of RLE dicts of ONE size, on the device: the runs cross the bus (ops.rle_pack), the
+    components are found on column segments (ops.rle_remove_small_regions) and the cleaned masks come back as runs; no mask
+    becomes pixels.  mode "holes" or "islands" as the reference's, or "both" (holes, then islands on the result).  Returns
+    (rles, changed): every dict in the form of its input (counts as a list, or as a COCO string), changed[i] True where a small
+    region was found -- the reference's flag.  Raises ValueError on sizes that differ and on an entry that does not decode."""
+    if len(rles) == 0:
+        return [], []
+    h, w = (int(v) for v in rles[0]["size"])
+    for i, r in enumerate(rles):
+        if [int(v) for v in r["size"]] != [h, w]:
+            raise ValueError(f"remove_small_regions_rles: entry {i} has size {list(r['size'])}, entry 0 has {[h, w]}")
+    n = len(rles)
+    counts = [rle_counts(r) for r in rles]
+    slots, table = ops.rle_pack(counts, h, w)
+    sw = int(slots.shape[1])
+    flat = torch.empty(n * (12 + ops.rle_slot_words(h, w)), dtype=torch.int32, device=slots.device)
+    ops.rle_remove_small_regions(slots, table, [(h, w)], [n], area_thresh, mode, seg_cap=sw // 2 + w + 1,
+                                 slot_words=ops.rle_slot_words(h, w), out=flat)
+    osw = ops.rle_slot_words(h, w)
+    host = flat.cpu().numpy()      # the one device -> host copy
+    s, t = ops.rle_split(host, n, osw)
+    result = host[n * (8 + osw):].reshape(n, 4)
+    bad = np.flatnonzero(result[:, 0] != 0)
+    if len(bad):
+        raise ValueError(f"remove_small_regions_rles: entry {int(bad[0])} does not decode to a {h} x {w} mask (status {int(result[bad[0], 0])})")
+    out = []
+    for i, r in enumerate(rles):
+        new = {"size": [h, w], "counts": rle_from_slot(s[i], int(t[i, 0]), int(t[i, 1]), h, w)}
+        out.append(coco_encode_rle(new) if isinstance(r["counts"], (str, bytes, bytearray)) else new)
+    return out, [bool(c) for c in result[:, 2]]
+
+
 def remove_small_regions(masks, area_thresh, mode, out=None):
     """utils/amg.py:267-291 for a batch [n,H,W] uint8 on the device -> (new masks, changed [n] uint8).
     out: (masks, changed) to write into (contiguous slices of a group's tensors) instead of fresh ones."""

@@ -935,6 +935,44 @@ int hgl_rle_select_device(const uint32_t* slots, long long slot_words, const int
                           const uint32_t* cols, int C,
                           uint32_t* out_slots, int32_t* out_table, uint32_t* out_cols,
                           int32_t* out_src, int32_t* out_n, void* stream);
+/* remove_small_regions (utils/amg.py:267-291) on an encoded set (csrc/rle_clean.hip): small holes filled, small islands dropped,
+ * every entry encoded again with its box -- the step of postprocess_small_regions that hgl_remove_small_regions /
+ * hgl_remove_small_regions_boxes take on byte masks, without the bytes.  No [S,H,W] byte array and no per-pixel label exists
+ * anywhere: the components are found on column segments (maximal vertical stretches of equal pixels inside one column).
+ * Asynchronous on `stream`; no host synchronisation or allocation; two calls give the same bytes; THREE launches whatever G, S and
+ * the sizes are, none for S = 0.  Integer atomics only where the order cannot show: atomicMin on the union-find's parent links
+ * (link by minimum), atomicAdd on a component's area, atomicMin on its raster key.
+ * Set = (slots, slot_words, table, S): as everywhere in the family, forms 0 and 1, with the code 0 / 1 / 2 rules of
+ * hgl_rle_decode_device; an entry of code 1 counts as decoded (clipped as the decoder clips).
+ * images_host: HOST [G,3] int64, G <= 64, row g = (H_g, W_g, first entry e_g) with the rules (and the limits) of
+ * hgl_rle_nms_device; read before the call returns.
+ * modes: bit 0 = holes, bit 1 = islands; both: holes first, then islands ON THE RESULT of the hole filling (SAM's order: a filled
+ * hole can join two islands, and the island pass sees the joined one).
+ * HGL_EINVAL, and nothing is enqueued: a bad geometry; slot_words or out_slot_words outside 0 .. 2^31 - 1; area_thresh < 0; modes
+ * outside 1 .. 3; seg_cap outside 1 .. 2^31 - 1.
+ * Rule: 8-connected components of the foreground are islands, 8-connected components of the complement are holes, the ones
+ * that touch the border included; a component of area < area_thresh is removed / filled; in islands mode, when every component
+ * is small, the largest survives, the first in raster (row-major) order of its first pixel among equals.  Padding bits beyond
+ * H in a column word are neither foreground nor background.
+ * out_slots [S, out_slot_words] / out_table [S,4]: what hgl_rle_encode_device writes for the cleaned mask at H_g x W_g: form 0
+ * whenever the counts fit out_slot_words, form 1 when they do not but the plane does, else form 2; words beyond what the form
+ * defines are not written.  With nothing to remove this is the canonical re-encoding of the input (zero-length runs gone).
+ * boxes_xyxy: device [S,4] int32, the hgl_mask_boxes rule for the cleaned mask.
+ * result: device [S,4] int32 = (code, area after, changed, area before); changed bit 0: the holes pass found a small component,
+ * bit 1: the islands pass did (also when it was the one island that stays) -- the `changed` flags of the pixel entries.
+ * Code 2 (the slot holds no mask): table row (0, 3, 0, 0), slot untouched, box zeros, result (2, 0, 0, 0).
+ * seg_cap: the column segments per entry and colour the workspace is sized for.  A form-0 entry of n counts has at most
+ * (n + 1) / 2 + W of either colour, any entry at most W * ceil(H / 2).  An entry that needs more, in a pass that runs, is refused
+ * with code 3 and the outputs of code 2 -- never truncated.
+ * ws: hgl_rle_clean_workspace_bytes for the same geometry (HGL_EWORKSPACE when smaller): the set's run starts, status and bit
+ * planes, one 32-bit word per 64-bit plane word, and 5 * min(seg_cap, the largest W * ceil(H / 2)) 32-bit words per entry.  The
+ * query returns 0 for a geometry the call refuses and for S = 0, which needs no workspace and takes ws = NULL.
+ * The outputs must not overlap the inputs. */
+size_t hgl_rle_clean_workspace_bytes(const int64_t* images_host, int G, int S, long long slot_words, long long seg_cap);
+int hgl_rle_clean_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S,
+                         const int64_t* images_host, int G, int area_thresh, int modes, long long seg_cap,
+                         uint32_t* out_slots, long long out_slot_words, int32_t* out_table,
+                         int32_t* boxes_xyxy, int32_t* result, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

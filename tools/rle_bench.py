@@ -51,6 +51,13 @@
              the kept lists read back, the kept rows re-packed with numpy and uploaded; equality of the two paths is checked
              before any timing; writes profiles/rle_select_bench.json as well
 
+  clean      (--clean, instead of the legs above) a stored set re-tuned to another min_mask_region_area: ONE
+             ops.rle_remove_small_regions call (mode both, area 100) for 64 entries of 640 x 640 -- blobs with a handful of small
+             islands and holes each, packed runs as a store holds them -- against the pixel path built from the existing entries
+             (ops.rle_decode_group -> sam.remove_small_regions holes -> sam.remove_small_regions_boxes islands -> ops.rle_encode),
+             outputs pre-allocated on both sides, HIP events, three alternating rounds; the workspace bytes of either path;
+             equality of the two paths is checked before any timing; writes profiles/rle_clean_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
     python tools/rle_bench.py --decode [--reps 30]
     python tools/rle_bench.py --match [--reps 30]
@@ -58,6 +65,7 @@
     python tools/rle_bench.py --merge [--reps 30]
     python tools/rle_bench.py --nms [--reps 30]
     python tools/rle_bench.py --select [--reps 20]
+    python tools/rle_bench.py --clean [--reps 30]
 """
 import argparse
 import json
@@ -490,6 +498,61 @@ def select_leg(dev, reps, H=640, W=640, G=16, thr=0.7):
     return rec
 
 
+def clean_leg(dev, reps, H=640, W=640, S=64, area=100):
+    """ops.rle_remove_small_regions (mode both) against the pixel path -- rle_decode_group -> remove_small_regions holes ->
+    remove_small_regions_boxes islands -> rle_encode -- on S entries as a store holds them: packed counts (ops.rle_pack), form 0,
+    blobs with a handful of small islands and holes each.  Outputs pre-allocated on both sides; the workspace of either path in
+    bytes: what the entry's query states, and for the pixel path the three [S,H,W] byte arrays, the union-find planes of the
+    clean-up and the planes of the decoder and the encoder."""
+    from hybridgl_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(31)
+    m = blobs(S, H, W, 29)
+    for i in range(S):      # speckle: 12 islands and 12 holes of 1 .. 40 pixels
+        for _ in range(24):
+            y, x, h, w = int(rng.integers(0, H - 8)), int(rng.integers(0, W - 8)), int(rng.integers(1, 6)), int(rng.integers(1, 9))
+            m[i, y:y + h, x:x + w] ^= 1
+    rles = [hsam.mask_to_rle(k)["counts"] for k in m]
+    slots, table = ops.rle_pack(rles, H, W, device=dev)
+    sw = int(slots.shape[1])
+    cap = sw // 2 + W + 1
+    osw = ops.rle_slot_words(H, W)
+    sizes, counts = [(H, W)], [S]
+    out = torch.empty(S * (12 + osw), dtype=torch.int32, device=dev)
+    run_new = lambda: ops.rle_remove_small_regions(slots, table, sizes, counts, area, "both", seg_cap=cap, slot_words=osw, out=out)
+    pix = torch.empty(S * H * W, dtype=torch.uint8, device=dev)
+    aux = torch.empty((2, S, 4), dtype=torch.int32, device=dev)
+    m1, m2 = torch.empty((S, H, W), dtype=torch.uint8, device=dev), torch.empty((S, H, W), dtype=torch.uint8, device=dev)
+    c1, c2 = torch.empty(S, dtype=torch.uint8, device=dev), torch.empty(S, dtype=torch.uint8, device=dev)
+    nb = torch.empty((S, 4), dtype=torch.int32, device=dev)
+    enc = torch.empty(S * (4 + osw), dtype=torch.int32, device=dev)
+
+    def run_pixels():
+        masks, _, _ = ops.rle_decode_group(slots, table, sizes, counts, out=pix, aux=aux)
+        hsam.remove_small_regions(masks[0], area, "holes", out=(m1, c1))
+        hsam.remove_small_regions_boxes(m1, area, "islands", out=(m2, c2, nb))
+        return ops.rle_encode(m2, slot_words=osw, out=enc)
+
+    s_new, t_new, b_new, r_new = run_new()
+    s_pix, t_pix = run_pixels()
+    torch.cuda.synchronize()
+    assert torch.equal(t_new, t_pix) and torch.equal(b_new, nb) and torch.equal(r_new[:, 2], (c1 | (c2 << 1)).to(torch.int32))
+    n_counts = t_new[:, 0].cpu().numpy()
+    for i in range(S):
+        assert torch.equal(s_new[i, :n_counts[i]], s_pix[i, :n_counts[i]])
+    images = ops.rle_clean_layout(sizes, counts)
+    ws_new = int(lib.hgl_rle_clean_workspace_bytes(images.ctypes.data, 1, S, sw, cap))
+    ws_pix = (3 * S * H * W + int(lib.hgl_remove_small_regions_workspace_bytes(S, H, W)) + int(lib.hgl_rle_decode_group_workspace_bytes(S, sw))
+              + int(lib.hgl_rle_encode_workspace_bytes(S, H, W)))
+    rounds = [(device_spread(run_new, reps), device_spread(run_pixels, reps)) for _ in range(3)]      # alternating: the spread between rounds shows
+    new, old = rounds[1]      # the middle round stands; all three are reported
+    return {"S": S, "H": H, "W": W, "area_thresh": area, "slot_words": sw, "seg_cap": cap, "changed": int((r_new[:, 2] != 0).sum()),
+            "rle_clean": new, "pixel_path": old, "ratio_pixel_over_clean": round(old["median_us"] / new["median_us"], 2),
+            "workspace_bytes_rle_clean": ws_new, "workspace_bytes_pixel_path": ws_pix,
+            "workspace_ratio_pixel_over_clean": round(ws_pix / ws_new, 2),
+            "rounds_median_us": [[r[0]["median_us"], r[1]["median_us"]] for r in rounds]}
+
+
 def polygons_leg(dev, reps, cli_images):
     import shutil
     import subprocess
@@ -595,6 +658,8 @@ def main():
                     help="measure rle_nms against the rle_match matrix walked in numpy; writes profiles/rle_nms_bench.json")
     ap.add_argument("--select", action="store_true",
                     help="measure rle_select against a device copy and the host re-pack; writes profiles/rle_select_bench.json")
+    ap.add_argument("--clean", action="store_true",
+                    help="measure rle_remove_small_regions against decode -> clean -> encode; writes profiles/rle_clean_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
@@ -605,6 +670,14 @@ def main():
     if args.polygons:
         out = {"polygons": polygons_leg(dev, args.reps, args.cli_images), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_polygons_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
+    if args.clean:
+        out = {"clean": clean_leg(dev, args.reps), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_clean_bench.json")
         with open(path, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
