@@ -73,6 +73,24 @@ def _pack(strings, H, W, device):
     return ops.rle_pack([rle_counts_from_string(s) for s in strings], H, W, device=device)
 
 
+def _stack_masks(targets, H, W):
+    """mask targets [H,W] bool / uint8 as one uint8 [n,H,W] for ops.rle_encode (a bool tensor is reinterpreted, not converted)"""
+    import torch
+    return torch.stack([t.reshape(H, W).to(torch.uint8) if t.dtype != torch.bool else t.reshape(H, W).view(torch.uint8) for t in targets])
+
+
+def _polygon_runs(who, names, entries, sizes, counts, device=None):
+    """(slots, table) of polygon targets, rasterised on the device by ONE ops.rle_from_polygons call (sizes, counts: its images);
+    ValueError in the name of the caller `who` for the first entry that is refused, which names[k] names"""
+    from . import ops
+    slots, table, status = ops.rle_from_polygons(entries, sizes, counts, rule="once", device=device)
+    code = status.cpu().numpy()[:, 0]
+    if (code != 0).any():
+        k = int(np.flatnonzero(code != 0)[0])
+        raise ValueError(f"{who}: the polygons of {names[k]} are refused (status {int(code[k])})")
+    return slots, table
+
+
 def _batches(keys, by_size_of, batch):
     """keys grouped by image size, at most `batch` per group: [((H, W), [key, ...])]"""
     groups = {}
@@ -128,16 +146,11 @@ def score(records, targets, batch=32):
         keys = [k for k, _ in items]
         n = len(keys)
         if isinstance(items[0][1], PolygonTarget):      # a flush holds one kind of target
-            s1, t1, status = ops.rle_from_polygons([t.polygons for _, t in items], [(H, W)], [n], rule="once")
+            s1, t1 = _polygon_runs("score", keys, [t.polygons for _, t in items], [(H, W)], [n])
             dev = s1.device
-            status = status.cpu().numpy()
-            if (status[:, 0] != 0).any():
-                raise ValueError(f"score: the polygons of {keys[int(np.flatnonzero(status[:, 0] != 0)[0])]} are refused "
-                                 f"(status {int(status[status[:, 0] != 0][0, 0])})")
             sg, tg = s1.repeat(len(MASKS), 1), t1.repeat(len(MASKS), 1)
         else:
-            gt = torch.stack([t.reshape(H, W).to(torch.uint8) if t.dtype != torch.bool else t.reshape(H, W).view(torch.uint8)
-                              for _, t in items])
+            gt = _stack_masks([t for _, t in items], H, W)
             dev = gt.device
             sel = torch.arange(n, device=dev).repeat(len(MASKS))
             sg, tg = ops.rle_encode(gt, sel)

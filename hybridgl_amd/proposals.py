@@ -262,12 +262,53 @@ class ProposalRecorder:
 
 class _Rows:
     """the proposals of one stored image, packed on a loader thread: ONE pinned int32 buffer = table [n,4] | slots [n,sw] |
-    the bits of predicted_iou [n] | of stability_score [n], and the stored boxes for the check"""
-    __slots__ = ("n", "H", "W", "sw", "buf", "bbox", "area")
+    the bits of predicted_iou [n] | of stability_score [n] (| of area [n], where the walk is ordered by it), the numpy views of
+    its parts (_split_group), and the stored boxes for the check"""
+    __slots__ = ("n", "H", "W", "sw", "buf", "table", "slots", "iou", "stab", "area", "bbox")
 
 
 class _Stored:
-    __slots__ = ("ids", "sizes", "counts", "first", "rows", "masks", "boxes", "iou", "stab", "host", "ev", "overflow", "thinned")
+    __slots__ = ("ids", "sizes", "counts", "first", "rows", "masks", "boxes", "iou", "stab", "host", "ev", "overflow")
+
+
+def _split_group(flat, S, sw):
+    """(slots [S,sw], table [S,4], cols [2,S] = the bits of predicted_iou | of stability_score, area bits [S] or nothing) as
+    views of a flat int32 buffer that holds S entries in the layout of _Rows.buf -- an image's rows, a staged group or its
+    upload: numpy array and tensor alike"""
+    slots, table = ops.rle_split(flat, S, sw)
+    return slots, table, flat[S * (4 + sw):S * (6 + sw)].reshape(2, S), flat[S * (6 + sw):S * (7 + sw)]
+
+
+def _group_words(S, sw, area):
+    """the int32 words of that layout"""
+    return S * (6 + sw + bool(area))
+
+
+def _stage_group(rows, counts, area, buf):
+    """The host half of a group: the first counts[g] entries of every image's rows, image after image, into the int32 numpy
+    buffer `buf` as table [S,4] | slots [S,sw] | iou bits [S] | stab bits [S] (| area bits [S] with `area`).  Returns (S, sw,
+    first [G+1]: where each image's entries begin); sw is the widest slot among the images that contribute an entry, and words
+    beyond an entry's n_counts stay as the buffer had them: they are never read.  _group_words(S, sw, area) words are written."""
+    first = np.cumsum([0] + [int(n) for n in counts])
+    S = int(first[-1])
+    if S == 0:
+        return 0, 0, first
+    sw = max(r.sw for r, n in zip(rows, counts) if n)
+    slots, table, cols, extra = _split_group(buf, S, sw)
+    for r, n, e in zip(rows, counts, first):
+        if n:
+            table[e:e + n] = r.table[:n]
+            slots[e:e + n, :r.sw] = r.slots[:n]
+            cols[0, e:e + n] = r.iou[:n]
+            cols[1, e:e + n] = r.stab[:n]
+            if area:
+                extra[e:e + n] = r.area[:n]
+    return S, sw, first
+
+
+def _undecoded(store, image_id, entry, code, what="mask of the stated size"):
+    return ValueError(f"proposal store {store.directory}: image {image_id} entry {entry}: its counts do not decode to a {what} "
+                      f"(status {code})")
 
 
 class StoredProposals:
@@ -342,35 +383,23 @@ class StoredProposals:
         return rows
 
     def _load(self, image_id, size):
-        from .sam import rle_counts_from_string
         recs = self.store.records(image_id)
         rows = _Rows()
-        rows.n = len(recs)
+        n = rows.n = len(recs)
         rows.H, rows.W = (int(v) for v in (size if size is not None else (recs[0]["segmentation"]["size"] if recs else (0, 0))))
-        counts = []
-        for k, r in enumerate(recs):
-            if [int(v) for v in r["segmentation"]["size"]] != [rows.H, rows.W]:
-                raise ValueError(f"proposal store {self.store.directory}: image {image_id} entry {k}: size "
-                                 f"{r['segmentation']['size']} differs from the image's {[rows.H, rows.W]}")
-            try:
-                counts.append(rle_counts_from_string(r["segmentation"]["counts"]))
-            except Exception as e:
-                raise ValueError(f"proposal store {self.store.directory}: image {image_id} entry {k}: bad counts string ({e})") from None
-        n = rows.n
+        _, counts = _record_runs(self.store, image_id, recs, (rows.H, rows.W))
+        by_area = self.mask_nms_thresh is not None and self.mask_nms_score == "area"
         rows.sw = max([len(c) for c in counts] + [1])
-        rows.buf = torch.zeros(n * (6 + rows.sw), dtype=torch.int32, pin_memory=torch.cuda.is_available())
-        h = rows.buf.numpy()
-        slots, table = ops.rle_split(h, n, rows.sw)
+        rows.buf = torch.zeros(_group_words(n, rows.sw, by_area), dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        rows.slots, rows.table, (rows.iou, rows.stab), rows.area = _split_group(rows.buf.numpy(), n, rows.sw)
         for k, c in enumerate(counts):
-            table[k, 0] = len(c)
-            slots[k, :len(c)] = np.asarray(c, dtype=np.uint32).view(np.int32)
-        tail = h[n * (4 + rows.sw):].view(np.float32)
-        tail[:n] = [r["predicted_iou"] for r in recs]
-        tail[n:] = [r["stability_score"] for r in recs]
+            rows.table[k, 0] = len(c)
+            rows.slots[k, :len(c)] = np.asarray(c, dtype=np.uint32).view(np.int32)
+        rows.iou.view(np.float32)[:] = [r["predicted_iou"] for r in recs]
+        rows.stab.view(np.float32)[:] = [r["stability_score"] for r in recs]
+        if by_area:
+            rows.area.view(np.float32)[:] = [float(r["area"]) for r in recs]
         rows.bbox = np.asarray([r["bbox"] for r in recs], dtype=np.int64).reshape(n, 4)
-        rows.area = None
-        if self.mask_nms_thresh is not None and self.mask_nms_score == "area":
-            rows.area = np.asarray([float(r["area"]) for r in recs], dtype=np.float32)
         return rows
 
     # ---- device half (the loop's thread)
@@ -388,51 +417,46 @@ class StoredProposals:
             raise ValueError("StoredProposals: the image ids of the group are needed (RefBatch.image_id)")
         st = _Stored()
         st.overflow = 0
-        st.thinned = None
         st.ids = list(image_ids)
         st.sizes = [tuple(int(v) for v in im.shape[:2]) for im in images]
         st.rows = [self.prefetch(iid, size) for iid, size in zip(st.ids, st.sizes)]
+        thin = self.mask_nms_thresh is not None
+        by_area = thin and self.mask_nms_score == "area"
         caps = [c for c in (cap, self.cap) if c]
-        if self.mask_nms_thresh is not None:
-            return self._begin_thinned(st, min(caps) if caps else None, encoded_event)
-        st.counts = [min([r.n] + caps) for r in st.rows]
-        st.first = np.cumsum([0] + st.counts)
-        S = int(st.first[-1])
+        # thinning: every stored entry goes up, and the caps apply to the survivors
+        st.counts = [r.n if thin else min([r.n] + caps) for r in st.rows]
         if encoded_event is not None:      # there is no encoder pass to wait for
             encoded_event.record(torch.cuda.current_stream(self.device))
         st.ev = None
+        # (room for the group however wide its slots are; a group without an entry stages nothing)
+        room = _group_words(sum(st.counts), max([r.sw for r in st.rows] + [0]), by_area)
+        host = self._staging(room) if room else torch.empty(0, dtype=torch.int32)
+        S, sw, st.first = _stage_group(st.rows, st.counts, by_area, host.numpy())
         if S == 0:
             return st
-        sw = max(r.sw for r, n in zip(st.rows, st.counts) if n)
-        numel = S * (6 + sw)
-        host = self._staging(numel)
-        h = host.numpy()[:numel]
-        slots, table = ops.rle_split(h, S, sw)
-        tail = h[S * (4 + sw):]
-        for r, n, e in zip(st.rows, st.counts, st.first):
-            if n == 0:
-                continue
-            rs, rt = ops.rle_split(r.buf.numpy(), r.n, r.sw)
-            table[e:e + n] = rt[:n]
-            slots[e:e + n, :r.sw] = rs[:n]      # words beyond an entry's n_counts are never read
-            rtail = r.buf.numpy()[r.n * (4 + r.sw):]
-            tail[e:e + n] = rtail[:n]
-            tail[S + e:S + e + n] = rtail[r.n:r.n + n]
+        G, numel = len(st.rows), _group_words(S, sw, by_area)
         dev = torch.empty(numel, dtype=torch.int32, device=self.device)
         dev.copy_(host[:numel], non_blocking=True)
         up = torch.cuda.Event()
         up.record()
         self._free.append((host, up))
-        dslots, dtable = ops.rle_split(dev, S, sw)
-        st.iou = dev[S * (4 + sw):S * (5 + sw)].view(torch.float32)
-        st.stab = dev[S * (5 + sw):].view(torch.float32)
-        # boxes and status share one buffer and leave in one copy into pooled pinned memory; group_cleanup reads it, where
-        # SAM reads its first counts, and hands the buffer back
-        aux = torch.empty((2, S, 4), dtype=torch.int32, device=self.device)
-        st.masks, st.boxes = self._decode(dslots, dtable, st.sizes, st.counts, aux)[:2]
-        fits = self._back and self._back[-1].numel() >= 8 * S
-        st.host = self._back.pop() if fits else torch.empty(max(8 * S, 4096), dtype=torch.int32, pin_memory=True)
-        st.host[:8 * S].copy_(aux.view(-1), non_blocking=True)
+        slots, table, cols, area = _split_group(dev, S, sw)
+        # ONE int32 buffer leaves in one copy into pooled pinned memory: boxes | status and, thinning, | out_src | out_n | the
+        # NMS's out_idx, result, out_n; group_cleanup reads it, where SAM reads its first counts, and hands the buffer back
+        back = torch.empty(14 * S + 2 * G if thin else 8 * S, dtype=torch.int32, device=self.device)
+        if thin:
+            scores = {"predicted_iou": cols[0], "stability_score": cols[1], "area": area, "stored": None}[self.mask_nms_score]
+            if scores is not None:
+                scores = scores.view(torch.float32)
+            result = ops.rle_nms(slots, table, st.sizes, st.counts, scores, self.mask_nms_thresh, self.mask_nms_metric,
+                                 out=back[9 * S + G:])[2]
+            slots, table, cols, _, _ = ops.rle_select(slots, table, st.sizes, st.counts, nms_result=result, cols=cols,
+                                                      max_keep=min(caps) if caps else None, back=back[8 * S:9 * S + G])
+        st.iou, st.stab = cols[0].view(torch.float32), cols[1].view(torch.float32)
+        st.masks, st.boxes = self._decode(slots, table, st.sizes, st.counts, back[:8 * S].view(2, S, 4))[:2]
+        fits = self._back and self._back[-1].numel() >= back.numel()
+        st.host = self._back.pop() if fits else torch.empty(max(back.numel(), 4096), dtype=torch.int32, pin_memory=True)
+        st.host[:back.numel()].copy_(back, non_blocking=True)
         st.ev = torch.cuda.Event()
         st.ev.record()
         return st
@@ -441,112 +465,48 @@ class StoredProposals:
         """the group's pixels, boxes (aux[0]) and status (aux[1]): two launches whatever the group holds"""
         return ops.rle_decode_group(slots, table, sizes, counts, aux=aux)
 
-    # ---- thinning on load (mask_nms_thresh): the same three calls over nms -> select -> decode
-    def _begin_thinned(self, st, cap, encoded_event):
-        st.counts = [r.n for r in st.rows]      # every stored entry goes up: the caps apply to the survivors
-        st.first = np.cumsum([0] + st.counts)
-        S, G = int(st.first[-1]), len(st.rows)
-        if encoded_event is not None:
-            encoded_event.record(torch.cuda.current_stream(self.device))
-        st.ev = None
-        st.thinned = cap
-        if S == 0:
-            return st
-        by_area = self.mask_nms_score == "area"
-        sw = max(r.sw for r in st.rows if r.n)
-        numel = S * (6 + sw + (1 if by_area else 0))
-        host = self._staging(numel)
-        h = host.numpy()[:numel]
-        slots, table = ops.rle_split(h, S, sw)
-        tail = h[S * (4 + sw):]
-        for r, n, e in zip(st.rows, st.counts, st.first):
-            if n == 0:
-                continue
-            rs, rt = ops.rle_split(r.buf.numpy(), n, r.sw)
-            table[e:e + n] = rt
-            slots[e:e + n, :r.sw] = rs      # words beyond an entry's n_counts are never read
-            rtail = r.buf.numpy()[n * (4 + r.sw):]
-            tail[e:e + n] = rtail[:n]
-            tail[S + e:S + e + n] = rtail[n:]
-            if by_area:
-                tail[2 * S + e:2 * S + e + n] = r.area.view(np.int32)
-        dev = torch.empty(numel, dtype=torch.int32, device=self.device)
-        dev.copy_(host[:numel], non_blocking=True)
-        up = torch.cuda.Event()
-        up.record()
-        self._free.append((host, up))
-        dslots, dtable = ops.rle_split(dev, S, sw)
-        cols = dev[S * (4 + sw):S * (6 + sw)].view(2, S)      # predicted_iou | stability_score, as bits
-        scores = {"predicted_iou": cols[0], "stability_score": cols[1], "area": dev[S * (6 + sw):], "stored": None}[self.mask_nms_score]
-        if scores is not None:
-            scores = scores.view(torch.float32)
-        # ONE int32 buffer leaves in one copy: boxes | status | out_src | out_n | the NMS's out_idx, result, out_n
-        back = torch.empty(8 * S + (S + G) + (5 * S + G), dtype=torch.int32, device=self.device)
-        result = ops.rle_nms(dslots, dtable, st.sizes, st.counts, scores, self.mask_nms_thresh, self.mask_nms_metric,
-                             out=back[9 * S + G:])[2]
-        cslots, ctable, ccols, _, _ = ops.rle_select(dslots, dtable, st.sizes, st.counts, nms_result=result, cols=cols, max_keep=cap,
-                                                     back=back[8 * S:9 * S + G])
-        st.iou, st.stab = ccols[0].view(torch.float32), ccols[1].view(torch.float32)
-        st.masks, st.boxes = self._decode(cslots, ctable, st.sizes, st.counts, back[:8 * S].view(2, S, 4))[:2]
-        fits = self._back and self._back[-1].numel() >= back.numel()
-        st.host = self._back.pop() if fits else torch.empty(max(back.numel(), 4096), dtype=torch.int32, pin_memory=True)
-        st.host[:back.numel()].copy_(back, non_blocking=True)
-        st.ev = torch.cuda.Event()
-        st.ev.record()
-        return st
-
-    def _cleanup_thinned(self, st):
-        S, G = int(st.first[-1]), len(st.rows)
-        st.ev.synchronize()
-        h = st.host.numpy()[:14 * S + 2 * G].copy()
-        self._back.append(st.host)
-        st.host = None
-        boxes, status = h[:8 * S].reshape(2, S, 4)
-        out_src, out_n = h[8 * S:9 * S], h[9 * S:9 * S + G]
-        codes = h[10 * S + G:14 * S + G].reshape(S, 4)[:, 0]      # the NMS's result rows: every source entry's code
-        kept = []
-        for g, (iid, r, n, e) in enumerate(zip(st.ids, st.rows, st.counts, st.first)):
-            bad = np.flatnonzero(codes[e:e + n] != 0)
-            if len(bad):
-                raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {int(bad[0])}: its counts do not decode to a "
-                                 f"{r.H} x {r.W} mask (status {int(codes[e + bad[0]])})")
-            k = int(out_n[g])
-            for p in range(k):
-                src, code = int(out_src[e + p]), int(status[e + p, 0])
-                if code != 0:
-                    raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {src}: its counts do not decode to a "
-                                     f"{r.H} x {r.W} mask (status {code})")
-                x0, y0, x1, y1 = (int(v) for v in boxes[e + p])
-                if int(status[e + p, 1]) > 0 and [x0, y0, x1 - x0, y1 - y0] != r.bbox[src].tolist():
-                    raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {src}: the stored bbox "
-                                     f"{r.bbox[src].tolist()} is not the box of its mask {[x0, y0, x1 - x0, y1 - y0]}")
-            kept.append(k)
-            self._thinned[iid] = (n, k)
-        st.masks = [m[:k] for m, k in zip(st.masks, kept)]
-        st.counts = kept      # st.first keeps the uploaded layout: the survivors lead every image's range
-        return st
+    def _check_image(self, iid, r, codes, srcs, boxes, status):
+        """what a store is held to, image by image: every uploaded entry decodes (codes: the NMS's, where it ran), and of the
+        entries handed out (position p is record srcs[p]) the first that did not decode, or whose stored bbox is not the box
+        of its mask, raises -- its status before its box"""
+        what = f"{r.H} x {r.W} mask"
+        bad = np.flatnonzero(codes != 0)
+        if len(bad):
+            raise _undecoded(self.store, iid, int(bad[0]), int(codes[bad[0]]), what)
+        xywh = np.concatenate([boxes[:, :2], boxes[:, 2:] - boxes[:, :2]], 1)
+        # (an empty mask has no box: the reference stores its zero box moved by the crop's origin, whatever that is)
+        off = (status[:, 1] > 0) & (xywh != r.bbox[srcs]).any(1)
+        bad = np.flatnonzero((status[:, 0] != 0) | off)
+        if len(bad):
+            p = int(bad[0])
+            k = int(srcs[p])
+            if status[p, 0] != 0:
+                raise _undecoded(self.store, iid, k, int(status[p, 0]), what)
+            raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {k}: the stored bbox "
+                             f"{r.bbox[k].tolist()} is not the box of its mask {xywh[p].tolist()}")
 
     def group_cleanup(self, st):
         if st.ev is None:
             return st
-        if self.mask_nms_thresh is not None:
-            return self._cleanup_thinned(st)
+        thin = self.mask_nms_thresh is not None
+        S, G = int(st.first[-1]), len(st.rows)
         st.ev.synchronize()
-        S = int(st.first[-1])
-        boxes, status = st.host.numpy()[:8 * S].reshape(2, S, 4).copy()
+        h = st.host.numpy()[:14 * S + 2 * G if thin else 8 * S].copy()
         self._back.append(st.host)
         st.host = None
+        boxes, status = h[:8 * S].reshape(2, S, 4)
+        out_src, out_n = h[8 * S:9 * S], h[9 * S:9 * S + G]      # (these three are empty without thinning)
+        codes = h[10 * S + G:14 * S + G].reshape(-1, 4)[:, 0]      # the NMS's result rows: every source entry's code
+        kept = []
         for g, (iid, r, n, e) in enumerate(zip(st.ids, st.rows, st.counts, st.first)):
-            for k in range(n):
-                code = int(status[e + k, 0])
-                if code != 0:
-                    raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {k}: its counts do not decode to a "
-                                     f"{r.H} x {r.W} mask (status {code})")
-                x0, y0, x1, y1 = (int(v) for v in boxes[e + k])
-                # (an empty mask has no box: the reference stores its zero box moved by the crop's origin, whatever that is)
-                if int(status[e + k, 1]) > 0 and [x0, y0, x1 - x0, y1 - y0] != r.bbox[k].tolist():
-                    raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {k}: the stored bbox "
-                                     f"{r.bbox[k].tolist()} is not the box of its mask {[x0, y0, x1 - x0, y1 - y0]}")
+            k = int(out_n[g]) if thin else n
+            self._check_image(iid, r, codes[e:e + n], out_src[e:e + k] if thin else np.arange(k), boxes[e:e + k], status[e:e + k])
+            kept.append(k)
+            if thin:
+                self._thinned[iid] = (n, k)
+        if thin:
+            st.masks = [m[:k] for m, k in zip(st.masks, kept)]
+            st.counts = kept      # st.first keeps the uploaded layout: the survivors lead every image's range
         return st
 
     def group_finish(self, st):
@@ -576,15 +536,18 @@ def _store(x):
     return x if isinstance(x, ProposalStore) else ProposalStore(x)
 
 
-def _record_runs(store, image_id, recs):
-    """(size (H, W) or None for an empty list, the run lists of the records)"""
+def _record_runs(store, image_id, recs, expect=None):
+    """(size (H, W), the run lists of the records).  expect: the image's size, which every record must state; without it the
+    records must agree with entry 0 on a size an image can have, and the size of an empty list is None"""
     from .sam import rle_counts_from_string
-    size, runs = None, []
+    size, runs = expect, []
     for k, r in enumerate(recs):
         hw = tuple(int(v) for v in r["segmentation"]["size"])
-        if size is None:
-            size = hw
-        if hw != size or hw[0] <= 0 or hw[1] <= 0 or hw[0] * hw[1] >= 1 << 31:
+        if expect is not None and hw != tuple(expect):
+            raise ValueError(f"proposal store {store.directory}: image {image_id} entry {k}: size {r['segmentation']['size']} "
+                             f"differs from the image's {list(expect)}")
+        size = size or hw
+        if expect is None and (hw != size or hw[0] <= 0 or hw[1] <= 0 or hw[0] * hw[1] >= 1 << 31):
             raise ValueError(f"proposal store {store.directory}: image {image_id} entry {k}: size {list(hw)} "
                              + (f"differs from entry 0's {list(size)}" if hw != size else "is no image size"))
         try:
@@ -613,8 +576,7 @@ def _check_decoded(store, ids, counts, match):
     for iid, n in zip(ids, counts):
         bad = np.flatnonzero(match[e:e + n, 0] != 0)
         if len(bad):
-            raise ValueError(f"proposal store {store.directory}: image {iid} entry {int(bad[0])}: its counts do not decode to a mask "
-                             f"of the stated size (status {int(match[e + bad[0], 0])})")
+            raise _undecoded(store, iid, int(bad[0]), int(match[e + bad[0], 0]))
         e += n
 
 
@@ -704,6 +666,7 @@ def ceiling(store, targets, cap=None, device=None, group=16):
     into run lengths, by ONE ops.rle_from_polygons call and never become pixels; either way they are
     met by the stored runs in ops.rle_match, `group` images per call.  device: where to (None: where the targets are).  cap:
     the first `cap` records of every image, as StoredProposals(cap=).  Rows are sorted by (index, sentence)."""
+    from .predictions import _polygon_runs, _stack_masks
     from .refer_io import PolygonTarget
     store = _store(store)
     rows, runs_of, seen = [], {}, set()
@@ -726,8 +689,7 @@ def ceiling(store, targets, cap=None, device=None, group=16):
             pol = [it for it in its if isinstance(it[1], PolygonTarget)]
             by_image[iid] = its = pix + pol
             if pix:
-                gt = torch.stack([t.reshape(H, W).to(torch.uint8) if t.dtype != torch.bool else t.reshape(H, W).view(torch.uint8)
-                                  for _, t in pix])
+                gt = _stack_masks([t for _, t in pix], H, W)
                 enc.append(ops.rle_encode(gt if device is None else gt.to(device)))
             else:
                 enc.append(None)
@@ -743,12 +705,8 @@ def ceiling(store, targets, cap=None, device=None, group=16):
             return
         dev = next((e[0].device for e in enc if e is not None), device)
         if poly_entries:
-            ps, pt, pst = ops.rle_from_polygons(poly_entries, sizes, poly_counts, rule="once", device=dev)
+            ps, pt = _polygon_runs("ceiling", [f"target {k}" for k in poly_keys], poly_entries, sizes, poly_counts, dev)
             dev = ps.device
-            pst = pst.cpu().numpy()
-            if (pst[:, 0] != 0).any():
-                raise ValueError(f"ceiling: the polygons of target {poly_keys[int(np.flatnonzero(pst[:, 0] != 0)[0])]} are refused "
-                                 f"(status {int(pst[pst[:, 0] != 0][0, 0])})")
             e, parts = 0, []
             for own, n in zip(enc, poly_counts):      # per image: its encoded masks, then its share of the polygon set
                 if own is not None:
@@ -794,6 +752,40 @@ def ceiling(store, targets, cap=None, device=None, group=16):
     return np.asarray(sorted(rows), dtype=np.int64).reshape(-1, 5)
 
 
+def _rewrite(op, src, dst, group, key, settings, extra, work):
+    """What thin and clean share: the store `src` read `group` images at a time and written, image by image, to `dst`, a
+    directory that holds no store yet.  work(chunk [(image_id, records)], sized [_record_runs of each], counts, check), called
+    for a chunk that holds a record at all, does the operation's device work, has check(result [S,4] on the host) raise for an
+    entry that did not decode, and returns per image (the records to write, the image's further counters: one per name in
+    `extra`).  dst's meta is src's plus {key: settings and "source"}.  Returns {"per_image": {image_id: [before, after,
+    *counters]}, "before": total, "after": total, and a total per name in `extra`}."""
+    src, dst = _store(src), _store(dst)
+    if os.path.realpath(src.directory) == os.path.realpath(dst.directory):
+        raise ValueError(f"{op}: the source and the destination are the same directory ({src.directory})")
+    if not os.path.isdir(src.directory):
+        raise ValueError(f"{op}: {src.directory}: no such directory")
+    if os.path.isdir(dst.directory) and any(n.endswith(".json") for n in os.listdir(dst.directory)):
+        raise ValueError(f"{op}: {dst.directory} already holds a store")
+    ids = src.image_ids()
+    per_image = {}
+    step = max(int(group), 1)
+    for c0 in range(0, len(ids), step):
+        chunk = [(iid, src.records(iid)) for iid in ids[c0:c0 + step]]
+        sized = [_record_runs(src, iid, recs) for iid, recs in chunk]
+        counts = [len(runs) for _, runs in sized]
+        out = [([], [0] * len(extra))] * len(chunk)
+        if sum(counts):
+            out = work(chunk, sized, counts, lambda result: _check_decoded(src, [iid for iid, _ in chunk], counts, result))
+        for (iid, recs), (kept, counters) in zip(chunk, out):
+            dst.write(iid, kept)
+            per_image[iid] = [len(recs), len(kept)] + list(counters)
+    meta = dict(src.meta())
+    meta[key] = dict(settings, source=src.directory)
+    dst.write_meta(meta)
+    return {"per_image": per_image,
+            **{name: sum(v[i] for v in per_image.values()) for i, name in enumerate(["before", "after"] + list(extra))}}
+
+
 THIN_SCORES = ("predicted_iou", "stability_score", "area", "stored")
 
 
@@ -804,7 +796,7 @@ def thin(src, dst, thr, metric="iou", score="predicted_iou", group=16, device=No
     it; metric "iou" or "containment" (I / the smaller area: a part nested in a whole, or the whole, whichever comes later).
     score: the record field the walk is ordered by, descending, the stored index breaking ties -- "predicted_iou",
     "stability_score" or "area" (compared as float32) -- or "stored": the stored order itself.  dst's meta is src's plus
-    {"thinned": {"thr", "metric", "score", "source"}}.  ValueError for dst == src, for a dst that already holds a store, for an
+    {"thinned": {"thr", "metric", "score", "source"}}.  ValueError for dst == src, for a dst that holds a store already, for an
     unknown score or metric and for a record that does not decode.  An image may hold at most 4096 records.
     Returns {"per_image": {image_id: [before, after]}, "before": total, "after": total}."""
     if metric not in ops.NMS_METRIC:
@@ -814,40 +806,21 @@ def thin(src, dst, thr, metric="iou", score="predicted_iou", group=16, device=No
     thr = float(thr)
     if thr != thr:
         raise ValueError("thin: the threshold is NaN")
-    src, dst = _store(src), _store(dst)
-    if os.path.realpath(src.directory) == os.path.realpath(dst.directory):
-        raise ValueError(f"thin: the source and the destination are the same directory ({src.directory})")
-    if not os.path.isdir(src.directory):
-        raise ValueError(f"thin: {src.directory}: no such directory")
-    if os.path.isdir(dst.directory) and any(n.endswith(".json") for n in os.listdir(dst.directory)):
-        raise ValueError(f"thin: {dst.directory} already holds a store")
-    ids = src.image_ids()
-    per_image = {}
-    step = max(int(group), 1)
-    for c0 in range(0, len(ids), step):
-        chunk = [(iid, src.records(iid)) for iid in ids[c0:c0 + step]]
-        sized = [_record_runs(src, iid, recs) for iid, recs in chunk]
-        counts = [len(runs) for _, runs in sized]
-        kept = [[] for _ in chunk]
-        if sum(counts):
-            slots, table = _pack([r for _, runs in sized for r in runs], device)
-            scores = None
-            if score != "stored":
-                scores = torch.tensor([float(r[score]) for _, recs in chunk for r in recs], dtype=torch.float32).to(slots.device)
-            out_idx, out_n, result = ops.rle_nms(slots, table, [size or (1, 1) for size, _ in sized], counts, scores, thr, metric)
-            out_idx, out_n, result = (x.cpu().numpy().astype(np.int64) for x in (out_idx, out_n, result))
-            _check_decoded(src, [iid for iid, _ in chunk], counts, result)
-            e = 0
-            for k, n in enumerate(counts):
-                kept[k] = sorted(int(i) for i in out_idx[e:e + int(out_n[k])])
-                e += n
-        for (iid, recs), keep in zip(chunk, kept):
-            dst.write(iid, [recs[i] for i in keep])
-            per_image[iid] = [len(recs), len(keep)]
-    meta = dict(src.meta())
-    meta["thinned"] = {"thr": thr, "metric": metric, "score": score, "source": src.directory}
-    dst.write_meta(meta)
-    return {"per_image": per_image, "before": sum(v[0] for v in per_image.values()), "after": sum(v[1] for v in per_image.values())}
+    def kept(chunk, sized, counts, check):
+        slots, table = _pack([r for _, runs in sized for r in runs], device)
+        scores = None
+        if score != "stored":
+            scores = torch.tensor([float(r[score]) for _, recs in chunk for r in recs], dtype=torch.float32).to(slots.device)
+        out_idx, out_n, result = ops.rle_nms(slots, table, [size or (1, 1) for size, _ in sized], counts, scores, thr, metric)
+        out_idx, out_n, result = (x.cpu().numpy().astype(np.int64) for x in (out_idx, out_n, result))
+        check(result)
+        out, e = [], 0
+        for (_, recs), n, k in zip(chunk, counts, out_n):
+            out.append(([recs[i] for i in sorted(int(i) for i in out_idx[e:e + int(k)])], []))
+            e += n
+        return out
+
+    return _rewrite("thin", src, dst, group, "thinned", {"thr": thr, "metric": metric, "score": score}, [], kept)
 
 
 def clean(src, dst, min_area, nms_thresh=0.7, group=16, device=None):
@@ -859,7 +832,7 @@ def clean(src, dst, min_area, nms_thresh=0.7, group=16, device=None):
     scoring 1.0 and a changed one 0.0 (sam.nms_segments; sam.nms for an image of more than 1024 records).  The kept records are
     written in the NMS's order, the order generate() hands them out in.  A kept record whose mask changed gets a new
     `segmentation`, `area` and `bbox`; its other fields, and an unchanged record, stay as they stood.  dst's meta is src's plus
-    {"cleaned": {"min_area", "nms_thresh", "source"}}.  ValueError for dst == src, for a dst that already holds a store, for a
+    {"cleaned": {"min_area", "nms_thresh", "source"}}.  ValueError for dst == src, for a dst that holds a store already, for a
     negative min_area or a NaN threshold and for a record that does not decode.  An image may hold at most 4096 records.
     Returns {"per_image": {image_id: [before, after, changed among the kept]}, "before": total, "after": total, "changed": total}."""
     from . import sam
@@ -869,69 +842,52 @@ def clean(src, dst, min_area, nms_thresh=0.7, group=16, device=None):
     nms_thresh = float(nms_thresh)
     if nms_thresh != nms_thresh:
         raise ValueError("clean: the threshold is NaN")
-    src, dst = _store(src), _store(dst)
-    if os.path.realpath(src.directory) == os.path.realpath(dst.directory):
-        raise ValueError(f"clean: the source and the destination are the same directory ({src.directory})")
-    if not os.path.isdir(src.directory):
-        raise ValueError(f"clean: {src.directory}: no such directory")
-    if os.path.isdir(dst.directory) and any(n.endswith(".json") for n in os.listdir(dst.directory)):
-        raise ValueError(f"clean: {dst.directory} already holds a store")
-    ids = src.image_ids()
-    per_image = {}
-    step = max(int(group), 1)
-    for c0 in range(0, len(ids), step):
-        chunk = [(iid, src.records(iid)) for iid in ids[c0:c0 + step]]
-        sized = [_record_runs(src, iid, recs) for iid, recs in chunk]
-        counts = [len(runs) for _, runs in sized]
+    def cleaned(chunk, sized, counts, check):
         S = sum(counts)
-        out = [[] for _ in chunk]
-        if S:
-            sizes = [size or (1, 1) for size, _ in sized]
-            slots, table = _pack([r for _, runs in sized for r in runs], device)
-            dev, sw = slots.device, int(slots.shape[1])
-            # an output slot of the plane's size loses no mask: runs where they fit, the bit plane otherwise; rle_from_slot reads either
-            osw = max([sw] + [ops.rle_slot_words(H, W) for (H, W), n in zip(sizes, counts) if n])
-            flat = torch.empty(S * (12 + osw), dtype=torch.int32, device=dev)
-            _, _, boxes, result = ops.rle_remove_small_regions(slots, table, sizes, counts, min_area, "both",
-                                                               seg_cap=sw // 2 + max(W for _, W in sizes) + 1, slot_words=osw, out=flat)
-            boxes = boxes.clone()      # a buffer of its own: the NMS wants its boxes 16-byte aligned, the view lies where S * (4 + osw) words end
-            scores = (result[:, 2] == 0).to(torch.float32)
-            keep = torch.ones(S, dtype=torch.uint8, device=dev)
-            if max(counts) <= 1024:
-                offs = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32).to(dev)
-                order, n = sam.nms_segments(boxes, scores, keep, offs, max(counts), nms_thresh)
-                order, n = order.cpu().numpy().astype(np.int64), n.cpu().numpy().astype(np.int64)
-            else:      # a list of any length, image by image
-                order, n, e = np.zeros(S, np.int64), np.zeros(len(counts), np.int64), 0
-                for k, c in enumerate(counts):
-                    if c:
-                        o, nn = sam.nms(boxes[e:e + c].contiguous(), scores[e:e + c].contiguous(), keep[e:e + c].contiguous(), nms_thresh)
-                        order[e:e + c], n[k] = o.cpu().numpy(), int(nn.cpu()[0])
-                    e += c
-            host = flat.cpu().numpy()
-            h_slots, h_table = ops.rle_split(host, S, osw)
-            h_boxes, h_result = host[S * (4 + osw):].reshape(2, S, 4)
-            _check_decoded(src, [iid for iid, _ in chunk], counts, h_result)
-            e = 0
-            for k, ((iid, recs), (size, _), c) in enumerate(zip(chunk, sized, counts)):
-                for i in order[e:e + int(n[k])]:
-                    r, s = recs[int(i)], e + int(i)
-                    if h_result[s, 2]:
-                        H, W = size
-                        runs = sam.rle_from_slot(h_slots[s], int(h_table[s, 0]), int(h_table[s, 1]), H, W)
-                        x0, y0, x1, y1 = (int(v) for v in h_boxes[s])
-                        r = dict(r, segmentation=sam.coco_encode_rle({"size": [H, W], "counts": runs}), area=int(h_result[s, 1]),
-                                 bbox=[x0, y0, x1 - x0, y1 - y0])
-                    out[k].append((r, bool(h_result[s, 2])))
+        sizes = [size or (1, 1) for size, _ in sized]
+        slots, table = _pack([r for _, runs in sized for r in runs], device)
+        dev, sw = slots.device, int(slots.shape[1])
+        # an output slot of the plane's size loses no mask: runs where they fit, the bit plane otherwise; rle_from_slot reads either
+        osw = max([sw] + [ops.rle_slot_words(H, W) for (H, W), n in zip(sizes, counts) if n])
+        flat = torch.empty(S * (12 + osw), dtype=torch.int32, device=dev)
+        _, _, boxes, result = ops.rle_remove_small_regions(slots, table, sizes, counts, min_area, "both",
+                                                           seg_cap=sw // 2 + max(W for _, W in sizes) + 1, slot_words=osw, out=flat)
+        boxes = boxes.clone()      # a buffer of its own: the NMS wants its boxes 16-byte aligned, the view lies where S * (4 + osw) words end
+        scores = (result[:, 2] == 0).to(torch.float32)
+        keep = torch.ones(S, dtype=torch.uint8, device=dev)
+        if max(counts) <= 1024:
+            offs = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32).to(dev)
+            order, n = sam.nms_segments(boxes, scores, keep, offs, max(counts), nms_thresh)
+            order, n = order.cpu().numpy().astype(np.int64), n.cpu().numpy().astype(np.int64)
+        else:      # a list of any length, image by image
+            order, n, e = np.zeros(S, np.int64), np.zeros(len(counts), np.int64), 0
+            for k, c in enumerate(counts):
+                if c:
+                    o, nn = sam.nms(boxes[e:e + c].contiguous(), scores[e:e + c].contiguous(), keep[e:e + c].contiguous(), nms_thresh)
+                    order[e:e + c], n[k] = o.cpu().numpy(), int(nn.cpu()[0])
                 e += c
-        for (iid, recs), kept in zip(chunk, out):
-            dst.write(iid, [r for r, _ in kept])
-            per_image[iid] = [len(recs), len(kept), sum(1 for _, ch in kept if ch)]
-    meta = dict(src.meta())
-    meta["cleaned"] = {"min_area": min_area, "nms_thresh": nms_thresh, "source": src.directory}
-    dst.write_meta(meta)
-    return {"per_image": per_image, "before": sum(v[0] for v in per_image.values()), "after": sum(v[1] for v in per_image.values()),
-            "changed": sum(v[2] for v in per_image.values())}
+        host = flat.cpu().numpy()
+        h_slots, h_table = ops.rle_split(host, S, osw)
+        h_boxes, h_result = host[S * (4 + osw):].reshape(2, S, 4)
+        check(h_result)
+        out, e = [], 0
+        for k, ((_, recs), (size, _), c) in enumerate(zip(chunk, sized, counts)):
+            kept, changed = [], 0
+            for i in order[e:e + int(n[k])]:
+                r, s = recs[int(i)], e + int(i)
+                if h_result[s, 2]:
+                    H, W = size
+                    runs = sam.rle_from_slot(h_slots[s], int(h_table[s, 0]), int(h_table[s, 1]), H, W)
+                    x0, y0, x1, y1 = (int(v) for v in h_boxes[s])
+                    r = dict(r, segmentation=sam.coco_encode_rle({"size": [H, W], "counts": runs}), area=int(h_result[s, 1]),
+                             bbox=[x0, y0, x1 - x0, y1 - y0])
+                    changed += 1
+                kept.append(r)
+            out.append((kept, [changed]))
+            e += c
+        return out
+
+    return _rewrite("clean", src, dst, group, "cleaned", {"min_area": min_area, "nms_thresh": nms_thresh}, ["changed"], cleaned)
 
 
 def _jsonable(report):
@@ -961,27 +917,21 @@ def main(argv=None):
     k.add_argument("--nms_thresh", type=float, default=0.7, help="the box NMS that follows (the generator's max(box_nms_thresh, crop_nms_thresh))")
     k.add_argument("--json", default="", metavar="OUT", help="also write the per-image counts here")
     args = p.parse_args(argv)
-    if args.cmd == "clean":
+    if args.cmd in ("thin", "clean"):
         try:
-            rep = clean(args.dir_in, args.dir_out, args.min_area, args.nms_thresh)
+            if args.cmd == "thin":
+                rep = thin(args.dir_in, args.dir_out, args.thr, args.metric, args.score)
+            else:
+                rep = clean(args.dir_in, args.dir_out, args.min_area, args.nms_thresh)
         except (OSError, ValueError) as e:
             raise SystemExit(f"hybridgl_amd.proposals: {e}")
-        print(f"images: {len(rep['per_image'])}   proposals: {rep['before']} -> {rep['after']}   changed among the kept: {rep['changed']}")
+        print(f"images: {len(rep['per_image'])}   proposals: {rep['before']} -> {rep['after']}"
+              + (f"   changed among the kept: {rep['changed']}" if "changed" in rep else ""))
         if args.json:
+            names = [name for name in rep if name != "per_image"]      # before, after and what else the operation counts
             with open(args.json, "w") as f:
-                json.dump({"before": rep["before"], "after": rep["after"], "changed": rep["changed"],
-                           "per_image": [{"image_id": i, "before": v[0], "after": v[1], "changed": v[2]} for i, v in rep["per_image"].items()]}, f)
-        return 0
-    if args.cmd == "thin":
-        try:
-            rep = thin(args.dir_in, args.dir_out, args.thr, args.metric, args.score)
-        except (OSError, ValueError) as e:
-            raise SystemExit(f"hybridgl_amd.proposals: {e}")
-        print(f"images: {len(rep['per_image'])}   proposals: {rep['before']} -> {rep['after']}")
-        if args.json:
-            with open(args.json, "w") as f:
-                json.dump({"before": rep["before"], "after": rep["after"],
-                           "per_image": [{"image_id": k, "before": v[0], "after": v[1]} for k, v in rep["per_image"].items()]}, f)
+                json.dump({**{name: rep[name] for name in names},
+                           "per_image": [{"image_id": i, **dict(zip(names, v))} for i, v in rep["per_image"].items()]}, f)
         return 0
     try:
         thresholds = [float(v) for v in args.iou.split(",") if v.strip()]

@@ -4,6 +4,7 @@ every image alone and the group of all four, under the second metric and the oth
 thinned list), at thr = 1.0 (the store itself); the driver's --mask_nms_thresh gives the metrics of a run from the thinned
 directory; the flag's refusals; a record that does not decode.  The store is the one of tests/test_gpu_proposals_thin.py: the tiny
 SAM without a box NMS at its median threshold, three images of 96 x 128, 150 x 200 and 70 x 37 plus one without a proposal."""
+import collections
 import json
 import os
 import shutil
@@ -42,7 +43,7 @@ def groups(w, cuda):
 
 @pytest.mark.parametrize("thr,metric,score", [(0.5, "iou", "predicted_iou"), (0.5, "containment", "area"), (0.3, "iou", "stored"),
                                               (0.6, "containment", "stability_score")])
-def test_thinned_on_load_equals_the_thinned_store(world, cuda, tmp_path, thr, metric, score):
+def test_thinned_on_load_equals_the_thinned_store(world, cuda, tmp_path, monkeypatch, thr, metric, score):
     from hybridgl_amd import proposals as P
     w = world
     dst = w.dst
@@ -66,6 +67,25 @@ def test_thinned_on_load_equals_the_thinned_store(world, cuda, tmp_path, thr, me
             # a cap of the call, on top: the first two of the thinned list
             same(live.generate_group(*groups(w, cuda)[-1], cap=2), disk.generate_group(*groups(w, cuda)[-1], cap=2))
     assert total > 3 * len(IDS)
+    if (thr, metric, score) == (0.5, "iou", "predicted_iou"):
+        # the class's contract, counted: one NMS, one compaction and one grouped decode per group that holds an entry
+        from hybridgl_amd import ops
+        calls = collections.Counter()
+
+        def counted(name, fn):
+            def call(*a, **kw):
+                calls[name] += 1
+                return fn(*a, **kw)
+            return call
+
+        for name in ("rle_nms", "rle_select", "rle_decode_group"):
+            monkeypatch.setattr(ops, name, counted(name, getattr(ops, name)))
+        four, none = groups(w, cuda)[-1], groups(w, cuda)[len(IDS)]
+        assert none[1] == [EMPTY]
+        for reader, group, want in ((live, four, (1, 1, 1)), (disk, four, (0, 0, 1)), (live, none, (0, 0, 0)), (disk, none, (0, 0, 0))):
+            calls.clear()
+            reader.generate_group(*group)
+            assert (calls["rle_nms"], calls["rle_select"], calls["rle_decode_group"]) == want
 
 
 def test_threshold_one_is_the_store_itself_and_none_is_todays_path(world, cuda):

@@ -191,6 +191,59 @@ def test_prefetch_packs_one_buffer_per_image(tmp_path, golden_records):
         sp.prefetch(6, (240, 320))
 
 
+def test_the_staged_group_holds_the_rows_of_its_images(tmp_path):
+    """the host half of a group, P._stage_group: table | slots | iou | stability (| area) of the first counts[g] entries of
+    every image, image after image -- a cap that cuts the first image, an image without a record in the middle, the widest slot
+    in an image that is not cut -- and the slot width of a group is that of the images that contribute an entry"""
+    def rec(m, iou, stab):
+        ys, xs = np.nonzero(m)
+        return {"segmentation": hsam.coco_encode_rle(hsam.mask_to_rle(m)), "area": int(m.sum()), "predicted_iou": iou, "stability_score": stab,
+                "bbox": [int(xs.min()), int(ys.min()), int(xs.max() - xs.min()), int(ys.max() - ys.min())], "point_coords": [[0.0, 0.0]],
+                "crop_box": [0, 0, 8, 8]}
+
+    def bar(y0, y1, x0, x1):
+        m = np.zeros((8, 8), np.uint8)
+        m[y0:y1, x0:x1] = 1
+        return m
+
+    checker = (np.indices((8, 8)).sum(0) % 2).astype(np.uint8)
+    store = P.ProposalStore(tmp_path)
+    store.write(1, [rec(bar(2, 6, 1, 4), 0.9, 0.5), rec(bar(1, 3, 0, 8), 0.8, 0.25), rec(bar(0, 8, 3, 4), 0.7, 0.125)])
+    store.write(2, [])
+    store.write(3, [rec(bar(0, 8, 2, 5), 0.6, 0.75)])
+    store.write(4, [rec(checker, 0.4, 0.0625), rec(bar(3, 5, 3, 5), 0.3, 1.0)])
+    ids = [1, 2, 3, 4]
+    for area, kw in ((False, {}), (True, {"mask_nms_thresh": 0.5, "mask_nms_score": "area"})):
+        sp = P.StoredProposals(store, "cpu", **kw)
+        rows = [sp.prefetch(i, (8, 8)) for i in ids]
+        assert [r.n for r in rows] == [3, 0, 1, 2] and rows[3].sw > rows[0].sw > rows[2].sw > 1
+        assert all(r.area.size == (r.n if area else 0) for r in rows)
+        for counts, sw in (([2, 0, 1, 2], rows[3].sw), ([0, 0, 1, 0], rows[2].sw), ([0, 0, 0, 0], 0)):
+            S = sum(counts)
+            words = S * (6 + sw + area)
+            buf = np.full(words + 5, -7, np.int32)
+            got = P._stage_group(rows, counts, area, buf)
+            assert got[:2] == (S, sw) and got[2].tolist() == np.cumsum([0] + counts).tolist()
+            assert (buf[words:] == -7).all()
+            table, slots = buf[:4 * S].reshape(S, 4), buf[4 * S:S * (4 + sw)].reshape(S, sw)
+            tail = buf[S * (4 + sw):words].reshape(2 + area, S)
+            for r, n, e in zip(rows, counts, got[2]):
+                assert np.array_equal(table[e:e + n], r.table[:n])
+                for k in range(n):
+                    nc = int(r.table[k, 0])
+                    assert nc > 0 and np.array_equal(slots[e + k, :nc], r.slots[k, :nc])
+                assert (slots[e:e + n, r.sw:] == -7).all()      # beyond an image's own slot width nothing is written
+                assert np.array_equal(tail[0, e:e + n], r.iou[:n]) and np.array_equal(tail[1, e:e + n], r.stab[:n])
+                if area:
+                    assert np.array_equal(tail[2, e:e + n], r.area[:n])
+        # the views are the one buffer's, and hold what the records say
+        r = rows[0]
+        assert r.iou.view(np.float32).tolist() == [np.float32(v) for v in (0.9, 0.8, 0.7)] and r.stab.view(np.float32).tolist() == [0.5, 0.25, 0.125]
+        assert np.shares_memory(r.table, r.buf.numpy()) and np.shares_memory(r.stab, r.buf.numpy())
+        if area:
+            assert r.area.view(np.float32).tolist() == [12.0, 16.0, 8.0]
+
+
 def test_generator_settings_and_the_flag_rules():
     from hybridgl_amd import main as drv
 

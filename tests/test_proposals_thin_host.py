@@ -1,6 +1,7 @@
 """proposals.thin and its command line without a device: the refusals (dst == src, an occupied dst, an unknown score or metric, a
 record that does not decode), the meta it writes, the records it keeps -- unchanged and in their stored order -- and what it hands
-to ops.rle_nms, which a fake stands in for here (tests/test_gpu_proposals_thin.py runs the real one)."""
+to ops.rle_nms, which a fake stands in for here (tests/test_gpu_proposals_thin.py runs the real one).  The refusals that
+proposals.clean shares with it, and clean's own, run here too: they come before any device call."""
 import json
 import os
 
@@ -70,31 +71,46 @@ def fake(monkeypatch):
     return calls, nms
 
 
-def test_refusals(src, tmp_path, fake):
+NAN = float("nan")
+THIN_BAD = [((0.5,), {"score": "iou"}, "score"), ((0.5,), {"score": None}, "score"), ((0.5,), {"metric": "dice"}, "metric"),
+            ((0.5,), {"metric": 0}, "metric"), ((NAN,), {}, "NaN")]
+CLEAN_BAD = [((-1,), {}, "min_area"), ((5, NAN), {}, "NaN"), ((5,), {"nms_thresh": NAN}, "NaN")]
+
+
+@pytest.mark.parametrize("op,args,bad_args", [(P.thin, (0.5,), THIN_BAD), (P.clean, (5,), CLEAN_BAD)], ids=["thin", "clean"])
+def test_refusals(src, tmp_path, fake, op, args, bad_args):
+    """what thin and clean refuse alike, and each one's own arguments: all of it before any device call"""
     calls, _ = fake
+    with pytest.raises(ValueError, match=f"{op.__name__}: .*same directory"):
+        op(src, src.directory, *args)
     with pytest.raises(ValueError, match="same directory"):
-        P.thin(src, src.directory, 0.5)
-    with pytest.raises(ValueError, match="same directory"):
-        P.thin(src.directory, os.path.join(src.directory, "..", "src"), 0.5)
-    for kw, why in (({"score": "iou"}, "score"), ({"score": None}, "score"), ({"metric": "dice"}, "metric"), ({"metric": 0}, "metric")):
+        op(src.directory, os.path.join(src.directory, "..", "src"), *args)
+    for a, kw, why in bad_args:
         with pytest.raises(ValueError, match=why):
-            P.thin(src, tmp_path / "never", 0.5, **kw)
-    with pytest.raises(ValueError, match="NaN"):
-        P.thin(src, tmp_path / "never", float("nan"))
+            op(src, tmp_path / "never", *a, **kw)
     with pytest.raises(ValueError, match="no such directory"):
-        P.thin(tmp_path / "absent", tmp_path / "never", 0.5)
+        op(tmp_path / "absent", tmp_path / "never", *args)
     assert not os.path.exists(tmp_path / "never") and calls == []
     # a directory that holds a store -- a record file or only its meta -- is not written into; an empty one is taken
     taken = P.ProposalStore(tmp_path / "taken")
     taken.write_meta({})
     with pytest.raises(ValueError, match="already holds a store"):
-        P.thin(src, taken, 0.5)
+        op(src, taken, *args)
     other = P.ProposalStore(tmp_path / "other")
     other.write(1, [])
     with pytest.raises(ValueError, match="already holds a store"):
-        P.thin(src, other.directory, 0.5)
+        op(src, other.directory, *args)
+    assert calls == []
     os.makedirs(tmp_path / "empty")
-    assert P.thin(src, tmp_path / "empty", 0.5)["before"] == 5
+    if op is P.thin:
+        assert P.thin(src, tmp_path / "empty", 0.5)["before"] == 5
+    else:      # (no fake stands in for clean's device work: a store whose images hold no record never reaches it)
+        bare = P.ProposalStore(tmp_path / "bare")
+        bare.write(5, [])
+        bare.write_meta({"sam_model": "tiny"})
+        assert P.clean(bare, tmp_path / "empty", 5) == {"per_image": {5: [0, 0, 0]}, "before": 0, "after": 0, "changed": 0}
+        done = P.ProposalStore(tmp_path / "empty")
+        assert done.records(5) == [] and done.meta() == {"sam_model": "tiny", "cleaned": {"min_area": 5, "nms_thresh": 0.7, "source": bare.directory}}
 
 
 def test_what_it_writes_and_what_it_asks(src, tmp_path, fake):
@@ -153,4 +169,17 @@ def test_command_line(src, tmp_path, fake, capsys):
         with pytest.raises(SystemExit):
             P.main(["thin", src.directory, str(tmp_path / "no")] + bad + ([] if not bad else ["--thr", "0.5"]))
         capsys.readouterr()
+    assert not os.path.exists(tmp_path / "no")
+    # clean's refusals come through the same writer of the command line, under its own name
+    with pytest.raises(SystemExit, match="hybridgl_amd.proposals: clean: .*same directory"):
+        P.main(["clean", src.directory, src.directory, "--min_area", "5"])
+    with pytest.raises(SystemExit, match="hybridgl_amd.proposals: clean: .*already holds a store"):
+        P.main(["clean", src.directory, str(out), "--min_area", "5"])
+    with pytest.raises(SystemExit, match="min_area"):
+        P.main(["clean", src.directory, str(tmp_path / "no"), "--min_area", "-1"])
+    with pytest.raises(SystemExit, match="NaN"):
+        P.main(["clean", src.directory, str(tmp_path / "no"), "--min_area", "5", "--nms_thresh", "nan"])
+    with pytest.raises(SystemExit):      # argparse refuses a call without --min_area
+        P.main(["clean", src.directory, str(tmp_path / "no")])
+    capsys.readouterr()
     assert not os.path.exists(tmp_path / "no")
