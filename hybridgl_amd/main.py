@@ -120,6 +120,10 @@ def default_argument_parser():
                    help="with --mask_nms_thresh: the ratio, I / union or I / the smaller area")
     p.add_argument("--mask_nms_score", default="predicted_iou", choices=["predicted_iou", "stability_score", "area", "stored"],
                    help="with --mask_nms_thresh: the record field the walk is ordered by, descending (stored: the stored order)")
+    p.add_argument("--rle_strings", default="host", choices=["host", "device"],
+                   help="with --save_proposals / --proposals_dir: where the COCO strings of the store are written and read -- on the "
+                        "host, one record at a time, or on the device (ops.rle_to_strings / ops.rle_from_strings); files and rows "
+                        "are identical either way")
     p.add_argument("--proposal_ceiling", default="", metavar="OUT",
                    help="with --proposals_dir: write the proposal ceiling of the store -- per sentence the stored proposal of the "
                         "largest IoU against the ground truth, {oIoU, mIoU, cum, n_sentences} as the sweep reports it -- here and "
@@ -450,7 +454,8 @@ def build_models(args, dev):
         from .proposals import StoredProposals
         gen = StoredProposals(args.proposals_dir, dev, mask_nms_thresh=getattr(args, "mask_nms_thresh", None),
                               mask_nms_metric=getattr(args, "mask_nms_metric", "iou"),
-                              mask_nms_score=getattr(args, "mask_nms_score", "predicted_iou"))
+                              mask_nms_score=getattr(args, "mask_nms_score", "predicted_iou"),
+                              strings=getattr(args, "rle_strings", "host"))
     elif args.sam or args.real:
         from .sam import SamAutomaticMaskGenerator, sam_model_registry
         sam = sam_model_registry[args.sam_model](device=dev, precision=args.precision)
@@ -707,7 +712,8 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
     if getattr(args, "save_proposals", ""):
         from .proposals import ProposalRecorder, generator_settings
         recorder = gen = ProposalRecorder(gen, args.save_proposals, generator_settings(
-            gen, sam_model=args.sam_model, precision=getattr(args, "precision", None), proposal_cap=getattr(args, "proposal_cap", 0)))
+            gen, sam_model=args.sam_model, precision=getattr(args, "precision", None), proposal_cap=getattr(args, "proposal_cap", 0)),
+            strings=getattr(args, "rle_strings", "host"))
     pipe = HybridGLPipeline(model, fusion_mode=args.fusion_mode, masking_block=getattr(args, "masking_block", 9), mask_generator=gen,
                             use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir), sweep=sweep,
                             on_overflow=getattr(args, "on_overflow", "raise"))

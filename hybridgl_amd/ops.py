@@ -476,6 +476,114 @@ def rle_pack(counts_list, H, W, slot_words=None, device=None):
     return rle_split(flat, S, slot_words)
 
 
+RLE_STRING_CAP_PER_ENTRY = 4096      # the default room of rle_to_strings per entry, in bytes: a guess until tools/rle_bench.py --strings says otherwise
+
+
+def rle_strings_split(flat, S, cap):
+    """(bytes uint8 [cap], offsets int64 [S+1], status int32 [S]) as views of the flat uint8 buffer rle_to_strings fills (device
+    tensor, host tensor or numpy array alike): the offsets first, then the status, then the bytes -- what a caller wants on the
+    host is one stretch from the front"""
+    S, cap = int(S), int(cap)
+    a, b = 8 * (S + 1), 8 * (S + 1) + 4 * S
+    if isinstance(flat, torch.Tensor):
+        return flat[b:b + cap], flat[:a].view(torch.int64), flat[a:b].view(torch.int32)
+    return flat[b:b + cap], flat[:a].view("int64"), flat[a:b].view("int32")
+
+
+def rle_strings_bytes(S, cap):
+    """the uint8 elements of the flat buffer of rle_to_strings for S entries and cap string bytes"""
+    return 8 * (int(S) + 1) + 4 * int(S) + int(cap)
+
+
+def rle_to_strings(slots, table, cap=None, out=None):
+    """COCO's compressed strings (maskApi.c:203-216 rleToString) of an encoded set on the device: hgl_rle_to_strings_device on
+    the current stream, no synchronisation.  slots / table: what rle_encode or rle_pack returns.  cap: the room for all strings
+    together, default RLE_STRING_CAP_PER_ENTRY * S.  Returns (bytes uint8 [cap], offsets int64 [S+1], status int32 [S]), three
+    views of one flat uint8 buffer (`out`: a contiguous uint8 device tensor of rle_strings_bytes(S, cap) elements to use for
+    it; rle_strings_split takes it apart).  The strings lie back to back in entry order, entry s at offsets[s] .. offsets[s+1];
+    the offsets are true also when cap is too small.  status 0: written; 1: the entry is a bit plane (form 1), finish it on the
+    host; 2: no mask; 3: the string does not lie wholly inside cap and no byte of it was written (include/hybridgl.h)."""
+    lib = _lib.load()
+    sp, sw, tp, S = _rle_set(slots, table, "rle_to_strings")
+    cap = RLE_STRING_CAP_PER_ENTRY * S if cap is None else int(cap)
+    if cap < 0:
+        raise ValueError(f"rle_to_strings: cap {cap}")
+    if out is None:
+        out = torch.empty(rle_strings_bytes(S, cap), dtype=torch.uint8, device=slots.device)
+    elif out.numel() != rle_strings_bytes(S, cap):
+        raise ValueError(f"out: expected {rle_strings_bytes(S, cap)} uint8 elements, got {out.numel()}")
+    base = _dev(out, torch.uint8, "out")
+    if base % 8:
+        raise ValueError("out: the buffer must be 8-byte aligned (it begins with the int64 offsets)")
+    data, offsets, status = rle_strings_split(out, S, cap)
+    check(lib.hgl_rle_to_strings_device(sp, sw, tp, S, base + 8 * (S + 1) + 4 * S, cap, base, base + 8 * (S + 1), _stream()),
+          "hgl_rle_to_strings_device")
+    return data, offsets, status
+
+
+def rle_strings_pack(strings):
+    """Compressed strings -> what one host -> device copy needs, on the host, vectorised over the concatenated bytes: returns
+    (buf: a pinned uint8 tensor holding the int64 offsets [S+1] and then the bytes back to back; offsets: the int64 numpy view
+    of its front; n_counts int64 [S]: the counts every string holds = its bytes that end a group).  strings: bytes or ASCII str.
+    Raises ValueError naming the entry for a NUL byte (the host parser stops there, the device would not) or a non-ASCII str."""
+    import numpy as np
+    raw = []
+    for k, s in enumerate(strings):
+        if isinstance(s, str):
+            try:
+                s = s.encode("ascii")
+            except UnicodeEncodeError:
+                raise ValueError(f"rle_strings_pack: entry {k} is not ASCII") from None
+        raw.append(bytes(s))
+    S = len(raw)
+    joined = b"".join(raw)
+    buf = torch.empty(8 * (S + 1) + len(joined), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    host = buf.numpy()
+    offsets = host[:8 * (S + 1)].view(np.int64)
+    offsets[0] = 0
+    np.cumsum(np.fromiter(map(len, raw), dtype=np.int64, count=S), out=offsets[1:])
+    data = host[8 * (S + 1):]
+    data[:] = np.frombuffer(joined, dtype=np.uint8)
+    nul = np.flatnonzero(data == 0)
+    if nul.size:
+        raise ValueError(f"rle_strings_pack: entry {int(np.searchsorted(offsets, nul[0], side='right')) - 1} holds a NUL byte")
+    ends = np.zeros(len(joined) + 1, dtype=np.int64)      # ends[p] = the bytes before p that end a group (csrc/rle_string.h: c & 32 == 0)
+    np.cumsum(((data - np.uint8(48)) & np.uint8(32)) == 0, out=ends[1:])
+    return buf, offsets, ends[offsets[1:]] - ends[offsets[:-1]]      # a difference of running sums: empty strings need no care
+
+
+def rle_from_strings(data, offsets, S, slot_words, out=None, status=None):
+    """The inverse of rle_to_strings on the device (maskApi.c:217-230 rleFrString without the decode):
+    hgl_rle_from_strings_device on the current stream, no synchronisation.  data: uint8 device tensor of the strings back to
+    back; offsets: int64 device tensor [S+1] (the two parts of rle_strings_pack's buffer once it is on the device).  Returns
+    (slots [S, slot_words] int32, table [S,4] int32, status [S,4] int32 = code, n_counts, 0, 0): slots and table are the views
+    of one flat buffer as rle_encode lays it out (`out`: S * (4 + slot_words) int32 elements), every accepted row in form 0.
+    code 0: read; 1: n_counts > slot_words (the true n_counts is in the status); 2: truncated; 3: a group of more than 7
+    characters; 4: broken offsets -- the rows of codes 1 to 4 say "no mask" to every decoder (include/hybridgl.h).  `status`: a
+    contiguous int32 device tensor [S,4] to use for it (a stretch of a buffer that leaves in one read-back)."""
+    lib = _lib.load()
+    S, slot_words = int(S), int(slot_words)
+    if offsets.numel() != S + 1:
+        raise ValueError(f"rle_from_strings: {S} entries need {S + 1} offsets, got {offsets.numel()}")
+    if out is None:
+        out = torch.empty(S * (4 + slot_words), dtype=torch.int32, device=data.device)
+    elif out.numel() != S * (4 + slot_words):
+        raise ValueError(f"out: expected {S * (4 + slot_words)} int32 elements, got {out.numel()}")
+    slots, table = rle_split(out, S, slot_words)
+    if status is None:
+        status = torch.empty((S, 4), dtype=torch.int32, device=data.device)
+    elif tuple(status.shape) != (S, 4):
+        raise ValueError(f"status: expected an int32 tensor [{S}, 4], got {tuple(status.shape)}")
+    if S == 0:
+        return slots, table, status
+    base = _dev(out, torch.int32, "out")
+    _dev(status, torch.int32, "status")
+    check(lib.hgl_rle_from_strings_device(_dev(data, torch.uint8, "data") if data.numel() else None, int(data.numel()),
+                                          _dev(offsets, torch.int64, "offsets"), S, base + 16 * S, slot_words, base,
+                                          status.data_ptr(), _stream()), "hgl_rle_from_strings_device")
+    return slots, table, status
+
+
 def _rle_set(slots, table, name):
     """(slots pointer, slot_words, table pointer, S) of one encoded set: int32 device tensors [S, slot_words] and [S, 4]"""
     if slots.dim() != 2 or table.dim() != 2 or table.shape[1] != 4 or table.shape[0] != slots.shape[0]:

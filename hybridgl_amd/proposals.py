@@ -119,13 +119,16 @@ class ProposalStore:
         return recs
 
 
-def build_records(H, W, counts, areas, xywh, iou, stab, points, crop_boxes):
-    """the record list of one image from its survivors' host arrays, field for field what generate() builds in coco_rle mode"""
+def build_records(H, W, counts, areas, xywh, iou, stab, points, crop_boxes, strings=None):
+    """the record list of one image from its survivors' host arrays, field for field what generate() builds in coco_rle mode;
+    strings: the COCO strings (bytes) of the masks where they exist already (written on the device), then counts is not read"""
     from .sam import coco_encode_rle
     out = []
-    for i in range(len(counts)):
+    for i in range(len(areas)):
         cb = crop_boxes[i]
-        out.append({"segmentation": coco_encode_rle({"size": [int(H), int(W)], "counts": counts[i]}), "area": int(areas[i]),
+        seg = (coco_encode_rle({"size": [int(H), int(W)], "counts": counts[i]}) if strings is None else
+               {"size": [int(H), int(W)], "counts": strings[i].decode("ascii")})
+        out.append({"segmentation": seg, "area": int(areas[i]),
                     "bbox": [int(v) for v in xywh[i]], "predicted_iou": float(iou[i]), "point_coords": [points[i].tolist()],
                     "stability_score": float(stab[i]),
                     "crop_box": [int(cb[0]), int(cb[1]), int(cb[2] - cb[0]), int(cb[3] - cb[1])]})   # XYWH
@@ -141,10 +144,20 @@ class ProposalRecorder:
     """A generator that writes what it hands out.  Every call goes to the wrapped generator unchanged -- the run's rows and
     report are those of an unwrapped run -- and the survivors of every image with an id are encoded (ops.rle_encode: runs,
     not pixels) and copied to pinned staging behind it.  A staging buffer is reused only after its copy's event; the files
-    are written when the events have completed: at later group boundaries, and in flush()."""
+    are written when the events have completed: at later group boundaries, and in flush().
+
+    strings "host": the runs are copied, n * (4 + ceil(H*W/32)) words per image, and become strings one record at a time in
+    _harvest.  "device": ops.rle_to_strings runs behind the encode and ONE copy brings offsets | status | the first string_cap
+    bytes (default ops.RLE_STRING_CAP_PER_ENTRY per proposal); _harvest slices.  Only when the strings did not fit, or an entry
+    is a bit plane (form 1), does it go back to the device buffers it kept: a second call at the true size, the host codec for
+    that entry, one wait.  The files are byte-identical."""
     wants_image_ids = True
 
-    def __init__(self, generator, store, meta=None):
+    def __init__(self, generator, store, meta=None, strings="host", string_cap=None):
+        if strings not in ("host", "device"):
+            raise ValueError(f"ProposalRecorder: strings {strings!r} (host or device)")
+        self.strings, self.string_cap = strings, string_cap
+        self.fallbacks = 0      # images whose strings needed the device buffers again
         self.generator = generator
         self.store = store if isinstance(store, ProposalStore) else ProposalStore(store)
         self.recording = True       # False: calls pass through unrecorded (a rehearsal on images that are not the dataset's)
@@ -212,26 +225,49 @@ class ProposalRecorder:
         self._seen.add(image_id)
         n, H, W = (int(v) for v in masks.shape)
         if n == 0:
-            self._pending.append((image_id, H, W, 0, 0, None, None, None))
+            self._pending.append((image_id, H, W, 0, 0, None, None, None, None))
             return
         sw = ops.rle_slot_words(H, W)
         flat = torch.empty(n * (4 + sw), dtype=torch.int32, device=masks.device)
         ops.rle_encode(masks if masks.is_contiguous() else masks.contiguous(), None, sw, out=flat)
-        runs = self._take(flat.numel(), torch.int32)
-        runs[:flat.numel()].copy_(flat, non_blocking=True)
         # the few scalars per proposal ride along: rows iou, stability, source, x, y, w, h (all exact in float64)
-        sc = torch.cat([iou.double()[None], stab.double()[None], src.double()[None], xywh.double().t()])
-        scal = self._take(7 * n, torch.float64)
-        scal[:7 * n].copy_(sc.reshape(-1), non_blocking=True)
+        sc = [iou.double()[None], stab.double()[None], src.double()[None], xywh.double().t()]
+        kept = None
+        if self.strings == "device":
+            cap = int(self.string_cap) if self.string_cap is not None else ops.RLE_STRING_CAP_PER_ENTRY * n
+            slots, table = ops.rle_split(flat, n, sw)
+            out = torch.empty(ops.rle_strings_bytes(n, cap), dtype=torch.uint8, device=masks.device)
+            ops.rle_to_strings(slots, table, cap, out=out)
+            sc.append(table[:, 2].double()[None])      # the areas, which the host mode reads from the table
+            kept, flat = (flat, cap), out              # the encoded set stays on the device until the file is written
+        runs = self._take(flat.numel(), flat.dtype)
+        runs[:flat.numel()].copy_(flat, non_blocking=True)
+        sc = torch.cat(sc)
+        scal = self._take(sc.numel(), torch.float64)
+        scal[:sc.numel()].copy_(sc.reshape(-1), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        self._pending.append((image_id, H, W, n, sw, runs, scal, ev))
+        self._pending.append((image_id, H, W, n, sw, runs, scal, ev, kept))
+
+    def _strings(self, n, sw, H, W, staged, kept):
+        """the strings of one image out of the staged offsets | status | bytes; `kept`: the encoded set on the device and the cap"""
+        from .sam import strings_from_bytes
+        flat, cap = kept
+        data, offsets, status = ops.rle_strings_split(staged[:ops.rle_strings_bytes(n, cap)], n, cap)
+        total = int(offsets[n])
+        slots, table = ops.rle_split(flat, n, sw)
+        if total > cap or (status == 1).any():
+            self.fallbacks += 1
+        if total > cap:      # the offsets are true under any cap: once more at the size they give, and one wait
+            d, _, st = ops.rle_to_strings(slots, table, total)
+            data, status = d.cpu().numpy(), st.cpu().numpy()
+        return strings_from_bytes(data[:total].tobytes(), offsets, status, slots, table, H, W)
 
     def _harvest(self, wait=False):
         """write the files of the copies that have completed (wait=True: of all), oldest first; their buffers return to the pool"""
         from .sam import rle_from_slot
         while self._pending:
-            image_id, H, W, n, sw, runs, scal, ev = self._pending[0]
+            image_id, H, W, n, sw, runs, scal, ev, kept = self._pending[0]
             if ev is not None:
                 if wait:
                     ev.synchronize()
@@ -241,12 +277,17 @@ class ProposalRecorder:
             if n == 0:
                 self.store.write(image_id, [])
             else:
-                slots, table = ops.rle_split(runs.numpy(), n, sw)
-                counts = [rle_from_slot(slots[e], int(table[e, 0]), int(table[e, 1]), H, W) for e in range(n)]
-                s = scal.numpy()[:7 * n].reshape(7, n)
+                rows = 7 if kept is None else 8
+                s = scal.numpy()[:rows * n].reshape(rows, n)
+                if kept is None:
+                    slots, table = ops.rle_split(runs.numpy(), n, sw)
+                    counts = [rle_from_slot(slots[e], int(table[e, 0]), int(table[e, 1]), H, W) for e in range(n)]
+                    strings, areas = None, table[:, 2]
+                else:
+                    counts, strings, areas = None, self._strings(n, sw, H, W, runs.numpy(), kept), s[7].astype(np.int64)
                 pts, cbs = self.generator._sources(torch.from_numpy(s[2].astype(np.int64)), H, W)
-                self.store.write(image_id, build_records(H, W, counts, table[:, 2], s[3:7].T.astype(np.int64), s[0].astype(np.float32),
-                                                         s[1].astype(np.float32), pts, cbs))
+                self.store.write(image_id, build_records(H, W, counts, areas, s[3:7].T.astype(np.int64), s[0].astype(np.float32),
+                                                         s[1].astype(np.float32), pts, cbs, strings))
                 self._free += [runs, scal]
             self.written += 1
 
@@ -264,7 +305,7 @@ class _Rows:
     """the proposals of one stored image, packed on a loader thread: ONE pinned int32 buffer = table [n,4] | slots [n,sw] |
     the bits of predicted_iou [n] | of stability_score [n] (| of area [n], where the walk is ordered by it), the numpy views of
     its parts (_split_group), and the stored boxes for the check"""
-    __slots__ = ("n", "H", "W", "sw", "buf", "table", "slots", "iou", "stab", "area", "bbox")
+    __slots__ = ("n", "H", "W", "sw", "buf", "table", "slots", "iou", "stab", "area", "bbox", "soff", "sbytes")
 
 
 class _Stored:
@@ -326,11 +367,22 @@ class StoredProposals:
     counts: the positions behind the survivors decode to empty masks that nobody is handed.  The caps then apply to the
     survivors.  The survivors' counts and source indices ride back in the read-back that carries boxes and status: still one
     per group, no further synchronisation.  thinned = [entries read, entries handed out] over the images met so far, each image
-    counted once (noted in group_cleanup)."""
+    counted once (noted in group_cleanup).
+
+    strings "host": sam.rle_counts_from_string per record on the loader thread, counts padded to the widest entry on the bus.
+    "device": the loader keeps every record's string bytes (ops.rle_strings_pack: offsets | bytes | iou bits | stability bits
+    (| area bits) in the one pinned buffer, the slot width from the number of bytes that end a count), group_begin uploads the
+    strings as they are and ops.rle_from_strings makes them the slots and the table the same chain takes.  The codec's status
+    rides in the group's one read-back; group_cleanup raises for a string that did not read, before the decode's own checks.
+    Rows and metrics are those of the host mode bit for bit."""
     wants_image_ids = True
     crop_n_layers = 0      # HybridGLPipeline.step: one generate_device call, whatever produced the store
 
-    def __init__(self, store, device, cap=None, keep=256, mask_nms_thresh=None, mask_nms_metric="iou", mask_nms_score="predicted_iou"):
+    def __init__(self, store, device, cap=None, keep=256, mask_nms_thresh=None, mask_nms_metric="iou", mask_nms_score="predicted_iou",
+                 strings="host"):
+        if strings not in ("host", "device"):
+            raise ValueError(f"StoredProposals: strings {strings!r} (host or device)")
+        self.strings = strings
         self.store = store if isinstance(store, ProposalStore) else ProposalStore(store)
         self.device = torch.device(device)
         self.cap = cap
@@ -387,8 +439,10 @@ class StoredProposals:
         rows = _Rows()
         n = rows.n = len(recs)
         rows.H, rows.W = (int(v) for v in (size if size is not None else (recs[0]["segmentation"]["size"] if recs else (0, 0))))
-        _, counts = _record_runs(self.store, image_id, recs, (rows.H, rows.W))
         by_area = self.mask_nms_thresh is not None and self.mask_nms_score == "area"
+        if self.strings == "device":
+            return self._load_strings(image_id, recs, rows, by_area)
+        _, counts = _record_runs(self.store, image_id, recs, (rows.H, rows.W))
         rows.sw = max([len(c) for c in counts] + [1])
         rows.buf = torch.zeros(_group_words(n, rows.sw, by_area), dtype=torch.int32, pin_memory=torch.cuda.is_available())
         rows.slots, rows.table, (rows.iou, rows.stab), rows.area = _split_group(rows.buf.numpy(), n, rows.sw)
@@ -401,6 +455,72 @@ class StoredProposals:
             rows.area.view(np.float32)[:] = [float(r["area"]) for r in recs]
         rows.bbox = np.asarray([r["bbox"] for r in recs], dtype=np.int64).reshape(n, 4)
         return rows
+
+    def _load_strings(self, image_id, recs, rows, by_area):
+        """_load with the strings kept as bytes: ONE pinned buffer = offsets int64 [n+1] | bytes, padded to a word | the bits of
+        predicted_iou [n] | of stability_score [n] (| of area [n]); no string is parsed here"""
+        n = rows.n
+        for k, r in enumerate(recs):
+            if tuple(int(v) for v in r["segmentation"]["size"]) != (rows.H, rows.W):
+                raise ValueError(f"proposal store {self.store.directory}: image {image_id} entry {k}: size {r['segmentation']['size']} "
+                                 f"differs from the image's {[rows.H, rows.W]}")
+        try:
+            packed, offsets, n_counts = ops.rle_strings_pack([r["segmentation"]["counts"] for r in recs])
+        except ValueError as e:
+            raise ValueError(f"proposal store {self.store.directory}: image {image_id}: bad counts string ({e})") from None
+        rows.sw = max([int(v) for v in n_counts] + [1])
+        head = (packed.numel() + 3) // 4 * 4
+        rows.buf = torch.zeros(head + 4 * n * (2 + by_area), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        host = rows.buf.numpy()
+        host[:packed.numel()] = packed.numpy()
+        rows.soff, rows.sbytes = host[:8 * (n + 1)].view(np.int64), host[8 * (n + 1):packed.numel()]
+        tail = host[head:].view(np.int32)
+        rows.iou, rows.stab, rows.area = tail[:n], tail[n:2 * n], tail[2 * n:]
+        rows.slots = rows.table = None
+        rows.iou.view(np.float32)[:] = [r["predicted_iou"] for r in recs]
+        rows.stab.view(np.float32)[:] = [r["stability_score"] for r in recs]
+        if by_area:
+            rows.area.view(np.float32)[:] = [float(r["area"]) for r in recs]
+        rows.bbox = np.asarray([r["bbox"] for r in recs], dtype=np.int64).reshape(n, 4)
+        return rows
+
+    def _upload_strings(self, st, by_area):
+        """The device mode's front of group_begin: the first counts[g] strings of every image, image after image, staged as
+        offsets int64 [S+1] | iou bits [S] | stab bits [S] (| area bits [S]) | bytes, in ONE upload.  Returns (S, sw, first,
+        (offsets, bytes, cols, area) on the device): _stage_group's three and the views of the upload; None in place of the views
+        for a group without an entry, which uploads nothing."""
+        first = np.cumsum([0] + [int(n) for n in st.counts])
+        S = int(first[-1])
+        if S == 0:
+            return 0, 0, first, None
+        sw = max(r.sw for r, n in zip(st.rows, st.counts) if n)
+        T = sum(int(r.soff[n]) for r, n in zip(st.rows, st.counts))
+        words = 2 * (S + 1) + S * (2 + by_area) + (T + 3) // 4
+        host = self._staging(words)
+        h = host.numpy()[:words]
+        offs = h[:2 * (S + 1)].view(np.int64)
+        cols = h[2 * (S + 1):2 * (S + 1) + 2 * S].reshape(2, S)
+        extra = h[2 * (S + 1) + 2 * S:2 * (S + 1) + S * (2 + by_area)]
+        data = h[2 * (S + 1) + S * (2 + by_area):].view(np.uint8)
+        base = 0
+        for r, n, e in zip(st.rows, st.counts, first):
+            if n:
+                t = int(r.soff[n])
+                offs[e:e + n] = r.soff[:n] + base
+                data[base:base + t] = r.sbytes[:t]
+                cols[0, e:e + n] = r.iou[:n]
+                cols[1, e:e + n] = r.stab[:n]
+                if by_area:
+                    extra[e:e + n] = r.area[:n]
+                base += t
+        offs[S] = base
+        dev = torch.empty(words, dtype=torch.int32, device=self.device)
+        dev.copy_(host[:words], non_blocking=True)
+        up = torch.cuda.Event()
+        up.record()
+        self._free.append((host, up))
+        a, b = 2 * (S + 1) + 2 * S, 2 * (S + 1) + S * (2 + by_area)
+        return S, sw, first, (dev[:2 * (S + 1)].view(torch.int64), dev[b:].view(torch.uint8)[:T], dev[2 * (S + 1):a].reshape(2, S), dev[a:b])
 
     # ---- device half (the loop's thread)
     def _staging(self, numel):
@@ -428,28 +548,40 @@ class StoredProposals:
         if encoded_event is not None:      # there is no encoder pass to wait for
             encoded_event.record(torch.cuda.current_stream(self.device))
         st.ev = None
-        # (room for the group however wide its slots are; a group without an entry stages nothing)
-        room = _group_words(sum(st.counts), max([r.sw for r in st.rows] + [0]), by_area)
-        host = self._staging(room) if room else torch.empty(0, dtype=torch.int32)
-        S, sw, st.first = _stage_group(st.rows, st.counts, by_area, host.numpy())
-        if S == 0:
-            return st
-        G, numel = len(st.rows), _group_words(S, sw, by_area)
-        dev = torch.empty(numel, dtype=torch.int32, device=self.device)
-        dev.copy_(host[:numel], non_blocking=True)
-        up = torch.cuda.Event()
-        up.record()
-        self._free.append((host, up))
-        slots, table, cols, area = _split_group(dev, S, sw)
+        dev_strings = self.strings == "device"
+        G = len(st.rows)
+        if dev_strings:
+            S, sw, st.first, parts = self._upload_strings(st, by_area)
+            if S == 0:
+                return st
+        else:
+            # (room for the group however wide its slots are; a group without an entry stages nothing)
+            room = _group_words(sum(st.counts), max([r.sw for r in st.rows] + [0]), by_area)
+            host = self._staging(room) if room else torch.empty(0, dtype=torch.int32)
+            S, sw, st.first = _stage_group(st.rows, st.counts, by_area, host.numpy())
+            if S == 0:
+                return st
+            numel = _group_words(S, sw, by_area)
+            dev = torch.empty(numel, dtype=torch.int32, device=self.device)
+            dev.copy_(host[:numel], non_blocking=True)
+            up = torch.cuda.Event()
+            up.record()
+            self._free.append((host, up))
+            slots, table, cols, area = _split_group(dev, S, sw)
         # ONE int32 buffer leaves in one copy into pooled pinned memory: boxes | status and, thinning, | out_src | out_n | the
-        # NMS's out_idx, result, out_n; group_cleanup reads it, where SAM reads its first counts, and hands the buffer back
-        back = torch.empty(14 * S + 2 * G if thin else 8 * S, dtype=torch.int32, device=self.device)
+        # NMS's out_idx, result, out_n (| the string codec's status, reading strings on the device); group_cleanup reads it,
+        # where SAM reads its first counts, and hands the buffer back
+        words = 14 * S + 2 * G if thin else 8 * S
+        back = torch.empty(words + (4 * S if dev_strings else 0), dtype=torch.int32, device=self.device)
+        if dev_strings:
+            offs, data, cols, area = parts
+            slots, table, _ = ops.rle_from_strings(data, offs, S, sw, status=back[words:].view(S, 4))
         if thin:
             scores = {"predicted_iou": cols[0], "stability_score": cols[1], "area": area, "stored": None}[self.mask_nms_score]
             if scores is not None:
                 scores = scores.view(torch.float32)
             result = ops.rle_nms(slots, table, st.sizes, st.counts, scores, self.mask_nms_thresh, self.mask_nms_metric,
-                                 out=back[9 * S + G:])[2]
+                                 out=back[9 * S + G:words])[2]
             slots, table, cols, _, _ = ops.rle_select(slots, table, st.sizes, st.counts, nms_result=result, cols=cols,
                                                       max_keep=min(caps) if caps else None, back=back[8 * S:9 * S + G])
         st.iou, st.stab = cols[0].view(torch.float32), cols[1].view(torch.float32)
@@ -491,14 +623,21 @@ class StoredProposals:
         thin = self.mask_nms_thresh is not None
         S, G = int(st.first[-1]), len(st.rows)
         st.ev.synchronize()
-        h = st.host.numpy()[:14 * S + 2 * G if thin else 8 * S].copy()
+        words = 14 * S + 2 * G if thin else 8 * S
+        h = st.host.numpy()[:words + (4 * S if self.strings == "device" else 0)].copy()
         self._back.append(st.host)
         st.host = None
+        read, h = h[words:].reshape(-1, 4)[:, 0], h[:words]      # the string codec's codes, reading strings on the device (else nothing)
         boxes, status = h[:8 * S].reshape(2, S, 4)
         out_src, out_n = h[8 * S:9 * S], h[9 * S:9 * S + G]      # (these three are empty without thinning)
         codes = h[10 * S + G:14 * S + G].reshape(-1, 4)[:, 0]      # the NMS's result rows: every source entry's code
         kept = []
         for g, (iid, r, n, e) in enumerate(zip(st.ids, st.rows, st.counts, st.first)):
+            bad = np.flatnonzero(read[e:e + n])
+            if len(bad):
+                code = int(read[e + bad[0]])
+                raise ValueError(f"proposal store {self.store.directory}: image {iid} entry {int(bad[0])}: bad counts string (code {code}: " +
+                                 {2: "it ends inside a count", 3: "a count of more than 7 characters"}.get(code, "not read") + ")")
             k = int(out_n[g]) if thin else n
             self._check_image(iid, r, codes[e:e + n], out_src[e:e + k] if thin else np.arange(k), boxes[e:e + k], status[e:e + k])
             kept.append(k)

@@ -1375,6 +1375,92 @@ def coco_encode_rle(uncompressed_rle):
     return {"size": [h, w], "counts": buf.raw[:n.value].decode("utf-8")}
 
 
+def strings_from_device(slots, table, H, W, cap=None):
+    """The COCO strings (bytes) of an encoded set that lives on the device: ops.rle_to_strings, one read of offsets and status,
+    one copy of exactly offsets[S] bytes.  A second call at the true size when `cap` (default: ops.rle_to_strings's) was too
+    small; an entry in form 1 (a bit plane) is finished by the host codec from its slot; an entry without a mask raises
+    ValueError, as rle_from_slot does."""
+    S = int(slots.shape[0])
+    if S == 0:
+        return []
+    cap = ops.RLE_STRING_CAP_PER_ENTRY * S if cap is None else int(cap)
+    flat = torch.empty(ops.rle_strings_bytes(S, cap), dtype=torch.uint8, device=slots.device)
+    data, _, _ = ops.rle_to_strings(slots, table, cap, out=flat)
+    head = flat[:ops.rle_strings_bytes(S, 0)].cpu().numpy()      # the one read of offsets and status
+    _, offsets, status = ops.rle_strings_split(head, S, 0)
+    total = int(offsets[S])
+    if total > cap:      # the offsets are true under any cap: once more, at the size they give
+        data, _, st = ops.rle_to_strings(slots, table, total)
+        status = st.cpu().numpy()
+    raw = data[:total].cpu().numpy().tobytes()      # the one copy of exactly offsets[S] bytes
+    return strings_from_bytes(raw, offsets, status, slots, table, H, W)
+
+
+def strings_from_bytes(raw, offsets, status, slots, table, H, W):
+    """the strings of strings_from_device out of the bytes, offsets and status on the host; slots / table (device or host)
+    are read only for an entry that the device did not finish"""
+    out = []
+    for s in range(len(status)):
+        code = int(status[s])
+        if code == 0:
+            out.append(raw[int(offsets[s]):int(offsets[s + 1])])
+            continue
+        if code == 3:
+            raise ValueError(f"strings_from_bytes: entry {s} was not written (the buffer was too small)")
+        row = [int(v) for v in (table[s].cpu().numpy() if isinstance(table, torch.Tensor) else table[s])]
+        slot = slots[s].cpu().numpy() if isinstance(slots, torch.Tensor) else slots[s]
+        counts = rle_from_slot(slot, row[0], row[1] if code == 1 else max(row[1], 2), H, W)      # code 2: raises
+        out.append(coco_encode_rle({"size": [H, W], "counts": counts})["counts"].encode("ascii"))
+    return out
+
+
+def masks_to_coco_rle(masks, sel=None):
+    """[coco_encode_rle(r) for r in masks_to_rle(masks, sel)] with the strings written on the device (ops.rle_encode ->
+    ops.rle_to_strings): what crosses the bus is the strings, about 1.3 bytes per run, and no Python loop touches a count.
+    Returns a list of {"size": [H, W], "counts": str}, identical to the host path's."""
+    n, H, W = masks.shape
+    S = n if sel is None else int(sel.numel())
+    if S == 0:
+        return []
+    if not masks.is_contiguous():
+        masks = masks.contiguous()
+    slots, table = ops.rle_encode(masks, sel, ops.rle_slot_words(H, W))
+    return [{"size": [H, W], "counts": b.decode("ascii")} for b in strings_from_device(slots, table, H, W)]
+
+
+def coco_rles_to_masks(rles, device=None):
+    """rles_to_masks for RLE dicts that carry their counts as COCO strings / bytes, with the strings read on the device: the
+    strings cross the bus as they are (ops.rle_strings_pack: one copy), ops.rle_from_strings makes them counts and
+    ops.rle_decode pixels.  Returns a bool [n,H,W] device tensor.  Raises ValueError naming the entry and the code for a
+    string that is truncated (2) or has a group of more than 7 characters (3), and rles_to_masks's ValueError for counts that
+    do not sum to H*W (one read-back of the two status tables)."""
+    if len(rles) == 0:
+        raise ValueError("coco_rles_to_masks: no entries (the size of the result is the entries')")
+    h, w = (int(v) for v in rles[0]["size"])
+    for i, r in enumerate(rles):
+        if [int(v) for v in r["size"]] != [h, w]:
+            raise ValueError(f"coco_rles_to_masks: entry {i} has size {list(r['size'])}, entry 0 has {[h, w]}")
+        if not isinstance(r["counts"], (str, bytes, bytearray)):
+            raise ValueError(f"coco_rles_to_masks: entry {i} carries its counts as {type(r['counts']).__name__}, not as a string")
+    S = len(rles)
+    buf, _, n_counts = ops.rle_strings_pack([r["counts"] for r in rles])
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    dev = buf.to(device, non_blocking=True)      # the one upload
+    slots, table, st = ops.rle_from_strings(dev[8 * (S + 1):], dev[:8 * (S + 1)].view(torch.int64), S, max(int(n_counts.max()), 1))
+    masks, status = ops.rle_decode(slots, table, h, w)
+    both = torch.stack([st[:, 0], status[:, 0]]).cpu().numpy()
+    bad = np.flatnonzero(both[0] != 0)
+    if len(bad):
+        k, code = int(bad[0]), int(both[0, bad[0]])
+        raise ValueError(f"coco_rles_to_masks: entry {k} is no compressed RLE string (code {code}: " +
+                         {2: "it ends inside a count", 3: "a count of more than 7 characters"}.get(code, "not read") + ")")
+    bad = np.flatnonzero(both[1] != 0)
+    if len(bad):
+        raise ValueError(f"coco_rles_to_masks: entry {int(bad[0])} does not decode to a {h} x {w} mask (status {int(both[1, bad[0]])}: "
+                         "its counts do not sum to H*W)")
+    return masks.view(torch.bool)
+
+
 def merge_rles(rles, intersect=False, device=None):
     """mask.merge of refer/external/mask.py (maskApi.c:49-70 rleMerge) for a list of RLE dicts of ONE size, on the device: the
     runs cross the bus (ops.rle_pack), the union -- or, with intersect, the intersection -- is formed on bit planes

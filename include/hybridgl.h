@@ -973,6 +973,42 @@ int hgl_rle_clean_device(const uint32_t* slots, long long slot_words, const int3
                          const int64_t* images_host, int G, int area_thresh, int modes, long long seg_cap,
                          uint32_t* out_slots, long long out_slot_words, int32_t* out_table,
                          int32_t* boxes_xyxy, int32_t* result, void* ws, size_t ws_bytes, void* stream);
+/* COCO's compressed RLE strings written and read on the DEVICE (csrc/rle_string.hip; the arithmetic of a count and of a
+ * character group once, in csrc/rle_string.h): the two ends of an encoded set's life, in place of hgl_rle_to_string per
+ * record (refer/external/maskApi.c:203-216 rleToString, what coco_encode_rle of utils/amg.py:294-300 ends in) and of
+ * hgl_rle_from_string per record (maskApi.c:217-230 rleFrString).  Asynchronous on `stream`; no host synchronisation,
+ * allocation or atomics; two calls give the same bytes; no workspace.
+ * hgl_rle_to_strings_device: THREE launches whatever S is (lengths, one scan over the S lengths, write); one for S = 0.
+ * Set = (slots, slot_words, table, S) as hgl_rle_encode_device writes it.  offsets: device int64 [S+1]; offsets[s] is where
+ * entry s's string begins in a buffer without limit -- the strings are packed in entry order with no separator and no
+ * terminator -- and offsets[S] the true total, BOTH ALSO WHEN cap IS SMALLER (the size-query convention of hgl_rle_to_string).
+ * status: device int32 [S]; the codes other than 0 contribute length 0:
+ *   0  the string was written: form 0 and 0 <= n_counts <= slot_words (n_counts == 0 gives the empty string); its bytes equal
+ *      hgl_rle_to_string of the slot's counts
+ *   1  the entry is in form 1: the slot holds the bit plane, its counts are not in memory; nothing is written, the caller
+ *      finishes such an entry on the host
+ *   2  no mask: form 2 or 3 or any other form value, n_counts < 0, n_counts > slot_words
+ *   3  the string is good (it has its length in offsets) but offsets[s+1] > cap: no byte of it is written
+ * bytes: device uint8 [cap] (may be NULL when cap is 0).  No byte outside the code-0 extents is written, the bytes between
+ * offsets[S] and cap included.  Neighbouring strings meet at any byte alignment: the kernel stores bytes, never words.
+ * hgl_rle_from_strings_device: ONE launch whatever S is, none for S = 0.  bytes: device uint8 [total_bytes], total_bytes
+ * < 2^31; offsets: device int64 [S+1], entry s's string is bytes[offsets[s] .. offsets[s+1]).  A byte b is read as
+ * c = (uint8)(b - 48), of which only c & 31 and c & 32 count (bytes >= 112 are accepted, as the host accepts them); the host
+ * parser stops at a NUL byte, the device does not: a string with one is outside the equality with the host.
+ * slots [S, slot_words] / table [S,4] receive what hgl_rle_encode_device would have written in form 0; status: device int32
+ * [S,4] = (code, n_counts, 0, 0):
+ *   0  the slot holds the n_counts counts, the table row is (n_counts, 0, 0, 0); words beyond n_counts are not written; the
+ *      empty string is code 0 with n_counts 0
+ *   1  n_counts > slot_words: the status carries the true n_counts, the row is (n_counts, 2, 0, 0), the slot is untouched
+ *   2  truncated: the string ends inside a group of at most seven characters
+ *   3  long: a group has an eighth character in the string (the first offending group in string order decides: a long group
+ *      lies before the end, so it wins over a truncated end)
+ *   4  offsets[s] > offsets[s+1], or the extent is not inside [0, total_bytes]
+ * Codes 2 to 4: row (0, 2, 0, 0), slot untouched, n_counts 0 in the status -- the decoders see "no mask". */
+int hgl_rle_to_strings_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S, uint8_t* bytes,
+                              long long cap, int64_t* offsets, int32_t* status, void* stream);
+int hgl_rle_from_strings_device(const uint8_t* bytes, long long total_bytes, const int64_t* offsets, int S, uint32_t* slots,
+                                long long slot_words, int32_t* table, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

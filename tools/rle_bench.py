@@ -58,7 +58,14 @@
              outputs pre-allocated on both sides, HIP events, three alternating rounds; the workspace bytes of either path;
              equality of the two paths is checked before any timing; writes profiles/rle_clean_bench.json as well
 
+--strings    COCO's compressed strings on the device (ops.rle_to_strings / ops.rle_from_strings) against the host codec one record
+             at a time, on the benchmark's 64 seeded masks of 640 x 640: (a) wall time from the encoded set on the device to
+             finished Python strings, (b) from Python strings to slots / table on the device, (c) the kernels alone under HIP
+             events, (d) minimum, median and maximum string length per mask; medians of --reps repetitions, the two paths
+             alternated; equality of the two paths is checked before any timing; writes profiles/rle_strings_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
+    python tools/rle_bench.py --strings [--reps 30]
     python tools/rle_bench.py --decode [--reps 30]
     python tools/rle_bench.py --match [--reps 30]
     python tools/rle_bench.py --polygons [--reps 30] [--cli_images 100]
@@ -553,6 +560,75 @@ def clean_leg(dev, reps, H=640, W=640, S=64, area=100):
             "rounds_median_us": [[r[0]["median_us"], r[1]["median_us"]] for r in rounds]}
 
 
+def alternated_ms(fa, fb, reps, warm=3):
+    """the median wall times (ms) of two paths run in turn, each from a quiet device"""
+    for _ in range(warm):
+        fa(), fb()
+    out = ([], [])
+    for _ in range(reps):
+        for k, fn in enumerate((fa, fb)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out[k].append((time.perf_counter() - t0) * 1e3)
+    return [{"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)} for v in out]
+
+
+def strings_leg(dev, reps, S=64, H=640, W=640):
+    """the two ends of an encoded set's life, host path against device path (see --strings at the top)"""
+    masks = torch.from_numpy(np.ascontiguousarray(synth.synth_masks(S, H, W, 2000))).to(dev).view(torch.uint8)
+    sw = ops.rle_slot_words(H, W)
+    flat = torch.empty(S * (4 + sw), dtype=torch.int32, device=dev)
+    slots, table = ops.rle_encode(masks, None, sw, out=flat)
+
+    def out_host():      # what ProposalRecorder and generate() do today: the whole set over the bus, a Python list per mask, ctypes per mask
+        s, t = ops.rle_split(flat.cpu().numpy(), S, sw)
+        return [hsam.coco_encode_rle({"size": [H, W], "counts": hsam.rle_from_slot(s[i], int(t[i, 0]), int(t[i, 1]), H, W)})["counts"]
+                for i in range(S)]
+
+    def out_device():
+        return [b.decode("ascii") for b in hsam.strings_from_device(slots, table, H, W)]
+
+    strings = out_host()
+    assert out_device() == strings
+    lengths = [len(x) for x in strings]
+    n_counts = table[:, 0].cpu().numpy()
+
+    def in_host():       # what StoredProposals._load + rle_pack do today
+        return ops.rle_pack([hsam.rle_counts_from_string(x) for x in strings], H, W, device=dev)
+
+    def in_device():
+        buf, _, n = ops.rle_strings_pack(strings)
+        d = buf.to(dev, non_blocking=True)
+        return ops.rle_from_strings(d[8 * (S + 1):], d[:8 * (S + 1)].view(torch.int64), S, max(int(n.max()), 1))[:2]
+
+    (hs, ht), (ds, dt) = in_host(), in_device()
+    torch.cuda.synchronize()
+    assert torch.equal(ht, dt) and hs.shape == ds.shape
+    for i in range(S):
+        assert torch.equal(hs[i, :n_counts[i]], ds[i, :n_counts[i]])
+    out_t = alternated_ms(out_host, out_device, reps)
+    in_t = alternated_ms(in_host, in_device, reps)
+    cap = ops.RLE_STRING_CAP_PER_ENTRY * S
+    sbuf = torch.empty(ops.rle_strings_bytes(S, cap), dtype=torch.uint8, device=dev)
+    data, offsets, _ = ops.rle_to_strings(slots, table, cap, out=sbuf)
+    back = torch.empty(S * (4 + int(ds.shape[1])), dtype=torch.int32, device=dev)
+    total = int(offsets[S])
+    k_out = device_spread(lambda: ops.rle_to_strings(slots, table, cap, out=sbuf), reps)
+    k_in = device_spread(lambda: ops.rle_from_strings(data[:total], offsets, S, int(ds.shape[1]), out=back), reps)
+    return {"S": S, "H": H, "W": W, "slot_words": sw, "counts_per_mask": {"min": int(n_counts.min()), "median": float(np.median(n_counts)),
+                                                                         "max": int(n_counts.max())},
+            "string_bytes_per_mask": {"min": min(lengths), "median": float(statistics.median(lengths)), "max": max(lengths)},
+            "string_bytes_total": total, "default_cap_bytes": cap, "bytes_per_count": round(total / float(n_counts.sum()), 3),
+            "bus_bytes_host_path_out": 4 * S * (4 + sw), "bus_bytes_device_path_out": ops.rle_strings_bytes(S, 0) + total,
+            "to_python_strings_host_path": out_t[0], "to_python_strings_device_path": out_t[1],
+            "ratio_out_host_over_device": round(out_t[0]["median_ms"] / out_t[1]["median_ms"], 2),
+            "from_python_strings_host_path": in_t[0], "from_python_strings_device_path": in_t[1],
+            "ratio_in_host_over_device": round(in_t[0]["median_ms"] / in_t[1]["median_ms"], 2),
+            "kernels_rle_to_strings": k_out, "kernel_rle_from_strings": k_in}
+
+
 def polygons_leg(dev, reps, cli_images):
     import shutil
     import subprocess
@@ -660,6 +736,8 @@ def main():
                     help="measure rle_select against a device copy and the host re-pack; writes profiles/rle_select_bench.json")
     ap.add_argument("--clean", action="store_true",
                     help="measure rle_remove_small_regions against decode -> clean -> encode; writes profiles/rle_clean_bench.json")
+    ap.add_argument("--strings", action="store_true",
+                    help="measure the device string codec against the host codec per record; writes profiles/rle_strings_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
@@ -670,6 +748,14 @@ def main():
     if args.polygons:
         out = {"polygons": polygons_leg(dev, args.reps, args.cli_images), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_polygons_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
+    if args.strings:
+        out = {"strings": strings_leg(dev, args.reps), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_strings_bench.json")
         with open(path, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
