@@ -127,6 +127,10 @@ constexpr int REF_MASK_GROUP = 32;
 //   lane: a = 0; for e = 0..15 in order: a = fma(m_e, v_e, a) in fp32 (m_e is 0 or 1: the products are exact, the 16-term sum
 //   carries at most a few 1e-8 of relative error); the 64 lane sums folded in fp32 by pool_sum_f's fixed DPP tree; the wave's
 //   sum widened to double; partials over a mask's waves are added in double by the scoring kernels as before.
+// The partials give a mask's INSIDE sum and the map's total; the final reductions (coherence_final_kernel, ref_coherence_body)
+// take the outside sum as  total - inside  while the mask leaves at least half of the plane outside (or covers all of it), and
+// otherwise sum the outside pixels themselves in double (pool_outside_sum, one function for both reductions: the entries stay
+// the same bits) -- the float32 roundings of two large sums must not be divided by a small outside count.
 struct PoolMap {
   const float* attn;   // the heat-map
   int dirflag, sidx;   // gen_dir_mask weight; index of the map in the partial arrays
@@ -298,6 +302,64 @@ __device__ __forceinline__ void pool_block(int blk, const PoolMap (&pm)[NS], int
   }
 }
 
+// ---- the outside sum of a mask that leaves little outside ---------------------------------------------------------------------
+// The final reductions take a mask's outside sum as  total - inside.  Both are sums of float32 wave partials: each carries up to
+// 22 roundings of its own size (15 adds in a lane, 6 folds, the widening exact), so the difference is off by up to
+// 22 u (total + inside), u = 2^-24 -- harmless beside an outside sum of the total's size, but divided by a small one it is
+// the whole error of the score: with one pixel outside a 64 x 65 plane the score missed the bound of
+// tests/coherence_cases.py 117 times over.
+// Switch point.  tests/coherence_cases.py allows an implementation C = 64 roundings of  |in| + |out|, of which the reference's
+// own rounding of its mean, of a / mean and of the result take 3.  With f = (HW - c) / HW the outside share of the plane and a
+// heat-map spread evenly over it (outside sum = f total), the outside term is  black / f * (1 - inside / total), and the up to
+// 22 + 22 roundings of inside / total reach it multiplied by (1 - f) / f:  44 (1 - f) / f + 3 <= 64  <=>  f >= 0.42.  The switch is
+// the next plain value above that, f < 1/2: a mask that covers more than half of the plane (and not all of it) has its outside
+// pixels summed directly.  (The 1 % .. 40 % masks of the benchmark and SAM's proposals but for a background-sized one stay on
+// the subtraction; a full mask does too: its  total - inside  is 0 bit for bit and the outside mean 0 / 0 = NaN, see pool_block.)
+__device__ __forceinline__ bool pool_outside_direct(unsigned long long c, long long HW) {
+  return (long long)c < HW && 2 * (HW - (long long)c) < HW;
+}
+// The direct sum, by ONE WHOLE WAVE (all 64 lanes call it with the same arguments; the result is valid in every lane): lane l
+// walks the 16-pixel runs l, l + 64, ... of the plane with pool_block's 16-byte mask loads and its byte -> (byte != 0) rule,
+// and adds the normalised value of every pixel outside the mask -- the same float32 expression as pool_block's, same bits -- in
+// double, in pixel order; the lanes are folded by wave_sum_d's fixed butterfly.  Deterministic; no float32 sum at all.  At most
+// half of the plane's values are computed, and a run without an outside pixel costs its mask load alone.  Out of line: the
+// reductions that call it are latency-bound loops unrolled four masks wide, and this is their cold path.
+__device__ __noinline__ double pool_outside_sum(const float* __restrict__ attn, const uint8_t* __restrict__ m, long long HW, int W,
+                                                int dirflag, float mn, float range) {
+  const int lane = threadIdx.x & 63;
+  DirRamp ramp;
+  ramp.init(dirflag, W);
+  double acc = 0.0;
+  for (long long p0 = (long long)lane * PX_LANE; p0 < HW; p0 += 64ll * PX_LANE) {
+    unsigned w4[4] = {0u, 0u, 0u, 0u};
+    if (p0 + PX_LANE <= HW) {
+      const pool_u32x4 mv = *(const pool_u32x4_u*)(m + p0);
+      w4[0] = mv.x; w4[1] = mv.y; w4[2] = mv.z; w4[3] = mv.w;
+    } else {      // the plane's last run: byte loads, pixels beyond the plane count as inside (never summed, never read)
+#pragma unroll
+      for (int e = 0; e < PX_LANE; ++e) {
+        const unsigned byte = p0 + e < HW ? (unsigned)m[e + p0] : 1u;
+        w4[e >> 2] |= byte << (8 * (e & 3));
+      }
+    }
+    unsigned out16 = 0;      // bit e: pixel p0 + e lies outside the mask
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const unsigned w = w4[q];
+      const unsigned z = ~((((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) >> 7) & 0x01010101u;      // 1 per zero byte (as pool_block)
+      out16 |= ((z & 1u) | ((z >> 7) & 2u) | ((z >> 14) & 4u) | ((z >> 21) & 8u)) << (4 * q);
+    }
+    if (out16 == 0) continue;
+    int xcol = (int)(p0 % W);
+#pragma unroll 1
+    for (int e = 0; e < PX_LANE; ++e) {
+      if ((out16 >> e) & 1u) acc += (double)(((attn[p0 + e] - mn) / range) * ramp.at(xcol));
+      if (++xcol >= W) xcol = 0;
+    }
+  }
+  return wave_sum_d(acc);
+}
+
 // The kernels below come in pairs: the main launch covers the blocks that lie wholly inside the plane (FULL: HW / PIX_PER_BLOCK
 // of them -- all 100 of a 640 x 640 plane), a second, small launch the partial last block when there is one (!FULL, one map at a
 // time; its 16 byte loads per lane and predicates would otherwise set the register count of the main kernel).
@@ -321,7 +383,9 @@ __global__ __launch_bounds__(256) void coherence_final_kernel(const double* __re
                                                               const unsigned* __restrict__ part_cnt,
                                                               const double* __restrict__ part_tot,
                                                               int nblk, int N, long long HW,
-                                                              float black, float* __restrict__ score) {
+                                                              float black, float* __restrict__ score,
+                                                              const float* __restrict__ attn, const uint8_t* __restrict__ masks, int W,
+                                                              int dirflag, const int* __restrict__ stats) {
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
@@ -336,9 +400,14 @@ __global__ __launch_bounds__(256) void coherence_final_kernel(const double* __re
   s = wave_sum_d(s);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+  double outside = tot - s;
+  if (pool_outside_direct(c, HW)) {      // wave-uniform: tot, s and c are the same in all lanes
+    const float mn = ord2f(stats[0]), mx = ord2f(stats[1]);
+    outside = pool_outside_sum(attn, masks + (long long)n * HW, HW, W, dirflag, mn, mx - mn);
+  }
   if (lane != 0) return;
   const double mean = tot / (double)HW;
-  const double in_sum = s / mean, out_sum = (tot - s) / mean;
+  const double in_sum = s / mean, out_sum = outside / mean;
   // (imgattn*(2-black)*m/m.sum()).sum() - (imgattn*black*(1-m)/(1-m).sum()).sum()
   const double a = (double)(2.f - black) * in_sum / (double)c;
   const double bterm = (double)black * out_sum / (double)(HW - (long long)c);
@@ -780,9 +849,12 @@ __device__ __forceinline__ void ref_masked_pool_last(int blk, const float* const
 
 // the coherence scores gem [N] of sentence s of a row from the pooling partials (one workgroup; shared by ref_score_body and the
 // sweep's scoring kernel: the same sums in the same order)
+// attn / dirflag: the sentence's heat-map and direction; masks, part_mm: the row's -- read only for a mask that takes
+// pool_outside_sum
 __device__ __forceinline__ void ref_coherence_body(float black, int s, int N, int H, int W, const double* __restrict__ part_sum,
                                                    const unsigned* __restrict__ part_cnt, const double* __restrict__ part_tot, int nparts,
-                                                   float* __restrict__ gem) {
+                                                   float* __restrict__ gem, const float* __restrict__ attn, int dirflag,
+                                                   const uint8_t* __restrict__ masks, const float* __restrict__ part_mm) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long HW = (long long)H * W;
   // coherence_final_kernel's reduction for this sentence's N masks.  One wave per mask, lanes stride over the per-wave
@@ -831,9 +903,15 @@ __device__ __forceinline__ void ref_coherence_body(float black, int s, int N, in
       unsigned long long cr = c[i];
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) cr += __shfl_xor(cr, o);
+      double outside = tot - smr;
+      if (nb + i < N && pool_outside_direct(cr, HW)) {      // wave-uniform, as in coherence_final_kernel
+        float mn, mx;
+        ref_fold_minmax(part_mm, s, lane, mn, mx);
+        outside = pool_outside_sum(attn, masks + (long long)(nb + i) * HW, HW, W, dirflag, mn, mx - mn);
+      }
       if (lane == 0 && nb + i < N) {
         const double mean = tot / (double)HW;
-        const double in_sum = smr / mean, out_sum = (tot - smr) / mean;
+        const double in_sum = smr / mean, out_sum = outside / mean;
         const double a = (double)(2.f - black) * in_sum / (double)cr;
         const double bterm = (double)black * out_sum / (double)(HW - (long long)cr);
         gem[nb + i] = (float)(a - bterm);
@@ -847,12 +925,13 @@ __device__ __forceinline__ void ref_score_body(const RefSentences& rs, int s, bo
                                                const float* __restrict__ text, const long long* __restrict__ boxes, int N, int E, int H,
                                                int W, float logit_scale, float r_mix, int k1, int k2, float alpha,
                                                const double* __restrict__ part_sum, const unsigned* __restrict__ part_cnt,
-                                               const double* __restrict__ part_tot, int nparts, float* __restrict__ gem_all,
+                                               const double* __restrict__ part_tot, int nparts, const uint8_t* __restrict__ masks,
+                                               const float* __restrict__ part_mm, float* __restrict__ gem_all,
                                                float* __restrict__ clip_all, float* __restrict__ neg_all, float* __restrict__ soft_all,
                                                int* __restrict__ idx_all, unsigned long long* __restrict__ iu_all,
                                                unsigned* __restrict__ done) {
   float* gem = gem_all + (long long)s * N;
-  ref_coherence_body(rs.black[s], s, N, H, W, part_sum, part_cnt, part_tot, nparts, gem);
+  ref_coherence_body(rs.black[s], s, N, H, W, part_sum, part_cnt, part_tot, nparts, gem, rs.attn[s], rs.dirflag[s], masks, part_mm);
   if (threadIdx.x < 4) iu_all[4 * s + threadIdx.x] = 0ull;
   if (first && threadIdx.x == 0) *done = 0u;
   __syncthreads();
@@ -932,7 +1011,7 @@ __global__ __launch_bounds__(256) void grp_score_kernel(const GroupRefDev* __res
   const int s = blockIdx.x;
   if (s >= g.S) return;
   ref_score_body(g.rs, s, blockIdx.x == 0 && blockIdx.y == 0, g.hybrid, g.text, g.boxes, g.N, E, g.H, g.W, logit_scale, r_mix, g.k1, g.k2,
-                 alpha, g.part_sum, g.part_cnt, g.part_tot, g.nparts, g.gem, g.clip, g.neg, g.soft, g.idx, g.iu, done);
+                 alpha, g.part_sum, g.part_cnt, g.part_tot, g.nparts, g.masks, g.part_mm, g.gem, g.clip, g.neg, g.soft, g.idx, g.iu, done);
 }
 
 // grid (blocks, 2 maxS, R): every block counts on `done` (those beyond their row's sentences do nothing else); the last one adds
@@ -1104,7 +1183,8 @@ __global__ __launch_bounds__(256) void grp_sweep_score_kernel(const GroupRefDev*
     float* clip = gem + N;
     float* neg = clip + N;
     float* soft = neg + N;
-    ref_coherence_body(g.rs.black[s], s, N, g.H, g.W, g.part_sum, g.part_cnt, g.part_tot, g.nparts, gem);
+    ref_coherence_body(g.rs.black[s], s, N, g.H, g.W, g.part_sum, g.part_cnt, g.part_tot, g.nparts, gem, g.rs.attn[s], g.rs.dirflag[s],
+                       g.masks, g.part_mm);
     __syncthreads();
     __threadfence_block();
     score_lists_body(g.hybrid, g.text + (long long)g.rs.sent_row[s] * E, g.text + (long long)g.rs.nphr_row[s] * E,
@@ -1439,7 +1519,7 @@ int hgl_coherence_scores(const float* imgattn, const uint8_t* masks, int N, int 
     if (coh_nblk(H, W) > nfull)
       hipLaunchKernelGGL(masked_pool_kernel<false>, dim3(1, ngrp), dim3(256), 0, st, imgattn, masks, N, H, W, dirflag, stats, psum, pcnt, ptot, nfull);
   }
-  hipLaunchKernelGGL(coherence_final_kernel, dim3((N + 3) / 4), dim3(256), 0, st, psum, pcnt, ptot, nb, N, HW, black, score);
+  hipLaunchKernelGGL(coherence_final_kernel, dim3((N + 3) / 4), dim3(256), 0, st, psum, pcnt, ptot, nb, N, HW, black, score, imgattn, masks, W, dirflag, stats);
   return hgl_check_launch("coherence_scores");
 }
 
