@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import ops, synth
+from .staging import HarvestQueue, PinnedPool
 
 
 @dataclass
@@ -144,7 +145,7 @@ class HybridGLPipeline:
         self.on_overflow = on_overflow
         # run(on_overflow="rescue"): moved totals met, groups / refs done again in f32, and those refs' dataset positions
         self.rescue_stats = {"events": 0, "groups": 0, "refs": 0, "positions": []}
-        self._rescue_bufs = []    # pinned int32 [3] snapshot buffers that are free
+        self._rescue_bufs = PinnedPool()      # pinned int32 [3] snapshot buffers that are free
         self._rs = None           # the running loop's rescue state
         # run(): proposals, hybrid features and GEM features of the last `image_cache` images with an image_id (the dataset
         # yields one item per REF, Hybridgl_main.py:79, and the refs of an image are not always neighbours: RefCOCO has 2.6
@@ -178,9 +179,9 @@ class HybridGLPipeline:
         self.idx_log = []   # per sentence: device int32 [2] = (index of the pure-CLIP winner, index with spatial guidance)
         self._n_refs = 0
         self.record_predictions = bool(record_predictions)
-        self._pred_pending = []   # copies in flight: (ref position, sentences, H, W, slot words, pinned buffer, event), in log order
+        self._pred_free = PinnedPool()      # pinned staging buffers whose copies have completed
+        self._pred_pending = HarvestQueue(self._pred_free)      # in log order: (ref position, sentences, H, W, slot words, pinned buffer)
         self._pred_done = []      # per sentence, in log order: ((H, W), counts of the pure winner, counts of the final one)
-        self._pred_free = []      # pinned staging buffers whose copies have completed
         self.sweep = None
         if sweep is not None:
             self.sweep = [(float(t[0]), float(t[1]), int(t[2]), int(t[3])) for t in sweep]
@@ -307,40 +308,20 @@ class HybridGLPipeline:
         flat = torch.empty(2 * n * (4 + sw), dtype=torch.int32, device=masks.device)
         ops.rle_encode(masks, idx.reshape(-1), sw, out=flat)
         self._harvest_predictions()
-        host = None
-        for i, b in enumerate(self._pred_free):
-            if b.numel() >= flat.numel():
-                host = self._pred_free.pop(i)
-                break
-        if host is None:
-            host = torch.empty(flat.numel(), dtype=torch.int32, pin_memory=True)
+        host = self._pred_free.take(flat.numel(), torch.int32)
         host[:flat.numel()].copy_(flat, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        self._pred_pending.append((ref_index, n, H, W, sw, host, ev))
+        self._pred_pending.put(ev, (ref_index, n, H, W, sw, host), (host,))
 
     def _harvest_predictions(self, wait=False):
         """The copies that have completed (wait=True: all of them), oldest first, reduced to their counts arrays; their
         staging buffers return to the pool.  Host memory grows with the number of runs, not with pixels."""
-        from .sam import rle_from_slot
-        while self._pred_pending:
-            ref_index, n, H, W, sw, host, ev = self._pred_pending[0]
-            if wait:
-                ev.synchronize()
-            elif not ev.query():
-                break
-            self._pred_pending.pop(0)
-            slots, table = ops.rle_split(host.numpy(), 2 * n, sw)
-            rows = []
-            for e in range(2 * n):
-                nc, form = int(table[e, 0]), int(table[e, 1])
-                if form == 0:
-                    rows.append(slots[e, :nc].astype(np.uint32))      # a copy: the buffer is reused
-                else:
-                    rows.append(np.asarray(rle_from_slot(slots[e], nc, form, H, W), dtype=np.uint32))
+        from .sam import counts_from_set
+        for ref_index, n, H, W, sw, host in self._pred_pending.drain(wait):
+            rows = counts_from_set(*ops.rle_split(host.numpy(), 2 * n, sw), H, W)      # copies: the buffer is reused
             for j in range(n):
                 self._pred_done.append(((H, W), rows[2 * j], rows[2 * j + 1]))
-            self._pred_free.append(host)
 
     def predictions(self):
         """The winning masks of every sentence scored so far, ordered and keyed like partial_rows(): a list of
@@ -786,7 +767,7 @@ class HybridGLPipeline:
 
     def _snapshot(self, gid, stream):
         """(gid, pinned int32 [3], event): the three range counters as of this point of `stream`, nothing waited for"""
-        buf = self._rescue_bufs.pop() if self._rescue_bufs else torch.zeros(3, dtype=torch.int32).pin_memory()
+        buf = self._rescue_bufs.take(3, torch.int32)
         with torch.cuda.stream(stream):
             ops.split_overflow_snapshot(buf)
             ev = torch.cuda.Event()
@@ -797,7 +778,7 @@ class HybridGLPipeline:
         _, buf, ev = snap
         ev.synchronize()
         total = sum(int(v) for v in buf.tolist())
-        self._rescue_bufs.append(buf)
+        self._rescue_bufs.give(buf)
         return total
 
     def _rescue_stage_end(self, gid, ready):
@@ -842,7 +823,7 @@ class HybridGLPipeline:
                 led.open(self.groups_run, nxt)
         torch.cuda.synchronize(dev)
         for snap in rs["snaps"]:
-            self._rescue_bufs.append(snap[1])
+            self._rescue_bufs.give(snap[1])
         rs["snaps"], rs["gate"] = [], None
         cp = led.oldest_checkpoint()
         if cp is not None:

@@ -36,6 +36,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .sam import build_records, counts_from_set      # noqa: F401  (build_records: the one record builder, importable from here)
+from .staging import HarvestQueue, PinnedPool
 
 RECORD_KEYS = ("segmentation", "area", "bbox", "predicted_iou", "point_coords", "stability_score", "crop_box")
 
@@ -119,22 +121,6 @@ class ProposalStore:
         return recs
 
 
-def build_records(H, W, counts, areas, xywh, iou, stab, points, crop_boxes, strings=None):
-    """the record list of one image from its survivors' host arrays, field for field what generate() builds in coco_rle mode;
-    strings: the COCO strings (bytes) of the masks where they exist already (written on the device), then counts is not read"""
-    from .sam import coco_encode_rle
-    out = []
-    for i in range(len(areas)):
-        cb = crop_boxes[i]
-        seg = (coco_encode_rle({"size": [int(H), int(W)], "counts": counts[i]}) if strings is None else
-               {"size": [int(H), int(W)], "counts": strings[i].decode("ascii")})
-        out.append({"segmentation": seg, "area": int(areas[i]),
-                    "bbox": [int(v) for v in xywh[i]], "predicted_iou": float(iou[i]), "point_coords": [points[i].tolist()],
-                    "stability_score": float(stab[i]),
-                    "crop_box": [int(cb[0]), int(cb[1]), int(cb[2] - cb[0]), int(cb[3] - cb[1])]})   # XYWH
-    return out
-
-
 class _Recorded:
     """a group on its way through a ProposalRecorder: the wrapped generator's state and the images' ids"""
     __slots__ = ("inner", "ids", "overflow")
@@ -162,8 +148,8 @@ class ProposalRecorder:
         self.store = store if isinstance(store, ProposalStore) else ProposalStore(store)
         self.recording = True       # False: calls pass through unrecorded (a rehearsal on images that are not the dataset's)
         self.written = 0
-        self._pending = collections.deque()      # (image_id, H, W, n, sw, runs host, scalars host, event)
-        self._free = []                          # pinned buffers whose copies have completed
+        self._pool = PinnedPool()
+        self._pending = HarvestQueue(self._pool)      # payloads (image_id, H, W, n, sw, runs host, scalars host, kept)
         self._seen = set()
         if meta is not None:
             self.store.write_meta(meta)
@@ -201,20 +187,12 @@ class ProposalRecorder:
         return out
 
     def generate_device_crops(self, image, image_id=None):
-        gen = self.generator
-        st = gen._begin([image], None, None, 8)      # generate_device_crops, with the sources kept for the record
-        m, xywh, iou, stab, src = gen.group_finish(gen.group_cleanup(st))[0]
+        (m, xywh, iou, stab, src), size = self.generator.crops_of_one(image)      # generate_device_crops, with the sources kept
         self._harvest()
         self._record(image_id, m, xywh, iou, stab, src)
-        return (m, xywh, iou, stab) + gen._sources(src, *st.sizes[0])
+        return (m, xywh, iou, stab) + self.generator._sources(src, *size)
 
     # ---- staging
-    def _take(self, numel, dtype):
-        for i, b in enumerate(self._free):
-            if b.dtype == dtype and b.numel() >= numel:
-                return self._free.pop(i)
-        return torch.empty(max(int(numel), 1), dtype=dtype, pin_memory=True)
-
     def _record(self, image_id, masks, xywh, iou, stab, src):
         if not self.recording:
             return
@@ -225,7 +203,7 @@ class ProposalRecorder:
         self._seen.add(image_id)
         n, H, W = (int(v) for v in masks.shape)
         if n == 0:
-            self._pending.append((image_id, H, W, 0, 0, None, None, None, None))
+            self._pending.put(None, (image_id, H, W, 0, 0, None, None, None))      # no copy to wait for: written in its turn
             return
         sw = ops.rle_slot_words(H, W)
         flat = torch.empty(n * (4 + sw), dtype=torch.int32, device=masks.device)
@@ -240,14 +218,14 @@ class ProposalRecorder:
             ops.rle_to_strings(slots, table, cap, out=out)
             sc.append(table[:, 2].double()[None])      # the areas, which the host mode reads from the table
             kept, flat = (flat, cap), out              # the encoded set stays on the device until the file is written
-        runs = self._take(flat.numel(), flat.dtype)
+        runs = self._pool.take(flat.numel(), flat.dtype)
         runs[:flat.numel()].copy_(flat, non_blocking=True)
         sc = torch.cat(sc)
-        scal = self._take(sc.numel(), torch.float64)
+        scal = self._pool.take(sc.numel(), torch.float64)
         scal[:sc.numel()].copy_(sc.reshape(-1), non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        self._pending.append((image_id, H, W, n, sw, runs, scal, ev, kept))
+        self._pending.put(ev, (image_id, H, W, n, sw, runs, scal, kept), (runs, scal))
 
     def _strings(self, n, sw, H, W, staged, kept):
         """the strings of one image out of the staged offsets | status | bytes; `kept`: the encoded set on the device and the cap"""
@@ -265,15 +243,7 @@ class ProposalRecorder:
 
     def _harvest(self, wait=False):
         """write the files of the copies that have completed (wait=True: of all), oldest first; their buffers return to the pool"""
-        from .sam import rle_from_slot
-        while self._pending:
-            image_id, H, W, n, sw, runs, scal, ev, kept = self._pending[0]
-            if ev is not None:
-                if wait:
-                    ev.synchronize()
-                elif not ev.query():
-                    break
-            self._pending.popleft()
+        for image_id, H, W, n, sw, runs, scal, kept in self._pending.drain(wait):
             if n == 0:
                 self.store.write(image_id, [])
             else:
@@ -281,14 +251,12 @@ class ProposalRecorder:
                 s = scal.numpy()[:rows * n].reshape(rows, n)
                 if kept is None:
                     slots, table = ops.rle_split(runs.numpy(), n, sw)
-                    counts = [rle_from_slot(slots[e], int(table[e, 0]), int(table[e, 1]), H, W) for e in range(n)]
-                    strings, areas = None, table[:, 2]
+                    counts, strings, areas = counts_from_set(slots, table, H, W), None, table[:, 2]
                 else:
                     counts, strings, areas = None, self._strings(n, sw, H, W, runs.numpy(), kept), s[7].astype(np.int64)
                 pts, cbs = self.generator._sources(torch.from_numpy(s[2].astype(np.int64)), H, W)
                 self.store.write(image_id, build_records(H, W, counts, areas, s[3:7].T.astype(np.int64), s[0].astype(np.float32),
                                                          s[1].astype(np.float32), pts, cbs, strings))
-                self._free += [runs, scal]
             self.written += 1
 
     def forget(self):
@@ -347,6 +315,17 @@ def _stage_group(rows, counts, area, buf):
     return S, sw, first
 
 
+def _back_layout(S, G, thin, device_strings):
+    """The one int32 read-back of a StoredProposals group of S entries in G images: (its words, the slices of its parts).
+    aux: boxes | status [2,S,4].  Thinning only: out_src [S] and out_n [G] of ops.rle_select; nms: the output block of ops.rle_nms
+    = out_idx [S] | result [S,4] | out_n [G], and codes: the result rows inside it.  Reading strings on the device only: read, the
+    codec's status [S,4].  The parts lie in this order without a gap; a part the mode does not have is empty."""
+    t = int(bool(thin))
+    e = np.cumsum([0, 8 * S, t * S, t * G, t * S, 4 * t * S, t * G, 4 * S * bool(device_strings)]).tolist()
+    return e[7], {"aux": slice(e[0], e[1]), "out_src": slice(e[1], e[2]), "out_n": slice(e[2], e[3]), "nms": slice(e[3], e[6]),
+                  "codes": slice(e[4], e[5]), "read": slice(e[6], e[7])}
+
+
 def _undecoded(store, image_id, entry, code, what="mask of the stated size"):
     return ValueError(f"proposal store {store.directory}: image {image_id} entry {entry}: its counts do not decode to a {what} "
                       f"(status {code})")
@@ -399,8 +378,8 @@ class StoredProposals:
         self._thinned = {}      # image id -> (entries read, entries handed out)
         self._rows = collections.OrderedDict()      # image id -> _Rows, the last `keep` images
         self._lock = threading.Lock()
-        self._free = collections.deque()            # (pinned buffer, the event behind its upload)
-        self._back = []                             # pinned read-back buffers group_cleanup has finished with
+        self._up = PinnedPool()                     # upload staging: a buffer returns with the event behind its upload
+        self._back = PinnedPool(floor=4096)         # read-back buffers group_cleanup has finished with
         self.loaded = 0                             # images parsed (<= images asked for)
 
     def records(self, image_id):
@@ -496,7 +475,7 @@ class StoredProposals:
         sw = max(r.sw for r, n in zip(st.rows, st.counts) if n)
         T = sum(int(r.soff[n]) for r, n in zip(st.rows, st.counts))
         words = 2 * (S + 1) + S * (2 + by_area) + (T + 3) // 4
-        host = self._staging(words)
+        host = self._up.take(words, torch.int32)
         h = host.numpy()[:words]
         offs = h[:2 * (S + 1)].view(np.int64)
         cols = h[2 * (S + 1):2 * (S + 1) + 2 * S].reshape(2, S)
@@ -514,23 +493,19 @@ class StoredProposals:
                     extra[e:e + n] = r.area[:n]
                 base += t
         offs[S] = base
-        dev = torch.empty(words, dtype=torch.int32, device=self.device)
-        dev.copy_(host[:words], non_blocking=True)
-        up = torch.cuda.Event()
-        up.record()
-        self._free.append((host, up))
+        dev = self._upload(host, words)
         a, b = 2 * (S + 1) + 2 * S, 2 * (S + 1) + S * (2 + by_area)
         return S, sw, first, (dev[:2 * (S + 1)].view(torch.int64), dev[b:].view(torch.uint8)[:T], dev[2 * (S + 1):a].reshape(2, S), dev[a:b])
 
     # ---- device half (the loop's thread)
-    def _staging(self, numel):
-        """a pinned buffer whose last upload has completed, or a new one"""
-        for _ in range(len(self._free)):
-            buf, ev = self._free.popleft()
-            if buf.numel() >= numel and ev.query():
-                return buf
-            self._free.append((buf, ev))
-        return torch.empty(max(int(numel), 1), dtype=torch.int32, pin_memory=True)
+    def _upload(self, host, words):
+        """the first `words` of a staging buffer on the device: one copy, and the buffer back in the pool behind its event"""
+        dev = torch.empty(words, dtype=torch.int32, device=self.device)
+        dev.copy_(host[:words], non_blocking=True)
+        up = torch.cuda.Event()
+        up.record()
+        self._up.give(host, up)
+        return dev
 
     def group_begin(self, images, cap=None, encoded_event=None, image_ids=None):
         if image_ids is None or len(image_ids) != len(images):
@@ -557,38 +532,32 @@ class StoredProposals:
         else:
             # (room for the group however wide its slots are; a group without an entry stages nothing)
             room = _group_words(sum(st.counts), max([r.sw for r in st.rows] + [0]), by_area)
-            host = self._staging(room) if room else torch.empty(0, dtype=torch.int32)
+            host = self._up.take(room, torch.int32) if room else torch.empty(0, dtype=torch.int32)
             S, sw, st.first = _stage_group(st.rows, st.counts, by_area, host.numpy())
             if S == 0:
                 return st
-            numel = _group_words(S, sw, by_area)
-            dev = torch.empty(numel, dtype=torch.int32, device=self.device)
-            dev.copy_(host[:numel], non_blocking=True)
-            up = torch.cuda.Event()
-            up.record()
-            self._free.append((host, up))
-            slots, table, cols, area = _split_group(dev, S, sw)
+            slots, table, cols, area = _split_group(self._upload(host, _group_words(S, sw, by_area)), S, sw)
         # ONE int32 buffer leaves in one copy into pooled pinned memory: boxes | status and, thinning, | out_src | out_n | the
         # NMS's out_idx, result, out_n (| the string codec's status, reading strings on the device); group_cleanup reads it,
         # where SAM reads its first counts, and hands the buffer back
-        words = 14 * S + 2 * G if thin else 8 * S
-        back = torch.empty(words + (4 * S if dev_strings else 0), dtype=torch.int32, device=self.device)
+        words, part = _back_layout(S, G, thin, dev_strings)
+        back = torch.empty(words, dtype=torch.int32, device=self.device)
         if dev_strings:
             offs, data, cols, area = parts
-            slots, table, _ = ops.rle_from_strings(data, offs, S, sw, status=back[words:].view(S, 4))
+            slots, table, _ = ops.rle_from_strings(data, offs, S, sw, status=back[part["read"]].view(S, 4))
         if thin:
             scores = {"predicted_iou": cols[0], "stability_score": cols[1], "area": area, "stored": None}[self.mask_nms_score]
             if scores is not None:
                 scores = scores.view(torch.float32)
             result = ops.rle_nms(slots, table, st.sizes, st.counts, scores, self.mask_nms_thresh, self.mask_nms_metric,
-                                 out=back[9 * S + G:words])[2]
+                                 out=back[part["nms"]])[2]
             slots, table, cols, _, _ = ops.rle_select(slots, table, st.sizes, st.counts, nms_result=result, cols=cols,
-                                                      max_keep=min(caps) if caps else None, back=back[8 * S:9 * S + G])
+                                                      max_keep=min(caps) if caps else None,
+                                                      back=back[part["out_src"].start:part["out_n"].stop])
         st.iou, st.stab = cols[0].view(torch.float32), cols[1].view(torch.float32)
-        st.masks, st.boxes = self._decode(slots, table, st.sizes, st.counts, back[:8 * S].view(2, S, 4))[:2]
-        fits = self._back and self._back[-1].numel() >= back.numel()
-        st.host = self._back.pop() if fits else torch.empty(max(back.numel(), 4096), dtype=torch.int32, pin_memory=True)
-        st.host[:back.numel()].copy_(back, non_blocking=True)
+        st.masks, st.boxes = self._decode(slots, table, st.sizes, st.counts, back[part["aux"]].view(2, S, 4))[:2]
+        st.host = self._back.take(words, torch.int32)
+        st.host[:words].copy_(back, non_blocking=True)
         st.ev = torch.cuda.Event()
         st.ev.record()
         return st
@@ -623,14 +592,14 @@ class StoredProposals:
         thin = self.mask_nms_thresh is not None
         S, G = int(st.first[-1]), len(st.rows)
         st.ev.synchronize()
-        words = 14 * S + 2 * G if thin else 8 * S
-        h = st.host.numpy()[:words + (4 * S if self.strings == "device" else 0)].copy()
-        self._back.append(st.host)
+        words, part = _back_layout(S, G, thin, self.strings == "device")
+        h = st.host.numpy()[:words].copy()
+        self._back.give(st.host)
         st.host = None
-        read, h = h[words:].reshape(-1, 4)[:, 0], h[:words]      # the string codec's codes, reading strings on the device (else nothing)
-        boxes, status = h[:8 * S].reshape(2, S, 4)
-        out_src, out_n = h[8 * S:9 * S], h[9 * S:9 * S + G]      # (these three are empty without thinning)
-        codes = h[10 * S + G:14 * S + G].reshape(-1, 4)[:, 0]      # the NMS's result rows: every source entry's code
+        read = h[part["read"]].reshape(-1, 4)[:, 0]      # the string codec's codes, reading strings on the device (else nothing)
+        boxes, status = h[part["aux"]].reshape(2, S, 4)
+        out_src, out_n = h[part["out_src"]], h[part["out_n"]]      # (these three are empty without thinning)
+        codes = h[part["codes"]].reshape(-1, 4)[:, 0]      # the NMS's result rows: every source entry's code
         kept = []
         for g, (iid, r, n, e) in enumerate(zip(st.ids, st.rows, st.counts, st.first)):
             bad = np.flatnonzero(read[e:e + n])

@@ -987,9 +987,13 @@ class SamAutomaticMaskGenerator:
         of one (its encoder batches hold up to 8 crops).  Returns device tensors (masks [n,H,W] u8, boxes_xywh [n,4] i64,
         iou [n], stability [n]) and host arrays (points [n,2] f64, crop_boxes [n,4] i64), in the reference's output order.
         Four host syncs: the group's three and the read-back of the survivors' sources."""
+        (m, xywh, iou, stab, src), size = self.crops_of_one(image)
+        return (m, xywh, iou, stab) + self._sources(src, *size)
+
+    def crops_of_one(self, image):
+        """the crop group of one image through the 8-crop encoder chunk: (group_finish's tuple of the image, its (H, W))"""
         st = self._begin([image], None, None, 8)
-        m, xywh, iou, stab, src = self.group_finish(self.group_cleanup(st))[0]
-        return (m, xywh, iou, stab) + self._sources(src, *st.sizes[0])
+        return self.group_finish(self.group_cleanup(st))[0], st.sizes[0]
 
     def _sources(self, src, H, W):
         """the source indices of an image's survivors on the host: (prompt points [n,2] f64 in image coordinates, crop boxes
@@ -1230,28 +1234,17 @@ class SamAutomaticMaskGenerator:
     def generate(self, image):
         """automatic_mask_generator.py:137-195 -> list of records."""
         H, W = image.shape[:2]
-        if self.crop_n_layers > 0:
-            m, xywh, iou, stab, pts, cbs = self.generate_device_crops(image)
-        else:
-            m, xywh, iou, stab, src = self.generate_device(image)
-            pts, cbs = self._sources(src, H, W)
+        m, xywh, iou, stab, src = self.crops_of_one(image)[0] if self.crop_n_layers > 0 else self.generate_device(image)
+        pts, cbs = self._sources(src, H, W)
         if self.output_mode == "binary_mask":
-            masks = m.bool().cpu().numpy()
-            segs, areas = masks, [int(k.sum()) for k in masks]
+            segs = m.bool().cpu().numpy()
+            areas = [int(k.sum()) for k in segs]
         else:
             # the RLE modes: runs encoded on the device, only runs cross to the host (no [n,H,W] byte copy, no host codec)
             segs, areas = _masks_to_rle(m)
             if self.output_mode == "coco_rle":
                 segs = [coco_encode_rle(r) for r in segs]
-        xywh, iou, stab = xywh.cpu().numpy(), iou.cpu().numpy(), stab.cpu().numpy()
-        out = []
-        for i in range(len(segs)):
-            cb = cbs[i]
-            out.append({"segmentation": segs[i], "area": areas[i], "bbox": [int(v) for v in xywh[i]],
-                        "predicted_iou": float(iou[i]), "point_coords": [pts[i].tolist()],
-                        "stability_score": float(stab[i]),
-                        "crop_box": [int(cb[0]), int(cb[1]), int(cb[2] - cb[0]), int(cb[3] - cb[1])]})   # XYWH
-        return out
+        return build_records(H, W, None, areas, xywh.cpu().numpy(), iou.cpu().numpy(), stab.cpu().numpy(), pts, cbs, segmentations=segs)
 
 
 def mask_to_rle(mask):
@@ -1285,6 +1278,32 @@ def rle_from_slot(slot, n_counts, form, H, W):
     return counts
 
 
+def counts_from_set(slots, table, H, W):
+    """rle_from_slot for every entry of an encoded set on the HOST (ops.rle_split of the copied buffer): a list of uint32
+    arrays, each a copy -- the buffer behind `slots` may be reused"""
+    out = []
+    for slot, (nc, form) in zip(slots, table[:, :2].tolist()):
+        out.append(slot[:nc].astype(np.uint32) if form == 0 else np.asarray(rle_from_slot(slot, nc, form, H, W), dtype=np.uint32))
+    return out
+
+
+def build_records(H, W, counts, areas, xywh, iou, stab, points, crop_boxes, strings=None, segmentations=None):
+    """The record list of one image from its survivors' host arrays (automatic_mask_generator.py:176-192); the `segmentation`
+    of a record, in this order: segmentations[i] as it is (a binary mask, an uncompressed RLE dict), the COCO string strings[i]
+    (bytes, where the device wrote it), the COCO encoding of counts[i]."""
+    out = []
+    for i in range(len(areas)):
+        cb = crop_boxes[i]
+        seg = (segmentations[i] if segmentations is not None else
+               {"size": [int(H), int(W)], "counts": strings[i].decode("ascii")} if strings is not None else
+               coco_encode_rle({"size": [int(H), int(W)], "counts": counts[i]}))
+        out.append({"segmentation": seg, "area": int(areas[i]),
+                    "bbox": [int(v) for v in xywh[i]], "predicted_iou": float(iou[i]), "point_coords": [points[i].tolist()],
+                    "stability_score": float(stab[i]),
+                    "crop_box": [int(cb[0]), int(cb[1]), int(cb[2] - cb[0]), int(cb[3] - cb[1])]})   # XYWH
+    return out
+
+
 def _masks_to_rle(masks, sel=None):
     """masks_to_rle plus the areas of the table: (list of RLE dicts, list of int)"""
     n, H, W = masks.shape
@@ -1297,8 +1316,7 @@ def _masks_to_rle(masks, sel=None):
     flat = torch.empty(S * (4 + sw), dtype=torch.int32, device=masks.device)
     ops.rle_encode(masks, sel, sw, out=flat)
     slots, table = ops.rle_split(flat.cpu().numpy(), S, sw)      # the one device -> host copy
-    rles = [{"size": [H, W], "counts": rle_from_slot(slots[i], int(table[i, 0]), int(table[i, 1]), H, W)} for i in range(S)]
-    return rles, [int(a) for a in table[:, 2]]
+    return [{"size": [H, W], "counts": c.tolist()} for c in counts_from_set(slots, table, H, W)], [int(a) for a in table[:, 2]]
 
 
 def masks_to_rle(masks, sel=None):

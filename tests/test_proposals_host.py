@@ -269,3 +269,51 @@ def test_generator_settings_and_the_flag_rules():
     for flags in (["--real", "--save_proposals", "a", "--save_masks", "m", "--sweep", "r=0.3,0.5"], ["--real", "--proposals_dir", "b"],
                   ["--real"], []):
         drv.check_proposal_flags(parse(flags))
+
+
+# (S, G, thin): the words of StoredProposals' read-back without the string codec's status, then the ranges aux, out_src, out_n,
+# nms, codes -- 8*S, or 14*S + 2*G with the bounds 8*S, 9*S, 9*S+G, 10*S+G and 14*S+G, worked out by hand
+BACK_LAYOUTS = {(1, 1, False): (8, (0, 8), (8, 8), (8, 8), (8, 8), (8, 8)),
+                (1, 3, False): (8, (0, 8), (8, 8), (8, 8), (8, 8), (8, 8)),
+                (5, 1, False): (40, (0, 40), (40, 40), (40, 40), (40, 40), (40, 40)),
+                (5, 3, False): (40, (0, 40), (40, 40), (40, 40), (40, 40), (40, 40)),
+                (1, 1, True): (16, (0, 8), (8, 9), (9, 10), (10, 16), (11, 15)),
+                (1, 3, True): (20, (0, 8), (8, 9), (9, 12), (12, 20), (13, 17)),
+                (5, 1, True): (72, (0, 40), (40, 45), (45, 46), (46, 72), (51, 71)),
+                (5, 3, True): (76, (0, 40), (40, 45), (45, 48), (48, 76), (53, 73))}
+
+
+@pytest.mark.parametrize("strings", [False, True])
+@pytest.mark.parametrize("case", sorted(BACK_LAYOUTS))
+def test_the_read_back_layout_is_the_one_both_halves_spelled_out(case, strings):
+    S, G, thin = case
+    words, aux, out_src, out_n, nms, codes = BACK_LAYOUTS[case]
+    total, part = P._back_layout(S, G, thin, strings)
+    assert total == words + ({1: 4, 5: 20}[S] if strings else 0)
+    got = {k: (v.start, v.stop) for k, v in part.items()}
+    assert got == {"aux": aux, "out_src": out_src, "out_n": out_n, "nms": nms, "codes": codes, "read": (words, total)}
+    chain = [got[k] for k in ("aux", "out_src", "out_n", "nms", "read")]      # disjoint, in order, and they cover [0, total)
+    assert chain[0][0] == 0 and chain[-1][1] == total
+    assert all(a <= b for a, b in chain) and all(x[1] == y[0] for x, y in zip(chain, chain[1:]))
+    assert nms[0] <= codes[0] <= codes[1] <= nms[1] and all(v.step is None for v in part.values())
+
+
+def test_build_records_is_one_builder_for_counts_strings_and_finished_segmentations(lib):
+    """two masks of 5 x 7: the records from their counts, from the strings the device would have written and from ready-made
+    segmentations are the JSON the builder gave before generate() shared it"""
+    counts = [[11, 3, 2, 3, 2, 3, 11], [0, 2, 3, 2, 3, 2, 3, 2, 3, 2, 3, 2, 3, 2, 2, 1]]
+    rest = ([9, 15], np.array([[2, 1, 3, 3], [0, 0, 7, 5]], np.int64), np.array([0.875, 0.5], np.float32),
+            np.array([0.96875, 1.0], np.float32), np.array([[3.5, 2.5], [0.25, 1.0]]), np.array([[0, 0, 7, 5], [1, 0, 7, 4]], np.int64))
+    want = ('[{"segmentation": {"size": [5, 7], "counts": ";320009"}, "area": 9, "bbox": [2, 1, 3, 3], "predicted_iou": 0.875, '
+            '"point_coords": [[3.5, 2.5]], "stability_score": 0.96875, "crop_box": [0, 0, 7, 5]}, '
+            '{"segmentation": {"size": [5, 7], "counts": "02300000000000OO"}, "area": 15, "bbox": [0, 0, 7, 5], "predicted_iou": 0.5, '
+            '"point_coords": [[0.25, 1.0]], "stability_score": 1.0, "crop_box": [1, 0, 6, 4]}]')
+    assert P.build_records is hsam.build_records
+    assert json.dumps(P.build_records(5, 7, counts, *rest)) == want
+    assert json.dumps(P.build_records(5, 7, [np.asarray(c, np.uint32) for c in counts], *rest)) == want
+    assert json.dumps(P.build_records(5, 7, None, *rest, [b";320009", b"02300000000000OO"])) == want
+    segs = [{"size": [5, 7], "counts": ";320009"}, {"size": [5, 7], "counts": "02300000000000OO"}]
+    assert json.dumps(P.build_records(5, 7, None, *rest, segmentations=segs)) == want
+    raw = P.build_records(5, 7, None, *rest, segmentations=[{"size": [5, 7], "counts": c} for c in counts])      # uncompressed_rle
+    assert [r["segmentation"]["counts"] for r in raw] == counts and [type(r["area"]) for r in raw] == [int, int]
+    assert all(type(r["predicted_iou"]) is float and type(r["bbox"][0]) is int and type(r["crop_box"][3]) is int for r in raw)
