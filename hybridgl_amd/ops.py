@@ -4,7 +4,8 @@ Every function validates device/dtype/contiguity, then passes raw pointers to
 libhybridgl.so.  Nothing here computes: a missing library or a CPU tensor raises.
 """
 import ctypes as C
-from itertools import repeat
+from itertools import accumulate, repeat
+from math import prod
 
 import torch
 
@@ -408,10 +409,71 @@ def rle_slot_words(H, W):
     return (int(H) * int(W) + 31) // 32
 
 
+# The int32 blocks the RLE entries hand out as views of ONE flat buffer: name -> the shapes of its parts, in memory order and
+# without a gap, from (S, slot_words, G, C, Sb).  The only statement of these layouts: rle_block and rle_block_words read it.
+RLE_BLOCKS = {
+    "set": lambda S, sw, G, C, Sb: ((S, 4), (S, sw)),                       # table | slots: rle_encode, rle_pack, rle_from_strings
+    "status": lambda S, sw, G, C, Sb: ((S, 4), (S, sw), (S, 4)),            # table | slots | status: rle_from_polygons, rle_merge
+    "clean": lambda S, sw, G, C, Sb: ((S, 4), (S, sw), (S, 4), (S, 4)),     # table | slots | boxes | result: rle_remove_small_regions
+    "select": lambda S, sw, G, C, Sb: ((S, 4), (S, sw), (C, S)),            # table | slots | cols: rle_select's `out`
+    "group": lambda S, sw, G, C, Sb: ((S, 4), (S, sw), (2, S), (C * S,)),   # table | slots | iou, stability bits | area bits, C = 0 / 1: a staged group of proposals.py
+    "back": lambda S, sw, G, C, Sb: ((S,), (G,)),                           # out_src | out_n: rle_select's `back`
+    "nms": lambda S, sw, G, C, Sb: ((S,), (S, 4), (G,)),                    # out_idx | result | out_n: rle_nms
+    "aux": lambda S, sw, G, C, Sb: ((S, 4), (S, 4)),                        # boxes | status: rle_decode_group
+    "match": lambda S, sw, G, C, Sb: ((S, 4), (Sb, 4)),                     # match_a | match_b: rle_match
+}
+
+
+def rle_block_ends(name, S, slot_words=0, G=0, C=0, Sb=0):
+    """where every part of block `name` (RLE_BLOCKS) ends, in int32 elements from the start of the block"""
+    return list(accumulate(map(prod, RLE_BLOCKS[name](S, slot_words, G, C, Sb))))
+
+
+def rle_block(name, flat, S, slot_words=0, G=0, C=0, Sb=0):
+    """the parts of block `name` as views of the flat int32 buffer that begins with it: device tensor, host tensor or numpy
+    array alike"""
+    parts, a = [], 0
+    for shape in RLE_BLOCKS[name](S, slot_words, G, C, Sb):
+        b = a + prod(shape)
+        parts.append(flat[a:b].reshape(shape))
+        a = b
+    return parts
+
+
+def rle_block_words(name, S, slot_words=0, G=0, C=0, Sb=0):
+    """the int32 elements of block `name`: what its flat buffer holds"""
+    return rle_block_ends(name, S, slot_words, G, C, Sb)[-1]
+
+
 def rle_split(flat, S, slot_words):
     """(slots [S, slot_words], table [S, 4]) as views of the flat int32 buffer rle_encode fills (device tensor, host tensor
     or numpy array alike): the table first, then the slots"""
-    return flat[4 * S:4 * S + S * slot_words].reshape(S, slot_words), flat[:4 * S].reshape(S, 4)
+    table, slots = rle_block("set", flat, S, slot_words)
+    return slots, table
+
+
+def _out(buf, numel, dtype, device, name):
+    """The one check of a buffer a caller lends (`out`, `aux`, `back`, `status`): a fresh one when buf is None, else buf itself,
+    both flat.  ValueError unless buf is a contiguous `dtype` tensor of exactly `numel` elements on `device`: its pointer goes
+    to a kernel as it is."""
+    if buf is None:
+        return torch.empty(numel, dtype=dtype, device=device)
+    if buf.numel() != numel or buf.dtype != dtype or not buf.is_contiguous() or buf.device != device:
+        raise ValueError(f"{name}: expected {numel} {str(dtype)[6:]} elements, contiguous, on {device}; got {tuple(buf.shape)} "
+                         f"{str(buf.dtype)[6:]} on {buf.device}" + ("" if buf.is_contiguous() else ", strided"))
+    return buf.view(-1)
+
+
+def _ptr(t):
+    """where a view begins in its buffer -- data_ptr(), except that torch gives 0 for a view without an element and the library
+    wants the slots named also where slot_words is 0"""
+    return t.data_ptr() or t.untyped_storage().data_ptr() + t.storage_offset() * t.element_size()
+
+
+def _rle_ws(device, size_fn, *args):
+    """(pointer, bytes) of the RLE workspace at the size the library's size_fn(*args) asks for"""
+    ws = workspace(size_fn(*args), device, "rle")
+    return ws.data_ptr(), ws.numel()
 
 
 def rle_encode(masks, sel=None, slot_words=None, out=None):
@@ -433,17 +495,12 @@ def rle_encode(masks, sel=None, slot_words=None, out=None):
         sel = sel.reshape(-1).to(torch.int64).contiguous()
         sp, S = sel.data_ptr(), int(sel.numel())
     slot_words = rle_slot_words(H, W) if slot_words is None else int(slot_words)
-    if out is None:
-        out = torch.empty(S * (4 + slot_words), dtype=torch.int32, device=masks.device)
-    elif out.numel() != S * (4 + slot_words):
-        raise ValueError(f"out: expected {S * (4 + slot_words)} int32 elements, got {out.numel()}")
+    out = _out(out, rle_block_words("set", S, slot_words), torch.int32, masks.device, "out")
     slots, table = rle_split(out, S, slot_words)
     if S == 0:
         return slots, table
-    need = lib.hgl_rle_encode_workspace_bytes(S, H, W)
-    ws = workspace(need, masks.device, "rle")
-    base = _dev(out, torch.int32, "out")
-    check(lib.hgl_rle_encode_device(mp, N, H, W, sp, S, base + 16 * S, slot_words, base, ws.data_ptr(), ws.numel(), _stream()),
+    check(lib.hgl_rle_encode_device(mp, N, H, W, sp, S, _ptr(slots), slot_words, table.data_ptr(),
+                                    *_rle_ws(masks.device, lib.hgl_rle_encode_workspace_bytes, S, H, W), _stream()),
           "hgl_rle_encode_device")
     return slots, table
 
@@ -467,7 +524,7 @@ def rle_pack(counts_list, H, W, slot_words=None, device=None):
         k = next(i for i, r in enumerate(rows) if len(r) > slot_words)
         raise ValueError(f"rle_pack: entry {k} has {len(rows[k])} counts, slot_words is {slot_words}")
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    stage = torch.zeros(S * (4 + slot_words), dtype=torch.int32, pin_memory=True)
+    stage = torch.zeros(rle_block_words("set", S, slot_words), dtype=torch.int32, pin_memory=True)
     slots, table = rle_split(stage.numpy(), S, slot_words)
     for i, r in enumerate(rows):
         table[i, 0] = len(r)
@@ -508,15 +565,11 @@ def rle_to_strings(slots, table, cap=None, out=None):
     cap = RLE_STRING_CAP_PER_ENTRY * S if cap is None else int(cap)
     if cap < 0:
         raise ValueError(f"rle_to_strings: cap {cap}")
-    if out is None:
-        out = torch.empty(rle_strings_bytes(S, cap), dtype=torch.uint8, device=slots.device)
-    elif out.numel() != rle_strings_bytes(S, cap):
-        raise ValueError(f"out: expected {rle_strings_bytes(S, cap)} uint8 elements, got {out.numel()}")
-    base = _dev(out, torch.uint8, "out")
-    if base % 8:
+    out = _out(out, rle_strings_bytes(S, cap), torch.uint8, slots.device, "out")
+    if out.data_ptr() % 8:
         raise ValueError("out: the buffer must be 8-byte aligned (it begins with the int64 offsets)")
     data, offsets, status = rle_strings_split(out, S, cap)
-    check(lib.hgl_rle_to_strings_device(sp, sw, tp, S, base + 8 * (S + 1) + 4 * S, cap, base, base + 8 * (S + 1), _stream()),
+    check(lib.hgl_rle_to_strings_device(sp, sw, tp, S, data.data_ptr(), cap, offsets.data_ptr(), status.data_ptr(), _stream()),
           "hgl_rle_to_strings_device")
     return data, offsets, status
 
@@ -565,21 +618,12 @@ def rle_from_strings(data, offsets, S, slot_words, out=None, status=None):
     S, slot_words = int(S), int(slot_words)
     if offsets.numel() != S + 1:
         raise ValueError(f"rle_from_strings: {S} entries need {S + 1} offsets, got {offsets.numel()}")
-    if out is None:
-        out = torch.empty(S * (4 + slot_words), dtype=torch.int32, device=data.device)
-    elif out.numel() != S * (4 + slot_words):
-        raise ValueError(f"out: expected {S * (4 + slot_words)} int32 elements, got {out.numel()}")
-    slots, table = rle_split(out, S, slot_words)
-    if status is None:
-        status = torch.empty((S, 4), dtype=torch.int32, device=data.device)
-    elif tuple(status.shape) != (S, 4):
-        raise ValueError(f"status: expected an int32 tensor [{S}, 4], got {tuple(status.shape)}")
+    slots, table = rle_split(_out(out, rle_block_words("set", S, slot_words), torch.int32, data.device, "out"), S, slot_words)
+    status = _out(status, 4 * S, torch.int32, data.device, "status").view(S, 4)
     if S == 0:
         return slots, table, status
-    base = _dev(out, torch.int32, "out")
-    _dev(status, torch.int32, "status")
     check(lib.hgl_rle_from_strings_device(_dev(data, torch.uint8, "data") if data.numel() else None, int(data.numel()),
-                                          _dev(offsets, torch.int64, "offsets"), S, base + 16 * S, slot_words, base,
+                                          _dev(offsets, torch.int64, "offsets"), S, _ptr(slots), slot_words, table.data_ptr(),
                                           status.data_ptr(), _stream()), "hgl_rle_from_strings_device")
     return slots, table, status
 
@@ -600,18 +644,12 @@ def rle_decode(slots, table, H, W, out=None):
     lib = _lib.load()
     H, W = int(H), int(W)
     sp, sw, tp, S = _rle_set(slots, table, "rle_decode")
-    if out is None:
-        out = torch.empty(S * H * W, dtype=torch.uint8, device=slots.device)
-    elif out.numel() != S * H * W:
-        raise ValueError(f"out: expected {S * H * W} uint8 elements, got {out.numel()}")
+    masks = _out(out, S * H * W, torch.uint8, slots.device, "out").view(S, H, W)
     status = torch.empty((S, 4), dtype=torch.int32, device=slots.device)
-    masks = out.view(S, H, W)
     if S == 0:
         return masks, status
-    op = _dev(out, torch.uint8, "out")
-    need = lib.hgl_rle_decode_workspace_bytes(S, H, W, sw)
-    ws = workspace(need, slots.device, "rle")
-    check(lib.hgl_rle_decode_device(sp, sw, tp, S, H, W, op, status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+    check(lib.hgl_rle_decode_device(sp, sw, tp, S, H, W, masks.data_ptr(), status.data_ptr(),
+                                    *_rle_ws(slots.device, lib.hgl_rle_decode_workspace_bytes, S, H, W, sw), _stream()),
           "hgl_rle_decode_device")
     return masks, status
 
@@ -641,6 +679,22 @@ def _rle_rows(name, sizes, counts_a, counts_b=None, tail=None, running=False):
     return np.array(flat, dtype=np.int64).reshape(G, 3 + two + (tail is not None)), off
 
 
+def _rle_group(name, sets, layout, sizes, *counts, **limits):
+    """The one check of the RLE group calls.  sets: per list of counts its (slots, table), or a number of entries where there
+    is no set (yet); layout: the call's rle_*_layout function, whose _rle_rows refuses lengths that differ and a negative
+    count.  Returns (per set: slots pointer, slot_words, table pointer, S), the image rows, the total behind them (0 where
+    the layout has none), G.  ValueError for counts that do not sum to their set's entries."""
+    two = sum(isinstance(s, tuple) for s in sets) == 2
+    sets = [_rle_set(*s, name + " " + "ab"[k] if two else name) if isinstance(s, tuple) else (None, 0, None, int(s))
+            for k, s in enumerate(sets)]
+    rows = layout(sizes, *counts, **limits)
+    images, total = rows if isinstance(rows, tuple) else (rows, 0)
+    for (_, _, _, S), c in zip(sets, counts):
+        if int(sum(int(n) for n in c)) != S:
+            raise ValueError(f"{name}: counts sum to {sum(c)}, the set has {S} entries")
+    return sets, images, total, len(images)
+
+
 def rle_group_layout(sizes, counts):
     """(images [G,4] int64 = H, W, first entry, byte offset; total bytes) of a group decoded back to back: image g's
     counts[g] masks of sizes[g] = (H, W) follow those of image g-1 with no padding"""
@@ -657,30 +711,16 @@ def rle_decode_group(slots, table, sizes, counts, out=None, aux=None):
     ONE int32 buffer [2,S,4] (`aux`: such a contiguous device tensor to use for it), so a caller that wants both on the host
     copies one tensor.  The number of launches depends neither on G nor on the sizes."""
     lib = _lib.load()
-    sp, sw, tp, S = _rle_set(slots, table, "rle_decode_group")
-    images, total = rle_group_layout(sizes, counts)
-    G = len(images)
-    if int(sum(int(n) for n in counts)) != S:
-        raise ValueError(f"rle_decode_group: counts sum to {sum(counts)}, the set has {S} entries")
-    if out is None:
-        out = torch.empty(total, dtype=torch.uint8, device=slots.device)
-    elif out.numel() != total:
-        raise ValueError(f"out: expected {total} uint8 elements, got {out.numel()}")
-    if aux is None:
-        aux = torch.empty((2, S, 4), dtype=torch.int32, device=slots.device)
-    elif tuple(aux.shape) != (2, S, 4) or aux.dtype != torch.int32 or not aux.is_contiguous():
-        raise ValueError(f"aux: expected a contiguous int32 tensor [2, {S}, 4], got {tuple(aux.shape)} {aux.dtype}")
-    boxes, status = aux[0], aux[1]
-    flat = out.view(-1)
+    ((sp, sw, tp, S),), images, total, G = _rle_group("rle_decode_group", [(slots, table)], rle_group_layout, sizes, counts)
+    flat = _out(out, total, torch.uint8, slots.device, "out")
+    boxes, status = rle_block("aux", _out(aux, rle_block_words("aux", S), torch.int32, slots.device, "aux"), S)
     masks = [flat[int(o):int(o) + int(n) * int(H) * int(W)].view(int(n), int(H), int(W))
              for (H, W, _, o), n in zip(images, counts)]
     if S == 0:
         return masks, boxes, status
-    op = _dev(out, torch.uint8, "out")
-    need = lib.hgl_rle_decode_group_workspace_bytes(S, sw)
-    ws = workspace(need, slots.device, "rle")
-    check(lib.hgl_rle_decode_group_device(sp, sw, tp, S, images.ctypes.data, G, op, total, boxes.data_ptr(), status.data_ptr(),
-                                          ws.data_ptr(), ws.numel(), _stream()), "hgl_rle_decode_group_device")
+    check(lib.hgl_rle_decode_group_device(sp, sw, tp, S, images.ctypes.data, G, flat.data_ptr(), total, boxes.data_ptr(), status.data_ptr(),
+                                          *_rle_ws(slots.device, lib.hgl_rle_decode_group_workspace_bytes, S, sw), _stream()),
+          "hgl_rle_decode_group_device")
     return masks, boxes, status
 
 
@@ -696,9 +736,8 @@ def rle_iou(slots_a, table_a, slots_b, table_b, H, W):
     iu = torch.empty((S, 2), dtype=torch.int64, device=slots_a.device)
     if S == 0:
         return iu
-    need = lib.hgl_rle_iou_workspace_bytes(S, H, W, asw, bsw)
-    ws = workspace(need, slots_a.device, "rle")
-    check(lib.hgl_rle_iou_device(ap, asw, atp, bp, bsw, btp, S, H, W, iu.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+    check(lib.hgl_rle_iou_device(ap, asw, atp, bp, bsw, btp, S, H, W, iu.data_ptr(),
+                                 *_rle_ws(slots_a.device, lib.hgl_rle_iou_workspace_bytes, S, H, W, asw, bsw), _stream()),
           "hgl_rle_iou_device")
     return iu
 
@@ -719,32 +758,26 @@ def rle_match(slots_a, table_a, slots_b, table_b, sizes, counts_a, counts_b, cro
     and the union elsewhere, compared exactly, the lowest index on a tie, -1 when nothing intersects (include/hybridgl.h).
     crowd_b: bool / uint8 device tensor [Sb] or None.  No mask becomes pixels."""
     lib = _lib.load()
-    ap, asw, atp, Sa = _rle_set(slots_a, table_a, "rle_match a")
-    bp, bsw, btp, Sb = _rle_set(slots_b, table_b, "rle_match b")
+    ((ap, asw, atp, Sa), (bp, bsw, btp, Sb)), images, total, G = _rle_group(
+        "rle_match", [(slots_a, table_a), (slots_b, table_b)], rle_match_layout, sizes, counts_a, counts_b)
     if slots_a.device != slots_b.device:
         raise ValueError("rle_match: the two sets live on different devices")
-    images, total = rle_match_layout(sizes, counts_a, counts_b)
-    G = len(images)
-    if int(sum(int(n) for n in counts_a)) != Sa or int(sum(int(n) for n in counts_b)) != Sb:
-        raise ValueError(f"rle_match: counts sum to {sum(counts_a)} and {sum(counts_b)}, the sets have {Sa} and {Sb} entries")
     dev = slots_a.device
     cp = None
     if crowd_b is not None:
         if crowd_b.numel() != Sb:
             raise ValueError(f"crowd_b: expected {Sb} flags, got {crowd_b.numel()}")
         cp, crowd_b = _u8(crowd_b, "crowd_b")
-    match = torch.empty((Sa + Sb, 4), dtype=torch.int32, device=dev)
-    match_a, match_b = match[:Sa], match[Sa:]
+    match_a, match_b = rle_block("match", torch.empty(rle_block_words("match", Sa, Sb=Sb), dtype=torch.int32, device=dev), Sa, Sb=Sb)
     flat = torch.empty(total, dtype=torch.int32, device=dev) if matrix else None
     inter = [flat[int(o):int(o) + int(na) * int(nb)].view(int(na), int(nb))
              for (_, _, _, _, o), na, nb in zip(images, counts_a, counts_b)] if matrix else None
     if Sa + Sb == 0:
         return inter, match_a, match_b
-    need = lib.hgl_rle_match_workspace_bytes(images.ctypes.data, G, Sa, asw, Sb, bsw, int(matrix))
-    ws = workspace(need, dev, "rle")
     check(lib.hgl_rle_match_device(ap, asw, atp, Sa, bp, bsw, btp, Sb, images.ctypes.data, G, cp,
                                    flat.data_ptr() if matrix else None, total, match_a.data_ptr(), match_b.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), _stream()), "hgl_rle_match_device")
+                                   *_rle_ws(dev, lib.hgl_rle_match_workspace_bytes, images.ctypes.data, G, Sa, asw, Sb, bsw, int(matrix)),
+                                   _stream()), "hgl_rle_match_device")
     return inter, match_a, match_b
 
 
@@ -752,9 +785,12 @@ NMS_METRIC = {"iou": 0, "containment": 1}
 
 
 def rle_nms_layout(sizes, counts):
-    """images [G,3] int64 = (H, W, first entry) of a mask NMS over G images: image g owns counts[g] consecutive entries of
-    sizes[g] = (H, W)"""
+    """images [G,3] int64 = (H, W, first entry) of a mask NMS, a clean-up or a rasterisation over G images: image g owns
+    counts[g] consecutive entries of sizes[g] = (H, W)"""
     return _rle_rows("rle_nms_layout", sizes, counts)[0]
+
+
+rle_clean_layout = rle_nms_layout
 
 
 def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou", out=None):
@@ -769,16 +805,12 @@ def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou", out
     entry of lowest rank that suppressed it, -1 for a kept one and for code 2).  No mask becomes pixels.  The three are views of
     ONE int32 buffer, out_idx | result | out_n (`out`: a contiguous int32 device tensor of 5 S + G elements to use for it)."""
     lib = _lib.load()
-    sp, sw, tp, S = _rle_set(slots, table, "rle_nms")
     if metric not in NMS_METRIC:
         raise ValueError(f"rle_nms: metric {metric!r} (one of {sorted(NMS_METRIC)})")
     thr = float(thr)
     if thr != thr:
         raise ValueError("rle_nms: the threshold is NaN")
-    images = rle_nms_layout(sizes, counts)
-    G = len(images)
-    if int(sum(int(n) for n in counts)) != S:
-        raise ValueError(f"rle_nms: counts sum to {sum(counts)}, the set has {S} entries")
+    ((sp, sw, tp, S),), images, _, G = _rle_group("rle_nms", [(slots, table)], rle_nms_layout, sizes, counts)
     dev = slots.device
     cp = None
     if scores is not None:
@@ -786,18 +818,14 @@ def rle_nms(slots, table, sizes, counts, scores=None, thr=0.7, metric="iou", out
             raise ValueError(f"scores: expected {S} values, got {scores.numel()}")
         scores = scores.reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
         cp = _dev(scores, torch.float32, "scores")
-    if out is None:
-        out = torch.empty(S * 5 + G, dtype=torch.int32, device=dev)      # one buffer: a caller that wants all three copies one tensor
-    elif out.numel() != S * 5 + G or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"out: expected a contiguous int32 tensor of {S * 5 + G} elements on {dev}, got {tuple(out.shape)} {out.dtype}")
-    out_idx, result, out_n = out[:S], out[S:5 * S].view(S, 4), out[5 * S:]
+    # one buffer: a caller that wants all three copies one tensor
+    out_idx, result, out_n = rle_block("nms", _out(out, rle_block_words("nms", S, G=G), torch.int32, dev, "out"), S, G=G)
     if S == 0:
         out_n.zero_()
         return out_idx, out_n, result
-    need = lib.hgl_rle_nms_workspace_bytes(images.ctypes.data, G, S, sw)
-    ws = workspace(need, dev, "rle")
     check(lib.hgl_rle_nms_device(sp, sw, tp, S, images.ctypes.data, G, cp, thr, NMS_METRIC[metric], out_idx.data_ptr(),
-                                 out_n.data_ptr(), result.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "hgl_rle_nms_device")
+                                 out_n.data_ptr(), result.data_ptr(),
+                                 *_rle_ws(dev, lib.hgl_rle_nms_workspace_bytes, images.ctypes.data, G, S, sw), _stream()), "hgl_rle_nms_device")
     return out_idx, out_n, result
 
 
@@ -828,11 +856,7 @@ def rle_select(slots, table, sizes, counts, keep=None, nms_result=None, cols=Non
     | cols (`out`: a contiguous int32 device tensor of S * (4 + slot_words + C) elements to use for it), the last two of another,
     out_src | out_n (`back`: S + G elements)."""
     lib = _lib.load()
-    sp, sw, tp, S = _rle_set(slots, table, "rle_select")
-    images = rle_select_layout(sizes, counts, max_keep)
-    G = len(images)
-    if int(sum(int(n) for n in counts)) != S:
-        raise ValueError(f"rle_select: counts sum to {sum(counts)}, the set has {S} entries")
+    ((sp, sw, tp, S),), images, _, G = _rle_group("rle_select", [(slots, table)], rle_select_layout, sizes, counts, max_keep=max_keep)
     if (keep is None) == (nms_result is None):
         raise ValueError("rle_select: exactly one of keep and nms_result selects the entries")
     dev = slots.device
@@ -852,35 +876,19 @@ def rle_select(slots, table, sizes, counts, keep=None, nms_result=None, cols=Non
         C, cdtype = int(cols.shape[0]), cols.dtype
         if C:
             cp = _dev(cols, cdtype, "cols")
-
-    def take(buf, numel, name):
-        if buf is None:
-            return torch.empty(numel, dtype=torch.int32, device=dev)
-        if buf.numel() != numel or buf.dtype != torch.int32 or not buf.is_contiguous() or buf.device != dev:
-            raise ValueError(f"{name}: expected a contiguous int32 tensor of {numel} elements on {dev}, got {tuple(buf.shape)} {buf.dtype}")
-        return buf.view(-1)
-
-    out = take(out, S * (4 + sw + C), "out")
-    back = take(back, S + G, "back")
-    out_slots, out_table = rle_split(out, S, sw)
-    out_cols = out[S * (4 + sw):].view(C, S).view(cdtype)
-    out_src, out_n = back[:S], back[S:]
+    out_table, out_slots, out_cols = rle_block("select", _out(out, rle_block_words("select", S, sw, C=C), torch.int32, dev, "out"), S, sw, C=C)
+    out_src, out_n = rle_block("back", _out(back, rle_block_words("back", S, G=G), torch.int32, dev, "back"), S, G=G)
+    out_cols = out_cols.view(cdtype)
     if S == 0:      # the entry launches nothing and leaves out_n alone
         out_n.zero_()
         return out_slots, out_table, out_cols, out_src, out_n
-    base = out.data_ptr()
-    check(lib.hgl_rle_select_device(sp, sw, tp, S, images.ctypes.data, G, kp, rp, cp, C, base + 16 * S, base, base + 4 * S * (4 + sw) if C else None,
-                                    out_src.data_ptr(), out_n.data_ptr(), _stream()), "hgl_rle_select_device")
+    check(lib.hgl_rle_select_device(sp, sw, tp, S, images.ctypes.data, G, kp, rp, cp, C, _ptr(out_slots), out_table.data_ptr(),
+                                    out_cols.data_ptr() if C else None, out_src.data_ptr(), out_n.data_ptr(), _stream()),
+          "hgl_rle_select_device")
     return out_slots, out_table, out_cols, out_src, out_n
 
 
 CLEAN_MODES = {"holes": 1, "islands": 2, "both": 3}
-
-
-def rle_clean_layout(sizes, counts):
-    """images [G,3] int64 = (H, W, first entry) of a clean-up over G images: image g owns counts[g] consecutive entries of
-    sizes[g] = (H, W)"""
-    return _rle_rows("rle_clean_layout", sizes, counts)[0]
 
 
 def rle_remove_small_regions(slots, table, sizes, counts, area_thresh, mode="both", seg_cap=None, slot_words=None, out=None):
@@ -899,31 +907,19 @@ def rle_remove_small_regions(slots, table, sizes, counts, area_thresh, mode="bot
     (no mask in the slot) and 3 (over seg_cap): table row (0, 3, 0, 0), slot untouched, box zeros.  The four are views of ONE
     int32 buffer, table | slots | boxes | result (`out`: a contiguous int32 device tensor of S * (12 + slot_words) elements)."""
     lib = _lib.load()
-    sp, sw, tp, S = _rle_set(slots, table, "rle_remove_small_regions")
     if mode not in CLEAN_MODES:
         raise ValueError(f"rle_remove_small_regions: mode {mode!r} (one of {sorted(CLEAN_MODES)})")
-    images = rle_clean_layout(sizes, counts)
-    G = len(images)
-    if int(sum(int(n) for n in counts)) != S:
-        raise ValueError(f"rle_remove_small_regions: counts sum to {sum(counts)}, the set has {S} entries")
+    ((sp, sw, tp, S),), images, _, G = _rle_group("rle_remove_small_regions", [(slots, table)], rle_clean_layout, sizes, counts)
     osw = sw if slot_words is None else int(slot_words)
     if seg_cap is None:
         seg_cap = max([int(W) * ((int(H) + 1) // 2) + int(W) for H, W in sizes], default=1)
     dev = slots.device
-    if out is None:
-        out = torch.empty(S * (12 + osw), dtype=torch.int32, device=dev)
-    elif out.numel() != S * (12 + osw) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"out: expected a contiguous int32 tensor of {S * (12 + osw)} elements on {dev}, got {tuple(out.shape)} {out.dtype}")
-    out = out.view(-1)
-    out_slots, out_table = rle_split(out, S, osw)
-    boxes, result = out[S * (4 + osw):S * (8 + osw)].view(S, 4), out[S * (8 + osw):].view(S, 4)
+    out_table, out_slots, boxes, result = rle_block("clean", _out(out, rle_block_words("clean", S, osw), torch.int32, dev, "out"), S, osw)
     if S == 0:
         return out_slots, out_table, boxes, result
-    need = lib.hgl_rle_clean_workspace_bytes(images.ctypes.data, G, S, sw, int(seg_cap))
-    ws = workspace(need, dev, "rle")
-    base = out.data_ptr()
-    check(lib.hgl_rle_clean_device(sp, sw, tp, S, images.ctypes.data, G, int(area_thresh), CLEAN_MODES[mode], int(seg_cap), base + 16 * S, osw,
-                                   base, base + 4 * S * (4 + osw), base + 4 * S * (8 + osw), ws.data_ptr(), ws.numel(), _stream()),
+    check(lib.hgl_rle_clean_device(sp, sw, tp, S, images.ctypes.data, G, int(area_thresh), CLEAN_MODES[mode], int(seg_cap),
+                                   _ptr(out_slots), osw, out_table.data_ptr(), boxes.data_ptr(), result.data_ptr(),
+                                   *_rle_ws(dev, lib.hgl_rle_clean_workspace_bytes, images.ctypes.data, G, S, sw, int(seg_cap)), _stream()),
           "hgl_rle_clean_device")
     return out_slots, out_table, boxes, result
 
@@ -947,11 +943,7 @@ def rle_from_polygons(entries, sizes, counts, rule="once", slot_words=None, devi
     lib = _lib.load()
     if rule not in POLY_RULE:
         raise ValueError(f"rle_from_polygons: rule {rule!r} (one of {sorted(POLY_RULE)})")
-    if len(sizes) != len(counts):
-        raise ValueError(f"rle_from_polygons: {len(sizes)} sizes and {len(counts)} counts")
-    S, G = len(entries), len(sizes)
-    if any(int(n) < 0 for n in counts) or int(sum(int(n) for n in counts)) != S:
-        raise ValueError(f"rle_from_polygons: counts sum to {sum(counts)}, there are {S} entries")
+    ((_, _, _, S),), images, _, G = _rle_group("rle_from_polygons", [len(entries)], rle_nms_layout, sizes, counts)
     polys, entry_polys = [], [0]
     for e, entry in enumerate(entries):
         for k, poly in enumerate(entry):
@@ -963,20 +955,14 @@ def rle_from_polygons(entries, sizes, counts, rule="once", slot_words=None, devi
             polys.append(xy)
         entry_polys.append(len(polys))
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    images = np.zeros((max(G, 1), 3), dtype=np.int64)
-    first = 0
-    for g, ((H, W), n) in enumerate(zip(sizes, counts)):
-        images[g] = (int(H), int(W), first)
-        first += int(n)
+    if device.type != "cuda":
+        raise _lib.HybridGLError(f"rle_from_polygons: device {device} (no CPU path exists)")
+    if device.index is None:      # "cuda" is the current device: a lent `out` states the one it is on
+        device = torch.device("cuda", torch.cuda.current_device())
     if slot_words is None:
         slot_words = max([rle_slot_words(H, W) for H, W in sizes], default=1)
     slot_words = int(slot_words)
-    if out is None:
-        out = torch.empty(S * (8 + slot_words), dtype=torch.int32, device=device)
-    elif out.numel() != S * (8 + slot_words):
-        raise ValueError(f"out: expected {S * (8 + slot_words)} int32 elements, got {out.numel()}")
-    slots, table = rle_split(out, S, slot_words)
-    status = out[S * (4 + slot_words):].reshape(S, 4)
+    table, slots, status = rle_block("status", _out(out, rle_block_words("status", S, slot_words), torch.int32, device, "out"), S, slot_words)
     if S == 0:
         return slots, table, status
     P, n_xy = len(polys), int(sum(len(p) for p in polys))
@@ -990,12 +976,10 @@ def rle_from_polygons(entries, sizes, counts, rule="once", slot_words=None, devi
     off[P + 1:] = entry_polys
     buf = stage.to(device, non_blocking=True)
     xy_p = buf.data_ptr()
-    need = lib.hgl_rle_from_polygons_workspace_bytes(images.ctypes.data, G, S, P)
-    ws = workspace(need, device, "rle")
-    base = _dev(out, torch.int32, "out")
     check(lib.hgl_rle_from_polygons_device(xy_p, xy_p + 8 * n_xy, P, xy_p + 8 * n_xy + 4 * (P + 1), S, images.ctypes.data, G,
-                                           POLY_RULE[rule], base + 16 * S, slot_words, base, status.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), _stream()), "hgl_rle_from_polygons_device")
+                                           POLY_RULE[rule], _ptr(slots), slot_words, table.data_ptr(), status.data_ptr(),
+                                           *_rle_ws(device, lib.hgl_rle_from_polygons_workspace_bytes, images.ctypes.data, G, S, P),
+                                           _stream()), "hgl_rle_from_polygons_device")
     return slots, table, status
 
 
@@ -1040,13 +1024,9 @@ def rle_merge(slots, table, sizes, counts_src, members, member_offsets, bounds, 
     S * (8 + slot_words) elements to use for it).  No mask becomes pixels."""
     import numpy as np
     lib = _lib.load()
-    sp, sw, tp, Ssrc = _rle_set(slots, table, "rle_merge")
+    ((sp, sw, tp, Ssrc), (_, _, _, S)), images, _, G = _rle_group(
+        "rle_merge", [(slots, table), sum(int(n) for n in counts_out)], rle_merge_layout, sizes, counts_src, counts_out)
     dev = slots.device
-    images = rle_merge_layout(sizes, counts_src, counts_out)
-    G = len(images)
-    if int(sum(int(n) for n in counts_src)) != Ssrc:
-        raise ValueError(f"rle_merge: counts_src sum to {sum(counts_src)}, the set has {Ssrc} entries")
-    S = int(sum(int(n) for n in counts_out))
     if member_offsets is None:
         lists = [np.asarray(m, dtype=np.int64).reshape(-1) for m in members]
         member_offsets = np.concatenate([[0], np.cumsum([len(m) for m in lists], dtype=np.int64)])
@@ -1071,20 +1051,13 @@ def rle_merge(slots, table, sizes, counts_src, members, member_offsets, bounds, 
     if slot_words is None:
         slot_words = max([rle_slot_words(H, W) for H, W in sizes], default=1)
     slot_words = int(slot_words)
-    if out is None:
-        out = torch.empty(S * (8 + slot_words), dtype=torch.int32, device=dev)
-    elif out.numel() != S * (8 + slot_words):
-        raise ValueError(f"out: expected {S * (8 + slot_words)} int32 elements, got {out.numel()}")
-    oslots, otable = rle_split(out, S, slot_words)
-    status = out[S * (4 + slot_words):].reshape(S, 4)
+    otable, oslots, status = rle_block("status", _out(out, rle_block_words("status", S, slot_words), torch.int32, dev, "out"), S, slot_words)
     if S == 0:
         return oslots, otable, status
-    need = lib.hgl_rle_merge_workspace_bytes(images.ctypes.data, G, Ssrc, sw, S, M)
-    ws = workspace(need, dev, "rle")
-    base = _dev(out, torch.int32, "out")
     check(lib.hgl_rle_merge_device(sp if Ssrc else None, sw, tp if Ssrc else None, Ssrc, images.ctypes.data, G,
                                    members.data_ptr() if M else None, M, member_offsets.data_ptr(), bounds.data_ptr(),
-                                   base + 16 * S, slot_words, base, S, status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                                   _ptr(oslots), slot_words, otable.data_ptr(), S, status.data_ptr(),
+                                   *_rle_ws(dev, lib.hgl_rle_merge_workspace_bytes, images.ctypes.data, G, Ssrc, sw, S, M), _stream()),
           "hgl_rle_merge_device")
     return oslots, otable, status
 

@@ -305,7 +305,7 @@ class HybridGLPipeline:
         copy of table and slots into a pinned buffer, both on the current stream; nothing here waits for the device."""
         _, H, W = masks.shape
         sw = ops.rle_slot_words(H, W)
-        flat = torch.empty(2 * n * (4 + sw), dtype=torch.int32, device=masks.device)
+        flat = torch.empty(ops.rle_block_words("set", 2 * n, sw), dtype=torch.int32, device=masks.device)
         ops.rle_encode(masks, idx.reshape(-1), sw, out=flat)
         self._harvest_predictions()
         host = self._pred_free.take(flat.numel(), torch.int32)

@@ -206,7 +206,7 @@ class ProposalRecorder:
             self._pending.put(None, (image_id, H, W, 0, 0, None, None, None))      # no copy to wait for: written in its turn
             return
         sw = ops.rle_slot_words(H, W)
-        flat = torch.empty(n * (4 + sw), dtype=torch.int32, device=masks.device)
+        flat = torch.empty(ops.rle_block_words("set", n, sw), dtype=torch.int32, device=masks.device)
         ops.rle_encode(masks if masks.is_contiguous() else masks.contiguous(), None, sw, out=flat)
         # the few scalars per proposal ride along: rows iou, stability, source, x, y, w, h (all exact in float64)
         sc = [iou.double()[None], stab.double()[None], src.double()[None], xywh.double().t()]
@@ -280,17 +280,17 @@ class _Stored:
     __slots__ = ("ids", "sizes", "counts", "first", "rows", "masks", "boxes", "iou", "stab", "host", "ev", "overflow")
 
 
-def _split_group(flat, S, sw):
-    """(slots [S,sw], table [S,4], cols [2,S] = the bits of predicted_iou | of stability_score, area bits [S] or nothing) as
-    views of a flat int32 buffer that holds S entries in the layout of _Rows.buf -- an image's rows, a staged group or its
-    upload: numpy array and tensor alike"""
-    slots, table = ops.rle_split(flat, S, sw)
-    return slots, table, flat[S * (4 + sw):S * (6 + sw)].reshape(2, S), flat[S * (6 + sw):S * (7 + sw)]
+def _split_group(flat, S, sw, area):
+    """(slots [S,sw], table [S,4], cols [2,S] = the bits of predicted_iou | of stability_score, area bits [S] or, without
+    `area`, nothing) as views of a flat int32 buffer that holds S entries in the layout of _Rows.buf (ops.RLE_BLOCKS "group") --
+    an image's rows, a staged group or its upload: numpy array and tensor alike"""
+    table, slots, cols, extra = ops.rle_block("group", flat, S, sw, C=int(bool(area)))
+    return slots, table, cols, extra
 
 
 def _group_words(S, sw, area):
     """the int32 words of that layout"""
-    return S * (6 + sw + bool(area))
+    return ops.rle_block_words("group", S, sw, C=int(bool(area)))
 
 
 def _stage_group(rows, counts, area, buf):
@@ -303,7 +303,7 @@ def _stage_group(rows, counts, area, buf):
     if S == 0:
         return 0, 0, first
     sw = max(r.sw for r, n in zip(rows, counts) if n)
-    slots, table, cols, extra = _split_group(buf, S, sw)
+    slots, table, cols, extra = _split_group(buf, S, sw, area)
     for r, n, e in zip(rows, counts, first):
         if n:
             table[e:e + n] = r.table[:n]
@@ -320,10 +320,13 @@ def _back_layout(S, G, thin, device_strings):
     aux: boxes | status [2,S,4].  Thinning only: out_src [S] and out_n [G] of ops.rle_select; nms: the output block of ops.rle_nms
     = out_idx [S] | result [S,4] | out_n [G], and codes: the result rows inside it.  Reading strings on the device only: read, the
     codec's status [S,4].  The parts lie in this order without a gap; a part the mode does not have is empty."""
-    t = int(bool(thin))
-    e = np.cumsum([0, 8 * S, t * S, t * G, t * S, 4 * t * S, t * G, 4 * S * bool(device_strings)]).tolist()
-    return e[7], {"aux": slice(e[0], e[1]), "out_src": slice(e[1], e[2]), "out_n": slice(e[2], e[3]), "nms": slice(e[3], e[6]),
-                  "codes": slice(e[4], e[5]), "read": slice(e[6], e[7])}
+    t = int(bool(thin))      # without thinning the blocks of ops.rle_select and ops.rle_nms are those of no entry in no image
+    aux = ops.rle_block_words("aux", S)
+    src, n = (aux + v for v in ops.rle_block_ends("back", t * S, G=t * G))
+    idx, res, nms = (n + v for v in ops.rle_block_ends("nms", t * S, G=t * G))
+    end = nms + 4 * S * bool(device_strings)
+    return end, {"aux": slice(0, aux), "out_src": slice(aux, src), "out_n": slice(src, n), "nms": slice(n, nms),
+                 "codes": slice(idx, res), "read": slice(nms, end)}
 
 
 def _undecoded(store, image_id, entry, code, what="mask of the stated size"):
@@ -424,7 +427,7 @@ class StoredProposals:
         _, counts = _record_runs(self.store, image_id, recs, (rows.H, rows.W))
         rows.sw = max([len(c) for c in counts] + [1])
         rows.buf = torch.zeros(_group_words(n, rows.sw, by_area), dtype=torch.int32, pin_memory=torch.cuda.is_available())
-        rows.slots, rows.table, (rows.iou, rows.stab), rows.area = _split_group(rows.buf.numpy(), n, rows.sw)
+        rows.slots, rows.table, (rows.iou, rows.stab), rows.area = _split_group(rows.buf.numpy(), n, rows.sw, by_area)
         for k, c in enumerate(counts):
             rows.table[k, 0] = len(c)
             rows.slots[k, :len(c)] = np.asarray(c, dtype=np.uint32).view(np.int32)
@@ -536,7 +539,7 @@ class StoredProposals:
             S, sw, st.first = _stage_group(st.rows, st.counts, by_area, host.numpy())
             if S == 0:
                 return st
-            slots, table, cols, area = _split_group(self._upload(host, _group_words(S, sw, by_area)), S, sw)
+            slots, table, cols, area = _split_group(self._upload(host, _group_words(S, sw, by_area)), S, sw, by_area)
         # ONE int32 buffer leaves in one copy into pooled pinned memory: boxes | status and, thinning, | out_src | out_n | the
         # NMS's out_idx, result, out_n (| the string codec's status, reading strings on the device); group_cleanup reads it,
         # where SAM reads its first counts, and hands the buffer back
@@ -957,10 +960,10 @@ def clean(src, dst, min_area, nms_thresh=0.7, group=16, device=None):
         dev, sw = slots.device, int(slots.shape[1])
         # an output slot of the plane's size loses no mask: runs where they fit, the bit plane otherwise; rle_from_slot reads either
         osw = max([sw] + [ops.rle_slot_words(H, W) for (H, W), n in zip(sizes, counts) if n])
-        flat = torch.empty(S * (12 + osw), dtype=torch.int32, device=dev)
+        flat = torch.empty(ops.rle_block_words("clean", S, osw), dtype=torch.int32, device=dev)
         _, _, boxes, result = ops.rle_remove_small_regions(slots, table, sizes, counts, min_area, "both",
                                                            seg_cap=sw // 2 + max(W for _, W in sizes) + 1, slot_words=osw, out=flat)
-        boxes = boxes.clone()      # a buffer of its own: the NMS wants its boxes 16-byte aligned, the view lies where S * (4 + osw) words end
+        boxes = boxes.clone()      # a buffer of its own: the NMS wants its boxes 16-byte aligned, the view lies where table and slots end
         scores = (result[:, 2] == 0).to(torch.float32)
         keep = torch.ones(S, dtype=torch.uint8, device=dev)
         if max(counts) <= 1024:
@@ -974,9 +977,7 @@ def clean(src, dst, min_area, nms_thresh=0.7, group=16, device=None):
                     o, nn = sam.nms(boxes[e:e + c].contiguous(), scores[e:e + c].contiguous(), keep[e:e + c].contiguous(), nms_thresh)
                     order[e:e + c], n[k] = o.cpu().numpy(), int(nn.cpu()[0])
                 e += c
-        host = flat.cpu().numpy()
-        h_slots, h_table = ops.rle_split(host, S, osw)
-        h_boxes, h_result = host[S * (4 + osw):].reshape(2, S, 4)
+        h_table, h_slots, h_boxes, h_result = ops.rle_block("clean", flat.cpu().numpy(), S, osw)
         check(h_result)
         out, e = [], 0
         for k, ((_, recs), (size, _), c) in enumerate(zip(chunk, sized, counts)):

@@ -1313,7 +1313,7 @@ def _masks_to_rle(masks, sel=None):
     if not masks.is_contiguous():
         masks = masks.contiguous()
     sw = ops.rle_slot_words(H, W)
-    flat = torch.empty(S * (4 + sw), dtype=torch.int32, device=masks.device)
+    flat = torch.empty(ops.rle_block_words("set", S, sw), dtype=torch.int32, device=masks.device)
     ops.rle_encode(masks, sel, sw, out=flat)
     slots, table = ops.rle_split(flat.cpu().numpy(), S, sw)      # the one device -> host copy
     return [{"size": [H, W], "counts": c.tolist()} for c in counts_from_set(slots, table, H, W)], [int(a) for a in table[:, 2]]
@@ -1544,14 +1544,10 @@ def remove_small_regions_rles(rles, area_thresh, mode):
     n = len(rles)
     counts = [rle_counts(r) for r in rles]
     slots, table = ops.rle_pack(counts, h, w)
-    sw = int(slots.shape[1])
-    flat = torch.empty(n * (12 + ops.rle_slot_words(h, w)), dtype=torch.int32, device=slots.device)
-    ops.rle_remove_small_regions(slots, table, [(h, w)], [n], area_thresh, mode, seg_cap=sw // 2 + w + 1,
-                                 slot_words=ops.rle_slot_words(h, w), out=flat)
-    osw = ops.rle_slot_words(h, w)
-    host = flat.cpu().numpy()      # the one device -> host copy
-    s, t = ops.rle_split(host, n, osw)
-    result = host[n * (8 + osw):].reshape(n, 4)
+    sw, osw = int(slots.shape[1]), ops.rle_slot_words(h, w)
+    flat = torch.empty(ops.rle_block_words("clean", n, osw), dtype=torch.int32, device=slots.device)
+    ops.rle_remove_small_regions(slots, table, [(h, w)], [n], area_thresh, mode, seg_cap=sw // 2 + w + 1, slot_words=osw, out=flat)
+    t, s, _, result = ops.rle_block("clean", flat.cpu().numpy(), n, osw)      # the one device -> host copy
     bad = np.flatnonzero(result[:, 0] != 0)
     if len(bad):
         raise ValueError(f"remove_small_regions_rles: entry {int(bad[0])} does not decode to a {h} x {w} mask (status {int(result[bad[0], 0])})")

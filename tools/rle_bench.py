@@ -123,7 +123,7 @@ def kernel_leg(masks, reps):
     rec = {}
     for name, sel in (("all_64", None), ("6_of_64", torch.tensor([5, 17, 17, 40, 63, 2], dtype=torch.int64, device=dev))):
         S = N if sel is None else int(sel.numel())
-        flat = torch.empty(S * (4 + sw), dtype=torch.int32, device=dev)
+        flat = torch.empty(ops.rle_block_words("set", S, sw), dtype=torch.int32, device=dev)
         us = device_us(lambda: ops.rle_encode(masks, sel, sw, out=flat), reps)
         nbytes = S * H * W
         # the yardstick: hgl_iou streams two byte arrays; half of each of `nbytes` bytes in total
@@ -330,8 +330,8 @@ def merge_leg(dev, reps, H=640, W=640):
         offsets = torch.arange(0, S * k + 1, k, dtype=torch.int32, device=dev)
         lo, hi = ops.rle_merge_rule(rule, k)
         bounds = torch.tensor([[lo, hi]] * S, dtype=torch.int32, device=dev)
-        out_m = torch.empty(S * (8 + sw), dtype=torch.int32, device=dev)
-        out_p = torch.empty(S * (4 + sw), dtype=torch.int32, device=dev)
+        out_m = torch.empty(ops.rle_block_words("status", S, sw), dtype=torch.int32, device=dev)
+        out_p = torch.empty(ops.rle_block_words("set", S, sw), dtype=torch.int32, device=dev)
         pix = torch.empty(S * k * H * W, dtype=torch.uint8, device=dev)
 
         def entry():
@@ -451,8 +451,8 @@ def select_leg(dev, reps, H=640, W=640, G=16, thr=0.7):
         sizes, counts = [(H, W)] * G, [n] * G
         slots_h, table_h = slots.cpu().numpy(), table.cpu().numpy()      # the host's copy: it packed the set
         result = ops.rle_nms(slots, table, sizes, counts, scores, thr, "iou")[2]
-        out = torch.empty(S * (4 + sw + 2), dtype=torch.int32, device=dev)
-        back = torch.empty(S + G, dtype=torch.int32, device=dev)
+        out = torch.empty(ops.rle_block_words("select", S, sw, C=2), dtype=torch.int32, device=dev)
+        back = torch.empty(ops.rle_block_words("back", S, G=G), dtype=torch.int32, device=dev)
 
         def select():
             return ops.rle_select(slots, table, sizes, counts, nms_result=result, cols=cols, out=out, back=back)
@@ -525,14 +525,14 @@ def clean_leg(dev, reps, H=640, W=640, S=64, area=100):
     cap = sw // 2 + W + 1
     osw = ops.rle_slot_words(H, W)
     sizes, counts = [(H, W)], [S]
-    out = torch.empty(S * (12 + osw), dtype=torch.int32, device=dev)
+    out = torch.empty(ops.rle_block_words("clean", S, osw), dtype=torch.int32, device=dev)
     run_new = lambda: ops.rle_remove_small_regions(slots, table, sizes, counts, area, "both", seg_cap=cap, slot_words=osw, out=out)
     pix = torch.empty(S * H * W, dtype=torch.uint8, device=dev)
     aux = torch.empty((2, S, 4), dtype=torch.int32, device=dev)
     m1, m2 = torch.empty((S, H, W), dtype=torch.uint8, device=dev), torch.empty((S, H, W), dtype=torch.uint8, device=dev)
     c1, c2 = torch.empty(S, dtype=torch.uint8, device=dev), torch.empty(S, dtype=torch.uint8, device=dev)
     nb = torch.empty((S, 4), dtype=torch.int32, device=dev)
-    enc = torch.empty(S * (4 + osw), dtype=torch.int32, device=dev)
+    enc = torch.empty(ops.rle_block_words("set", S, osw), dtype=torch.int32, device=dev)
 
     def run_pixels():
         masks, _, _ = ops.rle_decode_group(slots, table, sizes, counts, out=pix, aux=aux)
@@ -579,7 +579,7 @@ def strings_leg(dev, reps, S=64, H=640, W=640):
     """the two ends of an encoded set's life, host path against device path (see --strings at the top)"""
     masks = torch.from_numpy(np.ascontiguousarray(synth.synth_masks(S, H, W, 2000))).to(dev).view(torch.uint8)
     sw = ops.rle_slot_words(H, W)
-    flat = torch.empty(S * (4 + sw), dtype=torch.int32, device=dev)
+    flat = torch.empty(ops.rle_block_words("set", S, sw), dtype=torch.int32, device=dev)
     slots, table = ops.rle_encode(masks, None, sw, out=flat)
 
     def out_host():      # what ProposalRecorder and generate() do today: the whole set over the bus, a Python list per mask, ctypes per mask
@@ -613,7 +613,7 @@ def strings_leg(dev, reps, S=64, H=640, W=640):
     cap = ops.RLE_STRING_CAP_PER_ENTRY * S
     sbuf = torch.empty(ops.rle_strings_bytes(S, cap), dtype=torch.uint8, device=dev)
     data, offsets, _ = ops.rle_to_strings(slots, table, cap, out=sbuf)
-    back = torch.empty(S * (4 + int(ds.shape[1])), dtype=torch.int32, device=dev)
+    back = torch.empty(ops.rle_block_words("set", S, int(ds.shape[1])), dtype=torch.int32, device=dev)
     total = int(offsets[S])
     k_out = device_spread(lambda: ops.rle_to_strings(slots, table, cap, out=sbuf), reps)
     k_in = device_spread(lambda: ops.rle_from_strings(data[:total], offsets, S, int(ds.shape[1]), out=back), reps)
@@ -621,7 +621,7 @@ def strings_leg(dev, reps, S=64, H=640, W=640):
                                                                          "max": int(n_counts.max())},
             "string_bytes_per_mask": {"min": min(lengths), "median": float(statistics.median(lengths)), "max": max(lengths)},
             "string_bytes_total": total, "default_cap_bytes": cap, "bytes_per_count": round(total / float(n_counts.sum()), 3),
-            "bus_bytes_host_path_out": 4 * S * (4 + sw), "bus_bytes_device_path_out": ops.rle_strings_bytes(S, 0) + total,
+            "bus_bytes_host_path_out": 4 * ops.rle_block_words("set", S, sw), "bus_bytes_device_path_out": ops.rle_strings_bytes(S, 0) + total,
             "to_python_strings_host_path": out_t[0], "to_python_strings_device_path": out_t[1],
             "ratio_out_host_over_device": round(out_t[0]["median_ms"] / out_t[1]["median_ms"], 2),
             "from_python_strings_host_path": in_t[0], "from_python_strings_device_path": in_t[1],
@@ -672,13 +672,13 @@ def polygons_leg(dev, reps, cli_images):
     ep_d = d(np.arange(0, 2 * 64 + 1, 2), np.int32)
     images = np.asarray([[H, W, 0]], dtype=np.int64)
     sw = ops.rle_slot_words(H, W)
-    out = torch.empty(64 * (8 + sw), dtype=torch.int32, device=dev)
-    ws = ops.workspace(lib.hgl_rle_from_polygons_workspace_bytes(images.ctypes.data, 1, 64, len(polys)), dev, "rle")
-    base = out.data_ptr()
+    out = torch.empty(ops.rle_block_words("status", 64, sw), dtype=torch.int32, device=dev)
+    t_p, s_p, st_p = (p.data_ptr() for p in ops.rle_block("status", out, 64, sw))
+    ws =ops.workspace(lib.hgl_rle_from_polygons_workspace_bytes(images.ctypes.data, 1, 64, len(polys)), dev, "rle")
 
     def kernel():
         rc = lib.hgl_rle_from_polygons_device(xy_d.data_ptr(), po_d.data_ptr(), len(polys), ep_d.data_ptr(), 64, images.ctypes.data, 1, 0,
-                                              base + 16 * 64, sw, base, base + 4 * 64 * (4 + sw), ws.data_ptr(), ws.numel(),
+                                              s_p, sw, t_p, st_p, ws.data_ptr(), ws.numel(),
                                               torch.cuda.current_stream().cuda_stream)
         assert rc == 0
 
