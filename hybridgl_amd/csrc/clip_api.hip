@@ -28,10 +28,9 @@ static bool block_uses_x3(const HglResBlockW& w, int M, int D) {
 // the attention of a block on the split path, with q | k | v as fp16 hi | lo planes aliasing bf.QKV; its output is the fp16
 // hi | lo pair aliasing bf.H that the out-projection reads
 static HglAttn block_attn_planes(const HglBlockBufs& bf, int B, int S, int D, int heads) {
-  const uint16_t* Qh = (const uint16_t*)bf.QKV;
-  uint16_t* Hh = (uint16_t*)bf.H;
-  HglAttn d = hgl_attn_packed_planes(Qh, Qh + (size_t)B * S * 3 * D, B, heads, S, D / heads);
-  d.out_hi = Hh, d.out_lo = Hh + (size_t)B * S * D;
+  const HglAct Q = hgl_act(bf.QKV, (size_t)B * S * 3 * D, true), H = hgl_act(bf.H, (size_t)B * S * D, true);
+  HglAttn d = hgl_attn_packed_planes(Q.hi, Q.lo, B, heads, S, D / heads);
+  d.out_hi = H.hi, d.out_lo = H.lo;
   return d;
 }
 
@@ -60,55 +59,35 @@ HglClipBlockRoute hgl_clip_block_route(const HglResBlockW& w, const HglBlockBufs
   return r;
 }
 
+// the MLP half of a residual block (clip/model.py:198-200, :244-257)
+static HglMlp block_mlp(const HglResBlockW& w) { return {w.ln2_w, w.ln2_b, w.fc_w, w.fc_b, w.proj_w, w.proj_b, 1e-5f, HGL_ACT_QUICKGELU}; }
+
 // first half of a block: H = ln_1(X) (fp32, or the fp16 hi+lo pair aliasing bf.H on the split path), QKV = H W_in + b
 // (r.planes: q | k | v as fp16 hi / lo planes aliasing bf.QKV)
 int hgl_clip_block_qkv(const HglResBlockW& w, const HglClipBlockRoute& r, const float* X, int M, int D, const HglBlockBufs& bf,
                        hipStream_t st) {
-  if (r.x3) {
-    uint16_t* Hh = (uint16_t*)bf.H;
-    uint16_t* Hl = Hh + (size_t)M * D;
-    HGL_TRY(hgl_launch_layernorm_split(X, w.ln1_w, w.ln1_b, Hh, Hl, M, D, 1e-5f, st));
-    uint16_t* Qh = (uint16_t*)bf.QKV;
-    if (r.planes)
-      return hgl_launch_gemm(hgl_gemm_planes_split(Hh, Hl, w.in_proj_w, w.in_proj_b, Qh, Qh + (size_t)M * 3 * D, M, 3 * D, D), st);
-    return hgl_launch_gemm(hgl_gemm_planes(Hh, Hl, w.in_proj_w, w.in_proj_b, bf.QKV, M, 3 * D, D), st);
-  }
-  HGL_TRY(hgl_launch_layernorm(X, w.ln1_w, w.ln1_b, bf.H, M, D, 1e-5f, st));
-  return hgl_launch_gemm(hgl_gemm_linear(bf.H, w.in_proj_w, w.in_proj_b, bf.QKV, M, 3 * D, D), st);
+  const HglAct H = hgl_act(bf.H, (size_t)M * D, r.x3), QKV = hgl_act(bf.QKV, (size_t)M * 3 * D, r.planes);
+  HGL_TRY(hgl_launch_layernorm_act(X, w.ln1_w, w.ln1_b, H, M, D, 1e-5f, st));
+  return hgl_launch_gemm(hgl_gemm_act(H, w.in_proj_w, w.in_proj_b, QKV, M, 3 * D, D), st);
 }
 
 // second half: x <- x + out_proj(attention(QKV)) ; x <- x + mlp(ln_2 x)
 int hgl_clip_block_rest(const HglResBlockW& w, const HglClipBlockRoute& r, float* X, int B, int S, int D, int heads,
                         const HglBlockBufs& bf, int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st) {
   const int M = B * S;
+  // activations feeding a GEMM alias the fp32 scratch buffers (same byte size)
+  const HglAct H = hgl_act(bf.H, (size_t)M * D, r.x3), F = hgl_act(bf.F, (size_t)M * 4 * D, r.x3);
   HglAttn at = r.planes ? block_attn_planes(bf, B, S, D, heads) : hgl_attn_packed(bf.QKV, B, heads, S, D / heads);
   at.mask_kind = mask_kind, at.keep = keep, at.keep_b0 = keep_b0, at.keep_n = keep_n;
-  if (r.x3) {
-    // activations feeding a GEMM alias the fp32 scratch buffers (same byte size)
-    uint16_t* Hh = (uint16_t*)bf.H;
-    uint16_t* Hl = Hh + (size_t)M * D;
-    uint16_t* Fh = (uint16_t*)bf.F;
-    uint16_t* Fl = Fh + (size_t)M * 4 * D;
-    // the attention writes its output as the fp16 hi+lo pair the out-projection reads
-    at.out_hi = Hh, at.out_lo = Hl;
-    HGL_TRY(hgl_launch_attention(at, st));
-    // (balanced: whole rounds of the persistent tiling + a split-K tail when the last round would be mostly empty; the
-    // partial sums borrow the qkv buffer, dead after the attention)
-    HglGemm out = hgl_gemm_planes(Hh, Hl, w.out_proj_w, w.out_proj_b, X, M, D, D, HGL_ACT_NONE, X);
-    out.part = bf.QKV, out.part_bytes = (size_t)M * 3 * D * sizeof(float);
-    HGL_TRY(hgl_launch_gemm(out, st));
-    HGL_TRY(hgl_launch_layernorm_split(X, w.ln2_w, w.ln2_b, Hh, Hl, M, D, 1e-5f, st));
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes_split(Hh, Hl, w.fc_w, w.fc_b, Fh, Fl, M, 4 * D, D, HGL_ACT_QUICKGELU), st));
-    HglGemm proj = hgl_gemm_planes(Fh, Fl, w.proj_w, w.proj_b, X, M, D, 4 * D, HGL_ACT_NONE, X);
-    proj.part = out.part, proj.part_bytes = out.part_bytes, proj.ksplit = r.ks;   // r.ks 1: whole rounds + a tail where that pays
-    return hgl_launch_gemm(proj, st);
-  }
-  at.out = bf.H;
+  // (split path: the attention writes its output as the fp16 hi+lo pair the out-projection reads)
+  at.out = H.f32, at.out_hi = H.hi, at.out_lo = H.lo;
   HGL_TRY(hgl_launch_attention(at, st));
-  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(bf.H, w.out_proj_w, w.out_proj_b, X, M, D, D, HGL_ACT_NONE, X), st));
-  HGL_TRY(hgl_launch_layernorm(X, w.ln2_w, w.ln2_b, bf.H, M, D, 1e-5f, st));
-  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(bf.H, w.fc_w, w.fc_b, bf.F, M, 4 * D, D, HGL_ACT_QUICKGELU), st));
-  return hgl_launch_gemm(hgl_gemm_linear(bf.F, w.proj_w, w.proj_b, X, M, D, 4 * D, HGL_ACT_NONE, X), st);
+  // (balanced: whole rounds of the persistent tiling + a split-K tail when the last round would be mostly empty; the
+  // partial sums borrow the qkv buffer, dead after the attention)
+  HglGemm out = hgl_gemm_act(H, w.out_proj_w, w.out_proj_b, X, M, D, D, HGL_ACT_NONE, X);
+  out.part = bf.QKV, out.part_bytes = (size_t)M * 3 * D * sizeof(float);
+  HGL_TRY(hgl_launch_gemm(out, st));
+  return hgl_mlp_half(block_mlp(w), X, H, F, M, D, out.part, out.part_bytes, r.ks, st);   // r.ks 1: whole rounds + a tail where that pays
 }
 
 // x <- x + attn(ln_1 x) ; x <- x + mlp(ln_2 x)      (clip/model.py:244-257)
@@ -124,19 +103,20 @@ int hgl_clip_run_block(const HglResBlockW& w, float* X, int B, int S, int D, int
 int hgl_clip_embed_images(const HglClipVisionW* w, const float* imgs, int n_img, float* X, float* cols, float* tok,
                           hipStream_t st) {
   const int D = w->width, g = w->grid, P = g * g, S = P + 1, kd = 3 * w->patch * w->patch;
-  if (n_img * P > 512 && (w->patch & 3) == 0 && hgl_use_x3(w->conv1_w, kd)) {
-    // split-fp16 path: the im2col matrix is written directly as fp16 hi | lo planes (same bytes as the fp32 matrix)
-    uint16_t* ch = (uint16_t*)cols;
-    uint16_t* cl = ch + (size_t)n_img * P * kd;
-    HGL_TRY(hgl_launch_im2col_patch_split(imgs, n_img, g * w->patch, w->patch, ch, cl, st));
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(ch, cl, w->conv1_w, nullptr, tok, n_img * P, D, kd), st));
-  } else {
-    HGL_TRY(hgl_launch_im2col_patch(imgs, n_img, g * w->patch, w->patch, cols, st));
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(cols, w->conv1_w, nullptr, tok, n_img * P, D, kd), st));
-  }
+  // split-fp16 path: the im2col matrix is written directly as fp16 hi | lo planes (same bytes as the fp32 matrix)
+  const bool split = n_img * P > 512 && (w->patch & 3) == 0 && hgl_use_x3(w->conv1_w, kd);
+  HGL_TRY(hgl_linear_split_or_not(hgl_gemm_linear(cols, w->conv1_w, nullptr, tok, n_img * P, D, kd), split, cols, (size_t)n_img * P * kd,
+                                  [&](const HglAct& a) { return hgl_launch_im2col_patch_act(imgs, n_img, g * w->patch, w->patch, a, st); }, st));
   HGL_TRY(hgl_launch_assemble_lnpre(tok, w->class_embedding, w->positional_embedding, w->ln_pre_w,
                                     w->ln_pre_b, X, n_img, S, D, st));
   return HGL_OK;
+}
+
+bool hgl_valid_vision(const HglClipVisionW* w) {
+  return w && w->width > 0 && w->layers > 0 && w->heads > 0 && w->patch > 0 && w->grid > 0 &&
+         w->embed > 0 && w->width % w->heads == 0 && (w->width & 3) == 0 && (w->embed & 3) == 0 &&
+         w->conv1_w && w->class_embedding && w->positional_embedding && w->ln_pre_w && w->ln_pre_b &&
+         w->blocks && w->ln_post_w && w->ln_post_b && w->proj_t;
 }
 
 namespace {
@@ -197,9 +177,7 @@ int run_block_cls(const HglResBlockW& w, const float* X, int B, int S, int D, in
   HGL_TRY(hgl_launch_attention(at, st));
   HGL_TRY(hgl_launch_gather_rows(X, (long long)S * D, B, D, xcls, st));
   HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(att, w.out_proj_w, w.out_proj_b, xcls, B, D, D, HGL_ACT_NONE, xcls), st));
-  HGL_TRY(hgl_launch_layernorm(xcls, w.ln2_w, w.ln2_b, h, B, D, 1e-5f, st));
-  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(h, w.fc_w, w.fc_b, bf.F, B, 4 * D, D, HGL_ACT_QUICKGELU), st));
-  return hgl_launch_gemm(hgl_gemm_linear(bf.F, w.proj_w, w.proj_b, xcls, B, D, 4 * D, HGL_ACT_NONE, xcls), st);
+  return hgl_mlp_half(block_mlp(w), xcls, hgl_act(h, (size_t)B * D, false), hgl_act(bf.F, (size_t)B * 4 * D, false), B, D, nullptr, 0, 0, st);
 }
 
 // ln_post(rows) @ proj (+ R) on CLS rows that are already gathered (p.cls_rows)
@@ -211,20 +189,13 @@ int head_rows(const HglClipVisionW* w, int N, float* out, const float* R, const 
   return hgl_launch_gemm(head, st);
 }
 
-bool valid_vision(const HglClipVisionW* w) {
-  return w && w->width > 0 && w->layers > 0 && w->heads > 0 && w->patch > 0 && w->grid > 0 &&
-         w->embed > 0 && w->width % w->heads == 0 && (w->width & 3) == 0 && (w->embed & 3) == 0 &&
-         w->conv1_w && w->class_embedding && w->positional_embedding && w->ln_pre_w && w->ln_pre_b &&
-         w->blocks && w->ln_post_w && w->ln_post_b && w->proj_t;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t hgl_clip_hybrid_workspace_bytes(const HglClipVisionW* w, int N, int Hm, int Wm, int fusion_mode) {
   (void)Hm; (void)Wm;
-  if (!valid_vision(w) || N <= 0) return 0;
+  if (!hgl_valid_vision(w) || N <= 0) return 0;
   HglArena ar(nullptr, 0);
   ClipPlan p;
   carve(ar, w, N, fusion_mode, p);
@@ -244,7 +215,7 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
                                int masking_block, int last_layer, float* out, void* workspace,
                                size_t workspace_bytes, void* stream) {
   HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(valid_vision(w), "clip_hybrid_forward: invalid weight struct");
+  HGL_REQUIRE(hgl_valid_vision(w), "clip_hybrid_forward: invalid weight struct");
   HGL_REQUIRE(local_imgs && out && N > 0, "clip_hybrid_forward: null input");
   HGL_REQUIRE(fusion_mode >= 0 && fusion_mode <= 5, "clip_hybrid_forward: bad fusion mode %d", fusion_mode);
   const bool two_stream = n_streams(fusion_mode) >= 2;
@@ -324,7 +295,7 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
       for (int l = masking_block; l <= ret_block; ++l) {
         HGL_TRY(hgl_launch_mix(Y, X, 1.f, X + sN, 2.f, p.pm, N, S, D, st));
         if (l < ret_block) {
-          (void)hipMemcpyAsync(Y + sN, X + sN, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
+          HGL_TRY(hgl_copy_d2d(Y + sN, X + sN, sizeof(float) * sN, "clip_hybrid_forward: copying a stream", st));
           HGL_TRY(hgl_clip_run_block(w->blocks[l], Y, 2 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, N, N, st));
         } else {  // the global stream of the returning block is dead, and so are the non-CLS rows of the local one
           HGL_TRY(run_block_cls(w->blocks[l], Y, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, p, st));
@@ -338,7 +309,7 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
       for (int l = masking_block; l <= ret_block; ++l) {
         HGL_TRY(hgl_launch_mix(Y + sN, X, 1.f, X + sN, 2.f, nullptr, N, S, D, st));
         if (l < ret_block) {
-          (void)hipMemcpyAsync(Y, X, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
+          HGL_TRY(hgl_copy_d2d(Y, X, sizeof(float) * sN, "clip_hybrid_forward: copying a stream", st));
           HGL_TRY(hgl_clip_run_block(w->blocks[l], Y, 2 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, N, N, st));
         } else {  // the local stream of the returning block is dead, and so are the non-CLS rows of the global one
           HGL_TRY(run_block_cls(w->blocks[l], Y + sN, N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, 0, N, p, st));
@@ -350,16 +321,16 @@ static int hybrid_forward_impl(const HglClipVisionW* w, const float* local_imgs,
     case HGL_FUSION_G2L_L2G: {
       // stream order here: [xl | hl | xg | hg]  (keep applies to the last two)
       // init: xg currently at X+sN -> move to slot 2; hl = xl, hg = xg (model/backbone.py:272-276)
-      (void)hipMemcpyAsync(X + 2 * sN, X + sN, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
-      (void)hipMemcpyAsync(X + sN, X, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
-      (void)hipMemcpyAsync(X + 3 * sN, X + 2 * sN, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
+      HGL_TRY(hgl_copy_d2d(X + 2 * sN, X + sN, sizeof(float) * sN, "clip_hybrid_forward: copying a stream", st));
+      HGL_TRY(hgl_copy_d2d(X + sN, X, sizeof(float) * sN, "clip_hybrid_forward: copying a stream", st));
+      HGL_TRY(hgl_copy_d2d(X + 3 * sN, X + 2 * sN, sizeof(float) * sN, "clip_hybrid_forward: copying a stream", st));
       for (int l = masking_block; l <= ret_block; ++l) {
         // hl_in = hl + 2*tokmask(xg) ; hg_in = xl + 2*hg   (pre-block values of xl, xg)
         HGL_TRY(hgl_launch_mix(Y + sN, X + sN, 1.f, X + 2 * sN, 2.f, p.pm, N, S, D, st));
         HGL_TRY(hgl_launch_mix(Y + 3 * sN, X, 1.f, X + 3 * sN, 2.f, nullptr, N, S, D, st));
         if (l < ret_block) {
-          (void)hipMemcpyAsync(Y, X, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
-          (void)hipMemcpyAsync(Y + 2 * sN, X + 2 * sN, sizeof(float) * sN, hipMemcpyDeviceToDevice, st);
+          HGL_TRY(hgl_copy_d2d(Y, X, sizeof(float) * sN, "clip_hybrid_forward: copying a stream", st));
+          HGL_TRY(hgl_copy_d2d(Y + 2 * sN, X + 2 * sN, sizeof(float) * sN, "clip_hybrid_forward: copying a stream", st));
           HGL_TRY(hgl_clip_run_block(w->blocks[l], Y, 4 * N, S, D, heads, bf, HGL_MASK_CLS_KEEP, p.keep, 2 * N, N, st));
         } else {  // plain xl / xg streams of the returning block are dead; of hl / hg only the CLS rows are consumed
           HGL_TRY(run_block_cls(w->blocks[l], Y + sN, N, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, p, st));
@@ -447,10 +418,7 @@ int hgl_clip_encode_text_ex(const HglClipTextW* w, const int32_t* tokens, int B,
   HGL_TRY(hgl_launch_text_embed(tokens, w->token_embedding, w->positional_embedding, p.X, B, S, w->context, D,
                                 w->vocab, p.eot, st));
   if (pool_pos)   // clip/model.py:426-428: the pooled row is chosen by the caller
-    if (hipMemcpyAsync(p.eot, pool_pos, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-      hgl_set_error("clip_encode_text: copying pool_pos failed");
-      return HGL_ELAUNCH;
-    }
+    HGL_TRY(hgl_copy_d2d(p.eot, pool_pos, (size_t)B * sizeof(int32_t), "clip_encode_text: copying pool_pos", st));
   BlockBufs bf{p.H, p.QKV, p.F};
   for (int l = 0; l < w->layers; ++l) {
     if (n_zero > 0 && l >= masking_block) HGL_TRY(hgl_launch_zero_positions(p.X, B, S, D, zero_pos, n_zero, st));   // backbone.py:44-46

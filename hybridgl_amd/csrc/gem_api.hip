@@ -310,15 +310,16 @@ int gem_block(const HglResBlockW& w, const GemPlan& p, int S, int D, int heads, 
   // (the self-self attention below reads q | k | v as fp32)
   const HglClipBlockRoute r = hgl_clip_block_route(w, bf, nb, S, D, heads, HGL_MASK_NONE, need_ori ? HGL_BLOCK_FP32_QKV : HGL_BLOCK_QKV_ONLY);
   const bool x3 = r.x3;
+  const HglAct H = hgl_act(p.H, (size_t)MD, x3);   // ln_1(x)
   HGL_TRY(hgl_clip_block_qkv(w, r, p.X, M, D, bf, st));       // p.H = ln_1(x) (fp32 or the hi+lo pair), p.QKV
   if (ss_temp > 0.f) {
     hipLaunchKernelGGL(set_scalar_kernel, dim3(1), dim3(64), 0, st, p.t, ss_temp, nb);
   } else {
     if (x3)
-      hipLaunchKernelGGL(row_norm_split_kernel, dim3((M + 3) / 4), dim3(256), 0, st, (const _Float16*)p.H,
-                         hgl_split_terms() == 1 ? nullptr : (const _Float16*)p.H + MD, M, D, p.norms);
+      hipLaunchKernelGGL(row_norm_split_kernel, dim3((M + 3) / 4), dim3(256), 0, st, (const _Float16*)H.hi,
+                         hgl_split_terms() == 1 ? nullptr : (const _Float16*)H.lo, M, D, p.norms);
     else
-      hipLaunchKernelGGL(row_norm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, p.H, M, D, p.norms);
+      hipLaunchKernelGGL(row_norm_kernel, dim3((M + 3) / 4), dim3(256), 0, st, H.f32, M, D, p.norms);
     hipLaunchKernelGGL(temp_kernel, dim3(nb), dim3(256), 0, st, p.norms, S, scale, p.t);   // one temperature per image
   }
   HGL_TRY(hgl_check_launch("gem_temperature"));
@@ -348,27 +349,21 @@ int gem_block(const HglResBlockW& w, const GemPlan& p, int S, int D, int heads, 
       HGL_TRY(hgl_launch_attention(at, st));
     }
   }
-  if (x3) {
-    _Float16* Mh = (_Float16*)p.N3;
-    _Float16* Ml = Mh + MD;
-    hipLaunchKernelGGL(mean3_split_kernel, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, p.X1, MD, MD, Mh,
-                       hgl_split_terms() == 1 ? nullptr : Ml);
-    HGL_TRY(hgl_check_launch("gem_mean3"));
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(Mh, Ml, w.out_proj_w, w.out_proj_b, p.Xg, M, D, D, HGL_ACT_NONE, p.Xg), st));
-  } else {
-    hipLaunchKernelGGL(mean3_kernel, dim3((unsigned)((MD + 255) / 256)), dim3(256), 0, st, p.X1, MD, MD, p.N3);
-    HGL_TRY(hgl_check_launch("gem_mean3"));
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.N3, w.out_proj_w, w.out_proj_b, p.Xg, M, D, D, HGL_ACT_NONE, p.Xg), st));
-  }
+  // the mean of the three sets over N3 (dead by now), in the form the out-projection reads
+  const auto mean3 = [&](const HglAct& m) {
+    const dim3 grid((unsigned)((MD + 255) / 256));
+    if (m.hi)   // (f16 mode: the hi plane only)
+      hipLaunchKernelGGL(mean3_split_kernel, grid, dim3(256), 0, st, p.X1, MD, MD, (_Float16*)m.hi,
+                         hgl_split_terms() == 1 ? nullptr : (_Float16*)m.lo);
+    else
+      hipLaunchKernelGGL(mean3_kernel, grid, dim3(256), 0, st, p.X1, MD, MD, m.f32);
+    return hgl_check_launch("gem_mean3");
+  };
+  HGL_TRY(hgl_linear_split_or_not(hgl_gemm_linear(p.N3, w.out_proj_w, w.out_proj_b, p.Xg, M, D, D, HGL_ACT_NONE, p.Xg), x3, p.N3,
+                                  (size_t)MD, mean3, st));
   if (!need_ori) return HGL_OK;
   // original stream (clip/model.py:244-257): the plain block on the same QKV
   return hgl_clip_block_rest(w, r, p.X, nb, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st);
-}
-
-bool valid_vision(const HglClipVisionW* w) {
-  return w && w->width > 0 && w->layers > 0 && w->heads > 0 && w->patch > 0 && w->grid > 0 && w->embed > 0 &&
-         w->width % w->heads == 0 && (w->width & 3) == 0 && (w->embed & 3) == 0 && w->conv1_w && w->class_embedding &&
-         w->positional_embedding && w->ln_pre_w && w->ln_pre_b && w->blocks && w->ln_post_w && w->ln_post_b && w->proj_t;
 }
 
 }  // namespace
@@ -376,7 +371,7 @@ bool valid_vision(const HglClipVisionW* w) {
 extern "C" {
 
 size_t hgl_gem_batch_workspace_bytes(const HglClipVisionW* w, int nb) {
-  if (!valid_vision(w) || nb < 1) return 0;
+  if (!hgl_valid_vision(w) || nb < 1) return 0;
   HglArena ar(nullptr, 0);
   GemPlan p;
   carve(ar, w, nb, p);
@@ -389,7 +384,7 @@ int hgl_gem_image_features_batch(const HglClipVisionW* w, const float* imgs, int
                                  float ss_attn_temp, float* feat_gem, float* feat_ori, void* workspace, size_t workspace_bytes,
                                  void* stream) {
   HGL_TRY(hgl_require_device());
-  HGL_REQUIRE(valid_vision(w), "gem_image_features: invalid weight struct");
+  HGL_REQUIRE(hgl_valid_vision(w), "gem_image_features: invalid weight struct");
   HGL_REQUIRE(imgs && feat_gem && nb >= 1 && nb <= 64, "gem_image_features: bad arguments (nb %d)", nb);
   HGL_REQUIRE(gem_blocks >= 0 && gem_blocks <= w->layers, "gem_image_features: gem_blocks %d outside 0..%d", gem_blocks, w->layers);
   HGL_REQUIRE(ss_attn_iter >= 0 && ss_attn_iter <= 16, "gem_image_features: bad ss_attn_iter %d", ss_attn_iter);
@@ -408,7 +403,7 @@ int hgl_gem_image_features_batch(const HglClipVisionW* w, const float* imgs, int
     HGL_TRY(hgl_clip_run_block(w->blocks[l], p.X, nb, S, D, heads, bf, HGL_MASK_NONE, nullptr, 0, 0, st));
   const float* gem_stream = p.X;
   if (gem_blocks > 0) {
-    (void)hipMemcpyAsync(p.Xg, p.X, sizeof(float) * (size_t)M * D, hipMemcpyDeviceToDevice, st);
+    HGL_TRY(hgl_copy_d2d(p.Xg, p.X, sizeof(float) * (size_t)M * D, "gem_image_features: copying the stream", st));
     gem_stream = p.Xg;
     for (int l = first_gem; l < w->layers; ++l) {
       // the original stream of the last block only feeds feat_ori

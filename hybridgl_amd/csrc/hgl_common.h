@@ -389,6 +389,7 @@ int hgl_clip_block_rest(const HglResBlockW& w, const HglClipBlockRoute& r, float
                         const HglBlockBufs& bf, int mask_kind, const uint8_t* keep, int keep_b0, int keep_n, hipStream_t st);
 int hgl_clip_embed_images(const HglClipVisionW* w, const float* imgs, int n_img, float* X, float* cols, float* tok,
                           hipStream_t st);
+bool hgl_valid_vision(const HglClipVisionW* w);
 
 // ---- optional per-kernel-class timing with HIP events on the launch stream (bench roofline) ----
 enum HglProfClass { HGL_PROF_GEMM = 0, HGL_PROF_ATTN = 1, HGL_PROF_OTHER = 2, HGL_PROF_GEMM_X3 = 3, HGL_PROF_GEMM_X3G = 4, HGL_PROF_GEMM_X3_FEW = 5, HGL_PROF_NCLASS = 6 };
@@ -480,3 +481,80 @@ int hgl_gemm_f16x3_splitk_factor(int M, int N, int K);
 int hgl_launch_win_partition_split(const float* H, int g, int ws, int nw, int D, void* hi, void* lo, hipStream_t st);
 // true when the split-fp16 path applies to a GEMM with this weight and reduction length
 static inline bool hgl_use_x3(const float* W, int K) { return hgl_split_layout() && (K % 64) == 0 && hgl_has_split_weight(W); }
+
+// ---- the activation operand of the encoder blocks -----------------------------------------------------------------------
+// What a block step reads or writes: the fp32 rows of a scratch buffer, or -- the split-fp16 modes -- the fp16 hi | lo planes
+// that alias the same bytes (hi at the buffer's start, lo `elems` halfs behind it).  Exactly one form is set.  A block is
+// written ONCE over operands; its route (HglClipBlockRoute, EncBlockRoute in sam_api.hip) says which form each operand has and
+// what else differs.  (f16 mode: lo is still named; the launchers that take a null lo plane get it at their call site.)
+struct HglAct {
+  float* f32 = nullptr;
+  uint16_t *hi = nullptr, *lo = nullptr;
+};
+inline HglAct hgl_act(float* buf, size_t elems, bool split) {
+  HglAct a;
+  if (split) a.hi = (uint16_t*)buf, a.lo = a.hi + elems;
+  else a.f32 = buf;
+  return a;
+}
+// y = LayerNorm(x) into an operand
+inline int hgl_launch_layernorm_act(const float* x, const float* w, const float* b, const HglAct& y, int rows, int D, float eps,
+                                    hipStream_t st) {
+  return y.hi ? hgl_launch_layernorm_split(x, w, b, y.hi, y.lo, rows, D, eps, st) : hgl_launch_layernorm(x, w, b, y.f32, rows, D, eps, st);
+}
+// the im2col matrix of a patch embedding into an operand
+inline int hgl_launch_im2col_patch_act(const float* img, int N, int res, int patch, const HglAct& cols, hipStream_t st) {
+  return cols.hi ? hgl_launch_im2col_patch_split(img, N, res, patch, cols.hi, cols.lo, st) : hgl_launch_im2col_patch(img, N, res, patch, cols.f32, st);
+}
+// a dense nn.Linear from an operand to fp32 C: hgl_gemm_planes or hgl_gemm_linear ...
+inline HglGemm hgl_gemm_act(const HglAct& A, const float* W, const float* bias, float* C, int M, int N, int K, int act = HGL_ACT_NONE,
+                            const float* R = nullptr) {
+  return A.hi ? hgl_gemm_planes(A.hi, A.lo, W, bias, C, M, N, K, act, R) : hgl_gemm_linear(A.f32, W, bias, C, M, N, K, act, R);
+}
+// ... and to an operand: planes out (hgl_gemm_planes_split; the input is then planes as well), or the above on C.f32
+inline HglGemm hgl_gemm_act(const HglAct& A, const float* W, const float* bias, const HglAct& C, int M, int N, int K,
+                            int act = HGL_ACT_NONE) {
+  HglGemm d = hgl_gemm_act(A, W, bias, C.f32, M, N, K, act);
+  d.Ch = C.hi, d.Cl = C.lo;
+  return d;
+}
+// The MLP half of a transformer block, x <- x + proj(act(fc(ln(x)))) on M rows of D floats, through the operands H [M, D] and
+// F [M, 4D].  part / part_bytes: scratch for the partial sums of proj; ks: its split-K factor (HglGemm::ksplit: 0 / 1 leave the
+// cut to the launcher) -- both decided by the caller's route; the fp32 form of proj reads neither.
+struct HglMlp {
+  const float *ln_w, *ln_b, *fc_w, *fc_b, *proj_w, *proj_b;
+  float eps;
+  int act;
+};
+inline int hgl_mlp_half(const HglMlp& w, float* X, const HglAct& H, const HglAct& F, int M, int D, float* part, size_t part_bytes,
+                        int ks, hipStream_t st) {
+  HGL_TRY(hgl_launch_layernorm_act(X, w.ln_w, w.ln_b, H, M, D, w.eps, st));
+  HGL_TRY(hgl_launch_gemm(hgl_gemm_act(H, w.fc_w, w.fc_b, F, M, 4 * D, D, w.act), st));
+  HglGemm proj = hgl_gemm_act(F, w.proj_w, w.proj_b, X, M, D, 4 * D, HGL_ACT_NONE, X);
+  proj.part = part, proj.part_bytes = part_bytes, proj.ksplit = ks;
+  return hgl_launch_gemm(proj, st);
+}
+// A linear on fp32 values whose weight may have a registered split.  d: the GEMM on the fp32 rows d.A (lda == K), n values in
+// all.  split: produce(a) writes the values as the fp16 hi | lo planes a into the dead buffer `scratch` and the GEMM reads those
+// (hgl_gemm_planes); else produce(a) writes them to a.f32 == d.A -- or finds them there -- and d runs as it is.
+template <class Produce>
+inline int hgl_linear_split_or_not(HglGemm d, bool split, float* scratch, size_t n, Produce&& produce, hipStream_t st) {
+  const HglAct a = hgl_act(split ? scratch : const_cast<float*>(d.A), n, split);
+  HGL_TRY(produce(a));
+  if (split) d.A = nullptr, d.Ah = a.hi, d.Al = a.lo;
+  return hgl_launch_gemm(d, st);
+}
+// the same where the values exist as the fp32 rows d.A: the split producer is hgl_launch_split_f16
+inline int hgl_linear_split_or_not(const HglGemm& d, bool split, float* scratch, size_t n, hipStream_t st) {
+  const float* x = d.A;
+  return hgl_linear_split_or_not(
+      d, split, scratch, n, [=](const HglAct& a) { return a.hi ? hgl_launch_split_f16(x, 1.0f, a.hi, a.lo, (long long)n, st) : HGL_OK; }, st);
+}
+// a device-to-device copy on the stream, checked: `what` names the call and the copy in the error
+inline int hgl_copy_d2d(void* dst, const void* src, size_t bytes, const char* what, hipStream_t st) {
+  if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    hgl_set_error("%s failed", what);
+    return HGL_ELAUNCH;
+  }
+  return HGL_OK;
+}

@@ -89,26 +89,22 @@ struct EncBlockRoute {
   EncAttn attn;
   bool gather;          // the windowed GEMMs read and write the real tokens only (the window does not divide the grid)
   bool planes;          // the in-projection writes q | k | v as fp16 hi / lo planes (same bytes as the fp32 tensor)
+  int ks;               // split-K factor of mlp.lin2 (0: whole rounds + a tail where that pays)
 };
 
-// the fp16 hi | lo planes of the split path: each pair aliases an fp32 buffer of the plan (same bytes)
-struct EncPlanes {
-  uint16_t *Ah, *Al;    // GEMM input in window order, later the attention's output (the window buffer)
-  uint16_t *Hh, *Hl;    // norm2 (H)
-  uint16_t *Fh, *Fl;    // mlp.lin1 (F)
-  uint16_t *Qh, *Ql;    // split qkv (QKV)
-  EncPlanes(const EncPlan& p, const EncBlockRoute& r)
-      : Ah((uint16_t*)p.Hw), Al(Ah + (size_t)r.M * r.D), Hh((uint16_t*)p.H), Hl(Hh + (size_t)r.T * r.D), Fh((uint16_t*)p.F),
-        Fl(Fh + (size_t)r.T * 4 * r.D), Qh((uint16_t*)p.QKV), Ql(Qh + (size_t)r.M * 3 * r.D) {}
-};
+// q | k | v of the block's B windows, as fp32 or as the fp16 hi | lo planes aliasing the same buffer
+HglAct enc_qkv(const EncPlan& p, const EncBlockRoute& r, bool planes) { return hgl_act(p.QKV, (size_t)r.M * 3 * r.D, planes); }
+// the window buffer as an operand: the in-projection's input in window order and, on the split path, the attention's output
+HglAct enc_win(const EncPlan& p, const EncBlockRoute& r, bool planes) { return hgl_act(p.Hw, (size_t)r.M * r.D, planes); }
 
-// the attention of the B windows (or whole grids) as `kind` runs it: on p.QKV as planes or as fp32 -> the planes Ah | Al (x3) or
-// p.O (fp32); the rel-pos terms from the block's tables or as the tensors p.relh / p.relw that enc_attention computes first
+// the attention of the B windows (or whole grids) as `kind` runs it: on p.QKV as planes or as fp32 -> the planes of the window
+// buffer (x3) or p.O (fp32); the rel-pos terms from the block's tables or as the tensors p.relh / p.relw that enc_attention
+// computes first
 HglAttn enc_attn(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, EncAttn kind) {
-  const EncPlanes s(p, r);
   const bool planes = kind == ENC_ATTN_PS_WIN || kind == ENC_ATTN_PS_GLOBAL;
-  HglAttn d = planes ? hgl_attn_packed_planes(s.Qh, s.Ql, r.B, r.heads, r.S, r.hd) : hgl_attn_packed(p.QKV, r.B, r.heads, r.S, r.hd);
-  d.out = r.x3 ? nullptr : p.O, d.out_hi = s.Ah, d.out_lo = s.Al;
+  const HglAct Q = enc_qkv(p, r, planes), Ow = enc_win(p, r, true);
+  HglAttn d = planes ? hgl_attn_packed_planes(Q.hi, Q.lo, r.B, r.heads, r.S, r.hd) : hgl_attn_packed(p.QKV, r.B, r.heads, r.S, r.hd);
+  d.out = r.x3 ? nullptr : p.O, d.out_hi = Ow.hi, d.out_lo = Ow.lo;   // (the pair is named in both forms; read when out is null)
   if (kind == ENC_ATTN_PS_WIN || kind == ENC_ATTN_WIN14) d.tab_h = b.rel_pos_h, d.tab_w = b.rel_pos_w;
   else d.rel_h = p.relh, d.rel_w = p.relw, d.kh = d.kw = r.size;
   return d;
@@ -138,6 +134,10 @@ int enc_block_route(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPla
   else if (r.x3 && r.ws == 0 && r.size == 64 && ps_glob_on && serves(ENC_ATTN_PS_GLOBAL, HGL_ATTN_PS_RELT)) r.attn = ENC_ATTN_PS_GLOBAL;
   else if (r.x3 && r.ws == 14 && serves(ENC_ATTN_WIN14, HGL_ATTN_WIN14)) r.attn = ENC_ATTN_WIN14;
   r.planes = r.attn == ENC_ATTN_PS_WIN || r.attn == ENC_ATTN_PS_GLOBAL;
+  // mlp.lin2: few output tiles, K = 4D -> split-K over the idle CUs; the partial sums borrow the qkv buffer
+  static const int splitk_on = HGL_DIAG_SWITCH("HGL_SAM_SPLITK", 1);   // 0 disables (A/B timing)
+  const int ks = r.x3 && splitk_on ? hgl_gemm_f16x3_splitk_factor(r.T, D, 4 * D) : 1;
+  r.ks = ks > 1 && (size_t)ks * r.T * D <= (size_t)r.M * 3 * D ? ks : 0;   // its slices fit the qkv buffer
   return HGL_OK;
 }
 
@@ -168,93 +168,66 @@ int enc_relpos_tables(const float* qkv, const void* q_hi, const void* q_lo, int 
 // route named
 int enc_attention(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, hipStream_t st) {
   if (r.attn == ENC_ATTN_PS_GLOBAL || r.attn == ENC_ATTN_TABLES) {
-    const EncPlanes s(p, r);
-    const bool planes = r.attn == ENC_ATTN_PS_GLOBAL;
-    HGL_TRY(enc_relpos_tables(planes ? nullptr : p.QKV, planes ? s.Qh : nullptr, planes ? s.Ql : nullptr, 3 * r.D, r.B, r.heads, r.S,
-                              r.size, r.hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, p.Th, p.Tw, st));
+    const HglAct Q = enc_qkv(p, r, r.attn == ENC_ATTN_PS_GLOBAL);
+    HGL_TRY(enc_relpos_tables(Q.f32, Q.hi, Q.lo, 3 * r.D, r.B, r.heads, r.S, r.size, r.hd, b.rel_pos_h, b.rel_pos_w, p.relh, p.relw, p.Th,
+                              p.Tw, st));
   }
   // f16x3: the attention writes its output as the fp16 hi+lo pair the projection reads
   return hgl_launch_attention(enc_attn(b, p, r, r.attn), st);
 }
 
-// the block on the split-fp16 path
-int enc_block_x3(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, hipStream_t st) {
+// The block, once: the GEMM operand activations are fp32 rows of the plan's buffers or -- r.x3 -- fp16 hi | lo planes aliasing
+// the same buffers; what else differs between the routes is a condition on r where it differs
+int enc_block(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPlan& p, hipStream_t st) {
+  EncBlockRoute r;
+  HGL_TRY(enc_block_route(w, b, p, r));
   const int D = r.D, T = r.T, M = r.M, ws = r.ws;
-  const EncPlanes s(p, r);
-  // norm1 -> the split GEMM input in window order
+  const HglAct Hw = enc_win(p, r, r.x3), H = hgl_act(p.H, (size_t)T * D, r.x3), F = hgl_act(p.F, (size_t)T * 4 * D, r.x3);
+  // norm1 -> the in-projection's input: in window order (the split path writes there for global attention as well)
+  const HglAct& in = r.x3 || ws > 0 ? Hw : H;
   if (r.gather) {
     // the real tokens written straight to their rows of the padded window layout (the pad rows are never read: the GEMMs
     // below gather the real tokens only)
-    HGL_TRY(hgl_launch_layernorm_split_maps(p.X, b.norm1_w, b.norm1_b, s.Ah, s.Al, T, D, 1e-6f, p.tok_of, p.pad_of, st));
+    HGL_TRY(hgl_launch_layernorm_split_maps(p.X, b.norm1_w, b.norm1_b, Hw.hi, Hw.lo, T, D, 1e-6f, p.tok_of, p.pad_of, st));
   } else if (ws > 0) {
     HGL_TRY(hgl_launch_layernorm(p.X, b.norm1_w, b.norm1_b, p.H, T, D, 1e-6f, st));
-    for (int i = 0; i < p.nb; ++i)
-      HGL_TRY(hgl_launch_win_partition_split(p.H + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, s.Ah + (size_t)i * r.M1 * D,
-                                             s.Al + (size_t)i * r.M1 * D, st));
+    for (int i = 0; i < p.nb; ++i) {
+      const float* h = p.H + (size_t)i * r.T1 * D;
+      const size_t o = (size_t)i * r.M1 * D;
+      HGL_TRY(r.x3 ? hgl_launch_win_partition_split(h, r.g, ws, r.nw, D, Hw.hi + o, Hw.lo + o, st)
+                   : hgl_launch_win_partition(h, r.g, ws, r.nw, D, Hw.f32 + o, st));
+    }
   } else {
-    HGL_TRY(hgl_launch_layernorm_split(p.X, b.norm1_w, b.norm1_b, s.Ah, s.Al, T, D, 1e-6f, st));
+    HGL_TRY(hgl_launch_layernorm_act(p.X, b.norm1_w, b.norm1_b, in, T, D, 1e-6f, st));
   }
   // in-projection, (fp32 qkv | planes) x (every row | the real tokens gathered: a padded row of qkv is the bias).  Planes:
   // q | k | v as fp16 hi / lo planes (the write-out splits; same bytes as the fp32 tensor) for the attention kernel that stages
   // them by LDS-DMA without converting (attention_ps.hip)
-  HglGemm qkv = r.planes ? hgl_gemm_planes_split(s.Ah, s.Al, b.qkv_w, b.qkv_b, s.Qh, s.Ql, M, 3 * D, D)
-                         : hgl_gemm_planes(s.Ah, s.Al, b.qkv_w, b.qkv_b, p.QKV, M, 3 * D, D);
+  const HglAct Q = enc_qkv(p, r, r.planes);
+  HglGemm qkv = hgl_gemm_act(in, b.qkv_w, b.qkv_b, Q, M, 3 * D, D);
   if (r.gather) {
-    HGL_TRY(r.planes ? hgl_launch_fill_rows_split(s.Qh, s.Ql, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st)
-                     : hgl_launch_fill_rows(p.QKV, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st));
+    HGL_TRY(r.planes ? hgl_launch_fill_rows_split(Q.hi, Q.lo, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st)
+                     : hgl_launch_fill_rows(Q.f32, 3 * D, p.pad_list, p.pad_count, p.n_pad_max, b.qkv_b, 3 * D, st));
     qkv.M = T, qkv.amap = qkv.cmap = p.pad_of;
   }
   HGL_TRY(hgl_launch_gemm(qkv, st));
   HGL_TRY(enc_attention(b, p, r, st));
-  const size_t qkv_bytes = (size_t)M * 3 * D * sizeof(float);     // q, k, v are dead after the attention
+  const HglAct att = r.x3 ? Hw : hgl_act(p.O, (size_t)M * D, false);   // where enc_attn put the output
+  const size_t qkv_bytes = (size_t)M * 3 * D * sizeof(float);         // q, k, v are dead after the attention
   if (ws > 0 && !r.gather) {
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(s.Ah, s.Al, b.proj_w, b.proj_b, p.P, M, D, D), st));
+    HGL_TRY(hgl_launch_gemm(hgl_gemm_act(att, b.proj_w, b.proj_b, p.P, M, D, D), st));
     for (int i = 0; i < p.nb; ++i)
       HGL_TRY(hgl_launch_win_unpartition_add(p.X + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.P + (size_t)i * r.M1 * D, st));
   } else {
     // windows: the projection of the real tokens only, written straight back to token order with the residual added
     // (window_unpartition + shortcut, image_encoder.py:178-180); global: every row where it is
-    HglGemm proj = hgl_gemm_planes(s.Ah, s.Al, b.proj_w, b.proj_b, p.X, T, D, D, HGL_ACT_NONE, p.X);
+    HglGemm proj = hgl_gemm_act(att, b.proj_w, b.proj_b, p.X, T, D, D, HGL_ACT_NONE, p.X);
     if (r.gather) proj.amap = p.pad_of, proj.cmap = p.tok_of;
     proj.part = p.QKV, proj.part_bytes = qkv_bytes;
     HGL_TRY(hgl_launch_gemm(proj, st));
   }
-  HGL_TRY(hgl_launch_layernorm_split(p.X, b.norm2_w, b.norm2_b, s.Hh, s.Hl, T, D, 1e-6f, st));
-  HGL_TRY(hgl_launch_gemm(hgl_gemm_planes_split(s.Hh, s.Hl, b.lin1_w, b.lin1_b, s.Fh, s.Fl, T, 4 * D, D, HGL_ACT_GELU), st));
-  // mlp.lin2: few output tiles, K = 4D -> split-K over the idle CUs; the partial sums borrow the qkv buffer
-  static const int splitk_on = HGL_DIAG_SWITCH("HGL_SAM_SPLITK", 1);   // 0 disables (A/B timing)
-  const int ks = splitk_on ? hgl_gemm_f16x3_splitk_factor(T, D, 4 * D) : 1;
-  HglGemm lin2 = hgl_gemm_planes(s.Fh, s.Fl, b.lin2_w, b.lin2_b, p.X, T, D, 4 * D, HGL_ACT_NONE, p.X);
-  lin2.part = p.QKV, lin2.part_bytes = qkv_bytes;
-  if (ks > 1 && (size_t)ks * T * D * sizeof(float) <= qkv_bytes) lin2.ksplit = ks;   // else: whole rounds + a tail where that pays
-  return hgl_launch_gemm(lin2, st);
-}
-
-// the block on the fp32 kernels
-int enc_block_f32(const HglSamBlockW& b, const EncPlan& p, const EncBlockRoute& r, hipStream_t st) {
-  const int D = r.D, T = r.T, M = r.M, ws = r.ws;
-  HGL_TRY(hgl_launch_layernorm(p.X, b.norm1_w, b.norm1_b, p.H, T, D, 1e-6f, st));
-  if (ws > 0)
-    for (int i = 0; i < p.nb; ++i)
-      HGL_TRY(hgl_launch_win_partition(p.H + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.Hw + (size_t)i * r.M1 * D, st));
-  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(ws > 0 ? p.Hw : p.H, b.qkv_w, b.qkv_b, p.QKV, M, 3 * D, D), st));
-  HGL_TRY(enc_attention(b, p, r, st));
-  if (ws > 0) {
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.O, b.proj_w, b.proj_b, p.P, M, D, D), st));
-    for (int i = 0; i < p.nb; ++i)
-      HGL_TRY(hgl_launch_win_unpartition_add(p.X + (size_t)i * r.T1 * D, r.g, ws, r.nw, D, p.P + (size_t)i * r.M1 * D, st));
-  } else {
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.O, b.proj_w, b.proj_b, p.X, T, D, D, HGL_ACT_NONE, p.X), st));
-  }
-  HGL_TRY(hgl_launch_layernorm(p.X, b.norm2_w, b.norm2_b, p.H, T, D, 1e-6f, st));
-  HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.H, b.lin1_w, b.lin1_b, p.F, T, 4 * D, D, HGL_ACT_GELU), st));
-  return hgl_launch_gemm(hgl_gemm_linear(p.F, b.lin2_w, b.lin2_b, p.X, T, D, 4 * D, HGL_ACT_NONE, p.X), st);
-}
-
-int enc_block(const HglSamEncoderW* w, const HglSamBlockW& b, const EncPlan& p, hipStream_t st) {
-  EncBlockRoute r;
-  HGL_TRY(enc_block_route(w, b, p, r));
-  return r.x3 ? enc_block_x3(b, p, r, st) : enc_block_f32(b, p, r, st);
+  const HglMlp mlp{b.norm2_w, b.norm2_b, b.lin1_w, b.lin1_b, b.lin2_w, b.lin2_b, 1e-6f, HGL_ACT_GELU};
+  return hgl_mlp_half(mlp, p.X, H, F, T, D, p.QKV, qkv_bytes, r.ks, st);
 }
 
 // ------------------------------------------------------------------------------ decoder
@@ -442,8 +415,6 @@ int dec_attn(const HglSamDecoderW* w, const HglSamAttnW& a, const float* q, bool
 // The normalised image tokens exist as fp16 hi|lo planes (keysS) and, with the positional encoding added, as a
 // second pair (kpeS): ln256_pe_split emits both, the few-key attention emits its output split, so every large
 // GEMM below reads split operands and nothing is converted in a separate pass.
-struct SplitPair { uint16_t *hi, *lo; };
-inline SplitPair split_view(float* buf, size_t elems) { return SplitPair{(uint16_t*)buf, (uint16_t*)buf + elems}; }
 
 bool dec_x3_ready(const HglSamDecoderW* w) {
   if (!hgl_split_layout() || w->C != 256) return false;   // (f16 mode: the entry points pin three terms)
@@ -517,8 +488,8 @@ DecRoute dec_route(const HglSamDecoderW* w, int P, int n_img, int n_sparse, bool
 
 // steps (2) of a layer (step 0 / 1) and the final attention (step 2): the tokens attend to the image (transformer.py:126-131,
 // :98-104), queries += out_proj(attn): plain, or -- layer 1 and the final attention of the split path -- raw, merged or split
-int dec_t2i(const DecRoute& r, const HglSamDecoderW* w, const HglSamAttnW& a, int step, const DecPlan& p, const SplitPair& keysS,
-            const SplitPair& kpeS, hipStream_t st) {
+int dec_t2i(const DecRoute& r, const HglSamDecoderW* w, const HglSamAttnW& a, int step, const DecPlan& p, const HglAct& keysS,
+            const HglAct& kpeS, hipStream_t st) {
   const int P = r.P, HW = r.HW, T = r.T, C = w->C, I = a.internal, heads = w->heads, hd = I / heads;
   float* const part = r.chunked[step] ? p.atti : nullptr;   // the chunked attention's partials
   const long long sq = (long long)T * I, sk = (long long)HW * I;   // batch strides of the projected tokens / image tokens
@@ -565,7 +536,7 @@ int dec_t2i(const DecRoute& r, const HglSamDecoderW* w, const HglSamAttnW& a, in
 
 // step (4) of layer li: the image attends to the tokens: q = keys+pe, k = queries+pe, v = queries ; keys += out, then norm4
 // (transformer.py:139-150); the image tokens leave it in the form the next step of the route reads
-int dec_i2t(const DecRoute& r, const HglSamDecoderW* w, int li, const DecPlan& p, const SplitPair& keysS, const SplitPair& kpeS,
+int dec_i2t(const DecRoute& r, const HglSamDecoderW* w, int li, const DecPlan& p, const HglAct& keysS, const HglAct& kpeS,
             hipStream_t st) {
   const auto& L = w->layer[li];
   const auto& a = L.i2t;
@@ -615,7 +586,7 @@ int dec_i2t(const DecRoute& r, const HglSamDecoderW* w, int li, const DecPlan& p
     }
     HGL_TRY(lin(p.qpe, C, a.k, nullptr, 0, p.k1, I, P * T, I, C, HGL_ACT_NONE, st));
     HGL_TRY(lin(p.queries, C, a.v, nullptr, 0, p.v1, I, P * T, I, C, HGL_ACT_NONE, st));
-    const SplitPair at = split_view(p.atti, (size_t)P * HW * I);
+    const HglAct at = hgl_act(p.atti, (size_t)P * HW * I, true);
     HglAttn d;
     d.B = P, d.H = heads, d.Sq = HW, d.Sk = T, d.hd = hd, d.scale = 1.0f / sqrtf((float)hd);
     d.q = from_kvq ? p.kp + 2 * I : p.qi, d.k = p.k1, d.v = p.v1;
@@ -669,19 +640,13 @@ int hgl_sam_encode_batch(const HglSamEncoderW* w, const uint8_t* const* resized_
   for (int i = 0; i < nb; ++i)
     HGL_TRY(hgl_launch_sam_preprocess(resized_imgs[i], in_h[i], in_w[i], S, p.img + (size_t)i * 3 * S * S, st));
   // patch embedding + bias + absolute position embedding (image_encoder.py:107-109); the position rows repeat per image
-  if ((w->patch & 3) == 0 && hgl_use_x3(w->patch_w, kd)) {
-    uint16_t* ch = (uint16_t*)p.cols;            // im2col written as fp16 hi | lo planes (same bytes as fp32)
-    uint16_t* cl = ch + (size_t)T * kd;
-    HGL_TRY(hgl_launch_im2col_patch_split(p.img, nb, S, w->patch, ch, cl, st));
-    HglGemm embed = hgl_gemm_planes(ch, cl, w->patch_w, w->patch_b, p.X, T, D, kd, HGL_ACT_NONE, w->pos_embed);
-    embed.rmod = nb > 1 ? T1 : 0;
-    HGL_TRY(hgl_launch_gemm(embed, st));
-  } else {
-    HGL_TRY(hgl_launch_im2col_patch(p.img, nb, S, w->patch, p.cols, st));
-    HglGemm embed = hgl_gemm_linear(p.cols, w->patch_w, w->patch_b, p.X, T1, D, kd, HGL_ACT_NONE, w->pos_embed);
-    embed.batch = nb, embed.sA = (long long)T1 * kd, embed.sC = (long long)T1 * D;    // one batch per image, the table shared
-    HGL_TRY(hgl_launch_gemm(embed, st));
-  }
+  // (split: the im2col matrix written as fp16 hi | lo planes, same bytes as fp32)
+  const bool embed_x3 = (w->patch & 3) == 0 && hgl_use_x3(w->patch_w, kd);
+  HglGemm embed = hgl_gemm_linear(p.cols, w->patch_w, w->patch_b, p.X, embed_x3 ? T : T1, D, kd, HGL_ACT_NONE, w->pos_embed);
+  if (embed_x3) embed.rmod = nb > 1 ? T1 : 0;
+  else embed.batch = nb, embed.sA = (long long)T1 * kd, embed.sC = (long long)T1 * D;    // one batch per image, the table shared
+  HGL_TRY(hgl_linear_split_or_not(embed, embed_x3, p.cols, (size_t)T * kd,
+                                  [&](const HglAct& a) { return hgl_launch_im2col_patch_act(p.img, nb, S, w->patch, a, st); }, st));
   for (int i = 0; i < w->depth; ++i) {
     const int ws = w->blocks[i].window;
     if (ws > 0) {   // every windowed block shares one window size (build_sam.py:55-101)
@@ -692,25 +657,13 @@ int hgl_sam_encode_batch(const HglSamEncoderW* w, const uint8_t* const* resized_
   for (int i = 0; i < w->depth; ++i) HGL_TRY(enc_block(w, w->blocks[i], p, st));
   // neck: conv1x1 -> LayerNorm2d -> conv3x3(pad 1) -> LayerNorm2d, all on NHWC rows
   const bool neck_x3 = hgl_use_x3(w->neck0_w, D) && hgl_use_x3(w->neck2_w, C * 9);
-  if (neck_x3) {   // operands split into the (dead) MLP buffers: H holds T*D, F holds T*4D floats
-    uint16_t* xh = (uint16_t*)p.H;
-    uint16_t* xl = xh + (size_t)T * D;
-    HGL_TRY(hgl_launch_split_f16(p.X, 1.0f, xh, xl, (long long)T * D, st));
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(xh, xl, w->neck0_w, nullptr, p.neckA, T, C, D), st));
-  } else {
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.X, w->neck0_w, nullptr, p.neckA, T, C, D), st));
-  }
+  // (neck_x3: operands split into the (dead) MLP buffers: H holds T*D, F holds T*4D floats)
+  HGL_TRY(hgl_linear_split_or_not(hgl_gemm_linear(p.X, w->neck0_w, nullptr, p.neckA, T, C, D), neck_x3, p.H, (size_t)T * D, st));
   HGL_TRY(hgl_launch_layernorm(p.neckA, w->neck1_w, w->neck1_b, p.neckB, T, C, 1e-6f, st));
   for (int i = 0; i < nb; ++i)
     HGL_TRY(hgl_launch_im2col3x3(p.neckB + (size_t)i * T1 * C, g, C, p.cols3 + (size_t)i * T1 * C * 9, st));
-  if (neck_x3 && (size_t)C * 9 <= (size_t)4 * D) {
-    uint16_t* ch = (uint16_t*)p.F;
-    uint16_t* cl = ch + (size_t)T * C * 9;
-    HGL_TRY(hgl_launch_split_f16(p.cols3, 1.0f, ch, cl, (long long)T * C * 9, st));
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(ch, cl, w->neck2_w, nullptr, p.neckA, T, C, C * 9), st));
-  } else {
-    HGL_TRY(hgl_launch_gemm(hgl_gemm_linear(p.cols3, w->neck2_w, nullptr, p.neckA, T, C, C * 9), st));
-  }
+  HGL_TRY(hgl_linear_split_or_not(hgl_gemm_linear(p.cols3, w->neck2_w, nullptr, p.neckA, T, C, C * 9),
+                                  neck_x3 && (size_t)C * 9 <= (size_t)4 * D, p.F, (size_t)T * C * 9, st));
   HGL_TRY(hgl_launch_layernorm(p.neckA, w->neck3_w, w->neck3_b, emb, T, C, 1e-6f, st));
   return HGL_OK;
 }
@@ -833,9 +786,9 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
     HGL_TRY(hgl_launch_add_rows_bcast(emb, C, w->no_mask, C, n_img * HW, p.keys0, st));   // rows of C, "pe" = no_mask [C]
     HGL_TRY(hgl_launch_add_rows_bcast(p.keys0, n_img > 1 ? sK : 0, w->dense_pe, (long long)HW * C, n_img, p.kpe0, st));
   }
-  (void)hipMemcpyAsync(p.queries, p.tokens, sizeof(float) * P * sQ, hipMemcpyDeviceToDevice, st);
+  HGL_TRY(hgl_copy_d2d(p.queries, p.tokens, sizeof(float) * P * sQ, "sam_decode: copying the tokens", st));
 
-  const SplitPair keysS = split_view(p.keysS, (size_t)P * HW * C), kpeS = split_view(p.kpe, (size_t)P * HW * C);
+  const HglAct keysS = hgl_act(p.keysS, (size_t)P * HW * C, true), kpeS = hgl_act(p.kpe, (size_t)P * HW * C, true);
   // TwoWayAttentionBlock (transformer.py:109-150) x 2
   for (int li = 0; li < 2; ++li) {
     const auto& L = w->layer[li];
@@ -843,7 +796,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
     if (li == 0) {  // skip_first_layer_pe: queries = self_attn(q,q,q), no residual
       HGL_TRY(dec_attn(w, L.self_attn, p.queries, false, T, p.queries, p.queries, false, T, P, p.q1, p.k1, p.v1, p.att,
                        nullptr, 0, p.qpe, st));
-      (void)hipMemcpyAsync(p.queries, p.qpe, sizeof(float) * P * sQ, hipMemcpyDeviceToDevice, st);
+      HGL_TRY(hgl_copy_d2d(p.queries, p.qpe, sizeof(float) * P * sQ, "sam_decode: copying the tokens", st));
     } else {
       HGL_TRY(hgl_launch_add_rows_bcast(p.queries, P * sQ, p.tokens, P * sQ, 1, p.qpe, st));
       HGL_TRY(dec_attn(w, L.self_attn, p.qpe, false, T, p.qpe, p.queries, false, T, P, p.q1, p.k1, p.v1, p.att,
@@ -900,7 +853,7 @@ static int decode_impl(const HglSamDecoderW* w, const float* emb, const float* p
   } else {
     if (r.x3) {
       HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(keysS.hi, keysS.lo, w->up0_w, w->up0_b, p.u1, P * HW, 4 * C4, C), st));
-      const SplitPair u1S = split_view(p.kpe, (size_t)P * HW * 4 * C4);   // kpeS is dead from here on
+      const HglAct u1S = hgl_act(p.kpe, (size_t)P * HW * 4 * C4, true);   // kpeS is dead from here on
       HGL_TRY(hgl_launch_ln_gelu64(p.u1, w->up1.w, w->up1.b, (long long)P * HW * 4, 1e-6f, u1S.hi, u1S.lo, st));
       HGL_TRY(hgl_launch_gemm(hgl_gemm_planes(u1S.hi, u1S.lo, w->up3_w, w->up3_b, p.u2, P * HW * 4, 4 * C8, C4, HGL_ACT_GELU), st));
     } else {
