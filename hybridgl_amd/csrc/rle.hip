@@ -179,6 +179,17 @@ __device__ __forceinline__ void rle_entry_size(const GRP& grp, int s, int& H, in
   H = grp.H[g], W = grp.W[g];
 }
 __device__ __forceinline__ void rle_entry_size(const RleOne& one, int, int& H, int& W) { H = one.H, W = one.W; }
+__device__ __forceinline__ void rle_entry_size(const RlePick& pick, int t, int& H, int& W) { rle_entry_size(pick.pos, t, H, W); }
+
+// The entry whose table row and slot staged row s reads: s itself -- except under RlePick (the paint list), where row t reads the
+// entry its list position names, or nothing (-1, status code 3) when order[t] is outside the image's entries.
+template <class GEO>
+__device__ __forceinline__ int rle_entry_source(const GEO&, int s) { return s; }
+__device__ __forceinline__ int rle_entry_source(const RlePick& pick, int t) {
+  const int g = rle_group_find(pick.pos.first, pick.pos.G, t);
+  const int o = pick.order[t];
+  return (o >= 0 && o < pick.entries[g]) ? pick.entry0[g] + o : -1;
+}
 
 // What a block of the rows kernel needs of the image that owns its tile: size and tiling (rle_tiles' arithmetic; a call of one
 // brings the host's), first entry and tile, byte offset of the first entry, store path (V = 0: the image's own, else V's).
@@ -216,10 +227,18 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_starts_kernel(const uint32_t*
   int32_t* box = BOX ? boxes + (size_t)s * 4 : nullptr;
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
-  const int n = table[(size_t)s * 4], form = table[(size_t)s * 4 + 1];
+  int32_t* row = status + (size_t)s * 4;
+  const int src = rle_entry_source(geo, s);
+  if (src < 0) {      // uniform over the workgroup; RlePick alone
+    if (t == 0) {
+      row[0] = 3; row[1] = 0; row[2] = 0; row[3] = 0;
+      if (BOX) { box[0] = 0; box[1] = 0; box[2] = 0; box[3] = 0; }
+    }
+    return;
+  }
+  const int n = table[(size_t)src * 4], form = table[(size_t)src * 4 + 1];
   const unsigned HW = (unsigned)H * (unsigned)W;      // < 2^31 (checked by the host entry)
   const unsigned plane_words = (HW + 31u) / 32u;
-  int32_t* row = status + (size_t)s * 4;
   if (!rle_entry_usable(n, form, slot_words, plane_words)) {      // uniform over the workgroup
     if (t == 0) {
       row[0] = 2; row[1] = 0; row[2] = 0; row[3] = 0;
@@ -227,7 +246,7 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_starts_kernel(const uint32_t*
     }
     return;
   }
-  const uint32_t* slot = slots + (size_t)s * (size_t)slot_words;
+  const uint32_t* slot = slots + (size_t)src * (size_t)slot_words;
   unsigned area = 0;
   unsigned bx0 = 0x7fffffffu, by0 = 0x7fffffffu, bx1 = 0, by1 = 0;      // the box of this thread's pixels
   int code = 0;
@@ -386,7 +405,10 @@ __device__ __forceinline__ RlePlaneBlock rle_plane_block(const RleSet& grp, unsi
   return {grp.first[g] + (int)k, H, W, HW64, local % q_tiles, (size_t)grp.word0[g] + (size_t)k * Q};
 }
 
-// one thread per plane word: word q = x*HW64 + j of an entry, ceil(Q / 256) workgroups per entry.  GEO: RlePlaneOne or RleSet.
+__device__ __forceinline__ RlePlaneBlock rle_plane_block(const RlePick& pick, unsigned blk) { return rle_plane_block(pick.pos, blk); }
+
+// one thread per plane word: word q = x*HW64 + j of an entry, ceil(Q / 256) workgroups per entry.  GEO: RlePlaneOne, RleSet or
+// RlePick (a row of the list: status, run starts and plane are the row's, table row and slot the named entry's).
 template <class GEO>
 __global__ __launch_bounds__(RLE_THREADS) void rle_plane_kernel(const uint32_t* __restrict__ slots, long long slot_words,
                                                                 const int32_t* __restrict__ table, const uint32_t* __restrict__ E,
@@ -398,9 +420,10 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_plane_kernel(const uint32_t* 
   const unsigned Q = (unsigned)W * (unsigned)HW64;
   if (q >= Q) return;
   unsigned long long c = 0;
-  if (status[(size_t)s * 4] != 2) {
+  const int src = rle_entry_source(geo, s);
+  if (src >= 0 && status[(size_t)s * 4] != 2) {
     const unsigned plane_words = ((unsigned)H * (unsigned)W + 31u) / 32u;
-    c = rle_plane_word(slots + (size_t)s * (size_t)slot_words, table[(size_t)s * 4 + 1], table[(size_t)s * 4],
+    c = rle_plane_word(slots + (size_t)src * (size_t)slot_words, table[(size_t)src * 4 + 1], table[(size_t)src * 4],
                        E + (size_t)s * (size_t)e_stride, plane_words, H, (int)(q / (unsigned)HW64), (int)(q % (unsigned)HW64));
   }
   plane[b.word0 + q] = c;
@@ -1085,6 +1108,17 @@ void rle_stage_set(const uint32_t* slots, long long slot_words, const int32_t* t
   char* base = (char*)E;
   const RleStageWs w = {0, (size_t)((char*)status - base), RLE_NO_BOXES, (size_t)((char*)plane - base)};
   rle_stage_launch(slots, slot_words, table, S, set.blocks, set, set, base, w, (hipStream_t)stream);
+}
+
+// rle_scan.h: the staging of a paint list for rle_paint.hip: the starts kernel without boxes and the plane kernel over the K list
+// positions, each reading the entry it names; status is the caller's own [K,4].  K > 0.
+void rle_stage_picked(const uint32_t* slots, long long slot_words, const int32_t* table, int K, const RlePick& pick, uint32_t* E,
+                      int32_t* status, unsigned long long* plane, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((rle_starts_kernel<false, RlePick>), dim3((unsigned)K), dim3(RLE_THREADS), 0, st, slots, slot_words, table, pick, E,
+                     slot_words + 1, status, (int32_t*)nullptr);
+  hipLaunchKernelGGL(rle_plane_kernel<RlePick>, dim3((unsigned)pick.pos.blocks), dim3(RLE_THREADS), 0, st, slots, slot_words, table,
+                     (const uint32_t*)E, slot_words + 1, (const int32_t*)status, pick, plane);
 }
 
 extern "C" {

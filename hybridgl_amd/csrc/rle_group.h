@@ -3,11 +3,11 @@
 // one description of "a set of entries that belongs to G images" and of its bit planes in the workspace, built image by image
 // through rle_set_add; and the plans -- what the host works out of a decode call's rows (rle_group_plan), a match call's
 // (rle_match_plan), a merge call's (rle_merge_plan), a mask NMS call's (rle_nms_plan), a compaction's (rle_select_plan), a
-// polygon call's (rle_poly_plan) and a clean-up's (rle_clean_plan).  A plan holds the RleSets the plane kernel stages and the structs the other kernels take by
+// polygon call's (rle_poly_plan), a clean-up's (rle_clean_plan) and a paint call's (rle_paint_plan).  A plan holds the RleSets the plane kernel stages and the structs the other kernels take by
 // value (RleGroup, RleMatch, RleMerge, RleNms, RleSelect, RlePoly: their layout is the kernels' and stays); what such a struct
 // repeats of a set is copied out of the set in one place.  Plain C++ without a HIP construct: the .hip files include it, and so
 // do the sanitizer harnesses tests/native/rle_group_sanitize.cpp, rle_match_sanitize.cpp, rle_merge_sanitize.cpp,
-// rle_nms_sanitize.cpp, rle_select_sanitize.cpp and rle_clean_sanitize.cpp.
+// rle_nms_sanitize.cpp, rle_select_sanitize.cpp, rle_clean_sanitize.cpp and rle_paint_sanitize.cpp.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
 #include <stdint.h>
@@ -475,6 +475,84 @@ static inline int rle_clean_plan(const int64_t* images, int G, int S, long long 
     if (plan->set.first[g + 1] > plan->set.first[g] && b > most) most = b;
   }
   plan->cap = seg_cap < most ? seg_cap : most;
+  return 0;
+}
+
+// ---- hgl_rle_paint_device (csrc/rle_paint.hip): an ordered list of K positions, each naming an entry of its image, painted
+// onto the images' RGB canvases.  Only the listed entries are staged: the starts kernel and the plane kernel run over the LIST
+// (one row of run starts, one status row and one plane per position), and RlePick is the geometry they take for it -- the set of
+// the positions, and where a position's entry is found.  A wave of the paint kernel owns one tile of RLE_PAINT_TILE columns x 64
+// rows of one canvas.
+constexpr int RLE_PAINT_TILE = 64;
+
+struct RlePick {
+  RleSet pos;                                   // the positions as a set: first[] = the image's first list position, [G] = K
+  int entry0[RLE_GROUP_MAX], entries[RLE_GROUP_MAX];      // the image's first entry in the caller's set, and how many it owns
+  const int32_t* order;                         // device [K]: position t of image g names entry entry0[g] + order[t]
+};
+
+struct RlePaint {
+  long long pix0[RLE_GROUP_MAX];                // the pixel the image's canvas starts at
+  int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
+  int first[RLE_GROUP_MAX + 1];                 // first list positions; [G] = K
+  unsigned word0[RLE_GROUP_MAX];                // the plane word the image's first position starts at
+  unsigned tile0[RLE_GROUP_MAX];                // the image's first tile (increasing, tile0[0] = 0)
+  int G;
+};
+
+struct RlePaintPlan {
+  RlePick pick;
+  RlePaint p;
+  long long tiles;      // tiles of all canvases: ceil(tiles / 4) workgroups of the paint kernel
+};
+
+// images [G,5] = (H, W, first entry, first list position, pixel offset) -> *plan; 0, or -1 with the reason in why.  Checked:
+// 1 <= G <= 64; S, K >= 0; 0 <= slot_words < 2^31; 0 <= canvas_pixels < 2^60; H*W < 2^31; entries from 0 to S and list positions
+// from 0 to K without a step back; every canvas [p, p + H*W) inside [0, canvas_pixels) and no two overlapping; fewer than 2^32
+// plane words and 2^31 plane blocks over the list; fewer than 2^31 tiles; the 3 * canvas_pixels bytes at `out` apart from those at
+// `base` unless base is 0 (addresses as numbers: nothing is read through them here).
+static inline int rle_paint_plan(const int64_t* images, int G, int S, int K, long long slot_words, long long canvas_pixels,
+                                 uintptr_t base, uintptr_t out, RlePaintPlan* plan, char* why, size_t why_cap) {
+  if (rle_plan_count(G, why, why_cap)) return -1;
+  RLE_PLAN_REQUIRE(S >= 0 && K >= 0, "bad sizes: %d entries, %d list positions", S, K);
+  RLE_PLAN_REQUIRE(slot_words >= 0 && slot_words < (1ll << 31), "slot_words %lld (0 .. 2^31 - 1)", slot_words);
+  RLE_PLAN_REQUIRE(canvas_pixels >= 0 && canvas_pixels < (1ll << 60), "canvas_pixels %lld (0 .. 2^60 - 1)", canvas_pixels);
+  memset(plan, 0, sizeof(*plan));
+  RlePaint* p = &plan->p;
+  long long lo[RLE_GROUP_MAX], hi[RLE_GROUP_MAX];      // the pixel extent [lo, hi) of every canvas
+  for (int g = 0; g < G; ++g) {
+    const int64_t* r = images + 5 * g;
+    const long long H = r[0], W = r[1], e = r[2], k = r[3], o = r[4];
+    const long long e_next = rle_row_next(r, 5, 2, g, G, S), k_next = rle_row_next(r, 5, 3, g, G, K);
+    if (rle_plan_size(g, H, W, why, why_cap) || rle_plan_entries(g, e, e_next, S, "", "S", why, why_cap) ||
+        rle_plan_entries(g, k, k_next, K, "list ", "K", why, why_cap))
+      return -1;
+    RLE_PLAN_REQUIRE(o >= 0 && o <= canvas_pixels && H * W <= canvas_pixels - o,
+                     "image %d: pixels %lld .. %lld lie outside the %lld of the canvas", g, o, o + H * W, canvas_pixels);
+    lo[g] = o;
+    hi[g] = o + H * W;
+    for (int f = 0; f < g; ++f)
+      RLE_PLAN_REQUIRE(hi[f] <= lo[g] || hi[g] <= lo[f], "the canvases of images %d and %d overlap", f, g);
+    const int over = rle_set_add(&plan->pick.pos, g, H, W, k, k_next);
+    RLE_PLAN_REQUIRE(!(over & RLE_SET_WORDS), "%s", RLE_SET_WORDS_WHY);
+    RLE_PLAN_REQUIRE(!(over & RLE_SET_BLOCKS), "too many list positions (%d) for one launch", K);
+    plan->pick.entry0[g] = (int)e;
+    plan->pick.entries[g] = (int)(e_next - e);
+    p->pix0[g] = o;
+    p->H[g] = (int)H;
+    p->W[g] = (int)W;
+    p->first[g] = (int)k;
+    p->word0[g] = plan->pick.pos.word0[g];
+    p->tile0[g] = (unsigned)plan->tiles;
+    plan->tiles += ((W + RLE_PAINT_TILE - 1) / RLE_PAINT_TILE) * ((H + 63) / 64);
+    RLE_PLAN_REQUIRE(plan->tiles < (1ll << 31), "too many tiles (%lld) for one launch", plan->tiles);
+  }
+  p->first[G] = K;
+  p->G = G;
+  const unsigned long long bytes = 3ull * (unsigned long long)canvas_pixels;
+  RLE_PLAN_REQUIRE(base == 0 || bytes == 0 || (unsigned long long)base + bytes <= (unsigned long long)out ||
+                       (unsigned long long)out + bytes <= (unsigned long long)base,
+                   "out overlaps base");
   return 0;
 }
 

@@ -200,5 +200,11 @@ inline RleStageWs rle_stage_ws(size_t* p, int S, long long slot_words, long long
 struct RleSet;
 void rle_stage_set(const uint32_t* slots, long long slot_words, const int32_t* table, int S, const RleSet& set, uint32_t* E,
                    int32_t* status, unsigned long long* plane, void* stream);
+// The same two kernels over a paint list (RlePick, rle_group.h): one row of run starts, one status row and one plane per list
+// position, read from the entry the position names (status code 3 and an empty plane when it names none).  Two launches, K > 0.
+// Defined in rle.hip; called by rle_paint.hip.
+struct RlePick;
+void rle_stage_picked(const uint32_t* slots, long long slot_words, const int32_t* table, int K, const RlePick& pick, uint32_t* E,
+                      int32_t* status, unsigned long long* plane, void* stream);
 
 #endif  // HGL_RLE_SCAN_H

@@ -96,6 +96,13 @@ def default_argument_parser():
     p.add_argument("--score_masks", default="", metavar="DIR",
                    help="score the predictions a run saved with --save_masks DIR against the dataset's ground truth, without any "
                         "model or checkpoint (the dataset flags as in that run); exits non-zero when a stored count differs")
+    p.add_argument("--render_masks", default="", metavar="DIR",
+                   help="paint the predictions a run saved with --save_masks DIR over the dataset's images, on the device, without "
+                        "any model (the dataset flags as in that run): one PNG per sentence under --render_out")
+    p.add_argument("--render_out", default="", metavar="OUT", help="--render_masks: the directory of the {index:06d}_{sentence}.png files")
+    p.add_argument("--render_which", default="final", choices=["final", "pure", "both"],
+                   help="--render_masks: the winner with spatial guidance (the demo's blue), the pure CLIP winner, or pure (red) then final")
+    p.add_argument("--render_limit", type=int, default=0, metavar="N", help="--render_masks: stop after N pictures (0 = all)")
     p.add_argument("--ensemble_masks", nargs="+", default=[], metavar="DIR",
                    help="vote two or more runs saved with --save_masks into one prediction, mask by mask on the device "
                         "(predictions.ensemble: ops.rle_merge on the strings' runs), score it against the dataset's ground truth "
@@ -588,6 +595,76 @@ def score_masks_main(args, dev):
     return m
 
 
+RENDER_GROUP = 64      # pictures per ops.rle_paint call: the library's group limit
+
+
+def render_masks(args, dev):
+    """--render_masks DIR --render_out OUT: every saved sentence (--save_masks) painted over its image -- no model is built.  The
+    records come from predictions.load, the images from the dataset the flags name (the items as a run builds them), the
+    strings become runs on the device (ops.rle_from_strings) and RENDER_GROUP pictures leave one ops.rle_paint call; the PNG
+    files are written on the host (render.save_png).  --render_which both: the pure winner in red, then the final one in the
+    demo's blue over it.  Raises SystemExit for a record whose size differs from its image's, naming its key.  Returns the paths."""
+    import numpy as np
+    from . import ops, render
+    from . import predictions as P
+    resolve_defaults(args, loop=False)
+    if not args.render_out:
+        raise SystemExit("--render_masks needs --render_out OUT")
+    by_key = {(r["index"], r["sentence"]): r for r in P.load(args.render_masks)}
+    which = {"final": ["final"], "pure": ["pure"], "both": ["pure", "final"]}[args.render_which]
+    rows = {"final": ops.rle_paint_style(**render.DEMO_STYLE), "pure": ops.rle_paint_style(**render.PURE_STYLE)}
+    if args.render_which == "pure":
+        rows["pure"] = rows["final"]      # alone, either winner wears the demo's style
+    os.makedirs(args.render_out, exist_ok=True)
+    paths, pending = [], []
+
+    def flush():
+        if not pending:
+            return
+        strings = [rec[w] for _, rec, _ in pending for w in which]
+        buf, _, n_counts = ops.rle_strings_pack(strings)
+        S = len(strings)
+        d = buf.to(dev, non_blocking=True)
+        slots, table, _ = ops.rle_from_strings(d[8 * (S + 1):], d[:8 * (S + 1)].view(torch.int64), S, max(int(n_counts.max()), 1))
+        counts = [len(which)] * len(pending)
+        pics, _, status = ops.rle_paint(slots, table, [tuple(im.shape[:2]) for _, _, im in pending], counts,
+                                        np.tile(np.arange(len(which), dtype=np.int32), len(pending)), counts,
+                                        np.stack([rows[w] for _ in pending for w in which]), base=[im for _, _, im in pending])
+        codes = status[:, 0].cpu().numpy().reshape(len(pending), len(which))
+        for (key, _, _), pic, code in zip(pending, pics, codes):
+            if code.any():
+                raise SystemExit(f"--render_masks: index {key[0]} sentence {key[1]}: the saved string does not decode to a mask of "
+                                 f"the stated size (code {int(code.max())})")
+            paths.append(os.path.join(args.render_out, f"{key[0]:06d}_{key[1]}.png"))
+            render.save_png(paths[-1], pic)
+        pending.clear()
+
+    _, jobs, make = dataset_items(args, dev, 0, 1, sam_img_size=0, gem=False)
+    full = lambda: bool(args.render_limit) and len(paths) + len(pending) >= args.render_limit
+    for i in jobs:
+        if full():
+            break
+        ref = make(i)
+        if ref is None:
+            continue
+        index = ref.index if ref.index is not None else i
+        for j in range(len(ref.sentences)):
+            rec = by_key.get((index, j))
+            if rec is None:
+                continue
+            if [int(v) for v in rec["size"]] != [int(v) for v in ref.sam_img.shape[:2]]:
+                raise SystemExit(f"--render_masks: index {index} sentence {j}: the record's size {list(rec['size'])} differs from "
+                                 f"the image's {list(ref.sam_img.shape[:2])}")
+            if full():
+                break
+            pending.append(((index, j), rec, ref.sam_img))
+            if len(pending) == RENDER_GROUP:
+                flush()
+    flush()
+    print(f"painted {len(paths)} of {len(by_key)} saved sentences from {args.render_masks} into {args.render_out}")
+    return paths
+
+
 def check_ensemble_flags(args):
     """what --ensemble_masks needs and what it does not go with"""
     dirs = list(getattr(args, "ensemble_masks", None) or [])
@@ -793,6 +870,11 @@ def main(args):
             raise SystemExit("--score_masks runs on one rank: start it without a launcher (world size 1)")
         torch.cuda.set_device(dev)
         return score_masks_main(args, dev)
+    if getattr(args, "render_masks", ""):      # likewise: files and the dataset's images only
+        if world > 1:
+            raise SystemExit("--render_masks runs on one rank: start it without a launcher (world size 1)")
+        torch.cuda.set_device(dev)
+        return render_masks(args, dev)
     if getattr(args, "proposal_ceiling", ""):      # likewise: the store's files and ground truth only
         if world > 1:
             raise SystemExit("--proposal_ceiling runs on one rank: start it without a launcher (world size 1)")

@@ -924,6 +924,105 @@ def rle_remove_small_regions(slots, table, sizes, counts, area_thresh, mode="bot
     return out_slots, out_table, boxes, result
 
 
+PAINT_FILL, PAINT_OUTLINE = 1 << 24, 1 << 25
+_paint_pool = None      # the pinned staging of host paint lists: a buffer returns with the event behind its upload
+
+
+def rle_paint_style(fill=None, a=1.0, b=0.0, outline=None):
+    """One style row of rle_paint, uint32 [4]: fill / outline are (R, G, B) or None (the flag is then clear); a pixel of the mask
+    becomes sat_u8(rint(pixel * a + fill * b)) per channel, a pixel of the mask's edge the outline colour."""
+    import numpy as np
+    rgb = lambda c: 0 if c is None else (int(c[0]) & 255) << 16 | (int(c[1]) & 255) << 8 | (int(c[2]) & 255)
+    bits = np.array([a, b], dtype=np.float32).view(np.uint32)
+    return np.array([rgb(fill) | (PAINT_FILL if fill is not None else 0) | (PAINT_OUTLINE if outline is not None else 0),
+                     bits[0], bits[1], rgb(outline)], dtype=np.uint32)
+
+
+def rle_paint_layout(sizes, counts, order_counts):
+    """(images [G,5] int64 = H, W, first entry, first list position, pixel offset; total pixels) of a group's canvases packed
+    back to back: image g owns counts[g] entries and order_counts[g] list positions"""
+    return _rle_rows("rle_paint_layout", sizes, counts, order_counts, lambda g, H, W, n, m: H * W, running=True)
+
+
+def rle_paint(slots, table, sizes, counts, order, order_counts, style, base=None, out=None, labels=False):
+    """Entries of an encoded set painted over their images (hgl_rle_paint_device on the current stream, no synchronisation): the
+    S entries of slots / table belong to G = len(sizes) <= 64 images, counts[g] consecutive entries of sizes[g] = (H, W), and
+    the K list positions likewise, order_counts[g] each.  order [K]: position t of image g paints the image's entry order[t];
+    style [K,4]: one rle_paint_style row per position (one row alone serves every position).  Either is a host sequence / array --
+    both then travel in ONE pinned staging buffer and one copy -- or an int32 device tensor, taken as it is: the kept indices of
+    rle_nms or the tail's winner index can be the list with no read-back.  base: None (black canvases), a contiguous uint8 device
+    tensor of the packed canvases (3 * sum(H*W) bytes, RGB, row-major), or a list of G [H,W,3] uint8 device tensors.
+    Returns (images: G uint8 views [H,W,3] of one buffer (`out`: a contiguous uint8 device tensor of exactly 3 * sum(H*W)
+    elements, every byte of which is written); labels: G int32 views [H,W] -- the image-local list position that last changed
+    the pixel, -1 for none -- or None; status [K,4] int32 = code, area, edge pixels, 0 (include/hybridgl.h)).  No mask becomes
+    bytes.  ValueError, before anything is uploaded, for what the plan refuses."""
+    import numpy as np
+    global _paint_pool
+    lib = _lib.load()
+    on_dev = [torch.is_tensor(v) and v.is_cuda for v in (order, style)]
+    K = int(order.numel()) if on_dev[0] else len(order)
+    ((sp, sw, tp, S), _), images, total, G = _rle_group("rle_paint", [(slots, table), K], rle_paint_layout, sizes, counts, order_counts)
+    dev = slots.device
+    if not 1 <= G <= 64 or any(int(H) <= 0 or int(W) <= 0 or int(H) * int(W) >= 1 << 31 for H, W in sizes):
+        raise ValueError(f"rle_paint: {G} images of sizes {list(sizes)} (1 .. 64 images, 0 < H*W < 2^31)")
+    need = lib.hgl_rle_paint_workspace_bytes(images.ctypes.data, G, S, sw, K, total)
+    if K and not need:
+        raise ValueError("rle_paint: the library refuses this geometry (too many plane words or tiles for one call)")
+    if isinstance(base, (list, tuple)):
+        if len(base) != G or any(tuple(b.shape) != (int(H), int(W), 3) for b, (H, W) in zip(base, sizes)):
+            raise ValueError("base: expected one [H, W, 3] tensor per image")
+        base = torch.cat([b.reshape(-1) for b in base])
+    if base is not None:
+        base = _out(base, 3 * total, torch.uint8, dev, "base")
+    flat = _out(out, 3 * total, torch.uint8, dev, "out")
+    if base is not None and base.data_ptr() < flat.data_ptr() + flat.numel() and flat.data_ptr() < base.data_ptr() + base.numel():
+        raise ValueError("out overlaps base")
+    # the host halves of the list: one pinned buffer, one copy
+    host = []
+    if not on_dev[0]:
+        host.append(np.asarray(order, dtype=np.int32).reshape(-1))
+    if not on_dev[1]:
+        rows = np.asarray(style, dtype=np.uint32)
+        rows = np.broadcast_to(rows, (K, 4)) if rows.ndim == 1 else rows
+        if rows.shape != (K, 4):
+            raise ValueError(f"style: expected [{K}, 4] words, got {rows.shape}")
+        host.append(rows.reshape(-1).view(np.int32) if rows.flags.c_contiguous else np.ascontiguousarray(rows).reshape(-1).view(np.int32))
+    parts = []
+    if host and K:
+        if _paint_pool is None:
+            from .staging import PinnedPool
+            _paint_pool = PinnedPool(floor=1024)
+        n = sum(h.size for h in host)
+        pin = _paint_pool.take(n, torch.int32)
+        pin.numpy()[:n] = np.concatenate(host)
+        up = torch.empty(n, dtype=torch.int32, device=dev)
+        up.copy_(pin[:n], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        _paint_pool.give(pin, ev)
+        a = 0
+        for h in host:
+            parts.append(up[a:a + h.size])
+            a += h.size
+    order_d = order if on_dev[0] else (parts.pop(0) if K else None)
+    style_d = style if on_dev[1] else (parts.pop(0) if K else None)
+    op = sp_ = None
+    if K:
+        if order_d.numel() != K or style_d.numel() != 4 * K:
+            raise ValueError(f"rle_paint: {K} list positions, {order_d.numel()} indices and {style_d.numel()} style words")
+        op, sp_ = _dev(order_d, torch.int32, "order"), _dev(style_d, torch.int32, "style")
+    status = torch.empty((K, 4), dtype=torch.int32, device=dev)      # one tensor of its own: no flat buffer to share, no block
+    lab = torch.empty(total, dtype=torch.int32, device=dev) if labels else None
+    ws = workspace(need, dev, "rle")
+    check(lib.hgl_rle_paint_device(sp if S else None, sw, tp if S else None, S, op, sp_, K, images.ctypes.data, G,
+                                   None if base is None else base.data_ptr(), flat.data_ptr(), total,
+                                   None if lab is None else lab.data_ptr(), status.data_ptr() if K else None,
+                                   ws.data_ptr(), ws.numel(), _stream()), "hgl_rle_paint_device")
+    views = lambda buf, c: [buf[int(o) * c:(int(o) + int(H) * int(W)) * c].view(*((int(H), int(W), 3) if c == 3 else (int(H), int(W))))
+                            for H, W, _, _, o in images]
+    return views(flat, 3), (views(lab, 1) if labels else None), status
+
+
 POLY_RULE = {"once": 0, "any": 1}
 
 

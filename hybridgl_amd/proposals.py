@@ -999,6 +999,49 @@ def clean(src, dst, min_area, nms_thresh=0.7, group=16, device=None):
     return _rewrite("clean", src, dst, group, "cleaned", {"min_area": min_area, "nms_thresh": nms_thresh}, ["changed"], cleaned)
 
 
+IMAGE_NAMES = ("{0}.png", "{0}.jpg", "COCO_train2014_{0:012d}.jpg", "COCO_train2014_{0:012d}.png")
+
+
+def render(src, out, images, limit=0, group=16, device=None):
+    """Pictures of a proposal store: every stored proposal of an image painted over it in palette colours with outlines, the
+    largest area first and the stored order among equals, so that small proposals stay visible (demo.paint_all's style).  The
+    strings' runs cross the bus and `group` images leave one ops.rle_paint call; no entry is decoded to a byte mask.  images:
+    the directory that holds the image files, named by the image id (IMAGE_NAMES); out: the directory of the {image_id}.png
+    files.  ValueError for an image file that is missing or whose size differs from the records'.  Returns the paths."""
+    from PIL import Image
+    from . import render as R
+    src = _store(src)
+    if not os.path.isdir(src.directory):
+        raise ValueError(f"render: {src.directory}: no such directory")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    os.makedirs(out, exist_ok=True)
+    ids = src.image_ids()
+    if limit:
+        ids = ids[:int(limit)]
+    paths = []
+    step = min(max(int(group), 1), 64)
+    for c0 in range(0, len(ids), step):
+        chunk, pics, sized, order, styles = ids[c0:c0 + step], [], [], [], []
+        for iid in chunk:
+            path = next((p for p in (os.path.join(images, n.format(iid)) for n in IMAGE_NAMES) if os.path.exists(p)), None)
+            if path is None:
+                raise ValueError(f"render: no image file for image {iid} under {images}")
+            pics.append(R._image_u8(np.array(Image.open(path).convert("RGB")), device))
+            recs = src.records(iid)
+            sized.append(_record_runs(src, iid, recs, expect=tuple(int(v) for v in pics[-1].shape[:2])))
+            order += sorted(range(len(recs)), key=lambda k: (-int(recs[k]["area"]), k))
+            styles.append(R.proposal_styles(len(recs)))
+        counts = [len(runs) for _, runs in sized]
+        slots, table = _pack([r for _, runs in sized for r in runs], device)
+        painted, _, status = ops.rle_paint(slots, table, [tuple(p.shape[:2]) for p in pics], counts, np.asarray(order, dtype=np.int32),
+                                           counts, np.concatenate(styles).reshape(-1, 4), base=pics)
+        _check_decoded(src, chunk, counts, status.cpu().numpy())
+        for iid, pic in zip(chunk, painted):
+            paths.append(os.path.join(out, f"{iid}.png"))
+            R.save_png(paths[-1], pic)
+    return paths
+
+
 def _jsonable(report):
     return {"summary": report["summary"], "per_image": [dict(v, image_id=k) for k, v in report["per_image"].items()]}
 
@@ -1025,7 +1068,19 @@ def main(argv=None):
     k.add_argument("--min_area", type=int, required=True, help="a hole or an island of fewer pixels is filled / dropped")
     k.add_argument("--nms_thresh", type=float, default=0.7, help="the box NMS that follows (the generator's max(box_nms_thresh, crop_nms_thresh))")
     k.add_argument("--json", default="", metavar="OUT", help="also write the per-image counts here")
+    r = sub.add_parser("render", help="every stored proposal of an image painted over it, on the device: one PNG per image")
+    r.add_argument("dir_in")
+    r.add_argument("out")
+    r.add_argument("--images", required=True, metavar="ROOT", help="the directory of the image files, named by the image id")
+    r.add_argument("--limit", type=int, default=0, metavar="N", help="the first N images of the store (0 = all)")
     args = p.parse_args(argv)
+    if args.cmd == "render":
+        try:
+            paths = render(args.dir_in, args.out, args.images, args.limit)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"hybridgl_amd.proposals: {e}")
+        print(f"painted {len(paths)} images of {args.dir_in} into {args.out}")
+        return 0
     if args.cmd in ("thin", "clean"):
         try:
             if args.cmd == "thin":

@@ -1009,6 +1009,43 @@ int hgl_rle_to_strings_device(const uint32_t* slots, long long slot_words, const
                               long long cap, int64_t* offsets, int32_t* status, void* stream);
 int hgl_rle_from_strings_device(const uint8_t* bytes, long long total_bytes, const int64_t* offsets, int S, uint32_t* slots,
                                 long long slot_words, int32_t* table, int32_t* status, void* stream);
+/* Encoded masks painted onto RGB canvases on the DEVICE (csrc/rle_paint.hip): any ordered selection of an encoded set composited
+ * over the images it belongs to, for a whole group of images of different sizes -- the paint-side sibling of
+ * hgl_rle_decode_group_device.  It works from the runs: no byte mask exists and nothing is read back.  Asynchronous on `stream`; no
+ * host synchronisation, allocation or atomics; two calls give the same bytes; FOUR launches whatever G, K and the sizes are
+ * (starts and planes of the listed entries, edge counts, paint), ONE for K = 0, which still copies the bases.
+ * Set = (slots, slot_words, table, S): what hgl_rle_encode_device hands out, forms 0 and 1, with the code 0 / 1 / 2 rules of
+ * hgl_rle_decode_device.  S may be 0 (the set's pointers are then not read).
+ * images_host: HOST [G,5] int64, G <= 64, row g = (H_g, W_g, first entry e_g, first list position k_g, pixel offset p_g).  Entries
+ * with the rules of hgl_rle_decode_group_device: from 0 to S without a step back, an image may own none, H*W < 2^31.  List
+ * positions from 0 to K without a step back; an image may own none and is then a plain copy of its base.  Image g's canvas is
+ * H_g*W_g RGB pixels, row-major HWC: it sits at byte 3*p_g of base and of out and at element p_g of labels; the extents
+ * [p_g, p_g + H_g*W_g) must lie inside [0, canvas_pixels) and must not overlap; out must not overlap base.  slot_words outside
+ * 0 .. 2^31 - 1, a negative S or K and anything else above is HGL_EINVAL with the reason in hgl_last_error() and nothing is enqueued.
+ * The array is read before the call returns.
+ * order: device [K] int32.  Position t of image g paints entry e_g + order[t] when 0 <= order[t] < n_g; the same entry may be
+ * listed several times.  Only listed entries are staged as planes: one winner out of 64 proposals touches one entry.
+ * style: device [K,4] uint32, one row per position.  Word 0: the fill colour 0x00RRGGBB, bit 24 = fill, bit 25 = outline; words 1
+ * and 2: the bit patterns of the fp32 weights a and b; word 3: the outline colour 0x00RRGGBB.
+ * Pixel rule.  The positions of an image are applied in list order, each on the result of the one before.  M = the mask the
+ * decoder would write for the entry; edge = M & ~(up & down & left & right), a neighbour outside the image counting as clear.
+ * Fill: every channel c of every pixel of M becomes sat_u8(rint(f32(c)*a + f32(colour_c)*b)) -- both products and the sum each
+ * rounded to fp32, no fused multiply-add, rint to nearest even, the clamp to [0, 255], a NaN (inf - inf) to 0.  Outline:
+ * afterwards every pixel of edge becomes the outline colour.  A position with neither flag paints nothing.
+ * base: device, 3*canvas_pixels bytes, or NULL for black canvases.  out: device, 3*canvas_pixels bytes.  labels: device
+ * [canvas_pixels] int32 or NULL: the image-local list position (t - k_g) of the last position that changed the pixel (fill on M,
+ * outline on edge), -1 for none.  Every byte of every extent of out and, when given, every element of every extent of labels is
+ * written; nothing outside the extents is.
+ * status: device [K,4] int32 = (code, area, edge pixels, 0): area and edge pixels are those of M, whatever the flags.
+ *   0 / 1 / 2   as the decoder's status; a code-2 position paints nothing: (2, 0, 0, 0)
+ *   3           order[t] is outside the image's entries: (3, 0, 0, 0)
+ *   4           a or b is not finite; the position paints nothing: (4, area, 0, 0)
+ * ws: hgl_rle_paint_workspace_bytes for the same geometry (HGL_EWORKSPACE when smaller): one row of run starts and one set of
+ * bit planes per list position.  The query returns 0 for a geometry the call refuses and for K = 0, which takes ws = NULL. */
+size_t hgl_rle_paint_workspace_bytes(const int64_t* images_host, int G, int S, long long slot_words, int K, long long canvas_pixels);
+int hgl_rle_paint_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S, const int32_t* order,
+                         const uint32_t* style, int K, const int64_t* images_host, int G, const uint8_t* base, uint8_t* out,
+                         long long canvas_pixels, int32_t* labels, int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -64,7 +64,16 @@
              events, (d) minimum, median and maximum string length per mask; medians of --reps repetitions, the two paths
              alternated; equality of the two paths is checked before any timing; writes profiles/rle_strings_bench.json as well
 
+--paint      pictures of encoded masks (ops.rle_paint) for 64 images of 480 x 640 with 64 stored proposals each: one winner per image
+             in the demo's style, then every proposal of every image in palette style with outlines, largest first; (a) the
+             kernels alone under HIP events (the list already on the device), (b) the wall time of the call itself and of the call
+             to finished pictures, against the path it replaces: sam.rles_to_masks of the listed entries, the masks to the host,
+             the blend in numpy, the pictures uploaded (all 64 images for the winners, 2 images for the proposals, per image);
+             medians of --reps repetitions; equality of the two paths is checked before any timing; writes
+             profiles/rle_paint_bench.json as well
+
     python tools/rle_bench.py [--reps 30] [--evaluator --steps 64]
+    python tools/rle_bench.py --paint [--reps 30]
     python tools/rle_bench.py --strings [--reps 30]
     python tools/rle_bench.py --decode [--reps 30]
     python tools/rle_bench.py --match [--reps 30]
@@ -85,7 +94,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from hybridgl_amd import ops, synth
+from hybridgl_amd import _lib, ops, synth
 from hybridgl_amd import sam as hsam
 
 
@@ -629,6 +638,72 @@ def strings_leg(dev, reps, S=64, H=640, W=640):
             "kernels_rle_to_strings": k_out, "kernel_rle_from_strings": k_in}
 
 
+def paint_leg(dev, reps, G=64, H=480, W=640, N=64, host_images=2):
+    """pictures of encoded masks, device path against host path (see --paint at the top)"""
+    from hybridgl_amd import render
+    SW = 4096
+    f32 = np.float32
+    shapes = blobs(N, H, W, 7)
+    slots1, table1 = ops.rle_encode(torch.from_numpy(shapes).to(dev), None, SW)      # three ellipses: at most 6 W + 1 counts
+    assert int(table1[:, 1].max()) == 0
+    slots, table = slots1.repeat(G, 1), table1.repeat(G, 1)                              # every image owns N entries
+    sizes, counts = [(H, W)] * G, [N] * G
+    base = torch.from_numpy(np.random.default_rng(3).integers(0, 256, (G * H * W * 3,), dtype=np.uint8)).to(dev)
+    out = torch.empty_like(base)
+    area = table1[:, 2].cpu().numpy()
+    legs = {"winner": (np.array([(5 * g) % N for g in range(G)], np.int32), [1] * G, ops.rle_paint_style(**render.DEMO_STYLE)[None].repeat(G, 0)),
+            "all_proposals": (np.tile(np.argsort(-area, kind="stable").astype(np.int32), G), [N] * G, np.tile(render.proposal_styles(N), (G, 1)))}
+    host_counts = hsam.counts_from_set(*ops.rle_split(torch.cat([table1.reshape(-1), slots1.reshape(-1)]).cpu().numpy(), N, SW), H, W)
+
+    def edge(m):
+        p = np.zeros((H + 2, W + 2), bool)
+        p[1:-1, 1:-1] = m
+        return m & ~(p[:-2, 1:-1] & p[2:, 1:-1] & p[1:-1, :-2] & p[1:-1, 2:])
+
+    def host_path(order, order_counts, style, images):
+        """what a caller had before the entry: the listed masks to pixels (sam.rles_to_masks), to the host, the blend in numpy,
+        the pictures uploaded"""
+        k, pics = 0, []
+        for g in range(images):
+            ks = range(k, k + order_counts[g])
+            k += order_counts[g]
+            m = hsam.rles_to_masks([{"size": [H, W], "counts": host_counts[int(order[t])]} for t in ks], dev).cpu().numpy().astype(bool)
+            img = base[g * H * W * 3:(g + 1) * H * W * 3].view(H, W, 3).cpu().numpy().copy()
+            for t, mask in zip(ks, m):
+                w0, a, b, w3 = int(style[t, 0]), style[t, 1:2].view(f32)[0], style[t, 2:3].view(f32)[0], int(style[t, 3])
+                if w0 & ops.PAINT_FILL:
+                    col = np.array([(w0 >> 16) & 255, (w0 >> 8) & 255, w0 & 255], f32)
+                    img[mask] = np.clip(np.rint(img[mask].astype(f32) * a + col * b), 0, 255).astype(np.uint8)
+                if w0 & ops.PAINT_OUTLINE:
+                    img[edge(mask)] = [(w3 >> 16) & 255, (w3 >> 8) & 255, w3 & 255]
+            pics.append(torch.from_numpy(img).to(dev))
+        torch.cuda.synchronize()
+        return pics
+
+    rec = {"G": G, "H": H, "W": W, "proposals_per_image": N, "slot_words": SW, "reps": reps}
+    for name, (order, oc, style) in legs.items():
+        d_order, d_style = torch.from_numpy(order).to(dev), torch.from_numpy(style.view(np.int32).copy()).to(dev)
+        call = lambda: ops.rle_paint(slots, table, sizes, counts, order, oc, style, base=base, out=out)
+        pics = call()[0]
+        want = host_path(order, oc, style, host_images)
+        torch.cuda.synchronize()
+        assert all(torch.equal(p, w) for p, w in zip(pics, want)), name      # the two paths paint the same bytes
+        kernels = device_spread(lambda: ops.rle_paint(slots, table, sizes, counts, d_order, oc, d_style, base=base, out=out), reps)
+        wall = host_ms(call, reps)                                                        # the call itself: asynchronous
+        done = host_ms(lambda: (call(), torch.cuda.synchronize()), reps)                  # ... to finished pictures on the device
+        n_host = host_images if name == "all_proposals" else G
+        t_host = host_ms(lambda: host_path(order, oc, style, n_host), min(reps, 5), warm=1)
+        K = int(sum(oc))
+        rows = ops.rle_paint_layout(sizes, counts, oc)[0]      # kept alive across the call: the library reads it through the pointer
+        need = _lib.load().hgl_rle_paint_workspace_bytes(rows.ctypes.data, G, G * N, SW, K, G * H * W)
+        rec[name] = {"list_positions": K, "kernels": kernels, "call_ms": round(wall, 4), "call_and_sync_ms": round(done, 4),
+                     "host_path_images": n_host, "host_path_ms": round(t_host, 3), "host_path_ms_per_image": round(t_host / n_host, 3),
+                     "device_ms_per_image": round(done / G, 4), "workspace_bytes": int(need),
+                     "canvas_bytes_read_plus_written": 2 * 3 * G * H * W,
+                     "canvas_GBps_at_kernel_median": round(2 * 3 * G * H * W / (kernels["median_us"] * 1e-6) / 1e9, 1)}
+    return rec
+
+
 def polygons_leg(dev, reps, cli_images):
     import shutil
     import subprocess
@@ -738,6 +813,8 @@ def main():
                     help="measure rle_remove_small_regions against decode -> clean -> encode; writes profiles/rle_clean_bench.json")
     ap.add_argument("--strings", action="store_true",
                     help="measure the device string codec against the host codec per record; writes profiles/rle_strings_bench.json")
+    ap.add_argument("--paint", action="store_true",
+                    help="measure rle_paint against decode -> host blend -> upload; writes profiles/rle_paint_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
@@ -748,6 +825,14 @@ def main():
     if args.polygons:
         out = {"polygons": polygons_leg(dev, args.reps, args.cli_images), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_polygons_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
+    if args.paint:
+        out = {"paint": paint_leg(dev, args.reps), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_paint_bench.json")
         with open(path, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
