@@ -248,6 +248,8 @@ PROTOTYPES = {
     "hgl_rle_from_strings_device": (_I, [_VP, _LL, _VP, _I, _VP, _LL, _VP, _VP, _VP]),
     "hgl_rle_paint_workspace_bytes": (_SZ, [_VP, _I, _I, _LL, _I, _LL]),
     "hgl_rle_paint_device": (_I, [_VP, _LL, _VP, _I, _VP, _VP, _I, _VP, _I, _VP, _VP, _LL, _VP, _VP, _VP, _SZ, _VP]),
+    "hgl_heat_paint_workspace_bytes": (_SZ, [_VP, _I, _LL, _LL]),
+    "hgl_heat_paint_device": (_I, [_VP, _LL, _VP, _I, _VP, _VP, _VP, _LL, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 _lib = None

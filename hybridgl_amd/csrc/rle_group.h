@@ -7,7 +7,9 @@
 // value (RleGroup, RleMatch, RleMerge, RleNms, RleSelect, RlePoly: their layout is the kernels' and stays); what such a struct
 // repeats of a set is copied out of the set in one place.  Plain C++ without a HIP construct: the .hip files include it, and so
 // do the sanitizer harnesses tests/native/rle_group_sanitize.cpp, rle_match_sanitize.cpp, rle_merge_sanitize.cpp,
-// rle_nms_sanitize.cpp, rle_select_sanitize.cpp, rle_clean_sanitize.cpp and rle_paint_sanitize.cpp.
+// rle_nms_sanitize.cpp, rle_select_sanitize.cpp, rle_clean_sanitize.cpp and rle_paint_sanitize.cpp.  heat_paint_plan, the host
+// side of the heat-map painter in csrc/rle_paint.hip, lives here too (tests/native/heat_paint_sanitize.cpp): it shares the canvas
+// checks of rle_paint_plan.
 #ifndef HGL_RLE_GROUP_H
 #define HGL_RLE_GROUP_H
 #include <stdint.h>
@@ -59,6 +61,27 @@ static inline int rle_plan_entries(int g, long long e, long long e_next, int S, 
 // column `col` of the row after `row` (image g of G, `stride` numbers to a row), or S behind the last row: where g's entries end
 static inline long long rle_row_next(const int64_t* row, int stride, int col, int g, int G, int S) {
   return g + 1 < G ? row[stride + col] : (long long)S;
+}
+
+// canvas g (rle_paint_plan, heat_paint_plan): its n pixels from pixel o on lie inside [0, canvas_pixels) and apart from the
+// canvases before it; lo / hi collect the extents
+static inline int rle_plan_canvas(int g, long long o, long long n, long long canvas_pixels, long long* lo, long long* hi, char* why,
+                                  size_t why_cap) {
+  RLE_PLAN_REQUIRE(o >= 0 && o <= canvas_pixels && n <= canvas_pixels - o,
+                   "image %d: pixels %lld .. %lld lie outside the %lld of the canvas", g, o, o + n, canvas_pixels);
+  lo[g] = o;
+  hi[g] = o + n;
+  for (int f = 0; f < g; ++f)
+    RLE_PLAN_REQUIRE(hi[f] <= lo[g] || hi[g] <= lo[f], "the canvases of images %d and %d overlap", f, g);
+  return 0;
+}
+// the out_bytes at `out` apart from the base_bytes at `base`, unless base is 0 (addresses as numbers)
+static inline int rle_plan_apart(uintptr_t base, unsigned long long base_bytes, uintptr_t out, unsigned long long out_bytes, char* why,
+                                 size_t why_cap) {
+  RLE_PLAN_REQUIRE(base == 0 || base_bytes == 0 || out_bytes == 0 || (unsigned long long)base + base_bytes <= (unsigned long long)out ||
+                       (unsigned long long)out + out_bytes <= (unsigned long long)base,
+                   "out overlaps base");
+  return 0;
 }
 
 struct RleGroup {
@@ -527,12 +550,7 @@ static inline int rle_paint_plan(const int64_t* images, int G, int S, int K, lon
     if (rle_plan_size(g, H, W, why, why_cap) || rle_plan_entries(g, e, e_next, S, "", "S", why, why_cap) ||
         rle_plan_entries(g, k, k_next, K, "list ", "K", why, why_cap))
       return -1;
-    RLE_PLAN_REQUIRE(o >= 0 && o <= canvas_pixels && H * W <= canvas_pixels - o,
-                     "image %d: pixels %lld .. %lld lie outside the %lld of the canvas", g, o, o + H * W, canvas_pixels);
-    lo[g] = o;
-    hi[g] = o + H * W;
-    for (int f = 0; f < g; ++f)
-      RLE_PLAN_REQUIRE(hi[f] <= lo[g] || hi[g] <= lo[f], "the canvases of images %d and %d overlap", f, g);
+    if (rle_plan_canvas(g, o, H * W, canvas_pixels, lo, hi, why, why_cap)) return -1;
     const int over = rle_set_add(&plan->pick.pos, g, H, W, k, k_next);
     RLE_PLAN_REQUIRE(!(over & RLE_SET_WORDS), "%s", RLE_SET_WORDS_WHY);
     RLE_PLAN_REQUIRE(!(over & RLE_SET_BLOCKS), "too many list positions (%d) for one launch", K);
@@ -550,10 +568,76 @@ static inline int rle_paint_plan(const int64_t* images, int G, int S, int K, lon
   p->first[G] = K;
   p->G = G;
   const unsigned long long bytes = 3ull * (unsigned long long)canvas_pixels;
-  RLE_PLAN_REQUIRE(base == 0 || bytes == 0 || (unsigned long long)base + bytes <= (unsigned long long)out ||
-                       (unsigned long long)out + bytes <= (unsigned long long)base,
-                   "out overlaps base");
-  return 0;
+  return rle_plan_apart(base, bytes, out, bytes, why, why_cap);
+}
+
+// ---- hgl_heat_paint_device (csrc/rle_paint.hip): M heat-maps turned into colours on RGB canvases.  A workgroup of each of the
+// three kernels owns one share of consecutive pixels of one map: HEAT_BLOCK_PIX pixels, or the multiple of it that keeps a map
+// at HEAT_PARTS_MAX shares at the most -- a workgroup folds its map's partials, one per share, with one load per thread.
+constexpr int HEAT_BLOCK_PIX = 4096, HEAT_PARTS_MAX = 256;
+
+// the pixels of one share of a map of n pixels (0 < n < 2^31): a multiple of HEAT_BLOCK_PIX, ceil(n / share) <= HEAT_PARTS_MAX
+// (constexpr: the kernels call it as well)
+constexpr long long heat_share(long long n) {
+  const long long per = (n + HEAT_PARTS_MAX - 1) / HEAT_PARTS_MAX;
+  return ((per + HEAT_BLOCK_PIX - 1) / HEAT_BLOCK_PIX) * HEAT_BLOCK_PIX;
+}
+
+struct HeatPaint {
+  long long heat0[RLE_GROUP_MAX];               // the element of heat the map starts at
+  long long base0[RLE_GROUP_MAX];               // the pixel of base its image starts at
+  long long pix0[RLE_GROUP_MAX];                // the pixel of out (the element of levels) its canvas starts at
+  int H[RLE_GROUP_MAX], W[RLE_GROUP_MAX];
+  unsigned blk0[RLE_GROUP_MAX + 1];             // the map's first workgroup = its first partial (increasing, blk0[0] = 0); [M] = all
+  unsigned char dirflag[RLE_GROUP_MAX];
+  int M;
+};
+
+struct HeatPaintPlan {
+  HeatPaint p;
+  long long blocks;      // workgroups of each launch and partials of each kind: at most RLE_GROUP_MAX * HEAT_PARTS_MAX
+};
+
+// maps [M,6] = (H, W, dirflag, heat element, base pixel, out pixel) -> *plan; 0, or -1 with the reason in why.  Checked:
+// 1 <= M <= 64; 0 <= heat_elems, canvas_pixels < 2^60; H*W < 2^31; dirflag 0 .. 3; every heat extent [h, h + H*W) inside
+// [0, heat_elems) and every base extent from a pixel 0 <= b < 2^60 on (both are only read: they may coincide or overlap); every
+// canvas [p, p + H*W) inside [0, canvas_pixels) and no two overlapping; the 3 * canvas_pixels bytes at `out` apart from the bytes
+// of base that the maps name, unless base is 0 (addresses as numbers: nothing is read through them here).
+static inline int heat_paint_plan(const int64_t* maps, int M, long long heat_elems, long long canvas_pixels, uintptr_t base,
+                                  uintptr_t out, HeatPaintPlan* plan, char* why, size_t why_cap) {
+  RLE_PLAN_REQUIRE(M >= 1 && M <= RLE_GROUP_MAX, "%d maps (1 .. %d in one call)", M, RLE_GROUP_MAX);
+  RLE_PLAN_REQUIRE(heat_elems >= 0 && heat_elems < (1ll << 60), "heat_elems %lld (0 .. 2^60 - 1)", heat_elems);
+  RLE_PLAN_REQUIRE(canvas_pixels >= 0 && canvas_pixels < (1ll << 60), "canvas_pixels %lld (0 .. 2^60 - 1)", canvas_pixels);
+  memset(plan, 0, sizeof(*plan));
+  HeatPaint* p = &plan->p;
+  long long lo[RLE_GROUP_MAX], hi[RLE_GROUP_MAX];      // the pixel extent [lo, hi) of every canvas
+  long long b_lo = 0, b_hi = 0;                        // the pixels of base that some map names
+  for (int m = 0; m < M; ++m) {
+    const int64_t* r = maps + 6 * m;
+    const long long H = r[0], W = r[1], d = r[2], h = r[3], b = r[4], o = r[5];
+    if (rle_plan_size(m, H, W, why, why_cap)) return -1;
+    const long long n = H * W;
+    RLE_PLAN_REQUIRE(d >= 0 && d <= 3, "map %d: dirflag %lld (0 none, 1 left, 2 right, 3 middle)", m, d);
+    RLE_PLAN_REQUIRE(h >= 0 && h <= heat_elems && n <= heat_elems - h,
+                     "map %d: elements %lld .. %lld lie outside the %lld of heat", m, h, h + n, heat_elems);
+    RLE_PLAN_REQUIRE(b >= 0 && b < (1ll << 60), "map %d: base pixel %lld (0 .. 2^60 - 1)", m, b);
+    if (rle_plan_canvas(m, o, n, canvas_pixels, lo, hi, why, why_cap)) return -1;
+    if (m == 0 || b < b_lo) b_lo = b;
+    if (m == 0 || b + n > b_hi) b_hi = b + n;
+    p->heat0[m] = h;
+    p->base0[m] = b;
+    p->pix0[m] = o;
+    p->H[m] = (int)H;
+    p->W[m] = (int)W;
+    p->dirflag[m] = (unsigned char)d;
+    p->blk0[m] = (unsigned)plan->blocks;
+    const long long share = heat_share(n);
+    plan->blocks += (n + share - 1) / share;
+  }
+  p->blk0[M] = (unsigned)plan->blocks;
+  p->M = M;
+  return rle_plan_apart(base ? base + 3ull * (unsigned long long)b_lo : 0, 3ull * (unsigned long long)(b_hi - b_lo), out,
+                        3ull * (unsigned long long)canvas_pixels, why, why_cap);
 }
 
 #undef RLE_PLAN_REQUIRE

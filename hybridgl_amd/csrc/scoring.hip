@@ -5,6 +5,7 @@
 //   score_sentence       Hybridgl_main.py:153-196,225-228 (+ relation_boxes utils.py:240-268)
 //   synthesize_views     Hybridgl_main.py:93-125
 #include "hgl_common.h"
+#include "dir_ramp.h"      // linspace_at, dir_weight: shared with csrc/rle_paint.hip
 #include <mutex>
 #include <vector>
 #include <condition_variable>
@@ -79,27 +80,6 @@ __global__ __launch_bounds__(256) void minmax_kernel(const float* __restrict__ a
 __global__ void init_stats_kernel(int* stats) {
   stats[0] = 0x7fffffff;          // +max ordered key
   stats[1] = (int)0x80000000;     // -max ordered key
-}
-
-// torch.linspace(start,end,steps)[i] in fp32 (ATen RangeFactories: symmetric evaluation)
-__device__ __forceinline__ float linspace_at(float start, float end, int steps, int i) {
-  if (steps == 1) return start;
-  const float step = (end - start) / (float)(steps - 1);
-  const int half = steps / 2;
-  return i < half ? fmaf(step, (float)i, start) : fmaf(-step, (float)(steps - i - 1), end);  // fmas, as ATen
-}
-
-// gen_dir_mask column weight (utils.py:135-161): 0 none, 1 left, 2 right, 3 middle
-__device__ __forceinline__ float dir_weight(int dirflag, int x, int W) {
-  switch (dirflag) {
-    case 1: return linspace_at(1.f, 0.f, W, x);
-    case 2: return linspace_at(0.f, 1.f, W, x);
-    case 3: {
-      const int w1 = W / 2;
-      return x < w1 ? linspace_at(0.f, 1.f, w1, x) : linspace_at(1.f, 0.f, W - w1, x - w1);
-    }
-    default: return 1.f;
-  }
 }
 
 // Masked pooling.  One block = PIX_PER_BLOCK consecutive pixels x all masks.

@@ -21,7 +21,19 @@ import torch
 
 from . import ops, render
 
+OUTLINE_INK = (255, 255, 255)      # the final winner's outline over a heat picture
 PARSE_KEYS = ("sentence_for_spacy", "noun_phrase", "other_nouns", "dirflag", "relaflag")
+
+
+@dataclasses.dataclass
+class Explanation:
+    """what the scoring tail was given and what it computed for one text (HybridGL(explain=True)), on the device"""
+    heat: torch.Tensor         # float32 [H,W]: the raw GEM heat-map, before min-max and the direction weight
+    dirflag: str               # "none" / "left" / "right" / "middle": the weight gen_dir_mask multiplies the map with
+    black: float               # the relation's coherence constant (Hybridgl_main.py:211-216)
+    score_clip: torch.Tensor   # float32 [N]: the pure CLIP score of every proposal; its argmax is index_pure
+    score_neg: torch.Tensor    # float32 [N]: the score against the other nouns
+    gem_score: torch.Tensor    # float32 [N]: the coherence score, ops.coherence_scores(heat, proposals, dirflag, black)
 
 
 @dataclasses.dataclass
@@ -36,6 +48,7 @@ class Segmentation:
     proposals: torch.Tensor = dataclasses.field(repr=False)    # bool [N,H,W] on the device
     winners: tuple = dataclasses.field(repr=False)             # (slots, table) of the call's winners on the device, 2 per text
     row: int = 0                                               # this text's first entry in `winners`: pure, then final
+    explanation: Explanation = dataclasses.field(default=None, repr=False)      # with HybridGL(explain=True)
 
     def _which(self, which):
         if which not in ("pure", "final"):
@@ -51,15 +64,46 @@ class Segmentation:
         row = ops.rle_paint_style(**style) if isinstance(style, dict) else style
         return render.overlay(self.image, self.winners, order=[self.row + int(self._which(which))], style=row)
 
+    def _explained(self):
+        if self.explanation is None:
+            raise RuntimeError("this Segmentation carries no explanation: build HybridGL(explain=True)")
+        return self.explanation
+
+    def heat_overlay(self, ramp="heat", outline=True, with_status=False):
+        """the guided heat-map the scorer used -- min-max normalised, times the direction weight -- over the image (ops.heat_paint),
+        with the final winner's outline on top (ops.rle_paint, the heat picture as its base): uint8 [H,W,3] on the device.
+        with_status: (picture, status [1,4] int32 = code, bits of mn, mx, peak of ops.heat_paint)"""
+        ex = self._explained()
+        pics, _, status = render.heatmap_group([self.image], [ex.heat], [ex.dirflag], ramp=ramp)
+        pic = pics[0]
+        if outline:
+            pic = render.overlay(pic, self.winners, order=[self.row + 1], style=ops.rle_paint_style(outline=OUTLINE_INK))
+        return (pic, status) if with_status else pic
+
+    def topk_order(self, k=3):
+        """the k proposals with the highest score_clip, best LAST (the paint order): int32 [k] on the device, from a stable
+        descending sort there -- the shortlist the final choice is drawn from when k is the pipeline's k1"""
+        ex = self._explained()
+        k = max(0, min(int(k), self.n_proposals))
+        return torch.argsort(ex.score_clip, descending=True, stable=True)[:k].flip(0).to(torch.int32)
+
+    def topk_overlay(self, k=3):
+        """the k proposals with the highest score_clip over the image, in palette colours (the best is palette colour 0) with
+        outlines, the best painted last: uint8 [H,W,3] on the device; the order never leaves it"""
+        order = self.topk_order(k)
+        n = int(order.numel())
+        slots, table = ops.rle_encode(self.proposals.contiguous(), order)
+        return render.overlay(self.image, (slots, table), style=render.proposal_styles(n)[::-1].copy() if n else None)
+
 
 class HybridGL:
     """The three models, built once the way main.build_models builds them, behind one private ref-by-ref pipeline.  amg: the
     mask generator's settings over demo.py:44-54's (points_per_side=8, pred_iou_thresh=0.7, stability_score_thresh=0.7,
     crop_n_layers=0, crop_n_points_downscale_factor=1, min_mask_region_area=800); clip_checkpoint / sam_checkpoint / bpe_vocab:
-    files in place of the packages' defaults."""
+    files in place of the packages' defaults.  explain: every Segmentation carries an Explanation (the pipeline's keep_explain)."""
 
     def __init__(self, clip_model="ViT-B/16", sam_model="default", clip_checkpoint=None, sam_checkpoint=None, bpe_vocab=None,
-                 precision=None, fusion_mode="G2L", heatmap="device", amg=None, device="cuda"):
+                 precision=None, fusion_mode="G2L", heatmap="device", amg=None, device="cuda", explain=False):
         from .backbone import CLIPViTFM
         from .main import AMG_DEFAULTS
         from .pipeline import HybridGLPipeline
@@ -85,7 +129,8 @@ class HybridGL:
         self.tokenizer = SimpleTokenizer(bpe_vocab or None)
         self.context_length = CLIP_CONFIGS[clip_model]["context_length"]
         self._pipe = HybridGLPipeline(self.model, fusion_mode=fusion_mode, mask_generator=self.generator, use_sam_masks=True,
-                                      gem_model=self.gem_model, k_clamp="per_ref", record_predictions=True)
+                                      gem_model=self.gem_model, k_clamp="per_ref", record_predictions=True,
+                                      keep_explain=bool(explain))
         self._image = None      # (the caller's object, image id, sam_img, image_norm, tensor_img) of the last image
         self._calls = 0
 
@@ -161,8 +206,11 @@ class HybridGL:
         idx = torch.stack(pipe.idx_log)      # [n,2] int32 on the device: the tail's own
         winners = ops.rle_encode(proposals, idx.reshape(-1), ops.rle_slot_words(H, W))
         strings = [{"size": [H, W], "counts": b.decode("ascii")} for b in strings_from_device(*winners, H, W)]
+        kept = pipe.explained()
+        assert len(kept) in (0, n)
+        explain = [Explanation(e["heat"], e["dirflag"], e["black"], e["score_clip"], e["score_neg"], e["gem_score"]) for e in kept] or [None] * n
         return [Segmentation(texts[j], records[j]["pure_index"], records[j]["final_index"], strings[2 * j], strings[2 * j + 1],
-                             int(proposals.shape[0]), ref.sam_img, proposals, winners, 2 * j) for j in range(n)]
+                             int(proposals.shape[0]), ref.sam_img, proposals, winners, 2 * j, explain[j]) for j in range(n)]
 
     def all_proposals(self, seg):
         """every proposal of a Segmentation's image painted over it, largest area first (ties in stored order), in the
@@ -179,6 +227,17 @@ def paint_all(image, masks):
     return render.overlay(image, (slots, table), order=order, style=render.proposal_styles(N))
 
 
+def scores_record(seg):
+    """one text's explanation as plain numbers: the three score rows, both indices, and mn / mx / peak of the guided map"""
+    ex = seg._explained()
+    _, status = seg.heat_overlay(outline=False, with_status=True)
+    st = status[0].cpu()
+    mn, mx, peak = (float(v) for v in st[1:].view(torch.float32))
+    return {"text": seg.text, "index_pure": seg.index_pure, "index_final": seg.index_final, "dirflag": ex.dirflag, "black": ex.black,
+            "score_clip": ex.score_clip.cpu().tolist(), "score_neg": ex.score_neg.cpu().tolist(), "gem_score": ex.gem_score.cpu().tolist(),
+            "status": {"code": int(st[0]), "mn": mn, "mx": mx, "peak": peak}}
+
+
 def default_argument_parser():
     from .main import AMG_DEFAULTS
     p = argparse.ArgumentParser(prog="python -m hybridgl_amd.demo", description="segment one image by one sentence; write the overlay")
@@ -192,6 +251,10 @@ def default_argument_parser():
     p.add_argument("--dirflag", default=None)
     p.add_argument("--relaflag", default=None)
     p.add_argument("--all_proposals", default="", metavar="OUT2", help="PNG: every proposal, largest first, in palette colours")
+    p.add_argument("--heat_out", default="", metavar="PNG", help="the guided heat-map over the image, the final winner outlined")
+    p.add_argument("--topk_out", default="", metavar="PNG", help="the --topk proposals with the highest CLIP score, best last")
+    p.add_argument("--topk", type=int, default=3, metavar="K")
+    p.add_argument("--scores_json", default="", metavar="OUT", help="per text: the three score rows, both indices, the heat-map's mn / mx / peak")
     p.add_argument("--fusion_mode", default="G2L", choices=["G2L", "L2G", "G2L&L2G"])
     p.add_argument("--heatmap", default="device", choices=["device", "given"])
     p.add_argument("--clip_model", default="ViT-B/16")
@@ -227,7 +290,8 @@ def main(argv=None):
     amg["box_nms_thresh"] = args.box_nms_thresh
     rec = parse_record(args)
     hgl = HybridGL(args.clip_model, args.sam_model, bpe_vocab=args.bpe_vocab or None, precision=args.precision,
-                   fusion_mode=args.fusion_mode, heatmap=args.heatmap, amg=amg)
+                   fusion_mode=args.fusion_mode, heatmap=args.heatmap, amg=amg,
+                   explain=bool(args.heat_out or args.topk_out or args.scores_json))
     try:
         seg = hgl.segment(args.image, args.text, rec or None)[0]
     except EmptyProposals:
@@ -237,6 +301,14 @@ def main(argv=None):
     print(f"{args.text!r}: proposal {seg.index_final} of {seg.n_proposals} (pure CLIP: {seg.index_pure}) -> {args.out}")
     if args.all_proposals:
         render.save_png(args.all_proposals, hgl.all_proposals(seg))
+    if args.heat_out:
+        render.save_png(args.heat_out, seg.heat_overlay())
+    if args.topk_out:
+        render.save_png(args.topk_out, seg.topk_overlay(args.topk))
+    if args.scores_json:
+        import json
+        with open(args.scores_json, "w") as f:
+            json.dump([scores_record(seg)], f)
     return 0
 
 

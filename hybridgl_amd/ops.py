@@ -1023,6 +1023,110 @@ def rle_paint(slots, table, sizes, counts, order, order_counts, style, base=None
     return views(flat, 3), (views(lab, 1) if labels else None), status
 
 
+def heat_ramp(colours, a, b):
+    """A ramp of heat_paint, uint32 [256,3]: row L = (colour 0x00RRGGBB, the fp32 bits of a_L, of b_L).  colours: [256,3] (R, G,
+    B); a, b: 256 weights each, or one number for every level.  Level L paints sat_u8(rint(pixel * a_L + colour_L * b_L))."""
+    import numpy as np
+    c = np.asarray(colours, dtype=np.int64)
+    if c.shape != (256, 3) or c.min() < 0 or c.max() > 255:
+        raise ValueError(f"heat_ramp: expected [256, 3] colours in 0 .. 255, got {c.shape}")
+    rows = np.empty((256, 3), dtype=np.uint32)
+    rows[:, 0] = (c[:, 0] << 16) | (c[:, 1] << 8) | c[:, 2]
+    for col, w in ((1, a), (2, b)):
+        w = np.asarray(w, dtype=np.float32)
+        if w.shape not in ((), (256,)):
+            raise ValueError(f"heat_ramp: expected one weight or 256, got {w.shape}")
+        rows[:, col] = np.broadcast_to(w, (256,)).view(np.uint32) if w.shape else np.full(256, w, np.float32).view(np.uint32)
+    return rows
+
+
+def heat_paint_layout(sizes, dirflags=None, shared_heat=None, shared_base=None):
+    """(maps [M,6] int64 = H, W, dirflag, heat element, base pixel, canvas pixel; heat elements; base pixels; canvas pixels) of
+    M maps of sizes[m] = (H, W): the canvases packed back to back, and so the heat-maps and the base images -- except that maps
+    with the same number in shared_heat [M] read ONE heat extent (one map under several directions) and maps with the same
+    number in shared_base [M] ONE base image (several sentences over one image); both must then agree in size.  dirflags:
+    "none" / "left" / "right" / "middle" or 0 .. 3 per map (default none)."""
+    import numpy as np
+    M = len(sizes)
+    dirflags = [0] * M if dirflags is None else list(dirflags)
+    if len(dirflags) != M or any(s is not None and len(s) != M for s in (shared_heat, shared_base)):
+        raise ValueError(f"heat_paint_layout: {M} sizes, {len(dirflags)} dirflags and shared lists of other lengths")
+    rows = np.zeros((M, 6), dtype=np.int64)
+    ends = [0, 0, 0]      # heat, base, canvas
+    seen = [{}, {}]
+    for m, (H, W) in enumerate(sizes):
+        H, W = int(H), int(W)
+        d = dirflags[m]
+        d = DIRFLAG[d] if isinstance(d, str) else int(d)
+        if H <= 0 or W <= 0 or H * W >= 1 << 31 or not 0 <= d <= 3:
+            raise ValueError(f"heat_paint_layout: map {m}: size {H} x {W} (0 < H*W < 2^31), dirflag {dirflags[m]!r}")
+        rows[m, :3] = (H, W, d)
+        for k, shared in enumerate((shared_heat, shared_base)):
+            key = None if shared is None else shared[m]
+            if key is not None and key in seen[k]:
+                at, size = seen[k][key]
+                if size != (H, W):
+                    raise ValueError(f"heat_paint_layout: map {m} shares an extent of size {size} but is {(H, W)}")
+            else:
+                at = ends[k]
+                ends[k] += H * W
+                if key is not None:
+                    seen[k][key] = (at, (H, W))
+            rows[m, 3 + k] = at
+        rows[m, 5] = ends[2]
+        ends[2] += H * W
+    return rows, ends[0], ends[1], ends[2]
+
+
+def heat_paint(heat, maps, ramp, base=None, out=None, levels=False):
+    """Heat-maps turned into colours over their images (hgl_heat_paint_device on the current stream, no synchronisation; the
+    contract is include/hybridgl.h's).  heat: contiguous float32 device tensor, read flat; maps: HOST [M,6] int64 rows (H, W,
+    dirflag, heat element, base pixel, canvas pixel), what heat_paint_layout builds; ramp: [256,3] uint32 rows of heat_ramp, a
+    host array (uploaded) or a device tensor; base: None (black) or a contiguous uint8 device tensor that holds every base extent
+    (3 bytes per pixel); out: a contiguous uint8 device tensor of 3 * canvas pixels, every byte of a canvas written and none
+    between canvases (default: a fresh one that ends with the last canvas).
+    Returns (pictures: M uint8 views [H,W,3] of out; levels: M uint8 views [H,W] or None; status [M,4] int32 = code, bits of mn,
+    of mx, of peak).  levels: False, True, or a uint8 device tensor of canvas pixels to write them to.  ValueError for a geometry
+    the plan refuses; out over base is the library's HGL_EINVAL."""
+    import numpy as np
+    lib = _lib.load()
+    maps = np.ascontiguousarray(np.asarray(maps, dtype=np.int64))
+    if maps.ndim != 2 or maps.shape[1] != 6 or not 1 <= maps.shape[0] <= 64:
+        raise ValueError(f"heat_paint: maps {maps.shape} (expected [M, 6], 1 <= M <= 64)")
+    M = int(maps.shape[0])
+    dev = heat.device
+    hp = _dev(heat, torch.float32, "heat")
+    px = maps[:, 0] * maps[:, 1]
+    total = int((maps[:, 5] + px).max()) if out is None else out.numel() // 3
+    if out is not None and out.numel() % 3:
+        raise ValueError(f"out: {out.numel()} bytes are no whole number of pixels")
+    need = lib.hgl_heat_paint_workspace_bytes(maps.ctypes.data, M, heat.numel(), total)
+    if not need:
+        raise ValueError(f"heat_paint: the library refuses this geometry ({M} maps, {heat.numel()} heat elements, {total} canvas pixels)")
+    if base is not None:
+        _dev(base, torch.uint8, "base")
+        if int(maps[:, 4].min()) < 0 or 3 * int((maps[:, 4] + px).max()) > base.numel():
+            raise ValueError(f"base: {base.numel()} bytes do not hold every base extent")
+    flat = _out(out, 3 * total, torch.uint8, dev, "out")
+    if isinstance(ramp, np.ndarray):
+        if ramp.shape != (256, 3) or ramp.dtype != np.uint32:
+            raise ValueError(f"ramp: expected [256, 3] uint32, got {ramp.shape} {ramp.dtype}")
+        ramp = torch.from_numpy(ramp.view(np.int32).copy()).to(dev, non_blocking=True)
+    if ramp.numel() != 768 or ramp.element_size() != 4:
+        raise ValueError(f"ramp: expected [256, 3] words, got {tuple(ramp.shape)} {ramp.dtype}")
+    rp = _dev(ramp, ramp.dtype, "ramp")
+    status = torch.empty((M, 4), dtype=torch.int32, device=dev)
+    lev = None if levels is False else _out(None if levels is True else levels, total, torch.uint8, dev, "levels")
+    levels = lev is not None
+    ws = workspace(need, dev, "rle")
+    check(lib.hgl_heat_paint_device(hp, heat.numel(), maps.ctypes.data, M, rp, None if base is None else base.data_ptr(),
+                                    flat.data_ptr(), total, None if lev is None else lev.data_ptr(), status.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream()), "hgl_heat_paint_device")
+    views = lambda buf, c: [buf[int(p) * c:(int(p) + int(H) * int(W)) * c].view(*((int(H), int(W), 3) if c == 3 else (int(H), int(W))))
+                            for H, W, _, _, _, p in maps]
+    return views(flat, 3), (views(lev, 1) if levels else None), status
+
+
 POLY_RULE = {"once": 0, "any": 1}
 
 

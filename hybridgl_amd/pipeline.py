@@ -119,7 +119,7 @@ class HybridGLPipeline:
     def __init__(self, model, fusion_mode="G2L", masking_block=9, r=0.5, alpha=0.6, k1=3, k2=6, res=224,
                  mask_generator=None, use_sam_masks=False, fixed_proposals=None, cleanup_given_masks=False,
                  gem_model=None, k_clamp="persistent", image_cache=32, record_predictions=False, sweep=None,
-                 on_overflow="raise"):
+                 on_overflow="raise", keep_explain=False):
         """mask_generator: a hybridgl_amd.sam.SamAutomaticMaskGenerator; when given, every step runs the
         SAM proposal stage (encoder, decoder, post-processing, NMS) on ref.sam_img first.
         use_sam_masks=False keeps ref.masks for the CLIP stage (fixed N; synthetic benchmark, where
@@ -137,12 +137,16 @@ class HybridGLPipeline:
         exactly as without a sweep.  A ref the fused tail cannot serve raises ValueError then.
         on_overflow: what run() does when an activation leaves the fp16 range in f16x3 / f16 mode.  "raise" (default): it
         raises ops.SplitOverflow at the offending group.  "rescue": the groups that were in flight are run again in f32 and
-        the loop goes on (run()'s docstring; rescue_stats); step() and metrics() are the same in both modes."""
+        the loop goes on (run()'s docstring; rescue_stats); step() and metrics() are the same in both modes.
+        keep_explain: keep, on the device, what the tail of the most recent ref (step) or group (run) was given and what it
+        computed per sentence -- explained(); nothing is computed or copied for it, and nothing changes with it off."""
         if k_clamp not in ("persistent", "per_ref"):
             raise ValueError("k_clamp must be 'persistent' or 'per_ref'")
         if on_overflow not in ("raise", "rescue"):
             raise ValueError("on_overflow must be 'raise' or 'rescue'")
         self.on_overflow = on_overflow
+        self.keep_explain = bool(keep_explain)
+        self._explained = []
         # run(on_overflow="rescue"): moved totals met, groups / refs done again in f32, and those refs' dataset positions
         self.rescue_stats = {"events": 0, "groups": 0, "refs": 0, "positions": []}
         self._rescue_bufs = PinnedPool()      # pinned int32 [3] snapshot buffers that are free
@@ -287,6 +291,7 @@ class HybridGLPipeline:
             if from_gen and ref.image_id is not None:
                 self._cache_id, self._cache_ref, self._cache_hybrid = ref.image_id, ref, hybrid
         cur.wait_event(ev_text)
+        self._explained = []      # explained() speaks of this ref alone
         return hybrid, text, self._score_ref(ref, hybrid, text, heat)
 
     _DEFERRED = object()
@@ -337,6 +342,19 @@ class HybridGLPipeline:
                  "size": [int(hw[0]), int(hw[1])], "pure": [int(v) for v in a], "final": [int(v) for v in b]}
                 for o, w, (hw, a, b) in zip(self.iu_owner, win, self._pred_done)]
 
+    # ---- explanations: what the tail of the most recent ref or group saw (keep_explain=True) --------------------------------
+    def _explain(self, ref_index, recs, sc, sn, gm):
+        """recs: per sentence (heat-map, dirflag, black); sc / sn / gm: per sentence the tail's score_clip, score_neg, gem_score [N]"""
+        for j, (heat, dirflag, black) in enumerate(recs):
+            self._explained.append({"index": ref_index, "sentence": j, "heat": heat, "dirflag": dirflag, "black": black,
+                                    "score_clip": sc[j], "score_neg": sn[j], "gem_score": gm[j]})
+
+    def explained(self):
+        """Per sentence of the most recent ref (step) or group (run), in log order: {"index": dataset position, "sentence",
+        "heat": the raw heat-map [H,W] the tail was given, "dirflag", "black", "score_clip", "score_neg", "gem_score": [N]},
+        device tensors all; the fused tail and the per-sentence tail fill the same values.  Empty without keep_explain."""
+        return list(self._explained)
+
     def _flush_tails(self, defer):
         """the deferred tails of a group's refs in one hgl_score_group call; returns each ref's last-sentence tensors, in order"""
         if not defer:
@@ -347,6 +365,8 @@ class HybridGLPipeline:
         last = []
         for q, (idx, iu, sc, sn, gm) in zip(defer, outs):
             self._log_tail(q["ref_index"], len(q["sentences"]), idx, iu, q["masks"])
+            if self.keep_explain:
+                self._explain(q["ref_index"], [(r["imgattn"], r["dirflag"], r["black"]) for r in q["sentences"]], sc, sn, gm)
             last.append((idx[-1], sc[-1], sn[-1], gm[-1]))
         defer.clear()
         return last
@@ -403,8 +423,11 @@ class HybridGLPipeline:
                 self._sweep_tails([dict(hybrid=hybrid, text=text, boxes=ref.boxes, masks=ref.masks, sentences=recs,
                                         sweep_k=self._sweep_k)])
             self._log_tail(ref_index, len(recs), idx, iu, ref.masks)
+            if self.keep_explain:
+                self._explain(ref_index, [(r["imgattn"], r["dirflag"], r["black"]) for r in recs], sc, sn, gm)
             return (idx[-1], sc[-1], sn[-1], gm[-1]) if recs else None
         last = None
+        kept = []
         for sent_no, (s, imgattn) in enumerate(zip(ref.sentences, attn)):
             gem = ops.coherence_scores(imgattn, ref.masks, s.dirflag, black_for(s.relaflag))
             others = _rows(text, s.other_noun_rows)
@@ -420,6 +443,9 @@ class HybridGLPipeline:
             self.iu_owner.append((ref_index, sent_no))
             self.idx_log.append(idx)
             last = (idx, sc, sn, gem)
+            kept.append((imgattn, s.dirflag, black_for(s.relaflag), sc, sn, gem))
+        if self.keep_explain:
+            self._explain(ref_index, [k[:3] for k in kept], *[[k[c] for k in kept] for c in (3, 4, 5)])
         if self.record_predictions:
             n = len(ref.sentences)
             self._record_tail(ref_index, n, ref.masks, torch.stack(self.idx_log[-n:]))
@@ -961,6 +987,7 @@ class HybridGLPipeline:
                 live[i][3] = hybrid_all[moff[j]:moff[j + 1]]
         cur.wait_event(ev_text)
         k = 0
+        self._explained = []                         # explained() speaks of this group alone
         defer = [] if self.group_tail else None      # the refs whose tails go into ONE hgl_score_group call at the end
         waiting = []                                 # their (hybrid, text) for `collected`, in order
         for refs, mk, bx, hybrid, gfeat in live:

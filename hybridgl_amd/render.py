@@ -107,6 +107,65 @@ def overlay(image, masks, order=None, style=None, labels=False):
     return (pics[0], labs[0], status) if labels else pics[0]
 
 
+# ---- heat-maps: the scorer's guided map as colours (csrc/rle_paint.hip: hgl_heat_paint_device, ops.heat_paint) --------------------
+HEAT_STOPS = [(0, (0, 0, 255)), (85, (0, 255, 255)), (170, (255, 255, 0)), (255, (255, 0, 0))]      # (level, colour): blue, cyan, yellow, red
+HEAT_ALPHA = 0.7      # the weight of the colour at level 255; 0 at level 0: where the map is cold the image shows through
+_ramps = {}
+
+
+def ramp(name):
+    """A named ramp of ops.heat_paint, uint32 [256,3] on the host.  "heat": piecewise linear through HEAT_STOPS, the colour's
+    weight b rising from 0 at level 0 to HEAT_ALPHA at level 255 and a = 1 - b; "grey": level L is the grey (L, L, L), opaque."""
+    import numpy as np
+    if name not in _ramps:
+        L = np.arange(256)
+        if name == "heat":
+            at = [s[0] for s in HEAT_STOPS]
+            colours = np.stack([np.rint(np.interp(L, at, [s[1][c] for s in HEAT_STOPS])) for c in range(3)], axis=1)
+            b = (HEAT_ALPHA * L / 255.0).astype(np.float32)
+            _ramps[name] = ops.heat_ramp(colours, np.float32(1) - b, b)
+        elif name == "grey":
+            _ramps[name] = ops.heat_ramp(np.stack([L, L, L], axis=1), 0.0, 1.0)
+        else:
+            raise ValueError(f"ramp: {name!r} ('heat' or 'grey')")
+    return _ramps[name]
+
+
+_named_ramp = ramp      # the functions below take a parameter of this name
+
+def heatmap_group(images, heats, dirflags, ramp="heat", image_of=None, levels=False, out=None):
+    """Up to 64 heat-maps painted over their images in ONE ops.heat_paint call, nothing read back.  heats: float32 [H,W] device
+    tensors -- the raw maps the scoring tail is given; dirflags: "none" / "left" / "right" / "middle" per map; images: uint8
+    [H,W,3] device tensors, or None for black canvases; image_of[m]: the image under map m (default m: one image per map) --
+    several sentences over one image share it.  ramp: a name of ramp(), or [256,3] rows of ops.heat_ramp.  The same tensor
+    object given twice in heats is uploaded once and read under both directions.
+    Returns (pictures: uint8 [H,W,3] views, levels: uint8 [H,W] views or None, status [M,4] int32) as ops.heat_paint does."""
+    M = len(heats)
+    if len(dirflags) != M or (image_of is not None and len(image_of) != M):
+        raise ValueError(f"heatmap_group: {M} maps, {len(dirflags)} dirflags")
+    image_of = list(range(M)) if image_of is None else [int(i) for i in image_of]
+    sizes = [tuple(int(v) for v in h.shape) for h in heats]
+    if images is not None:
+        for m, i in enumerate(image_of):
+            if not 0 <= i < len(images) or tuple(images[i].shape) != (*sizes[m], 3):
+                raise ValueError(f"heatmap_group: map {m} of size {sizes[m]} over image {i}")
+    shared_heat = [id(h) for h in heats]
+    maps, _, _, _ = ops.heat_paint_layout(sizes, dirflags, shared_heat=shared_heat, shared_base=image_of)
+    first = lambda keys: [m for m, k in enumerate(keys) if k not in keys[:m]]      # the extents in the layout's order
+    flat = lambda parts: parts[0].reshape(-1) if len(parts) == 1 else torch.cat([p.reshape(-1) for p in parts])
+    heat = flat([heats[m].to(torch.float32).contiguous() for m in first(shared_heat)])
+    base = None if images is None else flat([images[image_of[m]].contiguous() for m in first(image_of)])
+    rows = _named_ramp(ramp) if isinstance(ramp, str) else ramp
+    return ops.heat_paint(heat, maps, rows, base=base, out=out, levels=levels)
+
+
+def heatmap(image, heat, dirflag="none", ramp="heat"):
+    """ONE heat-map over its image: uint8 [H,W,3] on the device.  image: an uint8 [H,W,3] array, tensor or path, or None for a
+    black canvas; heat: float32 [H,W] on the device."""
+    image = None if image is None else [_image_u8(image, heat.device)]
+    return heatmap_group(image, [heat], [dirflag], ramp=ramp)[0][0]
+
+
 def save_png(path, tensor):
     """uint8 [H,W,3] (device or host) -> a PNG file, through Pillow on the host"""
     from PIL import Image

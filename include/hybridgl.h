@@ -1046,6 +1046,39 @@ size_t hgl_rle_paint_workspace_bytes(const int64_t* images_host, int G, int S, l
 int hgl_rle_paint_device(const uint32_t* slots, long long slot_words, const int32_t* table, int S, const int32_t* order,
                          const uint32_t* style, int K, const int64_t* images_host, int G, const uint8_t* base, uint8_t* out,
                          long long canvas_pixels, int32_t* labels, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+/* Heat-maps painted onto RGB canvases on the DEVICE (csrc/rle_paint.hip): the guided map of the scoring tail -- min-max
+ * normalised, times the direction weight of gen_dir_mask -- turned into colours with a weight per pixel, for a whole group of maps
+ * of different sizes, with nothing read back.  Asynchronous on `stream`; no host synchronisation, allocation or atomics; two
+ * calls give the same bytes; THREE launches whatever M and the sizes are (min/max partials; peak partials; paint).
+ * maps_host: HOST [M,6] int64, 1 <= M <= 64, row m = (H_m, W_m, dirflag, h_m, b_m, p_m); H, W >= 1, H*W < 2^31; dirflag 0 none,
+ * 1 left, 2 right, 3 middle, as for hgl_coherence_scores.  Map m is H*W fp32 values, row-major, at element h_m of heat
+ * [heat_elems]; its base image is H*W RGB pixels, row-major HWC, at byte 3*b_m of base; its canvas sits at byte 3*p_m of out and
+ * at element p_m of levels.  Heat extents and base extents are only read: they may coincide or overlap (several sentences over
+ * one image, one map under two directions).  The extents [p_m, p_m + H*W) must lie inside [0, canvas_pixels) and must not
+ * overlap; out must not overlap the bytes of base that the maps name.  Anything else is HGL_EINVAL with the reason in
+ * hgl_last_error() and nothing is enqueued.  The array is read before the call returns.
+ * ramp: device [256,3] uint32, row L = (colour 0x00RRGGBB, the fp32 bits of a_L, the fp32 bits of b_L).
+ * base: device, or NULL for black.  out: device, 3*canvas_pixels bytes.  levels: device uint8 [canvas_pixels], or NULL.
+ * Pixel rule, every operation rounded to fp32 on its own (no fused multiply-add).  mn, mx = the map's minimum and maximum;
+ * n = (x - mn) / (mx - mn), IEEE division; g = n * w(col), w the column weight of gen_dir_mask(dirflag, H, W) -- the very bits
+ * the coherence pooling multiplies with; peak = max g; t = g / peak; L = (int)rint(t * 255), to nearest even; every channel c of
+ * the pixel becomes sat_u8(rint(f32(base_c)*a_L + f32(colour_c(L))*b_L)), the fill rule of hgl_rle_paint_device (both products and
+ * the sum rounded, the clamp, a NaN to 0); levels gets L.  The scorer's division by the mean scales g by a constant and cancels
+ * in g / peak.  Minimum and maximum do not depend on the order they are taken in: every byte is defined by this rule alone.
+ * status: device [M,4] int32 = (code, bits of mn, bits of mx, bits of peak):
+ *   0   painted
+ *   1   mx == mn: a flat map
+ *   2   a value is NaN or +-inf, or mx - mn is not finite
+ *   3   peak == 0: all of the map's weight lies where the direction weight is 0 (W = 1 under `right`)
+ * A map with a code other than 0 is a plain copy of its base with levels 0 and status (code, 0, 0, 0).  Every byte of every extent
+ * of out and, when given, of levels is written; nothing outside the extents is.
+ * ws: hgl_heat_paint_workspace_bytes for the same geometry (HGL_EWORKSPACE when smaller): a (min, max) pair and a peak per
+ * workgroup -- a map of n pixels takes ceil(n / 4096) of them, at most 256 -- and four words per map.  The query returns 0 for a
+ * geometry the call refuses. */
+size_t hgl_heat_paint_workspace_bytes(const int64_t* maps_host, int M, long long heat_elems, long long canvas_pixels);
+int hgl_heat_paint_device(const float* heat, long long heat_elems, const int64_t* maps_host, int M, const uint32_t* ramp,
+                          const uint8_t* base, uint8_t* out, long long canvas_pixels, uint8_t* levels, int32_t* status,
+                          void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

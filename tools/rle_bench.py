@@ -704,6 +704,67 @@ def paint_leg(dev, reps, G=64, H=480, W=640, N=64, host_images=2):
     return rec
 
 
+def heat_leg(dev, reps, M=16, H=480, W=640, inner=20):
+    """ops.heat_paint of M maps of H x W over their images (three launches) against the same steps as torch device ops: amin /
+    amax per map, the normalisation and the direction weight, the peak, the levels, the ramp gathered per pixel and the blend.
+    Device events around `inner` calls in a row, the two sides alternated window by window; median and range over reps windows.
+    The torch side is compared with the call first: the shares of equal levels and equal picture bytes are reported."""
+    from hybridgl_amd import render
+    from hybridgl_amd import utils as U
+    rng = np.random.default_rng(5)
+    heat = torch.from_numpy(rng.standard_normal((M, H, W)).astype(np.float32)).to(dev)
+    base = torch.from_numpy(rng.integers(0, 256, (M, H, W, 3), dtype=np.uint8)).to(dev)
+    dirs = [("none", "left", "right", "middle")[m % 4] for m in range(M)]
+    maps, _, _, total = ops.heat_paint_layout([(H, W)] * M, dirs)
+    rows = render.ramp("heat")
+    ramp = torch.from_numpy(rows.view(np.int32).copy()).to(dev)
+    out = torch.empty(3 * total, dtype=torch.uint8, device=dev)
+    lev = torch.empty(total, dtype=torch.uint8, device=dev)
+    call = lambda: ops.heat_paint(heat, maps, ramp, base=base.view(-1), out=out, levels=lev)
+    w = torch.stack([U.gen_dir_mask(d, 1, W, dev)[0] for d in dirs])[:, None, :]      # [M,1,W]
+    colours = torch.from_numpy(np.stack([(rows[:, 0] >> 16) & 255, (rows[:, 0] >> 8) & 255, rows[:, 0] & 255], 1).astype(np.float32)).to(dev)
+    a_l, b_l = (torch.from_numpy(rows[:, c].copy().view(np.float32)).to(dev) for c in (1, 2))
+
+    def steps():
+        mn, mx = heat.amin((1, 2), keepdim=True), heat.amax((1, 2), keepdim=True)
+        g = (heat - mn) / (mx - mn) * w
+        L = torch.round(g / g.amax((1, 2), keepdim=True) * 255.0).long()
+        pic = torch.round(base.float() * a_l[L][..., None] + colours[L] * b_l[L][..., None]).clamp_(0, 255).to(torch.uint8)
+        return pic, L
+
+    pics, levels, status = call()
+    pic_t, L_t = steps()
+    torch.cuda.synchronize()
+    assert not status[:, 0].any()
+    # the same steps, not the same contract: torch's own division and a fused multiply-add in its blend may move a last bit
+    same_l = float((torch.stack(levels).long() == L_t).float().mean())
+    same = float((torch.stack(pics) == pic_t).float().mean())
+
+    def window(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(inner):
+            fn()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) * 1e3 / inner
+
+    for _ in range(3):
+        window(call), window(steps)
+    t_call, t_steps = [], []
+    for _ in range(reps):
+        t_call.append(window(call))
+        t_steps.append(window(steps))
+    px = M * H * W
+    byt = px * (4 * 3 + 3 + 3 + 1)      # the map read three times, the base read, the picture and the levels written
+    stat = lambda t: {"median_us": round(statistics.median(t), 1), "min_us": round(min(t), 1), "max_us": round(max(t), 1)}
+    return {"maps": M, "size": [H, W], "inner_calls_per_window": inner, "heat_paint": stat(t_call), "torch_steps": stat(t_steps),
+            "speedup_median": round(statistics.median(t_steps) / statistics.median(t_call), 2),
+            "algorithmic_bytes": byt, "heat_paint_GBps": round(byt / statistics.median(t_call) / 1e3, 1),
+            "levels_equal_share": same_l, "pictures_equal_share": same,
+            "note": "device events around windows of calls issued back to back, so the host's enqueue cost counts where it exceeds the kernels'"}
+
+
 def polygons_leg(dev, reps, cli_images):
     import shutil
     import subprocess
@@ -815,6 +876,8 @@ def main():
                     help="measure the device string codec against the host codec per record; writes profiles/rle_strings_bench.json")
     ap.add_argument("--paint", action="store_true",
                     help="measure rle_paint against decode -> host blend -> upload; writes profiles/rle_paint_bench.json")
+    ap.add_argument("--heat", action="store_true",
+                    help="measure heat_paint against the same steps as torch device ops; writes profiles/rle_heat_bench.json")
     ap.add_argument("--decode", action="store_true", help="measure the decoder and rle_iou; writes profiles/rle_decode_bench.json")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--evaluator", action="store_true")
@@ -825,6 +888,14 @@ def main():
     if args.polygons:
         out = {"polygons": polygons_leg(dev, args.reps, args.cli_images), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
         path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_polygons_bench.json")
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out))
+        return
+    if args.heat:
+        out = {"heat": heat_leg(dev, args.reps), "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+        path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "rle_heat_bench.json")
         with open(path, "w") as f:
             json.dump(out, f, indent=1)
             f.write("\n")
