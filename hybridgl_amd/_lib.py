@@ -45,6 +45,13 @@ class HglSweepRef(C.Structure):
     _fields_ = [("k", C.POINTER(C.c_int32)), ("idx", C.c_void_p), ("iu", C.c_void_p), ("ceiling", C.c_void_p)]
 
 
+class HglViewPrompt(C.Structure):
+    """include/hybridgl.h HglViewPrompt: what the two CLIP views of a proposal show (ops.view_prompt builds it)"""
+    _fields_ = [("window", C.c_int), ("pad_permille", C.c_int), ("square", C.c_int), ("local_bg", C.c_int),
+                ("local_fill", C.c_float * 3), ("global_bg", C.c_int), ("global_fill", C.c_uint8 * 3),
+                ("marker_rgb", C.c_uint8 * 3), ("marker", C.c_int), ("thickness", C.c_int), ("grow", C.c_int)]
+
+
 class HglResBlockW(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "ln1_w", "ln1_b", "in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b",
@@ -170,6 +177,7 @@ PROTOTYPES = {
     "hgl_score_sentence": (_I, [_VP, _VP, _VP, _VP, _I, _F, _VP, _VP, _I, _I, _F, _I, _I, _F, _I, _I,
                                 _VP, _VP, _VP, _VP, _SZ, _VP]),
     "hgl_synthesize_views": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP]),
+    "hgl_synthesize_views_prompt": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, C.POINTER(HglViewPrompt), _VP, _VP, _VP]),
     "hgl_resize_pil_bilinear_workspace_bytes": (_SZ, [_I, _I, _I]),
     "hgl_resize_pil_bilinear": (_I, [_VP, _I, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _SZ, _VP]),
     "hgl_sam_encode_workspace_bytes": (_SZ, [C.POINTER(HglSamEncoderW)]),

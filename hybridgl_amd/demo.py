@@ -100,10 +100,12 @@ class HybridGL:
     """The three models, built once the way main.build_models builds them, behind one private ref-by-ref pipeline.  amg: the
     mask generator's settings over demo.py:44-54's (points_per_side=8, pred_iou_thresh=0.7, stability_score_thresh=0.7,
     crop_n_layers=0, crop_n_points_downscale_factor=1, min_mask_region_area=800); clip_checkpoint / sam_checkpoint / bpe_vocab:
-    files in place of the packages' defaults.  explain: every Segmentation carries an Explanation (the pipeline's keep_explain)."""
+    files in place of the packages' defaults.  explain: every Segmentation carries an Explanation (the pipeline's keep_explain).
+    view_prompt: what CLIP is shown for a proposal (the pipeline's view_prompt: a struct, a preset name or a spec)."""
 
     def __init__(self, clip_model="ViT-B/16", sam_model="default", clip_checkpoint=None, sam_checkpoint=None, bpe_vocab=None,
-                 precision=None, fusion_mode="G2L", heatmap="device", amg=None, device="cuda", explain=False):
+                 precision=None, fusion_mode="G2L", heatmap="device", amg=None, device="cuda", explain=False,
+                 view_prompt=None):
         from .backbone import CLIPViTFM
         from .main import AMG_DEFAULTS
         from .pipeline import HybridGLPipeline
@@ -130,7 +132,7 @@ class HybridGL:
         self.context_length = CLIP_CONFIGS[clip_model]["context_length"]
         self._pipe = HybridGLPipeline(self.model, fusion_mode=fusion_mode, mask_generator=self.generator, use_sam_masks=True,
                                       gem_model=self.gem_model, k_clamp="per_ref", record_predictions=True,
-                                      keep_explain=bool(explain))
+                                      keep_explain=bool(explain), view_prompt=view_prompt)
         self._image = None      # (the caller's object, image id, sam_img, image_norm, tensor_img) of the last image
         self._calls = 0
 
@@ -255,7 +257,10 @@ def default_argument_parser():
     p.add_argument("--topk_out", default="", metavar="PNG", help="the --topk proposals with the highest CLIP score, best last")
     p.add_argument("--topk", type=int, default=3, metavar="K")
     p.add_argument("--scores_json", default="", metavar="OUT", help="per text: the three score rows, both indices, the heat-map's mn / mx / peak")
-    p.add_argument("--fusion_mode", default="G2L", choices=["G2L", "L2G", "G2L&L2G"])
+    p.add_argument("--fusion_mode", default="G2L", choices=["G2L", "L2G", "G2L&L2G", "crop"])
+    p.add_argument("--view_prompt", default="", metavar="SPEC_OR_PRESET",
+                   help="what CLIP is shown for a proposal: a preset (hybridgl, black, gray, keep, red_circle, masked_crop, crop) or "
+                        "key=value,... over one (ops.parse_view_prompt); a box window needs --fusion_mode crop")
     p.add_argument("--heatmap", default="device", choices=["device", "given"])
     p.add_argument("--clip_model", default="ViT-B/16")
     p.add_argument("--sam_model", default="default")
@@ -291,7 +296,7 @@ def main(argv=None):
     rec = parse_record(args)
     hgl = HybridGL(args.clip_model, args.sam_model, bpe_vocab=args.bpe_vocab or None, precision=args.precision,
                    fusion_mode=args.fusion_mode, heatmap=args.heatmap, amg=amg,
-                   explain=bool(args.heat_out or args.topk_out or args.scores_json))
+                   explain=bool(args.heat_out or args.topk_out or args.scores_json), view_prompt=args.view_prompt or None)
     try:
         seg = hgl.segment(args.image, args.text, rec or None)[0]
     except EmptyProposals:

@@ -41,7 +41,12 @@ def default_argument_parser():
     p.add_argument("--seen_mode", action="store_true", help="PhraseCut: only phrases of COCO categories (:65)")
     p.add_argument("--split", default=None,
                    help="default: val (Hybridgl_main.py), test for --dataset phrasecut (Hybridgl_main_PhraseCut.py:42)")
-    p.add_argument("--fusion_mode", default="G2L", choices=["G2L", "L2G", "G2L&L2G"])
+    p.add_argument("--fusion_mode", default="G2L", choices=["G2L", "L2G", "G2L&L2G", "crop"],
+                   help="crop: the ViT on the local views alone (model/backbone.py:126); meant for --view_prompt crop / masked_crop")
+    p.add_argument("--view_prompt", default="", metavar="SPEC_OR_PRESET",
+                   help="what CLIP is shown for a proposal (ops.parse_view_prompt): hybridgl (default), black, gray, keep, red_circle, "
+                        "masked_crop, crop, or key=value,... over a preset, e.g. red_circle,thickness=3,marker_rgb=0:255:0; a box "
+                        "window (masked_crop, crop) needs --fusion_mode crop")
     p.add_argument("--refer_data_root", default="./refer/data")
     p.add_argument("--synthetic", type=int, default=4, help="number of seeded synthetic refs to evaluate")
     p.add_argument("--proposals", type=int, default=64)
@@ -501,7 +506,9 @@ def report_text(args, m, precision=None, rescued=None):
     """the result lines of Hybridgl_main.py:233-248 / Hybridgl_main_PhraseCut.py:224-238; rescued: HybridGLPipeline.rescue_stats,
     a line of its own when a rescue happened"""
     pc = args.dataset == "phrasecut"
-    return (f"\n\n fusion_mode={args.fusion_mode} "
+    from . import ops
+    prompt = ops.parse_view_prompt(getattr(args, "view_prompt", "") or None)
+    return (f"\n\n fusion_mode={args.fusion_mode} " + ("" if ops.view_prompt_is_default(prompt) else f"view_prompt={ops.view_prompt_name(prompt)} ")
             + (f"\nDataset: PhraseCut / {args.split}" if pc else f"\nDataset: {args.dataset} / {args.split} / {split_by(args.dataset)}") +
             f"\nOverall IoU / mean IoU"
             f"\npure hybridgl: {m['oIoU']:.2f} / {m['mIoU']:.2f}"
@@ -793,7 +800,7 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
             strings=getattr(args, "rle_strings", "host"))
     pipe = HybridGLPipeline(model, fusion_mode=args.fusion_mode, masking_block=getattr(args, "masking_block", 9), mask_generator=gen,
                             use_sam_masks=args.real, gem_model=gem_model, k_clamp=k_clamp, record_predictions=bool(save_dir), sweep=sweep,
-                            on_overflow=getattr(args, "on_overflow", "raise"))
+                            on_overflow=getattr(args, "on_overflow", "raise"), view_prompt=getattr(args, "view_prompt", "") or None)
     rr, jobs, make = dataset_items(args, dev, rank, world, sam_img_size=1024 if gen else 0, gem=gem_model is not None)
     if rr is not None and getattr(gen, "prefetch", None) is not None:
         rr.proposals = gen      # files, JSON and run lengths are the loader threads' work

@@ -1456,6 +1456,139 @@ def synthesize_views(sam_img, blurred, image_norm, masks, res=224, out=None):
     return loc, glo
 
 
+# ---- visual prompts (include/hybridgl.h HglViewPrompt; the rules are csrc/view_prompt.h) ----
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)      # Hybridgl_main.py:93
+_VP_ENUMS = {"window": {"frame": 0, "box": 1}, "local_bg": {"fill": 0, "keep": 1},
+             "global_bg": {"blur": 0, "keep": 1, "gray": 2, "fill": 3}, "marker": {"none": 0, "ellipse": 1, "box": 2},
+             "square": {"off": 0, "on": 1, "false": 0, "true": 1}}
+_VP_RANGES = {"window": (0, 1), "pad_permille": (0, 4000), "square": (0, 1), "local_bg": (0, 1), "global_bg": (0, 3),
+              "marker": (0, 2), "thickness": (1, 64), "grow": (0, 4096)}
+_VP_COLOURS = ("local_fill", "global_fill", "marker_rgb")
+VIEW_PROMPT_PRESETS = {
+    "hybridgl": {},                                                           # Hybridgl_main.py:93-125
+    "black": {"global_bg": "fill", "global_fill": (0, 0, 0)},                 # utils.py:336 'black'
+    "gray": {"global_bg": "gray"},
+    "keep": {"global_bg": "keep"},
+    "red_circle": {"global_bg": "keep", "marker": "ellipse", "marker_rgb": (255, 0, 0), "thickness": 2},   # utils.py:322 'circle'
+    "masked_crop": {"window": "box", "square": 1},
+    "crop": {"window": "box", "square": 1, "local_bg": "keep"},
+}
+
+
+def view_prompt(preset="hybridgl", **fields):
+    """-> _lib.HglViewPrompt: the preset (VIEW_PROMPT_PRESETS), then `fields` over it.  Enumerated fields take their number or
+    their name (window="box", global_bg="gray", marker="ellipse"); colours take three numbers.  ValueError names the field."""
+    if preset not in VIEW_PROMPT_PRESETS:
+        raise ValueError(f"view_prompt: unknown preset {preset!r} (one of {', '.join(VIEW_PROMPT_PRESETS)})")
+    vals = {"window": 0, "pad_permille": 0, "square": 0, "local_bg": 0, "local_fill": CLIP_MEAN, "global_bg": 0,
+            "global_fill": (0, 0, 0), "marker_rgb": (255, 0, 0), "marker": 0, "thickness": 1, "grow": 0}
+    p = _lib.HglViewPrompt()
+    for key, v in {**vals, **VIEW_PROMPT_PRESETS[preset], **fields}.items():
+        if key not in vals:
+            raise ValueError(f"view_prompt: unknown field {key!r}")
+        if key in _VP_COLOURS:
+            try:
+                v = [float(c) if key == "local_fill" else int(c) for c in v]
+            except (TypeError, ValueError):
+                v = []
+            ok = (lambda c: abs(c) < float("inf")) if key == "local_fill" else (lambda c: 0 <= c <= 255)
+            if len(v) != 3 or not all(ok(c) for c in v):
+                raise ValueError(f"view_prompt: {key} takes three " + ("finite numbers" if key == "local_fill" else "numbers 0..255"))
+            getattr(p, key)[:] = v
+            continue
+        if isinstance(v, str) and v in _VP_ENUMS.get(key, {}):
+            v = _VP_ENUMS[key][v]
+        try:
+            v = int(v) if not isinstance(v, float) or v == int(v) else None
+        except (TypeError, ValueError):
+            v = None
+        lo, hi = _VP_RANGES[key]
+        if v is None or not lo <= v <= hi:
+            names = f" or one of {', '.join(_VP_ENUMS[key])}" if key in _VP_ENUMS else ""
+            raise ValueError(f"view_prompt: {key} takes {lo}..{hi}{names}")
+        setattr(p, key, v)
+    return p
+
+
+def parse_view_prompt(spec):
+    """The command line's --view_prompt: a preset name, `key=value,key=value`, or a preset followed by such pairs
+    ("red_circle,thickness=3,marker_rgb=0:255:0"; the three numbers of a colour are joined by ':').  None / "" -> None."""
+    if spec is None or isinstance(spec, _lib.HglViewPrompt):
+        return spec
+    parts = [s.strip() for s in str(spec).split(",") if s.strip()]
+    if not parts:
+        return None
+    preset = parts.pop(0) if "=" not in parts[0] else "hybridgl"
+    fields = {}
+    for part in parts:
+        key, eq, val = (s.strip() for s in part.partition("="))
+        if not eq or not key or not val:
+            raise ValueError(f"view_prompt: {part!r} is not key=value")
+        if key in fields:
+            raise ValueError(f"view_prompt: {key} given twice")
+        fields[key] = val.split(":") if key in _VP_COLOURS else val
+    return view_prompt(preset, **fields)
+
+
+def view_prompt_fields(p):
+    """the struct as a plain dict (colours as tuples)"""
+    return {k: (tuple(getattr(p, k)) if k in _VP_COLOURS else getattr(p, k)) for k, _ in p._fields_}
+
+
+def view_prompt_is_default(p):
+    return p is None or view_prompt_fields(p) == view_prompt_fields(view_prompt())
+
+
+def view_prompt_name(p):
+    """the preset's name when the prompt is one, else its non-default fields as a spec (the result log's header)"""
+    f = view_prompt_fields(p if p is not None else view_prompt())
+    for name in VIEW_PROMPT_PRESETS:
+        if f == view_prompt_fields(view_prompt(name)):
+            return name
+    d = view_prompt_fields(view_prompt())
+    return ",".join(f"{k}={':'.join(str(c) for c in v) if isinstance(v, tuple) else v}" for k, v in f.items() if v != d[k])
+
+
+def view_prompt_needs_boxes(p):
+    return p.window == 1 or p.marker != 0
+
+
+def xywh_to_view_boxes(boxes):
+    """a record's XYWH boxes -> the inclusive int32 XYXY of hgl_mask_boxes: (x, y, x + w, y + h), as box_xyxy_to_xywh only
+    subtracts"""
+    b = boxes.to(torch.int32)
+    return torch.cat([b[:, :2], b[:, :2] + b[:, 2:]], dim=1).contiguous()
+
+
+def synthesize_views_prompt(sam_img, blurred, image_norm, masks, prompt, boxes=None, res=224, out=None):
+    """synthesize_views under a visual prompt (view_prompt / parse_view_prompt).  boxes: [N,4] int32 inclusive XYXY; None with
+    a prompt that needs boxes computes them with sam.mask_boxes.  blurred may be None unless the prompt's global background
+    is the blur."""
+    import ctypes as C
+    lib = _lib.load()
+    N, H, W = masks.shape
+    mp, masks = _u8(masks, "masks")
+    dev = masks.device
+    if out is not None:
+        loc, glo = out
+        assert tuple(loc.shape) == (N, 3, res, res) == tuple(glo.shape) and loc.is_contiguous() and glo.is_contiguous()
+    else:
+        loc = torch.empty((N, 3, res, res), dtype=torch.float32, device=dev)
+        glo = torch.empty((N, 3, res, res), dtype=torch.float32, device=dev)
+    if boxes is None and view_prompt_needs_boxes(prompt) and N > 0:
+        from . import sam
+        boxes = sam.mask_boxes(masks)
+    if boxes is not None and tuple(boxes.shape) != (N, 4):
+        raise ValueError(f"boxes: expected [{N}, 4], got {tuple(boxes.shape)}")
+    check(lib.hgl_synthesize_views_prompt(_dev(sam_img, torch.uint8, "sam_img"),
+                                          _dev(blurred, torch.uint8, "blurred") if blurred is not None else None,
+                                          _dev(image_norm, torch.float32, "image_norm"), mp,
+                                          _dev(boxes, torch.int32, "boxes") if boxes is not None else None, N, H, W, res,
+                                          C.byref(prompt), loc.data_ptr(), glo.data_ptr(), _stream()),
+          "hgl_synthesize_views_prompt")
+    return loc, glo
+
+
 def cv_gaussian_kernel_q8(k=15, sigma=0.0):
     """the k 8.8 fixed-point taps of cv2.GaussianBlur on uint8 (sum 256) -> ctypes uint16 array (host)"""
     import ctypes as C

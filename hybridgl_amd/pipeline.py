@@ -119,7 +119,7 @@ class HybridGLPipeline:
     def __init__(self, model, fusion_mode="G2L", masking_block=9, r=0.5, alpha=0.6, k1=3, k2=6, res=224,
                  mask_generator=None, use_sam_masks=False, fixed_proposals=None, cleanup_given_masks=False,
                  gem_model=None, k_clamp="persistent", image_cache=32, record_predictions=False, sweep=None,
-                 on_overflow="raise", keep_explain=False):
+                 on_overflow="raise", keep_explain=False, view_prompt=None):
         """mask_generator: a hybridgl_amd.sam.SamAutomaticMaskGenerator; when given, every step runs the
         SAM proposal stage (encoder, decoder, post-processing, NMS) on ref.sam_img first.
         use_sam_masks=False keeps ref.masks for the CLIP stage (fixed N; synthetic benchmark, where
@@ -139,7 +139,16 @@ class HybridGLPipeline:
         raises ops.SplitOverflow at the offending group.  "rescue": the groups that were in flight are run again in f32 and
         the loop goes on (run()'s docstring; rescue_stats); step() and metrics() are the same in both modes.
         keep_explain: keep, on the device, what the tail of the most recent ref (step) or group (run) was given and what it
-        computed per sentence -- explained(); nothing is computed or copied for it, and nothing changes with it off."""
+        computed per sentence -- explained(); nothing is computed or copied for it, and nothing changes with it off.
+        view_prompt: what CLIP is shown for a proposal -- an ops.view_prompt struct, a preset name or a `key=value,...` spec
+        (ops.parse_view_prompt).  None or the default prompt is the reference's pair of views through hgl_synthesize_views, as
+        ever; anything else goes through hgl_synthesize_views_prompt with the proposals' boxes.  A box window moves the local
+        view out of the frame the patch masks and the global stream live in, so it takes fusion_mode="crop"."""
+        prompt = ops.parse_view_prompt(view_prompt)
+        self.view_prompt = None if ops.view_prompt_is_default(prompt) else prompt
+        if self.view_prompt is not None and self.view_prompt.window == 1 and fusion_mode != "crop":
+            raise ValueError(f"view_prompt: a box window needs fusion_mode='crop', not {fusion_mode!r} (the patch masks and the "
+                             "global view stay in the frame)")
         if k_clamp not in ("persistent", "per_ref"):
             raise ValueError("k_clamp must be 'persistent' or 'per_ref'")
         if on_overflow not in ("raise", "rescue"):
@@ -196,6 +205,18 @@ class HybridGLPipeline:
             self.sweep_cum = torch.zeros((len(self.sweep), 4), dtype=torch.int64, device=dev)
             self.sweep_cum_ceiling = torch.zeros(2, dtype=torch.int64, device=dev)
             self._sweep_log = []      # per tail: (idx [C,S,2], iu [C,S,4], ceiling [S,3]) device tensors, in the order of iu_log
+
+    def _views(self, r0, masks, boxes, out=None):
+        """The two CLIP views of one image's proposals (Hybridgl_main.py:93-125): hgl_synthesize_views for the default prompt,
+        hgl_synthesize_views_prompt with the proposals' boxes (XYWH, as the records carry them) for any other."""
+        p = self.view_prompt
+        blurred = None
+        if p is None or p.global_bg == 0:
+            blurred = r0.blurred if r0.blurred is not None else ops.gaussian_blur_u8(r0.sam_img, 15)   # :99
+        if p is None:
+            return ops.synthesize_views(r0.sam_img, blurred, r0.image_norm, masks, self.res, out=out)
+        bx = ops.xywh_to_view_boxes(boxes) if ops.view_prompt_needs_boxes(p) else None
+        return ops.synthesize_views_prompt(r0.sam_img, blurred, r0.image_norm, masks, p, boxes=bx, res=self.res, out=out)
 
     def _join_side_streams(self, cur, outs):
         """The caller's stream waits for both side streams; every tensor that leaves them is recorded on the caller's
@@ -285,8 +306,7 @@ class HybridGLPipeline:
                     # (random-weight SAM logits are pixel noise, which is not what the clean-up sees in practice)
                     cm, _ = gen_here.cleanup_fixed(ref.masks.view(torch.uint8))
                     ref = dataclasses.replace(ref, masks=cm.view(torch.bool))
-            blurred = ref.blurred if ref.blurred is not None else ops.gaussian_blur_u8(ref.sam_img, 15)   # :99
-            local, glob = ops.synthesize_views(ref.sam_img, blurred, ref.image_norm, ref.masks, self.res)
+            local, glob = self._views(ref, ref.masks, ref.boxes)
             hybrid = m(local, glob, ref.masks, masking_block=self.masking_block, fusion_mode=self.fusion_mode)
             if from_gen and ref.image_id is not None:
                 self._cache_id, self._cache_ref, self._cache_hybrid = ref.image_id, ref, hybrid
@@ -978,10 +998,7 @@ class HybridGLPipeline:
             local = torch.empty((int(moff[-1]), 3, self.res, self.res), dtype=torch.float32, device=dev)
             glob = torch.empty_like(local)
             for j, i in enumerate(todo):
-                r0, mk = live[i][0][0], live[i][1]
-                blurred = r0.blurred if r0.blurred is not None else ops.gaussian_blur_u8(r0.sam_img, 15)   # :99
-                ops.synthesize_views(r0.sam_img, blurred, r0.image_norm, mk, self.res,
-                                     out=(local[moff[j]:moff[j + 1]], glob[moff[j]:moff[j + 1]]))
+                self._views(live[i][0][0], live[i][1], live[i][2], out=(local[moff[j]:moff[j + 1]], glob[moff[j]:moff[j + 1]]))
             hybrid_all = m(local, glob, [live[i][1] for i in todo], masking_block=self.masking_block, fusion_mode=self.fusion_mode)
             for j, i in enumerate(todo):
                 live[i][3] = hybrid_all[moff[j]:moff[j + 1]]

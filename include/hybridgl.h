@@ -445,6 +445,30 @@ int hgl_synthesize_views(const uint8_t* sam_img, const uint8_t* blurred, const f
                          const uint8_t* masks, int N, int H, int W, int res,
                          float* local_imgs, float* global_imgs, void* stream);
 
+/* Visual prompts: what the two views show, as one plain struct passed by value to the kernel.  The rules -- box clamping,
+ * window, taps, gray, marker bands, ranges -- are csrc/view_prompt.h, integer arithmetic throughout. */
+typedef struct HglViewPrompt {
+  int window;                 /* 0 frame, 1 the mask's box: what both views look at */
+  int pad_permille;           /* 0..4000: margin of the box window, in thousandths of the box's longer side */
+  int square;                 /* 0/1: the box window is the square about the box's centre */
+  int local_bg;               /* outside the mask in the local view: 0 local_fill, 1 the image */
+  float local_fill[3];        /* in the units of image_norm (the CLIP mean by default) */
+  int global_bg;              /* outside the mask in the global view: 0 blurred, 1 the image, 2 its gray, 3 global_fill */
+  uint8_t global_fill[3];
+  uint8_t marker_rgb[3];
+  int marker;                 /* drawn on the global view only: 0 none, 1 ellipse, 2 box */
+  int thickness;              /* 1..64 source pixels */
+  int grow;                   /* 0..4096 source pixels between the box and the band */
+} HglViewPrompt;
+
+/* hgl_synthesize_views under a prompt.  boxes_xyxy: [N,4] int32 inclusive XYXY on the device (what hgl_mask_boxes writes),
+ * NULL unless window == box or marker != none; blurred: NULL unless global_bg == blur.  H, W <= 8192.  At the default prompt
+ * (frame, CLIP-mean fill, blur, no marker) the views are hgl_synthesize_views' bit for bit.  No workspace, no
+ * synchronisation. */
+int hgl_synthesize_views_prompt(const uint8_t* sam_img, const uint8_t* blurred, const float* image_norm, const uint8_t* masks,
+                                const int32_t* boxes_xyxy, int N, int H, int W, int res, const HglViewPrompt* prompt,
+                                float* local_imgs, float* global_imgs, void* stream);
+
 /* ------------------------------------------------------------------------
  * SAM ViT-H mask proposals (third_party/segment-anything/segment_anything/,
  * driven by SamAutomaticMaskGenerator at Hybridgl_main.py:66-74,85)
