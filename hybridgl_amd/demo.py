@@ -203,7 +203,7 @@ class HybridGL:
         n = len(texts)
         records = pipe.predictions()      # waits for the winners' runs; the indices are winning_indices()'s
         assert len(records) == n
-        proposals = pipe._cache_ref.masks
+        proposals = pipe.last_image()[1]
         H, W = ref.sam_img.shape[:2]
         idx = torch.stack(pipe.idx_log)      # [n,2] int32 on the device: the tail's own
         winners = ops.rle_encode(proposals, idx.reshape(-1), ops.rle_slot_words(H, W))

@@ -824,8 +824,8 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
             try:
                 pipe.step(ref)
                 n += 1
-            except EmptyProposals:
-                pipe.skipped = getattr(pipe, "skipped", 0) + 1
+            except EmptyProposals:      # counted in pipe.skipped
+                pass
     else:
         n = pipe.run(loader, group=args.group, proposal_cap=cap)
     torch.cuda.synchronize(dev)
@@ -837,7 +837,7 @@ def evaluate(args, model, gen, gem_model, dev, rank=0, world=1, dist=None):
     m = pipe.metrics(dist)      # one all-gather of the metric rows; identical on every rank
     stats = {"refs": n, "seconds": dt, "seconds_job": D.max_over_ranks(dt, dist, dev), "loader_wait_s": loader.wait_s, "loader_make_s": loader.make_s,
              "images_decoded": rr.decoded if rr is not None else None, "image_cache_hits": pipe.cache_hits,
-             "skipped": getattr(pipe, "skipped", 0), "groups": getattr(pipe, "groups_run", None),
+             "skipped": pipe.skipped, "groups": pipe.groups_run,
              "workers": args.workers, "group": args.group,
              # this rank's own (ranks rescue independently); zeros without --on_overflow rescue
              "split_overflow_rescued": dict(pipe.rescue_stats, positions=list(pipe.rescue_stats["positions"]))}

@@ -16,7 +16,9 @@ reference's per-ref work:
 and accumulates cum_I/cum_U and the per-sentence IoUs on the device (Hybridgl_main.py:52-55,
 240-247).  Metrics are read back once, at the end.
 """
-from dataclasses import dataclass, field
+import os
+import time
+from dataclasses import dataclass, field, replace
 from typing import List, Optional
 
 import numpy as np
@@ -67,6 +69,31 @@ class RefBatch:
 
 class EmptyProposals(RuntimeError):
     """the proposal stage kept no mask for this image"""
+
+
+@dataclass
+class _Live:
+    """One image of a CLIP stage: its items, then an image-cache entry -- masks bool [n,H,W], boxes XYWH, hybrid features [n,E],
+    GEM image features -- of which the stage computes what is still None."""
+    refs: list
+    masks: Optional[torch.Tensor]
+    boxes: Optional[torch.Tensor]
+    hybrid: Optional[torch.Tensor] = None
+    gem: Optional[torch.Tensor] = None
+
+@dataclass
+class _Group:
+    """A group in flight between run()'s stages: _sam_begin makes it, _sam_end adds props and ready, _clip_group consumes it."""
+    LATE = object()              # in `held`: the group whose CLIP stage is enqueued next files this image's cache entry
+    gid: int                     # its number in groups_run
+    units: list
+    held: list                   # per unit: the image-cache entry pinned at look-up (a later put may evict it from the dict),
+                                 # LATE, or None (not cached -- or cached as "no proposals")
+    fresh: Optional[list] = None     # the indices of the units that go through the generator
+    state: object = None         # the generator's group state
+    ev_enc: object = None        # the event behind its encoder pass
+    props: Optional[list] = None     # per unit (masks u8 [n,H,W], boxes XYWH) or None = an image of the cache; no list: the items' own
+    ready: object = None         # the event behind the proposal stage
 
 
 def _adopt(ref, streams, produced=None):
@@ -165,9 +192,17 @@ class HybridGLPipeline:
         # refs per image).  0 = off.  Entries are device tensors: ~25 MB per 640 x 480 image with 64 proposals.
         self.image_cache = int(image_cache)
         self._img_cache = {}
+        self._cache_cap = self.image_cache      # run() widens it to two groups
         self.cache_hits = 0
+        # step(): (image id, image-cache entry) of the last image that had an id -- a cache of one, apart from _img_cache
+        self._last = (None, (None, None, None, None))
+        self.last_proposals = None      # what the proposal stage of the last step() / group returned
+        # images skipped for want of a proposal; run(): groups begun, refs scored by the running call
+        self.skipped = self.groups_run = self._done = 0
+        self.collected = None      # run(collect=True): step()'s return value per ref
+        self.group_marks = self.stage_marks = None      # opt-in timelines: a list assigned from outside switches one on
+        self._s_sam = self._s_clip = self._s_text = self._ev = None      # _streams() makes them
         self.k_clamp = k_clamp
-        import os
         # the per-sentence tail as ONE hgl_score_ref call per ref (HYBRIDGL_FUSED_TAIL=0: the per-sentence launches)
         self.fused_tail = os.environ.get("HYBRIDGL_FUSED_TAIL", "1") != "0"
         # run(): the tails of ALL refs of a group in one hgl_score_group call (HYBRIDGL_GROUP_TAIL=0: one hgl_score_ref per ref)
@@ -235,54 +270,25 @@ class HybridGLPipeline:
                 for y in x:
                     rec(y)
         rec(outs)
-        rec(getattr(self, "last_proposals", None))
+        rec(self.last_proposals)
 
     def step(self, ref: RefBatch, run_sam=True):
         """One dataset item; returns the device tensors of the last sentence (idx, scores).
         run_sam=False: the proposal stage of this ref is not part of this call (it ran earlier / on another stream)."""
-        import dataclasses
-        m = self.model
         _adopt(ref, (torch.cuda.current_stream(),))
         gen_here = self.mask_generator if run_sam else None
-        # The text encoder (9 strings: small, latency-bound kernels) is independent of the image path: it runs on its
-        # own stream underneath the SAM / CLIP image kernels and is joined before the scoring tail.
-        cur = torch.cuda.current_stream()
-        if not hasattr(self, "_s_text"):
-            self._streams()
-        ev_in, ev_text = torch.cuda.Event(), torch.cuda.Event()
-        ev_in.record(cur)
-        self._s_text.wait_event(ev_in)
-        heat = None
-        with torch.cuda.stream(self._s_text):
-            text = m.model.encode_text(ref.tokens, seq_len=ref.token_len)
-            gem_rows = [s.gem_row for s in ref.sentences if s.imgattn is None]
-            if gem_rows:
-                # Hybridgl_main.py:200-201: gem_model(tensor_img, [noun_phrase])[0] -> T.Resize((h, w), antialias=True).
-                # The image tower depends on the image only (the reference re-runs it for every sentence); the
-                # prompts' text features come out of the same text-encoder batch.
-                from . import gem as G
-                if self.gem_model is None or ref.tensor_img is None or any(r is None for r in gem_rows):
-                    raise ValueError("a sentence without imgattn needs gem_model, RefBatch.tensor_img and Sentence.gem_row")
-                if ref.image_id is not None and getattr(self, "_gem_cache_id", None) == ref.image_id:
-                    gfeat = self._gem_cache_feat
-                else:
-                    gfeat = self.gem_model.image_features(ref.tensor_img)
-                    if ref.image_id is not None:
-                        self._gem_cache_id, self._gem_cache_feat = ref.image_id, gfeat
-                maps = self.gem_model.heatmap(gfeat, _rows(text, gem_rows), ref.tensor_img.shape[-1])
-                heat = G.resize_antialias(maps, ref.sam_img.shape[:2])
-                heat.record_stream(cur)
-            ev_text.record(self._s_text)
-        text.record_stream(cur)
         # Per-image caching (SURVEY.md 8f-3): the dataset yields one item per REF and the same image backs
         # several consecutive refs (Hybridgl_main.py:79); proposals, views and hybrid features depend on the
         # image only, so they are computed once per image.  Results are identical.
         from_gen = self.mask_generator is not None and self.use_sam_masks     # given proposals belong to the ITEM, not to the image
-        if from_gen and ref.image_id is not None and getattr(self, "_cache_id", None) == ref.image_id:
-            hybrid = self._cache_hybrid
-            ref = dataclasses.replace(self._cache_ref, tokens=ref.tokens, token_len=ref.token_len, sentences=ref.sentences,
-                                      target=ref.target, index=ref.index)
-        else:
+        hit = self._last[1] if ref.image_id is not None and self._last[0] == ref.image_id else (None, None, None, None)
+        # (the GEM features are the image's whatever the source of the proposals)
+        unit = _Live([ref], *hit) if from_gen else _Live([ref], None, None, gem=hit[3])
+        # The text encoder (9 strings: small, latency-bound kernels) is independent of the image path: it runs on its
+        # own stream underneath the SAM / CLIP image kernels and is joined before the scoring tail -- so the text half of
+        # the stage is enqueued here, ahead of the proposal stage and its read-backs, and the rest of the stage after it.
+        front = self._stage_text([unit], serial=False)
+        if unit.hybrid is None:
             if gen_here is not None:
                 # Hybridgl_main.py:85 mask_generator.generate(sam_img), kept on the device
                 # a proposal store (hybridgl_amd/proposals.py) is keyed by the image id; SAM's own generator is called as ever
@@ -297,32 +303,28 @@ class HybridGLPipeline:
                     prop = gen_here.propose(ref.sam_img, resized=ref.sam_resized)
                 if self.use_sam_masks:
                     if prop[0].shape[0] == 0:
+                        self.skipped += 1
                         raise EmptyProposals("no proposals")
-                    ref = dataclasses.replace(ref, masks=prop[0].view(torch.bool) if prop[0].dtype == torch.uint8 else prop[0],
-                                              boxes=prop[1].contiguous())
+                    ref = replace(ref, masks=prop[0].view(torch.bool) if prop[0].dtype == torch.uint8 else prop[0],
+                                  boxes=prop[1].contiguous())
                 self.last_proposals = prop
                 if self.cleanup_given_masks and not self.use_sam_masks:
                     # synthetic benchmark: the small-region clean-up runs on the proposal-shaped seeded masks
                     # (random-weight SAM logits are pixel noise, which is not what the clean-up sees in practice)
                     cm, _ = gen_here.cleanup_fixed(ref.masks.view(torch.uint8))
-                    ref = dataclasses.replace(ref, masks=cm.view(torch.bool))
-            local, glob = self._views(ref, ref.masks, ref.boxes)
-            hybrid = m(local, glob, ref.masks, masking_block=self.masking_block, fusion_mode=self.fusion_mode)
-            if from_gen and ref.image_id is not None:
-                self._cache_id, self._cache_ref, self._cache_hybrid = ref.image_id, ref, hybrid
-        cur.wait_event(ev_text)
-        self._explained = []      # explained() speaks of this ref alone
-        return hybrid, text, self._score_ref(ref, hybrid, text, heat)
+                    ref = replace(ref, masks=cm.view(torch.bool))
+            unit.masks, unit.boxes = ref.masks, ref.boxes
+        (out,) = self._stage([unit], front, now=True)
+        if ref.image_id is not None:
+            self._last = (ref.image_id, (unit.masks, unit.boxes, unit.hybrid, unit.gem) if from_gen else (None, None, None, unit.gem))
+        return out
+
+    def last_image(self):
+        """(image id, masks bool [N,H,W], boxes XYWH [N,4]): the generator's proposals for the last image step() scored, which a
+        step() on the same image id uses again; Nones before there is one, or when the proposals were the items' own."""
+        return (self._last[0],) + self._last[1][:2]
 
     _DEFERRED = object()
-
-    def _log_tail(self, ref_index, n, idx, iu, masks=None):
-        for j in range(n):
-            self.iu_log.append((iu[j, 0:2], iu[j, 2:4]))
-            self.iu_owner.append((ref_index, j))
-            self.idx_log.append(idx[j])
-        if self.record_predictions:
-            self._record_tail(ref_index, n, masks, idx)
 
     # ---- predictions: the winning masks of every sentence as run lengths (record_predictions=True) --------------------------
     def _record_tail(self, ref_index, n, masks, idx):
@@ -377,17 +379,10 @@ class HybridGLPipeline:
 
     def _flush_tails(self, defer):
         """the deferred tails of a group's refs in one hgl_score_group call; returns each ref's last-sentence tensors, in order"""
-        if not defer:
-            return []
         outs = ops.score_group(defer, self.model.model._logit_scale_exp, self.r, self.alpha, cum=self.cum, want_scores=True)
         if self.sweep is not None:
             self._sweep_tails(defer)
-        last = []
-        for q, (idx, iu, sc, sn, gm) in zip(defer, outs):
-            self._log_tail(q["ref_index"], len(q["sentences"]), idx, iu, q["masks"])
-            if self.keep_explain:
-                self._explain(q["ref_index"], [(r["imgattn"], r["dirflag"], r["black"]) for r in q["sentences"]], sc, sn, gm)
-            last.append((idx[-1], sc[-1], sn[-1], gm[-1]))
+        last = [self._file_tail(q, out) for q, out in zip(defer, outs)]
         defer.clear()
         return last
 
@@ -401,79 +396,94 @@ class HybridGLPipeline:
     def _score_ref(self, ref, hybrid, text, heat, defer=None):
         """the per-sentence tail of Hybridgl_main.py:153-230 for one ref; returns the tensors of its last sentence.  defer (a
         list): a ref whose tail the fused kernels serve is appended to it instead (for _flush_tails) and _DEFERRED returned"""
-        m = self.model
+        scale = self.model.model._logit_scale_exp
+        ref_index, fused = self._ref_state(ref, hybrid.shape[0], text)
+        if fused is None:
+            return None
+        heats = iter(heat) if heat is not None else None
+        q = self._request(ref, hybrid, text, [s.imgattn if s.imgattn is not None else next(heats) for s in ref.sentences], ref_index)
+        if fused and defer is not None:
+            defer.append(q)
+            return self._DEFERRED
+        if fused:
+            # hgl_score_ref: every mask byte read once for all sentences' heat-maps, one scoring workgroup per sentence,
+            # both IoUs of every sentence and the accumulators of Hybridgl_main.py:52-55 in the same four launches
+            out = ops.score_ref(hybrid, text, ref.boxes, ref.masks, q["sentences"], scale, self.r, q["k1"], q["k2"], self.alpha,
+                                cum=self.cum, want_scores=True)
+            if self.sweep is not None:
+                self._sweep_tails([q])
+            return self._file_tail(q, out)
+        out = [], [], [], [], []      # per sentence: idx [2], (IU_pure, IU_final), score_clip, score_neg, gem_score
+        for s, r in zip(ref.sentences, q["sentences"]):
+            gem = ops.coherence_scores(r["imgattn"], ref.masks, r["dirflag"], r["black"])
+            idx, sc, sn = ops.score_sentence(hybrid, text[s.sentence_row], text[s.noun_phrase_row], _rows(text, s.other_noun_rows),
+                                             ref.boxes, gem, scale, self.r, q["k1"], q["k2"], self.alpha, r["relaword"],
+                                             r["has_other_nouns"])
+            iu0 = ops.iou_select(ref.masks, idx, 0, r["target"])
+            iu1 = ops.iou_select(ref.masks, idx, 1, r["target"])
+            self.cum[0:2] += iu0
+            self.cum[2:4] += iu1
+            for col, v in zip(out, (idx, (iu0, iu1), sc, sn, gem)):
+                col.append(v)
+        return self._file_tail(q, out)
+
+    def _ref_state(self, ref, n, text):
+        """What a ref with n proposals changes before its tail, whichever route serves it: the k1 / k2 clamp and the count of refs
+        -> (its dataset position, whether the fused kernels serve it -- None for a ref without a sentence)."""
         # the k1/k2 clamp of Hybridgl_main.py:178-181 persists across refs in the reference
         if self.k_clamp == "per_ref":
             self.k1, self.k2 = self._k0
-        self.k1 = min(self.k1, hybrid.shape[0])
-        self.k2 = min(self.k2, hybrid.shape[0])
+        self.k1 = min(self.k1, n)
+        self.k2 = min(self.k2, n)
         if self.sweep is not None:      # the same rule for every configuration's own pair
             if self.k_clamp == "per_ref":
                 self._sweep_k = [list(k) for k in self._sweep_k0]
-            self._sweep_k = [[min(k[0], hybrid.shape[0]), min(k[1], hybrid.shape[0])] for k in self._sweep_k]
+            self._sweep_k = [[min(k[0], n), min(k[1], n)] for k in self._sweep_k]
         ref_index = ref.index if ref.index is not None else self._n_refs
         self._n_refs += 1
         if not ref.sentences:        # an item without a sentence scores nothing (the reference's inner loop does not run)
-            return None
-        heats = iter(heat) if heat is not None else None
-        attn = [s.imgattn if s.imgattn is not None else next(heats) for s in ref.sentences]
+            return ref_index, None
         fused = self.fused_tail and text.is_contiguous() and all(
             list(s.other_noun_rows) == list(range(s.other_noun_rows[0], s.other_noun_rows[0] + len(s.other_noun_rows)))
             for s in ref.sentences if s.other_noun_rows)
         if self.sweep is not None and not fused:
             raise ValueError(f"sweep: the fused tail cannot serve ref {ref_index} (other-noun rows that are not consecutive, text "
                              "that is not contiguous, or HYBRIDGL_FUSED_TAIL=0), and the sweep runs on the fused tail's operands")
-        if fused:
-            # hgl_score_ref: every mask byte read once for all sentences' heat-maps, one scoring workgroup per sentence,
-            # both IoUs of every sentence and the accumulators of Hybridgl_main.py:52-55 in the same four launches
-            recs = [dict(sentence_row=s.sentence_row, noun_phrase_row=s.noun_phrase_row,
-                         other_row0=s.other_noun_rows[0] if s.other_noun_rows else 0, n_other=len(s.other_noun_rows),
-                         dirflag=s.dirflag, relaword=s.relaflag, has_other_nouns=s.n_nouns != 0, black=black_for(s.relaflag),
-                         imgattn=a if a.is_contiguous() else a.contiguous(), target=s.target if s.target is not None else ref.target)
-                    for s, a in zip(ref.sentences, attn)]
-            if defer is not None:
-                defer.append(dict(hybrid=hybrid, text=text, boxes=ref.boxes, masks=ref.masks, sentences=recs, k1=self.k1, k2=self.k2,
-                                  ref_index=ref_index))
-                if self.sweep is not None:
-                    defer[-1]["sweep_k"] = self._sweep_k
-                return self._DEFERRED
-            idx, iu, sc, sn, gm = ops.score_ref(hybrid, text, ref.boxes, ref.masks, recs, m.model._logit_scale_exp, self.r, self.k1,
-                                                self.k2, self.alpha, cum=self.cum, want_scores=True)
-            if self.sweep is not None:
-                self._sweep_tails([dict(hybrid=hybrid, text=text, boxes=ref.boxes, masks=ref.masks, sentences=recs,
-                                        sweep_k=self._sweep_k)])
-            self._log_tail(ref_index, len(recs), idx, iu, ref.masks)
-            if self.keep_explain:
-                self._explain(ref_index, [(r["imgattn"], r["dirflag"], r["black"]) for r in recs], sc, sn, gm)
-            return (idx[-1], sc[-1], sn[-1], gm[-1]) if recs else None
-        last = None
-        kept = []
-        for sent_no, (s, imgattn) in enumerate(zip(ref.sentences, attn)):
-            gem = ops.coherence_scores(imgattn, ref.masks, s.dirflag, black_for(s.relaflag))
-            others = _rows(text, s.other_noun_rows)
-            idx, sc, sn = ops.score_sentence(hybrid, text[s.sentence_row], text[s.noun_phrase_row], others,
-                                             ref.boxes, gem, m.model._logit_scale_exp, self.r, self.k1,
-                                             self.k2, self.alpha, s.relaflag, s.n_nouns != 0)
-            tgt = s.target if s.target is not None else ref.target
-            iu0 = ops.iou_select(ref.masks, idx, 0, tgt)
-            iu1 = ops.iou_select(ref.masks, idx, 1, tgt)
-            self.cum[0:2] += iu0
-            self.cum[2:4] += iu1
-            self.iu_log.append((iu0, iu1))
-            self.iu_owner.append((ref_index, sent_no))
-            self.idx_log.append(idx)
-            last = (idx, sc, sn, gem)
-            kept.append((imgattn, s.dirflag, black_for(s.relaflag), sc, sn, gem))
+        return ref_index, fused
+
+    def _request(self, ref, hybrid, text, attn, ref_index):
+        """One ref's tail as ops.score_ref / ops.score_group / _sweep_tails take it, under the clamp as it stands; attn: the
+        heat-map of every sentence.  (other_row0 / n_other mean something only to the fused kernels, which take consecutive rows.)"""
+        recs = [dict(sentence_row=s.sentence_row, noun_phrase_row=s.noun_phrase_row,
+                     other_row0=s.other_noun_rows[0] if s.other_noun_rows else 0, n_other=len(s.other_noun_rows),
+                     dirflag=s.dirflag, relaword=s.relaflag, has_other_nouns=s.n_nouns != 0, black=black_for(s.relaflag),
+                     imgattn=a if a.is_contiguous() else a.contiguous(), target=s.target if s.target is not None else ref.target)
+                for s, a in zip(ref.sentences, attn)]
+        q = dict(hybrid=hybrid, text=text, boxes=ref.boxes, masks=ref.masks, sentences=recs, k1=self.k1, k2=self.k2, ref_index=ref_index)
+        if self.sweep is not None:
+            q["sweep_k"] = self._sweep_k
+        return q
+
+    def _file_tail(self, q, out):
+        """A finished tail (q: its request) into the logs; out = (idx, iu, score_clip, score_neg, gem_score), per sentence: a fused
+        tail's tensors or the per-sentence route's lists with iu as (IU_pure, IU_final) pairs.  Returns the last sentence's."""
+        idx, iu, sc, sn, gm = out
+        self._log_tail(q["ref_index"], len(q["sentences"]), idx, iu, q["masks"])
         if self.keep_explain:
-            self._explain(ref_index, [k[:3] for k in kept], *[[k[c] for k in kept] for c in (3, 4, 5)])
+            self._explain(q["ref_index"], [(r["imgattn"], r["dirflag"], r["black"]) for r in q["sentences"]], sc, sn, gm)
+        return idx[-1], sc[-1], sn[-1], gm[-1]
+
+    def _log_tail(self, ref_index, n, idx, iu, masks=None):
+        for j in range(n):
+            self.iu_log.append((iu[j, 0:2], iu[j, 2:4]) if torch.is_tensor(iu) else iu[j])
+            self.iu_owner.append((ref_index, j))
+            self.idx_log.append(idx[j])
         if self.record_predictions:
-            n = len(ref.sentences)
-            self._record_tail(ref_index, n, ref.masks, torch.stack(self.idx_log[-n:]))
-        return last
+            self._record_tail(ref_index, n, masks, idx if torch.is_tensor(idx) else torch.stack(idx))
 
     # ---- the evaluation loop at the grouped rate ----------------------------------------------------------------------
     def _streams(self):
-        if not hasattr(self, "_s_sam"):
+        if self._s_sam is None:
             self._s_sam, self._s_clip, self._s_text = _side_streams(self.model.device)
             self._ev = torch.cuda.Event()
         return self._s_sam, self._s_clip
@@ -531,8 +541,7 @@ class HybridGLPipeline:
         if self.record_predictions:      # what the loop has recorded so far is filed before the rehearsal's records are dropped
             self._harvest_predictions(wait=True)
         keep = self._checkpoint()
-        extras = (getattr(self, "groups_run", 0), getattr(self, "group_marks", None), getattr(self, "stage_marks", None),
-                  dict(self.rescue_stats, positions=list(self.rescue_stats["positions"])))
+        extras = (self.groups_run, self.group_marks, self.stage_marks, dict(self.rescue_stats, positions=list(self.rescue_stats["positions"])))
         self.group_marks = self.stage_marks = None
         cap = proposals if (gen is not None and self.use_sam_masks) else None
         try:
@@ -602,7 +611,7 @@ class HybridGLPipeline:
         if total is not None:
             group = self.balanced_group(total, group)
         cur = torch.cuda.current_stream()
-        self._serial = bool(serial)
+        serial = bool(serial)
         if serial:
             s_sam = s_clip = cur
         else:
@@ -619,16 +628,14 @@ class HybridGLPipeline:
             led = RescueLedger()
             # the total the loop starts from, in stream order before anything of this run
             self._rs = dict(snaps=[], gate=None, base=self._snapshot(None, cur), cap=proposal_cap, group=group, cur=cur,
-                            s_sam=s_sam, s_clip=s_clip, serial=bool(serial))
+                            s_sam=s_sam, s_clip=s_clip, serial=serial)
         if not serial:
             self._ev.record(cur)
             s_sam.wait_event(self._ev)
             s_clip.wait_event(self._ev)
         self.collected = [] if collect else None
-        self.skipped = getattr(self, "skipped", 0)
         self._done = 0
         pending = None
-        self.groups_run = getattr(self, "groups_run", 0)
         # items of one image are merged into a unit only when the proposals come from the generator (then they are a function
         # of the image); with given proposals every item keeps its own masks / boxes, as step() does
         it = iter(self._units(loader, group, merge=gen is not None and self.use_sam_masks))
@@ -640,8 +647,7 @@ class HybridGLPipeline:
         try:
             for units in it:
                 self.groups_run += 1
-                if getattr(self, "group_marks", None) is not None:      # host-side stamp of every group boundary (tools/first_use.py)
-                    import time
+                if self.group_marks is not None:      # host-side stamp of every group boundary (tools/first_use.py)
                     self.group_marks.append(time.perf_counter())
                 produced = None
                 if not serial:      # items a lazy loader built on the caller's stream just now
@@ -654,25 +660,25 @@ class HybridGLPipeline:
                     led.open(self.groups_run, units)
                     if self._rs["gate"] is not None and not serial:      # no proposal stage beside a snapshot
                         s_sam.wait_event(self._rs["gate"])
-                state, ev_enc, cached, held, fresh = self._sam_begin(units, pending, s_sam, proposal_cap, serial, group)
+                g = self._sam_begin(self.groups_run, units, pending, s_sam, proposal_cap, serial, group)
                 if pending is not None:
                     with torch.cuda.stream(s_clip):
-                        if ev_enc is not None:
-                            s_clip.wait_event(ev_enc)
-                        self._clip_stage(pending, led)
-                props, ready, seen = self._sam_end(units, state, cached, fresh, s_sam, led is not None)
-                enqueued = pending[4] if pending is not None else None      # the group whose CLIP stage went out just now
-                pending = (units, props, ready, held, self.groups_run)
+                        if g.ev_enc is not None:
+                            s_clip.wait_event(g.ev_enc)
+                        self._clip_group(pending, serial, led)
+                seen = self._sam_end(g, s_sam, led is not None)
+                enqueued = pending.gid if pending is not None else None      # the group whose CLIP stage went out just now
+                pending = g
                 if led is not None:
                     if self._rescue_judge(led, it, seen):
                         pending = None
                     elif enqueued is not None:
-                        self._rescue_stage_end(enqueued, ready)
+                        self._rescue_stage_end(enqueued, g.ready)
             if pending is not None:
                 with torch.cuda.stream(s_clip):
-                    self._clip_stage(pending, led)
+                    self._clip_group(pending, serial, led)
                 if led is not None:
-                    self._rescue_stage_end(pending[4], None)
+                    self._rescue_stage_end(pending.gid, None)
             if led is not None:
                 self._rescue_judge(led, it, None)
         finally:
@@ -684,29 +690,26 @@ class HybridGLPipeline:
             self._join_side_streams(cur, self.collected)
         return self._done
 
-    def _sam_begin(self, units, pending, s_sam, proposal_cap, serial, group):
+    def _sam_begin(self, gid, units, pending, s_sam, proposal_cap, serial, group):
         """The image-cache look-up of a group and everything of its proposal stage up to the first count read-back, enqueued on
-        s_sam without a wait -> (the generator's group state or None, the event behind its encoder pass or None, cached [n],
-        held [n], the units that go through the generator)."""
+        s_sam without a wait -> the _Group (held, fresh, the generator's group state and the event behind its encoder pass)."""
         gen = self.mask_generator
-        state = None
-        ev_enc = None
         # images seen lately (or in the group whose CLIP stage is about to be enqueued: it files them before this
         # group's CLIP stage looks): no proposal stage, no hybrid forward for them
         cached = [False] * len(units)
-        held = [None] * len(units)      # the cache entry itself, pinned at look-up (a later put may evict it from the dict)
+        g = _Group(gid, units, held=[None] * len(units))
         if self.image_cache > 0 and gen is not None and self.use_sam_masks:
             self._cache_cap = max(self.image_cache, 2 * group)
-            in_pending = {u[0].image_id for u in pending[0]} if pending is not None else set()
+            in_pending = {u[0].image_id for u in pending.units} if pending is not None else set()
             for i, u in enumerate(units):
                 iid = u[0].image_id
                 if iid is None:
                     continue
                 if iid in self._img_cache:
-                    cached[i], held[i] = True, ("entry", self._img_cache[iid])
+                    cached[i], g.held[i] = True, self._img_cache[iid]
                 elif iid in in_pending:
-                    cached[i], held[i] = True, ("late",)
-        fresh = [i for i, c in enumerate(cached) if not c]
+                    cached[i], g.held[i] = True, g.LATE
+        fresh = g.fresh = [i for i, c in enumerate(cached) if not c]
         if gen is not None and fresh:
             with torch.cuda.stream(s_sam):
                 self._stage_mark("sam_begin")
@@ -716,30 +719,30 @@ class HybridGLPipeline:
                     # is through, so its large GEMMs run beside the latency-bound rest of the proposal stage (decoder,
                     # post-processing, NMS, clean-up) instead of beside the encoder's equally matrix-bound GEMMs
                     if self.stagger == "decoder" and not serial:
-                        ev_enc = torch.cuda.Event()
+                        g.ev_enc = torch.cuda.Event()
                     # everything of the group up to its first count read-back is enqueued here without a wait (with crop
                     # layers, the PhraseCut configuration: every crop of every image); the read-backs come after the CLIP
                     # stage of the previous group has been enqueued
                     if getattr(gen, "wants_image_ids", False):      # a store is keyed by the image, not by its pixels
-                        state = gen.group_begin(imgs, proposal_cap, ev_enc, image_ids=[units[i][0].image_id for i in fresh])
+                        g.state = gen.group_begin(imgs, proposal_cap, g.ev_enc, image_ids=[units[i][0].image_id for i in fresh])
                     else:
-                        state = gen.group_begin(imgs, proposal_cap, ev_enc)
+                        g.state = gen.group_begin(imgs, proposal_cap, g.ev_enc)
                 else:    # proposal kernels only; their output is not consumed (synthetic benchmark, seeded masks)
                     self.last_proposals = gen.propose_batch(imgs)[-1]
                     if self._rs is not None and not serial:      # the stage-end snapshot beside it waits for this (no `ready` here)
                         self._rs["beside"] = torch.cuda.Event()
                         self._rs["beside"].record(s_sam)
-        return state, ev_enc, cached, held, fresh
+        return g
 
-    def _sam_end(self, units, state, cached, fresh, s_sam, rescue=False):
-        """The rest of a group's proposal stage: waits for its counts and enqueues what they decide -> (props per unit or None,
-        the event behind the stage or None, the range counters' total that rode on the read-back -- rescue mode and a
-        generator that takes ops.split_overflow_snapshot there -- or None)."""
+    def _sam_end(self, g, s_sam, rescue=False):
+        """The rest of a group's proposal stage: waits for its counts and enqueues what they decide -- g.props and g.ready, the
+        event behind the stage -> the range counters' total that rode on the read-back (rescue mode and a generator that
+        takes ops.split_overflow_snapshot there) or None."""
         gen = self.mask_generator
-        props, ready, seen = None, None, None
-        if state is not None:
+        units, seen = g.units, None
+        if g.state is not None:
             with torch.cuda.stream(s_sam):
-                stc = gen.group_cleanup(state)
+                stc = gen.group_cleanup(g.state)
                 if rescue:
                     seen = int(stc.overflow) if getattr(gen, "__dict__", {}).get("overflow_snapshot", False) else None
                 elif stc.overflow:
@@ -753,30 +756,23 @@ class HybridGLPipeline:
                         f"loop ({stc.overflow} GPU threads saw one; refs up to dataset position {units[-1][-1].index}): the "
                         "results from the previous group on contain inf / NaN; rerun with HYBRIDGL_PRECISION=f32 (or precision='f32')")
                 got = [p[:2] for p in gen.group_finish(stc)]
-                ready = torch.cuda.Event()
-                ready.record(s_sam)
+                g.ready = torch.cuda.Event()
+                g.ready.record(s_sam)
                 self._stage_mark("sam_end")
-            props = [None] * len(units)          # None = take it from the image cache
-            for i, pr in zip(fresh, got):
-                props[i] = pr
-        elif any(cached):
-            props = [None] * len(units)
-        return props, ready, seen
-
-    def _clip_stage(self, pending, led=None):
-        """the CLIP stage of a pending group on the current stream; in rescue mode the checkpoint before it is taken first"""
-        units, props, ready, held, gid = pending
-        if led is not None:
-            led.checkpoint(gid, self._checkpoint())
-        self._done += self._clip_group(units, props, ready, held)
+            g.props = [None] * len(units)          # None = take it from the image cache
+            for i, pr in zip(g.fresh, got):
+                g.props[i] = pr
+        elif len(g.fresh) < len(units):
+            g.props = [None] * len(units)
+        return seen
 
     # ---- checkpoint and roll-back of everything a stage appends to or adds into (prepare(), on_overflow="rescue") -------------
     def _checkpoint(self):
         """The loop's state as of now; the accumulators are cloned on the current stream, the logs are append-only and kept as
-        lengths."""
-        cp = dict(cum=self.cum.clone(), n_log=len(self.iu_log), n_refs=self._n_refs, skipped=getattr(self, "skipped", 0),
-                  cache=dict(self._img_cache), cache_hits=self.cache_hits, k=(self.k1, self.k2), done=getattr(self, "_done", 0),
-                  collected=len(self.collected) if getattr(self, "collected", None) is not None else None,
+        lengths.  step()'s last-image record is no part of it: run(), and so a rescue inside it, never touches it."""
+        cp = dict(cum=self.cum.clone(), n_log=len(self.iu_log), n_refs=self._n_refs, skipped=self.skipped,
+                  cache=dict(self._img_cache), cache_hits=self.cache_hits, k=(self.k1, self.k2), done=self._done,
+                  collected=len(self.collected) if self.collected is not None else None,
                   n_pred=len(self._pred_done) + sum(p[1] for p in self._pred_pending))      # sentences recorded, filed or in flight
         if self.sweep is not None:
             cp["sweep"] = (self.sweep_cum.clone(), self.sweep_cum_ceiling.clone(), len(self._sweep_log), [list(k) for k in self._sweep_k])
@@ -792,7 +788,7 @@ class HybridGLPipeline:
         self._n_refs, self.skipped, self._done = cp["n_refs"], cp["skipped"], cp["done"]
         self._img_cache, self.cache_hits = cp["cache"], cp["cache_hits"]
         self.k1, self.k2 = cp["k"]
-        if cp["collected"] is not None and getattr(self, "collected", None) is not None:
+        if cp["collected"] is not None and self.collected is not None:
             del self.collected[cp["collected"]:]
         if self.sweep is not None:
             self.sweep_cum.copy_(cp["sweep"][0])
@@ -808,7 +804,7 @@ class HybridGLPipeline:
         """rescue mode, and a model of the loop that splits into fp16 planes (with f32 models the mode is a no-op)"""
         if self.on_overflow != "rescue":
             return False
-        owners = (getattr(self.model, "model", None), getattr(self.gem_model, "model", None), getattr(self.mask_generator, "model", None))
+        owners = [getattr(w, "model", None) for w in (self.model, self.gem_model, self.mask_generator)]
         return any(ops.split_mode(getattr(o, "precision", "f32")) for o in owners if o is not None)
 
     def _snapshot(self, gid, stream):
@@ -876,27 +872,23 @@ class HybridGLPipeline:
             self._rollback(cp)
         ops.split_overflow_count(reset=True, sync=False)      # the device is idle
         gids = led.in_flight()
-        was_serial, self._serial = self._serial, True
         stats = self.rescue_stats
         stats["events"] += 1
-        try:
-            with torch.cuda.stream(cur), ops.forced_precision("f32"):
-                for gid in gids:
-                    units = led.payload(gid)
-                    here = torch.cuda.Event()
-                    here.record(cur)
-                    for u in units:
-                        for r in u:
-                            _adopt(r, (cur,), here)
-                    state, _, cached, held, fresh = self._sam_begin(units, None, cur, rs["cap"], True, rs["group"])
-                    props, ready, _ = self._sam_end(units, state, cached, fresh, cur, True)
-                    self._done += self._clip_group(units, props, ready, held)
-                    stats["groups"] += 1
-                    for u in units:
-                        stats["refs"] += len(u)
-                        stats["positions"] += [r.index for r in u]
-        finally:
-            self._serial = was_serial
+        with torch.cuda.stream(cur), ops.forced_precision("f32"):
+            for gid in gids:
+                units = led.payload(gid)
+                here = torch.cuda.Event()
+                here.record(cur)
+                for u in units:
+                    for r in u:
+                        _adopt(r, (cur,), here)
+                g = self._sam_begin(gid, units, None, cur, rs["cap"], True, rs["group"])
+                self._sam_end(g, cur, True)
+                self._clip_group(g, serial=True)
+                stats["groups"] += 1
+                for u in units:
+                    stats["refs"] += len(u)
+                    stats["positions"] += [r.index for r in u]
         led.rescued(0)
         if not rs["serial"]:
             # the loop's streams go on behind the re-run; what it filed in the image cache is read on the CLIP stream from now on
@@ -908,25 +900,26 @@ class HybridGLPipeline:
             rs["s_sam"].wait_event(self._ev)
             rs["s_clip"].wait_event(self._ev)
 
-    def _clip_group(self, units, props, ready, held=None):
-        """CLIP + scoring stage of one group on the current stream; props[i] = (masks u8 [n,H,W], boxes XYWH) of unit i from
-        the proposal stage (None: the items' own masks / boxes).  Returns the number of refs scored."""
-        import dataclasses
-        m = self.model
+    def _clip_group(self, g, serial, led=None):
+        """CLIP + scoring stage of one group on the current stream: its units resolved against the proposal stage's output
+        and the image cache, the stage over those that have proposals, their entries filed in the image cache, the refs
+        counted in _done.  In rescue mode (led) the checkpoint before the group is taken first."""
+        if led is not None:
+            led.checkpoint(g.gid, self._checkpoint())
+        units, props, held = g.units, g.props, g.held
         cur = torch.cuda.current_stream()
-        if ready is not None:
-            cur.wait_event(ready)
+        if g.ready is not None:
+            cur.wait_event(g.ready)
         self._stage_mark("clip_begin")
-        gen = self.mask_generator
-        live = []     # [refs of the unit, masks bool [n,H,W], boxes, hybrid features or None, GEM features or None]
+        gen, live = self.mask_generator, []
         for i, refs in enumerate(units):
             if props is not None and props[i] is None:      # an image of the cache
-                hit = held[i][1] if held[i][0] == "entry" else self._img_cache.get(refs[0].image_id)
+                hit = self._img_cache.get(refs[0].image_id) if held[i] is g.LATE else held[i]
                 if hit is None:                              # filed as "no proposals"
                     self.skipped += len(refs)
                     continue
                 self.cache_hits += 1
-                live.append([refs, hit[0], hit[1], hit[2], hit[3]])
+                live.append(_Live(refs, *hit))
             elif props is not None:
                 mk, bx = props[i]
                 if mk.shape[0] == 0:
@@ -936,108 +929,113 @@ class HybridGLPipeline:
                     continue
                 mk.record_stream(cur)
                 bx.record_stream(cur)
-                live.append([refs, mk.view(torch.bool) if mk.dtype == torch.uint8 else mk, bx.contiguous(), None, None])
+                live.append(_Live(refs, mk.view(torch.bool) if mk.dtype == torch.uint8 else mk, bx.contiguous()))
             else:
                 mk = refs[0].masks
                 if self.cleanup_given_masks and gen is not None:
                     mk = gen.cleanup_fixed(mk.view(torch.uint8))[0].view(torch.bool)
-                live.append([refs, mk, refs[0].boxes, None, None])
+                live.append(_Live(refs, mk, refs[0].boxes))
         if not live:
-            return 0
-        if not hasattr(self, "_s_text"):
-            self._streams()
-        s_text = cur if getattr(self, "_serial", False) else self._s_text
+            return
+        outs = self._stage(live, self._stage_text(live, serial))
+        for u in live:
+            if self.image_cache > 0 and props is not None and u.refs[0].image_id is not None:
+                self._cache_put(u.refs[0].image_id, (u.masks, u.boxes, u.hybrid, u.gem))
+        if self.collected is not None:
+            self.collected += outs
+        self._done += len(outs)
+        self._stage_mark("clip_end")
+
+    def _stage_text(self, live, serial):
+        """The text half of _stage, enqueued ahead of the rest: ONE text-encoder batch over the strings of all refs of `live`, the
+        GEM tower for the images that need it, the heat-maps of the sentences that bring none.  serial: on the current stream
+        (run(serial=True), a rescue's re-run); else on the text stream, behind what the current stream holds now."""
+        m = self.model
+        cur = torch.cuda.current_stream()
+        self._streams()
+        s_text = cur if serial else self._s_text
         ev_in, ev_text = torch.cuda.Event(), torch.cuda.Event()
         ev_in.record(cur)
         s_text.wait_event(ev_in)
-        all_refs = [r for u in live for r in u[0]]
-        offs = np.cumsum([0] + [r.tokens.shape[0] for r in all_refs])
+        refs = [r for u in live for r in u.refs]
+        offs = np.cumsum([0] + [r.tokens.shape[0] for r in refs])
         heats = []
         with torch.cuda.stream(s_text):
-            lens = [r.token_len for r in all_refs]
-            text_all = m.model.encode_text(torch.cat([r.tokens for r in all_refs], dim=0) if len(all_refs) > 1 else all_refs[0].tokens,
+            lens = [r.token_len for r in refs]
+            text_all = m.model.encode_text(torch.cat([r.tokens for r in refs], dim=0) if len(refs) > 1 else refs[0].tokens,
                                            seq_len=None if any(v is None for v in lens) else max(lens))
-            # GEM image tower once per IMAGE that has a sentence without a given heat-map
-            wants = [i for i, u in enumerate(live) if any(s.imgattn is None for r in u[0] for s in r.sentences)]
-            gfeats = {i: live[i][4] for i in wants if live[i][4] is not None}
-            need = [i for i in wants if i not in gfeats]
-            if need:
-                if self.gem_model is None or any(live[i][0][0].tensor_img is None for i in need):
-                    raise ValueError("a sentence without imgattn needs gem_model, RefBatch.tensor_img and Sentence.gem_row")
-                timgs = [live[i][0][0].tensor_img for i in need]
-                if len(need) > 1 and all(t.shape == timgs[0].shape for t in timgs):
-                    fb = self.gem_model.image_features_batch(torch.stack(timgs, dim=0))
-                    gfeats.update({i: fb[j] for j, i in enumerate(need)})
-                else:
-                    gfeats.update({i: self.gem_model.image_features(t) for i, t in zip(need, timgs)})
-                for i in need:
-                    gfeats[i].record_stream(cur)
-                    live[i][4] = gfeats[i]
-            k = 0
-            for i, u in enumerate(live):
-                for ref in u[0]:
-                    text = text_all[offs[k]:offs[k + 1]]
-                    k += 1
-                    gem_rows = [s.gem_row for s in ref.sentences if s.imgattn is None]
-                    heat = None
-                    if gem_rows:
-                        from . import gem as G
-                        if any(r is None for r in gem_rows):
-                            raise ValueError("a sentence without imgattn needs gem_model, RefBatch.tensor_img and Sentence.gem_row")
-                        maps = self.gem_model.heatmap(gfeats[i], _rows(text, gem_rows), ref.tensor_img.shape[-1])
-                        heat = G.resize_antialias(maps, ref.sam_img.shape[:2])     # Hybridgl_main.py:201
-                        heat.record_stream(cur)
-                    heats.append(heat)
+            texts = [text_all[offs[k]:offs[k + 1]] for k in range(len(refs))]
+            # GEM image tower once per IMAGE that has a sentence without a given heat-map (Hybridgl_main.py:200-201:
+            # gem_model(tensor_img, [noun_phrase])[0] -> T.Resize((h, w), antialias=True); the tower depends on the image only --
+            # the reference re-runs it for every sentence -- and the prompts' text features come out of the text batch above)
+            wants = [u for u in live if any(s.imgattn is None for r in u.refs for s in r.sentences)]
+            if any(s.imgattn is None and (self.gem_model is None or r.tensor_img is None or s.gem_row is None)
+                   for u in wants for r in u.refs for s in r.sentences):
+                raise ValueError("a sentence without imgattn needs gem_model, RefBatch.tensor_img and Sentence.gem_row")
+            need = [u for u in wants if u.gem is None]
+            timgs = [u.refs[0].tensor_img for u in need]
+            if len(need) > 1 and all(t.shape == timgs[0].shape for t in timgs):
+                feats = self.gem_model.image_features_batch(torch.stack(timgs, dim=0))
+            else:
+                feats = [self.gem_model.image_features(t) for t in timgs]
+            for u, f in zip(need, feats):
+                u.gem = f
+                u.gem.record_stream(cur)
+            for (u, ref), text in zip(((u, r) for u in live for r in u.refs), texts):
+                gem_rows = [s.gem_row for s in ref.sentences if s.imgattn is None]
+                heat = None
+                if gem_rows:
+                    from . import gem as G
+                    maps = self.gem_model.heatmap(u.gem, _rows(text, gem_rows), ref.tensor_img.shape[-1])
+                    heat = G.resize_antialias(maps, ref.sam_img.shape[:2])     # Hybridgl_main.py:201
+                    heat.record_stream(cur)
+                heats.append(heat)
             ev_text.record(s_text)
         text_all.record_stream(cur)
-        todo = [i for i, u in enumerate(live) if u[3] is None]       # images whose hybrid features are not cached
+        return texts, heats, ev_text
+
+    def _stage(self, live, front, now=False):
+        """The CLIP + scoring stage (Hybridgl_main.py:93-230) on the current stream, under run() (a group's units) and step()
+        (one unit): the views and ONE hybrid forward over the units that have no hybrid features yet, the join with the text
+        half (`front` = _stage_text(live, serial)), every ref's tail in order -- called as the ref comes (now), else the fused
+        tails in one hgl_score_group call (HYBRIDGL_GROUP_TAIL).  -> step()'s (hybrid, text, last sentence) per ref."""
+        texts, heats, ev_text = front
+        todo = [u for u in live if u.hybrid is None]       # images whose hybrid features are not cached
         if todo:
-            ns = [live[i][1].shape[0] for i in todo]
-            moff = np.cumsum([0] + ns)
-            dev = live[todo[0]][1].device
-            local = torch.empty((int(moff[-1]), 3, self.res, self.res), dtype=torch.float32, device=dev)
+            moff = np.cumsum([0] + [u.masks.shape[0] for u in todo])
+            local = torch.empty((int(moff[-1]), 3, self.res, self.res), dtype=torch.float32, device=todo[0].masks.device)
             glob = torch.empty_like(local)
-            for j, i in enumerate(todo):
-                self._views(live[i][0][0], live[i][1], live[i][2], out=(local[moff[j]:moff[j + 1]], glob[moff[j]:moff[j + 1]]))
-            hybrid_all = m(local, glob, [live[i][1] for i in todo], masking_block=self.masking_block, fusion_mode=self.fusion_mode)
-            for j, i in enumerate(todo):
-                live[i][3] = hybrid_all[moff[j]:moff[j + 1]]
-        cur.wait_event(ev_text)
-        k = 0
-        self._explained = []                         # explained() speaks of this group alone
-        defer = [] if self.group_tail else None      # the refs whose tails go into ONE hgl_score_group call at the end
-        waiting = []                                 # their (hybrid, text) for `collected`, in order
-        for refs, mk, bx, hybrid, gfeat in live:
-            if self.image_cache > 0 and props is not None and refs[0].image_id is not None:
-                self._cache_put(refs[0].image_id, (mk, bx, hybrid, gfeat))
-            for ref in refs:
-                text = text_all[offs[k]:offs[k + 1]]
-                out = self._score_ref(dataclasses.replace(ref, masks=mk, boxes=bx), hybrid, text, heats[k], defer)
-                k += 1
-                if out is self._DEFERRED:
-                    waiting.append((hybrid, text))
-                    continue
-                if defer:      # a ref the group call does not serve: the deferred ones before it are logged first (order)
-                    for (h0, t0), o0 in zip(waiting, self._flush_tails(defer)):
-                        if self.collected is not None:
-                            self.collected.append((h0, t0, o0))
-                    waiting = []
-                if self.collected is not None:
-                    self.collected.append((hybrid, text, out))
+            for j, u in enumerate(todo):
+                self._views(u.refs[0], u.masks, u.boxes, out=(local[moff[j]:moff[j + 1]], glob[moff[j]:moff[j + 1]]))
+            hybrid_all = self.model(local, glob, [u.masks for u in todo], masking_block=self.masking_block, fusion_mode=self.fusion_mode)
+            for j, u in enumerate(todo):
+                u.hybrid = hybrid_all[moff[j]:moff[j + 1]]
+        torch.cuda.current_stream().wait_event(ev_text)
+        self._explained = []                         # explained() speaks of this ref / group alone
+        defer = [] if self.group_tail and not now else None      # the refs whose tails go into ONE hgl_score_group call at the end
+        outs, waiting = [], []                       # waiting: the deferred refs' (hybrid, text), in order
+
+        def flush():
+            outs.extend((h0, t0, o0) for (h0, t0), o0 in zip(waiting, self._flush_tails(defer)))
+            waiting.clear()
+        for (u, ref), text, heat in zip(((u, r) for u in live for r in u.refs), texts, heats):
+            out = self._score_ref(replace(ref, masks=u.masks, boxes=u.boxes), u.hybrid, text, heat, defer)
+            if out is self._DEFERRED:
+                waiting.append((u.hybrid, text))
+                continue
+            if defer:      # a ref the group call does not serve: the deferred ones before it are logged first (order)
+                flush()
+            outs.append((u.hybrid, text, out))
         if defer:
-            for (h0, t0), o0 in zip(waiting, self._flush_tails(defer)):
-                if self.collected is not None:
-                    self.collected.append((h0, t0, o0))
-        self._stage_mark("clip_end")
-        return len(all_refs)
+            flush()
+        return outs
 
     def _stage_mark(self, label, stream=None):
         """opt-in timeline of the loop (self.stage_marks = [] before run(); bench.py's timed_region, tools/first_use.py): a
         timing event on `stream` (default: the current one) plus the host time of the call"""
-        marks = getattr(self, "stage_marks", None)
+        marks = self.stage_marks
         if marks is None:
             return
-        import time
         ev = torch.cuda.Event(enable_timing=True)
         ev.record(stream if stream is not None else torch.cuda.current_stream())
         marks.append((label, self.groups_run, ev, time.perf_counter()))
@@ -1050,7 +1048,7 @@ class HybridGLPipeline:
         """most recently used last; the oldest entry leaves when the cache is full"""
         self._img_cache.pop(image_id, None)
         self._img_cache[image_id] = entry
-        while len(self._img_cache) > getattr(self, "_cache_cap", self.image_cache):
+        while len(self._img_cache) > self._cache_cap:
             self._img_cache.pop(next(iter(self._img_cache)))
 
     def partial_rows(self):
@@ -1118,7 +1116,8 @@ class HybridGLPipeline:
         from . import dist as D
         rows = self.partial_rows()
         overflow = 0
-        if ops.split_mode(getattr(self.model.model, "precision", "f32")):
+        clip = self.model.model
+        if ops.split_mode(getattr(clip, "precision", "f32")):
             overflow = ops.split_overflow_count(reset=True)
         # exchange first, raise afterwards and on EVERY rank: a rank that raised before the all-gather would leave the others
         # waiting in the collective

@@ -136,9 +136,9 @@ def test_the_strings_decode_to_the_winners_and_the_overlay_is_the_contract(cuda,
 def test_a_second_call_on_the_same_image_runs_no_proposal_stage(cuda, hgl, segs, tree):
     again = hgl.segment(tree[1], SENTENCES, PARSE)      # the same path: the same image
     first = hgl._pipe.last_proposals
-    hits = (hgl._pipe._cache_id, hgl._image[1])
+    hits = (hgl._pipe.last_image()[0], hgl._image[1])
     other = hgl.segment(tree[1], "a big dog", PARSE[1])
-    assert hgl._pipe.last_proposals is first and (hgl._pipe._cache_id, hgl._image[1]) == hits
+    assert hgl._pipe.last_proposals is first and (hgl._pipe.last_image()[0], hgl._image[1]) == hits
     assert other[0].proposals.data_ptr() == again[0].proposals.data_ptr()
     assert [(s.index_pure, s.index_final, s.rle_final) for s in again] == [(s.index_pure, s.index_final, s.rle_final) for s in segs]
     assert (other[0].index_pure, other[0].index_final, other[0].rle_pure) == (segs[1].index_pure, segs[1].index_final, segs[1].rle_pure)

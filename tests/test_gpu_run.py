@@ -100,7 +100,7 @@ def test_run_equals_per_ref_steps_on_a_refer_set(cuda, golden_dir, tmp_path, mod
     counts = []
     for i in rr.jobs():
         a.step(rr.load(i))
-        counts.append(int(a._cache_ref.masks.shape[0]))
+        counts.append(int(a.last_image()[1].shape[0]))
     torch.cuda.synchronize()
     assert len(set(counts)) >= 3, f"the proposal counts should be ragged, got {counts}"
     b = mk()
@@ -392,3 +392,78 @@ def test_phrasecut_from_disk_groups_equal_image_by_image(cuda, tmp_path):
     args_nc = drv.default_argument_parser().parse_args(uncapped + ["--group", "3"])
     m_nc, _ = drv.evaluate(args_nc, model, gen, gem, cuda)
     assert m_nc == m_one
+
+
+# ---- step() and run() share one CLIP + scoring stage: the two callers against each other, on every tail route ----------------
+@pytest.fixture(scope="module")
+def tiny_world(cuda):
+    """the tiny CLIP model (64 x 64 views, 16 token positions) with its GEM model, and four refs of 5-7 given proposals at
+    48 x 64 with 2-3 sentences; ref 1 brings no heat-maps, so the GEM branch computes them"""
+    from hybridgl_amd import weights
+    from hybridgl_amd.backbone import CLIPViTFM
+    from hybridgl_amd.gem import create_gem_model
+    from hybridgl_amd.pipeline import synthetic_ref
+    model = CLIPViTFM("tiny", state_dict=weights.clip_state_dict("tiny", 0), device=cuda)
+    refs = [synthetic_ref(i, cuda, N=5 + i % 3, H=48, W=64, n_sent=2 + i % 2, context=16, vocab=512, gem=i == 1, gem_size=128)[0]
+            for i in range(4)]
+    return model, create_gem_model("tiny", clip=model), refs
+
+
+def _tiny_pipe(world, route=(), **kw):
+    from hybridgl_amd.pipeline import HybridGLPipeline
+    p = HybridGLPipeline(world[0], masking_block=9, res=64, gem_model=world[1], **kw)
+    for name in route:      # HYBRIDGL_GROUP_TAIL=0 / HYBRIDGL_FUSED_TAIL=0
+        setattr(p, name, False)
+    return p
+
+
+def _same(a, b):
+    if isinstance(a, torch.Tensor):
+        return torch.equal(a, b)
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    return a == b
+
+
+@pytest.mark.parametrize("route", [(), ("group_tail",), ("fused_tail",)], ids=["group_tail", "ref_tail", "sentence_tail"])
+def test_step_and_run_of_one_are_the_same_stage(cuda, tiny_world, route):
+    """step() ref by ref against run(group=1, collect=True) over the same refs with given proposals, bit for bit: what
+    step() returns against `collected`, the rows, the winners, the last ref's explanation and every prediction"""
+    refs = tiny_world[2]
+    a, b = (_tiny_pipe(tiny_world, route, keep_explain=True, record_predictions=True) for _ in range(2))
+    outs = [a.step(r) for r in refs]
+    assert b.run(iter(refs), group=1, collect=True) == len(refs)
+    torch.cuda.synchronize()
+    assert len(b.collected) == len(refs)
+    for i, (x, y) in enumerate(zip(outs, b.collected)):
+        assert len(x) == 3 and len(x[2]) == 4 and _same(x, y), i
+    assert a.partial_rows().shape == (sum(len(r.sentences) for r in refs), 6)
+    assert np.array_equal(a.partial_rows(), b.partial_rows())
+    assert np.array_equal(a.winning_indices(), b.winning_indices())
+    ea, eb = a.explained(), b.explained()
+    assert [(e["index"], e["sentence"]) for e in ea] == [(refs[-1].index, j) for j in range(len(refs[-1].sentences))]
+    assert _same(ea, eb)
+    assert len(a.predictions()) == len(a.partial_rows()) and a.predictions() == b.predictions()
+
+
+def test_one_object_run_on_one_stream_then_step_then_run(cuda, tiny_world):
+    """one pipeline used as run(serial=True), then step(), then run(): its rows are those of three fresh objects doing one of
+    these each -- no call leaves a choice of stream behind for the next -- and the text step() returns after the serial run is
+    a fresh object's (the caller's stream is ordered behind the text stream's work)"""
+    refs = tiny_world[2]
+    mk = lambda: _tiny_pipe(tiny_world, k_clamp="per_ref")
+    one, f1, f2, f3 = mk(), mk(), mk(), mk()
+    assert one.run(iter(refs[:2]), group=2, serial=True) == 2
+    got = one.step(refs[2])
+    assert one.run(iter(refs[1:]), group=2) == 3
+    assert f1.run(iter(refs[:2]), group=2, serial=True) == 2
+    want = f2.step(refs[2])
+    assert f3.run(iter(refs[1:]), group=2) == 3
+    assert _same(got, want) and got[1].shape[0] == refs[2].tokens.shape[0]
+    torch.cuda.synchronize()
+    rows = np.concatenate([f.partial_rows() for f in (f1, f2, f3)])
+    assert rows.shape[0] == sum(len(r.sentences) for r in refs[:2] + refs[2:3] + refs[1:])
+    assert np.array_equal(one.partial_rows(), rows)
+    assert np.array_equal(one.winning_indices(), np.concatenate([f.winning_indices() for f in (f1, f2, f3)]))
